@@ -15,6 +15,17 @@ Workloads (morbit.jl_amd/workloads.py):
   --config C2            single build+solve (no evaluations)
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C4|C5] [--problems P] [--no-cpu-baseline] [--no-callers]
+                  [--dump-outputs DIR]
+  --steps K              exactly K timed steps; `ms_per_step` in the JSON line is the wall time of the timed region / K
+  --dump-outputs DIR     after the timed steps, the arrays the last timed step handed its caller, one file per problem and array:
+                         DIR/p<problem>_values.npy (m x k), DIR/p<problem>_jacobians.npy (m x d x k), DIR/p<problem>_weights.npy (n x k,
+                         where the path returns them; C2 also returns DIR/p<problem>_tail.npy, q x k), fp64.  The inputs are seeded
+                         (workloads.py), so two builds run with the same arguments can be compared file by file.  All files together stay
+                         under 64 MB: a problem whose arrays exceed its share (64 MB / problems per step) keeps a fixed, seeded sample of
+                         rows of each (`dump_sample_rows`), the same rows in every run.  The timed steps of a dump run are the plain
+                         ones when every worker has one problem (C2 aside, the default C3 included); otherwise the second and later
+                         problems of a worker write buffers of their own instead of sharing one set, and C2 also asks the fit for its
+                         weights and tail.  Quote `ms_per_step` from a run without --dump-outputs.
 With --gpus N > 1 and no torch.distributed environment the script launches the N ranks itself (python -m torch.distributed.run,
 rendezvous on 127.0.0.1) BEFORE anything touches a GPU, and exits with the launcher's code; under an external
 `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` it runs as one rank.
@@ -56,7 +67,16 @@ def parse_args():
     ap.add_argument("--gram-mode", type=int, default=0)
     ap.add_argument("--chol-impl", type=int, default=0)
     ap.add_argument("--eval-impl", type=int, default=0)
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (at most 64 MB in all; see the module docstring)")
+    args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup is not None and args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs is not None and args.dry_run:
+        ap.error("--dump-outputs needs the GPU path (a dry run computes nothing)")
+    return args
 
 
 def free_port():
@@ -136,6 +156,57 @@ def cpu_baselines(cfg, C, Y, X):
                            "(%d BLAS threads, as Julia's `\\`); %d of %d points, one output per closure call, value and gradient sweeps "
                            "separate, scaled to %.2fs" % (rows, n, t_asm_f, t_lu, cores, mf, m, t_eval_f))
     return port, faithful
+
+
+# ---- --dump-outputs ------------------------------------------------------------------------------------------------------
+DUMP_LIMIT_BYTES = 64 * 10 ** 6   # all files of one dump together, .npy headers included
+DUMP_HEADER_BYTES = 4096          # reserved per file for its .npy header (NumPy writes 128 bytes for these shapes)
+DUMP_SEED = 20261015
+
+
+def dump_sample_rows(p, group, rows, keep):
+    """Sorted row indices kept of a `rows`-row array group of problem p when it is sampled: fixed by (p, group), not by the run"""
+    rng = np.random.default_rng([DUMP_SEED, int(p), int(group)])
+    return np.sort(rng.choice(rows, size=keep, replace=False))
+
+
+def dump_outputs(path, outputs, problems_per_step):
+    """Write {problem: [(group, {name: array})]} as path/p<problem>_<name>.npy in fp64.  The arrays of one group share their
+    leading axis (the query points, the sites, ...).  Each problem's files get an equal share of DUMP_LIMIT_BYTES (problems_per_step
+    problems over all ranks); a problem over its share keeps the same fraction of the rows of every group, the sampled rows of a
+    group being the same for all of its arrays.  Arrays may be torch tensors (sampled where they live, then copied to the host) or
+    NumPy arrays.  Returns {"files", "bytes", "sampled": {problem: {group: [kept, rows]}}}."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, problems_per_step)
+    files, nbytes, sampled = 0, 0, {}
+    for p in sorted(outputs):
+        groups = outputs[p]
+        nfiles = sum(len(arrays) for _, arrays in groups)
+        data = sum(int(np.prod(a.shape)) * 8 for _, arrays in groups for a in arrays.values())
+        budget = share - DUMP_HEADER_BYTES * nfiles
+        frac = 1.0 if data <= budget else max(budget, 0) / data
+        for gi, (group, arrays) in enumerate(groups):
+            rows = int(next(iter(arrays.values())).shape[0])
+            keep = rows if frac >= 1.0 else int(frac * rows)
+            idx = None
+            if keep < rows:
+                idx = dump_sample_rows(p, gi, rows, keep)
+                sampled.setdefault(str(p), {})[group] = [keep, rows]
+            for name, a in arrays.items():
+                assert int(a.shape[0]) == rows, (p, group, name, tuple(a.shape))
+                if hasattr(a, "detach"):   # torch tensor: sample on its device, then one copy to the host
+                    if idx is not None:
+                        import torch
+                        a = a.index_select(0, torch.from_numpy(idx).to(a.device))
+                    a = a.detach().cpu().numpy()
+                elif idx is not None:
+                    a = np.asarray(a)[idx]
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                f = os.path.join(path, "p%03d_%s.npy" % (p, name))
+                np.save(f, a)
+                files += 1
+                nbytes += os.path.getsize(f)
+    return {"files": files, "bytes": nbytes, "sampled": sampled}
 
 
 # ---- one rank ----------------------------------------------------------------------------------------------------------
@@ -297,8 +368,10 @@ def main():
         class DryWorker:
             phases = {p: 0.0 for p in PH}
             fallbacks = 0
+            cycles = 0   # the cycles of the timed region (reported as `dry_run_cycles`)
 
             def cycle(self, p):
+                self.cycles += 1
                 time.sleep(0.001)
                 return [float(p), 0.0, 2.0, 0.0, 0.0, 0.0, 1.0, 0.0]
         workers = [DryWorker()]
@@ -320,17 +393,26 @@ def main():
         # more kernels in flight on the GPU -- the mrbf_batch_run arrangement (api.hip), here with device-resident inputs
         nworkers = args.workers if args.workers > 0 else (4 if (many and n <= 2048) else 1)
         nworkers = max(1, min(nworkers, max(1, len(mine))))
+        q_tail = 0 if cfg["deg"] < 0 else (1 if cfg["deg"] == 0 else d + 1)
+        dump = args.dump_outputs is not None
+        # what the fit hands back besides the model: the many-start path takes the weights; with --dump-outputs the build+solve-only
+        # config (no evaluations) takes its weights and tail coefficients too, as they are then all the path returns to its caller
+        want_w = many or (dump and m == 0)
+        want_tail = dump and m == 0 and q_tail > 0
 
         class Worker:
-            def __init__(self):
+            def __init__(self, subset=()):
                 self.ctx = pkg.Context(local_rank)
                 self.ctx.set_option(_lib.OPT_GRAM_MODE, args.gram_mode)
                 self.ctx.set_option(_lib.OPT_CHOL_IMPL, args.chol_impl)
                 self.ctx.set_option(_lib.OPT_EVAL_IMPL, args.eval_impl)
                 self.finfo, self.einfo = _lib.FitInfo(), _lib.EvalInfo()
-                self.dV = torch.empty((max(m, 1), k), dtype=torch.float64, device="cuda")
-                self.dJ = torch.empty((max(m, 1), d, k), dtype=torch.float64, device="cuda")
-                self.dW = torch.empty((n, k), dtype=torch.float64, device="cuda")
+                self.dV, self.dJ, self.dW, self.dL = self.buffers()
+                # with --dump-outputs every problem of this worker writes buffers of its own, so that after the last timed step the
+                # outputs of all of them are still there; the first one keeps the shared set, so that a worker with one problem runs
+                # the plain path (without the flag the problems share one set, as a caller would reuse it)
+                self.out = ({p: ((self.dV, self.dJ, self.dW, self.dL) if i == 0 else self.buffers()) for i, p in enumerate(subset)}
+                            if dump else None)
                 self.sums = torch.empty(2, dtype=torch.float64, device="cuda")
                 self.phases = {p: 0.0 for p in PH}
                 self.fallbacks = 0
@@ -339,14 +421,23 @@ def main():
                 self.slow_launches = 0
                 self.gram_inputs = (dev[mine[0]][0], (kid, a, b, cfg["deg"])) if mine else None
 
+            @staticmethod
+            def buffers():
+                return (torch.empty((max(m, 1), k), dtype=torch.float64, device="cuda"),
+                        torch.empty((max(m, 1), d, k), dtype=torch.float64, device="cuda"),
+                        torch.empty((n, k), dtype=torch.float64, device="cuda"),
+                        torch.empty((max(q_tail, 1), k), dtype=torch.float64, device="cuda"))
+
             def cycle(self, p):
                 ctx, lib, finfo, einfo = self.ctx, self.ctx.lib, self.finfo, self.einfo
                 dC, dY, dX = dev[p]
+                own = self.out.get(p) if self.out is not None else None   # (the one-of-eight share below also cycles other workers' problems)
+                dV, dJ, dW, dL = own if own is not None else (self.dV, self.dJ, self.dW, self.dL)
                 h = _lib.c_vp()
                 ctx.check(lib.mrbf_fit(ctx.h, n, d, k, _lib.as_ptr(dC), _lib.as_ptr(dY), kid, a, b, cfg["deg"], ctypes.byref(h),
-                                       _lib.as_ptr(self.dW) if many else None, None, ctypes.byref(finfo)))
+                                       _lib.as_ptr(dW) if want_w else None, _lib.as_ptr(dL) if want_tail else None, ctypes.byref(finfo)))
                 if m > 0:
-                    ctx.check(lib.mrbf_eval(ctx.h, h, m, _lib.as_ptr(dX), _lib.as_ptr(self.dV), _lib.as_ptr(self.dJ), ctypes.byref(einfo)))
+                    ctx.check(lib.mrbf_eval(ctx.h, h, m, _lib.as_ptr(dX), _lib.as_ptr(dV), _lib.as_ptr(dJ), ctypes.byref(einfo)))
                 ctx.check(lib.mrbf_free_model(ctx.h, h))
                 ph = self.phases
                 ph["gram"] += finfo.ms_gram
@@ -411,7 +502,7 @@ def main():
 
         mine_all = mine
         batched = many and n <= 512 and d <= 128 and not args.no_batch
-        workers = [BatchWorker()] if batched else [Worker() for _ in range(nworkers)]
+        workers = [BatchWorker()] if batched else [Worker(mine[wi::nworkers]) for wi in range(nworkers)]
         # one checked cycle per rank (residual through the eval kernels), then the timed loop without the extra check
         w0 = workers[0]
         if batched:
@@ -454,6 +545,8 @@ def main():
         for p in PH:
             w.phases[p] = 0.0
         w.fallbacks = 0
+        if dry:
+            w.cycles = 0
         if hasattr(w, "factor_ms"):
             w.factor_ms.clear()
         if hasattr(w, "factor_dev_ms"):
@@ -473,6 +566,19 @@ def main():
         dist.all_gather(allt, t)
         rank_times = [float(x.item()) for x in allt]
         elapsed = max(rank_times)
+    dumped = None
+    if args.dump_outputs is not None:
+        # what this rank's problems received in the last timed step, written before anything below runs the path again
+        outputs = {}
+        if batched:
+            for p, (dV, dJ, dW) in zip(workers[0].mine, workers[0].keep):
+                outputs[p] = ([("queries", {"values": dV, "jacobians": dJ})] if m > 0 else []) + [("sites", {"weights": dW})]
+        else:
+            for w in workers:
+                for p, (dV, dJ, dW, dL) in w.out.items():
+                    outputs[p] = (([("queries", {"values": dV, "jacobians": dJ})] if m > 0 else []) +
+                                  ([("sites", {"weights": dW})] if want_w else []) + ([("tail", {"tail": dL})] if want_tail else []))
+        dumped = dict(dump_outputs(args.dump_outputs, outputs, P), dir=os.path.abspath(args.dump_outputs))
     ncyc = max(1, steps * len(mine))
     # ms per launch, hipEvents on the library's stream inside the timed region (rank 0's problems)
     phases = {p: sum(w.phases[p] for w in workers) / ncyc for p in PH}
@@ -504,6 +610,9 @@ def main():
         }
         if dry:
             out["dry_run"] = True
+            out["dry_run_cycles"] = sum(w.cycles for w in workers)   # this rank's
+        if dumped is not None:
+            out["dump_outputs"] = dumped   # this rank's files
         if many and table is not None:
             out["records"] = {"gathered": int(table.shape[0]), "failed": int(np.sum(table[:, 1] != 0)),
                               "worst_rel_residual": (float(np.nanmax(table[:, 3])) if np.isfinite(table[:, 3]).any() else None)}
@@ -514,7 +623,6 @@ def main():
             # 4 n^2 + 8 n d bytes, i.e. MFMA-bound; `frac` is priced on those useful flops.  What the kernel issues on top of that
             # (mirrored tiles computed a second time, if the build still does) is reported beside it as `issued_flops`, never in `frac`.
             # The full-matrix kernel behind mrbf_gram (RBF.get_matrices) is measured below (kernels.gram_full: 8 n^2 + 8 n d bytes, HBM roof).
-            q_tail = 0 if cfg["deg"] < 0 else (1 if cfg["deg"] == 0 else d + 1)
             fused_gram = (not batched) and d <= 64 and q_tail >= 1 and n >= 1024 and args.gram_mode == 0
             gram_mfma = d >= 96 or fused_gram
             gram_flops = 3.0 * n * n * d if fused_gram else alg["gram_flops"]

@@ -13,6 +13,7 @@
    or a HipRbfModel in the container) and hand over to Morbit's method by `invoke` before any ccall can be reached.
 """
 import ctypes
+import json
 import os
 import re
 
@@ -232,7 +233,8 @@ def test_no_unguarded_global_state():
     assert "task_local_storage(_HIP_AFFINE_KEY" in code
 
 
-# functions of Morbit / Base that HipRbf.jl adds methods to (collected from the reference when it is present, see below)
+# functions of Morbit / Base that HipRbf.jl adds methods to; every other function name Morbit defines is in
+# tests/golden/morbit_function_names.json (see test_inert_for_users_who_do_not_select_hiprbfconfig)
 MORBIT_FUNCTIONS = {"prepare_init_model", "prepare_update_model", "prepare_improve_model", "init_model", "update_model", "improve_model",
                     "eval_models", "get_jacobian", "get_gradient", "max_evals", "combinable", "get_saveable_type", "fully_linear",
                     "num_outputs", "set_fully_linear!", "_rbf_round4", "_backtrack", "get_criticality", "_get_signature",
@@ -262,15 +264,11 @@ def _method_definitions(code):
 def test_inert_for_users_who_do_not_select_hiprbfconfig():
     src = open(JL, encoding="utf-8").read()
     code = _strip_jl_comments(src)
-    names = set(MORBIT_FUNCTIONS)
-    ref_src = "/root/reference/src"
-    if os.path.isdir(ref_src):                          # build container: every function name the reference defines
-        for base, _, files in os.walk(ref_src):
-            for f in files:
-                if f.endswith(".jl"):
-                    t = open(os.path.join(base, f), encoding="utf-8", errors="ignore").read()
-                    names.update(re.findall(r"^\s*function\s+([A-Za-z_][\w!]*)\s*\(", t, flags=re.M))
-                    names.update(re.findall(r"^([A-Za-z_][\w!]*)\([^\n]*\)\s*(?:where[^\n=]*)?=(?!=)", t, flags=re.M))
+    # every function name Morbit.jl defines (stored fixture; the Morbit names above are among them)
+    fixture = json.load(open(os.path.join(ROOT, "tests", "golden", "morbit_function_names.json"), encoding="utf-8"))
+    morbit_names = set(fixture["names"])
+    assert len(morbit_names) >= 400 and {n for n in MORBIT_FUNCTIONS if not n.startswith("Base.")} <= morbit_names
+    names = set(MORBIT_FUNCTIONS) | morbit_names
     defs = _method_definitions(code)
     assert len(defs) > 40
     guarded = set()
