@@ -355,6 +355,42 @@ int32_t mrbf_ps_step_problem(mrbf_ctx *ctx, const mrbf_ps_problem *problem, cons
 int32_t mrbf_debug_ps_rank(mrbf_ctx *ctx, int32_t lam, const double *f, const double *phi, uint64_t seed, int32_t gen, int32_t impl,
                            int32_t *order_out, int32_t *gave_up);
 
+/* ---- steepest-descent criticality: the direction LP on the device (sd_lp.hip) -------------------------------------------
+ * mrbf_sd_direction replaces the JuMP / OSQP model of _steepest_descent_direction (src/descent.jl:91-135) for n_lp LPs of one
+ * shape in one launch (one workgroup per LP, exact fp64 dual simplex with the bound-flipping ratio test):
+ *   minimise alpha over (d, alpha), d in [l, u] with l_j = max(-1, lb_j - x_j), u_j = min(1, ub_j - x_j), alpha free,
+ *   g_i . d <= w_i alpha (i < k; w_i = ||g_i||_2 with normalize, else 1), A_eq d = b_eq, A_ineq d <= b_ineq;
+ *   m = k + m_eq + m_ineq <= 64, 1 <= d <= 4096.
+ * Per LP (consecutive blocks): G k x d in mrbf_eval's jac_out layout (k x d column-major: a Jacobian from mrbf_eval goes in as it
+ * is), x / lb / ub d, A_eq m_eq x d and A_ineq m_ineq x d row-major, b_eq m_eq, b_ineq m_ineq (A / b may be NULL when the count
+ * is 0).  Outputs: d_out (d, inside [l, u] exactly), omega_out (1): -max_i (g_i . d) / w_i over the rows with w_i > 0, recomputed
+ * from the returned d; dual_out (m, may be NULL): the row multipliers (>= 0 on objective and inequality rows, sum_i<k w_i y_i = 1),
+ * the optimality certificate; status_out (1): MRBF_SD_*; iters_out (2, may be NULL): simplex iterations, bound flips.
+ * NO_OBJECTIVE (normalize and every g_i = 0) and INFEASIBLE (empty box or rows that cannot be met) return d = 0, omega = -Inf:
+ * the reference's catch branch (descent.jl:130-133).  Every LP gets a status; the call fails only on invalid arguments.  The
+ * result of an LP does not depend on its position in the batch. */
+enum { MRBF_SD_OK = 0, MRBF_SD_NO_OBJECTIVE = 1, MRBF_SD_INFEASIBLE = 2, MRBF_SD_GAVE_UP = 3 };
+int32_t mrbf_sd_direction(mrbf_ctx *ctx, int64_t n_lp, int32_t d, int32_t k, int32_t m_eq, int32_t m_ineq, const double *G,
+                          const double *x, const double *lb, const double *ub, const double *A_eq, const double *b_eq,
+                          const double *A_ineq, const double *b_ineq, int32_t normalize, double *d_out, double *omega_out,
+                          double *dual_out, int32_t *status_out, int32_t *iters_out);
+/* get_criticality(::SteepestDescentConfig, mop, scal, x_it, x_it_n, db, sc, ac) (src/descent.jl:187-241) for a container given as
+ * an mrbf_ps_problem (models, roles, linear constraints in scaled variables; eq_tol is not used): objective Jacobians at x_n,
+ * modelled-constraint Jacobians at x and values at x_n through the evaluation kernels, right-hand sides b - A x_n (linear rows)
+ * and -m(x_n) - Dm(x) (x_n - x) (modelled rows, descent.jl:214-229), then ONE direction LP at x_n over the global bounds lb / ub
+ * (full_bounds_internal, not the trust region) and one read-back.  Row order of dual_out: objectives, linear equalities, modelled
+ * equalities, linear inequalities, modelled inequalities (modelled rows in model order, then output order).  Returns -2 (take
+ * the reference method) when the decision table refuses the shape or the LP gave up (info->status = MRBF_SD_GAVE_UP). */
+typedef struct {
+    int32_t status;      /* MRBF_SD_* */
+    int32_t iterations;  /* dual simplex iterations */
+    int32_t bound_flips; /* bound flips of the ratio tests */
+    float ms_total;      /* hipEvent time of the whole call on the ctx stream */
+    double omega;        /* the criticality omega (-Inf for NO_OBJECTIVE / INFEASIBLE) */
+} mrbf_sd_info;
+int32_t mrbf_sd_criticality(mrbf_ctx *ctx, const mrbf_ps_problem *problem, const double *x, const double *x_n, const double *lb,
+                            const double *ub, int32_t normalize, double *d_out, double *dual_out, mrbf_sd_info *info);
+
 /* ---- the decision table of the host bindings ---------------------------------------------------------------------------
  * Which implementation a binding (morbit.jl_amd/julia/HipRbf.jl, the Python mirror) takes for one call of Morbit's interface:
  * the device entry point (MRBF_DISPATCH_DEVICE) or Morbit's own method on the same arguments (MRBF_DISPATCH_REFERENCE; Julia:
@@ -374,13 +410,17 @@ int32_t mrbf_debug_ps_rank(mrbf_ctx *ctx, int32_t lam, const double *f, const do
  *                            the training set (state_n0 + state_n_accepted == n_training, same sites in the same order:
  *                            same_sites != 0) with a unisolvent start set (state_n0 == q), at least one accepted site and at most
  *                            1024 training sites (beyond that the ordinary fit is as fast and more accurate).
+ *   mrbf_dispatch_sd         get_criticality(::SteepestDescentConfig, ...) (src/descent.jl:187-241): device iff no foreign
+ *                            surrogate, at least one device model, 1 <= d <= 4096, k >= 1 and k + n_nl + n_lin <= 64 LP rows.
  *   mrbf_dispatch_after      the return code rc of a device entry point (MRBF_ENTRY_*) that means "take the reference method
  *                            for this call" (start set without the tail or rank deficient, limits of the device path) rather
  *                            than an error: 1 = fall back, 0 = rc is what it says. */
 enum { MRBF_DISPATCH_REFERENCE = 0, MRBF_DISPATCH_DEVICE = 1 };
 enum { MRBF_FIT_FULL = 0, MRBF_FIT_FROM_ROUND4 = 1 };
-enum { MRBF_ENTRY_ROUND4 = 1, MRBF_ENTRY_FIT_FROM_ROUND4 = 2, MRBF_ENTRY_PS_STEP = 3, MRBF_ENTRY_BACKTRACK = 4, MRBF_ENTRY_AFFINE = 5 };
+enum { MRBF_ENTRY_ROUND4 = 1, MRBF_ENTRY_FIT_FROM_ROUND4 = 2, MRBF_ENTRY_PS_STEP = 3, MRBF_ENTRY_BACKTRACK = 4, MRBF_ENTRY_AFFINE = 5,
+       MRBF_ENTRY_SD = 6 };
 int32_t mrbf_dispatch_ps(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
+int32_t mrbf_dispatch_sd(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_backtrack(int32_t n_objective_models, int32_t n_foreign, int32_t outputs_in_order);
 int32_t mrbf_dispatch_affine(int64_t n_candidates, int32_t d);
 int32_t mrbf_dispatch_round4(int64_t n0, int32_t d, int32_t poly_deg, int64_t n_candidates);

@@ -58,7 +58,8 @@ PS_OK, PS_CRITICAL, PS_FAILURE = 0, 1, 2
 ROLE_NONE, ROLE_EQ, ROLE_INEQ = -1, -2, -3
 DISPATCH_REFERENCE, DISPATCH_DEVICE = 0, 1
 FIT_FULL, FIT_FROM_ROUND4 = 0, 1
-ENTRY_ROUND4, ENTRY_FIT_FROM_ROUND4, ENTRY_PS_STEP, ENTRY_BACKTRACK, ENTRY_AFFINE = 1, 2, 3, 4, 5
+ENTRY_ROUND4, ENTRY_FIT_FROM_ROUND4, ENTRY_PS_STEP, ENTRY_BACKTRACK, ENTRY_AFFINE, ENTRY_SD = 1, 2, 3, 4, 5, 6
+SD_OK, SD_NO_OBJECTIVE, SD_INFEASIBLE, SD_GAVE_UP = 0, 1, 2, 3
 
 
 class PsProblem(ctypes.Structure):
@@ -66,6 +67,14 @@ class PsProblem(ctypes.Structure):
                 ("roles", ctypes.POINTER(ctypes.c_int32)), ("n_lin_eq", ctypes.c_int32), ("n_lin_ineq", ctypes.c_int32),
                 ("A_eq", ctypes.c_void_p), ("b_eq", ctypes.c_void_p), ("A_ineq", ctypes.c_void_p), ("b_ineq", ctypes.c_void_p),
                 ("eq_tol", ctypes.c_double)]
+
+
+class SdInfo(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("iterations", ctypes.c_int32), ("bound_flips", ctypes.c_int32), ("ms_total", ctypes.c_float),
+                ("omega", ctypes.c_double)]
+
+    def asdict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
 
 
 class Problem(ctypes.Structure):
@@ -132,7 +141,12 @@ SIGNATURES = {
                                       ctypes.POINTER(PsInfo)]),
     "mrbf_ps_step_problem": (ctypes.c_int32, [c_vp, ctypes.POINTER(PsProblem), c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(PsOptions),
                                               c_vp, c_vp, c_vp, ctypes.POINTER(PsInfo)]),
+    "mrbf_sd_direction": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32] + [c_vp] * 8
+                          + [ctypes.c_int32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mrbf_sd_criticality": (ctypes.c_int32, [c_vp, ctypes.POINTER(PsProblem), c_vp, c_vp, c_vp, c_vp, ctypes.c_int32, c_vp, c_vp,
+                                             ctypes.POINTER(SdInfo)]),
     "mrbf_dispatch_ps": (ctypes.c_int32, [ctypes.c_int32] * 6),
+    "mrbf_dispatch_sd": (ctypes.c_int32, [ctypes.c_int32] * 6),
     "mrbf_dispatch_backtrack": (ctypes.c_int32, [ctypes.c_int32] * 3),
     "mrbf_dispatch_affine": (ctypes.c_int32, [ctypes.c_int64, ctypes.c_int32]),
     "mrbf_dispatch_round4": (ctypes.c_int32, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64]),

@@ -1,0 +1,702 @@
+// Steepest-descent criticality on the device: the direction LP of _steepest_descent_direction (src/descent.jl:91-135) and the whole
+// get_criticality(::SteepestDescentConfig, ...) (descent.jl:187-241) around it.
+//
+// One workgroup solves one LP:
+//   minimise alpha  s.t.  g_i . d - w_i alpha + s_i = 0 (i < k, s_i >= 0),  A_eq d + s = b_eq (s = 0),  A_ineq d + s = b_ineq (s >= 0),
+//   l <= d <= u, alpha free
+// by a dual simplex with the bound-flipping ratio test.  Columns: the d structural ones, alpha (column d), one slack per row (d + 1 + i).
+// Start basis: alpha basic in the first objective row i0 with w_i0 > 0, every other slack basic, each d_j at the bound its reduced
+// cost g_i0,j / w_i0 prefers -- dual feasible, so there is no phase I.  alpha is free, so it never leaves: the row duals are the row
+// of B^-1 at alpha's position.  B^-1 (m x m, m <= 64) lives in LDS, takes a rank-1 update per pivot and is refactored (Gauss-Jordan
+// with partial pivoting) every 16 pivots and before optimality is accepted.  The basic values and reduced costs are recomputed from
+// B^-1 every iteration (one pass over the rows, one over the columns), so no update error accumulates in them.  Every sum runs in a
+// fixed order that depends on the shape alone: an LP's result does not depend on its position in the batch, and no atomics touch
+// values (the one LDS atomic only compacts the ratio-test candidates, which are then sorted by (breakpoint, column)).
+#include "common.hpp"
+
+namespace mrbf {
+namespace sd {
+
+constexpr int THREADS = 256;
+constexpr int MAXM = 64;
+constexpr int MAXD = 4096;
+constexpr int REFACTOR_EVERY = 16;
+constexpr double FEAS_TOL = 1e-13;   // relative to the row's magnitude sum |b_i| + sum_j |A_ij| (|d_j| <= 1)
+constexpr double PIVOT_TOL = 1e-9;   // ratio-test candidates: |alpha_pj| > PIVOT_TOL * max_j |alpha_pj|
+constexpr double SNAP_TOL = 1e-12;   // a basic d_j this close to a bound is returned on it
+
+struct Args {
+    int n, k, meq, min, m, normalize, nc, p2;
+    const double *G, *x, *lb, *ub, *Aeq, *beq, *Ain, *bin;
+    double *d_out, *omega_out, *dual_out;
+    int *status_out, *iters_out;
+    double *ws;  // per LP 5 nc doubles: nonbasic values, lower, upper bounds, pivot row, reduced costs
+    int *wsi;    // per LP nc ints: basis position of each column (-1: nonbasic)
+};
+
+struct Lp {
+    const double *G, *Aeq, *Ain;
+    int n, k, meq;
+    __device__ double a(int i, int j) const {  // entry (row i, structural column j)
+        if (i < k) return G[(size_t)j * k + i];
+        if (i < k + meq) return Aeq[(size_t)(i - k) * n + j];
+        return Ain[(size_t)(i - k - meq) * n + j];
+    }
+};
+
+// LDS carve (host and device agree through this one function); offsets in bytes, each a multiple of 16
+struct Carve {
+    size_t binv, vec, part, dsc, head, isc, uni, total;
+};
+__host__ __device__ inline Carve carve(int m, int p2) {
+    Carve c;
+    auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    c.binv = 0;
+    c.vec = up(c.binv + (size_t)m * m * sizeof(double));
+    c.part = up(c.vec + (size_t)10 * MAXM * sizeof(double));
+    c.dsc = up(c.part + (size_t)THREADS * sizeof(double));
+    c.head = up(c.dsc + 8 * sizeof(double));
+    c.isc = up(c.head + MAXM * sizeof(int));
+    c.uni = up(c.isc + 16 * sizeof(int));
+    const size_t sort = (size_t)p2 * (sizeof(double) + sizeof(int)), aug = (size_t)m * 2 * m * sizeof(double);
+    c.total = up(c.uni + (sort > aug ? sort : aug));
+    return c;
+}
+
+enum { I_ACT = 0, I_P, I_DIR, I_CNT, I_TE, I_PIV, I_BAD, I_I0 };
+enum { A_PIVOT = 0, A_DONE, A_REFACTOR, A_GIVEUP, A_INFEASIBLE };
+enum { D_SLOPE = 0, D_AMAX };
+
+// out[i] = sum_{j < n} f(i, j) for rows i < rows: THREADS / rows strided segments per row, their partial sums added in order
+template <class F>
+__device__ void row_pass(int n, int rows, F f, double *part, double *out) {
+    const int t = threadIdx.x, S = THREADS / rows;
+    if (t < rows * S) {
+        const int i = t / S, s = t % S;
+        double acc = 0.0;
+        for (int j = s; j < n; j += S) acc += f(i, j);
+        part[t] = acc;
+    }
+    __syncthreads();
+    if (t < rows) {
+        double acc = 0.0;
+        for (int s = 0; s < S; ++s) acc += part[t * S + s];
+        out[t] = acc;
+    }
+    __syncthreads();
+}
+
+__device__ inline double col_entry(const Lp &L, const double *w, int col, int i) {
+    if (col < L.n) return L.a(i, col);
+    if (col == L.n) return i < L.k ? -w[i] : 0.0;
+    return i == col - L.n - 1 ? 1.0 : 0.0;
+}
+
+// B^-1 from scratch: Gauss-Jordan with partial pivoting on [B | I] (m x 2m in the union area).  false: B is singular.
+__device__ bool refactor(const Lp &L, int m, const double *w, const int *head, double *Binv, double *aug, double *rowbuf, double *fac,
+                         double *cmax, int *isc) {
+    const int t = threadIdx.x, W = 2 * m;
+    for (int e = t; e < m * W; e += THREADS) {
+        const int r = e / W, c = e % W;
+        aug[e] = c < m ? col_entry(L, w, head[c], r) : (c - m == r ? 1.0 : 0.0);
+    }
+    __syncthreads();
+    for (int c = t; c < m; c += THREADS) {
+        double mx = 0.0;
+        for (int r = 0; r < m; ++r) mx = fmax(mx, fabs(aug[r * W + c]));
+        cmax[c] = mx;
+    }
+    __syncthreads();
+    for (int c = 0; c < m; ++c) {
+        if (t == 0) {
+            int r = c;
+            double best = fabs(aug[c * W + c]);
+            for (int i = c + 1; i < m; ++i)
+                if (fabs(aug[i * W + c]) > best) best = fabs(aug[i * W + c]), r = i;
+            isc[I_PIV] = (best > 1e-14 * cmax[c] && best > 0.0) ? r : -1;
+        }
+        __syncthreads();
+        const int r = isc[I_PIV];
+        if (r < 0) return false;  // uniform: every thread read the same word
+        const double inv = 1.0 / aug[r * W + c];
+        for (int e = t; e < W; e += THREADS) rowbuf[e] = aug[r * W + e] * inv;
+        for (int i = t; i < m; i += THREADS) fac[i] = aug[i * W + c];
+        __syncthreads();
+        if (r != c)
+            for (int e = t; e < W; e += THREADS) aug[r * W + e] = aug[c * W + e];  // row c moves to r (row r is in rowbuf)
+        __syncthreads();
+        if (r != c && t == 0) fac[r] = fac[c];
+        __syncthreads();
+        for (int e = t; e < m * W; e += THREADS) {
+            const int i = e / W, cc = e % W;
+            aug[e] = i == c ? rowbuf[cc] : aug[e] - fac[i] * rowbuf[cc];
+        }
+        __syncthreads();
+    }
+    for (int e = t; e < m * m; e += THREADS) Binv[e] = aug[(e / m) * W + m + e % m];
+    __syncthreads();
+    return true;
+}
+
+__global__ __launch_bounds__(THREADS) void sd_lp_kernel(Args a, int64_t lp0) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int64_t lp = lp0 + blockIdx.x;
+    const int t = threadIdx.x, n = a.n, k = a.k, m = a.m, nc = a.nc, meq = a.meq;
+    const Carve cv = carve(m, a.p2);
+    double *Binv = (double *)(smem + cv.binv), *vec = (double *)(smem + cv.vec), *part = (double *)(smem + cv.part);
+    double *rho = vec, *yv = vec + MAXM, *aq = vec + 2 * MAXM, *rhs = vec + 3 * MAXM, *beta = vec + 4 * MAXM, *w = vec + 5 * MAXM;
+    double *bt = vec + 6 * MAXM, *ftol = vec + 7 * MAXM, *colq = vec + 8 * MAXM, *cmax = vec + 9 * MAXM;
+    double *dsc = (double *)(smem + cv.dsc);
+    int *head = (int *)(smem + cv.head), *isc = (int *)(smem + cv.isc);
+    double *skey = (double *)(smem + cv.uni), *aug = skey;
+    int *sidx = (int *)(smem + cv.uni + (size_t)a.p2 * sizeof(double));
+
+    const Lp L{a.G + lp * k * n, a.Aeq ? a.Aeq + lp * meq * n : nullptr, a.Ain ? a.Ain + lp * a.min * n : nullptr, n, k, meq};
+    const double *x = a.x + lp * n, *lb = a.lb + lp * n, *ub = a.ub + lp * n;
+    double *xv = a.ws + (size_t)blockIdx.x * 5 * nc, *lo = xv + nc, *hi = xv + 2 * nc, *ap = xv + 3 * nc, *dj = xv + 4 * nc;
+    int *pos = a.wsi + (size_t)blockIdx.x * nc;
+    const double INF = __builtin_huge_val();
+
+    // ---- bounds, row weights, right-hand sides, row tolerances
+    int bad = 0;
+    for (int j = t; j < nc; j += THREADS) {
+        double l, u;
+        if (j < n) {
+            l = fmax(-1.0, lb[j] - x[j]);
+            u = fmin(1.0, ub[j] - x[j]);
+            if (!(l <= u)) bad = 1;
+        } else if (j == n) {
+            l = -INF, u = INF;
+        } else {
+            const int i = j - n - 1;
+            l = 0.0, u = (i >= k && i < k + meq) ? 0.0 : INF;
+        }
+        lo[j] = l, hi[j] = u, pos[j] = -1, xv[j] = 0.0;
+    }
+    bad = __syncthreads_or(bad);
+    row_pass(n, k, [&](int i, int j) { const double g = L.G[(size_t)j * k + i]; return g * g; }, part, w);
+    row_pass(n, m, [&](int i, int j) { return fabs(L.a(i, j)); }, part, ftol);
+    if (t < m) {
+        if (t < k) w[t] = a.normalize ? sqrt(w[t]) : 1.0;
+        bt[t] = t < k ? 0.0 : (t < k + meq ? a.beq[lp * meq + t - k] : a.bin[lp * a.min + t - k - meq]);
+        ftol[t] = FEAS_TOL * fmax(1.0, fabs(bt[t]) + ftol[t] + (t < k ? ftol[t] : 0.0));
+    }
+    __syncthreads();
+    if (t == 0) {
+        int i0 = -1;
+        for (int i = 0; i < k && i0 < 0; ++i)
+            if (w[i] > 0.0) i0 = i;
+        isc[I_I0] = i0;
+        isc[I_BAD] = bad ? MRBF_SD_INFEASIBLE : (i0 < 0 ? MRBF_SD_NO_OBJECTIVE : MRBF_SD_OK);
+    }
+    __syncthreads();
+    int status = isc[I_BAD];
+    const int i0 = isc[I_I0];
+    int iters = 0, flips = 0;
+    if (status == MRBF_SD_OK) {
+        // ---- start basis (dual feasible)
+        for (int j = t; j < n; j += THREADS) {
+            const double r = L.G[(size_t)j * k + i0];
+            xv[j] = r > 0.0 ? lo[j] : (r < 0.0 ? hi[j] : (fabs(lo[j]) <= fabs(hi[j]) ? lo[j] : hi[j]));
+        }
+        if (t < m) {
+            head[t] = t == i0 ? n : n + 1 + t;
+            pos[head[t]] = t;
+        }
+        __syncthreads();
+        if (!refactor(L, m, w, head, Binv, aug, part, colq, cmax, isc)) status = MRBF_SD_GAVE_UP;
+        const int cap = 8 * (m + n);
+        int since = 0;
+        while (status == MRBF_SD_OK) {
+            // ---- basic values beta = B^-1 (b - N x_N): only structural columns carry non-zero nonbasic values
+            row_pass(n, m, [&](int i, int j) { return pos[j] < 0 ? L.a(i, j) * xv[j] : 0.0; }, part, rhs);
+            if (t < m) {
+                double acc = 0.0;
+                for (int q = 0; q < m; ++q) acc += Binv[t * m + q] * (bt[q] - rhs[q]);
+                beta[t] = acc;
+            }
+            __syncthreads();
+            // ---- pricing: the largest violation, ties to the lowest basis position
+            if (t == 0) {
+                int best = -1, dir = 0;
+                double bv = 0.0;
+                for (int p = 0; p < m; ++p) {
+                    const int v = head[p];
+                    const double tol = v < n ? FEAS_TOL : (v == n ? INF : ftol[v - n - 1]);
+                    double viol = 0.0;
+                    int dd = 0;
+                    if (beta[p] < lo[v] - tol) viol = lo[v] - beta[p], dd = -1;
+                    else if (beta[p] > hi[v] + tol) viol = beta[p] - hi[v], dd = 1;
+                    if (viol > bv) bv = viol, best = p, dir = dd;
+                }
+                int act = A_PIVOT;
+                if (best < 0) act = since > 0 ? A_REFACTOR : A_DONE;
+                else if (iters >= cap) act = A_GIVEUP;
+                isc[I_ACT] = act, isc[I_P] = best, isc[I_DIR] = dir, isc[I_CNT] = 0;
+                dsc[D_SLOPE] = bv;
+            }
+            __syncthreads();
+            const int act = isc[I_ACT];
+            if (act == A_DONE) break;
+            if (act == A_GIVEUP) {
+                status = MRBF_SD_GAVE_UP;
+                break;
+            }
+            if (act == A_REFACTOR) {
+                since = 0;
+                if (!refactor(L, m, w, head, Binv, aug, part, colq, cmax, isc)) status = MRBF_SD_GAVE_UP;
+                continue;
+            }
+            ++iters;
+            const int p = isc[I_P], dir = isc[I_DIR];
+            const double slope0 = dsc[D_SLOPE];
+            if (t < m) rho[t] = Binv[p * m + t], yv[t] = Binv[i0 * m + t];
+            __syncthreads();
+            // ---- pivot row alpha_p = e_p' B^-1 A and reduced costs d_j = c_j - y' A_j over all nonbasic columns
+            double amax = 0.0;
+            for (int j = t; j < nc; j += THREADS) {
+                if (pos[j] >= 0) continue;
+                double sy = 0.0, sr = 0.0;
+                if (j < n) {
+                    for (int i = 0; i < m; ++i) {
+                        const double aij = L.a(i, j);
+                        sy += aij * yv[i], sr += aij * rho[i];
+                    }
+                } else if (j == n) {
+                    for (int i = 0; i < k; ++i) sy -= w[i] * yv[i], sr -= w[i] * rho[i];
+                } else {
+                    sy = yv[j - n - 1], sr = rho[j - n - 1];
+                }
+                const double ah = dir < 0 ? -sr : sr;
+                ap[j] = ah, dj[j] = (j == n ? 1.0 : 0.0) - sy;
+                if (lo[j] < hi[j]) amax = fmax(amax, fabs(ah));
+            }
+            part[t] = amax;
+            __syncthreads();
+            for (int s = THREADS / 2; s > 0; s >>= 1) {
+                if (t < s) part[t] = fmax(part[t], part[t + s]);
+                __syncthreads();
+            }
+            const double ptol = PIVOT_TOL * part[0];
+            // ---- breakpoints of the dual step: compacted (index only), then sorted by (breakpoint, column)
+            for (int j = t; j < nc; j += THREADS) {
+                if (pos[j] >= 0 || !(lo[j] < hi[j])) continue;
+                const double ah = ap[j];
+                const bool at_lo = xv[j] == lo[j];
+                if (at_lo ? ah > ptol : ah < -ptol) {
+                    const int slot = atomicAdd(&isc[I_CNT], 1);
+                    skey[slot] = at_lo ? fmax(dj[j], 0.0) / ah : fmin(dj[j], 0.0) / ah;
+                    sidx[slot] = j;
+                }
+            }
+            __syncthreads();
+            const int cnt = isc[I_CNT];
+            if (cnt == 0) {
+                status = MRBF_SD_INFEASIBLE;  // dual unbounded
+                break;
+            }
+            int P2 = 1;
+            while (P2 < cnt) P2 <<= 1;
+            for (int e = cnt + t; e < P2; e += THREADS) skey[e] = INF, sidx[e] = 0x7fffffff;
+            __syncthreads();
+            for (int size = 2; size <= P2; size <<= 1)
+                for (int stride = size >> 1; stride > 0; stride >>= 1) {
+                    for (int e = t; e < P2 / 2; e += THREADS) {
+                        const int i = (e / stride) * 2 * stride + e % stride, jj = i + stride;
+                        const bool up = (i & size) == 0;
+                        const double ka = skey[i], kb = skey[jj];
+                        const int ia = sidx[i], ib = sidx[jj];
+                        const bool gt = ka > kb || (ka == kb && ia > ib);
+                        if (gt == up) skey[i] = kb, skey[jj] = ka, sidx[i] = ib, sidx[jj] = ia;
+                    }
+                    __syncthreads();
+                }
+            // ---- the slope walk: every boxed breakpoint passed is flipped; the one that turns the slope enters
+            const int chunk = (cnt + THREADS - 1) / THREADS;
+            {
+                double acc = 0.0;
+                for (int e = t * chunk; e < min(cnt, (t + 1) * chunk); ++e) {
+                    const int j = sidx[e];
+                    acc += fabs(ap[j]) * (hi[j] - lo[j]);
+                }
+                part[t] = acc;
+            }
+            __syncthreads();
+            if (t == 0) {
+                double run = 0.0;
+                int te = -1;
+                for (int c = 0; c < THREADS && te < 0; ++c) {
+                    if (run + part[c] < slope0) {
+                        run += part[c];
+                        continue;
+                    }
+                    for (int e = c * chunk; e < min(cnt, (c + 1) * chunk); ++e) {
+                        const int j = sidx[e];
+                        run += fabs(ap[j]) * (hi[j] - lo[j]);
+                        if (run >= slope0) {
+                            te = e;
+                            break;
+                        }
+                    }
+                }
+                isc[I_TE] = te;
+            }
+            __syncthreads();
+            const int te = isc[I_TE];
+            if (te < 0) {
+                status = MRBF_SD_INFEASIBLE;
+                break;
+            }
+            for (int e = t; e < te; e += THREADS) {
+                const int j = sidx[e];
+                xv[j] = xv[j] == lo[j] ? hi[j] : lo[j];
+            }
+            flips += te;
+            const int q = sidx[te];
+            // ---- FTRAN of the entering column and the rank-1 update of B^-1
+            if (t < m) colq[t] = col_entry(L, w, q, t);
+            __syncthreads();
+            if (t < m) {
+                double acc = 0.0;
+                for (int c = 0; c < m; ++c) acc += Binv[t * m + c] * colq[c];
+                aq[t] = acc;
+            }
+            __syncthreads();
+            const double piv = aq[p];
+            if (!(fabs(piv) > 0.0)) {
+                status = MRBF_SD_GAVE_UP;
+                break;
+            }
+            if (t < m) part[t] = Binv[p * m + t] / piv;
+            __syncthreads();
+            for (int e = t; e < m * m; e += THREADS) {
+                const int i = e / m, c = e % m;
+                Binv[e] = i == p ? part[c] : Binv[e] - aq[i] * part[c];
+            }
+            if (t == 0) {
+                const int v = head[p];
+                xv[v] = dir < 0 ? lo[v] : hi[v];
+                pos[v] = -1;
+                pos[q] = p;
+                head[p] = q;
+            }
+            __syncthreads();
+            if (++since >= REFACTOR_EVERY) {
+                since = 0;
+                if (!refactor(L, m, w, head, Binv, aug, part, colq, cmax, isc)) status = MRBF_SD_GAVE_UP;
+            }
+        }
+    }
+    // ---- outputs
+    double *dout = a.d_out + lp * n;
+    if (status == MRBF_SD_OK || status == MRBF_SD_GAVE_UP) {
+        for (int j = t; j < n; j += THREADS) {
+            double v = xv[j];
+            if (pos[j] >= 0) {
+                v = fmin(fmax(beta[pos[j]], lo[j]), hi[j]);
+                if (v - lo[j] <= SNAP_TOL) v = lo[j];
+                if (hi[j] - v <= SNAP_TOL) v = hi[j];
+            }
+            dout[j] = v;
+            dj[j] = v;
+        }
+        __syncthreads();
+        row_pass(n, k, [&](int i, int j) { return L.G[(size_t)j * k + i] * dj[j]; }, part, rhs);
+        if (t == 0) {
+            double mx = -INF;
+            for (int i = 0; i < k; ++i)
+                if (w[i] > 0.0) mx = fmax(mx, rhs[i] / w[i]);
+            a.omega_out[lp] = -mx;
+        }
+        if (a.dual_out && t < m) a.dual_out[lp * m + t] = -Binv[i0 * m + t];
+    } else {
+        for (int j = t; j < n; j += THREADS) dout[j] = 0.0;
+        if (t == 0) a.omega_out[lp] = -INF;
+        if (a.dual_out && t < m) a.dual_out[lp * m + t] = 0.0;
+    }
+    if (t == 0) {
+        a.status_out[lp] = status;
+        if (a.iters_out) a.iters_out[2 * lp] = iters, a.iters_out[2 * lp + 1] = flips;
+    }
+}
+
+// ---- get_criticality's right-hand sides: one workgroup per LP row, the Jacobians / values of the evaluation kernels as they lie
+struct RowSrc {
+    int kind;      // 0 objective row (Jacobian at x_n), 1 linear row, 2 modelled constraint row (Jacobian at x, value at x_n)
+    int dst;       // objective position / row of A_eq or A_ineq
+    int eq;        // 1: equality block
+    int stride;    // rows of the model (k_j): the Jacobian is k_j x d column-major per point
+    int64_t jac;   // offset of the row's first entry in the Jacobian buffer (point 0 = x_n; point 1 follows after k_j d)
+    int64_t val;   // offset of the row's value at x_n / index of the linear row
+};
+struct AsmArgs {
+    int n, k, rows;
+    const double *J, *V, *xn, *x, *Alin, *blin;
+    double *G, *Aeq, *beq, *Ain, *bin;
+    RowSrc src[MAXM];
+};
+
+__global__ __launch_bounds__(THREADS) void sd_assemble_kernel(AsmArgs a) {
+    __shared__ double part[THREADS];
+    const RowSrc s = a.src[blockIdx.x];
+    const int t = threadIdx.x, n = a.n;
+    if (s.kind == 0) {
+        for (int j = t; j < n; j += THREADS) a.G[(size_t)j * a.k + s.dst] = a.J[s.jac + (int64_t)j * s.stride];
+        return;
+    }
+    double *row = (s.eq ? a.Aeq : a.Ain) + (size_t)s.dst * n;
+    const double *src = s.kind == 1 ? a.Alin + s.val * n : a.J + s.jac + (int64_t)s.stride * n;  // modelled: point 1 (x)
+    const int64_t step = s.kind == 1 ? 1 : s.stride;
+    double acc = 0.0;
+    for (int j = t; j < n; j += THREADS) {
+        const double v = src[j * step];
+        row[j] = v;
+        acc += v * (s.kind == 1 ? a.xn[j] : a.xn[j] - a.x[j]);
+    }
+    part[t] = acc;
+    __syncthreads();
+    if (t == 0) {
+        double sum = 0.0;
+        for (int i = 0; i < THREADS; ++i) sum += part[i];
+        (s.eq ? a.beq : a.bin)[s.dst] = s.kind == 1 ? a.blin[s.val] - sum : -a.V[s.val] - sum;
+    }
+}
+
+// all device pointers; LPs in chunks so that the per-LP workspace stays below 256 MB
+static int launch(mrbf_ctx *ctx, int64_t n_lp, int n, int k, int meq, int min, int normalize, const double *G, const double *x,
+                  const double *lb, const double *ub, const double *Aeq, const double *beq, const double *Ain, const double *bin,
+                  double *d_out, double *omega_out, double *dual_out, int *status_out, int *iters_out) {
+    Args a;
+    a.n = n, a.k = k, a.meq = meq, a.min = min, a.m = k + meq + min, a.normalize = normalize != 0;
+    a.nc = n + 1 + a.m;
+    a.p2 = 1;
+    while (a.p2 < a.nc) a.p2 <<= 1;
+    a.G = G, a.x = x, a.lb = lb, a.ub = ub, a.Aeq = Aeq, a.beq = beq, a.Ain = Ain, a.bin = bin;
+    a.d_out = d_out, a.omega_out = omega_out, a.dual_out = dual_out, a.status_out = status_out, a.iters_out = iters_out;
+    const size_t per = (size_t)a.nc * (5 * sizeof(double) + sizeof(int));
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n_lp, ((size_t)256 << 20) / per));
+    MRBF_TRY(get_buf(ctx, S_SD_WS, (size_t)chunk * a.nc * 5, &a.ws));
+    int *wsi;
+    MRBF_TRY(get_buf(ctx, S_SD_OUT, (size_t)chunk * a.nc * sizeof(int), (void **)&wsi));
+    a.wsi = wsi;
+    const size_t shm = carve(a.m, a.p2).total;
+    MRBF_HIP(ctx, hipFuncSetAttribute((const void *)sd_lp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    for (int64_t lp0 = 0; lp0 < n_lp; lp0 += chunk) {
+        const unsigned grid = (unsigned)std::min<int64_t>(chunk, n_lp - lp0);
+        hipLaunchKernelGGL(sd_lp_kernel, dim3(grid), dim3(THREADS), shm, ctx->stream, a, lp0);
+        MRBF_HIP(ctx, hipGetLastError());
+    }
+    return 0;
+}
+
+}  // namespace sd
+}  // namespace mrbf
+
+using namespace mrbf;
+
+namespace {
+// device view of an input: the pointer itself when device memory, else a copy in `arena` (advanced)
+int sd_view(mrbf_ctx *ctx, const double *user, size_t count, double *&arena, const double **dev) {
+    if (!user || count == 0) {
+        *dev = nullptr;
+        return 0;
+    }
+    if (is_device_ptr(user)) {
+        *dev = user;
+        return 0;
+    }
+    MRBF_HIP(ctx, hipMemcpyAsync(arena, user, count * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    *dev = arena;
+    arena += count;
+    return 0;
+}
+int sd_fetch(mrbf_ctx *ctx, const double *src, size_t cnt, double *dst) {
+    if (cnt) MRBF_HIP(ctx, hipMemcpy(dst, src, cnt * sizeof(double), hipMemcpyDefault));
+    return 0;
+}
+}  // namespace
+
+extern "C" int32_t mrbf_sd_direction(mrbf_ctx *ctx, int64_t n_lp, int32_t d, int32_t k, int32_t m_eq, int32_t m_ineq, const double *G,
+                                     const double *x, const double *lb, const double *ub, const double *A_eq, const double *b_eq,
+                                     const double *A_ineq, const double *b_ineq, int32_t normalize, double *d_out, double *omega_out,
+                                     double *dual_out, int32_t *status_out, int32_t *iters_out) {
+    if (!ctx) return -1;
+    if (n_lp < 0) return fail(ctx, -2, "n_lp < 0");
+    if (d < 1 || d > sd::MAXD) return fail(ctx, -3, "d = %d out of range (1..%d)", d, sd::MAXD);
+    if (k < 1) return fail(ctx, -4, "k = %d: at least one objective row", k);
+    if (m_eq < 0) return fail(ctx, -5, "m_eq < 0");
+    if (m_ineq < 0) return fail(ctx, -6, "m_ineq < 0");
+    if ((int64_t)k + m_eq + m_ineq > sd::MAXM) return fail(ctx, -4, "k + m_eq + m_ineq = %d rows (at most %d)", k + m_eq + m_ineq, sd::MAXM);
+    if (!G) return fail(ctx, -7, "G is NULL");
+    if (!x) return fail(ctx, -8, "x is NULL");
+    if (!lb) return fail(ctx, -9, "lb is NULL");
+    if (!ub) return fail(ctx, -10, "ub is NULL");
+    if (m_eq && !A_eq) return fail(ctx, -11, "A_eq is NULL");
+    if (m_eq && !b_eq) return fail(ctx, -12, "b_eq is NULL");
+    if (m_ineq && !A_ineq) return fail(ctx, -13, "A_ineq is NULL");
+    if (m_ineq && !b_ineq) return fail(ctx, -14, "b_ineq is NULL");
+    if (!d_out) return fail(ctx, -16, "d_out is NULL");
+    if (!omega_out) return fail(ctx, -17, "omega_out is NULL");
+    if (!status_out) return fail(ctx, -19, "status_out is NULL");
+    if (n_lp == 0) return MRBF_OK;
+    (void)hipSetDevice(ctx->device);
+    PinGuard pin(ctx);
+    const int m = k + m_eq + m_ineq;
+    const size_t N = (size_t)n_lp;
+    const size_t in_cnt = N * ((size_t)k * d + 3 * (size_t)d + (size_t)(m_eq + m_ineq) * (d + 1));
+    double *arena;
+    MRBF_TRY(get_buf(ctx, S_SD_IN, in_cnt, &arena));
+    const double *dG, *dx, *dlb, *dub, *dAeq, *dbeq, *dAin, *dbin;
+    MRBF_TRY(sd_view(ctx, G, N * k * d, arena, &dG));
+    MRBF_TRY(sd_view(ctx, x, N * d, arena, &dx));
+    MRBF_TRY(sd_view(ctx, lb, N * d, arena, &dlb));
+    MRBF_TRY(sd_view(ctx, ub, N * d, arena, &dub));
+    MRBF_TRY(sd_view(ctx, A_eq, N * m_eq * d, arena, &dAeq));
+    MRBF_TRY(sd_view(ctx, b_eq, N * m_eq, arena, &dbeq));
+    MRBF_TRY(sd_view(ctx, A_ineq, N * m_ineq * d, arena, &dAin));
+    MRBF_TRY(sd_view(ctx, b_ineq, N * m_ineq, arena, &dbin));
+    // outputs: the caller's device buffers in place, else one staging buffer (doubles, then the int words)
+    const bool dev_d = is_device_ptr(d_out), dev_w = is_device_ptr(omega_out), dev_y = dual_out && is_device_ptr(dual_out);
+    const bool dev_s = is_device_ptr(status_out), dev_i = iters_out && is_device_ptr(iters_out);
+    const size_t out_dbl = N * d + N + N * m, out_int = 3 * N;
+    double *ob;
+    MRBF_TRY(get_buf(ctx, S_STAGE_D, out_dbl + (out_int + 1) / 2 + 1, &ob));
+    double *od = dev_d ? d_out : ob, *ow = dev_w ? omega_out : ob + N * d, *oy = dual_out ? (dev_y ? dual_out : ob + N * d + N) : nullptr;
+    int *oi = reinterpret_cast<int *>(ob + out_dbl);
+    int *os = dev_s ? status_out : oi, *ot = iters_out ? (dev_i ? iters_out : oi + N) : nullptr;
+    MRBF_TRY(sd::launch(ctx, n_lp, d, k, m_eq, m_ineq, normalize, dG, dx, dlb, dub, dAeq, dbeq, dAin, dbin, od, ow, oy, os, ot));
+    if (!dev_d) MRBF_HIP(ctx, hipMemcpyAsync(d_out, od, N * d * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (!dev_w) MRBF_HIP(ctx, hipMemcpyAsync(omega_out, ow, N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (oy && !dev_y) MRBF_HIP(ctx, hipMemcpyAsync(dual_out, oy, N * m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (!dev_s) MRBF_HIP(ctx, hipMemcpyAsync(status_out, os, N * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    if (ot && !dev_i) MRBF_HIP(ctx, hipMemcpyAsync(iters_out, ot, 2 * N * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    MRBF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    pin.flush();
+    return MRBF_OK;
+}
+
+extern "C" int32_t mrbf_sd_criticality(mrbf_ctx *ctx, const mrbf_ps_problem *prob, const double *x, const double *x_n, const double *lb,
+                                       const double *ub, int32_t normalize, double *d_out, double *dual_out, mrbf_sd_info *info) {
+    if (!ctx) return -1;
+    if (!prob) return fail(ctx, -2, "problem is NULL");
+    if (!x) return fail(ctx, -3, "x is NULL");
+    if (!x_n) return fail(ctx, -4, "x_n is NULL");
+    if (!lb) return fail(ctx, -5, "lb is NULL");
+    if (!ub) return fail(ctx, -6, "ub is NULL");
+    if (!d_out) return fail(ctx, -8, "d_out is NULL");
+    if (!info) return fail(ctx, -10, "info is NULL");
+    std::memset(info, 0, sizeof(*info));
+    if (prob->n_models < 1 || !prob->models || !prob->roles) return fail(ctx, -2, "mrbf_sd_criticality: grouped models with a roles table are required");
+    const int k = prob->n_objectives;
+    if (k < 1) return fail(ctx, -2, "mrbf_sd_criticality: %d objectives", k);
+    if (prob->n_lin_eq < 0 || prob->n_lin_ineq < 0) return fail(ctx, -2, "mrbf_sd_criticality: negative constraint count");
+    if ((prob->n_lin_eq && (!prob->A_eq || !prob->b_eq)) || (prob->n_lin_ineq && (!prob->A_ineq || !prob->b_ineq)))
+        return fail(ctx, -2, "mrbf_sd_criticality: linear constraint matrices are NULL");
+    // ---- the rows of the LP from the roles table
+    const int d = prob->models[0] ? prob->models[0]->d : 0;
+    std::vector<int> seen(k, 0);
+    std::vector<sd::RowSrc> obj(k), meq_rows, min_rows;
+    std::vector<int64_t> joff(prob->n_models), voff(prob->n_models);
+    int64_t jtot = 0, vtot = 0;
+    for (int j = 0, e = 0; j < prob->n_models; ++j) {
+        const mrbf_model *M = prob->models[j];
+        if (!M) return fail(ctx, -2, "mrbf_sd_criticality: model %d is NULL", j);
+        if (M->d != d) return fail(ctx, -2, "mrbf_sd_criticality: model %d has %d variables, model 0 has %d", j, M->d, d);
+        joff[j] = jtot, voff[j] = vtot;
+        jtot += (int64_t)2 * M->k * d, vtot += (int64_t)2 * M->k;
+        for (int c = 0; c < M->k; ++c, ++e) {
+            const int role = prob->roles[e];
+            sd::RowSrc s{0, 0, 0, M->k, joff[j] + c, voff[j] + c};
+            if (role >= 0) {
+                if (role >= k || seen[role]) return fail(ctx, -2, "mrbf_sd_criticality: roles[%d] = %d is not a (new) objective position", e, role);
+                seen[role] = 1;
+                s.dst = role;
+                obj[role] = s;
+            } else if (role == MRBF_ROLE_EQ || role == MRBF_ROLE_INEQ) {
+                s.kind = 2;
+                (role == MRBF_ROLE_EQ ? meq_rows : min_rows).push_back(s);
+            } else if (role != MRBF_ROLE_NONE) {
+                return fail(ctx, -2, "mrbf_sd_criticality: roles[%d] = %d is not a role", e, role);
+            }
+        }
+    }
+    for (int l = 0; l < k; ++l)
+        if (!seen[l]) return fail(ctx, -2, "mrbf_sd_criticality: objective %d is not an output of any model", l);
+    const int n_nl = (int)(meq_rows.size() + min_rows.size()), n_lin = prob->n_lin_eq + prob->n_lin_ineq;
+    if (mrbf_dispatch_sd(d, k, prob->n_models, n_nl, n_lin, 0) != MRBF_DISPATCH_DEVICE)
+        return fail(ctx, -2, "mrbf_sd_criticality: d = %d / k = %d / %d rows outside the device path (ask mrbf_dispatch_sd first)", d, k, k + n_nl + n_lin);
+    const int meq = prob->n_lin_eq + (int)meq_rows.size(), min = prob->n_lin_ineq + (int)min_rows.size(), m = k + meq + min;
+    (void)hipSetDevice(ctx->device);
+    PinGuard pin(ctx);
+    // ---- host inputs, packed: [x_n; x] (the two evaluation sites), lb, ub, linear rows (eq, then ineq), their b
+    const size_t nlin = (size_t)n_lin;
+    std::vector<double> h((size_t)4 * d + nlin * (d + 1));
+    double *hxn = h.data(), *hx = hxn + d, *hlb = hx + d, *hub = hlb + d, *hA = hub + d, *hb = hA + nlin * d;
+    MRBF_TRY(sd_fetch(ctx, x_n, d, hxn));
+    MRBF_TRY(sd_fetch(ctx, x, d, hx));
+    MRBF_TRY(sd_fetch(ctx, lb, d, hlb));
+    MRBF_TRY(sd_fetch(ctx, ub, d, hub));
+    MRBF_TRY(sd_fetch(ctx, prob->A_eq, (size_t)prob->n_lin_eq * d, hA));
+    MRBF_TRY(sd_fetch(ctx, prob->A_ineq, (size_t)prob->n_lin_ineq * d, hA + (size_t)prob->n_lin_eq * d));
+    MRBF_TRY(sd_fetch(ctx, prob->b_eq, prob->n_lin_eq, hb));
+    MRBF_TRY(sd_fetch(ctx, prob->b_ineq, prob->n_lin_ineq, hb + prob->n_lin_eq));
+    hipEvent_t e0 = ctx->ev[0], e1 = ctx->ev[1];
+    MRBF_HIP(ctx, hipEventRecord(e0, ctx->stream));
+    // device arena: inputs | Jacobians | values | LP data (G, A_eq, b_eq, A_ineq, b_ineq) | outputs (d, omega, dual, 3 int words)
+    const size_t lp_cnt = (size_t)k * d + (size_t)(meq + min) * (d + 1), out_cnt = (size_t)d + 1 + m + 2;
+    double *base;
+    MRBF_TRY(get_buf(ctx, S_SD_IN, h.size() + jtot + vtot + lp_cnt + out_cnt, &base));
+    double *dJ = base + h.size(), *dV = dJ + jtot, *dG = dV + vtot, *dAeq = dG + (size_t)k * d, *dbeq = dAeq + (size_t)meq * d;
+    double *dAin = dbeq + meq, *dbin = dAin + (size_t)min * d, *dout = dbin + min;
+    MRBF_HIP(ctx, hipMemcpyAsync(base, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    const double *dxn = base, *dx = base + d, *dlb = base + 2 * d, *dub = base + 3 * d, *dA = base + 4 * d, *db = dA + nlin * d;
+    // ---- values and Jacobians of every model at x_n and x: one sweep per model
+    for (int j = 0, e = 0; j < prob->n_models; ++j) {
+        const mrbf_model *M = prob->models[j];
+        bool used = false;
+        for (int c = 0; c < M->k; ++c) used = used || prob->roles[e + c] != MRBF_ROLE_NONE;
+        e += M->k;
+        if (used) MRBF_TRY(eval_model(ctx, M, 2, dxn, dV + voff[j], dJ + joff[j], nullptr));
+    }
+    // ---- assemble G, A_eq / b_eq (linear, then modelled), A_ineq / b_ineq (likewise) on the device
+    sd::AsmArgs aa;
+    aa.n = d, aa.k = k, aa.rows = m;
+    aa.J = dJ, aa.V = dV, aa.xn = dxn, aa.x = dx, aa.Alin = dA, aa.blin = db;
+    aa.G = dG, aa.Aeq = dAeq, aa.beq = dbeq, aa.Ain = dAin, aa.bin = dbin;
+    int r = 0;
+    for (int l = 0; l < k; ++l) aa.src[r++] = obj[l];
+    for (int i = 0; i < prob->n_lin_eq; ++i) aa.src[r++] = sd::RowSrc{1, i, 1, 1, 0, i};
+    for (size_t i = 0; i < meq_rows.size(); ++i) {
+        aa.src[r] = meq_rows[i];
+        aa.src[r].dst = prob->n_lin_eq + (int)i, aa.src[r++].eq = 1;
+    }
+    for (int i = 0; i < prob->n_lin_ineq; ++i) aa.src[r++] = sd::RowSrc{1, i, 0, 1, 0, prob->n_lin_eq + i};
+    for (size_t i = 0; i < min_rows.size(); ++i) {
+        aa.src[r] = min_rows[i];
+        aa.src[r].dst = prob->n_lin_ineq + (int)i, aa.src[r++].eq = 0;
+    }
+    hipLaunchKernelGGL(sd::sd_assemble_kernel, dim3((unsigned)m), dim3(sd::THREADS), 0, ctx->stream, aa);
+    MRBF_HIP(ctx, hipGetLastError());
+    int *oi = reinterpret_cast<int *>(dout + d + 1 + m);
+    MRBF_TRY(sd::launch(ctx, 1, d, k, meq, min, normalize, dG, dxn, dlb, dub, meq ? dAeq : nullptr, meq ? dbeq : nullptr,
+                        min ? dAin : nullptr, min ? dbin : nullptr, dout, dout + d, dout + d + 1, oi, oi + 1));
+    // ---- one read-back
+    std::vector<double> hout(out_cnt);
+    MRBF_HIP(ctx, hipMemcpyAsync(hout.data(), dout, out_cnt * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    MRBF_HIP(ctx, hipEventRecord(e1, ctx->stream));
+    MRBF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    pin.flush();
+    MRBF_HIP(ctx, hipEventElapsedTime(&info->ms_total, e0, e1));
+    int words[3];
+    std::memcpy(words, hout.data() + d + 1 + m, sizeof(words));
+    info->status = words[0], info->iterations = words[1], info->bound_flips = words[2];
+    info->omega = hout[d];
+    if (is_device_ptr(d_out)) MRBF_HIP(ctx, hipMemcpy(d_out, hout.data(), d * sizeof(double), hipMemcpyHostToDevice));
+    else std::memcpy(d_out, hout.data(), d * sizeof(double));
+    if (dual_out) {
+        if (is_device_ptr(dual_out)) MRBF_HIP(ctx, hipMemcpy(dual_out, hout.data() + d + 1, m * sizeof(double), hipMemcpyHostToDevice));
+        else std::memcpy(dual_out, hout.data() + d + 1, m * sizeof(double));
+    }
+    if (info->status == MRBF_SD_GAVE_UP) return fail(ctx, -2, "mrbf_sd_criticality: the direction LP gave up (take the reference method)");
+    return MRBF_OK;
+}

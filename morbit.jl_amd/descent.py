@@ -1,7 +1,9 @@
 """Host-side mirror of the descent-step consumers of the surrogate path.
 
 Mirrors /root/reference/src/descent.jl: SteepestDescentConfig backtracking fields (:55-66),
-_armijo_condition (:137-143) and _backtrack (:150-185).  The reference evaluates the <= max_loops
+_armijo_condition (:137-143) and _backtrack (:150-185); and the steepest-descent criticality: the direction LP
+_steepest_descent_direction (:91-135, HiGHS on the host), get_criticality (:187-241, routed to mrbf_sd_criticality) and
+compute_descent_step (:243-320) with intersect_box / _intersect_bounds (utilities.jl:126-287).  The reference evaluates the <= max_loops
 step sizes one after another; here all of them go to the device in one batch (mrbf_backtrack when the
 objectives are one grouped RbfModel, else one batched container sweep) and the same loop logic picks
 the step, so the returned (x_plus, mx_plus, step) are those of the sequential loop.
@@ -80,3 +82,298 @@ def _backtrack(x, direction, step_size, omega, sc, cfg, scal=None):
             break
         i += 1
     return X[i + 1], M[i + 1], steps[i] * direction, i
+
+
+# ---- steepest-descent criticality (descent.jl:91-135, :187-320) --------------------------------------------------------------------
+def _sd_box(x, lb, ub):
+    """the direction's box of descent.jl:112-116, exactly as the device kernel forms it: [max(-1, lb - x), min(1, ub - x)]"""
+    x = np.asarray(x, dtype=np.float64)
+    return np.maximum(-1.0, np.asarray(lb, dtype=np.float64) - x), np.minimum(1.0, np.asarray(ub, dtype=np.float64) - x)
+
+
+def _sd_omega(G, w, d):
+    """omega = -max_i (g_i . d) / w_i over the rows with w_i > 0 (recomputed from d, as mrbf_sd_direction does)"""
+    r = np.asarray(G, dtype=np.float64) @ np.asarray(d, dtype=np.float64)
+    ok = w > 0
+    return -float(np.max(r[ok] / w[ok])) if ok.any() else -np.inf
+
+
+def _steepest_descent_direction(x, G, lb, ub, A_eq=None, b_eq=None, A_ineq=None, b_ineq=None, normalize=True, tol=1e-10,
+                                want_status=False):
+    """descent.jl:91-135 with HiGHS (scipy.optimize.linprog) in place of JuMP + OSQP: min alpha over (d, alpha) subject to
+    G d <= alpha w (w = row norms with `normalize`, else 1), the box of `_sd_box`, A_eq d = b_eq, A_ineq d <= b_ineq.  Returns
+    (d, omega) with omega = -alpha recomputed from d; (zeros, -inf) where the reference's catch branch fires (descent.jl:130-133:
+    no objective row under `normalize`, an empty box, rows that cannot be met).  want_status: also the MRBF_SD_* status."""
+    from scipy.optimize import linprog
+
+    x = np.asarray(x, dtype=np.float64)
+    n = x.size
+    G = np.asarray(G, dtype=np.float64).reshape(-1, n)
+    k = G.shape[0]
+    w = np.sqrt(np.sum(G * G, axis=1)) if normalize else np.ones(k)
+    lo, hi = _sd_box(x, lb, ub)
+
+    def out(d, omega, status):
+        return (d, omega, status) if want_status else (d, omega)
+
+    if not np.all(lo <= hi):
+        return out(np.zeros(n), -np.inf, _lib.SD_INFEASIBLE)
+    if not np.any(w > 0):
+        return out(np.zeros(n), -np.inf, _lib.SD_NO_OBJECTIVE)
+    A_ub = [np.hstack([G, -w[:, None]])]
+    b_ub = [np.zeros(k)]
+    if b_ineq is not None and np.asarray(b_ineq).size:
+        A_ub.append(np.hstack([np.asarray(A_ineq, dtype=np.float64).reshape(-1, n), np.zeros((np.asarray(b_ineq).size, 1))]))
+        b_ub.append(np.asarray(b_ineq, dtype=np.float64).ravel())
+    Ae = be = None
+    if b_eq is not None and np.asarray(b_eq).size:
+        Ae = np.hstack([np.asarray(A_eq, dtype=np.float64).reshape(-1, n), np.zeros((np.asarray(b_eq).size, 1))])
+        be = np.asarray(b_eq, dtype=np.float64).ravel()
+    c = np.zeros(n + 1)
+    c[n] = 1.0
+    res = linprog(c, A_ub=np.vstack(A_ub), b_ub=np.concatenate(b_ub), A_eq=Ae, b_eq=be,
+                  bounds=list(zip(lo, hi)) + [(None, None)], method="highs",
+                  options={"primal_feasibility_tolerance": tol, "dual_feasibility_tolerance": tol})
+    if res.status != 0:
+        return out(np.zeros(n), -np.inf, _lib.SD_INFEASIBLE if res.status == 2 else _lib.SD_NO_OBJECTIVE)
+    d = np.clip(res.x[:n], lo, hi)
+    return out(d, _sd_omega(G, w, d), _lib.SD_OK)
+
+
+def _sd_problem(plan, lin):
+    """the mrbf_ps_problem of a container plan (linear constraints lin = (A_eq, b_eq, A_ineq, b_ineq) in scaled variables); the
+    second value keeps the arrays alive"""
+    A_eq, b_eq, A_in, b_in = [None if a is None or np.asarray(a).size == 0 else np.ascontiguousarray(a, dtype=np.float64) for a in lin]
+    handles = (ctypes.c_void_p * len(plan["models"]))(*[m.model.value if hasattr(m.model, "value") else m.model for m in plan["models"]])
+    roles = (ctypes.c_int32 * max(len(plan["roles"]), 1))(*plan["roles"])
+    prob = _lib.PsProblem(n_models=len(plan["models"]), n_objectives=plan["k"], models=handles, roles=roles,
+                          n_lin_eq=0 if b_eq is None else b_eq.size, n_lin_ineq=0 if b_in is None else b_in.size,
+                          A_eq=None if b_eq is None else A_eq.ctypes.data, b_eq=None if b_eq is None else b_eq.ctypes.data,
+                          A_ineq=None if b_in is None else A_in.ctypes.data, b_ineq=None if b_in is None else b_in.ctypes.data, eq_tol=-1.0)
+    return prob, (handles, roles, A_eq, b_eq, A_in, b_in)
+
+
+def sd_criticality_device(plan, x, x_n, lb, ub, normalize=True, lin=None, want_duals=False):
+    """one mrbf_sd_criticality call; returns (rc, omega, d, info dict[, duals])"""
+    ctx = plan["models"][0].ctx
+    x, x_n = np.ascontiguousarray(x, dtype=np.float64), np.ascontiguousarray(x_n, dtype=np.float64)
+    lb, ub = np.ascontiguousarray(lb, dtype=np.float64), np.ascontiguousarray(ub, dtype=np.float64)
+    prob, keep = _sd_problem(plan, lin or (None,) * 4)
+    m = plan["k"] + plan["n_con"] + sum(0 if b is None else b.size for b in (keep[3], keep[5]))
+    d = np.empty(x_n.size)
+    y = np.empty(m) if want_duals else None
+    info = _lib.SdInfo()
+    rc = ctx.lib.mrbf_sd_criticality(ctx.h, ctypes.byref(prob), _lib.as_ptr(x), _lib.as_ptr(x_n), _lib.as_ptr(lb), _lib.as_ptr(ub),
+                                     int(bool(normalize)), _lib.as_ptr(d), _lib.as_ptr(y), ctypes.byref(info))
+    out = (rc, float(info.omega), d, info.asdict())
+    return out + (y,) if want_duals else out
+
+
+def _sd_host_rows(sc, scal, x, x_n, lin):
+    """G, A_eq, b_eq, A_ineq, b_ineq of get_criticality (descent.jl:196-236) on container Jacobians"""
+    x, x_n = np.asarray(x, dtype=np.float64), np.asarray(x_n, dtype=np.float64)
+    n = x_n.size
+    G = sg.eval_container_objectives_jacobian_at_scaled_site(sc, scal, x_n)
+    lin = lin or (None,) * 4
+    step = x_n - x
+    A_eq, b_eq, A_in, b_in = [np.zeros((0, n))], [np.zeros(0)], [np.zeros((0, n))], [np.zeros(0)]
+    if lin[1] is not None and np.asarray(lin[1]).size:
+        A = np.asarray(lin[0], dtype=np.float64).reshape(-1, n)
+        A_eq.append(A)
+        b_eq.append(np.asarray(lin[1], dtype=np.float64) - A @ x_n)
+    if lin[3] is not None and np.asarray(lin[3]).size:
+        A = np.asarray(lin[2], dtype=np.float64).reshape(-1, n)
+        A_in.append(A)
+        b_in.append(np.asarray(lin[3], dtype=np.float64) - A @ x_n)
+    if sc.lists["nl_eq_constraint"]:
+        Dm = sg.eval_container_nl_eq_constraints_jacobian_at_scaled_site(sc, scal, x)
+        A_eq.append(Dm)
+        b_eq.append(-sg.eval_container_nl_eq_constraints_at_scaled_site(sc, scal, x_n) - Dm @ step)
+    if sc.lists["nl_ineq_constraint"]:
+        Dm = sg.eval_container_nl_ineq_constraints_jacobian_at_scaled_site(sc, scal, x)
+        A_in.append(Dm)
+        b_in.append(-sg.eval_container_nl_ineq_constraints_at_scaled_site(sc, scal, x_n) - Dm @ step)
+    return G, np.vstack(A_eq), np.concatenate(b_eq), np.vstack(A_in), np.concatenate(b_in)
+
+
+def get_criticality_sd(cfg, sc, scal, x, x_n, lb, ub, lin=None, stats=None):
+    """`get_criticality(::SteepestDescentConfig, mop, scal, x_it, x_it_n, db, sc, ac)` (descent.jl:187-241) as HipRbf.jl routes it:
+    mrbf_dispatch_sd decides, mrbf_sd_criticality solves on the device, and where the decision table or mrbf_dispatch_after say so
+    the reference method runs -- the HiGHS direction LP on container Jacobians.  lb / ub: the global bounds in scaled variables
+    (full_bounds_internal); lin = (A_eq, b_eq, A_ineq, b_ineq) in scaled variables.  Never raises on a size limit.  Returns (omega, d)."""
+    lib = _lib.load()
+    plan = sg.container_plan(sc)
+    n = int(np.asarray(x_n).size)
+    lin = lin or (None,) * 4
+    n_lin = sum(0 if b is None else int(np.asarray(b).size) for b in (lin[1], lin[3]))
+    if lib.mrbf_dispatch_sd(n, plan["k"], len(plan["models"]), plan["n_con"], n_lin, plan["n_foreign"]) == _lib.DISPATCH_DEVICE:
+        rc, omega, d, info = sd_criticality_device(plan, x, x_n, lb, ub, cfg.normalize, lin)
+        if stats is not None:
+            stats.update(info)
+            stats["path"] = "device"
+        if rc == 0:
+            return omega, d
+        if not lib.mrbf_dispatch_after(_lib.ENTRY_SD, rc):
+            plan["models"][0].ctx.check(rc)
+    if stats is not None:
+        stats["path"] = "reference"
+    G, A_eq, b_eq, A_in, b_in = _sd_host_rows(sc, scal, x, x_n, lin)
+    d, omega = _steepest_descent_direction(x_n, G, lb, ub, A_eq, b_eq, A_in, b_in, cfg.normalize)
+    return omega, d
+
+
+def _isapprox(a, b):
+    """Julia's isapprox with its defaults (atol = 0, rtol = sqrt(eps)): norm(a - b) <= rtol max(norm(a), norm(b)), or a == b"""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    if np.array_equal(a, b):
+        return True
+    if not (np.all(np.isfinite(a)) and np.all(np.isfinite(b))):
+        return False
+    return bool(np.linalg.norm(a - b) <= np.sqrt(np.finfo(np.float64).eps) * max(np.linalg.norm(a), np.linalg.norm(b)))
+
+
+def _local_bounds(x, delta, lb, ub):
+    """utilities.jl:290-294"""
+    x = np.asarray(x, dtype=np.float64)
+    return np.maximum(np.asarray(lb, dtype=np.float64), x - delta), np.minimum(np.asarray(ub, dtype=np.float64), x + delta)
+
+
+def _intersect_bound_vec(x, b, direction, sense):
+    """utilities.jl:126-152"""
+    b = np.asarray(b, dtype=np.float64)
+    if b.size == 0:
+        return np.zeros(0)
+    nz = direction != 0
+    dd = direction[nz]
+    tmp = b[nz] - x[nz]
+    tz = tmp == 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        s = tmp[~tz] / dd[~tz]
+    on = dd[tz]
+    if on.size == 0:
+        return s
+    onb = np.where(on > 0, np.inf, 0.0) if sense == "lb" else np.where(on < 0, np.inf, 0.0)
+    return np.concatenate([s, onb])
+
+
+def _intersect_bounds(x, d, lb=(), ub=(), A_eq=None, b_eq=None, A_ineq=None, b_ineq=None, ret_mode="pos", impossible_val=0.0):
+    """utilities.jl:156-282 (_eps = 0): the largest (ret_mode "pos") / smallest ("neg") step sigma with lb <= x + sigma d <= ub,
+    A_eq (x + sigma d) = b_eq, A_ineq (x + sigma d) <= b_ineq"""
+    x, d = np.asarray(x, dtype=np.float64), np.asarray(d, dtype=np.float64)
+    if not np.any(d):
+        return np.inf
+    has_eq = A_eq is not None and np.asarray(A_eq).size > 0
+    has_in = A_ineq is not None and np.asarray(A_ineq).size > 0
+    if not has_eq:
+        s = [_intersect_bound_vec(x, lb, d, "lb"), _intersect_bound_vec(x, ub, d, "ub")]
+        if has_in:
+            A = np.asarray(A_ineq, dtype=np.float64)
+            bi = np.zeros(x.size) if b_ineq is None or np.asarray(b_ineq).size == 0 else np.asarray(b_ineq, dtype=np.float64)
+            s.append(_intersect_bound_vec(A @ x, bi, A @ d, "ub"))
+        s = np.concatenate(s)
+        if s.size == 0:
+            return -np.inf if ret_mode == "neg" else np.inf
+        pos, neg = s[s >= 0], s[~(s >= 0)]
+        s_pos = float(pos.min()) if pos.size else 0.0
+        s_neg = float(neg.max()) if neg.size else 0.0
+        if ret_mode == "pos":
+            return s_pos
+        if ret_mode == "neg":
+            return s_neg
+        if ret_mode == "absmax":
+            return s_pos if abs(s_pos) >= abs(s_neg) else s_neg
+        return s_neg, s_pos
+    A = np.asarray(A_eq, dtype=np.float64)
+    be = np.zeros(A.shape[0]) if b_eq is None or np.asarray(b_eq).size == 0 else np.asarray(b_eq, dtype=np.float64)
+    sigma = None
+    for i in range(A.shape[0]):
+        ad = float(A[i] @ d)
+        if ad != 0:
+            s_i = -(float(A[i] @ x) - be[i]) / ad
+        else:
+            if abs(float(A[i] @ x) - be[i]) > np.finfo(np.float64).eps:
+                return impossible_val
+            continue
+        if sigma is None:
+            sigma = s_i
+        elif not (s_i == sigma or abs(s_i - sigma) <= np.sqrt(np.finfo(np.float64).eps) * max(abs(s_i), abs(sigma))):
+            return impossible_val
+    if sigma is None:
+        sigma = np.inf
+    if np.isinf(sigma):
+        return _intersect_bounds(x, d, lb, ub, None, None, A_ineq, b_ineq)
+    xt = x + sigma * d
+    bi = np.zeros(x.size) if b_ineq is None or np.asarray(b_ineq).size == 0 else np.asarray(b_ineq, dtype=np.float64)
+    if (np.size(lb) and np.any(xt < np.asarray(lb))) or (np.size(ub) and np.any(xt > np.asarray(ub))) or \
+            (has_in and np.any(np.asarray(A_ineq) @ xt - bi > 0)):
+        return impossible_val
+    if ret_mode == "pos" and sigma < 0:
+        return impossible_val
+    if ret_mode == "neg" and sigma >= 0:
+        return impossible_val
+    return sigma
+
+
+def intersect_box(x, d, lb, ub, return_vals="absmax"):
+    """utilities.jl:285-287"""
+    return _intersect_bounds(x, d, lb, ub, ret_mode=return_vals)
+
+
+def _blockdiag(A, B):
+    A, B = np.atleast_2d(np.asarray(A, dtype=np.float64)), np.atleast_2d(np.asarray(B, dtype=np.float64))
+    out = np.zeros((A.shape[0] + B.shape[0], A.shape[1] + B.shape[1]))
+    out[:A.shape[0], :A.shape[1]] = A
+    out[A.shape[0]:, A.shape[1]:] = B
+    return out
+
+
+def _sd_stepsize(x, x_n, delta, lb, ub, d, lin=None, constraints_at_x=None):
+    """the initial step size sigma of compute_descent_step (descent.jl:251-303) and the branch that chose it ("delta" for
+    Delta <= 1, "intersect" for ||d|| ~ 1 beyond, else "one").  constraints_at_x() -> (Dm_eq, m_eq, Dm_ineq, m_ineq) at x,
+    asked for only on the "intersect" branch."""
+    x, x_n, d = np.asarray(x, dtype=np.float64), np.asarray(x_n, dtype=np.float64), np.asarray(d, dtype=np.float64)
+    n = x.size
+    lb_eff, ub_eff = _local_bounds(x, delta, lb, ub)
+    Delta = delta if _isapprox(x, x_n) else intersect_box(x_n, d, lb_eff, ub_eff, return_vals="pos")
+    norm_d = float(np.max(np.abs(d))) if n else 0.0
+    if Delta <= 1:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r = np.float64(Delta) / np.float64(norm_d)
+        return (r if np.isnan(r) else min(float(r), 1.0)), "delta"
+    if not _isapprox(norm_d, 1.0):
+        return 1.0, "one"
+    lin = lin or (None,) * 4
+    A_eq = np.zeros((0, n)) if lin[1] is None else np.asarray(lin[0], dtype=np.float64).reshape(-1, n)
+    b_eq = np.zeros(0) if lin[1] is None else np.asarray(lin[1], dtype=np.float64).ravel()
+    A_in = np.zeros((0, n)) if lin[3] is None else np.asarray(lin[2], dtype=np.float64).reshape(-1, n)
+    b_in = np.zeros(0) if lin[3] is None else np.asarray(lin[3], dtype=np.float64).ravel()
+    Dm_eq, m_eq, Dm_in, m_in = constraints_at_x() if constraints_at_x else (np.zeros((0, n)), np.zeros(0), np.zeros((0, n)), np.zeros(0))
+    step_n = x_n - x
+    sigma = _intersect_bounds(np.concatenate([x_n, step_n]), np.concatenate([d, d]), np.concatenate([lb_eff, lb_eff - x]),
+                              np.concatenate([ub_eff, ub_eff - x]), _blockdiag(A_eq, np.reshape(Dm_eq, (-1, n))),
+                              np.concatenate([b_eq, -np.ravel(m_eq)]), _blockdiag(A_in, np.reshape(Dm_in, (-1, n))),
+                              np.concatenate([b_in, -np.ravel(m_in)]), ret_mode="pos")
+    return sigma, "intersect"
+
+
+def compute_descent_step_sd(cfg, sc, scal, x, x_n, delta, lb, ub, omega, d, lin=None):
+    """compute_descent_step(::SteepestDescentConfig, ...) (descent.jl:243-320): the initial step size sigma, then the batched
+    `_backtrack` from x_n along d.  lb / ub: global bounds in scaled variables.  Returns (omega, x_plus, mx_plus, ||step||_inf)."""
+    x, x_n = np.asarray(x, dtype=np.float64), np.asarray(x_n, dtype=np.float64)
+
+    def constraints_at_x():
+        n = x.size
+        out = []
+        for kind in ("nl_eq_constraints", "nl_ineq_constraints"):
+            if sc.lists[kind[:-1]]:
+                out += [getattr(sg, "eval_container_%s_jacobian_at_scaled_site" % kind)(sc, scal, x),
+                        getattr(sg, "eval_container_%s_at_scaled_site" % kind)(sc, scal, x)]
+            else:
+                out += [np.zeros((0, n)), np.zeros(0)]
+        return tuple(out)
+
+    sigma, _ = _sd_stepsize(x, x_n, delta, lb, ub, d, lin, constraints_at_x)
+    if sigma > cfg.min_stepsize:
+        xp, mxp, step, _ = _backtrack(x_n, d, sigma, omega, sc, cfg, scal)
+        return omega, xp, mxp, float(np.max(np.abs(step))) if step.size else 0.0
+    return 0, x_n.copy(), sg.eval_container_objectives_at_scaled_site(sc, scal, x_n), 0

@@ -42,6 +42,11 @@ struct MrbfPsInfo           # mirrors mrbf_ps_info, 32 bytes
     tau::Float64
 end
 
+struct MrbfSdInfo          # mirrors mrbf_sd_info, 24 bytes
+    status::Int32; iterations::Int32; bound_flips::Int32; ms_total::Float32
+    omega::Float64
+end
+
 struct MrbfPsProblem        # mirrors mrbf_ps_problem, 72 bytes
     n_models::Int32; n_objectives::Int32
     models::Ptr{Ptr{Cvoid}}; roles::Ptr{Int32}
@@ -205,6 +210,8 @@ set_fully_linear!(m::HipRbfModel, val) = (m.fully_linear = val; nothing)
 #      so both bindings route every call the same way; 1 = device entry point, 0 = Morbit's own method
 _dispatch_ps(d, k, n_models, n_nl, n_lin, n_foreign) =
     ccall((:mrbf_dispatch_ps, libmrbf), Int32, (Int32, Int32, Int32, Int32, Int32, Int32), d, k, n_models, n_nl, n_lin, n_foreign) == 1
+_dispatch_sd(d, k, n_models, n_nl, n_lin, n_foreign) =
+    ccall((:mrbf_dispatch_sd, libmrbf), Int32, (Int32, Int32, Int32, Int32, Int32, Int32), d, k, n_models, n_nl, n_lin, n_foreign) == 1
 _dispatch_backtrack(n_models, n_foreign, in_order::Bool) =
     ccall((:mrbf_dispatch_backtrack, libmrbf), Int32, (Int32, Int32, Int32), n_models, n_foreign, in_order) == 1
 _dispatch_affine(n_candidates, d) = ccall((:mrbf_dispatch_affine, libmrbf), Int32, (Int64, Int32), n_candidates, d) == 1
@@ -661,6 +668,49 @@ function get_criticality(desc_cfg::PascolettiSerafiniConfig, mop, scal, x_it, x_
     info[].status == 1 && return 0, copy(get_x_scaled(x_it_n)), mx_trial, 0    # critical: some r_l <= 0 (descent.jl:546-549)
     info[].status == 2 && return 0, copy(get_x_scaled(x_it)), mx_trial, 0      # failure (descent.jl:571-572)
     return Xet(abs(info[].tau)), (Xet.(x_trial), mx_trial, norm(x .- x_trial, Inf))
+end
+
+"""
+Steepest-descent criticality (descent.jl:187-241) on the device (`mrbf_sd_criticality`): objective Jacobians at x_n, modelled
+constraint Jacobians at x and values at x_n by the evaluation kernels, the linearised right-hand sides of descent.jl:196-229, then the
+direction LP of `_steepest_descent_direction` (descent.jl:91-135) solved exactly (dual simplex) instead of by JuMP + OSQP.  Whenever
+the decision table says so (a `CompositeSurrogate` or another model family, more than 64 LP rows, d > 4096) or the LP gave up, Morbit's
+own method runs on the same arguments.  Returns (ω, d) in the iterate's float type.  `compute_descent_step` stays Morbit's method:
+its `_backtrack` reaches the device through the method above.
+"""
+function get_criticality(desc_cfg::SteepestDescentConfig, mop, scal, x_it, x_it_n, data_base, sc::SurrogateContainer, algo_config)
+    reference() = invoke(get_criticality, Tuple{SteepestDescentConfig,Any,Any,Any,Any,Any,Any,Any}, desc_cfg, mop, scal, x_it, x_it_n, data_base, sc, algo_config)
+    _touches_device(sc) || return reference()      # no HipRbfModel in the container: Morbit's own method, libmrbf is not touched
+    plan = _container_plan(sc)
+    x = Vector{Float64}(get_x_scaled(x_it)); x_n = Vector{Float64}(get_x_scaled(x_it_n))
+    d, k = length(x_n), plan.k
+    A_eq, b_eq = transformed_linear_eq_constraints(scal, mop)                  # AbstractMOPInterface.jl:463-481: A x_scaled (=, <=) b
+    A_in, b_in = transformed_linear_ineq_constraints(scal, mop)
+    _dispatch_sd(d, k, length(plan.models), plan.n_con, length(b_eq) + length(b_in), plan.n_foreign) || return reference()
+    lb_g, ub_g = full_bounds_internal(scal)                                    # the global bounds, not the trust region (descent.jl:202)
+    lb = Vector{Float64}(lb_g); ub = Vector{Float64}(ub_g)
+    info = Ref{MrbfSdInfo}()
+    dir = Vector{Float64}(undef, d)
+    handles = Ptr{Cvoid}[m.handle for m in plan.models]
+    roles = plan.roles
+    Aeq = Matrix{Float64}(transpose(Matrix(A_eq))); beq = Vector{Float64}(b_eq)   # row-major rows x d == the d x rows column-major matrix
+    Ain = Matrix{Float64}(transpose(Matrix(A_in))); bin = Vector{Float64}(b_in)
+    ctx = plan.models[1].ctx
+    rc = GC.@preserve handles roles Aeq beq Ain bin x x_n lb ub dir begin
+        prob = Ref(MrbfPsProblem(length(handles), k, pointer(handles), pointer(roles), length(beq), length(bin),
+                                 isempty(beq) ? C_NULL : pointer(Aeq), isempty(beq) ? C_NULL : pointer(beq),
+                                 isempty(bin) ? C_NULL : pointer(Ain), isempty(bin) ? C_NULL : pointer(bin), -1.0))
+        _locked(ctx) do hctx
+            ccall((:mrbf_sd_criticality, libmrbf), Int32,
+                  (Ptr{Cvoid}, Ref{MrbfPsProblem}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64},
+                   Ptr{Float64}, Ref{MrbfSdInfo}),
+                  hctx, prob, x, x_n, lb, ub, desc_cfg.normalize, dir, C_NULL, info)
+        end
+    end
+    rc != 0 && _fallback_rc(6, rc) && return reference()       # the LP gave up: Morbit's JuMP model on the same arguments
+    _check(ctx, rc)
+    Xet = eltype(get_x_scaled(x_it_n))
+    return Xet(info[].omega), Xet.(dir)                        # NO_OBJECTIVE / INFEASIBLE: zeros and -Inf, as descent.jl:130-133
 end
 
 # ---- site selection on the device -----------------------------------------------------------------------------------------------------

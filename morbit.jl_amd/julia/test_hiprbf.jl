@@ -157,10 +157,33 @@ end
     end
 end
 
+# Steepest-descent criticality on the device (mrbf_sd_criticality, routed by the plug-in's get_criticality(::SteepestDescentConfig, ...))
+# against Morbit's own JuMP / OSQP model (descent.jl:187-241) on the same container: OSQP's eps_rel = 1e-5 bounds the agreement.  The
+# device direction lies exactly in the box max(-1, lb - x) .. min(1, ub - x).
+@testset "steepest descent criticality: device LP vs Morbit's" begin
+    g1 = x -> sum((x .- 1) .^ 2)
+    g2 = x -> sum((x .+ 1) .^ 2)
+    for n_vars in (2, 12)
+        mop = MOP(fill(-4.0, n_vars), fill(4.0, n_vars))
+        add_objective!(mop, g1; n_out = 1, model_cfg = HipRbfConfig(; kernel = :multiquadric))
+        add_objective!(mop, g2; n_out = 1, model_cfg = HipRbfConfig(; kernel = :multiquadric))
+        Morbit.Random.seed!(1234)
+        smop, it, sdb, sc, ac, _, scal = Morbit.initialize_data(mop, fill(0.5, n_vars); algo_config = AlgorithmConfig(; max_evals = 60))
+        desc_cfg = Morbit.SteepestDescentConfig()
+        ω, d = Morbit.get_criticality(desc_cfg, smop, scal, it, it, sdb, sc, ac)
+        ω_ref, d_ref = invoke(Morbit.get_criticality, Tuple{Morbit.SteepestDescentConfig,Any,Any,Any,Any,Any,Any,Any},
+                              desc_cfg, smop, scal, it, it, sdb, sc, ac)
+        @test ω ≈ ω_ref atol = 1e-4
+        lb, ub = Morbit.full_bounds_internal(scal)
+        x = Morbit.get_x_scaled(it)
+        @test all(max.(-1, lb .- x) .<= d .<= min.(1, ub .- x))
+    end
+end
+
 # Round 6: the plug-in is inert for users who do not select HipRbfConfig.  A plain RbfConfig run -- model update with many database
-# sites (the affine filter iterates), steepest descent (`_backtrack`) and the Pascoletti-Serafini step (`get_criticality`) -- makes no
+# sites (the affine filter iterates), steepest descent (`get_criticality`, `_backtrack`) and the Pascoletti-Serafini step (`get_criticality`) -- makes no
 # ccall: it gives Morbit's own result and creates no context.  (Run this testset FIRST in a fresh session to see that it also works
-# with MRBF_LIB pointing nowhere: the three methods the plug-in adds on Morbit's own types hand over before libmrbf is touched.)
+# with MRBF_LIB pointing nowhere: the methods the plug-in adds on Morbit's own types hand over before libmrbf is touched.)
 @testset "inert for plain RbfConfig runs" begin
     n_ctx = length(Morbit._CTX)
     g1 = x -> sum((x .- 1) .^ 2)
