@@ -391,6 +391,46 @@ typedef struct {
 int32_t mrbf_sd_criticality(mrbf_ctx *ctx, const mrbf_ps_problem *problem, const double *x, const double *x_n, const double *lb,
                             const double *ub, int32_t normalize, double *d_out, double *dual_out, mrbf_sd_info *info);
 
+/* ---- the normal step: its LP on the device (normal_lp.hip) ----------------------------------------------------------------
+ * mrbf_normal_direction replaces the JuMP / OSQP model of compute_normal_step (src/descent.jl:691-757) for n_lp LPs of one shape
+ * in one launch (one workgroup per LP, exact fp64 active-set dual simplex):
+ *   minimise alpha over (n, alpha >= 0), -alpha <= n_j <= alpha, lb_j - x_j <= n_j <= ub_j - x_j, A_eq n = b_eq, A_ineq n <= b_ineq;
+ *   1 <= m_eq + m_ineq <= 64 rows, 1 <= d <= 4096; the box may be infinite either way and x may lie outside it.
+ * The rows are in the step n: for Morbit's LP pass b_eq - A_eq x, b_ineq - A_ineq x (linear rows) and -m(x) with Dm(x) (modelled
+ * rows).  Per LP (consecutive blocks): x / lb / ub d, A_eq m_eq x d and A_ineq m_ineq x d row-major, b_eq m_eq, b_ineq m_ineq
+ * (A / b may be NULL when the count is 0).  Outputs: n_out (d): clamp(x + n, lb, ub) - x (_project_into_box); alpha_out (1):
+ * ||n_out||_inf of the returned n; dual_out (m, may be NULL): the row multipliers y (equalities first; >= 0 on inequality rows),
+ * the certificate: alpha* = -y.b + min over alpha >= alpha0 of [alpha + sum_j min over n_j of (C'y)_j n_j]; status_out (1):
+ * MRBF_NS_*; iters_out (2, may be NULL): simplex iterations, pivots that swap one column's constraints.  x already satisfying
+ * every row gives n = 0 after zero iterations.  INFEASIBLE (empty box or rows that cannot be met) and GAVE_UP (the iteration
+ * cap 8 (m + d), a singular working set, or multipliers that fail the dual-feasibility check at the end) return n = NaN,
+ * alpha = +Inf, y = 0.  Every LP gets a status; the call fails only on invalid arguments (-1 without a context).  The result of
+ * an LP does not depend on its position in the batch. */
+enum { MRBF_NS_OK = 0, MRBF_NS_INFEASIBLE = 1, MRBF_NS_GAVE_UP = 2 };
+int32_t mrbf_normal_direction(mrbf_ctx *ctx, int64_t n_lp, int32_t d, int32_t m_eq, int32_t m_ineq, const double *x, const double *lb,
+                              const double *ub, const double *A_eq, const double *b_eq, const double *A_ineq, const double *b_ineq,
+                              double *n_out, double *alpha_out, double *dual_out, int32_t *status_out, int32_t *iters_out);
+/* compute_normal_step(mop, scal, x_it, data_base, sc, algo_config; variable_radius) (src/descent.jl:691-757) for a container
+ * given as an mrbf_ps_problem (only MRBF_ROLE_EQ / MRBF_ROLE_INEQ rows are used; objective rows are ignored; n_models may be 0
+ * for linear rows only; n_objectives and eq_tol are not used) in d variables (the models' d): values and Jacobians of the
+ * modelled constraints at x through the evaluation kernels (one site per model that carries constraint rows), right-hand sides
+ * b - A x (linear rows) and -m(x) (modelled rows) assembled on the device, ONE LP over the global bounds lb / ub
+ * (full_bounds_internal) and one read-back.  Radius: delta as given (fixed), or alpha / kappa_delta when variable_radius
+ * (infeasible above delta_max).  Infeasible: n_out = NaN, info->delta = -Inf.  Row order of dual_out: linear equalities,
+ * modelled equalities, linear inequalities, modelled inequalities (modelled rows in model order, then output order).  Returns
+ * -2 (take the reference method) when the decision table refuses the shape or the LP gave up (info->status = MRBF_NS_GAVE_UP). */
+typedef struct {
+    int32_t status;      /* MRBF_NS_* */
+    int32_t iterations;  /* dual simplex iterations */
+    int32_t bound_flips; /* pivots that swap one column's constraints (n_j from one bound to another) */
+    float ms_total;      /* hipEvent time of the whole call on the ctx stream */
+    double alpha;        /* ||n||_inf of the returned step (+Inf when the LP is infeasible) */
+    double delta;        /* the radius the reference returns (-Inf when infeasible) */
+} mrbf_normal_info;
+int32_t mrbf_normal_step(mrbf_ctx *ctx, const mrbf_ps_problem *problem, int32_t d, const double *x, const double *lb, const double *ub,
+                         double delta, double kappa_delta, double delta_max, int32_t variable_radius, double *n_out, double *dual_out,
+                         mrbf_normal_info *info);
+
 /* ---- the decision table of the host bindings ---------------------------------------------------------------------------
  * Which implementation a binding (morbit.jl_amd/julia/HipRbf.jl, the Python mirror) takes for one call of Morbit's interface:
  * the device entry point (MRBF_DISPATCH_DEVICE) or Morbit's own method on the same arguments (MRBF_DISPATCH_REFERENCE; Julia:
@@ -412,15 +452,18 @@ int32_t mrbf_sd_criticality(mrbf_ctx *ctx, const mrbf_ps_problem *problem, const
  *                            1024 training sites (beyond that the ordinary fit is as fast and more accurate).
  *   mrbf_dispatch_sd         get_criticality(::SteepestDescentConfig, ...) (src/descent.jl:187-241): device iff no foreign
  *                            surrogate, at least one device model, 1 <= d <= 4096, k >= 1 and k + n_nl + n_lin <= 64 LP rows.
+ *   mrbf_dispatch_normal     compute_normal_step (src/descent.jl:691-757): device iff no modelled constraint row sits on a
+ *                            foreign surrogate, 1 <= d <= 4096 and 1 <= n_nl + n_lin <= 64 LP rows (n_models may be 0).
  *   mrbf_dispatch_after      the return code rc of a device entry point (MRBF_ENTRY_*) that means "take the reference method
  *                            for this call" (start set without the tail or rank deficient, limits of the device path) rather
  *                            than an error: 1 = fall back, 0 = rc is what it says. */
 enum { MRBF_DISPATCH_REFERENCE = 0, MRBF_DISPATCH_DEVICE = 1 };
 enum { MRBF_FIT_FULL = 0, MRBF_FIT_FROM_ROUND4 = 1 };
 enum { MRBF_ENTRY_ROUND4 = 1, MRBF_ENTRY_FIT_FROM_ROUND4 = 2, MRBF_ENTRY_PS_STEP = 3, MRBF_ENTRY_BACKTRACK = 4, MRBF_ENTRY_AFFINE = 5,
-       MRBF_ENTRY_SD = 6 };
+       MRBF_ENTRY_SD = 6, MRBF_ENTRY_NORMAL = 7 };
 int32_t mrbf_dispatch_ps(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_sd(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
+int32_t mrbf_dispatch_normal(int32_t d, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_backtrack(int32_t n_objective_models, int32_t n_foreign, int32_t outputs_in_order);
 int32_t mrbf_dispatch_affine(int64_t n_candidates, int32_t d);
 int32_t mrbf_dispatch_round4(int64_t n0, int32_t d, int32_t poly_deg, int64_t n_candidates);

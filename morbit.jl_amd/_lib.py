@@ -58,8 +58,9 @@ PS_OK, PS_CRITICAL, PS_FAILURE = 0, 1, 2
 ROLE_NONE, ROLE_EQ, ROLE_INEQ = -1, -2, -3
 DISPATCH_REFERENCE, DISPATCH_DEVICE = 0, 1
 FIT_FULL, FIT_FROM_ROUND4 = 0, 1
-ENTRY_ROUND4, ENTRY_FIT_FROM_ROUND4, ENTRY_PS_STEP, ENTRY_BACKTRACK, ENTRY_AFFINE, ENTRY_SD = 1, 2, 3, 4, 5, 6
+ENTRY_ROUND4, ENTRY_FIT_FROM_ROUND4, ENTRY_PS_STEP, ENTRY_BACKTRACK, ENTRY_AFFINE, ENTRY_SD, ENTRY_NORMAL = 1, 2, 3, 4, 5, 6, 7
 SD_OK, SD_NO_OBJECTIVE, SD_INFEASIBLE, SD_GAVE_UP = 0, 1, 2, 3
+NS_OK, NS_INFEASIBLE, NS_GAVE_UP = 0, 1, 2
 
 
 class PsProblem(ctypes.Structure):
@@ -72,6 +73,14 @@ class PsProblem(ctypes.Structure):
 class SdInfo(ctypes.Structure):
     _fields_ = [("status", ctypes.c_int32), ("iterations", ctypes.c_int32), ("bound_flips", ctypes.c_int32), ("ms_total", ctypes.c_float),
                 ("omega", ctypes.c_double)]
+
+    def asdict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class NormalInfo(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("iterations", ctypes.c_int32), ("bound_flips", ctypes.c_int32), ("ms_total", ctypes.c_float),
+                ("alpha", ctypes.c_double), ("delta", ctypes.c_double)]
 
     def asdict(self):
         return {f: getattr(self, f) for f, _ in self._fields_}
@@ -145,8 +154,12 @@ SIGNATURES = {
                           + [ctypes.c_int32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mrbf_sd_criticality": (ctypes.c_int32, [c_vp, ctypes.POINTER(PsProblem), c_vp, c_vp, c_vp, c_vp, ctypes.c_int32, c_vp, c_vp,
                                              ctypes.POINTER(SdInfo)]),
+    "mrbf_normal_direction": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32] + [c_vp] * 12),
+    "mrbf_normal_step": (ctypes.c_int32, [c_vp, ctypes.POINTER(PsProblem), ctypes.c_int32, c_vp, c_vp, c_vp, ctypes.c_double, ctypes.c_double,
+                                          ctypes.c_double, ctypes.c_int32, c_vp, c_vp, ctypes.POINTER(NormalInfo)]),
     "mrbf_dispatch_ps": (ctypes.c_int32, [ctypes.c_int32] * 6),
     "mrbf_dispatch_sd": (ctypes.c_int32, [ctypes.c_int32] * 6),
+    "mrbf_dispatch_normal": (ctypes.c_int32, [ctypes.c_int32] * 5),
     "mrbf_dispatch_backtrack": (ctypes.c_int32, [ctypes.c_int32] * 3),
     "mrbf_dispatch_affine": (ctypes.c_int32, [ctypes.c_int64, ctypes.c_int32]),
     "mrbf_dispatch_round4": (ctypes.c_int32, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64]),

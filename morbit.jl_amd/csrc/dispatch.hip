@@ -30,6 +30,13 @@ int32_t mrbf_dispatch_sd(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_co
     return (int64_t)k + n_nl_constraints + n_lin_constraints <= 64 ? MRBF_DISPATCH_DEVICE : MRBF_DISPATCH_REFERENCE;
 }
 
+// the normal-step LP (normal_lp.hip): at most 64 rows (M^-1 lives in LDS), d within the library's limit; linear rows need no model
+int32_t mrbf_dispatch_normal(int32_t d, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign) {
+    if (n_foreign != 0 || n_models < 0 || d < 1 || d > 4096 || n_nl_constraints < 0 || n_lin_constraints < 0) return MRBF_DISPATCH_REFERENCE;
+    const int64_t rows = (int64_t)n_nl_constraints + n_lin_constraints;
+    return rows >= 1 && rows <= 64 ? MRBF_DISPATCH_DEVICE : MRBF_DISPATCH_REFERENCE;
+}
+
 int32_t mrbf_dispatch_backtrack(int32_t n_objective_models, int32_t n_foreign, int32_t outputs_in_order) {
     return (n_objective_models == 1 && n_foreign == 0 && outputs_in_order != 0) ? MRBF_DISPATCH_DEVICE : MRBF_DISPATCH_REFERENCE;
 }
@@ -69,6 +76,7 @@ int32_t mrbf_dispatch_after(int32_t entry, int32_t rc) {
         case MRBF_ENTRY_FIT_FROM_ROUND4: return rc == -2 || rc == MRBF_ESINGULAR || rc == MRBF_ENOTPD;
         case MRBF_ENTRY_PS_STEP: return rc == -2;
         case MRBF_ENTRY_SD: return rc == -2;  // shape outside the device path, or the LP gave up (MRBF_SD_GAVE_UP)
+        case MRBF_ENTRY_NORMAL: return rc == -2;  // likewise (MRBF_NS_GAVE_UP)
         default: return 0;
     }
 }

@@ -222,6 +222,165 @@ def get_criticality_sd(cfg, sc, scal, x, x_n, lb, ub, lin=None, stats=None):
     return omega, d
 
 
+# ---- the normal step (descent.jl:691-757): host reference, the dual bound of its certificate, the device call, the routing
+def _ns_rows(n, A_eq, b_eq, A_ineq, b_ineq):
+    """(C, b, m_eq) of the normal-step LP's rows in the step n: equalities first"""
+    A = [np.zeros((0, n))]
+    b = [np.zeros(0)]
+    for M, v in ((A_eq, b_eq), (A_ineq, b_ineq)):
+        if v is not None and np.asarray(v).size:
+            A.append(np.asarray(M, dtype=np.float64).reshape(-1, n))
+            b.append(np.asarray(v, dtype=np.float64).ravel())
+        else:
+            A.append(np.zeros((0, n)))
+            b.append(np.zeros(0))
+    return np.vstack(A), np.concatenate(b), A[1].shape[0]
+
+
+def _normal_step_lp(x, lb, ub, A_eq=None, b_eq=None, A_ineq=None, b_ineq=None, tol=1e-10):
+    """The LP of compute_normal_step (descent.jl:691-757) with HiGHS (scipy.optimize.linprog) in place of JuMP + OSQP, on the
+    explicit LP with the 2d rows -alpha <= n_j <= alpha: min alpha over (n, alpha >= 0), lb - x <= n <= ub - x, A_eq n = b_eq,
+    A_ineq n <= b_ineq (rows in the step n).  Returns (n, alpha, status, y): n projected into the box (_project_into_box),
+    alpha = ||n||_inf, status MRBF_NS_*, y the row multipliers (equalities first, >= 0 on inequality rows); infeasible:
+    (NaN, +Inf, NS_INFEASIBLE, None)."""
+    from scipy.optimize import linprog
+
+    x = np.asarray(x, dtype=np.float64)
+    d = x.size
+    lb, ub = np.broadcast_to(np.asarray(lb, dtype=np.float64), (d,)), np.broadcast_to(np.asarray(ub, dtype=np.float64), (d,))
+    C, b, meq = _ns_rows(d, A_eq, b_eq, A_ineq, b_ineq)
+    lo, hi = lb - x, ub - x
+    bad = (np.full(d, np.nan), np.inf, _lib.NS_INFEASIBLE, None)
+    if not np.all(lo <= hi):
+        return bad
+    eye, one = np.eye(d), np.ones((d, 1))
+    A_ub = [np.hstack([eye, -one]), np.hstack([-eye, -one]), np.hstack([C[meq:], np.zeros((C.shape[0] - meq, 1))])]
+    b_ub = [np.zeros(d), np.zeros(d), b[meq:]]
+    Ae = np.hstack([C[:meq], np.zeros((meq, 1))]) if meq else None
+    c = np.zeros(d + 1)
+    c[d] = 1.0
+    bnd = [(None if l == -np.inf else l, None if u == np.inf else u) for l, u in zip(lo, hi)] + [(0.0, None)]
+    res = linprog(c, A_ub=np.vstack(A_ub), b_ub=np.concatenate(b_ub), A_eq=Ae, b_eq=b[:meq] if meq else None, bounds=bnd,
+                  method="highs", options={"primal_feasibility_tolerance": tol, "dual_feasibility_tolerance": tol})
+    if res.status != 0:
+        return bad
+    n = np.clip(x + res.x[:d], lb, ub) - x
+    y = np.concatenate([-res.eqlin.marginals if meq else np.zeros(0), -res.ineqlin.marginals[2 * d:]])
+    return n, float(np.max(np.abs(n))), _lib.NS_OK, y
+
+
+def normal_lp_dual_bound(y, x, lb, ub, A_eq=None, b_eq=None, A_ineq=None, b_ineq=None):
+    """phi(y) = -y.b + min over alpha >= alpha0 of [alpha + sum_j min over n_j in [max(l'_j, -alpha), min(u'_j, alpha)] of
+    (C'y)_j n_j] (l' = lb - x, u' = ub - x, alpha0 = max(0, max l', max -u')): a lower bound on the normal-step LP's alpha* for
+    every y with y >= 0 on the inequality rows (equal to alpha* at the optimal multipliers).  The inner function is convex and
+    piecewise linear in alpha: evaluated at alpha0 and at every finite breakpoint above it; -inf where its slope at +inf is
+    negative."""
+    x = np.asarray(x, dtype=np.float64)
+    d = x.size
+    C, b, _ = _ns_rows(d, A_eq, b_eq, A_ineq, b_ineq)
+    y = np.asarray(y, dtype=np.float64).ravel()
+    lo = np.broadcast_to(np.asarray(lb, dtype=np.float64), (d,)) - x
+    hi = np.broadcast_to(np.asarray(ub, dtype=np.float64), (d,)) - x
+    r = C.T @ y
+    a0 = max(0.0, float(np.max(lo)), float(np.max(-hi)))
+    pos, neg = r > 0, r < 0
+    if 1.0 - r[pos & (lo == -np.inf)].sum() + r[neg & (hi == np.inf)].sum() < 0:
+        return -np.inf
+
+    def f(al):
+        L, U = np.maximum(lo, -al), np.minimum(hi, al)
+        return al + float(np.sum(r[pos] * L[pos]) + np.sum(r[neg] * U[neg]))
+
+    bps = np.concatenate([-lo, hi])
+    bps = bps[np.isfinite(bps) & (bps > a0)]
+    return float(-y @ b + min([f(a0)] + [f(v) for v in bps]))
+
+
+def _ns_problem(plan, lin):
+    """the mrbf_ps_problem of a container plan for mrbf_normal_step (the objective rows are ignored there)"""
+    return _sd_problem(plan, lin)
+
+
+def normal_step_device(plan, x, lb, ub, delta, lin=None, kappa_delta=1.0, delta_max=np.inf, variable_radius=False, want_duals=False):
+    """one mrbf_normal_step call; returns (rc, n, delta, info dict[, duals])"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    lb, ub = np.ascontiguousarray(lb, dtype=np.float64), np.ascontiguousarray(ub, dtype=np.float64)
+    prob, keep = _ns_problem(plan, lin or (None,) * 4)
+    m = plan["n_con"] + sum(0 if b is None else b.size for b in (keep[3], keep[5]))
+    ctx = plan["models"][0].ctx if plan["models"] else _lib.default_context()
+    n = np.empty(x.size)
+    y = np.empty(max(m, 1)) if want_duals else None
+    info = _lib.NormalInfo()
+    rc = ctx.lib.mrbf_normal_step(ctx.h, ctypes.byref(prob), x.size, _lib.as_ptr(x), _lib.as_ptr(lb), _lib.as_ptr(ub), float(delta),
+                                  float(kappa_delta), float(delta_max), int(bool(variable_radius)), _lib.as_ptr(n), _lib.as_ptr(y),
+                                  ctypes.byref(info))
+    out = (rc, n, float(info.delta), info.asdict())
+    return out + (y[:m],) if want_duals else out
+
+
+def _ns_host_rows(sc, scal, x, lin):
+    """A_eq, b_eq, A_ineq, b_ineq of compute_normal_step (descent.jl:700-735) in the step n, on container values / Jacobians at x"""
+    x = np.asarray(x, dtype=np.float64)
+    n = x.size
+    lin = lin or (None,) * 4
+    A_eq, b_eq, A_in, b_in = [np.zeros((0, n))], [np.zeros(0)], [np.zeros((0, n))], [np.zeros(0)]
+    if lin[1] is not None and np.asarray(lin[1]).size:
+        A = np.asarray(lin[0], dtype=np.float64).reshape(-1, n)
+        A_eq.append(A)
+        b_eq.append(np.asarray(lin[1], dtype=np.float64) - A @ x)
+    if sc.lists["nl_eq_constraint"]:
+        A_eq.append(sg.eval_container_nl_eq_constraints_jacobian_at_scaled_site(sc, scal, x))
+        b_eq.append(-sg.eval_container_nl_eq_constraints_at_scaled_site(sc, scal, x))
+    if lin[3] is not None and np.asarray(lin[3]).size:
+        A = np.asarray(lin[2], dtype=np.float64).reshape(-1, n)
+        A_in.append(A)
+        b_in.append(np.asarray(lin[3], dtype=np.float64) - A @ x)
+    if sc.lists["nl_ineq_constraint"]:
+        A_in.append(sg.eval_container_nl_ineq_constraints_jacobian_at_scaled_site(sc, scal, x))
+        b_in.append(-sg.eval_container_nl_ineq_constraints_at_scaled_site(sc, scal, x))
+    return np.vstack(A_eq), np.concatenate(b_eq), np.vstack(A_in), np.concatenate(b_in)
+
+
+def _ns_radius(n, alpha, status, delta, kappa_delta, delta_max, variable_radius):
+    """compute_normal_step's return value from the LP's result: (n, delta) or (NaN, -Inf) when infeasible"""
+    if status == _lib.NS_OK:
+        if not variable_radius:
+            return n, float(delta)
+        r = alpha / kappa_delta
+        if r <= delta_max:
+            return n, float(r)
+    return np.full(np.asarray(n).size, np.nan), -np.inf
+
+
+def compute_normal_step(sc, scal, x, delta, lb, ub, lin=None, kappa_delta=1.0, delta_max=np.inf, variable_radius=False, stats=None):
+    """`compute_normal_step(mop, scal, x_it, data_base, sc, algo_config; variable_radius)` (descent.jl:691-757) as HipRbf.jl's
+    `hip_compute_normal_step` routes it: mrbf_dispatch_normal decides, mrbf_normal_step solves on the device, and where the decision
+    table or mrbf_dispatch_after say so the reference method runs -- the HiGHS LP on container values and Jacobians at x.  lb / ub:
+    the global bounds in scaled variables (full_bounds_internal); lin = (A_eq, b_eq, A_ineq, b_ineq) in scaled variables.
+    kappa_delta = filter_kappa_delta, delta_max the largest radius (variable radius only).  Returns (n, delta): n projected into
+    the box, delta the given radius or alpha* / kappa_delta; (NaN, -Inf) when infeasible."""
+    lib = _lib.load()
+    plan = sg.container_plan(sc)
+    n_foreign_con = plan["n_foreign"] - sg.container_plan(sc, objectives_only=True)["n_foreign"]
+    d = int(np.asarray(x).size)
+    lin = lin or (None,) * 4
+    n_lin = sum(0 if b is None else int(np.asarray(b).size) for b in (lin[1], lin[3]))
+    if lib.mrbf_dispatch_normal(d, len(plan["models"]), plan["n_con"], n_lin, n_foreign_con) == _lib.DISPATCH_DEVICE:
+        rc, n, dl, info = normal_step_device(plan, x, lb, ub, delta, lin, kappa_delta, delta_max, variable_radius)
+        if stats is not None:
+            stats.update(info)
+            stats["path"] = "device"
+        if rc == 0:
+            return n, dl
+        if not lib.mrbf_dispatch_after(_lib.ENTRY_NORMAL, rc):
+            (plan["models"][0].ctx if plan["models"] else _lib.default_context()).check(rc)
+    if stats is not None:
+        stats["path"] = "reference"
+    A_eq, b_eq, A_in, b_in = _ns_host_rows(sc, scal, x, lin)
+    n, alpha, status, _ = _normal_step_lp(x, lb, ub, A_eq, b_eq, A_in, b_in)
+    return _ns_radius(n, alpha, status, delta, kappa_delta, delta_max, variable_radius)
+
+
 def _isapprox(a, b):
     """Julia's isapprox with its defaults (atol = 0, rtol = sqrt(eps)): norm(a - b) <= rtol max(norm(a), norm(b)), or a == b"""
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)

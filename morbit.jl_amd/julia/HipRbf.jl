@@ -47,6 +47,11 @@ struct MrbfSdInfo          # mirrors mrbf_sd_info, 24 bytes
     omega::Float64
 end
 
+struct MrbfNormalInfo      # mirrors mrbf_normal_info, 32 bytes
+    status::Int32; iterations::Int32; bound_flips::Int32; ms_total::Float32
+    alpha::Float64; delta::Float64
+end
+
 struct MrbfPsProblem        # mirrors mrbf_ps_problem, 72 bytes
     n_models::Int32; n_objectives::Int32
     models::Ptr{Ptr{Cvoid}}; roles::Ptr{Int32}
@@ -212,6 +217,8 @@ _dispatch_ps(d, k, n_models, n_nl, n_lin, n_foreign) =
     ccall((:mrbf_dispatch_ps, libmrbf), Int32, (Int32, Int32, Int32, Int32, Int32, Int32), d, k, n_models, n_nl, n_lin, n_foreign) == 1
 _dispatch_sd(d, k, n_models, n_nl, n_lin, n_foreign) =
     ccall((:mrbf_dispatch_sd, libmrbf), Int32, (Int32, Int32, Int32, Int32, Int32, Int32), d, k, n_models, n_nl, n_lin, n_foreign) == 1
+_dispatch_normal(d, n_models, n_nl, n_lin, n_foreign) =
+    ccall((:mrbf_dispatch_normal, libmrbf), Int32, (Int32, Int32, Int32, Int32, Int32), d, n_models, n_nl, n_lin, n_foreign) == 1
 _dispatch_backtrack(n_models, n_foreign, in_order::Bool) =
     ccall((:mrbf_dispatch_backtrack, libmrbf), Int32, (Int32, Int32, Int32), n_models, n_foreign, in_order) == 1
 _dispatch_affine(n_candidates, d) = ccall((:mrbf_dispatch_affine, libmrbf), Int32, (Int64, Int32), n_candidates, d) == 1
@@ -711,6 +718,54 @@ function get_criticality(desc_cfg::SteepestDescentConfig, mop, scal, x_it, x_it_
     _check(ctx, rc)
     Xet = eltype(get_x_scaled(x_it_n))
     return Xet(info[].omega), Xet.(dir)                        # NO_OBJECTIVE / INFEASIBLE: zeros and -Inf, as descent.jl:130-133
+end
+
+"""
+The normal step (descent.jl:691-757) on the device (`mrbf_normal_step`): values and Jacobians of the modelled constraints at x by the
+evaluation kernels, the right-hand sides b - A x (linear rows) and -m(x) (modelled rows), then the LP min α, -α <= n <= α,
+lb <= x + n <= ub, rows in n, solved exactly (active-set dual simplex) instead of by JuMP + OSQP.  Morbit's `compute_normal_step` is
+typed on Morbit's own types, so this is a function of its own with the same arguments and result (n, Δ): `find_normal_step`
+(algorithm.jl:421,423) calls it in place of `compute_normal_step` (INTEGRATION.md).  Whenever the decision table says so (a modelled
+constraint row on a `CompositeSurrogate` or another model family, no row or more than 64 rows, d > 4096) or the LP gave up,
+Morbit's own method runs on the same arguments.
+"""
+function hip_compute_normal_step(mop, scal, x_it, data_base, sc::SurrogateContainer, algo_config; variable_radius::Bool = false)
+    reference() = compute_normal_step(mop, scal, x_it, data_base, sc, algo_config; variable_radius = variable_radius)
+    _touches_device(sc) || return reference()      # no HipRbfModel in the container: Morbit's own method, libmrbf is not touched
+    plan = _container_plan(sc)
+    n_foreign_con = plan.n_foreign - _container_plan(sc; objectives_only = true).n_foreign   # foreign objectives do not matter here
+    x = Vector{Float64}(get_x_scaled(x_it))
+    d = length(x)
+    A_eq, b_eq = transformed_linear_eq_constraints(scal, mop)                  # AbstractMOPInterface.jl:463-481: A x_scaled (=, <=) b
+    A_in, b_in = transformed_linear_ineq_constraints(scal, mop)
+    _dispatch_normal(d, length(plan.models), plan.n_con, length(b_eq) + length(b_in), n_foreign_con) || return reference()
+    lb_g, ub_g = full_bounds_internal(scal)
+    lb = Vector{Float64}(lb_g); ub = Vector{Float64}(ub_g)
+    info = Ref{MrbfNormalInfo}()
+    n = Vector{Float64}(undef, d)
+    handles = Ptr{Cvoid}[m.handle for m in plan.models]
+    roles = plan.roles
+    Aeq = Matrix{Float64}(transpose(Matrix(A_eq))); beq = Vector{Float64}(b_eq)   # row-major rows x d == the d x rows column-major matrix
+    Ain = Matrix{Float64}(transpose(Matrix(A_in))); bin = Vector{Float64}(b_in)
+    Δ = Float64(get_delta(x_it)); κ_Δ = Float64(filter_kappa_delta(algo_config)); Δ_max = Float64(delta_max(algo_config))
+    # the table admits linear rows only: the container's HipRbfModels may all sit in foreign surrogates (plan.models empty)
+    ctx = isempty(plan.models) ? mrbf_context() : plan.models[1].ctx
+    rc = GC.@preserve handles roles Aeq beq Ain bin x lb ub n begin
+        prob = Ref(MrbfPsProblem(length(handles), plan.k, pointer(handles), pointer(roles), length(beq), length(bin),
+                                 isempty(beq) ? C_NULL : pointer(Aeq), isempty(beq) ? C_NULL : pointer(beq),
+                                 isempty(bin) ? C_NULL : pointer(Ain), isempty(bin) ? C_NULL : pointer(bin), -1.0))
+        _locked(ctx) do hctx
+            ccall((:mrbf_normal_step, libmrbf), Int32,
+                  (Ptr{Cvoid}, Ref{MrbfPsProblem}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Float64, Float64, Int32,
+                   Ptr{Float64}, Ptr{Float64}, Ref{MrbfNormalInfo}),
+                  hctx, prob, d, x, lb, ub, Δ, κ_Δ, Δ_max, variable_radius, n, C_NULL, info)
+        end
+    end
+    rc != 0 && _fallback_rc(7, rc) && return reference()       # the LP gave up: Morbit's JuMP model on the same arguments
+    _check(ctx, rc)
+    info[].delta == -Inf && return fill(MIN_PRECISION(NaN64), d), -MIN_PRECISION(Inf)      # infeasible (descent.jl:746-748)
+    Xet = eltype(get_x_scaled(x_it))
+    return Xet.(n), Xet(info[].delta)                          # n already projected into [lb, ub] (descent.jl:752-754)
 end
 
 # ---- site selection on the device -----------------------------------------------------------------------------------------------------
