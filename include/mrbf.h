@@ -431,6 +431,41 @@ int32_t mrbf_normal_step(mrbf_ctx *ctx, const mrbf_ps_problem *problem, int32_t 
                          double delta, double kappa_delta, double delta_max, int32_t variable_radius, double *n_out, double *dual_out,
                          mrbf_normal_info *info);
 
+/* ---- the steepest-descent step on the device (sd_step.hip) ------------------------------------------------------------------
+ * compute_descent_step(::SteepestDescentConfig, mop, scal, x_it, x_it_n, db, sc, ac, omega, d) (src/descent.jl:243-318) for a
+ * container given as an mrbf_ps_problem (models, roles, linear constraints in scaled variables; eq_tol is not used) in one call:
+ * the initial step size sigma of descent.jl:251-310 -- _local_bounds(x, delta, lb, ub), isapprox(x, x_n), intersect_box(x_n, d,
+ * lb_eff, ub_eff; :pos) and, for Delta > 1 and ||d||_inf ~ 1, _intersect_bounds (utilities.jl:126-287) on the stacked [x_n; x_n - x]
+ * with the linear rows and the modelled constraints linearised at x (values and Jacobians through the evaluation kernels) --
+ * then the Armijo loop of _backtrack (descent.jl:150-185, condition :137-143) over all max_loops + 1 step sizes at once: the
+ * objective models evaluate x_n and the max_loops + 1 trial points x_n + sigma shrink^i d (step sizes formed one after another,
+ * never as a power) in one sweep each, and the index the reference loop stops at is picked on the device; one read-back.
+ * lb / ub: the global bounds in scaled variables (full_bounds_internal); omega / d: what mrbf_sd_criticality returned.  Every
+ * array may be a host or a device pointer.  x_plus (d) and mx_plus (n_objectives, objective order) are x+ and m(x+); sigma <=
+ * min_stepsize (NaN included) gives omega = 0, x+ = x_n, m(x_n) and a step norm of 0 (descent.jl:312-317).  The backtracking stop
+ * uses min_stepsize when it is >= 0, else eps (descent.jl:152).  Modelled rows are taken in model order, then output order
+ * (which only matters for the anchor of the equality test).  Returns -2 (take the reference method) when mrbf_dispatch_sd_step
+ * refuses the shape.  Trial points and Armijo right-hand sides round as the host loop's (no FMA contraction); every reduction has
+ * a fixed order, so the result does not depend on timing. */
+typedef struct {
+    int32_t strict;       /* strict_backtracking: every objective must decrease (1) or the maximum (0) */
+    int32_t max_loops;    /* 0 .. 1024 */
+    double const_rhs;     /* armijo_const_rhs */
+    double shrink;        /* armijo_const_shrink, in (0, 1) */
+    double min_stepsize;  /* cfg.min_stepsize as given (< 0: eps for the backtracking stop) */
+} mrbf_sd_step_options;
+typedef struct {
+    int32_t branch;      /* how sigma was chosen: 0 "delta" (Delta <= 1), 1 "one", 2 "intersect" */
+    int32_t loops;       /* the reference loop's counter i at its stop (0 for the sigma <= min_stepsize branch) */
+    float ms_total;      /* hipEvent time of the whole call on the ctx stream */
+    double sigma;        /* the initial step size */
+    double omega;        /* omega as given, or 0 for the sigma <= min_stepsize branch */
+    double step_norm;    /* ||sigma shrink^loops d||_inf (0 for the sigma <= min_stepsize branch) */
+} mrbf_sd_step_info;
+int32_t mrbf_sd_step(mrbf_ctx *ctx, const mrbf_ps_problem *problem, const double *x, const double *x_n, double delta, const double *lb,
+                     const double *ub, double omega, const double *d, const mrbf_sd_step_options *opts, double *x_plus, double *mx_plus,
+                     mrbf_sd_step_info *info);
+
 /* ---- the decision table of the host bindings ---------------------------------------------------------------------------
  * Which implementation a binding (morbit.jl_amd/julia/HipRbf.jl, the Python mirror) takes for one call of Morbit's interface:
  * the device entry point (MRBF_DISPATCH_DEVICE) or Morbit's own method on the same arguments (MRBF_DISPATCH_REFERENCE; Julia:
@@ -454,16 +489,21 @@ int32_t mrbf_normal_step(mrbf_ctx *ctx, const mrbf_ps_problem *problem, int32_t 
  *                            surrogate, at least one device model, 1 <= d <= 4096, k >= 1 and k + n_nl + n_lin <= 64 LP rows.
  *   mrbf_dispatch_normal     compute_normal_step (src/descent.jl:691-757): device iff no modelled constraint row sits on a
  *                            foreign surrogate, 1 <= d <= 4096 and 1 <= n_nl + n_lin <= 64 LP rows (n_models may be 0).
+ *   mrbf_dispatch_sd_step    compute_descent_step(::SteepestDescentConfig, ...) (src/descent.jl:243-318, _backtrack :150-185,
+ *                            utilities.jl:126-294): device iff no objective or modelled-constraint row is foreign, at least one
+ *                            device model, 1 <= d <= 4096, 1 <= k <= 64, n_nl + n_lin <= 256 rows and 0 <= max_loops <= 1024.
  *   mrbf_dispatch_after      the return code rc of a device entry point (MRBF_ENTRY_*) that means "take the reference method
  *                            for this call" (start set without the tail or rank deficient, limits of the device path) rather
  *                            than an error: 1 = fall back, 0 = rc is what it says. */
 enum { MRBF_DISPATCH_REFERENCE = 0, MRBF_DISPATCH_DEVICE = 1 };
 enum { MRBF_FIT_FULL = 0, MRBF_FIT_FROM_ROUND4 = 1 };
 enum { MRBF_ENTRY_ROUND4 = 1, MRBF_ENTRY_FIT_FROM_ROUND4 = 2, MRBF_ENTRY_PS_STEP = 3, MRBF_ENTRY_BACKTRACK = 4, MRBF_ENTRY_AFFINE = 5,
-       MRBF_ENTRY_SD = 6, MRBF_ENTRY_NORMAL = 7 };
+       MRBF_ENTRY_SD = 6, MRBF_ENTRY_NORMAL = 7, MRBF_ENTRY_SD_STEP = 8 };
 int32_t mrbf_dispatch_ps(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_sd(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_normal(int32_t d, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
+int32_t mrbf_dispatch_sd_step(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign,
+                              int32_t max_loops);
 int32_t mrbf_dispatch_backtrack(int32_t n_objective_models, int32_t n_foreign, int32_t outputs_in_order);
 int32_t mrbf_dispatch_affine(int64_t n_candidates, int32_t d);
 int32_t mrbf_dispatch_round4(int64_t n0, int32_t d, int32_t poly_deg, int64_t n_candidates);

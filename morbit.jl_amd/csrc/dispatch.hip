@@ -37,6 +37,16 @@ int32_t mrbf_dispatch_normal(int32_t d, int32_t n_models, int32_t n_nl_constrain
     return rows >= 1 && rows <= 64 ? MRBF_DISPATCH_DEVICE : MRBF_DISPATCH_REFERENCE;
 }
 
+// the steepest-descent step (sd_step.hip): the Armijo scan reads up to 64 objectives and max_loops + 2 trial rows, the step size
+// kernel one workgroup's worth of stacked constraint rows
+int32_t mrbf_dispatch_sd_step(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign,
+                              int32_t max_loops) {
+    if (n_foreign != 0 || n_models < 1) return MRBF_DISPATCH_REFERENCE;
+    if (d < 1 || d > 4096 || k < 1 || k > 64 || n_nl_constraints < 0 || n_lin_constraints < 0) return MRBF_DISPATCH_REFERENCE;
+    if (max_loops < 0 || max_loops > 1024) return MRBF_DISPATCH_REFERENCE;
+    return (int64_t)n_nl_constraints + n_lin_constraints <= 256 ? MRBF_DISPATCH_DEVICE : MRBF_DISPATCH_REFERENCE;
+}
+
 int32_t mrbf_dispatch_backtrack(int32_t n_objective_models, int32_t n_foreign, int32_t outputs_in_order) {
     return (n_objective_models == 1 && n_foreign == 0 && outputs_in_order != 0) ? MRBF_DISPATCH_DEVICE : MRBF_DISPATCH_REFERENCE;
 }
@@ -77,6 +87,7 @@ int32_t mrbf_dispatch_after(int32_t entry, int32_t rc) {
         case MRBF_ENTRY_PS_STEP: return rc == -2;
         case MRBF_ENTRY_SD: return rc == -2;  // shape outside the device path, or the LP gave up (MRBF_SD_GAVE_UP)
         case MRBF_ENTRY_NORMAL: return rc == -2;  // likewise (MRBF_NS_GAVE_UP)
+        case MRBF_ENTRY_SD_STEP: return rc == -2;  // shape outside the device path
         default: return 0;
     }
 }

@@ -1346,6 +1346,11 @@ static int rank_ws_setup(mrbf_ctx *ctx, int maxlam, ps::RankWs &rw, unsigned lon
     rw.cnt = rw.idx[1] + (size_t)MAXLAM * MAXRUNS;
     rw.sync = rw.cnt + (size_t)2 * MAXLAM * MAXRUNS;
     *draws = reinterpret_cast<unsigned long long *>(wsb + per_run * MAXRUNS + 64);
+    // ps_rank_wave_kernel's readers accept any word whose bits 16..31 equal the block's tag.  The arena is not cleared when it is
+    // handed out, so a word left by earlier work (a double of another buffer, a record of an earlier call whose launch number
+    // agrees modulo 256) could pass as a record and carry an individual index beyond lam into the parents' list.  A zero word has
+    // tag 0, which no block uses: both exchange buffers start as zeros at every call.
+    MRBF_HIP(ctx, hipMemsetAsync(rw.f[0], 0, (size_t)2 * MAXLAM * MAXRUNS * sizeof(double), ctx->stream));
     MRBF_HIP(ctx, hipMemsetAsync(rw.sync + RS_SYNC * MAXRUNS, 0, sizeof(int), ctx->stream));
     return MRBF_OK;
 }

@@ -1,0 +1,518 @@
+// The steepest-descent step on the device: compute_descent_step(::SteepestDescentConfig) (Morbit.jl src/descent.jl:243-318)
+// for a whole SurrogateContainer, with the step size sigma of descent.jl:251-310 (_local_bounds, intersect_box, _intersect_bounds of
+// utilities.jl:126-294) and the Armijo loop of _backtrack (descent.jl:150-185) over every step size at once.
+//
+// One call is a short chain on the ctx stream and one read-back:
+//   eval_model at x (values + Jacobians) of every model that carries a modelled constraint row  -- the "intersect" branch's rows
+//   sd_stepsize_kernel  (1 x 256)        lb_eff / ub_eff, isapprox(x, x_n), Delta, the branch, sigma; steps[i] = steps[i-1] * shrink
+//   sd_trial_kernel     ((L + 2) x d)    row 0 = x_n, row 1 + i = x_n + steps[i] * d
+//   eval_model at the L + 2 rows (values) of every model that carries an objective row
+//   sd_armijo_kernel    (1 x 256)        the index the reference loop stops at, x+, m(x+) in objective order, ||step||_inf
+// The host mirror (morbit.jl_amd/descent.py: _sd_stepsize, _intersect_bounds, _backtrack) is the specification.  Every sum runs in an
+// order fixed by the shape (lane-strided partials, a fixed shuffle / LDS tree); every min / max is exact; no atomics.  The trial points
+// and Armijo right-hand sides are formed without FMA contraction, so they round exactly as the host loop's `x + s * d` and
+// `s * c * omega` do.  DESIGN.md section 10.
+#include "common.hpp"
+
+namespace mrbf {
+namespace sdstep {
+
+constexpr int THREADS = 256;
+constexpr int MAXK = 64, MAXROWS = 256;  // the limits of mrbf_dispatch_sd_step (d <= 4096, max_loops <= 1024) need no array here
+constexpr double SQRT_EPS = 1.4901161193847656e-08;  // sqrt(eps(Float64)) = 2^-26: Julia's isapprox rtol
+constexpr double EPS = 2.220446049250313e-16;        // eps(Float64): _intersect_bounds' zero_tol
+
+enum Branch { B_DELTA = 0, B_ONE = 1, B_INTERSECT = 2 };
+
+// one constraint row of the stacked problem of descent.jl:279-285: the row acts on the x_n half (linear rows) or on the n = x_n - x
+// half (modelled rows); a(t) = A[a_off + t * stride], right-hand side b_lin[b_off] (linear) or -Vc[b_off] (modelled)
+struct RowRef {
+    int64_t a_off, b_off;
+    int32_t stride, modelled;
+};
+struct ObjSrc {
+    int64_t off;     // value of objective l at site p: V[off + p * stride]
+    int64_t stride;  // the model's output count
+};
+
+struct StepArgs {
+    int d, n_eq, n_in, max_loops;
+    double delta, shrink;
+    const double *xn, *x, *lb, *ub, *dir;
+    const double *Alin, *blin, *Jc, *Vc;
+    const RowRef *rows;  // n_eq equality rows (linear, then modelled), then n_in inequality rows (likewise)
+    double *steps;       // max_loops + 1
+    double *out;         // [sigma, branch]
+};
+
+__device__ __forceinline__ double nan_max(double a, double b) { return (a != a || b != b) ? a + b : (a > b ? a : b); }
+__device__ __forceinline__ double nan_min(double a, double b) { return (a != a || b != b) ? a + b : (a < b ? a : b); }
+
+// fixed-tree reductions over the 256 threads of the block (red: 256 doubles of LDS); every thread gets the result
+template <class Op>
+__device__ double block_reduce(double v, double *red, Op op) {
+    __syncthreads();
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = THREADS / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] = op(red[threadIdx.x], red[threadIdx.x + s]);
+        __syncthreads();
+    }
+    const double r = red[0];
+    __syncthreads();
+    return r;
+}
+struct OpAdd {
+    __device__ double operator()(double a, double b) const { return a + b; }
+};
+struct OpMin {
+    __device__ double operator()(double a, double b) const { return nan_min(a, b); }
+};
+struct OpMax {
+    __device__ double operator()(double a, double b) const { return nan_max(a, b); }
+};
+// wave-level fixed xor tree: every lane gets the sum
+__device__ __forceinline__ double wave_sum(double v) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// candidates of _intersect_bound_vec (utilities.jl:126-152) for one coordinate: the step to bound b from x along dd ("lb" / "ub" sense);
+// returns +Inf when there is none (direction 0) so that it never becomes the minimum of the non-negative ones; `has` is set when the
+// coordinate contributes an entry
+__device__ __forceinline__ double bound_candidate(double xv, double bv, double dd, bool ub_sense, bool &has) {
+    has = false;
+    if (dd == 0.0) return INFINITY;
+    has = true;
+    const double tmp = bv - xv;
+    if (tmp == 0.0) return ub_sense ? (dd < 0.0 ? INFINITY : 0.0) : (dd > 0.0 ? INFINITY : 0.0);
+    return tmp / dd;
+}
+// smallest non-negative candidate so far (NaN is not >= 0: it never counts)
+__device__ __forceinline__ void take_pos(double s, double &best, double &any_pos) {
+    if (s >= 0.0) {
+        best = s < best ? s : best;
+        any_pos = 1.0;
+    }
+}
+
+__global__ __launch_bounds__(THREADS) void sd_stepsize_kernel(StepArgs a) {
+#pragma clang fp contract(off)
+    __shared__ double red[THREADS];
+    __shared__ double rax[MAXROWS], rad[MAXROWS];
+    __shared__ double s_sigma;
+    __shared__ int s_mode;  // 0: finite equality sigma to check, 1: take the inequality-only candidates, 2: sigma decided
+    const int tid = threadIdx.x, d = a.d;
+    // ---- lb_eff, ub_eff (utilities.jl:290-294), isapprox(x, x_n), ||d||_inf, Delta = intersect_box(x_n, d, lb_eff, ub_eff; :pos)
+    double neq = 0.0, nonfin = 0.0, sdiff = 0.0, sx = 0.0, sxn = 0.0, nd = 0.0, dnz = 0.0, best = INFINITY, anyp = 0.0;
+    for (int t = tid; t < d; t += THREADS) {
+        const double xv = a.x[t], xn = a.xn[t], dv = a.dir[t];
+        const double lbe = nan_max(a.lb[t], xv - a.delta), ube = nan_min(a.ub[t], xv + a.delta);
+        neq += (xv == xn) ? 0.0 : 1.0;
+        nonfin += (isfinite(xv) && isfinite(xn)) ? 0.0 : 1.0;
+        const double df = xv - xn;
+        sdiff += df * df, sx += xv * xv, sxn += xn * xn;
+        nd = nan_max(nd, fabs(dv));
+        dnz += dv != 0.0 ? 1.0 : 0.0;
+        bool h;
+        take_pos(bound_candidate(xn, lbe, dv, false, h), best, anyp);
+        take_pos(bound_candidate(xn, ube, dv, true, h), best, anyp);
+    }
+    neq = block_reduce(neq, red, OpAdd());
+    nonfin = block_reduce(nonfin, red, OpAdd());
+    sdiff = block_reduce(sdiff, red, OpAdd());
+    sx = block_reduce(sx, red, OpAdd());
+    sxn = block_reduce(sxn, red, OpAdd());
+    nd = block_reduce(nd, red, OpMax());
+    dnz = block_reduce(dnz, red, OpAdd());
+    best = block_reduce(best, red, OpMin());
+    anyp = block_reduce(anyp, red, OpMax());
+    bool close;
+    if (neq == 0.0) close = true;
+    else if (nonfin != 0.0) close = false;
+    else close = sqrt(sdiff) <= SQRT_EPS * fmax(sqrt(sx), sqrt(sxn));
+    const double Delta = close ? a.delta : (dnz == 0.0 ? INFINITY : (anyp != 0.0 ? best : 0.0));
+    double sigma = 0.0;
+    int branch;
+    if (Delta <= 1.0) {
+        branch = B_DELTA;
+        const double r = Delta / nd;
+        sigma = (r != r) ? r : (1.0 < r ? 1.0 : r);
+    } else {
+        // isapprox(norm_d, 1)
+        const bool one = nd == 1.0 || (isfinite(nd) && fabs(nd - 1.0) <= SQRT_EPS * fmax(fabs(nd), 1.0));
+        branch = one ? B_INTERSECT : B_ONE;
+        sigma = 1.0;
+    }
+    if (branch == B_INTERSECT) {
+        // ---- _intersect_bounds([x_n; n], [d; d], [lb_eff; lb_eff - x], [ub_eff; ub_eff - x], blockdiag rows; :pos), n = x_n - x
+        const int R = a.n_eq + a.n_in, lane = tid & 63, wave = tid >> 6;
+        for (int r = wave; r < R; r += THREADS / 64) {
+            const RowRef rr = a.rows[r];
+            const double *A = rr.modelled ? a.Jc + rr.a_off : a.Alin + rr.a_off;
+            double px = 0.0, pd = 0.0;
+            for (int t = lane; t < d; t += 64) {
+                const double av = A[(int64_t)t * rr.stride];
+                const double xv = rr.modelled ? a.xn[t] - a.x[t] : a.xn[t];
+                px += av * xv, pd += av * a.dir[t];
+            }
+            px = wave_sum(px), pd = wave_sum(pd);
+            if (lane == 0) rax[r] = px, rad[r] = pd;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int mode = 1;
+            double sg = 0.0;
+            if (dnz == 0.0) {
+                mode = 2, sg = INFINITY;
+            } else if (a.n_eq > 0) {
+                bool have = false, impossible = false;
+                for (int r = 0; r < a.n_eq && !impossible; ++r) {
+                    const RowRef rr = a.rows[r];
+                    const double b = rr.modelled ? -a.Vc[rr.b_off] : a.blin[rr.b_off];
+                    const double ad = rad[r];
+                    double si;
+                    if (ad != 0.0) {
+                        si = -(rax[r] - b) / ad;
+                    } else {
+                        if (fabs(rax[r] - b) > EPS) impossible = true;
+                        continue;
+                    }
+                    if (!have) {
+                        sg = si, have = true;
+                    } else if (!(si == sg || fabs(si - sg) <= SQRT_EPS * fmax(fabs(si), fabs(sg)))) {
+                        impossible = true;
+                    }
+                }
+                if (impossible) mode = 2, sg = 0.0;
+                else if (!have || isinf(sg)) mode = 1;  // no row fixes sigma: the inequality-only problem (utilities.jl:262-264)
+                else mode = 0;
+            }
+            s_mode = mode, s_sigma = sg;
+        }
+        __syncthreads();
+        const int mode = s_mode;
+        if (mode == 1) {
+            // smallest non-negative candidate of the box rows of both halves and of the inequality rows (0 when there is none)
+            double b2 = INFINITY, p2 = 0.0, h2 = 0.0;
+            for (int t = tid; t < d; t += THREADS) {
+                const double xv = a.x[t], xn = a.xn[t], dv = a.dir[t], nv = xn - xv;
+                const double lbe = nan_max(a.lb[t], xv - a.delta), ube = nan_min(a.ub[t], xv + a.delta);
+                bool h;
+                take_pos(bound_candidate(xn, lbe, dv, false, h), b2, p2), h2 += h;
+                take_pos(bound_candidate(nv, lbe - xv, dv, false, h), b2, p2), h2 += h;
+                take_pos(bound_candidate(xn, ube, dv, true, h), b2, p2), h2 += h;
+                take_pos(bound_candidate(nv, ube - xv, dv, true, h), b2, p2), h2 += h;
+            }
+            for (int r = a.n_eq + tid; r < R; r += THREADS) {
+                const RowRef rr = a.rows[r];
+                const double b = rr.modelled ? -a.Vc[rr.b_off] : a.blin[rr.b_off];
+                bool h;
+                take_pos(bound_candidate(rax[r], b, rad[r], true, h), b2, p2), h2 += h;
+            }
+            b2 = block_reduce(b2, red, OpMin());
+            p2 = block_reduce(p2, red, OpMax());
+            h2 = block_reduce(h2, red, OpAdd());
+            sigma = h2 == 0.0 ? INFINITY : (p2 != 0.0 ? b2 : 0.0);
+        } else if (mode == 0) {
+            // x + sigma d against the box and the inequality rows (utilities.jl:266-281), then the sign test of :pos
+            const double sg = s_sigma;
+            double bad = 0.0;
+            for (int t = tid; t < d; t += THREADS) {
+                const double xv = a.x[t], xn = a.xn[t], dv = a.dir[t], nv = xn - xv;
+                const double lbe = nan_max(a.lb[t], xv - a.delta), ube = nan_min(a.ub[t], xv + a.delta);
+                const double sd = sg * dv;
+                const double t1 = xn + sd, t2 = nv + sd;
+                bad += (t1 < lbe || t1 > ube || t2 < lbe - xv || t2 > ube - xv) ? 1.0 : 0.0;
+            }
+            for (int r = a.n_eq + wave; r < R; r += THREADS / 64) {
+                const RowRef rr = a.rows[r];
+                const double *A = rr.modelled ? a.Jc + rr.a_off : a.Alin + rr.a_off;
+                double p = 0.0;
+                for (int t = lane; t < d; t += 64) {
+                    const double xv = rr.modelled ? a.xn[t] - a.x[t] : a.xn[t];
+                    const double sd = sg * a.dir[t];
+                    p += A[(int64_t)t * rr.stride] * (xv + sd);
+                }
+                p = wave_sum(p);
+                const double b = rr.modelled ? -a.Vc[rr.b_off] : a.blin[rr.b_off];
+                if (lane == 0 && p - b > 0.0) bad += 1.0;
+            }
+            bad = block_reduce(bad, red, OpAdd());
+            sigma = (bad != 0.0 || sg < 0.0) ? 0.0 : sg;
+        } else {
+            sigma = s_sigma;
+        }
+    }
+    if (tid == 0) {
+        // step sizes exactly as the sequential loop forms them: step_size *= alpha (descent.jl:175)
+        double s = sigma;
+        a.steps[0] = s;
+        for (int i = 1; i <= a.max_loops; ++i) {
+            s = s * a.shrink;
+            a.steps[i] = s;
+        }
+        a.out[0] = sigma;
+        a.out[1] = (double)branch;
+    }
+}
+
+// row 0 = x_n, row 1 + i = x_n + steps[i] * d (descent.jl:162, :177), i = 0 .. max_loops
+__global__ __launch_bounds__(THREADS) void sd_trial_kernel(const double *__restrict__ xn, const double *__restrict__ dir,
+                                                           const double *__restrict__ steps, int d, int64_t total, double *__restrict__ X) {
+#pragma clang fp contract(off)
+    const int64_t e = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+    if (e >= total) return;
+    const int64_t row = e / d;
+    const int t = (int)(e - row * d);
+    if (row == 0) {
+        X[e] = xn[t];
+    } else {
+        const double sd = steps[row - 1] * dir[t];
+        X[e] = xn[t] + sd;
+    }
+}
+
+struct ArmijoArgs {
+    int d, k, max_loops, strict;
+    double omega, const_rhs, min_stepsize_raw, min_step;
+    const double *V;      // values of the objective models at the L + 2 rows (each model's block: rows x its outputs)
+    const double *X;      // the L + 2 trial rows
+    const double *dir, *steps, *stepout;
+    double *out;          // [x+ (d) | mx+ (k) | omega, step_norm, loops]
+    ObjSrc obj[MAXK];
+};
+
+__global__ __launch_bounds__(THREADS) void sd_armijo_kernel(ArmijoArgs a) {
+#pragma clang fp contract(off)
+    __shared__ double red[THREADS];
+    __shared__ double mx[MAXK];
+    const int tid = threadIdx.x, k = a.k;
+    if (tid < k) mx[tid] = a.V[a.obj[tid].off];
+    __syncthreads();
+    const double sigma = a.stepout[0];
+    const bool zero = !(sigma > a.min_stepsize_raw);  // descent.jl:312-317 (NaN included)
+    double first = (double)a.max_loops;
+    if (!zero) {
+        double mxmax = mx[0];
+        for (int l = 1; l < k; ++l) mxmax = nan_max(mxmax, mx[l]);
+        for (int i = tid; i < a.max_loops; i += THREADS) {
+            const double st = a.steps[i];
+            const double sc = st * a.const_rhs;
+            const double rhs = sc * a.omega;
+            bool ok;
+            if (a.strict) {
+                ok = true;
+                for (int l = 0; l < k; ++l) {
+                    const double mp = a.V[a.obj[l].off + (int64_t)(i + 1) * a.obj[l].stride];
+                    ok = ok && ((mx[l] - mp) >= rhs);
+                }
+            } else {
+                double mpmax = a.V[a.obj[0].off + (int64_t)(i + 1) * a.obj[0].stride];
+                for (int l = 1; l < k; ++l) mpmax = nan_max(mpmax, a.V[a.obj[l].off + (int64_t)(i + 1) * a.obj[l].stride]);
+                ok = (mxmax - mpmax) >= rhs;
+            }
+            if (ok || st <= a.min_step) {
+                first = (double)i;
+                break;  // the smallest index of this thread's stride
+            }
+        }
+    }
+    first = block_reduce(first, red, OpMin());
+    const int i = (int)first;
+    const int64_t row = zero ? 0 : (int64_t)i + 1;
+    const double st = zero ? 0.0 : a.steps[i];
+    double nrm = 0.0;
+    for (int t = tid; t < a.d; t += THREADS) {
+        a.out[t] = a.X[row * a.d + t];
+        nrm = nan_max(nrm, fabs(st * a.dir[t]));
+    }
+    nrm = block_reduce(nrm, red, OpMax());
+    if (tid < k) a.out[a.d + tid] = a.V[a.obj[tid].off + row * a.obj[tid].stride];
+    if (tid == 0) {
+        a.out[a.d + k] = zero ? 0.0 : a.omega;
+        a.out[a.d + k + 1] = zero ? 0.0 : nrm;
+        a.out[a.d + k + 2] = zero ? 0.0 : (double)i;
+    }
+}
+
+}  // namespace sdstep
+}  // namespace mrbf
+
+using namespace mrbf;
+
+namespace {
+// host copy of a caller array that may live on the host or the device
+int step_fetch(mrbf_ctx *ctx, const double *src, size_t cnt, double *dst) {
+    if (!cnt) return 0;
+    if (is_device_ptr(src)) MRBF_HIP(ctx, hipMemcpy(dst, src, cnt * sizeof(double), hipMemcpyDeviceToHost));
+    else std::memcpy(dst, src, cnt * sizeof(double));
+    return 0;
+}
+}  // namespace
+
+extern "C" int32_t mrbf_sd_step(mrbf_ctx *ctx, const mrbf_ps_problem *prob, const double *x, const double *x_n, double delta,
+                                const double *lb, const double *ub, double omega, const double *dir, const mrbf_sd_step_options *opts,
+                                double *x_plus, double *mx_plus, mrbf_sd_step_info *info) {
+    using namespace sdstep;
+    if (!ctx) return -1;
+    if (!prob) return fail(ctx, -2, "problem is NULL");
+    if (!x) return fail(ctx, -3, "x is NULL");
+    if (!x_n) return fail(ctx, -4, "x_n is NULL");
+    if (!lb) return fail(ctx, -5, "lb is NULL");
+    if (!ub) return fail(ctx, -6, "ub is NULL");
+    if (!dir) return fail(ctx, -7, "d is NULL");
+    if (!opts) return fail(ctx, -8, "opts is NULL");
+    if (!x_plus) return fail(ctx, -9, "x_plus is NULL");
+    if (!mx_plus) return fail(ctx, -10, "mx_plus is NULL");
+    if (!info) return fail(ctx, -11, "info is NULL");
+    std::memset(info, 0, sizeof(*info));
+    if (!(opts->shrink > 0.0 && opts->shrink < 1.0)) return fail(ctx, -8, "mrbf_sd_step: shrink must lie in (0, 1)");
+    if (prob->n_models < 1 || !prob->models || !prob->roles) return fail(ctx, -2, "mrbf_sd_step: grouped models with a roles table are required");
+    const int k = prob->n_objectives;
+    if (k < 1) return fail(ctx, -2, "mrbf_sd_step: %d objectives", k);
+    if (prob->n_lin_eq < 0 || prob->n_lin_ineq < 0) return fail(ctx, -2, "mrbf_sd_step: negative constraint count");
+    if ((prob->n_lin_eq && (!prob->A_eq || !prob->b_eq)) || (prob->n_lin_ineq && (!prob->A_ineq || !prob->b_ineq)))
+        return fail(ctx, -2, "mrbf_sd_step: linear constraint matrices are NULL");
+    // ---- objective sources and modelled constraint rows from the roles table
+    const int d = prob->models[0] ? prob->models[0]->d : 0;
+    std::vector<int> seen(std::max(k, 1), 0);
+    std::vector<int> obj_model(k), obj_col(k);
+    std::vector<RowRef> meq_rows, min_rows;
+    std::vector<int64_t> joff(prob->n_models), voff(prob->n_models);
+    std::vector<char> has_obj(prob->n_models, 0), has_con(prob->n_models, 0);
+    int64_t jtot = 0, vtot = 0;
+    for (int j = 0, e = 0; j < prob->n_models; ++j) {
+        const mrbf_model *M = prob->models[j];
+        if (!M) return fail(ctx, -2, "mrbf_sd_step: model %d is NULL", j);
+        if (M->d != d) return fail(ctx, -2, "mrbf_sd_step: model %d has %d variables, model 0 has %d", j, M->d, d);
+        for (int c = 0; c < M->k; ++c, ++e) {
+            const int role = prob->roles[e];
+            if (role >= 0) {
+                if (role >= k || seen[role]) return fail(ctx, -2, "mrbf_sd_step: roles[%d] = %d is not a (new) objective position", e, role);
+                seen[role] = 1;
+                obj_model[role] = j, obj_col[role] = c;
+                has_obj[j] = 1;
+            } else if (role == MRBF_ROLE_EQ || role == MRBF_ROLE_INEQ) {
+                has_con[j] = 1;
+            } else if (role != MRBF_ROLE_NONE) {
+                return fail(ctx, -2, "mrbf_sd_step: roles[%d] = %d is not a role", e, role);
+            }
+        }
+        if (has_con[j]) {
+            joff[j] = jtot, voff[j] = vtot;
+            jtot += (int64_t)M->k * d, vtot += M->k;
+        }
+    }
+    for (int l = 0; l < k; ++l)
+        if (!seen[l]) return fail(ctx, -2, "mrbf_sd_step: objective %d is not an output of any model", l);
+    for (int j = 0, e = 0; j < prob->n_models; ++j) {
+        const mrbf_model *M = prob->models[j];
+        for (int c = 0; c < M->k; ++c, ++e) {
+            const int role = prob->roles[e];
+            // site 0's Jacobian block is k x d column-major: entry (c, t) at t * k + c
+            if (role == MRBF_ROLE_EQ || role == MRBF_ROLE_INEQ)
+                (role == MRBF_ROLE_EQ ? meq_rows : min_rows).push_back(RowRef{joff[j] + c, voff[j] + c, M->k, 1});
+        }
+    }
+    const int n_nl = (int)(meq_rows.size() + min_rows.size()), n_lin = prob->n_lin_eq + prob->n_lin_ineq;
+    if (mrbf_dispatch_sd_step(d, k, prob->n_models, n_nl, n_lin, 0, opts->max_loops) != MRBF_DISPATCH_DEVICE)
+        return fail(ctx, -2, "mrbf_sd_step: d = %d / k = %d / %d rows / max_loops = %d outside the device path (ask mrbf_dispatch_sd_step first)",
+                    d, k, n_nl + n_lin, opts->max_loops);
+    const int L = opts->max_loops;
+    (void)hipSetDevice(ctx->device);
+    PinGuard pin(ctx);
+    // ---- host inputs, packed: x_n, x, lb, ub, d, linear rows (eq, then ineq), their b
+    const size_t nlin = (size_t)n_lin;
+    std::vector<double> h((size_t)5 * d + nlin * (d + 1));
+    double *hxn = h.data(), *hx = hxn + d, *hlb = hx + d, *hub = hlb + d, *hd = hub + d, *hA = hd + d, *hb = hA + nlin * d;
+    MRBF_TRY(step_fetch(ctx, x_n, d, hxn));
+    MRBF_TRY(step_fetch(ctx, x, d, hx));
+    MRBF_TRY(step_fetch(ctx, lb, d, hlb));
+    MRBF_TRY(step_fetch(ctx, ub, d, hub));
+    MRBF_TRY(step_fetch(ctx, dir, d, hd));
+    MRBF_TRY(step_fetch(ctx, prob->A_eq, (size_t)prob->n_lin_eq * d, hA));
+    MRBF_TRY(step_fetch(ctx, prob->A_ineq, (size_t)prob->n_lin_ineq * d, hA + (size_t)prob->n_lin_eq * d));
+    MRBF_TRY(step_fetch(ctx, prob->b_eq, prob->n_lin_eq, hb));
+    MRBF_TRY(step_fetch(ctx, prob->b_ineq, prob->n_lin_ineq, hb + prob->n_lin_eq));
+    // the stacked rows: linear equalities, modelled equalities, linear inequalities, modelled inequalities
+    std::vector<RowRef> rows;
+    for (int i = 0; i < prob->n_lin_eq; ++i) rows.push_back(RowRef{(int64_t)i * d, i, 1, 0});
+    rows.insert(rows.end(), meq_rows.begin(), meq_rows.end());
+    for (int i = 0; i < prob->n_lin_ineq; ++i) rows.push_back(RowRef{(int64_t)(prob->n_lin_eq + i) * d, prob->n_lin_eq + i, 1, 0});
+    rows.insert(rows.end(), min_rows.begin(), min_rows.end());
+    const int n_eq = prob->n_lin_eq + (int)meq_rows.size(), n_in = prob->n_lin_ineq + (int)min_rows.size();
+    // objective values: one block of (L + 2) x M->k per model that carries an objective row
+    std::vector<int64_t> ooff(prob->n_models, 0);
+    int64_t otot = 0;
+    for (int j = 0; j < prob->n_models; ++j)
+        if (has_obj[j]) ooff[j] = otot, otot += (int64_t)(L + 2) * prob->models[j]->k;
+    // ---- device arena: inputs | rows table | Jc | Vc | steps | trial rows | objective values | outputs
+    const size_t rows_dbl = (rows.size() * sizeof(RowRef) + sizeof(double) - 1) / sizeof(double);
+    const size_t out_cnt = (size_t)d + k + 3;
+    const size_t total = h.size() + rows_dbl + jtot + vtot + (L + 1) + 2 + (size_t)(L + 2) * d + otot + out_cnt;
+    double *base;
+    MRBF_TRY(get_buf(ctx, S_SD_STEP, total, &base));
+    double *dRows = base + h.size(), *dJc = dRows + rows_dbl, *dVc = dJc + jtot, *dSteps = dVc + vtot, *dSig = dSteps + (L + 1);
+    double *dX = dSig + 2, *dV = dX + (size_t)(L + 2) * d, *dOut = dV + otot;
+    hipEvent_t e0 = ctx->ev[0], e1 = ctx->ev[1];
+    MRBF_HIP(ctx, hipEventRecord(e0, ctx->stream));
+    MRBF_HIP(ctx, hipMemcpyAsync(base, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (!rows.empty())
+        MRBF_HIP(ctx, hipMemcpyAsync(dRows, rows.data(), rows.size() * sizeof(RowRef), hipMemcpyHostToDevice, ctx->stream));
+    const double *dxn = base, *dx = base + d, *dlb = base + 2 * d, *dub = base + 3 * d, *ddir = base + 4 * d;
+    const double *dA = base + 5 * d, *db = dA + nlin * d;
+    // ---- the modelled constraint rows at x (values + Jacobians; the "intersect" branch reads them)
+    for (int j = 0; j < prob->n_models; ++j)
+        if (has_con[j]) MRBF_TRY(eval_model(ctx, prob->models[j], 1, dx, dVc + voff[j], dJc + joff[j], nullptr));
+    // ---- sigma and the step sizes
+    StepArgs sa;
+    sa.d = d, sa.n_eq = n_eq, sa.n_in = n_in, sa.max_loops = L;
+    sa.delta = delta, sa.shrink = opts->shrink;
+    sa.xn = dxn, sa.x = dx, sa.lb = dlb, sa.ub = dub, sa.dir = ddir;
+    sa.Alin = dA, sa.blin = db, sa.Jc = dJc, sa.Vc = dVc;
+    sa.rows = reinterpret_cast<const RowRef *>(dRows);
+    sa.steps = dSteps, sa.out = dSig;
+    hipLaunchKernelGGL(sd_stepsize_kernel, dim3(1), dim3(THREADS), 0, ctx->stream, sa);
+    MRBF_HIP(ctx, hipGetLastError());
+    // ---- the L + 2 trial rows and the objective models' values there
+    const int64_t tot = (int64_t)(L + 2) * d;
+    hipLaunchKernelGGL(sd_trial_kernel, dim3((unsigned)((tot + THREADS - 1) / THREADS)), dim3(THREADS), 0, ctx->stream, dxn, ddir,
+                       (const double *)dSteps, d, tot, dX);
+    MRBF_HIP(ctx, hipGetLastError());
+    for (int j = 0; j < prob->n_models; ++j)
+        if (has_obj[j]) MRBF_TRY(eval_model(ctx, prob->models[j], L + 2, dX, dV + ooff[j], nullptr, nullptr));
+    // ---- the Armijo scan
+    ArmijoArgs aa;
+    aa.d = d, aa.k = k, aa.max_loops = L, aa.strict = opts->strict != 0;
+    aa.omega = omega, aa.const_rhs = opts->const_rhs;
+    aa.min_stepsize_raw = opts->min_stepsize;
+    aa.min_step = opts->min_stepsize >= 0.0 ? opts->min_stepsize : EPS;  // descent.jl:152
+    aa.V = dV, aa.X = dX, aa.dir = ddir, aa.steps = dSteps, aa.stepout = dSig, aa.out = dOut;
+    for (int l = 0; l < k; ++l) {
+        const int j = obj_model[l];
+        aa.obj[l] = ObjSrc{ooff[j] + obj_col[l], prob->models[j]->k};
+    }
+    hipLaunchKernelGGL(sd_armijo_kernel, dim3(1), dim3(THREADS), 0, ctx->stream, aa);
+    MRBF_HIP(ctx, hipGetLastError());
+    // ---- one read-back: sigma, branch, x+, mx+, omega, ||step||, loops
+    std::vector<double> hout(2 + out_cnt);
+    MRBF_HIP(ctx, hipMemcpyAsync(hout.data(), dSig, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    MRBF_HIP(ctx, hipMemcpyAsync(hout.data() + 2, dOut, out_cnt * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    const bool dev_x = is_device_ptr(x_plus), dev_m = is_device_ptr(mx_plus);
+    if (dev_x) MRBF_HIP(ctx, hipMemcpyAsync(x_plus, dOut, (size_t)d * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    if (dev_m) MRBF_HIP(ctx, hipMemcpyAsync(mx_plus, dOut + d, (size_t)k * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    MRBF_HIP(ctx, hipEventRecord(e1, ctx->stream));
+    MRBF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    pin.flush();
+    MRBF_HIP(ctx, hipEventElapsedTime(&info->ms_total, e0, e1));
+    const double *o = hout.data() + 2;
+    if (!dev_x) std::memcpy(x_plus, o, (size_t)d * sizeof(double));
+    if (!dev_m) std::memcpy(mx_plus, o + d, (size_t)k * sizeof(double));
+    info->sigma = hout[0];
+    info->branch = (int32_t)hout[1];
+    info->omega = o[d + k];
+    info->step_norm = o[d + k + 1];
+    info->loops = (int32_t)o[d + k + 2];
+    return MRBF_OK;
+}

@@ -536,3 +536,56 @@ def compute_descent_step_sd(cfg, sc, scal, x, x_n, delta, lb, ub, omega, d, lin=
         xp, mxp, step, _ = _backtrack(x_n, d, sigma, omega, sc, cfg, scal)
         return omega, xp, mxp, float(np.max(np.abs(step))) if step.size else 0.0
     return 0, x_n.copy(), sg.eval_container_objectives_at_scaled_site(sc, scal, x_n), 0
+
+
+# ---- the steepest-descent step on the device (descent.jl:243-318 with _backtrack :150-185): mrbf_sd_step and its routing -------------
+_SD_BRANCHES = ("delta", "one", "intersect")
+
+
+def sd_step_device(plan, cfg, x, x_n, delta, lb, ub, omega, d, lin=None, out=None):
+    """one mrbf_sd_step call; returns (rc, x_plus, mx_plus, info dict with the branch name under "branch_name").  x, x_n, lb, ub, d
+    may be NumPy arrays or device tensors; out = (x_plus, mx_plus) lets the caller pass its own output buffers (host or device)."""
+    ctx = plan["models"][0].ctx
+
+    def arr(a):
+        return a if hasattr(a, "data_ptr") else np.ascontiguousarray(a, dtype=np.float64)
+
+    x, x_n, lb, ub, d = arr(x), arr(x_n), arr(lb), arr(ub), arr(d)
+    prob, keep = _sd_problem(plan, lin or (None,) * 4)
+    n = int(x_n.numel() if hasattr(x_n, "numel") else x_n.size)
+    xp, mxp = out if out is not None else (np.empty(n), np.empty(plan["k"]))
+    opts = _lib.SdStepOptions(strict=int(bool(cfg.strict_backtracking)), max_loops=int(cfg.max_loops), const_rhs=float(cfg.armijo_const_rhs),
+                              shrink=float(cfg.armijo_const_shrink), min_stepsize=float(cfg.min_stepsize))
+    info = _lib.SdStepInfo()
+    rc = ctx.lib.mrbf_sd_step(ctx.h, ctypes.byref(prob), _lib.as_ptr(x), _lib.as_ptr(x_n), float(delta), _lib.as_ptr(lb), _lib.as_ptr(ub),
+                              float(omega), _lib.as_ptr(d), ctypes.byref(opts), _lib.as_ptr(xp), _lib.as_ptr(mxp), ctypes.byref(info))
+    dd = info.asdict()
+    dd["branch_name"] = _SD_BRANCHES[info.branch] if rc == 0 and 0 <= info.branch < 3 else None
+    return rc, xp, mxp, dd
+
+
+def compute_descent_step_sd_routed(cfg, sc, scal, x, x_n, delta, lb, ub, omega, d, lin=None, stats=None):
+    """`compute_descent_step(::SteepestDescentConfig, ...)` (descent.jl:243-318) as HipRbf.jl's `hip_compute_descent_step` routes it:
+    mrbf_dispatch_sd_step decides, mrbf_sd_step computes sigma, the trial points, their values and the Armijo stop in one call, and
+    where the decision table or mrbf_dispatch_after say so `compute_descent_step_sd` runs.  Same arguments and result:
+    (omega, x_plus, mx_plus, ||step||_inf)."""
+    lib = _lib.load()
+    plan = sg.container_plan(sc)
+    n = int(np.asarray(x_n).size)
+    lin = lin or (None,) * 4
+    n_lin = sum(0 if b is None else int(np.asarray(b).size) for b in (lin[1], lin[3]))
+    if lib.mrbf_dispatch_sd_step(n, plan["k"], len(plan["models"]), plan["n_con"], n_lin, plan["n_foreign"], int(cfg.max_loops)) \
+            == _lib.DISPATCH_DEVICE:
+        rc, xp, mxp, info = sd_step_device(plan, cfg, x, x_n, delta, lb, ub, omega, d, lin)
+        if stats is not None:
+            stats.update(info)
+            stats["path"] = "device"
+        if rc == 0:
+            if not info["sigma"] > cfg.min_stepsize:       # descent.jl:317: the reference returns integer zeros here
+                return 0, xp, mxp, 0
+            return omega, xp, mxp, info["step_norm"]
+        if not lib.mrbf_dispatch_after(_lib.ENTRY_SD_STEP, rc):
+            plan["models"][0].ctx.check(rc)
+    if stats is not None:
+        stats["path"] = "reference"
+    return compute_descent_step_sd(cfg, sc, scal, x, x_n, delta, lb, ub, omega, d, lin)

@@ -52,6 +52,16 @@ struct MrbfNormalInfo      # mirrors mrbf_normal_info, 32 bytes
     alpha::Float64; delta::Float64
 end
 
+struct MrbfSdStepOptions    # mirrors mrbf_sd_step_options, 32 bytes
+    strict::Int32; max_loops::Int32
+    const_rhs::Float64; shrink::Float64; min_stepsize::Float64
+end
+
+struct MrbfSdStepInfo       # mirrors mrbf_sd_step_info, 40 bytes
+    branch::Int32; loops::Int32; ms_total::Float32
+    sigma::Float64; omega::Float64; step_norm::Float64
+end
+
 struct MrbfPsProblem        # mirrors mrbf_ps_problem, 72 bytes
     n_models::Int32; n_objectives::Int32
     models::Ptr{Ptr{Cvoid}}; roles::Ptr{Int32}
@@ -219,6 +229,9 @@ _dispatch_sd(d, k, n_models, n_nl, n_lin, n_foreign) =
     ccall((:mrbf_dispatch_sd, libmrbf), Int32, (Int32, Int32, Int32, Int32, Int32, Int32), d, k, n_models, n_nl, n_lin, n_foreign) == 1
 _dispatch_normal(d, n_models, n_nl, n_lin, n_foreign) =
     ccall((:mrbf_dispatch_normal, libmrbf), Int32, (Int32, Int32, Int32, Int32, Int32), d, n_models, n_nl, n_lin, n_foreign) == 1
+_dispatch_sd_step(d, k, n_models, n_nl, n_lin, n_foreign, max_loops) =
+    ccall((:mrbf_dispatch_sd_step, libmrbf), Int32, (Int32, Int32, Int32, Int32, Int32, Int32, Int32),
+          d, k, n_models, n_nl, n_lin, n_foreign, max_loops) == 1
 _dispatch_backtrack(n_models, n_foreign, in_order::Bool) =
     ccall((:mrbf_dispatch_backtrack, libmrbf), Int32, (Int32, Int32, Int32), n_models, n_foreign, in_order) == 1
 _dispatch_affine(n_candidates, d) = ccall((:mrbf_dispatch_affine, libmrbf), Int32, (Int64, Int32), n_candidates, d) == 1
@@ -766,6 +779,58 @@ function hip_compute_normal_step(mop, scal, x_it, data_base, sc::SurrogateContai
     info[].delta == -Inf && return fill(MIN_PRECISION(NaN64), d), -MIN_PRECISION(Inf)      # infeasible (descent.jl:746-748)
     Xet = eltype(get_x_scaled(x_it))
     return Xet.(n), Xet(info[].delta)                          # n already projected into [lb, ub] (descent.jl:752-754)
+end
+
+"""
+The steepest-descent step (descent.jl:243-318) on the device (`mrbf_sd_step`): the initial step size σ of descent.jl:251-310 (trust
+region and global box, and for Δ > 1 with ‖d‖∞ ≈ 1 the linear rows and the modelled constraints linearised at x), then all
+`max_loops + 1` Armijo step sizes of `_backtrack` (descent.jl:150-185) evaluated in one sweep per objective model and the stop of the
+reference loop picked on the device -- one call for any container of `HipRbfModel`s (several models, objectives out of order,
+objectives grouped with modelled constraints).  Morbit's `compute_descent_step` is typed on Morbit's own types, so this is a function
+of its own with the same arguments and result (ω, x₊, mx₊, ‖step‖∞): `iterate!` (algorithm.jl:752) calls it in place of
+`compute_descent_step` (INTEGRATION.md).  Whenever the decision table says so (a `CompositeSurrogate` or another model family, more
+than 64 objectives or 256 constraint rows, d > 4096, max_loops > 1024) Morbit's own method runs on the same arguments.
+"""
+function hip_compute_descent_step(desc_cfg::SteepestDescentConfig, mop, scal, x_it, x_it_n, data_base, sc::SurrogateContainer,
+                                  algo_config, ω, d)
+    reference() = compute_descent_step(desc_cfg, mop, scal, x_it, x_it_n, data_base, sc, algo_config, ω, d)
+    _touches_device(sc) || return reference()      # no HipRbfModel in the container: Morbit's own method, libmrbf is not touched
+    plan = _container_plan(sc)
+    x = Vector{Float64}(get_x_scaled(x_it)); x_n = Vector{Float64}(get_x_scaled(x_it_n)); dir = Vector{Float64}(d)
+    n, k = length(x_n), plan.k
+    A_eq, b_eq = transformed_linear_eq_constraints(scal, mop)                  # AbstractMOPInterface.jl:463-481: A x_scaled (=, <=) b
+    A_in, b_in = transformed_linear_ineq_constraints(scal, mop)
+    _dispatch_sd_step(n, k, length(plan.models), plan.n_con, length(b_eq) + length(b_in), plan.n_foreign, desc_cfg.max_loops) ||
+        return reference()
+    lb_g, ub_g = full_bounds_internal(scal)                                    # descent.jl:253
+    lb = Vector{Float64}(lb_g); ub = Vector{Float64}(ub_g)
+    opts = Ref(MrbfSdStepOptions(desc_cfg.strict_backtracking, desc_cfg.max_loops, desc_cfg.armijo_const_rhs, desc_cfg.armijo_const_shrink,
+                                 desc_cfg.min_stepsize))
+    info = Ref{MrbfSdStepInfo}()
+    x₊, mx₊ = Vector{Float64}(undef, n), Vector{Float64}(undef, k)
+    handles = Ptr{Cvoid}[m.handle for m in plan.models]
+    roles = plan.roles
+    Aeq = Matrix{Float64}(transpose(Matrix(A_eq))); beq = Vector{Float64}(b_eq)   # row-major rows x d == the d x rows column-major matrix
+    Ain = Matrix{Float64}(transpose(Matrix(A_in))); bin = Vector{Float64}(b_in)
+    Δ = Float64(get_delta(x_it))
+    ctx = plan.models[1].ctx
+    rc = GC.@preserve handles roles Aeq beq Ain bin x x_n lb ub dir x₊ mx₊ begin
+        prob = Ref(MrbfPsProblem(length(handles), k, pointer(handles), pointer(roles), length(beq), length(bin),
+                                 isempty(beq) ? C_NULL : pointer(Aeq), isempty(beq) ? C_NULL : pointer(beq),
+                                 isempty(bin) ? C_NULL : pointer(Ain), isempty(bin) ? C_NULL : pointer(bin), -1.0))
+        _locked(ctx) do hctx
+            ccall((:mrbf_sd_step, libmrbf), Int32,
+                  (Ptr{Cvoid}, Ref{MrbfPsProblem}, Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64},
+                   Ref{MrbfSdStepOptions}, Ptr{Float64}, Ptr{Float64}, Ref{MrbfSdStepInfo}),
+                  hctx, prob, x, x_n, Δ, lb, ub, Float64(ω), dir, opts, x₊, mx₊, info)
+        end
+    end
+    rc != 0 && _fallback_rc(8, rc) && return reference()       # a shape outside the device path: Morbit's own method
+    _check(ctx, rc)
+    Xet = eltype(get_x_scaled(x_it_n))
+    info[].sigma > desc_cfg.min_stepsize ||
+        return 0, copy(get_x_scaled(x_it_n)), Xet.(mx₊), 0      # σ too small: no step, m(x_n) (descent.jl:317)
+    return ω, Xet.(x₊), Xet.(mx₊), Xet(info[].step_norm)
 end
 
 # ---- site selection on the device -----------------------------------------------------------------------------------------------------
