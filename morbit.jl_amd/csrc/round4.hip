@@ -12,13 +12,17 @@
 // one has  w' Phi w = v' K v  and  w' w = v' H v,  H = I + P G0^-1 P',  hence
 //     tau^2(xi | accepted) = s_K(xi) / s_H(xi),
 // the ratio of the running Cholesky pivots of K = kappa(candidates, candidates) and of H when xi joins the accepted set.  That
-// makes round 4 a left-looking Cholesky factorisation of K in candidate order that SKIPS the columns whose pivot ratio fails the
-// test: one GEMM chain builds K for all candidates at once; the candidates are then walked in blocks of 128 -- per block one
-// triangular solve with the accepted factor (all rows of the block at once, rocBLAS), one Schur-complement GEMM, and one workgroup
-// that takes the sequential decisions inside the block with the 128 x 128 complement in LDS (s_H from a q x q matrix updated by
-// Sherman-Morrison) -- so the O(n_acc^3) arithmetic runs on the whole device and only ~2 us per candidate are sequential (d = 64,
-// 10^4 candidates, 2080 accepted: 5.1 s for the one-workgroup walk of round 2, see profiles/).  The factor of the accepted block
-// is exactly what the fit needs:
+// makes round 4 a blocked Cholesky factorisation of K in candidate order that SKIPS the columns whose pivot ratio fails the test.
+// kappa is evaluated on demand, and the candidates are walked in blocks of 128: one workgroup takes the sequential decisions inside
+// a block from its Schur complement w.r.t. the accepted sites (s_H from a q x q matrix updated by Sherman-Morrison), everything
+// else runs on the whole device, and only ~2 us per candidate are sequential (d = 64, 10^4 candidates, 2080 accepted: 5.1 s for the
+// one-workgroup walk of round 2, see profiles/).  The walk has two forms:
+//   right-looking (wherever R = L_acc^-1 kappa(accepted, candidates) fits in memory): R is kept for every candidate ahead and
+//     extended by the rows of each block's accepted sites (the library's own split-k product and substitution kernels, the far
+//     columns on a second stream), and a block's complement is kappa(block, block) - R(:, block)' R(:, block);
+//   left-looking (the memory fallback): per block kappa(accepted | block, block), the block's columns of R by a triangular solve
+//     with the accepted factor and the complement by one GEMM (rocBLAS dtrsm + dgemm).
+// The factor of the accepted block is exactly what the fit needs:
 //     K_acc v = Y_acc - Lam_acc Y_0,   w_0 = -Lam_acc' v,   Pi0 lambda = Y_0 - Phi00 w_0 - Phi0a v        (start set unisolvent: N0 = q)
 // so the fit costs two triangular solves instead of an n^3 / 3 factorisation.  Checked against an independent from-scratch
 // restatement (oracle/sampling_oracle.py) in tests/test_sampling.py.
@@ -45,7 +49,7 @@ struct mrbf_round4_state {
     double *Phi00 = nullptr, *P0c = nullptr;       // n0 x n0; phi(X0, candidates) n0 x mc column-major
     double *Pi0 = nullptr;                         // n0 x q column-major
     double *LamT = nullptr;                        // n0 x mc column-major: column j = lam(xi_j)
-    double *K = nullptr, *LK = nullptr, *diagK = nullptr;  // mc x mc kappa matrix; factor of the ACCEPTED block (maxacc x maxacc lower, ld maxacc); unused
+    double *LK = nullptr;                          // factor of the ACCEPTED block (maxacc x maxacc lower, ld maxacc)
     double *Prow = nullptr, *Ginv = nullptr;       // mc x q row-major polynomial rows; q x q
     int *acc = nullptr;                            // accepted candidate positions, acceptance order; acc[maxacc] = count
 };
@@ -66,41 +70,15 @@ __global__ void identity_kernel(double *__restrict__ A, int q) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx < q * q) A[idx] = (idx % q == idx / q) ? 1.0 : 0.0;
 }
-// K = Phicc - E - E' + Q  (all mc x mc; Phicc symmetric), diag -> diagK
-__global__ void kappa_kernel(const double *__restrict__ Phicc, const double *__restrict__ E, const double *__restrict__ Q, int64_t mc,
-                             double *__restrict__ K, double *__restrict__ diagK, int have_tail) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= mc * mc) return;
-    const int64_t i = idx % mc, j = idx / mc;
-    double v = Phicc[idx];
-    if (have_tail) v = (v - E[i + j * mc]) - E[j + i * mc] + 0.5 * (Q[i + j * mc] + Q[j + i * mc]);
-    K[idx] = v;
-    if (i == j) diagK[i] = v;
-}
 
 // ---- blocked walk: per block of SB candidates --------------------------------------------------------------------------------
 // (SB = 128, the block of candidates decided inside one kernel: walk_kernel.hpp)
-// Kab[a + j * ld] = K[acc[a]][i0 + j]  (rows = accepted sites so far, columns = the block's candidates)
-__global__ void gather_kab_kernel(const double *__restrict__ K, int64_t mc, const int *__restrict__ acc, int nacc, int64_t i0, int b,
-                                  double *__restrict__ Kab, int ld) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (int64_t)nacc * b) return;
-    const int a = (int)(idx % nacc), j = (int)(idx / nacc);
-    Kab[a + (int64_t)j * ld] = K[(i0 + j) + (int64_t)acc[a] * mc];  // K symmetric: read along a column of K
-}
-// S[r + c * SB] = K[i0 + r][i0 + c]
-__global__ void block_copy_kernel(const double *__restrict__ K, int64_t mc, int64_t i0, int b, double *__restrict__ S) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= SB * SB) return;
-    const int r = idx % SB, c = idx / SB;
-    S[idx] = (r < b && c < b) ? K[(i0 + r) + (i0 + c) * mc] : 0.0;
-}
 // Round 5: kappa on demand.  Rounds 3 / 4 built K = kappa(candidates, candidates) for ALL mc candidates up front (a cross-Gram block, two
 // mc x mc x n0 products, a pass over four mc x mc matrices: 4.3 of the 21 ms of a call with 10^4 candidates at d = 64, and 3.2 GB of
 // buffers) although the walk only ever reads the columns of the current block at the rows (accepted so far | the block itself), and
 // stops after 17 of the 79 blocks once max_points is reached.  Here one launch per block evaluates exactly those entries:
 //   kappa(xi, eta) = phi(|xi - eta|) - lam(xi).p(eta) - lam(eta).p(xi) + (lam(xi).f(eta) + lam(eta).f(xi)) / 2
-// with lam = LamT[:, .] (n0), p = P0c[:, .] = phi(X0, .), f = F[:, .] = Phi00 lam(.) -- the symmetrised form kappa_kernel wrote.
+// with lam = LamT[:, .] (n0), p = P0c[:, .] = phi(X0, .), f = F[:, .] = Phi00 lam(.) (symmetrised in the tail terms).
 // rows rr < nacc: accepted site acc[rr] -> Kab[rr + j ld]; rows nacc + r: candidate i0 + r -> S[r + j SB].  64 x 64 tiles, 4 x 4 per thread
 // (the shape of cross_gram_kernel: difference-form distances, then the four n0-term sums).
 // Wide k chunks (64 coordinates, 32 tail terms per round, every load of a round in flight at once): with 16-wide rounds the kernel was a
@@ -291,11 +269,12 @@ __global__ __launch_bounds__(SEL_THREADS) void select_block_kernel(const double 
         acc[maxacc] = nacc;
     }
 }
-// The same decisions for q <= 128 with the inverse Gram matrix of the tail IN REGISTERS.  The kernel above is a chain of global-memory
-// round trips per candidate -- pi from memory, 65 dependent column loads of Ginv for Ginv pi, the Sherman-Morrison update written
-// back through memory behind a __threadfence, six workgroup barriers: 13.7 us per candidate, 30 of the 43 ms of a round 4 with 10^4
-// candidates at d = 64 (profiles/r04_round4_kernel_stats.csv) -- although the arithmetic per candidate is 4 q^2 + SB^2 flops.  Here
-// thread (lane, wave) owns Ginv[t][u] for t = lane + 64 a, u = wave + 16 b (at most 2 x 8 entries), the product Ginv pi is formed as
+// The same decisions with the inverse Gram matrix of the tail IN REGISTERS (the walk instantiates <3, 12, 16>: 145 <= q <= 192).  The
+// kernel above is a chain of global-memory round trips per candidate -- pi from memory, 65 dependent column loads of Ginv for Ginv pi,
+// the Sherman-Morrison update written back through memory behind a __threadfence, six workgroup barriers: 13.7 us per candidate, 30 of
+// the 43 ms of a round 4 with 10^4 candidates at d = 64 (profiles/r04_round4_kernel_stats.csv) -- although the arithmetic per candidate
+// is 4 q^2 + SB^2 flops.  Here
+// thread (lane, wave) owns Ginv[t][u] for t = lane + 64 a, u = wave + 16 b (at most NA x NB_ entries), the product Ginv pi is formed as
 // 16 partial sums per row through LDS, every thread takes the accept / reject decision itself from the same sums (same order: same
 // result), the factor column is read off S's column j, pi of the next candidate is fetched one candidate ahead: three barriers and
 // no global round trip per candidate.  Same arithmetic per entry as above except for the order of the q-term sums.
@@ -444,45 +423,8 @@ __global__ void append_rows_kernel(const double *__restrict__ R, int ldr, int na
 // the rows of a block's accepted sites as soon as they are known, so that no block ever needs a triangular solve against the whole
 // accepted factor (rocBLAS dtrsm: a chain of ~25 small launches per block, 4 of the 16.5 ms at d = 64 / 10^4 candidates and all of the
 // 226 ms at d = 128 with 6000 accepted).  Per block:  Kn = kappa(new, ahead) - R(old, new)' R(old, ahead)  (one fat GEMM),
-// R(new, ahead) = L_bb^-1 Kn  (a 128-row triangular solve, one thread per candidate) -- the blocked right-looking Cholesky with skipped
+// R(new, ahead) = L_bb^-1 Kn  (a 128-row triangular solve) -- the blocked right-looking Cholesky with skipped
 // columns that the walk is.  Same quantities as the left-looking form, summed in a different order.
-// A(:, a) = R(0 .. rows-1, i0 + blkidx[a])   (the new sites' columns of R, compact, for the GEMM)
-__global__ void gather_newcols_kernel(const double *__restrict__ R, int ldr, int rows, int64_t i0, const int *__restrict__ blkidx, int nblk,
-                                      double *__restrict__ A, int lda) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (int64_t)rows * nblk) return;
-    const int r = (int)(idx % rows), a = (int)(idx / rows);
-    A[r + (int64_t)a * lda] = R[r + (i0 + blkidx[a]) * (int64_t)ldr];
-}
-// X = L_bb^-1 Kn for ncols candidates, L_bb(a, a') = Lblk[blkidx[a] + a' SB] (a' <= a); X(a, j) -> Rout[a + j ldr].  One thread per
-// candidate: the factor entry of a step is uniform (scalar loads), the partial solution lives in LDS, column-private.
-__global__ __launch_bounds__(64) void block_forward_kernel(const double *__restrict__ Kn, int ldk, const double *__restrict__ Lblk,
-                                                          const int *__restrict__ blkidx, int nblk, int64_t ncols, double *__restrict__ Rout,
-                                                          int ldr) {
-    extern __shared__ double fw_smem[];  // xs[SB][64] | bi[SB] (66 KB: dynamic, the host raises the limit)
-    double(*xs)[64] = reinterpret_cast<double(*)[64]>(fw_smem);
-    int *bi = reinterpret_cast<int *>(fw_smem + SB * 64);
-    const int tid = threadIdx.x;
-    const int64_t j = (int64_t)blockIdx.x * 64 + tid;
-    for (int a = tid; a < nblk; a += 64) bi[a] = blkidx[a];
-    __syncthreads();
-    if (j >= ncols) return;
-    for (int a = 0; a < nblk; ++a) {
-        double sacc = Kn[a + j * ldk];
-        const double *Lrow = Lblk + bi[a];  // L_bb(a, a') = Lrow[a' * SB]
-        int a2 = 0;
-        for (; a2 + 4 <= a; a2 += 4) {
-            sacc = fma(-Lrow[(a2 + 0) * SB], xs[a2 + 0][tid], sacc);
-            sacc = fma(-Lrow[(a2 + 1) * SB], xs[a2 + 1][tid], sacc);
-            sacc = fma(-Lrow[(a2 + 2) * SB], xs[a2 + 2][tid], sacc);
-            sacc = fma(-Lrow[(a2 + 3) * SB], xs[a2 + 3][tid], sacc);
-        }
-        for (; a2 < a; ++a2) sacc = fma(-Lrow[a2 * SB], xs[a2][tid], sacc);
-        const double x = sacc / Lrow[a * SB];
-        xs[a][tid] = x;
-        Rout[a + j * (int64_t)ldr] = x;
-    }
-}
 
 // The tail part of kappa as a product: kappa(xi, eta) = phi - TA(:, xi)' TB(:, eta) with the stacked vectors
 //   TA(:, s) = [lam_s; p_s; -lam_s / 2; -f_s / 2],  TB(:, s) = [p_s; lam_s; f_s; lam_s]   (4 n0 entries per site)
@@ -507,7 +449,7 @@ __global__ void tail_forms_kernel(const double *__restrict__ LamT, const double 
 
 // ---- the right-looking walk's own kernels (round 5, second half): rocBLAS ran the fat product at ~6 TFLOP/s (m = 128: one workgroup per 64
 // columns, no split over k) and the substitution took one thread per candidate (267 us per block).
-// P[s](a, j) = sum over the k slice s of  A(k, a) B(k, j):  A = Anew (K x nblk, the new sites' columns of R), B = R(old rows, candidates
+// P[s](a, j) = sum over the k slice s of  A(k, a) B(k, j):  A = the new sites' columns of R (K x nblk), B = R(old rows, candidates
 // ahead) (K x ncols); both operands are contiguous along k, so a lane fetches 32 contiguous bytes per 16-deep k group (k = 16 g + 4 (l >> 4)
 // + s for MFMA step s: the same permutation on both sides).  Workgroup = 128 rows a x 64 columns j (wave w: 32 rows), grid (ncols / 64,
 // ksplit); fragments double buffered in registers, no LDS.  lda, ldb multiples of 4 (32-byte aligned fragments).
@@ -836,16 +778,12 @@ extern "C" int32_t mrbf_round4(mrbf_ctx *ctx, int64_t n0, int32_t d, const doubl
     // one allocation for everything that outlives the call
     auto *st = new mrbf_round4_state();
     st->n0 = n0; st->mc = mc; st->d = d; st->q = q; st->deg = poly_deg; st->kid = kernel_id; st->a = a; st->b = b; st->maxacc = maxacc;
-    // kappa(candidates, candidates) on demand, block by block (kappa_block_kernel; MRBF_R4_LAZY=0: the full mc x mc matrix up front as in rounds 3 / 4)
-    const int lazy_env = mrbf_env("MRBF_R4_LAZY") ? atoi(mrbf_env("MRBF_R4_LAZY")) : 1;  // (read per call: the tests switch it)
-    const bool lazy = lazy_env != 0;
-    const size_t cnt[11] = {(size_t)n0 * d, (size_t)mc * d, (size_t)n0 * n0, (size_t)n0 * mc, (size_t)n0 * std::max(q, 1), (size_t)n0 * mc,
-                            lazy ? (size_t)1 : (size_t)mc * mc, (size_t)maxacc * maxacc, (size_t)mc, (size_t)mc * std::max(q, 1),
-                            (size_t)std::max(q, 1) * std::max(q, 1)};
-    size_t off[12];
+    const size_t cnt[9] = {(size_t)n0 * d, (size_t)mc * d, (size_t)n0 * n0, (size_t)n0 * mc, (size_t)n0 * std::max(q, 1), (size_t)n0 * mc,
+                           (size_t)maxacc * maxacc, (size_t)mc * std::max(q, 1), (size_t)std::max(q, 1) * std::max(q, 1)};
+    size_t off[10];
     off[0] = 0;
-    for (int i = 0; i < 11; ++i) off[i + 1] = off[i] + ((cnt[i] * sizeof(double) + 255) & ~size_t(255));
-    const size_t total = off[11] + ((size_t)(maxacc + 1) * sizeof(int) + 255);
+    for (int i = 0; i < 9; ++i) off[i + 1] = off[i] + ((cnt[i] * sizeof(double) + 255) & ~size_t(255));
+    const size_t total = off[9] + ((size_t)(maxacc + 1) * sizeof(int) + 255);
     if (hipMalloc(&st->block, total) != hipSuccess) {
         delete st;
         return fail(ctx, MRBF_ENOMEM, "round 4 state allocation of %zu bytes failed", total);
@@ -853,26 +791,19 @@ extern "C" int32_t mrbf_round4(mrbf_ctx *ctx, int64_t n0, int32_t d, const doubl
     char *base = (char *)st->block;
     st->C0 = (double *)(base + off[0]); st->Xc = (double *)(base + off[1]); st->Phi00 = (double *)(base + off[2]);
     st->P0c = (double *)(base + off[3]); st->Pi0 = (double *)(base + off[4]); st->LamT = (double *)(base + off[5]);
-    st->K = (double *)(base + off[6]); st->LK = (double *)(base + off[7]); st->diagK = (double *)(base + off[8]);
-    st->Prow = (double *)(base + off[9]); st->Ginv = (double *)(base + off[10]); st->acc = (int *)(base + off[11]);
+    st->LK = (double *)(base + off[6]); st->Prow = (double *)(base + off[7]); st->Ginv = (double *)(base + off[8]); st->acc = (int *)(base + off[9]);
     auto run = [&]() -> int {
         const KP kp = make_kp(kernel_id, a, b);
         const double one = 1.0, zero = 0.0;
         hipStream_t s = ctx->stream;
         MRBF_HIP(ctx, hipMemcpyAsync(st->C0, start_sites, (size_t)n0 * d * sizeof(double), hipMemcpyDefault, s));
         MRBF_HIP(ctx, hipMemcpyAsync(st->Xc, cand_sites, (size_t)mc * d * sizeof(double), hipMemcpyDefault, s));
-        // kernel blocks (difference-form arithmetic, like norm(x - c)): Phi00, phi(candidates, X0) (= P0c as n0 x mc column-major), Phicc
-        double *Phicc = nullptr, *E = nullptr, *Qm = nullptr, *F = nullptr, *T;
-        if (!lazy) MRBF_TRY(get_buf(ctx, S_PHI, (size_t)mc * mc, &Phicc));
+        // kernel blocks (difference-form arithmetic, like norm(x - c)): Phi00, phi(candidates, X0) (= P0c as n0 x mc column-major)
+        double *F = nullptr, *T;
         MRBF_TRY(launch_cross_gram(ctx, st->C0, n0, st->C0, n0, d, kp, st->Phi00));
         MRBF_TRY(launch_cross_gram(ctx, st->Xc, mc, st->C0, n0, d, kp, st->P0c));
-        if (!lazy) MRBF_TRY(launch_cross_gram(ctx, st->Xc, mc, st->Xc, mc, d, kp, Phicc));
         int *dinfo = nullptr;  // info word of the start set's factorisation (read with the first block's counts)
         if (q > 0) {
-            if (!lazy) {
-                MRBF_TRY(get_buf(ctx, S_STAGE_C, (size_t)mc * mc, &E));
-                MRBF_TRY(get_buf(ctx, S_STAGE_D, (size_t)mc * mc, &Qm));
-            }
             MRBF_TRY(get_buf(ctx, S_W1, (size_t)n0 * mc, &F));
             MRBF_TRY(get_buf(ctx, S_T1, (size_t)q * std::max<int64_t>(mc, q), &T));
             MRBF_TRY(get_buf(ctx, S_INFO, (size_t)4, &dinfo));
@@ -885,8 +816,7 @@ extern "C" int32_t mrbf_round4(mrbf_ctx *ctx, int64_t n0, int32_t d, const doubl
                                          st->Pi0, (int)n0, &zero, G0, q));
             // (the factorisation's info word is read with the first block's counts -- no host round trip of its own; a rank-deficient start
             // set fills the walk with NaNs, which accept nothing, and the call then returns MRBF_ESINGULAR)
-            static const int own_g0 = mrbf_env("MRBF_R4_OWNG0") ? atoi(mrbf_env("MRBF_R4_OWNG0")) : 1;
-            if (q <= SB && own_g0) {
+            if (q <= SB) {
                 // q <= 128: the library's own diagonal-block kernel on G0 padded with the identity -- factor and inverse of the factor in one
                 // launch -- and G0^-1 = inv(L)' inv(L)  (rocSOLVER: potf2 59 us + two substitution launches on the identity 94 us)
                 double *Gp, *Li;
@@ -906,90 +836,60 @@ extern "C" int32_t mrbf_round4(mrbf_ctx *ctx, int64_t n0, int32_t d, const doubl
                                          q));
             MRBF_BLAS(ctx, rocblas_dgemm(ctx->blas, rocblas_operation_none, rocblas_operation_none, (int)n0, (int)mc, q, &one, st->Pi0, (int)n0, T, q,
                                          &zero, st->LamT, (int)n0));
-            // E = Lam Phi0c = LamT' P0c ; F = Phi00 LamT ; Q = LamT' F   (on demand: only F, the n0 x mc panel, is formed here)
-            if (!lazy)
-                MRBF_BLAS(ctx, rocblas_dgemm(ctx->blas, rocblas_operation_transpose, rocblas_operation_none, (int)mc, (int)mc, (int)n0, &one, st->LamT,
-                                             (int)n0, st->P0c, (int)n0, &zero, E, (int)mc));
+            // F = Phi00 LamT (n0 x mc): with lam and p = phi(X0, .) all the tail of kappa needs (kappa_block_kernel, tail_forms_kernel)
             MRBF_BLAS(ctx, rocblas_dgemm(ctx->blas, rocblas_operation_none, rocblas_operation_none, (int)n0, (int)mc, (int)n0, &one, st->Phi00, (int)n0,
                                          st->LamT, (int)n0, &zero, F, (int)n0));
-            if (!lazy)
-                MRBF_BLAS(ctx, rocblas_dgemm(ctx->blas, rocblas_operation_transpose, rocblas_operation_none, (int)mc, (int)mc, (int)n0, &one, st->LamT,
-                                             (int)n0, F, (int)n0, &zero, Qm, (int)mc));
-        } else {
-            E = Qm = Phicc;
         }
-        if (!lazy) hipLaunchKernelGGL(kappa_kernel, dim3(nb(mc * mc)), dim3(256), 0, s, Phicc, E, Qm, mc, st->K, st->diagK, q > 0 ? 1 : 0);
         const double thr = (theta_pivot_cholesky * theta_pivot_cholesky) * (theta_pivot_cholesky * theta_pivot_cholesky);
-        const size_t shm = ((size_t)SB * SB + SB + 2 * (size_t)std::max(q, 1) + SEL_THREADS / 64) * sizeof(double);
-        MRBF_HIP(ctx, hipFuncSetAttribute((const void *)select_block_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-        // the register variant of the decision kernel: q <= 80 (2 x 5 entries of Ginv per thread) or q <= 128 (2 x 8); needs q >= 1
-        const int sel_env = mrbf_env("MRBF_R4_SELECT") ? atoi(mrbf_env("MRBF_R4_SELECT")) : 2;  // 0: S and Ginv through memory; 1: registers, three barriers; 2: the one-barrier walk
-        // the decision kernel asks for (nearly) the whole LDS of its compute unit: no workgroup of the side stream's kappa / substitution
-        // kernels then fits beside it (sharing the unit's VALUs cost the one sequential kernel of the walk 40 us per block)
+        // The decision kernel, by q.  q <= 80: the two halves of a step on different waves (select_block_duo_kernel: same bits; 119 against
+        // 140 us per block at q = 65).  q <= 144: the one-barrier walk with every wave doing both halves -- beyond q = 80 the G waves' share
+        // (2 q^2 / 256 entries per thread + q / 16 row sums) outweighs the S waves' -- and beyond q = 144 its <8, 6, 12> shape spills.
+        // q <= 192: the register kernel, three rows x twelve columns of Ginv per thread.  q = 0 and q > 192: S and Ginv through memory.
+        // The walk kernels ask for (nearly) the whole LDS of their compute unit: no workgroup of the side stream's kappa / substitution
+        // kernels then fits beside them (sharing the unit's VALUs cost the one sequential kernel of the walk 40 us per block).
         constexpr size_t R4_SEL_LDS = 152 * 1024;
-        const bool duo = mrbf_env("MRBF_R4_DUO") ? atoi(mrbf_env("MRBF_R4_DUO")) != 0 : true;
-        const bool walk_sel = sel_env >= 2 && q >= 1 && q <= 144;  // (beyond: the register kernel; the walk's <8, 6, 12> shape spills)
-        // (3: q <= 192 -- d = 128 has q = 129 -- three rows x twelve columns of Ginv per thread)
-        const int fast_sel = (sel_env && q >= 1 && q <= 80) ? 1 : ((sel_env && q >= 1 && q <= 128) ? 2 : ((sel_env && q >= 1 && q <= 192) ? 3 : 0));
+        auto walk_lds = [&](int nbw) { return std::max<size_t>((size_t)SB * 16 * nbw * sizeof(double), R4_SEL_LDS); };
+        const size_t shm = ((size_t)SB * SB + SB + 2 * (size_t)std::max(q, 1) + SEL_THREADS / 64) * sizeof(double);
         const size_t shm_reg = ((size_t)SB * SB + 2 * (size_t)std::max(q, 1) + 16 * (size_t)std::max(q, 1) + 16) * sizeof(double);
-        static const int selw = mrbf_env("MRBF_R4_SELW") ? atoi(mrbf_env("MRBF_R4_SELW")) : 16;  // waves of the decision kernel (8 or 16; 8 measured 6 % slower at d = 64)
-        if (fast_sel == 1) {
-            MRBF_HIP(ctx, hipFuncSetAttribute((const void *)select_block_reg_kernel<2, 5, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_reg));
-            MRBF_HIP(ctx, hipFuncSetAttribute((const void *)select_block_reg_kernel<2, 10, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_reg));
-        }
-        if (fast_sel == 2) {
-            MRBF_HIP(ctx, hipFuncSetAttribute((const void *)select_block_reg_kernel<2, 8, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_reg));
-            MRBF_HIP(ctx, hipFuncSetAttribute((const void *)select_block_reg_kernel<2, 16, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_reg));
-        }
-        if (fast_sel == 3)
-            MRBF_HIP(ctx, hipFuncSetAttribute((const void *)select_block_reg_kernel<3, 12, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_reg));
-        double *Rb, *Sb, *Rfull = nullptr, *Anew = nullptr, *Kn = nullptr;
-        int *cnt;
-        // right-looking walk (see gather_newcols_kernel): needs the on-demand kappa; MRBF_R4_EAGER=0 keeps the per-block dtrsm.
-        // Default wherever R for every candidate fits (see below): with its own product and substitution kernels and the far
-        // columns' update on a second stream it wins at every shape measured (d = 64, 2080 of 10^4 accepted, where the walk stops after 17
-        // of 79 blocks and most of R(:, ahead) is never used, as well as d = 128, 6000 of 6000).
-        const int eager_env = mrbf_env("MRBF_R4_EAGER") ? atoi(mrbf_env("MRBF_R4_EAGER")) : -1;
-        //  the right-looking form keeps R for every candidate plus (KSPLIT_MAX + 2) 128-row panels over all candidates in the
-        // context's pool for the life of the process: by default only while that is at most 2 GB of R and all of it fits into half of the
-        // card's free memory -- beyond, the left-looking form (maxacc x 128 per block) does the same walk
-        bool eager_fits = (int64_t)round_up(maxacc, 4) * mc <= ((int64_t)1 << 28);
-        if (eager_fits) {
+        // The right-looking walk (see block_forward_mfma_kernel) wherever R for every candidate fits: with its own product and substitution
+        // kernels and the far columns' update on a second stream it wins at every shape measured (d = 64, 2080 of 10^4 accepted, where the
+        // walk stops after 17 of 79 blocks and most of R(:, ahead) is never used, as well as d = 128, 6000 of 6000).
+        //  it keeps R for every candidate plus (KSPLIT_MAX + 2) 128-row panels over all candidates in the context's pool for the
+        // life of the process: only while that is at most 2 GB of R and all of it fits into half of the card's free memory -- beyond, the
+        // left-looking walk (maxacc x 128 per block) does the same walk.  MRBF_R4_EAGER=0 forces the left-looking walk (read per call: the
+        // tests switch it).
+        const char *eager_env = mrbf_env("MRBF_R4_EAGER");
+        bool eager = !(eager_env && atoi(eager_env) == 0) && (int64_t)round_up(maxacc, 4) * mc <= ((int64_t)1 << 28);
+        if (eager) {
             size_t free_b = 0, total_b = 0;
             const size_t need = ((size_t)round_up(maxacc, 4) * (mc + 2 * SB) + (size_t)(KSPLIT_MAX_R4 + 2) * SB * mc) * sizeof(double);
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b / 2) eager_fits = false;
+            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b / 2) eager = false;
         }
-        const bool eager = lazy && (eager_env >= 0 ? eager_env != 0 : eager_fits);
         const int ldr = eager ? (int)round_up(maxacc, 4) : maxacc;  // leading dimension of R (32-byte aligned columns for the right-looking kernels)
-        const int custom = eager && (mrbf_env("MRBF_R4_CUSTOM") ? atoi(mrbf_env("MRBF_R4_CUSTOM")) : 1);  // 0: rocBLAS dgemm + one thread per candidate
         constexpr int KSPLIT_MAX = KSPLIT_MAX_R4;
-        double *Ppart = nullptr;
-        if (eager) {
-            MRBF_TRY(get_buf(ctx, S_PHI, (size_t)ldr * (mc + SB), &Rfull));  // R(:, j) for every candidate j (+ one block: the products read whole 128-column tiles)
-            MRBF_TRY(get_buf(ctx, S_STAGE_C, (size_t)ldr * SB, &Anew));      // the new sites' columns of R, compact
-            MRBF_TRY(get_buf(ctx, S_STAGE_D, (size_t)SB * mc, &Kn));         // kappa(new, ahead), ld = SB
-            if (custom) MRBF_TRY(get_buf(ctx, S_STAGE_A, (size_t)(KSPLIT_MAX + 1) * SB * mc, &Ppart));  // the k slices of R(old, new)' R(old, ahead) (+ the tail's)
-        }
-        // the block's own Schur complement without rocBLAS (right-looking walk): kappa(block, block) of every block in one launch up front,
+        // the block's own Schur complement (right-looking walk): kappa(block, block) of every block in one launch up front,
         // R(:, block)' R(:, block) by the split-k product kernel (rocBLAS ran this 128 x 128 x nacc product on two workgroups: 165 us at
         // nacc = 5000), slices summed by schur_reduce_kernel
         constexpr int KSPLIT_NEAR = 32;
-        const bool own_schur = custom && (mrbf_env("MRBF_R4_SCHUR") ? atoi(mrbf_env("MRBF_R4_SCHUR")) != 0 : true);
         const int64_t nblocks = (mc + SB - 1) / SB;
-        double *KbbAll = nullptr, *Spart = nullptr, *Pnear = nullptr, *Kpre = nullptr, *TA = nullptr, *TB = nullptr;
-        const bool tailgemm = own_schur && q > 0 && (mrbf_env("MRBF_R4_TAILGEMM") ? atoi(mrbf_env("MRBF_R4_TAILGEMM")) != 0 : true);
         const int L4 = 4 * (int)n0;
-        if (own_schur) {
+        double *Rb, *Sb, *Rfull = nullptr, *Kn = nullptr, *Ppart = nullptr;
+        double *KbbAll = nullptr, *Spart = nullptr, *Pnear = nullptr, *Kpre = nullptr, *TA = nullptr, *TB = nullptr;
+        int *cnt;
+        if (eager) {
+            MRBF_TRY(get_buf(ctx, S_PHI, (size_t)ldr * (mc + SB), &Rfull));  // R(:, j) for every candidate j (+ one block: the products read whole 128-column tiles)
+            MRBF_TRY(get_buf(ctx, S_STAGE_D, (size_t)SB * mc, &Kn));         // kappa(new, ahead), ld = SB
+            MRBF_TRY(get_buf(ctx, S_STAGE_A, (size_t)(KSPLIT_MAX + 1) * SB * mc, &Ppart));  // the k slices of R(old, new)' R(old, ahead) (+ the tail's)
             MRBF_TRY(get_buf(ctx, S_OUT_A, (size_t)SB * SB * nblocks, &KbbAll));
             MRBF_TRY(get_buf(ctx, S_STAGE_B, (size_t)(2 * KSPLIT_NEAR + 2) * SB * SB, &Spart));
             Pnear = Spart + (size_t)KSPLIT_NEAR * SB * SB;       // the k slices of the next block's update (few columns: split 32 ways; + the tail's)
             Kpre = Pnear + (size_t)(KSPLIT_NEAR + 1) * SB * SB;  // kappa(every candidate of the block, the next block's columns)
-            if (tailgemm) {
+            if (q > 0) {
                 MRBF_TRY(get_buf(ctx, S_T2, (size_t)4 * n0 * mc, &TA));
                 MRBF_TRY(get_buf(ctx, S_OUT_B, (size_t)4 * n0 * mc, &TB));
             }
         }
-        MRBF_TRY(get_buf(ctx, S_Q1, (size_t)maxacc * SB, &Rb));          // R = L_acc^-1 K[acc, block]
+        MRBF_TRY(get_buf(ctx, S_Q1, (size_t)maxacc * SB, &Rb));          // R = L_acc^-1 K[acc, block] (left-looking walk)
         MRBF_TRY(get_buf(ctx, S_RHS, (size_t)3 * SB * SB, &Sb));          // Schur complement of the block | in-block factor columns (two: see below)
         double *const Lblk2[2] = {Sb + (size_t)SB * SB, Sb + (size_t)2 * SB * SB};
         MRBF_TRY(get_buf(ctx, S_IPIV, (size_t)2 * SB + 8, &cnt));
@@ -998,33 +898,27 @@ extern "C" int32_t mrbf_round4(mrbf_ctx *ctx, int64_t n0, int32_t d, const doubl
         // extended on the main stream, the far columns on the side stream while the next block's decision kernel -- one workgroup, 0.46
         // to 0.8 ms -- runs.  The side stream reads the block's factor columns and indices while the next decision kernel writes its own:
         // two copies, by block parity; the main stream waits for the side stream's previous update before it touches what that one
-        // reads or writes (Anew, Kn, Ppart, the next block's columns of R).
+        // reads or writes (Kn, Ppart, the next block's columns of R).
         // The side stream's work is released by an event recorded just before the decision kernel's launch: the decision kernel's one
         // workgroup is then placed at about the same time as the side stream's first workgroups, and with (nearly) the whole LDS of its
         // compute unit asked for, none of them joins it there.  (Tried and dropped: a stream of its own for the walk, with or without the
         // lowest priority -- the process's fifth stream lands on a hardware queue it shares with the main stream, and every small kernel
         // of the walk became 2 to 4 times slower, 5.4 -> 11.3 ms at d = 64.  The context's bulk stream has a queue of its own.)
-        const bool split = eager && custom && (mrbf_env("MRBF_R4_SPLIT") ? atoi(mrbf_env("MRBF_R4_SPLIT")) != 0 : true) && ctx->bulk_stream && ctx->evx[0];
-        hipStream_t sfar = split ? ctx->bulk_stream : s;
-        // kappa(block, next block) for ALL the block's candidates on the side stream while they are being decided: the update of the next
-        // block's columns then starts from rows picked out of it instead of a kappa launch of its own on the critical path
-        const bool prek = split && own_schur && ctx->evx[2] && (mrbf_env("MRBF_R4_PREK") ? atoi(mrbf_env("MRBF_R4_PREK")) != 0 : true);
+        // kappa(block, next block) for ALL the block's candidates goes on the side stream while they are being decided: the update of the
+        // next block's columns then starts from rows picked out of it instead of a kappa launch of its own on the critical path.
+        hipStream_t sfar = ctx->bulk_stream;
         bool far_pending = false, prek_any = false;
         int64_t far_from = 0;  // first candidate of the side stream's pending update
         if (eager) {
-            const size_t fw_shm = (size_t)SB * 64 * sizeof(double) + SB * sizeof(int);
             // (per call: the attribute is per device, and one process may drive several)
-            MRBF_HIP(ctx, hipFuncSetAttribute((const void *)block_forward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fw_shm));
             MRBF_HIP(ctx, hipFuncSetAttribute((const void *)block_forward_mfma_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fwm_shm_bytes(64)));
             MRBF_HIP(ctx, hipFuncSetAttribute((const void *)block_forward_mfma_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fwm_shm_bytes(16)));
-        }
-        if (own_schur) {
             MRBF_HIP(ctx, hipMemsetAsync(KbbAll + (size_t)SB * SB * (nblocks - 1), 0, (size_t)SB * SB * sizeof(double), s));  // (the last block may be partial)
             const dim3 kgrid(2, SB / 16, (unsigned)nblocks);
             MRBF_DISPATCH_KID(kp.kid, hipLaunchKernelGGL((kappa_block_kernel<KID, 1>), kgrid, dim3(256), 0, s, st->Xc, d, st->LamT, st->P0c, F, (int)n0,
                                                          q > 0 ? 1 : 0, st->acc, 0, (int64_t)0, SB, kp, (double *)nullptr, 0, KbbAll, 1, mc));
+            if (q > 0) hipLaunchKernelGGL(tail_forms_kernel, dim3(nb((int64_t)n0 * mc)), dim3(256), 0, s, st->LamT, st->P0c, F, (int)n0, mc, TA, TB);
         }
-        if (tailgemm) hipLaunchKernelGGL(tail_forms_kernel, dim3(nb((int64_t)n0 * mc)), dim3(256), 0, s, st->LamT, st->P0c, F, (int)n0, mc, TA, TB);
         // rows nacc_old .. nacc_old + nblk - 1 of R for the candidates [j0, j0 + ncols) on stream su (Kn, Ppart by absolute candidate index)
         struct ExtJob {
             int64_t i0, j0, ncols;
@@ -1041,21 +935,19 @@ extern "C" int32_t mrbf_round4(mrbf_ctx *ctx, int64_t n0, int32_t d, const doubl
             const int nacc_old = J.nacc_old, nblk = J.nblk;
             double *const Lblk = J.Lblk;
             int *const blkidx = J.blkidx;
-            const bool is_near = J.is_near;
-            const double mone = -1.0;
-            const bool small = is_near && Pnear && ncols <= SB;
+            const bool small = J.is_near && ncols <= SB;
             const bool pre = small && J.pre;  // kappa(block, these columns) is there already, for every candidate of the block
             if (pre) {
                 MRBF_HIP(ctx, hipStreamWaitEvent(su, ctx->evx[2], 0));
             } else {
                 const dim3 kgrid((unsigned)((ncols + 63) / 64), (unsigned)((nblk + 15) / 16));
-                if (tailgemm) {
+                if (q > 0) {  // (the tail goes through the product below)
                     MRBF_DISPATCH_KID(kp.kid, hipLaunchKernelGGL((kappa_block_kernel<KID, 0>), kgrid, dim3(256), 0, su, st->Xc, d, st->LamT, st->P0c, F,
                                                                  (int)n0, 0, st->acc + nacc_old, nblk, j0, (int)ncols, kp, Kn + j0 * SB, SB,
                                                                  (double *)nullptr, 0));
                 } else {
                     MRBF_DISPATCH_KID(kp.kid, hipLaunchKernelGGL((kappa_block_kernel<KID, 1>), kgrid, dim3(256), 0, su, st->Xc, d, st->LamT, st->P0c, F,
-                                                                 (int)n0, q > 0 ? 1 : 0, st->acc + nacc_old, nblk, j0, (int)ncols, kp, Kn + j0 * SB, SB,
+                                                                 (int)n0, 0, st->acc + nacc_old, nblk, j0, (int)ncols, kp, Kn + j0 * SB, SB,
                                                                  (double *)nullptr, 0));
                 }
             }
@@ -1064,40 +956,32 @@ extern "C" int32_t mrbf_round4(mrbf_ctx *ctx, int64_t n0, int32_t d, const doubl
             double *const Pb = small ? Pnear : Ppart + j0 * SB;
             const int64_t ps = small ? (int64_t)SB * SB : pstride;
             if (nacc_old > 0) {
-                if (custom) {
-                    // enough (column tile, k slice) workgroups to fill the device twice over, slices of whole 16-deep groups
-                    const int ntile = (int)((ncols + 63) / 64);
-                    ksplit = std::max(1, std::min({small ? KSPLIT_NEAR : KSPLIT_MAX, (512 + ntile - 1) / ntile, (nacc_old + 63) / 64}));
-                    const int kchunk = (int)round_up((nacc_old + ksplit - 1) / ksplit, 16);
-                    ksplit = (nacc_old + kchunk - 1) / kchunk;
-                    // (left operand: the new sites' columns of R in place, through the block's index list)
-                    hipLaunchKernelGGL(r4_tn_gemm_kernel, dim3((unsigned)ntile, (unsigned)ksplit), dim3(256), 0, su, Rfull + i0 * (int64_t)ldr, ldr,
-                                       Rfull + j0 * (int64_t)ldr, (int64_t)ldr, nacc_old, ncols, kchunk, Pb, ps, blkidx, nblk);
-                } else {
-                    MRBF_BLAS(ctx, rocblas_dgemm(ctx->blas, rocblas_operation_transpose, rocblas_operation_none, nblk, (int)ncols, nacc_old, &mone,
-                                                 Anew, ldr, Rfull + j0 * (int64_t)ldr, ldr, &one, Kn + j0 * SB, SB));
-                }
+                // enough (column tile, k slice) workgroups to fill the device twice over, slices of whole 16-deep groups
+                const int ntile = (int)((ncols + 63) / 64);
+                ksplit = std::max(1, std::min({small ? KSPLIT_NEAR : KSPLIT_MAX, (512 + ntile - 1) / ntile, (nacc_old + 63) / 64}));
+                const int kchunk = (int)round_up((nacc_old + ksplit - 1) / ksplit, 16);
+                ksplit = (nacc_old + kchunk - 1) / kchunk;
+                // (left operand: the new sites' columns of R in place, through the block's index list)
+                hipLaunchKernelGGL(r4_tn_gemm_kernel, dim3((unsigned)ntile, (unsigned)ksplit), dim3(256), 0, su, Rfull + i0 * (int64_t)ldr, ldr,
+                                   Rfull + j0 * (int64_t)ldr, (int64_t)ldr, nacc_old, ncols, kchunk, Pb, ps, blkidx, nblk);
             }
-            if (tailgemm && !pre) {  // the tail of kappa(new, these columns): one more slice, TA(:, new)' TB(:, columns)
+            if (q > 0 && !pre) {  // the tail of kappa(new, these columns): one more slice, TA(:, new)' TB(:, columns)
                 hipLaunchKernelGGL(r4_tn_gemm_kernel, dim3((unsigned)((ncols + 63) / 64), 1), dim3(256), 0, su, TA + i0 * (int64_t)L4, L4, TB + j0 * (int64_t)L4,
                                    (int64_t)L4, L4, ncols, (int)round_up(L4, 16), Pb + (int64_t)ksplit * ps, ps, blkidx, nblk);
                 ++ksplit;
             }
-            if (custom && ncols <= 1024)
+            if (ncols <= 1024)
                 hipLaunchKernelGGL(block_forward_mfma_kernel<16>, dim3((unsigned)((ncols + 15) / 16)), dim3(256), fwm_shm_bytes(16), su, Kin, Pb, ksplit, ps,
                                    Lblk, blkidx, nblk, ncols, Rfull + j0 * (int64_t)ldr + nacc_old, (int64_t)ldr, pre ? 1 : 0);
-            else if (custom)
+            else
                 hipLaunchKernelGGL(block_forward_mfma_kernel<64>, dim3((unsigned)((ncols + 63) / 64)), dim3(256), fwm_shm_bytes(64), su, Kin, Pb, ksplit, ps,
                                    Lblk, blkidx, nblk, ncols, Rfull + j0 * (int64_t)ldr + nacc_old, (int64_t)ldr, 0);
-            else
-                hipLaunchKernelGGL(block_forward_kernel, dim3((unsigned)((ncols + 63) / 64)), dim3(64), (size_t)SB * 64 * sizeof(double) + SB * sizeof(int),
-                                   su, Kn + j0 * SB, SB, Lblk, blkidx, nblk, ncols, Rfull + j0 * (int64_t)ldr + nacc_old, ldr);
             return 0;
         };
         ExtJob far_job{};  // the far columns' update of the block before: issued after this block's decision kernel is on its way
         int blkno = 0;
         bool info_checked = false;
-        if (prek) {  // the side stream's first kernel reads what the main stream has just set up (lambda, F, the candidates' coordinates)
+        if (eager) {  // the side stream's first kernel reads what the main stream has just set up (lambda, F, the candidates' coordinates)
             MRBF_HIP(ctx, hipEventRecord(ctx->evx[0], s));
             MRBF_HIP(ctx, hipStreamWaitEvent(sfar, ctx->evx[0], 0));
         }
@@ -1114,10 +998,10 @@ extern "C" int32_t mrbf_round4(mrbf_ctx *ctx, int64_t n0, int32_t d, const doubl
             double *const Lblk = Lblk2[blkno & 1];
             int *const blkidx = blkidx2[blkno & 1];
             ++blkno;
-            if (eager) Rb = Rfull + i0 * (int64_t)ldr;  // this block's columns of R are up to date: every earlier block extended them
             const int64_t near_next = std::min<int64_t>(SB, mc - (i0 + bsz));
-            const bool have_prek = prek && near_next > 0;
-            if (own_schur) {
+            const bool have_prek = eager && near_next > 0;
+            if (eager) {
+                Rb = Rfull + i0 * (int64_t)ldr;  // this block's columns of R are up to date: every earlier block extended them
                 int ks = 0;
                 if (nacc > 0) {
                     const int ntile = (bsz + 63) / 64;
@@ -1128,81 +1012,41 @@ extern "C" int32_t mrbf_round4(mrbf_ctx *ctx, int64_t n0, int32_t d, const doubl
                                        kchunk, Spart, (int64_t)SB * SB);
                 }
                 hipLaunchKernelGGL(schur_reduce_kernel, dim3(SB * SB / 256), dim3(256), 0, s, KbbAll + (size_t)(i0 / SB) * SB * SB, Spart, ks, bsz, Sb);
-            } else if (lazy) {
-                if (bsz < SB) MRBF_HIP(ctx, hipMemsetAsync(Sb, 0, (size_t)SB * SB * sizeof(double), s));
-                const int nlist = eager ? 0 : nacc;  // (eager: only kappa(block, block) is needed here)
-                const dim3 kgrid((unsigned)((bsz + 63) / 64), (unsigned)((nlist + bsz + 15) / 16));
-                MRBF_DISPATCH_KID(kp.kid, hipLaunchKernelGGL((kappa_block_kernel<KID, 1>), kgrid, dim3(256), 0, s, st->Xc, d, st->LamT, st->P0c, F, (int)n0,
-                                                             q > 0 ? 1 : 0, st->acc, nlist, i0, bsz, kp, Rb, maxacc, Sb, 1));
             } else {
-                hipLaunchKernelGGL(block_copy_kernel, dim3(nb(SB * SB)), dim3(256), 0, s, st->K, mc, i0, bsz, Sb);
-            }
-            if (nacc > 0 && !own_schur) {
-                if (!lazy)
-                    hipLaunchKernelGGL(gather_kab_kernel, dim3(nb((int64_t)nacc * bsz)), dim3(256), 0, s, st->K, mc, st->acc, nacc, i0, bsz, Rb, maxacc);
-                if (!eager)
+                // left-looking walk: kappa(accepted | block, block), the block's columns of R by a triangular solve with the accepted factor
+                if (bsz < SB) MRBF_HIP(ctx, hipMemsetAsync(Sb, 0, (size_t)SB * SB * sizeof(double), s));
+                const dim3 kgrid((unsigned)((bsz + 63) / 64), (unsigned)((nacc + bsz + 15) / 16));
+                MRBF_DISPATCH_KID(kp.kid, hipLaunchKernelGGL((kappa_block_kernel<KID, 1>), kgrid, dim3(256), 0, s, st->Xc, d, st->LamT, st->P0c, F, (int)n0,
+                                                             q > 0 ? 1 : 0, st->acc, nacc, i0, bsz, kp, Rb, maxacc, Sb, 1));
+                if (nacc > 0) {
                     MRBF_BLAS(ctx, rocblas_dtrsm(ctx->blas, rocblas_side_left, rocblas_fill_lower, rocblas_operation_none, rocblas_diagonal_non_unit, nacc,
                                                  bsz, &one, st->LK, maxacc, Rb, ldr));
-                MRBF_BLAS(ctx, rocblas_dgemm(ctx->blas, rocblas_operation_transpose, rocblas_operation_none, bsz, bsz, nacc, &mone, Rb, ldr, Rb, ldr,
-                                             &one, Sb, SB));
+                    MRBF_BLAS(ctx, rocblas_dgemm(ctx->blas, rocblas_operation_transpose, rocblas_operation_none, bsz, bsz, nacc, &mone, Rb, ldr, Rb, ldr,
+                                                 &one, Sb, SB));
+                }
             }
-            if (far_job.valid) MRBF_HIP(ctx, hipEventRecord(ctx->evx[0], s));  // (releases the side stream's update: see `split`)
-            if (walk_sel) {
-#define MRBF_R4_WALK(TW_, NA_, NB__)                                                                                                              \
-    do {                                                                                                                                          \
-        const size_t pis = std::max<size_t>((size_t)SB * 16 * NB__ * sizeof(double), R4_SEL_LDS);                                                  \
-        if (blkno == 1)                                                                                                                           \
-            MRBF_HIP(ctx, hipFuncSetAttribute((const void *)select_block_walk_kernel<TW_, NA_, NB__>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                              (int)pis));                                                                                         \
-        hipLaunchKernelGGL((select_block_walk_kernel<TW_, NA_, NB__>), dim3(1), dim3(64 * TW_), pis, s, Sb, bsz, i0, (int)n0, q, (int)max_points, \
-                           maxacc, thr, st->Prow, st->Ginv, st->acc, cnt, Lblk, blkidx, (unsigned long long *)nullptr);                           \
+            if (far_job.valid) MRBF_HIP(ctx, hipEventRecord(ctx->evx[0], s));  // (releases the side stream's update: see the two streams above)
+#define R4_DECIDE(KERNEL_, THREADS_, SHM_, ...)                                                                                                  \
+    do {                                                                                                                                         \
+        if (blkno == 1) MRBF_HIP(ctx, hipFuncSetAttribute((const void *)KERNEL_, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(SHM_)));      \
+        hipLaunchKernelGGL(KERNEL_, dim3(1), dim3(THREADS_), SHM_, s, Sb, bsz, i0, (int)n0, q, (int)max_points, maxacc, thr, st->Prow, st->Ginv, \
+                           st->acc, cnt, Lblk, blkidx, ##__VA_ARGS__);                                                                              \
     } while (0)
-#define MRBF_R4_DUO(N_)                                                                                                                             \
-    do {                                                                                                                                            \
-        const size_t pis = std::max<size_t>((size_t)SB * 16 * N_ * sizeof(double), R4_SEL_LDS);                                                      \
-        if (blkno == 1)                                                                                                                             \
-            MRBF_HIP(ctx, hipFuncSetAttribute((const void *)select_block_duo_kernel<N_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pis));     \
-        hipLaunchKernelGGL((select_block_duo_kernel<N_>), dim3(1), dim3(512), pis, s, Sb, bsz, i0, (int)n0, q, (int)max_points, maxacc, thr, st->Prow, \
-                           st->Ginv, st->acc, cnt, Lblk, blkidx, (unsigned long long *)nullptr);                                                    \
-    } while (0)
-                // q <= 80: the two halves of a step on different waves (same bits; 119 against 140 us per block at q = 65); beyond, the G waves'
-                // share (2 q^2 / 256 entries per thread + q / 16 row sums) outweighs the S waves' and every wave does both
-                if (q <= 32 && duo)
-                    MRBF_R4_DUO(2);
-                else if (q <= 64 && duo)
-                    MRBF_R4_DUO(4);
-                else if (q <= 80 && duo)
-                    MRBF_R4_DUO(5);
-                else if (q <= 32)
-                    MRBF_R4_WALK(8, 1, 2);
-                else if (q <= 64)
-                    MRBF_R4_WALK(8, 2, 4);
-                else if (q <= 80)
-                    MRBF_R4_WALK(8, 3, 5);
-                else if (q <= 128)
-                    MRBF_R4_WALK(8, 4, 8);
-                else
-                    MRBF_R4_WALK(8, 5, 9);
-#undef MRBF_R4_DUO
-#undef MRBF_R4_WALK
-            } else if (fast_sel == 1 && selw == 8)
-                hipLaunchKernelGGL((select_block_reg_kernel<2, 10, 8>), dim3(1), dim3(512), shm_reg, s, Sb, bsz, i0, (int)n0, q, (int)max_points, maxacc,
-                                   thr, st->Prow, st->Ginv, st->acc, cnt, Lblk, blkidx);
-            else if (fast_sel == 2 && selw == 8)
-                hipLaunchKernelGGL((select_block_reg_kernel<2, 16, 8>), dim3(1), dim3(512), shm_reg, s, Sb, bsz, i0, (int)n0, q, (int)max_points, maxacc,
-                                   thr, st->Prow, st->Ginv, st->acc, cnt, Lblk, blkidx);
-            else if (fast_sel == 1)
-                hipLaunchKernelGGL((select_block_reg_kernel<2, 5, 16>), dim3(1), dim3(SEL_THREADS), shm_reg, s, Sb, bsz, i0, (int)n0, q, (int)max_points, maxacc,
-                                   thr, st->Prow, st->Ginv, st->acc, cnt, Lblk, blkidx);
-            else if (fast_sel == 2)
-                hipLaunchKernelGGL((select_block_reg_kernel<2, 8, 16>), dim3(1), dim3(SEL_THREADS), shm_reg, s, Sb, bsz, i0, (int)n0, q, (int)max_points, maxacc,
-                                   thr, st->Prow, st->Ginv, st->acc, cnt, Lblk, blkidx);
-            else if (fast_sel == 3)
-                hipLaunchKernelGGL((select_block_reg_kernel<3, 12, 16>), dim3(1), dim3(SEL_THREADS), shm_reg, s, Sb, bsz, i0, (int)n0, q, (int)max_points, maxacc,
-                                   thr, st->Prow, st->Ginv, st->acc, cnt, Lblk, blkidx);
+            if (q == 0 || q > 192)
+                R4_DECIDE(select_block_kernel, SEL_THREADS, shm);
+            else if (q <= 32)
+                R4_DECIDE((select_block_duo_kernel<2>), 512, walk_lds(2), (unsigned long long *)nullptr);
+            else if (q <= 64)
+                R4_DECIDE((select_block_duo_kernel<4>), 512, walk_lds(4), (unsigned long long *)nullptr);
+            else if (q <= 80)
+                R4_DECIDE((select_block_duo_kernel<5>), 512, walk_lds(5), (unsigned long long *)nullptr);
+            else if (q <= 128)
+                R4_DECIDE((select_block_walk_kernel<8, 4, 8>), 512, walk_lds(8), (unsigned long long *)nullptr);
+            else if (q <= 144)
+                R4_DECIDE((select_block_walk_kernel<8, 5, 9>), 512, walk_lds(9), (unsigned long long *)nullptr);
             else
-                hipLaunchKernelGGL(select_block_kernel, dim3(1), dim3(SEL_THREADS), shm, s, Sb, bsz, i0, (int)n0, q, (int)max_points, maxacc, thr, st->Prow,
-                                   st->Ginv, st->acc, cnt, Lblk, blkidx);
+                R4_DECIDE((select_block_reg_kernel<3, 12, 16>), SEL_THREADS, shm_reg);
+#undef R4_DECIDE
             // side stream, issued only now (the host calls cost ~40 us; ahead of the Schur product and the decision kernel they delayed the
             // critical path by as much): the far columns' update of the block before, then kappa(this block, next block)
             auto issue_side = [&]() -> int {
@@ -1244,14 +1088,11 @@ extern "C" int32_t mrbf_round4(mrbf_ctx *ctx, int64_t n0, int32_t d, const doubl
             const int64_t i1 = i0 + bsz, ahead = mc - i1;
             if (eager && nblk > 0 && ahead > 0 && (int64_t)n0 + nacc < max_points && nacc < maxacc) {
                 if (far_pending) MRBF_HIP(ctx, hipStreamWaitEvent(s, ctx->evx[1], 0));  // the side stream's update of the block before
-                if (nacc_old > 0 && !custom)
-                    hipLaunchKernelGGL(gather_newcols_kernel, dim3(nb((int64_t)nacc_old * nblk)), dim3(256), 0, s, Rfull, ldr, nacc_old, i0, blkidx, nblk,
-                                       Anew, ldr);
                 // the next block's columns first, alone on the device (started together, the far update's 150 workgroups doubled the
                 // duration of these few); the far columns then run under the next block's Schur product and decisions
-                const int64_t near = split ? std::min<int64_t>(SB, ahead) : ahead;
-                MRBF_TRY(extend(ExtJob{i0, i1, near, nacc_old, nblk, Lblk, blkidx, split, have_prek, true}, s));
-                if (split && ahead > near) {
+                const int64_t near = std::min<int64_t>(SB, ahead);
+                MRBF_TRY(extend(ExtJob{i0, i1, near, nacc_old, nblk, Lblk, blkidx, true, have_prek, true}, s));
+                if (ahead > near) {
                     far_job = ExtJob{i0, i1 + near, ahead - near, nacc_old, nblk, Lblk, blkidx, false, false, true};
                     far_pending = true;  // (its event is recorded when it is issued: before the next host wait)
                     far_from = i1 + near;

@@ -251,13 +251,17 @@ def test_round4_device_selection_and_factor_reuse(name, deg, d, n, k):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name,deg,d,n,mp", [("cubic", 1, 130, 150, 231), ("multiquadric", 1, 12, 700, 91), ("gaussian", 1, 40, 900, 500),
-                                             ("inv_multiquadric", 0, 8, 333, 200), ("gaussian", -1, 6, 300, 180)])
+                                             ("inv_multiquadric", 0, 8, 333, 200), ("gaussian", -1, 6, 300, 180), ("multiquadric", 1, 70, 200, 211),
+                                             ("gaussian", 1, 100, 200, 241), ("multiquadric", 1, 136, 200, 277), ("cubic", 1, 150, 200, 291),
+                                             ("cubic", 1, 200, 200, 341)])
 def test_round4_walk_variants_agree(name, deg, d, n, mp):
-    """Round 5 gave the walk three forms (and the right-looking one a set of switches that select its earlier stages): kappa on demand + per-block triangular solve (left-looking), kappa on demand + R kept for every
-    candidate ahead (right-looking, no triangular solve against the accepted factor), and the mc x mc construction of rounds 3 / 4
-    (MRBF_R4_LAZY=0).  They compute the same quantities in different orders: the accepted lists must be identical, the fits from the
-    kept factors equal to rounding, and the list equal to the independent oracle's.  d = 130: q = 131, the decision kernel's
-    three-row register variant; every case crosses at least one block boundary."""
+    """The walk has two forms: R kept for every candidate ahead (right-looking, the default) and kappa(accepted | block, block) + a
+    per-block triangular solve against the accepted factor (left-looking, the memory fallback; MRBF_R4_EAGER=0).  They compute the
+    same quantities in different orders: the accepted lists must be identical, the fits from the kept factors equal to rounding, and
+    the list equal to the independent oracle's.  Every decision-kernel range of q has a case that crosses at least one block
+    boundary: q = 0 (d = 6), q <= 32 (d = 8; d = 12 stops inside the first block), 33-64 (d = 40), 65-80 (d = 70), 81-128 (d = 100),
+    129-144 (d = 136; d = 130, q = 131, stops inside the first block), 145-192 (d = 150: the register kernel), q > 192 (d = 200: the
+    memory kernel)."""
     import os
 
     rng = np.random.default_rng(300 + d)
@@ -270,13 +274,7 @@ def test_round4_walk_variants_agree(name, deg, d, n, mp):
     kidp, ap, bp = pkg.rbf_model._get_kernel_params(1.0, cfg)
     S0, Cc = sites[start], sites[cands]
     results = {}
-    # (right-looking walk: also with the register / memory decision kernels of rounds 4 / 3, every wave doing both halves of a step, one
-    # stream, rocBLAS for the block's Schur complement, the tail of kappa inside the kappa kernel, no kappa ahead of the decisions)
-    variants = (("left", {"MRBF_R4_EAGER": "0"}), ("right", {"MRBF_R4_EAGER": "1"}), ("full", {"MRBF_R4_LAZY": "0"}),
-                ("right/select1", {"MRBF_R4_SELECT": "1"}), ("right/select0", {"MRBF_R4_SELECT": "0"}), ("right/noduo", {"MRBF_R4_DUO": "0"}),
-                ("right/onestream", {"MRBF_R4_SPLIT": "0"}), ("right/blas-schur", {"MRBF_R4_SCHUR": "0"}),
-                ("right/tail-in-kappa", {"MRBF_R4_TAILGEMM": "0"}), ("right/no-prek", {"MRBF_R4_PREK": "0"}),
-                ("right/blas-update", {"MRBF_R4_CUSTOM": "0"}))
+    variants = (("left", {"MRBF_R4_EAGER": "0"}), ("right", {}))
     for tag, env in variants:
         os.environ.update(env)
         try:
