@@ -289,6 +289,13 @@ int32_t mrbf_debug_mega_tables(int32_t nt, int32_t mt, int32_t slack, int32_t sl
  * number of streamed rows and every one of these job shapes (each tile finished / updated exactly once). */
 int32_t mrbf_debug_mega_tables2(int32_t nt, int32_t mt, int32_t slack, int32_t slack_chain, int32_t first, int32_t win, int32_t srows,
                                 int32_t half_cols, const int32_t *opt5, int64_t *out6);
+/* Host only: the schedule the persistent factorisation picks by size alone (no option or switch set) for nt block columns / mt block
+ * rows, with xreal > 0 when only so many of the rows below the square are non-zero (the fit's right-hand sides), and its job tables
+ * checked.  out39[0..8] = slack, slack_chain, first window, window, streamed rows, half_cols, tail_half, tail_half_w, chain queues;
+ * [9..17] = the edge regime: head, tail_c0, srows_edge, pstream_edge, shalf, sh_head, sh_tail_c0, tfull1, xhalf; [18..32] = nchain,
+ * ndedicated, nreserve, head_job1, reserve_job0, xchain, quiet_tail, pstream, look, use_quiet, wbias, cboost, panel_dma, grid, srows_max;
+ * [33..38] = the six words of mrbf_debug_mega_tables for these tables.  Returns 0, or -(argument index) for a parameter out of range. */
+int32_t mrbf_debug_mega_plan(int32_t nt, int32_t mt, int32_t xreal, int64_t *out39);
 
 /* ---- Pascoletti-Serafini descent step with the subproblem solver on the device ----------------------------------------
  * Replaces, for objectives that share ONE grouped RBF model and carry no modelled constraints, the NLopt runs inside

@@ -8,7 +8,6 @@
 
 namespace mrbf {
 
-int potrf_blocked(mrbf_ctx *ctx, int64_t n, double *A, int64_t lda, int *dinfo);  // chol_blocked.hip
 int debug_diag(mrbf_ctx *ctx, const double *A128_dev, int reps, float *ms_per_call, unsigned long long *stamps_host);
 int launch_pad_identity(mrbf_ctx *ctx, double *A, int64_t n, int64_t npad, int64_t ld);  // chol_blocked.hip
 
@@ -19,19 +18,14 @@ int potrf_lower(mrbf_ctx *ctx, int impl, int64_t n, double *A, int64_t lda, int 
     int *dinfo;
     MRBF_TRY(get_buf(ctx, S_INFO, (size_t)4, &dinfo));
     const int64_t npad = round_up(n, 128);
-    if (impl == 0) impl = (lda >= npad) ? ((npad >= ctx->mega_min && npad <= ctx->mega_max) ? 3 : 2) : 1;
+    if (impl == 0) impl = (lda >= npad) ? ((npad >= ctx->mega.min && npad <= ctx->mega.max) ? 3 : 2) : 1;
     if (impl == 2 || impl == 3) {
-        const int saved = ctx->chol_impl, saved_min = ctx->mega_min;
-        ctx->chol_impl = impl;
-        if (impl == 3) ctx->mega_min = 0;
-        struct Restore {
-            mrbf_ctx *c;
-            int a, b;
-            ~Restore() { c->chol_impl = a; c->mega_min = b; }
-        } restore{ctx, saved, saved_min};
         if (lda < npad) return fail(ctx, MRBF_EHIP, "built-in Cholesky needs lda >= round_up(n,128)");
         MRBF_TRY(launch_pad_identity(ctx, A, n, npad, lda));
-        MRBF_TRY(potrf_blocked(ctx, npad, A, lda, dinfo));
+        PotrfOpts opt;
+        opt.impl = impl;
+        opt.any_size = true;  // impl 3 asked for by name: the persistent launch whatever the size
+        MRBF_TRY(potrf_blocked_tall(ctx, npad, npad, A, lda, dinfo, nullptr, opt));
     } else {
         MRBF_BLAS(ctx, rocsolver_dpotrf(ctx->blas, rocblas_fill_lower, (int)n, A, (int)lda, dinfo));
     }

@@ -25,7 +25,6 @@ constexpr int CNB = 128;  // block size of the factorisation
 
 enum { UPD_LOWER_SUB = 0, UPD_OVERWRITE = 1, UPD_FULL_SUB = 2, UPD_COLUMN_SUB = 3 };
 int launch_diag_v4(mrbf_ctx *ctx, hipStream_t st, double *Ajj, int64_t lda, double *Linv, int *dinfo, int col0);  // chol_diag.hip
-int potrf_mega_tall(mrbf_ctx *ctx, int64_t ncols, int64_t mrows, double *A, int64_t lda, int *dinfo, double *linv_all);  // chol_mega.hip
 
 // C(i,j) (op)= sum_k A(i,k) * B(j,k).  A: (tiles_i*TM) x K, B: (tiles_j*128) x K, all column-major.
 // MODE LOWER_SUB: square region, grid.x = lower-triangular tile pairs (TM == 128), C -= ..., strictly-upper
@@ -477,16 +476,17 @@ int launch_update_lower(mrbf_ctx *ctx, const double *A, int64_t lda, const doubl
 // A_below * L^-T.  Appending right-hand sides as extra ROWS therefore yields the forward substitution
 // L^-1 b for free, and appending a tall matrix X below its Gram matrix X'X yields the Q factor of X
 // (Cholesky-QR).  linv_all (optional) receives the 128 x 128 inverses of all diagonal blocks of L.
-int potrf_blocked_tall(mrbf_ctx *ctx, int64_t ncols, int64_t mrows, double *A, int64_t lda, int *dinfo, double *linv_all) {
+int potrf_blocked_tall(mrbf_ctx *ctx, int64_t ncols, int64_t mrows, double *A, int64_t lda, int *dinfo, double *linv_all, PotrfOpts opt) {
     if (ncols % CNB != 0 || mrows % CNB != 0 || mrows < ncols || (lda & 1) || (reinterpret_cast<uintptr_t>(A) & 15))
         return fail(ctx, MRBF_EHIP, "potrf_blocked needs 128-padded, 16-byte aligned storage (ncols=%lld mrows=%lld lda=%lld)",
                     (long long)ncols, (long long)mrows, (long long)lda);
-    // chol_impl 3 (and the default, 0, from mega_min columns on): the whole factorisation as one persistent launch (chol_mega.hip);
-    // chol_impl 2 forces the host-driven launches below
+    // impl 3 (and the default, 0, from mega.min columns on): the whole factorisation as one persistent launch (chol_mega.hip);
+    // impl 2 forces the host-driven launches below
     // (measured, end of round 2: the persistent launch wins from 256 columns on -- n = 256: 0.107 vs 0.142 ms, 384: 0.138 vs 0.242,
     //  8192: 4.4 vs 8.2, 16384: 27 vs 35.6; a single 128-column block is faster as one diagonal kernel + panel launch)
-    if ((ctx->chol_impl == 3 || (ctx->chol_impl == 0 && ncols <= ctx->mega_max)) && ncols >= ctx->mega_min)
-        return potrf_mega_tall(ctx, ncols, mrows, A, lda, dinfo, linv_all);
+    const int impl = opt.impl != 0 ? opt.impl : ctx->chol_impl;
+    if ((impl == 3 || (impl == 0 && ncols <= ctx->mega.max)) && (opt.any_size || ncols >= ctx->mega.min))
+        return potrf_mega_tall(ctx, ncols, mrows, A, lda, dinfo, linv_all, opt);
     double *Lone = nullptr;
     if (!linv_all) MRBF_TRY(get_buf(ctx, S_CHOL_WS, (size_t)CNB * CNB, &Lone));
     // Look-ahead over two streams.  Panel stream P (high priority): D(j), T(j), U1(j) = update of block column j+1
@@ -589,10 +589,6 @@ int potrf_blocked_tall(mrbf_ctx *ctx, int64_t ncols, int64_t mrows, double *A, i
         MRBF_HIP(ctx, hipStreamWaitEvent(S, evStart, 0));
     }
     return 0;
-}
-
-int potrf_blocked(mrbf_ctx *ctx, int64_t n, double *A, int64_t lda, int *dinfo) {
-    return potrf_blocked_tall(ctx, n, n, A, lda, dinfo, nullptr);
 }
 
 // ---- backward substitution  L' x = y  for k right-hand sides, using the stored diagonal-block inverses ----------

@@ -25,7 +25,7 @@
 // closed at least `slack` chain steps before c as bulk jobs (right-looking, rank 512..1024) and takes the newer panels
 // left-looking inside its own panel job, so a panel that has just been finished never has to pass through a bulk job
 // before the next diagonal blocks can start; the bulk of the flops streams the trailing matrix once per window.
-// (`srows`, `nchain` and the chain tiles' slack are chosen by matrix size in potrf_mega_tall.)
+// (`srows`, `nchain` and the chain tiles' slack are chosen by matrix size in plan_for.)
 // Three pools of workgroups: `nchain` serve the chain queue (P, S jobs, in order; their CU partner pauses), `ndedicated`
 // serve the panel queue (T jobs, column by column, rows ascending) and may wait inside a job, all others take the head of
 // the panel queue when it can run (diagonal block at most `look` steps away AND its bulk updates in), else a bulk job: bulk
@@ -71,16 +71,7 @@ __host__ __device__ inline int nbulk_updates(int i, int c, int slack, int slack_
     return t < first ? 0 : (t - first) / win + 1;
 }
 
-// Edge regime: the first `head` and the last block columns (from `tail_c0` on) are chain-bound whatever the matrix size (the machine
-// is still filling / already emptying), the middle is throughput-bound.  Streamed rows below the diagonal and the diagonal job's
-// stream depth are therefore chosen per block column: the chain-bound values at the edges, the size's own in between.
-struct Edge {
-    int head, tail_c0, srows_edge, pstream_edge;
-    int shalf, sh_head, sh_tail_c0;  // shalf: streamed tiles of the block columns c < sh_head and c >= sh_tail_c0 as two 64-row jobs (see run_stream)
-    int tfull1;  // > 0: panel tiles more than tfull1 - 1 block rows below the streamed ones are ONE 128-row job (Job::w = 2), not two halves
-    int xhalf;   // the block rows below the square (i >= NT: right-hand sides riding along) hold at most 64 non-zero rows: rows 64 .. 127 of
-                 // their tiles are zero and stay zero -- panel and bulk jobs work on the upper half only and publish for both (Job::w = 3 / half code 2)
-};
+// (Edge -- the per-column regime at the first and last block columns -- lives in common.hpp next to TableParams)
 __host__ __device__ inline bool edge_col(int c, const Edge &e) { return c < e.head || c >= e.tail_c0; }
 __host__ __device__ inline int srows_at(int c, int srows, const Edge &e) { return edge_col(c, e) ? e.srows_edge : srows; }
 __host__ __device__ inline bool shalf_at(int c, int srows, const Edge &e) { return e.shalf && (c < e.sh_head || c >= e.sh_tail_c0) && srows_at(c, srows, e) >= 5; }
@@ -1096,8 +1087,12 @@ __global__ void mega_status_kernel(const unsigned *ctl, int *info, unsigned long
 //   bulk queues  two per window w (ordinary tiles: queue w, chain tiles: queue nwin + w, empty without `chainq`): U(i, c, w) for
 //                every tile the window reaches through a bulk job (nbulk_updates), as two 64-row halves when block column c lies
 //                within `slack + half_cols` columns behind the window's end.
-static void build_job_tables(int NT, int MT, int slack, int slack_chain, int first, int win, int srows, const mega::Edge &edge, int half_cols,
-                             int tail_half, int tail_half_w, bool chainq, std::vector<mega::Job> &pj, std::vector<mega::Job> &bj, std::vector<mega::Job> &cj, std::vector<int> &wqs) {
+static void build_job_tables(int NT, int MT, const mega::TableParams &p, std::vector<mega::Job> &pj, std::vector<mega::Job> &bj, std::vector<mega::Job> &cj,
+                             std::vector<int> &wqs) {
+    const int slack = p.slack, slack_chain = p.slack_chain, first = p.first, win = p.win, srows = p.srows, half_cols = p.half_cols;
+    const int tail_half = p.tail_half, tail_half_w = p.tail_half_w;
+    const bool chainq = p.chainq != 0;
+    const mega::Edge &edge = p.edge;
     using namespace mega;
     pj.clear();
     bj.clear();
@@ -1149,10 +1144,160 @@ static void build_job_tables(int NT, int MT, int slack, int slack_chain, int fir
     wqs.push_back((int)bj.size());
 }
 
+namespace mega {
+// The schedule of one NT x MT launch: the job tables' parameters and the launch geometry (copied into Args by potrf_mega_tall).
+struct Plan {
+    TableParams tp;
+    int nchain, ndedicated, nreserve, head_job1, reserve_job0, xchain, quiet_tail, pstream, look, use_quiet, wbias, cboost, panel_dma, grid;
+    int srows_max;  // most streamed rows of any block column (sizes the sprog flags)
+};
+
+// Pure (no context, no environment, no GPU call; mrbf_debug_mega_plan runs it in the CPU container): the size rules, each overridden
+// by its knob.  `xreal` > 0: only so many of the rows below the square are non-zero (PotrfOpts::xreal).
+static Plan plan_for(int NT, int MT, const Knobs &k, int xreal) {
+    Plan p{};
+    TableParams &tp = p.tp;
+    Edge &edge = tp.edge;
+    // Streamed tile rows below the diagonal, chain workgroups and the chain tiles' slack by size (measured, tools/sweep_sizes.sh): a
+    // streamed row takes its predecessor column's panel in step instead of in one 14-us piece after a T job, which shortens the
+    // dependency loop T(c+2,c-1) -> S(c+2,c) -> S(c+2,c+1) -> P(c+2) that paces chain-bound sizes (n <= 6144: 5-8 % with five rows);
+    // every streamed row is one more resident job per column in flight (and one more paused CU partner), which the saturated middle of
+    // large matrices pays for (n = 8192: three rows, n >= 12288: two).  Environment / option values override.
+    const int srows_auto = NT <= 48 ? 5 : (NT <= 96 ? 3 : 2);
+    // streamed tiles as 64-row halves where the whole factorisation is chain-bound (n <= 4096), with twice the chain workgroups (each
+    // on a CU of its own: four XCDs).  Measured r04 (tools/sweep_shalf.sh): n = 1024 / 2048 / 3072 / 4096: -8.6 / -10 / -9 /
+    // -6 %; n >= 6144: the halves cost more matrix-pipe time than the chain gains (in the last 16 block columns only: -2.6 .. 0 %).
+    const int sh_tail = k.shalf >= 0 ? k.shalf : (NT <= 40 ? 1 << 20 : 0), sh_head = k.shalf_head >= 0 ? k.shalf_head : 0;
+    const bool shalf_all = sh_tail >= NT;
+    // (n = 4608 / 5120 with 48 chain workgroups on two XCDs: -9 / -8 %, with 64 on four: -7 / -6 %; n = 6144: +4 %, left alone)
+    const int chain_auto = NT <= 48 ? (shalf_all ? (NT <= 32 ? 64 : 48) : 32) : (NT <= 96 ? 20 : 12);
+    const int slack_chain_auto = (NT > 48 && NT <= 96) ? 7 : 6;
+    tp.slack = std::max(1, k.slack);
+    tp.slack_chain = std::max(tp.slack, k.slack_chain > 0 ? k.slack_chain : slack_chain_auto);
+    // longer windows for large matrices (measured: n = 16384: 33.8 / 31.7 / 30.8 ms with 4 / 6 / 8 panels per window; n = 8192: the same)
+    tp.win = std::max(1, k.win > 0 ? k.win : (NT >= 88 ? 8 : (NT >= 56 ? 6 : WIN_DEFAULT)));
+    tp.first = std::min(tp.win, std::max(1, k.first_window));
+    const int srows = tp.srows = k.srows > 0 ? k.srows : srows_auto;  // streamed tiles below each diagonal block
+    tp.half_cols = k.half_cols;
+    // the edge regime (first / last block columns: chain-bound at every size, see mega::Edge); only where the middle differs from it
+    edge.srows_edge = std::max(srows, 5);
+    edge.pstream_edge = 2;
+    {
+        // (measured r04, alternating A/B: sixteen tail columns in the edge regime + 64-row bulk jobs in the last twenty block columns
+        //  -- tail_half below --: n = 6144 / 8192 / 12288 / 16384: -2.5 / -5.3 / -2.6 / -1.2 %; the head alone: no change)
+        const int head = k.head >= 0 ? k.head : 0, tail = k.tail >= 0 ? k.tail : 16;
+        edge.head = (srows < edge.srows_edge) ? std::min(head, NT) : 0;
+        edge.tail_c0 = (srows < edge.srows_edge) ? std::max(edge.head, NT - tail) : NT;
+    }
+    {
+        // streamed tiles as 64-row halves: the last `MRBF_MEGA_SHALF` block columns (and the first MRBF_MEGA_SHALF_HEAD)
+        edge.shalf = (sh_tail > 0 || sh_head > 0) ? 1 : 0;
+        edge.sh_head = std::min(sh_head, NT);
+        edge.sh_tail_c0 = std::max(edge.sh_head, NT - sh_tail);
+        // panel tiles far below the diagonal as 128-row jobs (MRBF_MEGA_TFULL = block rows below the streamed ones that stay halves; -1: all halves)
+        // (64-row halves keep a block row's column-to-column recurrence ahead of the chain; at n >= 12288 the rows more than eight below
+        //  the streamed ones have the slack for 128-row jobs, whose GEMM loop shares the B operand between twice the MFMAs:
+        //  alternating A/B r04: n = 12288 / 16384: -0.9 / -1.1 %, n = 10240: 0; all panel tiles full at n <= 8192: +4 .. +28 %)
+        edge.tfull1 = k.tfull >= 0 ? k.tfull + 1 : (k.tfull == -1 && NT >= 96 ? 9 : 0);
+        // rows below the square that are known to be zero (the fit's right-hand sides: k of the 128 rows of the extra block row)
+        edge.xhalf = (k.xhalf && MT == NT + 1 && xreal > 0 && xreal <= 64) ? 1 : 0;
+    }
+    p.srows_max = std::max(srows, (edge.head > 0 || edge.tail_c0 < NT) ? edge.srows_edge : srows);
+    tp.chainq = k.chainq != 0;
+    p.cboost = k.cboost;
+    // bulk jobs of the last block columns as 64-row halves (diagonal tiles included): there the machine runs empty and what is left
+    // are per-tile chains of window updates -- each a K = 128 win GEMM of one workgroup, one after the other on the same tile --
+    // that the diagonal chain ends up waiting for (job log r04: P(56) at n = 8192 waited 146 us for the last three windows of its
+    // tile); two workgroups per tile halve every link.  n = 4096: -1.8 %, smaller: no change.
+    tp.tail_half = k.tail_half >= 0 ? k.tail_half : (NT >= 32 ? 20 : 0);
+    tp.tail_half_w = k.tail_half_w >= 0 ? k.tail_half_w : 1000;  // only the last so many window updates of such a tile
+    p.nchain = k.chain > 0 ? k.chain : chain_auto;
+    p.ndedicated = k.dedicated;
+    p.look = k.look;
+    p.use_quiet = k.quiet;
+    p.wbias = k.wbias;
+    {
+        // chain jobs in front of the block columns `head` and `tail_c0 - 3` (the reserves are in place when the tail begins)
+        int job = 0;
+        p.head_job1 = 0;
+        p.reserve_job0 = 1 << 30;
+        // (edge columns here: those of the edge regime and those whose streamed tiles are halved -- twice the chain jobs per column)
+        const int e_head = std::max(edge.head, edge.shalf ? edge.sh_head : 0), e_tail_c0 = std::min(edge.tail_c0, edge.shalf ? edge.sh_tail_c0 : NT);
+        const int lead_c0 = std::max(e_head, e_tail_c0 - 3);
+        for (int c = 0; c <= NT; ++c) {
+            if (c == e_head) p.head_job1 = job;
+            if (c == lead_c0 && e_tail_c0 < NT) p.reserve_job0 = job;
+            if (c < NT) job += 1 + (shalf_at(c, srows, edge) ? 2 : 1) * std::min(srows_at(c, srows, edge), MT - 1 - c);
+        }
+        p.nreserve = (e_head > 0 || e_tail_c0 < NT) ? (k.reserve >= 0 ? k.reserve : 12) : 0;
+    }
+    p.panel_dma = k.panel_dma;
+    p.pstream = k.pstream > 0 ? std::min(k.pstream, srows) : (NT <= 48 && srows >= 2 ? 2 : 1);
+    // small matrices: one workgroup per CU is plenty (and leaves room for other contexts' launches: mrbf_batch_run)
+    p.grid = (NT <= 16 && k.grid > 256) ? 256 : k.grid;
+    if (p.nchain < 1) p.nchain = 1;
+    if (p.nchain + p.ndedicated >= p.grid) p.ndedicated = std::max(0, p.grid / 2 - p.nchain);
+    {
+        const int xc = k.xchain >= 0 ? k.xchain : (p.nchain > 48 ? 4 : (p.nchain > 32 ? 2 : 1));
+        p.xchain = (xc > 0 && 8 * p.nchain <= std::min(xc, 8) * p.grid) ? std::min(xc, 8) : 0;  // enough blocks = 0 .. xc-1 (mod 8) for the chain
+        // (n = 16384: the CU partners of the 12 chain workgroups join the bulk work until 32 block columns are left: 27.0 -> 26.5 ms;
+        //  at n <= 8192 the chain is never far from critical and pausing the partners throughout is as good or better)
+        p.quiet_tail = k.quiet_tail >= 0 ? k.quiet_tail : (NT > 96 ? 32 : 1 << 20);
+    }
+    return p;
+}
+}  // namespace mega
+
+// The one place that reads the schedule's switches (each honoured behind MRBF_EXPERIMENTS only: mrbf_env).  mrbf_init calls it for
+// every new context; the switches that were function-local statics of the launcher are still read once per process.
+mega::Knobs mega_knobs_from_env() {
+    auto num = [](const char *e, int unset) { return e ? atoi(e) : unset; };
+    static const mega::Knobs once = [&] {
+        mega::Knobs k;
+        k.shalf = num(mrbf_env("MRBF_MEGA_SHALF"), -1);
+        k.shalf_head = num(mrbf_env("MRBF_MEGA_SHALF_HEAD"), -1);
+        k.head = num(mrbf_env("MRBF_MEGA_HEAD"), -1);
+        k.tail = num(mrbf_env("MRBF_MEGA_TAIL"), -1);
+        k.reserve = num(mrbf_env("MRBF_MEGA_RESERVE"), -1);
+        if (const char *e = mrbf_env("MRBF_MEGA_TFULL")) k.tfull = atoi(e) >= 0 ? atoi(e) : -2;  // (a negative value: all halves)
+        k.xhalf = num(mrbf_env("MRBF_MEGA_XHALF"), 1);
+        k.chainq = num(mrbf_env("MRBF_MEGA_CHAINQ"), 0);
+        k.cboost = num(mrbf_env("MRBF_MEGA_CBOOST"), 12);
+        k.tail_half = num(mrbf_env("MRBF_MEGA_TAILHALF"), -1);
+        k.tail_half_w = num(mrbf_env("MRBF_MEGA_TAILHALF_W"), -1);
+        k.panel_dma = num(mrbf_env("MRBF_MEGA_PANELDMA"), 1);
+        k.xchain = num(mrbf_env("MRBF_MEGA_XCHAIN"), -1);
+        k.quiet_tail = num(mrbf_env("MRBF_MEGA_QUIET_TAIL"), -1);
+        return k;
+    }();
+    mega::Knobs k = once;
+    k.grid = num(mrbf_env("MRBF_MEGA_GRID"), k.grid);
+    k.dedicated = num(mrbf_env("MRBF_MEGA_DEDICATED"), k.dedicated);
+    k.look = num(mrbf_env("MRBF_MEGA_LOOK"), k.look);
+    k.min = num(mrbf_env("MRBF_MEGA_MIN"), k.min);
+    k.max = num(mrbf_env("MRBF_MEGA_MAX"), k.max);
+    k.quiet = num(mrbf_env("MRBF_MEGA_QUIET"), k.quiet);
+    k.chain = num(mrbf_env("MRBF_MEGA_CHAIN"), k.chain);
+    k.slack = num(mrbf_env("MRBF_MEGA_SLACK"), k.slack);
+    k.slack_chain = num(mrbf_env("MRBF_MEGA_SLACK_CHAIN"), k.slack_chain);
+    k.half_cols = num(mrbf_env("MRBF_MEGA_HALF_COLS"), k.half_cols);
+    k.first_window = num(mrbf_env("MRBF_MEGA_FIRST_WINDOW"), k.first_window);
+    k.win = num(mrbf_env("MRBF_MEGA_WIN"), k.win);
+    k.wbias = num(mrbf_env("MRBF_MEGA_WBIAS"), k.wbias);
+    k.srows = num(mrbf_env("MRBF_MEGA_SROWS"), k.srows);
+    k.pstream = num(mrbf_env("MRBF_MEGA_PSTREAM"), k.pstream);
+    return k;
+}
+
+// Two parameter sets that the decimal-weight key this cache once used could not tell apart (tail_c0 = 100 against tail_half = 1)
+static_assert(!(mega::TableParams{3, 6, 1, 8, 2, 0, 0, 1000, 0, mega::Edge{0, 100, 5, 2, 0, 0, 0, 0, 0}} ==
+                mega::TableParams{3, 6, 1, 8, 2, 0, 1, 1000, 0, mega::Edge{0, 0, 5, 2, 0, 0, 0, 0, 0}}),
+              "the job-table cache compares every field of TableParams");
+
 // Same contract as potrf_blocked_tall (chol_blocked.hip): on return the leading ncols x ncols block holds L, the rows
 // below hold A_below * L^-T, linv_all (optional) the inverses of the diagonal blocks; *dinfo = 0, the 1-based index of
 // the first non-positive pivot, or a negative code when the launch gave up on a dependency (never observed; every spin is bounded).
-int potrf_mega_tall(mrbf_ctx *ctx, int64_t ncols, int64_t mrows, double *A, int64_t lda, int *dinfo, double *linv_all) {
+int potrf_mega_tall(mrbf_ctx *ctx, int64_t ncols, int64_t mrows, double *A, int64_t lda, int *dinfo, double *linv_all, PotrfOpts opt) {
     using namespace mega;
     if (ncols % NB != 0 || mrows % NB != 0 || mrows < ncols || (lda & 1) || (reinterpret_cast<uintptr_t>(A) & 15))
         return fail(ctx, MRBF_EHIP, "potrf_mega needs 128-padded, 16-byte aligned storage (ncols=%lld mrows=%lld lda=%lld)",
@@ -1167,6 +1312,8 @@ int potrf_mega_tall(mrbf_ctx *ctx, int64_t ncols, int64_t mrows, double *A, int6
         if (host_trace_ms > 0.0 && nh < 8) hstamp[nh++] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
     };
     hnow();
+    const Plan plan = plan_for(NT, MT, ctx->mega, opt.xreal);
+    const TableParams &tp = plan.tp;
     Args a{};
     a.A = A;
     a.lda = lda;
@@ -1178,82 +1325,16 @@ int potrf_mega_tall(mrbf_ctx *ctx, int64_t ncols, int64_t mrows, double *A, int6
         MRBF_TRY(get_buf(ctx, S_CHOL_WS, (size_t)NT * NB * NB, &a.linv));
     }
     MRBF_TRY(get_buf(ctx, S_MEGA_IT, (size_t)NT * 8 * 256, &a.itg));
-    // job tables (cached per shape)
-    // Streamed tile rows below the diagonal, chain workgroups and the chain tiles' slack by size (measured, tools/sweep_sizes.sh): a
-    // streamed row takes its predecessor column's panel in step instead of in one 14-us piece after a T job, which shortens the
-    // dependency loop T(c+2,c-1) -> S(c+2,c) -> S(c+2,c+1) -> P(c+2) that paces chain-bound sizes (n <= 6144: 5-8 % with five rows);
-    // every streamed row is one more resident job per column in flight (and one more paused CU partner), which the saturated middle of
-    // large matrices pays for (n = 8192: three rows, n >= 12288: two).  Environment / option values override.
-    const int NTq = (int)(ncols / NB);
-    const int srows_auto = NTq <= 48 ? 5 : (NTq <= 96 ? 3 : 2);
-    // streamed tiles as 64-row halves where the whole factorisation is chain-bound (n <= 4096), with twice the chain workgroups (each
-    // on a CU of its own: four XCDs).  Measured r04 (tools/sweep_shalf.sh): n = 1024 / 2048 / 3072 / 4096: -8.6 / -10 / -9 /
-    // -6 %; n >= 6144: the halves cost more matrix-pipe time than the chain gains (in the last 16 block columns only: -2.6 .. 0 %).
-    static const int env_shalf = mrbf_env("MRBF_MEGA_SHALF") ? atoi(mrbf_env("MRBF_MEGA_SHALF")) : -1;
-    static const int env_shalf_head = mrbf_env("MRBF_MEGA_SHALF_HEAD") ? atoi(mrbf_env("MRBF_MEGA_SHALF_HEAD")) : -1;
-    const int sh_tail = env_shalf >= 0 ? env_shalf : (NTq <= 40 ? 1 << 20 : 0), sh_head = env_shalf_head >= 0 ? env_shalf_head : 0;
-    const bool shalf_all = sh_tail >= NTq;
-    // (n = 4608 / 5120 with 48 chain workgroups on two XCDs: -9 / -8 %, with 64 on four: -7 / -6 %; n = 6144: +4 %, left alone)
-    const int chain_auto = NTq <= 48 ? (shalf_all ? (NTq <= 32 ? 64 : 48) : 32) : (NTq <= 96 ? 20 : 12);
-    const int slack_chain_auto = (NTq > 48 && NTq <= 96) ? 7 : 6;
-    const int slack = std::max(1, ctx->mega_slack), slack_chain = std::max(slack, ctx->mega_slack_chain > 0 ? ctx->mega_slack_chain : slack_chain_auto);
-    // longer windows for large matrices (measured: n = 16384: 33.8 / 31.7 / 30.8 ms with 4 / 6 / 8 panels per window; n = 8192: the same)
-    const int win = std::max(1, ctx->mega_win > 0 ? ctx->mega_win : (NT >= 88 ? 8 : (NT >= 56 ? 6 : WIN_DEFAULT)));
-    const int first = std::min(win, std::max(1, ctx->mega_first_window));
-    const int srows = ctx->mega_srows > 0 ? ctx->mega_srows : srows_auto;  // streamed tiles below each diagonal block
-    // the edge regime (first / last block columns: chain-bound at every size, see mega::Edge); only where the middle differs from it
-    static const int env_head = mrbf_env("MRBF_MEGA_HEAD") ? atoi(mrbf_env("MRBF_MEGA_HEAD")) : -1;
-    static const int env_tail = mrbf_env("MRBF_MEGA_TAIL") ? atoi(mrbf_env("MRBF_MEGA_TAIL")) : -1;
-    static const int env_reserve = mrbf_env("MRBF_MEGA_RESERVE") ? atoi(mrbf_env("MRBF_MEGA_RESERVE")) : -1;
-    Edge edge{};
-    edge.srows_edge = std::max(srows, 5);
-    edge.pstream_edge = 2;
-    {
-        // (measured r04, alternating A/B: sixteen tail columns in the edge regime + 64-row bulk jobs in the last twenty block columns
-        //  -- tail_half below --: n = 6144 / 8192 / 12288 / 16384: -2.5 / -5.3 / -2.6 / -1.2 %; the head alone: no change)
-        const int head = env_head >= 0 ? env_head : 0, tail = env_tail >= 0 ? env_tail : 16;
-        edge.head = (srows < edge.srows_edge) ? std::min(head, NT) : 0;
-        edge.tail_c0 = (srows < edge.srows_edge) ? std::max(edge.head, NT - tail) : NT;
-    }
-    {
-        // streamed tiles as 64-row halves: the last `MRBF_MEGA_SHALF` block columns (and the first MRBF_MEGA_SHALF_HEAD)
-        edge.shalf = (sh_tail > 0 || sh_head > 0) ? 1 : 0;
-        edge.sh_head = std::min(sh_head, NT);
-        edge.sh_tail_c0 = std::max(edge.sh_head, NT - sh_tail);
-        // panel tiles far below the diagonal as 128-row jobs (MRBF_MEGA_TFULL = block rows below the streamed ones that stay halves; -1: all halves)
-        static const int env_tfull = mrbf_env("MRBF_MEGA_TFULL") ? atoi(mrbf_env("MRBF_MEGA_TFULL")) : -1;
-        // (64-row halves keep a block row's column-to-column recurrence ahead of the chain; at n >= 12288 the rows more than eight below
-        //  the streamed ones have the slack for 128-row jobs, whose GEMM loop shares the B operand between twice the MFMAs:
-        //  alternating A/B r04: n = 12288 / 16384: -0.9 / -1.1 %, n = 10240: 0; all panel tiles full at n <= 8192: +4 .. +28 %)
-        edge.tfull1 = env_tfull >= 0 ? env_tfull + 1 : (mrbf_env("MRBF_MEGA_TFULL") ? 0 : (NTq >= 96 ? 9 : 0));
-        // rows below the square that are known to be zero (the fit's right-hand sides: k of the 128 rows of the extra block row)
-        static const int env_xhalf = mrbf_env("MRBF_MEGA_XHALF") ? atoi(mrbf_env("MRBF_MEGA_XHALF")) : 1;
-        edge.xhalf = (env_xhalf && MT == NT + 1 && ctx->mega_xreal > 0 && ctx->mega_xreal <= 64) ? 1 : 0;
-    }
-    const int srows_max = std::max(srows, (edge.head > 0 || edge.tail_c0 < NT) ? edge.srows_edge : srows);
-    // job tables: one set per (NT, MT, schedule parameters), kept in a small per-context LRU -- Morbit's training sets grow and shrink
+    // job tables: one set per (NT, MT, table parameters), kept in a small per-context LRU -- Morbit's training sets grow and shrink
     // by a few sites between iterations, so n keeps crossing 128-boundaries back and forth; rebuilding the tables on every change
     // cost three copies and a stream synchronisation inside the factorisation phase
-    static const int chainq = mrbf_env("MRBF_MEGA_CHAINQ") ? atoi(mrbf_env("MRBF_MEGA_CHAINQ")) : 0;
-    static const int cboost = mrbf_env("MRBF_MEGA_CBOOST") ? atoi(mrbf_env("MRBF_MEGA_CBOOST")) : 12;
-    // bulk jobs of the last block columns as 64-row halves (diagonal tiles included): there the machine runs empty and what is left
-    // are per-tile chains of window updates -- each a K = 128 win GEMM of one workgroup, one after the other on the same tile --
-    // that the diagonal chain ends up waiting for (job log r04: P(56) at n = 8192 waited 146 us for the last three windows of its
-    // tile); two workgroups per tile halve every link.  n = 4096: -1.8 %, smaller: no change.
-    static const int env_tail_half = mrbf_env("MRBF_MEGA_TAILHALF") ? atoi(mrbf_env("MRBF_MEGA_TAILHALF")) : -1;
-    const int tail_half = env_tail_half >= 0 ? env_tail_half : (NT >= 32 ? 20 : 0);
-    static const int env_tail_half_w = mrbf_env("MRBF_MEGA_TAILHALF_W") ? atoi(mrbf_env("MRBF_MEGA_TAILHALF_W")) : -1;
-    const int tail_half_w = env_tail_half_w >= 0 ? env_tail_half_w : 1000;  // only the last so many window updates of such a tile
-    const long tab_key = (chainq ? 50 : 0) + slack + 100000000000000L * tail_half + 10000000000000000L * std::min(tail_half_w, 99) + 100 * ctx->mega_half_cols + 10000 * slack_chain + 1000000 * first + 10000000 * win + 100000000 * (long)srows +
-                         1000000000L * edge.head + 1000000000000L * edge.tail_c0;
-    const long tab_key2 = (edge.shalf ? 1 + edge.sh_head + 1000L * edge.sh_tail_c0 : 0) + 1000000L * edge.tfull1 + 1000000000L * edge.xhalf;
     MegaTables *tab = nullptr;
     for (auto &t : ctx->mega_tables)
-        if (t.nt == NT && t.mt == MT && t.key == tab_key && t.key2 == tab_key2) tab = &t;
+        if (t.nt == NT && t.mt == MT && t.params == tp) tab = &t;
     if (!tab) {
         std::vector<Job> pj, bj, cj;
         std::vector<int> wqs;
-        build_job_tables(NT, MT, slack, slack_chain, first, win, srows, edge, ctx->mega_half_cols, tail_half, tail_half_w, chainq != 0, pj, bj, cj, wqs);
+        build_job_tables(NT, MT, tp, pj, bj, cj, wqs);
         if (ctx->mega_tables.size() >= 8) {  // evict the least recently used set (nothing on the stream may still read it)
             MRBF_HIP(ctx, hipStreamSynchronize(ctx->stream));
             size_t lru = 0;
@@ -1265,8 +1346,7 @@ int potrf_mega_tall(mrbf_ctx *ctx, int64_t ncols, int64_t mrows, double *A, int6
         MegaTables t{};
         t.nt = NT;
         t.mt = MT;
-        t.key = tab_key;
-        t.key2 = tab_key2;
+        t.params = tp;
         t.npanel = (int)pj.size();
         t.nbulk = (int)bj.size();
         t.nchainjobs = (int)cj.size();
@@ -1288,85 +1368,54 @@ int potrf_mega_tall(mrbf_ctx *ctx, int64_t ncols, int64_t mrows, double *A, int6
         tab = &ctx->mega_tables.back();
     }
     tab->stamp = ++ctx->mega_table_clock;
-    ctx->mega_nt = NT;
-    ctx->mega_mt = MT;
-    ctx->mega_npanel = tab->npanel;
-    ctx->mega_nbulk = tab->nbulk;
-    ctx->mega_nchainjobs = tab->nchainjobs;
-    ctx->mega_nwin = tab->nwin;
     Job *dj = (Job *)tab->jobs;
-    a.cjobs = dj + ctx->mega_npanel + ctx->mega_nbulk;
-    a.nchainjobs = ctx->mega_nchainjobs;
     a.pjobs = dj;
-    a.npanel = ctx->mega_npanel;
-    a.bjobs = dj + ctx->mega_npanel;
-    a.nbulk = ctx->mega_nbulk;
-    a.nwin = ctx->mega_nwin;
+    a.npanel = tab->npanel;
+    a.bjobs = dj + tab->npanel;
+    a.nbulk = tab->nbulk;
+    a.cjobs = dj + tab->npanel + tab->nbulk;
+    a.nchainjobs = tab->nchainjobs;
+    a.nwin = tab->nwin;
     a.wq_start = (int *)tab->wq;
     // flags: one block, zeroed before every launch
-    const size_t nfl = ((size_t)CTL_WORDS + (size_t)QSTRIDE * (2 * a.nwin + 1) + (size_t)QSTRIDE * 512 + (size_t)QSTRIDE * (1 + 2 * srows_max) * NT + 2 * (size_t)MT * NT + 3) / 4 * 4;
+    const size_t nfl = ((size_t)CTL_WORDS + (size_t)QSTRIDE * (2 * a.nwin + 1) + (size_t)QSTRIDE * 512 + (size_t)QSTRIDE * (1 + 2 * plan.srows_max) * NT + 2 * (size_t)MT * NT + 3) / 4 * 4;
     unsigned *fl;
     MRBF_TRY(get_buf(ctx, S_MEGA_FLAGS, nfl, &fl));
     hnow();  // 1: buffers / job tables
     MRBF_HIP(ctx, hipMemsetAsync(fl, 0, nfl * sizeof(unsigned), ctx->stream));
     hnow();  // 2: first memset enqueued
-    if (!ctx->mega_info_clean) MRBF_HIP(ctx, hipMemsetAsync(dinfo, 0, sizeof(int), ctx->stream));  // (the fit zeroes its flag words itself, in front of everything)
+    if (!opt.info_clean) MRBF_HIP(ctx, hipMemsetAsync(dinfo, 0, sizeof(int), ctx->stream));  // (the fit zeroes its flag words itself, in front of everything)
     hnow();  // 3: second memset enqueued
     a.ctl = fl;
     a.wq_head = fl + CTL_WORDS;
     a.quiet = a.wq_head + (size_t)QSTRIDE * (2 * a.nwin + 1);
     a.dprog = a.quiet + (size_t)QSTRIDE * 512;
     a.sprog = a.dprog + (size_t)QSTRIDE * NT;
-    a.tdone = a.sprog + (size_t)QSTRIDE * 2 * srows_max * NT;
+    a.tdone = a.sprog + (size_t)QSTRIDE * 2 * plan.srows_max * NT;
     a.ucnt = a.tdone + (size_t)MT * NT;
     a.info = dinfo;
-    a.nchain = ctx->mega_chain > 0 ? ctx->mega_chain : chain_auto;
-    a.ndedicated = ctx->mega_dedicated;
-    a.look = ctx->mega_look;
-    a.use_quiet = ctx->mega_quiet;
-    a.slack = slack;
-    a.slack_chain = slack_chain;
-    a.first = first;
-    a.win = win;
-    a.wbias = ctx->mega_wbias;
-    a.srows = srows;
-    a.edge = edge;
-    a.cboost = cboost;
-    {
-        // chain jobs in front of the block columns `head` and `tail_c0 - 3` (the reserves are in place when the tail begins)
-        int job = 0;
-        a.head_job1 = 0;
-        a.reserve_job0 = 1 << 30;
-        // (edge columns here: those of the edge regime and those whose streamed tiles are halved -- twice the chain jobs per column)
-        const int e_head = std::max(edge.head, edge.shalf ? edge.sh_head : 0), e_tail_c0 = std::min(edge.tail_c0, edge.shalf ? edge.sh_tail_c0 : NT);
-        const int lead_c0 = std::max(e_head, e_tail_c0 - 3);
-        for (int c = 0; c <= NT; ++c) {
-            if (c == e_head) a.head_job1 = job;
-            if (c == lead_c0 && e_tail_c0 < NT) a.reserve_job0 = job;
-            if (c < NT) job += 1 + (shalf_at(c, srows, edge) ? 2 : 1) * std::min(srows_at(c, srows, edge), MT - 1 - c);
-        }
-        a.nreserve = (e_head > 0 || e_tail_c0 < NT) ? (env_reserve >= 0 ? env_reserve : 12) : 0;
-    }
-    {
-        static const int env_pdma = mrbf_env("MRBF_MEGA_PANELDMA") ? atoi(mrbf_env("MRBF_MEGA_PANELDMA")) : 1;
-        a.panel_dma = env_pdma;
-    }
-    a.pstream = ctx->mega_pstream > 0 ? std::min(ctx->mega_pstream, srows) : (NTq <= 48 && srows >= 2 ? 2 : 1);
+    a.nchain = plan.nchain;
+    a.ndedicated = plan.ndedicated;
+    a.look = plan.look;
+    a.use_quiet = plan.use_quiet;
+    a.slack = tp.slack;
+    a.slack_chain = tp.slack_chain;
+    a.first = tp.first;
+    a.win = tp.win;
+    a.wbias = plan.wbias;
+    a.srows = tp.srows;
+    a.edge = tp.edge;
+    a.cboost = plan.cboost;
+    a.head_job1 = plan.head_job1;
+    a.reserve_job0 = plan.reserve_job0;
+    a.nreserve = plan.nreserve;
+    a.panel_dma = plan.panel_dma;
+    a.pstream = plan.pstream;
+    a.xchain = plan.xchain;
+    a.quiet_tail = plan.quiet_tail;
     a.spin_ticks = (unsigned long long)std::max(1, ctx->spin_ms) * 100000ull;  // wall_clock64 runs at 100 MHz
     a.fault = (ctx->debug_fault & 1) && MT > 1;
-    // small matrices: one workgroup per CU is plenty (and leaves room for other contexts' launches: mrbf_batch_run)
-    const int grid = (NT <= 16 && ctx->mega_grid > 256) ? 256 : ctx->mega_grid;
-    if (a.nchain < 1) a.nchain = 1;
-    if (a.nchain + a.ndedicated >= grid) a.ndedicated = std::max(0, grid / 2 - a.nchain);
-    {
-        static const int env_xc = mrbf_env("MRBF_MEGA_XCHAIN") ? atoi(mrbf_env("MRBF_MEGA_XCHAIN")) : -1;
-        const int xc = env_xc >= 0 ? env_xc : (a.nchain > 48 ? 4 : (a.nchain > 32 ? 2 : 1));
-        a.xchain = (xc > 0 && 8 * a.nchain <= std::min(xc, 8) * grid) ? std::min(xc, 8) : 0;  // enough blocks = 0 .. xc-1 (mod 8) for the chain
-        // (n = 16384: the CU partners of the 12 chain workgroups join the bulk work until 32 block columns are left: 27.0 -> 26.5 ms;
-        //  at n <= 8192 the chain is never far from critical and pausing the partners throughout is as good or better)
-        static const int qt = mrbf_env("MRBF_MEGA_QUIET_TAIL") ? atoi(mrbf_env("MRBF_MEGA_QUIET_TAIL")) : -1;
-        a.quiet_tail = qt >= 0 ? qt : (NTq > 96 ? 32 : 1 << 20);
-    }
+    const int grid = plan.grid;
     const char *trace_path = mrbf_env("MRBF_MEGA_TRACE");
     if (trace_path) {
         a.trace_dbg = mrbf_env("MRBF_MEGA_TRACE_WAVE") ? 12 + 16 * (atoi(mrbf_env("MRBF_MEGA_TRACE_WAVE")) & 3) : 4;
@@ -1375,7 +1424,7 @@ int potrf_mega_tall(mrbf_ctx *ctx, int64_t ncols, int64_t mrows, double *A, int6
     }
     const char *jlog_path = mrbf_env("MRBF_MEGA_JLOG");
     if (jlog_path) {
-        a.jlog_cap = ctx->mega_npanel + ctx->mega_nbulk + ctx->mega_nchainjobs + 16;
+        a.jlog_cap = a.npanel + a.nbulk + a.nchainjobs + 16;
         MRBF_TRY(get_buf(ctx, S_MEGA_JLOG, (size_t)8 * a.jlog_cap + 16, &a.jlog));
         MRBF_HIP(ctx, hipMemsetAsync(a.jlog, 0, ((size_t)8 * a.jlog_cap + 16) * sizeof(unsigned long long), ctx->stream));
     }
@@ -1477,13 +1526,15 @@ int potrf_mega_tall(mrbf_ctx *ctx, int64_t ncols, int64_t mrows, double *A, int6
 //   w < nbulk_updates(i, c) exactly once (one full job or both halves, over the ordinary and the chain tiles' queue of that window
 //   together) and no other; every window only updates tiles of block columns behind its own last panel; a queue lists its jobs by
 //   ascending block column; the chain tiles' queues hold chain tiles only (and all of them when they are in use).
-static int32_t check_mega_tables(int nt, int mt, int slack, int slack_chain, int first, int win, int srows, const mrbf::mega::Edge &edge,
-                                 int half_cols, int tail_half, int tail_half_w, bool chainq, int64_t *out) {
+static int32_t check_mega_tables(int nt, int mt, const mrbf::mega::TableParams &p, int64_t *out) {
     using namespace mrbf;
     using namespace mrbf::mega;
     std::vector<Job> pj, bj, cj;
     std::vector<int> wqs;
-    build_job_tables(nt, mt, slack, slack_chain, first, win, srows, edge, half_cols, tail_half, tail_half_w, chainq, pj, bj, cj, wqs);
+    build_job_tables(nt, mt, p, pj, bj, cj, wqs);
+    const int slack = p.slack, slack_chain = p.slack_chain, first = p.first, win = p.win, srows = p.srows;
+    const bool chainq = p.chainq != 0;
+    const Edge &edge = p.edge;
     int64_t bad = 0;
     auto sr = [&](int c) { return srows_at(c, srows, edge); };
     std::vector<int> fin((size_t)mt * nt, 0);
@@ -1553,7 +1604,7 @@ extern "C" int32_t mrbf_debug_mega_tables(int32_t nt, int32_t mt, int32_t slack,
     if (slack < 1 || slack_chain < slack || win < 1 || first < 1 || first > win || srows < 0 || half_cols < 0) return -3;
     if (!out) return -9;
     const mrbf::mega::Edge no_edge{0, nt, srows, 1, 0};
-    return check_mega_tables(nt, mt, slack, slack_chain, first, win, srows, no_edge, half_cols, 0, 0, false, out);
+    return check_mega_tables(nt, mt, mrbf::mega::TableParams{slack, slack_chain, first, win, srows, half_cols, 0, 0, 0, no_edge}, out);
 }
 
 // The same with the round-4 options: opt[0] = head columns, opt[1] = tail columns of the edge regime (five streamed rows there),
@@ -1576,5 +1627,25 @@ extern "C" int32_t mrbf_debug_mega_tables2(int32_t nt, int32_t mt, int32_t slack
     edge.sh_tail_c0 = ((opt5[4] >> 10) & 0xff) ? std::max(edge.sh_head, nt - ((opt5[4] >> 10) & 0xff)) : (edge.sh_head ? nt : 0);
     edge.xhalf = (opt5[4] >> 26) & 1;  // bit 26: the block rows below the square hold at most 64 non-zero rows
     edge.tfull1 = (opt5[4] >> 18) & 0xff;  // bits 18..25: panel tiles more than this - 1 block rows below the streamed ones as one 128-row job
-    return check_mega_tables(nt, mt, slack, slack_chain, first, win, srows, edge, half_cols, opt5[2], opt5[3] > 0 ? opt5[3] : 1000, (opt5[4] & 1) != 0, out);
+    return check_mega_tables(nt, mt, mrbf::mega::TableParams{slack, slack_chain, first, win, srows, half_cols, opt5[2], opt5[3] > 0 ? opt5[3] : 1000, opt5[4] & 1, edge}, out);
+}
+
+// The schedule the launcher picks by size alone (plan_for with no knob set) for nt block columns / mt block rows, `xreal` as in
+// PotrfOpts, and its job tables checked.  out[0..8] = slack, slack_chain, first, win, srows, half_cols, tail_half, tail_half_w, chainq;
+// out[9..17] = the edge regime: head, tail_c0, srows_edge, pstream_edge, shalf, sh_head, sh_tail_c0, tfull1, xhalf; out[18..32] = nchain,
+// ndedicated, nreserve, head_job1, reserve_job0, xchain, quiet_tail, pstream, look, use_quiet, wbias, cboost, panel_dma, grid, srows_max;
+// out[33..38] = the six words of mrbf_debug_mega_tables for these tables.
+extern "C" int32_t mrbf_debug_mega_plan(int32_t nt, int32_t mt, int32_t xreal, int64_t *out) {
+    if (nt < 1 || mt < nt || mt > 32000) return -1;
+    if (xreal < 0) return -3;
+    if (!out) return -4;
+    const mrbf::mega::Plan p = mrbf::mega::plan_for(nt, mt, mrbf::mega::Knobs{}, xreal);
+    const mrbf::mega::TableParams &t = p.tp;
+    const mrbf::mega::Edge &e = t.edge;
+    const int v[33] = {t.slack, t.slack_chain, t.first, t.win, t.srows, t.half_cols, t.tail_half, t.tail_half_w, t.chainq,
+                       e.head, e.tail_c0, e.srows_edge, e.pstream_edge, e.shalf, e.sh_head, e.sh_tail_c0, e.tfull1, e.xhalf,
+                       p.nchain, p.ndedicated, p.nreserve, p.head_job1, p.reserve_job0, p.xchain, p.quiet_tail, p.pstream, p.look, p.use_quiet,
+                       p.wbias, p.cboost, p.panel_dma, p.grid, p.srows_max};
+    for (int i = 0; i < 33; ++i) out[i] = v[i];
+    return check_mega_tables(nt, mt, t, out + 33);
 }

@@ -46,13 +46,59 @@ struct Buf {
 }  // namespace mrbf
 
 namespace mrbf {
+namespace mega {
+// Edge regime: the first `head` and the last block columns (from `tail_c0` on) are chain-bound whatever the matrix size (the machine
+// is still filling / already emptying), the middle is throughput-bound.  Streamed rows below the diagonal and the diagonal job's
+// stream depth are therefore chosen per block column: the chain-bound values at the edges, the size's own in between.
+struct Edge {
+    int head, tail_c0, srows_edge, pstream_edge;
+    int shalf, sh_head, sh_tail_c0;  // shalf: streamed tiles of the block columns c < sh_head and c >= sh_tail_c0 as two 64-row jobs (see run_stream)
+    int tfull1;  // > 0: panel tiles more than tfull1 - 1 block rows below the streamed ones are ONE 128-row job (Job::w = 2), not two halves
+    int xhalf;   // the block rows below the square (i >= NT: right-hand sides riding along) hold at most 64 non-zero rows: rows 64 .. 127 of
+                 // their tiles are zero and stay zero -- panel and bulk jobs work on the upper half only and publish for both (Job::w = 3 / half code 2)
+};
+// Everything the job tables of an NT x MT launch depend on (build_job_tables) -- and therefore what the table cache compares.
+struct TableParams {
+    int slack, slack_chain, first, win, srows, half_cols, tail_half, tail_half_w, chainq;
+    Edge edge;
+};
+constexpr bool operator==(const TableParams &a, const TableParams &b) {
+    return a.slack == b.slack && a.slack_chain == b.slack_chain && a.first == b.first && a.win == b.win && a.srows == b.srows &&
+           a.half_cols == b.half_cols && a.tail_half == b.tail_half && a.tail_half_w == b.tail_half_w && a.chainq == b.chainq &&
+           a.edge.head == b.edge.head && a.edge.tail_c0 == b.edge.tail_c0 && a.edge.srows_edge == b.edge.srows_edge &&
+           a.edge.pstream_edge == b.edge.pstream_edge && a.edge.shalf == b.edge.shalf && a.edge.sh_head == b.edge.sh_head &&
+           a.edge.sh_tail_c0 == b.edge.sh_tail_c0 && a.edge.tfull1 == b.edge.tfull1 && a.edge.xhalf == b.edge.xhalf;
+}
+// Every override the schedule of the persistent factorisation listens to (options and MRBF_MEGA_* switches, read by knobs_from_env
+// in chol_mega.hip when a context is created); plan_for turns them and the shape into the schedule of one launch.
+struct Knobs {
+    int grid = 512, dedicated = 64, look = 2, quiet = 1, slack = 3, half_cols = 0, first_window = 1, wbias = 4, xhalf = 1, chainq = 0, cboost = 12, panel_dma = 1;
+    int min = 256, max = 32768;  // columns from / up to which the default implementation is the persistent launch (chol_blocked.hip)
+    int chain = 0, slack_chain = 0, win = 0, pstream = 0, srows = 0;  // 0: by matrix size
+    int shalf = -1, shalf_head = -1, head = -1, tail = -1, reserve = -1, tail_half = -1, tail_half_w = -1, xchain = -1, quiet_tail = -1;  // < 0: by matrix size
+    int tfull = -1;  // -1: by matrix size; any other negative value: every panel tile as two halves
+};
+}  // namespace mega
 // job tables of the persistent factorisation for one shape (chol_mega.hip), device resident
 struct MegaTables {
     int nt, mt;
-    long key, key2 = 0;
+    mega::TableParams params;  // what the tables were built for: a launch finds its set by nt, mt and these
     void *block, *jobs, *wq;
     int npanel, nbulk, nchainjobs, nwin;
     unsigned long long stamp;
+};
+// per-call facts of the tall factorisation (potrf_blocked_tall, potrf_mega_tall)
+struct PotrfOpts {
+    int impl = 0;             // 0: by the context's option and the size; 2: the host-driven launches; 3: the persistent launch
+    bool any_size = false;    // impl 3 below mega.min columns too (potrf_lower's explicit request; the context's own option honours mega.min)
+    int xreal = 0;            // > 0: only so many of the rows below the square are non-zero (the fit's right-hand sides)
+    bool info_clean = false;  // the caller has zeroed *dinfo on the same stream already
+};
+// per-call hints of an evaluation (eval_model, eval_fused)
+struct EvalHints {
+    bool population = false;         // a population sweep of the PS solver (values only): eval_nsplit may split small models there
+    bool check_call = false;         // the residual check's evaluation at the model's own sites: eval_nsplit keeps the pre-round-5 rule for it (batch.hip does the same)
+    const double *pre_xq = nullptr;  // the PS solver's next population already centred / padded in the evaluation's own query buffers (eval_fused skips its centring launch when they are these)
 };
 }  // namespace mrbf
 
@@ -69,9 +115,7 @@ struct mrbf_ctx {
     hipStream_t bulk_stream = nullptr;   // CU-masked stream for the aggregated trailing updates: leaves CUs free for the panel chain
     int bulk_masked = 0;
     int bulk_grid = 384;  // > 0: cap on the workgroups of a bulk trailing update (persistent tile loop)
-    // persistent factorisation (chol_mega.hip): cached job tables + launch geometry
-    int mega_nt = 0, mega_mt = 0, mega_npanel = 0, mega_nbulk = 0, mega_nwin = 0, mega_nchainjobs = 0;
-    int mega_grid = 512, mega_dedicated = 64, mega_look = 2, mega_min = 256, mega_max = 32768, mega_quiet = 1, mega_chain = 0, mega_slack = 3, mega_slack_chain = 0, mega_tab_slack = -1, mega_half_cols = 0, mega_first_window = 1, mega_win = 0, mega_wbias = 4, mega_pstream = 0, mega_srows = 0;  // chain, slack_chain, srows: 0 = by matrix size (potrf_mega_tall)
+    mrbf::mega::Knobs mega;  // persistent factorisation (chol_mega.hip): the schedule's overrides
     std::string err;
     std::vector<mrbf::Buf> model_pool;  // released model blocks, reused by the next model of similar size (hipMalloc/hipFree cost
                                         // ~0.1-0.3 ms each and serialise across host threads)
@@ -98,16 +142,11 @@ struct mrbf_ctx {
     };
     std::vector<PinOut> pin_out;
     unsigned long long *hpin = nullptr;  // 64 pinned host words: the small read-backs of a fit (flags, shift, device clock) land here in one round trip
-    int mega_info_clean = 0;  // the caller of the tall factorisation has zeroed *dinfo on the same stream already
-    int mega_xreal = 0;  // > 0: the caller of the tall factorisation knows that only so many of the rows below the square are non-zero (the fit's right-hand sides)
     float last_device_ms = 0.f;
     int slow_launches = 0;
     int small_nc = 4;  // 1 after a cluster failure on this context (XCD placement, or a result that one workgroup does not reproduce)
     int small_cluster_ok = 0;    // the device is what the clusters' visibility argument assumes: gfx950, 8 XCDs x 32 CUs (context.hip)
     int small_timeouts = 0;      // barrier time-outs of clustered launches in a row (three: clusters off for this context)
-    const double *eval_pre_xq = nullptr;  // the PS solver's next population already centred / padded in the evaluation's own query buffers (eval_fused skips its centring launch when they are these)
-    int eval_population = 0;     // set around the PS solver's population sweeps (values only): eval_nsplit may split small models there
-    int eval_check_call = 0;     // set around the residual check's evaluation at the model's own sites: eval_nsplit keeps the pre-round-5 rule for it (batch.hip does the same)
     int live_models = 0, live_round4 = 0;  // handles created through this context and not yet released (MRBF_OPT_LIVE_HANDLES)
     unsigned ps_rank_epoch = 0;  // launches of the PS ranking's wave kernel so far (part of the tag its exchanged records carry)
     int ps_multi_off = 0;        // the several-workgroup PS ranking timed out on this context (a device shared with other work): one workgroup per run from then on
@@ -228,8 +267,11 @@ int launch_projection_small(mrbf_ctx *ctx, const mrbf_model *M, const double *Wp
                             double *v0);
 // eval.hip
 int eval_model(mrbf_ctx *ctx, const mrbf_model *M, int64_t m, const double *Xdev, double *vals_dev, double *jac_dev,
-               mrbf_eval_info *info);
-// chol.hip
+               mrbf_eval_info *info, EvalHints hints = {});
+// chol_blocked.hip (the tall factorisation; chol_mega.hip: the same as one persistent launch) / chol.hip
+int potrf_blocked_tall(mrbf_ctx *ctx, int64_t ncols, int64_t mrows, double *A, int64_t lda, int *dinfo, double *linv_all, PotrfOpts opt = {});
+int potrf_mega_tall(mrbf_ctx *ctx, int64_t ncols, int64_t mrows, double *A, int64_t lda, int *dinfo, double *linv_all, PotrfOpts opt = {});
+mega::Knobs mega_knobs_from_env();  // chol_mega.hip: the one place that reads the schedule's switches
 int potrf_lower(mrbf_ctx *ctx, int impl, int64_t n, double *A, int64_t lda, int *info_host);
 // solve.hip
 int fit_model(mrbf_ctx *ctx, mrbf_model *M, const double *Ydev, mrbf_fit_info *info);

@@ -815,7 +815,7 @@ __global__ void center_pad_batch_kernel(const EvalDesc *__restrict__ many, int D
     if (lane == 0) E.xsq[row] = s;
 }
 
-int eval_nsplit(const mrbf_ctx *ctx, int64_t m, int ntiles, bool check_call) {
+int eval_nsplit(const mrbf_ctx *ctx, int64_t m, int ntiles, bool check_call, bool population) {
     const int64_t mpad = round_up(m, EQ);
     // Split the centre range so that the grid fills the resident workgroup slots (2 per CU) in whole rounds: the cost of a
     // split count is (rounds of workgroups) x (tiles per workgroup) plus the combine pass, which reads one partial per split.
@@ -834,13 +834,13 @@ int eval_nsplit(const mrbf_ctx *ctx, int64_t m, int ntiles, bool check_call) {
     // splitting them cost C4 1.6 % (19 540 against 19 870 problems/s, three alternating runs); the single fit's check follows the same rule.
     const bool small_batch = !check_call && qtiles * 8 <= slots;
     if (ntiles >= 4 && ntiles <= 8 && small_split > 1 && small_batch) return std::min(small_split, ntiles);
-    // the PS solver's populations (ctx->eval_population, values only): a query batch that fills less than half of the workgroup slots
+    // the PS solver's populations (`population`, values only): a query batch that fills less than half of the workgroup slots
     // (round 6: the ideal-point populations of a step at d = 128, 5160 points on n = 257 sites = 81 unsplit workgroups on 256 CUs, 40 us
     // per generation) takes one tile per workgroup + the combine pass, which for values reads a few bytes per point.  Only there: the
     // API's own calls keep ONE rule for values and Jacobians (a values-only call and a call with Jacobians return the same bits, and so
     // does a member of a batch: tests/test_gpu_configs.py), and C4's batches fill the chip by their number.
     static const int vals_split = mrbf_env("MRBF_EVAL_NSPLIT_VALS") ? atoi(mrbf_env("MRBF_EVAL_NSPLIT_VALS")) : 1;
-    if (ctx->eval_population && vals_split && !check_call && ntiles >= 4 && ntiles <= 8 && qtiles * 2 <= slots) return (int)std::min<int64_t>(ntiles, slots / qtiles);
+    if (population && vals_split && !check_call && ntiles >= 4 && ntiles <= 8 && qtiles * 2 <= slots) return (int)std::min<int64_t>(ntiles, slots / qtiles);
     if (ntiles <= 8) return 1;
     static const double comb_small = mrbf_env("MRBF_EVAL_COMB_SMALL") ? atof(mrbf_env("MRBF_EVAL_COMB_SMALL")) : 0.1;
     int nsplit = 1;
@@ -1030,7 +1030,7 @@ int eval_fused_batch(mrbf_ctx *ctx, const KP &kp, int D, int k, bool want_jac, c
     return run_passes(ctx, kp, D, k, want_jac, max_split == 1, grid, cgrid, host_descs[0], dev_descs);
 }
 
-int eval_fused(mrbf_ctx *ctx, const mrbf_model *M, int64_t m, const double *X, double *vals, double *jac, mrbf_eval_info *info) {
+int eval_fused(mrbf_ctx *ctx, const mrbf_model *M, int64_t m, const double *X, double *vals, double *jac, mrbf_eval_info *info, EvalHints hints) {
     const int d = M->d, k = M->k, q = M->q;
     const int D = (M->dpad <= 64) ? 64 : (M->dpad <= 128 ? 128 : 256);
     if (M->dpad > 256) return fail(ctx, MRBF_EHIP, "eval_fused supports d <= 256");
@@ -1038,7 +1038,7 @@ int eval_fused(mrbf_ctx *ctx, const mrbf_model *M, int64_t m, const double *X, d
     const int64_t mpad = round_up(m, EQ);
     // (n = 2d + 1 = 257 sites are five tiles, not the six of the 128-padded storage: a sixth of a C4 evaluation)
     const int ntiles = (int)((M->n + EC - 1) / EC);
-    const int nsplit = eval_nsplit(ctx, m, ntiles, ctx->eval_check_call != 0);
+    const int nsplit = eval_nsplit(ctx, m, ntiles, hints.check_call, hints.population);
     const int KO = outputs_per_pass(k, D, jac != nullptr);
     EvalDesc E;
     std::memset(&E, 0, sizeof(E));
@@ -1072,7 +1072,7 @@ int eval_fused(mrbf_ctx *ctx, const mrbf_model *M, int64_t m, const double *X, d
     if (timing) MRBF_HIP(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
     // (the PS solver's breeding kernel writes its offspring centred and padded straight into these buffers -- same arithmetic as the
     //  centring kernel, one launch per generation less; any other caller, or a buffer that moved, takes the launch)
-    if (!(ctx->eval_pre_xq && ctx->eval_pre_xq == E.Xq)) MRBF_TRY(launch_center_pad(ctx, X, m, d, M->mean, nullptr, E.Xq, mpad, D, E.xsq));
+    if (!(hints.pre_xq && hints.pre_xq == E.Xq)) MRBF_TRY(launch_center_pad(ctx, X, m, d, M->mean, nullptr, E.Xq, mpad, D, E.xsq));
     dim3 grid((unsigned)(mpad / EQ), (unsigned)nsplit);
     MRBF_TRY(run_passes(ctx, M->kp, D, k, jac != nullptr, nsplit == 1, grid, dim3((unsigned)m), E, nullptr));
     if (timing) {

@@ -26,9 +26,6 @@
 
 namespace mrbf {
 
-int eval_model(mrbf_ctx *ctx, const mrbf_model *M, int64_t m, const double *Xdev, double *vals_dev, double *jac_dev,
-               mrbf_eval_info *info);
-
 namespace ps {
 
 constexpr int MAXLAM = 7168;   // population limit: the ranking keeps one run's records in one workgroup's LDS
@@ -1903,13 +1900,10 @@ extern "C" int32_t mrbf_ps_step_problem(mrbf_ctx *ctx, const mrbf_ps_problem *pr
         const unsigned wave_blocks = (unsigned)((a.rows + 3) / 4);
         for (int g = 0; g < max_gens; ++g) {
             a.gen = g;
-            ctx->eval_population = 1;
-            ctx->eval_pre_xq = (g > 0 && a.Xq) ? a.Xq : nullptr;  // (generation 0 comes from ps_init_kernel: centred by the evaluation's own launch)
-            int erc = 0;
-            for (int j = 0; j < P.nmodels && !erc; ++j) erc = eval_model(ctx, P.models[j], a.rows, a.Xeval, const_cast<double *>(a.F[j]), nullptr, nullptr);
-            ctx->eval_population = 0;
-            ctx->eval_pre_xq = nullptr;
-            MRBF_TRY(erc);
+            EvalHints hints;
+            hints.population = true;
+            hints.pre_xq = (g > 0 && a.Xq) ? a.Xq : nullptr;  // (generation 0 comes from ps_init_kernel: centred by the evaluation's own launch)
+            for (int j = 0; j < P.nmodels; ++j) MRBF_TRY(eval_model(ctx, P.models[j], a.rows, a.Xeval, const_cast<double *>(a.F[j]), nullptr, nullptr, hints));
             if (!a.score_fused) hipLaunchKernelGGL(ps_score_kernel, dim3(wave_blocks), dim3(256), 0, ctx->stream, a);
             hipLaunchKernelGGL(ps_rank_kernel, dim3((unsigned)a.nruns), dim3(rank_threads), shm, ctx->stream, a, multi ? 1 : 0, rw);
             if (multi) {

@@ -322,7 +322,6 @@ static int fit_minnorm(mrbf_ctx *ctx, mrbf_model *M, const double *Y, mrbf_fit_i
 }
 
 // ---- Cholesky paths ------------------------------------------------------------------------------
-int potrf_blocked_tall(mrbf_ctx *ctx, int64_t ncols, int64_t mrows, double *A, int64_t lda, int *dinfo, double *linv_all);
 int backsolve_blocked(mrbf_ctx *ctx, int64_t npad, const double *L, int64_t lda, const double *linv_all, double *Y, int64_t ldy, int k);
 int backsolve_persistent(mrbf_ctx *ctx, int64_t npad, const double *L, int64_t lda, const double *linv_all, double *Y, int64_t ldy, int k,
                          int *status);  // backsolve.hip
@@ -638,14 +637,18 @@ __global__ __launch_bounds__(256) void tail_apply_kernel(const double *__restric
 }
 
 // returns 0 with *not_pd = 1 when a factorisation met a non-positive pivot (caller may retry with LU), and 0 with *gave_up = 1
-// when the persistent factorisation abandoned a dependency (caller re-runs this function with the host-driven factorisation)
-static int fit_chol(mrbf_ctx *ctx, mrbf_model *M, const double *Y, mrbf_fit_info *info, int *not_pd, int *gave_up) {
+// when the persistent factorisation abandoned a dependency (caller re-runs this function with the host-driven factorisation, impl 2;
+// impl 0: the factorisation the context's option names)
+static int fit_chol(mrbf_ctx *ctx, mrbf_model *M, const double *Y, mrbf_fit_info *info, int *not_pd, int *gave_up, int impl = 0) {
     const int64_t n = M->n, npad = M->npad;
     const int k = M->k, q = M->q, d = M->d;
     const double one = 1.0, mhalf = -0.5;
     *not_pd = 0;
     *gave_up = 0;
-    const bool builtin = ctx->chol_impl != 1;
+    if (impl == 0) impl = ctx->chol_impl;
+    const bool builtin = impl != 1;
+    PotrfOpts popt;
+    popt.impl = impl;
     const int xt = builtin ? (int)round_up(k, 128) : 0;  // extra row tiles: right-hand sides ride along the factorisation
     const int64_t ld = npad + xt;
     double *Phi, *B;
@@ -698,7 +701,7 @@ static int fit_chol(mrbf_ctx *ctx, mrbf_model *M, const double *Y, mrbf_fit_info
             MRBF_TRY(launch_pad_identity(ctx, Tall, d, dq, lt));
             // (one diagonal block: its inverse is kept for the tail coefficients of the solve)
             if (dq == 128) MRBF_TRY(get_buf(ctx, S_QR_INV, (size_t)128 * 128, &LxInv));
-            MRBF_TRY(potrf_blocked_tall(ctx, dq, lt, Tall, lt, dinfo + 1, LxInv));  // flag read back with the main one
+            MRBF_TRY(potrf_blocked_tall(ctx, dq, lt, Tall, lt, dinfo + 1, LxInv, popt));  // flag read back with the main one
         }
         if (!tailq) hipLaunchKernelGGL(build_q1_kernel, dim3(nblk(npad * q)), dim3(256), 0, ctx->stream, Tall, lt, dq, n, npad, q, Q1);
         if (!fused) MRBF_HIP(ctx, hipMemsetAsync(Wm, 0, (size_t)npad * q * sizeof(double), ctx->stream));
@@ -759,12 +762,9 @@ static int fit_chol(mrbf_ctx *ctx, mrbf_model *M, const double *Y, mrbf_fit_info
         MRBF_TRY(get_buf(ctx, S_CHOL_WS, (size_t)npad * 128, &linv_all));
         MRBF_TRY(launch_pad_identity(ctx, Phi, n, npad, ld));
         if (q == 0) hipLaunchKernelGGL(set_rhs_rows_kernel, dim3(nblk(npad * xt)), dim3(256), 0, ctx->stream, Phi, ld, npad, xt, B, k);
-        ctx->mega_xreal = k;  // (rows k .. xt - 1 of the extra block row are zero: the persistent factorisation skips their half tiles)
-        ctx->mega_info_clean = 1;  // (dinfo[0 .. 3] were zeroed at the top of this function; nothing has written dinfo[0] since)
-        const int rc_potrf = potrf_blocked_tall(ctx, npad, npad + xt, Phi, ld, dinfo, linv_all);
-        ctx->mega_xreal = 0;
-        ctx->mega_info_clean = 0;
-        if (rc_potrf != 0) return rc_potrf;
+        popt.xreal = k;  // (rows k .. xt - 1 of the extra block row are zero: the persistent factorisation skips their half tiles)
+        popt.info_clean = true;  // (dinfo[0 .. 3] were zeroed at the top of this function; nothing has written dinfo[0] since)
+        MRBF_TRY(potrf_blocked_tall(ctx, npad, npad + xt, Phi, ld, dinfo, linv_all, popt));
         MRBF_HIP(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
     } else {
         int *dpot;
@@ -1040,10 +1040,9 @@ static int fit_check_enqueue(mrbf_ctx *ctx, mrbf_model *M, const double *Y, doub
     MRBF_TRY(get_buf(ctx, S_STAGE_D, (size_t)n * k, &V));
     MRBF_TRY(get_buf(ctx, S_CHECK_SCAL, (size_t)8, &scal));
     MRBF_HIP(ctx, hipEventRecord(e0, ctx->stream));
-    ctx->eval_check_call = 1;  // (the residual check keeps the split rule its batch twin uses: eval_nsplit)
-    const int rc_eval = eval_model(ctx, M, n, M->C, V, nullptr, nullptr);
-    ctx->eval_check_call = 0;
-    if (rc_eval != 0) return rc_eval;
+    EvalHints hints;
+    hints.check_call = true;  // (the residual check keeps the split rule its batch twin uses: eval_nsplit)
+    MRBF_TRY(eval_model(ctx, M, n, M->C, V, nullptr, nullptr, hints));
     hipLaunchKernelGGL(residual_kernel, dim3(1), dim3(256), 0, ctx->stream, V, Y, n * k, scal);
     if (q > 0) {
         double *Pi, *T;
@@ -1105,13 +1104,9 @@ int fit_model(mrbf_ctx *ctx, mrbf_model *M, const double *Y, mrbf_fit_info *info
         int not_pd = 0, gave_up = 0;
         MRBF_TRY(fit_chol(ctx, M, Y, info, &not_pd, &gave_up));
         if (gave_up) {
-            // same call, same GPU: re-assemble and factor with the host-driven blocked Cholesky (chol_impl 2)
-            const int saved = ctx->chol_impl;
-            ctx->chol_impl = 2;
+            // same call, same GPU: re-assemble and factor with the host-driven blocked Cholesky (impl 2)
             info->fallbacks |= MRBF_FB_CHOL_HOST_DRIVEN;
-            const int rc2 = fit_chol(ctx, M, Y, info, &not_pd, &gave_up);
-            ctx->chol_impl = saved;
-            if (rc2 != 0) return rc2;
+            MRBF_TRY(fit_chol(ctx, M, Y, info, &not_pd, &gave_up, 2));
             if (gave_up) return fail(ctx, MRBF_EHIP, "host-driven Cholesky reported a give-up code (0x%x)", info->giveup_code);
         }
         if (not_pd) {

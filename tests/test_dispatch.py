@@ -303,8 +303,9 @@ def test_mega_job_tables_are_consistent():
     lib = _lib.load()
     out = (ctypes.c_int64 * 6)()
     seen = {}
-    # (nt, mt, slack, slack_chain, first, win, srows, half_cols): potrf_mega_tall's choices for n = 256 .. 16384 (+1 row tile of
-    # right-hand sides), and corner cases: one block column, more streamed rows than rows, no slack beyond one
+    # (nt, mt, slack, slack_chain, first, win, srows, half_cols): hand-picked valid parameter sets near what the launcher used for
+    # n = 256 .. 16384 in round 2 (+1 row tile of right-hand sides) -- not its choices today: test_mega_default_plan checks those --
+    # and corner cases: one block column, more streamed rows than rows, no slack beyond one
     cases = [(2, 3, 3, 6, 1, 4, 5, 0), (16, 17, 3, 6, 1, 4, 5, 0), (48, 49, 3, 6, 1, 4, 5, 0), (64, 65, 3, 7, 1, 6, 3, 0), (96, 97, 3, 7, 1, 8, 3, 0),
              (128, 129, 3, 6, 1, 8, 2, 0), (1, 1, 1, 1, 1, 1, 0, 0), (1, 2, 3, 6, 1, 4, 5, 0), (5, 9, 1, 1, 1, 1, 7, 2), (33, 33, 2, 2, 4, 4, 0, 3),
              (20, 24, 3, 9, 2, 5, 2, 1)]
@@ -327,7 +328,7 @@ def test_mega_job_tables_are_consistent():
     assert lib.mrbf_debug_mega_tables(4, 5, 3, 6, 5, 4, 5, 0, out) == -3
     assert lib.mrbf_debug_mega_tables(4, 5, 3, 6, 1, 4, 5, 0, None) == -9
     # round-4 options (per-column streamed rows at the edges, 64-row bulk halves in the last block columns, chain tiles' queues):
-    # the defaults potrf_mega_tall picks for n = 4096 .. 16384, every option alone, all together, and tails longer than the matrix
+    # parameter sets near the launcher's for n = 4096 .. 16384, every option alone, all together, and tails longer than the matrix
     opt_cases = [((32, 33, 3, 6, 1, 4, 5, 0), (0, 16, 20, 0, 0)), ((64, 65, 3, 7, 1, 6, 3, 0), (0, 16, 20, 0, 0)), ((96, 97, 3, 7, 1, 8, 3, 0), (0, 16, 20, 0, 0)),
                  ((128, 129, 3, 6, 1, 8, 2, 0), (0, 16, 20, 0, 0)), ((64, 65, 3, 7, 1, 6, 3, 0), (8, 0, 0, 0, 0)), ((64, 65, 3, 7, 1, 6, 3, 0), (0, 0, 20, 3, 0)),
                  ((64, 65, 3, 7, 1, 6, 3, 0), (0, 0, 0, 0, 1)), ((64, 65, 3, 7, 1, 6, 3, 2), (6, 24, 28, 2, 1)), ((10, 12, 2, 4, 1, 3, 2, 0), (40, 40, 40, 1, 1)),
@@ -380,3 +381,74 @@ def test_mega_job_tables_are_consistent():
         assert lib.mrbf_debug_mega_tables2(*c, opt, out) == 0 and out[4] == seen[c], c
     assert lib.mrbf_debug_mega_tables2(4, 5, 3, 6, 1, 4, 5, 0, None, out) == -9
     assert lib.mrbf_debug_mega_tables2(4, 5, 3, 6, 1, 4, 5, 0, (ctypes.c_int32 * 5)(0, -1, 0, 0, 0), out) == -9
+
+
+MEGA_PLAN_FIELDS = ["slack", "slack_chain", "first", "win", "srows", "half_cols", "tail_half", "tail_half_w", "chainq",
+                    "head", "tail_c0", "srows_edge", "pstream_edge", "shalf", "sh_head", "sh_tail_c0", "tfull1", "xhalf",
+                    "nchain", "ndedicated", "nreserve", "head_job1", "reserve_job0", "xchain", "quiet_tail", "pstream", "look", "use_quiet",
+                    "wbias", "cboost", "panel_dma", "grid", "srows_max"]  # order of mrbf_debug_mega_plan's out[0..32]
+
+
+def _mega_tables2_args(nt, p):
+    """A plan's table parameters as arguments of mrbf_debug_mega_tables2 (the entry's own packing of its fifth option)."""
+    import ctypes
+
+    tail_cols = nt - p["tail_c0"]
+    assert p["srows_edge"] == max(p["srows"], 5) and p["pstream_edge"] == 2
+    assert (p["head"] == 0 and tail_cols == 0) or p["srows"] < 5          # the entry applies the edge regime only there
+    sh_tail = nt - p["sh_tail_c0"]
+    assert 0 <= p["sh_head"] < 256 and 0 <= sh_tail < 256 and 0 <= p["tfull1"] < 256
+    if p["shalf"] and p["sh_head"] == 0 and p["sh_tail_c0"] == 0:
+        sh_tail = 0                                                          # 0 / 0 = every block column
+    else:
+        assert not p["shalf"] or sh_tail > 0 or p["sh_head"] > 0
+    bits = (p["chainq"] & 1) | (2 if p["shalf"] else 0) | (p["sh_head"] << 2) | (sh_tail << 10) | (p["tfull1"] << 18) | (p["xhalf"] << 26)
+    opt = (ctypes.c_int32 * 5)(p["head"], tail_cols, p["tail_half"], p["tail_half_w"], bits)
+    return (p["slack"], p["slack_chain"], p["first"], p["win"], p["srows"], p["half_cols"], opt)
+
+
+def test_mega_default_plan():
+    """The schedule the persistent factorisation picks by size (chol_mega.hip: plan_for, through the host-only mrbf_debug_mega_plan):
+    valid for EVERY shape up to 256 block columns, and at both sides of every threshold of the size rules exactly what the launcher
+    derived before plan_for existed (tests/golden/mega_plan_defaults.json, recorded on the GPU from that commit)."""
+    import ctypes
+    import json
+
+    from morbit.jl_amd import _lib
+
+    lib = _lib.load()
+    out = (ctypes.c_int64 * 39)()
+    out2 = (ctypes.c_int64 * 6)()
+    for nt in range(1, 257):
+        for mt, xreal in ((nt, 0), (nt + 1, 1), (nt + 1, 64), (nt + 1, 65), (nt + 3, 0)):
+            assert lib.mrbf_debug_mega_plan(nt, mt, xreal, out) == 0, (nt, mt, xreal)
+            p = dict(zip(MEGA_PLAN_FIELDS, list(out)[:33]))
+            npanel, nbulk, nchainjobs, nwin, checksum, bad = list(out)[33:]
+            where = (nt, mt, xreal, p)
+            assert bad == 0, where
+            assert p["nchain"] >= 1 and p["nchain"] + p["ndedicated"] < p["grid"], where
+            assert p["xchain"] == 0 or (1 <= p["xchain"] <= 8 and 8 * p["nchain"] <= p["xchain"] * p["grid"]), where
+            assert p["srows_max"] >= p["srows"] and p["srows_max"] >= (p["srows_edge"] if p["head"] > 0 or p["tail_c0"] < nt else 0), where
+            assert 0 <= p["head_job1"] <= nchainjobs, where
+            assert 0 <= p["reserve_job0"] <= nchainjobs or p["reserve_job0"] == 1 << 30, where
+            assert p["xhalf"] == (1 if mt == nt + 1 and 1 <= xreal <= 64 else 0), where
+            # the same tables through the entry that takes the parameters one by one
+            a = _mega_tables2_args(nt, p)
+            assert lib.mrbf_debug_mega_tables2(nt, mt, *a, out2) == 0, where
+            assert list(out2) == list(out)[33:], where
+    gold = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mega_plan_defaults.json")))["plans"]
+    assert sorted({g["nt"] for g in gold}) == [2, 8, 16, 17, 24, 32, 33, 40, 41, 48, 49, 55, 56, 64, 87, 88, 96, 97, 128, 256]
+    assert len(gold) == 40
+    for g in gold:
+        assert g["mt"] - g["nt"] == (1 if g["xreal"] else 0) and g["xreal"] in (0, 8), g
+        assert lib.mrbf_debug_mega_plan(g["nt"], g["mt"], g["xreal"], out) == 0, g
+        got = dict(zip(MEGA_PLAN_FIELDS, list(out)[:33]))
+        assert got == {k: g[k] for k in MEGA_PLAN_FIELDS}, (g, got)
+        assert list(out)[33:37] == [g["npanel"], g["nbulk"], g["nchainjobs"], g["nwin"]] and out[38] == 0, (g, list(out)[33:])
+        # ... and the job tables are those of the unchanged table entry called with the FIXTURE's parameters
+        assert lib.mrbf_debug_mega_tables2(g["nt"], g["mt"], *_mega_tables2_args(g["nt"], g), out2) == 0, g
+        assert list(out2) == list(out)[33:], g
+    assert lib.mrbf_debug_mega_plan(0, 1, 0, out) == -1
+    assert lib.mrbf_debug_mega_plan(4, 3, 0, out) == -1
+    assert lib.mrbf_debug_mega_plan(4, 5, -1, out) == -3
+    assert lib.mrbf_debug_mega_plan(4, 5, 8, None) == -4
