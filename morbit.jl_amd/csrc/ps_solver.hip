@@ -34,18 +34,17 @@ constexpr int MAXMODELS = 8;   // grouped models of one container
 constexpr int MAXOBJ = 8;
 constexpr int MAXCON = 32;     // modelled (nonlinear) constraint rows
 constexpr int RANK_THREADS = 1024;
-// ranking of a large population on several compute units (ps_rank_sort_kernel): workgroups per run, phases per chunk (= halo width),
-// smallest population that takes this path, longest window (owned part + two halos) of one workgroup
-constexpr int RS_THREADS = 512, RS_W = 16, RS_B = 256, RS_MINLAM = 1024;
-constexpr int RS_MAXWIN = ((MAXLAM + RS_W - 1) / RS_W + 2) + 2 * RS_B;
-constexpr int RS_SYNC = 64;  // sync words per run: [0] arrivals, [1] failure, [2] the run asks for the sort, [3] buffer that holds the result, [4 + c] chunk c moved something
+// ranking of a large population on several compute units (ps_rank_wave_kernel): phases between two no-swap tests (the exit-rule
+// period), smallest population that takes this path, compute units the device must have per run for it (the waves of a run wait for
+// each other, so they have to be resident together)
+constexpr int RS_B = 256, RS_MINLAM = 1024, RS_CUS_PER_RUN = 16;
+constexpr int RS_SYNC = 64;  // sync words per run: [0] arrivals, [1] failure, [2] the run asks for the phases (1) / the counted sort (2), [3] free, [4 + c] chunk c moved something
 
-struct RankWs {  // device work space of the multi-workgroup ranking, run r at offset r * MAXLAM (r * RS_SYNC)
-    double *f[2], *phi[2];
-    int *idx[2];
+struct RankWs {  // device work space of the several-compute-unit ranking, run r at offset r * MAXLAM (r * RS_SYNC)
+    double *f[2];  // ps_rank_wave_kernel's two exchange buffers (64-bit records)
+    int *idx;      // the order it found, for the finishing launch
     int *sync;
-    int *cnt;  // ps_rank_wave_kernel's keys: per run MAXLAM counts for f, MAXLAM for phi
-    int count_plain;  // ps_rank_prep_kernel is part of the launch sequence: a generation without violations is ranked by counting there
+    int *cnt;      // its keys: per run MAXLAM counts for f, MAXLAM for phi
 };
 
 struct Run {  // one (mu, lambda) run; all pointers into device arenas
@@ -86,8 +85,18 @@ struct Args {
     unsigned long long seed;
     double xtol_rel;
     int gen;
-    int dbg;  // experiments (MRBF_PS_DBG): 128 the plain sort as one pair per thread through LDS (the form before round 6), 64 the multi-workgroup ranking gives up at once (fallback test), 1 no ranking, 2 no breeding, 4 transposition phases also when a sort would do, 8 t stays a free
-              // variable (no repair), 16 uniform start population
+    int dbg;  // Dbg bits (MRBF_PS_DBG, mrbf_debug_ps_rank)
+};
+// Args::dbg: each bit makes a population take a live path that its size or its values would not take by default, so that the tests
+// can put the same generation through both and compare
+enum Dbg : int {
+    DBG_PHASES = 4,          // transposition phases also when no individual violates anything (default: the plain sort / the counted sort)
+    DBG_GIVE_UP = 64,        // ps_rank_wave_kernel gives up at once, as after a counter time-out: the finishing launch runs the phases itself
+    DBG_SORT_PAIRS = 128,    // plain sort as one pair per thread through LDS (default: a run much smaller than the launch's largest)
+    DBG_NO_SELECT = 256,     // plain sort of the whole population (default below 8 elements per thread: no parent selection)
+    DBG_SELECT = 512,        // parent selection also below 8 elements per thread
+    DBG_PHASE_PAIRS = 2048,  // populations below RS_MINLAM: phases as one pair per thread through LDS (default: a generation with a NaN, the larger populations' fallback)
+    DBG_ALL = DBG_PHASES | DBG_GIVE_UP | DBG_SORT_PAIRS | DBG_NO_SELECT | DBG_SELECT | DBG_PHASE_PAIRS
 };
 
 // ---- Philox 4x32-10 ---------------------------------------------------------------------------------------------
@@ -141,7 +150,7 @@ __global__ __launch_bounds__(256) void ps_init_kernel(Args a, const double *xn, 
         if (i == 0 || (i == 1 && R.kind == 1)) {
             v = (R.kind == 1) ? (j == 0 ? (i == 0 ? t0 : 0.0) : xn[j - 1]) : xn[j];
             v = fmin(fmax(v, lo), hi);
-        } else if ((i & 1) && !(a.dbg & 16)) {
+        } else if (i & 1) {
             // every second individual is a mutation of the start point with a scale from 1/4 of the box down to 2^-11 of it (NLopt's
             // ISRES starts its whole population at x0 too): at d >= 64 a uniform population holds no point that improves every
             // objective at once, i.e. no feasible chi with t < 0, and the run ended where it began (omega = 0 at d = 64 .. 256)
@@ -183,17 +192,15 @@ __device__ __forceinline__ void score_row(const Args &a, const Run &R, int i, in
             phi = 0.0;
         } else {
             double t = R.X[a.gen & 1][(size_t)i * R.nvar];
-            if (!(a.dbg & 8)) {
-                // the subproblem is min_x max_l (m_l(x) - m_l(x_n)) / r_l in disguise: the best t an x admits is known once x has been
-                // evaluated, so the individual carries THAT t (pulled a hair towards 0 so that rounding cannot make it infeasible);
-                // an x that worsens some objective keeps t = 0 and is ranked by its violation
-                double ts = -INFINITY;
-                for (int l = 0; l < a.nobj; ++l)
-                    ts = fmax(ts, (a.F[a.obj_model[l]][(size_t)row * a.kf[a.obj_model[l]] + a.obj_col[l]] - a.mx[l]) / a.r[l]);
-                if (ts == ts) {
-                    t = ts <= 0.0 ? fmax(ts * (1.0 - 1e-14), -1.0) : 0.0;
-                    if (lane == 0) R.X[a.gen & 1][(size_t)i * R.nvar] = t;
-                }
+            // the subproblem is min_x max_l (m_l(x) - m_l(x_n)) / r_l in disguise: the best t an x admits is known once x has been
+            // evaluated, so the individual carries THAT t (pulled a hair towards 0 so that rounding cannot make it infeasible);
+            // an x that worsens some objective keeps t = 0 and is ranked by its violation
+            double ts = -INFINITY;
+            for (int l = 0; l < a.nobj; ++l)
+                ts = fmax(ts, (a.F[a.obj_model[l]][(size_t)row * a.kf[a.obj_model[l]] + a.obj_col[l]] - a.mx[l]) / a.r[l]);
+            if (ts == ts) {
+                t = ts <= 0.0 ? fmax(ts * (1.0 - 1e-14), -1.0) : 0.0;
+                if (lane == 0) R.X[a.gen & 1][(size_t)i * R.nvar] = t;
             }
             f = t;
             phi = 0.0;
@@ -426,7 +433,7 @@ __device__ __forceinline__ bool select_parents(const double *__restrict__ fin, i
 
 // ---- one workgroup per run: best so far, stop tests, ranking
 // mode 0: everything in this launch.  Large populations with infeasible individuals (mode 1 / 2): mode 1 does the bookkeeping and, when
-// the transposition phases are due, hands them to ps_rank_sort_kernel (sixteen workgroups per run); mode 2 picks the order up (or runs the
+// the transposition phases are due, hands them to ps_rank_wave_kernel (one wave per 64 individuals); mode 2 picks the order up (or runs the
 // phases here after all if that kernel gave up: it never touches f / phi) and finishes the generation.
 constexpr int RW_OWN = 64, RW_H = 32;
 constexpr int RW_CNT_T = 256;  // individuals per counting workgroup
@@ -502,14 +509,13 @@ __device__ __forceinline__ void rw_block(unsigned &KA, unsigned &KB, unsigned &I
     }
 }
 
-
 // ---- populations below RS_MINLAM: the same phases inside ps_rank_kernel's ONE workgroup (round 6).  The one-pair-per-thread loop
 // through LDS costs 0.35 us per phase (a barrier of the whole workgroup per phase: 99 us per ranking at lam = 280, the largest item of
 // a generation at d = 12); here wave w < ceil(lam / 96) holds a window of 128 two-word records in registers (its own 96, 16 of either
 // neighbour), runs sixteen phases on them without a barrier (rw_block), and the waves exchange their parts through LDS at ONE
 // workgroup barrier per sixteen phases -- which is also where this population size tests for sixteen phases without a swap.  Keys by
 // counting and draws (one chunk of 256 phases at a time) are made by all threads of the workgroup.  Same comparisons, same draws,
-// same exit rule as the loop it replaces (MRBF_PS_DBG 2048 keeps that loop; tests compare both with the NumPy oracle).
+// same exit rule as the loop it replaces (DBG_PHASE_PAIRS keeps that loop; tests compare both with the NumPy oracle).
 constexpr int RWS_OWN = 96, RWS_H = 16;
 __host__ __device__ inline int rws_waves(int lam) { return (lam + RWS_OWN - 1) / RWS_OWN; }
 __host__ __device__ inline int rws_pitch(int lam) { return ((lam / 2 + 64 + 7) / 8) * 8; }
@@ -708,7 +714,7 @@ __global__ __launch_bounds__(RANK_THREADS) void ps_rank_kernel(Args a, int mode,
     // usually so late in a PS run) every comparison of the pairwise rule is decided by (violation, objective) whatever is drawn,
     // and lam phases of the stable transposition sort end in THE sorted order (ties by index): a bitonic network over the padded
     // array reaches the same order in log2(N) (log2(N) + 1) / 2 phases (91 instead of 5160 at lam = 5160).
-    const bool plain_sort = s_infeas == 0 && !(a.dbg & 4);
+    const bool plain_sort = s_infeas == 0 && !(a.dbg & DBG_PHASES);
     if (mode == 1) {
         // Populations of RS_MINLAM and more leave this workgroup here, either way:
         //   sy[2] = 1  violations inside the budget: the transposition phases on several compute units (ps_rank_wave_kernel)
@@ -720,8 +726,8 @@ __global__ __launch_bounds__(RANK_THREADS) void ps_rank_kernel(Args a, int mode,
         bool nan = false;
         if (lam >= RS_MINLAM)
             for (int i = tid; i < lam; i += NT) nan = nan || R.f[i] != R.f[i] || R.phi[i] != R.phi[i];
-        const bool leave = !(a.dbg & 1) && lam >= RS_MINLAM && !__syncthreads_or(nan ? 1 : 0);
-        const int kind = !leave ? 0 : (!plain_sort ? 1 : ((ws.count_plain && !(a.dbg & (128 | 256 | 512))) ? 2 : 0));
+        const bool leave = lam >= RS_MINLAM && !__syncthreads_or(nan ? 1 : 0);
+        const int kind = !leave ? 0 : (!plain_sort ? 1 : (!(a.dbg & (DBG_SORT_PAIRS | DBG_NO_SELECT | DBG_SELECT)) ? 2 : 0));
         for (int i = tid; i < RS_SYNC; i += NT) sy[i] = i == 2 ? kind : 0;
         if (kind) {
             int *cnt = ws.cnt + (size_t)run * 2 * MAXLAM;
@@ -735,20 +741,16 @@ __global__ __launch_bounds__(RANK_THREADS) void ps_rank_kernel(Args a, int mode,
         const int *cnt = ws.cnt + (size_t)run * 2 * MAXLAM;
         for (int i = tid; i < lam; i += NT) sidx[cnt[i]] = i;
         __syncthreads();
-    } else if (mode == 2 && sy[1] == 0) {  // the order found by ps_rank_wave_kernel / ps_rank_sort_kernel
+    } else if (mode == 2 && sy[1] == 0) {  // the order found by ps_rank_wave_kernel
         sidx = (int *)smem;
-        const int *src = ws.idx[sy[3]] + (size_t)run * MAXLAM;
+        const int *src = ws.idx + (size_t)run * MAXLAM;
         for (int i = tid; i < lam; i += NT) sidx[i] = src[i];
         __syncthreads();
-    } else if (a.dbg & 1) {
-        sidx = (int *)smem;
-        for (int i = tid; i < lam; i += NT) sidx[i] = i;
-        __syncthreads();
-    } else if (plain_sort && !(a.dbg & (128 | 256)) && NT >= 256 && mu * 4 <= lam && (npow2(lam) >= 8 * NT || (a.dbg & 512)) &&
+    } else if (plain_sort && !(a.dbg & (DBG_SORT_PAIRS | DBG_NO_SELECT)) && NT >= 256 && mu * 4 <= lam && (npow2(lam) >= 8 * NT || (a.dbg & DBG_SELECT)) &&
                select_parents(R.f, lam, mu, smem, (int *)(smem + npow2(lam)))) {  // (measured: pays from lam > 4096 on -- 135 against 195 us per ranking at
-                                                                                  // lam = 5160; below, its sampling pass costs what the shorter sort saves; dbg 512 forces it)
+                                                                                  // lam = 5160; below, its sampling pass costs what the shorter sort saves; DBG_SELECT forces it)
         sidx = (int *)(smem + npow2(lam));  // (parents found and ranked without sorting the rest: see select_parents)
-    } else if (plain_sort && !(a.dbg & 128) && (npow2(lam) == NT || npow2(lam) == 2 * NT || npow2(lam) == 4 * NT || npow2(lam) == 8 * NT)) {
+    } else if (plain_sort && !(a.dbg & DBG_SORT_PAIRS) && (npow2(lam) == NT || npow2(lam) == 2 * NT || npow2(lam) == 4 * NT || npow2(lam) == 8 * NT)) {
         // (the launch's thread count follows the LARGEST population: N / 2 up to N = 2048, 1024 beyond; a run whose padded size is not
         // 2, 4 or 8 elements per thread -- a much smaller run in the same launch -- takes the one-pair-per-thread form below)
         const int N = npow2(lam);
@@ -763,8 +765,7 @@ __global__ __launch_bounds__(RANK_THREADS) void ps_rank_kernel(Args a, int mode,
         else
             bitonic_regs<8>(R.f, nullptr, lam, N, sf, sidx);
     } else if (plain_sort) {
-        int N = 1;
-        while (N < lam) N <<= 1;
+        const int N = npow2(lam);
         double *sf = smem;      // N keys: violation is 0 or inf here, and inf comes with f = inf
         sidx = (int *)(sf + N);
         for (int i = tid; i < N; i += NT) {
@@ -793,7 +794,7 @@ __global__ __launch_bounds__(RANK_THREADS) void ps_rank_kernel(Args a, int mode,
         // lam phases of odd-even transposition; a pair is compared by f when both are feasible or with probability 0.45, else by
         // the constraint violation (Runarsson & Yao).  The records themselves are swapped; one Philox call feeds four phases of a
         // pair; one barrier per phase.
-        if (lam < RS_MINLAM && !(a.dbg & 2048) && NT >= 64 * rws_waves(lam) && rank_small_waves(a, R, run, smem, sidx)) {
+        if (lam < RS_MINLAM && !(a.dbg & DBG_PHASE_PAIRS) && NT >= 64 * rws_waves(lam) && rank_small_waves(a, R, run, smem, sidx)) {
             // (the order is in sidx: the records stayed in registers -- see rank_small_waves)
         } else {
         double *sf = smem, *sphi = sf + lam;
@@ -808,8 +809,8 @@ __global__ __launch_bounds__(RANK_THREADS) void ps_rank_kernel(Args a, int mode,
         constexpr int PSLOTS = (MAXLAM / 2 + RANK_THREADS - 1) / RANK_THREADS;  // pairs per thread and phase
         // ONE exit rule for a population size, whichever kernel ranks it: with stochastic comparisons a stretch of phases without a
         // swap is not a fixed point (a pair that disagrees on f and phi can still swap on a later draw), so WHERE the no-swap test
-        // sits decides the order that comes out.  Populations of RS_MINLAM and more -- the ones ps_rank_sort_kernel takes, which can
-        // only test at its chunk boundaries -- are tested every RS_B phases here too (this code is also that kernel's fallback after
+        // sits decides the order that comes out.  Populations of RS_MINLAM and more -- the ones ps_rank_wave_kernel takes, whose waves
+        // meet only every RS_B phases -- are tested every RS_B phases here too (this code is also that kernel's fallback after
         // a time-out and the MRBF_PS_MULTI=0 path); smaller ones every sixteen.
         const int quiet = lam >= RS_MINLAM ? RS_B : 16;
         for (int ph0 = 0; ph0 < lam; ph0 += 4) {
@@ -904,132 +905,19 @@ __global__ __launch_bounds__(RANK_THREADS) void ps_rank_kernel(Args a, int mode,
     }
 }
 
-// ---- the transposition phases of one run on RS_W workgroups.  A phase moves information by one position, so a workgroup that loads
-// its part of the array plus RS_B positions on either side can run RS_B phases on its own and its part comes out exactly as if the
-// whole array had been worked on (the halo positions go wrong from the window's edges inwards, one position per phase, and are thrown
-// away); every comparison is a function of (pair, phase, values) -- the Philox counter is the pair and the four-phase group, as in
-// ps_rank_kernel -- so the redundant comparisons in the halos agree with the owner's.  Between chunks the parts are exchanged through
-// global memory (write-through stores, coherent loads: the workgroups sit behind different L2s) and the workgroups of a run meet at a
-// counter.  A chunk in which no workgroup moved anything inside its own part ends the ranking (ps_rank_kernel applies the same test
-// at the same phases for these population sizes: one exit rule, hence one order, whichever kernel runs).  The counter wait is bounded: on a time-out the failure word is set and ps_rank_kernel (mode 2) runs the phases
-// itself -- this kernel never writes f / phi.
-__device__ __forceinline__ unsigned long long rs_clock() { return __builtin_amdgcn_s_memrealtime(); }  // 100 MHz
-__global__ __launch_bounds__(RS_THREADS) void ps_rank_sort_kernel(Args a, RankWs ws) {
-    __shared__ double sf[RS_MAXWIN], sphi[RS_MAXWIN];
-    __shared__ int sidx[RS_MAXWIN];
-    __shared__ int s_sw, s_ok, s_any;
-    const int run = blockIdx.y, w = blockIdx.x, tid = threadIdx.x;
-    const Run &R = a.runs[run];
-    int *const sy = ws.sync + run * RS_SYNC;
-    if (R.stat[1] || sy[2] != 1) return;
-    if (a.dbg & 64) {  // (test switch: give up at once, as after a counter time-out)
-        if (threadIdx.x == 0) __hip_atomic_store(sy + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
-    const int lam = R.lam, gen = a.gen;
-    const int per = ((lam + RS_W - 1) / RS_W + 1) & ~1;  // even: windows start at even positions (a thread keeps its pair slot over both parities)
-    const int s0 = min(lam, w * per), e0 = min(lam, s0 + per);
-    const int ws0 = max(0, s0 - RS_B), we0 = min(lam, e0 + RS_B), wn = we0 - ws0;
-    const size_t ro = (size_t)run * MAXLAM;
-    const int nch = (lam + RS_B - 1) / RS_B;
-    for (int c = 0; c < nch; ++c) {
-        const int sb = c & 1, db = sb ^ 1;
-        for (int i = tid; i < wn; i += RS_THREADS) {
-            const int g = ws0 + i;
-            if (c == 0) {
-                sf[i] = R.f[g];
-                sphi[i] = R.phi[g];
-                sidx[i] = g;
-            } else {
-                sf[i] = __hip_atomic_load(ws.f[sb] + ro + g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                sphi[i] = __hip_atomic_load(ws.phi[sb] + ro + g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                sidx[i] = __hip_atomic_load(ws.idx[sb] + ro + g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-        if (tid == 0) s_sw = 0;
-        __syncthreads();
-        const int ph_end = min(lam, (c + 1) * RS_B);
-        for (int ph0 = c * RS_B; ph0 < ph_end; ph0 += 4) {
-            unsigned c4[4];
-            bool drawn = false;
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) {
-                const int ph = ph0 + q4;
-                if (ph < lam) {
-                    const int j = ws0 + (ph & 1) + 2 * tid;  // (ws0 even)
-                    if (j + 1 < we0 && s0 < e0) {
-                        const int li = j - ws0;
-                        const double fa = sf[li], fb = sf[li + 1], pa = sphi[li], pb = sphi[li + 1];
-                        const int ia = sidx[li], ib = sidx[li + 1];  // (with the keys: a swap then costs no second LDS round trip)
-                        bool by_f = pa == 0.0 && pb == 0.0;
-                        if (!by_f) {
-                            if (!drawn) {
-                                c4[0] = (unsigned)(j >> 1);
-                                c4[1] = (unsigned)ph0;
-                                c4[2] = (unsigned)(gen * 16 + 1);
-                                c4[3] = (unsigned)run;
-                                philox(c4, (unsigned)a.seed, (unsigned)(a.seed >> 32));
-                                drawn = true;
-                            }
-                            by_f = ((double)c4[q4] + 0.5) * (1.0 / 4294967296.0) < 0.45;
-                        }
-                        const bool worse = by_f ? (fa > fb) : (pa > pb);
-                        if (worse) {
-                            sf[li] = fb;
-                            sf[li + 1] = fa;
-                            sphi[li] = pb;
-                            sphi[li + 1] = pa;
-                            sidx[li] = ib;
-                            sidx[li + 1] = ia;
-                            if (j >= s0 && j < e0) s_sw = 1;
-                        }
-                    }
-                }
-                __syncthreads();
-            }
-        }
-        for (int i = tid; i < e0 - s0; i += RS_THREADS) {
-            const int li = s0 - ws0 + i;
-            __hip_atomic_store(ws.f[db] + ro + s0 + i, sf[li], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(ws.phi[db] + ro + s0 + i, sphi[li], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(ws.idx[db] + ro + s0 + i, sidx[li], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's stores have left the CU
-        __syncthreads();
-        if (tid == 0) {
-            if (s_sw) __hip_atomic_fetch_or(sy + 4 + c, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            // arrival = RELEASE (orders the part's stores and the "moved" flag before the count, by the memory model and not only by
-            // the s_waitcnt above), the wait ends with an ACQUIRE load of the same counter before s_any and the next chunk's loads
-            __hip_atomic_fetch_add(sy, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-            const int target = RS_W * (c + 1);
-            const unsigned long long t0 = rs_clock();
-            bool ok = true;
-            while (__hip_atomic_load(sy, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < target) {
-                if (__hip_atomic_load(sy + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0 || rs_clock() - t0 > 500000ull) {  // 5 ms
-                    __hip_atomic_store(sy + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(ws.sync + RS_SYNC * MAXRUNS, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (sticky: the host stops using this kernel)
-                    ok = false;
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(2);
-            }
-            s_ok = ok ? 1 : 0;
-            s_any = __hip_atomic_load(sy + 4 + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __syncthreads();
-        if (!s_ok) return;
-        if (w == 0 && tid == 0) sy[3] = db;  // (the result so far; read by the next kernel in the stream)
-        if (!s_any) return;                  // nothing moved in RS_B phases: ranked under the drawn rules
-    }
-}
-
-// ---- the same phases with one WAVE per part and the records in registers (round 6; ps_rank_sort_kernel above stays as the A/B form,
-// MRBF_PS_MULTI=2).  The workgroup form pays an LDS round trip and a barrier of eight waves per phase (0.32 us: 425 us per ranking at
-// lam = 1320) and works on a window seven times its own part.  Here a wave holds a window of 128 records, two per lane (its own
-// RW_OWN = 64 in the middle, RW_H = 32 of either neighbour on each side), so an even phase is lane-local, an odd phase takes the
-// neighbouring lane's record by DPP (wave_shl / wave_shr), and no phase needs a barrier; after RW_H phases the waves publish their parts
-// (write-through stores of self-describing records: see the kernel) and take the neighbours' halves -- a wave waits for its two
-// neighbours only.  Every RS_B phases all waves of the run meet at the arrival counter for the one exit rule.
+// ---- the transposition phases of large populations on several compute units: one WAVE per part, the records in registers (round 6).
+// A phase moves information by one position, so a wave that holds its part of the array plus RW_H positions on either side can run
+// RW_H phases on its own and its part comes out exactly as if the whole array had been worked on (the halo positions go wrong from the
+// window's edges inwards, one position per phase, and are thrown away); every comparison is a function of (pair, phase, values) --
+// the Philox counter is the pair and the four-phase group, as in ps_rank_kernel -- so the redundant comparisons in the halos agree
+// with the owner's.  A wave holds a window of 128 records, two per lane (its own RW_OWN = 64 in the middle, RW_H = 32 of either
+// neighbour on each side), so an even phase is lane-local, an odd phase takes the neighbouring lane's record by DPP (wave_shl /
+// wave_shr), and no phase needs a barrier (one workgroup per run pays an LDS round trip and a barrier per phase); after RW_H phases
+// the waves publish their parts (write-through stores of self-describing records: see the kernel) and take the neighbours' halves --
+// a wave waits for its two neighbours only.  Every RS_B phases all waves of the run meet at the arrival counter: a chunk in which no
+// wave moved anything inside its own part ends the ranking (ps_rank_kernel applies the same test at the same phases for these
+// population sizes: one exit rule, hence one order, whichever kernel runs).  The waits are bounded: on a time-out the failure word
+// is set and ps_rank_kernel (mode 2) runs the phases itself -- this kernel never writes f / phi.
 // A wave alone on its SIMD issues one instruction every four cycles whatever its kind, so the instruction count of a phase IS its
 // time (measured 0.11 us with records of two doubles + index: 22 vector + 14 scalar instructions).  Two things are therefore taken
 // out of the phases and done beforehand on the whole chip by ps_rank_prep_kernel, since neither depends on the order so far:
@@ -1101,6 +989,7 @@ __global__ __launch_bounds__(256) void ps_rank_prep_kernel(Args a, RankWs ws, u6
     }
 }
 
+__device__ __forceinline__ unsigned long long rs_clock() { return __builtin_amdgcn_s_memrealtime(); }  // 100 MHz
 __global__ __launch_bounds__(64) void ps_rank_wave_kernel(Args a, RankWs ws, const u64 *draws, size_t per_run, unsigned epoch) {
     const int run = blockIdx.y, w = blockIdx.x, lane = threadIdx.x;
     const Run &R = a.runs[run];
@@ -1108,7 +997,7 @@ __global__ __launch_bounds__(64) void ps_rank_wave_kernel(Args a, RankWs ws, con
     if (R.stat[1] || sy[2] != 1) return;
     const int lam = R.lam, nw = rw_waves(lam);
     if (w >= nw) return;
-    if (a.dbg & 64) {  // (test switch: give up at once, as after a counter time-out)
+    if (a.dbg & DBG_GIVE_UP) {  // (test switch: give up at once, as after a counter time-out)
         if (lane == 0) __hip_atomic_store(sy + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return;
     }
@@ -1172,15 +1061,14 @@ __global__ __launch_bounds__(64) void ps_rank_wave_kernel(Args a, RankWs ws, con
             any = __builtin_amdgcn_readfirstlane(any);
             moved = 0;
             if (ok && (!any || blk + 1 == nblk)) {  // nothing moved in RS_B phases (ranked under the drawn rules), or all phases done
-                int *out = ws.idx[0] + ro;          // the order, for the finishing launch
+                int *out = ws.idx + ro;             // the order, for the finishing launch
                 if (ownA) out[gA] = (int)IA;
                 if (ownB) out[gB] = (int)IB;
-                if (w == 0 && lane == 0) sy[3] = 0;
                 return;
             }
         }
         // ---- take the neighbours' halves: poll the records until they carry this block's tag
-        if (ok && !(a.dbg & 1024)) {  // (1024, a timing experiment: no wait for the neighbours -- the result is not a ranking)
+        if (ok) {
             int spins = 0;
             for (;;) {
                 const u64 ra = needA ? __hip_atomic_load(xr[db] + gA, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
@@ -1219,7 +1107,7 @@ __global__ __launch_bounds__(256) void ps_breed_kernel(Args a) {
     const int run = run_of_row(a, row);
     const Run &R = a.runs[run];
     const int gen = a.gen;
-    if (R.stat[3] != gen + 1 || (a.dbg & 2)) return;
+    if (R.stat[3] != gen + 1) return;
     const int n = R.nvar, mu = R.mu, o = row - R.off;
     const double *X = R.X[gen & 1], *S = R.S[gen & 1];
     double *Xn = R.X[(gen + 1) & 1], *Sn = R.S[(gen + 1) & 1];
@@ -1323,26 +1211,52 @@ struct Problem {
 
 }  // namespace ps
 
-// all model outputs at m points (row-major m x nftot) and, optionally (m == 1), the objectives' Jacobian rows
-// work space of the several-compute-unit ranking + the launches of its phases (form 1: one wave per part, ps_rank_wave_kernel, after
-// the draws; form 2: the workgroup form of round 5, ps_rank_sort_kernel)
-// work space of the several-compute-unit ranking + the launches of its phases (form 1: one wave per part, ps_rank_wave_kernel, after
-// the draws and the keys; form 2: the workgroup form of round 5, ps_rank_sort_kernel)
-static int rank_ws_setup(mrbf_ctx *ctx, int maxlam, ps::RankWs &rw, unsigned long long **draws, size_t *draws_per_run) {
+// ---- how the ranking of the runs of one Args is launched: ps_rank_kernel's thread count and dynamic LDS and, on the
+// several-compute-unit path, the work space and the draws.  The step and the test hook both go through these two functions.
+struct RankLaunch {
+    int maxlam = 0, threads = 0;
+    size_t shm = 0;
+    bool several = false;  // populations of RS_MINLAM and more leave ps_rank_kernel's one workgroup (modes 1 / 2 around ps_rank_wave_kernel)
+    ps::RankWs ws{};
+    unsigned long long *draws = nullptr;
+    size_t draws_per_run = 0;
+};
+// once per call, before the first generation (`allow_several`: the caller's say on the several-compute-unit path)
+static int rank_launch_setup(mrbf_ctx *ctx, const ps::Args &a, bool allow_several, RankLaunch &L) {
     using namespace ps;
+    // (populations below RS_MINLAM: room and waves for rank_small_waves -- a wave per 96 individuals, a chunk of draws in LDS;
+    //  over ALL runs of the launch: a small run beside a large one must find its room too)
+    size_t small_need = 0;
+    int small_waves = 0;
+    for (int q = 0; q < a.nruns; ++q) {
+        const int lam = a.runs[q].lam;
+        L.maxlam = std::max(L.maxlam, lam);
+        if (lam < RS_MINLAM) {
+            small_need = std::max(small_need, rws_smem_bytes(lam));
+            small_waves = std::max(small_waves, rws_waves(lam));
+        }
+    }
+    int N = 1;
+    while (N < L.maxlam) N <<= 1;
+    L.shm = std::max(std::max((size_t)20 * L.maxlam, (size_t)12 * N), small_need);
+    // one thread per pair of the largest population (the bitonic network's N / 2 pairs), whole waves, at most RANK_THREADS
+    // (a small population that needs more waves than N / 2 threads hold takes N threads: the plain sort then runs as one element per thread)
+    L.threads = (int)std::min<int64_t>(RANK_THREADS, std::max<int64_t>(64, round_up(N / 2, 64)));
+    if (64 * small_waves > L.threads) L.threads = (int)std::min<int64_t>(RANK_THREADS, std::max<int64_t>(N, 64 * small_waves));
+    MRBF_HIP(ctx, hipFuncSetAttribute((const void *)ps_rank_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.shm));
+    L.several = allow_several && L.maxlam >= RS_MINLAM;
+    if (!L.several) return MRBF_OK;
+    L.draws_per_run = (size_t)((L.maxlam + RW_H - 1) / RW_H) * rw_pitch(L.maxlam);
+    RankWs &rw = L.ws;
     double *wsb;
-    const size_t per_run = (size_t)MAXLAM * 6 + RS_SYNC / 2;  // f, phi twice, idx twice and the two counts (as doubles: 4 x 1/2), sync words
-    *draws_per_run = (size_t)((maxlam + RW_H - 1) / RW_H) * rw_pitch(maxlam);
-    MRBF_TRY(get_buf(ctx, S_PS_RANK, per_run * MAXRUNS + 64 + *draws_per_run * MAXRUNS, &wsb));
+    const size_t per_run = (size_t)MAXLAM * 7 / 2 + RS_SYNC / 2;  // two exchange buffers, the order and the two counts (as doubles: 3 x 1/2), sync words
+    MRBF_TRY(get_buf(ctx, S_PS_RANK, per_run * MAXRUNS + 64 + L.draws_per_run * MAXRUNS, &wsb));
     rw.f[0] = wsb;
     rw.f[1] = rw.f[0] + (size_t)MAXLAM * MAXRUNS;
-    rw.phi[0] = rw.f[1] + (size_t)MAXLAM * MAXRUNS;
-    rw.phi[1] = rw.phi[0] + (size_t)MAXLAM * MAXRUNS;
-    rw.idx[0] = reinterpret_cast<int *>(rw.phi[1] + (size_t)MAXLAM * MAXRUNS);
-    rw.idx[1] = rw.idx[0] + (size_t)MAXLAM * MAXRUNS;
-    rw.cnt = rw.idx[1] + (size_t)MAXLAM * MAXRUNS;
+    rw.idx = reinterpret_cast<int *>(rw.f[1] + (size_t)MAXLAM * MAXRUNS);
+    rw.cnt = rw.idx + (size_t)MAXLAM * MAXRUNS;
     rw.sync = rw.cnt + (size_t)2 * MAXLAM * MAXRUNS;
-    *draws = reinterpret_cast<unsigned long long *>(wsb + per_run * MAXRUNS + 64);
+    L.draws = reinterpret_cast<unsigned long long *>(wsb + per_run * MAXRUNS + 64);
     // ps_rank_wave_kernel's readers accept any word whose bits 16..31 equal the block's tag.  The arena is not cleared when it is
     // handed out, so a word left by earlier work (a double of another buffer, a record of an earlier call whose launch number
     // agrees modulo 256) could pass as a record and carry an individual index beyond lam into the parents' list.  A zero word has
@@ -1351,20 +1265,21 @@ static int rank_ws_setup(mrbf_ctx *ctx, int maxlam, ps::RankWs &rw, unsigned lon
     MRBF_HIP(ctx, hipMemsetAsync(rw.sync + RS_SYNC * MAXRUNS, 0, sizeof(int), ctx->stream));
     return MRBF_OK;
 }
-static void rank_phases_launch(mrbf_ctx *ctx, const ps::Args &a, const ps::RankWs &rw, unsigned long long *draws, size_t draws_per_run, int maxlam, int form,
-                               bool phases_possible) {
+// one generation's ranking: ps_rank_kernel alone (mode 0) or, on the several-compute-unit path, its bookkeeping (mode 1), the draws /
+// keys / counted sort on the whole chip, the transposition phases with one wave per part, and the finishing launch (mode 2)
+static void rank_launch(mrbf_ctx *ctx, const ps::Args &a, const RankLaunch &L, bool phases_possible) {
     using namespace ps;
-    if (form == 2) {
-        hipLaunchKernelGGL(ps_rank_sort_kernel, dim3(RS_W, (unsigned)a.nruns), dim3(RS_THREADS), 0, ctx->stream, a, rw);
-        return;
-    }
-    const int draw_blocks = (int)std::min<size_t>(512, (draws_per_run + 255) / 256);
-    const int count_blocks = ((maxlam + RW_CNT_T - 1) / RW_CNT_T) * rw_jsplit(maxlam);
-    hipLaunchKernelGGL(ps_rank_prep_kernel, dim3((unsigned)(draw_blocks + count_blocks), (unsigned)a.nruns), dim3(256), 0, ctx->stream, a, rw, draws, draws_per_run, draw_blocks);
+    hipLaunchKernelGGL(ps_rank_kernel, dim3((unsigned)a.nruns), dim3(L.threads), L.shm, ctx->stream, a, L.several ? 1 : 0, L.ws);
+    if (!L.several) return;
+    const int draw_blocks = (int)std::min<size_t>(512, (L.draws_per_run + 255) / 256);
+    const int count_blocks = ((L.maxlam + RW_CNT_T - 1) / RW_CNT_T) * rw_jsplit(L.maxlam);
+    hipLaunchKernelGGL(ps_rank_prep_kernel, dim3((unsigned)(draw_blocks + count_blocks), (unsigned)a.nruns), dim3(256), 0, ctx->stream, a, L.ws, L.draws, L.draws_per_run, draw_blocks);
     if (phases_possible)  // (runs without modelled or linear constraints -- ideal-point runs of a box-constrained problem -- never violate anything)
-        hipLaunchKernelGGL(ps_rank_wave_kernel, dim3((unsigned)rw_waves(maxlam), (unsigned)a.nruns), dim3(64), 0, ctx->stream, a, rw, draws, draws_per_run, ++ctx->ps_rank_epoch);
+        hipLaunchKernelGGL(ps_rank_wave_kernel, dim3((unsigned)rw_waves(L.maxlam), (unsigned)a.nruns), dim3(64), 0, ctx->stream, a, L.ws, L.draws, L.draws_per_run, ++ctx->ps_rank_epoch);
+    hipLaunchKernelGGL(ps_rank_kernel, dim3((unsigned)a.nruns), dim3(L.threads), L.shm, ctx->stream, a, 2, L.ws);
 }
 
+// all model outputs at m points (row-major m x nftot) and, optionally (m == 1), the objectives' Jacobian rows
 static int ps_eval_points(mrbf_ctx *ctx, const ps::Problem &P, const double *x_host, int m, std::vector<double> &allF, std::vector<double> *Jobj) {
     const int d = P.d;
     double *dX;
@@ -1809,9 +1724,8 @@ extern "C" int32_t mrbf_ps_step_problem(mrbf_ctx *ctx, const mrbf_ps_problem *pr
     // The evolution strategy is a global method: in d + 1 >= 25 variables it locates a basin, it does not descend into it (with the
     // reference's defaults the step at d = 128 stayed at 7 % of what the subproblem allows).  A tenth of every global budget is
     // therefore kept back for gradient steps from the strategy's best point (ps_descend) -- the evaluations are counted against the
-    // same budget, so the call never evaluates more than the configuration allows.  MRBF_PS_DBG bit 5 (32): the strategy alone.
-    const int dbg_env = mrbf_env("MRBF_PS_DBG") ? atoi(mrbf_env("MRBF_PS_DBG")) : 0;
-    const auto reserve = [&](int budget) { return (dbg_env & 32) || budget < 20 * 13 ? 0 : budget / 10; };
+    // same budget, so the call never evaluates more than the configuration allows.
+    const auto reserve = [&](int budget) { return budget < 20 * 13 ? 0 : budget / 10; };
     const int res_ip = reserve(max_ip), res_ps = opts->max_polish_evals > 0 ? 0 : reserve(max_ps);
     const double xtol = opts->xtol_rel > 0.0 ? opts->xtol_rel : 1e-3;                        // descent.jl:379, :485
 
@@ -1840,41 +1754,20 @@ extern "C" int32_t mrbf_ps_step_problem(mrbf_ctx *ctx, const mrbf_ps_problem *pr
         R.stat = st;
     };
     auto run_batch = [&](Args &a, const double *start, double t0, int max_gens) -> int {
-        int maxlam = 0, maxel = 0;
+        int maxel = 0;
         a.rows = 0;
         for (int q2 = 0; q2 < a.nruns; ++q2) {
             a.rows = std::max(a.rows, a.runs[q2].off + a.runs[q2].lam);
-            maxlam = std::max(maxlam, a.runs[q2].lam);
             maxel = std::max(maxel, a.runs[q2].lam * a.runs[q2].nvar);
         }
-        int N = 1;
-        while (N < maxlam) N <<= 1;
-        // (populations below RS_MINLAM: room and waves for rank_small_waves -- a wave per 96 individuals, a chunk of draws in LDS;
-        //  over ALL runs of the launch: a small run beside a large one must find its room too)
-        size_t small_need = 0;
-        int small_waves = 0;
-        for (int q2 = 0; q2 < a.nruns; ++q2)
-            if (a.runs[q2].lam < RS_MINLAM) {
-                small_need = std::max(small_need, rws_smem_bytes(a.runs[q2].lam));
-                small_waves = std::max(small_waves, rws_waves(a.runs[q2].lam));
-            }
-        const size_t shm = std::max(std::max((size_t)20 * maxlam, (size_t)12 * N), small_need);
-        MRBF_HIP(ctx, hipFuncSetAttribute((const void *)ps_rank_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-        // one thread per pair of the largest population (the bitonic network's N / 2 pairs), whole waves, at most RANK_THREADS
-        // (a small population that needs more waves than N / 2 threads hold takes N threads: the plain sort then runs as one element per thread)
-        int rank_threads = (int)std::min<int64_t>(RANK_THREADS, std::max<int64_t>(64, round_up(N / 2, 64)));
-        if (64 * small_waves > rank_threads) rank_threads = (int)std::min<int64_t>(RANK_THREADS, std::max<int64_t>(N, 64 * small_waves));
-        // large populations: the transposition phases on RS_W workgroups per run (MRBF_PS_MULTI=0: one workgroup as in rounds 3 / 4)
-        RankWs rw{};
-        // (a counter wait that times out -- the workgroups of a run not resident together: a device shared with other work -- costs 5 ms; the
-        // host sees the sticky failure word with the status words, every eight generations, and keeps to one workgroup per run from then on)
-        const int multi_env = mrbf_env("MRBF_PS_MULTI") ? atoi(mrbf_env("MRBF_PS_MULTI")) : 1;  // 0: one workgroup per run; 2: the workgroup form of round 5
-        bool multi = maxlam >= RS_MINLAM && ctx->ncu >= RS_W * a.nruns && !ctx->ps_multi_off && multi_env != 0;
-        unsigned long long *draws = nullptr;
-        size_t draws_per_run = 0;
-        if (multi) MRBF_TRY(rank_ws_setup(ctx, maxlam, rw, &draws, &draws_per_run));
-        rw.count_plain = (multi && multi_env != 2) ? 1 : 0;
-        bool phases_possible = a.ncon + a.nlin_eq + a.nlin_ineq > 0 || (a.dbg & 4);
+        // large populations: the transposition phases with one wave per 64 individuals (MRBF_PS_MULTI=0, read per call: one workgroup per
+        // run as in rounds 3 / 4).  A counter wait that times out -- the waves of a run not resident together: a device shared with other
+        // work -- costs 5 ms; the host sees the sticky failure word with the status words, every eight generations, and keeps to one
+        // workgroup per run from then on.
+        const bool multi_env = !(mrbf_env("MRBF_PS_MULTI") && atoi(mrbf_env("MRBF_PS_MULTI")) == 0);
+        RankLaunch L;
+        MRBF_TRY(rank_launch_setup(ctx, a, ctx->ncu >= RS_CUS_PER_RUN * a.nruns && !ctx->ps_multi_off && multi_env, L));
+        bool phases_possible = a.ncon + a.nlin_eq + a.nlin_ineq > 0 || (a.dbg & DBG_PHASES);
         for (int q2 = 0; q2 < a.nruns; ++q2) phases_possible = phases_possible || a.runs[q2].kind == 1;
         // one model, fused evaluation: the breeding kernel writes the next population centred and padded into the evaluation's own query
         // buffers (a launch per generation less; MRBF_PS_FUSEPAD=0: the evaluation's centring launch).  The buffers are the arena slots the
@@ -1905,19 +1798,15 @@ extern "C" int32_t mrbf_ps_step_problem(mrbf_ctx *ctx, const mrbf_ps_problem *pr
             hints.pre_xq = (g > 0 && a.Xq) ? a.Xq : nullptr;  // (generation 0 comes from ps_init_kernel: centred by the evaluation's own launch)
             for (int j = 0; j < P.nmodels; ++j) MRBF_TRY(eval_model(ctx, P.models[j], a.rows, a.Xeval, const_cast<double *>(a.F[j]), nullptr, nullptr, hints));
             if (!a.score_fused) hipLaunchKernelGGL(ps_score_kernel, dim3(wave_blocks), dim3(256), 0, ctx->stream, a);
-            hipLaunchKernelGGL(ps_rank_kernel, dim3((unsigned)a.nruns), dim3(rank_threads), shm, ctx->stream, a, multi ? 1 : 0, rw);
-            if (multi) {
-                rank_phases_launch(ctx, a, rw, draws, draws_per_run, maxlam, multi_env == 2 ? 2 : 1, phases_possible);
-                hipLaunchKernelGGL(ps_rank_kernel, dim3((unsigned)a.nruns), dim3(rank_threads), shm, ctx->stream, a, 2, rw);
-            }
+            rank_launch(ctx, a, L, phases_possible);
             hipLaunchKernelGGL(ps_breed_kernel, dim3(wave_blocks), dim3(256), 0, ctx->stream, a);
             if ((g & 7) == 7 || g + 1 == max_gens) {  // status words every 8 generations: stop when every run is done
                 MRBF_HIP(ctx, hipMemcpyAsync(hstat.data(), a.runs[0].stat, hstat.size() * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
                 int hfail = 0;
-                if (multi) MRBF_HIP(ctx, hipMemcpyAsync(&hfail, rw.sync + RS_SYNC * MAXRUNS, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+                if (L.several) MRBF_HIP(ctx, hipMemcpyAsync(&hfail, L.ws.sync + RS_SYNC * MAXRUNS, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
                 MRBF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                if (hfail && !(a.dbg & 64)) {
-                    multi = false;
+                if (hfail && !(a.dbg & DBG_GIVE_UP)) {
+                    L.several = false;
                     ctx->ps_multi_off = 1;
                 }
                 bool all = true;
@@ -1964,7 +1853,7 @@ extern "C" int32_t mrbf_ps_step_problem(mrbf_ctx *ctx, const mrbf_ps_problem *pr
     a.eq_tol = P.eq_tol;
     a.Xeval = Xeval;
     a.seed = opts->seed;
-    a.dbg = dbg_env;
+    a.dbg = (mrbf_env("MRBF_PS_DBG") ? atoi(mrbf_env("MRBF_PS_DBG")) : 0) & DBG_ALL;
     a.xtol_rel = xtol;
     // ---- local ideal point: the k single-objective minimisations side by side (descent.jl:404-412)
     if (need_ideal) {
@@ -1990,7 +1879,7 @@ extern "C" int32_t mrbf_ps_step_problem(mrbf_ctx *ctx, const mrbf_ps_problem *pr
             info->evals_ideal += hs[(size_t)4 * l];
             info->generations += hs[(size_t)4 * l + 2];
             const int left = max_ip - hs[(size_t)4 * l];
-            if (found && left >= 13 && !(dbg_env & 32)) {
+            if (found && left >= 13) {
                 ds.emplace_back();
                 Descent &D = ds.back();
                 D.P = &P;
@@ -2044,7 +1933,7 @@ extern "C" int32_t mrbf_ps_step_problem(mrbf_ctx *ctx, const mrbf_ps_problem *pr
             std::vector<int> objs(k);
             for (int l = 0; l < k; ++l) objs[l] = l;
             const bool own = opts->max_polish_evals > 0;
-            const int pbudget = own ? opts->max_polish_evals : ((dbg_env & 32) ? 0 : max_ps - hs[0]);
+            const int pbudget = own ? opts->max_polish_evals : max_ps - hs[0];
             if (pbudget >= 13) {
                 int pe = 0;
                 MRBF_TRY(ps_descend(ctx, P, hlb, hub, objs, mx, r, true, pbudget, xtol, tau, xt, &pe));
@@ -2096,11 +1985,11 @@ extern "C" int32_t mrbf_ps_step(mrbf_ctx *ctx, const mrbf_model *model, const do
 }
 
 // Test hook: ONE ranking of a given generation (objective values f, violations phi; inf = outside the budget) by the kernels of the
-// step above -- impl 0: ps_rank_kernel alone (one workgroup); 1: hand-over to ps_rank_wave_kernel (one wave per 64 individuals) and the
-// finishing launch; 2: the same with the kernel giving up at once (what a counter time-out leaves behind); 6: hand-over to
-// ps_rank_sort_kernel (sixteen workgroups, round 5); 3 - 5: see include/mrbf.h.  order_out[lam] = the
-// individuals in rank order.  Lets the tests put crafted populations (nearly ranked, a few infeasible individuals: the no-swap exit
-// is taken early) through both kernels and compare the orders entry by entry.
+// step above, launched as the step launches them -- impl 0: ps_rank_kernel alone (one workgroup); 1: hand-over to ps_rank_wave_kernel
+// (one wave per 64 individuals) and the finishing launch; 2: the same with the kernel giving up at once (what a counter time-out
+// leaves behind); 3 - 5, 9: see include/mrbf.h.  order_out[lam] = the individuals in rank order.  Lets the tests put crafted
+// populations (nearly ranked, a few infeasible individuals: the no-swap exit is taken early) through both kernels and compare the
+// orders entry by entry.
 extern "C" int32_t mrbf_debug_ps_rank(mrbf_ctx *ctx, int32_t lam, const double *f, const double *phi, uint64_t seed, int32_t gen,
                                       int32_t impl, int32_t *order_out, int32_t *gave_up) {
     if (!ctx) return -1;
@@ -2108,8 +1997,9 @@ extern "C" int32_t mrbf_debug_ps_rank(mrbf_ctx *ctx, int32_t lam, const double *
     if (lam < 2 || lam > MAXLAM) return fail(ctx, -2, "mrbf_debug_ps_rank: lam = %d outside 2..%d", lam, MAXLAM);
     if (!f || !phi) return fail(ctx, -3, "f / phi is NULL");
     if (gen < 0) return fail(ctx, -6, "gen < 0");
-    if (impl < 0 || impl > 9 || impl == 8) return fail(ctx, -7, "impl must be 0 .. 7 or 9");
-    if ((impl == 1 || impl == 2 || impl == 6 || impl == 7) && lam < RS_MINLAM) return fail(ctx, -7, "mrbf_debug_ps_rank: the several-workgroup ranking takes populations >= %d", RS_MINLAM);
+    if (impl < 0 || impl > 9 || (impl >= 6 && impl <= 8)) return fail(ctx, -7, "impl must be 0 .. 5 or 9");
+    const bool several = impl == 1 || impl == 2;
+    if (several && lam < RS_MINLAM) return fail(ctx, -7, "mrbf_debug_ps_rank: the several-workgroup ranking takes populations >= %d", RS_MINLAM);
     if (!order_out) return fail(ctx, -8, "order_out is NULL");
     (void)hipSetDevice(ctx->device);
     double *base;
@@ -2122,7 +2012,7 @@ extern "C" int32_t mrbf_debug_ps_rank(mrbf_ctx *ctx, int32_t lam, const double *
     a.seed = seed;
     a.gen = gen;
     a.xtol_rel = 1e-3;
-    a.dbg = impl == 2 ? 64 : (impl == 3 ? 128 : (impl == 5 ? 256 : (impl == 4 ? 512 : (impl == 7 ? 1024 : (impl == 9 ? 2048 : 0)))));  // (3: the plain sort as one pair per thread through LDS; 5: no parent selection)
+    a.dbg = impl == 2 ? DBG_GIVE_UP : (impl == 3 ? DBG_SORT_PAIRS : (impl == 5 ? DBG_NO_SELECT : (impl == 4 ? DBG_SELECT : (impl == 9 ? DBG_PHASE_PAIRS : 0))));
     R.nvar = 1;
     R.lam = lam;
     R.mu = (impl == 4 || impl == 5) ? (lam + 6) / 7 : lam;  // mu = lam: the whole order comes out; 4 / 5: the step's own mu (order_out beyond it: -1)
@@ -2139,26 +2029,12 @@ extern "C" int32_t mrbf_debug_ps_rank(mrbf_ctx *ctx, int32_t lam, const double *
     MRBF_HIP(ctx, hipMemcpyAsync(R.f, f, (size_t)lam * sizeof(double), hipMemcpyDefault, ctx->stream));
     MRBF_HIP(ctx, hipMemcpyAsync(R.phi, phi, (size_t)lam * sizeof(double), hipMemcpyDefault, ctx->stream));
     MRBF_HIP(ctx, hipMemsetAsync(stat, 0, (size_t)4 * MAXRUNS * sizeof(int), ctx->stream));
-    int N = 1;
-    while (N < lam) N <<= 1;
-    const size_t shm = std::max(std::max((size_t)20 * lam, (size_t)12 * N), lam < RS_MINLAM ? rws_smem_bytes(lam) : (size_t)0);
-    MRBF_HIP(ctx, hipFuncSetAttribute((const void *)ps_rank_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    int rank_threads = (int)std::min<int64_t>(RANK_THREADS, std::max<int64_t>(64, round_up(N / 2, 64)));
-    if (lam < RS_MINLAM && 64 * rws_waves(lam) > rank_threads) rank_threads = (int)std::min<int64_t>(RANK_THREADS, std::max<int64_t>(N, 64 * rws_waves(lam)));
-    RankWs rw{};
-    const bool several = impl == 1 || impl == 2 || impl == 6 || impl == 7;
-    unsigned long long *draws = nullptr;
-    size_t draws_per_run = 0;
-    if (several) MRBF_TRY(rank_ws_setup(ctx, lam, rw, &draws, &draws_per_run));
-    rw.count_plain = (several && impl != 6) ? 1 : 0;
-    hipLaunchKernelGGL(ps_rank_kernel, dim3(1), dim3(rank_threads), shm, ctx->stream, a, several ? 1 : 0, rw);
-    if (several) {
-        rank_phases_launch(ctx, a, rw, draws, draws_per_run, lam, impl == 6 ? 2 : 1, true);
-        hipLaunchKernelGGL(ps_rank_kernel, dim3(1), dim3(rank_threads), shm, ctx->stream, a, 2, rw);
-    }
+    RankLaunch L;
+    MRBF_TRY(rank_launch_setup(ctx, a, several, L));
+    rank_launch(ctx, a, L, true);
     MRBF_HIP(ctx, hipGetLastError());
     int hsync[2] = {0, 0};
-    if (several) MRBF_HIP(ctx, hipMemcpyAsync(hsync, rw.sync, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    if (L.several) MRBF_HIP(ctx, hipMemcpyAsync(hsync, L.ws.sync, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     MRBF_HIP(ctx, hipMemsetAsync(R.order + R.mu, 0xff, (size_t)(lam - R.mu) * sizeof(int), ctx->stream));
     MRBF_HIP(ctx, hipMemcpyAsync(order_out, R.order, (size_t)lam * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     MRBF_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -6,8 +6,8 @@ sweeps with the pairwise rule of Runarsson & Yao (compare by objective when both
 constraint violation).  The device solver runs the PARALLEL form of those sweeps -- lambda odd-even transposition phases with the
 same pairwise rule, draws from a counter-based Philox 4x32-10 keyed by (pair, four-phase group, generation, run) -- and its
 trajectory is by design not NLopt's ("parity unpinned" against NLopt: SURVEY.md section 7, "NLopt owns the loop").  What this file
-pins is that the two device kernels that can rank a population (one workgroup: ps_rank_kernel; sixteen workgroups with halo
-windows: ps_rank_sort_kernel, csrc/ps_solver.hip) compute THE SAME ranking as this plain NumPy loop, including where the no-swap
+pins is that the two device kernels that can rank a population (one workgroup: ps_rank_kernel; one wave per 64 individuals with
+halo windows: ps_rank_wave_kernel, csrc/ps_solver.hip) compute THE SAME ranking as this plain NumPy loop, including where the no-swap
 exit is taken: tests/test_pascoletti_serafini.py compares the orders entry by entry.
 
 Only tests/ may import this module.

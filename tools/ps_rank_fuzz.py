@@ -25,7 +25,7 @@ for case in range(ncase):
         phi = rng.random(lam); nout = int(rng.integers(0, 20)); f[lam - nout:] = np.inf; phi[lam - nout:] = np.inf
     seed, gen = int(rng.integers(0, 2 ** 62)), int(rng.integers(0, 200))
     want, phases = pro.stochastic_rank(f, phi, seed=seed, gen=gen)
-    impls = (0, 1, 6) if lam >= 1024 else (0, 9)
+    impls = (0, 1) if lam >= 1024 else (0, 9)
     for impl in impls:
         order = np.empty(lam, dtype=np.int32)
         ctx.check(ctx.lib.mrbf_debug_ps_rank(ctx.h, lam, _lib.as_ptr(f), _lib.as_ptr(phi), seed, gen, impl, order.ctypes.data_as(_lib.c_ip), None))
