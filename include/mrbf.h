@@ -474,6 +474,33 @@ int32_t mrbf_sd_step(mrbf_ctx *ctx, const mrbf_ps_problem *problem, const double
                      const double *ub, double omega, const double *d, const mrbf_sd_step_options *opts, double *x_plus, double *mx_plus,
                      mrbf_sd_step_info *info);
 
+/* ---- many-start steepest descent: one call for a batch of starts (sd_batch.hip) -----------------------------------------------
+ * get_criticality(::SteepestDescentConfig, ...) (src/descent.jl:187-241) followed by compute_descent_step (descent.jl:243-318) for
+ * n_starts independent starts of one problem -- the reference's Threads.@threads loop over starts
+ * (examples/large_scale_benchmarks.jl:102-109) -- as one chain on the ctx stream with one read-back.  For start p the outputs are,
+ * bit for bit, those of mrbf_sd_criticality(x_p, x_n_p, lb, ub, normalize) -> (omega_p, d_p) and mrbf_sd_step(x_p, x_n_p, delta_p,
+ * lb, ub, omega_p, d_p, opts) chained on start p's container: the roles table and linear rows of `shape` with row p of `models`
+ * (n_starts x shape->n_models handles, start-major; shape->models is ignored).  The starts share d, the model count, every model
+ * slot's output count, the roles and the linear rows; the number of centres and the kernel parameters may differ between starts.
+ * x, x_n: n_starts x d; delta: n_starts; lb / ub (d): the one MOP's global bounds; d_out, x_plus: n_starts x d; mx_plus: n_starts x
+ * n_objectives; every array may be a host or a device pointer, records is host memory; ms_total may be NULL.  The step runs on
+ * whatever the LP returned (NO_OBJECTIVE / INFEASIBLE: d = 0, omega = -Inf, x+ = x_n), except MRBF_SD_GAVE_UP: that start's record
+ * carries the status and its d, x+ and mx+ are NaN (take the reference method for it).  Every start gets a record.  Returns 0 unless
+ * an argument is invalid, -2 (take the reference method) when mrbf_dispatch_sd_batch refuses the shape. */
+typedef struct {
+    int32_t sd_status;              /* MRBF_SD_* of this start's direction LP */
+    int32_t iterations, bound_flips;
+    int32_t branch, loops;          /* as mrbf_sd_step_info */
+    int32_t reserved;
+    double omega;                   /* criticality from the LP (-Inf for NO_OBJECTIVE / INFEASIBLE) */
+    double omega_step;              /* what the step returns: omega, or 0 on the sigma <= min_stepsize branch */
+    double sigma, step_norm;
+} mrbf_sd_batch_record;
+int32_t mrbf_sd_iterate_batch(mrbf_ctx *ctx, int64_t n_starts, const mrbf_ps_problem *shape, const mrbf_model *const *models,
+                              const double *x, const double *x_n, const double *delta, const double *lb, const double *ub,
+                              int32_t normalize, const mrbf_sd_step_options *opts, double *d_out, double *x_plus, double *mx_plus,
+                              mrbf_sd_batch_record *records, float *ms_total);
+
 /* ---- the decision table of the host bindings ---------------------------------------------------------------------------
  * Which implementation a binding (morbit.jl_amd/julia/HipRbf.jl, the Python mirror) takes for one call of Morbit's interface:
  * the device entry point (MRBF_DISPATCH_DEVICE) or Morbit's own method on the same arguments (MRBF_DISPATCH_REFERENCE; Julia:
@@ -500,18 +527,23 @@ int32_t mrbf_sd_step(mrbf_ctx *ctx, const mrbf_ps_problem *problem, const double
  *   mrbf_dispatch_sd_step    compute_descent_step(::SteepestDescentConfig, ...) (src/descent.jl:243-318, _backtrack :150-185,
  *                            utilities.jl:126-294): device iff no objective or modelled-constraint row is foreign, at least one
  *                            device model, 1 <= d <= 4096, 1 <= k <= 64, n_nl + n_lin <= 256 rows and 0 <= max_loops <= 1024.
+ *   mrbf_dispatch_sd_batch   the two calls above for n_starts starts in one (mrbf_sd_iterate_batch): device iff mrbf_dispatch_sd
+ *                            and mrbf_dispatch_sd_step both say so, d <= 256 (the fused evaluation kernels' range) and
+ *                            1 <= n_starts <= 65535 (a grid dimension).
  *   mrbf_dispatch_after      the return code rc of a device entry point (MRBF_ENTRY_*) that means "take the reference method
  *                            for this call" (start set without the tail or rank deficient, limits of the device path) rather
  *                            than an error: 1 = fall back, 0 = rc is what it says. */
 enum { MRBF_DISPATCH_REFERENCE = 0, MRBF_DISPATCH_DEVICE = 1 };
 enum { MRBF_FIT_FULL = 0, MRBF_FIT_FROM_ROUND4 = 1 };
 enum { MRBF_ENTRY_ROUND4 = 1, MRBF_ENTRY_FIT_FROM_ROUND4 = 2, MRBF_ENTRY_PS_STEP = 3, MRBF_ENTRY_BACKTRACK = 4, MRBF_ENTRY_AFFINE = 5,
-       MRBF_ENTRY_SD = 6, MRBF_ENTRY_NORMAL = 7, MRBF_ENTRY_SD_STEP = 8 };
+       MRBF_ENTRY_SD = 6, MRBF_ENTRY_NORMAL = 7, MRBF_ENTRY_SD_STEP = 8, MRBF_ENTRY_SD_BATCH = 9 };
 int32_t mrbf_dispatch_ps(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_sd(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_normal(int32_t d, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_sd_step(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign,
                               int32_t max_loops);
+int32_t mrbf_dispatch_sd_batch(int64_t n_starts, int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints,
+                               int32_t n_lin_constraints, int32_t n_foreign, int32_t max_loops);
 int32_t mrbf_dispatch_backtrack(int32_t n_objective_models, int32_t n_foreign, int32_t outputs_in_order);
 int32_t mrbf_dispatch_affine(int64_t n_candidates, int32_t d);
 int32_t mrbf_dispatch_round4(int64_t n0, int32_t d, int32_t poly_deg, int64_t n_candidates);

@@ -59,6 +59,7 @@ ROLE_NONE, ROLE_EQ, ROLE_INEQ = -1, -2, -3
 DISPATCH_REFERENCE, DISPATCH_DEVICE = 0, 1
 FIT_FULL, FIT_FROM_ROUND4 = 0, 1
 ENTRY_ROUND4, ENTRY_FIT_FROM_ROUND4, ENTRY_PS_STEP, ENTRY_BACKTRACK, ENTRY_AFFINE, ENTRY_SD, ENTRY_NORMAL, ENTRY_SD_STEP = 1, 2, 3, 4, 5, 6, 7, 8
+ENTRY_SD_BATCH = 9
 SD_OK, SD_NO_OBJECTIVE, SD_INFEASIBLE, SD_GAVE_UP = 0, 1, 2, 3
 NS_OK, NS_INFEASIBLE, NS_GAVE_UP = 0, 1, 2
 SD_BRANCH_DELTA, SD_BRANCH_ONE, SD_BRANCH_INTERSECT = 0, 1, 2
@@ -95,6 +96,15 @@ class SdStepOptions(ctypes.Structure):
 class SdStepInfo(ctypes.Structure):
     _fields_ = [("branch", ctypes.c_int32), ("loops", ctypes.c_int32), ("ms_total", ctypes.c_float), ("sigma", ctypes.c_double),
                 ("omega", ctypes.c_double), ("step_norm", ctypes.c_double)]
+
+    def asdict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class SdBatchRecord(ctypes.Structure):
+    _fields_ = [("sd_status", ctypes.c_int32), ("iterations", ctypes.c_int32), ("bound_flips", ctypes.c_int32), ("branch", ctypes.c_int32),
+                ("loops", ctypes.c_int32), ("reserved", ctypes.c_int32), ("omega", ctypes.c_double), ("omega_step", ctypes.c_double),
+                ("sigma", ctypes.c_double), ("step_norm", ctypes.c_double)]
 
     def asdict(self):
         return {f: getattr(self, f) for f, _ in self._fields_}
@@ -174,6 +184,10 @@ SIGNATURES = {
                                           ctypes.c_double, ctypes.c_int32, c_vp, c_vp, ctypes.POINTER(NormalInfo)]),
     "mrbf_sd_step": (ctypes.c_int32, [c_vp, ctypes.POINTER(PsProblem), c_vp, c_vp, ctypes.c_double, c_vp, c_vp, ctypes.c_double, c_vp,
                                       ctypes.POINTER(SdStepOptions), c_vp, c_vp, ctypes.POINTER(SdStepInfo)]),
+    "mrbf_sd_iterate_batch": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.POINTER(PsProblem), ctypes.POINTER(ctypes.c_void_p), c_vp, c_vp, c_vp,
+                                               c_vp, c_vp, ctypes.c_int32, ctypes.POINTER(SdStepOptions), c_vp, c_vp, c_vp,
+                                               ctypes.POINTER(SdBatchRecord), c_fp]),
+    "mrbf_dispatch_sd_batch": (ctypes.c_int32, [ctypes.c_int64] + [ctypes.c_int32] * 7),
     "mrbf_dispatch_ps": (ctypes.c_int32, [ctypes.c_int32] * 6),
     "mrbf_dispatch_sd_step": (ctypes.c_int32, [ctypes.c_int32] * 7),
     "mrbf_dispatch_sd": (ctypes.c_int32, [ctypes.c_int32] * 6),

@@ -47,6 +47,15 @@ int32_t mrbf_dispatch_sd_step(int32_t d, int32_t k, int32_t n_models, int32_t n_
     return (int64_t)n_nl_constraints + n_lin_constraints <= 256 ? MRBF_DISPATCH_DEVICE : MRBF_DISPATCH_REFERENCE;
 }
 
+// many starts in one call (sd_batch.hip): what both single calls take, inside the fused evaluation kernels' range (dpad in {64, 128,
+// 256}) and with the start on a grid dimension
+int32_t mrbf_dispatch_sd_batch(int64_t n_starts, int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints,
+                               int32_t n_foreign, int32_t max_loops) {
+    if (n_starts < 1 || n_starts > 65535 || d > 256) return MRBF_DISPATCH_REFERENCE;
+    if (mrbf_dispatch_sd(d, k, n_models, n_nl_constraints, n_lin_constraints, n_foreign) != MRBF_DISPATCH_DEVICE) return MRBF_DISPATCH_REFERENCE;
+    return mrbf_dispatch_sd_step(d, k, n_models, n_nl_constraints, n_lin_constraints, n_foreign, max_loops);
+}
+
 int32_t mrbf_dispatch_backtrack(int32_t n_objective_models, int32_t n_foreign, int32_t outputs_in_order) {
     return (n_objective_models == 1 && n_foreign == 0 && outputs_in_order != 0) ? MRBF_DISPATCH_DEVICE : MRBF_DISPATCH_REFERENCE;
 }
@@ -88,6 +97,7 @@ int32_t mrbf_dispatch_after(int32_t entry, int32_t rc) {
         case MRBF_ENTRY_SD: return rc == -2;  // shape outside the device path, or the LP gave up (MRBF_SD_GAVE_UP)
         case MRBF_ENTRY_NORMAL: return rc == -2;  // likewise (MRBF_NS_GAVE_UP)
         case MRBF_ENTRY_SD_STEP: return rc == -2;  // shape outside the device path
+        case MRBF_ENTRY_SD_BATCH: return rc == -2;  // likewise; a start whose LP gave up says so in its record, not in rc
         default: return 0;
     }
 }

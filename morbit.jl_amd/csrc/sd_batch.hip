@@ -1,0 +1,425 @@
+// Many-start steepest descent: get_criticality(::SteepestDescentConfig, ...) (Morbit.jl src/descent.jl:187-241) followed by
+// compute_descent_step (descent.jl:243-318) for n_starts independent starts of one problem in one call -- the reference's
+// Threads.@threads loop over Halton starts (examples/large_scale_benchmarks.jl:102-109), where every start carries its own surrogate
+// container of one shared shape.  For start p the outputs are, bit for bit, those of mrbf_sd_criticality and mrbf_sd_step chained on
+// start p's container: the kernels are the single calls' own, with the start on a grid dimension (sd.hpp).
+//
+// One call is one chain on the ctx stream and one read-back, with no host synchronisation in between:
+//   one packed upload           [x_n; x] pairs, delta, lb, ub, the linear rows, the rows table, the evaluation descriptors
+//   eval_fused_batch            values + Jacobians at [x_n; x] of every used model and at x of the models with constraint rows, one
+//                               launch group per (site, kernel and parameters, k, dpad, split or unsplit centre range): the evaluations
+//                               and query counts of the single calls, so the centre-range split and the order of every sum are theirs
+//   sd_assemble_kernel          (rows x n_starts)   G, A_eq / b_eq, A_ineq / b_ineq of every start in consecutive per-LP blocks
+//   sd_lp_kernel                (n_starts)          the direction LPs
+//   sd_stepsize_kernel          (n_starts x 256)    sigma, the branch, the step sizes; omega and d are read where the LP left them
+//   sd_trial_kernel             (n_starts x (L + 2) x d)
+//   eval_fused_batch            values of the objective models at the L + 2 trial rows of every start
+//   sd_armijo_kernel            (n_starts x 256)    x+, m(x+) and the record words into one output block
+//   one download of that block  (device to device for outputs given as device pointers)
+// The starts share d, the model count, every model slot's output count, the roles table and the linear rows; the number of centres
+// and the kernel parameters may differ from start to start (such members fall into different launch groups).  A member the fused
+// evaluation does not take (MRBF_OPT_EVAL_IMPL = 1) is evaluated by eval_model on the same stream.  At a homogeneous batch the launch
+// count does not depend on n_starts.  DESIGN.md section 11.
+#include <limits>
+
+#include "sd.hpp"
+#include "small.hpp"
+
+using namespace mrbf;
+
+namespace {
+
+int batch_fetch(mrbf_ctx *ctx, const double *src, size_t cnt, double *dst) {
+    if (!cnt) return 0;
+    if (is_device_ptr(src)) MRBF_HIP(ctx, hipMemcpy(dst, src, cnt * sizeof(double), hipMemcpyDeviceToHost));
+    else std::memcpy(dst, src, cnt * sizeof(double));
+    return 0;
+}
+
+enum Site { SITE_PAIR = 0, SITE_X = 1, SITE_TRIAL = 2 };
+
+// one evaluation of the batch: model slot j of start p at one of the three sites
+struct Member {
+    int site, j;
+    int64_t p;
+    int group;  // launch group, or -1: eval_model
+};
+struct Group {
+    int site, D, k;
+    bool jac;
+    KP kp;
+    std::vector<size_t> members;
+    size_t first;  // index of the group's first descriptor in the device array
+};
+
+constexpr int64_t MAX_GROUP_LAUNCH = 65535;  // blockIdx.z of the evaluation kernels
+
+}  // namespace
+
+extern "C" int32_t mrbf_sd_iterate_batch(mrbf_ctx *ctx, int64_t n_starts, const mrbf_ps_problem *shape, const mrbf_model *const *models,
+                                         const double *x, const double *x_n, const double *delta, const double *lb, const double *ub,
+                                         int32_t normalize, const mrbf_sd_step_options *opts, double *d_out, double *x_plus, double *mx_plus,
+                                         mrbf_sd_batch_record *records, float *ms_total) {
+    using sdstep::RowRef;
+    if (!ctx) return -1;
+    if (ms_total) *ms_total = 0.f;
+    if (!shape) return fail(ctx, -3, "shape is NULL");
+    if (!models) return fail(ctx, -4, "models is NULL");
+    if (!x) return fail(ctx, -5, "x is NULL");
+    if (!x_n) return fail(ctx, -6, "x_n is NULL");
+    if (!delta) return fail(ctx, -7, "delta is NULL");
+    if (!lb) return fail(ctx, -8, "lb is NULL");
+    if (!ub) return fail(ctx, -9, "ub is NULL");
+    if (!opts) return fail(ctx, -11, "opts is NULL");
+    if (!d_out) return fail(ctx, -12, "d_out is NULL");
+    if (!x_plus) return fail(ctx, -13, "x_plus is NULL");
+    if (!mx_plus) return fail(ctx, -14, "mx_plus is NULL");
+    if (!records) return fail(ctx, -15, "records is NULL");
+    if (!(opts->shrink > 0.0 && opts->shrink < 1.0)) return fail(ctx, -11, "mrbf_sd_iterate_batch: shrink must lie in (0, 1)");
+    if (shape->n_models < 1 || !shape->roles) return fail(ctx, -3, "mrbf_sd_iterate_batch: grouped models with a roles table are required");
+    const int k = shape->n_objectives, nm = shape->n_models;
+    if (k < 1) return fail(ctx, -3, "mrbf_sd_iterate_batch: %d objectives", k);
+    if (shape->n_lin_eq < 0 || shape->n_lin_ineq < 0) return fail(ctx, -3, "mrbf_sd_iterate_batch: negative constraint count");
+    if ((shape->n_lin_eq && (!shape->A_eq || !shape->b_eq)) || (shape->n_lin_ineq && (!shape->A_ineq || !shape->b_ineq)))
+        return fail(ctx, -3, "mrbf_sd_iterate_batch: linear constraint matrices are NULL");
+    if (n_starts < 1) return fail(ctx, -2, "mrbf_sd_iterate_batch: %lld starts (ask mrbf_dispatch_sd_batch first)", (long long)n_starts);
+    const int64_t N = n_starts;
+    // ---- the shape: start 0's models give d and every slot's output count; every other start must agree
+    for (int j = 0; j < nm; ++j)
+        if (!models[j]) return fail(ctx, -4, "mrbf_sd_iterate_batch: model %d of start 0 is NULL", j);
+    const int d = models[0]->d;
+    std::vector<int> kj(nm);
+    for (int j = 0; j < nm; ++j) kj[j] = models[j]->k;
+    // ---- rows of the LP and of the step from the roles table (as mrbf_sd_criticality and mrbf_sd_step read it)
+    std::vector<int> seen(k, 0), obj_model(k), obj_col(k);
+    std::vector<sd::RowSrc> obj(k), meq_src, min_src;
+    std::vector<RowRef> meq_ref, min_ref;
+    std::vector<int64_t> joffA(nm), voffA(nm), joffB(nm, 0), voffB(nm, 0), ooff(nm, 0);
+    std::vector<char> used(nm, 0), has_obj(nm, 0), has_con(nm, 0);
+    int64_t jtotA = 0, vtotA = 0, jtotB = 0, vtotB = 0, otot = 0;
+    const int L = opts->max_loops;
+    for (int j = 0, e = 0; j < nm; ++j) {
+        joffA[j] = jtotA, voffA[j] = vtotA;
+        jtotA += (int64_t)2 * kj[j] * d, vtotA += (int64_t)2 * kj[j];
+        for (int c = 0; c < kj[j]; ++c, ++e) {
+            const int role = shape->roles[e];
+            if (role >= 0) {
+                if (role >= k || seen[role]) return fail(ctx, -3, "mrbf_sd_iterate_batch: roles[%d] = %d is not a (new) objective position", e, role);
+                seen[role] = 1;
+                obj[role] = sd::RowSrc{0, role, 0, kj[j], joffA[j] + c, voffA[j] + c};
+                obj_model[role] = j, obj_col[role] = c;
+                has_obj[j] = 1, used[j] = 1;
+            } else if (role == MRBF_ROLE_EQ || role == MRBF_ROLE_INEQ) {
+                has_con[j] = 1, used[j] = 1;
+            } else if (role != MRBF_ROLE_NONE) {
+                return fail(ctx, -3, "mrbf_sd_iterate_batch: roles[%d] = %d is not a role", e, role);
+            }
+        }
+        if (has_con[j]) {
+            joffB[j] = jtotB, voffB[j] = vtotB;
+            jtotB += (int64_t)kj[j] * d, vtotB += kj[j];
+        }
+    }
+    for (int l = 0; l < k; ++l)
+        if (!seen[l]) return fail(ctx, -3, "mrbf_sd_iterate_batch: objective %d is not an output of any model", l);
+    for (int j = 0, e = 0; j < nm; ++j)
+        for (int c = 0; c < kj[j]; ++c, ++e) {
+            const int role = shape->roles[e];
+            if (role != MRBF_ROLE_EQ && role != MRBF_ROLE_INEQ) continue;
+            const bool eq = role == MRBF_ROLE_EQ;
+            (eq ? meq_src : min_src).push_back(sd::RowSrc{2, 0, eq ? 1 : 0, kj[j], joffA[j] + c, voffA[j] + c});
+            // site 0's Jacobian block is k x d column-major: entry (c, t) at t * k + c
+            (eq ? meq_ref : min_ref).push_back(RowRef{joffB[j] + c, voffB[j] + c, kj[j], 1});
+        }
+    const int n_nl = (int)(meq_src.size() + min_src.size()), n_lin = shape->n_lin_eq + shape->n_lin_ineq;
+    if (mrbf_dispatch_sd_batch(N, d, k, nm, n_nl, n_lin, 0, L) != MRBF_DISPATCH_DEVICE)
+        return fail(ctx, -2, "mrbf_sd_iterate_batch: %lld starts / d = %d / k = %d / %d rows / max_loops = %d outside the device path (ask mrbf_dispatch_sd_batch first)",
+                    (long long)N, d, k, n_nl + n_lin, L);
+    for (int64_t p = 0; p < N; ++p)
+        for (int j = 0; j < nm; ++j) {
+            const mrbf_model *M = models[p * nm + j];
+            if (!M) return fail(ctx, -4, "mrbf_sd_iterate_batch: model %d of start %lld is NULL", j, (long long)p);
+            if (M->d != d || M->k != kj[j])
+                return fail(ctx, -4, "mrbf_sd_iterate_batch: model %d of start %lld is %d variables x %d outputs, start 0 has %d x %d", j, (long long)p,
+                            M->d, M->k, d, kj[j]);
+            if (M->n == 0) return fail(ctx, -4, "mrbf_sd_iterate_batch: model %d of start %lld has no centres", j, (long long)p);
+        }
+    const int meq = shape->n_lin_eq + (int)meq_src.size(), min = shape->n_lin_ineq + (int)min_src.size(), m = k + meq + min;
+    for (int j = 0; j < nm; ++j)
+        if (has_obj[j]) ooff[j] = otot, otot += (int64_t)(L + 2) * kj[j];
+    (void)hipSetDevice(ctx->device);
+    PinGuard pin(ctx);
+    // ---- the evaluations of the two single calls, grouped by what one eval_fused_batch launch requires
+    std::vector<Member> mem;
+    std::vector<Group> groups;
+    const bool fused_ok = ctx->eval_impl != 1;
+    auto group_of = [&](int site, const mrbf_model *M, bool jac, bool split) -> int {
+        if (!fused_ok || !(M->dpad == 64 || M->dpad == 128 || M->dpad == 256)) return -1;
+        for (size_t g = 0; g < groups.size(); ++g) {
+            const Group &G = groups[g];
+            if (G.site == site && G.D == M->dpad && G.k == M->k && G.jac == jac && std::memcmp(&G.kp, &M->kp, sizeof(KP)) == 0) {
+                // (the group's kernels either all write partial sums or none does: split and unsplit members launch apart)
+                return (int)(g & ~(size_t)1) + (split ? 1 : 0);
+            }
+        }
+        // a new key: its unsplit group, then its split group
+        for (int s = 0; s < 2; ++s) {
+            Group G;
+            G.site = site, G.D = M->dpad, G.k = M->k, G.jac = jac, G.kp = M->kp, G.first = 0;
+            groups.push_back(G);
+        }
+        return (int)groups.size() - 2 + (split ? 1 : 0);
+    };
+    auto site_m = [&](int site) -> int64_t { return site == SITE_PAIR ? 2 : (site == SITE_X ? 1 : L + 2); };
+    for (int site = 0; site < 3; ++site)
+        for (int64_t p = 0; p < N; ++p)
+            for (int j = 0; j < nm; ++j) {
+                if (!(site == SITE_PAIR ? used[j] : (site == SITE_X ? has_con[j] : has_obj[j]))) continue;
+                const mrbf_model *M = models[p * nm + j];
+                const int nsplit = eval_nsplit(ctx, site_m(site), (int)((M->n + 63) / 64));
+                Member mb{site, j, p, group_of(site, M, site != SITE_TRIAL, nsplit > 1)};
+                if (mb.group >= 0) groups[mb.group].members.push_back(mem.size());
+                mem.push_back(mb);
+            }
+    size_t n_desc = 0;
+    for (Group &G : groups) G.first = n_desc, n_desc += G.members.size();
+    // ---- the arena (doubles; every piece a multiple of 16): upload | work | evaluation scratch | output block
+    size_t total = 0;
+    auto take = [&](size_t cnt) {
+        const size_t at = total;
+        total += (cnt + 15) & ~(size_t)15;
+        return at;
+    };
+    const size_t nlin = (size_t)n_lin, SN = (size_t)N;
+    std::vector<RowRef> rows;
+    for (int i = 0; i < shape->n_lin_eq; ++i) rows.push_back(RowRef{(int64_t)i * d, i, 1, 0});
+    rows.insert(rows.end(), meq_ref.begin(), meq_ref.end());
+    for (int i = 0; i < shape->n_lin_ineq; ++i) rows.push_back(RowRef{(int64_t)(shape->n_lin_eq + i) * d, shape->n_lin_eq + i, 1, 0});
+    rows.insert(rows.end(), min_ref.begin(), min_ref.end());
+    const size_t rows_dbl = (rows.size() * sizeof(RowRef) + sizeof(double) - 1) / sizeof(double);
+    const size_t desc_dbl = (n_desc * sizeof(EvalDesc) + sizeof(double) - 1) / sizeof(double);
+    const size_t oPairs = take(SN * 2 * d), oDelta = take(SN), oLb = take(d), oUb = take(d), oA = take(nlin * d), oB = take(nlin);
+    const size_t oRows = take(rows_dbl), oDesc = take(desc_dbl);
+    const size_t up_cnt = total;
+    const size_t oJA = take(SN * jtotA), oVA = take(SN * vtotA), oJB = take(SN * jtotB), oVB = take(SN * vtotB);
+    const size_t oG = take(SN * k * d), oAeq = take(SN * meq * d), oBeq = take(SN * meq), oAin = take(SN * min * d), oBin = take(SN * min);
+    const size_t oSteps = take(SN * (L + 1)), oSig = take(SN * 2), oX = take(SN * (L + 2) * d), oVO = take(SN * otot);
+    struct Scratch {
+        size_t Xq, xsq, vpart, gpart;
+        int64_t mpad;
+        int nsplit, KO;
+    };
+    std::vector<Scratch> scr(mem.size());
+    for (size_t i = 0; i < mem.size(); ++i) {
+        if (mem[i].group < 0) continue;
+        const mrbf_model *M = models[mem[i].p * nm + mem[i].j];
+        const bool jac = mem[i].site != SITE_TRIAL;
+        Scratch &S = scr[i];
+        const int64_t mq = site_m(mem[i].site);
+        S.mpad = round_up(mq, 64);
+        S.nsplit = eval_nsplit(ctx, mq, (int)((M->n + 63) / 64));
+        S.KO = outputs_per_pass(M->k, M->dpad, jac);
+        S.Xq = take((size_t)S.mpad * M->dpad);
+        S.xsq = take((size_t)S.mpad);
+        S.vpart = take(S.nsplit > 1 ? (size_t)S.nsplit * S.mpad * S.KO * 2 : 0);
+        S.gpart = take((S.nsplit > 1 && jac) ? (size_t)S.nsplit * S.mpad * S.KO * M->dpad : 0);
+    }
+    // the output block: x+ | m(x+) | [omega_step, step_norm, loops, sigma, branch] | d | omega | status, (iterations, flips) words
+    const size_t out0 = total;
+    const size_t oXp = take(SN * d), oMxp = take(SN * k), oTail = take(SN * sdstep::ARMIJO_TAIL), oDir = take(SN * d), oOmega = take(SN);
+    const size_t oInts = take((3 * SN + 1) / 2);
+    const size_t out_cnt = total - out0;
+    double *base;
+    MRBF_TRY(get_buf(ctx, S_SD_BATCH, total, &base));
+    // ---- the upload, staged in the pinned block where it fits
+    std::vector<double> hup_v;
+    double *hup = reinterpret_cast<double *>(up_cnt * sizeof(double) <= ((size_t)4 << 20) ? pin_take(ctx, up_cnt * sizeof(double)) : nullptr);
+    if (!hup) {
+        hup_v.resize(up_cnt);
+        hup = hup_v.data();
+    }
+    std::memset(hup, 0, up_cnt * sizeof(double));
+    {
+        std::vector<double> tmp(SN * d);
+        MRBF_TRY(batch_fetch(ctx, x_n, SN * d, tmp.data()));
+        for (size_t p = 0; p < SN; ++p) std::memcpy(hup + oPairs + p * 2 * d, tmp.data() + p * d, (size_t)d * sizeof(double));
+        MRBF_TRY(batch_fetch(ctx, x, SN * d, tmp.data()));
+        for (size_t p = 0; p < SN; ++p) std::memcpy(hup + oPairs + p * 2 * d + d, tmp.data() + p * d, (size_t)d * sizeof(double));
+    }
+    MRBF_TRY(batch_fetch(ctx, delta, SN, hup + oDelta));
+    MRBF_TRY(batch_fetch(ctx, lb, d, hup + oLb));
+    MRBF_TRY(batch_fetch(ctx, ub, d, hup + oUb));
+    MRBF_TRY(batch_fetch(ctx, shape->A_eq, (size_t)shape->n_lin_eq * d, hup + oA));
+    MRBF_TRY(batch_fetch(ctx, shape->A_ineq, (size_t)shape->n_lin_ineq * d, hup + oA + (size_t)shape->n_lin_eq * d));
+    MRBF_TRY(batch_fetch(ctx, shape->b_eq, shape->n_lin_eq, hup + oB));
+    MRBF_TRY(batch_fetch(ctx, shape->b_ineq, shape->n_lin_ineq, hup + oB + shape->n_lin_eq));
+    if (!rows.empty()) std::memcpy(hup + oRows, rows.data(), rows.size() * sizeof(RowRef));
+    double *dPairs = base + oPairs, *dX = base + oX;
+    EvalDesc *hdesc = reinterpret_cast<EvalDesc *>(hup + oDesc);
+    const EvalDesc *ddesc = reinterpret_cast<const EvalDesc *>(base + oDesc);
+    for (const Group &G : groups)
+        for (size_t r = 0; r < G.members.size(); ++r) {
+            const size_t i = G.members[r];
+            const Member &mb = mem[i];
+            const mrbf_model *M = models[mb.p * nm + mb.j];
+            const Scratch &S = scr[i];
+            const int j = mb.j;
+            const size_t p = (size_t)mb.p;
+            EvalDesc E;
+            std::memset(&E, 0, sizeof(E));
+            E.X = mb.site == SITE_PAIR ? dPairs + p * 2 * d : (mb.site == SITE_X ? dPairs + p * 2 * d + d : dX + p * (size_t)(L + 2) * d);
+            E.mean = M->mean;
+            E.Xq = base + S.Xq;
+            E.xsq = base + S.xsq;
+            E.Cc = M->Xc;
+            E.csq = M->sq;
+            E.Wc = M->Wc;
+            E.lam = M->lam;
+            E.npad = M->npad;
+            E.mpad = S.mpad;
+            E.m = site_m(mb.site);
+            E.d = d;
+            E.k = M->k;
+            E.q = M->q;
+            E.nsplit = S.nsplit;
+            E.ntiles = (int)((M->n + 63) / 64);
+            E.nsub = (int)((M->n + 15) / 16);
+            E.tiles_per_split = (E.ntiles + E.nsplit - 1) / E.nsplit;
+            E.kp = M->kp;
+            if (S.nsplit > 1) {
+                E.vpart = base + S.vpart;
+                E.sapart = E.vpart + (size_t)S.nsplit * S.mpad * S.KO;
+                if (mb.site != SITE_TRIAL) E.gpart = base + S.gpart;
+            }
+            if (mb.site == SITE_PAIR) E.vals = base + oVA + p * vtotA + voffA[j], E.jac = base + oJA + p * jtotA + joffA[j];
+            else if (mb.site == SITE_X) E.vals = base + oVB + p * vtotB + voffB[j], E.jac = base + oJB + p * jtotB + joffB[j];
+            else E.vals = base + oVO + p * otot + ooff[j], E.jac = nullptr;
+            std::memcpy(&hdesc[G.first + r], &E, sizeof(E));
+        }
+    hipStream_t st = ctx->stream;
+    hipEvent_t e0 = ctx->ev[0], e1 = ctx->ev[1];
+    MRBF_HIP(ctx, hipEventRecord(e0, st));
+    MRBF_HIP(ctx, hipMemcpyAsync(base, hup, up_cnt * sizeof(double), hipMemcpyHostToDevice, st));
+    auto evaluate = [&](int site) -> int {
+        for (const Group &G : groups) {
+            if (G.site != site) continue;
+            for (size_t r0 = 0; r0 < G.members.size(); r0 += MAX_GROUP_LAUNCH) {
+                const int cnt = (int)std::min<size_t>(MAX_GROUP_LAUNCH, G.members.size() - r0);
+                MRBF_TRY(eval_fused_batch(ctx, G.kp, G.D, G.k, G.jac, hdesc + G.first + r0, ddesc + G.first + r0, cnt));
+            }
+        }
+        for (const Member &mb : mem) {
+            if (mb.site != site || mb.group >= 0) continue;
+            const mrbf_model *M = models[mb.p * nm + mb.j];
+            const size_t p = (size_t)mb.p;
+            const int j = mb.j;
+            if (site == SITE_PAIR)
+                MRBF_TRY(eval_model(ctx, M, 2, dPairs + p * 2 * d, base + oVA + p * vtotA + voffA[j], base + oJA + p * jtotA + joffA[j], nullptr));
+            else if (site == SITE_X)
+                MRBF_TRY(eval_model(ctx, M, 1, dPairs + p * 2 * d + d, base + oVB + p * vtotB + voffB[j], base + oJB + p * jtotB + joffB[j], nullptr));
+            else
+                MRBF_TRY(eval_model(ctx, M, L + 2, dX + p * (size_t)(L + 2) * d, base + oVO + p * otot + ooff[j], nullptr, nullptr));
+        }
+        return 0;
+    };
+    MRBF_TRY(evaluate(SITE_PAIR));
+    MRBF_TRY(evaluate(SITE_X));
+    // ---- G, A_eq / b_eq (linear, then modelled), A_ineq / b_ineq (likewise) of every start
+    sd::AsmArgs aa;
+    aa.n = d, aa.k = k, aa.rows = m, aa.meq = meq, aa.min = min;
+    aa.sJ = jtotA, aa.sV = vtotA, aa.sx = 2 * (int64_t)d;
+    aa.J = base + oJA, aa.V = base + oVA, aa.xn = dPairs, aa.x = dPairs + d, aa.Alin = base + oA, aa.blin = base + oB;
+    aa.G = base + oG, aa.Aeq = base + oAeq, aa.beq = base + oBeq, aa.Ain = base + oAin, aa.bin = base + oBin;
+    {
+        int r = 0;
+        for (int l = 0; l < k; ++l) aa.src[r++] = obj[l];
+        for (int i = 0; i < shape->n_lin_eq; ++i) aa.src[r++] = sd::RowSrc{1, i, 1, 1, 0, i};
+        for (size_t i = 0; i < meq_src.size(); ++i) {
+            aa.src[r] = meq_src[i];
+            aa.src[r++].dst = shape->n_lin_eq + (int)i;
+        }
+        for (int i = 0; i < shape->n_lin_ineq; ++i) aa.src[r++] = sd::RowSrc{1, i, 0, 1, 0, shape->n_lin_eq + i};
+        for (size_t i = 0; i < min_src.size(); ++i) {
+            aa.src[r] = min_src[i];
+            aa.src[r++].dst = shape->n_lin_ineq + (int)i;
+        }
+    }
+    MRBF_TRY(sd::launch_assemble(ctx, aa, N));
+    double *dDir = base + oDir, *dOmega = base + oOmega;
+    int *dInts = reinterpret_cast<int *>(base + oInts);
+    MRBF_TRY(sd::launch(ctx, N, d, k, meq, min, normalize, base + oG, dPairs, 2 * (int64_t)d, base + oLb, base + oUb, 0,
+                        meq ? base + oAeq : nullptr, meq ? base + oBeq : nullptr, min ? base + oAin : nullptr, min ? base + oBin : nullptr, dDir,
+                        dOmega, nullptr, dInts, dInts + N));
+    // ---- sigma and the step sizes, the trial rows, the objective models' values there, the Armijo scan
+    sdstep::StepArgs sa;
+    sa.d = d, sa.n_eq = meq, sa.n_in = min, sa.max_loops = L;
+    sa.shrink = opts->shrink;
+    sa.sx = 2 * (int64_t)d, sa.sdir = d, sa.sJ = jtotB, sa.sV = vtotB;
+    sa.delta = base + oDelta;
+    sa.xn = dPairs, sa.x = dPairs + d, sa.lb = base + oLb, sa.ub = base + oUb, sa.dir = dDir;
+    sa.Alin = base + oA, sa.blin = base + oB, sa.Jc = base + oJB, sa.Vc = base + oVB;
+    sa.rows = reinterpret_cast<const RowRef *>(base + oRows);
+    sa.steps = base + oSteps, sa.out = base + oSig;
+    MRBF_TRY(sdstep::launch_stepsize(ctx, sa, N));
+    MRBF_TRY(sdstep::launch_trial(ctx, dPairs, 2 * (int64_t)d, dDir, d, base + oSteps, d, L, N, dX));
+    MRBF_TRY(evaluate(SITE_TRIAL));
+    sdstep::ArmijoArgs am;
+    am.d = d, am.k = k, am.max_loops = L, am.strict = opts->strict != 0;
+    am.const_rhs = opts->const_rhs;
+    am.min_stepsize_raw = opts->min_stepsize;
+    am.min_step = opts->min_stepsize >= 0.0 ? opts->min_stepsize : std::numeric_limits<double>::epsilon();  // descent.jl:152
+    am.sV = otot, am.sdir = d;
+    am.omega = dOmega;
+    am.V = base + oVO, am.X = dX, am.dir = dDir, am.steps = base + oSteps, am.stepout = base + oSig;
+    am.xplus = base + oXp, am.mxplus = base + oMxp, am.tail = base + oTail;
+    for (int l = 0; l < k; ++l) {
+        const int j = obj_model[l];
+        am.obj[l] = sdstep::ObjSrc{ooff[j] + obj_col[l], kj[j]};
+    }
+    MRBF_TRY(sdstep::launch_armijo(ctx, am, N));
+    // ---- one read-back
+    std::vector<double> hout_v;
+    double *hout = reinterpret_cast<double *>(out_cnt * sizeof(double) <= ((size_t)4 << 20) ? pin_take(ctx, out_cnt * sizeof(double)) : nullptr);
+    if (!hout) {
+        hout_v.resize(out_cnt);
+        hout = hout_v.data();
+    }
+    MRBF_HIP(ctx, hipMemcpyAsync(hout, base + out0, out_cnt * sizeof(double), hipMemcpyDeviceToHost, st));
+    const bool dev_d = is_device_ptr(d_out), dev_x = is_device_ptr(x_plus), dev_m = is_device_ptr(mx_plus);
+    if (dev_d) MRBF_HIP(ctx, hipMemcpyAsync(d_out, dDir, SN * d * sizeof(double), hipMemcpyDeviceToDevice, st));
+    if (dev_x) MRBF_HIP(ctx, hipMemcpyAsync(x_plus, base + oXp, SN * d * sizeof(double), hipMemcpyDeviceToDevice, st));
+    if (dev_m) MRBF_HIP(ctx, hipMemcpyAsync(mx_plus, base + oMxp, SN * k * sizeof(double), hipMemcpyDeviceToDevice, st));
+    MRBF_HIP(ctx, hipEventRecord(e1, st));
+    MRBF_HIP(ctx, hipStreamSynchronize(st));
+    pin.flush();
+    if (ms_total) MRBF_HIP(ctx, hipEventElapsedTime(ms_total, e0, e1));
+    const double *hXp = hout + (oXp - out0), *hMxp = hout + (oMxp - out0), *hTail = hout + (oTail - out0), *hDir = hout + (oDir - out0);
+    const double *hOmega = hout + (oOmega - out0);
+    const int *hInts = reinterpret_cast<const int *>(hout + (oInts - out0));
+    if (!dev_d) std::memcpy(d_out, hDir, SN * d * sizeof(double));
+    if (!dev_x) std::memcpy(x_plus, hXp, SN * d * sizeof(double));
+    if (!dev_m) std::memcpy(mx_plus, hMxp, SN * k * sizeof(double));
+    std::vector<double> nanrow;
+    for (size_t p = 0; p < SN; ++p) {
+        mrbf_sd_batch_record &R = records[p];
+        const double *t = hTail + p * sdstep::ARMIJO_TAIL;
+        std::memset(&R, 0, sizeof(R));
+        R.sd_status = hInts[p];
+        R.iterations = hInts[SN + 2 * p], R.bound_flips = hInts[SN + 2 * p + 1];
+        R.omega = hOmega[p];
+        R.omega_step = t[0], R.step_norm = t[1], R.loops = (int32_t)t[2], R.sigma = t[3], R.branch = (int32_t)t[4];
+        if (R.sd_status != MRBF_SD_GAVE_UP) continue;
+        // the single call refuses this start (take the reference method): its outputs say so
+        if (nanrow.empty()) nanrow.assign((size_t)std::max(d, k), std::numeric_limits<double>::quiet_NaN());
+        const struct {
+            double *out;
+            bool dev;
+            size_t cnt;
+        } outs[3] = {{d_out, dev_d, (size_t)d}, {x_plus, dev_x, (size_t)d}, {mx_plus, dev_m, (size_t)k}};
+        for (const auto &o : outs) {
+            if (o.dev) MRBF_HIP(ctx, hipMemcpy(o.out + p * o.cnt, nanrow.data(), o.cnt * sizeof(double), hipMemcpyHostToDevice));
+            else std::memcpy(o.out + p * o.cnt, nanrow.data(), o.cnt * sizeof(double));
+        }
+    }
+    return MRBF_OK;
+}

@@ -12,14 +12,11 @@
 // B^-1 every iteration (one pass over the rows, one over the columns), so no update error accumulates in them.  Every sum runs in a
 // fixed order that depends on the shape alone: an LP's result does not depend on its position in the batch, and no atomics touch
 // values (the one LDS atomic only compacts the ratio-test candidates, which are then sorted by (breakpoint, column)).
-#include "common.hpp"
+#include "sd.hpp"
 
 namespace mrbf {
 namespace sd {
 
-constexpr int THREADS = 256;
-constexpr int MAXM = 64;
-constexpr int MAXD = 4096;
 constexpr int REFACTOR_EVERY = 16;
 constexpr double FEAS_TOL = 1e-13;   // relative to the row's magnitude sum |b_i| + sum_j |A_ij| (|d_j| <= 1)
 constexpr double PIVOT_TOL = 1e-9;   // ratio-test candidates: |alpha_pj| > PIVOT_TOL * max_j |alpha_pj|
@@ -27,6 +24,7 @@ constexpr double SNAP_TOL = 1e-12;   // a basic d_j this close to a bound is ret
 
 struct Args {
     int n, k, meq, min, m, normalize, nc, p2;
+    int64_t xs, bs;  // LP p reads x at x + p xs and its bounds at lb / ub + p bs (0: one box for every LP)
     const double *G, *x, *lb, *ub, *Aeq, *beq, *Ain, *bin;
     double *d_out, *omega_out, *dual_out;
     int *status_out, *iters_out;
@@ -152,7 +150,7 @@ __global__ __launch_bounds__(THREADS) void sd_lp_kernel(Args a, int64_t lp0) {
     int *sidx = (int *)(smem + cv.uni + (size_t)a.p2 * sizeof(double));
 
     const Lp L{a.G + lp * k * n, a.Aeq ? a.Aeq + lp * meq * n : nullptr, a.Ain ? a.Ain + lp * a.min * n : nullptr, n, k, meq};
-    const double *x = a.x + lp * n, *lb = a.lb + lp * n, *ub = a.ub + lp * n;
+    const double *x = a.x + lp * a.xs, *lb = a.lb + lp * a.bs, *ub = a.ub + lp * a.bs;
     double *xv = a.ws + (size_t)blockIdx.x * 5 * nc, *lo = xv + nc, *hi = xv + 2 * nc, *ap = xv + 3 * nc, *dj = xv + 4 * nc;
     int *pos = a.wsi + (size_t)blockIdx.x * nc;
     const double INF = __builtin_huge_val();
@@ -420,26 +418,15 @@ __global__ __launch_bounds__(THREADS) void sd_lp_kernel(Args a, int64_t lp0) {
     }
 }
 
-// ---- get_criticality's right-hand sides: one workgroup per LP row, the Jacobians / values of the evaluation kernels as they lie
-struct RowSrc {
-    int kind;      // 0 objective row (Jacobian at x_n), 1 linear row, 2 modelled constraint row (Jacobian at x, value at x_n)
-    int dst;       // objective position / row of A_eq or A_ineq
-    int eq;        // 1: equality block
-    int stride;    // rows of the model (k_j): the Jacobian is k_j x d column-major per point
-    int64_t jac;   // offset of the row's first entry in the Jacobian buffer (point 0 = x_n; point 1 follows after k_j d)
-    int64_t val;   // offset of the row's value at x_n / index of the linear row
-};
-struct AsmArgs {
-    int n, k, rows;
-    const double *J, *V, *xn, *x, *Alin, *blin;
-    double *G, *Aeq, *beq, *Ain, *bin;
-    RowSrc src[MAXM];
-};
-
+// ---- get_criticality's right-hand sides (RowSrc, AsmArgs: sd.hpp): one workgroup per LP row and start
 __global__ __launch_bounds__(THREADS) void sd_assemble_kernel(AsmArgs a) {
     __shared__ double part[THREADS];
     const RowSrc s = a.src[blockIdx.x];
     const int t = threadIdx.x, n = a.n;
+    // ---- this start's arrays (the linear rows are shared)
+    const int64_t p = blockIdx.y;
+    a.J += p * a.sJ, a.V += p * a.sV, a.xn += p * a.sx, a.x += p * a.sx;
+    a.G += p * a.k * n, a.Aeq += p * a.meq * n, a.beq += p * a.meq, a.Ain += p * a.min * n, a.bin += p * a.min;
     if (s.kind == 0) {
         for (int j = t; j < n; j += THREADS) a.G[(size_t)j * a.k + s.dst] = a.J[s.jac + (int64_t)j * s.stride];
         return;
@@ -462,11 +449,18 @@ __global__ __launch_bounds__(THREADS) void sd_assemble_kernel(AsmArgs a) {
     }
 }
 
-// all device pointers; LPs in chunks so that the per-LP workspace stays below 256 MB
-static int launch(mrbf_ctx *ctx, int64_t n_lp, int n, int k, int meq, int min, int normalize, const double *G, const double *x,
-                  const double *lb, const double *ub, const double *Aeq, const double *beq, const double *Ain, const double *bin,
-                  double *d_out, double *omega_out, double *dual_out, int *status_out, int *iters_out) {
+int launch_assemble(mrbf_ctx *ctx, const AsmArgs &a, int64_t n_starts) {
+    hipLaunchKernelGGL(sd_assemble_kernel, dim3((unsigned)a.rows, (unsigned)n_starts), dim3(THREADS), 0, ctx->stream, a);
+    MRBF_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
+// all device pointers; LPs in chunks so that the per-LP workspace stays below 256 MB (strides: sd.hpp)
+int launch(mrbf_ctx *ctx, int64_t n_lp, int n, int k, int meq, int min, int normalize, const double *G, const double *x, int64_t x_stride,
+           const double *lb, const double *ub, int64_t bound_stride, const double *Aeq, const double *beq, const double *Ain,
+           const double *bin, double *d_out, double *omega_out, double *dual_out, int *status_out, int *iters_out) {
     Args a;
+    a.xs = x_stride, a.bs = bound_stride;
     a.n = n, a.k = k, a.meq = meq, a.min = min, a.m = k + meq + min, a.normalize = normalize != 0;
     a.nc = n + 1 + a.m;
     a.p2 = 1;
@@ -564,7 +558,7 @@ extern "C" int32_t mrbf_sd_direction(mrbf_ctx *ctx, int64_t n_lp, int32_t d, int
     double *od = dev_d ? d_out : ob, *ow = dev_w ? omega_out : ob + N * d, *oy = dual_out ? (dev_y ? dual_out : ob + N * d + N) : nullptr;
     int *oi = reinterpret_cast<int *>(ob + out_dbl);
     int *os = dev_s ? status_out : oi, *ot = iters_out ? (dev_i ? iters_out : oi + N) : nullptr;
-    MRBF_TRY(sd::launch(ctx, n_lp, d, k, m_eq, m_ineq, normalize, dG, dx, dlb, dub, dAeq, dbeq, dAin, dbin, od, ow, oy, os, ot));
+    MRBF_TRY(sd::launch(ctx, n_lp, d, k, m_eq, m_ineq, normalize, dG, dx, d, dlb, dub, d, dAeq, dbeq, dAin, dbin, od, ow, oy, os, ot));
     if (!dev_d) MRBF_HIP(ctx, hipMemcpyAsync(d_out, od, N * d * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (!dev_w) MRBF_HIP(ctx, hipMemcpyAsync(omega_out, ow, N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (oy && !dev_y) MRBF_HIP(ctx, hipMemcpyAsync(dual_out, oy, N * m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -660,7 +654,8 @@ extern "C" int32_t mrbf_sd_criticality(mrbf_ctx *ctx, const mrbf_ps_problem *pro
     }
     // ---- assemble G, A_eq / b_eq (linear, then modelled), A_ineq / b_ineq (likewise) on the device
     sd::AsmArgs aa;
-    aa.n = d, aa.k = k, aa.rows = m;
+    aa.n = d, aa.k = k, aa.rows = m, aa.meq = meq, aa.min = min;
+    aa.sJ = aa.sV = aa.sx = 0;  // one start
     aa.J = dJ, aa.V = dV, aa.xn = dxn, aa.x = dx, aa.Alin = dA, aa.blin = db;
     aa.G = dG, aa.Aeq = dAeq, aa.beq = dbeq, aa.Ain = dAin, aa.bin = dbin;
     int r = 0;
@@ -675,10 +670,9 @@ extern "C" int32_t mrbf_sd_criticality(mrbf_ctx *ctx, const mrbf_ps_problem *pro
         aa.src[r] = min_rows[i];
         aa.src[r].dst = prob->n_lin_ineq + (int)i, aa.src[r++].eq = 0;
     }
-    hipLaunchKernelGGL(sd::sd_assemble_kernel, dim3((unsigned)m), dim3(sd::THREADS), 0, ctx->stream, aa);
-    MRBF_HIP(ctx, hipGetLastError());
+    MRBF_TRY(sd::launch_assemble(ctx, aa, 1));
     int *oi = reinterpret_cast<int *>(dout + d + 1 + m);
-    MRBF_TRY(sd::launch(ctx, 1, d, k, meq, min, normalize, dG, dxn, dlb, dub, meq ? dAeq : nullptr, meq ? dbeq : nullptr,
+    MRBF_TRY(sd::launch(ctx, 1, d, k, meq, min, normalize, dG, dxn, 0, dlb, dub, 0, meq ? dAeq : nullptr, meq ? dbeq : nullptr,
                         min ? dAin : nullptr, min ? dbin : nullptr, dout, dout + d, dout + d + 1, oi, oi + 1));
     // ---- one read-back
     std::vector<double> hout(out_cnt);

@@ -12,38 +12,15 @@
 // order fixed by the shape (lane-strided partials, a fixed shuffle / LDS tree); every min / max is exact; no atomics.  The trial points
 // and Armijo right-hand sides are formed without FMA contraction, so they round exactly as the host loop's `x + s * d` and
 // `s * c * omega` do.  DESIGN.md section 10.
-#include "common.hpp"
+#include "sd.hpp"
 
 namespace mrbf {
 namespace sdstep {
 
-constexpr int THREADS = 256;
-constexpr int MAXK = 64, MAXROWS = 256;  // the limits of mrbf_dispatch_sd_step (d <= 4096, max_loops <= 1024) need no array here
 constexpr double SQRT_EPS = 1.4901161193847656e-08;  // sqrt(eps(Float64)) = 2^-26: Julia's isapprox rtol
 constexpr double EPS = 2.220446049250313e-16;        // eps(Float64): _intersect_bounds' zero_tol
 
 enum Branch { B_DELTA = 0, B_ONE = 1, B_INTERSECT = 2 };
-
-// one constraint row of the stacked problem of descent.jl:279-285: the row acts on the x_n half (linear rows) or on the n = x_n - x
-// half (modelled rows); a(t) = A[a_off + t * stride], right-hand side b_lin[b_off] (linear) or -Vc[b_off] (modelled)
-struct RowRef {
-    int64_t a_off, b_off;
-    int32_t stride, modelled;
-};
-struct ObjSrc {
-    int64_t off;     // value of objective l at site p: V[off + p * stride]
-    int64_t stride;  // the model's output count
-};
-
-struct StepArgs {
-    int d, n_eq, n_in, max_loops;
-    double delta, shrink;
-    const double *xn, *x, *lb, *ub, *dir;
-    const double *Alin, *blin, *Jc, *Vc;
-    const RowRef *rows;  // n_eq equality rows (linear, then modelled), then n_in inequality rows (likewise)
-    double *steps;       // max_loops + 1
-    double *out;         // [sigma, branch]
-};
 
 __device__ __forceinline__ double nan_max(double a, double b) { return (a != a || b != b) ? a + b : (a > b ? a : b); }
 __device__ __forceinline__ double nan_min(double a, double b) { return (a != a || b != b) ? a + b : (a < b ? a : b); }
@@ -103,11 +80,16 @@ __global__ __launch_bounds__(THREADS) void sd_stepsize_kernel(StepArgs a) {
     __shared__ double s_sigma;
     __shared__ int s_mode;  // 0: finite equality sigma to check, 1: take the inequality-only candidates, 2: sigma decided
     const int tid = threadIdx.x, d = a.d;
+    // ---- this start's arrays (lb / ub, the linear rows and the rows table are shared)
+    const int64_t p = blockIdx.x;
+    const double delta = a.delta[p];
+    a.xn += p * a.sx, a.x += p * a.sx, a.dir += p * a.sdir, a.Jc += p * a.sJ, a.Vc += p * a.sV;
+    a.steps += p * (a.max_loops + 1), a.out += p * 2;
     // ---- lb_eff, ub_eff (utilities.jl:290-294), isapprox(x, x_n), ||d||_inf, Delta = intersect_box(x_n, d, lb_eff, ub_eff; :pos)
     double neq = 0.0, nonfin = 0.0, sdiff = 0.0, sx = 0.0, sxn = 0.0, nd = 0.0, dnz = 0.0, best = INFINITY, anyp = 0.0;
     for (int t = tid; t < d; t += THREADS) {
         const double xv = a.x[t], xn = a.xn[t], dv = a.dir[t];
-        const double lbe = nan_max(a.lb[t], xv - a.delta), ube = nan_min(a.ub[t], xv + a.delta);
+        const double lbe = nan_max(a.lb[t], xv - delta), ube = nan_min(a.ub[t], xv + delta);
         neq += (xv == xn) ? 0.0 : 1.0;
         nonfin += (isfinite(xv) && isfinite(xn)) ? 0.0 : 1.0;
         const double df = xv - xn;
@@ -131,7 +113,7 @@ __global__ __launch_bounds__(THREADS) void sd_stepsize_kernel(StepArgs a) {
     if (neq == 0.0) close = true;
     else if (nonfin != 0.0) close = false;
     else close = sqrt(sdiff) <= SQRT_EPS * fmax(sqrt(sx), sqrt(sxn));
-    const double Delta = close ? a.delta : (dnz == 0.0 ? INFINITY : (anyp != 0.0 ? best : 0.0));
+    const double Delta = close ? delta : (dnz == 0.0 ? INFINITY : (anyp != 0.0 ? best : 0.0));
     double sigma = 0.0;
     int branch;
     if (Delta <= 1.0) {
@@ -197,7 +179,7 @@ __global__ __launch_bounds__(THREADS) void sd_stepsize_kernel(StepArgs a) {
             double b2 = INFINITY, p2 = 0.0, h2 = 0.0;
             for (int t = tid; t < d; t += THREADS) {
                 const double xv = a.x[t], xn = a.xn[t], dv = a.dir[t], nv = xn - xv;
-                const double lbe = nan_max(a.lb[t], xv - a.delta), ube = nan_min(a.ub[t], xv + a.delta);
+                const double lbe = nan_max(a.lb[t], xv - delta), ube = nan_min(a.ub[t], xv + delta);
                 bool h;
                 take_pos(bound_candidate(xn, lbe, dv, false, h), b2, p2), h2 += h;
                 take_pos(bound_candidate(nv, lbe - xv, dv, false, h), b2, p2), h2 += h;
@@ -220,7 +202,7 @@ __global__ __launch_bounds__(THREADS) void sd_stepsize_kernel(StepArgs a) {
             double bad = 0.0;
             for (int t = tid; t < d; t += THREADS) {
                 const double xv = a.x[t], xn = a.xn[t], dv = a.dir[t], nv = xn - xv;
-                const double lbe = nan_max(a.lb[t], xv - a.delta), ube = nan_min(a.ub[t], xv + a.delta);
+                const double lbe = nan_max(a.lb[t], xv - delta), ube = nan_min(a.ub[t], xv + delta);
                 const double sd = sg * dv;
                 const double t1 = xn + sd, t2 = nv + sd;
                 bad += (t1 < lbe || t1 > ube || t2 < lbe - xv || t2 > ube - xv) ? 1.0 : 0.0;
@@ -257,14 +239,18 @@ __global__ __launch_bounds__(THREADS) void sd_stepsize_kernel(StepArgs a) {
     }
 }
 
-// row 0 = x_n, row 1 + i = x_n + steps[i] * d (descent.jl:162, :177), i = 0 .. max_loops
-__global__ __launch_bounds__(THREADS) void sd_trial_kernel(const double *__restrict__ xn, const double *__restrict__ dir,
-                                                           const double *__restrict__ steps, int d, int64_t total, double *__restrict__ X) {
+// per start: row 0 = x_n, row 1 + i = x_n + steps[i] * d (descent.jl:162, :177), i = 0 .. max_loops
+__global__ __launch_bounds__(THREADS) void sd_trial_kernel(const double *__restrict__ xn, int64_t sx, const double *__restrict__ dir, int64_t sdir,
+                                                           const double *__restrict__ steps, int d, int max_loops, int64_t total,
+                                                           double *__restrict__ X) {
 #pragma clang fp contract(off)
     const int64_t e = (int64_t)blockIdx.x * THREADS + threadIdx.x;
     if (e >= total) return;
-    const int64_t row = e / d;
-    const int t = (int)(e - row * d);
+    const int64_t per = (int64_t)(max_loops + 2) * d;
+    const int64_t p = e / per, r = e - p * per;
+    const int64_t row = r / d;
+    const int t = (int)(r - row * d);
+    xn += p * sx, dir += p * sdir, steps += p * (max_loops + 1);
     if (row == 0) {
         X[e] = xn[t];
     } else {
@@ -273,21 +259,16 @@ __global__ __launch_bounds__(THREADS) void sd_trial_kernel(const double *__restr
     }
 }
 
-struct ArmijoArgs {
-    int d, k, max_loops, strict;
-    double omega, const_rhs, min_stepsize_raw, min_step;
-    const double *V;      // values of the objective models at the L + 2 rows (each model's block: rows x its outputs)
-    const double *X;      // the L + 2 trial rows
-    const double *dir, *steps, *stepout;
-    double *out;          // [x+ (d) | mx+ (k) | omega, step_norm, loops]
-    ObjSrc obj[MAXK];
-};
-
 __global__ __launch_bounds__(THREADS) void sd_armijo_kernel(ArmijoArgs a) {
 #pragma clang fp contract(off)
     __shared__ double red[THREADS];
     __shared__ double mx[MAXK];
     const int tid = threadIdx.x, k = a.k;
+    const int64_t p = blockIdx.x;
+    const double omega = a.omega[p];
+    a.V += p * a.sV, a.X += p * (int64_t)(a.max_loops + 2) * a.d, a.dir += p * a.sdir;
+    a.steps += p * (a.max_loops + 1), a.stepout += p * 2;
+    a.xplus += p * a.d, a.mxplus += p * k, a.tail += p * ARMIJO_TAIL;
     if (tid < k) mx[tid] = a.V[a.obj[tid].off];
     __syncthreads();
     const double sigma = a.stepout[0];
@@ -299,7 +280,7 @@ __global__ __launch_bounds__(THREADS) void sd_armijo_kernel(ArmijoArgs a) {
         for (int i = tid; i < a.max_loops; i += THREADS) {
             const double st = a.steps[i];
             const double sc = st * a.const_rhs;
-            const double rhs = sc * a.omega;
+            const double rhs = sc * omega;
             bool ok;
             if (a.strict) {
                 ok = true;
@@ -324,16 +305,37 @@ __global__ __launch_bounds__(THREADS) void sd_armijo_kernel(ArmijoArgs a) {
     const double st = zero ? 0.0 : a.steps[i];
     double nrm = 0.0;
     for (int t = tid; t < a.d; t += THREADS) {
-        a.out[t] = a.X[row * a.d + t];
+        a.xplus[t] = a.X[row * a.d + t];
         nrm = nan_max(nrm, fabs(st * a.dir[t]));
     }
     nrm = block_reduce(nrm, red, OpMax());
-    if (tid < k) a.out[a.d + tid] = a.V[a.obj[tid].off + row * a.obj[tid].stride];
+    if (tid < k) a.mxplus[tid] = a.V[a.obj[tid].off + row * a.obj[tid].stride];
     if (tid == 0) {
-        a.out[a.d + k] = zero ? 0.0 : a.omega;
-        a.out[a.d + k + 1] = zero ? 0.0 : nrm;
-        a.out[a.d + k + 2] = zero ? 0.0 : (double)i;
+        a.tail[0] = zero ? 0.0 : omega;
+        a.tail[1] = zero ? 0.0 : nrm;
+        a.tail[2] = zero ? 0.0 : (double)i;
+        a.tail[3] = sigma;
+        a.tail[4] = a.stepout[1];
     }
+}
+
+int launch_stepsize(mrbf_ctx *ctx, const StepArgs &a, int64_t n_starts) {
+    hipLaunchKernelGGL(sd_stepsize_kernel, dim3((unsigned)n_starts), dim3(THREADS), 0, ctx->stream, a);
+    MRBF_HIP(ctx, hipGetLastError());
+    return 0;
+}
+int launch_trial(mrbf_ctx *ctx, const double *xn, int64_t sx, const double *dir, int64_t sdir, const double *steps, int d, int max_loops,
+                 int64_t n_starts, double *X) {
+    const int64_t tot = n_starts * (int64_t)(max_loops + 2) * d;
+    hipLaunchKernelGGL(sd_trial_kernel, dim3((unsigned)((tot + THREADS - 1) / THREADS)), dim3(THREADS), 0, ctx->stream, xn, sx, dir, sdir, steps, d,
+                       max_loops, tot, X);
+    MRBF_HIP(ctx, hipGetLastError());
+    return 0;
+}
+int launch_armijo(mrbf_ctx *ctx, const ArmijoArgs &a, int64_t n_starts) {
+    hipLaunchKernelGGL(sd_armijo_kernel, dim3((unsigned)n_starts), dim3(THREADS), 0, ctx->stream, a);
+    MRBF_HIP(ctx, hipGetLastError());
+    return 0;
 }
 
 }  // namespace sdstep
@@ -422,10 +424,11 @@ extern "C" int32_t mrbf_sd_step(mrbf_ctx *ctx, const mrbf_ps_problem *prob, cons
     const int L = opts->max_loops;
     (void)hipSetDevice(ctx->device);
     PinGuard pin(ctx);
-    // ---- host inputs, packed: x_n, x, lb, ub, d, linear rows (eq, then ineq), their b
+    // ---- host inputs, packed: x_n, x, lb, ub, d, linear rows (eq, then ineq), their b, delta, omega
     const size_t nlin = (size_t)n_lin;
-    std::vector<double> h((size_t)5 * d + nlin * (d + 1));
+    std::vector<double> h((size_t)5 * d + nlin * (d + 1) + 2);
     double *hxn = h.data(), *hx = hxn + d, *hlb = hx + d, *hub = hlb + d, *hd = hub + d, *hA = hd + d, *hb = hA + nlin * d;
+    hb[nlin] = delta, hb[nlin + 1] = omega;
     MRBF_TRY(step_fetch(ctx, x_n, d, hxn));
     MRBF_TRY(step_fetch(ctx, x, d, hx));
     MRBF_TRY(step_fetch(ctx, lb, d, hlb));
@@ -449,7 +452,7 @@ extern "C" int32_t mrbf_sd_step(mrbf_ctx *ctx, const mrbf_ps_problem *prob, cons
         if (has_obj[j]) ooff[j] = otot, otot += (int64_t)(L + 2) * prob->models[j]->k;
     // ---- device arena: inputs | rows table | Jc | Vc | steps | trial rows | objective values | outputs
     const size_t rows_dbl = (rows.size() * sizeof(RowRef) + sizeof(double) - 1) / sizeof(double);
-    const size_t out_cnt = (size_t)d + k + 3;
+    const size_t out_cnt = (size_t)d + k + ARMIJO_TAIL;
     const size_t total = h.size() + rows_dbl + jtot + vtot + (L + 1) + 2 + (size_t)(L + 2) * d + otot + out_cnt;
     double *base;
     MRBF_TRY(get_buf(ctx, S_SD_STEP, total, &base));
@@ -461,44 +464,43 @@ extern "C" int32_t mrbf_sd_step(mrbf_ctx *ctx, const mrbf_ps_problem *prob, cons
     if (!rows.empty())
         MRBF_HIP(ctx, hipMemcpyAsync(dRows, rows.data(), rows.size() * sizeof(RowRef), hipMemcpyHostToDevice, ctx->stream));
     const double *dxn = base, *dx = base + d, *dlb = base + 2 * d, *dub = base + 3 * d, *ddir = base + 4 * d;
-    const double *dA = base + 5 * d, *db = dA + nlin * d;
+    const double *dA = base + 5 * d, *db = dA + nlin * d, *ddelta = db + nlin, *domega = ddelta + 1;
     // ---- the modelled constraint rows at x (values + Jacobians; the "intersect" branch reads them)
     for (int j = 0; j < prob->n_models; ++j)
         if (has_con[j]) MRBF_TRY(eval_model(ctx, prob->models[j], 1, dx, dVc + voff[j], dJc + joff[j], nullptr));
     // ---- sigma and the step sizes
     StepArgs sa;
     sa.d = d, sa.n_eq = n_eq, sa.n_in = n_in, sa.max_loops = L;
-    sa.delta = delta, sa.shrink = opts->shrink;
+    sa.shrink = opts->shrink;
+    sa.sx = sa.sdir = sa.sJ = sa.sV = 0;  // one start
+    sa.delta = ddelta;
     sa.xn = dxn, sa.x = dx, sa.lb = dlb, sa.ub = dub, sa.dir = ddir;
     sa.Alin = dA, sa.blin = db, sa.Jc = dJc, sa.Vc = dVc;
     sa.rows = reinterpret_cast<const RowRef *>(dRows);
     sa.steps = dSteps, sa.out = dSig;
-    hipLaunchKernelGGL(sd_stepsize_kernel, dim3(1), dim3(THREADS), 0, ctx->stream, sa);
-    MRBF_HIP(ctx, hipGetLastError());
+    MRBF_TRY(launch_stepsize(ctx, sa, 1));
     // ---- the L + 2 trial rows and the objective models' values there
-    const int64_t tot = (int64_t)(L + 2) * d;
-    hipLaunchKernelGGL(sd_trial_kernel, dim3((unsigned)((tot + THREADS - 1) / THREADS)), dim3(THREADS), 0, ctx->stream, dxn, ddir,
-                       (const double *)dSteps, d, tot, dX);
-    MRBF_HIP(ctx, hipGetLastError());
+    MRBF_TRY(launch_trial(ctx, dxn, 0, ddir, 0, dSteps, d, L, 1, dX));
     for (int j = 0; j < prob->n_models; ++j)
         if (has_obj[j]) MRBF_TRY(eval_model(ctx, prob->models[j], L + 2, dX, dV + ooff[j], nullptr, nullptr));
     // ---- the Armijo scan
     ArmijoArgs aa;
     aa.d = d, aa.k = k, aa.max_loops = L, aa.strict = opts->strict != 0;
-    aa.omega = omega, aa.const_rhs = opts->const_rhs;
+    aa.const_rhs = opts->const_rhs;
+    aa.sV = aa.sdir = 0;
+    aa.omega = domega;
     aa.min_stepsize_raw = opts->min_stepsize;
     aa.min_step = opts->min_stepsize >= 0.0 ? opts->min_stepsize : EPS;  // descent.jl:152
-    aa.V = dV, aa.X = dX, aa.dir = ddir, aa.steps = dSteps, aa.stepout = dSig, aa.out = dOut;
+    aa.V = dV, aa.X = dX, aa.dir = ddir, aa.steps = dSteps, aa.stepout = dSig;
+    aa.xplus = dOut, aa.mxplus = dOut + d, aa.tail = dOut + d + k;
     for (int l = 0; l < k; ++l) {
         const int j = obj_model[l];
         aa.obj[l] = ObjSrc{ooff[j] + obj_col[l], prob->models[j]->k};
     }
-    hipLaunchKernelGGL(sd_armijo_kernel, dim3(1), dim3(THREADS), 0, ctx->stream, aa);
-    MRBF_HIP(ctx, hipGetLastError());
-    // ---- one read-back: sigma, branch, x+, mx+, omega, ||step||, loops
-    std::vector<double> hout(2 + out_cnt);
-    MRBF_HIP(ctx, hipMemcpyAsync(hout.data(), dSig, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    MRBF_HIP(ctx, hipMemcpyAsync(hout.data() + 2, dOut, out_cnt * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    MRBF_TRY(launch_armijo(ctx, aa, 1));
+    // ---- one read-back: x+, mx+, omega, ||step||, loops, sigma, branch
+    std::vector<double> hout(out_cnt);
+    MRBF_HIP(ctx, hipMemcpyAsync(hout.data(), dOut, out_cnt * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     const bool dev_x = is_device_ptr(x_plus), dev_m = is_device_ptr(mx_plus);
     if (dev_x) MRBF_HIP(ctx, hipMemcpyAsync(x_plus, dOut, (size_t)d * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     if (dev_m) MRBF_HIP(ctx, hipMemcpyAsync(mx_plus, dOut + d, (size_t)k * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
@@ -506,11 +508,11 @@ extern "C" int32_t mrbf_sd_step(mrbf_ctx *ctx, const mrbf_ps_problem *prob, cons
     MRBF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     pin.flush();
     MRBF_HIP(ctx, hipEventElapsedTime(&info->ms_total, e0, e1));
-    const double *o = hout.data() + 2;
+    const double *o = hout.data();
     if (!dev_x) std::memcpy(x_plus, o, (size_t)d * sizeof(double));
     if (!dev_m) std::memcpy(mx_plus, o + d, (size_t)k * sizeof(double));
-    info->sigma = hout[0];
-    info->branch = (int32_t)hout[1];
+    info->sigma = o[d + k + 3];
+    info->branch = (int32_t)o[d + k + 4];
     info->omega = o[d + k];
     info->step_norm = o[d + k + 1];
     info->loops = (int32_t)o[d + k + 2];

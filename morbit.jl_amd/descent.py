@@ -589,3 +589,90 @@ def compute_descent_step_sd_routed(cfg, sc, scal, x, x_n, delta, lb, ub, omega, 
     if stats is not None:
         stats["path"] = "reference"
     return compute_descent_step_sd(cfg, sc, scal, x, x_n, delta, lb, ub, omega, d, lin)
+
+
+# ---- many starts in one device call (mrbf_sd_iterate_batch): the reference's Threads.@threads loop over starts ---------------------
+def sd_iterate_batch_device(plans, cfg, X, X_n, deltas, lb, ub, lin=None, out=None):
+    """one mrbf_sd_iterate_batch call on the containers' plans (one shape, checked by the caller); X, X_n (n_starts x d), deltas,
+    lb, ub may be NumPy arrays or device tensors; out = (d, x_plus, mx_plus) lets the caller pass its own output buffers (host or
+    device).  Returns (rc, d, x_plus, mx_plus, list of record dicts with "branch_name", event ms)."""
+    ctx = plans[0]["models"][0].ctx
+    ns, nm, k = len(plans), len(plans[0]["models"]), plans[0]["k"]
+
+    def arr(a):
+        return a if hasattr(a, "data_ptr") else np.ascontiguousarray(a, dtype=np.float64)
+
+    X, X_n, deltas, lb, ub = arr(X), arr(X_n), arr(deltas), arr(lb), arr(ub)
+    n = int(lb.numel() if hasattr(lb, "numel") else lb.size)
+    prob, keep = _sd_problem(plans[0], lin or (None,) * 4)
+    handles = (ctypes.c_void_p * (ns * nm))(*[m.model.value if hasattr(m.model, "value") else m.model for p in plans for m in p["models"]])
+    dd, xp, mxp = out if out is not None else (np.empty((ns, n)), np.empty((ns, n)), np.empty((ns, k)))
+    opts = _lib.SdStepOptions(strict=int(bool(cfg.strict_backtracking)), max_loops=int(cfg.max_loops), const_rhs=float(cfg.armijo_const_rhs),
+                              shrink=float(cfg.armijo_const_shrink), min_stepsize=float(cfg.min_stepsize))
+    recs = (_lib.SdBatchRecord * ns)()
+    ms = ctypes.c_float()
+    rc = ctx.lib.mrbf_sd_iterate_batch(ctx.h, ns, ctypes.byref(prob), handles, _lib.as_ptr(X), _lib.as_ptr(X_n), _lib.as_ptr(deltas),
+                                       _lib.as_ptr(lb), _lib.as_ptr(ub), int(bool(cfg.normalize)), ctypes.byref(opts), _lib.as_ptr(dd),
+                                       _lib.as_ptr(xp), _lib.as_ptr(mxp), recs, ctypes.byref(ms))
+    records = []
+    for r in recs:
+        rd = r.asdict()
+        rd["branch_name"] = _SD_BRANCHES[r.branch] if rc == 0 and 0 <= r.branch < 3 else None
+        records.append(rd)
+    return rc, dd, xp, mxp, records, ms.value
+
+
+def _same_plan_shape(plans):
+    """do the containers share what mrbf_sd_iterate_batch requires: the model count, every slot's output count, the roles table and
+    no foreign surrogate count that differs"""
+    p0 = plans[0]
+    sig0 = ([m.num_outputs for m in p0["models"]], p0["roles"], p0["k"], p0["n_con"], p0["n_foreign"])
+    return all(([m.num_outputs for m in p["models"]], p["roles"], p["k"], p["n_con"], p["n_foreign"]) == sig0 for p in plans[1:])
+
+
+def sd_iterate_many(cfg, containers, scal, X, X_n, deltas, lb, ub, lin=None, stats=None):
+    """get_criticality then compute_descent_step (descent.jl:187-318) for many independent starts of one problem -- the reference's
+    `Threads.@threads` loop over starts (examples/large_scale_benchmarks.jl:102-109): containers[p] is start p's surrogate container,
+    X[p] / X_n[p] / deltas[p] its iterate, normal-step iterate and radius; lb / ub and lin belong to the one MOP.  Where the
+    containers share one plan shape and mrbf_dispatch_sd_batch says so, ONE mrbf_sd_iterate_batch call serves all starts ("batch");
+    otherwise, and for every start whose direction LP gave up, the routed single-start functions run (`get_criticality_sd`, then
+    `compute_descent_step_sd_routed`).  Returns a list of (omega, d, x_plus, mx_plus, ||step||_inf); stats gets "path" ("batch" or
+    "loop") and "rerouted", the starts that took the single-start functions after a batch call."""
+    lib = _lib.load()
+    X, X_n = np.asarray(X, dtype=np.float64), np.asarray(X_n, dtype=np.float64)
+    deltas = np.asarray(deltas, dtype=np.float64).ravel()
+    ns = len(containers)
+    lin = lin or (None,) * 4
+    n_lin = sum(0 if b is None else int(np.asarray(b).size) for b in (lin[1], lin[3]))
+
+    def single(p):
+        omega, d = get_criticality_sd(cfg, containers[p], scal, X[p], X_n[p], lb, ub, lin)
+        om, xp, mxp, nrm = compute_descent_step_sd_routed(cfg, containers[p], scal, X[p], X_n[p], float(deltas[p]), lb, ub, omega, d, lin)
+        return om, d, xp, mxp, nrm
+
+    if stats is not None:
+        stats["path"], stats["rerouted"] = "loop", []
+    if ns == 0:
+        return []
+    plans = [sg.container_plan(sc) for sc in containers]
+    n = int(X_n.shape[1])
+    p0 = plans[0]
+    if _same_plan_shape(plans) and lib.mrbf_dispatch_sd_batch(ns, n, p0["k"], len(p0["models"]), p0["n_con"], n_lin, p0["n_foreign"],
+                                                              int(cfg.max_loops)) == _lib.DISPATCH_DEVICE:
+        rc, dd, xp, mxp, records, ms = sd_iterate_batch_device(plans, cfg, X, X_n, deltas, lb, ub, lin)
+        if rc == 0:
+            res, rerouted = [], []
+            for p, r in enumerate(records):
+                if r["sd_status"] == _lib.SD_GAVE_UP:          # this start's LP gave up: the reference method for it alone
+                    rerouted.append(p)
+                    res.append(single(p))
+                elif not r["sigma"] > cfg.min_stepsize:        # descent.jl:317: the reference returns integer zeros here
+                    res.append((0, dd[p].copy(), xp[p].copy(), mxp[p].copy(), 0))
+                else:
+                    res.append((r["omega"], dd[p].copy(), xp[p].copy(), mxp[p].copy(), r["step_norm"]))
+            if stats is not None:
+                stats.update(path="batch", rerouted=rerouted, records=records, ms_total=ms)
+            return res
+        if not lib.mrbf_dispatch_after(_lib.ENTRY_SD_BATCH, rc):
+            p0["models"][0].ctx.check(rc)
+    return [single(p) for p in range(ns)]

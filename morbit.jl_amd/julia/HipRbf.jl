@@ -62,6 +62,11 @@ struct MrbfSdStepInfo       # mirrors mrbf_sd_step_info, 40 bytes
     sigma::Float64; omega::Float64; step_norm::Float64
 end
 
+struct MrbfSdBatchRecord    # mirrors mrbf_sd_batch_record, 56 bytes
+    sd_status::Int32; iterations::Int32; bound_flips::Int32; branch::Int32; loops::Int32; reserved::Int32
+    omega::Float64; omega_step::Float64; sigma::Float64; step_norm::Float64
+end
+
 struct MrbfPsProblem        # mirrors mrbf_ps_problem, 72 bytes
     n_models::Int32; n_objectives::Int32
     models::Ptr{Ptr{Cvoid}}; roles::Ptr{Int32}
@@ -232,6 +237,9 @@ _dispatch_normal(d, n_models, n_nl, n_lin, n_foreign) =
 _dispatch_sd_step(d, k, n_models, n_nl, n_lin, n_foreign, max_loops) =
     ccall((:mrbf_dispatch_sd_step, libmrbf), Int32, (Int32, Int32, Int32, Int32, Int32, Int32, Int32),
           d, k, n_models, n_nl, n_lin, n_foreign, max_loops) == 1
+_dispatch_sd_batch(n_starts, d, k, n_models, n_nl, n_lin, n_foreign, max_loops) =
+    ccall((:mrbf_dispatch_sd_batch, libmrbf), Int32, (Int64, Int32, Int32, Int32, Int32, Int32, Int32, Int32),
+          n_starts, d, k, n_models, n_nl, n_lin, n_foreign, max_loops) == 1
 _dispatch_backtrack(n_models, n_foreign, in_order::Bool) =
     ccall((:mrbf_dispatch_backtrack, libmrbf), Int32, (Int32, Int32, Int32), n_models, n_foreign, in_order) == 1
 _dispatch_affine(n_candidates, d) = ccall((:mrbf_dispatch_affine, libmrbf), Int32, (Int64, Int32), n_candidates, d) == 1
@@ -831,6 +839,76 @@ function hip_compute_descent_step(desc_cfg::SteepestDescentConfig, mop, scal, x_
     info[].sigma > desc_cfg.min_stepsize ||
         return 0, copy(get_x_scaled(x_it_n)), Xet.(mx₊), 0      # σ too small: no step, m(x_n) (descent.jl:317)
     return ω, Xet.(x₊), Xet.(mx₊), Xet(info[].step_norm)
+end
+
+"""
+Many starts in one device call (`mrbf_sd_iterate_batch`): `get_criticality` (descent.jl:187-241) followed by the steepest-descent
+step (descent.jl:243-318) for independent starts of one problem -- the `Threads.@threads` loop over starts of
+examples/large_scale_benchmarks.jl:102-109 -- as one chain of launches and one read-back.  `x_its[p]`, `x_it_ns[p]` and `scs[p]` are
+start p's iterate, normal-step iterate and surrogate container; `mop`, `scal` and the configurations belong to the one problem.  For
+every start the result is, bit for bit, what `get_criticality` and `hip_compute_descent_step` return on that start alone.  Where the
+containers do not share one plan shape, the decision table refuses (`mrbf_dispatch_sd_batch`: a foreign surrogate, d > 256, more than
+65535 starts, the limits of the two single calls) or a start's direction LP gave up, those starts take the two single-start functions.
+Returns a vector of (ω, d, x₊, mx₊, ‖step‖∞).
+"""
+function hip_sd_iterate_many(desc_cfg::SteepestDescentConfig, mop, scal, x_its::AbstractVector, x_it_ns::AbstractVector, data_base,
+                             scs::AbstractVector{<:SurrogateContainer}, algo_config)
+    function single(p)
+        ω, d = get_criticality(desc_cfg, mop, scal, x_its[p], x_it_ns[p], data_base, scs[p], algo_config)
+        ω₊, x₊, mx₊, nrm = hip_compute_descent_step(desc_cfg, mop, scal, x_its[p], x_it_ns[p], data_base, scs[p], algo_config, ω, d)
+        return ω₊, d, x₊, mx₊, nrm
+    end
+    loop() = [single(p) for p in eachindex(scs)]
+    ns = length(scs)
+    (ns >= 1 && all(_touches_device, scs)) || return loop()
+    plans = [_container_plan(sc) for sc in scs]
+    p1 = plans[1]
+    same = all(pl -> pl.roles == p1.roles && pl.k == p1.k && pl.n_con == p1.n_con && pl.n_foreign == p1.n_foreign &&
+                     length(pl.models) == length(p1.models), plans)
+    same || return loop()
+    n, k, nm = length(get_x_scaled(x_it_ns[1])), p1.k, length(p1.models)
+    A_eq, b_eq = transformed_linear_eq_constraints(scal, mop)                  # AbstractMOPInterface.jl:463-481: A x_scaled (=, <=) b
+    A_in, b_in = transformed_linear_ineq_constraints(scal, mop)
+    _dispatch_sd_batch(ns, n, k, nm, p1.n_con, length(b_eq) + length(b_in), p1.n_foreign, desc_cfg.max_loops) || return loop()
+    lb_g, ub_g = full_bounds_internal(scal)
+    lb = Vector{Float64}(lb_g); ub = Vector{Float64}(ub_g)
+    X = Matrix{Float64}(undef, n, ns); X_n = Matrix{Float64}(undef, n, ns)     # column p = start p: the n_starts x d row-major array
+    for p in 1:ns
+        X[:, p] .= get_x_scaled(x_its[p]); X_n[:, p] .= get_x_scaled(x_it_ns[p])
+    end
+    Δ = Float64[get_delta(x_it) for x_it in x_its]
+    opts = Ref(MrbfSdStepOptions(desc_cfg.strict_backtracking, desc_cfg.max_loops, desc_cfg.armijo_const_rhs, desc_cfg.armijo_const_shrink,
+                                 desc_cfg.min_stepsize))
+    dirs = Matrix{Float64}(undef, n, ns); X₊ = Matrix{Float64}(undef, n, ns); MX₊ = Matrix{Float64}(undef, k, ns)
+    records = Vector{MrbfSdBatchRecord}(undef, ns)
+    ms = Ref{Float32}(0)
+    handles = Ptr{Cvoid}[m.handle for pl in plans for m in pl.models]          # start-major
+    roles = p1.roles
+    Aeq = Matrix{Float64}(transpose(Matrix(A_eq))); beq = Vector{Float64}(b_eq)   # row-major rows x d == the d x rows column-major matrix
+    Ain = Matrix{Float64}(transpose(Matrix(A_in))); bin = Vector{Float64}(b_in)
+    ctx = p1.models[1].ctx
+    rc = GC.@preserve handles roles Aeq beq Ain bin X X_n Δ lb ub dirs X₊ MX₊ records begin
+        prob = Ref(MrbfPsProblem(nm, k, C_NULL, pointer(roles), length(beq), length(bin),
+                                 isempty(beq) ? C_NULL : pointer(Aeq), isempty(beq) ? C_NULL : pointer(beq),
+                                 isempty(bin) ? C_NULL : pointer(Ain), isempty(bin) ? C_NULL : pointer(bin), -1.0))
+        _locked(ctx) do hctx
+            ccall((:mrbf_sd_iterate_batch, libmrbf), Int32,
+                  (Ptr{Cvoid}, Int64, Ref{MrbfPsProblem}, Ptr{Ptr{Cvoid}}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                   Ptr{Float64}, Int32, Ref{MrbfSdStepOptions}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{MrbfSdBatchRecord},
+                   Ref{Float32}),
+                  hctx, ns, prob, handles, X, X_n, Δ, lb, ub, desc_cfg.normalize, opts, dirs, X₊, MX₊, records, ms)
+        end
+    end
+    rc != 0 && _fallback_rc(9, rc) && return loop()            # a shape outside the device path: the single-start functions
+    _check(ctx, rc)
+    Xet = eltype(get_x_scaled(x_it_ns[1]))
+    return map(1:ns) do p
+        r = records[p]
+        r.sd_status == 3 && return single(p)                   # MRBF_SD_GAVE_UP: Morbit's JuMP model for this start alone
+        r.sigma > desc_cfg.min_stepsize ||
+            return 0, Xet.(dirs[:, p]), copy(get_x_scaled(x_it_ns[p])), Xet.(MX₊[:, p]), 0    # descent.jl:317
+        (Xet(r.omega), Xet.(dirs[:, p]), Xet.(X₊[:, p]), Xet.(MX₊[:, p]), Xet(r.step_norm))
+    end
 end
 
 # ---- site selection on the device -----------------------------------------------------------------------------------------------------
