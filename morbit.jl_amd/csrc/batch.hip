@@ -247,27 +247,10 @@ static int run_small_batch(mrbf_ctx *ctx, const std::vector<int64_t> &idx, const
         probs[i].mean_given = 1;  // small_mean_kernel below: the queries are centred beside the fit, not after it
         for (int e = 0; e < 2; ++e) {
             EvalDesc &E = evs[(size_t)e * P + i];  // [residual evaluations of all problems | query evaluations of all problems]
-            const int64_t m = e == 0 ? (check ? pr.n : 0) : pr.m;
+            eval_desc_model(E, &M, e == 0 ? (check ? pr.n : 0) : pr.m, e == 0 ? L.nsplit0 : L.nsplit1);
             E.X = e == 0 ? C : X;
-            E.mean = M.mean;
             E.Xq = base + (e == 0 ? L.Xq0 : L.Xq1);
             E.xsq = base + (e == 0 ? L.xsq0 : L.xsq1);
-            E.Cc = M.Xc;
-            E.csq = M.sq;
-            E.Wc = M.Wc;
-            E.lam = M.lam;
-            E.npad = L.npad;
-            E.mpad = e == 0 ? L.mpad0 : L.mpad1;
-            E.m = m;
-            E.d = pr.d;
-            E.k = pr.k;
-            E.q = L.q;
-            E.nsplit = e == 0 ? L.nsplit0 : L.nsplit1;
-            const int ntiles = (int)((pr.n + 63) / 64);
-            E.ntiles = ntiles;
-            E.nsub = (int)((pr.n + 15) / 16);
-            E.tiles_per_split = (ntiles + E.nsplit - 1) / E.nsplit;
-            E.kp = M.kp;
             E.vpart = base + (e == 0 ? L.vp0 : L.vp1);
             E.sapart = E.vpart + (size_t)E.nsplit * E.mpad * L.KO;
             E.gpart = base + (e == 0 ? L.gp0 : L.gp1);

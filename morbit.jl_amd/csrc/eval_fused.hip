@@ -1,8 +1,8 @@
-// Fused batched surrogate evaluation on the fp64 matrix cores (dpad <= 128).
+// Fused batched surrogate evaluation on the fp64 matrix cores (dpad in {64, 128, 256}).
 //
 // For a block of 64 query points and a run of 64-centre tiles, per tile:
 //   1. S'[c][q] = <cc_c, xc_q>                     MFMA, A operand = centre tile from LDS, B operand = query fragments (kept in
-//                                                  registers for the whole kernel, or in LDS when two outputs share a pass at D = 128)
+//                                                  registers for the whole kernel)
 //   2. s = |xc_q|^2 + |cc_c|^2 - 2 S', phi(s), psi(s);  per output l:  v_l[q] += w_lc phi,  a_lc = w_lc psi
 //   3. G_l'[t][q] += cc_c[t] a_lc                  MFMA: the a_l tile sits in the C/D register layout with the summed
 //                                                  index c on its ROW axis, which is exactly the B-operand layout of the
@@ -13,6 +13,11 @@
 // Small models (<= 8 centre tiles, never split): the kernel's own epilogue does that (FINAL) -- no partials, no combine pass.
 // Every launch takes its operands from an EvalDesc: one by value for a single mrbf_eval, an array (blockIdx.z = problem) for the
 // batched entry points (mrbf_batch_run); the arithmetic per problem is the same, so a batch and single calls agree bit for bit.
+// Three kernels by the padded dimension: eval_fused_kernel (D = 64), eval_fused_split_kernel (D = 128 and 256: the coordinates cut in two
+// halves over two groups of waves) and eval_vals256_kernel (D = 256, values only, split centre range); launch_pass is the table of
+// which call takes which.
+#include <type_traits>
+
 #include "radial.hpp"
 #ifndef MRBF_EVAL_DBG
 #define MRBF_EVAL_DBG 0  // diagnostics builds only (tools/build_variant.sh): 1 no Jacobian epilogue, 2 no Jacobian MFMAs, 64 unpaired epilogue
@@ -27,15 +32,14 @@ typedef double v2d __attribute__((ext_vector_type(2)));
 constexpr int EQ = 64;  // queries per workgroup
 constexpr int EC = 64;  // centres per tile
 
-// QLDS: the query fragments live in LDS instead of registers (frees D / 2 VGPRs per lane: two outputs per pass fit at D = 128 without
-// accumulators in AGPRs, where the f64 MFMA runs at half rate -- tools/microbench.py)
-template <int KID, bool FAST, int KOUT, int DT, bool JAC, bool FINAL, bool QLDS>
-__global__ __launch_bounds__(256, (DT <= 4) ? 2 : 1) void eval_fused_kernel(EvalDesc one, const EvalDesc *__restrict__ many, int l0) {
-    constexpr int D = DT * 16, LDC = D + 2;
+// ---- D = 64: four waves, each with the 64 coordinates of its sixteen queries in registers (16 VGPRs) next to the Jacobian accumulators
+// of up to two outputs (KOUT x 4 tiles = 32 VGPRs); two workgroups per CU.  KOUT outputs l0 .. l0 + KOUT - 1 per pass.
+template <int KID, bool FAST, int KOUT, bool JAC, bool FINAL>
+__global__ __launch_bounds__(256, 2) void eval_fused_kernel(EvalDesc one, const EvalDesc *__restrict__ many, int l0) {
+    constexpr int D = 64, DT = D / 16, LDC = D + 2;
     __shared__ __attribute__((aligned(16))) double Cs[EC * LDC];              // centre tile
     __shared__ double Ws[KOUT * EC];                                          // weights of the tile
     __shared__ double Sq[EC];                                                 // squared norms of the tile's centres
-    __shared__ __attribute__((aligned(16))) double Xs[QLDS ? EQ * LDC : 2];   // QLDS: the query block
     const EvalDesc &E = many ? many[blockIdx.z] : one;
     if (many && ((int64_t)blockIdx.x * EQ >= E.mpad || (int)blockIdx.y >= E.nsplit)) return;
     const double *__restrict__ Xq = E.Xq;
@@ -52,16 +56,9 @@ __global__ __launch_bounds__(256, (DT <= 4) ? 2 : 1) void eval_fused_kernel(Eval
     const int64_t qrow = q0 + wave * 16 + l15;
 
     // query fragments: B operand of phase 1, k-slice s -> Xq[qrow][4s + l4]
-    double xb[QLDS ? 1 : D / 4];
-    if constexpr (QLDS) {
-        for (int e = tid; e < EQ * D / 2; e += 256) {
-            const int row = (2 * e) / D, col = (2 * e) % D;
-            *(v2d *)&Xs[row * LDC + col] = *(const v2d *)&Xq[(q0 + row) * D + col];
-        }
-    } else {
+    double xb[D / 4];
 #pragma unroll
-        for (int s = 0; s < D / 4; ++s) xb[s] = Xq[qrow * D + 4 * s + l4];
-    }
+    for (int s = 0; s < D / 4; ++s) xb[s] = Xq[qrow * D + 4 * s + l4];
     const double xs = E.xsq[qrow];
 
     v4d JT[KOUT][DT];
@@ -134,14 +131,8 @@ __global__ __launch_bounds__(256, (DT <= 4) ? 2 : 1) void eval_fused_kernel(Eval
             // ---- phase 1
             v4d S = {0.0, 0.0, 0.0, 0.0};
             const double *crow = &Cs[(16 * ct + l15) * LDC + l4];
-            if constexpr (QLDS) {
-                const double *xrow = &Xs[(wave * 16 + l15) * LDC + l4];
 #pragma unroll
-                for (int s = 0; s < D / 4; ++s) S = __builtin_amdgcn_mfma_f64_16x16x4f64(crow[4 * s], xrow[4 * s], S, 0, 0, 0);
-            } else {
-#pragma unroll
-                for (int s = 0; s < D / 4; ++s) S = __builtin_amdgcn_mfma_f64_16x16x4f64(crow[4 * s], xb[s], S, 0, 0, 0);
-            }
+            for (int s = 0; s < D / 4; ++s) S = __builtin_amdgcn_mfma_f64_16x16x4f64(crow[4 * s], xb[s], S, 0, 0, 0);
             // ---- phase 2: C/D layout: register r <-> centre c = 16 ct + l4 + 4 r, lane & 15 <-> query
             v4d Aw[KOUT];
 #pragma unroll
@@ -234,10 +225,7 @@ __global__ __launch_bounds__(256, (DT <= 4) ? 2 : 1) void eval_fused_kernel(Eval
             for (int l = 0; l < KOUT; ++l) {
                 double acc = 0.0, cst = 0.0;
 #pragma unroll
-                for (int s = 0; s < D / 4; ++s) {
-                    const double xq = QLDS ? Xs[(wave * 16 + l15) * LDC + 4 * s + l4] : xb[QLDS ? 0 : s];
-                    acc = fma(Lm[l * D + 4 * s + l4], xq, acc);
-                }
+                for (int s = 0; s < D / 4; ++s) acc = fma(Lm[l * D + 4 * s + l4], xb[s], acc);
                 for (int t = lane; t < D; t += 64) cst = fma(Lm[l * D + t], Lm[KOUT * D + t], cst);
                 for (int off = 32; off > 0; off >>= 1) cst += __shfl_xor(cst, off);
                 acc += __shfl_xor(acc, 16);
@@ -673,6 +661,7 @@ __global__ __launch_bounds__(512, 1) void eval_vals256_kernel(EvalDesc one, cons
 }
 
 // vals[p][l0 + l] = sum_s vpart + p_l(x);   jac[p][t*k + l0 + l] = (sum_s sa) xc[p][t] - sum_s G + lam[t+1]
+// Launched only when Jacobians are wanted (jac != NULL in every descriptor; a pass for values takes eval_combine_vals_kernel below).
 // One workgroup of 128 threads per query point.  The polynomial tail of the value -- a dot product over d coordinates per output --
 // is spread over the threads that also produce the Jacobian entries and summed in a fixed order through LDS (it used to be a serial
 // d-term loop of one thread per output, the critical path of the whole workgroup: 54 us for 10^4 points at d = 64, 92 us at d = 128).
@@ -729,7 +718,6 @@ __global__ __launch_bounds__(128) void eval_combine_kernel(EvalDesc one, const E
         }
         vals[p * k + l0 + tid] = v;
     }
-    if (!jac) return;
     for (int e = tid; e < KOUT * d; e += blockDim.x) {
         const int l = e / d, t = e % d;
         if (l0 + l >= k) continue;
@@ -827,128 +815,81 @@ int eval_nsplit(const mrbf_ctx *ctx, int64_t m, int ntiles, bool check_call, boo
     // no combine pass), and such models are evaluated in batches that fill the chip anyway (mrbf_batch_run, the PS solver)
     // -- unless the query batch is small as well (at most an eighth of the workgroup slots: the populations of a PS step at d <= 24,
     // single points): the launch then is one workgroup's walk over the tiles, 35 us at n = 512 whatever m; one tile per workgroup
-    // + the combine pass: 10 + 7 us (PS step d = 12, n = 512: 7.25 -> 5.15 ms; MRBF_EVAL_NSPLIT_SMALL=1 keeps them unsplit)
-    static const int small_split = mrbf_env("MRBF_EVAL_NSPLIT_SMALL") ? atoi(mrbf_env("MRBF_EVAL_NSPLIT_SMALL")) : 8;
+    // + the combine pass: 10 + 7 us (PS step d = 12, n = 512: 7.25 -> 5.15 ms)
+    constexpr int small_split = 8;  // (at most so many pieces: with 4 ... 8 tiles, one tile per workgroup)
     // (the same rule for a member of a batch -- bit-identical to the single call --: batch.hip launches split and unsplit members apart)
     // Not for the residual check (the model at its own sites: m = n): in a batch of 64 starts those launches fill the chip together and
     // splitting them cost C4 1.6 % (19 540 against 19 870 problems/s, three alternating runs); the single fit's check follows the same rule.
     const bool small_batch = !check_call && qtiles * 8 <= slots;
-    if (ntiles >= 4 && ntiles <= 8 && small_split > 1 && small_batch) return std::min(small_split, ntiles);
+    if (ntiles >= 4 && ntiles <= 8 && small_batch) return std::min(small_split, ntiles);
     // the PS solver's populations (`population`, values only): a query batch that fills less than half of the workgroup slots
     // (round 6: the ideal-point populations of a step at d = 128, 5160 points on n = 257 sites = 81 unsplit workgroups on 256 CUs, 40 us
     // per generation) takes one tile per workgroup + the combine pass, which for values reads a few bytes per point.  Only there: the
     // API's own calls keep ONE rule for values and Jacobians (a values-only call and a call with Jacobians return the same bits, and so
     // does a member of a batch: tests/test_gpu_configs.py), and C4's batches fill the chip by their number.
-    static const int vals_split = mrbf_env("MRBF_EVAL_NSPLIT_VALS") ? atoi(mrbf_env("MRBF_EVAL_NSPLIT_VALS")) : 1;
-    if (population && vals_split && !check_call && ntiles >= 4 && ntiles <= 8 && qtiles * 2 <= slots) return (int)std::min<int64_t>(ntiles, slots / qtiles);
+    if (population && !check_call && ntiles >= 4 && ntiles <= 8 && qtiles * 2 <= slots) return (int)std::min<int64_t>(ntiles, slots / qtiles);
     if (ntiles <= 8) return 1;
-    static const double comb_small = mrbf_env("MRBF_EVAL_COMB_SMALL") ? atof(mrbf_env("MRBF_EVAL_COMB_SMALL")) : 0.1;
+    constexpr double comb_small = 0.1, comb = 0.75;  // the combine pass per split, in tile-times: for a small query batch it reads next to nothing
     int nsplit = 1;
     double best_cost = 1e300;
     for (int s = 1; s <= std::min(ntiles, 32); ++s) {
         const int tps_s = (ntiles + s - 1) / s;
         if ((int64_t)(s - 1) * tps_s >= ntiles) continue;  // the last piece would be empty
         const double rounds = std::ceil((double)(qtiles * s) / slots);
-        const double cost = rounds * tps_s + (small_batch ? comb_small : 0.75) * s;  // (a small query batch: the combine pass reads next to nothing)
+        const double cost = rounds * tps_s + (small_batch ? comb_small : comb) * s;
         if (cost < best_cost) {
             best_cost = cost;
             nsplit = s;
         }
     }
-    static const int force_split = mrbf_env("MRBF_EVAL_NSPLIT") ? atoi(mrbf_env("MRBF_EVAL_NSPLIT")) : 0;
+    // MRBF_EVAL_NSPLIT forces the split count of a model with more than 8 tiles (tools/eval_vals_sweep.py); read per call.  It is the only
+    // evaluation switch left, and it selects no other kernel.
+    const int force_split = mrbf_env("MRBF_EVAL_NSPLIT") ? atoi(mrbf_env("MRBF_EVAL_NSPLIT")) : 0;
     if (force_split > 0 && force_split <= ntiles && (int64_t)(force_split - 1) * ((ntiles + force_split - 1) / force_split) < ntiles)
         nsplit = force_split;
     return nsplit;
 }
 
-// outputs per pass: two when the model has several (at D = 128 with the query block in LDS)
-int outputs_per_pass(int k, int D, bool want_jac) {
-    static const int ko128 = mrbf_env("MRBF_EVAL_KO128") ? atoi(mrbf_env("MRBF_EVAL_KO128")) : 2;
-    static const int ko256 = mrbf_env("MRBF_EVAL_KO256") ? atoi(mrbf_env("MRBF_EVAL_KO256")) : 2;
-    // D = 256: the Jacobian tiles of one output fill the accumulator budget; a pass for values only carries no such tiles and takes two
-    // outputs -- the distances, the radial function and the centre traffic once instead of twice (a population of the PS solver at
-    // d = 256, k = 2: 2 x 161 -> 1 x ~170 us per generation)
-    if (D == 256) return (want_jac || k < 2) ? 1 : ko256;
-    return k >= 2 ? (D == 128 ? ko128 : 2) : 1;
-}
+// outputs per pass: two when the model has several -- except with Jacobians at D = 256, where the Jacobian tiles of one output fill the
+// accumulator budget; a pass for values only carries no such tiles and takes two outputs there as well -- the distances, the radial
+// function and the centre traffic once instead of twice (a population of the PS solver at d = 256, k = 2: 2 x 161 -> 1 x ~170 us per
+// generation)
+int outputs_per_pass(int k, int D, bool want_jac) { return (k < 2 || (D == 256 && want_jac)) ? 1 : 2; }
 
-template <int KID, bool FAST, int KOUT, int DT, bool QLDS>
-static int launch_fused3(mrbf_ctx *ctx, bool want_jac, bool final_, dim3 grid, const EvalDesc &one, const EvalDesc *many, int l0) {
-#define MRBF_EFL(JACV, FINV) \
-    hipLaunchKernelGGL((eval_fused_kernel<KID, FAST, KOUT, DT, JACV, FINV, QLDS>), grid, dim3(256), 0, ctx->stream, one, many, l0)
-    if (want_jac && final_)
-        MRBF_EFL(true, true);
-    else if (want_jac)
-        MRBF_EFL(true, false);
-    else if (final_)
-        MRBF_EFL(false, true);
-    else
-        MRBF_EFL(false, false);
-#undef MRBF_EFL
-    return 0;
-}
-template <int KID, bool FAST, int KOUT, int H, int ECT>
-static int launch_split_b(mrbf_ctx *ctx, bool want_jac, bool final_, dim3 grid, const EvalDesc &one, const EvalDesc *many, int l0) {
-#define MRBF_EFL(JACV, FINV) \
-    hipLaunchKernelGGL((eval_fused_split_kernel<KID, FAST, KOUT, H, ECT, JACV, FINV>), grid, dim3(512), 0, ctx->stream, one, many, l0)
-    if (want_jac && final_)
-        MRBF_EFL(true, true);
-    else if (want_jac)
-        MRBF_EFL(true, false);
-    else if (final_)
-        MRBF_EFL(false, true);
-    else
-        MRBF_EFL(false, false);
-#undef MRBF_EFL
-    return 0;
-}
-template <int KID, int KOUT, int H, int ECT>
-static int launch_split(mrbf_ctx *ctx, bool want_jac, bool final_, dim3 grid, const KP &kp, const EvalDesc &one, const EvalDesc *many, int l0) {
-    if (kp.fast && (KID == MRBF_MULTIQUADRIC || KID == MRBF_INV_MULTIQUADRIC || KID == MRBF_CUBIC))
-        return launch_split_b<KID, true, KOUT, H, ECT>(ctx, want_jac, final_, grid, one, many, l0);
-    return launch_split_b<KID, false, KOUT, H, ECT>(ctx, want_jac, final_, grid, one, many, l0);
-}
-
-template <int KID, int KOUT, int H, int ECT>
-static int launch_split_vals(mrbf_ctx *ctx, bool final_, dim3 grid, const KP &kp, const EvalDesc &one, const EvalDesc *many, int l0) {
-    const bool fast = kp.fast && (KID == MRBF_MULTIQUADRIC || KID == MRBF_INV_MULTIQUADRIC || KID == MRBF_CUBIC);
-    static const int wide = mrbf_env("MRBF_EVAL_WIDE256") ? atoi(mrbf_env("MRBF_EVAL_WIDE256")) : 1;
-    if (H == 128 && !final_ && wide) {  // values only, split centre range: one wave per sixteen queries with all 256 coordinates
-        const dim3 g2((grid.x + 1) / 2, grid.y, grid.z);
-        if (fast)
-            hipLaunchKernelGGL((eval_vals256_kernel<KID, true, KOUT>), g2, dim3(512), 0, ctx->stream, one, many, l0);
-        else
-            hipLaunchKernelGGL((eval_vals256_kernel<KID, false, KOUT>), g2, dim3(512), 0, ctx->stream, one, many, l0);
-        return 0;
+// One pass (outputs l0 .. l0 + KOUT - 1) of one evaluation: every kernel of this file that the library launches, and when.
+//   D = 64                              eval_fused_kernel<KID, FAST, KOUT, JAC, FINAL>
+//   D = 128                             eval_fused_split_kernel<KID, FAST, KOUT, 64, 64, JAC, FINAL>
+//   D = 256, Jacobians (one output)     eval_fused_split_kernel<KID, FAST, 1, 128, 32, true, FINAL>
+//   D = 256, values only, final         eval_fused_split_kernel<KID, FAST, KOUT, 128, 32, false, true>
+//   D = 256, values only, split range   eval_vals256_kernel<KID, FAST, KOUT>   (128 queries per workgroup: half the grid)
+// and behind a pass that leaves partials (!FINAL) the combine pass: eval_combine_kernel with Jacobians, eval_combine_vals_kernel without.
+template <int KID, bool FAST, int KOUT, bool JAC, bool FINAL>
+static int launch_pass(mrbf_ctx *ctx, int D, dim3 grid, dim3 cgrid, const EvalDesc &one, const EvalDesc *many, int l0) {
+    hipStream_t st = ctx->stream;
+    if (D == 64) {
+        hipLaunchKernelGGL((eval_fused_kernel<KID, FAST, KOUT, JAC, FINAL>), grid, dim3(256), 0, st, one, many, l0);
+    } else if (D == 128) {
+        hipLaunchKernelGGL((eval_fused_split_kernel<KID, FAST, KOUT, 64, 64, JAC, FINAL>), grid, dim3(512), 0, st, one, many, l0);
+    } else if constexpr (JAC && KOUT == 1) {
+        hipLaunchKernelGGL((eval_fused_split_kernel<KID, FAST, 1, 128, 32, true, FINAL>), grid, dim3(512), 0, st, one, many, l0);
+    } else if constexpr (JAC) {
+        return fail(ctx, MRBF_EHIP, "eval_fused: a pass with Jacobians at D = 256 carries one output");  // (outputs_per_pass)
+    } else if constexpr (FINAL) {
+        hipLaunchKernelGGL((eval_fused_split_kernel<KID, FAST, KOUT, 128, 32, false, true>), grid, dim3(512), 0, st, one, many, l0);
+    } else {
+        hipLaunchKernelGGL((eval_vals256_kernel<KID, FAST, KOUT>), dim3((grid.x + 1) / 2, grid.y, grid.z), dim3(512), 0, st, one, many, l0);
     }
-#define MRBF_EFL(FASTV, FINV) \
-    hipLaunchKernelGGL((eval_fused_split_kernel<KID, FASTV, KOUT, H, ECT, false, FINV>), grid, dim3(512), 0, ctx->stream, one, many, l0)
-    if (fast && final_)
-        MRBF_EFL(true, true);
-    else if (fast)
-        MRBF_EFL(true, false);
-    else if (final_)
-        MRBF_EFL(false, true);
-    else
-        MRBF_EFL(false, false);
-#undef MRBF_EFL
+    if constexpr (!FINAL && JAC)
+        hipLaunchKernelGGL(eval_combine_kernel<KOUT>, cgrid, dim3(128), 0, st, one, many, l0, D);
+    else if constexpr (!FINAL)
+        hipLaunchKernelGGL(eval_combine_vals_kernel<KOUT>, dim3((cgrid.x + 3) / 4, cgrid.y), dim3(256), 0, st, one, many, l0);
     return 0;
 }
 
-template <int KID, int KOUT, int DT, bool QLDS>
-static int launch_fused(mrbf_ctx *ctx, bool want_jac, bool final_, dim3 grid, const KP &kp, const EvalDesc &one, const EvalDesc *many, int l0) {
-    if (kp.fast && (KID == MRBF_MULTIQUADRIC || KID == MRBF_INV_MULTIQUADRIC || KID == MRBF_CUBIC))
-        return launch_fused3<KID, true, KOUT, DT, QLDS>(ctx, want_jac, final_, grid, one, many, l0);
-    return launch_fused3<KID, false, KOUT, DT, QLDS>(ctx, want_jac, final_, grid, one, many, l0);
-}
-
-template <int KOUT>
-static void launch_combine(mrbf_ctx *ctx, bool want_jac, dim3 cgrid, const EvalDesc &one, const EvalDesc *many, int l0, int D) {
-    static const int vals_combine = mrbf_env("MRBF_EVAL_COMBINE_VALS") ? atoi(mrbf_env("MRBF_EVAL_COMBINE_VALS")) : 1;
-    if (!want_jac && vals_combine)
-        hipLaunchKernelGGL(eval_combine_vals_kernel<KOUT>, dim3((cgrid.x + 3) / 4, cgrid.y), dim3(256), 0, ctx->stream, one, many, l0);
-    else
-        hipLaunchKernelGGL(eval_combine_kernel<KOUT>, cgrid, dim3(128), 0, ctx->stream, one, many, l0, D);
+// a run-time bool as a template argument: f(std::true_type{}) or f(std::false_type{})
+template <class F>
+static int with_bool(bool b, F &&f) {
+    return b ? f(std::true_type{}) : f(std::false_type{});
 }
 
 // the passes over the outputs of one evaluation (single: many == nullptr, `one` by value; batch: blockIdx.z / .y = problem)
@@ -956,43 +897,21 @@ static int run_passes(mrbf_ctx *ctx, const KP &kp, int D, int k, bool want_jac, 
                       const EvalDesc *many) {
     const int KO = outputs_per_pass(k, D, want_jac);
     for (int l0 = 0; l0 < k; l0 += KO) {
-        const int ko = std::min(KO, k - l0);
-#define MRBF_EF(KOV, DTV, QL) MRBF_DISPATCH_KID(kp.kid, MRBF_TRY((launch_fused<KID, KOV, DTV, QL>(ctx, want_jac, final_, grid, kp, one, many, l0))))
-        static const int split128 = mrbf_env("MRBF_EVAL_SPLIT128") ? atoi(mrbf_env("MRBF_EVAL_SPLIT128")) : 1;
-#define MRBF_EF128(KOV) MRBF_DISPATCH_KID(kp.kid, MRBF_TRY((launch_split<KID, KOV, 64, 64>(ctx, want_jac, final_, grid, kp, one, many, l0))))
-#define MRBF_EF256(KOV) MRBF_DISPATCH_KID(kp.kid, MRBF_TRY((launch_split<KID, KOV, 128, 32>(ctx, want_jac, final_, grid, kp, one, many, l0))))
-        if (D == 256 && ko == 2) {  // (values only)
-            MRBF_DISPATCH_KID(kp.kid, MRBF_TRY((launch_split_vals<KID, 2, 128, 32>(ctx, final_, grid, kp, one, many, l0))));
-            if (!final_) launch_combine<2>(ctx, want_jac, cgrid, one, many, l0, D);
-        } else if (D == 256) {
-            if (!want_jac) {
-                MRBF_DISPATCH_KID(kp.kid, MRBF_TRY((launch_split_vals<KID, 1, 128, 32>(ctx, final_, grid, kp, one, many, l0))));
-            } else {
-                MRBF_EF256(1);
-            }
-            if (!final_) launch_combine<1>(ctx, want_jac, cgrid, one, many, l0, D);
-        } else if (ko == 2) {
-            if (D == 64) {
-                MRBF_EF(2, 4, false);
-            } else if (split128) {
-                MRBF_EF128(2);
-            } else {
-                MRBF_EF(2, 8, true);
-            }
-            if (!final_) launch_combine<2>(ctx, want_jac, cgrid, one, many, l0, D);
-        } else {
-            if (D == 64) {
-                MRBF_EF(1, 4, false);
-            } else if (split128) {
-                MRBF_EF128(1);
-            } else {
-                MRBF_EF(1, 8, false);
-            }
-            if (!final_) launch_combine<1>(ctx, want_jac, cgrid, one, many, l0, D);
-        }
-#undef MRBF_EF
-#undef MRBF_EF128
-#undef MRBF_EF256
+        const bool two = std::min(KO, k - l0) == 2;
+        MRBF_DISPATCH_KID(kp.kid, {
+            // (the fast radial functions exist for these three kernels only: rbf_phi_psi_t)
+            constexpr bool HAS_FAST = KID == MRBF_MULTIQUADRIC || KID == MRBF_INV_MULTIQUADRIC || KID == MRBF_CUBIC;
+            MRBF_TRY(with_bool(HAS_FAST && kp.fast, [&](auto fast) {
+                return with_bool(two, [&](auto two_) {
+                    return with_bool(want_jac, [&](auto jac) {
+                        return with_bool(final_, [&](auto fin) {
+                            return launch_pass<KID, HAS_FAST && decltype(fast)::value, decltype(two_)::value ? 2 : 1, decltype(jac)::value, decltype(fin)::value>(
+                                ctx, D, grid, cgrid, one, many, l0);
+                        });
+                    });
+                });
+            }));
+        });
     }
     MRBF_HIP(ctx, hipGetLastError());
     return 0;
@@ -1031,7 +950,7 @@ int eval_fused_batch(mrbf_ctx *ctx, const KP &kp, int D, int k, bool want_jac, c
 }
 
 int eval_fused(mrbf_ctx *ctx, const mrbf_model *M, int64_t m, const double *X, double *vals, double *jac, mrbf_eval_info *info, EvalHints hints) {
-    const int d = M->d, k = M->k, q = M->q;
+    const int d = M->d, k = M->k;
     const int D = (M->dpad <= 64) ? 64 : (M->dpad <= 128 ? 128 : 256);
     if (M->dpad > 256) return fail(ctx, MRBF_EHIP, "eval_fused supports d <= 256");
     if (D != M->dpad) return fail(ctx, MRBF_EHIP, "eval_fused needs dpad in {64, 128, 256} (got %d)", M->dpad);
@@ -1042,25 +961,10 @@ int eval_fused(mrbf_ctx *ctx, const mrbf_model *M, int64_t m, const double *X, d
     const int KO = outputs_per_pass(k, D, jac != nullptr);
     EvalDesc E;
     std::memset(&E, 0, sizeof(E));
+    eval_desc_model(E, M, m, nsplit);
     E.X = X;
-    E.mean = M->mean;
     MRBF_TRY(get_buf(ctx, S_EVAL_XC, (size_t)mpad * D, &E.Xq));
     MRBF_TRY(get_buf(ctx, S_EVAL_XSQ, (size_t)mpad, &E.xsq));
-    E.Cc = M->Xc;
-    E.csq = M->sq;
-    E.Wc = M->Wc;
-    E.lam = M->lam;
-    E.npad = M->npad;
-    E.mpad = mpad;
-    E.m = m;
-    E.d = d;
-    E.k = k;
-    E.q = q;
-    E.nsplit = nsplit;
-    E.ntiles = ntiles;
-    E.nsub = (int)((M->n + 15) / 16);
-    E.tiles_per_split = (ntiles + nsplit - 1) / nsplit;
-    E.kp = M->kp;
     if (nsplit > 1) {
         MRBF_TRY(get_buf(ctx, S_EVAL_SA, (size_t)nsplit * mpad * KO * 2, &E.vpart));
         E.sapart = E.vpart + (size_t)nsplit * mpad * KO;

@@ -267,25 +267,10 @@ extern "C" int32_t mrbf_sd_iterate_batch(mrbf_ctx *ctx, int64_t n_starts, const 
             const size_t p = (size_t)mb.p;
             EvalDesc E;
             std::memset(&E, 0, sizeof(E));
+            eval_desc_model(E, M, site_m(mb.site), S.nsplit);
             E.X = mb.site == SITE_PAIR ? dPairs + p * 2 * d : (mb.site == SITE_X ? dPairs + p * 2 * d + d : dX + p * (size_t)(L + 2) * d);
-            E.mean = M->mean;
             E.Xq = base + S.Xq;
             E.xsq = base + S.xsq;
-            E.Cc = M->Xc;
-            E.csq = M->sq;
-            E.Wc = M->Wc;
-            E.lam = M->lam;
-            E.npad = M->npad;
-            E.mpad = S.mpad;
-            E.m = site_m(mb.site);
-            E.d = d;
-            E.k = M->k;
-            E.q = M->q;
-            E.nsplit = S.nsplit;
-            E.ntiles = (int)((M->n + 63) / 64);
-            E.nsub = (int)((M->n + 15) / 16);
-            E.tiles_per_split = (E.ntiles + E.nsplit - 1) / E.nsplit;
-            E.kp = M->kp;
             if (S.nsplit > 1) {
                 E.vpart = base + S.vpart;
                 E.sapart = E.vpart + (size_t)S.nsplit * S.mpad * S.KO;

@@ -77,11 +77,32 @@ struct EvalDesc {
     double *vpart, *sapart, *gpart;     // per-split partials (scratch)
     double *vals, *jac;                 // m x k, m x (k x d column-major); jac may be NULL for the whole batch only
 };
+// everything a descriptor derives from the model, the number of query points and the split of the centre range (eval_nsplit): a single
+// call and a member of a batch must agree on all of it to agree bit for bit.  The buffers -- X, Xq, xsq, vpart, sapart, gpart, vals,
+// jac -- are the caller's to set.
+inline void eval_desc_model(EvalDesc &E, const mrbf_model *M, int64_t m, int nsplit) {
+    E.mean = M->mean;
+    E.Cc = M->Xc;
+    E.csq = M->sq;
+    E.Wc = M->Wc;
+    E.lam = M->lam;
+    E.npad = M->npad;
+    E.d = M->d;
+    E.k = M->k;
+    E.q = M->q;
+    E.kp = M->kp;
+    E.m = m;
+    E.mpad = round_up(m, 64);
+    E.nsplit = nsplit;
+    E.ntiles = (int)((M->n + 63) / 64);
+    E.nsub = (int)((M->n + 15) / 16);
+    E.tiles_per_split = (E.ntiles + nsplit - 1) / nsplit;
+}
 // the centre-range split a single mrbf_eval of m points on a model with ntiles tiles of 64 centres uses (the batch takes the same one, so
 // that a batch and single calls add up their partial sums in the same order)
 int eval_nsplit(const mrbf_ctx *ctx, int64_t m, int ntiles, bool check_call = false, bool population = false);  // ntiles = ceil(n / 64); check_call: the residual check's evaluation at the sites; population: a PS population sweep (EvalHints)
 int outputs_per_pass(int k, int D, bool want_jac = true);  // outputs of a model the fused evaluation handles per pass
-// all descriptors: same kernel id / fast flag / padded dimension D (64 or 128) / k; dev_descs = the same array in device memory
+// all descriptors: same kernel id / fast flag / padded dimension D (64, 128 or 256) / k; dev_descs = the same array in device memory
 // centred: the descriptors' Xq / xsq are already filled (center_pad_batch on all descriptors of a batch, launched beside the fit)
 int eval_fused_batch(mrbf_ctx *ctx, const KP &kp, int D, int k, bool want_jac, const EvalDesc *host_descs, const EvalDesc *dev_descs, int count,
                      bool centred = false);

@@ -148,3 +148,7 @@ def test_environment_switches_sit_behind_one_gate(lib):
         names.update(re.findall(r"mrbf_env\(\"(MRBF_[A-Z0-9_]+)\"\)", open(path).read()))
     missing = sorted(n for n in names if ("`%s`" % n) not in doc)
     assert not missing, "switches missing from INTEGRATION.md's appendix: %s" % missing
+    # ... and the appendix lists nothing that the sources no longer read (a switch that was retired leaves the list with its code)
+    listed = set(re.findall(r"^\| `(MRBF_[A-Z0-9_]+)` \|", doc[doc.index("## Appendix: every environment switch"):], flags=re.M))
+    stale = sorted(listed - names)
+    assert not stale, "INTEGRATION.md's appendix lists switches that no source reads: %s" % stale
