@@ -198,6 +198,31 @@ int32_t mrbf_affine_scores(mrbf_ctx *ctx, int64_t mc, int32_t d, int32_t dz, con
 int32_t mrbf_affine_select(mrbf_ctx *ctx, int64_t mc, int32_t d, const double *shifted, int32_t j0, const double *Q0, int32_t max_picks,
                            double pivot_val, int32_t p_is_inf, int64_t *picked_out, int32_t *n_picked, double *Z_out);
 
+/* The pick loop for a batch of starts in one call (affine.hip): rounds 1-2 of the training-site selection of n_starts independent
+ * starts -- the filter loops (src/models/AffinelyIndependentPoints.jl:71-106, called by _find_suitable_points, RbfModel.jl:205-238)
+ * inside the reference's Threads.@threads loop over starts (examples/large_scale_benchmarks.jl:102-109, :253).  For every start p,
+ * the values of picked_out, n_picked and Z_out are, bit for bit, those of mrbf_affine_select(ctx, mc_p, d, shifted_p, j0_p, Q0_p,
+ * max_picks_p, pivot_p, p_is_inf, ...); they do not depend on the start's position in the batch or on which other starts share it.
+ * One launch per pick serves all starts (start p works at j = j0_p + t in launch t and sits out once it is done or has its
+ * max_picks picks), the host looks at the starts' "done" words every sixteen launches and reads counts and pick lists back once.
+ * The starts share d and the norm.  Returns -2 (take mrbf_affine_select per start, or the host filter) and writes nothing when
+ * mrbf_dispatch_affine_batch refuses the shape; an invalid field of a job is an invalid `jobs` (-5).  At most 2^26 candidates in
+ * all.  ms_total (may be NULL): hipEvent time of the chain on the ctx stream, without the final copies of Z_out. */
+typedef struct {
+    int64_t mc;            /* candidates of this start; 0: nothing to pick */
+    int32_t j0;            /* directions chosen so far, 0 .. d */
+    int32_t max_picks;     /* clipped to d - j0 */
+    double pivot_val;
+    const double *shifted; /* mc x d row-major, host or device; chosen sites: zero rows */
+    const double *Q0;      /* d x d column-major, host or device; NULL with j0 = 0 */
+    int64_t *picked_out;   /* host, max_picks entries (may be NULL when max_picks = 0) */
+    double *Z_out;         /* d x (d - j0 - n_picked) column-major, host or device, may be NULL */
+    int32_t n_picked;      /* out */
+    int32_t reserved;
+} mrbf_affine_job;
+int32_t mrbf_affine_select_batch(mrbf_ctx *ctx, int64_t n_starts, int32_t d, int32_t p_is_inf, mrbf_affine_job *jobs,
+                                 float *ms_total);
+
 /* ---- round 4 of the training-site selection on the device, with factor reuse -------------------------------------------
  * mrbf_round4 replaces _rbf_round4 (src/models/RbfModel.jl:352-499): start_sites (n0 x d, the sites found so far -- centre and
  * rounds 1-3 -- which must carry the polynomial tail: n0 >= q, full rank) and cand_sites (mc x d, the database candidates in
@@ -514,6 +539,10 @@ int32_t mrbf_sd_iterate_batch(mrbf_ctx *ctx, int64_t n_starts, const mrbf_ps_pro
  *                            device model (then mrbf_backtrack applies); otherwise the reference loop (on batched container
  *                            sweeps where the binding has them).
  *   mrbf_dispatch_affine     candidate scan of the affinely-independent-point filter (AffinelyIndependentPoints.jl:71-106).
+ *   mrbf_dispatch_affine_batch  the filters of n_starts starts in one call (mrbf_affine_select_batch): device iff
+ *                            1 <= n_starts <= 65535 (a grid dimension), the inf-norm and 8 (d + 1) coordinates of 8 bytes within
+ *                            64 KiB of LDS (d <= 1023) -- the range of the one-launch-per-pick kernel.  Whether a start's filter is
+ *                            worth the device at all stays mrbf_dispatch_affine's decision, start by start.
  *   mrbf_dispatch_round4     _rbf_round4 (src/models/RbfModel.jl:352-499): device iff the start set can carry the tail (n0 >= q)
  *                            and there are candidates.
  *   mrbf_dispatch_fit        update_model (RbfModel.jl:743-767): MRBF_FIT_FROM_ROUND4 iff a kept round-4 state describes exactly
@@ -536,7 +565,7 @@ int32_t mrbf_sd_iterate_batch(mrbf_ctx *ctx, int64_t n_starts, const mrbf_ps_pro
 enum { MRBF_DISPATCH_REFERENCE = 0, MRBF_DISPATCH_DEVICE = 1 };
 enum { MRBF_FIT_FULL = 0, MRBF_FIT_FROM_ROUND4 = 1 };
 enum { MRBF_ENTRY_ROUND4 = 1, MRBF_ENTRY_FIT_FROM_ROUND4 = 2, MRBF_ENTRY_PS_STEP = 3, MRBF_ENTRY_BACKTRACK = 4, MRBF_ENTRY_AFFINE = 5,
-       MRBF_ENTRY_SD = 6, MRBF_ENTRY_NORMAL = 7, MRBF_ENTRY_SD_STEP = 8, MRBF_ENTRY_SD_BATCH = 9 };
+       MRBF_ENTRY_SD = 6, MRBF_ENTRY_NORMAL = 7, MRBF_ENTRY_SD_STEP = 8, MRBF_ENTRY_SD_BATCH = 9, MRBF_ENTRY_AFFINE_BATCH = 10 };
 int32_t mrbf_dispatch_ps(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_sd(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_normal(int32_t d, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
@@ -546,6 +575,7 @@ int32_t mrbf_dispatch_sd_batch(int64_t n_starts, int32_t d, int32_t k, int32_t n
                                int32_t n_lin_constraints, int32_t n_foreign, int32_t max_loops);
 int32_t mrbf_dispatch_backtrack(int32_t n_objective_models, int32_t n_foreign, int32_t outputs_in_order);
 int32_t mrbf_dispatch_affine(int64_t n_candidates, int32_t d);
+int32_t mrbf_dispatch_affine_batch(int64_t n_starts, int32_t d, int32_t p_is_inf);
 int32_t mrbf_dispatch_round4(int64_t n0, int32_t d, int32_t poly_deg, int64_t n_candidates);
 int32_t mrbf_dispatch_fit(int64_t n_training, int64_t state_n0, int32_t state_q, int32_t state_n_accepted, int32_t same_sites);
 int32_t mrbf_dispatch_after(int32_t entry, int32_t rc);

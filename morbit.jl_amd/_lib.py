@@ -60,6 +60,7 @@ DISPATCH_REFERENCE, DISPATCH_DEVICE = 0, 1
 FIT_FULL, FIT_FROM_ROUND4 = 0, 1
 ENTRY_ROUND4, ENTRY_FIT_FROM_ROUND4, ENTRY_PS_STEP, ENTRY_BACKTRACK, ENTRY_AFFINE, ENTRY_SD, ENTRY_NORMAL, ENTRY_SD_STEP = 1, 2, 3, 4, 5, 6, 7, 8
 ENTRY_SD_BATCH = 9
+ENTRY_AFFINE_BATCH = 10
 SD_OK, SD_NO_OBJECTIVE, SD_INFEASIBLE, SD_GAVE_UP = 0, 1, 2, 3
 NS_OK, NS_INFEASIBLE, NS_GAVE_UP = 0, 1, 2
 SD_BRANCH_DELTA, SD_BRANCH_ONE, SD_BRANCH_INTERSECT = 0, 1, 2
@@ -110,6 +111,13 @@ class SdBatchRecord(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class AffineJob(ctypes.Structure):
+    """mrbf_affine_job: one start of mrbf_affine_select_batch"""
+    _fields_ = [("mc", ctypes.c_int64), ("j0", ctypes.c_int32), ("max_picks", ctypes.c_int32), ("pivot_val", ctypes.c_double),
+                ("shifted", ctypes.c_void_p), ("Q0", ctypes.c_void_p), ("picked_out", ctypes.c_void_p), ("Z_out", ctypes.c_void_p),
+                ("n_picked", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class Problem(ctypes.Structure):
     _fields_ = [("n", ctypes.c_int64), ("m", ctypes.c_int64), ("d", ctypes.c_int32), ("k", ctypes.c_int32),
                 ("kernel_id", ctypes.c_int32), ("poly_deg", ctypes.c_int32), ("a", ctypes.c_double), ("b", ctypes.c_double),
@@ -150,6 +158,7 @@ SIGNATURES = {
                                             ctypes.POINTER(ctypes.c_int64), c_dp]),
     "mrbf_affine_select": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.c_int32, c_vp, ctypes.c_int32, c_vp, ctypes.c_int32, ctypes.c_double,
                                             ctypes.c_int32, ctypes.POINTER(ctypes.c_int64), c_ip, c_vp]),
+    "mrbf_affine_select_batch": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(AffineJob), c_fp]),
     "mrbf_round4": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.c_int32, c_vp, ctypes.c_int64, c_vp, ctypes.c_int32, ctypes.c_double,
                                      ctypes.c_double, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, c_vp, c_ip, ctypes.POINTER(c_vp)]),
     "mrbf_fit_from_round4": (ctypes.c_int32, [c_vp, c_vp, ctypes.c_int32, c_vp, ctypes.POINTER(c_vp), c_vp, c_vp, ctypes.POINTER(FitInfo)]),
@@ -194,6 +203,7 @@ SIGNATURES = {
     "mrbf_dispatch_normal": (ctypes.c_int32, [ctypes.c_int32] * 5),
     "mrbf_dispatch_backtrack": (ctypes.c_int32, [ctypes.c_int32] * 3),
     "mrbf_dispatch_affine": (ctypes.c_int32, [ctypes.c_int64, ctypes.c_int32]),
+    "mrbf_dispatch_affine_batch": (ctypes.c_int32, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
     "mrbf_dispatch_round4": (ctypes.c_int32, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64]),
     "mrbf_dispatch_fit": (ctypes.c_int32, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "mrbf_dispatch_after": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32]),

@@ -121,7 +121,10 @@ __global__ __launch_bounds__(256) void affsel_score_kernel(AffSel a, int j) {
 }
 
 // C[:, c] = Q' s_c for eight candidates per workgroup (once per call): thread i owns row i of the eight products
-__global__ __launch_bounds__(256) void affsel_project_kernel(AffSel a, const double *__restrict__ S) {
+// (the bodies below are templates over the view: AffSel with the kernel's own arguments, whose pointers the compiler knows to be global
+// memory, or AffSelG for pointers that come out of a descriptor in memory -- typed as global there, or every access would be a flat one)
+template <class View, class Sites>
+__device__ __forceinline__ void affsel_project_body(const View &a, const Sites S) {
     extern __shared__ double sx[];  // [AFF_G][d]
     const int tid = threadIdx.x, d = a.d;
     const int64_t c0 = (int64_t)blockIdx.x * AFF_G;
@@ -134,7 +137,7 @@ __global__ __launch_bounds__(256) void affsel_project_kernel(AffSel a, const dou
         double u[AFF_G];
 #pragma unroll
         for (int g = 0; g < AFF_G; ++g) u[g] = 0.0;
-        const double *q = a.Q + (size_t)i * d;
+        const auto q = a.Q + (size_t)i * d;
         for (int r = 0; r < d; ++r) {
             const double z = q[r];
 #pragma unroll
@@ -145,6 +148,7 @@ __global__ __launch_bounds__(256) void affsel_project_kernel(AffSel a, const dou
             if (c0 + g < a.mc) a.C[(size_t)(c0 + g) * d + i] = u[g];
     }
 }
+__global__ __launch_bounds__(256) void affsel_project_kernel(AffSel a, const double *__restrict__ S) { affsel_project_body(a, S); }
 
 // ONE launch per pick (inf-norm, d < 1024).  Every workgroup first brings its eight candidates up to date with the reflector of the pick
 // before (C[jq:, c] <- H C[jq:, c], jq = j - 1), scores them against Zs, and the LAST workgroup to finish (a ticket) takes the decision for
@@ -157,14 +161,15 @@ __device__ __forceinline__ double wave_max(double v) {
 }
 constexpr int AFF_NT = 1024;  // threads of the one-launch-per-pick kernel: the last workgroup's tail (d x (d - j) elements, three passes) is
                               // latency-bound on one CU -- sixteen waves and eight independent loads per thread hide it
-__global__ __launch_bounds__(AFF_NT) void affsel_pick_kernel(AffSel a, int j, int apply) {
+// (the body of both pick kernels, entered only while the start is not done; nwg = workgroups of THIS start, what the ticket counts up to)
+template <class View>
+__device__ __forceinline__ void affsel_pick_body(const View &a, const int j, const int apply, const int nwg) {
     extern __shared__ double sx[];  // [AFF_G][dz + 1]: the candidates' coordinates from row j - 1 on (last block afterwards: column maxima)
     __shared__ double red[AFF_NT];
     __shared__ long long redi[AFF_NT];
     __shared__ double s_scal[4];
     __shared__ int s_last;
     const int tid = threadIdx.x, lane = tid & 63, d = a.d, dz = d - j, ldx = dz + 1;
-    if (a.state[0]) return;
     unsigned long long st[12];
     int nst = 0;
 #define AFF_STAMP() do { if (a.stamps && tid == 0 && nst < 12) st[nst++] = __builtin_amdgcn_s_memrealtime(); } while (0)
@@ -179,7 +184,7 @@ __global__ __launch_bounds__(AFF_NT) void affsel_pick_kernel(AffSel a, int j, in
     if (apply) {  // x <- x - tau v (v' x) over rows jq .. d - 1, 32 lanes per candidate
         if (tid < 32 * AFF_G) {
             const double tau = a.hv[0];
-            const double *v = a.hv + 1;
+            const auto v = a.hv + 1;
             const int g = tid >> 5, l = tid & 31;
             double dot = 0.0;
             for (int k8 = l; k8 < ldx; k8 += 32 * 8) {
@@ -265,7 +270,7 @@ __global__ __launch_bounds__(AFF_NT) void affsel_pick_kernel(AffSel a, int j, in
     __syncthreads();
     if (tid == 0) {
         const int t = __hip_atomic_fetch_add(a.state + 2, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = t == (int)gridDim.x - 1;
+        s_last = t == nwg - 1;
     }
     __syncthreads();
     if (!s_last) return;
@@ -314,7 +319,7 @@ __global__ __launch_bounds__(AFF_NT) void affsel_pick_kernel(AffSel a, int j, in
         if (tid == 0) a.state[0] = 1;
         return;
     }
-    double *x = a.C + (size_t)best * d + j;
+    const auto x = a.C + (size_t)best * d + j;
     double part = 0.0;
     for (int c = 1 + tid; c < dz; c += AFF_NT) {
         const double xv = __hip_atomic_load(x + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -342,7 +347,7 @@ __global__ __launch_bounds__(AFF_NT) void affsel_pick_kernel(AffSel a, int j, in
     }
     __syncthreads();
     const double tau = s_scal[0], scale = s_scal[1];
-    double *v = a.hv + 1, *w = a.hv + 1 + d;
+    const auto v = a.hv + 1, w = a.hv + 1 + d;
     unsigned long long *cmax = reinterpret_cast<unsigned long long *>(sx);  // (non-negative doubles order like their bit patterns)
     double *sv = sx + dz;                                                    // v in LDS behind the column maxima (2 dz <= AFF_G (dz + 1))
     for (int c = tid; c < dz; c += AFF_NT) {
@@ -415,6 +420,10 @@ __global__ __launch_bounds__(AFF_NT) void affsel_pick_kernel(AffSel a, int j, in
     if (a.stamps && tid == 0)
         for (int q2 = 0; q2 < nst; ++q2) a.stamps[q2] = st[q2];
 #undef AFF_STAMP
+}
+__global__ __launch_bounds__(AFF_NT) void affsel_pick_kernel(AffSel a, int j, int apply) {
+    if (a.state[0]) return;
+    affsel_pick_body(a, j, apply, (int)gridDim.x);
 }
 
 // one workgroup: first maximiser of val, pivot test, the pick's reflector and w; the picked candidate becomes the zero vector
@@ -491,15 +500,16 @@ __global__ __launch_bounds__(1024) void affsel_decide_kernel(AffSel a, int j) {
 
 // blocks 0 .. d - jq - 1: column jq + b of Q gets the reflector (apply != 0) and, for columns >= jz, its p-normalised-twice copy goes to Zs;
 // the blocks behind them: four candidate columns of C each (C[jq:, col] <- H C[jq:, col])
-__global__ __launch_bounds__(256) void affsel_update_kernel(AffSel a, int jq, int jz, int apply) {
+template <class View>
+__device__ __forceinline__ void affsel_update_body(const View &a, const int jq, const int jz, const int apply) {
     __shared__ double red[256];
     const int tid = threadIdx.x, d = a.d, ncol = d - jq;
     if (a.state[0]) return;
     const double tau = apply ? a.hv[0] : 0.0;
-    const double *v = a.hv + 1, *w = a.hv + 1 + d;
+    const auto v = a.hv + 1, w = a.hv + 1 + d;
     if ((int)blockIdx.x < ncol) {
         const int c = blockIdx.x;
-        double *q = a.Q + (size_t)(jq + c) * d;
+        const auto q = a.Q + (size_t)(jq + c) * d;
         const double tv = apply ? tau * v[c] : 0.0;
         double m = 0.0;
         for (int r = tid; r < d; r += 256) {
@@ -519,7 +529,7 @@ __global__ __launch_bounds__(256) void affsel_update_kernel(AffSel a, int jq, in
         }
         const double nrm = a.use_inf ? red[0] : sqrt(red[0]);
         const double s2n = 1.0 / (nrm * nrm);  // Z Z' = Q2 D^2 Q2'
-        double *z = a.Zs + (size_t)(jq + c - jz) * d;
+        const auto z = a.Zs + (size_t)(jq + c - jz) * d;
         for (int r = tid; r < d; r += 256) z[r] = q[r] * s2n;
         return;
     }
@@ -527,17 +537,90 @@ __global__ __launch_bounds__(256) void affsel_update_kernel(AffSel a, int jq, in
     const int64_t col = ((int64_t)blockIdx.x - ncol) * 4 + (tid >> 6);
     const int lane = tid & 63;
     if (col >= a.mc) return;
-    double *x = a.C + (size_t)col * d + jq;
+    const auto x = a.C + (size_t)col * d + jq;
     double dot = 0.0;
     for (int c = lane; c < ncol; c += 64) dot = fma(v[c], x[c], dot);
     for (int off = 32; off > 0; off >>= 1) dot += __shfl_xor(dot, off);
     const double td = tau * dot;
     for (int c = lane; c < ncol; c += 64) x[c] = fma(-td, v[c], x[c]);
 }
+__global__ __launch_bounds__(256) void affsel_update_kernel(AffSel a, int jq, int jz, int apply) { affsel_update_body(a, jq, jz, apply); }
+
+// ---- the pick loop for a BATCH of starts: blockIdx.y = start, blockIdx.x = group of eight candidates ------------------------------------
+// The many-start mode (the reference's Threads.@threads loop over starts, examples/large_scale_benchmarks.jl:102-109, :253) runs one
+// filter per start; one launch per pick serves all of them, so the last workgroups' latency-bound tails -- one per start -- run side by
+// side on as many CUs and the launch cost is paid once.  The starts share d; everything else is the start's own (AffJob, an array in
+// device memory): its slices of the workspace, its candidate count, the directions it begins with, its pivot, its own done / picks /
+// ticket words.  The bodies are the single-start kernels' (above), so a start's result does not depend on the batch around it.
+struct AffJob {
+    double *Q, *C, *Zs, *val, *hv;
+    const double *S;
+    long long *picks;
+    int *state;  // [0] done, [1] picks so far, [2] ticket, [3] unused
+    int64_t mc;
+    double pivot;
+    int j0, max_picks;  // max_picks = 0: nothing to pick (no candidates, or none wanted): every kernel leaves the start alone
+};
+// AffSel with its pointers typed as global memory (what a descriptor's pointers are)
+#define AFF_GLOBAL __attribute__((address_space(1)))
+struct AffSelG {
+    AFF_GLOBAL double *Q, *C, *Zs, *val, *hv;
+    AFF_GLOBAL long long *picks;
+    AFF_GLOBAL int *state;
+    unsigned long long *stamps;
+    int d, use_inf;
+    int64_t mc;
+    double pivot;
+};
+__device__ __forceinline__ AffSelG affsel_view(const AffJob &jb, int d) {
+    AffSelG a;
+    a.Q = (AFF_GLOBAL double *)jb.Q, a.C = (AFF_GLOBAL double *)jb.C, a.Zs = (AFF_GLOBAL double *)jb.Zs;
+    a.val = (AFF_GLOBAL double *)jb.val, a.hv = (AFF_GLOBAL double *)jb.hv;
+    a.picks = (AFF_GLOBAL long long *)jb.picks, a.state = (AFF_GLOBAL int *)jb.state, a.stamps = nullptr;
+    a.d = d, a.use_inf = 1, a.mc = jb.mc, a.pivot = jb.pivot;
+    return a;
+}
+__global__ __launch_bounds__(256) void affsel_project_batch_kernel(const AffJob *__restrict__ jobs, int d) {
+    const AffJob jb = jobs[blockIdx.y];
+    if (jb.max_picks <= 0 || (int64_t)blockIdx.x * AFF_G >= jb.mc) return;
+    affsel_project_body(affsel_view(jb, d), (const AFF_GLOBAL double *)jb.S);
+}
+__global__ __launch_bounds__(256) void affsel_update_batch_kernel(const AffJob *__restrict__ jobs, int d) {  // Zs of every start's own basis
+    const AffJob jb = jobs[blockIdx.y];
+    if (jb.max_picks <= 0 || (int)blockIdx.x >= d - jb.j0) return;
+    affsel_update_body(affsel_view(jb, d), jb.j0, jb.j0, 0);
+}
+// launch t of the loop: start p works at j = j0_p + t.  A workgroup leaves before the ticket when its start is done, has its max_picks
+// picks, or has fewer groups than the grid is wide; the ticket of a start counts that start's own groups.
+// (the starts' state words sit in one array, four per start: read through `states` their loads go out together with the descriptor's
+// instead of behind it -- one memory round trip less at the head of every workgroup of every launch)
+__global__ __launch_bounds__(AFF_NT) void affsel_pick_batch_kernel(const AffJob *__restrict__ jobs, const int *states, int d, int t,
+                                                                   unsigned long long *stamps) {
+    const int done = states[4 * blockIdx.y], npk = states[4 * blockIdx.y + 1];
+    const AffJob jb = jobs[blockIdx.y];
+    const int64_t ngrp = (jb.mc + AFF_G - 1) / AFF_G;
+    if (t >= jb.max_picks || (int64_t)blockIdx.x >= ngrp) return;
+    if (done || npk >= jb.max_picks) return;
+    AffSelG a = affsel_view(jb, d);
+    if (blockIdx.y == 0) a.stamps = stamps;  // (diagnostic: the phases of start 0's last workgroup)
+    affsel_pick_body(a, jb.j0 + t, t > 0 ? 1 : 0, (int)ngrp);
+}
 
 }  // namespace mrbf
 
 using namespace mrbf;
+
+namespace {
+// Z_out of both select entry points: the columns of q (d x dz, column-major, on the host) scaled to unit p-norm, one division per element
+void normalise_columns(double *q, int d, int dz, int p_is_inf) {
+    for (int c = 0; c < dz; ++c) {
+        double nrm = 0.0;
+        for (int r = 0; r < d; ++r) nrm = p_is_inf ? std::max(nrm, std::fabs(q[(size_t)c * d + r])) : nrm + q[(size_t)c * d + r] * q[(size_t)c * d + r];
+        if (!p_is_inf) nrm = std::sqrt(nrm);
+        for (int r = 0; r < d; ++r) q[(size_t)c * d + r] /= nrm;
+    }
+}
+}  // namespace
 
 extern "C" int32_t mrbf_affine_scores(mrbf_ctx *ctx, int64_t mc, int32_t d, int32_t dz, const double *shifted, const double *Z, int32_t p_is_inf,
                                       double *vals_out, int64_t *argmax, double *maxval) {
@@ -692,13 +775,148 @@ extern "C" int32_t mrbf_affine_select(mrbf_ctx *ctx, int64_t mc, int32_t d, cons
         if (dz > 0) {
             hq.resize((size_t)d * dz);
             MRBF_HIP(ctx, hipMemcpy(hq.data(), a.Q + (size_t)jf * d, hq.size() * sizeof(double), hipMemcpyDeviceToHost));
-            for (int c = 0; c < dz; ++c) {
-                double nrm = 0.0;
-                for (int r = 0; r < d; ++r) nrm = p_is_inf ? std::max(nrm, std::fabs(hq[(size_t)c * d + r])) : nrm + hq[(size_t)c * d + r] * hq[(size_t)c * d + r];
-                if (!p_is_inf) nrm = std::sqrt(nrm);
-                for (int r = 0; r < d; ++r) hq[(size_t)c * d + r] /= nrm;
-            }
+            normalise_columns(hq.data(), d, dz, p_is_inf);
             MRBF_HIP(ctx, hipMemcpy(Z_out, hq.data(), hq.size() * sizeof(double), hipMemcpyDefault));
+        }
+    }
+    return MRBF_OK;
+}
+
+// The pick loop for n_starts filters in one call: one arena, one descriptor upload, one launch per pick for all starts, the "done" words
+// looked at every sixteen launches, one read-back of counts and pick lists (include/mrbf.h).
+extern "C" int32_t mrbf_affine_select_batch(mrbf_ctx *ctx, int64_t n_starts, int32_t d, int32_t p_is_inf, mrbf_affine_job *jobs, float *ms_total) {
+    if (!ctx) return -1;
+    if (d < 1) return fail(ctx, -3, "mrbf_affine_select_batch: d = %d", d);
+    if (!jobs) return fail(ctx, -5, "jobs is NULL");
+    if (mrbf_dispatch_affine_batch(n_starts, d, p_is_inf) != MRBF_DISPATCH_DEVICE)
+        return fail(ctx, -2, "mrbf_affine_select_batch: %lld starts, d = %d, p_is_inf = %d is outside the batched pick loop (ask mrbf_dispatch_affine_batch first)",
+                    (long long)n_starts, d, p_is_inf);
+    const size_t N = (size_t)n_starts, D = (size_t)d;
+    int64_t mc_sum = 0;
+    int T = 0;  // launches of the loop
+    int64_t ngrp_max = 0;
+    std::vector<int> want(N);
+    for (size_t p = 0; p < N; ++p) {
+        const mrbf_affine_job &jb = jobs[p];
+        if (jb.mc < 0 || jb.mc > ((int64_t)1 << 26)) return fail(ctx, -5, "jobs[%zu].mc out of range", p);
+        if (jb.j0 < 0 || jb.j0 > d) return fail(ctx, -5, "jobs[%zu].j0 must lie in [0, d]", p);
+        if (jb.j0 > 0 && !jb.Q0) return fail(ctx, -5, "jobs[%zu].Q0 is NULL", p);
+        if (jb.max_picks < 0) return fail(ctx, -5, "jobs[%zu].max_picks < 0", p);
+        if (jb.mc > 0 && !jb.shifted) return fail(ctx, -5, "jobs[%zu].shifted is NULL", p);
+        const int mp = std::min(jb.max_picks, d - jb.j0);
+        if (mp > 0 && !jb.picked_out) return fail(ctx, -5, "jobs[%zu].picked_out is NULL", p);
+        mc_sum += jb.mc;
+        if (mc_sum > ((int64_t)1 << 26)) return fail(ctx, -5, "mrbf_affine_select_batch: more than 2^26 candidates in all");
+        want[p] = jb.mc > 0 ? mp : 0;
+        if (want[p] > 0) {
+            T = std::max(T, want[p]);
+            ngrp_max = std::max(ngrp_max, (jb.mc + AFF_G - 1) / AFF_G);
+        }
+    }
+    for (size_t p = 0; p < N; ++p) jobs[p].n_picked = 0;
+    if (ms_total) *ms_total = 0.f;
+    (void)hipSetDevice(ctx->device);
+    hipStream_t s = ctx->stream;
+    // ---- the arena: state | picks | hv | descriptors | Q | Zs | val | C | S, every piece a multiple of 256 bytes (state and picks come back
+    // in one copy, descriptors and start bases go up in one)
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t hvn = 2 * D + 8, mcs = (size_t)std::max<int64_t>(mc_sum, 1);
+    const size_t bState = up(N * 4 * sizeof(int)), bPicks = up(N * D * sizeof(long long)), bDesc = up(N * sizeof(AffJob)),
+                 bHv = up(N * hvn * sizeof(double)), bQ = up(N * D * D * sizeof(double)), bVal = up(mcs * sizeof(double)),
+                 bC = up(mcs * D * sizeof(double));
+    const size_t oState = 0, oPicks = oState + bState, oHv = oPicks + bPicks, oDesc = oHv + bHv, oQ = oDesc + bDesc, oZs = oQ + bQ,
+                 oVal = oZs + bQ, oC = oVal + bVal, oS = oC + bC, total = oS + bC;
+    char *base;
+    MRBF_TRY(get_buf(ctx, S_AFF_BATCH, total, &base));
+    int *dState = reinterpret_cast<int *>(base + oState);
+    long long *dPicks = reinterpret_cast<long long *>(base + oPicks);
+    AffJob *dDesc = reinterpret_cast<AffJob *>(base + oDesc);
+    double *dHv = reinterpret_cast<double *>(base + oHv), *dQ = reinterpret_cast<double *>(base + oQ), *dZs = reinterpret_cast<double *>(base + oZs),
+           *dVal = reinterpret_cast<double *>(base + oVal), *dC = reinterpret_cast<double *>(base + oC), *dS = reinterpret_cast<double *>(base + oS);
+    static const int want_stamps = mrbf_env("MRBF_AFFINE_STAMPS") ? atoi(mrbf_env("MRBF_AFFINE_STAMPS")) : 0;
+    unsigned long long *stamps = nullptr;
+    if (want_stamps) MRBF_TRY(get_buf(ctx, S_MISC, (size_t)16, &stamps));
+    hipEvent_t e0 = ctx->ev[0], e1 = ctx->ev[1];
+    if (ms_total) MRBF_HIP(ctx, hipEventRecord(e0, s));
+    MRBF_HIP(ctx, hipMemsetAsync(dState, 0, bState, s));
+    // ---- uploads: the start bases (identity with j0 = 0) in one copy, then whatever already lives on the device; the candidates likewise
+    std::vector<char> hup(bDesc + N * D * D * sizeof(double), 0);
+    AffJob *hdesc = reinterpret_cast<AffJob *>(hup.data());
+    double *hq = reinterpret_cast<double *>(hup.data() + bDesc);
+    std::vector<char> q_dev(N, 0), s_dev(N, 0);
+    size_t coff = 0;
+    for (size_t p = 0; p < N; ++p) {
+        const mrbf_affine_job &jb = jobs[p];
+        AffJob &h = hdesc[p];
+        h.Q = dQ + p * D * D, h.Zs = dZs + p * D * D, h.hv = dHv + p * hvn, h.picks = dPicks + p * D, h.state = dState + p * 4;
+        h.C = dC + coff * D, h.S = dS + coff * D, h.val = dVal + coff;
+        h.mc = jb.mc, h.pivot = jb.pivot_val, h.j0 = jb.j0, h.max_picks = want[p];
+        coff += (size_t)jb.mc;
+        double *q = hq + p * D * D;
+        if (jb.j0 == 0) {
+            for (size_t i = 0; i < D; ++i) q[i * D + i] = 1.0;
+        } else if (is_device_ptr(jb.Q0)) {
+            q_dev[p] = 1;
+        } else {
+            std::memcpy(q, jb.Q0, D * D * sizeof(double));
+        }
+        if (want[p] > 0) s_dev[p] = is_device_ptr(jb.shifted) ? 1 : 0;
+    }
+    MRBF_HIP(ctx, hipMemcpyAsync(dDesc, hup.data(), hup.size(), hipMemcpyHostToDevice, s));
+    for (size_t p = 0; p < N; ++p)
+        if (q_dev[p]) MRBF_HIP(ctx, hipMemcpyAsync(hdesc[p].Q, jobs[p].Q0, D * D * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (T > 0) {
+        for (size_t p = 0; p < N; ++p)  // the candidates, straight from where they are (a host copy into one block first costs more than it saves)
+            if (want[p] > 0)
+                MRBF_HIP(ctx, hipMemcpyAsync(const_cast<double *>(hdesc[p].S), jobs[p].shifted, (size_t)jobs[p].mc * D * sizeof(double),
+                                             s_dev[p] ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+        // ---- C = Q' S and the start bases' Zs for every start, then one launch per pick
+        const dim3 gcand((unsigned)ngrp_max, (unsigned)N);
+        hipLaunchKernelGGL(affsel_project_batch_kernel, gcand, dim3(256), (size_t)AFF_G * D * sizeof(double), s, dDesc, d);
+        hipLaunchKernelGGL(affsel_update_batch_kernel, dim3((unsigned)d, (unsigned)N), dim3(256), 0, s, dDesc, d);
+        const size_t shm_pick_total = (size_t)AFF_G * (D + 1) * sizeof(double) + (size_t)AFF_G * AFF_NT * sizeof(double);
+        MRBF_HIP(ctx, hipFuncSetAttribute((const void *)affsel_pick_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_pick_total));
+        std::vector<int> hstate(N * 4);
+        for (int t = 0; t < T; ++t) {
+            hipLaunchKernelGGL(affsel_pick_batch_kernel, gcand, dim3(AFF_NT), shm_pick_total, s, dDesc, dState, d, t, stamps);
+            if (t == 0) MRBF_HIP(ctx, hipGetLastError());
+            if ((t & 15) == 15 && t + 1 < T) {  // every start done, or with all the picks it wanted?
+                MRBF_HIP(ctx, hipMemcpyAsync(hstate.data(), dState, N * 4 * sizeof(int), hipMemcpyDeviceToHost, s));
+                MRBF_HIP(ctx, hipStreamSynchronize(s));
+                bool all_done = true;
+                for (size_t p = 0; p < N && all_done; ++p) all_done = hstate[p * 4] != 0 || hstate[p * 4 + 1] >= want[p];
+                if (all_done) break;
+            }
+        }
+        MRBF_HIP(ctx, hipGetLastError());
+    }
+    // ---- one read-back: per-start counts and pick lists (state and picks are neighbours in the arena)
+    std::vector<char> hback(bState + N * D * sizeof(long long));
+    MRBF_HIP(ctx, hipMemcpyAsync(hback.data(), base + oState, hback.size(), hipMemcpyDeviceToHost, s));
+    if (ms_total) MRBF_HIP(ctx, hipEventRecord(e1, s));
+    MRBF_HIP(ctx, hipStreamSynchronize(s));
+    if (ms_total) MRBF_HIP(ctx, hipEventElapsedTime(ms_total, e0, e1));
+    if (stamps && T > 0) {  // phases of start 0's last workgroup in the last launch it took part in, us since its start
+        unsigned long long hst[12];
+        MRBF_HIP(ctx, hipMemcpy(hst, stamps, sizeof(hst), hipMemcpyDeviceToHost));
+        fprintf(stderr, "affsel_pick_batch_kernel phases (us):");
+        for (int q2 = 1; q2 < 10; ++q2) fprintf(stderr, " %.2f", (double)(hst[q2] - hst[0]) * 0.01);
+        fprintf(stderr, "\n");
+    }
+    const int *hst_all = reinterpret_cast<const int *>(hback.data());
+    const long long *hpk = reinterpret_cast<const long long *>(hback.data() + bState);
+    std::vector<double> hz;
+    for (size_t p = 0; p < N; ++p) {
+        mrbf_affine_job &jb = jobs[p];
+        const int npick = want[p] > 0 ? hst_all[p * 4 + 1] : 0;
+        for (int i = 0; i < npick; ++i) jb.picked_out[i] = (int64_t)hpk[p * D + i];
+        jb.n_picked = npick;
+        const int jf = jb.j0 + npick, dz = d - jf;
+        if (jb.Z_out && dz > 0) {
+            hz.resize(D * dz);
+            MRBF_HIP(ctx, hipMemcpy(hz.data(), hdesc[p].Q + (size_t)jf * D, hz.size() * sizeof(double), hipMemcpyDeviceToHost));
+            normalise_columns(hz.data(), d, dz, p_is_inf);
+            MRBF_HIP(ctx, hipMemcpy(jb.Z_out, hz.data(), hz.size() * sizeof(double), hipMemcpyDefault));
         }
     }
     return MRBF_OK;

@@ -69,6 +69,13 @@ int32_t mrbf_dispatch_affine(int64_t n_candidates, int32_t d) {
     return n_candidates * (int64_t)d >= AFFINE_MIN_WORK ? MRBF_DISPATCH_DEVICE : MRBF_DISPATCH_REFERENCE;
 }
 
+// many filters in one call (affine.hip, affsel_pick_batch_kernel): the start on a grid dimension, the filter's own norm, and the eight
+// candidates' coordinates of a workgroup within 64 KiB of LDS -- the range of the one-launch-per-pick kernel
+int32_t mrbf_dispatch_affine_batch(int64_t n_starts, int32_t d, int32_t p_is_inf) {
+    if (n_starts < 1 || n_starts > 65535 || d < 1 || p_is_inf == 0) return MRBF_DISPATCH_REFERENCE;
+    return (int64_t)8 * (d + 1) * 8 <= 64 * 1024 ? MRBF_DISPATCH_DEVICE : MRBF_DISPATCH_REFERENCE;
+}
+
 int32_t mrbf_dispatch_round4(int64_t n0, int32_t d, int32_t poly_deg, int64_t n_candidates) {
     const int q = mrbf::poly_dim(d, poly_deg);
     if (n_candidates < 1 || n0 < 1 || n0 > 8192) return MRBF_DISPATCH_REFERENCE;
@@ -98,6 +105,7 @@ int32_t mrbf_dispatch_after(int32_t entry, int32_t rc) {
         case MRBF_ENTRY_NORMAL: return rc == -2;  // likewise (MRBF_NS_GAVE_UP)
         case MRBF_ENTRY_SD_STEP: return rc == -2;  // shape outside the device path
         case MRBF_ENTRY_SD_BATCH: return rc == -2;  // likewise; a start whose LP gave up says so in its record, not in rc
+        case MRBF_ENTRY_AFFINE_BATCH: return rc == -2;  // likewise: the callers run the single-start call (or the host filter) per start
         default: return 0;
     }
 }

@@ -67,6 +67,14 @@ struct MrbfSdBatchRecord    # mirrors mrbf_sd_batch_record, 56 bytes
     omega::Float64; omega_step::Float64; sigma::Float64; step_norm::Float64
 end
 
+struct MrbfAffineJob        # mirrors mrbf_affine_job, 64 bytes
+    mc::Int64
+    j0::Int32; max_picks::Int32
+    pivot_val::Float64
+    shifted::Ptr{Float64}; Q0::Ptr{Float64}; picked_out::Ptr{Int64}; Z_out::Ptr{Float64}
+    n_picked::Int32; reserved::Int32
+end
+
 struct MrbfPsProblem        # mirrors mrbf_ps_problem, 72 bytes
     n_models::Int32; n_objectives::Int32
     models::Ptr{Ptr{Cvoid}}; roles::Ptr{Int32}
@@ -243,6 +251,8 @@ _dispatch_sd_batch(n_starts, d, k, n_models, n_nl, n_lin, n_foreign, max_loops) 
 _dispatch_backtrack(n_models, n_foreign, in_order::Bool) =
     ccall((:mrbf_dispatch_backtrack, libmrbf), Int32, (Int32, Int32, Int32), n_models, n_foreign, in_order) == 1
 _dispatch_affine(n_candidates, d) = ccall((:mrbf_dispatch_affine, libmrbf), Int32, (Int64, Int32), n_candidates, d) == 1
+_dispatch_affine_batch(n_starts, d, p) =
+    ccall((:mrbf_dispatch_affine_batch, libmrbf), Int32, (Int64, Int32, Int32), n_starts, d, isinf(p) ? 1 : 0) == 1
 _dispatch_round4(n0, d, deg, n_candidates) =
     ccall((:mrbf_dispatch_round4, libmrbf), Int32, (Int64, Int32, Int32, Int64), n0, d, deg, n_candidates) == 1
 _dispatch_fit(n_training, n0, q, n_accepted, same_sites::Bool) =
@@ -1010,6 +1020,46 @@ function affine_select(S::Matrix{Float64}, Q0::Matrix{Float64}, j0::Int, want::I
     _check(ctx, rc)
     np = Int(npick[])
     return Int.(picks[1:np]) .+ 1, Zbuf[:, 1:(d - j0 - np)]
+end
+"""
+Many filters in one device call (`mrbf_affine_select_batch`): the pick loops of rounds 1-2 of the training-site selection
+(AffinelyIndependentPoints.jl:71-106, called by `_find_suitable_points`, RbfModel.jl:205-238) for independent starts of one problem --
+the `Threads.@threads` loop over starts of examples/large_scale_benchmarks.jl:102-109 -- as one launch per pick for all starts and one
+read-back.  `Ss[p]` (d x mc_p shifted seeds, picked columns zero), `Q0s[p]` (the full orthogonal factor of the directions chosen so
+far, first `j0s[p]` columns), `wants[p]` and `pivot_vals[p]` are start p's arguments of `affine_select`; the starts share d and the
+norm `p`.  For every start the result is, bit for bit, what `affine_select` returns on that start alone, whatever its position in the
+batch.  Where the decision table refuses the batch (`mrbf_dispatch_affine_batch`: the 2-norm, d > 1023, more than 65535 starts) or the
+library does (rc -2), every start takes `affine_select`.  Returns a vector of (1-based positions in pick order, final p-normalised
+complement basis).
+"""
+function affine_select_batch(Ss::AbstractVector{Matrix{Float64}}, Q0s::AbstractVector{Matrix{Float64}}, j0s::AbstractVector{<:Integer},
+                             wants::AbstractVector{<:Integer}, pivot_vals::AbstractVector{<:Real}, p)
+    ns = length(Ss)
+    loop() = [affine_select(Ss[q], Q0s[q], Int(j0s[q]), Int(wants[q]), Float64(pivot_vals[q]), p) for q in 1:ns]
+    ns >= 1 || return loop()
+    d = size(Ss[1], 1)
+    (all(S -> size(S, 1) == d, Ss) && _dispatch_affine_batch(ns, d, p)) || return loop()
+    ctx = mrbf_context()
+    picks = [Vector{Int64}(undef, max(Int(wants[q]), 1)) for q in 1:ns]
+    Zbufs = [Matrix{Float64}(undef, d, max(d - Int(j0s[q]), 1)) for q in 1:ns]
+    ms = Ref{Float32}(0)
+    jobs = Vector{MrbfAffineJob}(undef, ns)
+    rc = GC.@preserve Ss Q0s picks Zbufs jobs begin
+        for q in 1:ns
+            jobs[q] = MrbfAffineJob(size(Ss[q], 2), j0s[q], wants[q], pivot_vals[q], pointer(Ss[q]), pointer(Q0s[q]), pointer(picks[q]),
+                                    pointer(Zbufs[q]), 0, 0)
+        end
+        _locked(ctx) do hctx
+            ccall((:mrbf_affine_select_batch, libmrbf), Int32, (Ptr{Cvoid}, Int64, Int32, Int32, Ptr{MrbfAffineJob}, Ref{Float32}),
+                  hctx, ns, d, isinf(p) ? 1 : 0, jobs, ms)
+        end
+    end
+    rc != 0 && _fallback_rc(10, rc) && return loop()           # a shape outside the batched pick loop: the single call per start
+    _check(ctx, rc)
+    return map(1:ns) do q
+        np = Int(jobs[q].n_picked)
+        (Int.(picks[q][1:np]) .+ 1, Zbufs[q][:, 1:(d - Int(j0s[q]) - np)])
+    end
 end
 "Scores `‖Z (Zᵀ(ξ - x₀))‖_p` of all filter candidates and the first maximiser (AffinelyIndependentPoints.jl:71-106)."
 affine_scores(shifted_seeds::AbstractVector, Z::AbstractMatrix, p = Inf) = affine_scores(_dense(_as_matrix(shifted_seeds)), Z, p)

@@ -107,30 +107,40 @@ class AffinelyIndependentPointFilter:
         qr.append(self.shifted[i])
         self.Z = qr.complement(self.p)
 
-    def collect(self):
-        out = []
-        if not self.shifted:
-            return out
+    def _begin(self):
+        """the first pick (the largest shifted seed) and the factorisation it starts, on the host: (out, qr, S, i, cand)"""
         i = int(np.argmax([np.linalg.norm(s, ord=self.p) for s in self.shifted]))
         cand = [c for c in range(len(self.shifted)) if c != i]
         qr = _GrowingQR(self.x_0.size, self.Y)
         self._take(qr, i)
-        out.append(i)
         S = np.array(self.shifted) if self.shifted else np.empty((0, self.x_0.size))
+        return [i], qr, S, i, cand
+
+    def _device_job(self, out, qr, S, i):
+        """what the device pick loop needs after `_begin`: the candidates with the chosen site zeroed and the picks still wanted"""
+        Sd = np.ascontiguousarray(S, dtype=np.float64)
+        Sd[i] = 0.0   # chosen sites score 0 (the reference removes them from the candidate list)
+        return Sd, min(self.n - len(out), self.x_0.size - qr.j)
+
+    def _accept_device(self, out, S, got, Z):
+        if got:
+            self.Y = np.hstack([self.Y, S[got].T])
+            self.Z = Z
+            out.extend(got)
+        return out
+
+    def collect(self):
+        if not self.shifted:
+            return []
+        out, qr, S, i, cand = self._begin()
         on_device = self.ctx is not None or \
             _lib.load().mrbf_dispatch_affine(len(cand), self.x_0.size) == _lib.DISPATCH_DEVICE
         if on_device:
             # the whole pick loop in ONE device call (mrbf_affine_select): the factorisation grows by a reflector per pick on the
             # device, no host round trip between picks (until round 6: one mrbf_affine_scores call + a host QR update per pick)
-            Sd = np.ascontiguousarray(S, dtype=np.float64)
-            Sd[i] = 0.0   # chosen sites score 0 (the reference removes them from the candidate list)
-            want = min(self.n - len(out), self.x_0.size - qr.j)
+            Sd, want = self._device_job(out, qr, S, i)
             got, Z = self._select_device(Sd, qr, want)
-            if got:
-                self.Y = np.hstack([self.Y, S[got].T])
-                self.Z = Z
-                out.extend(got)
-            return out
+            return self._accept_device(out, S, got, Z)
         while len(out) < self.n and cand:
             if self.Z.shape[1]:
                 P = (S[cand] @ self.Z) @ self.Z.T                     # all candidates at once: rows Z Z'(xi - x0)
@@ -145,6 +155,83 @@ class AffinelyIndependentPointFilter:
             cand.remove(best)
             out.append(best)
         return out
+
+
+def affine_select_batch_device(items, d, p=np.inf, ctx=None):
+    """mrbf_affine_select_batch: `items` = one (Sd, qr, want, pivot_val) per start -- the rows of Sd are the start's candidates
+    (picked rows zeroed), `qr` the `_GrowingQR` of the directions chosen so far -> (rc, [(positions, final Z)] or None, ms).  Raises
+    nothing for an rc that `mrbf_dispatch_after` reads as "take the single calls"."""
+    ctx = ctx or _lib.default_context()
+    n = len(items)
+    jobs = (_lib.AffineJob * max(n, 1))()
+    keep = []
+    for k, (Sd, qr, want, pivot) in enumerate(items):
+        Sd = np.ascontiguousarray(Sd, dtype=np.float64)
+        Q0 = np.asfortranarray(qr.Q)
+        picks = np.empty(max(want, 1), dtype=np.int64)
+        Zbuf = np.empty((max(d - qr.j, 1), d))                          # (column-major d x dz)
+        keep.append((Sd, Q0, picks, Zbuf))
+        jobs[k].mc, jobs[k].j0, jobs[k].max_picks, jobs[k].pivot_val = Sd.shape[0], qr.j, want, float(pivot)
+        jobs[k].shifted, jobs[k].Q0 = Sd.ctypes.data, Q0.ctypes.data
+        jobs[k].picked_out, jobs[k].Z_out = picks.ctypes.data, Zbuf.ctypes.data
+    ms = ctypes.c_float(0.0)
+    rc = ctx.lib.mrbf_affine_select_batch(ctx.h, n, d, 1 if np.isinf(p) else 0, jobs, ctypes.byref(ms))
+    if rc != 0:
+        if not ctx.lib.mrbf_dispatch_after(_lib.ENTRY_AFFINE_BATCH, rc):
+            ctx.check(rc)
+        return rc, None, 0.0
+    res = []
+    for k, (Sd, qr, want, pivot) in enumerate(items):
+        _, _, picks, Zbuf = keep[k]
+        got = [int(v) for v in picks[: jobs[k].n_picked]]
+        res.append((got, Zbuf[: d - qr.j - len(got)].T.copy()))
+    return 0, res, float(ms.value)
+
+
+def affine_collect_many(filters, stats=None, ctx=None):
+    """`collect()` for a list of AffinelyIndependentPointFilters -- the filters of the starts of a many-start run -- with the device
+    pick loops of all of them in ONE call (mrbf_affine_select_batch): the first pick and the start of the factorisation stay on the
+    host exactly as in `collect()`; the filters the decision table sends to the device (mrbf_dispatch_affine, per filter) form the
+    batch when mrbf_dispatch_affine_batch takes it (one d and one norm per call: filters are grouped by them), every other filter
+    runs `collect()`; a batch the library refuses (rc -2, mrbf_dispatch_after) continues with the single call per filter.  Sets every
+    filter's Y and Z as `collect()` would and returns the lists of picks; stats["path"] = "batch" when a batched call ran, else
+    "loop", stats["batched"] = the positions of the filters it served."""
+    filters = list(filters)
+    out = [None] * len(filters)
+    lib = _lib.load() if filters else None
+    groups = {}
+    for k, f in enumerate(filters):
+        if not f.shifted:
+            out[k] = []
+        elif f.ctx is not None or lib.mrbf_dispatch_affine(len(f.shifted) - 1, f.x_0.size) == _lib.DISPATCH_DEVICE:
+            groups.setdefault((f.x_0.size, bool(np.isinf(f.p)), id(f.ctx or ctx)), []).append(k)
+        else:
+            out[k] = f.collect()
+    batched = []
+    for (d, is_inf, _), members in groups.items():
+        if lib.mrbf_dispatch_affine_batch(len(members), d, 1 if is_inf else 0) != _lib.DISPATCH_DEVICE:
+            for k in members:
+                out[k] = filters[k].collect()
+            continue
+        begun, items = [], []
+        for k in members:
+            f = filters[k]
+            o, qr, S, i, _ = f._begin()
+            Sd, want = f._device_job(o, qr, S, i)
+            begun.append((o, qr, S, Sd, want))
+            items.append((Sd, qr, want, f.pivot_val))
+        f0 = filters[members[0]]
+        rc, res, _ = affine_select_batch_device(items, d, f0.p, ctx=f0.ctx or ctx)
+        for pos, k in enumerate(members):
+            o, qr, S, Sd, want = begun[pos]
+            got, Z = res[pos] if rc == 0 else filters[k]._select_device(Sd, qr, want)   # refused: the single call, from the same state
+            out[k] = filters[k]._accept_device(o, S, got, Z)
+        if rc == 0:
+            batched.extend(members)
+    if stats is not None:
+        stats["path"] = "batch" if batched else "loop"
+        stats["batched"] = sorted(batched)
+    return out
 
 
 def results_in_box_indices(sites, lb, ub, exclude_indices=()):
@@ -164,6 +251,31 @@ def _find_suitable_points(sites, lb, ub, x, x_index, piv_val, already_inspected_
     picked = [cand[i] for i in flt.collect()]
     dirs = [flt.Z[:, j].copy() for j in range(flt.Z.shape[1])][::-1] if collect_improving_directions else None
     return picked, dirs, cand, flt.Y, flt.Z
+
+
+def find_suitable_points_many(sites_list, lbs, ubs, xs, x_indices, piv_val, already_inspected_indices=None, Ys=None, Zs=None, n_missing=None,
+                              collect_improving_directions=True, stats=None, ctx=None):
+    """`_find_suitable_points` (RbfModel.jl:205-238) for a list of starts -- start p has its own database `sites_list[p]`, box, centre
+    and, for a second round, its own Y / Z and `n_missing[p]` (entries may be None) -- with the filters of all starts collected by
+    `affine_collect_many`.  Returns the list of `_find_suitable_points`' tuples."""
+    ns = len(sites_list)
+    opt = lambda seq, p: None if seq is None else seq[p]
+    cands, filters = [], []
+    for p in range(ns):
+        x = np.asarray(xs[p], dtype=np.float64)
+        sites = sites_list[p]
+        cand = results_in_box_indices(sites, lbs[p], ubs[p], [x_indices[p], *(opt(already_inspected_indices, p) or ())])
+        nm = opt(n_missing, p)
+        cands.append(cand)
+        filters.append(AffinelyIndependentPointFilter(x, [sites[i] for i in cand], n=x.size if nm is None else nm, Y=opt(Ys, p), Z=opt(Zs, p),
+                                                      p=np.inf, pivot_val=piv_val))
+    picks = affine_collect_many(filters, stats=stats, ctx=ctx)
+    res = []
+    for p, flt in enumerate(filters):
+        picked = [cands[p][i] for i in picks[p]]
+        dirs = [flt.Z[:, j].copy() for j in range(flt.Z.shape[1])][::-1] if collect_improving_directions else None
+        res.append((picked, dirs, cands[p], flt.Y, flt.Z))
+    return res
 
 
 def _nullify_last_row(R):
