@@ -285,6 +285,37 @@ typedef struct {
 int32_t mrbf_batch_run(int32_t n_dev, const int32_t *device_ids, int64_t n_problems, const mrbf_problem *problems,
                        mrbf_result *results);
 
+/* ---- many-start model update: one call fits a batch of starts and keeps the models (batch.hip) -----------------------------
+ * update_model (src/models/RbfModel.jl:743-767) for n_starts independent starts -- the reference's Threads.@threads loop over
+ * starts (examples/large_scale_benchmarks.jl:102-109, :253) -- on ONE context.  For every start p, weights_out, poly_out and every
+ * later result computed from jobs[p].model (mrbf_eval values and Jacobians, the start's outputs and record of
+ * mrbf_sd_iterate_batch) are, bit for bit, those of mrbf_fit on that start's arguments on the same context; they do not depend on
+ * the start's position in the batch or on which other starts share it.  info.path, fallbacks, n and q equal the single call's;
+ * rel_residual and max_pitw come from the batch's own check kernel (same quantities, sums in another order).
+ * Starts in the range of the one-launch fit (n <= 512, d <= 128, k <= 16, Cholesky paths) share a handful of launches whose grids
+ * span all of them, one packed descriptor upload and one read-back; every other start, and a start whose batched fit raised a flag
+ * (not positive definite, rank-deficient tail), takes mrbf_fit inside the same call.
+ * Lifetime: jobs[p].model is a handle like any other -- mrbf_eval, mrbf_sd_iterate_batch, mrbf_ps_step_problem, mrbf_model_dims
+ * accept it, MRBF_OPT_LIVE_HANDLES counts it, and the caller releases it with mrbf_free_model, in any order.  The models of one
+ * call that took the batched path are carved from one device allocation of that call; each holds a share, and the allocation goes
+ * back to the context's pool of released model blocks (or to the device) when the last of them is freed: device memory of a batch
+ * is reusable only once ALL its models are released.
+ * A failing start sets its own status and leaves its model NULL; the call returns 0 unless an argument is invalid (an invalid field
+ * of a job is an invalid `jobs`: -3) or mrbf_dispatch_fit_batch refuses n_starts (-2: take mrbf_fit per start; nothing is written).
+ * ms_total (may be NULL): hipEvent time of the batched launches plus info.ms_total of the starts that took the single call. */
+typedef struct {
+    int64_t n;
+    int32_t d, k, kernel_id, poly_deg;
+    double a, b;
+    const double *centres, *values;   /* n x d, n x k row-major; host or device (detected per pointer) */
+    double *weights_out, *poly_out;   /* n x k, q x k; host or device; may be NULL */
+    mrbf_model *model;                /* out: the resident model; NULL when status != 0 */
+    int32_t status;                   /* out: what mrbf_fit would have returned for this start */
+    int32_t reserved;
+    mrbf_fit_info info;               /* out */
+} mrbf_fit_job;                       /* 168 bytes */
+int32_t mrbf_fit_batch(mrbf_ctx *ctx, int64_t n_starts, mrbf_fit_job *jobs, float *ms_total);
+
 /* debug / test hooks (exported so the parity tests can pin kernel-level behaviour) */
 /* Environment switches.  The library reads a number of MRBF_* variables (schedule experiments of the persistent factorisation,
  * earlier forms of kernels kept selectable for A/B runs, diagnostics: INTEGRATION.md "Tuning knobs").  NONE of them is honoured
@@ -559,13 +590,16 @@ int32_t mrbf_sd_iterate_batch(mrbf_ctx *ctx, int64_t n_starts, const mrbf_ps_pro
  *   mrbf_dispatch_sd_batch   the two calls above for n_starts starts in one (mrbf_sd_iterate_batch): device iff mrbf_dispatch_sd
  *                            and mrbf_dispatch_sd_step both say so, d <= 256 (the fused evaluation kernels' range) and
  *                            1 <= n_starts <= 65535 (a grid dimension).
+ *   mrbf_dispatch_fit_batch  update_model of n_starts starts in one call (mrbf_fit_batch): device iff 1 <= n_starts <= 65535 (a grid
+ *                            dimension).  Which starts share the batched launches is decided inside the call, start by start.
  *   mrbf_dispatch_after      the return code rc of a device entry point (MRBF_ENTRY_*) that means "take the reference method
  *                            for this call" (start set without the tail or rank deficient, limits of the device path) rather
  *                            than an error: 1 = fall back, 0 = rc is what it says. */
 enum { MRBF_DISPATCH_REFERENCE = 0, MRBF_DISPATCH_DEVICE = 1 };
 enum { MRBF_FIT_FULL = 0, MRBF_FIT_FROM_ROUND4 = 1 };
 enum { MRBF_ENTRY_ROUND4 = 1, MRBF_ENTRY_FIT_FROM_ROUND4 = 2, MRBF_ENTRY_PS_STEP = 3, MRBF_ENTRY_BACKTRACK = 4, MRBF_ENTRY_AFFINE = 5,
-       MRBF_ENTRY_SD = 6, MRBF_ENTRY_NORMAL = 7, MRBF_ENTRY_SD_STEP = 8, MRBF_ENTRY_SD_BATCH = 9, MRBF_ENTRY_AFFINE_BATCH = 10 };
+       MRBF_ENTRY_SD = 6, MRBF_ENTRY_NORMAL = 7, MRBF_ENTRY_SD_STEP = 8, MRBF_ENTRY_SD_BATCH = 9, MRBF_ENTRY_AFFINE_BATCH = 10,
+       MRBF_ENTRY_FIT_BATCH = 11 };
 int32_t mrbf_dispatch_ps(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_sd(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_normal(int32_t d, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
@@ -577,6 +611,7 @@ int32_t mrbf_dispatch_backtrack(int32_t n_objective_models, int32_t n_foreign, i
 int32_t mrbf_dispatch_affine(int64_t n_candidates, int32_t d);
 int32_t mrbf_dispatch_affine_batch(int64_t n_starts, int32_t d, int32_t p_is_inf);
 int32_t mrbf_dispatch_round4(int64_t n0, int32_t d, int32_t poly_deg, int64_t n_candidates);
+int32_t mrbf_dispatch_fit_batch(int64_t n_starts);
 int32_t mrbf_dispatch_fit(int64_t n_training, int64_t state_n0, int32_t state_q, int32_t state_n_accepted, int32_t same_sites);
 int32_t mrbf_dispatch_after(int32_t entry, int32_t rc);
 

@@ -16,5 +16,5 @@ from ._lib import Context, MrbfError, default_context, load  # noqa: F401
 from .rbf_model import (RbfConfig, RbfKernels, RbfModel, combinable, eval_models, eval_models_at_sites,  # noqa: F401
                         fully_linear, get_gradient, get_jacobian, get_jacobians_at_sites, get_matrices, improve_model,
                         init_model, max_evals, model_from_coeffs, num_outputs, parse_shape_param_string,
-                        set_fully_linear, update_model)
+                        set_fully_linear, update_model, update_models_many)
 from . import descent, pascoletti_serafini, sampling, surrogates  # noqa: F401

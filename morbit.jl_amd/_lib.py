@@ -61,6 +61,7 @@ FIT_FULL, FIT_FROM_ROUND4 = 0, 1
 ENTRY_ROUND4, ENTRY_FIT_FROM_ROUND4, ENTRY_PS_STEP, ENTRY_BACKTRACK, ENTRY_AFFINE, ENTRY_SD, ENTRY_NORMAL, ENTRY_SD_STEP = 1, 2, 3, 4, 5, 6, 7, 8
 ENTRY_SD_BATCH = 9
 ENTRY_AFFINE_BATCH = 10
+ENTRY_FIT_BATCH = 11
 SD_OK, SD_NO_OBJECTIVE, SD_INFEASIBLE, SD_GAVE_UP = 0, 1, 2, 3
 NS_OK, NS_INFEASIBLE, NS_GAVE_UP = 0, 1, 2
 SD_BRANCH_DELTA, SD_BRANCH_ONE, SD_BRANCH_INTERSECT = 0, 1, 2
@@ -118,6 +119,14 @@ class AffineJob(ctypes.Structure):
                 ("n_picked", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class FitJob(ctypes.Structure):
+    """mrbf_fit_job: one start of mrbf_fit_batch"""
+    _fields_ = [("n", ctypes.c_int64), ("d", ctypes.c_int32), ("k", ctypes.c_int32), ("kernel_id", ctypes.c_int32),
+                ("poly_deg", ctypes.c_int32), ("a", ctypes.c_double), ("b", ctypes.c_double), ("centres", ctypes.c_void_p),
+                ("values", ctypes.c_void_p), ("weights_out", ctypes.c_void_p), ("poly_out", ctypes.c_void_p), ("model", ctypes.c_void_p),
+                ("status", ctypes.c_int32), ("reserved", ctypes.c_int32), ("info", FitInfo)]
+
+
 class Problem(ctypes.Structure):
     _fields_ = [("n", ctypes.c_int64), ("m", ctypes.c_int64), ("d", ctypes.c_int32), ("k", ctypes.c_int32),
                 ("kernel_id", ctypes.c_int32), ("poly_deg", ctypes.c_int32), ("a", ctypes.c_double), ("b", ctypes.c_double),
@@ -168,6 +177,8 @@ SIGNATURES = {
     "mrbf_free_model": (ctypes.c_int32, [c_vp, c_vp]),
     "mrbf_batch_run": (ctypes.c_int32, [ctypes.c_int32, c_ip, ctypes.c_int64, ctypes.POINTER(Problem),
                                         ctypes.POINTER(Result)]),
+    "mrbf_fit_batch": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.POINTER(FitJob), c_fp]),
+    "mrbf_dispatch_fit_batch": (ctypes.c_int32, [ctypes.c_int64]),
     "mrbf_debug_mfma_layout": (ctypes.c_int32, [c_vp, c_vp, c_vp, c_vp]),
     "mrbf_debug_potrf": (ctypes.c_int32, [c_vp, ctypes.c_int64, c_vp, ctypes.c_int32, c_ip, c_fp]),
     "mrbf_debug_env": (ctypes.c_int32, [ctypes.c_char_p]),

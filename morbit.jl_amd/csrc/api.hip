@@ -7,7 +7,9 @@
 
 using namespace mrbf;
 
-static int check_kernel(mrbf_ctx *ctx, int kid, double a, double b, int deg, int argpos) {
+namespace mrbf {
+// (shared with mrbf_fit_batch, batch.hip)
+int check_kernel(mrbf_ctx *ctx, int kid, double a, double b, int deg, int argpos) {
     if (kid < 0 || kid > 4) return fail(ctx, -argpos, "kernel_id %d not in 0..4 (Morbit.RbfKernels)", kid);
     // same sanity checks as RbfConfig's @assert block (RbfModel.jl:102-111)
     if (kid == MRBF_CUBIC && !(a >= 1.0 && std::fmod(a, 2.0) == 1.0))
@@ -23,6 +25,7 @@ static int check_kernel(mrbf_ctx *ctx, int kid, double a, double b, int deg, int
     if (deg < -1 || deg > 1) return fail(ctx, -(argpos + 3), "polynomial_degree must be -1, 0 or 1 (RbfModel.jl:21), got %d", deg);
     return 0;
 }
+}  // namespace mrbf
 
 // contexts of mrbf_batch_run's worker threads are kept between calls (creating a rocBLAS handle and streams costs tens of
 // milliseconds, more than a whole small problem)

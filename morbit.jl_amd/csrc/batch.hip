@@ -12,6 +12,14 @@
 // instead of ~65 device operations per problem.  A batch and single calls (mrbf_fit + mrbf_eval) run the same kernels with the same
 // split of the centre range, so their results agree bit for bit (tests/test_gpu_configs.py::test_c4_many_start_batch).  Problems of
 // any other shape, and problems whose factorisation raised a flag, take the per-problem chain (api.hip: batch_run_chain).
+//
+// mrbf_fit_batch: the model update (update_model, src/models/RbfModel.jl:743-767) of a batch of starts on ONE context, models kept.
+// The fit half of the launches above (means, fit, residual evaluation at the sites, part 0 of the check kernel) with the model
+// arrays of every start carved from one device allocation of the call (a slab, ModelSlab in common.hpp) instead of the arena:
+//     1   batch_copy_kernel           centres given as device pointers -> their slab positions (host centres: uploaded there)
+//     1   small_mean_kernel, 1 small_fit_kernel, 1 center_pad_batch_kernel, 2 eval_fused / eval_combine, 1 batch_check_kernel
+//     1   batch_copy_kernel           weights and tail coefficients -> outputs given as device pointers
+// Starts outside the one-launch range and flagged starts take mrbf_fit on the same context inside the call.
 #include <algorithm>
 #include <thread>
 
@@ -25,6 +33,7 @@ mrbf_ctx *batch_pool_acquire(int device, int *rc);
 void batch_pool_release(mrbf_ctx *c);
 void fill_small_prob(const mrbf_ctx *ctx, const mrbf_model *M, const double *Y, double *ws, int *flags, double *scal, int *cl, smallfit::Prob *P);
 int small_fit_verdict(const mrbf_model *M, const int *hflags, const double *hscal, mrbf_fit_info *info);
+int check_kernel(mrbf_ctx *ctx, int kid, double a, double b, int deg, int argpos);
 
 struct CheckDesc {
     const double *V, *Y;       // surrogate values at the sites / data, n x k
@@ -118,9 +127,53 @@ __global__ __launch_bounds__(256) void batch_check_kernel(const CheckDesc *__res
 
 static inline size_t al16(size_t c) { return (c + 15) & ~size_t(15); }
 
+// cnt doubles from src to dst, both device memory
+struct CopySeg {
+    const double *src;
+    double *dst;
+    int64_t cnt;
+};
+// The device-to-device copies of a whole batch in one launch: segment blockIdx.y, 16 bytes per lane (consecutive lanes, consecutive
+// 16-byte words: 1 KiB per wave and instruction) where both ends are 16-byte aligned, four loads in flight per lane before the first
+// store; 8 bytes per lane otherwise (a caller's array may start at any double).  A segment of cnt = 0 is skipped.
+__global__ __launch_bounds__(256) void batch_copy_kernel(const CopySeg *__restrict__ many) {
+    const CopySeg S = many[blockIdx.y];
+    const int tid = threadIdx.x;
+    if (((reinterpret_cast<uintptr_t>(S.src) | reinterpret_cast<uintptr_t>(S.dst)) & 15) == 0) {
+        const double2 *__restrict__ s2 = reinterpret_cast<const double2 *>(S.src);
+        double2 *__restrict__ d2 = reinterpret_cast<double2 *>(S.dst);
+        const int64_t pairs = S.cnt >> 1;
+        for (int64_t i0 = (int64_t)blockIdx.x * 1024 + tid; i0 < pairs; i0 += (int64_t)gridDim.x * 1024) {
+            double2 v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (i0 + 256 * u < pairs) v[u] = s2[i0 + 256 * u];
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (i0 + 256 * u < pairs) d2[i0 + 256 * u] = v[u];
+        }
+        if ((S.cnt & 1) && blockIdx.x == 0 && tid == 0) S.dst[S.cnt - 1] = S.src[S.cnt - 1];
+    } else {
+        for (int64_t i = (int64_t)blockIdx.x * 256 + tid; i < S.cnt; i += (int64_t)gridDim.x * 256) S.dst[i] = S.src[i];
+    }
+}
+// `count` segments of the device array `dsegs` (host copy: `hsegs`) on the context's stream; nothing to copy: no launch
+static int launch_batch_copy(mrbf_ctx *ctx, const CopySeg *hsegs, const CopySeg *dsegs, int count) {
+    int64_t longest = 0;
+    for (int i = 0; i < count; ++i) longest = std::max(longest, hsegs[i].cnt);
+    if (longest == 0) return 0;
+    const unsigned gx = (unsigned)std::min<int64_t>((longest + 2047) / 2048, 256);  // 1024 pairs of doubles per workgroup and step
+    hipLaunchKernelGGL(batch_copy_kernel, dim3(gx, (unsigned)count), dim3(256), 0, ctx->stream, dsegs);
+    MRBF_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
 // all small problems of one GPU; `redo` receives the problems that have to take the per-problem chain after all (flags)
+// keep (mrbf_fit_batch; indexed like `problems`, every m = 0): the model arrays of problem p are keep[p]'s -- storage that outlives the
+// call -- instead of arena positions: the centres are copied (or uploaded) there first, the fit writes Xc, sq, mean, W, Wc and lam
+// there, and weights_out / poly_out receive copies.  *ms_sum (may be NULL) += the event time of every launch group that ran.
 static int run_small_batch(mrbf_ctx *ctx, const std::vector<int64_t> &idx, const mrbf_problem *problems, mrbf_result *results,
-                           std::vector<int64_t> *redo, int force_nc = 0) {
+                           std::vector<int64_t> *redo, int force_nc = 0, const mrbf_model *keep = nullptr, float *ms_sum = nullptr) {
     const int P = (int)idx.size();
     if (P == 0) return 0;
     (void)hipSetDevice(ctx->device);
@@ -128,6 +181,7 @@ static int run_small_batch(mrbf_ctx *ctx, const std::vector<int64_t> &idx, const
         size_t C, Y, X, Xc, sq, mean, W, Wc, lam, ws, Xq0, xsq0, vp0, gp0, V0, Xq1, xsq1, vp1, gp1, vals, jac, out;
         int nsplit0, nsplit1, D, q, KO;
         int64_t npad, mpad0, mpad1;
+        bool w_host, lam_host;  // weights_out / poly_out are host memory: copied back behind the launches
     };
     std::vector<Lay> lay(P);
     size_t total = 0;
@@ -149,15 +203,21 @@ static int run_small_batch(mrbf_ctx *ctx, const std::vector<int64_t> &idx, const
         L.D = d <= 64 ? 64 : 128;
         L.KO = outputs_per_pass(k, L.D);
         const int q16 = (int)round_up(std::max(L.q, 1), 16);
-        L.C = is_device_ptr(pr.centres) ? (size_t)-1 : take((size_t)pr.n * d);
+        L.C = (keep || is_device_ptr(pr.centres)) ? (size_t)-1 : take((size_t)pr.n * d);
         L.Y = is_device_ptr(pr.values) ? (size_t)-1 : take((size_t)pr.n * k);
         L.X = (pr.m == 0 || is_device_ptr(pr.X)) ? (size_t)-1 : take((size_t)pr.m * d);
-        L.Xc = take((size_t)L.npad * L.D);
-        L.sq = take((size_t)L.npad);
-        L.mean = take((size_t)L.D);
-        L.W = (pr.weights_out && is_device_ptr(pr.weights_out)) ? (size_t)-1 : take((size_t)pr.n * k);  // device output: written in place
-        L.Wc = take((size_t)L.npad * k);
-        L.lam = (pr.poly_out && L.q > 0 && is_device_ptr(pr.poly_out)) ? (size_t)-1 : take((size_t)std::max(L.q, 1) * k);
+        const bool w_dev = pr.weights_out && is_device_ptr(pr.weights_out), lam_dev = pr.poly_out && L.q > 0 && is_device_ptr(pr.poly_out);
+        L.w_host = pr.weights_out && !w_dev;
+        L.lam_host = pr.poly_out && L.q > 0 && !lam_dev;
+        L.Xc = L.sq = L.mean = L.W = L.Wc = L.lam = (size_t)-1;
+        if (!keep) {
+            L.Xc = take((size_t)L.npad * L.D);
+            L.sq = take((size_t)L.npad);
+            L.mean = take((size_t)L.D);
+            if (!w_dev) L.W = take((size_t)pr.n * k);  // device output: written in place
+            L.Wc = take((size_t)L.npad * k);
+            if (!lam_dev) L.lam = take((size_t)std::max(L.q, 1) * k);
+        }
         L.ws = take(smallfit::carve((int)L.npad, q16).total);
         // evaluation 0: the fit's residual at the sites; evaluation 1: the caller's queries
         L.mpad0 = check ? round_up(pr.n, 64) : 0;
@@ -183,8 +243,8 @@ static int run_small_batch(mrbf_ctx *ctx, const std::vector<int64_t> &idx, const
     const size_t arena_budget = (size_t)(mrbf_env("MRBF_BATCH_ARENA_MB") ? atoll(mrbf_env("MRBF_BATCH_ARENA_MB")) : 8192) << 20;
     auto halves = [&]() -> int {
         const std::vector<int64_t> lo(idx.begin(), idx.begin() + P / 2), hi(idx.begin() + P / 2, idx.end());
-        MRBF_TRY(run_small_batch(ctx, lo, problems, results, redo, force_nc));
-        return run_small_batch(ctx, hi, problems, results, redo, force_nc);
+        MRBF_TRY(run_small_batch(ctx, lo, problems, results, redo, force_nc, keep, ms_sum));
+        return run_small_batch(ctx, hi, problems, results, redo, force_nc, keep, ms_sum);
     };
     if (P > 1 && total * sizeof(double) > arena_budget) return halves();
     double *base;
@@ -197,7 +257,9 @@ static int run_small_batch(mrbf_ctx *ctx, const std::vector<int64_t> &idx, const
     flags = reinterpret_cast<int *>(base + out0 + (size_t)8 * P);
     PinGuard pin(ctx);  // this batch's share of the pinned staging block (descriptor upload, result words); released on every return path
     // descriptors: [Prob x P | EvalDesc x 2P | CheckDesc x P | CL_WORDS cluster words x P (zero)] in one device buffer
-    const size_t desc_bytes = (size_t)P * (sizeof(smallfit::Prob) + 2 * sizeof(EvalDesc) + sizeof(CheckDesc) + smallfit::CL_WORDS * sizeof(int)) + 256;
+    // (with `keep`, behind them: CopySeg x 3P -- centres in | weights out | tail coefficients out)
+    const size_t desc_bytes = (size_t)P * (sizeof(smallfit::Prob) + 2 * sizeof(EvalDesc) + sizeof(CheckDesc) + smallfit::CL_WORDS * sizeof(int) +
+                                           (keep ? 3 * sizeof(CopySeg) : 0)) + 256;
     char *ddesc;
     MRBF_TRY(get_buf(ctx, S_SMALL_DESC, desc_bytes, (void **)&ddesc));
     // (the device addresses of the three arrays and of the cluster words are known before the host copies are filled)
@@ -205,6 +267,8 @@ static int run_small_batch(mrbf_ctx *ctx, const std::vector<int64_t> &idx, const
     EvalDesc *devs_ = (EvalDesc *)(ddesc + al16((size_t)P * sizeof(smallfit::Prob)));
     CheckDesc *dchk = (CheckDesc *)((char *)devs_ + al16((size_t)2 * P * sizeof(EvalDesc)));
     int *dcl = (int *)((char *)dchk + al16((size_t)P * sizeof(CheckDesc)));
+    CopySeg *dsegs = (CopySeg *)((char *)dcl + al16((size_t)P * smallfit::CL_WORDS * sizeof(int)));
+    std::vector<CopySeg> segs(keep ? (size_t)3 * P : 0, CopySeg{nullptr, nullptr, 0});
     std::vector<char> hdesc;
     std::vector<smallfit::Prob> probs(P);
     std::vector<EvalDesc> evs((size_t)2 * P);
@@ -224,7 +288,15 @@ static int run_small_batch(mrbf_ctx *ctx, const std::vector<int64_t> &idx, const
         const mrbf_problem &pr = problems[idx[i]];
         const Lay &L = lay[i];
         const double *C, *Y, *X = nullptr;
-        MRBF_TRY(dev_in(pr.centres, L.C, (size_t)pr.n * pr.d, &C));
+        if (keep) {
+            C = keep[idx[i]].C;
+            if (is_device_ptr(pr.centres))
+                segs[i] = CopySeg{pr.centres, keep[idx[i]].C, pr.n * pr.d};
+            else
+                MRBF_HIP(ctx, hipMemcpyAsync(keep[idx[i]].C, pr.centres, (size_t)pr.n * pr.d * sizeof(double), hipMemcpyHostToDevice, st));
+        } else {
+            MRBF_TRY(dev_in(pr.centres, L.C, (size_t)pr.n * pr.d, &C));
+        }
         MRBF_TRY(dev_in(pr.values, L.Y, (size_t)pr.n * pr.k, &Y));
         if (pr.m > 0) MRBF_TRY(dev_in(pr.X, L.X, (size_t)pr.m * pr.d, &X));
         mrbf_model &M = models[i];
@@ -237,12 +309,24 @@ static int run_small_batch(mrbf_ctx *ctx, const std::vector<int64_t> &idx, const
         M.deg = pr.poly_deg;
         M.kp = make_kp(pr.kernel_id, pr.a, pr.b);
         M.C = const_cast<double *>(C);
-        M.Xc = base + L.Xc;
-        M.sq = base + L.sq;
-        M.mean = base + L.mean;
-        M.W = L.W == (size_t)-1 ? pr.weights_out : base + L.W;
-        M.Wc = base + L.Wc;
-        M.lam = L.lam == (size_t)-1 ? pr.poly_out : base + L.lam;
+        if (keep) {
+            const mrbf_model &K = keep[idx[i]];
+            M.Xc = K.Xc;
+            M.sq = K.sq;
+            M.mean = K.mean;
+            M.W = K.W;
+            M.Wc = K.Wc;
+            M.lam = K.lam;
+            if (pr.weights_out && !L.w_host) segs[(size_t)P + i] = CopySeg{M.W, pr.weights_out, pr.n * pr.k};
+            if (pr.poly_out && L.q > 0 && !L.lam_host) segs[(size_t)2 * P + i] = CopySeg{M.lam, pr.poly_out, (int64_t)L.q * pr.k};
+        } else {
+            M.Xc = base + L.Xc;
+            M.sq = base + L.sq;
+            M.mean = base + L.mean;
+            M.W = L.W == (size_t)-1 ? pr.weights_out : base + L.W;
+            M.Wc = base + L.Wc;
+            M.lam = L.lam == (size_t)-1 ? pr.poly_out : base + L.lam;
+        }
         fill_small_prob(ctx, &M, Y, base + L.ws, flags + 4 * i, base + L.out + 5, dcl + smallfit::CL_WORDS * i, &probs[i]);
         probs[i].mean_given = 1;  // small_mean_kernel below: the queries are centred beside the fit, not after it
         for (int e = 0; e < 2; ++e) {
@@ -286,6 +370,7 @@ static int run_small_batch(mrbf_ctx *ctx, const std::vector<int64_t> &idx, const
         memcpy(hd, probs.data(), (size_t)P * sizeof(smallfit::Prob));
         memcpy(hd + ((char *)devs_ - ddesc), evs.data(), (size_t)2 * P * sizeof(EvalDesc));
         memcpy(hd + ((char *)dchk - ddesc), chk.data(), (size_t)P * sizeof(CheckDesc));
+        if (keep) memcpy(hd + ((char *)dsegs - ddesc), segs.data(), segs.size() * sizeof(CopySeg));
         MRBF_HIP(ctx, hipMemcpyAsync(ddesc, hd, desc_bytes, hipMemcpyHostToDevice, st));
     }
     MRBF_HIP(ctx, hipEventRecord(ctx->ev[0], st));
@@ -294,6 +379,7 @@ static int run_small_batch(mrbf_ctx *ctx, const std::vector<int64_t> &idx, const
     // the centroids first (the fit kernel's own arithmetic, small.hip: column_means), then -- on the side stream, under the
     // latency-bound fit launch -- the centring of all evaluation points of the batch (sites for the residual, queries): 423 MB of
     // queries at C4, 0.11 ms that used to stand between the fit and the evaluation
+    if (keep) MRBF_TRY(launch_batch_copy(ctx, segs.data(), dsegs, P));  // the centres of all starts into their models (the means read them there)
     MRBF_TRY(launch_small_means(ctx, dprobs, P));
     if (side != st) {
         MRBF_HIP(ctx, hipEventRecord(ctx->evx[0], st));
@@ -303,6 +389,10 @@ static int run_small_batch(mrbf_ctx *ctx, const std::vector<int64_t> &idx, const
     //  1600 blocks arrive on the high-priority side stream; the other way round the fit took 0.83 or 0.96 ms from run to run)
     MRBF_TRY(launch_small_fit(ctx, probs.data(), P, dprobs, nc));
     MRBF_HIP(ctx, hipEventRecord(ctx->ev[1], st));
+    if (keep) {  // coefficients -> outputs in device memory (a launch per group: at most P segments on a grid dimension)
+        MRBF_TRY(launch_batch_copy(ctx, segs.data() + P, dsegs + P, P));
+        MRBF_TRY(launch_batch_copy(ctx, segs.data() + 2 * (size_t)P, dsegs + 2 * (size_t)P, P));
+    }
     {
         int64_t max_mpad = 0;
         for (const EvalDesc &E : evs) max_mpad = std::max(max_mpad, E.mpad);
@@ -370,7 +460,7 @@ static int run_small_batch(mrbf_ctx *ctx, const std::vector<int64_t> &idx, const
         MRBF_HIP(ctx, hipEventRecord(ctx->evx[1], side));
         MRBF_HIP(ctx, hipStreamWaitEvent(st, ctx->evx[1], 0));
     }
-    hipLaunchKernelGGL(batch_check_kernel, dim3((unsigned)P), dim3(256), 0, st, dchk, 1);
+    if (!keep) hipLaunchKernelGGL(batch_check_kernel, dim3((unsigned)P), dim3(256), 0, st, dchk, 1);  // (no queries with `keep`)
     MRBF_HIP(ctx, hipGetLastError());
     MRBF_HIP(ctx, hipEventRecord(ctx->ev[2], st));
     // results
@@ -387,10 +477,10 @@ static int run_small_batch(mrbf_ctx *ctx, const std::vector<int64_t> &idx, const
     for (int i = 0; i < P; ++i) {
         const mrbf_problem &pr = problems[idx[i]];
         const Lay &L = lay[i];
-        if (pr.weights_out && L.W != (size_t)-1)
-            MRBF_HIP(ctx, hipMemcpyAsync(pr.weights_out, base + L.W, (size_t)pr.n * pr.k * sizeof(double), hipMemcpyDeviceToHost, st));
-        if (pr.poly_out && L.q > 0 && L.lam != (size_t)-1)
-            MRBF_HIP(ctx, hipMemcpyAsync(pr.poly_out, base + L.lam, (size_t)L.q * pr.k * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (L.w_host)
+            MRBF_HIP(ctx, hipMemcpyAsync(pr.weights_out, models[i].W, (size_t)pr.n * pr.k * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (L.lam_host)
+            MRBF_HIP(ctx, hipMemcpyAsync(pr.poly_out, models[i].lam, (size_t)L.q * pr.k * sizeof(double), hipMemcpyDeviceToHost, st));
         if (pr.m > 0 && pr.vals_out && L.vals != (size_t)-1)
             MRBF_HIP(ctx, hipMemcpyAsync(pr.vals_out, base + L.vals, (size_t)pr.m * pr.k * sizeof(double), hipMemcpyDeviceToHost, st));
         if (pr.m > 0 && pr.jac_out && L.jac != (size_t)-1)
@@ -414,7 +504,7 @@ static int run_small_batch(mrbf_ctx *ctx, const std::vector<int64_t> &idx, const
             // solve.hip).  A problem that is ill-conditioned in its own right (near-duplicate sites of a trust region) gives the same
             // residual either way and must not cost a pooled context its clusters for the rest of the process.
             if (worst == 2 || (worst == 1 && ++ctx->small_timeouts >= 3)) ctx->small_nc = 1;
-            const int rc1 = run_small_batch(ctx, idx, problems, results, redo, 1);
+            const int rc1 = run_small_batch(ctx, idx, problems, results, redo, 1, keep, ms_sum);
             if (rc1 == 0 && worst == 0) {
                 for (const auto &sp : suspects) {
                     const double r1 = results[sp.first].fit.rel_residual;
@@ -428,6 +518,7 @@ static int run_small_batch(mrbf_ctx *ctx, const std::vector<int64_t> &idx, const
     float ms_fit = 0.f, ms_eval = 0.f;
     MRBF_HIP(ctx, hipEventElapsedTime(&ms_fit, ctx->ev[0], ctx->ev[1]));
     MRBF_HIP(ctx, hipEventElapsedTime(&ms_eval, ctx->ev[1], ctx->ev[2]));
+    if (ms_sum) *ms_sum += ms_fit + ms_eval;
     for (int i = 0; i < P; ++i) {
         const mrbf_problem &pr = problems[idx[i]];
         mrbf_result &res = results[idx[i]];
@@ -456,9 +547,124 @@ static int run_small_batch(mrbf_ctx *ctx, const std::vector<int64_t> &idx, const
     return 0;
 }
 
+// does the batched small-problem path take a fit of this shape on this context?  (decided as fit_model decides the path of a single call)
+static bool batch_takes(const mrbf_ctx *ctx, int64_t n, int d, int k, int kernel_id, double a, double b, int poly_deg) {
+    const int q = poly_dim(d, poly_deg);
+    int path = MRBF_PATH_LU;
+    if (kernel_id >= 0 && kernel_id <= 4 && n > q && poly_deg >= -1 && poly_deg <= 1 && cpd_order(kernel_id, a, b) <= poly_deg + 1)
+        path = q > 0 ? MRBF_PATH_PROJ_CHOL : MRBF_PATH_CHOL;
+    return ctx->force_path == 0 && ctx->eval_impl != 1 && small_fit_applies(ctx, n, d, k, q, path);
+}
+
 }  // namespace mrbf
 
 using namespace mrbf;
+
+extern "C" int32_t mrbf_fit_batch(mrbf_ctx *ctx, int64_t n_starts, mrbf_fit_job *jobs, float *ms_total) {
+    if (!ctx) return -1;
+    if (mrbf_dispatch_fit_batch(n_starts) != MRBF_DISPATCH_DEVICE) return -2;  // (nothing written)
+    if (!jobs) return fail(ctx, -3, "jobs is NULL");
+    for (int64_t p = 0; p < n_starts; ++p) {  // what mrbf_fit checks, job by job, before anything is written
+        const mrbf_fit_job &J = jobs[p];
+        if (J.n < 1 || J.n > 46000 || J.d < 1 || J.d > 4096 || J.k < 1 || J.k > 1024 || !J.centres || !J.values)
+            return fail(ctx, -3, "jobs[%lld]: n, d, k out of range or centres / values NULL", (long long)p);
+        if (check_kernel(ctx, J.kernel_id, J.a, J.b, J.poly_deg, 7) != 0) return fail(ctx, -3, "jobs[%lld]: invalid kernel parameters", (long long)p);
+    }
+    (void)hipSetDevice(ctx->device);
+    float ms_sum = 0.f;
+    std::vector<int64_t> small, single, redo;
+    std::vector<mrbf_problem> problems((size_t)n_starts);
+    std::vector<mrbf_result> results((size_t)n_starts);
+    std::vector<mrbf_model> shells((size_t)n_starts);
+    std::vector<size_t> at((size_t)n_starts, 0);
+    size_t total = 0;
+    for (int64_t p = 0; p < n_starts; ++p) {
+        mrbf_fit_job &J = jobs[p];
+        J.model = nullptr;
+        J.status = 0;
+        std::memset(&J.info, 0, sizeof(J.info));
+        mrbf_problem &pr = problems[p];
+        std::memset(&pr, 0, sizeof(pr));
+        pr.n = J.n;
+        pr.d = J.d;
+        pr.k = J.k;
+        pr.kernel_id = J.kernel_id;
+        pr.poly_deg = J.poly_deg;
+        pr.a = J.a;
+        pr.b = J.b;
+        pr.centres = J.centres;
+        pr.values = J.values;
+        pr.weights_out = J.weights_out;
+        pr.poly_out = J.poly_out;
+        if (!batch_takes(ctx, J.n, J.d, J.k, J.kernel_id, J.a, J.b, J.poly_deg)) {
+            single.push_back(p);
+            continue;
+        }
+        // the model's share of the slab: carved exactly as build_model_shell carves a block of its own
+        small.push_back(p);
+        model_set_dims(&shells[p], J.n, J.d, J.k, J.kernel_id, J.a, J.b, J.poly_deg);
+        size_t off[7];
+        at[p] = total;
+        total += model_block_layout(&shells[p], off);
+    }
+    ModelSlab *slab = nullptr;
+    if (!small.empty()) {
+        slab = new ModelSlab();
+        if (model_block_acquire(ctx, total, &slab->p, &slab->bytes) != 0) {  // no room for the slab: every start on its own
+            delete slab;
+            slab = nullptr;
+            single.insert(single.end(), small.begin(), small.end());
+            small.clear();
+        }
+    }
+    if (slab) {
+        for (int64_t p : small) {
+            size_t off[7];
+            (void)model_block_layout(&shells[p], off);
+            model_carve(&shells[p], (char *)slab->p + at[p], off);
+        }
+        // groups of at most 32767 starts: the batched launches put up to two descriptors per start on a grid dimension (65535).  A group
+        // whose launches fail has failed as a whole: every start of it carries the return code, none keeps a model or is fitted again.
+        constexpr size_t GROUP = 32767;
+        for (size_t g0 = 0; g0 < small.size(); g0 += GROUP) {
+            const std::vector<int64_t> group(small.begin() + g0, small.begin() + std::min(small.size(), g0 + GROUP));
+            std::vector<int64_t> flagged;
+            const int rc = run_small_batch(ctx, group, problems.data(), results.data(), &flagged, 0, shells.data(), &ms_sum);
+            if (rc != 0) {
+                (void)hipStreamSynchronize(ctx->stream);
+                for (int64_t p : group) jobs[p].status = rc;
+                continue;
+            }
+            std::sort(flagged.begin(), flagged.end());
+            for (int64_t p : group) {
+                if (std::binary_search(flagged.begin(), flagged.end(), p)) continue;
+                mrbf_fit_job &J = jobs[p];
+                mrbf_model *M = new mrbf_model(shells[p]);
+                M->slab = slab;
+                ++slab->refs;
+                ++ctx->live_models;
+                J.model = M;
+                J.info = results[p].fit;
+                J.info.slow_launches = ctx->slow_launches;
+            }
+            redo.insert(redo.end(), flagged.begin(), flagged.end());
+        }
+        if (slab->refs == 0) {  // no start kept a model here
+            model_block_release(ctx, slab->p, slab->bytes, true);
+            delete slab;
+        }
+        single.insert(single.end(), redo.begin(), redo.end());
+    }
+    // starts outside the one-launch range and flagged starts: the single call, on this context, with a block of its own
+    for (int64_t p : single) {
+        mrbf_fit_job &J = jobs[p];
+        J.status = mrbf_fit(ctx, J.n, J.d, J.k, J.centres, J.values, J.kernel_id, J.a, J.b, J.poly_deg, &J.model, J.weights_out, J.poly_out, &J.info);
+        if (J.status != 0) J.model = nullptr;
+        ms_sum += J.info.ms_total;
+    }
+    if (ms_total) *ms_total = ms_sum;
+    return MRBF_OK;
+}
 
 extern "C" int32_t mrbf_batch_run(int32_t n_dev, const int32_t *device_ids, int64_t n_problems, const mrbf_problem *problems,
                                   mrbf_result *results) {
@@ -506,13 +712,8 @@ extern "C" int32_t mrbf_batch_run(int32_t n_dev, const int32_t *device_ids, int6
         if (rc != 0) return rc;
         for (int64_t p = 0; p < n_problems; ++p) {
             const mrbf_problem &pr = problems[p];
-            const int q = poly_dim(pr.d, pr.poly_deg);
-            int path = MRBF_PATH_LU;
-            if (pr.kernel_id >= 0 && pr.kernel_id <= 4 && pr.n > q && pr.poly_deg >= -1 && pr.poly_deg <= 1 &&
-                cpd_order(pr.kernel_id, pr.a, pr.b) <= pr.poly_deg + 1)
-                path = q > 0 ? MRBF_PATH_PROJ_CHOL : MRBF_PATH_CHOL;
-            const bool ok = pr.centres && pr.values && (pr.m == 0 || pr.X) && pr.m >= 0 && probe->force_path == 0 && probe->eval_impl != 1 &&
-                            small_fit_applies(probe, pr.n, pr.d, pr.k, q, path);
+            const bool ok = pr.centres && pr.values && (pr.m == 0 || pr.X) && pr.m >= 0 &&
+                            batch_takes(probe, pr.n, pr.d, pr.k, pr.kernel_id, pr.a, pr.b, pr.poly_deg);
             if (ok)
                 small[p % n_dev].push_back(p);
             else

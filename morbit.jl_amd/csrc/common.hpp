@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/mrbf.h"
+#include "model_pool.hpp"  // Buf, ModelSlab and the pool of released model blocks
 
 namespace mrbf {
 
@@ -38,11 +39,6 @@ enum Slot {
     S_OUT_A, S_OUT_B, S_CHOL_WS, S_MISC, S_MEGA_JOBS, S_MEGA_FLAGS, S_MEGA_WQ, S_MEGA_IT, S_BSOLVE_FLAGS, S_MEGA_TRACE, S_MEGA_JLOG,
     S_T1W, S_PS_STATE, S_PS_STAT, S_PS_POLISH, S_BSOLVE_X, S_V0, S_QR_INV, S_DIAG_SCR, S_SMALL_WS, S_SMALL_DESC, S_SMALL_FLAGS, S_MEGA_STAT, S_BSOLVE_M, S_SMALL_CL, S_GW_PART, S_GW_RS, S_GW_GP, S_GW_M, S_CHECK_SCAL, S_TAIL_PART, S_PS_RANK, S_SD_IN, S_SD_OUT, S_SD_WS, S_NS_IN, S_NS_OUT, S_NS_WS, S_SD_STEP, S_SD_BATCH, S_AFF_BATCH, S_NSLOTS
 };
-struct Buf {
-    void *p = nullptr;
-    size_t bytes = 0;
-};
-
 }  // namespace mrbf
 
 namespace mrbf {
@@ -168,6 +164,7 @@ struct mrbf_model {
     double *lam = nullptr;   // q x k row-major
     void *block = nullptr;   // one device allocation carved into the arrays above
     size_t block_bytes = 0;
+    mrbf::ModelSlab *slab = nullptr;  // instead of `block`: the arrays are carved from an allocation shared with the other models of one mrbf_fit_batch call
 };
 
 namespace mrbf {
@@ -278,6 +275,14 @@ int fit_model(mrbf_ctx *ctx, mrbf_model *M, const double *Ydev, mrbf_fit_info *i
 int build_model_shell(mrbf_ctx *ctx, int64_t n, int d, int k, const double *Cdev, int kid, double a, double b, int deg,
                       mrbf_model **out);
 void destroy_model(mrbf_ctx *ctx, mrbf_model *M);
+// the pieces of build_model_shell / destroy_model that mrbf_fit_batch (batch.hip) shares: sizes and padding of a model, the layout of its
+// block (byte offsets of C, Xc, sq, mean, W, Wc, lam in off[0..6], 256-byte granularity; returns the block's size), the arrays carved
+// at `base`, and the context's pool of released blocks (model_block_acquire: *bytes = the size of the block handed out, >= total)
+void model_set_dims(mrbf_model *M, int64_t n, int d, int k, int kid, double a, double b, int deg);
+size_t model_block_layout(const mrbf_model *M, size_t off[7]);
+void model_carve(mrbf_model *M, char *base, const size_t off[7]);
+int model_block_acquire(mrbf_ctx *ctx, size_t total, void **p, size_t *bytes);
+void model_block_release(mrbf_ctx *ctx, void *p, size_t bytes, bool slab = false);  // slab: may take the place of a smaller pooled block
 int fit_check(mrbf_ctx *ctx, mrbf_model *M, const double *Y, mrbf_fit_info *info);
 // chol_mega.hip's launch clock: call after the stream has been synchronised behind a persistent factorisation
 int mega_collect_stat(mrbf_ctx *ctx);

@@ -76,6 +76,10 @@ int32_t mrbf_dispatch_affine_batch(int64_t n_starts, int32_t d, int32_t p_is_inf
     return (int64_t)8 * (d + 1) * 8 <= 64 * 1024 ? MRBF_DISPATCH_DEVICE : MRBF_DISPATCH_REFERENCE;
 }
 
+// the model updates of many starts in one call (batch.hip, mrbf_fit_batch): the start on a grid dimension; which starts the batched fit
+// takes and which the single call inside it is decided start by start in the library
+int32_t mrbf_dispatch_fit_batch(int64_t n_starts) { return n_starts >= 1 && n_starts <= 65535 ? MRBF_DISPATCH_DEVICE : MRBF_DISPATCH_REFERENCE; }
+
 int32_t mrbf_dispatch_round4(int64_t n0, int32_t d, int32_t poly_deg, int64_t n_candidates) {
     const int q = mrbf::poly_dim(d, poly_deg);
     if (n_candidates < 1 || n0 < 1 || n0 > 8192) return MRBF_DISPATCH_REFERENCE;
@@ -106,6 +110,7 @@ int32_t mrbf_dispatch_after(int32_t entry, int32_t rc) {
         case MRBF_ENTRY_SD_STEP: return rc == -2;  // shape outside the device path
         case MRBF_ENTRY_SD_BATCH: return rc == -2;  // likewise; a start whose LP gave up says so in its record, not in rc
         case MRBF_ENTRY_AFFINE_BATCH: return rc == -2;  // likewise: the callers run the single-start call (or the host filter) per start
+        case MRBF_ENTRY_FIT_BATCH: return rc == -2;  // likewise: the callers run the single fit per start
         default: return 0;
     }
 }

@@ -131,28 +131,26 @@ __global__ void residual_kernel(const double *__restrict__ a, const double *__re
 
 static inline unsigned nblk(int64_t cnt) { return (unsigned)((cnt + 255) / 256); }
 
+void model_block_release(mrbf_ctx *ctx, void *p, size_t bytes, bool slab) {
+    if (!ctx) {
+        (void)hipFree(p);
+        return;
+    }
+    model_pool_release(ctx->model_pool, p, bytes, slab, [](void *q) { (void)hipFree(q); });
+}
+
 void destroy_model(mrbf_ctx *ctx, mrbf_model *M) {
     if (!M) return;
-    if (ctx && M->block) --ctx->live_models;
-    if (M->block) {
-        size_t pooled = 0;
-        if (ctx)
-            for (auto &b : ctx->model_pool) pooled += b.bytes;
-        if (ctx && ctx->model_pool.size() < 8 && pooled + M->block_bytes <= (size_t(8) << 30)) {
-            Buf b;
-            b.p = M->block;
-            b.bytes = M->block_bytes;
-            ctx->model_pool.push_back(b);
-        } else {
-            (void)hipFree(M->block);
-        }
+    if (ctx && (M->block || M->slab)) --ctx->live_models;
+    if (M->block) model_block_release(ctx, M->block, M->block_bytes);
+    if (M->slab && slab_drop(M->slab)) {  // the last model of its mrbf_fit_batch call: the shared allocation goes as one block
+        model_block_release(ctx, M->slab->p, M->slab->bytes, true);
+        delete M->slab;
     }
     delete M;
 }
 
-int build_model_shell(mrbf_ctx *ctx, int64_t n, int d, int k, const double *Cdev, int kid, double a, double b, int deg,
-                      mrbf_model **out) {
-    mrbf_model *M = new mrbf_model();
+void model_set_dims(mrbf_model *M, int64_t n, int d, int k, int kid, double a, double b, int deg) {
     M->n = n;
     M->d = d;
     M->k = k;
@@ -162,39 +160,21 @@ int build_model_shell(mrbf_ctx *ctx, int64_t n, int d, int k, const double *Cdev
     // the fused evaluation kernels are instantiated for row strides 64, 128 and 256; wider problems keep the minimal padding
     M->dpad = (d <= 64) ? 64 : (d <= 128 ? 128 : (d <= 256 ? 256 : (int)round_up(d, 16)));
     M->kp = make_kp(kid, a, b);
-    // one block, carved at 256-byte granularity
-    const size_t cnt[7] = {(size_t)n * d, (size_t)M->npad * M->dpad, (size_t)M->npad, (size_t)M->dpad, (size_t)n * k,
-                           (size_t)M->npad * k, (size_t)std::max(M->q, 1) * k};
-    size_t off[8];
-    off[0] = 0;
-    for (int i = 0; i < 7; ++i) off[i + 1] = off[i] + ((std::max<size_t>(cnt[i], 2) * sizeof(double) + 255) & ~size_t(255));
-    const size_t total = off[7];
-    // reuse a released block when one fits without wasting more than half of it
-    int best = -1;
-    for (int i = 0; i < (int)ctx->model_pool.size(); ++i)
-        if (ctx->model_pool[i].bytes >= total && ctx->model_pool[i].bytes <= 2 * total &&
-            (best < 0 || ctx->model_pool[i].bytes < ctx->model_pool[best].bytes))
-            best = i;
-    if (best >= 0) {
-        M->block = ctx->model_pool[best].p;
-        M->block_bytes = ctx->model_pool[best].bytes;
-        ctx->model_pool.erase(ctx->model_pool.begin() + best);
-    } else {
-        hipError_t e = hipMalloc(&M->block, total);
-        if (e != hipSuccess) {
-            // drop the pool and retry once before giving up
-            for (auto &b : ctx->model_pool) (void)hipFree(b.p);
-            ctx->model_pool.clear();
-            e = hipMalloc(&M->block, total);
-        }
-        if (e != hipSuccess) {
-            delete M;
-            return fail(ctx, MRBF_ENOMEM, "model allocation failed: %s", hipGetErrorString(e));
-        }
-        M->block_bytes = total;
+}
+
+// one block, carved at 256-byte granularity
+size_t model_block_layout(const mrbf_model *M, size_t off[7]) {
+    const size_t cnt[7] = {(size_t)M->n * M->d, (size_t)M->npad * M->dpad, (size_t)M->npad, (size_t)M->dpad, (size_t)M->n * M->k,
+                           (size_t)M->npad * M->k, (size_t)std::max(M->q, 1) * M->k};
+    size_t at = 0;
+    for (int i = 0; i < 7; ++i) {
+        off[i] = at;
+        at += (std::max<size_t>(cnt[i], 2) * sizeof(double) + 255) & ~size_t(255);
     }
-    ++ctx->live_models;  // (MRBF_OPT_LIVE_HANDLES: models and round-4 states created through this context and not yet released)
-    char *base = (char *)M->block;
+    return at;
+}
+
+void model_carve(mrbf_model *M, char *base, const size_t off[7]) {
     M->C = (double *)(base + off[0]);
     M->Xc = (double *)(base + off[1]);
     M->sq = (double *)(base + off[2]);
@@ -202,6 +182,33 @@ int build_model_shell(mrbf_ctx *ctx, int64_t n, int d, int k, const double *Cdev
     M->W = (double *)(base + off[4]);
     M->Wc = (double *)(base + off[5]);
     M->lam = (double *)(base + off[6]);
+}
+
+int model_block_acquire(mrbf_ctx *ctx, size_t total, void **p, size_t *bytes) {
+    hipError_t e = hipSuccess;
+    auto alloc = [&](size_t b) -> void * {
+        void *q = nullptr;
+        e = hipMalloc(&q, b);
+        return e == hipSuccess ? q : nullptr;
+    };
+    if (!model_pool_acquire(ctx->model_pool, total, p, bytes, alloc, [](void *q) { (void)hipFree(q); }))
+        return fail(ctx, MRBF_ENOMEM, "model allocation failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+int build_model_shell(mrbf_ctx *ctx, int64_t n, int d, int k, const double *Cdev, int kid, double a, double b, int deg,
+                      mrbf_model **out) {
+    mrbf_model *M = new mrbf_model();
+    model_set_dims(M, n, d, k, kid, a, b, deg);
+    size_t off[7];
+    const size_t total = model_block_layout(M, off);
+    const int rc_block = model_block_acquire(ctx, total, &M->block, &M->block_bytes);
+    if (rc_block != 0) {
+        delete M;
+        return rc_block;
+    }
+    ++ctx->live_models;  // (MRBF_OPT_LIVE_HANDLES: models and round-4 states created through this context and not yet released)
+    model_carve(M, (char *)M->block, off);
     auto init = [&]() -> int {
         if (Cdev != M->C)
             MRBF_HIP(ctx, hipMemcpyAsync(M->C, Cdev, (size_t)n * d * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));

@@ -75,6 +75,16 @@ struct MrbfAffineJob        # mirrors mrbf_affine_job, 64 bytes
     n_picked::Int32; reserved::Int32
 end
 
+struct MrbfFitJob           # mirrors mrbf_fit_job, 168 bytes
+    n::Int64
+    d::Int32; k::Int32; kernel_id::Int32; poly_deg::Int32
+    a::Float64; b::Float64
+    centres::Ptr{Float64}; values::Ptr{Float64}; weights_out::Ptr{Float64}; poly_out::Ptr{Float64}
+    model::Ptr{Cvoid}
+    status::Int32; reserved::Int32
+    info::MrbfFitInfo
+end
+
 struct MrbfPsProblem        # mirrors mrbf_ps_problem, 72 bytes
     n_models::Int32; n_objectives::Int32
     models::Ptr{Ptr{Cvoid}}; roles::Ptr{Int32}
@@ -253,6 +263,7 @@ _dispatch_backtrack(n_models, n_foreign, in_order::Bool) =
 _dispatch_affine(n_candidates, d) = ccall((:mrbf_dispatch_affine, libmrbf), Int32, (Int64, Int32), n_candidates, d) == 1
 _dispatch_affine_batch(n_starts, d, p) =
     ccall((:mrbf_dispatch_affine_batch, libmrbf), Int32, (Int64, Int32, Int32), n_starts, d, isinf(p) ? 1 : 0) == 1
+_dispatch_fit_batch(n_starts) = ccall((:mrbf_dispatch_fit_batch, libmrbf), Int32, (Int64,), n_starts) == 1
 _dispatch_round4(n0, d, deg, n_candidates) =
     ccall((:mrbf_dispatch_round4, libmrbf), Int32, (Int64, Int32, Int32, Int64), n0, d, deg, n_candidates) == 1
 _dispatch_fit(n_training, n0, q, n_accepted, same_sites::Bool) =
@@ -1060,6 +1071,59 @@ function affine_select_batch(Ss::AbstractVector{Matrix{Float64}}, Q0s::AbstractV
         np = Int(jobs[q].n_picked)
         (Int.(picks[q][1:np]) .+ 1, Zbufs[q][:, 1:(d - Int(j0s[q]) - np)])
     end
+end
+"""
+The model updates of many starts in one device call (`mrbf_fit_batch`): the arithmetic half of `update_model` (RbfModel.jl:743-767) for
+independent starts -- the `Threads.@threads` loop over starts of examples/large_scale_benchmarks.jl:102-109 -- with the models kept.
+`Cs[p]` (d x n_p sites, one per column), `Ys[p]` (k x n_p values), `Δs[p]` and `cfgs[p]` are start p's training data, radius and
+config; `fully_linear[p]` what its meta says.  For every start the model is, bit for bit, the one `mrbf_fit` gives on that start alone.
+Where the decision table refuses the batch (`mrbf_dispatch_fit_batch`) or the library does (rc -2), every start takes `mrbf_fit`.
+Returns a vector of `HipRbfModel` (`nothing` for a start whose fit failed) and the vector of return codes.  The models of one call
+share one device allocation: its memory is reusable once all of them are released (finalizers, or `_free_model!`).
+"""
+function hip_update_models_many(cfgs::AbstractVector{HipRbfConfig}, Cs::AbstractVector{Matrix{Float64}}, Ys::AbstractVector{Matrix{Float64}},
+                                Δs::AbstractVector{<:Real}, fully_linear::AbstractVector{Bool} = fill(false, length(Cs)))
+    ns = length(Cs)
+    ctx = mrbf_context()
+    params = [_mrbf_kernel_params(Δs[q], cfgs[q]) for q in 1:ns]
+    function single(q)
+        d, n = size(Cs[q]); k = size(Ys[q], 1); kid, a, b = params[q]
+        h = Ref{Ptr{Cvoid}}(C_NULL); info = Ref{MrbfFitInfo}()
+        rc = GC.@preserve Cs Ys begin
+            _locked(ctx) do hctx
+                ccall((:mrbf_fit, libmrbf), Int32,
+                      (Ptr{Cvoid}, Int64, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Float64, Float64, Int32,
+                       Ref{Ptr{Cvoid}}, Ptr{Float64}, Ptr{Float64}, Ref{MrbfFitInfo}),
+                      hctx, n, d, k, Cs[q], Ys[q], kid, a, b, cfgs[q].polynomial_degree, h, C_NULL, C_NULL, info)
+            end
+        end
+        return rc == 0 ? HipRbfModel(ctx, h[], d, k, fully_linear[q], info[]) : nothing, rc
+    end
+    function loop()
+        res = [single(q) for q in 1:ns]
+        return [r[1] for r in res], Int32[r[2] for r in res]
+    end
+    _dispatch_fit_batch(ns) || return loop()
+    jobs = Vector{MrbfFitJob}(undef, ns)
+    ms = Ref{Float32}(0)
+    zero_info = MrbfFitInfo(ntuple(i -> zero(fieldtype(MrbfFitInfo, i)), fieldcount(MrbfFitInfo))...)
+    rc = GC.@preserve Cs Ys jobs begin
+        for q in 1:ns
+            kid, a, b = params[q]
+            jobs[q] = MrbfFitJob(size(Cs[q], 2), size(Cs[q], 1), size(Ys[q], 1), kid, cfgs[q].polynomial_degree, a, b, pointer(Cs[q]),
+                                 pointer(Ys[q]), C_NULL, C_NULL, C_NULL, 0, 0, zero_info)
+        end
+        _locked(ctx) do hctx
+            ccall((:mrbf_fit_batch, libmrbf), Int32, (Ptr{Cvoid}, Int64, Ptr{MrbfFitJob}, Ref{Float32}), hctx, ns, jobs, ms)
+        end
+    end
+    rc != 0 && _fallback_rc(11, rc) && return loop()           # the library refuses the batch: the single fit per start
+    _check(ctx, rc)
+    models = map(1:ns) do q
+        J = jobs[q]
+        J.status == 0 ? HipRbfModel(ctx, J.model, size(Cs[q], 1), size(Ys[q], 1), fully_linear[q], J.info) : nothing
+    end
+    return models, Int32[jobs[q].status for q in 1:ns]
 end
 "Scores `‖Z (Zᵀ(ξ - x₀))‖_p` of all filter candidates and the first maximiser (AffinelyIndependentPoints.jl:71-106)."
 affine_scores(shifted_seeds::AbstractVector, Z::AbstractMatrix, p = Inf) = affine_scores(_dense(_as_matrix(shifted_seeds)), Z, p)

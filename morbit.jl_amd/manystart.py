@@ -34,6 +34,35 @@ def gpu_solve_problem(problem, ctx=None):
     return rec
 
 
+def gpu_solve_shard_keep_models(problems, ctx=None, stats=None):
+    """fit + eval of a shard of problem dicts with the models KEPT: one `update_models_many` call fits all of them (mrbf_fit_batch where
+    the decision table allows it), then one evaluation per problem.  Returns (records, models): a record per problem as
+    `gpu_solve_problem` writes it (a failed fit: its status and NaNs, model None), and the resident models in problem order -- what
+    a many-start driver hands to `descent.sd_iterate_many` (wrapped in its containers) before it frees them."""
+    from . import rbf_model as rm
+
+    stats = stats if stats is not None else {}
+    mods = rm.update_models_many([p["cfg"] for p in problems], [p["sites"] for p in problems], [p["values"] for p in problems],
+                                 [p.get("delta", 1.0) for p in problems], ctx=ctx, stats=stats)
+    recs = []
+    for problem, mod, status in zip(problems, mods, stats["status"]):
+        if mod is None:
+            recs.append([float(problem["id"]), float(status) if status != 0 else -999.0] + [float("nan")] * (RECORD_LEN - 2))
+            continue
+        info = {}
+        vals = None
+        if problem.get("X") is not None and len(problem["X"]):
+            vals, _ = mod.eval_sites(problem["X"], want_values=True, want_jac=problem.get("want_jac", True), info=info)
+        recs.append([float(problem["id"]), 0.0, float(mod.info["path"]), float(mod.info["rel_residual"]), float(np.sum(mod.weights)),
+                     float(np.sum(vals)) if vals is not None else 0.0, float(mod.info["ms_total"]), float(info.get("ms_total", 0.0))])
+    return np.asarray(recs, dtype=np.float64).reshape(-1, RECORD_LEN), mods
+
+
+def run_local_keep_models(problems, rank, world_size, ctx=None, stats=None):
+    """this rank's shard through `gpu_solve_shard_keep_models`: (n_local x RECORD_LEN table, models of the shard in shard order)"""
+    return gpu_solve_shard_keep_models([problems[p] for p in shard_indices(len(problems), rank, world_size)], ctx=ctx, stats=stats)
+
+
 def run_local(problems, rank, world_size, solve=gpu_solve_problem, **kw):
     """solve this rank's shard; returns an (n_local x RECORD_LEN) float64 array"""
     recs = []

@@ -210,6 +210,72 @@ def update_model(cfg, training_sites, training_values, delta=1.0, fully_linear=F
     return RbfModel(ctx, h, n, d, k, q, fully_linear, W, L[:q], info.asdict())
 
 
+def _as_fit_input(a, rows=None):
+    """a host array (made contiguous float64) or a device tensor (used in place) as a 2-d array of `rows` rows"""
+    if hasattr(a, "data_ptr"):
+        a = a.contiguous()
+        return a.reshape(rows, -1) if rows is not None else a
+    a = _lib.host_f64(a)
+    return a.reshape(rows, -1) if rows is not None else a
+
+
+def update_models_many(cfgs, sites_list, values_list, deltas, fully_linear=False, ctx=None, stats=None):
+    """update_model for a batch of starts (the Threads.@threads loop over starts of examples/large_scale_benchmarks.jl:102-109 around
+    RbfModel.jl:743-767) in ONE mrbf_fit_batch call where mrbf_dispatch_fit_batch says so; otherwise, or when the call returns -2, the
+    loop over update_model.  cfgs / deltas / fully_linear: one per start, or one for all.  Sites and values may be NumPy arrays or torch
+    device tensors (used in place).  Returns a list of RbfModel -- for every start bit for bit the model update_model gives -- with None
+    for a start whose fit failed; stats (optional dict) receives "path" ("batch" or "loop"), "status" (return code per start) and
+    "ms_total"."""
+    ctx = ctx or _lib.default_context()
+    ns = len(sites_list)
+    per = lambda v: list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v] * ns
+    cfgs, deltas, fls = per(cfgs), per(deltas), per(fully_linear)
+    stats = stats if stats is not None else {}
+
+    def loop():
+        mods, status = [], []
+        for p in range(ns):
+            try:
+                mods.append(update_model(cfgs[p], sites_list[p], values_list[p], deltas[p], fls[p], ctx=ctx))
+                status.append(0)
+            except _lib.MrbfError as e:
+                mods.append(None)
+                status.append(e.code)
+        stats.update(path="loop", status=status, ms_total=float(sum(m.info["ms_total"] for m in mods if m is not None)))
+        return mods
+
+    if ctx.lib.mrbf_dispatch_fit_batch(ns) != _lib.DISPATCH_DEVICE:
+        return loop()
+    jobs = (_lib.FitJob * ns)()
+    keep = []
+    for p in range(ns):
+        C = _as_fit_input(sites_list[p])
+        assert C.ndim == 2, "training_sites: n sites of dimension d"
+        n, d = (int(v) for v in C.shape)
+        Y = _as_fit_input(values_list[p], n)
+        k = int(Y.shape[1])
+        kid, a, b = _get_kernel_params(deltas[p], cfgs[p])
+        deg = cfgs[p].polynomial_degree
+        q = 0 if deg < 0 else (1 if deg == 0 else d + 1)
+        W, L = np.empty((n, k)), np.empty((max(q, 1), k))
+        keep.append((C, Y, W, L, n, d, k, q))
+        J = jobs[p]
+        J.n, J.d, J.k, J.kernel_id, J.poly_deg, J.a, J.b = n, d, k, kid, deg, a, b
+        J.centres, J.values = _lib.as_ptr(C), _lib.as_ptr(Y)
+        J.weights_out, J.poly_out = _lib.as_ptr(W), _lib.as_ptr(L)
+    ms = ctypes.c_float()
+    rc = ctx.lib.mrbf_fit_batch(ctx.h, ns, jobs, ctypes.byref(ms))
+    if rc != 0 and ctx.lib.mrbf_dispatch_after(_lib.ENTRY_FIT_BATCH, rc) == 1:
+        return loop()
+    ctx.check(rc)
+    mods = []
+    for p, (C, Y, W, L, n, d, k, q) in enumerate(keep):
+        J = jobs[p]
+        mods.append(RbfModel(ctx, _lib.c_vp(J.model), n, d, k, q, fls[p], W, L[:q], J.info.asdict()) if J.status == 0 else None)
+    stats.update(path="batch", status=[int(J.status) for J in jobs], ms_total=float(ms.value))
+    return mods
+
+
 init_model = update_model      # RbfModel.jl:738-741 delegates
 improve_model = update_model   # RbfModel.jl:770-776 delegates
 
