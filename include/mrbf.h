@@ -557,6 +557,35 @@ int32_t mrbf_sd_iterate_batch(mrbf_ctx *ctx, int64_t n_starts, const mrbf_ps_pro
                               int32_t normalize, const mrbf_sd_step_options *opts, double *d_out, double *x_plus, double *mx_plus,
                               mrbf_sd_batch_record *records, float *ms_total);
 
+/* ---- many-start normal step: one call for a batch of starts (normal_batch.hip) -------------------------------------------------
+ * compute_normal_step (src/descent.jl:691-757) for n_starts independent starts of one problem -- the reference's Threads.@threads loop
+ * over starts (examples/large_scale_benchmarks.jl:102-109) -- as one chain on the ctx stream with one read-back.  For start p n_out,
+ * dual_out and every record field are, bit for bit, what mrbf_normal_step(x_p, lb, ub, delta_p, kappa_delta, delta_max,
+ * variable_radius) returns on start p's container: the roles table and linear rows of `shape` with row p of `models` (n_starts x
+ * shape->n_models handles, start-major; shape->models is ignored; models may be NULL when shape->n_models == 0: linear rows only).
+ * The starts share d, the model count, every model slot's output count, the roles and the linear rows; the number of centres and the
+ * kernel parameters may differ between starts.  x: n_starts x d; delta: n_starts; lb / ub (d): the one MOP's global bounds; n_out:
+ * n_starts x d; x_n_out (n_starts x d, may be NULL): x + n, one fp64 add per entry -- it can stay on the device and be passed as x_n
+ * to mrbf_sd_iterate_batch; dual_out (n_starts x m, may be NULL): row order as mrbf_normal_step; every array may be a host or a
+ * device pointer, records is host memory; ms_total may be NULL.  A start whose LP is infeasible, or whose radius alpha / kappa_delta
+ * exceeds delta_max, gets n = NaN, x_n = NaN and delta = -Inf in its record, as the single call returns; a start whose LP gave up
+ * (MRBF_NS_GAVE_UP) gets the same with that status in its record and does not fail the call (take the reference method for it).
+ * Every start gets a record.  Returns 0 unless an argument is invalid, -2 (take the reference method) when
+ * mrbf_dispatch_normal_batch refuses the shape (n_starts < 1 included).  -2 means nothing else here: an invalid argument (a NULL
+ * pointer, a negative count, an unknown role, kappa_delta <= 0 with a variable radius, models that do not share the shape) returns
+ * -1 or a code from -3 down, as in mrbf_sd_iterate_batch and unlike mrbf_normal_step, which answers -2 to those too. */
+typedef struct {
+    int32_t status;              /* MRBF_NS_* of this start's LP */
+    int32_t iterations, bound_flips;
+    int32_t reserved;
+    double alpha;                /* as mrbf_normal_info.alpha */
+    double delta;                /* as mrbf_normal_info.delta (-Inf: infeasible, or above delta_max) */
+} mrbf_normal_batch_record;      /* 32 bytes */
+int32_t mrbf_normal_step_batch(mrbf_ctx *ctx, int64_t n_starts, const mrbf_ps_problem *shape, const mrbf_model *const *models, int32_t d,
+                               const double *x, const double *lb, const double *ub, const double *delta, double kappa_delta,
+                               double delta_max, int32_t variable_radius, double *n_out, double *x_n_out, double *dual_out,
+                               mrbf_normal_batch_record *records, float *ms_total);
+
 /* ---- the decision table of the host bindings ---------------------------------------------------------------------------
  * Which implementation a binding (morbit.jl_amd/julia/HipRbf.jl, the Python mirror) takes for one call of Morbit's interface:
  * the device entry point (MRBF_DISPATCH_DEVICE) or Morbit's own method on the same arguments (MRBF_DISPATCH_REFERENCE; Julia:
@@ -590,6 +619,9 @@ int32_t mrbf_sd_iterate_batch(mrbf_ctx *ctx, int64_t n_starts, const mrbf_ps_pro
  *   mrbf_dispatch_sd_batch   the two calls above for n_starts starts in one (mrbf_sd_iterate_batch): device iff mrbf_dispatch_sd
  *                            and mrbf_dispatch_sd_step both say so, d <= 256 (the fused evaluation kernels' range) and
  *                            1 <= n_starts <= 65535 (a grid dimension).
+ *   mrbf_dispatch_normal_batch  compute_normal_step for n_starts starts in one call (mrbf_normal_step_batch): device iff
+ *                            mrbf_dispatch_normal says so, 1 <= n_starts <= 65535 (a grid dimension) and, where modelled rows are
+ *                            evaluated (n_nl > 0), d <= 256 (the fused evaluation kernels' range); linear rows alone keep d <= 4096.
  *   mrbf_dispatch_fit_batch  update_model of n_starts starts in one call (mrbf_fit_batch): device iff 1 <= n_starts <= 65535 (a grid
  *                            dimension).  Which starts share the batched launches is decided inside the call, start by start.
  *   mrbf_dispatch_after      the return code rc of a device entry point (MRBF_ENTRY_*) that means "take the reference method
@@ -599,7 +631,7 @@ enum { MRBF_DISPATCH_REFERENCE = 0, MRBF_DISPATCH_DEVICE = 1 };
 enum { MRBF_FIT_FULL = 0, MRBF_FIT_FROM_ROUND4 = 1 };
 enum { MRBF_ENTRY_ROUND4 = 1, MRBF_ENTRY_FIT_FROM_ROUND4 = 2, MRBF_ENTRY_PS_STEP = 3, MRBF_ENTRY_BACKTRACK = 4, MRBF_ENTRY_AFFINE = 5,
        MRBF_ENTRY_SD = 6, MRBF_ENTRY_NORMAL = 7, MRBF_ENTRY_SD_STEP = 8, MRBF_ENTRY_SD_BATCH = 9, MRBF_ENTRY_AFFINE_BATCH = 10,
-       MRBF_ENTRY_FIT_BATCH = 11 };
+       MRBF_ENTRY_FIT_BATCH = 11, MRBF_ENTRY_NORMAL_BATCH = 12 };
 int32_t mrbf_dispatch_ps(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_sd(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_normal(int32_t d, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
@@ -607,6 +639,8 @@ int32_t mrbf_dispatch_sd_step(int32_t d, int32_t k, int32_t n_models, int32_t n_
                               int32_t max_loops);
 int32_t mrbf_dispatch_sd_batch(int64_t n_starts, int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints,
                                int32_t n_lin_constraints, int32_t n_foreign, int32_t max_loops);
+int32_t mrbf_dispatch_normal_batch(int64_t n_starts, int32_t d, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints,
+                                   int32_t n_foreign);
 int32_t mrbf_dispatch_backtrack(int32_t n_objective_models, int32_t n_foreign, int32_t outputs_in_order);
 int32_t mrbf_dispatch_affine(int64_t n_candidates, int32_t d);
 int32_t mrbf_dispatch_affine_batch(int64_t n_starts, int32_t d, int32_t p_is_inf);

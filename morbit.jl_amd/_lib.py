@@ -62,6 +62,7 @@ ENTRY_ROUND4, ENTRY_FIT_FROM_ROUND4, ENTRY_PS_STEP, ENTRY_BACKTRACK, ENTRY_AFFIN
 ENTRY_SD_BATCH = 9
 ENTRY_AFFINE_BATCH = 10
 ENTRY_FIT_BATCH = 11
+ENTRY_NORMAL_BATCH = 12
 SD_OK, SD_NO_OBJECTIVE, SD_INFEASIBLE, SD_GAVE_UP = 0, 1, 2, 3
 NS_OK, NS_INFEASIBLE, NS_GAVE_UP = 0, 1, 2
 SD_BRANCH_DELTA, SD_BRANCH_ONE, SD_BRANCH_INTERSECT = 0, 1, 2
@@ -107,6 +108,14 @@ class SdBatchRecord(ctypes.Structure):
     _fields_ = [("sd_status", ctypes.c_int32), ("iterations", ctypes.c_int32), ("bound_flips", ctypes.c_int32), ("branch", ctypes.c_int32),
                 ("loops", ctypes.c_int32), ("reserved", ctypes.c_int32), ("omega", ctypes.c_double), ("omega_step", ctypes.c_double),
                 ("sigma", ctypes.c_double), ("step_norm", ctypes.c_double)]
+
+    def asdict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class NormalBatchRecord(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("iterations", ctypes.c_int32), ("bound_flips", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("alpha", ctypes.c_double), ("delta", ctypes.c_double)]
 
     def asdict(self):
         return {f: getattr(self, f) for f, _ in self._fields_}
@@ -208,6 +217,10 @@ SIGNATURES = {
                                                c_vp, c_vp, ctypes.c_int32, ctypes.POINTER(SdStepOptions), c_vp, c_vp, c_vp,
                                                ctypes.POINTER(SdBatchRecord), c_fp]),
     "mrbf_dispatch_sd_batch": (ctypes.c_int32, [ctypes.c_int64] + [ctypes.c_int32] * 7),
+    "mrbf_normal_step_batch": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.POINTER(PsProblem), ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
+                                                c_vp, c_vp, c_vp, c_vp, ctypes.c_double, ctypes.c_double, ctypes.c_int32, c_vp, c_vp, c_vp,
+                                                ctypes.POINTER(NormalBatchRecord), c_fp]),
+    "mrbf_dispatch_normal_batch": (ctypes.c_int32, [ctypes.c_int64] + [ctypes.c_int32] * 5),
     "mrbf_dispatch_ps": (ctypes.c_int32, [ctypes.c_int32] * 6),
     "mrbf_dispatch_sd_step": (ctypes.c_int32, [ctypes.c_int32] * 7),
     "mrbf_dispatch_sd": (ctypes.c_int32, [ctypes.c_int32] * 6),

@@ -1,0 +1,134 @@
+// What the many-start chains (sd_batch.hip, normal_batch.hip) share: the fetch of an input into the packed upload, and the evaluations of
+// a batch -- model slot j of start p at one of the chain's sites -- grouped by what one eval_fused_batch launch requires, with their
+// descriptors and their scratch in the chain's arena.  Every member takes the centre-range split of the single call it stands for
+// (eval_nsplit on its own query count) and partial buffers of its own, so the order of every sum is that call's.
+#pragma once
+#include "small.hpp"
+
+namespace mrbf {
+namespace chain {
+
+inline int batch_fetch(mrbf_ctx *ctx, const double *src, size_t cnt, double *dst) {
+    if (!cnt) return 0;
+    if (is_device_ptr(src)) MRBF_HIP(ctx, hipMemcpy(dst, src, cnt * sizeof(double), hipMemcpyDeviceToHost));
+    else std::memcpy(dst, src, cnt * sizeof(double));
+    return 0;
+}
+
+constexpr int64_t MAX_GROUP_LAUNCH = 65535;  // blockIdx.z of the evaluation kernels
+
+// one evaluation of the batch: model slot j of start p at `site`, mq query rows
+struct Member {
+    int site, j;
+    int64_t p;
+    int group;  // launch group, or -1: eval_model
+    const mrbf_model *M;
+    int64_t mq;
+    bool jac;
+    // where the member reads and writes, offsets in doubles from the arena's base: the caller's to set before fill() / launch()
+    size_t X = 0, vals = 0, jacs = 0;
+    // scratch (carve): offsets likewise
+    size_t Xq = 0, xsq = 0, vpart = 0, gpart = 0;
+    int64_t mpad = 0;
+    int nsplit = 1, KO = 0;
+};
+struct Group {
+    int site, D, k;
+    bool jac;
+    KP kp;
+    std::vector<size_t> members;
+    size_t first;  // index of the group's first descriptor in the device array
+};
+
+struct Plan {
+    std::vector<Member> mem;
+    std::vector<Group> groups;
+    size_t n_desc = 0;
+
+    // members are added site by site; a group is (site, kernel and parameters, k, dpad, split or unsplit centre range)
+    void add(const mrbf_ctx *ctx, int site, int64_t p, int j, const mrbf_model *M, int64_t mq, bool jac) {
+        Member mb;
+        mb.site = site, mb.j = j, mb.p = p, mb.M = M, mb.mq = mq, mb.jac = jac;
+        mb.nsplit = eval_nsplit(ctx, mq, (int)((M->n + 63) / 64));
+        mb.group = group_of(ctx, site, M, jac, mb.nsplit > 1);
+        if (mb.group >= 0) groups[mb.group].members.push_back(mem.size());
+        mem.push_back(mb);
+    }
+    // after the last add: the descriptors' places
+    void close() {
+        n_desc = 0;
+        for (Group &G : groups) G.first = n_desc, n_desc += G.members.size();
+    }
+    size_t desc_doubles() const { return (n_desc * sizeof(EvalDesc) + sizeof(double) - 1) / sizeof(double); }
+    // the scratch of every grouped member, in member order: take(count) returns the offset of `count` doubles of the arena
+    template <class Take>
+    void carve(Take &&take) {
+        for (Member &S : mem) {
+            if (S.group < 0) continue;
+            S.mpad = round_up(S.mq, 64);
+            S.KO = outputs_per_pass(S.M->k, S.M->dpad, S.jac);
+            S.Xq = take((size_t)S.mpad * S.M->dpad);
+            S.xsq = take((size_t)S.mpad);
+            S.vpart = take(S.nsplit > 1 ? (size_t)S.nsplit * S.mpad * S.KO * 2 : 0);
+            S.gpart = take((S.nsplit > 1 && S.jac) ? (size_t)S.nsplit * S.mpad * S.KO * S.M->dpad : 0);
+        }
+    }
+    // the descriptors (host copy, to be uploaded to the same place of the arena), group by group
+    void fill(double *base, EvalDesc *hdesc) const {
+        for (const Group &G : groups)
+            for (size_t r = 0; r < G.members.size(); ++r) {
+                const Member &S = mem[G.members[r]];
+                EvalDesc E;
+                std::memset(&E, 0, sizeof(E));
+                eval_desc_model(E, S.M, S.mq, S.nsplit);
+                E.X = base + S.X;
+                E.Xq = base + S.Xq;
+                E.xsq = base + S.xsq;
+                if (S.nsplit > 1) {
+                    E.vpart = base + S.vpart;
+                    E.sapart = E.vpart + (size_t)S.nsplit * S.mpad * S.KO;
+                    if (S.jac) E.gpart = base + S.gpart;
+                }
+                E.vals = base + S.vals;
+                E.jac = S.jac ? base + S.jacs : nullptr;
+                std::memcpy(&hdesc[G.first + r], &E, sizeof(E));
+            }
+    }
+    // the evaluations of one site on the ctx stream: its launch groups, then the members the fused kernels do not take
+    int launch(mrbf_ctx *ctx, int site, double *base, const EvalDesc *hdesc, const EvalDesc *ddesc) const {
+        for (const Group &G : groups) {
+            if (G.site != site) continue;
+            for (size_t r0 = 0; r0 < G.members.size(); r0 += MAX_GROUP_LAUNCH) {
+                const int cnt = (int)std::min<size_t>(MAX_GROUP_LAUNCH, G.members.size() - r0);
+                MRBF_TRY(eval_fused_batch(ctx, G.kp, G.D, G.k, G.jac, hdesc + G.first + r0, ddesc + G.first + r0, cnt));
+            }
+        }
+        for (const Member &S : mem) {
+            if (S.site != site || S.group >= 0) continue;
+            MRBF_TRY(eval_model(ctx, S.M, S.mq, base + S.X, base + S.vals, S.jac ? base + S.jacs : nullptr, nullptr));
+        }
+        return 0;
+    }
+
+private:
+    int group_of(const mrbf_ctx *ctx, int site, const mrbf_model *M, bool jac, bool split) {
+        if (ctx->eval_impl == 1 || !(M->dpad == 64 || M->dpad == 128 || M->dpad == 256)) return -1;
+        for (size_t g = 0; g < groups.size(); ++g) {
+            const Group &G = groups[g];
+            if (G.site == site && G.D == M->dpad && G.k == M->k && G.jac == jac && std::memcmp(&G.kp, &M->kp, sizeof(KP)) == 0) {
+                // (the group's kernels either all write partial sums or none does: split and unsplit members launch apart)
+                return (int)(g & ~(size_t)1) + (split ? 1 : 0);
+            }
+        }
+        // a new key: its unsplit group, then its split group
+        for (int s = 0; s < 2; ++s) {
+            Group G;
+            G.site = site, G.D = M->dpad, G.k = M->k, G.jac = jac, G.kp = M->kp, G.first = 0;
+            groups.push_back(G);
+        }
+        return (int)groups.size() - 2 + (split ? 1 : 0);
+    }
+};
+
+}  // namespace chain
+}  // namespace mrbf

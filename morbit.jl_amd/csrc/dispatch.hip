@@ -56,6 +56,15 @@ int32_t mrbf_dispatch_sd_batch(int64_t n_starts, int32_t d, int32_t k, int32_t n
     return mrbf_dispatch_sd_step(d, k, n_models, n_nl_constraints, n_lin_constraints, n_foreign, max_loops);
 }
 
+// the normal steps of many starts in one call (normal_batch.hip): what the single call takes, with the start on a grid dimension;
+// modelled rows are evaluated by the fused evaluation kernels (dpad in {64, 128, 256}), linear rows alone need no evaluation
+int32_t mrbf_dispatch_normal_batch(int64_t n_starts, int32_t d, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints,
+                                   int32_t n_foreign) {
+    if (n_starts < 1 || n_starts > 65535) return MRBF_DISPATCH_REFERENCE;
+    if (n_nl_constraints != 0 && d > 256) return MRBF_DISPATCH_REFERENCE;
+    return mrbf_dispatch_normal(d, n_models, n_nl_constraints, n_lin_constraints, n_foreign);
+}
+
 int32_t mrbf_dispatch_backtrack(int32_t n_objective_models, int32_t n_foreign, int32_t outputs_in_order) {
     return (n_objective_models == 1 && n_foreign == 0 && outputs_in_order != 0) ? MRBF_DISPATCH_DEVICE : MRBF_DISPATCH_REFERENCE;
 }
@@ -111,6 +120,7 @@ int32_t mrbf_dispatch_after(int32_t entry, int32_t rc) {
         case MRBF_ENTRY_SD_BATCH: return rc == -2;  // likewise; a start whose LP gave up says so in its record, not in rc
         case MRBF_ENTRY_AFFINE_BATCH: return rc == -2;  // likewise: the callers run the single-start call (or the host filter) per start
         case MRBF_ENTRY_FIT_BATCH: return rc == -2;  // likewise: the callers run the single fit per start
+        case MRBF_ENTRY_NORMAL_BATCH: return rc == -2;  // likewise; a start whose LP gave up says so in its record, not in rc
         default: return 0;
     }
 }

@@ -19,14 +19,11 @@
 // nothing accumulates; the primal point and the multipliers are recomputed from it.  A result is accepted only when, besides
 // primal feasibility, every multiplier of an inequality member of W is >= -DUAL_TOL (else GAVE_UP).  Every sum runs in a fixed order that
 // depends on the shape alone, and no atomics touch values: an LP's result does not depend on its position in the batch.
-#include "common.hpp"
+#include "normal.hpp"
 
 namespace mrbf {
 namespace ns {
 
-constexpr int THREADS = 256;
-constexpr int MAXM = 64;
-constexpr int MAXD = 4096;
 constexpr double FEAS_TOL = 1e-13;    // relative to the constraint's magnitude
 constexpr double PIVOT_TOL = 1e-9;    // ratio-test candidates: rate > PIVOT_TOL * the largest |rate|
 constexpr double PIVOT_FLOOR = 1e-13; // ... and > PIVOT_FLOOR (a lone rate at rounding level is no pivot)
@@ -41,6 +38,7 @@ __host__ __device__ inline int tau(int t) { return t >> 1; }
 
 struct Args {
     int n, meq, min, m;
+    int64_t bs;  // LP p reads lb / ub at + p * bs (0: one box for every LP)
     const double *x, *lb, *ub, *Aeq, *beq, *Ain, *bin;
     double *n_out, *alpha_out, *dual_out;
     int *status_out, *iters_out;
@@ -167,7 +165,7 @@ __global__ __launch_bounds__(THREADS) void normal_lp_kernel(Args a, int64_t lp0)
     double *cmaxv = vec + 12 * ms, *cnrm = vec + 13 * ms;  // rowbuf takes 2 ms
 
     const Lp L{a.Aeq ? a.Aeq + lp * meq * n : nullptr, a.Ain ? a.Ain + lp * a.min * n : nullptr, n, meq};
-    const double *x = a.x + lp * n, *lb = a.lb + lp * n, *ub = a.ub + lp * n;
+    const double *x = a.x + lp * n, *lb = a.lb + lp * a.bs, *ub = a.ub + lp * a.bs;
     double *nv = a.ws + (size_t)blockIdx.x * 6 * n, *lo = nv + n, *hi = nv + 2 * n, *mu = nv + 3 * n, *lam = nv + 4 * n, *pc = nv + 5 * n;
     int *pin = a.wsi + (size_t)blockIdx.x * n;
     const double INF = __builtin_huge_val();
@@ -511,50 +509,45 @@ __global__ __launch_bounds__(THREADS) void normal_lp_kernel(Args a, int64_t lp0)
     }
 }
 
-// ---- the right-hand sides of the normal step: one workgroup per LP row, the Jacobians / values of the evaluation kernels as they lie
-struct RowSrc {
-    int kind;      // 1 linear row, 2 modelled constraint row
-    int dst;       // row of A_eq or A_ineq
-    int eq;        // 1: equality block
-    int stride;    // rows of the model (k_j): the Jacobian is k_j x d column-major
-    int64_t jac;   // offset of the row's first Jacobian entry at x
-    int64_t val;   // offset of the row's value at x / index of the linear row
-};
-struct AsmArgs {
-    int n;
-    const double *J, *V, *x, *Alin, *blin;
-    double *Aeq, *beq, *Ain, *bin;
-    RowSrc src[MAXM];
-};
-
+// ---- the right-hand sides of the normal step (normal.hpp): one workgroup per LP row and start
 __global__ __launch_bounds__(THREADS) void normal_assemble_kernel(AsmArgs a) {
     __shared__ double part[THREADS];
     const RowSrc s = a.src[blockIdx.x];
     const int t = threadIdx.x, n = a.n;
-    double *row = (s.eq ? a.Aeq : a.Ain) + (size_t)s.dst * n;
-    const double *src = s.kind == 1 ? a.Alin + s.val * n : a.J + s.jac;
+    // the start's blocks (the argument itself stays untouched: a modified copy of it would live in scratch memory)
+    const int64_t p = blockIdx.y;
+    const double *J = a.J + p * a.sJ, *V = a.V + p * a.sV, *x = a.x + p * a.sx;
+    double *A = s.eq ? a.Aeq + p * a.meq * n : a.Ain + p * a.min * n, *b = s.eq ? a.beq + p * a.meq : a.bin + p * a.min;
+    double *row = A + (size_t)s.dst * n;
+    const double *src = s.kind == 1 ? a.Alin + s.val * n : J + s.jac;
     const int64_t step = s.kind == 1 ? 1 : s.stride;
     double acc = 0.0;
     for (int j = t; j < n; j += THREADS) {
         const double v = src[j * step];
         row[j] = v;
-        if (s.kind == 1) acc += v * a.x[j];
+        if (s.kind == 1) acc += v * x[j];
     }
     part[t] = acc;
     __syncthreads();
     if (t == 0) {
         double sum = 0.0;
         for (int i = 0; i < THREADS; ++i) sum += part[i];
-        (s.eq ? a.beq : a.bin)[s.dst] = s.kind == 1 ? a.blin[s.val] - sum : -a.V[s.val];  // b - A x  /  -m(x)
+        b[s.dst] = s.kind == 1 ? a.blin[s.val] - sum : -V[s.val];  // b - A x  /  -m(x)
     }
 }
 
-// all device pointers; LPs in chunks so that the per-LP workspace stays below 256 MB
-static int launch(mrbf_ctx *ctx, int64_t n_lp, int n, int meq, int min, const double *x, const double *lb, const double *ub,
-                  const double *Aeq, const double *beq, const double *Ain, const double *bin, double *n_out, double *alpha_out,
-                  double *dual_out, int *status_out, int *iters_out) {
+int launch_assemble(mrbf_ctx *ctx, const AsmArgs &a, int64_t n_starts) {
+    hipLaunchKernelGGL(normal_assemble_kernel, dim3((unsigned)a.rows, (unsigned)n_starts), dim3(THREADS), 0, ctx->stream, a);
+    MRBF_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
+int launch(mrbf_ctx *ctx, int64_t n_lp, int n, int meq, int min, const double *x, const double *lb, const double *ub, int64_t bound_stride,
+           const double *Aeq, const double *beq, const double *Ain, const double *bin, double *n_out, double *alpha_out, double *dual_out,
+           int *status_out, int *iters_out) {
     Args a;
     a.n = n, a.meq = meq, a.min = min, a.m = meq + min;
+    a.bs = bound_stride;
     a.x = x, a.lb = lb, a.ub = ub, a.Aeq = Aeq, a.beq = beq, a.Ain = Ain, a.bin = bin;
     a.n_out = n_out, a.alpha_out = alpha_out, a.dual_out = dual_out, a.status_out = status_out, a.iters_out = iters_out;
     const size_t per = (size_t)n * (6 * sizeof(double) + sizeof(int));
@@ -651,7 +644,7 @@ extern "C" int32_t mrbf_normal_direction(mrbf_ctx *ctx, int64_t n_lp, int32_t d,
     double *on = dev_n ? n_out : ob, *oa = dev_a ? alpha_out : ob + N * d, *oy = dual_out ? (dev_y ? dual_out : ob + N * d + N) : nullptr;
     int *oi = reinterpret_cast<int *>(ob + out_dbl);
     int *os = dev_s ? status_out : oi, *ot = iters_out ? (dev_i ? iters_out : oi + N) : nullptr;
-    MRBF_TRY(ns::launch(ctx, n_lp, d, m_eq, m_ineq, dx, dlb, dub, dAeq, dbeq, dAin, dbin, on, oa, oy, os, ot));
+    MRBF_TRY(ns::launch(ctx, n_lp, d, m_eq, m_ineq, dx, dlb, dub, d, dAeq, dbeq, dAin, dbin, on, oa, oy, os, ot));
     if (!dev_n) MRBF_HIP(ctx, hipMemcpyAsync(n_out, on, N * d * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (!dev_a) MRBF_HIP(ctx, hipMemcpyAsync(alpha_out, oa, N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (oy && !dev_y) MRBF_HIP(ctx, hipMemcpyAsync(dual_out, oy, N * m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -734,17 +727,18 @@ extern "C" int32_t mrbf_normal_step(mrbf_ctx *ctx, const mrbf_ps_problem *prob, 
         if (used[j]) MRBF_TRY(eval_model(ctx, prob->models[j], 1, dx, dV + voff[j], dJ + joff[j], nullptr));
     // ---- A_eq / b_eq (linear, then modelled), A_ineq / b_ineq (likewise) on the device
     ns::AsmArgs aa;
-    aa.n = d, aa.J = dJ, aa.V = dV, aa.x = dx, aa.Alin = dA, aa.blin = db;
+    aa.n = d, aa.rows = m, aa.meq = meq, aa.min = min;
+    aa.sJ = jtot, aa.sV = vtot, aa.sx = d;
+    aa.J = dJ, aa.V = dV, aa.x = dx, aa.Alin = dA, aa.blin = db;
     aa.Aeq = dAeq, aa.beq = dbeq, aa.Ain = dAin, aa.bin = dbin;
     int r = 0;
     for (int i = 0; i < prob->n_lin_eq; ++i) aa.src[r++] = ns::RowSrc{1, i, 1, 1, 0, i};
     for (size_t i = 0; i < meq_rows.size(); ++i) aa.src[r] = meq_rows[i], aa.src[r++].dst = prob->n_lin_eq + (int)i;
     for (int i = 0; i < prob->n_lin_ineq; ++i) aa.src[r++] = ns::RowSrc{1, i, 0, 1, 0, prob->n_lin_eq + i};
     for (size_t i = 0; i < min_rows.size(); ++i) aa.src[r] = min_rows[i], aa.src[r++].dst = prob->n_lin_ineq + (int)i;
-    hipLaunchKernelGGL(ns::normal_assemble_kernel, dim3((unsigned)m), dim3(ns::THREADS), 0, ctx->stream, aa);
-    MRBF_HIP(ctx, hipGetLastError());
+    MRBF_TRY(ns::launch_assemble(ctx, aa, 1));
     int *oi = reinterpret_cast<int *>(dout + d + 1 + m);
-    MRBF_TRY(ns::launch(ctx, 1, d, meq, min, dx, dlb, dub, meq ? dAeq : nullptr, meq ? dbeq : nullptr, min ? dAin : nullptr,
+    MRBF_TRY(ns::launch(ctx, 1, d, meq, min, dx, dlb, dub, 0, meq ? dAeq : nullptr, meq ? dbeq : nullptr, min ? dAin : nullptr,
                         min ? dbin : nullptr, dout, dout + d, dout + d + 1, oi, oi + 1));
     // ---- one read-back
     std::vector<double> hout(out_cnt);

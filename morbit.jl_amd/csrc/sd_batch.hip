@@ -22,38 +22,14 @@
 // count does not depend on n_starts.  DESIGN.md section 11.
 #include <limits>
 
+#include "batch_chain.hpp"
 #include "sd.hpp"
-#include "small.hpp"
 
 using namespace mrbf;
+using chain::batch_fetch;
 
 namespace {
-
-int batch_fetch(mrbf_ctx *ctx, const double *src, size_t cnt, double *dst) {
-    if (!cnt) return 0;
-    if (is_device_ptr(src)) MRBF_HIP(ctx, hipMemcpy(dst, src, cnt * sizeof(double), hipMemcpyDeviceToHost));
-    else std::memcpy(dst, src, cnt * sizeof(double));
-    return 0;
-}
-
 enum Site { SITE_PAIR = 0, SITE_X = 1, SITE_TRIAL = 2 };
-
-// one evaluation of the batch: model slot j of start p at one of the three sites
-struct Member {
-    int site, j;
-    int64_t p;
-    int group;  // launch group, or -1: eval_model
-};
-struct Group {
-    int site, D, k;
-    bool jac;
-    KP kp;
-    std::vector<size_t> members;
-    size_t first;  // index of the group's first descriptor in the device array
-};
-
-constexpr int64_t MAX_GROUP_LAUNCH = 65535;  // blockIdx.z of the evaluation kernels
-
 }  // namespace
 
 extern "C" int32_t mrbf_sd_iterate_batch(mrbf_ctx *ctx, int64_t n_starts, const mrbf_ps_problem *shape, const mrbf_model *const *models,
@@ -149,40 +125,16 @@ extern "C" int32_t mrbf_sd_iterate_batch(mrbf_ctx *ctx, int64_t n_starts, const 
         if (has_obj[j]) ooff[j] = otot, otot += (int64_t)(L + 2) * kj[j];
     (void)hipSetDevice(ctx->device);
     PinGuard pin(ctx);
-    // ---- the evaluations of the two single calls, grouped by what one eval_fused_batch launch requires
-    std::vector<Member> mem;
-    std::vector<Group> groups;
-    const bool fused_ok = ctx->eval_impl != 1;
-    auto group_of = [&](int site, const mrbf_model *M, bool jac, bool split) -> int {
-        if (!fused_ok || !(M->dpad == 64 || M->dpad == 128 || M->dpad == 256)) return -1;
-        for (size_t g = 0; g < groups.size(); ++g) {
-            const Group &G = groups[g];
-            if (G.site == site && G.D == M->dpad && G.k == M->k && G.jac == jac && std::memcmp(&G.kp, &M->kp, sizeof(KP)) == 0) {
-                // (the group's kernels either all write partial sums or none does: split and unsplit members launch apart)
-                return (int)(g & ~(size_t)1) + (split ? 1 : 0);
-            }
-        }
-        // a new key: its unsplit group, then its split group
-        for (int s = 0; s < 2; ++s) {
-            Group G;
-            G.site = site, G.D = M->dpad, G.k = M->k, G.jac = jac, G.kp = M->kp, G.first = 0;
-            groups.push_back(G);
-        }
-        return (int)groups.size() - 2 + (split ? 1 : 0);
-    };
+    // ---- the evaluations of the two single calls, grouped by what one eval_fused_batch launch requires (batch_chain.hpp)
+    chain::Plan ev;
     auto site_m = [&](int site) -> int64_t { return site == SITE_PAIR ? 2 : (site == SITE_X ? 1 : L + 2); };
     for (int site = 0; site < 3; ++site)
         for (int64_t p = 0; p < N; ++p)
             for (int j = 0; j < nm; ++j) {
                 if (!(site == SITE_PAIR ? used[j] : (site == SITE_X ? has_con[j] : has_obj[j]))) continue;
-                const mrbf_model *M = models[p * nm + j];
-                const int nsplit = eval_nsplit(ctx, site_m(site), (int)((M->n + 63) / 64));
-                Member mb{site, j, p, group_of(site, M, site != SITE_TRIAL, nsplit > 1)};
-                if (mb.group >= 0) groups[mb.group].members.push_back(mem.size());
-                mem.push_back(mb);
+                ev.add(ctx, site, p, j, models[p * nm + j], site_m(site), site != SITE_TRIAL);
             }
-    size_t n_desc = 0;
-    for (Group &G : groups) G.first = n_desc, n_desc += G.members.size();
+    ev.close();
     // ---- the arena (doubles; every piece a multiple of 16): upload | work | evaluation scratch | output block
     size_t total = 0;
     auto take = [&](size_t cnt) {
@@ -197,32 +149,20 @@ extern "C" int32_t mrbf_sd_iterate_batch(mrbf_ctx *ctx, int64_t n_starts, const 
     for (int i = 0; i < shape->n_lin_ineq; ++i) rows.push_back(RowRef{(int64_t)(shape->n_lin_eq + i) * d, shape->n_lin_eq + i, 1, 0});
     rows.insert(rows.end(), min_ref.begin(), min_ref.end());
     const size_t rows_dbl = (rows.size() * sizeof(RowRef) + sizeof(double) - 1) / sizeof(double);
-    const size_t desc_dbl = (n_desc * sizeof(EvalDesc) + sizeof(double) - 1) / sizeof(double);
+    const size_t desc_dbl = ev.desc_doubles();
     const size_t oPairs = take(SN * 2 * d), oDelta = take(SN), oLb = take(d), oUb = take(d), oA = take(nlin * d), oB = take(nlin);
     const size_t oRows = take(rows_dbl), oDesc = take(desc_dbl);
     const size_t up_cnt = total;
     const size_t oJA = take(SN * jtotA), oVA = take(SN * vtotA), oJB = take(SN * jtotB), oVB = take(SN * vtotB);
     const size_t oG = take(SN * k * d), oAeq = take(SN * meq * d), oBeq = take(SN * meq), oAin = take(SN * min * d), oBin = take(SN * min);
     const size_t oSteps = take(SN * (L + 1)), oSig = take(SN * 2), oX = take(SN * (L + 2) * d), oVO = take(SN * otot);
-    struct Scratch {
-        size_t Xq, xsq, vpart, gpart;
-        int64_t mpad;
-        int nsplit, KO;
-    };
-    std::vector<Scratch> scr(mem.size());
-    for (size_t i = 0; i < mem.size(); ++i) {
-        if (mem[i].group < 0) continue;
-        const mrbf_model *M = models[mem[i].p * nm + mem[i].j];
-        const bool jac = mem[i].site != SITE_TRIAL;
-        Scratch &S = scr[i];
-        const int64_t mq = site_m(mem[i].site);
-        S.mpad = round_up(mq, 64);
-        S.nsplit = eval_nsplit(ctx, mq, (int)((M->n + 63) / 64));
-        S.KO = outputs_per_pass(M->k, M->dpad, jac);
-        S.Xq = take((size_t)S.mpad * M->dpad);
-        S.xsq = take((size_t)S.mpad);
-        S.vpart = take(S.nsplit > 1 ? (size_t)S.nsplit * S.mpad * S.KO * 2 : 0);
-        S.gpart = take((S.nsplit > 1 && jac) ? (size_t)S.nsplit * S.mpad * S.KO * M->dpad : 0);
+    ev.carve(take);
+    for (chain::Member &mb : ev.mem) {
+        const size_t p = (size_t)mb.p;
+        const int j = mb.j;
+        if (mb.site == SITE_PAIR) mb.X = oPairs + p * 2 * d, mb.vals = oVA + p * vtotA + voffA[j], mb.jacs = oJA + p * jtotA + joffA[j];
+        else if (mb.site == SITE_X) mb.X = oPairs + p * 2 * d + d, mb.vals = oVB + p * vtotB + voffB[j], mb.jacs = oJB + p * jtotB + joffB[j];
+        else mb.X = oX + p * (size_t)(L + 2) * d, mb.vals = oVO + p * otot + ooff[j];
     }
     // the output block: x+ | m(x+) | [omega_step, step_norm, loops, sigma, branch] | d | omega | status, (iterations, flips) words
     const size_t out0 = total;
@@ -257,56 +197,12 @@ extern "C" int32_t mrbf_sd_iterate_batch(mrbf_ctx *ctx, int64_t n_starts, const 
     double *dPairs = base + oPairs, *dX = base + oX;
     EvalDesc *hdesc = reinterpret_cast<EvalDesc *>(hup + oDesc);
     const EvalDesc *ddesc = reinterpret_cast<const EvalDesc *>(base + oDesc);
-    for (const Group &G : groups)
-        for (size_t r = 0; r < G.members.size(); ++r) {
-            const size_t i = G.members[r];
-            const Member &mb = mem[i];
-            const mrbf_model *M = models[mb.p * nm + mb.j];
-            const Scratch &S = scr[i];
-            const int j = mb.j;
-            const size_t p = (size_t)mb.p;
-            EvalDesc E;
-            std::memset(&E, 0, sizeof(E));
-            eval_desc_model(E, M, site_m(mb.site), S.nsplit);
-            E.X = mb.site == SITE_PAIR ? dPairs + p * 2 * d : (mb.site == SITE_X ? dPairs + p * 2 * d + d : dX + p * (size_t)(L + 2) * d);
-            E.Xq = base + S.Xq;
-            E.xsq = base + S.xsq;
-            if (S.nsplit > 1) {
-                E.vpart = base + S.vpart;
-                E.sapart = E.vpart + (size_t)S.nsplit * S.mpad * S.KO;
-                if (mb.site != SITE_TRIAL) E.gpart = base + S.gpart;
-            }
-            if (mb.site == SITE_PAIR) E.vals = base + oVA + p * vtotA + voffA[j], E.jac = base + oJA + p * jtotA + joffA[j];
-            else if (mb.site == SITE_X) E.vals = base + oVB + p * vtotB + voffB[j], E.jac = base + oJB + p * jtotB + joffB[j];
-            else E.vals = base + oVO + p * otot + ooff[j], E.jac = nullptr;
-            std::memcpy(&hdesc[G.first + r], &E, sizeof(E));
-        }
+    ev.fill(base, hdesc);
     hipStream_t st = ctx->stream;
     hipEvent_t e0 = ctx->ev[0], e1 = ctx->ev[1];
     MRBF_HIP(ctx, hipEventRecord(e0, st));
     MRBF_HIP(ctx, hipMemcpyAsync(base, hup, up_cnt * sizeof(double), hipMemcpyHostToDevice, st));
-    auto evaluate = [&](int site) -> int {
-        for (const Group &G : groups) {
-            if (G.site != site) continue;
-            for (size_t r0 = 0; r0 < G.members.size(); r0 += MAX_GROUP_LAUNCH) {
-                const int cnt = (int)std::min<size_t>(MAX_GROUP_LAUNCH, G.members.size() - r0);
-                MRBF_TRY(eval_fused_batch(ctx, G.kp, G.D, G.k, G.jac, hdesc + G.first + r0, ddesc + G.first + r0, cnt));
-            }
-        }
-        for (const Member &mb : mem) {
-            if (mb.site != site || mb.group >= 0) continue;
-            const mrbf_model *M = models[mb.p * nm + mb.j];
-            const size_t p = (size_t)mb.p;
-            const int j = mb.j;
-            if (site == SITE_PAIR)
-                MRBF_TRY(eval_model(ctx, M, 2, dPairs + p * 2 * d, base + oVA + p * vtotA + voffA[j], base + oJA + p * jtotA + joffA[j], nullptr));
-            else if (site == SITE_X)
-                MRBF_TRY(eval_model(ctx, M, 1, dPairs + p * 2 * d + d, base + oVB + p * vtotB + voffB[j], base + oJB + p * jtotB + joffB[j], nullptr));
-            else
-                MRBF_TRY(eval_model(ctx, M, L + 2, dX + p * (size_t)(L + 2) * d, base + oVO + p * otot + ooff[j], nullptr, nullptr));
-        }
-        return 0;
-    };
+    auto evaluate = [&](int site) -> int { return ev.launch(ctx, site, base, hdesc, ddesc); };
     MRBF_TRY(evaluate(SITE_PAIR));
     MRBF_TRY(evaluate(SITE_X));
     // ---- G, A_eq / b_eq (linear, then modelled), A_ineq / b_ineq (likewise) of every start

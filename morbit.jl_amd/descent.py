@@ -676,3 +676,83 @@ def sd_iterate_many(cfg, containers, scal, X, X_n, deltas, lb, ub, lin=None, sta
         if not lib.mrbf_dispatch_after(_lib.ENTRY_SD_BATCH, rc):
             p0["models"][0].ctx.check(rc)
     return [single(p) for p in range(ns)]
+
+
+# ---- the normal steps of many starts in one device call (mrbf_normal_step_batch) ------------------------------------------------------
+def normal_step_batch_device(plans, X, lb, ub, deltas, lin=None, kappa_delta=1.0, delta_max=np.inf, variable_radius=False, out=None,
+                             want_duals=False):
+    """one mrbf_normal_step_batch call on the containers' plans (one shape, checked by the caller); X (n_starts x d), lb, ub, deltas
+    may be NumPy arrays or device tensors; out = (n, x_n) lets the caller pass its own output buffers (host or device).  Returns
+    (rc, n, x_n, list of record dicts, event ms[, duals])."""
+    ns, nm = len(plans), len(plans[0]["models"])
+    ctx = plans[0]["models"][0].ctx if nm else _lib.default_context()
+
+    def arr(a):
+        return a if hasattr(a, "data_ptr") else np.ascontiguousarray(a, dtype=np.float64)
+
+    X, lb, ub, deltas = arr(X), arr(lb), arr(ub), arr(deltas)
+    d = int(lb.numel() if hasattr(lb, "numel") else lb.size)
+    prob, keep = _ns_problem(plans[0], lin or (None,) * 4)
+    m = plans[0]["n_con"] + sum(0 if b is None else b.size for b in (keep[3], keep[5]))
+    handles = (ctypes.c_void_p * max(ns * nm, 1))(*[m_.model.value if hasattr(m_.model, "value") else m_.model
+                                                    for p in plans for m_ in p["models"]])
+    n, x_n = out if out is not None else (np.empty((ns, d)), np.empty((ns, d)))
+    y = np.empty((ns, max(m, 1))) if want_duals else None
+    recs = (_lib.NormalBatchRecord * ns)()
+    ms = ctypes.c_float()
+    rc = ctx.lib.mrbf_normal_step_batch(ctx.h, ns, ctypes.byref(prob), handles if nm else None, d, _lib.as_ptr(X), _lib.as_ptr(lb),
+                                        _lib.as_ptr(ub), _lib.as_ptr(deltas), float(kappa_delta), float(delta_max),
+                                        int(bool(variable_radius)), _lib.as_ptr(n), _lib.as_ptr(x_n), _lib.as_ptr(y), recs, ctypes.byref(ms))
+    res = (rc, n, x_n, [r.asdict() for r in recs], ms.value)
+    return res + (y[:, :m],) if want_duals else res
+
+
+def normal_steps_many(containers, scal, X, deltas, lb, ub, lin=None, kappa_delta=1.0, delta_max=np.inf, variable_radius=False, stats=None,
+                      x_n_out=None):
+    """compute_normal_step (descent.jl:691-757) for many independent starts of one problem -- the reference's `Threads.@threads` loop
+    over starts (examples/large_scale_benchmarks.jl:102-109): containers[p] is start p's surrogate container, X[p] / deltas[p] its
+    iterate and radius; lb / ub and lin belong to the one MOP.  Where the containers share one plan shape and
+    mrbf_dispatch_normal_batch says so, ONE mrbf_normal_step_batch call serves all starts ("batch"); otherwise, and for every start
+    whose LP gave up, the routed single-start function runs (`compute_normal_step`).  Returns a list of (n, delta); stats gets "path"
+    ("batch" or "loop"), "rerouted" (the starts that took the single-start function after a batch call), and after a batch call
+    "records" and "ms_total".  x_n_out (n_starts x d, a NumPy array or a device tensor) receives x + n of every start: given a device
+    tensor the batch writes it on the device, ready to be the X_n of `sd_iterate_batch_device`."""
+    lib = _lib.load()
+    X = np.asarray(X, dtype=np.float64)
+    deltas = np.asarray(deltas, dtype=np.float64).ravel()
+    ns = len(containers)
+    lin = lin or (None,) * 4
+    n_lin = sum(0 if b is None else int(np.asarray(b).size) for b in (lin[1], lin[3]))
+
+    def single(p):
+        n, dl = compute_normal_step(containers[p], scal, X[p], float(deltas[p]), lb, ub, lin, kappa_delta, delta_max, variable_radius)
+        if x_n_out is not None:
+            x_n_out[p] = x_n_out.new_tensor(X[p] + n) if hasattr(x_n_out, "new_tensor") else X[p] + n
+        return n, dl
+
+    if stats is not None:
+        stats["path"], stats["rerouted"] = "loop", []
+    if ns == 0:
+        return []
+    plans = [sg.container_plan(sc) for sc in containers]
+    d = int(X.shape[1])
+    p0 = plans[0]
+    n_foreign_con = p0["n_foreign"] - sg.container_plan(containers[0], objectives_only=True)["n_foreign"]
+    if _same_plan_shape(plans) and lib.mrbf_dispatch_normal_batch(ns, d, len(p0["models"]), p0["n_con"], n_lin, n_foreign_con) \
+            == _lib.DISPATCH_DEVICE:
+        out = None if x_n_out is None else (np.empty((ns, d)), x_n_out)
+        rc, n, _, records, ms = normal_step_batch_device(plans, X, lb, ub, deltas, lin, kappa_delta, delta_max, variable_radius, out=out)
+        if rc == 0:
+            res, rerouted = [], []
+            for p, r in enumerate(records):
+                if r["status"] == _lib.NS_GAVE_UP:             # this start's LP gave up: the reference method for it alone
+                    rerouted.append(p)
+                    res.append(single(p))
+                else:
+                    res.append((n[p].copy(), float(r["delta"])))
+            if stats is not None:
+                stats.update(path="batch", rerouted=rerouted, records=records, ms_total=ms)
+            return res
+        if not lib.mrbf_dispatch_after(_lib.ENTRY_NORMAL_BATCH, rc):
+            (p0["models"][0].ctx if p0["models"] else _lib.default_context()).check(rc)
+    return [single(p) for p in range(ns)]

@@ -67,6 +67,11 @@ struct MrbfSdBatchRecord    # mirrors mrbf_sd_batch_record, 56 bytes
     omega::Float64; omega_step::Float64; sigma::Float64; step_norm::Float64
 end
 
+struct MrbfNormalBatchRecord    # mirrors mrbf_normal_batch_record, 32 bytes
+    status::Int32; iterations::Int32; bound_flips::Int32; reserved::Int32
+    alpha::Float64; delta::Float64
+end
+
 struct MrbfAffineJob        # mirrors mrbf_affine_job, 64 bytes
     mc::Int64
     j0::Int32; max_picks::Int32
@@ -258,6 +263,9 @@ _dispatch_sd_step(d, k, n_models, n_nl, n_lin, n_foreign, max_loops) =
 _dispatch_sd_batch(n_starts, d, k, n_models, n_nl, n_lin, n_foreign, max_loops) =
     ccall((:mrbf_dispatch_sd_batch, libmrbf), Int32, (Int64, Int32, Int32, Int32, Int32, Int32, Int32, Int32),
           n_starts, d, k, n_models, n_nl, n_lin, n_foreign, max_loops) == 1
+_dispatch_normal_batch(n_starts, d, n_models, n_nl, n_lin, n_foreign) =
+    ccall((:mrbf_dispatch_normal_batch, libmrbf), Int32, (Int64, Int32, Int32, Int32, Int32, Int32),
+          n_starts, d, n_models, n_nl, n_lin, n_foreign) == 1
 _dispatch_backtrack(n_models, n_foreign, in_order::Bool) =
     ccall((:mrbf_dispatch_backtrack, libmrbf), Int32, (Int32, Int32, Int32), n_models, n_foreign, in_order) == 1
 _dispatch_affine(n_candidates, d) = ccall((:mrbf_dispatch_affine, libmrbf), Int32, (Int64, Int32), n_candidates, d) == 1
@@ -929,6 +937,70 @@ function hip_sd_iterate_many(desc_cfg::SteepestDescentConfig, mop, scal, x_its::
         r.sigma > desc_cfg.min_stepsize ||
             return 0, Xet.(dirs[:, p]), copy(get_x_scaled(x_it_ns[p])), Xet.(MX₊[:, p]), 0    # descent.jl:317
         (Xet(r.omega), Xet.(dirs[:, p]), Xet.(X₊[:, p]), Xet.(MX₊[:, p]), Xet(r.step_norm))
+    end
+end
+
+"""
+The normal steps of many starts in one device call (`mrbf_normal_step_batch`): `compute_normal_step` (descent.jl:691-757) for
+independent starts of one problem -- the `Threads.@threads` loop over starts of examples/large_scale_benchmarks.jl:102-109 -- as one
+chain of launches and one read-back.  `x_its[p]` and `scs[p]` are start p's iterate and surrogate container; `mop`, `scal` and the
+configuration belong to the one problem.  For every start the result is, bit for bit, what `hip_compute_normal_step` returns on that
+start alone.  Where the containers do not share one plan shape, the decision table refuses (`mrbf_dispatch_normal_batch`: a modelled
+constraint row on a foreign surrogate, modelled rows at d > 256, more than 65535 starts, the limits of the single call) or a start's LP
+gave up, those starts take the single-start function.  Returns a vector of (n, Δ).
+"""
+function hip_normal_steps_many(mop, scal, x_its::AbstractVector, data_base, scs::AbstractVector{<:SurrogateContainer}, algo_config;
+                               variable_radius::Bool = false)
+    single(p) = hip_compute_normal_step(mop, scal, x_its[p], data_base, scs[p], algo_config; variable_radius = variable_radius)
+    loop() = [single(p) for p in eachindex(scs)]
+    ns = length(scs)
+    (ns >= 1 && all(_touches_device, scs)) || return loop()
+    plans = [_container_plan(sc) for sc in scs]
+    p1 = plans[1]
+    same = all(pl -> pl.roles == p1.roles && pl.k == p1.k && pl.n_con == p1.n_con && pl.n_foreign == p1.n_foreign &&
+                     length(pl.models) == length(p1.models), plans)
+    same || return loop()
+    n_foreign_con = p1.n_foreign - _container_plan(scs[1]; objectives_only = true).n_foreign   # foreign objectives do not matter here
+    d, nm = length(get_x_scaled(x_its[1])), length(p1.models)
+    A_eq, b_eq = transformed_linear_eq_constraints(scal, mop)                  # AbstractMOPInterface.jl:463-481: A x_scaled (=, <=) b
+    A_in, b_in = transformed_linear_ineq_constraints(scal, mop)
+    _dispatch_normal_batch(ns, d, nm, p1.n_con, length(b_eq) + length(b_in), n_foreign_con) || return loop()
+    lb_g, ub_g = full_bounds_internal(scal)
+    lb = Vector{Float64}(lb_g); ub = Vector{Float64}(ub_g)
+    X = Matrix{Float64}(undef, d, ns)                                          # column p = start p: the n_starts x d row-major array
+    for p in 1:ns
+        X[:, p] .= get_x_scaled(x_its[p])
+    end
+    Δ = Float64[get_delta(x_it) for x_it in x_its]
+    κ_Δ = Float64(filter_kappa_delta(algo_config)); Δ_max = Float64(delta_max(algo_config))
+    N = Matrix{Float64}(undef, d, ns)
+    records = Vector{MrbfNormalBatchRecord}(undef, ns)
+    ms = Ref{Float32}(0)
+    handles = Ptr{Cvoid}[m.handle for pl in plans for m in pl.models]          # start-major
+    roles = p1.roles
+    Aeq = Matrix{Float64}(transpose(Matrix(A_eq))); beq = Vector{Float64}(b_eq)   # row-major rows x d == the d x rows column-major matrix
+    Ain = Matrix{Float64}(transpose(Matrix(A_in))); bin = Vector{Float64}(b_in)
+    # the table admits linear rows only: the containers' HipRbfModels may all sit in foreign surrogates (no model in the plans)
+    ctx = isempty(p1.models) ? mrbf_context() : p1.models[1].ctx
+    rc = GC.@preserve handles roles Aeq beq Ain bin X Δ lb ub N records begin
+        prob = Ref(MrbfPsProblem(nm, p1.k, C_NULL, pointer(roles), length(beq), length(bin),
+                                 isempty(beq) ? C_NULL : pointer(Aeq), isempty(beq) ? C_NULL : pointer(beq),
+                                 isempty(bin) ? C_NULL : pointer(Ain), isempty(bin) ? C_NULL : pointer(bin), -1.0))
+        _locked(ctx) do hctx
+            ccall((:mrbf_normal_step_batch, libmrbf), Int32,
+                  (Ptr{Cvoid}, Int64, Ref{MrbfPsProblem}, Ptr{Ptr{Cvoid}}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                   Float64, Float64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{MrbfNormalBatchRecord}, Ref{Float32}),
+                  hctx, ns, prob, handles, d, X, lb, ub, Δ, κ_Δ, Δ_max, variable_radius, N, C_NULL, C_NULL, records, ms)
+        end
+    end
+    rc != 0 && _fallback_rc(12, rc) && return loop()           # a shape outside the device path: the single-start function
+    _check(ctx, rc)
+    Xet = eltype(get_x_scaled(x_its[1]))
+    return map(1:ns) do p
+        r = records[p]
+        r.status == 2 && return single(p)                      # MRBF_NS_GAVE_UP: Morbit's JuMP model for this start alone
+        r.delta == -Inf && return fill(MIN_PRECISION(NaN64), d), -MIN_PRECISION(Inf)      # infeasible (descent.jl:746-748)
+        (Xet.(N[:, p]), Xet(r.delta))                          # n already projected into [lb, ub] (descent.jl:752-754)
     end
 end
 
