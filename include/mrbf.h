@@ -243,6 +243,38 @@ int32_t mrbf_fit_from_round4(mrbf_ctx *ctx, const mrbf_round4_state *state, int3
 int32_t mrbf_round4_sites(const mrbf_round4_state *state, int64_t *n0, int64_t *n_candidates, int32_t *n_accepted);
 int32_t mrbf_free_round4(mrbf_ctx *ctx, mrbf_round4_state *state);
 
+/* ---- many-start round 4: the site selection of a batch of small starts in one call (round4_small.hip) ------------------------
+ * _rbf_round4 (src/models/RbfModel.jl:352-499) for n_starts independent starts -- the reference's Threads.@threads loop over starts
+ * (examples/large_scale_benchmarks.jl:102-109, :253) -- on ONE context.  For every start p, accepted_out and n_accepted are the list
+ * mrbf_round4(ctx, n0_p, d, start_sites_p, mc_p, cand_sites_p, ...) returns: the same acceptance test, tau^2 > (theta_pivot_cholesky^2)^2
+ * with at most max_points sites in all (<= 0: (d+1)(d+2)/2), walked in candidate order by a kernel of its own for the small shape (one
+ * workgroup per start, right-looking; the sums run in another order than the blocked walk's, so a decision that sits on the threshold
+ * to within rounding may differ).  A start's list does not depend on its position in the batch or on which other starts share it.
+ * NO FACTOR STATE IS KEPT: there is no mrbf_round4_state to hand to mrbf_fit_from_round4; the fits of a batch go through
+ * mrbf_fit_batch.  Nothing of the call outlives it (MRBF_OPT_LIVE_HANDLES is unchanged; the workspace is the context's arena).
+ * The small range -- starts that share six launches whose grids span all of them, one packed descriptor upload and one read-back:
+ *   d <= 128,  q <= n0 <= 256,  1 <= mc <= 4096,  min(mc, max_points - n0) <= 256 (the resulting model is in mrbf_fit_batch's one-launch
+ *   range), and at most 2 GiB of workspace for the batch.
+ * Every other start of an otherwise valid batch (and a start whose start set the batched chain finds rank deficient) runs mrbf_round4
+ * inside the call, after the batched chain, with state = NULL; what that returned is the start's rc (read it with
+ * mrbf_dispatch_after(MRBF_ENTRY_ROUND4_BATCH, rc): -2 / MRBF_ESINGULAR = take the host mirror for this start).  One such start does
+ * not fail the others.  The call returns 0 unless an argument is invalid (an invalid field of a job is an invalid `jobs`: -4) or
+ * mrbf_dispatch_round4_batch refuses the shape (-2: take mrbf_round4 per start; nothing is written).  ms_total (may be NULL): hipEvent
+ * time of the batched chain on the ctx stream, without the starts that took the single call. */
+typedef struct {
+    int64_t n0, mc;                 /* start sites, candidates (mc = 0: nothing to do) */
+    const double *start_sites;      /* n0 x d row-major, host or device */
+    const double *cand_sites;       /* mc x d row-major, host or device, database order */
+    int32_t kernel_id, poly_deg;
+    double a, b;
+    int32_t max_points;
+    double theta_pivot_cholesky;
+    int32_t *accepted_out;          /* host, min(mc, max_points - n0) entries */
+    int32_t n_accepted;             /* out */
+    int32_t rc;                     /* out: 0, or what mrbf_round4 returned for a start that took it */
+} mrbf_round4_job;                  /* 88 bytes */
+int32_t mrbf_round4_batch(mrbf_ctx *ctx, int64_t n_starts, int32_t d, mrbf_round4_job *jobs, float *ms_total);
+
 int32_t mrbf_model_dims(const mrbf_model *model, int64_t *n, int32_t *d, int32_t *k, int32_t *q);
 int32_t mrbf_free_model(mrbf_ctx *ctx, mrbf_model *model);
 
@@ -624,6 +656,11 @@ int32_t mrbf_normal_step_batch(mrbf_ctx *ctx, int64_t n_starts, const mrbf_ps_pr
  *                            evaluated (n_nl > 0), d <= 256 (the fused evaluation kernels' range); linear rows alone keep d <= 4096.
  *   mrbf_dispatch_fit_batch  update_model of n_starts starts in one call (mrbf_fit_batch): device iff 1 <= n_starts <= 65535 (a grid
  *                            dimension).  Which starts share the batched launches is decided inside the call, start by start.
+ *   mrbf_dispatch_round4_batch  _rbf_round4 of n_starts starts in one call (mrbf_round4_batch): device iff 1 <= n_starts <= 65535 (a grid
+ *                            dimension) and 1 <= d <= 1024 (mrbf_round4's own limit).  Which starts share the batched launches (the small
+ *                            range: d <= 128, q <= n0 <= 256, mc <= 4096, at most 256 sites to accept) is decided inside the call.
+ *                            The bindings keep the loop of single calls where the batch does not pay (measured, DESIGN.md section
+ *                            14: fewer than 8 starts, or fewer than one start per 32 candidates of the largest start).
  *   mrbf_dispatch_after      the return code rc of a device entry point (MRBF_ENTRY_*) that means "take the reference method
  *                            for this call" (start set without the tail or rank deficient, limits of the device path) rather
  *                            than an error: 1 = fall back, 0 = rc is what it says. */
@@ -631,7 +668,7 @@ enum { MRBF_DISPATCH_REFERENCE = 0, MRBF_DISPATCH_DEVICE = 1 };
 enum { MRBF_FIT_FULL = 0, MRBF_FIT_FROM_ROUND4 = 1 };
 enum { MRBF_ENTRY_ROUND4 = 1, MRBF_ENTRY_FIT_FROM_ROUND4 = 2, MRBF_ENTRY_PS_STEP = 3, MRBF_ENTRY_BACKTRACK = 4, MRBF_ENTRY_AFFINE = 5,
        MRBF_ENTRY_SD = 6, MRBF_ENTRY_NORMAL = 7, MRBF_ENTRY_SD_STEP = 8, MRBF_ENTRY_SD_BATCH = 9, MRBF_ENTRY_AFFINE_BATCH = 10,
-       MRBF_ENTRY_FIT_BATCH = 11, MRBF_ENTRY_NORMAL_BATCH = 12 };
+       MRBF_ENTRY_FIT_BATCH = 11, MRBF_ENTRY_NORMAL_BATCH = 12, MRBF_ENTRY_ROUND4_BATCH = 13 };
 int32_t mrbf_dispatch_ps(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_sd(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_normal(int32_t d, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
@@ -646,6 +683,7 @@ int32_t mrbf_dispatch_affine(int64_t n_candidates, int32_t d);
 int32_t mrbf_dispatch_affine_batch(int64_t n_starts, int32_t d, int32_t p_is_inf);
 int32_t mrbf_dispatch_round4(int64_t n0, int32_t d, int32_t poly_deg, int64_t n_candidates);
 int32_t mrbf_dispatch_fit_batch(int64_t n_starts);
+int32_t mrbf_dispatch_round4_batch(int64_t n_starts, int32_t d);
 int32_t mrbf_dispatch_fit(int64_t n_training, int64_t state_n0, int32_t state_q, int32_t state_n_accepted, int32_t same_sites);
 int32_t mrbf_dispatch_after(int32_t entry, int32_t rc);
 

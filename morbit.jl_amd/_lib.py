@@ -63,6 +63,7 @@ ENTRY_SD_BATCH = 9
 ENTRY_AFFINE_BATCH = 10
 ENTRY_FIT_BATCH = 11
 ENTRY_NORMAL_BATCH = 12
+ENTRY_ROUND4_BATCH = 13
 SD_OK, SD_NO_OBJECTIVE, SD_INFEASIBLE, SD_GAVE_UP = 0, 1, 2, 3
 NS_OK, NS_INFEASIBLE, NS_GAVE_UP = 0, 1, 2
 SD_BRANCH_DELTA, SD_BRANCH_ONE, SD_BRANCH_INTERSECT = 0, 1, 2
@@ -128,6 +129,14 @@ class AffineJob(ctypes.Structure):
                 ("n_picked", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class Round4Job(ctypes.Structure):
+    """mrbf_round4_job: one start of mrbf_round4_batch"""
+    _fields_ = [("n0", ctypes.c_int64), ("mc", ctypes.c_int64), ("start_sites", ctypes.c_void_p), ("cand_sites", ctypes.c_void_p),
+                ("kernel_id", ctypes.c_int32), ("poly_deg", ctypes.c_int32), ("a", ctypes.c_double), ("b", ctypes.c_double),
+                ("max_points", ctypes.c_int32), ("theta_pivot_cholesky", ctypes.c_double), ("accepted_out", ctypes.c_void_p),
+                ("n_accepted", ctypes.c_int32), ("rc", ctypes.c_int32)]
+
+
 class FitJob(ctypes.Structure):
     """mrbf_fit_job: one start of mrbf_fit_batch"""
     _fields_ = [("n", ctypes.c_int64), ("d", ctypes.c_int32), ("k", ctypes.c_int32), ("kernel_id", ctypes.c_int32),
@@ -182,6 +191,8 @@ SIGNATURES = {
     "mrbf_fit_from_round4": (ctypes.c_int32, [c_vp, c_vp, ctypes.c_int32, c_vp, ctypes.POINTER(c_vp), c_vp, c_vp, ctypes.POINTER(FitInfo)]),
     "mrbf_round4_sites": (ctypes.c_int32, [c_vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), c_ip]),
     "mrbf_free_round4": (ctypes.c_int32, [c_vp, c_vp]),
+    "mrbf_round4_batch": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(Round4Job), c_fp]),
+    "mrbf_dispatch_round4_batch": (ctypes.c_int32, [ctypes.c_int64, ctypes.c_int32]),
     "mrbf_model_dims": (ctypes.c_int32, [c_vp, ctypes.POINTER(ctypes.c_int64), c_ip, c_ip, c_ip]),
     "mrbf_free_model": (ctypes.c_int32, [c_vp, c_vp]),
     "mrbf_batch_run": (ctypes.c_int32, [ctypes.c_int32, c_ip, ctypes.c_int64, ctypes.POINTER(Problem),

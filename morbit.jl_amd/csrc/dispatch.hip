@@ -98,6 +98,13 @@ int32_t mrbf_dispatch_round4(int64_t n0, int32_t d, int32_t poly_deg, int64_t n_
     return n0 >= q ? MRBF_DISPATCH_DEVICE : MRBF_DISPATCH_REFERENCE;
 }
 
+// round 4 of many starts in one call (round4_small.hip, mrbf_round4_batch): the start on a grid dimension and mrbf_round4's own limit on
+// d (a start outside the small kernel's range takes mrbf_round4 inside the call); which starts share the batched launches is decided
+// inside the call, start by start
+int32_t mrbf_dispatch_round4_batch(int64_t n_starts, int32_t d) {
+    return n_starts >= 1 && n_starts <= 65535 && d >= 1 && d <= 1024 ? MRBF_DISPATCH_DEVICE : MRBF_DISPATCH_REFERENCE;
+}
+
 int32_t mrbf_dispatch_fit(int64_t n_training, int64_t state_n0, int32_t state_q, int32_t state_n_accepted, int32_t same_sites) {
     if (state_n0 < 1 || state_n_accepted < 1 || !same_sites) return MRBF_FIT_FULL;
     if (state_n0 != state_q) return MRBF_FIT_FULL;  // the kept factor only covers the directions added by round 4
@@ -121,6 +128,9 @@ int32_t mrbf_dispatch_after(int32_t entry, int32_t rc) {
         case MRBF_ENTRY_AFFINE_BATCH: return rc == -2;  // likewise: the callers run the single-start call (or the host filter) per start
         case MRBF_ENTRY_FIT_BATCH: return rc == -2;  // likewise: the callers run the single fit per start
         case MRBF_ENTRY_NORMAL_BATCH: return rc == -2;  // likewise; a start whose LP gave up says so in its record, not in rc
+        // the call itself: -2 (the table refuses the shape: the single call, or the host mirror, per start); a start's own rc
+        // (mrbf_round4_job.rc, what mrbf_round4 returned for it) reads as MRBF_ENTRY_ROUND4's
+        case MRBF_ENTRY_ROUND4_BATCH: return rc == -2 || rc == -3 || rc == -5 || rc == MRBF_ESINGULAR || rc == MRBF_ENOMEM;
         default: return 0;
     }
 }

@@ -80,6 +80,17 @@ struct MrbfAffineJob        # mirrors mrbf_affine_job, 64 bytes
     n_picked::Int32; reserved::Int32
 end
 
+struct MrbfRound4Job        # mirrors mrbf_round4_job, 88 bytes
+    n0::Int64; mc::Int64
+    start_sites::Ptr{Float64}; cand_sites::Ptr{Float64}
+    kernel_id::Int32; poly_deg::Int32
+    a::Float64; b::Float64
+    max_points::Int32
+    theta_pivot_cholesky::Float64
+    accepted_out::Ptr{Int32}
+    n_accepted::Int32; rc::Int32
+end
+
 struct MrbfFitJob           # mirrors mrbf_fit_job, 168 bytes
     n::Int64
     d::Int32; k::Int32; kernel_id::Int32; poly_deg::Int32
@@ -272,11 +283,17 @@ _dispatch_affine(n_candidates, d) = ccall((:mrbf_dispatch_affine, libmrbf), Int3
 _dispatch_affine_batch(n_starts, d, p) =
     ccall((:mrbf_dispatch_affine_batch, libmrbf), Int32, (Int64, Int32, Int32), n_starts, d, isinf(p) ? 1 : 0) == 1
 _dispatch_fit_batch(n_starts) = ccall((:mrbf_dispatch_fit_batch, libmrbf), Int32, (Int64,), n_starts) == 1
+_dispatch_round4_batch(n_starts, d) = ccall((:mrbf_dispatch_round4_batch, libmrbf), Int32, (Int64, Int32), n_starts, d) == 1
 _dispatch_round4(n0, d, deg, n_candidates) =
     ccall((:mrbf_dispatch_round4, libmrbf), Int32, (Int64, Int32, Int32, Int64), n0, d, deg, n_candidates) == 1
 _dispatch_fit(n_training, n0, q, n_accepted, same_sites::Bool) =
     ccall((:mrbf_dispatch_fit, libmrbf), Int32, (Int64, Int64, Int32, Int32, Int32), n_training, n0, q, n_accepted, same_sites) == 1
 "Does return code `rc` of device entry point `entry` (1 round4, 2 fit_from_round4, 3 ps_step) mean: take the reference method?"
+# Where `hip_round4_many` takes the batched call (measured: tools/round4_batch_bench.py, DESIGN.md section 14): at least 8 starts, and at
+# least one start per 32 candidates of the largest start; below that the loop of single calls is faster.
+const ROUND4_BATCH_MIN_STARTS = 8
+const ROUND4_BATCH_CANDIDATES_PER_START = 32
+_round4_batch_pays(n_starts, max_candidates) = n_starts >= ROUND4_BATCH_MIN_STARTS && n_starts * ROUND4_BATCH_CANDIDATES_PER_START >= max_candidates
 _fallback_rc(entry, rc) = ccall((:mrbf_dispatch_after, libmrbf), Int32, (Int32, Int32), entry, rc) == 1
 
 # ---- two-phase construction: phase I (which sites) stays Morbit's control flow (RbfModel.jl:506-655 is generic in `cfg`); the
@@ -1065,6 +1082,50 @@ function rbf_round4_device(cfg::HipRbfConfig, Δ, start_sites, cand_sites; keep_
     end
     rc_only && return rc, accepted, state
     return keep_state ? (accepted, state) : accepted
+end
+"""
+Round 4 of many starts in one device call (`mrbf_round4_batch`): `_rbf_round4`'s selection (RbfModel.jl:352-499) for independent
+starts of one problem -- the `Threads.@threads` loop over starts of examples/large_scale_benchmarks.jl:102-109 -- with small starts
+(d <= 128, q <= n0 <= 256, at most 4096 candidates and 256 sites to accept) sharing six launches and one read-back; any other start
+runs `mrbf_round4` inside the call.  `cfgs[p]`, `Δs[p]`, `start_sites[p]` and `cand_sites[p]` (vectors of sites; with `use_max_points`
+the caller appends the random box points, as for `rbf_round4_device`) are start p's arguments of `rbf_round4_device`; the starts share
+d.  No factor state is kept: the fits of a batch go through `hip_update_models_many`.  Returns, per start, `(rc, positions)`: rc 0 and the
+1-based positions of the accepted candidates in acceptance order, or the return code `mrbf_round4` gave for that start (read it with
+`_fallback_rc(13, rc)`: take Morbit's own loop for it).  Where the batch does not pay (`_round4_batch_pays`: measured, DESIGN.md section 14), where
+the decision table refuses the batch (`mrbf_dispatch_round4_batch`) or the library does (rc -2), every start takes `rbf_round4_device`.
+"""
+function hip_round4_many(cfgs::AbstractVector{HipRbfConfig}, Δs::AbstractVector{<:Real}, start_sites::AbstractVector, cand_sites::AbstractVector)
+    ns = length(cfgs)
+    function loop()
+        return map(1:ns) do p
+            rc, accepted, _ = rbf_round4_device(cfgs[p], Δs[p], start_sites[p], cand_sites[p]; rc_only = true)
+            (Int32(rc), accepted)
+        end
+    end
+    (ns >= 1 && _round4_batch_pays(ns, maximum(length, cand_sites))) || return loop()
+    C0s = [_dense(_as_matrix(start_sites[p])) for p in 1:ns]
+    d = size(C0s[1], 1)
+    (all(C -> size(C, 1) == d, C0s) && _dispatch_round4_batch(ns, d)) || return loop()
+    Xcs = [isempty(cand_sites[p]) ? Matrix{Float64}(undef, d, 0) : _dense(_as_matrix(cand_sites[p])) for p in 1:ns]
+    accs = [Vector{Int32}(undef, max(size(Xcs[p], 2), 1)) for p in 1:ns]
+    ctx = mrbf_context()
+    ms = Ref{Float32}(0)
+    jobs = Vector{MrbfRound4Job}(undef, ns)
+    rc = GC.@preserve C0s Xcs accs jobs begin
+        for p in 1:ns
+            kid, a, b = _mrbf_kernel_params(Δs[p], cfgs[p])
+            jobs[p] = MrbfRound4Job(size(C0s[p], 2), size(Xcs[p], 2), pointer(C0s[p]), pointer(Xcs[p]), kid, cfgs[p].polynomial_degree, a, b,
+                                    cfgs[p].max_model_points, cfgs[p].θ_pivot_cholesky, pointer(accs[p]), 0, 0)
+        end
+        _locked(ctx) do hctx
+            ccall((:mrbf_round4_batch, libmrbf), Int32, (Ptr{Cvoid}, Int64, Int32, Ptr{MrbfRound4Job}, Ref{Float32}), hctx, ns, d, jobs, ms)
+        end
+    end
+    rc != 0 && _fallback_rc(13, rc) && return loop()           # the library refuses the batch: the single call per start
+    _check(ctx, rc)
+    return map(1:ns) do p
+        (jobs[p].rc, Int.(accs[p][1:jobs[p].n_accepted]) .+ 1)
+    end
 end
 "The model on (start sites, accepted sites) from the factor round 4 kept (RbfModel.jl:657-660): `values` in that order, k x n."
 function fit_from_round4(state::HipRound4State, values, n_vars::Int, fully_linear::Bool; rc_only::Bool = false)

@@ -364,6 +364,105 @@ def rbf_round4_device(cfg, start_sites, cand_sites, delta=1.0, ctx=None, keep_st
     return (accepted, state) if keep_state else accepted
 
 
+# Where the batched call pays: measured (tools/round4_batch_bench.py, DESIGN.md section 14, next to the decision-table row), not chosen
+# in advance.  One workgroup walks one start, so a batch call takes about 0.022 ms per candidate of its largest start whatever the
+# number of starts, against 0.9 - 1.2 ms per start for the loop of single calls: the batch and the loop tie at 8 starts of 300
+# candidates, and the batch wins from about 10 starts on there and from about 44 on at 1400 candidates.  HipRbf.jl carries the same two numbers.
+ROUND4_BATCH_MIN_STARTS = 8
+ROUND4_BATCH_CANDIDATES_PER_START = 32
+
+
+def round4_batch_pays(n_starts, max_candidates):
+    """the measured rule: at least 8 starts, and at least one start per 32 candidates of the largest start"""
+    return n_starts >= ROUND4_BATCH_MIN_STARTS and n_starts * ROUND4_BATCH_CANDIDATES_PER_START >= max_candidates
+
+
+def rbf_round4_batch_device(items, d, ctx=None):
+    """mrbf_round4_batch: `items` = one (cfg, start_sites, cand_sites, delta) per start -> (rc, [(rc_p, positions)] or None, ms): per
+    start the return code of its own selection (0, or what mrbf_round4 returned for a start that took it inside the call) and the
+    positions (into its cand_sites) of the accepted sites in acceptance order.  No factor state is kept: the fits of a batch go
+    through `update_models_many`.  Raises nothing for an rc that `mrbf_dispatch_after` reads as "take the single calls"."""
+    ctx = ctx or _lib.default_context()
+    n = len(items)
+    jobs = (_lib.Round4Job * max(n, 1))()
+    keep = []
+    for k, (cfg, C0, Xc, delta) in enumerate(items):
+        C0, Xc = _lib.host_f64(C0), _lib.host_f64(Xc).reshape(-1, d)
+        kid, a, b = rm._get_kernel_params(delta, cfg)
+        acc = np.zeros(max(Xc.shape[0], 1), dtype=np.int32)
+        keep.append((C0, Xc, acc))
+        J = jobs[k]
+        J.n0, J.mc, J.start_sites, J.cand_sites = C0.shape[0], Xc.shape[0], C0.ctypes.data, Xc.ctypes.data if Xc.shape[0] else None
+        J.kernel_id, J.poly_deg, J.a, J.b = kid, cfg.polynomial_degree, a, b
+        J.max_points, J.theta_pivot_cholesky, J.accepted_out = int(cfg.max_model_points), float(cfg.θ_pivot_cholesky), acc.ctypes.data
+    ms = ctypes.c_float(0.0)
+    rc = ctx.lib.mrbf_round4_batch(ctx.h, n, d, jobs, ctypes.byref(ms))
+    if rc != 0:
+        if not ctx.lib.mrbf_dispatch_after(_lib.ENTRY_ROUND4_BATCH, rc):
+            ctx.check(rc)
+        return rc, None, 0.0
+    return 0, [(int(jobs[k].rc), [int(v) for v in keep[k][2][: jobs[k].n_accepted]]) for k in range(n)], float(ms.value)
+
+
+def rbf_round4_many(sites_list, lb2s, ub2s, xs, deltas, indices_found_list, cfgs, ctx=None, stats=None, min_starts=None):
+    """`_rbf_round4` (RbfModel.jl:352-499) for a list of starts -- start p has its own database `sites_list[p]`, box, centre, radius,
+    indices found so far and (one per start, or one for all) config -- with the selections of all starts the decision table sends to
+    the device (mrbf_dispatch_round4, per start) in ONE call (mrbf_round4_batch) when mrbf_dispatch_round4_batch takes the group (one d
+    per call) and the batch pays (`round4_batch_pays`, measured; `min_starts` replaces the rule by a plain count: tests).  Every other start runs `_rbf_round4`: start sets that cannot carry
+    the tail, starts with `use_max_points` (their random box points need the caller's generator and site list, as for the single
+    call), a batch the library refuses (rc -2: every start of it), and a start whose own rc `mrbf_dispatch_after` reads as "take the
+    reference method".  Returns, per start, what `_rbf_round4` returns: database indices in acceptance order.  stats["path"] =
+    "batch" when a batched call ran, else "loop"; stats["batched"] = the starts it served; stats["fallback"] = starts of a batch
+    that went back to `_rbf_round4`."""
+    ns = len(sites_list)
+    per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * ns
+    cfgs, deltas = per(cfgs), per(deltas)
+    out = [None] * ns
+    lib = _lib.load() if ns else None
+    single = lambda p: _rbf_round4(sites_list[p], lb2s[p], ub2s[p], xs[p], deltas[p], indices_found_list[p], cfgs[p], ctx=ctx)
+    groups, prepared = {}, {}
+    for p in range(ns):
+        sites = np.asarray(sites_list[p], dtype=np.float64)
+        d, cfg, found = sites.shape[1], cfgs[p], list(indices_found_list[p])
+        max_points = (d + 1) * (d + 2) // 2 if cfg.max_model_points <= 0 else cfg.max_model_points
+        cand = results_in_box_indices(sites, lb2s[p], ub2s[p], found)
+        if cfg.use_max_points:
+            out[p] = single(p)
+        elif not (len(found) < max_points and cand):
+            out[p] = []
+        elif lib.mrbf_dispatch_round4(len(found), d, cfg.polynomial_degree, len(cand)) != _lib.DISPATCH_DEVICE:
+            out[p] = single(p)
+        else:
+            prepared[p] = (cfg, sites[found], sites[cand], deltas[p], cand)
+            groups.setdefault(d, []).append(p)
+    batched, fallback = [], []
+    for d, members in groups.items():
+        pays = len(members) >= min_starts if min_starts is not None else round4_batch_pays(len(members), max(len(prepared[p][4]) for p in members))
+        if not pays or lib.mrbf_dispatch_round4_batch(len(members), d) != _lib.DISPATCH_DEVICE:
+            for p in members:
+                out[p] = single(p)
+            continue
+        rc, res, _ = rbf_round4_batch_device([prepared[p][:4] for p in members], d, ctx=ctx)
+        for pos, p in enumerate(members):
+            if rc != 0:                                   # refused: the single call per start
+                out[p] = single(p)
+                continue
+            rc_p, accepted = res[pos]
+            if rc_p == 0:
+                out[p] = [prepared[p][4][a] for a in accepted]
+                batched.append(p)
+            elif lib.mrbf_dispatch_after(_lib.ENTRY_ROUND4_BATCH, rc_p):
+                out[p] = single(p)
+                fallback.append(p)
+            else:
+                (ctx or _lib.default_context()).check(rc_p)
+    if stats is not None:
+        stats["path"] = "batch" if batched else "loop"
+        stats["batched"] = sorted(batched)
+        stats["fallback"] = sorted(fallback)
+    return out
+
+
 def fit_from_round4(state, training_values, fully_linear=False, rc_only=False):
     """update_model (RbfModel.jl:743-767) for the training set (start sites + sites accepted by round 4) from the factor round 4
     left on the device -- the reference's TODO at RbfModel.jl:657-660.  `training_values`: (n0 + n_accepted) x k in that order.
