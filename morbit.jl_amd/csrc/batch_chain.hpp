@@ -1,5 +1,5 @@
-// What the many-start chains (sd_batch.hip, normal_batch.hip) share: the fetch of an input into the packed upload, and the evaluations of
-// a batch -- model slot j of start p at one of the chain's sites -- grouped by what one eval_fused_batch launch requires, with their
+// What the many-start chains (sd_batch.hip, normal_batch.hip) share: the arena's bookkeeping, the host blocks of the packed upload and
+// of the read-back, and the evaluations of a batch -- model slot j of start p at one of the chain's sites -- grouped by what one eval_fused_batch launch requires, with their
 // descriptors and their scratch in the chain's arena.  Every member takes the centre-range split of the single call it stands for
 // (eval_nsplit on its own query count) and partial buffers of its own, so the order of every sum is that call's.
 #pragma once
@@ -8,12 +8,27 @@
 namespace mrbf {
 namespace chain {
 
-inline int batch_fetch(mrbf_ctx *ctx, const double *src, size_t cnt, double *dst) {
-    if (!cnt) return 0;
-    if (is_device_ptr(src)) MRBF_HIP(ctx, hipMemcpy(dst, src, cnt * sizeof(double), hipMemcpyDeviceToHost));
-    else std::memcpy(dst, src, cnt * sizeof(double));
-    return 0;
-}
+// the chain's one device arena, counted in doubles: every piece a multiple of 16
+struct Arena {
+    size_t total = 0;
+    size_t take(size_t cnt) {
+        const size_t at = total;
+        total += (cnt + 15) & ~(size_t)15;
+        return at;
+    }
+};
+// a host block of `cnt` doubles for the upload or the read-back: in the armed pinned block where it fits in 4 MiB, else pageable
+struct Staging {
+    std::vector<double> own;
+    double *p;
+    Staging(mrbf_ctx *ctx, size_t cnt) {
+        p = reinterpret_cast<double *>(cnt * sizeof(double) <= ((size_t)4 << 20) ? pin_take(ctx, cnt * sizeof(double)) : nullptr);
+        if (!p) {
+            own.resize(cnt);
+            p = own.data();
+        }
+    }
+};
 
 constexpr int64_t MAX_GROUP_LAUNCH = 65535;  // blockIdx.z of the evaluation kernels
 
@@ -60,9 +75,9 @@ struct Plan {
         for (Group &G : groups) G.first = n_desc, n_desc += G.members.size();
     }
     size_t desc_doubles() const { return (n_desc * sizeof(EvalDesc) + sizeof(double) - 1) / sizeof(double); }
-    // the scratch of every grouped member, in member order: take(count) returns the offset of `count` doubles of the arena
-    template <class Take>
-    void carve(Take &&take) {
+    // the scratch of every grouped member, in member order
+    void carve(Arena &ar) {
+        auto take = [&](size_t cnt) { return ar.take(cnt); };
         for (Member &S : mem) {
             if (S.group < 0) continue;
             S.mpad = round_up(S.mq, 64);

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/mrbf.h"
+#include "descent_problem.hpp"  // the reader of a container's roles table and the layout the descent entry points build on it
 #include "model_pool.hpp"  // Buf, ModelSlab and the pool of released model blocks
 
 namespace mrbf {
@@ -201,6 +202,18 @@ int stage_in(mrbf_ctx *ctx, Slot s, const double *user, size_t count, const doub
 // device buffer to produce an output into (user's own when device memory, else staging)
 int stage_out(mrbf_ctx *ctx, Slot s, double *user, size_t count, double **dev);
 int finish_out(mrbf_ctx *ctx, double *user, const double *dev, size_t count);
+// the synchronous forms, for the entry points that pack their inputs on the host: a host copy of an input that may be host or device
+// memory; the device view of an input (the pointer itself when device memory, else a copy in `arena`, which advances; NULL or nothing
+// to copy: NULL); an output, host or device memory, from its host copy
+int input_fetch(mrbf_ctx *ctx, const double *src, size_t count, double *dst);
+int input_view(mrbf_ctx *ctx, const double *user, size_t count, double *&arena, const double **dev);
+int output_put(mrbf_ctx *ctx, double *dst, const double *src, size_t count);
+// the linear rows of a container, packed for one upload: A = [A_eq; A_ineq] ((n_lin_eq + n_lin_ineq) x d), b = [b_eq; b_ineq]
+int fetch_linear_rows(mrbf_ctx *ctx, const mrbf_ps_problem *prob, int d, double *A, double *b);
+// what descent::read (descent_problem.hpp) is told of a container: the handles' d, k and n in `slots` (start-major n_starts x n_models;
+// models may be NULL only where n_models is 0), the table and the counts of `prob`
+descent::Shape descent_shape(const mrbf_ps_problem *prob, const mrbf_model *const *models, int64_t n_starts,
+                             std::vector<descent::SlotShape> &slots);
 void pin_reset(mrbf_ctx *ctx);   // top of an API entry (through PinGuard)
 void pin_flush(mrbf_ctx *ctx);   // behind the stream synchronisation that follows finish_out (through PinGuard::flush)
 void pin_discard(mrbf_ctx *ctx); // an entry that leaves early: queued outputs dropped, block disarmed

@@ -144,6 +144,59 @@ int finish_out(mrbf_ctx *ctx, double *user, const double *dev, size_t count) {
     return 0;
 }
 
+int input_fetch(mrbf_ctx *ctx, const double *src, size_t count, double *dst) {
+    if (!count) return 0;
+    if (is_device_ptr(src)) MRBF_HIP(ctx, hipMemcpy(dst, src, count * sizeof(double), hipMemcpyDeviceToHost));
+    else std::memcpy(dst, src, count * sizeof(double));
+    return 0;
+}
+
+int input_view(mrbf_ctx *ctx, const double *user, size_t count, double *&arena, const double **dev) {
+    if (!user || count == 0) {
+        *dev = nullptr;
+        return 0;
+    }
+    if (is_device_ptr(user)) {
+        *dev = user;
+        return 0;
+    }
+    MRBF_HIP(ctx, hipMemcpyAsync(arena, user, count * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    *dev = arena;
+    arena += count;
+    return 0;
+}
+
+int output_put(mrbf_ctx *ctx, double *dst, const double *src, size_t count) {
+    if (!count) return 0;
+    if (is_device_ptr(dst)) MRBF_HIP(ctx, hipMemcpy(dst, src, count * sizeof(double), hipMemcpyHostToDevice));
+    else std::memcpy(dst, src, count * sizeof(double));
+    return 0;
+}
+
+int fetch_linear_rows(mrbf_ctx *ctx, const mrbf_ps_problem *prob, int d, double *A, double *b) {
+    const size_t neq = (size_t)prob->n_lin_eq, nin = (size_t)prob->n_lin_ineq;
+    MRBF_TRY(input_fetch(ctx, prob->A_eq, neq * d, A));
+    MRBF_TRY(input_fetch(ctx, prob->A_ineq, nin * d, A + neq * d));
+    MRBF_TRY(input_fetch(ctx, prob->b_eq, neq, b));
+    MRBF_TRY(input_fetch(ctx, prob->b_ineq, nin, b + neq));
+    return 0;
+}
+
+descent::Shape descent_shape(const mrbf_ps_problem *prob, const mrbf_model *const *models, int64_t n_starts,
+                             std::vector<descent::SlotShape> &slots) {
+    descent::Shape S;
+    S.n_slots = prob->n_models, S.n_starts = n_starts;
+    slots.clear();
+    for (int64_t i = 0; i < n_starts * (prob->n_models > 0 ? prob->n_models : 0); ++i) {
+        const mrbf_model *M = models[i];
+        slots.push_back(M ? descent::SlotShape{true, M->d, M->k, M->n} : descent::SlotShape{false, 0, 0, 0});
+    }
+    S.slots = slots.data(), S.roles = prob->roles;
+    S.n_objectives = prob->n_objectives, S.n_lin_eq = prob->n_lin_eq, S.n_lin_ineq = prob->n_lin_ineq;
+    S.lin_eq_given = prob->A_eq && prob->b_eq, S.lin_ineq_given = prob->A_ineq && prob->b_ineq;
+    return S;
+}
+
 void pin_reset(mrbf_ctx *ctx) {
     ctx->pin_off = 0;
     ctx->pin_out.clear();

@@ -11,15 +11,9 @@ constexpr int THREADS = 256;
 constexpr int MAXM = 64;
 constexpr int MAXD = 4096;
 
-// ---- the right-hand sides of the normal step: one workgroup per LP row and start, the Jacobians / values of the evaluation kernels as they lie
-struct RowSrc {
-    int kind;      // 1 linear row, 2 modelled constraint row
-    int dst;       // row of A_eq or A_ineq
-    int eq;        // 1: equality block
-    int stride;    // rows of the model (k_j): the Jacobian is k_j x d column-major
-    int64_t jac;   // offset of the row's first Jacobian entry at x
-    int64_t val;   // offset of the row's value at x / index of the linear row
-};
+// ---- the right-hand sides of the normal step: one workgroup per LP row and start (RowSrc and its filler: descent_problem.hpp); only
+// linear (kind 1) and modelled constraint rows (kind 2), Jacobian and value both at x
+using descent::RowSrc;
 struct AsmArgs {
     int n, rows, meq, min;
     int64_t sJ, sV, sx;  // per-start strides of J, of V, of x; A_eq, b_eq, A_ineq, b_ineq lie in the consecutive per-LP blocks of launch()

@@ -21,7 +21,6 @@
 #include "normal.hpp"
 
 using namespace mrbf;
-using chain::batch_fetch;
 
 namespace {
 
@@ -87,101 +86,61 @@ extern "C" int32_t mrbf_normal_step_batch(mrbf_ctx *ctx, int64_t n_starts, const
     if (!records) return fail(ctx, -16, "records is NULL");
     const int nm = shape->n_models;
     if (nm < 0 || (nm > 0 && (!models || !shape->roles))) return fail(ctx, -4, "mrbf_normal_step_batch: models need handles and a roles table");
-    if (shape->n_lin_eq < 0 || shape->n_lin_ineq < 0) return fail(ctx, -3, "mrbf_normal_step_batch: negative constraint count");
-    if ((shape->n_lin_eq && (!shape->A_eq || !shape->b_eq)) || (shape->n_lin_ineq && (!shape->A_ineq || !shape->b_ineq)))
-        return fail(ctx, -3, "mrbf_normal_step_batch: linear constraint matrices are NULL");
     if (variable_radius && !(kappa_delta > 0.0)) return fail(ctx, -10, "mrbf_normal_step_batch: kappa_delta = %g", kappa_delta);
     if (n_starts < 1) return fail(ctx, -2, "mrbf_normal_step_batch: %lld starts (ask mrbf_dispatch_normal_batch first)", (long long)n_starts);
     const int64_t N = n_starts;
-    // ---- the shape: start 0's models give every slot's output count; every other start must agree
-    std::vector<int> kj(nm);
-    for (int j = 0; j < nm; ++j) {
-        if (!models[j]) return fail(ctx, -4, "mrbf_normal_step_batch: model %d of start 0 is NULL", j);
-        kj[j] = models[j]->k;
-    }
-    // ---- the modelled constraint rows from the roles table (as mrbf_normal_step reads it)
-    std::vector<ns::RowSrc> meq_rows, min_rows;
-    std::vector<int64_t> joff(nm, 0), voff(nm, 0);
-    std::vector<char> used(nm, 0);
-    int64_t jtot = 0, vtot = 0;
-    for (int j = 0, e = 0; j < nm; ++j)
-        for (int c = 0; c < kj[j]; ++c, ++e) {
-            const int role = shape->roles[e];
-            if (role == MRBF_ROLE_EQ || role == MRBF_ROLE_INEQ) {
-                if (!used[j]) {
-                    used[j] = 1, joff[j] = jtot, voff[j] = vtot;
-                    jtot += (int64_t)kj[j] * d, vtot += kj[j];
-                }
-                ns::RowSrc s{2, 0, role == MRBF_ROLE_EQ, kj[j], joff[j] + c, voff[j] + c};
-                (role == MRBF_ROLE_EQ ? meq_rows : min_rows).push_back(s);
-            } else if (role < 0 && role != MRBF_ROLE_NONE) {
-                return fail(ctx, -3, "mrbf_normal_step_batch: roles[%d] = %d is not a role", e, role);
-            }
-        }
-    const int n_nl = (int)(meq_rows.size() + min_rows.size()), n_lin = shape->n_lin_eq + shape->n_lin_ineq;
-    if (mrbf_dispatch_normal_batch(N, d, nm, n_nl, n_lin, 0) != MRBF_DISPATCH_DEVICE)
+    // ---- the modelled constraint rows from the roles table (as mrbf_normal_step reads it); the starts' slots agree
+    std::vector<descent::SlotShape> slots;
+    descent::Shape sh = descent_shape(shape, models, N, slots);
+    sh.d = d, sh.batch = true;
+    descent::Layout lay;
+    if (descent::Defect D = descent::read(sh, {false, descent::Centres::CONSTRAINED_SLOTS}, lay))
+        return fail(ctx, D.cls == descent::Defect::MODELS ? -4 : -3, "mrbf_normal_step_batch: %s", D.msg.c_str());
+    const int n_lin = shape->n_lin_eq + shape->n_lin_ineq;
+    if (mrbf_dispatch_normal_batch(N, d, nm, lay.n_nl, n_lin, 0) != MRBF_DISPATCH_DEVICE)
         return fail(ctx, -2, "mrbf_normal_step_batch: %lld starts / d = %d / %d rows outside the device path (ask mrbf_dispatch_normal_batch first)",
-                    (long long)N, d, n_nl + n_lin);
-    for (int64_t p = 0; p < N; ++p)
-        for (int j = 0; j < nm; ++j) {
-            const mrbf_model *M = models[p * nm + j];
-            if (!M) return fail(ctx, -4, "mrbf_normal_step_batch: model %d of start %lld is NULL", j, (long long)p);
-            if (M->d != d || M->k != kj[j])
-                return fail(ctx, -4, "mrbf_normal_step_batch: model %d of start %lld is %d variables x %d outputs, expected %d x %d", j, (long long)p,
-                            M->d, M->k, d, kj[j]);
-            if (used[j] && M->n == 0) return fail(ctx, -4, "mrbf_normal_step_batch: model %d of start %lld has no centres", j, (long long)p);
-        }
-    const int meq = shape->n_lin_eq + (int)meq_rows.size(), min = shape->n_lin_ineq + (int)min_rows.size(), m = meq + min;
+                    (long long)N, d, lay.n_nl + n_lin);
+    const descent::Offsets at = lay.offsets(1, descent::Slots::CONSTRAINED);
+    const int64_t jtot = at.jtot, vtot = at.vtot;
+    const int meq = lay.meq, min = lay.min, m = meq + min;
     (void)hipSetDevice(ctx->device);
     PinGuard pin(ctx);
     // ---- the evaluations of the single calls (one query row at x per model slot with constraint rows), grouped (batch_chain.hpp)
     chain::Plan ev;
     for (int64_t p = 0; p < N; ++p)
         for (int j = 0; j < nm; ++j)
-            if (used[j]) ev.add(ctx, 0, p, j, models[p * nm + j], 1, true);
+            if (lay.has_con[j]) ev.add(ctx, 0, p, j, models[p * nm + j], 1, true);
     ev.close();
     // ---- the arena (doubles; every piece a multiple of 16): upload | work | evaluation scratch | output block
-    size_t total = 0;
-    auto take = [&](size_t cnt) {
-        const size_t at = total;
-        total += (cnt + 15) & ~(size_t)15;
-        return at;
-    };
+    chain::Arena ar;
     const size_t nlin = (size_t)n_lin, SN = (size_t)N;
-    const size_t oX = take(SN * d), oDelta = take(SN), oLb = take(d), oUb = take(d), oA = take(nlin * d), oB = take(nlin);
-    const size_t oDesc = take(ev.desc_doubles());
-    const size_t up_cnt = total;
-    const size_t oJ = take(SN * jtot), oV = take(SN * vtot);
-    const size_t oAeq = take(SN * meq * d), oBeq = take(SN * meq), oAin = take(SN * min * d), oBin = take(SN * min);
-    const size_t oAlpha = take(SN), oInts = take((3 * SN + 1) / 2);
-    ev.carve(take);
+    const size_t oX = ar.take(SN * d), oDelta = ar.take(SN), oLb = ar.take(d), oUb = ar.take(d), oA = ar.take(nlin * d), oB = ar.take(nlin);
+    const size_t oDesc = ar.take(ev.desc_doubles());
+    const size_t up_cnt = ar.total;
+    const size_t oJ = ar.take(SN * jtot), oV = ar.take(SN * vtot);
+    const size_t oAeq = ar.take(SN * meq * d), oBeq = ar.take(SN * meq), oAin = ar.take(SN * min * d), oBin = ar.take(SN * min);
+    const size_t oAlpha = ar.take(SN), oInts = ar.take((3 * SN + 1) / 2);
+    ev.carve(ar);
     for (chain::Member &mb : ev.mem) {
         const size_t p = (size_t)mb.p;
-        mb.X = oX + p * d, mb.vals = oV + p * vtot + voff[mb.j], mb.jacs = oJ + p * jtot + joff[mb.j];
+        mb.X = oX + p * d, mb.vals = oV + p * vtot + at.val[mb.j], mb.jacs = oJ + p * jtot + at.jac[mb.j];
     }
     // the output block: n | x + n | duals | records
-    const size_t out0 = total;
-    const size_t oN = take(SN * d), oXn = take(SN * d), oDual = take(SN * m);
-    const size_t oRec = take(SN * sizeof(mrbf_normal_batch_record) / sizeof(double));
-    const size_t out_cnt = total - out0;
+    const size_t out0 = ar.total;
+    const size_t oN = ar.take(SN * d), oXn = ar.take(SN * d), oDual = ar.take(SN * m);
+    const size_t oRec = ar.take(SN * sizeof(mrbf_normal_batch_record) / sizeof(double));
+    const size_t out_cnt = ar.total - out0;
     double *base;
-    MRBF_TRY(get_buf(ctx, S_NS_BATCH, total, &base));
+    MRBF_TRY(get_buf(ctx, S_NS_BATCH, ar.total, &base));
     // ---- the upload, staged in the pinned block where it fits
-    std::vector<double> hup_v;
-    double *hup = reinterpret_cast<double *>(up_cnt * sizeof(double) <= ((size_t)4 << 20) ? pin_take(ctx, up_cnt * sizeof(double)) : nullptr);
-    if (!hup) {
-        hup_v.resize(up_cnt);
-        hup = hup_v.data();
-    }
+    chain::Staging up(ctx, up_cnt);
+    double *hup = up.p;
     std::memset(hup, 0, up_cnt * sizeof(double));
-    MRBF_TRY(batch_fetch(ctx, x, SN * d, hup + oX));
-    MRBF_TRY(batch_fetch(ctx, delta, SN, hup + oDelta));
-    MRBF_TRY(batch_fetch(ctx, lb, d, hup + oLb));
-    MRBF_TRY(batch_fetch(ctx, ub, d, hup + oUb));
-    MRBF_TRY(batch_fetch(ctx, shape->A_eq, (size_t)shape->n_lin_eq * d, hup + oA));
-    MRBF_TRY(batch_fetch(ctx, shape->A_ineq, (size_t)shape->n_lin_ineq * d, hup + oA + (size_t)shape->n_lin_eq * d));
-    MRBF_TRY(batch_fetch(ctx, shape->b_eq, shape->n_lin_eq, hup + oB));
-    MRBF_TRY(batch_fetch(ctx, shape->b_ineq, shape->n_lin_ineq, hup + oB + shape->n_lin_eq));
+    MRBF_TRY(input_fetch(ctx, x, SN * d, hup + oX));
+    MRBF_TRY(input_fetch(ctx, delta, SN, hup + oDelta));
+    MRBF_TRY(input_fetch(ctx, lb, d, hup + oLb));
+    MRBF_TRY(input_fetch(ctx, ub, d, hup + oUb));
+    MRBF_TRY(fetch_linear_rows(ctx, shape, d, hup + oA, hup + oB));
     EvalDesc *hdesc = reinterpret_cast<EvalDesc *>(hup + oDesc);
     const EvalDesc *ddesc = reinterpret_cast<const EvalDesc *>(base + oDesc);
     ev.fill(base, hdesc);
@@ -196,13 +155,7 @@ extern "C" int32_t mrbf_normal_step_batch(mrbf_ctx *ctx, int64_t n_starts, const
     aa.sJ = jtot, aa.sV = vtot, aa.sx = d;
     aa.J = base + oJ, aa.V = base + oV, aa.x = base + oX, aa.Alin = base + oA, aa.blin = base + oB;
     aa.Aeq = base + oAeq, aa.beq = base + oBeq, aa.Ain = base + oAin, aa.bin = base + oBin;
-    {
-        int r = 0;
-        for (int i = 0; i < shape->n_lin_eq; ++i) aa.src[r++] = ns::RowSrc{1, i, 1, 1, 0, i};
-        for (size_t i = 0; i < meq_rows.size(); ++i) aa.src[r] = meq_rows[i], aa.src[r++].dst = shape->n_lin_eq + (int)i;
-        for (int i = 0; i < shape->n_lin_ineq; ++i) aa.src[r++] = ns::RowSrc{1, i, 0, 1, 0, shape->n_lin_eq + i};
-        for (size_t i = 0; i < min_rows.size(); ++i) aa.src[r] = min_rows[i], aa.src[r++].dst = shape->n_lin_ineq + (int)i;
-    }
+    descent::fill_sources(lay, at, false, aa.src);
     MRBF_TRY(ns::launch_assemble(ctx, aa, N));
     int *dInts = reinterpret_cast<int *>(base + oInts);
     MRBF_TRY(ns::launch(ctx, N, d, meq, min, base + oX, base + oLb, base + oUb, 0, meq ? base + oAeq : nullptr, meq ? base + oBeq : nullptr,
@@ -219,12 +172,8 @@ extern "C" int32_t mrbf_normal_step_batch(mrbf_ctx *ctx, int64_t n_starts, const
     hipLaunchKernelGGL(normal_finish_kernel, dim3((unsigned)N), dim3(ns::THREADS), 0, st, fa);
     MRBF_HIP(ctx, hipGetLastError());
     // ---- one read-back
-    std::vector<double> hout_v;
-    double *hout = reinterpret_cast<double *>(out_cnt * sizeof(double) <= ((size_t)4 << 20) ? pin_take(ctx, out_cnt * sizeof(double)) : nullptr);
-    if (!hout) {
-        hout_v.resize(out_cnt);
-        hout = hout_v.data();
-    }
+    chain::Staging down(ctx, out_cnt);
+    double *hout = down.p;
     MRBF_HIP(ctx, hipMemcpyAsync(hout, base + out0, out_cnt * sizeof(double), hipMemcpyDeviceToHost, st));
     const bool dev_n = is_device_ptr(n_out), dev_x = x_n_out && is_device_ptr(x_n_out), dev_y = dual_out && is_device_ptr(dual_out);
     if (dev_n) MRBF_HIP(ctx, hipMemcpyAsync(n_out, base + oN, SN * d * sizeof(double), hipMemcpyDeviceToDevice, st));

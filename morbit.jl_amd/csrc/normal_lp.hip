@@ -571,34 +571,6 @@ int launch(mrbf_ctx *ctx, int64_t n_lp, int n, int meq, int min, const double *x
 
 using namespace mrbf;
 
-namespace {
-// device view of an input: the pointer itself when device memory, else a copy in `arena` (advanced)
-int ns_view(mrbf_ctx *ctx, const double *user, size_t count, double *&arena, const double **dev) {
-    if (!user || count == 0) {
-        *dev = nullptr;
-        return 0;
-    }
-    if (is_device_ptr(user)) {
-        *dev = user;
-        return 0;
-    }
-    MRBF_HIP(ctx, hipMemcpyAsync(arena, user, count * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    *dev = arena;
-    arena += count;
-    return 0;
-}
-int ns_fetch(mrbf_ctx *ctx, const double *src, size_t cnt, double *dst) {
-    if (cnt) MRBF_HIP(ctx, hipMemcpy(dst, src, cnt * sizeof(double), hipMemcpyDefault));
-    return 0;
-}
-int ns_put(mrbf_ctx *ctx, double *dst, const double *src, size_t cnt) {
-    if (!cnt) return 0;
-    if (is_device_ptr(dst)) MRBF_HIP(ctx, hipMemcpy(dst, src, cnt * sizeof(double), hipMemcpyHostToDevice));
-    else std::memcpy(dst, src, cnt * sizeof(double));
-    return 0;
-}
-}  // namespace
-
 extern "C" int32_t mrbf_normal_direction(mrbf_ctx *ctx, int64_t n_lp, int32_t d, int32_t m_eq, int32_t m_ineq, const double *x,
                                          const double *lb, const double *ub, const double *A_eq, const double *b_eq, const double *A_ineq,
                                          const double *b_ineq, double *n_out, double *alpha_out, double *dual_out, int32_t *status_out,
@@ -629,13 +601,13 @@ extern "C" int32_t mrbf_normal_direction(mrbf_ctx *ctx, int64_t n_lp, int32_t d,
     double *arena;
     MRBF_TRY(get_buf(ctx, S_NS_IN, in_cnt, &arena));
     const double *dx, *dlb, *dub, *dAeq, *dbeq, *dAin, *dbin;
-    MRBF_TRY(ns_view(ctx, x, N * d, arena, &dx));
-    MRBF_TRY(ns_view(ctx, lb, N * d, arena, &dlb));
-    MRBF_TRY(ns_view(ctx, ub, N * d, arena, &dub));
-    MRBF_TRY(ns_view(ctx, A_eq, N * m_eq * d, arena, &dAeq));
-    MRBF_TRY(ns_view(ctx, b_eq, N * m_eq, arena, &dbeq));
-    MRBF_TRY(ns_view(ctx, A_ineq, N * m_ineq * d, arena, &dAin));
-    MRBF_TRY(ns_view(ctx, b_ineq, N * m_ineq, arena, &dbin));
+    MRBF_TRY(input_view(ctx, x, N * d, arena, &dx));
+    MRBF_TRY(input_view(ctx, lb, N * d, arena, &dlb));
+    MRBF_TRY(input_view(ctx, ub, N * d, arena, &dub));
+    MRBF_TRY(input_view(ctx, A_eq, N * m_eq * d, arena, &dAeq));
+    MRBF_TRY(input_view(ctx, b_eq, N * m_eq, arena, &dbeq));
+    MRBF_TRY(input_view(ctx, A_ineq, N * m_ineq * d, arena, &dAin));
+    MRBF_TRY(input_view(ctx, b_ineq, N * m_ineq, arena, &dbin));
     const bool dev_n = is_device_ptr(n_out), dev_a = is_device_ptr(alpha_out), dev_y = dual_out && is_device_ptr(dual_out);
     const bool dev_s = is_device_ptr(status_out), dev_i = iters_out && is_device_ptr(iters_out);
     const size_t out_dbl = N * d + N + N * m, out_int = 3 * N;
@@ -668,50 +640,29 @@ extern "C" int32_t mrbf_normal_step(mrbf_ctx *ctx, const mrbf_ps_problem *prob, 
     std::memset(info, 0, sizeof(*info));
     if (prob->n_models < 0 || (prob->n_models > 0 && (!prob->models || !prob->roles)))
         return fail(ctx, -2, "mrbf_normal_step: models need a roles table");
-    if (prob->n_lin_eq < 0 || prob->n_lin_ineq < 0) return fail(ctx, -2, "mrbf_normal_step: negative constraint count");
-    if ((prob->n_lin_eq && (!prob->A_eq || !prob->b_eq)) || (prob->n_lin_ineq && (!prob->A_ineq || !prob->b_ineq)))
-        return fail(ctx, -2, "mrbf_normal_step: linear constraint matrices are NULL");
     if (variable_radius && !(kappa_delta > 0.0)) return fail(ctx, -2, "mrbf_normal_step: kappa_delta = %g", kappa_delta);
-    // ---- the modelled constraint rows from the roles table
-    std::vector<ns::RowSrc> meq_rows, min_rows;
-    std::vector<int64_t> joff(prob->n_models), voff(prob->n_models);
-    std::vector<char> used(prob->n_models, 0);
-    int64_t jtot = 0, vtot = 0;
-    for (int j = 0, e = 0; j < prob->n_models; ++j) {
-        const mrbf_model *M = prob->models[j];
-        if (!M) return fail(ctx, -2, "mrbf_normal_step: model %d is NULL", j);
-        if (M->d != d) return fail(ctx, -2, "mrbf_normal_step: model %d has %d variables, model 0 has %d", j, M->d, d);
-        for (int c = 0; c < M->k; ++c, ++e) {
-            const int role = prob->roles[e];
-            if (role == MRBF_ROLE_EQ || role == MRBF_ROLE_INEQ) {
-                if (!used[j]) {
-                    used[j] = 1, joff[j] = jtot, voff[j] = vtot;
-                    jtot += (int64_t)M->k * d, vtot += M->k;
-                }
-                ns::RowSrc s{2, 0, role == MRBF_ROLE_EQ, M->k, joff[j] + c, voff[j] + c};
-                (role == MRBF_ROLE_EQ ? meq_rows : min_rows).push_back(s);
-            } else if (role < 0 && role != MRBF_ROLE_NONE) {
-                return fail(ctx, -2, "mrbf_normal_step: roles[%d] = %d is not a role", e, role);
-            }
-        }
-    }
-    const int n_nl = (int)(meq_rows.size() + min_rows.size()), n_lin = prob->n_lin_eq + prob->n_lin_ineq;
-    if (mrbf_dispatch_normal(d, prob->n_models, n_nl, n_lin, 0) != MRBF_DISPATCH_DEVICE)
-        return fail(ctx, -2, "mrbf_normal_step: d = %d / %d rows outside the device path (ask mrbf_dispatch_normal first)", d, n_nl + n_lin);
-    const int meq = prob->n_lin_eq + (int)meq_rows.size(), min = prob->n_lin_ineq + (int)min_rows.size(), m = meq + min;
+    // ---- the modelled constraint rows from the roles table (the objective rows are not this call's); their evaluations at x
+    std::vector<descent::SlotShape> slots;
+    descent::Shape shape = descent_shape(prob, prob->models, 1, slots);
+    shape.d = d;
+    descent::Layout lay;
+    if (descent::Defect D = descent::read(shape, {false, descent::Centres::UNCHECKED}, lay)) return fail(ctx, -2, "mrbf_normal_step: %s", D.msg.c_str());
+    const int n_lin = prob->n_lin_eq + prob->n_lin_ineq;
+    if (mrbf_dispatch_normal(d, prob->n_models, lay.n_nl, n_lin, 0) != MRBF_DISPATCH_DEVICE)
+        return fail(ctx, -2, "mrbf_normal_step: d = %d / %d rows outside the device path (ask mrbf_dispatch_normal first)", d, lay.n_nl + n_lin);
+    const descent::Offsets at = lay.offsets(1, descent::Slots::CONSTRAINED);
+    const int64_t jtot = at.jtot, vtot = at.vtot;
+    const int meq = lay.meq, min = lay.min, m = meq + min;
     (void)hipSetDevice(ctx->device);
     PinGuard pin(ctx);
     // ---- host inputs, packed: x, lb, ub, linear rows (eq, then ineq), their b
     const size_t nlin = (size_t)n_lin;
     std::vector<double> h((size_t)3 * d + nlin * (d + 1));
     double *hx = h.data(), *hlb = hx + d, *hub = hlb + d, *hA = hub + d, *hb = hA + nlin * d;
-    MRBF_TRY(ns_fetch(ctx, x, d, hx));
-    MRBF_TRY(ns_fetch(ctx, lb, d, hlb));
-    MRBF_TRY(ns_fetch(ctx, ub, d, hub));
-    MRBF_TRY(ns_fetch(ctx, prob->A_eq, (size_t)prob->n_lin_eq * d, hA));
-    MRBF_TRY(ns_fetch(ctx, prob->A_ineq, (size_t)prob->n_lin_ineq * d, hA + (size_t)prob->n_lin_eq * d));
-    MRBF_TRY(ns_fetch(ctx, prob->b_eq, prob->n_lin_eq, hb));
-    MRBF_TRY(ns_fetch(ctx, prob->b_ineq, prob->n_lin_ineq, hb + prob->n_lin_eq));
+    MRBF_TRY(input_fetch(ctx, x, d, hx));
+    MRBF_TRY(input_fetch(ctx, lb, d, hlb));
+    MRBF_TRY(input_fetch(ctx, ub, d, hub));
+    MRBF_TRY(fetch_linear_rows(ctx, prob, d, hA, hb));
     hipEvent_t e0 = ctx->ev[0], e1 = ctx->ev[1];
     MRBF_HIP(ctx, hipEventRecord(e0, ctx->stream));
     // device arena: inputs | Jacobians | values | LP data (A_eq, b_eq, A_ineq, b_ineq) | outputs (n, alpha, dual, 3 int words)
@@ -724,18 +675,14 @@ extern "C" int32_t mrbf_normal_step(mrbf_ctx *ctx, const mrbf_ps_problem *prob, 
     const double *dx = base, *dlb = base + d, *dub = base + 2 * d, *dA = base + 3 * d, *db = dA + nlin * d;
     // ---- values and Jacobians at x: one site per model that carries constraint rows
     for (int j = 0; j < prob->n_models; ++j)
-        if (used[j]) MRBF_TRY(eval_model(ctx, prob->models[j], 1, dx, dV + voff[j], dJ + joff[j], nullptr));
+        if (lay.has_con[j]) MRBF_TRY(eval_model(ctx, prob->models[j], 1, dx, dV + at.val[j], dJ + at.jac[j], nullptr));
     // ---- A_eq / b_eq (linear, then modelled), A_ineq / b_ineq (likewise) on the device
     ns::AsmArgs aa;
     aa.n = d, aa.rows = m, aa.meq = meq, aa.min = min;
     aa.sJ = jtot, aa.sV = vtot, aa.sx = d;
     aa.J = dJ, aa.V = dV, aa.x = dx, aa.Alin = dA, aa.blin = db;
     aa.Aeq = dAeq, aa.beq = dbeq, aa.Ain = dAin, aa.bin = dbin;
-    int r = 0;
-    for (int i = 0; i < prob->n_lin_eq; ++i) aa.src[r++] = ns::RowSrc{1, i, 1, 1, 0, i};
-    for (size_t i = 0; i < meq_rows.size(); ++i) aa.src[r] = meq_rows[i], aa.src[r++].dst = prob->n_lin_eq + (int)i;
-    for (int i = 0; i < prob->n_lin_ineq; ++i) aa.src[r++] = ns::RowSrc{1, i, 0, 1, 0, prob->n_lin_eq + i};
-    for (size_t i = 0; i < min_rows.size(); ++i) aa.src[r] = min_rows[i], aa.src[r++].dst = prob->n_lin_ineq + (int)i;
+    descent::fill_sources(lay, at, false, aa.src);
     MRBF_TRY(ns::launch_assemble(ctx, aa, 1));
     int *oi = reinterpret_cast<int *>(dout + d + 1 + m);
     MRBF_TRY(ns::launch(ctx, 1, d, meq, min, dx, dlb, dub, 0, meq ? dAeq : nullptr, meq ? dbeq : nullptr, min ? dAin : nullptr,
@@ -763,8 +710,8 @@ extern "C" int32_t mrbf_normal_step(mrbf_ctx *ctx, const mrbf_ps_problem *prob, 
         info->delta = -__builtin_huge_val();
         for (int j = 0; j < d; ++j) hout[j] = NAN;
     }
-    MRBF_TRY(ns_put(ctx, n_out, hout.data(), d));
-    if (dual_out) MRBF_TRY(ns_put(ctx, dual_out, hout.data() + d + 1, m));
+    MRBF_TRY(output_put(ctx, n_out, hout.data(), d));
+    if (dual_out) MRBF_TRY(output_put(ctx, dual_out, hout.data() + d + 1, m));
     if (info->status == MRBF_NS_GAVE_UP) return fail(ctx, -2, "mrbf_normal_step: the normal-step LP gave up (take the reference method)");
     return MRBF_OK;
 }

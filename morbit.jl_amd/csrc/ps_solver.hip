@@ -1599,8 +1599,7 @@ static int ps_descend(mrbf_ctx *ctx, const ps::Problem &P, const std::vector<dou
 
 static int fetch_host(mrbf_ctx *ctx, const double *src, size_t cnt, std::vector<double> &dst) {
     dst.resize(cnt);
-    if (cnt) MRBF_HIP(ctx, hipMemcpy(dst.data(), src, cnt * sizeof(double), hipMemcpyDefault));
-    return 0;
+    return input_fetch(ctx, src, cnt, dst.data());
 }
 
 }  // namespace mrbf
@@ -1631,43 +1630,27 @@ extern "C" int32_t mrbf_ps_step_problem(mrbf_ctx *ctx, const mrbf_ps_problem *pr
     P.nmodels = prob->n_models;
     P.nobj = prob->n_objectives;
     if (P.nobj < 1 || P.nobj > MAXOBJ) return fail(ctx, -2, "mrbf_ps_step: %d objectives (device path: 1..%d)", P.nobj, MAXOBJ);
-    std::vector<int> seen(P.nobj, 0);
-    for (int j = 0, e = 0; j < P.nmodels; ++j) {
-        const mrbf_model *M = prob->models[j];
-        if (!M) return fail(ctx, -2, "mrbf_ps_step: model %d is NULL", j);
-        if (j == 0) P.d = M->d;
-        if (M->d != P.d) return fail(ctx, -2, "mrbf_ps_step: model %d has %d variables, model 0 has %d", j, M->d, P.d);
-        P.models[j] = M;
+    std::vector<descent::SlotShape> slots;
+    descent::Layout lay;
+    if (descent::Defect D = descent::read(descent_shape(prob, prob->models, 1, slots), {true, descent::Centres::UNCHECKED}, lay))
+        return fail(ctx, -2, "mrbf_ps_step: %s", D.msg.c_str());
+    if (lay.n_nl > MAXCON) return fail(ctx, -2, "mrbf_ps_step: more than %d modelled constraints", MAXCON);
+    P.d = lay.d;
+    for (int j = 0; j < P.nmodels; ++j) {
+        P.models[j] = prob->models[j];
         P.foff[j] = P.nftot;
-        P.nftot += M->k;
-        for (int c = 0; c < M->k; ++c, ++e) {
-            const int role = prob->roles[e];
-            if (role >= 0) {
-                if (role >= P.nobj || seen[role]) return fail(ctx, -2, "mrbf_ps_step: roles[%d] = %d is not a (new) objective position", e, role);
-                seen[role] = 1;
-                P.obj_model[role] = j;
-                P.obj_col[role] = c;
-            } else if (role == MRBF_ROLE_EQ || role == MRBF_ROLE_INEQ) {
-                if (P.ncon >= MAXCON) return fail(ctx, -2, "mrbf_ps_step: more than %d modelled constraints", MAXCON);
-                P.con_model[P.ncon] = j;
-                P.con_col[P.ncon] = c;
-                P.con_eq[P.ncon] = role == MRBF_ROLE_EQ;
-                ++P.ncon;
-            } else if (role != MRBF_ROLE_NONE) {
-                return fail(ctx, -2, "mrbf_ps_step: roles[%d] = %d is not a role", e, role);
-            }
-        }
+        P.nftot += lay.k[j];
     }
-    for (int l = 0; l < P.nobj; ++l)
-        if (!seen[l]) return fail(ctx, -2, "mrbf_ps_step: objective %d is not an output of any model", l);
+    for (int l = 0; l < P.nobj; ++l) P.obj_model[l] = lay.obj[l].slot, P.obj_col[l] = lay.obj[l].col;
+    for (const descent::Row &r : lay.rows) {
+        P.con_model[P.ncon] = r.slot, P.con_col[P.ncon] = r.col, P.con_eq[P.ncon] = r.eq;
+        ++P.ncon;
+    }
     const int d = P.d, k = P.nobj;
     if (mrbf_dispatch_ps(d, k, P.nmodels, P.ncon, prob->n_lin_eq + prob->n_lin_ineq, 0) != MRBF_DISPATCH_DEVICE)
         return fail(ctx, -2, "mrbf_ps_step: d = %d / k = %d / %d constraints outside the device path (ask mrbf_dispatch_ps first)", d, k, P.ncon);
     P.nlin_eq = prob->n_lin_eq;
     P.nlin_ineq = prob->n_lin_ineq;
-    if (P.nlin_eq < 0 || P.nlin_ineq < 0) return fail(ctx, -2, "mrbf_ps_step: negative constraint count");
-    if ((P.nlin_eq && (!prob->A_eq || !prob->b_eq)) || (P.nlin_ineq && (!prob->A_ineq || !prob->b_ineq)))
-        return fail(ctx, -2, "mrbf_ps_step: linear constraint matrices are NULL");
     P.eq_tol = prob->eq_tol >= 0.0 ? prob->eq_tol : 1e-8;
     // box, start point, direction: host copies first (the pointers may be host or device memory)
     std::vector<double> hlb, hub, hxn, hfx, r(k), mx(k), allF;

@@ -11,15 +11,9 @@ constexpr int THREADS = 256;
 constexpr int MAXM = 64;
 constexpr int MAXD = 4096;
 
-// ---- get_criticality's right-hand sides: one workgroup per LP row and start, the Jacobians / values of the evaluation kernels as they lie
-struct RowSrc {
-    int kind;      // 0 objective row (Jacobian at x_n), 1 linear row, 2 modelled constraint row (Jacobian at x, value at x_n)
-    int dst;       // objective position / row of A_eq or A_ineq
-    int eq;        // 1: equality block
-    int stride;    // rows of the model (k_j): the Jacobian is k_j x d column-major per point
-    int64_t jac;   // offset of the row's first entry in the Jacobian buffer (point 0 = x_n; point 1 follows after k_j d)
-    int64_t val;   // offset of the row's value at x_n / index of the linear row
-};
+// ---- get_criticality's right-hand sides: one workgroup per LP row and start (RowSrc and its filler: descent_problem.hpp); kind 0 rows read
+// the Jacobian at x_n, kind 2 rows the Jacobian at x and the value at x_n
+using descent::RowSrc;
 struct AsmArgs {
     int n, k, rows, meq, min;
     int64_t sJ, sV, sx;  // per-start strides of J, of V, of xn / x; G, A_eq, b_eq, A_ineq, b_ineq lie in the consecutive per-LP blocks of launch()
@@ -66,6 +60,19 @@ struct StepArgs {
     double *out;         // per start [sigma, branch]
 };
 int launch_stepsize(mrbf_ctx *ctx, const StepArgs &a, int64_t n_starts);
+// StepArgs::rows of a container: linear equalities, modelled equalities, linear inequalities, modelled inequalities; `at` = the
+// offsets of the one-site evaluations at x of the slots with constraint rows
+inline std::vector<RowRef> stacked_rows(const descent::Layout &L, const descent::Offsets &at) {
+    std::vector<RowRef> rows;
+    for (int eq = 1; eq >= 0; --eq) {
+        const int first = eq ? 0 : L.n_lin_eq, nlin = eq ? L.n_lin_eq : L.n_lin_ineq;
+        for (int i = first; i < first + nlin; ++i) rows.push_back(RowRef{(int64_t)i * L.d, i, 1, 0});
+        // the Jacobian block of a slot is k x d column-major: entry (c, t) at t * k + c
+        for (const descent::Row &m : L.rows)
+            if (m.eq == (eq != 0)) rows.push_back(RowRef{at.jac[m.slot] + m.col, at.val[m.slot] + m.col, L.k[m.slot], 1});
+    }
+    return rows;
+}
 // per start: row 0 = x_n, row 1 + i = x_n + steps[i] * d, i = 0 .. max_loops
 int launch_trial(mrbf_ctx *ctx, const double *xn, int64_t sx, const double *dir, int64_t sdir, const double *steps, int d, int max_loops,
                  int64_t n_starts, double *X);
@@ -84,6 +91,10 @@ struct ArmijoArgs {
 };
 constexpr int ARMIJO_TAIL = 5;  // words per start of ArmijoArgs::tail
 int launch_armijo(mrbf_ctx *ctx, const ArmijoArgs &a, int64_t n_starts);
+// ArmijoArgs::obj of a container; `at` = the offsets of the objective slots' values at the L + 2 trial rows
+inline void fill_objectives(const descent::Layout &L, const descent::Offsets &at, ObjSrc *obj) {
+    for (size_t l = 0; l < L.obj.size(); ++l) obj[l] = ObjSrc{at.val[L.obj[l].slot] + L.obj[l].col, L.k[L.obj[l].slot]};
+}
 
 }  // namespace sdstep
 }  // namespace mrbf

@@ -26,7 +26,6 @@
 #include "sd.hpp"
 
 using namespace mrbf;
-using chain::batch_fetch;
 
 namespace {
 enum Site { SITE_PAIR = 0, SITE_X = 1, SITE_TRIAL = 2 };
@@ -54,145 +53,79 @@ extern "C" int32_t mrbf_sd_iterate_batch(mrbf_ctx *ctx, int64_t n_starts, const 
     if (!(opts->shrink > 0.0 && opts->shrink < 1.0)) return fail(ctx, -11, "mrbf_sd_iterate_batch: shrink must lie in (0, 1)");
     if (shape->n_models < 1 || !shape->roles) return fail(ctx, -3, "mrbf_sd_iterate_batch: grouped models with a roles table are required");
     const int k = shape->n_objectives, nm = shape->n_models;
-    if (k < 1) return fail(ctx, -3, "mrbf_sd_iterate_batch: %d objectives", k);
-    if (shape->n_lin_eq < 0 || shape->n_lin_ineq < 0) return fail(ctx, -3, "mrbf_sd_iterate_batch: negative constraint count");
-    if ((shape->n_lin_eq && (!shape->A_eq || !shape->b_eq)) || (shape->n_lin_ineq && (!shape->A_ineq || !shape->b_ineq)))
-        return fail(ctx, -3, "mrbf_sd_iterate_batch: linear constraint matrices are NULL");
     if (n_starts < 1) return fail(ctx, -2, "mrbf_sd_iterate_batch: %lld starts (ask mrbf_dispatch_sd_batch first)", (long long)n_starts);
     const int64_t N = n_starts;
-    // ---- the shape: start 0's models give d and every slot's output count; every other start must agree
-    for (int j = 0; j < nm; ++j)
-        if (!models[j]) return fail(ctx, -4, "mrbf_sd_iterate_batch: model %d of start 0 is NULL", j);
-    const int d = models[0]->d;
-    std::vector<int> kj(nm);
-    for (int j = 0; j < nm; ++j) kj[j] = models[j]->k;
-    // ---- rows of the LP and of the step from the roles table (as mrbf_sd_criticality and mrbf_sd_step read it)
-    std::vector<int> seen(k, 0), obj_model(k), obj_col(k);
-    std::vector<sd::RowSrc> obj(k), meq_src, min_src;
-    std::vector<RowRef> meq_ref, min_ref;
-    std::vector<int64_t> joffA(nm), voffA(nm), joffB(nm, 0), voffB(nm, 0), ooff(nm, 0);
-    std::vector<char> used(nm, 0), has_obj(nm, 0), has_con(nm, 0);
-    int64_t jtotA = 0, vtotA = 0, jtotB = 0, vtotB = 0, otot = 0;
-    const int L = opts->max_loops;
-    for (int j = 0, e = 0; j < nm; ++j) {
-        joffA[j] = jtotA, voffA[j] = vtotA;
-        jtotA += (int64_t)2 * kj[j] * d, vtotA += (int64_t)2 * kj[j];
-        for (int c = 0; c < kj[j]; ++c, ++e) {
-            const int role = shape->roles[e];
-            if (role >= 0) {
-                if (role >= k || seen[role]) return fail(ctx, -3, "mrbf_sd_iterate_batch: roles[%d] = %d is not a (new) objective position", e, role);
-                seen[role] = 1;
-                obj[role] = sd::RowSrc{0, role, 0, kj[j], joffA[j] + c, voffA[j] + c};
-                obj_model[role] = j, obj_col[role] = c;
-                has_obj[j] = 1, used[j] = 1;
-            } else if (role == MRBF_ROLE_EQ || role == MRBF_ROLE_INEQ) {
-                has_con[j] = 1, used[j] = 1;
-            } else if (role != MRBF_ROLE_NONE) {
-                return fail(ctx, -3, "mrbf_sd_iterate_batch: roles[%d] = %d is not a role", e, role);
-            }
-        }
-        if (has_con[j]) {
-            joffB[j] = jtotB, voffB[j] = vtotB;
-            jtotB += (int64_t)kj[j] * d, vtotB += kj[j];
-        }
-    }
-    for (int l = 0; l < k; ++l)
-        if (!seen[l]) return fail(ctx, -3, "mrbf_sd_iterate_batch: objective %d is not an output of any model", l);
-    for (int j = 0, e = 0; j < nm; ++j)
-        for (int c = 0; c < kj[j]; ++c, ++e) {
-            const int role = shape->roles[e];
-            if (role != MRBF_ROLE_EQ && role != MRBF_ROLE_INEQ) continue;
-            const bool eq = role == MRBF_ROLE_EQ;
-            (eq ? meq_src : min_src).push_back(sd::RowSrc{2, 0, eq ? 1 : 0, kj[j], joffA[j] + c, voffA[j] + c});
-            // site 0's Jacobian block is k x d column-major: entry (c, t) at t * k + c
-            (eq ? meq_ref : min_ref).push_back(RowRef{joffB[j] + c, voffB[j] + c, kj[j], 1});
-        }
-    const int n_nl = (int)(meq_src.size() + min_src.size()), n_lin = shape->n_lin_eq + shape->n_lin_ineq;
-    if (mrbf_dispatch_sd_batch(N, d, k, nm, n_nl, n_lin, 0, L) != MRBF_DISPATCH_DEVICE)
+    // ---- rows of the LP and of the step from the roles table (as mrbf_sd_criticality and mrbf_sd_step read it); the starts' slots agree
+    std::vector<descent::SlotShape> slots;
+    descent::Shape sh = descent_shape(shape, models, N, slots);
+    sh.batch = true;
+    descent::Layout lay;
+    if (descent::Defect D = descent::read(sh, {true, descent::Centres::EVERY_SLOT}, lay))
+        return fail(ctx, D.cls == descent::Defect::MODELS ? -4 : -3, "mrbf_sd_iterate_batch: %s", D.msg.c_str());
+    const int d = lay.d, L = opts->max_loops, n_lin = shape->n_lin_eq + shape->n_lin_ineq;
+    if (mrbf_dispatch_sd_batch(N, d, k, nm, lay.n_nl, n_lin, 0, L) != MRBF_DISPATCH_DEVICE)
         return fail(ctx, -2, "mrbf_sd_iterate_batch: %lld starts / d = %d / k = %d / %d rows / max_loops = %d outside the device path (ask mrbf_dispatch_sd_batch first)",
-                    (long long)N, d, k, n_nl + n_lin, L);
-    for (int64_t p = 0; p < N; ++p)
-        for (int j = 0; j < nm; ++j) {
-            const mrbf_model *M = models[p * nm + j];
-            if (!M) return fail(ctx, -4, "mrbf_sd_iterate_batch: model %d of start %lld is NULL", j, (long long)p);
-            if (M->d != d || M->k != kj[j])
-                return fail(ctx, -4, "mrbf_sd_iterate_batch: model %d of start %lld is %d variables x %d outputs, start 0 has %d x %d", j, (long long)p,
-                            M->d, M->k, d, kj[j]);
-            if (M->n == 0) return fail(ctx, -4, "mrbf_sd_iterate_batch: model %d of start %lld has no centres", j, (long long)p);
-        }
-    const int meq = shape->n_lin_eq + (int)meq_src.size(), min = shape->n_lin_ineq + (int)min_src.size(), m = k + meq + min;
-    for (int j = 0; j < nm; ++j)
-        if (has_obj[j]) ooff[j] = otot, otot += (int64_t)(L + 2) * kj[j];
+                    (long long)N, d, k, lay.n_nl + n_lin, L);
+    // the evaluations: [x_n; x] of every used slot (A), x of the slots with constraint rows (B), the L + 2 trial rows of the objective slots
+    const descent::Offsets atA = lay.offsets(2, descent::Slots::USED), atB = lay.offsets(1, descent::Slots::CONSTRAINED);
+    const descent::Offsets atO = lay.offsets(L + 2, descent::Slots::OBJECTIVE);
+    const int64_t jtotA = atA.jtot, vtotA = atA.vtot, jtotB = atB.jtot, vtotB = atB.vtot, otot = atO.vtot;
+    const int meq = lay.meq, min = lay.min, m = k + meq + min;
     (void)hipSetDevice(ctx->device);
     PinGuard pin(ctx);
     // ---- the evaluations of the two single calls, grouped by what one eval_fused_batch launch requires (batch_chain.hpp)
     chain::Plan ev;
+    const descent::Slots site_slots[3] = {descent::Slots::USED, descent::Slots::CONSTRAINED, descent::Slots::OBJECTIVE};
     auto site_m = [&](int site) -> int64_t { return site == SITE_PAIR ? 2 : (site == SITE_X ? 1 : L + 2); };
     for (int site = 0; site < 3; ++site)
         for (int64_t p = 0; p < N; ++p)
             for (int j = 0; j < nm; ++j) {
-                if (!(site == SITE_PAIR ? used[j] : (site == SITE_X ? has_con[j] : has_obj[j]))) continue;
+                if (!lay.chosen(j, site_slots[site])) continue;
                 ev.add(ctx, site, p, j, models[p * nm + j], site_m(site), site != SITE_TRIAL);
             }
     ev.close();
     // ---- the arena (doubles; every piece a multiple of 16): upload | work | evaluation scratch | output block
-    size_t total = 0;
-    auto take = [&](size_t cnt) {
-        const size_t at = total;
-        total += (cnt + 15) & ~(size_t)15;
-        return at;
-    };
+    chain::Arena ar;
     const size_t nlin = (size_t)n_lin, SN = (size_t)N;
-    std::vector<RowRef> rows;
-    for (int i = 0; i < shape->n_lin_eq; ++i) rows.push_back(RowRef{(int64_t)i * d, i, 1, 0});
-    rows.insert(rows.end(), meq_ref.begin(), meq_ref.end());
-    for (int i = 0; i < shape->n_lin_ineq; ++i) rows.push_back(RowRef{(int64_t)(shape->n_lin_eq + i) * d, shape->n_lin_eq + i, 1, 0});
-    rows.insert(rows.end(), min_ref.begin(), min_ref.end());
+    const std::vector<RowRef> rows = sdstep::stacked_rows(lay, atB);
     const size_t rows_dbl = (rows.size() * sizeof(RowRef) + sizeof(double) - 1) / sizeof(double);
     const size_t desc_dbl = ev.desc_doubles();
-    const size_t oPairs = take(SN * 2 * d), oDelta = take(SN), oLb = take(d), oUb = take(d), oA = take(nlin * d), oB = take(nlin);
-    const size_t oRows = take(rows_dbl), oDesc = take(desc_dbl);
-    const size_t up_cnt = total;
-    const size_t oJA = take(SN * jtotA), oVA = take(SN * vtotA), oJB = take(SN * jtotB), oVB = take(SN * vtotB);
-    const size_t oG = take(SN * k * d), oAeq = take(SN * meq * d), oBeq = take(SN * meq), oAin = take(SN * min * d), oBin = take(SN * min);
-    const size_t oSteps = take(SN * (L + 1)), oSig = take(SN * 2), oX = take(SN * (L + 2) * d), oVO = take(SN * otot);
-    ev.carve(take);
+    const size_t oPairs = ar.take(SN * 2 * d), oDelta = ar.take(SN), oLb = ar.take(d), oUb = ar.take(d), oA = ar.take(nlin * d), oB = ar.take(nlin);
+    const size_t oRows = ar.take(rows_dbl), oDesc = ar.take(desc_dbl);
+    const size_t up_cnt = ar.total;
+    const size_t oJA = ar.take(SN * jtotA), oVA = ar.take(SN * vtotA), oJB = ar.take(SN * jtotB), oVB = ar.take(SN * vtotB);
+    const size_t oG = ar.take(SN * k * d), oAeq = ar.take(SN * meq * d), oBeq = ar.take(SN * meq), oAin = ar.take(SN * min * d), oBin = ar.take(SN * min);
+    const size_t oSteps = ar.take(SN * (L + 1)), oSig = ar.take(SN * 2), oX = ar.take(SN * (L + 2) * d), oVO = ar.take(SN * otot);
+    ev.carve(ar);
     for (chain::Member &mb : ev.mem) {
         const size_t p = (size_t)mb.p;
         const int j = mb.j;
-        if (mb.site == SITE_PAIR) mb.X = oPairs + p * 2 * d, mb.vals = oVA + p * vtotA + voffA[j], mb.jacs = oJA + p * jtotA + joffA[j];
-        else if (mb.site == SITE_X) mb.X = oPairs + p * 2 * d + d, mb.vals = oVB + p * vtotB + voffB[j], mb.jacs = oJB + p * jtotB + joffB[j];
-        else mb.X = oX + p * (size_t)(L + 2) * d, mb.vals = oVO + p * otot + ooff[j];
+        if (mb.site == SITE_PAIR) mb.X = oPairs + p * 2 * d, mb.vals = oVA + p * vtotA + atA.val[j], mb.jacs = oJA + p * jtotA + atA.jac[j];
+        else if (mb.site == SITE_X) mb.X = oPairs + p * 2 * d + d, mb.vals = oVB + p * vtotB + atB.val[j], mb.jacs = oJB + p * jtotB + atB.jac[j];
+        else mb.X = oX + p * (size_t)(L + 2) * d, mb.vals = oVO + p * otot + atO.val[j];
     }
     // the output block: x+ | m(x+) | [omega_step, step_norm, loops, sigma, branch] | d | omega | status, (iterations, flips) words
-    const size_t out0 = total;
-    const size_t oXp = take(SN * d), oMxp = take(SN * k), oTail = take(SN * sdstep::ARMIJO_TAIL), oDir = take(SN * d), oOmega = take(SN);
-    const size_t oInts = take((3 * SN + 1) / 2);
-    const size_t out_cnt = total - out0;
+    const size_t out0 = ar.total;
+    const size_t oXp = ar.take(SN * d), oMxp = ar.take(SN * k), oTail = ar.take(SN * sdstep::ARMIJO_TAIL), oDir = ar.take(SN * d), oOmega = ar.take(SN);
+    const size_t oInts = ar.take((3 * SN + 1) / 2);
+    const size_t out_cnt = ar.total - out0;
     double *base;
-    MRBF_TRY(get_buf(ctx, S_SD_BATCH, total, &base));
+    MRBF_TRY(get_buf(ctx, S_SD_BATCH, ar.total, &base));
     // ---- the upload, staged in the pinned block where it fits
-    std::vector<double> hup_v;
-    double *hup = reinterpret_cast<double *>(up_cnt * sizeof(double) <= ((size_t)4 << 20) ? pin_take(ctx, up_cnt * sizeof(double)) : nullptr);
-    if (!hup) {
-        hup_v.resize(up_cnt);
-        hup = hup_v.data();
-    }
+    chain::Staging up(ctx, up_cnt);
+    double *hup = up.p;
     std::memset(hup, 0, up_cnt * sizeof(double));
     {
         std::vector<double> tmp(SN * d);
-        MRBF_TRY(batch_fetch(ctx, x_n, SN * d, tmp.data()));
+        MRBF_TRY(input_fetch(ctx, x_n, SN * d, tmp.data()));
         for (size_t p = 0; p < SN; ++p) std::memcpy(hup + oPairs + p * 2 * d, tmp.data() + p * d, (size_t)d * sizeof(double));
-        MRBF_TRY(batch_fetch(ctx, x, SN * d, tmp.data()));
+        MRBF_TRY(input_fetch(ctx, x, SN * d, tmp.data()));
         for (size_t p = 0; p < SN; ++p) std::memcpy(hup + oPairs + p * 2 * d + d, tmp.data() + p * d, (size_t)d * sizeof(double));
     }
-    MRBF_TRY(batch_fetch(ctx, delta, SN, hup + oDelta));
-    MRBF_TRY(batch_fetch(ctx, lb, d, hup + oLb));
-    MRBF_TRY(batch_fetch(ctx, ub, d, hup + oUb));
-    MRBF_TRY(batch_fetch(ctx, shape->A_eq, (size_t)shape->n_lin_eq * d, hup + oA));
-    MRBF_TRY(batch_fetch(ctx, shape->A_ineq, (size_t)shape->n_lin_ineq * d, hup + oA + (size_t)shape->n_lin_eq * d));
-    MRBF_TRY(batch_fetch(ctx, shape->b_eq, shape->n_lin_eq, hup + oB));
-    MRBF_TRY(batch_fetch(ctx, shape->b_ineq, shape->n_lin_ineq, hup + oB + shape->n_lin_eq));
+    MRBF_TRY(input_fetch(ctx, delta, SN, hup + oDelta));
+    MRBF_TRY(input_fetch(ctx, lb, d, hup + oLb));
+    MRBF_TRY(input_fetch(ctx, ub, d, hup + oUb));
+    MRBF_TRY(fetch_linear_rows(ctx, shape, d, hup + oA, hup + oB));
     if (!rows.empty()) std::memcpy(hup + oRows, rows.data(), rows.size() * sizeof(RowRef));
     double *dPairs = base + oPairs, *dX = base + oX;
     EvalDesc *hdesc = reinterpret_cast<EvalDesc *>(hup + oDesc);
@@ -211,20 +144,7 @@ extern "C" int32_t mrbf_sd_iterate_batch(mrbf_ctx *ctx, int64_t n_starts, const 
     aa.sJ = jtotA, aa.sV = vtotA, aa.sx = 2 * (int64_t)d;
     aa.J = base + oJA, aa.V = base + oVA, aa.xn = dPairs, aa.x = dPairs + d, aa.Alin = base + oA, aa.blin = base + oB;
     aa.G = base + oG, aa.Aeq = base + oAeq, aa.beq = base + oBeq, aa.Ain = base + oAin, aa.bin = base + oBin;
-    {
-        int r = 0;
-        for (int l = 0; l < k; ++l) aa.src[r++] = obj[l];
-        for (int i = 0; i < shape->n_lin_eq; ++i) aa.src[r++] = sd::RowSrc{1, i, 1, 1, 0, i};
-        for (size_t i = 0; i < meq_src.size(); ++i) {
-            aa.src[r] = meq_src[i];
-            aa.src[r++].dst = shape->n_lin_eq + (int)i;
-        }
-        for (int i = 0; i < shape->n_lin_ineq; ++i) aa.src[r++] = sd::RowSrc{1, i, 0, 1, 0, shape->n_lin_eq + i};
-        for (size_t i = 0; i < min_src.size(); ++i) {
-            aa.src[r] = min_src[i];
-            aa.src[r++].dst = shape->n_lin_ineq + (int)i;
-        }
-    }
+    descent::fill_sources(lay, atA, true, aa.src);
     MRBF_TRY(sd::launch_assemble(ctx, aa, N));
     double *dDir = base + oDir, *dOmega = base + oOmega;
     int *dInts = reinterpret_cast<int *>(base + oInts);
@@ -253,18 +173,11 @@ extern "C" int32_t mrbf_sd_iterate_batch(mrbf_ctx *ctx, int64_t n_starts, const 
     am.omega = dOmega;
     am.V = base + oVO, am.X = dX, am.dir = dDir, am.steps = base + oSteps, am.stepout = base + oSig;
     am.xplus = base + oXp, am.mxplus = base + oMxp, am.tail = base + oTail;
-    for (int l = 0; l < k; ++l) {
-        const int j = obj_model[l];
-        am.obj[l] = sdstep::ObjSrc{ooff[j] + obj_col[l], kj[j]};
-    }
+    sdstep::fill_objectives(lay, atO, am.obj);
     MRBF_TRY(sdstep::launch_armijo(ctx, am, N));
     // ---- one read-back
-    std::vector<double> hout_v;
-    double *hout = reinterpret_cast<double *>(out_cnt * sizeof(double) <= ((size_t)4 << 20) ? pin_take(ctx, out_cnt * sizeof(double)) : nullptr);
-    if (!hout) {
-        hout_v.resize(out_cnt);
-        hout = hout_v.data();
-    }
+    chain::Staging down(ctx, out_cnt);
+    double *hout = down.p;
     MRBF_HIP(ctx, hipMemcpyAsync(hout, base + out0, out_cnt * sizeof(double), hipMemcpyDeviceToHost, st));
     const bool dev_d = is_device_ptr(d_out), dev_x = is_device_ptr(x_plus), dev_m = is_device_ptr(mx_plus);
     if (dev_d) MRBF_HIP(ctx, hipMemcpyAsync(d_out, dDir, SN * d * sizeof(double), hipMemcpyDeviceToDevice, st));

@@ -488,28 +488,6 @@ int launch(mrbf_ctx *ctx, int64_t n_lp, int n, int k, int meq, int min, int norm
 
 using namespace mrbf;
 
-namespace {
-// device view of an input: the pointer itself when device memory, else a copy in `arena` (advanced)
-int sd_view(mrbf_ctx *ctx, const double *user, size_t count, double *&arena, const double **dev) {
-    if (!user || count == 0) {
-        *dev = nullptr;
-        return 0;
-    }
-    if (is_device_ptr(user)) {
-        *dev = user;
-        return 0;
-    }
-    MRBF_HIP(ctx, hipMemcpyAsync(arena, user, count * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    *dev = arena;
-    arena += count;
-    return 0;
-}
-int sd_fetch(mrbf_ctx *ctx, const double *src, size_t cnt, double *dst) {
-    if (cnt) MRBF_HIP(ctx, hipMemcpy(dst, src, cnt * sizeof(double), hipMemcpyDefault));
-    return 0;
-}
-}  // namespace
-
 extern "C" int32_t mrbf_sd_direction(mrbf_ctx *ctx, int64_t n_lp, int32_t d, int32_t k, int32_t m_eq, int32_t m_ineq, const double *G,
                                      const double *x, const double *lb, const double *ub, const double *A_eq, const double *b_eq,
                                      const double *A_ineq, const double *b_ineq, int32_t normalize, double *d_out, double *omega_out,
@@ -541,14 +519,14 @@ extern "C" int32_t mrbf_sd_direction(mrbf_ctx *ctx, int64_t n_lp, int32_t d, int
     double *arena;
     MRBF_TRY(get_buf(ctx, S_SD_IN, in_cnt, &arena));
     const double *dG, *dx, *dlb, *dub, *dAeq, *dbeq, *dAin, *dbin;
-    MRBF_TRY(sd_view(ctx, G, N * k * d, arena, &dG));
-    MRBF_TRY(sd_view(ctx, x, N * d, arena, &dx));
-    MRBF_TRY(sd_view(ctx, lb, N * d, arena, &dlb));
-    MRBF_TRY(sd_view(ctx, ub, N * d, arena, &dub));
-    MRBF_TRY(sd_view(ctx, A_eq, N * m_eq * d, arena, &dAeq));
-    MRBF_TRY(sd_view(ctx, b_eq, N * m_eq, arena, &dbeq));
-    MRBF_TRY(sd_view(ctx, A_ineq, N * m_ineq * d, arena, &dAin));
-    MRBF_TRY(sd_view(ctx, b_ineq, N * m_ineq, arena, &dbin));
+    MRBF_TRY(input_view(ctx, G, N * k * d, arena, &dG));
+    MRBF_TRY(input_view(ctx, x, N * d, arena, &dx));
+    MRBF_TRY(input_view(ctx, lb, N * d, arena, &dlb));
+    MRBF_TRY(input_view(ctx, ub, N * d, arena, &dub));
+    MRBF_TRY(input_view(ctx, A_eq, N * m_eq * d, arena, &dAeq));
+    MRBF_TRY(input_view(ctx, b_eq, N * m_eq, arena, &dbeq));
+    MRBF_TRY(input_view(ctx, A_ineq, N * m_ineq * d, arena, &dAin));
+    MRBF_TRY(input_view(ctx, b_ineq, N * m_ineq, arena, &dbin));
     // outputs: the caller's device buffers in place, else one staging buffer (doubles, then the int words)
     const bool dev_d = is_device_ptr(d_out), dev_w = is_device_ptr(omega_out), dev_y = dual_out && is_device_ptr(dual_out);
     const bool dev_s = is_device_ptr(status_out), dev_i = iters_out && is_device_ptr(iters_out);
@@ -581,59 +559,28 @@ extern "C" int32_t mrbf_sd_criticality(mrbf_ctx *ctx, const mrbf_ps_problem *pro
     if (!info) return fail(ctx, -10, "info is NULL");
     std::memset(info, 0, sizeof(*info));
     if (prob->n_models < 1 || !prob->models || !prob->roles) return fail(ctx, -2, "mrbf_sd_criticality: grouped models with a roles table are required");
-    const int k = prob->n_objectives;
-    if (k < 1) return fail(ctx, -2, "mrbf_sd_criticality: %d objectives", k);
-    if (prob->n_lin_eq < 0 || prob->n_lin_ineq < 0) return fail(ctx, -2, "mrbf_sd_criticality: negative constraint count");
-    if ((prob->n_lin_eq && (!prob->A_eq || !prob->b_eq)) || (prob->n_lin_ineq && (!prob->A_ineq || !prob->b_ineq)))
-        return fail(ctx, -2, "mrbf_sd_criticality: linear constraint matrices are NULL");
-    // ---- the rows of the LP from the roles table
-    const int d = prob->models[0] ? prob->models[0]->d : 0;
-    std::vector<int> seen(k, 0);
-    std::vector<sd::RowSrc> obj(k), meq_rows, min_rows;
-    std::vector<int64_t> joff(prob->n_models), voff(prob->n_models);
-    int64_t jtot = 0, vtot = 0;
-    for (int j = 0, e = 0; j < prob->n_models; ++j) {
-        const mrbf_model *M = prob->models[j];
-        if (!M) return fail(ctx, -2, "mrbf_sd_criticality: model %d is NULL", j);
-        if (M->d != d) return fail(ctx, -2, "mrbf_sd_criticality: model %d has %d variables, model 0 has %d", j, M->d, d);
-        joff[j] = jtot, voff[j] = vtot;
-        jtot += (int64_t)2 * M->k * d, vtot += (int64_t)2 * M->k;
-        for (int c = 0; c < M->k; ++c, ++e) {
-            const int role = prob->roles[e];
-            sd::RowSrc s{0, 0, 0, M->k, joff[j] + c, voff[j] + c};
-            if (role >= 0) {
-                if (role >= k || seen[role]) return fail(ctx, -2, "mrbf_sd_criticality: roles[%d] = %d is not a (new) objective position", e, role);
-                seen[role] = 1;
-                s.dst = role;
-                obj[role] = s;
-            } else if (role == MRBF_ROLE_EQ || role == MRBF_ROLE_INEQ) {
-                s.kind = 2;
-                (role == MRBF_ROLE_EQ ? meq_rows : min_rows).push_back(s);
-            } else if (role != MRBF_ROLE_NONE) {
-                return fail(ctx, -2, "mrbf_sd_criticality: roles[%d] = %d is not a role", e, role);
-            }
-        }
-    }
-    for (int l = 0; l < k; ++l)
-        if (!seen[l]) return fail(ctx, -2, "mrbf_sd_criticality: objective %d is not an output of any model", l);
-    const int n_nl = (int)(meq_rows.size() + min_rows.size()), n_lin = prob->n_lin_eq + prob->n_lin_ineq;
-    if (mrbf_dispatch_sd(d, k, prob->n_models, n_nl, n_lin, 0) != MRBF_DISPATCH_DEVICE)
-        return fail(ctx, -2, "mrbf_sd_criticality: d = %d / k = %d / %d rows outside the device path (ask mrbf_dispatch_sd first)", d, k, k + n_nl + n_lin);
-    const int meq = prob->n_lin_eq + (int)meq_rows.size(), min = prob->n_lin_ineq + (int)min_rows.size(), m = k + meq + min;
+    // ---- the rows of the LP from the roles table; the evaluations at [x_n; x] of every used model
+    std::vector<descent::SlotShape> slots;
+    descent::Layout lay;
+    if (descent::Defect D = descent::read(descent_shape(prob, prob->models, 1, slots), {true, descent::Centres::UNCHECKED}, lay))
+        return fail(ctx, -2, "mrbf_sd_criticality: %s", D.msg.c_str());
+    const int d = lay.d, k = prob->n_objectives, n_lin = prob->n_lin_eq + prob->n_lin_ineq;
+    if (mrbf_dispatch_sd(d, k, prob->n_models, lay.n_nl, n_lin, 0) != MRBF_DISPATCH_DEVICE)
+        return fail(ctx, -2, "mrbf_sd_criticality: d = %d / k = %d / %d rows outside the device path (ask mrbf_dispatch_sd first)", d, k, k + lay.n_nl + n_lin);
+    const descent::Offsets at = lay.offsets(2, descent::Slots::USED);
+    const int64_t jtot = at.jtot, vtot = at.vtot;
+    const int meq = lay.meq, min = lay.min, m = k + meq + min;
     (void)hipSetDevice(ctx->device);
     PinGuard pin(ctx);
     // ---- host inputs, packed: [x_n; x] (the two evaluation sites), lb, ub, linear rows (eq, then ineq), their b
     const size_t nlin = (size_t)n_lin;
     std::vector<double> h((size_t)4 * d + nlin * (d + 1));
     double *hxn = h.data(), *hx = hxn + d, *hlb = hx + d, *hub = hlb + d, *hA = hub + d, *hb = hA + nlin * d;
-    MRBF_TRY(sd_fetch(ctx, x_n, d, hxn));
-    MRBF_TRY(sd_fetch(ctx, x, d, hx));
-    MRBF_TRY(sd_fetch(ctx, lb, d, hlb));
-    MRBF_TRY(sd_fetch(ctx, ub, d, hub));
-    MRBF_TRY(sd_fetch(ctx, prob->A_eq, (size_t)prob->n_lin_eq * d, hA));
-    MRBF_TRY(sd_fetch(ctx, prob->A_ineq, (size_t)prob->n_lin_ineq * d, hA + (size_t)prob->n_lin_eq * d));
-    MRBF_TRY(sd_fetch(ctx, prob->b_eq, prob->n_lin_eq, hb));
-    MRBF_TRY(sd_fetch(ctx, prob->b_ineq, prob->n_lin_ineq, hb + prob->n_lin_eq));
+    MRBF_TRY(input_fetch(ctx, x_n, d, hxn));
+    MRBF_TRY(input_fetch(ctx, x, d, hx));
+    MRBF_TRY(input_fetch(ctx, lb, d, hlb));
+    MRBF_TRY(input_fetch(ctx, ub, d, hub));
+    MRBF_TRY(fetch_linear_rows(ctx, prob, d, hA, hb));
     hipEvent_t e0 = ctx->ev[0], e1 = ctx->ev[1];
     MRBF_HIP(ctx, hipEventRecord(e0, ctx->stream));
     // device arena: inputs | Jacobians | values | LP data (G, A_eq, b_eq, A_ineq, b_ineq) | outputs (d, omega, dual, 3 int words)
@@ -645,31 +592,15 @@ extern "C" int32_t mrbf_sd_criticality(mrbf_ctx *ctx, const mrbf_ps_problem *pro
     MRBF_HIP(ctx, hipMemcpyAsync(base, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     const double *dxn = base, *dx = base + d, *dlb = base + 2 * d, *dub = base + 3 * d, *dA = base + 4 * d, *db = dA + nlin * d;
     // ---- values and Jacobians of every model at x_n and x: one sweep per model
-    for (int j = 0, e = 0; j < prob->n_models; ++j) {
-        const mrbf_model *M = prob->models[j];
-        bool used = false;
-        for (int c = 0; c < M->k; ++c) used = used || prob->roles[e + c] != MRBF_ROLE_NONE;
-        e += M->k;
-        if (used) MRBF_TRY(eval_model(ctx, M, 2, dxn, dV + voff[j], dJ + joff[j], nullptr));
-    }
+    for (int j = 0; j < prob->n_models; ++j)
+        if (lay.chosen(j, descent::Slots::USED)) MRBF_TRY(eval_model(ctx, prob->models[j], 2, dxn, dV + at.val[j], dJ + at.jac[j], nullptr));
     // ---- assemble G, A_eq / b_eq (linear, then modelled), A_ineq / b_ineq (likewise) on the device
     sd::AsmArgs aa;
     aa.n = d, aa.k = k, aa.rows = m, aa.meq = meq, aa.min = min;
     aa.sJ = aa.sV = aa.sx = 0;  // one start
     aa.J = dJ, aa.V = dV, aa.xn = dxn, aa.x = dx, aa.Alin = dA, aa.blin = db;
     aa.G = dG, aa.Aeq = dAeq, aa.beq = dbeq, aa.Ain = dAin, aa.bin = dbin;
-    int r = 0;
-    for (int l = 0; l < k; ++l) aa.src[r++] = obj[l];
-    for (int i = 0; i < prob->n_lin_eq; ++i) aa.src[r++] = sd::RowSrc{1, i, 1, 1, 0, i};
-    for (size_t i = 0; i < meq_rows.size(); ++i) {
-        aa.src[r] = meq_rows[i];
-        aa.src[r].dst = prob->n_lin_eq + (int)i, aa.src[r++].eq = 1;
-    }
-    for (int i = 0; i < prob->n_lin_ineq; ++i) aa.src[r++] = sd::RowSrc{1, i, 0, 1, 0, prob->n_lin_eq + i};
-    for (size_t i = 0; i < min_rows.size(); ++i) {
-        aa.src[r] = min_rows[i];
-        aa.src[r].dst = prob->n_lin_ineq + (int)i, aa.src[r++].eq = 0;
-    }
+    descent::fill_sources(lay, at, true, aa.src);
     MRBF_TRY(sd::launch_assemble(ctx, aa, 1));
     int *oi = reinterpret_cast<int *>(dout + d + 1 + m);
     MRBF_TRY(sd::launch(ctx, 1, d, k, meq, min, normalize, dG, dxn, 0, dlb, dub, 0, meq ? dAeq : nullptr, meq ? dbeq : nullptr,
@@ -685,12 +616,8 @@ extern "C" int32_t mrbf_sd_criticality(mrbf_ctx *ctx, const mrbf_ps_problem *pro
     std::memcpy(words, hout.data() + d + 1 + m, sizeof(words));
     info->status = words[0], info->iterations = words[1], info->bound_flips = words[2];
     info->omega = hout[d];
-    if (is_device_ptr(d_out)) MRBF_HIP(ctx, hipMemcpy(d_out, hout.data(), d * sizeof(double), hipMemcpyHostToDevice));
-    else std::memcpy(d_out, hout.data(), d * sizeof(double));
-    if (dual_out) {
-        if (is_device_ptr(dual_out)) MRBF_HIP(ctx, hipMemcpy(dual_out, hout.data() + d + 1, m * sizeof(double), hipMemcpyHostToDevice));
-        else std::memcpy(dual_out, hout.data() + d + 1, m * sizeof(double));
-    }
+    MRBF_TRY(output_put(ctx, d_out, hout.data(), d));
+    if (dual_out) MRBF_TRY(output_put(ctx, dual_out, hout.data() + d + 1, m));
     if (info->status == MRBF_SD_GAVE_UP) return fail(ctx, -2, "mrbf_sd_criticality: the direction LP gave up (take the reference method)");
     return MRBF_OK;
 }

@@ -343,16 +343,6 @@ int launch_armijo(mrbf_ctx *ctx, const ArmijoArgs &a, int64_t n_starts) {
 
 using namespace mrbf;
 
-namespace {
-// host copy of a caller array that may live on the host or the device
-int step_fetch(mrbf_ctx *ctx, const double *src, size_t cnt, double *dst) {
-    if (!cnt) return 0;
-    if (is_device_ptr(src)) MRBF_HIP(ctx, hipMemcpy(dst, src, cnt * sizeof(double), hipMemcpyDeviceToHost));
-    else std::memcpy(dst, src, cnt * sizeof(double));
-    return 0;
-}
-}  // namespace
-
 extern "C" int32_t mrbf_sd_step(mrbf_ctx *ctx, const mrbf_ps_problem *prob, const double *x, const double *x_n, double delta,
                                 const double *lb, const double *ub, double omega, const double *dir, const mrbf_sd_step_options *opts,
                                 double *x_plus, double *mx_plus, mrbf_sd_step_info *info) {
@@ -371,56 +361,15 @@ extern "C" int32_t mrbf_sd_step(mrbf_ctx *ctx, const mrbf_ps_problem *prob, cons
     std::memset(info, 0, sizeof(*info));
     if (!(opts->shrink > 0.0 && opts->shrink < 1.0)) return fail(ctx, -8, "mrbf_sd_step: shrink must lie in (0, 1)");
     if (prob->n_models < 1 || !prob->models || !prob->roles) return fail(ctx, -2, "mrbf_sd_step: grouped models with a roles table are required");
-    const int k = prob->n_objectives;
-    if (k < 1) return fail(ctx, -2, "mrbf_sd_step: %d objectives", k);
-    if (prob->n_lin_eq < 0 || prob->n_lin_ineq < 0) return fail(ctx, -2, "mrbf_sd_step: negative constraint count");
-    if ((prob->n_lin_eq && (!prob->A_eq || !prob->b_eq)) || (prob->n_lin_ineq && (!prob->A_ineq || !prob->b_ineq)))
-        return fail(ctx, -2, "mrbf_sd_step: linear constraint matrices are NULL");
     // ---- objective sources and modelled constraint rows from the roles table
-    const int d = prob->models[0] ? prob->models[0]->d : 0;
-    std::vector<int> seen(std::max(k, 1), 0);
-    std::vector<int> obj_model(k), obj_col(k);
-    std::vector<RowRef> meq_rows, min_rows;
-    std::vector<int64_t> joff(prob->n_models), voff(prob->n_models);
-    std::vector<char> has_obj(prob->n_models, 0), has_con(prob->n_models, 0);
-    int64_t jtot = 0, vtot = 0;
-    for (int j = 0, e = 0; j < prob->n_models; ++j) {
-        const mrbf_model *M = prob->models[j];
-        if (!M) return fail(ctx, -2, "mrbf_sd_step: model %d is NULL", j);
-        if (M->d != d) return fail(ctx, -2, "mrbf_sd_step: model %d has %d variables, model 0 has %d", j, M->d, d);
-        for (int c = 0; c < M->k; ++c, ++e) {
-            const int role = prob->roles[e];
-            if (role >= 0) {
-                if (role >= k || seen[role]) return fail(ctx, -2, "mrbf_sd_step: roles[%d] = %d is not a (new) objective position", e, role);
-                seen[role] = 1;
-                obj_model[role] = j, obj_col[role] = c;
-                has_obj[j] = 1;
-            } else if (role == MRBF_ROLE_EQ || role == MRBF_ROLE_INEQ) {
-                has_con[j] = 1;
-            } else if (role != MRBF_ROLE_NONE) {
-                return fail(ctx, -2, "mrbf_sd_step: roles[%d] = %d is not a role", e, role);
-            }
-        }
-        if (has_con[j]) {
-            joff[j] = jtot, voff[j] = vtot;
-            jtot += (int64_t)M->k * d, vtot += M->k;
-        }
-    }
-    for (int l = 0; l < k; ++l)
-        if (!seen[l]) return fail(ctx, -2, "mrbf_sd_step: objective %d is not an output of any model", l);
-    for (int j = 0, e = 0; j < prob->n_models; ++j) {
-        const mrbf_model *M = prob->models[j];
-        for (int c = 0; c < M->k; ++c, ++e) {
-            const int role = prob->roles[e];
-            // site 0's Jacobian block is k x d column-major: entry (c, t) at t * k + c
-            if (role == MRBF_ROLE_EQ || role == MRBF_ROLE_INEQ)
-                (role == MRBF_ROLE_EQ ? meq_rows : min_rows).push_back(RowRef{joff[j] + c, voff[j] + c, M->k, 1});
-        }
-    }
-    const int n_nl = (int)(meq_rows.size() + min_rows.size()), n_lin = prob->n_lin_eq + prob->n_lin_ineq;
-    if (mrbf_dispatch_sd_step(d, k, prob->n_models, n_nl, n_lin, 0, opts->max_loops) != MRBF_DISPATCH_DEVICE)
+    std::vector<descent::SlotShape> slots;
+    descent::Layout lay;
+    if (descent::Defect D = descent::read(descent_shape(prob, prob->models, 1, slots), {true, descent::Centres::UNCHECKED}, lay))
+        return fail(ctx, -2, "mrbf_sd_step: %s", D.msg.c_str());
+    const int d = lay.d, k = prob->n_objectives, n_lin = prob->n_lin_eq + prob->n_lin_ineq;
+    if (mrbf_dispatch_sd_step(d, k, prob->n_models, lay.n_nl, n_lin, 0, opts->max_loops) != MRBF_DISPATCH_DEVICE)
         return fail(ctx, -2, "mrbf_sd_step: d = %d / k = %d / %d rows / max_loops = %d outside the device path (ask mrbf_dispatch_sd_step first)",
-                    d, k, n_nl + n_lin, opts->max_loops);
+                    d, k, lay.n_nl + n_lin, opts->max_loops);
     const int L = opts->max_loops;
     (void)hipSetDevice(ctx->device);
     PinGuard pin(ctx);
@@ -429,27 +378,17 @@ extern "C" int32_t mrbf_sd_step(mrbf_ctx *ctx, const mrbf_ps_problem *prob, cons
     std::vector<double> h((size_t)5 * d + nlin * (d + 1) + 2);
     double *hxn = h.data(), *hx = hxn + d, *hlb = hx + d, *hub = hlb + d, *hd = hub + d, *hA = hd + d, *hb = hA + nlin * d;
     hb[nlin] = delta, hb[nlin + 1] = omega;
-    MRBF_TRY(step_fetch(ctx, x_n, d, hxn));
-    MRBF_TRY(step_fetch(ctx, x, d, hx));
-    MRBF_TRY(step_fetch(ctx, lb, d, hlb));
-    MRBF_TRY(step_fetch(ctx, ub, d, hub));
-    MRBF_TRY(step_fetch(ctx, dir, d, hd));
-    MRBF_TRY(step_fetch(ctx, prob->A_eq, (size_t)prob->n_lin_eq * d, hA));
-    MRBF_TRY(step_fetch(ctx, prob->A_ineq, (size_t)prob->n_lin_ineq * d, hA + (size_t)prob->n_lin_eq * d));
-    MRBF_TRY(step_fetch(ctx, prob->b_eq, prob->n_lin_eq, hb));
-    MRBF_TRY(step_fetch(ctx, prob->b_ineq, prob->n_lin_ineq, hb + prob->n_lin_eq));
-    // the stacked rows: linear equalities, modelled equalities, linear inequalities, modelled inequalities
-    std::vector<RowRef> rows;
-    for (int i = 0; i < prob->n_lin_eq; ++i) rows.push_back(RowRef{(int64_t)i * d, i, 1, 0});
-    rows.insert(rows.end(), meq_rows.begin(), meq_rows.end());
-    for (int i = 0; i < prob->n_lin_ineq; ++i) rows.push_back(RowRef{(int64_t)(prob->n_lin_eq + i) * d, prob->n_lin_eq + i, 1, 0});
-    rows.insert(rows.end(), min_rows.begin(), min_rows.end());
-    const int n_eq = prob->n_lin_eq + (int)meq_rows.size(), n_in = prob->n_lin_ineq + (int)min_rows.size();
-    // objective values: one block of (L + 2) x M->k per model that carries an objective row
-    std::vector<int64_t> ooff(prob->n_models, 0);
-    int64_t otot = 0;
-    for (int j = 0; j < prob->n_models; ++j)
-        if (has_obj[j]) ooff[j] = otot, otot += (int64_t)(L + 2) * prob->models[j]->k;
+    MRBF_TRY(input_fetch(ctx, x_n, d, hxn));
+    MRBF_TRY(input_fetch(ctx, x, d, hx));
+    MRBF_TRY(input_fetch(ctx, lb, d, hlb));
+    MRBF_TRY(input_fetch(ctx, ub, d, hub));
+    MRBF_TRY(input_fetch(ctx, dir, d, hd));
+    MRBF_TRY(fetch_linear_rows(ctx, prob, d, hA, hb));
+    // the stacked rows over the modelled rows' evaluations at x; one block of (L + 2) x k_j objective values per model with an objective row
+    const descent::Offsets con = lay.offsets(1, descent::Slots::CONSTRAINED), objv = lay.offsets(L + 2, descent::Slots::OBJECTIVE);
+    const std::vector<RowRef> rows = stacked_rows(lay, con);
+    const int n_eq = lay.meq, n_in = lay.min;
+    const int64_t jtot = con.jtot, vtot = con.vtot, otot = objv.vtot;
     // ---- device arena: inputs | rows table | Jc | Vc | steps | trial rows | objective values | outputs
     const size_t rows_dbl = (rows.size() * sizeof(RowRef) + sizeof(double) - 1) / sizeof(double);
     const size_t out_cnt = (size_t)d + k + ARMIJO_TAIL;
@@ -467,7 +406,7 @@ extern "C" int32_t mrbf_sd_step(mrbf_ctx *ctx, const mrbf_ps_problem *prob, cons
     const double *dA = base + 5 * d, *db = dA + nlin * d, *ddelta = db + nlin, *domega = ddelta + 1;
     // ---- the modelled constraint rows at x (values + Jacobians; the "intersect" branch reads them)
     for (int j = 0; j < prob->n_models; ++j)
-        if (has_con[j]) MRBF_TRY(eval_model(ctx, prob->models[j], 1, dx, dVc + voff[j], dJc + joff[j], nullptr));
+        if (lay.has_con[j]) MRBF_TRY(eval_model(ctx, prob->models[j], 1, dx, dVc + con.val[j], dJc + con.jac[j], nullptr));
     // ---- sigma and the step sizes
     StepArgs sa;
     sa.d = d, sa.n_eq = n_eq, sa.n_in = n_in, sa.max_loops = L;
@@ -482,7 +421,7 @@ extern "C" int32_t mrbf_sd_step(mrbf_ctx *ctx, const mrbf_ps_problem *prob, cons
     // ---- the L + 2 trial rows and the objective models' values there
     MRBF_TRY(launch_trial(ctx, dxn, 0, ddir, 0, dSteps, d, L, 1, dX));
     for (int j = 0; j < prob->n_models; ++j)
-        if (has_obj[j]) MRBF_TRY(eval_model(ctx, prob->models[j], L + 2, dX, dV + ooff[j], nullptr, nullptr));
+        if (lay.has_obj[j]) MRBF_TRY(eval_model(ctx, prob->models[j], L + 2, dX, dV + objv.val[j], nullptr, nullptr));
     // ---- the Armijo scan
     ArmijoArgs aa;
     aa.d = d, aa.k = k, aa.max_loops = L, aa.strict = opts->strict != 0;
@@ -493,10 +432,7 @@ extern "C" int32_t mrbf_sd_step(mrbf_ctx *ctx, const mrbf_ps_problem *prob, cons
     aa.min_step = opts->min_stepsize >= 0.0 ? opts->min_stepsize : EPS;  // descent.jl:152
     aa.V = dV, aa.X = dX, aa.dir = ddir, aa.steps = dSteps, aa.stepout = dSig;
     aa.xplus = dOut, aa.mxplus = dOut + d, aa.tail = dOut + d + k;
-    for (int l = 0; l < k; ++l) {
-        const int j = obj_model[l];
-        aa.obj[l] = ObjSrc{ooff[j] + obj_col[l], prob->models[j]->k};
-    }
+    fill_objectives(lay, objv, aa.obj);
     MRBF_TRY(launch_armijo(ctx, aa, 1));
     // ---- one read-back: x+, mx+, omega, ||step||, loops, sigma, branch
     std::vector<double> hout(out_cnt);

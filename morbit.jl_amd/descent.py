@@ -140,11 +140,28 @@ def _steepest_descent_direction(x, G, lb, ub, A_eq=None, b_eq=None, A_ineq=None,
     return out(d, _sd_omega(G, w, d), _lib.SD_OK)
 
 
+def _arr(a):
+    """an input of a device call: a device tensor as it is, anything else as a contiguous float64 array"""
+    return a if hasattr(a, "data_ptr") else np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _handles(plans):
+    """the model handles of the plans, start-major (at least one entry, so that the array exists for a container without models)"""
+    hs = [m.model.value if hasattr(m.model, "value") else m.model for p in plans for m in p["models"]]
+    return (ctypes.c_void_p * max(len(hs), 1))(*hs)
+
+
+def _step_options(cfg):
+    """the mrbf_sd_step_options of a SteepestDescentConfig"""
+    return _lib.SdStepOptions(strict=int(bool(cfg.strict_backtracking)), max_loops=int(cfg.max_loops), const_rhs=float(cfg.armijo_const_rhs),
+                              shrink=float(cfg.armijo_const_shrink), min_stepsize=float(cfg.min_stepsize))
+
+
 def _sd_problem(plan, lin):
-    """the mrbf_ps_problem of a container plan (linear constraints lin = (A_eq, b_eq, A_ineq, b_ineq) in scaled variables); the
-    second value keeps the arrays alive"""
+    """the mrbf_ps_problem of a container plan (linear constraints lin = (A_eq, b_eq, A_ineq, b_ineq) in scaled variables), for the
+    steepest-descent calls and for the normal step alike (which ignores the objective rows); the second value keeps the arrays alive"""
     A_eq, b_eq, A_in, b_in = [None if a is None or np.asarray(a).size == 0 else np.ascontiguousarray(a, dtype=np.float64) for a in lin]
-    handles = (ctypes.c_void_p * len(plan["models"]))(*[m.model.value if hasattr(m.model, "value") else m.model for m in plan["models"]])
+    handles = _handles([plan])
     roles = (ctypes.c_int32 * max(len(plan["roles"]), 1))(*plan["roles"])
     prob = _lib.PsProblem(n_models=len(plan["models"]), n_objectives=plan["k"], models=handles, roles=roles,
                           n_lin_eq=0 if b_eq is None else b_eq.size, n_lin_ineq=0 if b_in is None else b_in.size,
@@ -296,16 +313,11 @@ def normal_lp_dual_bound(y, x, lb, ub, A_eq=None, b_eq=None, A_ineq=None, b_ineq
     return float(-y @ b + min([f(a0)] + [f(v) for v in bps]))
 
 
-def _ns_problem(plan, lin):
-    """the mrbf_ps_problem of a container plan for mrbf_normal_step (the objective rows are ignored there)"""
-    return _sd_problem(plan, lin)
-
-
 def normal_step_device(plan, x, lb, ub, delta, lin=None, kappa_delta=1.0, delta_max=np.inf, variable_radius=False, want_duals=False):
     """one mrbf_normal_step call; returns (rc, n, delta, info dict[, duals])"""
     x = np.ascontiguousarray(x, dtype=np.float64)
     lb, ub = np.ascontiguousarray(lb, dtype=np.float64), np.ascontiguousarray(ub, dtype=np.float64)
-    prob, keep = _ns_problem(plan, lin or (None,) * 4)
+    prob, keep = _sd_problem(plan, lin or (None,) * 4)
     m = plan["n_con"] + sum(0 if b is None else b.size for b in (keep[3], keep[5]))
     ctx = plan["models"][0].ctx if plan["models"] else _lib.default_context()
     n = np.empty(x.size)
@@ -546,16 +558,11 @@ def sd_step_device(plan, cfg, x, x_n, delta, lb, ub, omega, d, lin=None, out=Non
     """one mrbf_sd_step call; returns (rc, x_plus, mx_plus, info dict with the branch name under "branch_name").  x, x_n, lb, ub, d
     may be NumPy arrays or device tensors; out = (x_plus, mx_plus) lets the caller pass its own output buffers (host or device)."""
     ctx = plan["models"][0].ctx
-
-    def arr(a):
-        return a if hasattr(a, "data_ptr") else np.ascontiguousarray(a, dtype=np.float64)
-
-    x, x_n, lb, ub, d = arr(x), arr(x_n), arr(lb), arr(ub), arr(d)
+    x, x_n, lb, ub, d = _arr(x), _arr(x_n), _arr(lb), _arr(ub), _arr(d)
     prob, keep = _sd_problem(plan, lin or (None,) * 4)
     n = int(x_n.numel() if hasattr(x_n, "numel") else x_n.size)
     xp, mxp = out if out is not None else (np.empty(n), np.empty(plan["k"]))
-    opts = _lib.SdStepOptions(strict=int(bool(cfg.strict_backtracking)), max_loops=int(cfg.max_loops), const_rhs=float(cfg.armijo_const_rhs),
-                              shrink=float(cfg.armijo_const_shrink), min_stepsize=float(cfg.min_stepsize))
+    opts = _step_options(cfg)
     info = _lib.SdStepInfo()
     rc = ctx.lib.mrbf_sd_step(ctx.h, ctypes.byref(prob), _lib.as_ptr(x), _lib.as_ptr(x_n), float(delta), _lib.as_ptr(lb), _lib.as_ptr(ub),
                               float(omega), _lib.as_ptr(d), ctypes.byref(opts), _lib.as_ptr(xp), _lib.as_ptr(mxp), ctypes.byref(info))
@@ -597,18 +604,13 @@ def sd_iterate_batch_device(plans, cfg, X, X_n, deltas, lb, ub, lin=None, out=No
     lb, ub may be NumPy arrays or device tensors; out = (d, x_plus, mx_plus) lets the caller pass its own output buffers (host or
     device).  Returns (rc, d, x_plus, mx_plus, list of record dicts with "branch_name", event ms)."""
     ctx = plans[0]["models"][0].ctx
-    ns, nm, k = len(plans), len(plans[0]["models"]), plans[0]["k"]
-
-    def arr(a):
-        return a if hasattr(a, "data_ptr") else np.ascontiguousarray(a, dtype=np.float64)
-
-    X, X_n, deltas, lb, ub = arr(X), arr(X_n), arr(deltas), arr(lb), arr(ub)
+    ns, k = len(plans), plans[0]["k"]
+    X, X_n, deltas, lb, ub = _arr(X), _arr(X_n), _arr(deltas), _arr(lb), _arr(ub)
     n = int(lb.numel() if hasattr(lb, "numel") else lb.size)
     prob, keep = _sd_problem(plans[0], lin or (None,) * 4)
-    handles = (ctypes.c_void_p * (ns * nm))(*[m.model.value if hasattr(m.model, "value") else m.model for p in plans for m in p["models"]])
+    handles = _handles(plans)
     dd, xp, mxp = out if out is not None else (np.empty((ns, n)), np.empty((ns, n)), np.empty((ns, k)))
-    opts = _lib.SdStepOptions(strict=int(bool(cfg.strict_backtracking)), max_loops=int(cfg.max_loops), const_rhs=float(cfg.armijo_const_rhs),
-                              shrink=float(cfg.armijo_const_shrink), min_stepsize=float(cfg.min_stepsize))
+    opts = _step_options(cfg)
     recs = (_lib.SdBatchRecord * ns)()
     ms = ctypes.c_float()
     rc = ctx.lib.mrbf_sd_iterate_batch(ctx.h, ns, ctypes.byref(prob), handles, _lib.as_ptr(X), _lib.as_ptr(X_n), _lib.as_ptr(deltas),
@@ -686,16 +688,11 @@ def normal_step_batch_device(plans, X, lb, ub, deltas, lin=None, kappa_delta=1.0
     (rc, n, x_n, list of record dicts, event ms[, duals])."""
     ns, nm = len(plans), len(plans[0]["models"])
     ctx = plans[0]["models"][0].ctx if nm else _lib.default_context()
-
-    def arr(a):
-        return a if hasattr(a, "data_ptr") else np.ascontiguousarray(a, dtype=np.float64)
-
-    X, lb, ub, deltas = arr(X), arr(lb), arr(ub), arr(deltas)
+    X, lb, ub, deltas = _arr(X), _arr(lb), _arr(ub), _arr(deltas)
     d = int(lb.numel() if hasattr(lb, "numel") else lb.size)
-    prob, keep = _ns_problem(plans[0], lin or (None,) * 4)
+    prob, keep = _sd_problem(plans[0], lin or (None,) * 4)
     m = plans[0]["n_con"] + sum(0 if b is None else b.size for b in (keep[3], keep[5]))
-    handles = (ctypes.c_void_p * max(ns * nm, 1))(*[m_.model.value if hasattr(m_.model, "value") else m_.model
-                                                    for p in plans for m_ in p["models"]])
+    handles = _handles(plans)
     n, x_n = out if out is not None else (np.empty((ns, d)), np.empty((ns, d)))
     y = np.empty((ns, max(m, 1))) if want_duals else None
     recs = (_lib.NormalBatchRecord * ns)()
