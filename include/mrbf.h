@@ -618,6 +618,32 @@ int32_t mrbf_normal_step_batch(mrbf_ctx *ctx, int64_t n_starts, const mrbf_ps_pr
                                double delta_max, int32_t variable_radius, double *n_out, double *x_n_out, double *dual_out,
                                mrbf_normal_batch_record *records, float *ms_total);
 
+/* ---- many-start Pascoletti-Serafini step: one call for a batch of starts (ps_solver.hip) ----------------------------------------
+ * get_criticality(::PascolettiSerafiniConfig, ...) (src/descent.jl:512-581) for n_starts independent starts of one problem -- the
+ * reference's Threads.@threads loop over starts (examples/large_scale_benchmarks.jl:102-109) with descent_method = :ps (:70, budgets
+ * :215-219).  For start p, x_trial, mx_trial, r_out and every field of infos[p] except ms_total are, bit for bit, what
+ * mrbf_ps_step_problem returns for start p's container -- the roles table, the linear rows and eq_tol of `shape` with row p of `models`
+ * (n_starts x shape->n_models handles, start-major; shape->models is ignored) -- called with row p of the arrays and the seed seeds[p]:
+ * the kernels are that call's own with the start on a grid dimension, every run keeps its index within its own start and its start's
+ * seed as the generator's key, and every evaluation keeps the query count of the single call it stands for.  The starts share d, the
+ * model count, every model slot's output count, the roles and the linear rows; the number of centres and the kernel parameters may
+ * differ between starts.  x_n, lb_eff, ub_eff, x_trial: n_starts x d (the effective box is a start's own: it follows its trust
+ * region); fx_n, r_or_null, mx_trial, r_out: n_starts x n_objectives; r_or_null == NULL: the ideal-point phase runs for every start;
+ * r_out may be NULL; every one of these arrays may be a host or a device pointer.  infos (n_starts) and seeds_or_null (n_starts; NULL:
+ * opts->seed for every start) are host memory; ms_total may be NULL, and every infos[p].ms_total carries the whole call's event time.
+ * Per generation there is one population sweep per launch group, the optional score launch, the ranking and the breeding for all
+ * starts together; the refinements of all starts advance in lockstep with one host synchronisation per iteration.  The several-
+ * compute-unit ranking is used while all runs of a launch can be resident together (16 compute units per run); beyond that count every
+ * run is ranked by one workgroup.  A batch whose state exceeds 2 GiB is processed in chunks of starts inside the call.
+ * A start's MRBF_PS_CRITICAL or MRBF_PS_FAILURE is that start's status and does not fail the call; a critical start takes no part in
+ * the PS-run phase.  Returns 0; -1 or a code from -3 down for an invalid argument (the table and the linear rows -3, models that do
+ * not share the shape -4); -2 (take mrbf_ps_step_problem, or the reference method, per start) only when mrbf_dispatch_ps_batch refuses
+ * the shape (n_starts < 1 included). */
+int32_t mrbf_ps_step_batch(mrbf_ctx *ctx, int64_t n_starts, const mrbf_ps_problem *shape, const mrbf_model *const *models,
+                           const double *x_n, const double *lb_eff, const double *ub_eff, const double *fx_n, const double *r_or_null,
+                           const mrbf_ps_options *opts, const uint64_t *seeds_or_null, double *x_trial, double *mx_trial, double *r_out,
+                           mrbf_ps_info *infos, float *ms_total);
+
 /* ---- the decision table of the host bindings ---------------------------------------------------------------------------
  * Which implementation a binding (morbit.jl_amd/julia/HipRbf.jl, the Python mirror) takes for one call of Morbit's interface:
  * the device entry point (MRBF_DISPATCH_DEVICE) or Morbit's own method on the same arguments (MRBF_DISPATCH_REFERENCE; Julia:
@@ -661,6 +687,10 @@ int32_t mrbf_normal_step_batch(mrbf_ctx *ctx, int64_t n_starts, const mrbf_ps_pr
  *                            range: d <= 128, q <= n0 <= 256, mc <= 4096, at most 256 sites to accept) is decided inside the call.
  *                            The bindings keep the loop of single calls where the batch does not pay (measured, DESIGN.md section
  *                            14: fewer than 8 starts, or fewer than one start per 32 candidates of the largest start).
+ *   mrbf_dispatch_ps_batch   get_criticality(::PascolettiSerafiniConfig, ...) for n_starts starts in one call (mrbf_ps_step_batch):
+ *                            device iff mrbf_dispatch_ps says so, d <= 256 (the fused evaluation kernels' range) and
+ *                            1 <= n_starts <= 65535 (a grid dimension).  The bindings keep the loop of single calls where the
+ *                            batch does not pay.
  *   mrbf_dispatch_after      the return code rc of a device entry point (MRBF_ENTRY_*) that means "take the reference method
  *                            for this call" (start set without the tail or rank deficient, limits of the device path) rather
  *                            than an error: 1 = fall back, 0 = rc is what it says. */
@@ -668,8 +698,10 @@ enum { MRBF_DISPATCH_REFERENCE = 0, MRBF_DISPATCH_DEVICE = 1 };
 enum { MRBF_FIT_FULL = 0, MRBF_FIT_FROM_ROUND4 = 1 };
 enum { MRBF_ENTRY_ROUND4 = 1, MRBF_ENTRY_FIT_FROM_ROUND4 = 2, MRBF_ENTRY_PS_STEP = 3, MRBF_ENTRY_BACKTRACK = 4, MRBF_ENTRY_AFFINE = 5,
        MRBF_ENTRY_SD = 6, MRBF_ENTRY_NORMAL = 7, MRBF_ENTRY_SD_STEP = 8, MRBF_ENTRY_SD_BATCH = 9, MRBF_ENTRY_AFFINE_BATCH = 10,
-       MRBF_ENTRY_FIT_BATCH = 11, MRBF_ENTRY_NORMAL_BATCH = 12, MRBF_ENTRY_ROUND4_BATCH = 13 };
+       MRBF_ENTRY_FIT_BATCH = 11, MRBF_ENTRY_NORMAL_BATCH = 12, MRBF_ENTRY_ROUND4_BATCH = 13, MRBF_ENTRY_PS_BATCH = 14 };
 int32_t mrbf_dispatch_ps(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
+int32_t mrbf_dispatch_ps_batch(int64_t n_starts, int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints,
+                               int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_sd(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_normal(int32_t d, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_sd_step(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign,

@@ -64,6 +64,7 @@ ENTRY_AFFINE_BATCH = 10
 ENTRY_FIT_BATCH = 11
 ENTRY_NORMAL_BATCH = 12
 ENTRY_ROUND4_BATCH = 13
+ENTRY_PS_BATCH = 14
 SD_OK, SD_NO_OBJECTIVE, SD_INFEASIBLE, SD_GAVE_UP = 0, 1, 2, 3
 NS_OK, NS_INFEASIBLE, NS_GAVE_UP = 0, 1, 2
 SD_BRANCH_DELTA, SD_BRANCH_ONE, SD_BRANCH_INTERSECT = 0, 1, 2
@@ -215,6 +216,10 @@ SIGNATURES = {
                                       ctypes.POINTER(PsInfo)]),
     "mrbf_ps_step_problem": (ctypes.c_int32, [c_vp, ctypes.POINTER(PsProblem), c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(PsOptions),
                                               c_vp, c_vp, c_vp, ctypes.POINTER(PsInfo)]),
+    "mrbf_ps_step_batch": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.POINTER(PsProblem), ctypes.POINTER(ctypes.c_void_p), c_vp, c_vp, c_vp,
+                                            c_vp, c_vp, ctypes.POINTER(PsOptions), ctypes.POINTER(ctypes.c_uint64), c_vp, c_vp, c_vp,
+                                            ctypes.POINTER(PsInfo), c_fp]),
+    "mrbf_dispatch_ps_batch": (ctypes.c_int32, [ctypes.c_int64] + [ctypes.c_int32] * 6),
     "mrbf_sd_direction": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32] + [c_vp] * 8
                           + [ctypes.c_int32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mrbf_sd_criticality": (ctypes.c_int32, [c_vp, ctypes.POINTER(PsProblem), c_vp, c_vp, c_vp, c_vp, ctypes.c_int32, c_vp, c_vp,

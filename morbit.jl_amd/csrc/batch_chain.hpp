@@ -61,13 +61,27 @@ struct Plan {
     size_t n_desc = 0;
 
     // members are added site by site; a group is (site, kernel and parameters, k, dpad, split or unsplit centre range)
-    void add(const mrbf_ctx *ctx, int site, int64_t p, int j, const mrbf_model *M, int64_t mq, bool jac) {
+    // (population: a sweep over a population of the PS solver -- EvalHints::population of the single call it stands for)
+    void add(const mrbf_ctx *ctx, int site, int64_t p, int j, const mrbf_model *M, int64_t mq, bool jac, bool population = false) {
         Member mb;
         mb.site = site, mb.j = j, mb.p = p, mb.M = M, mb.mq = mq, mb.jac = jac;
-        mb.nsplit = eval_nsplit(ctx, mq, (int)((M->n + 63) / 64));
+        mb.nsplit = eval_nsplit(ctx, mq, (int)((M->n + 63) / 64), false, population);
         mb.group = group_of(ctx, site, M, jac, mb.nsplit > 1);
         if (mb.group >= 0) groups[mb.group].members.push_back(mem.size());
         mem.push_back(mb);
+    }
+    // the plan of the members `which` of this plan alone, in that order, every one in the places it has here (its inputs and outputs, and
+    // the scratch carve() gave it): a later phase of a chain that only some starts take part in
+    Plan select(const mrbf_ctx *ctx, const std::vector<size_t> &which) const {
+        Plan out;
+        for (size_t i : which) {
+            Member mb = mem[i];
+            mb.group = out.group_of(ctx, mb.site, mb.M, mb.jac, mb.nsplit > 1);
+            if (mb.group >= 0) out.groups[mb.group].members.push_back(out.mem.size());
+            out.mem.push_back(mb);
+        }
+        out.close();
+        return out;
     }
     // after the last add: the descriptors' places
     void close() {
@@ -110,12 +124,13 @@ struct Plan {
             }
     }
     // the evaluations of one site on the ctx stream: its launch groups, then the members the fused kernels do not take
-    int launch(mrbf_ctx *ctx, int site, double *base, const EvalDesc *hdesc, const EvalDesc *ddesc) const {
+    // (centred: every grouped member's Xq / xsq are filled already -- the PS solver's breeding kernel wrote them)
+    int launch(mrbf_ctx *ctx, int site, double *base, const EvalDesc *hdesc, const EvalDesc *ddesc, bool centred = false) const {
         for (const Group &G : groups) {
             if (G.site != site) continue;
             for (size_t r0 = 0; r0 < G.members.size(); r0 += MAX_GROUP_LAUNCH) {
                 const int cnt = (int)std::min<size_t>(MAX_GROUP_LAUNCH, G.members.size() - r0);
-                MRBF_TRY(eval_fused_batch(ctx, G.kp, G.D, G.k, G.jac, hdesc + G.first + r0, ddesc + G.first + r0, cnt));
+                MRBF_TRY(eval_fused_batch(ctx, G.kp, G.D, G.k, G.jac, hdesc + G.first + r0, ddesc + G.first + r0, cnt, centred));
             }
         }
         for (const Member &S : mem) {

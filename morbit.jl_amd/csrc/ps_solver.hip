@@ -22,6 +22,12 @@
 // run here, not in a host loop.
 // Parity with the reference is the contract of get_criticality (problem solved, budgets, start values, critical / failure
 // short cuts, returned tuple), not NLopt's random trajectory; the returned point is always feasible for the subproblem.
+// Many starts of one problem -- the reference's Threads.@threads loop over starts, examples/large_scale_benchmarks.jl:102-109, with
+// descent_method = :ps -- take the same kernels in ONE call (mrbf_ps_step_batch): every start has its block (ps::Args: runs, box,
+// x_n, m(x_n), r, seed, result blocks) in device memory, the start is a grid dimension, a generation of all starts is one sweep per
+// launch group (batch_chain.hpp), one ranking and one breeding launch, and the refinements advance in lockstep.  The single call is
+// the batch of one (ps_step_many).  DESIGN.md section 15.
+#include "batch_chain.hpp"
 #include "radial.hpp"
 
 namespace mrbf {
@@ -40,11 +46,12 @@ constexpr int RANK_THREADS = 1024;
 constexpr int RS_B = 256, RS_MINLAM = 1024, RS_CUS_PER_RUN = 16;
 constexpr int RS_SYNC = 64;  // sync words per run: [0] arrivals, [1] failure, [2] the run asks for the phases (1) / the counted sort (2), [3] free, [4 + c] chunk c moved something
 
-struct RankWs {  // device work space of the several-compute-unit ranking, run r at offset r * MAXLAM (r * RS_SYNC)
+struct RankWs {  // device work space of the several-compute-unit ranking, run r OF THE LAUNCH (Args::grun0 + the start's own run index) at offset r * MAXLAM (r * RS_SYNC)
     double *f[2];  // ps_rank_wave_kernel's two exchange buffers (64-bit records)
     int *idx;      // the order it found, for the finishing launch
     int *sync;
     int *cnt;      // its keys: per run MAXLAM counts for f, MAXLAM for phi
+    int *sticky;   // one word behind the runs' sync words: a wait of ps_rank_wave_kernel timed out (the host stops using that kernel)
 };
 
 struct Run {  // one (mu, lambda) run; all pointers into device arenas
@@ -62,11 +69,17 @@ struct Run {  // one (mu, lambda) run; all pointers into device arenas
     int *stat;      // [0] evals so far, [1] done, [2] generations run, [3] generation + 1 whose offspring are to be bred
 };
 
+// One start's block.  The blocks of a launch's starts lie side by side in device memory and every kernel takes the start from a grid
+// dimension (mrbf_ps_step_problem: one block; mrbf_ps_step_batch: one per start that takes part in the phase).  A run's index -- the
+// generator's key beside the start's own seed -- is its index within its start.
 struct Args {
     Run runs[MAXRUNS];
     int nruns, d, nobj, rows;
     const double *lb, *ub;   // d
     const double *mx, *r;    // nobj (PS run)
+    const double *xn;        // d: the start point of generation 0
+    double t0;               //    and of t (PS run)
+    int grun0;               // the launch-wide index of this start's first run (RankWs)
     // evaluation batch results: one rows x kf[j] block per grouped model
     const double *F[MAXMODELS];
     int kf[MAXMODELS];
@@ -84,7 +97,6 @@ struct Args {
     int xqD;
     unsigned long long seed;
     double xtol_rel;
-    int gen;
     int dbg;  // Dbg bits (MRBF_PS_DBG, mrbf_debug_ps_rank)
 };
 // Args::dbg: each bit makes a population take a live path that its size or its values would not take by default, so that the tests
@@ -136,7 +148,10 @@ __device__ __forceinline__ int run_of_row(const Args &a, int row) {  // runs are
 
 // generation 0: uniform population in the box, individual 0 = the start point (PS: [t0; x_n]), PS individual 1 = [0; x_n]
 // (feasible for the PS constraints: m(x_n) - m(x_n) - 0 r = 0); step sizes (ub - lb) / sqrt(n)
-__global__ __launch_bounds__(256) void ps_init_kernel(Args a, const double *xn, double t0) {
+__global__ __launch_bounds__(256) void ps_init_kernel(const Args *__restrict__ A) {
+    const Args &a = A[blockIdx.z];
+    const double *xn = a.xn;
+    const double t0 = a.t0;
     const Run &R = a.runs[blockIdx.y];
     const int n = R.nvar;
     const int e = blockIdx.x * 256 + threadIdx.x;
@@ -183,7 +198,7 @@ __device__ __forceinline__ double wave_sum(double v) {
 // work on the row together (the linear constraints' dot products are summed over the lanes); otherwise one thread does the row --
 // problems without linear constraints only (ps_rank_kernel scores its own run that way: a launch per generation less).
 template <bool WAVE>
-__device__ __forceinline__ void score_row(const Args &a, const Run &R, int i, int row, int lane, double &f_out, double &phi_out) {
+__device__ __forceinline__ void score_row(const Args &a, int gen, const Run &R, int i, int row, int lane, double &f_out, double &phi_out) {
     const int m = min(R.lam, R.max_evals - R.stat[0]);  // individuals of this generation inside the budget
     double f = INFINITY, phi = INFINITY;
     if (i < m) {
@@ -191,7 +206,7 @@ __device__ __forceinline__ void score_row(const Args &a, const Run &R, int i, in
             f = a.F[a.obj_model[R.obj]][(size_t)row * a.kf[a.obj_model[R.obj]] + a.obj_col[R.obj]];
             phi = 0.0;
         } else {
-            double t = R.X[a.gen & 1][(size_t)i * R.nvar];
+            double t = R.X[gen & 1][(size_t)i * R.nvar];
             // the subproblem is min_x max_l (m_l(x) - m_l(x_n)) / r_l in disguise: the best t an x admits is known once x has been
             // evaluated, so the individual carries THAT t (pulled a hair towards 0 so that rounding cannot make it infeasible);
             // an x that worsens some objective keeps t = 0 and is ranked by its violation
@@ -200,7 +215,7 @@ __device__ __forceinline__ void score_row(const Args &a, const Run &R, int i, in
                 ts = fmax(ts, (a.F[a.obj_model[l]][(size_t)row * a.kf[a.obj_model[l]] + a.obj_col[l]] - a.mx[l]) / a.r[l]);
             if (ts == ts) {
                 t = ts <= 0.0 ? fmax(ts * (1.0 - 1e-14), -1.0) : 0.0;
-                if (lane == 0) R.X[a.gen & 1][(size_t)i * R.nvar] = t;
+                if (lane == 0) R.X[gen & 1][(size_t)i * R.nvar] = t;
             }
             f = t;
             phi = 0.0;
@@ -240,7 +255,8 @@ __device__ __forceinline__ void score_row(const Args &a, const Run &R, int i, in
 }
 
 // one wave per row of the evaluation batch (problems with linear constraints; without, ps_rank_kernel scores its run itself)
-__global__ __launch_bounds__(256) void ps_score_kernel(Args a) {
+__global__ __launch_bounds__(256) void ps_score_kernel(const Args *__restrict__ A, int gen) {
+    const Args &a = A[blockIdx.y];
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= a.rows) return;
@@ -249,7 +265,7 @@ __global__ __launch_bounds__(256) void ps_score_kernel(Args a) {
     if (R.stat[1]) return;  // finished earlier
     const int i = row - R.off;
     double f, phi;
-    score_row<true>(a, R, i, row, lane, f, phi);
+    score_row<true>(a, gen, R, i, row, lane, f, phi);
     if (lane == 0) {
         R.f[i] = f;
         R.phi[i] = phi;
@@ -524,7 +540,7 @@ __host__ __device__ inline size_t rws_smem_bytes(int lam) {  // f, phi | keys | 
     return 16 * lp + 4 * lp + 16 * lp + 4 * lp + (size_t)64 * rws_pitch(lam) + 64;
 }
 // false: the generation holds a NaN (no rank): the caller's loop ranks it.  On success sidx_out[0 .. lam) is the order.
-__device__ __forceinline__ bool rank_small_waves(const Args &a, const Run &R, int run, double *smem, int *&sidx_out) {
+__device__ __forceinline__ bool rank_small_waves(const Args &a, int gen, const Run &R, int run, double *smem, int *&sidx_out) {
     const int tid = threadIdx.x, NT = blockDim.x, lane = tid & 63, wave = tid >> 6;
     const int lam = R.lam, lp = (lam + 1) & ~1, nw = rws_waves(lam), pitch = rws_pitch(lam), nslots = lam / 2;
     double *sf = smem, *sphi = sf + lp;
@@ -572,7 +588,7 @@ __device__ __forceinline__ bool rank_small_waves(const Args &a, const Run &R, in
             const int g = e / pitch, m = e % pitch;
             unsigned bits = 0;
             if (m < nslots) {
-                unsigned c4[4] = {(unsigned)m, (unsigned)(256 * c + 4 * g), (unsigned)(a.gen * 16 + 1), (unsigned)run};
+                unsigned c4[4] = {(unsigned)m, (unsigned)(256 * c + 4 * g), (unsigned)(gen * 16 + 1), (unsigned)run};
                 philox(c4, (unsigned)a.seed, (unsigned)(a.seed >> 32));
 #pragma unroll
                 for (int q = 0; q < 4; ++q) bits |= (((double)c4[q] + 0.5) * (1.0 / 4294967296.0) < 0.45) ? (1u << q) : 0u;
@@ -628,7 +644,8 @@ __device__ __forceinline__ bool rank_small_waves(const Args &a, const Run &R, in
     return true;
 }
 
-__global__ __launch_bounds__(RANK_THREADS) void ps_rank_kernel(Args a, int mode, RankWs ws) {
+__global__ __launch_bounds__(RANK_THREADS) void ps_rank_kernel(const Args *__restrict__ A, int gen, int mode, RankWs ws) {
+    const Args &a = A[blockIdx.y];
     extern __shared__ double smem[];
     __shared__ double s_red[2 * (RANK_THREADS / 64)];
     __shared__ int s_ired[2 * (RANK_THREADS / 64)];
@@ -637,9 +654,10 @@ __global__ __launch_bounds__(RANK_THREADS) void ps_rank_kernel(Args a, int mode,
     const int NT = (int)blockDim.x;  // 64 .. RANK_THREADS: a small population is ranked by as many waves as it has pairs (a barrier of three waves instead of sixteen)
     const Run &R = a.runs[run];
     if (R.stat[1]) return;
-    int *const sy = ws.sync ? ws.sync + run * RS_SYNC : nullptr;
+    const int grun = a.grun0 + run;
+    int *const sy = ws.sync ? ws.sync + grun * RS_SYNC : nullptr;
     if (mode == 2 && sy[2] == 0) return;  // (this run's generation was finished in mode 1)
-    const int n = R.nvar, lam = R.lam, mu = R.mu, gen = a.gen;
+    const int n = R.nvar, lam = R.lam, mu = R.mu;
     const double *X = R.X[gen & 1];
     const int evals0 = R.stat[0];
     const int m = min(lam, R.max_evals - evals0);
@@ -652,7 +670,7 @@ __global__ __launch_bounds__(RANK_THREADS) void ps_rank_kernel(Args a, int mode,
     if (mode != 2 && a.score_fused) {
         for (int i = tid; i < lam; i += NT) {
             double fi, pi;
-            score_row<false>(a, R, i, R.off + i, 0, fi, pi);
+            score_row<false>(a, gen, R, i, R.off + i, 0, fi, pi);
             R.f[i] = fi;
             R.phi[i] = pi;
         }
@@ -730,7 +748,7 @@ __global__ __launch_bounds__(RANK_THREADS) void ps_rank_kernel(Args a, int mode,
         const int kind = !leave ? 0 : (!plain_sort ? 1 : (!(a.dbg & (DBG_SORT_PAIRS | DBG_NO_SELECT | DBG_SELECT)) ? 2 : 0));
         for (int i = tid; i < RS_SYNC; i += NT) sy[i] = i == 2 ? kind : 0;
         if (kind) {
-            int *cnt = ws.cnt + (size_t)run * 2 * MAXLAM;
+            int *cnt = ws.cnt + (size_t)grun * 2 * MAXLAM;
             for (int i = tid; i < lam; i += NT) cnt[i] = cnt[MAXLAM + i] = 0;
             return;
         }
@@ -738,12 +756,12 @@ __global__ __launch_bounds__(RANK_THREADS) void ps_rank_kernel(Args a, int mode,
     int *sidx;
     if (mode == 2 && sy[2] == 2) {  // the positions found by counting (ps_rank_prep_kernel)
         sidx = (int *)smem;
-        const int *cnt = ws.cnt + (size_t)run * 2 * MAXLAM;
+        const int *cnt = ws.cnt + (size_t)grun * 2 * MAXLAM;
         for (int i = tid; i < lam; i += NT) sidx[cnt[i]] = i;
         __syncthreads();
     } else if (mode == 2 && sy[1] == 0) {  // the order found by ps_rank_wave_kernel
         sidx = (int *)smem;
-        const int *src = ws.idx + (size_t)run * MAXLAM;
+        const int *src = ws.idx + (size_t)grun * MAXLAM;
         for (int i = tid; i < lam; i += NT) sidx[i] = src[i];
         __syncthreads();
     } else if (plain_sort && !(a.dbg & (DBG_SORT_PAIRS | DBG_NO_SELECT)) && NT >= 256 && mu * 4 <= lam && (npow2(lam) >= 8 * NT || (a.dbg & DBG_SELECT)) &&
@@ -794,7 +812,7 @@ __global__ __launch_bounds__(RANK_THREADS) void ps_rank_kernel(Args a, int mode,
         // lam phases of odd-even transposition; a pair is compared by f when both are feasible or with probability 0.45, else by
         // the constraint violation (Runarsson & Yao).  The records themselves are swapped; one Philox call feeds four phases of a
         // pair; one barrier per phase.
-        if (lam < RS_MINLAM && !(a.dbg & DBG_PHASE_PAIRS) && NT >= 64 * rws_waves(lam) && rank_small_waves(a, R, run, smem, sidx)) {
+        if (lam < RS_MINLAM && !(a.dbg & DBG_PHASE_PAIRS) && NT >= 64 * rws_waves(lam) && rank_small_waves(a, gen, R, run, smem, sidx)) {
             // (the order is in sidx: the records stayed in registers -- see rank_small_waves)
         } else {
         double *sf = smem, *sphi = sf + lam;
@@ -929,25 +947,26 @@ __global__ __launch_bounds__(RANK_THREADS) void ps_rank_kernel(Args a, int mode,
 //     generation over.)
 // grid.x = [draw workgroups | counting workgroups]; the counts (ws.cnt: lam objective counts, then lam violation counts per run) are
 // zeroed by ps_rank_kernel (mode 1) when it hands the generation over
-__global__ __launch_bounds__(256) void ps_rank_prep_kernel(Args a, RankWs ws, u64 *draws, size_t per_run, int draw_blocks) {
+__global__ __launch_bounds__(256) void ps_rank_prep_kernel(const Args *__restrict__ A, int gen, RankWs ws, u64 *draws, size_t per_run, int draw_blocks) {
     __shared__ double sf[RW_CNT_T], sp[RW_CNT_T];
-    const int run = blockIdx.y;
+    const Args &a = A[blockIdx.z];
+    const int run = blockIdx.y, grun = a.grun0 + run;
     const Run &R = a.runs[run];
-    const int *sy = ws.sync + run * RS_SYNC;
+    const int *sy = ws.sync + grun * RS_SYNC;
     const int kind = sy[2];  // 1: draws + keys for the transposition phases; 2: the sorted order of a generation without violations
     if (R.stat[1] || kind == 0) return;
     const int lam = R.lam;
     if ((int)blockIdx.x < draw_blocks) {
         if (kind != 1) return;
         const int pitch = rw_pitch(lam), nblk = (lam + RW_H - 1) / RW_H, npair = lam / 2;
-        u64 *out = draws + (size_t)run * per_run;  // [block of RW_H phases][pair slot]: byte g = the block's g-th group of four phases
+        u64 *out = draws + (size_t)grun * per_run;  // [block of RW_H phases][pair slot]: byte g = the block's g-th group of four phases
         for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < (int64_t)nblk * pitch; e += (int64_t)draw_blocks * 256) {
             const int blk = (int)(e / pitch), m = (int)(e % pitch);
             u64 bits = 0;
             if (m < npair) {
 #pragma unroll
                 for (int g = 0; g < RW_H / 4; ++g) {
-                    unsigned c4[4] = {(unsigned)m, (unsigned)(blk * RW_H + 4 * g), (unsigned)(a.gen * 16 + 1), (unsigned)run};
+                    unsigned c4[4] = {(unsigned)m, (unsigned)(blk * RW_H + 4 * g), (unsigned)(gen * 16 + 1), (unsigned)run};
                     philox(c4, (unsigned)a.seed, (unsigned)(a.seed >> 32));
 #pragma unroll
                     for (int q = 0; q < 4; ++q)
@@ -983,16 +1002,17 @@ __global__ __launch_bounds__(256) void ps_rank_prep_kernel(Args a, RankWs ws, u6
         }
     }
     if (i < lam) {
-        int *cnt = ws.cnt + (size_t)run * 2 * MAXLAM;
+        int *cnt = ws.cnt + (size_t)grun * 2 * MAXLAM;
         atomicAdd(cnt + i, cf);
         atomicAdd(cnt + MAXLAM + i, cp);
     }
 }
 
 __device__ __forceinline__ unsigned long long rs_clock() { return __builtin_amdgcn_s_memrealtime(); }  // 100 MHz
-__global__ __launch_bounds__(64) void ps_rank_wave_kernel(Args a, RankWs ws, const u64 *draws, size_t per_run, unsigned epoch) {
-    const int run = blockIdx.y, w = blockIdx.x, lane = threadIdx.x;
-    const Run &R = a.runs[run];
+__global__ __launch_bounds__(64) void ps_rank_wave_kernel(const Args *__restrict__ A, RankWs ws, const u64 *draws, size_t per_run, unsigned epoch) {
+    const Args &a = A[blockIdx.z];
+    const int run = a.grun0 + (int)blockIdx.y, w = blockIdx.x, lane = threadIdx.x;  // (the launch-wide index: this kernel draws nothing)
+    const Run &R = a.runs[blockIdx.y];
     int *const sy = ws.sync + run * RS_SYNC;
     if (R.stat[1] || sy[2] != 1) return;
     const int lam = R.lam, nw = rw_waves(lam);
@@ -1092,7 +1112,7 @@ __global__ __launch_bounds__(64) void ps_rank_wave_kernel(Args a, RankWs ws, con
         if (!ok) {
             if (lane == 0) {
                 __hip_atomic_store(sy + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(ws.sync + RS_SYNC * MAXRUNS, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (sticky: the host stops using this kernel)
+                __hip_atomic_store(ws.sticky, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (sticky: the host stops using this kernel)
             }
             return;
         }
@@ -1100,13 +1120,13 @@ __global__ __launch_bounds__(64) void ps_rank_wave_kernel(Args a, RankWs ws, con
 }
 
 // ---- next generation: one wave per offspring, lanes over the components
-__global__ __launch_bounds__(256) void ps_breed_kernel(Args a) {
+__global__ __launch_bounds__(256) void ps_breed_kernel(const Args *__restrict__ A, int gen) {
+    const Args &a = A[blockIdx.y];
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= a.rows) return;
     const int run = run_of_row(a, row);
     const Run &R = a.runs[run];
-    const int gen = a.gen;
     if (R.stat[3] != gen + 1) return;
     const int n = R.nvar, mu = R.mu, o = row - R.off;
     const double *X = R.X[gen & 1], *S = R.S[gen & 1];
@@ -1221,8 +1241,9 @@ struct RankLaunch {
     unsigned long long *draws = nullptr;
     size_t draws_per_run = 0;
 };
-// once per call, before the first generation (`allow_several`: the caller's say on the several-compute-unit path)
-static int rank_launch_setup(mrbf_ctx *ctx, const ps::Args &a, bool allow_several, RankLaunch &L) {
+// once per phase, before the first generation: `a` is the block of one of the launch's `nstarts` starts (they share the runs' shapes);
+// `allow_several`: the caller's say on the several-compute-unit path
+static int rank_launch_setup(mrbf_ctx *ctx, const ps::Args &a, int nstarts, bool allow_several, RankLaunch &L) {
     using namespace ps;
     // (populations below RS_MINLAM: room and waves for rank_small_waves -- a wave per 96 individuals, a chunk of draws in LDS;
     //  over ALL runs of the launch: a small run beside a large one must find its room too)
@@ -1250,33 +1271,37 @@ static int rank_launch_setup(mrbf_ctx *ctx, const ps::Args &a, bool allow_severa
     RankWs &rw = L.ws;
     double *wsb;
     const size_t per_run = (size_t)MAXLAM * 7 / 2 + RS_SYNC / 2;  // two exchange buffers, the order and the two counts (as doubles: 3 x 1/2), sync words
-    MRBF_TRY(get_buf(ctx, S_PS_RANK, per_run * MAXRUNS + 64 + L.draws_per_run * MAXRUNS, &wsb));
+    const size_t TR = (size_t)std::max(MAXRUNS, nstarts * a.nruns);  // runs of the launch (the residency rule keeps them few: the caller's allow_several)
+    MRBF_TRY(get_buf(ctx, S_PS_RANK, per_run * TR + 64 + L.draws_per_run * TR, &wsb));
     rw.f[0] = wsb;
-    rw.f[1] = rw.f[0] + (size_t)MAXLAM * MAXRUNS;
-    rw.idx = reinterpret_cast<int *>(rw.f[1] + (size_t)MAXLAM * MAXRUNS);
-    rw.cnt = rw.idx + (size_t)MAXLAM * MAXRUNS;
-    rw.sync = rw.cnt + (size_t)2 * MAXLAM * MAXRUNS;
-    L.draws = reinterpret_cast<unsigned long long *>(wsb + per_run * MAXRUNS + 64);
+    rw.f[1] = rw.f[0] + (size_t)MAXLAM * TR;
+    rw.idx = reinterpret_cast<int *>(rw.f[1] + (size_t)MAXLAM * TR);
+    rw.cnt = rw.idx + (size_t)MAXLAM * TR;
+    rw.sync = rw.cnt + (size_t)2 * MAXLAM * TR;
+    rw.sticky = rw.sync + RS_SYNC * TR;
+    L.draws = reinterpret_cast<unsigned long long *>(wsb + per_run * TR + 64);
     // ps_rank_wave_kernel's readers accept any word whose bits 16..31 equal the block's tag.  The arena is not cleared when it is
     // handed out, so a word left by earlier work (a double of another buffer, a record of an earlier call whose launch number
     // agrees modulo 256) could pass as a record and carry an individual index beyond lam into the parents' list.  A zero word has
     // tag 0, which no block uses: both exchange buffers start as zeros at every call.
-    MRBF_HIP(ctx, hipMemsetAsync(rw.f[0], 0, (size_t)2 * MAXLAM * MAXRUNS * sizeof(double), ctx->stream));
-    MRBF_HIP(ctx, hipMemsetAsync(rw.sync + RS_SYNC * MAXRUNS, 0, sizeof(int), ctx->stream));
+    MRBF_HIP(ctx, hipMemsetAsync(rw.f[0], 0, (size_t)2 * MAXLAM * TR * sizeof(double), ctx->stream));
+    MRBF_HIP(ctx, hipMemsetAsync(rw.sticky, 0, sizeof(int), ctx->stream));
     return MRBF_OK;
 }
 // one generation's ranking: ps_rank_kernel alone (mode 0) or, on the several-compute-unit path, its bookkeeping (mode 1), the draws /
 // keys / counted sort on the whole chip, the transposition phases with one wave per part, and the finishing launch (mode 2)
-static void rank_launch(mrbf_ctx *ctx, const ps::Args &a, const RankLaunch &L, bool phases_possible) {
+// (dA: the `nstarts` blocks in device memory, `nruns` runs each)
+static void rank_launch(mrbf_ctx *ctx, const ps::Args *dA, int nstarts, int nruns, int gen, const RankLaunch &L, bool phases_possible) {
     using namespace ps;
-    hipLaunchKernelGGL(ps_rank_kernel, dim3((unsigned)a.nruns), dim3(L.threads), L.shm, ctx->stream, a, L.several ? 1 : 0, L.ws);
+    const unsigned NS = (unsigned)nstarts, NR = (unsigned)nruns;
+    hipLaunchKernelGGL(ps_rank_kernel, dim3(NR, NS), dim3(L.threads), L.shm, ctx->stream, dA, gen, L.several ? 1 : 0, L.ws);
     if (!L.several) return;
     const int draw_blocks = (int)std::min<size_t>(512, (L.draws_per_run + 255) / 256);
     const int count_blocks = ((L.maxlam + RW_CNT_T - 1) / RW_CNT_T) * rw_jsplit(L.maxlam);
-    hipLaunchKernelGGL(ps_rank_prep_kernel, dim3((unsigned)(draw_blocks + count_blocks), (unsigned)a.nruns), dim3(256), 0, ctx->stream, a, L.ws, L.draws, L.draws_per_run, draw_blocks);
+    hipLaunchKernelGGL(ps_rank_prep_kernel, dim3((unsigned)(draw_blocks + count_blocks), NR, NS), dim3(256), 0, ctx->stream, dA, gen, L.ws, L.draws, L.draws_per_run, draw_blocks);
     if (phases_possible)  // (runs without modelled or linear constraints -- ideal-point runs of a box-constrained problem -- never violate anything)
-        hipLaunchKernelGGL(ps_rank_wave_kernel, dim3((unsigned)rw_waves(L.maxlam), (unsigned)a.nruns), dim3(64), 0, ctx->stream, a, L.ws, L.draws, L.draws_per_run, ++ctx->ps_rank_epoch);
-    hipLaunchKernelGGL(ps_rank_kernel, dim3((unsigned)a.nruns), dim3(L.threads), L.shm, ctx->stream, a, 2, L.ws);
+        hipLaunchKernelGGL(ps_rank_wave_kernel, dim3((unsigned)rw_waves(L.maxlam), NR, NS), dim3(64), 0, ctx->stream, dA, L.ws, L.draws, L.draws_per_run, ++ctx->ps_rank_epoch);
+    hipLaunchKernelGGL(ps_rank_kernel, dim3(NR, NS), dim3(L.threads), L.shm, ctx->stream, dA, gen, 2, L.ws);
 }
 
 // all model outputs at m points (row-major m x nftot) and, optionally (m == 1), the objectives' Jacobian rows
@@ -1411,7 +1436,7 @@ static void prox_weights(int k, const std::vector<double> &M, const std::vector<
 // search without improvement.  Every accepted iterate is feasible.  Each iteration costs 1 + NSTEP evaluations.
 // One proximal minimax descent as a state machine: `trials` writes the NSTEP trial points of the next iteration (false: the descent has
 // ended), `consume` takes their values and Jacobians.  Several independent descents (the k ideal-point refinements) advance in
-// lockstep through ONE evaluation per iteration (ps_descend_many) -- a round trip per iteration for all of them instead of one each.
+// lockstep through ONE evaluation per iteration (ps_descend_groups) -- a round trip per iteration for all of them instead of one each.
 struct Descent {
     static constexpr int NSTEP = 12;
     const ps::Problem *P = nullptr;
@@ -1544,62 +1569,614 @@ struct Descent {
     }
 };
 
-// the descents of `ds` in lockstep: one evaluation (values + Jacobians of every active descent's points) per iteration
-static int ps_descend_many(mrbf_ctx *ctx, const ps::Problem &P, std::vector<Descent> &ds) {
-    const int d = P.d;
-    constexpr int NSTEP = Descent::NSTEP;
-    std::vector<double> X, allF, J;
-    std::vector<int> who;
-    for (auto &D : ds) D.start();
-    // the start points (values + Jacobian rows), one call
-    for (size_t i = 0; i < ds.size(); ++i)
-        if (ds[i].wants_start_eval()) who.push_back((int)i);
-    if (!who.empty()) {
-        X.resize(who.size() * (size_t)d);
-        for (size_t w = 0; w < who.size(); ++w) std::copy(ds[who[w]].x.begin(), ds[who[w]].x.end(), X.begin() + w * (size_t)d);
-        MRBF_TRY(ps_eval_points(ctx, P, X.data(), (int)who.size(), allF, &J));
-        for (size_t w = 0; w < who.size(); ++w) ds[who[w]].take_start(&allF[w * (size_t)P.nftot], &J[w * (size_t)P.nobj * d]);
+// one evaluation of the refinement: all model outputs of problem P at m points (and the objectives' Jacobian rows)
+struct EvalReq {
+    const ps::Problem *P;
+    const double *x;
+    int m;
+    std::vector<double> *allF, *Jobj;  // Jobj may be null
+};
+// The evaluations of several starts' points as ONE chain: a packed upload (points, descriptors), one launch group per (kernel and
+// parameters, k, dpad, Jacobians or not, split or unsplit centre range), one download, one synchronisation.  Every member keeps the
+// query count -- hence the split of the centre range and the order of every sum -- of the ps_eval_points call it stands for.  A single
+// request takes that call itself.
+static int ps_eval_points_many(mrbf_ctx *ctx, std::vector<EvalReq> &reqs) {
+    if (reqs.empty()) return 0;
+    if (reqs.size() == 1) return ps_eval_points(ctx, *reqs[0].P, reqs[0].x, reqs[0].m, *reqs[0].allF, reqs[0].Jobj);
+    const size_t R = reqs.size();
+    chain::Plan ev;
+    chain::Arena ar;
+    std::vector<size_t> oX(R), oV(R), oJ(R * ps::MAXMODELS, 0);
+    for (size_t i = 0; i < R; ++i) {
+        const ps::Problem &P = *reqs[i].P;
+        oX[i] = ar.take((size_t)reqs[i].m * P.d);
+        for (int j = 0; j < P.nmodels; ++j) {
+            bool need = false;
+            for (int l = 0; reqs[i].Jobj && l < P.nobj; ++l) need = need || P.obj_model[l] == j;
+            ev.add(ctx, 0, (int64_t)i, j, P.models[j], reqs[i].m, need);
+        }
     }
-    for (;;) {
-        who.clear();
-        for (size_t i = 0; i < ds.size(); ++i)
-            if (ds[i].trials()) who.push_back((int)i);
-        if (who.empty()) break;
-        X.resize(who.size() * (size_t)NSTEP * d);
-        for (size_t w = 0; w < who.size(); ++w) std::copy(ds[who[w]].XT.begin(), ds[who[w]].XT.end(), X.begin() + w * (size_t)NSTEP * d);
-        MRBF_TRY(ps_eval_points(ctx, P, X.data(), (int)who.size() * NSTEP, allF, &J));
-        for (size_t w = 0; w < who.size(); ++w)
-            ds[who[w]].consume(&allF[w * (size_t)NSTEP * P.nftot], &J[w * (size_t)NSTEP * P.nobj * d]);
+    ev.close();
+    const size_t oDesc = ar.take(ev.desc_doubles());
+    const size_t up_cnt = ar.total;
+    for (size_t i = 0; i < R; ++i) oV[i] = ar.take((size_t)reqs[i].m * reqs[i].P->nftot);
+    for (const chain::Member &mb : ev.mem)
+        if (mb.jac) oJ[(size_t)mb.p * ps::MAXMODELS + mb.j] = ar.take((size_t)mb.mq * mb.M->k * mb.M->d);
+    const size_t down_cnt = ar.total - up_cnt;
+    ev.carve(ar);
+    for (chain::Member &mb : ev.mem) {
+        const ps::Problem &P = *reqs[mb.p].P;
+        mb.X = oX[mb.p];
+        mb.vals = oV[mb.p] + (size_t)mb.mq * P.foff[mb.j];  // model j's m x k_j block
+        mb.jacs = oJ[(size_t)mb.p * ps::MAXMODELS + mb.j];
+    }
+    double *base;
+    MRBF_TRY(get_buf(ctx, S_PS_POLISH, ar.total, &base));
+    // (the context's pinned block is free during a PS step: no entry point arms it here)
+    double *pin = (ctx->pin_base && !ctx->pin_armed && (up_cnt + down_cnt) * sizeof(double) <= ((size_t)6 << 20)) ? reinterpret_cast<double *>(ctx->pin_base) : nullptr;
+    std::vector<double> own;
+    if (!pin) own.resize(up_cnt + down_cnt);
+    double *hup = pin ? pin : own.data(), *hdown = hup + up_cnt;
+    for (size_t i = 0; i < R; ++i) std::memcpy(hup + oX[i], reqs[i].x, (size_t)reqs[i].m * reqs[i].P->d * sizeof(double));
+    EvalDesc *hdesc = reinterpret_cast<EvalDesc *>(hup + oDesc);
+    ev.fill(base, hdesc);
+    MRBF_HIP(ctx, hipMemcpyAsync(base, hup, up_cnt * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    MRBF_TRY(ev.launch(ctx, 0, base, hdesc, reinterpret_cast<const EvalDesc *>(base + oDesc)));
+    MRBF_HIP(ctx, hipMemcpyAsync(hdown, base + up_cnt, down_cnt * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    MRBF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t i = 0; i < R; ++i) {
+        const ps::Problem &P = *reqs[i].P;
+        const int m = reqs[i].m, d = P.d;
+        const double *blocks = hdown + (oV[i] - up_cnt);
+        std::vector<double> &allF = *reqs[i].allF;
+        allF.resize((size_t)m * P.nftot);
+        for (int j = 0; j < P.nmodels; ++j) {
+            const int kj = P.models[j]->k;
+            for (int p = 0; p < m; ++p)
+                for (int c = 0; c < kj; ++c) allF[(size_t)p * P.nftot + P.foff[j] + c] = blocks[(size_t)m * P.foff[j] + (size_t)p * kj + c];
+        }
+        if (reqs[i].Jobj) {  // [point][objective][coordinate]
+            std::vector<double> &Jobj = *reqs[i].Jobj;
+            Jobj.resize((size_t)m * P.nobj * d);
+            for (int p = 0; p < m; ++p)
+                for (int l = 0; l < P.nobj; ++l) {
+                    const int j = P.obj_model[l], kj = P.models[j]->k;
+                    const double *Jp = hdown + (oJ[i * ps::MAXMODELS + j] - up_cnt) + (size_t)p * kj * d;  // per point k x d column-major
+                    for (int t = 0; t < d; ++t) Jobj[((size_t)p * P.nobj + l) * d + t] = Jp[(size_t)t * kj + P.obj_col[l]];
+                }
+        }
     }
     return 0;
 }
 
-static int ps_descend(mrbf_ctx *ctx, const ps::Problem &P, const std::vector<double> &lb, const std::vector<double> &ub, const std::vector<int> &objs,
-                      const std::vector<double> &off, const std::vector<double> &scale, bool clamp, int max_evals, double xtol_rel, double &val,
-                      std::vector<double> &x, int *evals_out) {
-    std::vector<Descent> ds(1);
-    Descent &D = ds[0];
-    D.P = &P;
-    D.lb = &lb;
-    D.ub = &ub;
-    D.objs = objs;
-    D.off = off;
-    D.scale = scale;
-    D.clamp = clamp;
-    D.max_evals = max_evals;
-    D.xtol_rel = xtol_rel;
-    D.val = val;
-    D.x = x;
-    MRBF_TRY(ps_descend_many(ctx, P, ds));
-    val = D.val;
-    x = D.x;
-    *evals_out = D.evals;
+// the descents of one start: they advance in lockstep through one evaluation per iteration (12 points per active descent)
+struct DescentGroup {
+    const ps::Problem *P = nullptr;
+    std::vector<Descent> ds;
+    // per iteration
+    std::vector<int> who;
+    std::vector<double> X, allF, J;
+};
+// The descents of all groups in lockstep: per iteration ONE chain of evaluations and one host synchronisation for all groups together
+// (ps_eval_points_many).  A group's own sequence of evaluations -- which descents are active, how many points -- is what it would be alone.
+static int ps_descend_groups(mrbf_ctx *ctx, std::vector<DescentGroup> &gs) {
+    constexpr int NSTEP = Descent::NSTEP;
+    std::vector<EvalReq> reqs;
+    // the start points (values + Jacobian rows)
+    for (DescentGroup &G : gs) {
+        const size_t d = (size_t)G.P->d;
+        for (auto &D : G.ds) D.start();
+        G.who.clear();
+        for (size_t i = 0; i < G.ds.size(); ++i)
+            if (G.ds[i].wants_start_eval()) G.who.push_back((int)i);
+        if (G.who.empty()) continue;
+        G.X.resize(G.who.size() * d);
+        for (size_t w = 0; w < G.who.size(); ++w) std::copy(G.ds[G.who[w]].x.begin(), G.ds[G.who[w]].x.end(), G.X.begin() + w * d);
+        reqs.push_back(EvalReq{G.P, G.X.data(), (int)G.who.size(), &G.allF, &G.J});
+    }
+    MRBF_TRY(ps_eval_points_many(ctx, reqs));
+    for (DescentGroup &G : gs)
+        for (size_t w = 0; w < G.who.size(); ++w)
+            G.ds[G.who[w]].take_start(&G.allF[w * (size_t)G.P->nftot], &G.J[w * (size_t)G.P->nobj * G.P->d]);
+    for (;;) {
+        reqs.clear();
+        for (DescentGroup &G : gs) {
+            const size_t d = (size_t)G.P->d;
+            G.who.clear();
+            for (size_t i = 0; i < G.ds.size(); ++i)
+                if (G.ds[i].trials()) G.who.push_back((int)i);
+            if (G.who.empty()) continue;
+            G.X.resize(G.who.size() * (size_t)NSTEP * d);
+            for (size_t w = 0; w < G.who.size(); ++w) std::copy(G.ds[G.who[w]].XT.begin(), G.ds[G.who[w]].XT.end(), G.X.begin() + w * (size_t)NSTEP * d);
+            reqs.push_back(EvalReq{G.P, G.X.data(), (int)G.who.size() * NSTEP, &G.allF, &G.J});
+        }
+        if (reqs.empty()) break;
+        MRBF_TRY(ps_eval_points_many(ctx, reqs));
+        for (DescentGroup &G : gs)
+            for (size_t w = 0; w < G.who.size(); ++w)
+                G.ds[G.who[w]].consume(&G.allF[w * (size_t)NSTEP * G.P->nftot], &G.J[w * (size_t)NSTEP * G.P->nobj * G.P->d]);
+    }
     return 0;
 }
 
 static int fetch_host(mrbf_ctx *ctx, const double *src, size_t cnt, std::vector<double> &dst) {
     dst.resize(cnt);
     return input_fetch(ctx, src, cnt, dst.data());
+}
+
+// one start of a step: the host view of its container, its inputs and what the step returns for it
+struct PsStart {
+    ps::Problem P;
+    std::vector<double> hlb, hub, hxn, hfx, r, mx, xt;
+    unsigned long long seed = 0;
+    mrbf_ps_info info{};
+    ps::Args a{};  // its block of the current phase
+};
+
+// the function table of a container from the roles table's layout and one start's handles
+static void ps_problem_fill(ps::Problem &P, const descent::Layout &lay, const mrbf_ps_problem *prob, const mrbf_model *const *models) {
+    P.nmodels = prob->n_models;
+    P.nobj = prob->n_objectives;
+    P.d = lay.d;
+    for (int j = 0; j < P.nmodels; ++j) {
+        P.models[j] = models[j];
+        P.foff[j] = P.nftot;
+        P.nftot += lay.k[j];
+    }
+    for (int l = 0; l < P.nobj; ++l) P.obj_model[l] = lay.obj[l].slot, P.obj_col[l] = lay.obj[l].col;
+    for (const descent::Row &r : lay.rows) {
+        P.con_model[P.ncon] = r.slot, P.con_col[P.ncon] = r.col, P.con_eq[P.ncon] = r.eq;
+        ++P.ncon;
+    }
+    P.nlin_eq = prob->n_lin_eq;
+    P.nlin_ineq = prob->n_lin_ineq;
+    P.eq_tol = prob->eq_tol >= 0.0 ? prob->eq_tol : 1e-8;
+}
+
+// doubles of device memory a start of the step takes in the state slot (run state, evaluation batch, results and the sweeps' scratch):
+// mrbf_ps_step_batch sizes its chunks of starts with it.  An estimate of "the state": the ranking's work space (S_PS_RANK: only while
+// at most 16 runs share a launch) and the refinement's chain (S_PS_POLISH: a few points per start) are not counted.
+static size_t ps_start_doubles(const mrbf_ctx *ctx, const mrbf_model *const *models, int nm, int d, int k, int nftot, bool need_ideal) {
+    const size_t lam_ip = 20 * (size_t)(d + 1), lam_ps = 20 * (size_t)(d + 2);
+    const size_t rows = std::max(need_ideal ? k * lam_ip : 0, lam_ps);
+    const size_t state = std::max(need_ideal ? k * (4 * lam_ip * d + 3 * lam_ip) : 0, 4 * lam_ps * (d + 1) + 3 * lam_ps);
+    size_t scratch = 0;  // of the larger sweep: centred queries, their norms and the partial sums of a split centre range, per model slot
+    for (size_t m : {need_ideal ? k * lam_ip : 0, lam_ps}) {
+        size_t s = 0;
+        for (int j = 0; j < nm && m; ++j) {
+            const size_t mpad = (size_t)round_up((int64_t)m, 64);
+            const int nsplit = eval_nsplit(ctx, (int64_t)m, (int)((models[j]->n + 63) / 64), false, true);
+            s += mpad * (models[j]->dpad + 1) + (nsplit > 1 ? (size_t)nsplit * mpad * 2 * 2 : 0) + 64;
+        }
+        scratch = std::max(scratch, s);
+    }
+    return rows * (d + nftot) + state + scratch + 4096;
+}
+
+// The step for the starts of S (mrbf_ps_step_problem: one; mrbf_ps_step_batch: a batch, or a chunk of one): the phases of
+// get_criticality(::PascolettiSerafiniConfig, ...) for all starts together.  Per generation ONE population sweep per launch group,
+// the optional score launch, the ranking and the breeding for every run of every start that takes part in the phase; the refinements
+// advance in lockstep.  Nothing a start computes depends on another start: its block, its runs' indices and its seed are its own, a
+// finished run is inert in every kernel (R.stat[1], R.stat[3] != gen + 1), the evaluations keep the single call's query counts.
+static int ps_step_many(mrbf_ctx *ctx, std::vector<PsStart> &S, bool need_ideal, const mrbf_ps_options *opts, float *ms_out) {
+    using namespace ps;
+    const size_t N = S.size();
+    const bool single = N == 1;  // the one start's evaluations are eval_model's own launches (its arena slots, its pinned block)
+    const Problem &P0 = S[0].P;
+    const int d = P0.d, k = P0.nobj, nm = P0.nmodels, nftot = P0.nftot;
+    hipStream_t st = ctx->stream;
+    hipEvent_t e0 = ctx->ev[0], e1 = ctx->ev[1];
+    MRBF_HIP(ctx, hipEventRecord(e0, st));
+    const int lam_ip = 20 * (d + 1), lam_ps = 20 * (d + 2);
+    const int rows = std::max(need_ideal ? k * lam_ip : 0, lam_ps);
+    // ---- device arena: linear constraints, the starts' blocks, boxes and start points, mx, r, the runs' best records, then per start the
+    // evaluation batch, its results and the runs' state; in a batch also the sweeps' descriptors and scratch (batch_chain.hpp)
+    const size_t nlin = (size_t)P0.nlin_eq + P0.nlin_ineq;
+    const size_t per_ip = (size_t)4 * lam_ip * d + (size_t)3 * lam_ip, per_ps = (size_t)4 * lam_ps * (d + 1) + (size_t)3 * lam_ps;
+    const size_t best_per = std::max((size_t)k * (d + 2), (size_t)d + 3);
+    const size_t args_dbl = (sizeof(Args) + sizeof(double) - 1) / sizeof(double);
+    chain::Arena ar;
+    const size_t oLin = ar.take(nlin * (d + 1)), oArgs = ar.take(N * args_dbl), oBox = ar.take(N * 3 * d), oMx = ar.take(N * k), oR = ar.take(N * k);
+    const size_t oBest = ar.take(N * best_per);
+    const size_t start_cnt = (size_t)rows * d + (size_t)rows * nftot + std::max(need_ideal ? k * per_ip : 0, per_ps);
+    std::vector<size_t> oStart(N);
+    for (size_t p = 0; p < N; ++p) oStart[p] = ar.take(start_cnt);
+    chain::Plan ev_ip, ev_ps_all, ev_ps;
+    size_t oDesc = 0;
+    enum { SITE_IP = 0, SITE_PS = 1 };
+    if (!single) {
+        for (size_t p = 0; p < N && need_ideal; ++p)
+            for (int j = 0; j < nm; ++j) ev_ip.add(ctx, SITE_IP, (int64_t)p, j, S[p].P.models[j], (int64_t)k * lam_ip, false, true);
+        for (size_t p = 0; p < N; ++p)
+            for (int j = 0; j < nm; ++j) ev_ps_all.add(ctx, SITE_PS, (int64_t)p, j, S[p].P.models[j], lam_ps, false, true);
+        ev_ip.close();
+        ev_ps_all.close();
+        oDesc = ar.take(std::max(ev_ip.desc_doubles(), ev_ps_all.desc_doubles()));
+        chain::Arena a0, a1;  // (the two phases follow each other: their scratch shares its place)
+        a0.total = a1.total = ar.total;
+        ev_ip.carve(a0);
+        ev_ps_all.carve(a1);
+        ar.total = std::max(a0.total, a1.total);
+        for (chain::Plan *pl : {&ev_ip, &ev_ps_all})
+            for (chain::Member &mb : pl->mem) {
+                mb.X = oStart[mb.p];
+                mb.vals = oStart[mb.p] + (size_t)rows * d + (size_t)rows * P0.foff[mb.j];
+            }
+    }
+    double *base;
+    int *stat;
+    MRBF_TRY(get_buf(ctx, S_PS_STATE, ar.total + 64, &base));
+    MRBF_TRY(get_buf(ctx, S_PS_STAT, (size_t)4 * std::max((size_t)MAXRUNS, N * (size_t)k), &stat));
+    const Args *dA = reinterpret_cast<const Args *>(base + oArgs);
+    std::vector<double> hbox(N * 3 * d), hmx(N * k), hr(N * k);
+    for (size_t p = 0; p < N; ++p) {
+        std::copy(S[p].hlb.begin(), S[p].hlb.end(), hbox.begin() + p * 3 * d);
+        std::copy(S[p].hub.begin(), S[p].hub.end(), hbox.begin() + p * 3 * d + d);
+        std::copy(S[p].hxn.begin(), S[p].hxn.end(), hbox.begin() + p * 3 * d + 2 * d);
+    }
+    MRBF_HIP(ctx, hipMemcpyAsync(base + oBox, hbox.data(), hbox.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    {
+        double *p = base + oLin;
+        const double *dev[4];
+        const std::vector<double> *src[4] = {&P0.A_eq, &P0.b_eq, &P0.A_ineq, &P0.b_ineq};
+        for (int q = 0; q < 4; ++q) {
+            dev[q] = p;
+            if (!src[q]->empty()) MRBF_HIP(ctx, hipMemcpyAsync(p, src[q]->data(), src[q]->size() * sizeof(double), hipMemcpyHostToDevice, st));
+            p += src[q]->size();
+        }
+        for (PsStart &s : S) s.P.dA_eq = dev[0], s.P.db_eq = dev[1], s.P.dA_ineq = dev[2], s.P.db_ineq = dev[3];
+    }
+    // mx = m(x_n)  (descent.jl:543)
+    std::vector<std::vector<double>> allF(N);
+    std::vector<EvalReq> reqs;
+    for (size_t p = 0; p < N; ++p) reqs.push_back(EvalReq{&S[p].P, S[p].hxn.data(), 1, &allF[p], nullptr});
+    MRBF_TRY(ps_eval_points_many(ctx, reqs));
+    for (size_t p = 0; p < N; ++p) {
+        S[p].mx.resize(k);
+        for (int l = 0; l < k; ++l) S[p].mx[l] = hmx[p * k + l] = S[p].P.objective(allF[p], l);
+    }
+    MRBF_HIP(ctx, hipMemcpyAsync(base + oMx, hmx.data(), hmx.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    const int max_ip = opts->max_ideal_evals < 0 ? 500 * (d + 1) : opts->max_ideal_evals;   // descent.jl:527
+    const int max_ps = opts->max_ps_evals < 0 ? 500 * (d + 1) : opts->max_ps_evals;          // descent.jl:416
+    // The evolution strategy is a global method: in d + 1 >= 25 variables it locates a basin, it does not descend into it (with the
+    // reference's defaults the step at d = 128 stayed at 7 % of what the subproblem allows).  A tenth of every global budget is
+    // therefore kept back for gradient steps from the strategy's best point (ps_descend_groups) -- the evaluations are counted against
+    // the same budget, so the call never evaluates more than the configuration allows.
+    const auto reserve = [&](int budget) { return budget < 20 * 13 ? 0 : budget / 10; };
+    const int res_ip = reserve(max_ip), res_ps = opts->max_polish_evals > 0 ? 0 : reserve(max_ps);
+    const double xtol = opts->xtol_rel > 0.0 ? opts->xtol_rel : 1e-3;                        // descent.jl:379, :485
+    const int dbg = (mrbf_env("MRBF_PS_DBG") ? atoi(mrbf_env("MRBF_PS_DBG")) : 0) & DBG_ALL;
+
+    auto make_run = [&](Run &R, int kind, int obj, int lam, int nvar, int off, int max_evals, double *&p, double *best, int *stp) {
+        R.kind = kind;
+        R.obj = obj;
+        R.lam = lam;
+        R.mu = (lam + 6) / 7;
+        R.nvar = nvar;
+        R.off = off;
+        R.max_evals = max_evals;
+        for (int b = 0; b < 2; ++b) {
+            R.X[b] = p;
+            p += (size_t)lam * nvar;
+            R.S[b] = p;
+            p += (size_t)lam * nvar;
+        }
+        R.best = best;
+        R.f = p;
+        p += lam;
+        R.phi = p;
+        p += lam;
+        R.order = (int *)p;
+        p += lam;
+        R.stat = stp;
+    };
+    // the block of start p (everything but the runs)
+    auto make_args = [&](size_t p) {
+        const Problem &P = S[p].P;
+        Args &a = S[p].a;
+        a = Args{};
+        a.d = d;
+        a.nobj = k;
+        a.lb = base + oBox + p * 3 * d;
+        a.ub = a.lb + d;
+        a.xn = a.ub + d;
+        a.mx = base + oMx + p * k;
+        a.r = base + oR + p * k;
+        a.nmodels = nm;
+        double *fp = base + oStart[p] + (size_t)rows * d;
+        for (int j = 0; j < nm; ++j) {
+            a.F[j] = fp;
+            a.kf[j] = P.models[j]->k;
+            fp += (size_t)rows * P.models[j]->k;
+        }
+        for (int l = 0; l < k; ++l) {
+            a.obj_model[l] = (short)P.obj_model[l];
+            a.obj_col[l] = (short)P.obj_col[l];
+        }
+        a.ncon = P.ncon;
+        for (int c = 0; c < P.ncon; ++c) {
+            a.con_model[c] = (short)P.con_model[c];
+            a.con_col[c] = (short)P.con_col[c];
+            a.con_eq[c] = (short)P.con_eq[c];
+        }
+        a.nlin_eq = P.nlin_eq;
+        a.nlin_ineq = P.nlin_ineq;
+        a.A_eq = P.dA_eq;
+        a.b_eq = P.db_eq;
+        a.A_ineq = P.dA_ineq;
+        a.b_ineq = P.db_ineq;
+        a.eq_tol = P.eq_tol;
+        a.Xeval = base + oStart[p];
+        a.seed = S[p].seed;
+        a.dbg = dbg;
+        a.xtol_rel = xtol;
+    };
+    std::vector<Args> harr;
+    std::vector<EvalDesc> hdesc;
+    // one phase: the runs of the starts `act` (their blocks' runs are set), generation by generation until every run of every start is done
+    auto run_batch = [&](const std::vector<size_t> &act, const chain::Plan *plan, int site, double t0, int max_gens) -> int {
+        const int NA = (int)act.size();
+        const Args &a0 = S[act[0]].a;
+        const int nruns = a0.nruns;
+        int maxel = 0, nrows = 0;
+        for (int q2 = 0; q2 < nruns; ++q2) {
+            nrows = std::max(nrows, a0.runs[q2].off + a0.runs[q2].lam);
+            maxel = std::max(maxel, a0.runs[q2].lam * a0.runs[q2].nvar);
+        }
+        // large populations: the transposition phases with one wave per 64 individuals (MRBF_PS_MULTI=0, read per call: one workgroup per
+        // run as in rounds 3 / 4) while ALL runs of the launch can be resident together -- their waves wait for each other; beyond that
+        // count every run takes the one-workgroup ranking, and the many runs are the parallelism.  A counter wait that times out -- a
+        // device shared with other work -- costs 5 ms; the host sees the sticky failure word with the status words, every eight
+        // generations, and keeps to one workgroup per run from then on.
+        const bool multi_env = !(mrbf_env("MRBF_PS_MULTI") && atoi(mrbf_env("MRBF_PS_MULTI")) == 0);
+        RankLaunch L;
+        MRBF_TRY(rank_launch_setup(ctx, a0, NA, (int64_t)ctx->ncu >= (int64_t)RS_CUS_PER_RUN * nruns * NA && !ctx->ps_multi_off && multi_env, L));
+        bool phases_possible = a0.ncon + a0.nlin_eq + a0.nlin_ineq > 0 || (a0.dbg & DBG_PHASES);
+        for (int q2 = 0; q2 < nruns; ++q2) phases_possible = phases_possible || a0.runs[q2].kind == 1;
+        // one model, fused evaluation: the breeding kernel writes the next population centred and padded into the evaluation's own query
+        // buffers (a launch per generation less; MRBF_PS_FUSEPAD=0: the evaluation's centring launch).  The one start's buffers are the
+        // arena slots the evaluation will ask for -- same size, same pointer; eval_fused checks that and centres itself otherwise; a
+        // batch's are its members' own.
+        const int fusepad = mrbf_env("MRBF_PS_FUSEPAD") ? atoi(mrbf_env("MRBF_PS_FUSEPAD")) : 1;  // (read per call: the tests switch it inside one process)
+        const int score_fused = (a0.nlin_eq + a0.nlin_ineq == 0 && !(mrbf_env("MRBF_PS_FUSESCORE") && atoi(mrbf_env("MRBF_PS_FUSESCORE")) == 0)) ? 1 : 0;
+        bool fused = fusepad && nm == 1 && ctx->eval_impl != 1 && d <= 360;
+        for (int i = 0; i < NA && fused; ++i) {
+            const int dp = S[act[i]].P.models[0]->dpad;
+            fused = dp == 64 || dp == 128 || dp == 256;
+        }
+        double *xq1 = nullptr, *xsq1 = nullptr;
+        if (fused && single) {
+            const int64_t mpad = round_up((int64_t)nrows, 64);
+            MRBF_TRY(get_buf(ctx, S_EVAL_XC, (size_t)mpad * P0.models[0]->dpad, &xq1));
+            MRBF_TRY(get_buf(ctx, S_EVAL_XSQ, (size_t)mpad, &xsq1));
+        }
+        harr.resize(NA);
+        for (int i = 0; i < NA; ++i) {
+            Args &a = S[act[i]].a;
+            a.rows = nrows;
+            a.t0 = t0;
+            a.grun0 = i * nruns;
+            a.score_fused = score_fused;
+            a.Xq = nullptr;
+            a.xsq = nullptr;
+            a.xmean = nullptr;
+            a.xqD = 0;
+            if (fused) {
+                const mrbf_model *M0 = S[act[i]].P.models[0];
+                a.Xq = single ? xq1 : base + plan->mem[(size_t)i * nm].Xq;
+                a.xsq = single ? xsq1 : base + plan->mem[(size_t)i * nm].xsq;
+                a.xmean = M0->mean;
+                a.xqD = M0->dpad;
+            }
+            harr[i] = a;
+        }
+        MRBF_HIP(ctx, hipMemcpyAsync(base + oArgs, harr.data(), (size_t)NA * sizeof(Args), hipMemcpyHostToDevice, st));
+        const EvalDesc *ddesc = reinterpret_cast<const EvalDesc *>(base + oDesc);
+        if (!single) {
+            hdesc.resize(plan->n_desc);
+            plan->fill(base, hdesc.data());
+            if (plan->n_desc) MRBF_HIP(ctx, hipMemcpyAsync(base + oDesc, hdesc.data(), plan->n_desc * sizeof(EvalDesc), hipMemcpyHostToDevice, st));
+        }
+        hipLaunchKernelGGL(ps_init_kernel, dim3((unsigned)((maxel + 255) / 256), (unsigned)nruns, (unsigned)NA), dim3(256), 0, st, dA);
+        std::vector<int> hstat((size_t)4 * nruns * NA);
+        const unsigned wave_blocks = (unsigned)((nrows + 3) / 4);
+        for (int g = 0; g < max_gens; ++g) {
+            // (generation 0 comes from ps_init_kernel: centred by the evaluation's own launch)
+            if (single) {
+                EvalHints hints;
+                hints.population = true;
+                hints.pre_xq = (g > 0 && fused) ? xq1 : nullptr;
+                for (int j = 0; j < nm; ++j) MRBF_TRY(eval_model(ctx, P0.models[j], nrows, a0.Xeval, const_cast<double *>(a0.F[j]), nullptr, nullptr, hints));
+            } else {
+                MRBF_TRY(plan->launch(ctx, site, base, hdesc.data(), ddesc, g > 0 && fused));
+            }
+            if (!score_fused) hipLaunchKernelGGL(ps_score_kernel, dim3(wave_blocks, (unsigned)NA), dim3(256), 0, st, dA, g);
+            rank_launch(ctx, dA, NA, nruns, g, L, phases_possible);
+            hipLaunchKernelGGL(ps_breed_kernel, dim3(wave_blocks, (unsigned)NA), dim3(256), 0, st, dA, g);
+            if ((g & 7) == 7 || g + 1 == max_gens) {  // status words every 8 generations: stop when every run of every start is done
+                MRBF_HIP(ctx, hipMemcpyAsync(hstat.data(), stat, hstat.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+                int hfail = 0;
+                if (L.several) MRBF_HIP(ctx, hipMemcpyAsync(&hfail, L.ws.sticky, sizeof(int), hipMemcpyDeviceToHost, st));
+                MRBF_HIP(ctx, hipStreamSynchronize(st));
+                if (hfail && !(a0.dbg & DBG_GIVE_UP)) {
+                    L.several = false;
+                    ctx->ps_multi_off = 1;
+                }
+                bool all = true;
+                for (size_t q2 = 0; q2 < hstat.size() / 4; ++q2) all = all && hstat[4 * q2 + 1] != 0;
+                if (all) break;
+            }
+        }
+        MRBF_HIP(ctx, hipGetLastError());
+        return 0;
+    };
+
+    for (size_t p = 0; p < N; ++p) make_args(p);
+    std::vector<double> hbest(N * best_per);
+    std::vector<int> hs((size_t)4 * std::max((size_t)MAXRUNS, N * (size_t)k));
+    // ---- local ideal point: the k single-objective minimisations of every start side by side (descent.jl:404-412)
+    if (need_ideal) {
+        std::vector<size_t> act(N);
+        for (size_t p = 0; p < N; ++p) {
+            act[p] = p;
+            Args &a = S[p].a;
+            double *pp = base + oStart[p] + (size_t)rows * d + (size_t)rows * nftot;
+            a.nruns = k;
+            for (int l = 0; l < k; ++l)
+                make_run(a.runs[l], 0, l, lam_ip, d, l * lam_ip, max_ip - res_ip, pp, base + oBest + p * best_per + (size_t)l * (d + 2), stat + 4 * (p * k + l));
+        }
+        MRBF_TRY(run_batch(act, &ev_ip, SITE_IP, 0.0, (max_ip - res_ip + lam_ip - 1) / lam_ip + 1));
+        MRBF_HIP(ctx, hipMemcpyAsync(hbest.data(), base + oBest, hbest.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        MRBF_HIP(ctx, hipMemcpyAsync(hs.data(), stat, (size_t)4 * N * k * sizeof(int), hipMemcpyDeviceToHost, st));
+        MRBF_HIP(ctx, hipStreamSynchronize(st));
+        // r = f(x_n) - ideal point (descent.jl:536-538); a run that never met a feasible point contributes its start value.  The runs'
+        // best points are refined by gradient steps on their objective -- all descents of all starts in lockstep, one chain of
+        // evaluations per iteration
+        std::vector<std::vector<double>> ideal(N, std::vector<double>(k));
+        std::vector<DescentGroup> gs;
+        std::vector<std::pair<size_t, int>> dl;  // (start, objective) of every descent, group by group
+        for (size_t p = 0; p < N; ++p) {
+            DescentGroup G;
+            G.P = &S[p].P;
+            for (int l = 0; l < k; ++l) {
+                const double *b = &hbest[p * best_per + (size_t)l * (d + 2)];
+                const int *h = &hs[4 * (p * k + l)];
+                const bool found = b[d + 1] == 0.0 && std::isfinite(b[d]);
+                ideal[p][l] = found ? b[d] : S[p].mx[l];
+                S[p].info.evals_ideal += h[0];
+                S[p].info.generations += h[2];
+                const int left = max_ip - h[0];
+                if (found && left >= 13) {
+                    G.ds.emplace_back();
+                    Descent &D = G.ds.back();
+                    D.P = &S[p].P;
+                    D.lb = &S[p].hlb;
+                    D.ub = &S[p].hub;
+                    D.objs = std::vector<int>{l};
+                    D.off = std::vector<double>{0.0};
+                    D.scale = std::vector<double>{1.0};
+                    D.clamp = false;
+                    D.max_evals = left;
+                    D.xtol_rel = xtol;
+                    D.val = ideal[p][l];
+                    D.x.assign(b, b + d);
+                    dl.emplace_back(p, l);
+                }
+            }
+            if (!G.ds.empty()) gs.push_back(std::move(G));
+        }
+        MRBF_TRY(ps_descend_groups(ctx, gs));
+        {
+            size_t at = 0;
+            for (DescentGroup &G : gs)
+                for (Descent &D : G.ds) {
+                    ideal[dl[at].first][dl[at].second] = D.val;
+                    S[dl[at].first].info.evals_ideal += D.evals;
+                    ++at;
+                }
+        }
+        for (size_t p = 0; p < N; ++p)
+            for (int l = 0; l < k; ++l) S[p].r[l] = S[p].hfx[l] - ideal[p][l];
+    }
+    // ---- the Pascoletti-Serafini runs of the starts that are not critical
+    std::vector<size_t> act;
+    for (size_t p = 0; p < N; ++p) {
+        PsStart &s = S[p];
+        s.info.tau = 0.0;
+        s.xt = s.hxn;
+        bool critical = false;
+        for (int l = 0; l < k; ++l) {
+            critical = critical || !(s.r[l] > 0.0);
+            hr[p * k + l] = s.r[l];
+        }
+        if (critical)
+            s.info.status = MRBF_PS_CRITICAL;  // any(r .<= 0): omega = 0, the point itself (descent.jl:546-549)
+        else
+            act.push_back(p);
+    }
+    if (!act.empty()) {
+        MRBF_HIP(ctx, hipMemcpyAsync(base + oR, hr.data(), hr.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        for (size_t i = 0; i < act.size(); ++i) {
+            const size_t p = act[i];
+            Args &a = S[p].a;
+            double *pp = base + oStart[p] + (size_t)rows * d + (size_t)rows * nftot;
+            a.nruns = 1;
+            make_run(a.runs[0], 1, 0, lam_ps, d + 1, 0, max_ps - res_ps, pp, base + oBest + p * best_per, stat + 4 * i);
+        }
+        if (!single) {  // the sweep of the starts that take part, every member where the plan of all starts has it
+            std::vector<size_t> which;
+            for (size_t p : act)
+                for (int j = 0; j < nm; ++j) which.push_back(p * nm + j);
+            ev_ps = ev_ps_all.select(ctx, which);
+        }
+        MRBF_TRY(run_batch(act, &ev_ps, SITE_PS, opts->t0, (max_ps - res_ps + lam_ps - 1) / lam_ps + 1));
+        MRBF_HIP(ctx, hipMemcpyAsync(hbest.data(), base + oBest, hbest.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        MRBF_HIP(ctx, hipMemcpyAsync(hs.data(), stat, (size_t)4 * act.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+        MRBF_HIP(ctx, hipStreamSynchronize(st));
+        std::vector<DescentGroup> gs;
+        std::vector<size_t> gp;
+        const bool own = opts->max_polish_evals > 0;
+        for (size_t i = 0; i < act.size(); ++i) {
+            PsStart &s = S[act[i]];
+            const double *best = &hbest[act[i] * best_per];
+            const int *h = &hs[4 * i];
+            s.info.evals_ps = h[0];
+            s.info.generations += h[2];
+            const double bf = best[d + 1], bphi = best[d + 2];
+            if (!(bphi == 0.0) || !std::isfinite(bf)) {
+                s.info.status = MRBF_PS_FAILURE;  // descent.jl:571-572
+                continue;
+            }
+            s.info.tau = bf;
+            s.info.status = MRBF_PS_OK;
+            for (int t = 0; t < d; ++t) s.xt[t] = best[1 + t];
+            // the polish the configuration asks for (its own budget, descent.jl:423-429); without one, the part of the global budget
+            // that was kept back or left over
+            const int pbudget = own ? opts->max_polish_evals : max_ps - h[0];
+            if (pbudget < 13) continue;
+            DescentGroup G;
+            G.P = &s.P;
+            G.ds.emplace_back();
+            Descent &D = G.ds.back();
+            D.P = &s.P;
+            D.lb = &s.hlb;
+            D.ub = &s.hub;
+            D.objs.resize(k);
+            for (int l = 0; l < k; ++l) D.objs[l] = l;
+            D.off = s.mx;
+            D.scale = s.r;
+            D.clamp = true;
+            D.max_evals = pbudget;
+            D.xtol_rel = xtol;
+            D.val = s.info.tau;
+            D.x = s.xt;
+            gs.push_back(std::move(G));
+            gp.push_back(act[i]);
+        }
+        MRBF_TRY(ps_descend_groups(ctx, gs));
+        for (size_t g = 0; g < gs.size(); ++g) {
+            PsStart &s = S[gp[g]];
+            const Descent &D = gs[g].ds[0];
+            s.info.tau = D.val;
+            s.xt = D.x;
+            if (own)
+                s.info.evals_polish = D.evals;
+            else
+                s.info.evals_ps += D.evals;
+        }
+    }
+    // mx_trial = m(x_trial)
+    reqs.clear();
+    for (size_t p = 0; p < N; ++p)
+        if (S[p].info.status == MRBF_PS_OK) reqs.push_back(EvalReq{&S[p].P, S[p].xt.data(), 1, &allF[p], nullptr});
+    MRBF_TRY(ps_eval_points_many(ctx, reqs));
+    for (size_t p = 0; p < N; ++p)
+        if (S[p].info.status == MRBF_PS_OK)
+            for (int l = 0; l < k; ++l) S[p].mx[l] = S[p].P.objective(allF[p], l);
+    MRBF_HIP(ctx, hipEventRecord(e1, st));
+    MRBF_HIP(ctx, hipStreamSynchronize(st));
+    MRBF_HIP(ctx, hipEventElapsedTime(ms_out, e0, e1));
+    return MRBF_OK;
 }
 
 }  // namespace mrbf
@@ -1626,324 +2203,138 @@ extern "C" int32_t mrbf_ps_step_problem(mrbf_ctx *ctx, const mrbf_ps_problem *pr
     // ---- the function table
     if (prob->n_models < 1 || prob->n_models > MAXMODELS || !prob->models || !prob->roles)
         return fail(ctx, -2, "mrbf_ps_step: 1..%d grouped models with a roles table are required", MAXMODELS);
-    Problem P;
-    P.nmodels = prob->n_models;
-    P.nobj = prob->n_objectives;
-    if (P.nobj < 1 || P.nobj > MAXOBJ) return fail(ctx, -2, "mrbf_ps_step: %d objectives (device path: 1..%d)", P.nobj, MAXOBJ);
+    if (prob->n_objectives < 1 || prob->n_objectives > MAXOBJ) return fail(ctx, -2, "mrbf_ps_step: %d objectives (device path: 1..%d)", prob->n_objectives, MAXOBJ);
     std::vector<descent::SlotShape> slots;
     descent::Layout lay;
     if (descent::Defect D = descent::read(descent_shape(prob, prob->models, 1, slots), {true, descent::Centres::UNCHECKED}, lay))
         return fail(ctx, -2, "mrbf_ps_step: %s", D.msg.c_str());
     if (lay.n_nl > MAXCON) return fail(ctx, -2, "mrbf_ps_step: more than %d modelled constraints", MAXCON);
-    P.d = lay.d;
-    for (int j = 0; j < P.nmodels; ++j) {
-        P.models[j] = prob->models[j];
-        P.foff[j] = P.nftot;
-        P.nftot += lay.k[j];
-    }
-    for (int l = 0; l < P.nobj; ++l) P.obj_model[l] = lay.obj[l].slot, P.obj_col[l] = lay.obj[l].col;
-    for (const descent::Row &r : lay.rows) {
-        P.con_model[P.ncon] = r.slot, P.con_col[P.ncon] = r.col, P.con_eq[P.ncon] = r.eq;
-        ++P.ncon;
-    }
+    std::vector<PsStart> S(1);
+    PsStart &s = S[0];
+    Problem &P = s.P;
+    ps_problem_fill(P, lay, prob, prob->models);
     const int d = P.d, k = P.nobj;
     if (mrbf_dispatch_ps(d, k, P.nmodels, P.ncon, prob->n_lin_eq + prob->n_lin_ineq, 0) != MRBF_DISPATCH_DEVICE)
         return fail(ctx, -2, "mrbf_ps_step: d = %d / k = %d / %d constraints outside the device path (ask mrbf_dispatch_ps first)", d, k, P.ncon);
-    P.nlin_eq = prob->n_lin_eq;
-    P.nlin_ineq = prob->n_lin_ineq;
-    P.eq_tol = prob->eq_tol >= 0.0 ? prob->eq_tol : 1e-8;
     // box, start point, direction: host copies first (the pointers may be host or device memory)
-    std::vector<double> hlb, hub, hxn, hfx, r(k), mx(k), allF;
-    MRBF_TRY(fetch_host(ctx, lb_eff, d, hlb));
-    MRBF_TRY(fetch_host(ctx, ub_eff, d, hub));
-    MRBF_TRY(fetch_host(ctx, x_n, d, hxn));
-    if (fx_n) MRBF_TRY(fetch_host(ctx, fx_n, k, hfx));
-    if (r_or_null) MRBF_TRY(fetch_host(ctx, r_or_null, k, r));
+    s.r.assign(k, 0.0);
+    MRBF_TRY(fetch_host(ctx, lb_eff, d, s.hlb));
+    MRBF_TRY(fetch_host(ctx, ub_eff, d, s.hub));
+    MRBF_TRY(fetch_host(ctx, x_n, d, s.hxn));
+    if (fx_n) MRBF_TRY(fetch_host(ctx, fx_n, k, s.hfx));
+    if (r_or_null) MRBF_TRY(fetch_host(ctx, r_or_null, k, s.r));
     for (int t = 0; t < d; ++t)
-        if (!(hlb[t] <= hub[t])) return fail(ctx, -4, "lb_eff[%d] > ub_eff[%d]", t, t);
+        if (!(s.hlb[t] <= s.hub[t])) return fail(ctx, -4, "lb_eff[%d] > ub_eff[%d]", t, t);
     MRBF_TRY(fetch_host(ctx, prob->A_eq, (size_t)P.nlin_eq * d, P.A_eq));
     MRBF_TRY(fetch_host(ctx, prob->b_eq, (size_t)P.nlin_eq, P.b_eq));
     MRBF_TRY(fetch_host(ctx, prob->A_ineq, (size_t)P.nlin_ineq * d, P.A_ineq));
     MRBF_TRY(fetch_host(ctx, prob->b_ineq, (size_t)P.nlin_ineq, P.b_ineq));
+    s.seed = opts->seed;
+    float ms = 0.f;
+    MRBF_TRY(ps_step_many(ctx, S, r_or_null == nullptr, opts, &ms));
+    *info = s.info;
+    info->ms_total = ms;
+    MRBF_TRY(output_put(ctx, x_trial, s.xt.data(), d));
+    MRBF_TRY(output_put(ctx, mx_trial, s.mx.data(), k));
+    if (r_out) MRBF_TRY(output_put(ctx, r_out, s.r.data(), k));
+    return MRBF_OK;
+}
 
-    hipEvent_t e0 = ctx->ev[0], e1 = ctx->ev[1];
-    MRBF_HIP(ctx, hipEventRecord(e0, ctx->stream));
-    const bool need_ideal = r_or_null == nullptr;
-    const int lam_ip = 20 * (d + 1), lam_ps = 20 * (d + 2);
-    const int rows = std::max(need_ideal ? k * lam_ip : 0, lam_ps);
-    // device arena: box, x_n, mx, r, linear constraints, evaluation batch, results, per-run state
-    const size_t nlin = (size_t)P.nlin_eq + P.nlin_ineq;
-    const size_t per_ip = (size_t)4 * lam_ip * d + d + 2 + (size_t)3 * lam_ip, per_ps = (size_t)4 * lam_ps * (d + 1) + d + 3 + (size_t)3 * lam_ps;
-    const size_t cnt = (size_t)3 * d + 2 * k + nlin * (d + 1) + (size_t)rows * d + (size_t)rows * P.nftot + std::max(k * per_ip, per_ps) + 64;
-    double *base;
-    int *stat;
-    MRBF_TRY(get_buf(ctx, S_PS_STATE, cnt, &base));
-    MRBF_TRY(get_buf(ctx, S_PS_STAT, (size_t)4 * MAXRUNS, &stat));
-    double *dlb = base, *dub = dlb + d, *dxn = dub + d, *dmx = dxn + d, *dr = dmx + k, *dlin = dr + k;
-    double *Xeval = dlin + nlin * (d + 1), *F = Xeval + (size_t)rows * d;
-    double *pool = F + (size_t)rows * P.nftot;
-    MRBF_HIP(ctx, hipMemcpyAsync(dlb, hlb.data(), d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    MRBF_HIP(ctx, hipMemcpyAsync(dub, hub.data(), d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    MRBF_HIP(ctx, hipMemcpyAsync(dxn, hxn.data(), d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    {
-        double *p = dlin;
-        auto up = [&](const std::vector<double> &v, const double **dev) -> int {
-            *dev = p;
-            if (!v.empty()) MRBF_HIP(ctx, hipMemcpyAsync(p, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-            p += v.size();
-            return 0;
-        };
-        MRBF_TRY(up(P.A_eq, &P.dA_eq));
-        MRBF_TRY(up(P.b_eq, &P.db_eq));
-        MRBF_TRY(up(P.A_ineq, &P.dA_ineq));
-        MRBF_TRY(up(P.b_ineq, &P.db_ineq));
-    }
-    // mx = m(x_n)  (descent.jl:543)
-    MRBF_TRY(ps_eval_point(ctx, P, hxn.data(), allF, nullptr));
-    for (int l = 0; l < k; ++l) mx[l] = P.objective(allF, l);
-    MRBF_HIP(ctx, hipMemcpyAsync(dmx, mx.data(), k * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    const int max_ip = opts->max_ideal_evals < 0 ? 500 * (d + 1) : opts->max_ideal_evals;   // descent.jl:527
-    const int max_ps = opts->max_ps_evals < 0 ? 500 * (d + 1) : opts->max_ps_evals;          // descent.jl:416
-    // The evolution strategy is a global method: in d + 1 >= 25 variables it locates a basin, it does not descend into it (with the
-    // reference's defaults the step at d = 128 stayed at 7 % of what the subproblem allows).  A tenth of every global budget is
-    // therefore kept back for gradient steps from the strategy's best point (ps_descend) -- the evaluations are counted against the
-    // same budget, so the call never evaluates more than the configuration allows.
-    const auto reserve = [&](int budget) { return budget < 20 * 13 ? 0 : budget / 10; };
-    const int res_ip = reserve(max_ip), res_ps = opts->max_polish_evals > 0 ? 0 : reserve(max_ps);
-    const double xtol = opts->xtol_rel > 0.0 ? opts->xtol_rel : 1e-3;                        // descent.jl:379, :485
-
-    auto make_run = [&](Run &R, int kind, int obj, int lam, int nvar, int off, int max_evals, double *&p, int *st) {
-        R.kind = kind;
-        R.obj = obj;
-        R.lam = lam;
-        R.mu = (lam + 6) / 7;
-        R.nvar = nvar;
-        R.off = off;
-        R.max_evals = max_evals;
-        for (int b = 0; b < 2; ++b) {
-            R.X[b] = p;
-            p += (size_t)lam * nvar;
-            R.S[b] = p;
-            p += (size_t)lam * nvar;
+// ---- many-start Pascoletti-Serafini step: get_criticality(::PascolettiSerafiniConfig, ...) (Morbit.jl src/descent.jl:512-581) for
+// n_starts independent starts of one problem in one call -- the reference's Threads.@threads loop over starts
+// (examples/large_scale_benchmarks.jl:102-109) with descent_method = :ps.  For start p the outputs are, bit for bit, those of
+// mrbf_ps_step_problem on start p's container: the step above is that call's own, with the start on a grid dimension.
+extern "C" int32_t mrbf_ps_step_batch(mrbf_ctx *ctx, int64_t n_starts, const mrbf_ps_problem *shape, const mrbf_model *const *models,
+                                      const double *x_n, const double *lb_eff, const double *ub_eff, const double *fx_n, const double *r_or_null,
+                                      const mrbf_ps_options *opts, const uint64_t *seeds_or_null, double *x_trial, double *mx_trial, double *r_out,
+                                      mrbf_ps_info *infos, float *ms_total) {
+    if (!ctx) return -1;
+    if (ms_total) *ms_total = 0.f;
+    if (!shape) return fail(ctx, -3, "shape is NULL");
+    if (!models) return fail(ctx, -4, "models is NULL");
+    if (!x_n) return fail(ctx, -5, "x_n is NULL");
+    if (!lb_eff) return fail(ctx, -6, "lb_eff is NULL");
+    if (!ub_eff) return fail(ctx, -7, "ub_eff is NULL");
+    if (!r_or_null && !fx_n) return fail(ctx, -8, "fx_n is NULL but no direction was given");
+    if (!opts) return fail(ctx, -10, "opts is NULL");
+    if (opts->t0 < -1.0 || opts->t0 > 0.0) return fail(ctx, -10, "opts.t0 must lie in [-1, 0]");
+    if (!x_trial) return fail(ctx, -12, "x_trial is NULL");
+    if (!mx_trial) return fail(ctx, -13, "mx_trial is NULL");
+    if (!infos) return fail(ctx, -15, "infos is NULL");
+    using namespace ps;
+    if (shape->n_models < 1 || !shape->roles) return fail(ctx, -3, "mrbf_ps_step_batch: grouped models with a roles table are required");
+    if (n_starts < 1) return fail(ctx, -2, "mrbf_ps_step_batch: %lld starts (ask mrbf_dispatch_ps_batch first)", (long long)n_starts);
+    const int64_t N = n_starts;
+    const int k = shape->n_objectives, nm = shape->n_models;
+    std::vector<descent::SlotShape> slots;
+    descent::Shape sh = descent_shape(shape, models, N, slots);
+    sh.batch = true;
+    descent::Layout lay;
+    if (descent::Defect D = descent::read(sh, {true, descent::Centres::EVERY_SLOT}, lay))
+        return fail(ctx, D.cls == descent::Defect::MODELS ? -4 : -3, "mrbf_ps_step_batch: %s", D.msg.c_str());
+    const int d = lay.d, n_lin = shape->n_lin_eq + shape->n_lin_ineq;
+    if (mrbf_dispatch_ps_batch(N, d, k, nm, lay.n_nl, n_lin, 0) != MRBF_DISPATCH_DEVICE)
+        return fail(ctx, -2, "mrbf_ps_step_batch: %lld starts / d = %d / k = %d / %d constraints outside the device path (ask mrbf_dispatch_ps_batch first)",
+                    (long long)N, d, k, lay.n_nl + n_lin);
+    (void)hipSetDevice(ctx->device);
+    const size_t SN = (size_t)N;
+    std::memset(infos, 0, SN * sizeof(*infos));
+    // the inputs: host copies (the pointers may be host or device memory)
+    std::vector<double> hx, hlb, hub, hfx, hr, A_eq, b_eq, A_ineq, b_ineq;
+    MRBF_TRY(fetch_host(ctx, x_n, SN * d, hx));
+    MRBF_TRY(fetch_host(ctx, lb_eff, SN * d, hlb));
+    MRBF_TRY(fetch_host(ctx, ub_eff, SN * d, hub));
+    if (fx_n) MRBF_TRY(fetch_host(ctx, fx_n, SN * k, hfx));
+    if (r_or_null) MRBF_TRY(fetch_host(ctx, r_or_null, SN * k, hr));
+    for (size_t t = 0; t < SN * d; ++t)
+        if (!(hlb[t] <= hub[t])) return fail(ctx, -6, "start %lld: lb_eff[%d] > ub_eff[%d]", (long long)(t / d), (int)(t % d), (int)(t % d));
+    MRBF_TRY(fetch_host(ctx, shape->A_eq, (size_t)shape->n_lin_eq * d, A_eq));
+    MRBF_TRY(fetch_host(ctx, shape->b_eq, (size_t)shape->n_lin_eq, b_eq));
+    MRBF_TRY(fetch_host(ctx, shape->A_ineq, (size_t)shape->n_lin_ineq * d, A_ineq));
+    MRBF_TRY(fetch_host(ctx, shape->b_ineq, (size_t)shape->n_lin_ineq, b_ineq));
+    int nftot = 0;
+    for (int j = 0; j < nm; ++j) nftot += lay.k[j];
+    // a batch whose state exceeds 2 GiB is processed in chunks of starts
+    size_t per_start = 0;
+    for (size_t p = 0; p < SN; ++p)
+        per_start = std::max(per_start, ps_start_doubles(ctx, models + p * nm, nm, d, k, nftot, r_or_null == nullptr) * sizeof(double));
+    // (MRBF_PS_CHUNK_KB: another limit, so that a test can split a small batch)
+    const size_t limit = mrbf_env("MRBF_PS_CHUNK_KB") ? (size_t)std::max(1, atoi(mrbf_env("MRBF_PS_CHUNK_KB"))) << 10 : (size_t)2 << 30;
+    const size_t chunk = std::max<size_t>(1, limit / per_start);
+    std::vector<double> ox(SN * d), omx(SN * k), orr(SN * k);
+    float ms_sum = 0.f;
+    for (size_t p0 = 0; p0 < SN; p0 += chunk) {
+        const size_t n = std::min(chunk, SN - p0);
+        std::vector<PsStart> S(n);
+        for (size_t i = 0; i < n; ++i) {
+            const size_t p = p0 + i;
+            PsStart &s = S[i];
+            ps_problem_fill(s.P, lay, shape, models + p * nm);
+            s.P.A_eq = A_eq, s.P.b_eq = b_eq, s.P.A_ineq = A_ineq, s.P.b_ineq = b_ineq;
+            s.hlb.assign(hlb.begin() + p * d, hlb.begin() + (p + 1) * d);
+            s.hub.assign(hub.begin() + p * d, hub.begin() + (p + 1) * d);
+            s.hxn.assign(hx.begin() + p * d, hx.begin() + (p + 1) * d);
+            if (fx_n) s.hfx.assign(hfx.begin() + p * k, hfx.begin() + (p + 1) * k);
+            s.r.assign(k, 0.0);
+            if (r_or_null) s.r.assign(hr.begin() + p * k, hr.begin() + (p + 1) * k);
+            s.seed = seeds_or_null ? seeds_or_null[p] : opts->seed;
         }
-        R.best = p;
-        p += nvar + 2;
-        R.f = p;
-        p += lam;
-        R.phi = p;
-        p += lam;
-        R.order = (int *)p;
-        p += lam;
-        R.stat = st;
-    };
-    auto run_batch = [&](Args &a, const double *start, double t0, int max_gens) -> int {
-        int maxel = 0;
-        a.rows = 0;
-        for (int q2 = 0; q2 < a.nruns; ++q2) {
-            a.rows = std::max(a.rows, a.runs[q2].off + a.runs[q2].lam);
-            maxel = std::max(maxel, a.runs[q2].lam * a.runs[q2].nvar);
-        }
-        // large populations: the transposition phases with one wave per 64 individuals (MRBF_PS_MULTI=0, read per call: one workgroup per
-        // run as in rounds 3 / 4).  A counter wait that times out -- the waves of a run not resident together: a device shared with other
-        // work -- costs 5 ms; the host sees the sticky failure word with the status words, every eight generations, and keeps to one
-        // workgroup per run from then on.
-        const bool multi_env = !(mrbf_env("MRBF_PS_MULTI") && atoi(mrbf_env("MRBF_PS_MULTI")) == 0);
-        RankLaunch L;
-        MRBF_TRY(rank_launch_setup(ctx, a, ctx->ncu >= RS_CUS_PER_RUN * a.nruns && !ctx->ps_multi_off && multi_env, L));
-        bool phases_possible = a.ncon + a.nlin_eq + a.nlin_ineq > 0 || (a.dbg & DBG_PHASES);
-        for (int q2 = 0; q2 < a.nruns; ++q2) phases_possible = phases_possible || a.runs[q2].kind == 1;
-        // one model, fused evaluation: the breeding kernel writes the next population centred and padded into the evaluation's own query
-        // buffers (a launch per generation less; MRBF_PS_FUSEPAD=0: the evaluation's centring launch).  The buffers are the arena slots the
-        // evaluation will ask for -- same size, same pointer; eval_fused checks that and centres itself otherwise.
-        a.Xq = nullptr;
-        a.xsq = nullptr;
-        a.xmean = nullptr;
-        a.xqD = 0;
-        a.score_fused = (a.nlin_eq + a.nlin_ineq == 0 && !(mrbf_env("MRBF_PS_FUSESCORE") && atoi(mrbf_env("MRBF_PS_FUSESCORE")) == 0)) ? 1 : 0;
-        {
-            const int fusepad = mrbf_env("MRBF_PS_FUSEPAD") ? atoi(mrbf_env("MRBF_PS_FUSEPAD")) : 1;  // (read per call: the tests switch it inside one process)
-            const mrbf_model *M0 = P.models[0];
-            if (fusepad && P.nmodels == 1 && ctx->eval_impl != 1 && (M0->dpad == 64 || M0->dpad == 128 || M0->dpad == 256) && a.d <= 360) {
-                const int64_t mpad = round_up((int64_t)a.rows, 64);
-                MRBF_TRY(get_buf(ctx, S_EVAL_XC, (size_t)mpad * M0->dpad, &a.Xq));
-                MRBF_TRY(get_buf(ctx, S_EVAL_XSQ, (size_t)mpad, &a.xsq));
-                a.xmean = M0->mean;
-                a.xqD = M0->dpad;
-            }
-        }
-        hipLaunchKernelGGL(ps_init_kernel, dim3((unsigned)((maxel + 255) / 256), (unsigned)a.nruns), dim3(256), 0, ctx->stream, a, start, t0);
-        std::vector<int> hstat((size_t)4 * a.nruns);
-        const unsigned wave_blocks = (unsigned)((a.rows + 3) / 4);
-        for (int g = 0; g < max_gens; ++g) {
-            a.gen = g;
-            EvalHints hints;
-            hints.population = true;
-            hints.pre_xq = (g > 0 && a.Xq) ? a.Xq : nullptr;  // (generation 0 comes from ps_init_kernel: centred by the evaluation's own launch)
-            for (int j = 0; j < P.nmodels; ++j) MRBF_TRY(eval_model(ctx, P.models[j], a.rows, a.Xeval, const_cast<double *>(a.F[j]), nullptr, nullptr, hints));
-            if (!a.score_fused) hipLaunchKernelGGL(ps_score_kernel, dim3(wave_blocks), dim3(256), 0, ctx->stream, a);
-            rank_launch(ctx, a, L, phases_possible);
-            hipLaunchKernelGGL(ps_breed_kernel, dim3(wave_blocks), dim3(256), 0, ctx->stream, a);
-            if ((g & 7) == 7 || g + 1 == max_gens) {  // status words every 8 generations: stop when every run is done
-                MRBF_HIP(ctx, hipMemcpyAsync(hstat.data(), a.runs[0].stat, hstat.size() * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-                int hfail = 0;
-                if (L.several) MRBF_HIP(ctx, hipMemcpyAsync(&hfail, L.ws.sync + RS_SYNC * MAXRUNS, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-                MRBF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                if (hfail && !(a.dbg & DBG_GIVE_UP)) {
-                    L.several = false;
-                    ctx->ps_multi_off = 1;
-                }
-                bool all = true;
-                for (int q2 = 0; q2 < a.nruns; ++q2) all = all && hstat[(size_t)4 * q2 + 1] != 0;
-                if (all) break;
-            }
-        }
-        MRBF_HIP(ctx, hipGetLastError());
-        return 0;
-    };
-
-    Args a{};
-    a.d = d;
-    a.nobj = k;
-    a.lb = dlb;
-    a.ub = dub;
-    a.mx = dmx;
-    a.r = dr;
-    a.nmodels = P.nmodels;
-    {
-        double *fp = F;
-        for (int j = 0; j < P.nmodels; ++j) {
-            a.F[j] = fp;
-            a.kf[j] = P.models[j]->k;
-            fp += (size_t)rows * P.models[j]->k;
+        float ms = 0.f;
+        MRBF_TRY(ps_step_many(ctx, S, r_or_null == nullptr, opts, &ms));
+        ms_sum += ms;
+        for (size_t i = 0; i < n; ++i) {
+            const size_t p = p0 + i;
+            infos[p] = S[i].info;
+            std::copy(S[i].xt.begin(), S[i].xt.end(), ox.begin() + p * d);
+            std::copy(S[i].mx.begin(), S[i].mx.end(), omx.begin() + p * k);
+            std::copy(S[i].r.begin(), S[i].r.end(), orr.begin() + p * k);
         }
     }
-    for (int l = 0; l < k; ++l) {
-        a.obj_model[l] = (short)P.obj_model[l];
-        a.obj_col[l] = (short)P.obj_col[l];
-    }
-    a.ncon = P.ncon;
-    for (int c = 0; c < P.ncon; ++c) {
-        a.con_model[c] = (short)P.con_model[c];
-        a.con_col[c] = (short)P.con_col[c];
-        a.con_eq[c] = (short)P.con_eq[c];
-    }
-    a.nlin_eq = P.nlin_eq;
-    a.nlin_ineq = P.nlin_ineq;
-    a.A_eq = P.dA_eq;
-    a.b_eq = P.db_eq;
-    a.A_ineq = P.dA_ineq;
-    a.b_ineq = P.db_ineq;
-    a.eq_tol = P.eq_tol;
-    a.Xeval = Xeval;
-    a.seed = opts->seed;
-    a.dbg = (mrbf_env("MRBF_PS_DBG") ? atoi(mrbf_env("MRBF_PS_DBG")) : 0) & DBG_ALL;
-    a.xtol_rel = xtol;
-    // ---- local ideal point: the k single-objective minimisations side by side (descent.jl:404-412)
-    if (need_ideal) {
-        double *p = pool;
-        a.nruns = k;
-        for (int l = 0; l < k; ++l) make_run(a.runs[l], 0, l, lam_ip, d, l * lam_ip, max_ip - res_ip, p, stat + 4 * l);
-        MRBF_TRY(run_batch(a, dxn, 0.0, (max_ip - res_ip + lam_ip - 1) / lam_ip + 1));
-        std::vector<double> bx((size_t)k * (d + 2));
-        std::vector<int> hs((size_t)4 * k);
-        for (int l = 0; l < k; ++l)
-            MRBF_HIP(ctx, hipMemcpyAsync(&bx[(size_t)l * (d + 2)], a.runs[l].best, (d + 2) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        MRBF_HIP(ctx, hipMemcpyAsync(hs.data(), stat, hs.size() * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        MRBF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        // r = f(x_n) - ideal point (descent.jl:536-538); a run that never met a feasible point contributes its start value.  The runs'
-        // best points are refined by gradient steps on their objective -- all k descents in lockstep, one evaluation per iteration
-        std::vector<double> ideal(k);
-        std::vector<Descent> ds;
-        std::vector<int> dl;
-        for (int l = 0; l < k; ++l) {
-            const double *b = &bx[(size_t)l * (d + 2)];
-            const bool found = b[d + 1] == 0.0 && std::isfinite(b[d]);
-            ideal[l] = found ? b[d] : mx[l];
-            info->evals_ideal += hs[(size_t)4 * l];
-            info->generations += hs[(size_t)4 * l + 2];
-            const int left = max_ip - hs[(size_t)4 * l];
-            if (found && left >= 13) {
-                ds.emplace_back();
-                Descent &D = ds.back();
-                D.P = &P;
-                D.lb = &hlb;
-                D.ub = &hub;
-                D.objs = std::vector<int>{l};
-                D.off = std::vector<double>{0.0};
-                D.scale = std::vector<double>{1.0};
-                D.clamp = false;
-                D.max_evals = left;
-                D.xtol_rel = xtol;
-                D.val = ideal[l];
-                D.x.assign(b, b + d);
-                dl.push_back(l);
-            }
-        }
-        if (!ds.empty()) MRBF_TRY(ps_descend_many(ctx, P, ds));
-        for (size_t i = 0; i < ds.size(); ++i) {
-            ideal[dl[i]] = ds[i].val;
-            info->evals_ideal += ds[i].evals;
-        }
-        for (int l = 0; l < k; ++l) r[l] = hfx[l] - ideal[l];
-    }
-    info->tau = 0.0;
-    bool critical = false;
-    for (int l = 0; l < k; ++l) critical = critical || !(r[l] > 0.0);
-    std::vector<double> xt(hxn);
-    if (critical) {
-        info->status = MRBF_PS_CRITICAL;  // any(r .<= 0): omega = 0, the point itself (descent.jl:546-549)
-    } else {
-        MRBF_HIP(ctx, hipMemcpyAsync(dr, r.data(), k * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        double *p = pool;
-        a.nruns = 1;
-        make_run(a.runs[0], 1, 0, lam_ps, d + 1, 0, max_ps - res_ps, p, stat);
-        MRBF_TRY(run_batch(a, dxn, opts->t0, (max_ps - res_ps + lam_ps - 1) / lam_ps + 1));
-        std::vector<double> best((size_t)d + 3);
-        int hs[4];
-        MRBF_HIP(ctx, hipMemcpyAsync(best.data(), a.runs[0].best, (d + 3) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        MRBF_HIP(ctx, hipMemcpyAsync(hs, stat, sizeof(hs), hipMemcpyDeviceToHost, ctx->stream));
-        MRBF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        info->evals_ps = hs[0];
-        info->generations += hs[2];
-        const double bf = best[d + 1], bphi = best[d + 2];
-        if (!(bphi == 0.0) || !std::isfinite(bf)) {
-            info->status = MRBF_PS_FAILURE;  // descent.jl:571-572
-        } else {
-            double tau = bf;
-            for (int t = 0; t < d; ++t) xt[t] = best[1 + t];
-            // the polish the configuration asks for (its own budget, descent.jl:423-429); without one, the part of the global budget
-            // that was kept back or left over
-            std::vector<int> objs(k);
-            for (int l = 0; l < k; ++l) objs[l] = l;
-            const bool own = opts->max_polish_evals > 0;
-            const int pbudget = own ? opts->max_polish_evals : max_ps - hs[0];
-            if (pbudget >= 13) {
-                int pe = 0;
-                MRBF_TRY(ps_descend(ctx, P, hlb, hub, objs, mx, r, true, pbudget, xtol, tau, xt, &pe));
-                if (own)
-                    info->evals_polish = pe;
-                else
-                    info->evals_ps += pe;
-            }
-            info->tau = tau;
-            info->status = MRBF_PS_OK;
-        }
-    }
-    // mx_trial = m(x_trial)
-    if (info->status == MRBF_PS_OK) {
-        MRBF_TRY(ps_eval_point(ctx, P, xt.data(), allF, nullptr));
-        for (int l = 0; l < k; ++l) mx[l] = P.objective(allF, l);
-    }
-    MRBF_HIP(ctx, hipEventRecord(e1, ctx->stream));
-    MRBF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    MRBF_HIP(ctx, hipEventElapsedTime(&info->ms_total, e0, e1));
-    auto put = [&](double *dst, const double *src, size_t c) -> int {
-        MRBF_HIP(ctx, hipMemcpy(dst, src, c * sizeof(double), hipMemcpyDefault));
-        return 0;
-    };
-    MRBF_TRY(put(x_trial, xt.data(), d));
-    MRBF_TRY(put(mx_trial, mx.data(), k));
-    if (r_out) MRBF_TRY(put(r_out, r.data(), k));
+    for (size_t p = 0; p < SN; ++p) infos[p].ms_total = ms_sum;
+    if (ms_total) *ms_total = ms_sum;
+    MRBF_TRY(output_put(ctx, x_trial, ox.data(), SN * d));
+    MRBF_TRY(output_put(ctx, mx_trial, omx.data(), SN * k));
+    if (r_out) MRBF_TRY(output_put(ctx, r_out, orr.data(), SN * k));
     return MRBF_OK;
 }
 
@@ -1987,13 +2378,13 @@ extern "C" int32_t mrbf_debug_ps_rank(mrbf_ctx *ctx, int32_t lam, const double *
     (void)hipSetDevice(ctx->device);
     double *base;
     int *stat;
-    MRBF_TRY(get_buf(ctx, S_PS_STATE, (size_t)4 * lam + 16, &base));
+    const size_t args_at = ((size_t)4 * lam + 16 + 15) & ~(size_t)15;  // the one start's block behind the generation
+    MRBF_TRY(get_buf(ctx, S_PS_STATE, args_at + (sizeof(Args) + sizeof(double) - 1) / sizeof(double), &base));
     MRBF_TRY(get_buf(ctx, S_PS_STAT, (size_t)4 * MAXRUNS, &stat));
     Args a{};
     Run &R = a.runs[0];
     a.nruns = 1;
     a.seed = seed;
-    a.gen = gen;
     a.xtol_rel = 1e-3;
     a.dbg = impl == 2 ? DBG_GIVE_UP : (impl == 3 ? DBG_SORT_PAIRS : (impl == 5 ? DBG_NO_SELECT : (impl == 4 ? DBG_SELECT : (impl == 9 ? DBG_PHASE_PAIRS : 0))));
     R.nvar = 1;
@@ -2012,9 +2403,11 @@ extern "C" int32_t mrbf_debug_ps_rank(mrbf_ctx *ctx, int32_t lam, const double *
     MRBF_HIP(ctx, hipMemcpyAsync(R.f, f, (size_t)lam * sizeof(double), hipMemcpyDefault, ctx->stream));
     MRBF_HIP(ctx, hipMemcpyAsync(R.phi, phi, (size_t)lam * sizeof(double), hipMemcpyDefault, ctx->stream));
     MRBF_HIP(ctx, hipMemsetAsync(stat, 0, (size_t)4 * MAXRUNS * sizeof(int), ctx->stream));
+    const Args *dA = reinterpret_cast<const Args *>(base + args_at);
+    MRBF_HIP(ctx, hipMemcpyAsync(base + args_at, &a, sizeof(Args), hipMemcpyHostToDevice, ctx->stream));
     RankLaunch L;
-    MRBF_TRY(rank_launch_setup(ctx, a, several, L));
-    rank_launch(ctx, a, L, true);
+    MRBF_TRY(rank_launch_setup(ctx, a, 1, several, L));
+    rank_launch(ctx, dA, 1, 1, gen, L, true);
     MRBF_HIP(ctx, hipGetLastError());
     int hsync[2] = {0, 0};
     if (L.several) MRBF_HIP(ctx, hipMemcpyAsync(hsync, L.ws.sync, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));

@@ -264,6 +264,9 @@ set_fully_linear!(m::HipRbfModel, val) = (m.fully_linear = val; nothing)
 #      so both bindings route every call the same way; 1 = device entry point, 0 = Morbit's own method
 _dispatch_ps(d, k, n_models, n_nl, n_lin, n_foreign) =
     ccall((:mrbf_dispatch_ps, libmrbf), Int32, (Int32, Int32, Int32, Int32, Int32, Int32), d, k, n_models, n_nl, n_lin, n_foreign) == 1
+_dispatch_ps_batch(n_starts, d, k, n_models, n_nl, n_lin, n_foreign) =
+    ccall((:mrbf_dispatch_ps_batch, libmrbf), Int32, (Int64, Int32, Int32, Int32, Int32, Int32, Int32),
+          n_starts, d, k, n_models, n_nl, n_lin, n_foreign) == 1
 _dispatch_sd(d, k, n_models, n_nl, n_lin, n_foreign) =
     ccall((:mrbf_dispatch_sd, libmrbf), Int32, (Int32, Int32, Int32, Int32, Int32, Int32), d, k, n_models, n_nl, n_lin, n_foreign) == 1
 _dispatch_normal(d, n_models, n_nl, n_lin, n_foreign) =
@@ -294,6 +297,10 @@ _dispatch_fit(n_training, n0, q, n_accepted, same_sites::Bool) =
 const ROUND4_BATCH_MIN_STARTS = 8
 const ROUND4_BATCH_CANDIDATES_PER_START = 32
 _round4_batch_pays(n_starts, max_candidates) = n_starts >= ROUND4_BATCH_MIN_STARTS && n_starts * ROUND4_BATCH_CANDIDATES_PER_START >= max_candidates
+# Where `hip_ps_criticality_many` takes the batched call (tools/ps_batch_bench.py, DESIGN.md section 15): the batch of one is the single
+# call itself, from two starts on the starts share every generation's launches and every refinement iteration's synchronisation.
+const PS_BATCH_MIN_STARTS = 2
+_ps_batch_pays(n_starts) = n_starts >= PS_BATCH_MIN_STARTS
 _fallback_rc(entry, rc) = ccall((:mrbf_dispatch_after, libmrbf), Int32, (Int32, Int32), entry, rc) == 1
 
 # ---- two-phase construction: phase I (which sites) stays Morbit's control flow (RbfModel.jl:506-655 is generic in `cfg`); the
@@ -742,6 +749,76 @@ function get_criticality(desc_cfg::PascolettiSerafiniConfig, mop, scal, x_it, x_
     info[].status == 1 && return 0, copy(get_x_scaled(x_it_n)), mx_trial, 0    # critical: some r_l <= 0 (descent.jl:546-549)
     info[].status == 2 && return 0, copy(get_x_scaled(x_it)), mx_trial, 0      # failure (descent.jl:571-572)
     return Xet(abs(info[].tau)), (Xet.(x_trial), mx_trial, norm(x .- x_trial, Inf))
+end
+
+"""
+Many starts in one device call (`mrbf_ps_step_batch`): `get_criticality(::PascolettiSerafiniConfig, ...)` (descent.jl:512-581) for
+independent starts of one problem -- the `Threads.@threads` loop over starts of examples/large_scale_benchmarks.jl:102-109 with
+`descent_method = :ps`.  `x_its[p]`, `x_it_ns[p]` and `scs[p]` are start p's iterate, normal-step iterate and surrogate container,
+`seeds[p]` keys its generator; `mop`, `scal` and the configurations belong to the one problem.  For every start the result is, bit for
+bit, what `get_criticality` returns on that start alone with `seed = seeds[p]`.  Where the containers do not share one plan shape, the
+decision table refuses (`mrbf_dispatch_ps_batch`: a foreign surrogate, d > 256, more than 65535 starts, the limits of the single
+call) or the batch does not pay (`_ps_batch_pays`), every start takes the single-start method.  Returns a vector of that method's results.
+"""
+function hip_ps_criticality_many(desc_cfg::PascolettiSerafiniConfig, mop, scal, x_its::AbstractVector, x_it_ns::AbstractVector, data_base,
+                                 scs::AbstractVector{<:SurrogateContainer}, algo_config;
+                                 seeds::AbstractVector{UInt64} = rand(UInt64, length(scs)))
+    single(p) = get_criticality(desc_cfg, mop, scal, x_its[p], x_it_ns[p], data_base, scs[p], algo_config; seed = seeds[p])
+    loop() = [single(p) for p in eachindex(scs)]
+    ns = length(scs)
+    (_ps_batch_pays(ns) && all(_touches_device, scs)) || return loop()
+    plans = [_container_plan(sc) for sc in scs]
+    p1 = plans[1]
+    same = all(pl -> pl.roles == p1.roles && pl.k == p1.k && pl.n_con == p1.n_con && pl.n_foreign == p1.n_foreign &&
+                     length(pl.models) == length(p1.models) &&
+                     all(num_outputs(a) == num_outputs(b) for (a, b) in zip(pl.models, p1.models)), plans)
+    same || return loop()
+    d, k, nm = length(get_x_scaled(x_it_ns[1])), p1.k, length(p1.models)
+    A_eq, b_eq = transformed_linear_eq_constraints(scal, mop)                  # AbstractMOPInterface.jl:463-481: A x_scaled (=, <=) b
+    A_in, b_in = transformed_linear_ineq_constraints(scal, mop)
+    _dispatch_ps_batch(ns, d, k, nm, p1.n_con, length(b_eq) + length(b_in), p1.n_foreign) || return loop()
+    X_n = Matrix{Float64}(undef, d, ns); LB = Matrix{Float64}(undef, d, ns); UB = Matrix{Float64}(undef, d, ns)   # column p = start p
+    FX_n = Matrix{Float64}(undef, k, ns)
+    for p in 1:ns
+        X_n[:, p] .= get_x_scaled(x_it_ns[p]); FX_n[:, p] .= get_fx(x_it_ns[p])
+        lb_eff, ub_eff = local_bounds(scal, Vector{Float64}(get_x_scaled(x_its[p])), get_delta(x_its[p]))
+        LB[:, p] .= lb_eff; UB[:, p] .= ub_eff
+    end
+    rs = [_get_global_dir(desc_cfg, FX_n[:, p]) for p in 1:ns]                 # descent.jl:360-368
+    R = rs[1] === nothing ? nothing : Matrix{Float64}(hcat(rs...))
+    g_evals, l_evals = _ps_max_evals(desc_cfg, d)                              # descent.jl:414-432
+    opts = Ref(MrbfPsOptions(desc_cfg.max_ideal_point_problem_evals, g_evals, l_evals, 0, UInt64(0), -0.5, 1e-3))
+    infos = Vector{MrbfPsInfo}(undef, ns)
+    X_t = Matrix{Float64}(undef, d, ns); MX_t = Matrix{Float64}(undef, k, ns)
+    ms = Ref{Float32}(0)
+    seedv = Vector{UInt64}(seeds)
+    handles = Ptr{Cvoid}[m.handle for pl in plans for m in pl.models]          # start-major
+    roles = p1.roles
+    Aeq = Matrix{Float64}(transpose(Matrix(A_eq))); beq = Vector{Float64}(b_eq)   # row-major rows x d == the d x rows column-major matrix
+    Ain = Matrix{Float64}(transpose(Matrix(A_in))); bin = Vector{Float64}(b_in)
+    ctx = p1.models[1].ctx
+    rc = GC.@preserve handles roles Aeq beq Ain bin X_n LB UB FX_n R seedv X_t MX_t infos begin
+        prob = Ref(MrbfPsProblem(nm, k, C_NULL, pointer(roles), length(beq), length(bin),
+                                 isempty(beq) ? C_NULL : pointer(Aeq), isempty(beq) ? C_NULL : pointer(beq),
+                                 isempty(bin) ? C_NULL : pointer(Ain), isempty(bin) ? C_NULL : pointer(bin), -1.0))
+        _locked(ctx) do hctx
+            ccall((:mrbf_ps_step_batch, libmrbf), Int32,
+                  (Ptr{Cvoid}, Int64, Ref{MrbfPsProblem}, Ptr{Ptr{Cvoid}}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                   Ptr{Float64}, Ref{MrbfPsOptions}, Ptr{UInt64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{MrbfPsInfo},
+                   Ref{Float32}),
+                  hctx, ns, prob, handles, X_n, LB, UB, FX_n, R === nothing ? C_NULL : pointer(R), opts, seedv, X_t, MX_t, C_NULL, infos, ms)
+        end
+    end
+    rc != 0 && _fallback_rc(14, rc) && return loop()           # a shape outside the device path: the single-start method
+    _check(ctx, rc)
+    Xet = eltype(get_x_scaled(x_it_ns[1]))
+    return map(1:ns) do p
+        info = infos[p]
+        info.status == 1 && return 0, copy(get_x_scaled(x_it_ns[p])), MX_t[:, p], 0    # critical: some r_l <= 0 (descent.jl:546-549)
+        info.status == 2 && return 0, copy(get_x_scaled(x_its[p])), MX_t[:, p], 0      # failure (descent.jl:571-572)
+        x_trial = X_t[:, p]
+        (Xet(abs(info.tau)), (Xet.(x_trial), MX_t[:, p], norm(Vector{Float64}(get_x_scaled(x_its[p])) .- x_trial, Inf)))
+    end
 end
 
 """

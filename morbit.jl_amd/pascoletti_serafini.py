@@ -379,6 +379,115 @@ def get_criticality_container(desc_cfg, sc, scal, x, x_n, fx_n, lb_eff, ub_eff, 
                            rng=rng if rng is not None else np.random.default_rng(seed), stats=stats)
 
 
+# ---- many starts in one device call (mrbf_ps_step_batch): the reference's Threads.@threads loop over starts, descent_method = :ps ------
+# Where the batch pays (measured, DESIGN.md section 15: the batch of one costs what the single call costs, from two starts on the
+# starts share every generation's launches and every refinement iteration's synchronisation); below, the loop of single calls.
+PS_BATCH_MIN_STARTS = 2
+
+
+def ps_batch_pays(n_starts):
+    """does one mrbf_ps_step_batch call beat the loop of mrbf_ps_step_problem calls for this many starts"""
+    return n_starts >= PS_BATCH_MIN_STARTS
+
+
+def _ps_options(desc_cfg, d, seed=0):
+    g_evals, l_evals = _ps_max_evals(desc_cfg, d)
+    from . import _lib
+    return _lib.PsOptions(max_ideal_evals=int(desc_cfg.max_ideal_point_problem_evals), max_ps_evals=int(g_evals),
+                          max_polish_evals=int(l_evals), reserved=0, seed=int(seed) & (2 ** 64 - 1), t0=-0.5, xtol_rel=1e-3)
+
+
+def ps_step_batch_device(desc_cfg, plans, X_n, FX_n, lb_effs, ub_effs, R=None, lin=None, seeds=None, eq_tol=-1.0, out=None):
+    """one mrbf_ps_step_batch call on the containers' plans (one shape, checked by the caller).  X_n, lb_effs, ub_effs (n_starts x d),
+    FX_n and the directions R (n_starts x k, or None: the ideal-point phase runs) may be NumPy arrays or device tensors;
+    out = (x_trial, mx_trial, r_out) lets the caller pass its own output buffers (host or device).
+    Returns (rc, x_trial, mx_trial, r_out, list of info dicts, event ms)."""
+    import ctypes
+
+    from . import _lib
+
+    def arr(a):
+        return a if a is None or hasattr(a, "data_ptr") else np.ascontiguousarray(a, dtype=np.float64)
+
+    p0 = plans[0]
+    ctx = p0["models"][0].ctx
+    ns, k = len(plans), p0["k"]
+    X_n, FX_n, lb, ub, R = arr(X_n), arr(FX_n), arr(lb_effs), arr(ub_effs), arr(R)
+    d = int((X_n.numel() if hasattr(X_n, "numel") else X_n.size) // ns)
+    A_eq, b_eq, A_in, b_in = [None if a is None or np.asarray(a).size == 0 else np.ascontiguousarray(a, dtype=np.float64) for a in (lin or (None,) * 4)]
+    hs = [m.model.value if hasattr(m.model, "value") else m.model for p in plans for m in p["models"]]
+    handles = (ctypes.c_void_p * max(len(hs), 1))(*hs)
+    roles_c = (ctypes.c_int32 * max(len(p0["roles"]), 1))(*p0["roles"])
+    prob = _lib.PsProblem(n_models=len(p0["models"]), n_objectives=k, models=None, roles=roles_c,
+                          n_lin_eq=0 if b_eq is None else b_eq.size, n_lin_ineq=0 if b_in is None else b_in.size,
+                          A_eq=None if b_eq is None else A_eq.ctypes.data, b_eq=None if b_eq is None else b_eq.ctypes.data,
+                          A_ineq=None if b_in is None else A_in.ctypes.data, b_ineq=None if b_in is None else b_in.ctypes.data, eq_tol=float(eq_tol))
+    opts = _ps_options(desc_cfg, d)
+    seeds_c = None if seeds is None else (ctypes.c_uint64 * ns)(*[int(s) & (2 ** 64 - 1) for s in seeds])
+    xt, mt, r_out = out if out is not None else (np.empty((ns, d)), np.empty((ns, k)), np.empty((ns, k)))
+    infos = (_lib.PsInfo * ns)()
+    ms = ctypes.c_float()
+    rc = ctx.lib.mrbf_ps_step_batch(ctx.h, ns, ctypes.byref(prob), handles, _lib.as_ptr(X_n), _lib.as_ptr(lb), _lib.as_ptr(ub), _lib.as_ptr(FX_n),
+                                    _lib.as_ptr(R), ctypes.byref(opts), seeds_c, _lib.as_ptr(xt), _lib.as_ptr(mt), _lib.as_ptr(r_out), infos,
+                                    ctypes.byref(ms))
+    return rc, xt, mt, r_out, [i.asdict() for i in infos], ms.value
+
+
+def get_criticality_many(desc_cfg, containers, scal, X, X_n, FX_n, lb_effs, ub_effs, lin=None, seeds=None, stats=None, eq_tol=1e-8):
+    """`get_criticality(::PascolettiSerafiniConfig, ...)` (descent.jl:512-581) for many independent starts of one problem -- the
+    reference's `Threads.@threads` loop over starts (examples/large_scale_benchmarks.jl:102-109) with `descent_method = :ps`:
+    containers[p] is start p's surrogate container, X[p] / X_n[p] / FX_n[p] its iterate, the point its step starts from and the true
+    objective values there, lb_effs[p] / ub_effs[p] its effective box; lin belongs to the one MOP; seeds[p] keys start p's generator
+    (None: 0 for every start).  Where the containers share one plan shape, mrbf_dispatch_ps_batch says so and the batch pays
+    (`ps_batch_pays`), ONE mrbf_ps_step_batch call serves all starts and every
+    start's status is mapped exactly as `get_criticality_container` maps it; otherwise every start alone goes through
+    `get_criticality_container`.  Returns the list of that function's results; stats gets "path" ("batch" or "loop") and, for a
+    batch, "infos", "r" and "ms_total"."""
+    from . import _lib
+    from . import surrogates as sg
+
+    lib = _lib.load()
+    X, X_n, FX_n = np.asarray(X, dtype=np.float64), np.asarray(X_n, dtype=np.float64), np.asarray(FX_n, dtype=np.float64)
+    lb_effs, ub_effs = np.asarray(lb_effs, dtype=np.float64), np.asarray(ub_effs, dtype=np.float64)
+    ns = len(containers)
+    seeds = [0] * ns if seeds is None else [int(s) for s in seeds]
+    lin = lin or (None,) * 4
+    n_lin = sum(0 if b is None else int(np.asarray(b).size) for b in (lin[1], lin[3]))
+
+    def single(p):
+        return get_criticality_container(desc_cfg, containers[p], scal, X[p], X_n[p], FX_n[p], lb_effs[p], ub_effs[p], lin=lin, seed=seeds[p],
+                                         eq_tol=eq_tol)
+
+    if stats is not None:
+        stats["path"] = "loop"
+    if ns == 0:
+        return []
+    plans = [sg.container_plan(sc) for sc in containers]
+    p0 = plans[0]
+    sig0 = ([m.num_outputs for m in p0["models"]], p0["roles"], p0["k"], p0["n_con"], p0["n_foreign"])
+    same = all(([m.num_outputs for m in p["models"]], p["roles"], p["k"], p["n_con"], p["n_foreign"]) == sig0 for p in plans[1:])
+    d = int(X_n.shape[1])
+    if same and ps_batch_pays(ns) and lib.mrbf_dispatch_ps_batch(ns, d, p0["k"], len(p0["models"]), p0["n_con"], n_lin, p0["n_foreign"]) == _lib.DISPATCH_DEVICE:
+        dirs = [_get_global_dir(desc_cfg, FX_n[p]) for p in range(ns)]
+        R = None if dirs[0] is None else np.ascontiguousarray(np.stack(dirs), dtype=np.float64)
+        rc, xt, mt, r_out, infos, ms = ps_step_batch_device(desc_cfg, plans, X_n, FX_n, lb_effs, ub_effs, R=R, lin=lin, seeds=seeds, eq_tol=eq_tol)
+        if rc == 0:
+            res = []
+            for p, info in enumerate(infos):
+                if info["status"] == _lib.PS_CRITICAL:
+                    res.append((0, X_n[p].copy(), mt[p].copy(), 0))          # descent.jl:546-549
+                elif info["status"] == _lib.PS_FAILURE:
+                    res.append((0, X[p].copy(), mt[p].copy(), 0))            # descent.jl:571-572
+                else:
+                    res.append((abs(float(info["tau"])), (xt[p].copy(), mt[p].copy(), float(np.linalg.norm(X[p] - xt[p], ord=np.inf)))))
+            if stats is not None:
+                stats.update(path="batch", infos=infos, r=r_out.copy(), ms_total=ms)
+            return res
+        if not lib.mrbf_dispatch_after(_lib.ENTRY_PS_BATCH, rc):
+            p0["models"][0].ctx.check(rc)
+    return [single(p) for p in range(ns)]
+
+
 def get_criticality(desc_cfg, x, x_n, fx_n, lb_eff, ub_eff, eval_objectives: Callable, eval_jacobians: Optional[Callable] = None,
                     eval_constraints: Optional[Callable] = None, rng=None, stats=None):
     """descent.jl:512-581.  `x` / `x_n`: scaled iterate and the point the step starts from (the same unless a normal step was taken);
