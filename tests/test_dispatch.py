@@ -452,3 +452,28 @@ def test_mega_default_plan():
     assert lib.mrbf_debug_mega_plan(4, 3, 0, out) == -1
     assert lib.mrbf_debug_mega_plan(4, 5, -1, out) == -3
     assert lib.mrbf_debug_mega_plan(4, 5, 8, None) == -4
+
+
+def test_mega_plan_extra_block_rows_of_many_outputs():
+    """The fit's right-hand sides ride along the factorisation as extra block rows (solve.hip: xt = round_up(k, 128), xreal = k).  Up to
+    64 outputs the one extra row is scheduled as upper halves (xhalf); 65 .. 128 outputs fill it; more than 128 take MT = NT + 2 .. NT + 8
+    block rows, never as halves.  tests/test_gpu_many_outputs.py runs these shapes on the GPU."""
+    import ctypes
+
+    from morbit.jl_amd import _lib
+
+    lib = _lib.load()
+    out = (ctypes.c_int64 * 39)()
+
+    def plan(nt, mt, xreal):
+        assert lib.mrbf_debug_mega_plan(nt, mt, xreal, out) == 0, (nt, mt, xreal)
+        assert out[38] == 0, (nt, mt, xreal, list(out)[33:])           # the job tables are consistent
+        return dict(zip(MEGA_PLAN_FIELDS, list(out)[:33]))
+
+    for nt in (4, 12):
+        p64, p65 = plan(nt, nt + 1, 64), plan(nt, nt + 1, 65)
+        assert p64["xhalf"] == 1 and p65["xhalf"] == 0
+        assert {f for f in MEGA_PLAN_FIELDS if p64[f] != p65[f]} == {"xhalf"}, (nt, p64, p65)   # the plans differ in exactly that field
+        for extra, xreal in ((2, 129), (2, 256), (3, 257), (8, 1024)):
+            p = plan(nt, nt + extra, xreal)
+            assert p["xhalf"] == 0, (nt, extra, xreal, p)

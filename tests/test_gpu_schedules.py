@@ -52,7 +52,9 @@ def test_schedule_variant_factors_correctly(env):
 def test_fit_front_ends_agree(tmp_path):
     """The fit's two front ends for d <= 64 -- tail basis, Q1'Y and projected right-hand sides in three launches (small.hip, TailQ,
     the default) against the twelve-launch chain it replaces (MRBF_TAILQ=0) -- give the same models: weights and tail coefficients
-    agree to rounding-times-conditioning, both interpolate (eight shapes: d = 3 .. 64, k = 1 .. 16, n = 513 .. 3000 incl. non-multiples of 16).  (The switch is read once per process: one child per setting.)"""
+    agree to rounding-times-conditioning, both interpolate (eight shapes: d = 3 .. 64, k = 1 .. 16, n = 513 .. 3000 incl. non-multiples of 16).  (The switch is read once per process: one child per setting.)
+    k <= 16 is the range of the three-launch front end, not of the library: fits take 1 <= k <= 1024, and with k >= 17 the twelve-launch
+    chain is the only front end -- tests/test_gpu_many_outputs.py runs it in-process against the oracle."""
     import numpy as np
     outs = []
     for v in ("1", "0"):
