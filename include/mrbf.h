@@ -348,6 +348,82 @@ typedef struct {
 } mrbf_fit_job;                       /* 168 bytes */
 int32_t mrbf_fit_batch(mrbf_ctx *ctx, int64_t n_starts, mrbf_fit_job *jobs, float *ms_total);
 
+/* ---- resident site database: box scan and gathers for many-start updates (db.hip, host logic in db_host.hpp) -----------------
+ * A start's evaluation database -- the ArrayDB of src/Databases.jl: sites (d) and values (k), rows in insertion order, a row's
+ * position being its id -- kept on the device and appended to as the run goes, so that the batched calls above read their inputs from
+ * device memory instead of a fresh host array per start and call.  All indices are 0-based positions in database order, like
+ * accepted_out and picked_out.  MRBF_OPT_LIVE_HANDLES counts databases; MRBF_OPT_ARENA_BYTES does not: a database owns its own
+ * allocation, which grows geometrically (db_host.hpp: twice the capacity, at least what is needed, at least 64 rows).
+ *   mrbf_db_create      an empty database (init_db, Databases.jl:41-54); capacity_hint rows are allocated at once (<= 0: on first use).
+ *   mrbf_db_append      new_result!(db, x, y) (Databases.jl:174-186) for m rows: sites m x d, values m x k row-major, host or device;
+ *                       values == NULL: the rows are unevaluated and stored as NaN -- new_result!(db, p, F[]) of round 3,
+ *                       RbfModel.jl:303.  Grows the allocation when needed; earlier rows keep their bits.  *first_index (may be NULL):
+ *                       the position of the first new row.
+ *   mrbf_db_set_values  eval_missing! (Databases.jl:258-277): the values (m x k row-major, host or device) of the rows `indices`
+ *                       (host, m distinct positions; one out of range: -4, nothing written).
+ *   mrbf_db_read        rows first .. first + m - 1 to sites_out (m x d) / values_out (m x k), host or device, either may be NULL:
+ *                       get_sites / get_values (Databases.jl:128-137).
+ *   mrbf_db_dims        n_sites, d, k (any may be NULL).
+ *   mrbf_db_free        releases the allocation; views into the database (below) end with it. */
+typedef struct mrbf_db mrbf_db;   /* one start's database: sites (d) and values (k), rows in insertion order (ArrayDB ids) */
+int32_t mrbf_db_create(mrbf_ctx *ctx, int32_t d, int32_t k, int64_t capacity_hint, mrbf_db **db);
+int32_t mrbf_db_append(mrbf_ctx *ctx, mrbf_db *db, int64_t m, const double *sites, const double *values, int64_t *first_index);
+int32_t mrbf_db_set_values(mrbf_ctx *ctx, mrbf_db *db, int64_t m, const int64_t *indices, const double *values);
+int32_t mrbf_db_read(mrbf_ctx *ctx, const mrbf_db *db, int64_t first, int64_t m, double *sites_out, double *values_out);
+int32_t mrbf_db_dims(const mrbf_db *db, int64_t *n_sites, int32_t *d, int32_t *k);
+int32_t mrbf_db_free(mrbf_ctx *ctx, mrbf_db *db);
+
+/* The box scan for a batch of starts: results_in_box_indices (src/Databases.jl:324-327) as called by _find_suitable_points
+ * (src/models/RbfModel.jl:214) and _rbf_round4 (:360), the shifted seeds xi - x0 of the filter (AffinelyIndependentPoints.jl:25)
+ * and its first pick, findmax(norm.(shifted_seeds, p)) (:53), for n_starts databases of one d in four launches whose grids span all
+ * starts, with one packed descriptor upload and one read-back.
+ * Candidate i is in the box iff i is not in `exclude` and lb[j] <= site[i][j] <= ub[j] for all j: inclusive comparisons, a NaN
+ * coordinate fails them, infinite bounds work.  Candidates come out in ascending database order (a scan of per-block counts, no
+ * atomics).  A shifted row is site - x0, one fp64 subtraction per element.  first_pick: the position among the candidates of the
+ * first maximiser of ||xi - x0||_p (p_is_inf: 1 = inf-norm, 0 = 2-norm as sqrt of the sum of squares); the lowest position wins ties,
+ * the pivot value is not consulted; -1 when mc = 0.  With zero_first_pick != 0 that row of shifted_dev (and of shifted_out) is zero
+ * afterwards and first_row still holds it: the state mrbf_affine_select[_batch] expects ("chosen sites: zero rows").
+ * Lifetime of the views: cand_sites_dev and shifted_dev point into memory of the context and stay valid until the next
+ * mrbf_db_box_batch on the same context; sites_dev and values_dev of mrbf_db_gather_batch until the next mrbf_db_gather_batch on it;
+ * box views and gather views do not disturb each other, and no other entry point writes to either (the batched calls copy their
+ * inputs into their own arena).  A database's release or the context's shutdown also ends them.
+ * A database may appear at most once per batch call.  Returns 0; -2 (do it on the host; nothing is written) when
+ * mrbf_dispatch_db_batch refuses the shape; an invalid field of a job is an invalid `jobs` (-5; mrbf_db_gather_batch: -4).  A job
+ * that fails sets its own rc, leaves its outputs untouched and does not fail the others.  ms_total (may be NULL): hipEvent time of
+ * the launches and the read-back on the ctx stream, without the copies to sites_out / shifted_out. */
+typedef struct {
+    mrbf_db *db;
+    const double *lb, *ub, *x0;     /* host, d doubles each */
+    int64_t n_exclude;
+    const int64_t *exclude;         /* host; duplicates allowed, entries outside [0, n_sites) ignored; NULL with n_exclude = 0 */
+    int32_t zero_first_pick;
+    int32_t rc;                     /* out */
+    int64_t *indices_out;           /* host, room for n_sites entries; may be NULL */
+    double *sites_out, *shifted_out; /* host or device, mc x d row-major (room for n_sites x d); may be NULL */
+    double *first_row;              /* host, d doubles: the first pick's shifted row (untouched when mc = 0) */
+    int64_t mc;                     /* out: candidates in the box */
+    int64_t first_pick;             /* out */
+    const double *cand_sites_dev;   /* out: device, mc x d row-major, database order */
+    const double *shifted_dev;      /* out: device, mc x d row-major */
+} mrbf_db_box_job;                  /* 120 bytes */
+int32_t mrbf_db_box_batch(mrbf_ctx *ctx, int64_t n_starts, int32_t d, int32_t p_is_inf, mrbf_db_box_job *jobs, float *ms_total);
+
+/* Row gathers for a batch of starts: get_site.(db, indices_found_so_far) of round 4 (RbfModel.jl:372) and the training set of the
+ * fit (get_site / get_value over _collect_indices(meta), RbfModel.jl:747-757) in one launch, with one packed upload of the index
+ * lists.  indices: host, any order, repeats allowed; an index outside [0, n_sites) sets the job's rc to -3 and leaves its outputs
+ * untouched.  sites_dev (n_idx x d) and values_dev (n_idx x k) come in the order of `indices`. */
+typedef struct {
+    mrbf_db *db;
+    int64_t n_idx;
+    const int64_t *indices;         /* host */
+    double *sites_out, *values_out; /* host or device, n_idx x d / n_idx x k; may be NULL */
+    const double *sites_dev;        /* out: device, n_idx x d row-major */
+    const double *values_dev;       /* out: device, n_idx x k row-major */
+    int32_t rc;                     /* out */
+    int32_t reserved;
+} mrbf_db_gather_job;               /* 64 bytes */
+int32_t mrbf_db_gather_batch(mrbf_ctx *ctx, int64_t n_starts, int32_t d, mrbf_db_gather_job *jobs, float *ms_total);
+
 /* debug / test hooks (exported so the parity tests can pin kernel-level behaviour) */
 /* Environment switches.  The library reads a number of MRBF_* variables (schedule experiments of the persistent factorisation,
  * earlier forms of kernels kept selectable for A/B runs, diagnostics: INTEGRATION.md "Tuning knobs").  NONE of them is honoured
@@ -691,6 +767,9 @@ int32_t mrbf_ps_step_batch(mrbf_ctx *ctx, int64_t n_starts, const mrbf_ps_proble
  *                            device iff mrbf_dispatch_ps says so, d <= 256 (the fused evaluation kernels' range) and
  *                            1 <= n_starts <= 65535 (a grid dimension).  The bindings keep the loop of single calls where the
  *                            batch does not pay.
+ *   mrbf_dispatch_db_batch   results_in_box_indices (src/Databases.jl:324-327) and the row gathers of n_starts resident databases in one
+ *                            call (mrbf_db_box_batch, mrbf_db_gather_batch): device iff 1 <= n_starts <= 65535 (a grid dimension) and
+ *                            1 <= d <= 4096; otherwise the scan and the copies run on the caller's host copy of the database.
  *   mrbf_dispatch_after      the return code rc of a device entry point (MRBF_ENTRY_*) that means "take the reference method
  *                            for this call" (start set without the tail or rank deficient, limits of the device path) rather
  *                            than an error: 1 = fall back, 0 = rc is what it says. */
@@ -698,7 +777,8 @@ enum { MRBF_DISPATCH_REFERENCE = 0, MRBF_DISPATCH_DEVICE = 1 };
 enum { MRBF_FIT_FULL = 0, MRBF_FIT_FROM_ROUND4 = 1 };
 enum { MRBF_ENTRY_ROUND4 = 1, MRBF_ENTRY_FIT_FROM_ROUND4 = 2, MRBF_ENTRY_PS_STEP = 3, MRBF_ENTRY_BACKTRACK = 4, MRBF_ENTRY_AFFINE = 5,
        MRBF_ENTRY_SD = 6, MRBF_ENTRY_NORMAL = 7, MRBF_ENTRY_SD_STEP = 8, MRBF_ENTRY_SD_BATCH = 9, MRBF_ENTRY_AFFINE_BATCH = 10,
-       MRBF_ENTRY_FIT_BATCH = 11, MRBF_ENTRY_NORMAL_BATCH = 12, MRBF_ENTRY_ROUND4_BATCH = 13, MRBF_ENTRY_PS_BATCH = 14 };
+       MRBF_ENTRY_FIT_BATCH = 11, MRBF_ENTRY_NORMAL_BATCH = 12, MRBF_ENTRY_ROUND4_BATCH = 13, MRBF_ENTRY_PS_BATCH = 14,
+       MRBF_ENTRY_DB_BOX = 15, MRBF_ENTRY_DB_GATHER = 16 };
 int32_t mrbf_dispatch_ps(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_ps_batch(int64_t n_starts, int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints,
                                int32_t n_lin_constraints, int32_t n_foreign);
@@ -716,6 +796,7 @@ int32_t mrbf_dispatch_affine_batch(int64_t n_starts, int32_t d, int32_t p_is_inf
 int32_t mrbf_dispatch_round4(int64_t n0, int32_t d, int32_t poly_deg, int64_t n_candidates);
 int32_t mrbf_dispatch_fit_batch(int64_t n_starts);
 int32_t mrbf_dispatch_round4_batch(int64_t n_starts, int32_t d);
+int32_t mrbf_dispatch_db_batch(int64_t n_starts, int32_t d);
 int32_t mrbf_dispatch_fit(int64_t n_training, int64_t state_n0, int32_t state_q, int32_t state_n_accepted, int32_t same_sites);
 int32_t mrbf_dispatch_after(int32_t entry, int32_t rc);
 

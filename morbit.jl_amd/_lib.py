@@ -65,6 +65,8 @@ ENTRY_FIT_BATCH = 11
 ENTRY_NORMAL_BATCH = 12
 ENTRY_ROUND4_BATCH = 13
 ENTRY_PS_BATCH = 14
+ENTRY_DB_BOX = 15
+ENTRY_DB_GATHER = 16
 SD_OK, SD_NO_OBJECTIVE, SD_INFEASIBLE, SD_GAVE_UP = 0, 1, 2, 3
 NS_OK, NS_INFEASIBLE, NS_GAVE_UP = 0, 1, 2
 SD_BRANCH_DELTA, SD_BRANCH_ONE, SD_BRANCH_INTERSECT = 0, 1, 2
@@ -146,6 +148,22 @@ class FitJob(ctypes.Structure):
                 ("status", ctypes.c_int32), ("reserved", ctypes.c_int32), ("info", FitInfo)]
 
 
+class DbBoxJob(ctypes.Structure):
+    """mrbf_db_box_job: one start of mrbf_db_box_batch"""
+    _fields_ = [("db", ctypes.c_void_p), ("lb", ctypes.c_void_p), ("ub", ctypes.c_void_p), ("x0", ctypes.c_void_p),
+                ("n_exclude", ctypes.c_int64), ("exclude", ctypes.c_void_p), ("zero_first_pick", ctypes.c_int32), ("rc", ctypes.c_int32),
+                ("indices_out", ctypes.c_void_p), ("sites_out", ctypes.c_void_p), ("shifted_out", ctypes.c_void_p),
+                ("first_row", ctypes.c_void_p), ("mc", ctypes.c_int64), ("first_pick", ctypes.c_int64),
+                ("cand_sites_dev", ctypes.c_void_p), ("shifted_dev", ctypes.c_void_p)]
+
+
+class DbGatherJob(ctypes.Structure):
+    """mrbf_db_gather_job: one start of mrbf_db_gather_batch"""
+    _fields_ = [("db", ctypes.c_void_p), ("n_idx", ctypes.c_int64), ("indices", ctypes.c_void_p), ("sites_out", ctypes.c_void_p),
+                ("values_out", ctypes.c_void_p), ("sites_dev", ctypes.c_void_p), ("values_dev", ctypes.c_void_p),
+                ("rc", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class Problem(ctypes.Structure):
     _fields_ = [("n", ctypes.c_int64), ("m", ctypes.c_int64), ("d", ctypes.c_int32), ("k", ctypes.c_int32),
                 ("kernel_id", ctypes.c_int32), ("poly_deg", ctypes.c_int32), ("a", ctypes.c_double), ("b", ctypes.c_double),
@@ -200,6 +218,15 @@ SIGNATURES = {
                                         ctypes.POINTER(Result)]),
     "mrbf_fit_batch": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.POINTER(FitJob), c_fp]),
     "mrbf_dispatch_fit_batch": (ctypes.c_int32, [ctypes.c_int64]),
+    "mrbf_db_create": (ctypes.c_int32, [c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.POINTER(c_vp)]),
+    "mrbf_db_append": (ctypes.c_int32, [c_vp, c_vp, ctypes.c_int64, c_vp, c_vp, ctypes.POINTER(ctypes.c_int64)]),
+    "mrbf_db_set_values": (ctypes.c_int32, [c_vp, c_vp, ctypes.c_int64, c_vp, c_vp]),
+    "mrbf_db_read": (ctypes.c_int32, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, c_vp, c_vp]),
+    "mrbf_db_dims": (ctypes.c_int32, [c_vp, ctypes.POINTER(ctypes.c_int64), c_ip, c_ip]),
+    "mrbf_db_free": (ctypes.c_int32, [c_vp, c_vp]),
+    "mrbf_db_box_batch": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(DbBoxJob), c_fp]),
+    "mrbf_db_gather_batch": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(DbGatherJob), c_fp]),
+    "mrbf_dispatch_db_batch": (ctypes.c_int32, [ctypes.c_int64, ctypes.c_int32]),
     "mrbf_debug_mfma_layout": (ctypes.c_int32, [c_vp, c_vp, c_vp, c_vp]),
     "mrbf_debug_potrf": (ctypes.c_int32, [c_vp, ctypes.c_int64, c_vp, ctypes.c_int32, c_ip, c_fp]),
     "mrbf_debug_env": (ctypes.c_int32, [ctypes.c_char_p]),

@@ -38,7 +38,7 @@ enum Slot {
     S_XC = 0, S_SQ, S_MEAN, S_PHI, S_PI, S_Q1, S_W1, S_G, S_R, S_TAU, S_RHS, S_T1, S_T2, S_IPIV, S_INFO,
     S_STAGE_A, S_STAGE_B, S_STAGE_C, S_STAGE_D, S_EVAL_E, S_EVAL_A, S_EVAL_J, S_EVAL_SA, S_EVAL_XC, S_EVAL_XSQ,
     S_OUT_A, S_OUT_B, S_CHOL_WS, S_MISC, S_MEGA_JOBS, S_MEGA_FLAGS, S_MEGA_WQ, S_MEGA_IT, S_BSOLVE_FLAGS, S_MEGA_TRACE, S_MEGA_JLOG,
-    S_T1W, S_PS_STATE, S_PS_STAT, S_PS_POLISH, S_BSOLVE_X, S_V0, S_QR_INV, S_DIAG_SCR, S_SMALL_WS, S_SMALL_DESC, S_SMALL_FLAGS, S_MEGA_STAT, S_BSOLVE_M, S_SMALL_CL, S_GW_PART, S_GW_RS, S_GW_GP, S_GW_M, S_CHECK_SCAL, S_TAIL_PART, S_PS_RANK, S_SD_IN, S_SD_OUT, S_SD_WS, S_NS_IN, S_NS_OUT, S_NS_WS, S_SD_STEP, S_SD_BATCH, S_AFF_BATCH, S_NS_BATCH, S_R4_BATCH, S_NSLOTS
+    S_T1W, S_PS_STATE, S_PS_STAT, S_PS_POLISH, S_BSOLVE_X, S_V0, S_QR_INV, S_DIAG_SCR, S_SMALL_WS, S_SMALL_DESC, S_SMALL_FLAGS, S_MEGA_STAT, S_BSOLVE_M, S_SMALL_CL, S_GW_PART, S_GW_RS, S_GW_GP, S_GW_M, S_CHECK_SCAL, S_TAIL_PART, S_PS_RANK, S_SD_IN, S_SD_OUT, S_SD_WS, S_NS_IN, S_NS_OUT, S_NS_WS, S_SD_STEP, S_SD_BATCH, S_AFF_BATCH, S_NS_BATCH, S_R4_BATCH, S_DB_BOX, S_DB_GATHER, S_DB_WS, S_NSLOTS
 };
 }  // namespace mrbf
 
@@ -145,6 +145,7 @@ struct mrbf_ctx {
     int small_cluster_ok = 0;    // the device is what the clusters' visibility argument assumes: gfx950, 8 XCDs x 32 CUs (context.hip)
     int small_timeouts = 0;      // barrier time-outs of clustered launches in a row (three: clusters off for this context)
     int live_models = 0, live_round4 = 0;  // handles created through this context and not yet released (MRBF_OPT_LIVE_HANDLES)
+    int live_dbs = 0;                      // likewise: resident site databases (db.hip)
     unsigned ps_rank_epoch = 0;  // launches of the PS ranking's wave kernel so far (part of the tag its exchanged records carry)
     int ps_multi_off = 0;        // the several-workgroup PS ranking timed out on this context (a device shared with other work): one workgroup per run from then on
     std::map<long, float> mega_best_ms;
@@ -166,6 +167,14 @@ struct mrbf_model {
     void *block = nullptr;   // one device allocation carved into the arrays above
     size_t block_bytes = 0;
     mrbf::ModelSlab *slab = nullptr;  // instead of `block`: the arrays are carved from an allocation shared with the other models of one mrbf_fit_batch call
+};
+
+// one start's resident site database (db.hip): rows 0 .. n - 1 of `sites` (cap x d) and `values` (cap x k), each an allocation of its own
+struct mrbf_db {
+    mrbf_ctx *ctx = nullptr;
+    int d = 0, k = 0;
+    int64_t n = 0, cap = 0;
+    double *sites = nullptr, *values = nullptr;
 };
 
 namespace mrbf {

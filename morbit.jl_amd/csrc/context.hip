@@ -416,7 +416,7 @@ int32_t mrbf_get_option(const mrbf_ctx *ctx, int32_t key, double *value) {
             *value = bytes;
             break;
         }
-        case MRBF_OPT_LIVE_HANDLES: *value = ctx->live_models + ctx->live_round4; break;
+        case MRBF_OPT_LIVE_HANDLES: *value = ctx->live_models + ctx->live_round4 + ctx->live_dbs; break;
         default: return -2;
     }
     return MRBF_OK;

@@ -113,6 +113,12 @@ int32_t mrbf_dispatch_round4_batch(int64_t n_starts, int32_t d) {
     return n_starts >= 1 && n_starts <= 65535 && d >= 1 && d <= 1024 ? MRBF_DISPATCH_DEVICE : MRBF_DISPATCH_REFERENCE;
 }
 
+// the box scans and row gathers of many resident databases in one call (db.hip): the start on a grid dimension; the kernels walk a row
+// with a wave whatever its length, so d only has the library's own limit
+int32_t mrbf_dispatch_db_batch(int64_t n_starts, int32_t d) {
+    return n_starts >= 1 && n_starts <= 65535 && d >= 1 && d <= 4096 ? MRBF_DISPATCH_DEVICE : MRBF_DISPATCH_REFERENCE;
+}
+
 int32_t mrbf_dispatch_fit(int64_t n_training, int64_t state_n0, int32_t state_q, int32_t state_n_accepted, int32_t same_sites) {
     if (state_n0 < 1 || state_n_accepted < 1 || !same_sites) return MRBF_FIT_FULL;
     if (state_n0 != state_q) return MRBF_FIT_FULL;  // the kept factor only covers the directions added by round 4
@@ -140,6 +146,9 @@ int32_t mrbf_dispatch_after(int32_t entry, int32_t rc) {
         // the call itself: -2 (the table refuses the shape: the single call, or the host mirror, per start); a start's own rc
         // (mrbf_round4_job.rc, what mrbf_round4 returned for it) reads as MRBF_ENTRY_ROUND4's
         case MRBF_ENTRY_ROUND4_BATCH: return rc == -2 || rc == -3 || rc == -5 || rc == MRBF_ESINGULAR || rc == MRBF_ENOMEM;
+        // the table refuses the shape: results_in_box_indices / the row copies on the host copy of the database; a job's own rc is an error
+        case MRBF_ENTRY_DB_BOX: return rc == -2;
+        case MRBF_ENTRY_DB_GATHER: return rc == -2;
         default: return 0;
     }
 }

@@ -1,0 +1,268 @@
+"""A start's evaluation database kept resident on the device (include/mrbf.h "resident site database", csrc/db.hip).
+
+`DeviceDatabase` mirrors the reference's ArrayDB (src/Databases.jl): sites and values in insertion order, a row's position being its
+id, appended to as the run goes.  `box_many` is results_in_box_indices (Databases.jl:324-327) with the filter's shifted rows and first
+pick (AffinelyIndependentPoints.jl:25, :53) for a batch of starts in one call, `gather_many` the row gathers of round 4 and the fit
+(RbfModel.jl:372, :747-757).  Their outputs are `DeviceView`s -- a device pointer with a shape -- which `_lib.as_ptr` and
+`rbf_model._as_fit_input` take like a device tensor, so the batched calls read them in place.
+
+A database keeps a host copy of its sites and values, as the caller's own database does: the small host-side steps (the filter's Y,
+the fall-backs to the host filter or to the single calls) need no read-back, and when the decision table (mrbf_dispatch_db_batch) sends a
+call to the host, the scan and the copies run on that copy.
+"""
+import ctypes
+
+import numpy as np
+
+from . import _lib
+
+_NAN = np.float64(np.nan)
+
+
+class DeviceView:
+    """`shape` doubles, row-major, at device address `ptr`, owned by the library (its lifetime is the view's, include/mrbf.h).
+    `host` (optional): a callable that returns the same rows from the host copy, for the code paths that want a NumPy array."""
+
+    def __init__(self, ptr, shape, host=None):
+        self.ptr, self.shape, self._host = int(ptr or 0), tuple(int(v) for v in shape), host
+
+    @property
+    def ndim(self):
+        return len(self.shape)
+
+    def data_ptr(self):
+        return self.ptr
+
+    def contiguous(self):
+        return self
+
+    def reshape(self, *shape):
+        shape = tuple(shape[0]) if len(shape) == 1 and isinstance(shape[0], (tuple, list)) else tuple(shape)
+        total = int(np.prod(self.shape, dtype=np.int64))
+        known = int(np.prod([v for v in shape if v != -1], dtype=np.int64))
+        shape = tuple((total // known if known else 0) if v == -1 else int(v) for v in shape)
+        assert int(np.prod(shape, dtype=np.int64)) == total, "reshape of %r to %r" % (self.shape, shape)
+        host = self._host
+        return DeviceView(self.ptr, shape, None if host is None else (lambda: host().reshape(shape)))
+
+    def __array__(self, dtype=None, copy=None):
+        if self._host is None:
+            raise TypeError("this DeviceView has no host copy")
+        a = np.asarray(self._host(), dtype=np.float64).reshape(self.shape)
+        return a if dtype is None else a.astype(dtype, copy=False)
+
+
+class DeviceDatabase:
+    """mrbf_db: the sites (d) and values (k) of one start, rows in insertion order, with a host copy (`sites`, `values`)."""
+
+    def __init__(self, d, k, ctx=None, capacity=0):
+        self.ctx = ctx or _lib.default_context()
+        self.d, self.k = int(d), int(k)
+        h = _lib.c_vp()
+        self.ctx.check(self.ctx.lib.mrbf_db_create(self.ctx.h, self.d, self.k, int(capacity), ctypes.byref(h)))
+        self.h = h
+        self._n = 0
+        self._S = np.empty((max(int(capacity), 16), self.d))
+        self._V = np.empty((max(int(capacity), 16), self.k))
+
+    def __len__(self):
+        return self._n
+
+    @property
+    def sites(self):
+        return self._S[: self._n]
+
+    @property
+    def values(self):
+        return self._V[: self._n]
+
+    def _host_rows(self, a):
+        if hasattr(a, "data_ptr"):          # a torch tensor, host or device
+            return a.detach().cpu().numpy()
+        return a
+
+    def append(self, sites, values=None):
+        """new_result! for m rows: `sites` m x d, `values` m x k or None (unevaluated rows, stored as NaN: round 3, RbfModel.jl:303);
+        NumPy arrays or torch tensors (a device tensor is read in place).  Returns the position of the first new row."""
+        S = sites.contiguous() if hasattr(sites, "data_ptr") else _lib.host_f64(sites).reshape(-1, self.d)
+        m = int(S.shape[0]) if S.ndim == 2 else int(S.numel() // self.d)
+        V = None
+        if values is not None:
+            V = values.contiguous() if hasattr(values, "data_ptr") else _lib.host_f64(values).reshape(m, self.k)
+        first = ctypes.c_int64(-1)
+        self.ctx.check(self.ctx.lib.mrbf_db_append(self.ctx.h, self.h, m, _lib.as_ptr(S), _lib.as_ptr(V), ctypes.byref(first)))
+        if self._n + m > self._S.shape[0]:
+            cap = max(2 * self._S.shape[0], self._n + m)
+            self._S = np.concatenate([self._S[: self._n], np.empty((cap - self._n, self.d))])
+            self._V = np.concatenate([self._V[: self._n], np.empty((cap - self._n, self.k))])
+        self._S[self._n: self._n + m] = np.asarray(self._host_rows(S), dtype=np.float64).reshape(m, self.d)
+        self._V[self._n: self._n + m] = _NAN if V is None else np.asarray(self._host_rows(V), dtype=np.float64).reshape(m, self.k)
+        self._n += m
+        assert first.value == self._n - m
+        return int(first.value)
+
+    def set_values(self, indices, values):
+        """eval_missing! (Databases.jl:258-277): the values of the rows `indices` (distinct positions)"""
+        idx = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
+        V = values.contiguous() if hasattr(values, "data_ptr") else _lib.host_f64(values).reshape(idx.size, self.k)
+        self.ctx.check(self.ctx.lib.mrbf_db_set_values(self.ctx.h, self.h, idx.size, _lib.as_ptr(idx), _lib.as_ptr(V)))
+        if idx.size:
+            self._V[idx] = np.asarray(self._host_rows(V), dtype=np.float64).reshape(idx.size, self.k)
+
+    def read(self, first=0, m=None):
+        """rows first .. first + m - 1 as the device holds them -> (sites, values)"""
+        m = self._n - first if m is None else int(m)
+        S, V = np.empty((m, self.d)), np.empty((m, self.k))
+        self.ctx.check(self.ctx.lib.mrbf_db_read(self.ctx.h, self.h, int(first), m, _lib.as_ptr(S), _lib.as_ptr(V)))
+        return S, V
+
+    def dims(self):
+        n, d, k = ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int32()
+        self.ctx.check(self.ctx.lib.mrbf_db_dims(self.h, ctypes.byref(n), ctypes.byref(d), ctypes.byref(k)))
+        return int(n.value), int(d.value), int(k.value)
+
+    def free(self):
+        if getattr(self, "h", None) and self.ctx.h:
+            self.ctx.lib.mrbf_db_free(self.ctx.h, self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class BoxResult:
+    """one start of `box_many`: `indices` (database positions of the candidates, ascending), `mc`, `first_pick` (position among the
+    candidates, -1 without candidates), `first_row` (its shifted row), `sites` / `shifted` (mc x d: DeviceViews, or NumPy arrays when
+    the call ran on the host copy), `rc`"""
+    __slots__ = ("indices", "mc", "first_pick", "first_row", "sites", "shifted", "rc")
+
+
+def _box_host(db, lb, ub, x0, exclude, p, zero_first_pick):
+    from .sampling import results_in_box_indices
+
+    r = BoxResult()
+    r.indices = [int(i) for i in results_in_box_indices(db.sites, lb, ub, exclude)]
+    r.mc, r.rc = len(r.indices), 0
+    r.sites = db.sites[r.indices].copy() if r.mc else np.empty((0, db.d))
+    r.shifted = r.sites - x0
+    r.first_pick, r.first_row = -1, None
+    if r.mc:
+        r.first_pick = int(np.argmax(np.linalg.norm(r.shifted, ord=p, axis=1)))
+        r.first_row = r.shifted[r.first_pick].copy()
+        if zero_first_pick:
+            r.shifted[r.first_pick] = 0.0
+    return r
+
+
+def box_many(dbs, lbs, ubs, x0s, excludes, p=np.inf, zero_first_pick=True, ctx=None, stats=None):
+    """results_in_box_indices + shifted rows + the filter's first pick for a list of databases of one d in ONE call
+    (mrbf_db_box_batch) -> list of BoxResult.  `excludes[p]`: positions to leave out (duplicates and positions outside the database
+    allowed).  Where mrbf_dispatch_db_batch sends the call to the host (or it returns -2), the same runs on the host copies;
+    stats["path"] = "device" or "host".  The views stay valid until the next `box_many` on the context."""
+    ns = len(dbs)
+    stats = stats if stats is not None else {}
+    ctx = ctx or (dbs[0].ctx if ns else _lib.default_context())
+    d = dbs[0].d if ns else 1
+    assert all(db.d == d for db in dbs), "the databases of a call share d"
+    x0s = [_lib.host_f64(x).reshape(d) for x in x0s]
+
+    def host():
+        stats["path"] = "host"
+        return [_box_host(dbs[q], np.asarray(lbs[q], dtype=np.float64), np.asarray(ubs[q], dtype=np.float64), x0s[q], excludes[q], p,
+                          zero_first_pick) for q in range(ns)]
+
+    if ctx.lib.mrbf_dispatch_db_batch(ns, d) != _lib.DISPATCH_DEVICE:
+        return host()
+    jobs = (_lib.DbBoxJob * ns)()
+    keep = []
+    for q, db in enumerate(dbs):
+        lb, ub = _lib.host_f64(lbs[q]).reshape(d), _lib.host_f64(ubs[q]).reshape(d)
+        ex = np.ascontiguousarray(list(excludes[q]), dtype=np.int64).reshape(-1)
+        idx, row = np.empty(max(len(db), 1), dtype=np.int64), np.empty(d)
+        keep.append((lb, ub, ex, idx, row))
+        J = jobs[q]
+        J.db, J.lb, J.ub, J.x0 = db.h, lb.ctypes.data, ub.ctypes.data, x0s[q].ctypes.data
+        J.n_exclude, J.exclude = ex.size, ex.ctypes.data if ex.size else None
+        J.zero_first_pick, J.indices_out, J.first_row = 1 if zero_first_pick else 0, idx.ctypes.data, row.ctypes.data
+    ms = ctypes.c_float(0.0)
+    rc = ctx.lib.mrbf_db_box_batch(ctx.h, ns, d, 1 if np.isinf(p) else 0, jobs, ctypes.byref(ms))
+    if rc != 0:
+        if ctx.lib.mrbf_dispatch_after(_lib.ENTRY_DB_BOX, rc):
+            return host()
+        ctx.check(rc)
+    out = []
+    for q, db in enumerate(dbs):
+        J, (_, _, _, idx, row) = jobs[q], keep[q]
+        if J.rc != 0:
+            raise _lib.MrbfError(J.rc, "mrbf_db_box_batch: start %d" % q)
+        r = BoxResult()
+        r.mc, r.first_pick, r.rc = int(J.mc), int(J.first_pick), 0
+        r.indices = [int(v) for v in idx[: r.mc]]
+        r.first_row = row if r.mc else None
+        x0, cand, zero = x0s[q], r.indices, bool(zero_first_pick)
+
+        def host_shifted(db=db, cand=cand, x0=x0, pick=r.first_pick, zero=zero):
+            S = db.sites[cand] - x0
+            if zero and pick >= 0:
+                S[pick] = 0.0
+            return S
+
+        r.sites = DeviceView(J.cand_sites_dev, (r.mc, d), lambda db=db, cand=cand: db.sites[cand])
+        r.shifted = DeviceView(J.shifted_dev, (r.mc, d), host_shifted)
+        out.append(r)
+    stats.update(path="device", ms_total=float(ms.value))
+    return out
+
+
+class GatherResult:
+    """one start of `gather_many`: `sites` (n_idx x d) and `values` (n_idx x k) in the order of the index list -- DeviceViews, or
+    NumPy arrays when the call ran on the host copy -- and `rc` (-3: an index outside the database; sites and values are None)"""
+    __slots__ = ("sites", "values", "rc")
+
+
+def gather_many(dbs, index_lists, ctx=None, stats=None):
+    """the rows `index_lists[p]` (any order, repeats allowed) of every database of one d in ONE call (mrbf_db_gather_batch) -> list of
+    GatherResult.  Falls back to the host copies like `box_many`.  The views stay valid until the next `gather_many` on the context."""
+    ns = len(dbs)
+    stats = stats if stats is not None else {}
+    ctx = ctx or (dbs[0].ctx if ns else _lib.default_context())
+    d = dbs[0].d if ns else 1
+    assert all(db.d == d for db in dbs), "the databases of a call share d"
+    lists = [np.ascontiguousarray(list(l), dtype=np.int64).reshape(-1) for l in index_lists]
+
+    def host():
+        stats["path"] = "host"
+        out = []
+        for db, idx in zip(dbs, lists):
+            r = GatherResult()
+            ok = bool(np.all((idx >= 0) & (idx < len(db))))
+            r.rc = 0 if ok else -3
+            r.sites, r.values = (db.sites[idx].copy(), db.values[idx].copy()) if ok else (None, None)
+            out.append(r)
+        return out
+
+    if ctx.lib.mrbf_dispatch_db_batch(ns, d) != _lib.DISPATCH_DEVICE:
+        return host()
+    jobs = (_lib.DbGatherJob * ns)()
+    for q, db in enumerate(dbs):
+        jobs[q].db, jobs[q].n_idx, jobs[q].indices = db.h, lists[q].size, lists[q].ctypes.data if lists[q].size else None
+    ms = ctypes.c_float(0.0)
+    rc = ctx.lib.mrbf_db_gather_batch(ctx.h, ns, d, jobs, ctypes.byref(ms))
+    if rc != 0:
+        if ctx.lib.mrbf_dispatch_after(_lib.ENTRY_DB_GATHER, rc):
+            return host()
+        ctx.check(rc)
+    out = []
+    for q, db in enumerate(dbs):
+        r, idx = GatherResult(), lists[q]
+        r.rc = int(jobs[q].rc)
+        r.sites = r.values = None
+        if r.rc == 0:
+            r.sites = DeviceView(jobs[q].sites_dev, (idx.size, d), lambda db=db, idx=idx: db.sites[idx])
+            r.values = DeviceView(jobs[q].values_dev, (idx.size, db.k), lambda db=db, idx=idx: db.values[idx])
+        out.append(r)
+    stats.update(path="device", ms_total=float(ms.value))
+    return out

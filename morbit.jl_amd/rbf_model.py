@@ -276,6 +276,39 @@ def update_models_many(cfgs, sites_list, values_list, deltas, fully_linear=False
     return mods
 
 
+def update_models_resident(cfgs, dbs, index_lists, deltas, fully_linear=False, ctx=None, stats=None):
+    """`update_models_many` on resident databases (database.DeviceDatabase): start p's training set is the rows `index_lists[p]` of
+    `dbs[p]` (get_site / get_value over _collect_indices(meta), RbfModel.jl:747-757), gathered on the device for all starts in ONE call
+    (mrbf_db_gather_batch) and handed to mrbf_fit_batch as device views: no site or value crosses PCIe.  Returns exactly what
+    `update_models_many(cfgs, [db.sites[idx]], [db.values[idx]], ...)` returns, by the same decision-table answers; wherever that
+    driver takes the loop of single fits, or the gather itself goes to the host (mrbf_dispatch_db_batch), the rows come from the
+    databases' host copies."""
+    from . import database
+
+    ns = len(dbs)
+    by_d = {}
+    for p in range(ns):
+        by_d.setdefault(dbs[p].d, []).append(p)
+    per = lambda v: list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v] * ns
+    cfgs, deltas, fls = per(cfgs), per(deltas), per(fully_linear)
+    mods, status, ms, paths = [None] * ns, [0] * ns, 0.0, []
+    for members in by_d.values():   # one gather and one fit call per d (a gather's views last until the next gather)
+        got = database.gather_many([dbs[p] for p in members], [index_lists[p] for p in members], ctx=ctx)
+        for p, g in zip(members, got):
+            if g.rc != 0:
+                raise _lib.MrbfError(g.rc, "update_models_resident: start %d has a training index outside its database" % p)
+        st = {}
+        res = update_models_many([cfgs[p] for p in members], [g.sites for g in got], [g.values for g in got], [deltas[p] for p in members],
+                                 [fls[p] for p in members], ctx=ctx, stats=st)
+        for pos, p in enumerate(members):
+            mods[p], status[p] = res[pos], st["status"][pos]
+        ms += st["ms_total"]
+        paths.append(st["path"])
+    if stats is not None:
+        stats.update(path="batch" if "batch" in paths else "loop", status=status, ms_total=ms)
+    return mods
+
+
 init_model = update_model      # RbfModel.jl:738-741 delegates
 improve_model = update_model   # RbfModel.jl:770-776 delegates
 

@@ -641,3 +641,207 @@ def _rbf_round4(sites, lb_2, ub_2, x, delta, indices_found_so_far, cfg, ctx=None
             cols.append(n0 + pos)
             N += 1
     return round4
+
+
+# ---- the many-start drivers on resident databases (database.DeviceDatabase): the twins of find_suitable_points_many and
+# rbf_round4_many.  The box scans, the shifted rows, the filter's first pick and the gathers of the start sites run on the device for
+# all starts of a call (mrbf_db_box_batch, mrbf_db_gather_batch) and the batched calls read the resulting device views in place; the
+# small host-side steps (the filter's Y, the Householder start) and every fall-back use the databases' host copies.
+
+
+def _affine_select_batch_views(items, d, p=np.inf, ctx=None):
+    """`affine_select_batch_device` with the candidates given as anything `_lib.as_ptr` takes with a `shape` (a DeviceView is read in
+    place): `items` = one (Sd, qr, want, pivot_val) per start -> (rc, [(positions, final Z)] or None, ms)"""
+    ctx = ctx or _lib.default_context()
+    n = len(items)
+    jobs = (_lib.AffineJob * max(n, 1))()
+    keep = []
+    for k, (Sd, qr, want, pivot) in enumerate(items):
+        Q0 = np.asfortranarray(qr.Q)
+        picks = np.empty(max(want, 1), dtype=np.int64)
+        Zbuf = np.empty((max(d - qr.j, 1), d))                          # (column-major d x dz)
+        keep.append((Sd, Q0, picks, Zbuf))
+        jobs[k].mc, jobs[k].j0, jobs[k].max_picks, jobs[k].pivot_val = int(Sd.shape[0]), qr.j, want, float(pivot)
+        jobs[k].shifted, jobs[k].Q0 = _lib.as_ptr(Sd), Q0.ctypes.data
+        jobs[k].picked_out, jobs[k].Z_out = picks.ctypes.data, Zbuf.ctypes.data
+    ms = ctypes.c_float(0.0)
+    rc = ctx.lib.mrbf_affine_select_batch(ctx.h, n, d, 1 if np.isinf(p) else 0, jobs, ctypes.byref(ms))
+    if rc != 0:
+        if not ctx.lib.mrbf_dispatch_after(_lib.ENTRY_AFFINE_BATCH, rc):
+            ctx.check(rc)
+        return rc, None, 0.0
+    res = []
+    for k, (Sd, qr, want, pivot) in enumerate(items):
+        _, _, picks, Zbuf = keep[k]
+        got = [int(v) for v in picks[: jobs[k].n_picked]]
+        res.append((got, Zbuf[: d - qr.j - len(got)].T.copy()))
+    return 0, res, float(ms.value)
+
+
+def find_suitable_points_resident(dbs, lbs, ubs, xs, x_indices, piv_val, already_inspected_indices=None, Ys=None, Zs=None, n_missing=None,
+                                  collect_improving_directions=True, stats=None, ctx=None):
+    """`find_suitable_points_many` on resident databases: returns exactly its list of `_find_suitable_points` tuples.  The box scan,
+    the shifted rows and the first pick of every start come from ONE mrbf_db_box_batch call per d (first pick's row zeroed: the state the
+    pick loop expects); the first reflector starts on the host from the returned row; the pick loops of the starts the decision table
+    sends to the device (mrbf_dispatch_affine per start, mrbf_dispatch_affine_batch per group) read the shifted rows in place.  A start
+    the table keeps on the host runs the host filter on the host copy, a batch the library refuses (rc -2) continues with the single
+    call per start on the same view; where mrbf_dispatch_db_batch sends the scan to the host the whole call is the host driver's."""
+    from . import database
+
+    ns = len(dbs)
+    opt = lambda seq, p: None if seq is None else seq[p]
+    lib = _lib.load() if ns else None
+    stats = stats if stats is not None else {}
+    by_d = {}
+    for p in range(ns):
+        by_d.setdefault(dbs[p].d, []).append(p)
+    if any(lib.mrbf_dispatch_db_batch(len(m), d) != _lib.DISPATCH_DEVICE for d, m in by_d.items()):
+        return find_suitable_points_many([db.sites for db in dbs], lbs, ubs, xs, x_indices, piv_val, already_inspected_indices, Ys, Zs,
+                                         n_missing, collect_improving_directions, stats=stats, ctx=ctx)
+    res, batched = [None] * ns, []
+    for d, members in by_d.items():
+        xs_m = [np.asarray(xs[p], dtype=np.float64) for p in members]
+        excl = [[x_indices[p], *(opt(already_inspected_indices, p) or ())] for p in members]
+        boxes = database.box_many([dbs[p] for p in members], [lbs[p] for p in members], [ubs[p] for p in members], xs_m, excl,
+                                  p=np.inf, zero_first_pick=True, ctx=ctx)
+        filters, device = {}, []
+        for pos, p in enumerate(members):
+            x, B, sites = xs_m[pos], boxes[pos], dbs[p].sites
+            nm = opt(n_missing, p)
+            on_host_copy = isinstance(B.shifted, np.ndarray)    # the scan itself fell back: everything from the host copy
+            flt = AffinelyIndependentPointFilter(x, [] if not on_host_copy else [sites[i] for i in B.indices], n=x.size if nm is None else nm,
+                                                 Y=opt(Ys, p), Z=opt(Zs, p), p=np.inf, pivot_val=piv_val)
+            filters[p] = flt
+            if B.mc == 0:
+                picks = []
+            elif on_host_copy or lib.mrbf_dispatch_affine(B.mc - 1, d) != _lib.DISPATCH_DEVICE:
+                if not on_host_copy:
+                    flt.shifted = [sites[i] - x for i in B.indices]
+                picks = flt.collect()
+            else:
+                # `_begin` with the device's first pick: Y gains its row, the factorisation its first reflector
+                i = B.first_pick
+                qr = _GrowingQR(d, flt.Y)
+                flt.Y = np.hstack([flt.Y, B.first_row[:, None]])
+                qr.append(B.first_row)
+                flt.Z = qr.complement(flt.p)
+                device.append((p, pos, [i], qr, min(flt.n - 1, d - qr.j)))
+                continue
+            res[p] = ([B.indices[i] for i in picks], flt, B.indices)
+        if device:
+            rc = -2
+            if lib.mrbf_dispatch_affine_batch(len(device), d, 1) == _lib.DISPATCH_DEVICE:
+                rc, got_all, _ = _affine_select_batch_views([(boxes[pos].shifted, qr, want, piv_val) for (_, pos, _, qr, want) in device], d,
+                                                            np.inf, ctx=ctx)
+            for k, (p, pos, out, qr, want) in enumerate(device):
+                flt, B = filters[p], boxes[pos]
+                flt.ctx = flt.ctx or ctx
+                got, Z = got_all[k] if rc == 0 else flt._select_device(B.shifted, qr, want)   # refused: the single call, from the same state
+                S_got = dbs[p].sites[[B.indices[g] for g in got]] - xs_m[pos] if got else np.empty((0, d))
+                if got:
+                    flt.Y = np.hstack([flt.Y, S_got.T])
+                    flt.Z = Z
+                    out.extend(got)
+                res[p] = ([B.indices[i] for i in out], flt, B.indices)
+                if rc == 0:
+                    batched.append(p)
+    stats["path"] = "batch" if batched else "loop"
+    stats["batched"] = sorted(batched)
+    final = []
+    for p in range(ns):
+        picked, flt, cand = res[p]
+        dirs = [flt.Z[:, j].copy() for j in range(flt.Z.shape[1])][::-1] if collect_improving_directions else None
+        final.append((picked, dirs, cand, flt.Y, flt.Z))
+    return final
+
+
+def _round4_batch_views(items, d, ctx=None):
+    """`rbf_round4_batch_device` with the sites given as anything `_lib.as_ptr` takes with a `shape` (DeviceViews are read in place):
+    `items` = one (cfg, start_sites, cand_sites, delta) per start -> (rc, [(rc_p, positions)] or None, ms)"""
+    ctx = ctx or _lib.default_context()
+    n = len(items)
+    jobs = (_lib.Round4Job * max(n, 1))()
+    keep = []
+    for k, (cfg, C0, Xc, delta) in enumerate(items):
+        kid, a, b = rm._get_kernel_params(delta, cfg)
+        mc = int(Xc.shape[0])
+        acc = np.zeros(max(mc, 1), dtype=np.int32)
+        keep.append((C0, Xc, acc))
+        J = jobs[k]
+        J.n0, J.mc, J.start_sites, J.cand_sites = int(C0.shape[0]), mc, _lib.as_ptr(C0), _lib.as_ptr(Xc) if mc else None
+        J.kernel_id, J.poly_deg, J.a, J.b = kid, cfg.polynomial_degree, a, b
+        J.max_points, J.theta_pivot_cholesky, J.accepted_out = int(cfg.max_model_points), float(cfg.θ_pivot_cholesky), acc.ctypes.data
+    ms = ctypes.c_float(0.0)
+    rc = ctx.lib.mrbf_round4_batch(ctx.h, n, d, jobs, ctypes.byref(ms))
+    if rc != 0:
+        if not ctx.lib.mrbf_dispatch_after(_lib.ENTRY_ROUND4_BATCH, rc):
+            ctx.check(rc)
+        return rc, None, 0.0
+    return 0, [(int(jobs[k].rc), [int(v) for v in keep[k][2][: jobs[k].n_accepted]]) for k in range(n)], float(ms.value)
+
+
+def rbf_round4_resident(dbs, lb2s, ub2s, xs, deltas, indices_found_list, cfgs, ctx=None, stats=None, min_starts=None):
+    """`rbf_round4_many` on resident databases: returns exactly its lists of database indices in acceptance order, by the same
+    decision-table answers and the same rule for when the batch pays.  The candidates of every start come from ONE mrbf_db_box_batch
+    call per d (the box of round 4 without the sites found so far), the start sites of the starts that form a batch from ONE
+    mrbf_db_gather_batch call; mrbf_round4_batch reads both views in place (a box view and a gather view are alive at once).  Every
+    start that `rbf_round4_many` would hand to `_rbf_round4` gets it here too, on the database's host copy."""
+    from . import database
+
+    ns = len(dbs)
+    per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * ns
+    cfgs, deltas = per(cfgs), per(deltas)
+    out = [None] * ns
+    lib = _lib.load() if ns else None
+    single = lambda p: _rbf_round4(dbs[p].sites, lb2s[p], ub2s[p], xs[p], deltas[p], indices_found_list[p], cfgs[p], ctx=ctx)
+    by_d = {}
+    for p in range(ns):
+        by_d.setdefault(dbs[p].d, []).append(p)
+    batched, fallback = [], []
+    for d, all_members in by_d.items():
+        boxes = database.box_many([dbs[p] for p in all_members], [lb2s[p] for p in all_members], [ub2s[p] for p in all_members],
+                                  [xs[p] for p in all_members], [list(indices_found_list[p]) for p in all_members], p=np.inf,
+                                  zero_first_pick=False, ctx=ctx)
+        members, prepared = [], {}
+        for pos, p in enumerate(all_members):
+            cfg, found, B = cfgs[p], list(indices_found_list[p]), boxes[pos]
+            max_points = (d + 1) * (d + 2) // 2 if cfg.max_model_points <= 0 else cfg.max_model_points
+            if cfg.use_max_points:
+                out[p] = single(p)
+            elif not (len(found) < max_points and B.mc):
+                out[p] = []
+            elif lib.mrbf_dispatch_round4(len(found), d, cfg.polynomial_degree, B.mc) != _lib.DISPATCH_DEVICE:
+                out[p] = single(p)
+            else:
+                prepared[p] = (cfg, found, B, deltas[p])
+                members.append(p)
+        if not members:
+            continue
+        pays = len(members) >= min_starts if min_starts is not None else round4_batch_pays(len(members), max(prepared[p][2].mc for p in members))
+        if not pays or lib.mrbf_dispatch_round4_batch(len(members), d) != _lib.DISPATCH_DEVICE:
+            for p in members:
+                out[p] = single(p)
+            continue
+        starts = database.gather_many([dbs[p] for p in members], [prepared[p][1] for p in members], ctx=ctx)
+        for p, g in zip(members, starts):
+            if g.rc != 0:
+                raise _lib.MrbfError(g.rc, "rbf_round4_resident: start %d has a found index outside its database" % p)
+        rc, res, _ = _round4_batch_views([(prepared[p][0], g.sites, prepared[p][2].sites, prepared[p][3]) for p, g in zip(members, starts)], d, ctx=ctx)
+        for pos, p in enumerate(members):
+            if rc != 0:                                   # refused: the single call per start
+                out[p] = single(p)
+                continue
+            rc_p, accepted = res[pos]
+            if rc_p == 0:
+                out[p] = [prepared[p][2].indices[a] for a in accepted]
+                batched.append(p)
+            elif lib.mrbf_dispatch_after(_lib.ENTRY_ROUND4_BATCH, rc_p):
+                out[p] = single(p)
+                fallback.append(p)
+            else:
+                (ctx or _lib.default_context()).check(rc_p)
+    if stats is not None:
+        stats["path"] = "batch" if batched else "loop"
+        stats["batched"] = sorted(batched)
+        stats["fallback"] = sorted(fallback)
+    return out
