@@ -424,6 +424,72 @@ typedef struct {
 } mrbf_db_gather_job;               /* 64 bytes */
 int32_t mrbf_db_gather_batch(mrbf_ctx *ctx, int64_t n_starts, int32_t d, mrbf_db_gather_job *jobs, float *ms_total);
 
+/* mrbf_db_append and mrbf_db_set_values for a batch of starts (db.hip): one packed upload, one launch whose grid spans all starts and
+ * one synchronisation per call, whatever n_starts -- the trial points of an iteration and eval_missing! of every start.  Every
+ * database is left bit-identical to the per-start calls.  sites / values: host or device (detected per pointer; device rows are read
+ * in place); indices: host, distinct positions.  A database may appear at most once per call; the databases may differ in d and k.
+ * Returns 0; -2 (nothing written) when mrbf_dispatch_db_batch(n_starts, 1) refuses the batch; an invalid field of a job is an invalid
+ * `jobs` (-3).  mrbf_db_set_values_batch: an index outside the database sets that job's rc to -4, nothing of that job is written and
+ * the others are not disturbed. */
+typedef struct {
+    mrbf_db *db;
+    int64_t m;
+    const double *sites;            /* m x d row-major, host or device */
+    const double *values;           /* m x k row-major, host or device; NULL: unevaluated rows, stored as NaN */
+    int64_t first_index;            /* out: the position of the first new row */
+    int32_t rc;                     /* out */
+    int32_t reserved;
+} mrbf_db_append_job;               /* 48 bytes */
+int32_t mrbf_db_append_batch(mrbf_ctx *ctx, int64_t n_starts, mrbf_db_append_job *jobs, float *ms_total);
+typedef struct {
+    mrbf_db *db;
+    int64_t m;
+    const int64_t *indices;         /* host, m distinct positions */
+    const double *values;           /* m x k row-major, host or device */
+    int32_t rc;                     /* out */
+    int32_t reserved;
+} mrbf_db_set_values_job;           /* 40 bytes */
+int32_t mrbf_db_set_values_batch(mrbf_ctx *ctx, int64_t n_starts, mrbf_db_set_values_job *jobs, float *ms_total);
+
+/* Round 3 of the training-site selection for a batch of starts (round3.hip, host logic in round3_host.hpp): _rbf_round3
+ * (src/models/RbfModel.jl:269-307) with the rebuild along the coordinate axes it falls back to (:286-289 -> :633-637), and the
+ * improvement step prepare_improve_model (:699-732), written straight into the resident databases.
+ * MRBF_R3_UPDATE, per start: n_new = max(0, min(n_missing, max_new)); for i < n_new, len = intersect_box(x, dir_i, lb, ub; :absmax)
+ * (utilities.jl:126-221: zero components are skipped, an on-bound component gives Inf or 0 by sign and sense, sigma+ is the minimum
+ * of the entries >= 0, sigma- the maximum of the others, NaN included, an empty set gives 0, |sigma+| >= |sigma-| picks; a zero
+ * direction gives Inf), offset = len .* dir and the new point x .+ offset, each rounded once.  Direction i fails iff
+ * norm(offset, Inf) <= pivot_val (the maximum propagates NaN: a NaN norm does not fail).  If a direction fails and
+ * ensure_fully_linear && !force_rebuild, nothing of that attempt is kept and the start is redone inside the call along the
+ * coordinate axes with n_new = max(0, min(d, max_new)): status = MRBF_R3_REBUILT, fully_linear = n_new >= d and no axis fails,
+ * n_dirs_used = n_new (of the axes).  Otherwise fully_linear = n_new >= n_missing and no direction fails.  (Whether round 2 found
+ * sites, RbfModel.jl:631, is the caller's business.)
+ * MRBF_R3_IMPROVE: direction 0 alone; its point is appended iff norm(offset, Inf) > pivot_val (:718: a NaN norm appends nothing);
+ * n_new is 0 or 1, fully_linear = n_new == 1 && n_dirs == 1, n_dirs_used = min(n_dirs, 1).
+ * The n_new points are appended to the start's database in direction order as unevaluated rows (NaN values); first_index is the
+ * position of the first; the same rows come back in new_sites_out.  The allocation grows by the rule of mrbf_db_append before the
+ * first launch (room for the larger of the first attempt and the rebuild); earlier rows keep their bits.
+ * One packed upload, at most four launches whose grids span all starts (two when no job can rebuild), one read-back.
+ * Returns 0; -2 (nothing written) when mrbf_dispatch_db_batch refuses the shape; an invalid field, a database of another d or
+ * context or one named twice is an invalid `jobs` (-4).  n_dirs < n_new (the reference's @assert, :278; with dirs == NULL n_dirs is
+ * d) sets the job's own rc to -3, leaves its outputs and its database untouched and does not fail the others. */
+enum { MRBF_R3_UPDATE = 0, MRBF_R3_IMPROVE = 1 };
+enum { MRBF_R3_DONE = 0, MRBF_R3_REBUILT = 1 };
+typedef struct {
+    mrbf_db *db;
+    const double *x, *lb, *ub;      /* host, d doubles each: x, lb_1, ub_1 (local_bounds of Delta_1) */
+    double pivot_val;               /* piv_val_1 */
+    const double *dirs;             /* d x n_dirs column-major, host or device (a Z_out of mrbf_affine_select[_batch] is read in place);
+                                       NULL: the coordinate axes, n_dirs = d (force_rebuild, RbfModel.jl:568) */
+    int32_t n_dirs, reversed;       /* reversed != 0: direction i is column n_dirs - 1 - i (reverse(eachcol(Z)), :232) */
+    int32_t n_missing, max_new;
+    int32_t ensure_fully_linear, force_rebuild, mode;
+    int32_t rc;                     /* out */
+    double *new_sites_out;          /* host, room for max(min(n_missing, max_new), min(d, max_new)) x d; may be NULL */
+    int64_t first_index;            /* out: the database position of the first new row */
+    int32_t n_new, fully_linear, status, n_dirs_used;   /* out */
+} mrbf_round3_job;                  /* 112 bytes */
+int32_t mrbf_db_round3_batch(mrbf_ctx *ctx, int64_t n_starts, int32_t d, mrbf_round3_job *jobs, float *ms_total);
+
 /* debug / test hooks (exported so the parity tests can pin kernel-level behaviour) */
 /* Environment switches.  The library reads a number of MRBF_* variables (schedule experiments of the persistent factorisation,
  * earlier forms of kernels kept selectable for A/B runs, diagnostics: INTEGRATION.md "Tuning knobs").  NONE of them is honoured
@@ -770,6 +836,8 @@ int32_t mrbf_ps_step_batch(mrbf_ctx *ctx, int64_t n_starts, const mrbf_ps_proble
  *   mrbf_dispatch_db_batch   results_in_box_indices (src/Databases.jl:324-327) and the row gathers of n_starts resident databases in one
  *                            call (mrbf_db_box_batch, mrbf_db_gather_batch): device iff 1 <= n_starts <= 65535 (a grid dimension) and
  *                            1 <= d <= 4096; otherwise the scan and the copies run on the caller's host copy of the database.
+ *                            mrbf_db_round3_batch, mrbf_db_append_batch and mrbf_db_set_values_batch (MRBF_ENTRY_DB_ROUND3,
+ *                            _DB_APPEND_BATCH, _DB_SET_VALUES_BATCH) are routed by the same rule.
  *   mrbf_dispatch_after      the return code rc of a device entry point (MRBF_ENTRY_*) that means "take the reference method
  *                            for this call" (start set without the tail or rank deficient, limits of the device path) rather
  *                            than an error: 1 = fall back, 0 = rc is what it says. */
@@ -778,7 +846,8 @@ enum { MRBF_FIT_FULL = 0, MRBF_FIT_FROM_ROUND4 = 1 };
 enum { MRBF_ENTRY_ROUND4 = 1, MRBF_ENTRY_FIT_FROM_ROUND4 = 2, MRBF_ENTRY_PS_STEP = 3, MRBF_ENTRY_BACKTRACK = 4, MRBF_ENTRY_AFFINE = 5,
        MRBF_ENTRY_SD = 6, MRBF_ENTRY_NORMAL = 7, MRBF_ENTRY_SD_STEP = 8, MRBF_ENTRY_SD_BATCH = 9, MRBF_ENTRY_AFFINE_BATCH = 10,
        MRBF_ENTRY_FIT_BATCH = 11, MRBF_ENTRY_NORMAL_BATCH = 12, MRBF_ENTRY_ROUND4_BATCH = 13, MRBF_ENTRY_PS_BATCH = 14,
-       MRBF_ENTRY_DB_BOX = 15, MRBF_ENTRY_DB_GATHER = 16 };
+       MRBF_ENTRY_DB_BOX = 15, MRBF_ENTRY_DB_GATHER = 16, MRBF_ENTRY_DB_ROUND3 = 17, MRBF_ENTRY_DB_APPEND_BATCH = 18,
+       MRBF_ENTRY_DB_SET_VALUES_BATCH = 19 };
 int32_t mrbf_dispatch_ps(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_ps_batch(int64_t n_starts, int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints,
                                int32_t n_lin_constraints, int32_t n_foreign);

@@ -67,6 +67,11 @@ ENTRY_ROUND4_BATCH = 13
 ENTRY_PS_BATCH = 14
 ENTRY_DB_BOX = 15
 ENTRY_DB_GATHER = 16
+ENTRY_DB_ROUND3 = 17
+ENTRY_DB_APPEND_BATCH = 18
+ENTRY_DB_SET_VALUES_BATCH = 19
+R3_UPDATE, R3_IMPROVE = 0, 1
+R3_DONE, R3_REBUILT = 0, 1
 SD_OK, SD_NO_OBJECTIVE, SD_INFEASIBLE, SD_GAVE_UP = 0, 1, 2, 3
 NS_OK, NS_INFEASIBLE, NS_GAVE_UP = 0, 1, 2
 SD_BRANCH_DELTA, SD_BRANCH_ONE, SD_BRANCH_INTERSECT = 0, 1, 2
@@ -164,6 +169,28 @@ class DbGatherJob(ctypes.Structure):
                 ("rc", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class DbAppendJob(ctypes.Structure):
+    """mrbf_db_append_job: one start of mrbf_db_append_batch"""
+    _fields_ = [("db", ctypes.c_void_p), ("m", ctypes.c_int64), ("sites", ctypes.c_void_p), ("values", ctypes.c_void_p),
+                ("first_index", ctypes.c_int64), ("rc", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class DbSetValuesJob(ctypes.Structure):
+    """mrbf_db_set_values_job: one start of mrbf_db_set_values_batch"""
+    _fields_ = [("db", ctypes.c_void_p), ("m", ctypes.c_int64), ("indices", ctypes.c_void_p), ("values", ctypes.c_void_p),
+                ("rc", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class Round3Job(ctypes.Structure):
+    """mrbf_round3_job: one start of mrbf_db_round3_batch"""
+    _fields_ = [("db", ctypes.c_void_p), ("x", ctypes.c_void_p), ("lb", ctypes.c_void_p), ("ub", ctypes.c_void_p),
+                ("pivot_val", ctypes.c_double), ("dirs", ctypes.c_void_p), ("n_dirs", ctypes.c_int32), ("reversed", ctypes.c_int32),
+                ("n_missing", ctypes.c_int32), ("max_new", ctypes.c_int32), ("ensure_fully_linear", ctypes.c_int32),
+                ("force_rebuild", ctypes.c_int32), ("mode", ctypes.c_int32), ("rc", ctypes.c_int32), ("new_sites_out", ctypes.c_void_p),
+                ("first_index", ctypes.c_int64), ("n_new", ctypes.c_int32), ("fully_linear", ctypes.c_int32), ("status", ctypes.c_int32),
+                ("n_dirs_used", ctypes.c_int32)]
+
+
 class Problem(ctypes.Structure):
     _fields_ = [("n", ctypes.c_int64), ("m", ctypes.c_int64), ("d", ctypes.c_int32), ("k", ctypes.c_int32),
                 ("kernel_id", ctypes.c_int32), ("poly_deg", ctypes.c_int32), ("a", ctypes.c_double), ("b", ctypes.c_double),
@@ -226,6 +253,9 @@ SIGNATURES = {
     "mrbf_db_free": (ctypes.c_int32, [c_vp, c_vp]),
     "mrbf_db_box_batch": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(DbBoxJob), c_fp]),
     "mrbf_db_gather_batch": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(DbGatherJob), c_fp]),
+    "mrbf_db_append_batch": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.POINTER(DbAppendJob), c_fp]),
+    "mrbf_db_set_values_batch": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.POINTER(DbSetValuesJob), c_fp]),
+    "mrbf_db_round3_batch": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(Round3Job), c_fp]),
     "mrbf_dispatch_db_batch": (ctypes.c_int32, [ctypes.c_int64, ctypes.c_int32]),
     "mrbf_debug_mfma_layout": (ctypes.c_int32, [c_vp, c_vp, c_vp, c_vp]),
     "mrbf_debug_potrf": (ctypes.c_int32, [c_vp, ctypes.c_int64, c_vp, ctypes.c_int32, c_ip, c_fp]),

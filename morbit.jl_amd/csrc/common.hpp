@@ -206,6 +206,8 @@ inline int get_buf(mrbf_ctx *ctx, Slot s, size_t count, T **out) {
     return get_buf(ctx, s, count * sizeof(T), (void **)out);
 }
 bool is_device_ptr(const void *p);
+// room for `needed` rows in a resident database (db.hip; the growth rule of db_host.hpp): earlier rows keep their bits
+int db_reserve(mrbf_ctx *ctx, mrbf_db *db, int64_t needed);
 // device view of a caller buffer: the pointer itself when it is device memory, else a staged copy
 int stage_in(mrbf_ctx *ctx, Slot s, const double *user, size_t count, const double **dev);
 // device buffer to produce an output into (user's own when device memory, else staging)

@@ -12,6 +12,8 @@
 //   db_compact_kernel  index, site row, shifted row and norm of every candidate to its position: ascending database order by the scan
 //   db_pick_kernel     per start: first maximiser of the candidates' norms (lowest position wins ties), its shifted row to the read-back
 //                      block, then zeroed in the view when asked
+// mrbf_db_append_batch and mrbf_db_set_values_batch are mrbf_db_append and mrbf_db_set_values for every start of a batch: the host-side
+// rows and index lists of all starts travel in one packed upload behind the descriptors, one launch copies or scatters them.
 #include "batch_chain.hpp"  // chain::Staging: the host blocks of the packed upload and of the read-back
 #include "db_host.hpp"
 
@@ -19,6 +21,7 @@ namespace mrbf {
 namespace db {
 
 static_assert(sizeof(mrbf_db_box_job) == 120 && sizeof(mrbf_db_gather_job) == 64, "the job structs of include/mrbf.h");
+static_assert(sizeof(mrbf_db_append_job) == 48 && sizeof(mrbf_db_set_values_job) == 40, "the job structs of include/mrbf.h");
 constexpr int NT = 256;            // four waves
 constexpr int WROWS = ROWS / 4;    // rows of a wave
 
@@ -242,7 +245,37 @@ static DbInfo info_of(const mrbf_ctx *ctx, const mrbf_db *db) {
     return db ? DbInfo{db, db->d, db->k, db->n, db->ctx == ctx} : DbInfo{nullptr, 0, 0, 0, false};
 }
 
+// ---- the batched siblings of mrbf_db_append and mrbf_db_set_values: one workgroup column per start, rows strided over blockIdx.x
+struct AppendDesc {
+    double *S, *V;            // the database's first new row
+    const double *ss, *sv;    // the new rows (device view of the caller's, or the uploaded copy); sv == NULL: NaN
+    long long m;
+    int d, k;
+};
+struct SetDesc {
+    double *V;
+    const long long *idx;
+    const double *vals;
+    long long m;
+    int k, pad;
+};
+__global__ __launch_bounds__(NT) void db_append_batch_kernel(const AppendDesc *desc) {
+    const AppendDesc J = desc[blockIdx.y];
+    const long long cs = J.m * J.d, cv = J.m * J.k, step = (long long)gridDim.x * NT;
+    for (long long t = (long long)blockIdx.x * NT + threadIdx.x; t < cs; t += step) J.S[t] = J.ss[t];
+    for (long long t = (long long)blockIdx.x * NT + threadIdx.x; t < cv; t += step)
+        J.V[t] = J.sv ? J.sv[t] : __longlong_as_double(0x7ff8000000000000ll);
+}
+__global__ __launch_bounds__(NT) void db_set_values_batch_kernel(const SetDesc *desc) {
+    const SetDesc J = desc[blockIdx.y];
+    const long long cv = J.m * J.k, step = (long long)gridDim.x * NT;
+    for (long long t = (long long)blockIdx.x * NT + threadIdx.x; t < cv; t += step) J.V[J.idx[t / J.k] * J.k + t % J.k] = J.vals[t];
+}
+
 }  // namespace db
+
+int db_reserve(mrbf_ctx *ctx, mrbf_db *h, int64_t needed) { return db::reserve(ctx, h, needed); }
+
 }  // namespace mrbf
 
 using namespace mrbf;
@@ -517,6 +550,134 @@ int32_t mrbf_db_gather_batch(mrbf_ctx *ctx, int64_t n_starts, int32_t d, mrbf_db
         jb.sites_dev = hdesc[p].so, jb.values_dev = hdesc[p].vo;
         jb.rc = 0;
     }
+    return MRBF_OK;
+}
+
+int32_t mrbf_db_append_batch(mrbf_ctx *ctx, int64_t n_starts, mrbf_db_append_job *jobs, float *ms_total) {
+    using namespace db;
+    if (!ctx) return -1;
+    if (mrbf_dispatch_db_batch(n_starts, 1) != MRBF_DISPATCH_DEVICE)
+        return fail(ctx, -2, "mrbf_db_append_batch: %lld starts is outside the batched append (ask mrbf_dispatch_db_batch first)", (long long)n_starts);
+    if (!jobs) return fail(ctx, -3, "jobs is NULL");
+    const size_t N = (size_t)n_starts;
+    std::vector<DbInfo> info(N);
+    for (size_t p = 0; p < N; ++p) info[p] = info_of(ctx, jobs[p].db);
+    if (Defect df = check_append_jobs(n_starts, jobs, info.data(), 3)) return fail(ctx, df.code, "mrbf_db_append_batch: %s", df.msg.c_str());
+    (void)hipSetDevice(ctx->device);
+    hipStream_t s = ctx->stream;
+    // ---- the layout of the upload: descriptors, then the host-side rows of every start (device-side rows are read in place)
+    PackLayout L;
+    L.take(N * sizeof(AppendDesc));
+    std::vector<size_t> os(N, 0), ov(N, 0);
+    std::vector<char> hs(N, 0), hv(N, 0);
+    int64_t cnt_max = 0;
+    for (size_t p = 0; p < N; ++p) {
+        const mrbf_db_append_job &jb = jobs[p];
+        const size_t M = (size_t)jb.m, D = (size_t)info[p].d, K = (size_t)info[p].k;
+        cnt_max = std::max<int64_t>(cnt_max, (int64_t)(M * std::max(D, K)));
+        if (M == 0) continue;
+        hs[p] = !is_device_ptr(jb.sites), hv[p] = jb.values && !is_device_ptr(jb.values);
+        if (hs[p]) os[p] = L.take(M * D * sizeof(double));
+        if (hv[p]) ov[p] = L.take(M * K * sizeof(double));
+    }
+    for (size_t p = 0; p < N; ++p) MRBF_TRY(reserve(ctx, jobs[p].db, info[p].n + jobs[p].m));
+    char *base;
+    MRBF_TRY(get_buf(ctx, S_DB_WS, L.at, &base));
+    PinGuard pin(ctx);
+    chain::Staging up_block(ctx, L.at / sizeof(double));
+    char *const up_p = reinterpret_cast<char *>(up_block.p);
+    AppendDesc *hdesc = reinterpret_cast<AppendDesc *>(up_p);
+    for (size_t p = 0; p < N; ++p) {
+        const mrbf_db_append_job &jb = jobs[p];
+        const mrbf_db *h = jb.db;
+        const size_t M = (size_t)jb.m, D = (size_t)h->d, K = (size_t)h->k, n = (size_t)h->n;
+        AppendDesc &a = hdesc[p];
+        std::memset(&a, 0, sizeof(a));
+        a.S = h->sites + n * D, a.V = h->values + n * K, a.m = jb.m, a.d = h->d, a.k = h->k;
+        if (M == 0) continue;
+        a.ss = hs[p] ? reinterpret_cast<const double *>(base + os[p]) : jb.sites;
+        a.sv = !jb.values ? nullptr : (hv[p] ? reinterpret_cast<const double *>(base + ov[p]) : jb.values);
+        if (hs[p]) std::memcpy(up_p + os[p], jb.sites, M * D * sizeof(double));
+        if (hv[p]) std::memcpy(up_p + ov[p], jb.values, M * K * sizeof(double));
+    }
+    hipEvent_t e0 = ctx->ev[0], e1 = ctx->ev[1];
+    if (ms_total) MRBF_HIP(ctx, hipEventRecord(e0, s));
+    MRBF_HIP(ctx, hipMemcpyAsync(base, up_p, L.at, hipMemcpyHostToDevice, s));
+    if (cnt_max > 0) {
+        const dim3 grid((unsigned)std::min<int64_t>((cnt_max + NT - 1) / NT, 1024), (unsigned)N);
+        hipLaunchKernelGGL(db_append_batch_kernel, grid, dim3(NT), 0, s, reinterpret_cast<const AppendDesc *>(base));
+        MRBF_HIP(ctx, hipGetLastError());
+    }
+    if (ms_total) MRBF_HIP(ctx, hipEventRecord(e1, s));
+    MRBF_HIP(ctx, hipStreamSynchronize(s));  // the callers' buffers are their own again
+    if (ms_total) MRBF_HIP(ctx, hipEventElapsedTime(ms_total, e0, e1));
+    for (size_t p = 0; p < N; ++p) {
+        jobs[p].first_index = jobs[p].db->n;
+        jobs[p].db->n += jobs[p].m;
+        jobs[p].rc = 0;
+    }
+    return MRBF_OK;
+}
+
+int32_t mrbf_db_set_values_batch(mrbf_ctx *ctx, int64_t n_starts, mrbf_db_set_values_job *jobs, float *ms_total) {
+    using namespace db;
+    if (!ctx) return -1;
+    if (mrbf_dispatch_db_batch(n_starts, 1) != MRBF_DISPATCH_DEVICE)
+        return fail(ctx, -2, "mrbf_db_set_values_batch: %lld starts is outside the batched update (ask mrbf_dispatch_db_batch first)", (long long)n_starts);
+    if (!jobs) return fail(ctx, -3, "jobs is NULL");
+    const size_t N = (size_t)n_starts;
+    std::vector<DbInfo> info(N);
+    for (size_t p = 0; p < N; ++p) info[p] = info_of(ctx, jobs[p].db);
+    if (Defect df = check_set_values_jobs(n_starts, jobs, info.data(), 3)) return fail(ctx, df.code, "mrbf_db_set_values_batch: %s", df.msg.c_str());
+    (void)hipSetDevice(ctx->device);
+    hipStream_t s = ctx->stream;
+    PackLayout L;
+    L.take(N * sizeof(SetDesc));
+    std::vector<size_t> oi(N, 0), ov(N, 0);
+    std::vector<char> hv(N, 0);
+    std::vector<int> rcs(N, 0);
+    int64_t cnt_max = 0;
+    for (size_t p = 0; p < N; ++p) {
+        const mrbf_db_set_values_job &jb = jobs[p];
+        rcs[p] = set_values_job_rc(info[p].n, jb.m, jb.indices);
+        if (rcs[p] != 0 || jb.m == 0) continue;  // a job that failed its own check takes no part
+        const size_t M = (size_t)jb.m, K = (size_t)info[p].k;
+        cnt_max = std::max<int64_t>(cnt_max, (int64_t)(M * K));
+        hv[p] = !is_device_ptr(jb.values);
+        oi[p] = L.take(M * sizeof(int64_t));
+        if (hv[p]) ov[p] = L.take(M * K * sizeof(double));
+    }
+    char *base;
+    MRBF_TRY(get_buf(ctx, S_DB_WS, L.at, &base));
+    PinGuard pin(ctx);
+    chain::Staging up_block(ctx, L.at / sizeof(double));
+    char *const up_p = reinterpret_cast<char *>(up_block.p);
+    SetDesc *hdesc = reinterpret_cast<SetDesc *>(up_p);
+    for (size_t p = 0; p < N; ++p) {
+        const mrbf_db_set_values_job &jb = jobs[p];
+        SetDesc &a = hdesc[p];
+        std::memset(&a, 0, sizeof(a));
+        a.V = jb.db->values, a.k = jb.db->k;
+        if (rcs[p] != 0 || jb.m == 0) continue;
+        const size_t M = (size_t)jb.m, K = (size_t)a.k;
+        a.m = jb.m;
+        a.idx = reinterpret_cast<const long long *>(base + oi[p]);
+        a.vals = hv[p] ? reinterpret_cast<const double *>(base + ov[p]) : jb.values;
+        std::memcpy(up_p + oi[p], jb.indices, M * sizeof(int64_t));
+        if (hv[p]) std::memcpy(up_p + ov[p], jb.values, M * K * sizeof(double));
+    }
+    hipEvent_t e0 = ctx->ev[0], e1 = ctx->ev[1];
+    if (ms_total) MRBF_HIP(ctx, hipEventRecord(e0, s));
+    MRBF_HIP(ctx, hipMemcpyAsync(base, up_p, L.at, hipMemcpyHostToDevice, s));
+    if (cnt_max > 0) {
+        const dim3 grid((unsigned)std::min<int64_t>((cnt_max + NT - 1) / NT, 1024), (unsigned)N);
+        hipLaunchKernelGGL(db_set_values_batch_kernel, grid, dim3(NT), 0, s, reinterpret_cast<const SetDesc *>(base));
+        MRBF_HIP(ctx, hipGetLastError());
+    }
+    if (ms_total) MRBF_HIP(ctx, hipEventRecord(e1, s));
+    MRBF_HIP(ctx, hipStreamSynchronize(s));
+    if (ms_total) MRBF_HIP(ctx, hipEventElapsedTime(ms_total, e0, e1));
+    for (size_t p = 0; p < N; ++p) jobs[p].rc = rcs[p];
     return MRBF_OK;
 }
 

@@ -101,6 +101,48 @@ inline int gather_job_rc(int64_t n_sites, int64_t n_idx, const int64_t *indices)
 
 inline size_t up256(size_t b) { return (b + 255) / 256 * 256; }
 
+// mrbf_db_append_batch / mrbf_db_set_values_batch: `jobs` is argument `arg` (3); the databases of a call may differ in d and k
+inline Defect check_dbs_any_d(int64_t n_starts, const DbInfo *info, int arg) {
+    for (int64_t p = 0; p < n_starts; ++p) {
+        if (!info[p].id) return defect(-arg, "db is NULL", p);
+        if (!info[p].own) return defect(-arg, "db belongs to another context", p);
+    }
+    const int64_t rep = first_repeated(n_starts, info);
+    if (rep >= 0) return defect(-arg, "db appears twice in the batch", rep);
+    return Defect();
+}
+inline Defect check_append_jobs(int64_t n_starts, const mrbf_db_append_job *jobs, const DbInfo *info, int arg) {
+    if (Defect D = check_dbs_any_d(n_starts, info, arg)) return D;
+    for (int64_t p = 0; p < n_starts; ++p) {
+        if (jobs[p].m < 0 || info[p].n + jobs[p].m > ((int64_t)1 << 31) - ROWS) return defect(-arg, "m is negative or beyond the row limit", p);
+        if (jobs[p].m > 0 && !jobs[p].sites) return defect(-arg, "sites is NULL", p);
+    }
+    return Defect();
+}
+inline Defect check_set_values_jobs(int64_t n_starts, const mrbf_db_set_values_job *jobs, const DbInfo *info, int arg) {
+    if (Defect D = check_dbs_any_d(n_starts, info, arg)) return D;
+    for (int64_t p = 0; p < n_starts; ++p) {
+        if (jobs[p].m < 0) return defect(-arg, "m is negative", p);
+        if (jobs[p].m > 0 && (!jobs[p].indices || !jobs[p].values)) return defect(-arg, "indices or values is NULL", p);
+    }
+    return Defect();
+}
+constexpr int SET_VALUES_RC_INDEX = -4;  // what mrbf_db_set_values returns for an index that is not a row
+inline int set_values_job_rc(int64_t n_sites, int64_t m, const int64_t *indices) {
+    for (int64_t i = 0; i < m; ++i)
+        if (indices[i] < 0 || indices[i] >= n_sites) return SET_VALUES_RC_INDEX;
+    return 0;
+}
+// the packed upload of either call: the descriptors, then piece after piece (bytes, each a multiple of 256)
+struct PackLayout {
+    size_t at = 0;
+    size_t take(size_t bytes) {
+        const size_t o = at;
+        at += up256(bytes);
+        return o;
+    }
+};
+
 // ---- the layout of a box batch.  Start p owns the rows roff[p] .. roff[p] + n_p - 1 of every per-row array (roff: prefix sums of n_p
 // rounded up to ROWS, so a workgroup's rows belong to one start) and the workgroups roff[p] / ROWS ...
 //   views (doubles, a buffer of their own): candidate sites of start p at roff[p] * d, shifted rows at (rows + roff[p]) * d --

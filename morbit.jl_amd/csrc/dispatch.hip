@@ -149,6 +149,10 @@ int32_t mrbf_dispatch_after(int32_t entry, int32_t rc) {
         // the table refuses the shape: results_in_box_indices / the row copies on the host copy of the database; a job's own rc is an error
         case MRBF_ENTRY_DB_BOX: return rc == -2;
         case MRBF_ENTRY_DB_GATHER: return rc == -2;
+        // likewise: _rbf_round3 / the per-start appends and value updates on the host copy; a job's own rc is an error
+        case MRBF_ENTRY_DB_ROUND3: return rc == -2;
+        case MRBF_ENTRY_DB_APPEND_BATCH: return rc == -2;
+        case MRBF_ENTRY_DB_SET_VALUES_BATCH: return rc == -2;
         default: return 0;
     }
 }

@@ -133,6 +133,37 @@ class DeviceDatabase:
             pass
 
 
+class HostDatabase:
+    """the host copy alone, with `DeviceDatabase`'s interface (`sites`, `values`, `append`, `set_values`): what the host-array twins
+    of the resident drivers (`sampling.prepare_update_models_many`) append their new sites to"""
+
+    def __init__(self, d, k):
+        self.d, self.k, self._n = int(d), int(k), 0
+        self._S, self._V = np.empty((16, self.d)), np.empty((16, self.k))
+
+    def __len__(self):
+        return self._n
+
+    @property
+    def sites(self):
+        return self._S[: self._n]
+
+    @property
+    def values(self):
+        return self._V[: self._n]
+
+    def append(self, sites, values=None):
+        S = np.asarray(sites, dtype=np.float64).reshape(-1, self.d)
+        first = self._n
+        _adopt_rows(self, S, None if values is None else np.asarray(values, dtype=np.float64).reshape(S.shape[0], self.k))
+        return first
+
+    def set_values(self, indices, values):
+        idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+        if idx.size:
+            self._V[idx] = np.asarray(values, dtype=np.float64).reshape(idx.size, self.k)
+
+
 class BoxResult:
     """one start of `box_many`: `indices` (database positions of the candidates, ascending), `mc`, `first_pick` (position among the
     candidates, -1 without candidates), `first_row` (its shifted row), `sites` / `shifted` (mc x d: DeviceViews, or NumPy arrays when
@@ -266,3 +297,123 @@ def gather_many(dbs, index_lists, ctx=None, stats=None):
         out.append(r)
     stats.update(path="device", ms_total=float(ms.value))
     return out
+
+
+def _grow_host(db, m):
+    if db._n + m > db._S.shape[0]:
+        cap = max(2 * db._S.shape[0], db._n + m)
+        db._S = np.concatenate([db._S[: db._n], np.empty((cap - db._n, db.d))])
+        db._V = np.concatenate([db._V[: db._n], np.empty((cap - db._n, db.k))])
+
+
+def _adopt_rows(db, S, V=None):
+    """the host copy's side of an append the device has done already: `S` m x d, `V` m x k or None (NaN)"""
+    m = int(S.shape[0])
+    _grow_host(db, m)
+    db._S[db._n: db._n + m] = S
+    db._V[db._n: db._n + m] = _NAN if V is None else V
+    db._n += m
+
+
+def append_many(dbs, sites_list, values_list=None, ctx=None, stats=None):
+    """`DeviceDatabase.append` for every database of the list in ONE call (mrbf_db_append_batch: one packed upload, one launch, one
+    synchronisation) -- the trial points of an iteration.  `sites_list[p]`: m_p x d_p, `values_list[p]`: m_p x k_p or None (unevaluated
+    rows); NumPy arrays or torch tensors.  Returns the position of the first new row per database; the host copies are kept in step.
+    Where mrbf_dispatch_db_batch sends the call to the host it is the loop of single appends; stats["path"] says which."""
+    ns = len(dbs)
+    stats = stats if stats is not None else {}
+    if ns == 0:
+        return []
+    ctx = ctx or dbs[0].ctx
+    values_list = [None] * ns if values_list is None else values_list
+
+    def loop():
+        stats["path"] = "loop"
+        return [db.append(sites_list[q], values_list[q]) for q, db in enumerate(dbs)]
+
+    if ctx.lib.mrbf_dispatch_db_batch(ns, 1) != _lib.DISPATCH_DEVICE:
+        return loop()
+    jobs = (_lib.DbAppendJob * ns)()
+    keep = []
+    for q, db in enumerate(dbs):
+        S = sites_list[q]
+        S = S.contiguous() if hasattr(S, "data_ptr") else _lib.host_f64(S).reshape(-1, db.d)
+        m = int(S.shape[0]) if S.ndim == 2 else int(S.numel() // db.d)
+        V = values_list[q]
+        if V is not None:
+            V = V.contiguous() if hasattr(V, "data_ptr") else _lib.host_f64(V).reshape(m, db.k)
+        keep.append((S, V, m))
+        J = jobs[q]
+        J.db, J.m = db.h, m
+        J.sites, J.values = (_lib.as_ptr(S) if m else None), (_lib.as_ptr(V) if (V is not None and m) else None)
+    ms = ctypes.c_float(0.0)
+    rc = ctx.lib.mrbf_db_append_batch(ctx.h, ns, jobs, ctypes.byref(ms))
+    if rc != 0:
+        if ctx.lib.mrbf_dispatch_after(_lib.ENTRY_DB_APPEND_BATCH, rc):
+            return loop()
+        ctx.check(rc)
+    out = []
+    for q, db in enumerate(dbs):
+        S, V, m = keep[q]
+        if jobs[q].rc != 0:
+            raise _lib.MrbfError(jobs[q].rc, "mrbf_db_append_batch: start %d" % q)
+        assert int(jobs[q].first_index) == len(db)
+        out.append(len(db))
+        _adopt_rows(db, np.asarray(db._host_rows(S), dtype=np.float64).reshape(m, db.d),
+                    None if V is None else np.asarray(db._host_rows(V), dtype=np.float64).reshape(m, db.k))
+    stats.update(path="device", ms_total=float(ms.value))
+    return out
+
+
+def set_values_many(dbs, index_lists, values_list, ctx=None, stats=None, strict=True):
+    """`DeviceDatabase.set_values` (eval_missing!, Databases.jl:258-277) for every database of the list in ONE call
+    (mrbf_db_set_values_batch).  Returns the rc of every start: 0, or -4 for an index list with a position outside the database --
+    nothing of that start is written; with `strict` that raises after the other starts are done.  The host copies are kept in step."""
+    ns = len(dbs)
+    stats = stats if stats is not None else {}
+    if ns == 0:
+        return []
+    ctx = ctx or dbs[0].ctx
+    idxs = [np.ascontiguousarray(list(l) if not isinstance(l, np.ndarray) else l, dtype=np.int64).reshape(-1) for l in index_lists]
+
+    def loop():
+        stats["path"] = "loop"
+        rcs = []
+        for q, db in enumerate(dbs):
+            try:
+                db.set_values(idxs[q], values_list[q])
+                rcs.append(0)
+            except _lib.MrbfError as e:
+                if strict or e.code != -4:
+                    raise
+                rcs.append(e.code)
+        return rcs
+
+    if ctx.lib.mrbf_dispatch_db_batch(ns, 1) != _lib.DISPATCH_DEVICE:
+        return loop()
+    jobs = (_lib.DbSetValuesJob * ns)()
+    keep = []
+    for q, db in enumerate(dbs):
+        m = idxs[q].size
+        V = values_list[q]
+        V = V.contiguous() if hasattr(V, "data_ptr") else _lib.host_f64(V).reshape(m, db.k)
+        keep.append(V)
+        J = jobs[q]
+        J.db, J.m = db.h, m
+        J.indices, J.values = (idxs[q].ctypes.data if m else None), (_lib.as_ptr(V) if m else None)
+    ms = ctypes.c_float(0.0)
+    rc = ctx.lib.mrbf_db_set_values_batch(ctx.h, ns, jobs, ctypes.byref(ms))
+    if rc != 0:
+        if ctx.lib.mrbf_dispatch_after(_lib.ENTRY_DB_SET_VALUES_BATCH, rc):
+            return loop()
+        ctx.check(rc)
+    rcs = []
+    for q, db in enumerate(dbs):
+        rcs.append(int(jobs[q].rc))
+        if rcs[q] == 0 and idxs[q].size:
+            db._V[idxs[q]] = np.asarray(db._host_rows(keep[q]), dtype=np.float64).reshape(idxs[q].size, db.k)
+    stats.update(path="device", ms_total=float(ms.value))
+    bad = [q for q, r in enumerate(rcs) if r != 0]
+    if strict and bad:
+        raise _lib.MrbfError(rcs[bad[0]], "mrbf_db_set_values_batch: start %d has an index outside its database" % bad[0])
+    return rcs

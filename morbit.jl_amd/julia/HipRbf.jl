@@ -1349,3 +1349,139 @@ function affine_scores(S::AbstractMatrix{Float64}, Z::AbstractMatrix, p = Inf)  
     _check(ctx, rc)
     return Int(best[]) + 1, val[]
 end
+
+# ---- resident site databases: round 3, appends and value updates of many starts in one call each (include/mrbf.h) -------------------
+
+struct MrbfRound3Job        # mirrors mrbf_round3_job, 112 bytes
+    db::Ptr{Cvoid}
+    x::Ptr{Float64}; lb::Ptr{Float64}; ub::Ptr{Float64}
+    pivot_val::Float64
+    dirs::Ptr{Float64}
+    n_dirs::Int32; reversed::Int32; n_missing::Int32; max_new::Int32
+    ensure_fully_linear::Int32; force_rebuild::Int32; mode::Int32; rc::Int32
+    new_sites_out::Ptr{Float64}
+    first_index::Int64
+    n_new::Int32; fully_linear::Int32; status::Int32; n_dirs_used::Int32
+end
+
+struct MrbfDbAppendJob      # mirrors mrbf_db_append_job, 48 bytes
+    db::Ptr{Cvoid}
+    m::Int64
+    sites::Ptr{Float64}; values::Ptr{Float64}
+    first_index::Int64
+    rc::Int32; reserved::Int32
+end
+
+struct MrbfDbSetValuesJob   # mirrors mrbf_db_set_values_job, 40 bytes
+    db::Ptr{Cvoid}
+    m::Int64
+    indices::Ptr{Int64}; values::Ptr{Float64}
+    rc::Int32; reserved::Int32
+end
+
+_dispatch_db_batch(n_starts, d) = ccall((:mrbf_dispatch_db_batch, libmrbf), Int32, (Int64, Int32), n_starts, d) == 1
+
+"An empty resident database for sites of dimension `d` and values of dimension `k` (`mrbf_db_create`); release it with `hip_db_free`."
+function hip_db_create(d::Integer, k::Integer; capacity::Integer = 0)
+    ctx = mrbf_context(); h = Ref{Ptr{Cvoid}}(C_NULL)
+    rc = _locked(ctx) do hctx
+        ccall((:mrbf_db_create, libmrbf), Int32, (Ptr{Cvoid}, Int32, Int32, Int64, Ref{Ptr{Cvoid}}), hctx, d, k, capacity, h)
+    end
+    _check(ctx, rc)
+    return h[]
+end
+function hip_db_free(db::Ptr{Cvoid})
+    ctx = mrbf_context()
+    rc = _locked(ctx) do hctx
+        ccall((:mrbf_db_free, libmrbf), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), hctx, db)
+    end
+    _check(ctx, rc)
+    return nothing
+end
+
+"""
+`new_result!(db, x, y)` for every start in one device call (`mrbf_db_append_batch`): `sites[p]` is d x m_p (a site per column), `values[p]`
+k x m_p or `nothing` (unevaluated rows, stored as NaN).  Returns the 1-based id of the first new row of every database, or `nothing` where
+the decision table keeps the call on the host (rc -2: append start by start).
+"""
+function hip_db_append_many(dbs::AbstractVector{Ptr{Cvoid}}, sites::AbstractVector{Matrix{Float64}}, values::AbstractVector)
+    ns = length(dbs)
+    (ns >= 1 && _dispatch_db_batch(ns, 1)) || return nothing
+    Vs = [values[p] === nothing ? nothing : Matrix{Float64}(values[p]) for p in 1:ns]
+    ctx = mrbf_context(); ms = Ref{Float32}(0)
+    jobs = Vector{MrbfDbAppendJob}(undef, ns)
+    rc = GC.@preserve sites Vs jobs begin
+        for p in 1:ns
+            jobs[p] = MrbfDbAppendJob(dbs[p], size(sites[p], 2), pointer(sites[p]), Vs[p] === nothing ? Ptr{Float64}(C_NULL) : pointer(Vs[p]), 0, 0, 0)
+        end
+        _locked(ctx) do hctx
+            ccall((:mrbf_db_append_batch, libmrbf), Int32, (Ptr{Cvoid}, Int64, Ptr{MrbfDbAppendJob}, Ref{Float32}), hctx, ns, jobs, ms)
+        end
+    end
+    rc != 0 && _fallback_rc(18, rc) && return nothing
+    _check(ctx, rc)
+    return [Int(jobs[p].first_index) + 1 for p in 1:ns]
+end
+
+"""
+`eval_missing!` for every start in one device call (`mrbf_db_set_values_batch`): `ids[p]` are 1-based row ids, `values[p]` is k x m_p.
+Returns the return code of every start (0, or -4 for an id outside the database: nothing of that start is written), or `nothing` where
+the decision table keeps the call on the host.
+"""
+function hip_db_set_values_many(dbs::AbstractVector{Ptr{Cvoid}}, ids::AbstractVector{<:AbstractVector{<:Integer}}, values::AbstractVector{Matrix{Float64}})
+    ns = length(dbs)
+    (ns >= 1 && _dispatch_db_batch(ns, 1)) || return nothing
+    idx = [Int64.(ids[p]) .- 1 for p in 1:ns]
+    ctx = mrbf_context(); ms = Ref{Float32}(0)
+    jobs = Vector{MrbfDbSetValuesJob}(undef, ns)
+    rc = GC.@preserve idx values jobs begin
+        for p in 1:ns
+            jobs[p] = MrbfDbSetValuesJob(dbs[p], length(idx[p]), pointer(idx[p]), pointer(values[p]), 0, 0)
+        end
+        _locked(ctx) do hctx
+            ccall((:mrbf_db_set_values_batch, libmrbf), Int32, (Ptr{Cvoid}, Int64, Ptr{MrbfDbSetValuesJob}, Ref{Float32}), hctx, ns, jobs, ms)
+        end
+    end
+    rc != 0 && _fallback_rc(19, rc) && return nothing
+    _check(ctx, rc)
+    return Int32[jobs[p].rc for p in 1:ns]
+end
+
+"""
+`_rbf_round3` (RbfModel.jl:269-307) for many starts in one device call (`mrbf_db_round3_batch`), the rebuild along the coordinate axes
+(:633-637) done inside the call and the new sites written straight into the resident databases.  `dirs[p]` is a d x n_dirs matrix whose
+columns are the improving directions in the order round 3 takes them, or `nothing` for the coordinate axes; `improve = true` is the
+improvement step of `prepare_improve_model` (:699-732).  Returns, per start, `(rc, ids, new_sites, fully_linear, rebuilt, n_dirs_used)`
+with 1-based ids, or `nothing` where the decision table keeps the call on the host (rc -2: Morbit's own `_rbf_round3` per start).
+"""
+function hip_db_round3_many(dbs::AbstractVector{Ptr{Cvoid}}, xs::AbstractVector{Vector{Float64}}, lbs::AbstractVector{Vector{Float64}},
+        ubs::AbstractVector{Vector{Float64}}, piv_vals::AbstractVector{<:Real}, dirs::AbstractVector, max_news::AbstractVector{<:Integer},
+        n_missings::AbstractVector{<:Integer}, ensure_fully_linear::AbstractVector{Bool}, force_rebuild::AbstractVector{Bool}; improve::Bool = false)
+    ns = length(dbs)
+    ns >= 1 || return nothing
+    d = length(xs[1])
+    (all(x -> length(x) == d, xs) && _dispatch_db_batch(ns, d)) || return nothing
+    Ds = [dirs[p] === nothing ? nothing : Matrix{Float64}(dirs[p]) for p in 1:ns]
+    clamp32(v) = Int32(clamp(v, typemin(Int32), typemax(Int32)))
+    outs = [Matrix{Float64}(undef, d, max(min(n_missings[p], max_news[p]), min(d, max_news[p]), 1)) for p in 1:ns]
+    ctx = mrbf_context(); ms = Ref{Float32}(0)
+    jobs = Vector{MrbfRound3Job}(undef, ns)
+    rc = GC.@preserve xs lbs ubs Ds outs jobs begin
+        for p in 1:ns
+            jobs[p] = MrbfRound3Job(dbs[p], pointer(xs[p]), pointer(lbs[p]), pointer(ubs[p]), Float64(piv_vals[p]),
+                                    Ds[p] === nothing ? Ptr{Float64}(C_NULL) : pointer(Ds[p]), Ds[p] === nothing ? 0 : size(Ds[p], 2), 0,
+                                    clamp32(n_missings[p]), clamp32(max_news[p]), ensure_fully_linear[p] ? 1 : 0, force_rebuild[p] ? 1 : 0,
+                                    improve ? 1 : 0, 0, pointer(outs[p]), 0, 0, 0, 0, 0)
+        end
+        _locked(ctx) do hctx
+            ccall((:mrbf_db_round3_batch, libmrbf), Int32, (Ptr{Cvoid}, Int64, Int32, Ptr{MrbfRound3Job}, Ref{Float32}), hctx, ns, d, jobs, ms)
+        end
+    end
+    rc != 0 && _fallback_rc(17, rc) && return nothing
+    _check(ctx, rc)
+    return map(1:ns) do p
+        J = jobs[p]
+        n = J.rc == 0 ? Int(J.n_new) : 0
+        (J.rc, collect(Int(J.first_index) + 1 : Int(J.first_index) + n), outs[p][:, 1:n], J.fully_linear != 0, J.status == 1, Int(J.n_dirs_used))
+    end
+end

@@ -649,9 +649,11 @@ def _rbf_round4(sites, lb_2, ub_2, x, delta, indices_found_so_far, cfg, ctx=None
 # small host-side steps (the filter's Y, the Householder start) and every fall-back use the databases' host copies.
 
 
-def _affine_select_batch_views(items, d, p=np.inf, ctx=None):
+def _affine_select_batch_views(items, d, p=np.inf, ctx=None, device_Z=None):
     """`affine_select_batch_device` with the candidates given as anything `_lib.as_ptr` takes with a `shape` (a DeviceView is read in
-    place): `items` = one (Sd, qr, want, pivot_val) per start -> (rc, [(positions, final Z)] or None, ms)"""
+    place): `items` = one (Sd, qr, want, pivot_val) per start -> (rc, [(positions, final Z)] or None, ms).  `device_Z[k]` (optional):
+    start k's Z_out is a device buffer and its final Z comes back as a (dz, d) device tensor whose ROWS are the columns of Z (the
+    memory of the column-major d x dz matrix), for mrbf_db_round3_batch to read in place."""
     ctx = ctx or _lib.default_context()
     n = len(items)
     jobs = (_lib.AffineJob * max(n, 1))()
@@ -659,11 +661,16 @@ def _affine_select_batch_views(items, d, p=np.inf, ctx=None):
     for k, (Sd, qr, want, pivot) in enumerate(items):
         Q0 = np.asfortranarray(qr.Q)
         picks = np.empty(max(want, 1), dtype=np.int64)
-        Zbuf = np.empty((max(d - qr.j, 1), d))                          # (column-major d x dz)
+        if device_Z is not None and device_Z[k]:
+            import torch
+
+            Zbuf = torch.empty((max(d - qr.j, 1), d), dtype=torch.float64, device="cuda")
+        else:
+            Zbuf = np.empty((max(d - qr.j, 1), d))                      # (column-major d x dz)
         keep.append((Sd, Q0, picks, Zbuf))
         jobs[k].mc, jobs[k].j0, jobs[k].max_picks, jobs[k].pivot_val = int(Sd.shape[0]), qr.j, want, float(pivot)
         jobs[k].shifted, jobs[k].Q0 = _lib.as_ptr(Sd), Q0.ctypes.data
-        jobs[k].picked_out, jobs[k].Z_out = picks.ctypes.data, Zbuf.ctypes.data
+        jobs[k].picked_out, jobs[k].Z_out = picks.ctypes.data, _lib.as_ptr(Zbuf)
     ms = ctypes.c_float(0.0)
     rc = ctx.lib.mrbf_affine_select_batch(ctx.h, n, d, 1 if np.isinf(p) else 0, jobs, ctypes.byref(ms))
     if rc != 0:
@@ -674,13 +681,18 @@ def _affine_select_batch_views(items, d, p=np.inf, ctx=None):
     for k, (Sd, qr, want, pivot) in enumerate(items):
         _, _, picks, Zbuf = keep[k]
         got = [int(v) for v in picks[: jobs[k].n_picked]]
-        res.append((got, Zbuf[: d - qr.j - len(got)].T.copy()))
+        Zk = Zbuf[: d - qr.j - len(got)]
+        res.append((got, Zk if hasattr(Zk, "data_ptr") else Zk.T.copy()))
     return 0, res, float(ms.value)
 
 
 def find_suitable_points_resident(dbs, lbs, ubs, xs, x_indices, piv_val, already_inspected_indices=None, Ys=None, Zs=None, n_missing=None,
-                                  collect_improving_directions=True, stats=None, ctx=None):
-    """`find_suitable_points_many` on resident databases: returns exactly its list of `_find_suitable_points` tuples.  The box scan,
+                                  collect_improving_directions=True, stats=None, ctx=None, keep_Z_on_device=None):
+    """`find_suitable_points_many` on resident databases: returns exactly its list of `_find_suitable_points` tuples.
+    `keep_Z_on_device[p]` (optional; the default keeps what is said here): the caller will not run a second round from start p's Y
+    and Z (its round 2 is skipped), so where the batched pick loop served the start and picked something its final Z stays on the device:
+    the tuple's directions AND its Z are then one (dz, d) device tensor whose rows are the columns of Z -- the improving directions
+    are its rows from the last to the first (`rbf_round3_resident(..., reversed_order=True)` reads them in place).  The box scan,
     the shifted rows and the first pick of every start come from ONE mrbf_db_box_batch call per d (first pick's row zeroed: the state the
     pick loop expects); the first reflector starts on the host from the returned row; the pick loops of the starts the decision table
     sends to the device (mrbf_dispatch_affine per start, mrbf_dispatch_affine_batch per group) read the shifted rows in place.  A start
@@ -732,7 +744,8 @@ def find_suitable_points_resident(dbs, lbs, ubs, xs, x_indices, piv_val, already
             rc = -2
             if lib.mrbf_dispatch_affine_batch(len(device), d, 1) == _lib.DISPATCH_DEVICE:
                 rc, got_all, _ = _affine_select_batch_views([(boxes[pos].shifted, qr, want, piv_val) for (_, pos, _, qr, want) in device], d,
-                                                            np.inf, ctx=ctx)
+                                                            np.inf, ctx=ctx,
+                                                            device_Z=None if keep_Z_on_device is None else [bool(keep_Z_on_device[p]) for (p, *_) in device])
             for k, (p, pos, out, qr, want) in enumerate(device):
                 flt, B = filters[p], boxes[pos]
                 flt.ctx = flt.ctx or ctx
@@ -750,7 +763,10 @@ def find_suitable_points_resident(dbs, lbs, ubs, xs, x_indices, piv_val, already
     final = []
     for p in range(ns):
         picked, flt, cand = res[p]
-        dirs = [flt.Z[:, j].copy() for j in range(flt.Z.shape[1])][::-1] if collect_improving_directions else None
+        if hasattr(flt.Z, "data_ptr"):                       # left on the device: rows are directions, last to first
+            dirs = flt.Z if collect_improving_directions else None
+        else:
+            dirs = [flt.Z[:, j].copy() for j in range(flt.Z.shape[1])][::-1] if collect_improving_directions else None
         final.append((picked, dirs, cand, flt.Y, flt.Z))
     return final
 
@@ -845,3 +861,344 @@ def rbf_round4_resident(dbs, lb2s, ub2s, xs, deltas, indices_found_list, cfgs, c
         stats["batched"] = sorted(batched)
         stats["fallback"] = sorted(fallback)
     return out
+
+
+# ---- round 3 (RbfModel.jl:269-307), the improvement step (:699-732) and phase I as one driver (:518-655) -------------------------------
+
+def _rbf_round3(sites, lb_1, ub_1, x, piv_val_1, improving_directions, max_new, n_missing, ensure_fully_linear, force_rebuild):
+    """RbfModel.jl:269-307 on `descent.intersect_box` -> (new_points, fully_linear, remaining_directions), or (None, None, None) when a
+    direction fails the pivot test and the caller has to rebuild along the coordinate axes (:286-289).  new_points: n_new x d, to be
+    appended to the database as unevaluated rows by the caller (:299-305; `sites` itself is not consulted, as in the reference)."""
+    from .descent import intersect_box
+
+    x = np.asarray(x, dtype=np.float64)
+    n_new = max(0, min(int(n_missing), int(max_new)))
+    fully_linear = n_new >= n_missing
+    assert len(improving_directions) >= n_new, "There must be more improving directions than points missing."
+    new_points = np.empty((n_new, x.size))
+    for i in range(n_new):
+        direction = np.asarray(improving_directions[i], dtype=np.float64)
+        length = intersect_box(x, direction, lb_1, ub_1, return_vals="absmax")
+        with np.errstate(invalid="ignore"):
+            offset = length * direction
+        if np.max(np.abs(offset)) <= piv_val_1:          # (the maximum propagates NaN: a NaN norm does not fail)
+            if ensure_fully_linear and not force_rebuild:
+                return None, None, None
+            fully_linear = False
+        with np.errstate(invalid="ignore"):
+            new_points[i] = x + offset
+    return new_points, bool(fully_linear), list(improving_directions[n_new:])
+
+
+def _axes(d):
+    return [row for row in np.eye(d)]
+
+
+class Round3Result:
+    """one start of round 3: `new_points` (n_new x d), `indices` (their database positions, or None where nothing was appended for the
+    caller), `fully_linear`, `remaining_directions`, `rebuilt` (the start was redone along the coordinate axes, RbfModel.jl:633-637)"""
+    __slots__ = ("new_points", "indices", "fully_linear", "remaining_directions", "rebuilt")
+
+    def __init__(self, new_points, fully_linear, remaining, rebuilt, indices=None):
+        self.new_points, self.fully_linear, self.remaining_directions, self.rebuilt, self.indices = new_points, fully_linear, remaining, rebuilt, indices
+
+
+def _per(v, ns):
+    return list(v) if isinstance(v, (list, tuple)) else [v] * ns
+
+
+def _direction_rows(dirs, d, reverse):
+    """the directions of one start in the order round 3 takes them: a list of vectors, a (n_dirs, d) array (rows are directions; the
+    memory of a column-major d x n_dirs Z), or None for the coordinate axes"""
+    if dirs is None:
+        return _axes(d)
+    rows = [np.asarray(v, dtype=np.float64) for v in (np.asarray(dirs, dtype=np.float64).reshape(-1, d) if not isinstance(dirs, list) else dirs)]
+    return rows[::-1] if reverse else rows
+
+
+def rbf_round3_many(lb1s, ub1s, xs, piv_vals, directions, max_news, n_missings, ensure_fully_linear=False, force_rebuild=False,
+                    reversed_order=None):
+    """`_rbf_round3` for a list of starts, with the rebuild done in place: a start whose round 3 returns nothing is redone along the
+    coordinate axes with the arguments of the recursive call at RbfModel.jl:634-637 (n_missing = d, ensure_fully_linear and force_rebuild
+    set).  -> list of Round3Result (`indices` None: nothing is appended here)."""
+    ns = len(xs)
+    piv_vals, max_news, n_missings = _per(piv_vals, ns), _per(max_news, ns), _per(n_missings, ns)
+    efl, force, rev = _per(ensure_fully_linear, ns), _per(force_rebuild, ns), _per(False if reversed_order is None else reversed_order, ns)
+    out = []
+    for p in range(ns):
+        x = np.asarray(xs[p], dtype=np.float64)
+        rows = _direction_rows(directions[p], x.size, rev[p])
+        pts, fl, rem = _rbf_round3(None, lb1s[p], ub1s[p], x, piv_vals[p], rows, max_news[p], n_missings[p], efl[p], force[p])
+        rebuilt = pts is None
+        if rebuilt:
+            pts, fl, rem = _rbf_round3(None, lb1s[p], ub1s[p], x, piv_vals[p], _axes(x.size), max_news[p], x.size, True, True)
+        out.append(Round3Result(pts, fl, rem, rebuilt))
+    return out
+
+
+def _improve_host(lb1, ub1, x, piv, rows):
+    """prepare_improve_model's geometry (RbfModel.jl:715-728) -> Round3Result with 0 or 1 new point"""
+    from .descent import intersect_box
+
+    x = np.asarray(x, dtype=np.float64)
+    if not rows:
+        return Round3Result(np.empty((0, x.size)), False, [], False)
+    direction = np.asarray(rows[0], dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        offset = intersect_box(x, direction, lb1, ub1, return_vals="absmax") * direction
+        ok = bool(np.max(np.abs(offset)) > piv)
+        pts = (x + offset)[None, :] if ok else np.empty((0, x.size))
+    return Round3Result(pts, ok and len(rows) == 1, list(rows[1:]), False)
+
+
+def rbf_round3_resident(dbs, lb1s, ub1s, xs, piv_vals, directions, max_news, n_missings, ensure_fully_linear=False, force_rebuild=False,
+                        reversed_order=None, improve=False, ctx=None, stats=None):
+    """`rbf_round3_many` on resident databases, the new points appended to them as unevaluated rows: ONE mrbf_db_round3_batch per d
+    (rebuild included).  `directions[p]`: a list of vectors, a (n_dirs, d) NumPy array or device tensor (rows are directions: the
+    memory of a column-major d x n_dirs Z, read in place), or None for the coordinate axes; `reversed_order[p]`: take the rows from the
+    last to the first.  `improve`: the improvement step (prepare_improve_model) instead.  Where the decision table says host, the
+    host loop runs and its points are appended through `database.append_many`.  -> list of Round3Result with `indices`."""
+    from . import database
+
+    ns = len(dbs)
+    stats = stats if stats is not None else {}
+    piv_vals, max_news, n_missings = _per(piv_vals, ns), _per(max_news, ns), _per(n_missings, ns)
+    efl, force, rev = _per(ensure_fully_linear, ns), _per(force_rebuild, ns), _per(False if reversed_order is None else reversed_order, ns)
+    out = [None] * ns
+    lib = _lib.load() if ns else None
+    by_d = {}
+    for p in range(ns):
+        by_d.setdefault(dbs[p].d, []).append(p)
+    stats["path"] = "device"
+    for d, members in by_d.items():
+        c = ctx or dbs[members[0]].ctx
+
+        def host(members=members, d=d):
+            stats["path"] = "host"
+            host_rows = lambda p: _direction_rows(directions[p] if not hasattr(directions[p], "data_ptr") else directions[p].detach().cpu().numpy(),
+                                                  d, rev[p])
+            if improve:
+                res = [_improve_host(lb1s[p], ub1s[p], xs[p], piv_vals[p], host_rows(p)) for p in members]
+            else:
+                res = rbf_round3_many([lb1s[p] for p in members], [ub1s[p] for p in members], [xs[p] for p in members],
+                                      [piv_vals[p] for p in members], [host_rows(p) for p in members], [max_news[p] for p in members],
+                                      [n_missings[p] for p in members], [efl[p] for p in members], [force[p] for p in members])
+            firsts = database.append_many([dbs[p] for p in members], [r.new_points for r in res], ctx=c)
+            for p, r, f in zip(members, res, firsts):
+                r.indices = list(range(f, f + r.new_points.shape[0]))
+                out[p] = r
+
+        if lib.mrbf_dispatch_db_batch(len(members), d) != _lib.DISPATCH_DEVICE:
+            host()
+            continue
+        jobs = (_lib.Round3Job * len(members))()
+        keep = []
+        for q, p in enumerate(members):
+            x, lb, ub = (_lib.host_f64(v).reshape(d) for v in (xs[p], lb1s[p], ub1s[p]))
+            D = directions[p]
+            if D is None:
+                n_dirs, ptr = d, None
+            elif hasattr(D, "data_ptr"):
+                D = D.contiguous()
+                n_dirs, ptr = int(D.shape[0]), D.data_ptr()
+            else:
+                D = _lib.host_f64(np.asarray(D, dtype=np.float64).reshape(-1, d))
+                n_dirs, ptr = int(D.shape[0]), (D.ctypes.data if D.size else None)
+                if ptr is None:                              # an empty list is not the axes
+                    D = np.zeros((1, d))
+                    ptr = D.ctypes.data
+            rows_out = max(min(int(n_missings[p]), int(max_news[p])), min(d, int(max_news[p])), 1)
+            buf = np.empty((rows_out, d))
+            keep.append((x, lb, ub, D, buf, n_dirs))
+            J = jobs[q]
+            J.db, J.x, J.lb, J.ub, J.pivot_val = dbs[p].h, x.ctypes.data, lb.ctypes.data, ub.ctypes.data, float(piv_vals[p])
+            J.dirs, J.n_dirs, J.reversed = ptr, n_dirs, 1 if rev[p] else 0
+            clamp = lambda v: int(max(-2 ** 31, min(2 ** 31 - 1, int(v))))
+            J.n_missing, J.max_new = clamp(n_missings[p]), clamp(max_news[p])
+            J.ensure_fully_linear, J.force_rebuild, J.mode = int(bool(efl[p])), int(bool(force[p])), _lib.R3_IMPROVE if improve else _lib.R3_UPDATE
+            J.new_sites_out = buf.ctypes.data
+        ms = ctypes.c_float(0.0)
+        rc = c.lib.mrbf_db_round3_batch(c.h, len(members), d, jobs, ctypes.byref(ms))
+        if rc != 0:
+            if c.lib.mrbf_dispatch_after(_lib.ENTRY_DB_ROUND3, rc):
+                host()
+                continue
+            c.check(rc)
+        stats["ms_total"] = stats.get("ms_total", 0.0) + float(ms.value)
+        failed = None
+        for q, p in enumerate(members):
+            J, (x, lb, ub, D, buf, n_dirs) = jobs[q], keep[q]
+            if J.rc != 0:                                    # its database is untouched; the others are served before it is reported
+                failed = failed or (p, int(J.rc))
+                continue
+            n_new, first = int(J.n_new), int(J.first_index)
+            pts = buf[:n_new].copy()
+            database._adopt_rows(dbs[p], pts)
+            rebuilt = J.status == _lib.R3_REBUILT
+            if rebuilt:
+                rem = _axes(d)[int(J.n_dirs_used):]
+            else:
+                Dh = directions[p]
+                if int(J.n_dirs_used) >= n_dirs:
+                    rem = []                                 # (no read-back of a device-side block for nothing)
+                else:
+                    if hasattr(Dh, "data_ptr"):
+                        Dh = Dh.detach().cpu().numpy()
+                    rem = _direction_rows(Dh, d, rev[p])[int(J.n_dirs_used):]
+            out[p] = Round3Result(pts, bool(J.fully_linear), rem, rebuilt, list(range(first, first + n_new)))
+        if failed is not None and failed[1] == -3:
+            raise AssertionError("There must be more improving directions than points missing (start %d)." % failed[0])
+        if failed is not None:
+            raise _lib.MrbfError(failed[1], "mrbf_db_round3_batch: start %d" % failed[0])
+    return out
+
+
+def prepare_improve_models_resident(dbs, metas, cfgs, xs, deltas, lb, ub, ctx=None, stats=None):
+    """prepare_improve_model (RbfModel.jl:699-732) for a batch of starts: every meta that is not fully linear and has improving
+    directions takes one improvement step, all of them in ONE mrbf_db_round3_batch (MRBF_R3_IMPROVE) per d.  The metas (dicts as
+    `prepare_update_models_*` return them) are updated in place and returned."""
+    from .descent import _local_bounds
+
+    ns = len(dbs)
+    cfgs, deltas = _per(cfgs, ns), _per(deltas, ns)
+    act = [p for p in range(ns) if not metas[p]["fully_linear"] and len(metas[p]["improving_directions"]) > 0]
+    if not act:
+        return metas
+    lb1s, ub1s, pivs = [], [], []
+    for p in act:
+        d1 = cfgs[p].θ_enlarge_1 * deltas[p]
+        l1, u1 = _local_bounds(xs[p], d1, lb, ub)
+        lb1s.append(l1), ub1s.append(u1), pivs.append(d1 * cfgs[p].θ_pivot)
+    res = rbf_round3_resident([dbs[p] for p in act], lb1s, ub1s, [xs[p] for p in act], pivs, [list(metas[p]["improving_directions"]) for p in act],
+                              1, 1, improve=True, ctx=ctx, stats=stats)
+    for p, r in zip(act, res):
+        metas[p]["improving_directions"] = r.remaining_directions
+        metas[p]["round1_indices"] = list(metas[p]["round1_indices"]) + list(r.indices)
+        if r.fully_linear:
+            metas[p]["fully_linear"] = True
+    return metas
+
+
+def _num_unevaluated(values):
+    """length(_missing_ids(db)): rows whose values are NaN"""
+    V = np.asarray(values, dtype=np.float64)
+    return int(np.count_nonzero(np.isnan(V).any(axis=1))) if V.size else 0
+
+
+def _prepare_update_models(cfgs, dbs, xs, x_indices, deltas, delta_max, lb, ub, ensure_fully_linear, max_evals, num_evals, force_rebuild, find,
+                           round3, round4):
+    """prepare_update_model (RbfModel.jl:518-655) for a list of starts, phase by phase; `find`, `round3` and `round4` are the list
+    forms of _find_suitable_points, _rbf_round3 (rebuild included, points appended) and _rbf_round4 on the databases `dbs`.  Round 1 is
+    told which starts skip round 2 whatever it finds (`skips_round2`): the resident form leaves their Z on the device for round 3."""
+    from .descent import _isapprox, _local_bounds
+
+    ns = len(dbs)
+    cfgs, deltas, efl, force, num_evals = _per(cfgs, ns), _per(deltas, ns), _per(ensure_fully_linear, ns), _per(force_rebuild, ns), _per(num_evals, ns)
+    xs = [np.asarray(x, dtype=np.float64) for x in xs]
+    metas = [dict(center_index=int(x_indices[p]), round1_indices=[], round2_indices=[], round3_indices=[], round4_indices=[],
+                  fully_linear=False, improving_directions=[], rebuilt=False) for p in range(ns)]
+    lb1, ub1, piv1, lb2, ub2 = [None] * ns, [None] * ns, [None] * ns, [None] * ns, [None] * ns
+    for p in range(ns):
+        d1 = cfgs[p].θ_enlarge_1 * deltas[p]
+        lb1[p], ub1[p] = _local_bounds(xs[p], d1, lb, ub)
+        piv1[p] = cfgs[p].θ_pivot * d1
+        lb2[p], ub2[p] = _local_bounds(xs[p], cfgs[p].θ_enlarge_2 * delta_max, lb, ub)
+    sub = lambda seq, which: [seq[p] for p in which]
+    # ---- round 1 (:564-579)
+    searching = [p for p in range(ns) if not (force[p] or not cfgs[p].optimized_sampling)]
+    cand1, Y1, Z1, dirs = {}, {}, {}, {p: None for p in range(ns)}       # (None: the coordinate axes, :568)
+    # (the filter takes one pivot value per call: starts are grouped by theirs)
+    groups = {}
+    for p in searching:
+        groups.setdefault(float(piv1[p]), []).append(p)
+    # (:588 without its first clause: known before round 1; such a start never continues from its Y and Z)
+    skips2 = [bool(force[p] or not cfgs[p].optimized_sampling or efl[p] or
+                   (_isapprox(deltas[p], delta_max) and cfgs[p].θ_enlarge_1 == cfgs[p].θ_enlarge_2)) for p in range(ns)]
+    for piv, which in groups.items():
+        for p, (picked, drs, cand, Y, Z) in zip(which, find(sub(dbs, which), sub(lb1, which), sub(ub1, which), sub(xs, which), sub(x_indices, which), piv,
+                                                            skips_round2=sub(skips2, which))):
+            metas[p]["round1_indices"], dirs[p], cand1[p], Y1[p], Z1[p] = list(picked), drs, cand, Y, Z
+    # ---- round 2 (:586-603)
+    n_missing = [xs[p].size - len(metas[p]["round1_indices"]) for p in range(ns)]
+    second = {}
+    for p in range(ns):
+        c = cfgs[p]
+        if n_missing[p] == 0 or force[p] or not c.optimized_sampling or efl[p] or \
+                (_isapprox(deltas[p], delta_max) and c.θ_enlarge_1 == c.θ_enlarge_2):
+            metas[p]["fully_linear"] = True
+        else:
+            second.setdefault(float(piv1[p]), []).append(p)
+    for piv, which in second.items():
+        res = find(sub(dbs, which), sub(lb2, which), sub(ub2, which), sub(xs, which), sub(x_indices, which), piv,
+                   already_inspected_indices=[cand1[p] for p in which], Ys=[Y1[p] for p in which], Zs=[Z1[p] for p in which],
+                   n_missing=[n_missing[p] for p in which], collect_improving_directions=False)
+        for p, r in zip(which, res):
+            metas[p]["round2_indices"] = list(r[0])
+    # ---- round 3 (:609-639), the rebuild inside the call
+    third = []
+    for p in range(ns):
+        n_missing[p] -= len(metas[p]["round2_indices"])
+        on_device = hasattr(dirs[p], "data_ptr")            # (d - |round 1| rows: with any row left, round 3 below replaces the list)
+        metas[p]["improving_directions"] = _axes(xs[p].size) if dirs[p] is None else ([] if on_device else list(dirs[p]))
+        if n_missing[p] > 0:
+            third.append(p)
+    if third:
+        max_new = [max(0, min(max_evals, cfgs[p].max_evals) - 1 - num_evals[p] - _num_unevaluated(dbs[p].values)) for p in third]
+        res = round3(sub(dbs, third), sub(lb1, third), sub(ub1, third), sub(xs, third), sub(piv1, third), [dirs[p] for p in third], max_new,
+                     [n_missing[p] for p in third], [efl[p] for p in third], [force[p] for p in third],
+                     [hasattr(dirs[p], "data_ptr") for p in third])
+        for p, r in zip(third, res):
+            m = metas[p]
+            if r.rebuilt:   # the recursive call with force_rebuild: rounds 1 and 2 are empty, round 2 is skipped (fully linear so far)
+                m["round1_indices"], m["round2_indices"], m["rebuilt"] = [], [], True
+                m["fully_linear"] = bool(r.fully_linear)
+            else:
+                m["fully_linear"] = bool(r.fully_linear) and len(m["round2_indices"]) == 0     # :631
+            m["round3_indices"], m["improving_directions"] = list(r.indices), r.remaining_directions
+    # ---- round 4 (:645-652)
+    fourth = [p for p in range(ns) if cfgs[p].optimized_sampling]
+    if fourth:
+        found = [[metas[p]["center_index"], *metas[p]["round1_indices"], *metas[p]["round2_indices"], *metas[p]["round3_indices"]] for p in fourth]
+        for p, r4 in zip(fourth, round4(sub(dbs, fourth), sub(lb2, fourth), sub(ub2, fourth), sub(xs, fourth), sub(deltas, fourth), found, sub(cfgs, fourth))):
+            metas[p]["round4_indices"] = list(r4)
+    return metas
+
+
+def prepare_update_models_many(cfgs, dbs, xs, x_indices, deltas, delta_max, lb, ub, ensure_fully_linear=False, max_evals=2 ** 63 - 1,
+                               num_evals=0, force_rebuild=False, ctx=None):
+    """prepare_update_model (RbfModel.jl:518-655) for a list of starts on host databases (`database.HostDatabase`: `sites`, `values`,
+    `append`): the host-array twin of `prepare_update_models_resident`, built from `find_suitable_points_many`, `rbf_round3_many` and
+    `rbf_round4_many`.  -> one meta (dict) per start: center_index, round1..4_indices, fully_linear, improving_directions, rebuilt.
+    One RBF config per start (_exploit_other_rbf_metas! is not mirrored)."""
+    def find(dbs_, *a, skips_round2=None, **kw):
+        return find_suitable_points_many([db.sites for db in dbs_], *a, ctx=ctx, **kw)
+
+    def round3(dbs_, lb1s, ub1s, xs_, pivs, dirs, max_news, n_missings, efl, force, rev):
+        res = rbf_round3_many(lb1s, ub1s, xs_, pivs, dirs, max_news, n_missings, efl, force, reversed_order=rev)
+        for db, r in zip(dbs_, res):
+            first = db.append(r.new_points)
+            r.indices = list(range(first, first + r.new_points.shape[0]))
+        return res
+
+    def round4(dbs_, lb2s, ub2s, xs_, deltas_, found, cfgs_):
+        return rbf_round4_many([db.sites for db in dbs_], lb2s, ub2s, xs_, deltas_, found, cfgs_, ctx=ctx)
+
+    return _prepare_update_models(cfgs, dbs, xs, x_indices, deltas, delta_max, lb, ub, ensure_fully_linear, max_evals, num_evals, force_rebuild,
+                                  find, round3, round4)
+
+
+def prepare_update_models_resident(cfgs, dbs, xs, x_indices, deltas, delta_max, lb, ub, ensure_fully_linear=False, max_evals=2 ** 63 - 1,
+                                   num_evals=0, force_rebuild=False, ctx=None):
+    """`prepare_update_models_many` on resident databases: `find_suitable_points_resident`, `rbf_round3_resident` (one
+    mrbf_db_round3_batch per d, the new sites written straight into the databases) and `rbf_round4_resident`.  Returns the same metas."""
+    def find(dbs_, *a, skips_round2=None, **kw):
+        return find_suitable_points_resident(dbs_, *a, ctx=ctx, keep_Z_on_device=skips_round2, **kw)
+
+    def round3(dbs_, lb1s, ub1s, xs_, pivs, dirs, max_news, n_missings, efl, force, rev):
+        return rbf_round3_resident(dbs_, lb1s, ub1s, xs_, pivs, dirs, max_news, n_missings, efl, force, reversed_order=rev, ctx=ctx)
+
+    def round4(dbs_, lb2s, ub2s, xs_, deltas_, found, cfgs_):
+        return rbf_round4_resident(dbs_, lb2s, ub2s, xs_, deltas_, found, cfgs_, ctx=ctx)
+
+    return _prepare_update_models(cfgs, dbs, xs, x_indices, deltas, delta_max, lb, ub, ensure_fully_linear, max_evals, num_evals, force_rebuild,
+                                  find, round3, round4)
