@@ -19,4 +19,4 @@ from .rbf_model import (RbfConfig, RbfKernels, RbfModel, combinable, eval_models
                         init_model, max_evals, model_from_coeffs, num_outputs, parse_shape_param_string,
                         set_fully_linear, update_model, update_models_many, update_models_resident)
 from . import database, descent, pascoletti_serafini, sampling, surrogates  # noqa: F401
-from .database import DeviceDatabase, DeviceView, box_many, gather_many  # noqa: F401
+from .database import DeviceDatabase, DeviceView, HostDatabase, box_many, gather_many  # noqa: F401

@@ -8,7 +8,8 @@ pick (AffinelyIndependentPoints.jl:25, :53) for a batch of starts in one call, `
 
 A database keeps a host copy of its sites and values, as the caller's own database does: the small host-side steps (the filter's Y,
 the fall-backs to the host filter or to the single calls) need no read-back, and when the decision table (mrbf_dispatch_db_batch) sends a
-call to the host, the scan and the copies run on that copy.
+call to the host, the scan and the copies run on that copy.  `HostDatabase` is that copy alone; the batched functions take lists of
+either kind (one kind per call) and serve host databases by their host branch, without a context.
 """
 import ctypes
 
@@ -52,18 +53,28 @@ class DeviceView:
         return a if dtype is None else a.astype(dtype, copy=False)
 
 
-class DeviceDatabase:
-    """mrbf_db: the sites (d) and values (k) of one start, rows in insertion order, with a host copy (`sites`, `values`)."""
+def _host_rows(a):
+    if hasattr(a, "data_ptr"):          # a torch tensor, host or device
+        return a.detach().cpu().numpy()
+    return a
 
-    def __init__(self, d, k, ctx=None, capacity=0):
-        self.ctx = ctx or _lib.default_context()
-        self.d, self.k = int(d), int(k)
-        h = _lib.c_vp()
-        self.ctx.check(self.ctx.lib.mrbf_db_create(self.ctx.h, self.d, self.k, int(capacity), ctypes.byref(h)))
-        self.h = h
-        self._n = 0
-        self._S = np.empty((max(int(capacity), 16), self.d))
-        self._V = np.empty((max(int(capacity), 16), self.k))
+
+class HostDatabase:
+    """the sites (d) and values (k) of one start on the host, rows in insertion order: the database of a start where the device is not
+    asked, and the host copy a `DeviceDatabase` keeps.  The many-start drivers (`sampling.prepare_update_models`) take either kind."""
+
+    def __init__(self, d, k, capacity=0):
+        self.d, self.k, self._n = int(d), int(k), 0
+        self._S, self._V = np.empty((max(int(capacity), 16), self.d)), np.empty((max(int(capacity), 16), self.k))
+
+    @classmethod
+    def of_sites(cls, sites, d):
+        """a plain (N, d) array or list of sites as a database without values; the caller's array is read, never written"""
+        db = cls.__new__(cls)
+        S = np.asarray(sites, dtype=np.float64).reshape(-1, int(d)).view()
+        S.flags.writeable = False
+        db.d, db.k, db._n, db._S, db._V = int(d), 0, S.shape[0], S, np.empty((S.shape[0], 0))
+        return db
 
     def __len__(self):
         return self._n
@@ -76,14 +87,46 @@ class DeviceDatabase:
     def values(self):
         return self._V[: self._n]
 
-    def _host_rows(self, a):
-        if hasattr(a, "data_ptr"):          # a torch tensor, host or device
-            return a.detach().cpu().numpy()
-        return a
+    def _adopt_rows(self, S, V=None):
+        """m new rows on the host: `S` m x d, `V` m x k or None (NaN); the capacity doubles when they do not fit"""
+        n, m = self._n, int(S.shape[0])
+        if m == 0:
+            return
+        if n + m > self._S.shape[0]:
+            cap = max(2 * self._S.shape[0], n + m)
+            self._S = np.concatenate([self._S[:n], np.empty((cap - n, self.d))])
+            self._V = np.concatenate([self._V[:n], np.empty((cap - n, self.k))])
+        self._S[n: n + m] = S
+        self._V[n: n + m] = _NAN if V is None else V
+        self._n += m
 
     def append(self, sites, values=None):
-        """new_result! for m rows: `sites` m x d, `values` m x k or None (unevaluated rows, stored as NaN: round 3, RbfModel.jl:303);
-        NumPy arrays or torch tensors (a device tensor is read in place).  Returns the position of the first new row."""
+        """new_result! for m rows: `sites` m x d, `values` m x k or None (unevaluated rows, stored as NaN: round 3, RbfModel.jl:303).
+        Returns the position of the first new row."""
+        S = np.asarray(_host_rows(sites), dtype=np.float64).reshape(-1, self.d)
+        first = self._n
+        self._adopt_rows(S, None if values is None else np.asarray(_host_rows(values), dtype=np.float64).reshape(S.shape[0], self.k))
+        return first
+
+    def set_values(self, indices, values):
+        """eval_missing! (Databases.jl:258-277): the values of the rows `indices` (distinct positions)"""
+        idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+        if idx.size:
+            self._V[idx] = np.asarray(_host_rows(values), dtype=np.float64).reshape(idx.size, self.k)
+
+
+class DeviceDatabase(HostDatabase):
+    """mrbf_db: the sites (d) and values (k) of one start resident on the device, with the host copy (`sites`, `values`) it inherits"""
+
+    def __init__(self, d, k, ctx=None, capacity=0):
+        super().__init__(d, k, capacity)
+        self.ctx = ctx or _lib.default_context()
+        h = _lib.c_vp()
+        self.ctx.check(self.ctx.lib.mrbf_db_create(self.ctx.h, self.d, self.k, int(capacity), ctypes.byref(h)))
+        self.h = h
+
+    def append(self, sites, values=None):
+        """`HostDatabase.append` on the device and on the host copy; NumPy arrays or torch tensors (a device tensor is read in place)"""
         S = sites.contiguous() if hasattr(sites, "data_ptr") else _lib.host_f64(sites).reshape(-1, self.d)
         m = int(S.shape[0]) if S.ndim == 2 else int(S.numel() // self.d)
         V = None
@@ -91,23 +134,15 @@ class DeviceDatabase:
             V = values.contiguous() if hasattr(values, "data_ptr") else _lib.host_f64(values).reshape(m, self.k)
         first = ctypes.c_int64(-1)
         self.ctx.check(self.ctx.lib.mrbf_db_append(self.ctx.h, self.h, m, _lib.as_ptr(S), _lib.as_ptr(V), ctypes.byref(first)))
-        if self._n + m > self._S.shape[0]:
-            cap = max(2 * self._S.shape[0], self._n + m)
-            self._S = np.concatenate([self._S[: self._n], np.empty((cap - self._n, self.d))])
-            self._V = np.concatenate([self._V[: self._n], np.empty((cap - self._n, self.k))])
-        self._S[self._n: self._n + m] = np.asarray(self._host_rows(S), dtype=np.float64).reshape(m, self.d)
-        self._V[self._n: self._n + m] = _NAN if V is None else np.asarray(self._host_rows(V), dtype=np.float64).reshape(m, self.k)
-        self._n += m
-        assert first.value == self._n - m
-        return int(first.value)
+        at = super().append(S, V)
+        assert first.value == at
+        return at
 
     def set_values(self, indices, values):
-        """eval_missing! (Databases.jl:258-277): the values of the rows `indices` (distinct positions)"""
         idx = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
         V = values.contiguous() if hasattr(values, "data_ptr") else _lib.host_f64(values).reshape(idx.size, self.k)
         self.ctx.check(self.ctx.lib.mrbf_db_set_values(self.ctx.h, self.h, idx.size, _lib.as_ptr(idx), _lib.as_ptr(V)))
-        if idx.size:
-            self._V[idx] = np.asarray(self._host_rows(V), dtype=np.float64).reshape(idx.size, self.k)
+        super().set_values(idx, V)
 
     def read(self, first=0, m=None):
         """rows first .. first + m - 1 as the device holds them -> (sites, values)"""
@@ -133,35 +168,17 @@ class DeviceDatabase:
             pass
 
 
-class HostDatabase:
-    """the host copy alone, with `DeviceDatabase`'s interface (`sites`, `values`, `append`, `set_values`): what the host-array twins
-    of the resident drivers (`sampling.prepare_update_models_many`) append their new sites to"""
+def as_databases(dbs, xs):
+    """the databases of one call of a many-start driver -> (list of databases, resident): every entry is a `DeviceDatabase`, a
+    `HostDatabase`, or a plain (N, d) array or list of sites (d that of the start's centre `xs[p]`), which is wrapped; all of one kind"""
+    dbs = [db if isinstance(db, HostDatabase) else HostDatabase.of_sites(db, np.size(xs[p])) for p, db in enumerate(dbs)]
+    return dbs, _resident(dbs)
 
-    def __init__(self, d, k):
-        self.d, self.k, self._n = int(d), int(k), 0
-        self._S, self._V = np.empty((16, self.d)), np.empty((16, self.k))
 
-    def __len__(self):
-        return self._n
-
-    @property
-    def sites(self):
-        return self._S[: self._n]
-
-    @property
-    def values(self):
-        return self._V[: self._n]
-
-    def append(self, sites, values=None):
-        S = np.asarray(sites, dtype=np.float64).reshape(-1, self.d)
-        first = self._n
-        _adopt_rows(self, S, None if values is None else np.asarray(values, dtype=np.float64).reshape(S.shape[0], self.k))
-        return first
-
-    def set_values(self, indices, values):
-        idx = np.asarray(indices, dtype=np.int64).reshape(-1)
-        if idx.size:
-            self._V[idx] = np.asarray(values, dtype=np.float64).reshape(idx.size, self.k)
+def _resident(dbs):
+    kinds = {isinstance(db, DeviceDatabase) for db in dbs}
+    assert len(kinds) <= 1, "the databases of a call are all resident or all on the host"
+    return kinds == {True}
 
 
 class BoxResult:
@@ -191,11 +208,11 @@ def _box_host(db, lb, ub, x0, exclude, p, zero_first_pick):
 def box_many(dbs, lbs, ubs, x0s, excludes, p=np.inf, zero_first_pick=True, ctx=None, stats=None):
     """results_in_box_indices + shifted rows + the filter's first pick for a list of databases of one d in ONE call
     (mrbf_db_box_batch) -> list of BoxResult.  `excludes[p]`: positions to leave out (duplicates and positions outside the database
-    allowed).  Where mrbf_dispatch_db_batch sends the call to the host (or it returns -2), the same runs on the host copies;
-    stats["path"] = "device" or "host".  The views stay valid until the next `box_many` on the context."""
+    allowed).  On host databases, and where mrbf_dispatch_db_batch sends the call to the host (or it returns -2), the same runs on the
+    host copies, without a context; stats["path"] = "device" or "host".  The views stay valid until the next `box_many` on the context."""
     ns = len(dbs)
     stats = stats if stats is not None else {}
-    ctx = ctx or (dbs[0].ctx if ns else _lib.default_context())
+    resident = _resident(dbs)
     d = dbs[0].d if ns else 1
     assert all(db.d == d for db in dbs), "the databases of a call share d"
     x0s = [_lib.host_f64(x).reshape(d) for x in x0s]
@@ -205,8 +222,9 @@ def box_many(dbs, lbs, ubs, x0s, excludes, p=np.inf, zero_first_pick=True, ctx=N
         return [_box_host(dbs[q], np.asarray(lbs[q], dtype=np.float64), np.asarray(ubs[q], dtype=np.float64), x0s[q], excludes[q], p,
                           zero_first_pick) for q in range(ns)]
 
-    if ctx.lib.mrbf_dispatch_db_batch(ns, d) != _lib.DISPATCH_DEVICE:
+    if not resident or _lib.load().mrbf_dispatch_db_batch(ns, d) != _lib.DISPATCH_DEVICE:
         return host()
+    ctx = ctx or dbs[0].ctx
     jobs = (_lib.DbBoxJob * ns)()
     keep = []
     for q, db in enumerate(dbs):
@@ -256,10 +274,10 @@ class GatherResult:
 
 def gather_many(dbs, index_lists, ctx=None, stats=None):
     """the rows `index_lists[p]` (any order, repeats allowed) of every database of one d in ONE call (mrbf_db_gather_batch) -> list of
-    GatherResult.  Falls back to the host copies like `box_many`.  The views stay valid until the next `gather_many` on the context."""
+    GatherResult.  Host databases, and the fall-backs, as in `box_many`.  The views stay valid until the next `gather_many` on the context."""
     ns = len(dbs)
     stats = stats if stats is not None else {}
-    ctx = ctx or (dbs[0].ctx if ns else _lib.default_context())
+    resident = _resident(dbs)
     d = dbs[0].d if ns else 1
     assert all(db.d == d for db in dbs), "the databases of a call share d"
     lists = [np.ascontiguousarray(list(l), dtype=np.int64).reshape(-1) for l in index_lists]
@@ -275,8 +293,9 @@ def gather_many(dbs, index_lists, ctx=None, stats=None):
             out.append(r)
         return out
 
-    if ctx.lib.mrbf_dispatch_db_batch(ns, d) != _lib.DISPATCH_DEVICE:
+    if not resident or _lib.load().mrbf_dispatch_db_batch(ns, d) != _lib.DISPATCH_DEVICE:
         return host()
+    ctx = ctx or dbs[0].ctx
     jobs = (_lib.DbGatherJob * ns)()
     for q, db in enumerate(dbs):
         jobs[q].db, jobs[q].n_idx, jobs[q].indices = db.h, lists[q].size, lists[q].ctypes.data if lists[q].size else None
@@ -299,40 +318,26 @@ def gather_many(dbs, index_lists, ctx=None, stats=None):
     return out
 
 
-def _grow_host(db, m):
-    if db._n + m > db._S.shape[0]:
-        cap = max(2 * db._S.shape[0], db._n + m)
-        db._S = np.concatenate([db._S[: db._n], np.empty((cap - db._n, db.d))])
-        db._V = np.concatenate([db._V[: db._n], np.empty((cap - db._n, db.k))])
-
-
-def _adopt_rows(db, S, V=None):
-    """the host copy's side of an append the device has done already: `S` m x d, `V` m x k or None (NaN)"""
-    m = int(S.shape[0])
-    _grow_host(db, m)
-    db._S[db._n: db._n + m] = S
-    db._V[db._n: db._n + m] = _NAN if V is None else V
-    db._n += m
-
-
 def append_many(dbs, sites_list, values_list=None, ctx=None, stats=None):
     """`DeviceDatabase.append` for every database of the list in ONE call (mrbf_db_append_batch: one packed upload, one launch, one
     synchronisation) -- the trial points of an iteration.  `sites_list[p]`: m_p x d_p, `values_list[p]`: m_p x k_p or None (unevaluated
     rows); NumPy arrays or torch tensors.  Returns the position of the first new row per database; the host copies are kept in step.
-    Where mrbf_dispatch_db_batch sends the call to the host it is the loop of single appends; stats["path"] says which."""
+    On host databases, and where mrbf_dispatch_db_batch sends the call to the host, it is the loop of single appends; stats["path"]
+    says which."""
     ns = len(dbs)
     stats = stats if stats is not None else {}
     if ns == 0:
         return []
-    ctx = ctx or dbs[0].ctx
+    resident = _resident(dbs)
     values_list = [None] * ns if values_list is None else values_list
 
     def loop():
         stats["path"] = "loop"
         return [db.append(sites_list[q], values_list[q]) for q, db in enumerate(dbs)]
 
-    if ctx.lib.mrbf_dispatch_db_batch(ns, 1) != _lib.DISPATCH_DEVICE:
+    if not resident or _lib.load().mrbf_dispatch_db_batch(ns, 1) != _lib.DISPATCH_DEVICE:
         return loop()
+    ctx = ctx or dbs[0].ctx
     jobs = (_lib.DbAppendJob * ns)()
     keep = []
     for q, db in enumerate(dbs):
@@ -359,8 +364,7 @@ def append_many(dbs, sites_list, values_list=None, ctx=None, stats=None):
             raise _lib.MrbfError(jobs[q].rc, "mrbf_db_append_batch: start %d" % q)
         assert int(jobs[q].first_index) == len(db)
         out.append(len(db))
-        _adopt_rows(db, np.asarray(db._host_rows(S), dtype=np.float64).reshape(m, db.d),
-                    None if V is None else np.asarray(db._host_rows(V), dtype=np.float64).reshape(m, db.k))
+        HostDatabase.append(db, S, V)
     stats.update(path="device", ms_total=float(ms.value))
     return out
 
@@ -368,12 +372,13 @@ def append_many(dbs, sites_list, values_list=None, ctx=None, stats=None):
 def set_values_many(dbs, index_lists, values_list, ctx=None, stats=None, strict=True):
     """`DeviceDatabase.set_values` (eval_missing!, Databases.jl:258-277) for every database of the list in ONE call
     (mrbf_db_set_values_batch).  Returns the rc of every start: 0, or -4 for an index list with a position outside the database --
-    nothing of that start is written; with `strict` that raises after the other starts are done.  The host copies are kept in step."""
+    nothing of that start is written; with `strict` that raises after the other starts are done.  The host copies are kept in step.
+    Host databases take the loop of single calls."""
     ns = len(dbs)
     stats = stats if stats is not None else {}
     if ns == 0:
         return []
-    ctx = ctx or dbs[0].ctx
+    resident = _resident(dbs)
     idxs = [np.ascontiguousarray(list(l) if not isinstance(l, np.ndarray) else l, dtype=np.int64).reshape(-1) for l in index_lists]
 
     def loop():
@@ -389,8 +394,9 @@ def set_values_many(dbs, index_lists, values_list, ctx=None, stats=None, strict=
                 rcs.append(e.code)
         return rcs
 
-    if ctx.lib.mrbf_dispatch_db_batch(ns, 1) != _lib.DISPATCH_DEVICE:
+    if not resident or _lib.load().mrbf_dispatch_db_batch(ns, 1) != _lib.DISPATCH_DEVICE:
         return loop()
+    ctx = ctx or dbs[0].ctx
     jobs = (_lib.DbSetValuesJob * ns)()
     keep = []
     for q, db in enumerate(dbs):
@@ -410,8 +416,8 @@ def set_values_many(dbs, index_lists, values_list, ctx=None, stats=None, strict=
     rcs = []
     for q, db in enumerate(dbs):
         rcs.append(int(jobs[q].rc))
-        if rcs[q] == 0 and idxs[q].size:
-            db._V[idxs[q]] = np.asarray(db._host_rows(keep[q]), dtype=np.float64).reshape(idxs[q].size, db.k)
+        if rcs[q] == 0:
+            HostDatabase.set_values(db, idxs[q], keep[q])
     stats.update(path="device", ms_total=float(ms.value))
     bad = [q for q, r in enumerate(rcs) if r != 0]
     if strict and bad:

@@ -157,23 +157,47 @@ class AffinelyIndependentPointFilter:
         return out
 
 
-def affine_select_batch_device(items, d, p=np.inf, ctx=None):
+def _per(v, ns):
+    return list(v) if isinstance(v, (list, tuple)) else [v] * ns
+
+
+def _by_d(dbs):
+    """the positions of the databases of a call, grouped by d (one d per batched library call)"""
+    groups = {}
+    for p, db in enumerate(dbs):
+        groups.setdefault(db.d, []).append(p)
+    return groups
+
+
+def _job_rows(a, d):
+    """a job's block of sites: a device view or tensor is read in place, anything else becomes a contiguous float64 (m, d) array"""
+    return a if hasattr(a, "data_ptr") else _lib.host_f64(a).reshape(-1, d)
+
+
+def affine_select_batch_device(items, d, p=np.inf, ctx=None, device_Z=None):
     """mrbf_affine_select_batch: `items` = one (Sd, qr, want, pivot_val) per start -- the rows of Sd are the start's candidates
-    (picked rows zeroed), `qr` the `_GrowingQR` of the directions chosen so far -> (rc, [(positions, final Z)] or None, ms).  Raises
-    nothing for an rc that `mrbf_dispatch_after` reads as "take the single calls"."""
+    (picked rows zeroed; a NumPy array, or a DeviceView or tensor, which is read in place), `qr` the `_GrowingQR` of the directions
+    chosen so far -> (rc, [(positions, final Z)] or None, ms).  `device_Z[k]` (optional): start k's Z_out is a device buffer and its
+    final Z comes back as a (dz, d) device tensor whose ROWS are the columns of Z (the memory of the column-major d x dz matrix), for
+    mrbf_db_round3_batch to read in place.  Raises nothing for an rc that `mrbf_dispatch_after` reads as "take the single calls"."""
     ctx = ctx or _lib.default_context()
     n = len(items)
     jobs = (_lib.AffineJob * max(n, 1))()
     keep = []
     for k, (Sd, qr, want, pivot) in enumerate(items):
-        Sd = np.ascontiguousarray(Sd, dtype=np.float64)
+        Sd = _job_rows(Sd, d)
         Q0 = np.asfortranarray(qr.Q)
         picks = np.empty(max(want, 1), dtype=np.int64)
-        Zbuf = np.empty((max(d - qr.j, 1), d))                          # (column-major d x dz)
+        if device_Z is not None and device_Z[k]:
+            import torch
+
+            Zbuf = torch.empty((max(d - qr.j, 1), d), dtype=torch.float64, device="cuda")
+        else:
+            Zbuf = np.empty((max(d - qr.j, 1), d))                      # (column-major d x dz)
         keep.append((Sd, Q0, picks, Zbuf))
-        jobs[k].mc, jobs[k].j0, jobs[k].max_picks, jobs[k].pivot_val = Sd.shape[0], qr.j, want, float(pivot)
-        jobs[k].shifted, jobs[k].Q0 = Sd.ctypes.data, Q0.ctypes.data
-        jobs[k].picked_out, jobs[k].Z_out = picks.ctypes.data, Zbuf.ctypes.data
+        jobs[k].mc, jobs[k].j0, jobs[k].max_picks, jobs[k].pivot_val = int(Sd.shape[0]), qr.j, want, float(pivot)
+        jobs[k].shifted, jobs[k].Q0 = _lib.as_ptr(Sd), Q0.ctypes.data
+        jobs[k].picked_out, jobs[k].Z_out = picks.ctypes.data, _lib.as_ptr(Zbuf)
     ms = ctypes.c_float(0.0)
     rc = ctx.lib.mrbf_affine_select_batch(ctx.h, n, d, 1 if np.isinf(p) else 0, jobs, ctypes.byref(ms))
     if rc != 0:
@@ -184,8 +208,23 @@ def affine_select_batch_device(items, d, p=np.inf, ctx=None):
     for k, (Sd, qr, want, pivot) in enumerate(items):
         _, _, picks, Zbuf = keep[k]
         got = [int(v) for v in picks[: jobs[k].n_picked]]
-        res.append((got, Zbuf[: d - qr.j - len(got)].T.copy()))
+        Zk = Zbuf[: d - qr.j - len(got)]
+        res.append((got, Zk if hasattr(Zk, "data_ptr") else Zk.T.copy()))
     return 0, res, float(ms.value)
+
+
+def _pick_loops(begun, d, p, ctx=None, device_Z=None):
+    """the device pick loops of one (d, norm) group of filters past their first pick -- `begun` = one (filter, Sd, qr, want) each -- in
+    ONE call (mrbf_affine_select_batch) when mrbf_dispatch_affine_batch takes the group; a group it does not take, and a batch the
+    library refuses (rc -2, mrbf_dispatch_after), run the single call per filter on the same Sd, from the same state
+    -> ([(positions, final Z)], whether the batched call served them)"""
+    rc = -2
+    if _lib.load().mrbf_dispatch_affine_batch(len(begun), d, 1 if np.isinf(p) else 0) == _lib.DISPATCH_DEVICE:
+        kw = {} if device_Z is None else {"device_Z": device_Z}
+        rc, res, _ = affine_select_batch_device([(Sd, qr, want, f.pivot_val) for f, Sd, qr, want in begun], d, p, ctx=ctx, **kw)
+    if rc != 0:
+        res = [f._select_device(Sd, qr, want) for f, Sd, qr, want in begun]
+    return res, rc == 0
 
 
 def affine_collect_many(filters, stats=None, ctx=None):
@@ -208,25 +247,18 @@ def affine_collect_many(filters, stats=None, ctx=None):
         else:
             out[k] = f.collect()
     batched = []
-    for (d, is_inf, _), members in groups.items():
-        if lib.mrbf_dispatch_affine_batch(len(members), d, 1 if is_inf else 0) != _lib.DISPATCH_DEVICE:
-            for k in members:
-                out[k] = filters[k].collect()
-            continue
-        begun, items = [], []
+    for (d, _, _), members in groups.items():
+        begun = []
         for k in members:
             f = filters[k]
-            o, qr, S, i, _ = f._begin()
-            Sd, want = f._device_job(o, qr, S, i)
-            begun.append((o, qr, S, Sd, want))
-            items.append((Sd, qr, want, f.pivot_val))
+            out[k], qr, S, i, _ = f._begin()
+            Sd, want = f._device_job(out[k], qr, S, i)
+            begun.append((f, Sd, qr, want, S))
         f0 = filters[members[0]]
-        rc, res, _ = affine_select_batch_device(items, d, f0.p, ctx=f0.ctx or ctx)
-        for pos, k in enumerate(members):
-            o, qr, S, Sd, want = begun[pos]
-            got, Z = res[pos] if rc == 0 else filters[k]._select_device(Sd, qr, want)   # refused: the single call, from the same state
-            out[k] = filters[k]._accept_device(o, S, got, Z)
-        if rc == 0:
+        res, served = _pick_loops([b[:4] for b in begun], d, f0.p, ctx=f0.ctx or ctx)
+        for k, (f, _, _, _, S), (got, Z) in zip(members, begun, res):
+            f._accept_device(out[k], S, got, Z)
+        if served:
             batched.extend(members)
     if stats is not None:
         stats["path"] = "batch" if batched else "loop"
@@ -253,29 +285,70 @@ def _find_suitable_points(sites, lb, ub, x, x_index, piv_val, already_inspected_
     return picked, dirs, cand, flt.Y, flt.Z
 
 
-def find_suitable_points_many(sites_list, lbs, ubs, xs, x_indices, piv_val, already_inspected_indices=None, Ys=None, Zs=None, n_missing=None,
-                              collect_improving_directions=True, stats=None, ctx=None):
-    """`_find_suitable_points` (RbfModel.jl:205-238) for a list of starts -- start p has its own database `sites_list[p]`, box, centre
-    and, for a second round, its own Y / Z and `n_missing[p]` (entries may be None) -- with the filters of all starts collected by
-    `affine_collect_many`.  Returns the list of `_find_suitable_points`' tuples."""
-    ns = len(sites_list)
+def find_suitable_points_many(dbs, lbs, ubs, xs, x_indices, piv_val, already_inspected_indices=None, Ys=None, Zs=None, n_missing=None,
+                              collect_improving_directions=True, stats=None, ctx=None, keep_Z_on_device=None):
+    """`_find_suitable_points` (RbfModel.jl:205-238) for a list of starts -- start p has its own database `dbs[p]` (resident, host, or a
+    plain array of sites: `database.as_databases`), box, centre and, for a second round, its own Y / Z and `n_missing[p]` (entries may
+    be None).  Returns the list of `_find_suitable_points`' tuples.  The box scan, the shifted rows and the first pick of every start
+    come from `database.box_many` (resident: ONE mrbf_db_box_batch per d, first pick's row zeroed: the state the pick loop expects);
+    the first reflector starts on the host from the returned row; the pick loops of the starts the decision table sends to the device
+    (mrbf_dispatch_affine per start, mrbf_dispatch_affine_batch per group) read the shifted rows in place, in ONE
+    mrbf_affine_select_batch per d; a start the table keeps on the host runs the host filter on the host copy.
+    `keep_Z_on_device[p]` (optional, resident databases): the caller will not run a second round from start p's Y and Z (its round 2 is
+    skipped), so where the batched pick loop served the start and picked something its final Z stays on the device: the tuple's
+    directions AND its Z are then one (dz, d) device tensor whose rows are the columns of Z -- the improving directions are its rows
+    from the last to the first (`rbf_round3_append(..., reversed_order=True)` reads them in place)."""
+    from . import database
+
+    ns = len(dbs)
     opt = lambda seq, p: None if seq is None else seq[p]
-    cands, filters = [], []
-    for p in range(ns):
-        x = np.asarray(xs[p], dtype=np.float64)
-        sites = sites_list[p]
-        cand = results_in_box_indices(sites, lbs[p], ubs[p], [x_indices[p], *(opt(already_inspected_indices, p) or ())])
-        nm = opt(n_missing, p)
-        cands.append(cand)
-        filters.append(AffinelyIndependentPointFilter(x, [sites[i] for i in cand], n=x.size if nm is None else nm, Y=opt(Ys, p), Z=opt(Zs, p),
-                                                      p=np.inf, pivot_val=piv_val))
-    picks = affine_collect_many(filters, stats=stats, ctx=ctx)
-    res = []
-    for p, flt in enumerate(filters):
-        picked = [cands[p][i] for i in picks[p]]
-        dirs = [flt.Z[:, j].copy() for j in range(flt.Z.shape[1])][::-1] if collect_improving_directions else None
-        res.append((picked, dirs, cands[p], flt.Y, flt.Z))
-    return res
+    xs = [np.asarray(x, dtype=np.float64) for x in xs]
+    dbs, _ = database.as_databases(dbs, xs)
+    lib = _lib.load() if ns else None
+    res, batched = [None] * ns, []
+    for d, members in _by_d(dbs).items():
+        sub = lambda seq: [seq[p] for p in members]
+        excl = [[x_indices[p], *(opt(already_inspected_indices, p) or ())] for p in members]
+        boxes = database.box_many(sub(dbs), sub(lbs), sub(ubs), sub(xs), excl, p=np.inf, zero_first_pick=True, ctx=ctx)
+        begun, served = [], []
+        for p, B in zip(members, boxes):
+            nm = opt(n_missing, p)
+            flt = AffinelyIndependentPointFilter(xs[p], [], n=d if nm is None else nm, Y=opt(Ys, p), Z=opt(Zs, p), p=np.inf, pivot_val=piv_val)
+            res[p] = ([], flt, B.indices)
+            if B.mc == 0:
+                continue
+            if lib.mrbf_dispatch_affine(B.mc - 1, d) != _lib.DISPATCH_DEVICE:
+                flt.shifted = list(dbs[p].sites[B.indices] - xs[p])
+                res[p] = ([B.indices[i] for i in flt.collect()], flt, B.indices)
+                continue
+            qr = _GrowingQR(d, flt.Y)         # `_begin` with the scan's first pick: Y gains its row, the factorisation its first reflector
+            flt.Y = np.hstack([flt.Y, B.first_row[:, None]])
+            qr.append(B.first_row)
+            flt.Z = qr.complement(flt.p)
+            flt.ctx = ctx
+            begun.append((flt, B.shifted, qr, min(flt.n - 1, d - qr.j)))
+            served.append((p, B))
+        if not begun:
+            continue
+        in_place = keep_Z_on_device is not None and hasattr(begun[0][1], "data_ptr")
+        got_all, ok = _pick_loops(begun, d, np.inf, ctx=ctx, device_Z=[bool(keep_Z_on_device[p]) for p, _ in served] if in_place else None)
+        for (p, B), (flt, *_), (got, Z) in zip(served, begun, got_all):
+            picked = [B.indices[i] for i in [B.first_pick, *got]]
+            if got:
+                flt.Y, flt.Z = np.hstack([flt.Y, (dbs[p].sites[picked[1:]] - xs[p]).T]), Z
+            res[p] = (picked, flt, B.indices)
+        if ok:
+            batched.extend(p for p, _ in served)
+    if stats is not None:
+        stats["path"] = "batch" if batched else "loop"
+        stats["batched"] = sorted(batched)
+    final = []
+    for picked, flt, cand in res:
+        dirs = None
+        if collect_improving_directions:     # (a Z left on the device: its rows are the directions, last to first)
+            dirs = flt.Z if hasattr(flt.Z, "data_ptr") else [flt.Z[:, j].copy() for j in range(flt.Z.shape[1])][::-1]
+        final.append((picked, dirs, cand, flt.Y, flt.Z))
+    return final
 
 
 def _nullify_last_row(R):
@@ -380,19 +453,21 @@ def round4_batch_pays(n_starts, max_candidates):
 def rbf_round4_batch_device(items, d, ctx=None):
     """mrbf_round4_batch: `items` = one (cfg, start_sites, cand_sites, delta) per start -> (rc, [(rc_p, positions)] or None, ms): per
     start the return code of its own selection (0, or what mrbf_round4 returned for a start that took it inside the call) and the
-    positions (into its cand_sites) of the accepted sites in acceptance order.  No factor state is kept: the fits of a batch go
-    through `update_models_many`.  Raises nothing for an rc that `mrbf_dispatch_after` reads as "take the single calls"."""
+    positions (into its cand_sites) of the accepted sites in acceptance order.  The sites are NumPy arrays, or DeviceViews or tensors,
+    which are read in place.  No factor state is kept: the fits of a batch go through `update_models_many`.  Raises nothing for an rc
+    that `mrbf_dispatch_after` reads as "take the single calls"."""
     ctx = ctx or _lib.default_context()
     n = len(items)
     jobs = (_lib.Round4Job * max(n, 1))()
     keep = []
     for k, (cfg, C0, Xc, delta) in enumerate(items):
-        C0, Xc = _lib.host_f64(C0), _lib.host_f64(Xc).reshape(-1, d)
+        C0, Xc = _job_rows(C0, d), _job_rows(Xc, d)
         kid, a, b = rm._get_kernel_params(delta, cfg)
-        acc = np.zeros(max(Xc.shape[0], 1), dtype=np.int32)
+        mc = int(Xc.shape[0])
+        acc = np.zeros(max(mc, 1), dtype=np.int32)
         keep.append((C0, Xc, acc))
         J = jobs[k]
-        J.n0, J.mc, J.start_sites, J.cand_sites = C0.shape[0], Xc.shape[0], C0.ctypes.data, Xc.ctypes.data if Xc.shape[0] else None
+        J.n0, J.mc, J.start_sites, J.cand_sites = int(C0.shape[0]), mc, _lib.as_ptr(C0), _lib.as_ptr(Xc) if mc else None
         J.kernel_id, J.poly_deg, J.a, J.b = kid, cfg.polynomial_degree, a, b
         J.max_points, J.theta_pivot_cholesky, J.accepted_out = int(cfg.max_model_points), float(cfg.θ_pivot_cholesky), acc.ctypes.data
     ms = ctypes.c_float(0.0)
@@ -404,52 +479,65 @@ def rbf_round4_batch_device(items, d, ctx=None):
     return 0, [(int(jobs[k].rc), [int(v) for v in keep[k][2][: jobs[k].n_accepted]]) for k in range(n)], float(ms.value)
 
 
-def rbf_round4_many(sites_list, lb2s, ub2s, xs, deltas, indices_found_list, cfgs, ctx=None, stats=None, min_starts=None):
-    """`_rbf_round4` (RbfModel.jl:352-499) for a list of starts -- start p has its own database `sites_list[p]`, box, centre, radius,
-    indices found so far and (one per start, or one for all) config -- with the selections of all starts the decision table sends to
-    the device (mrbf_dispatch_round4, per start) in ONE call (mrbf_round4_batch) when mrbf_dispatch_round4_batch takes the group (one d
-    per call) and the batch pays (`round4_batch_pays`, measured; `min_starts` replaces the rule by a plain count: tests).  Every other start runs `_rbf_round4`: start sets that cannot carry
+def rbf_round4_many(dbs, lb2s, ub2s, xs, deltas, indices_found_list, cfgs, ctx=None, stats=None, min_starts=None):
+    """`_rbf_round4` (RbfModel.jl:352-499) for a list of starts -- start p has its own database `dbs[p]` (resident, host, or a plain
+    array of sites: `database.as_databases`), box, centre, radius, indices found so far and (one per start, or one for all) config --
+    with the selections of all starts the decision table sends to the device (mrbf_dispatch_round4, per start) in ONE call
+    (mrbf_round4_batch) when mrbf_dispatch_round4_batch takes the group (one d per call) and the batch pays (`round4_batch_pays`,
+    measured; `min_starts` replaces the rule by a plain count: tests).  The candidates of every start come from `database.box_many`
+    (the box of round 4 without the sites found so far; resident: ONE mrbf_db_box_batch per d), the start sites of the starts that form
+    a batch from `database.gather_many` (ONE mrbf_db_gather_batch); mrbf_round4_batch reads both in place (a box view and a gather view
+    are alive at once).  Every other start runs `_rbf_round4` on the database's host copy: start sets that cannot carry
     the tail, starts with `use_max_points` (their random box points need the caller's generator and site list, as for the single
     call), a batch the library refuses (rc -2: every start of it), and a start whose own rc `mrbf_dispatch_after` reads as "take the
     reference method".  Returns, per start, what `_rbf_round4` returns: database indices in acceptance order.  stats["path"] =
     "batch" when a batched call ran, else "loop"; stats["batched"] = the starts it served; stats["fallback"] = starts of a batch
     that went back to `_rbf_round4`."""
-    ns = len(sites_list)
-    per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * ns
-    cfgs, deltas = per(cfgs), per(deltas)
+    from . import database
+
+    ns = len(dbs)
+    cfgs, deltas = _per(cfgs, ns), _per(deltas, ns)
+    dbs, _ = database.as_databases(dbs, xs)
     out = [None] * ns
     lib = _lib.load() if ns else None
-    single = lambda p: _rbf_round4(sites_list[p], lb2s[p], ub2s[p], xs[p], deltas[p], indices_found_list[p], cfgs[p], ctx=ctx)
-    groups, prepared = {}, {}
-    for p in range(ns):
-        sites = np.asarray(sites_list[p], dtype=np.float64)
-        d, cfg, found = sites.shape[1], cfgs[p], list(indices_found_list[p])
-        max_points = (d + 1) * (d + 2) // 2 if cfg.max_model_points <= 0 else cfg.max_model_points
-        cand = results_in_box_indices(sites, lb2s[p], ub2s[p], found)
-        if cfg.use_max_points:
-            out[p] = single(p)
-        elif not (len(found) < max_points and cand):
-            out[p] = []
-        elif lib.mrbf_dispatch_round4(len(found), d, cfg.polynomial_degree, len(cand)) != _lib.DISPATCH_DEVICE:
-            out[p] = single(p)
-        else:
-            prepared[p] = (cfg, sites[found], sites[cand], deltas[p], cand)
-            groups.setdefault(d, []).append(p)
+    single = lambda p: _rbf_round4(dbs[p].sites, lb2s[p], ub2s[p], xs[p], deltas[p], indices_found_list[p], cfgs[p], ctx=ctx)
     batched, fallback = [], []
-    for d, members in groups.items():
-        pays = len(members) >= min_starts if min_starts is not None else round4_batch_pays(len(members), max(len(prepared[p][4]) for p in members))
+    for d, all_members in _by_d(dbs).items():
+        sub = lambda seq: [seq[p] for p in all_members]
+        boxes = database.box_many(sub(dbs), sub(lb2s), sub(ub2s), sub(xs), [list(indices_found_list[p]) for p in all_members], p=np.inf,
+                                  zero_first_pick=False, ctx=ctx)
+        members, prepared = [], {}
+        for p, B in zip(all_members, boxes):
+            cfg, found = cfgs[p], list(indices_found_list[p])
+            max_points = (d + 1) * (d + 2) // 2 if cfg.max_model_points <= 0 else cfg.max_model_points
+            if cfg.use_max_points:
+                out[p] = single(p)
+            elif not (len(found) < max_points and B.mc):
+                out[p] = []
+            elif lib.mrbf_dispatch_round4(len(found), d, cfg.polynomial_degree, B.mc) != _lib.DISPATCH_DEVICE:
+                out[p] = single(p)
+            else:
+                prepared[p] = (found, B)
+                members.append(p)
+        if not members:
+            continue
+        pays = len(members) >= min_starts if min_starts is not None else round4_batch_pays(len(members), max(prepared[p][1].mc for p in members))
         if not pays or lib.mrbf_dispatch_round4_batch(len(members), d) != _lib.DISPATCH_DEVICE:
             for p in members:
                 out[p] = single(p)
             continue
-        rc, res, _ = rbf_round4_batch_device([prepared[p][:4] for p in members], d, ctx=ctx)
+        starts = database.gather_many([dbs[p] for p in members], [prepared[p][0] for p in members], ctx=ctx)
+        for p, g in zip(members, starts):
+            if g.rc != 0:
+                raise _lib.MrbfError(g.rc, "rbf_round4_many: start %d has a found index outside its database" % p)
+        rc, res, _ = rbf_round4_batch_device([(cfgs[p], g.sites, prepared[p][1].sites, deltas[p]) for p, g in zip(members, starts)], d, ctx=ctx)
         for pos, p in enumerate(members):
             if rc != 0:                                   # refused: the single call per start
                 out[p] = single(p)
                 continue
             rc_p, accepted = res[pos]
             if rc_p == 0:
-                out[p] = [prepared[p][4][a] for a in accepted]
+                out[p] = [prepared[p][1].indices[a] for a in accepted]
                 batched.append(p)
             elif lib.mrbf_dispatch_after(_lib.ENTRY_ROUND4_BATCH, rc_p):
                 out[p] = single(p)
@@ -643,226 +731,6 @@ def _rbf_round4(sites, lb_2, ub_2, x, delta, indices_found_so_far, cfg, ctx=None
     return round4
 
 
-# ---- the many-start drivers on resident databases (database.DeviceDatabase): the twins of find_suitable_points_many and
-# rbf_round4_many.  The box scans, the shifted rows, the filter's first pick and the gathers of the start sites run on the device for
-# all starts of a call (mrbf_db_box_batch, mrbf_db_gather_batch) and the batched calls read the resulting device views in place; the
-# small host-side steps (the filter's Y, the Householder start) and every fall-back use the databases' host copies.
-
-
-def _affine_select_batch_views(items, d, p=np.inf, ctx=None, device_Z=None):
-    """`affine_select_batch_device` with the candidates given as anything `_lib.as_ptr` takes with a `shape` (a DeviceView is read in
-    place): `items` = one (Sd, qr, want, pivot_val) per start -> (rc, [(positions, final Z)] or None, ms).  `device_Z[k]` (optional):
-    start k's Z_out is a device buffer and its final Z comes back as a (dz, d) device tensor whose ROWS are the columns of Z (the
-    memory of the column-major d x dz matrix), for mrbf_db_round3_batch to read in place."""
-    ctx = ctx or _lib.default_context()
-    n = len(items)
-    jobs = (_lib.AffineJob * max(n, 1))()
-    keep = []
-    for k, (Sd, qr, want, pivot) in enumerate(items):
-        Q0 = np.asfortranarray(qr.Q)
-        picks = np.empty(max(want, 1), dtype=np.int64)
-        if device_Z is not None and device_Z[k]:
-            import torch
-
-            Zbuf = torch.empty((max(d - qr.j, 1), d), dtype=torch.float64, device="cuda")
-        else:
-            Zbuf = np.empty((max(d - qr.j, 1), d))                      # (column-major d x dz)
-        keep.append((Sd, Q0, picks, Zbuf))
-        jobs[k].mc, jobs[k].j0, jobs[k].max_picks, jobs[k].pivot_val = int(Sd.shape[0]), qr.j, want, float(pivot)
-        jobs[k].shifted, jobs[k].Q0 = _lib.as_ptr(Sd), Q0.ctypes.data
-        jobs[k].picked_out, jobs[k].Z_out = picks.ctypes.data, _lib.as_ptr(Zbuf)
-    ms = ctypes.c_float(0.0)
-    rc = ctx.lib.mrbf_affine_select_batch(ctx.h, n, d, 1 if np.isinf(p) else 0, jobs, ctypes.byref(ms))
-    if rc != 0:
-        if not ctx.lib.mrbf_dispatch_after(_lib.ENTRY_AFFINE_BATCH, rc):
-            ctx.check(rc)
-        return rc, None, 0.0
-    res = []
-    for k, (Sd, qr, want, pivot) in enumerate(items):
-        _, _, picks, Zbuf = keep[k]
-        got = [int(v) for v in picks[: jobs[k].n_picked]]
-        Zk = Zbuf[: d - qr.j - len(got)]
-        res.append((got, Zk if hasattr(Zk, "data_ptr") else Zk.T.copy()))
-    return 0, res, float(ms.value)
-
-
-def find_suitable_points_resident(dbs, lbs, ubs, xs, x_indices, piv_val, already_inspected_indices=None, Ys=None, Zs=None, n_missing=None,
-                                  collect_improving_directions=True, stats=None, ctx=None, keep_Z_on_device=None):
-    """`find_suitable_points_many` on resident databases: returns exactly its list of `_find_suitable_points` tuples.
-    `keep_Z_on_device[p]` (optional; the default keeps what is said here): the caller will not run a second round from start p's Y
-    and Z (its round 2 is skipped), so where the batched pick loop served the start and picked something its final Z stays on the device:
-    the tuple's directions AND its Z are then one (dz, d) device tensor whose rows are the columns of Z -- the improving directions
-    are its rows from the last to the first (`rbf_round3_resident(..., reversed_order=True)` reads them in place).  The box scan,
-    the shifted rows and the first pick of every start come from ONE mrbf_db_box_batch call per d (first pick's row zeroed: the state the
-    pick loop expects); the first reflector starts on the host from the returned row; the pick loops of the starts the decision table
-    sends to the device (mrbf_dispatch_affine per start, mrbf_dispatch_affine_batch per group) read the shifted rows in place.  A start
-    the table keeps on the host runs the host filter on the host copy, a batch the library refuses (rc -2) continues with the single
-    call per start on the same view; where mrbf_dispatch_db_batch sends the scan to the host the whole call is the host driver's."""
-    from . import database
-
-    ns = len(dbs)
-    opt = lambda seq, p: None if seq is None else seq[p]
-    lib = _lib.load() if ns else None
-    stats = stats if stats is not None else {}
-    by_d = {}
-    for p in range(ns):
-        by_d.setdefault(dbs[p].d, []).append(p)
-    if any(lib.mrbf_dispatch_db_batch(len(m), d) != _lib.DISPATCH_DEVICE for d, m in by_d.items()):
-        return find_suitable_points_many([db.sites for db in dbs], lbs, ubs, xs, x_indices, piv_val, already_inspected_indices, Ys, Zs,
-                                         n_missing, collect_improving_directions, stats=stats, ctx=ctx)
-    res, batched = [None] * ns, []
-    for d, members in by_d.items():
-        xs_m = [np.asarray(xs[p], dtype=np.float64) for p in members]
-        excl = [[x_indices[p], *(opt(already_inspected_indices, p) or ())] for p in members]
-        boxes = database.box_many([dbs[p] for p in members], [lbs[p] for p in members], [ubs[p] for p in members], xs_m, excl,
-                                  p=np.inf, zero_first_pick=True, ctx=ctx)
-        filters, device = {}, []
-        for pos, p in enumerate(members):
-            x, B, sites = xs_m[pos], boxes[pos], dbs[p].sites
-            nm = opt(n_missing, p)
-            on_host_copy = isinstance(B.shifted, np.ndarray)    # the scan itself fell back: everything from the host copy
-            flt = AffinelyIndependentPointFilter(x, [] if not on_host_copy else [sites[i] for i in B.indices], n=x.size if nm is None else nm,
-                                                 Y=opt(Ys, p), Z=opt(Zs, p), p=np.inf, pivot_val=piv_val)
-            filters[p] = flt
-            if B.mc == 0:
-                picks = []
-            elif on_host_copy or lib.mrbf_dispatch_affine(B.mc - 1, d) != _lib.DISPATCH_DEVICE:
-                if not on_host_copy:
-                    flt.shifted = [sites[i] - x for i in B.indices]
-                picks = flt.collect()
-            else:
-                # `_begin` with the device's first pick: Y gains its row, the factorisation its first reflector
-                i = B.first_pick
-                qr = _GrowingQR(d, flt.Y)
-                flt.Y = np.hstack([flt.Y, B.first_row[:, None]])
-                qr.append(B.first_row)
-                flt.Z = qr.complement(flt.p)
-                device.append((p, pos, [i], qr, min(flt.n - 1, d - qr.j)))
-                continue
-            res[p] = ([B.indices[i] for i in picks], flt, B.indices)
-        if device:
-            rc = -2
-            if lib.mrbf_dispatch_affine_batch(len(device), d, 1) == _lib.DISPATCH_DEVICE:
-                rc, got_all, _ = _affine_select_batch_views([(boxes[pos].shifted, qr, want, piv_val) for (_, pos, _, qr, want) in device], d,
-                                                            np.inf, ctx=ctx,
-                                                            device_Z=None if keep_Z_on_device is None else [bool(keep_Z_on_device[p]) for (p, *_) in device])
-            for k, (p, pos, out, qr, want) in enumerate(device):
-                flt, B = filters[p], boxes[pos]
-                flt.ctx = flt.ctx or ctx
-                got, Z = got_all[k] if rc == 0 else flt._select_device(B.shifted, qr, want)   # refused: the single call, from the same state
-                S_got = dbs[p].sites[[B.indices[g] for g in got]] - xs_m[pos] if got else np.empty((0, d))
-                if got:
-                    flt.Y = np.hstack([flt.Y, S_got.T])
-                    flt.Z = Z
-                    out.extend(got)
-                res[p] = ([B.indices[i] for i in out], flt, B.indices)
-                if rc == 0:
-                    batched.append(p)
-    stats["path"] = "batch" if batched else "loop"
-    stats["batched"] = sorted(batched)
-    final = []
-    for p in range(ns):
-        picked, flt, cand = res[p]
-        if hasattr(flt.Z, "data_ptr"):                       # left on the device: rows are directions, last to first
-            dirs = flt.Z if collect_improving_directions else None
-        else:
-            dirs = [flt.Z[:, j].copy() for j in range(flt.Z.shape[1])][::-1] if collect_improving_directions else None
-        final.append((picked, dirs, cand, flt.Y, flt.Z))
-    return final
-
-
-def _round4_batch_views(items, d, ctx=None):
-    """`rbf_round4_batch_device` with the sites given as anything `_lib.as_ptr` takes with a `shape` (DeviceViews are read in place):
-    `items` = one (cfg, start_sites, cand_sites, delta) per start -> (rc, [(rc_p, positions)] or None, ms)"""
-    ctx = ctx or _lib.default_context()
-    n = len(items)
-    jobs = (_lib.Round4Job * max(n, 1))()
-    keep = []
-    for k, (cfg, C0, Xc, delta) in enumerate(items):
-        kid, a, b = rm._get_kernel_params(delta, cfg)
-        mc = int(Xc.shape[0])
-        acc = np.zeros(max(mc, 1), dtype=np.int32)
-        keep.append((C0, Xc, acc))
-        J = jobs[k]
-        J.n0, J.mc, J.start_sites, J.cand_sites = int(C0.shape[0]), mc, _lib.as_ptr(C0), _lib.as_ptr(Xc) if mc else None
-        J.kernel_id, J.poly_deg, J.a, J.b = kid, cfg.polynomial_degree, a, b
-        J.max_points, J.theta_pivot_cholesky, J.accepted_out = int(cfg.max_model_points), float(cfg.θ_pivot_cholesky), acc.ctypes.data
-    ms = ctypes.c_float(0.0)
-    rc = ctx.lib.mrbf_round4_batch(ctx.h, n, d, jobs, ctypes.byref(ms))
-    if rc != 0:
-        if not ctx.lib.mrbf_dispatch_after(_lib.ENTRY_ROUND4_BATCH, rc):
-            ctx.check(rc)
-        return rc, None, 0.0
-    return 0, [(int(jobs[k].rc), [int(v) for v in keep[k][2][: jobs[k].n_accepted]]) for k in range(n)], float(ms.value)
-
-
-def rbf_round4_resident(dbs, lb2s, ub2s, xs, deltas, indices_found_list, cfgs, ctx=None, stats=None, min_starts=None):
-    """`rbf_round4_many` on resident databases: returns exactly its lists of database indices in acceptance order, by the same
-    decision-table answers and the same rule for when the batch pays.  The candidates of every start come from ONE mrbf_db_box_batch
-    call per d (the box of round 4 without the sites found so far), the start sites of the starts that form a batch from ONE
-    mrbf_db_gather_batch call; mrbf_round4_batch reads both views in place (a box view and a gather view are alive at once).  Every
-    start that `rbf_round4_many` would hand to `_rbf_round4` gets it here too, on the database's host copy."""
-    from . import database
-
-    ns = len(dbs)
-    per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * ns
-    cfgs, deltas = per(cfgs), per(deltas)
-    out = [None] * ns
-    lib = _lib.load() if ns else None
-    single = lambda p: _rbf_round4(dbs[p].sites, lb2s[p], ub2s[p], xs[p], deltas[p], indices_found_list[p], cfgs[p], ctx=ctx)
-    by_d = {}
-    for p in range(ns):
-        by_d.setdefault(dbs[p].d, []).append(p)
-    batched, fallback = [], []
-    for d, all_members in by_d.items():
-        boxes = database.box_many([dbs[p] for p in all_members], [lb2s[p] for p in all_members], [ub2s[p] for p in all_members],
-                                  [xs[p] for p in all_members], [list(indices_found_list[p]) for p in all_members], p=np.inf,
-                                  zero_first_pick=False, ctx=ctx)
-        members, prepared = [], {}
-        for pos, p in enumerate(all_members):
-            cfg, found, B = cfgs[p], list(indices_found_list[p]), boxes[pos]
-            max_points = (d + 1) * (d + 2) // 2 if cfg.max_model_points <= 0 else cfg.max_model_points
-            if cfg.use_max_points:
-                out[p] = single(p)
-            elif not (len(found) < max_points and B.mc):
-                out[p] = []
-            elif lib.mrbf_dispatch_round4(len(found), d, cfg.polynomial_degree, B.mc) != _lib.DISPATCH_DEVICE:
-                out[p] = single(p)
-            else:
-                prepared[p] = (cfg, found, B, deltas[p])
-                members.append(p)
-        if not members:
-            continue
-        pays = len(members) >= min_starts if min_starts is not None else round4_batch_pays(len(members), max(prepared[p][2].mc for p in members))
-        if not pays or lib.mrbf_dispatch_round4_batch(len(members), d) != _lib.DISPATCH_DEVICE:
-            for p in members:
-                out[p] = single(p)
-            continue
-        starts = database.gather_many([dbs[p] for p in members], [prepared[p][1] for p in members], ctx=ctx)
-        for p, g in zip(members, starts):
-            if g.rc != 0:
-                raise _lib.MrbfError(g.rc, "rbf_round4_resident: start %d has a found index outside its database" % p)
-        rc, res, _ = _round4_batch_views([(prepared[p][0], g.sites, prepared[p][2].sites, prepared[p][3]) for p, g in zip(members, starts)], d, ctx=ctx)
-        for pos, p in enumerate(members):
-            if rc != 0:                                   # refused: the single call per start
-                out[p] = single(p)
-                continue
-            rc_p, accepted = res[pos]
-            if rc_p == 0:
-                out[p] = [prepared[p][2].indices[a] for a in accepted]
-                batched.append(p)
-            elif lib.mrbf_dispatch_after(_lib.ENTRY_ROUND4_BATCH, rc_p):
-                out[p] = single(p)
-                fallback.append(p)
-            else:
-                (ctx or _lib.default_context()).check(rc_p)
-    if stats is not None:
-        stats["path"] = "batch" if batched else "loop"
-        stats["batched"] = sorted(batched)
-        stats["fallback"] = sorted(fallback)
-    return out
-
-
 # ---- round 3 (RbfModel.jl:269-307), the improvement step (:699-732) and phase I as one driver (:518-655) -------------------------------
 
 def _rbf_round3(sites, lb_1, ub_1, x, piv_val_1, improving_directions, max_new, n_missing, ensure_fully_linear, force_rebuild):
@@ -901,10 +769,6 @@ class Round3Result:
 
     def __init__(self, new_points, fully_linear, remaining, rebuilt, indices=None):
         self.new_points, self.fully_linear, self.remaining_directions, self.rebuilt, self.indices = new_points, fully_linear, remaining, rebuilt, indices
-
-
-def _per(v, ns):
-    return list(v) if isinstance(v, (list, tuple)) else [v] * ns
 
 
 def _direction_rows(dirs, d, reverse):
@@ -951,28 +815,25 @@ def _improve_host(lb1, ub1, x, piv, rows):
     return Round3Result(pts, ok and len(rows) == 1, list(rows[1:]), False)
 
 
-def rbf_round3_resident(dbs, lb1s, ub1s, xs, piv_vals, directions, max_news, n_missings, ensure_fully_linear=False, force_rebuild=False,
-                        reversed_order=None, improve=False, ctx=None, stats=None):
-    """`rbf_round3_many` on resident databases, the new points appended to them as unevaluated rows: ONE mrbf_db_round3_batch per d
-    (rebuild included).  `directions[p]`: a list of vectors, a (n_dirs, d) NumPy array or device tensor (rows are directions: the
+def rbf_round3_append(dbs, lb1s, ub1s, xs, piv_vals, directions, max_news, n_missings, ensure_fully_linear=False, force_rebuild=False,
+                      reversed_order=None, improve=False, ctx=None, stats=None):
+    """`rbf_round3_many` with the new points appended to the databases `dbs` (`database.as_databases`) as unevaluated rows; on
+    resident databases ONE mrbf_db_round3_batch per d (rebuild included).  `directions[p]`: a list of vectors, a (n_dirs, d) NumPy array or device tensor (rows are directions: the
     memory of a column-major d x n_dirs Z, read in place), or None for the coordinate axes; `reversed_order[p]`: take the rows from the
-    last to the first.  `improve`: the improvement step (prepare_improve_model) instead.  Where the decision table says host, the
-    host loop runs and its points are appended through `database.append_many`.  -> list of Round3Result with `indices`."""
+    last to the first.  `improve`: the improvement step (prepare_improve_model) instead.  On host databases, and where the decision
+    table says host, the host loop runs and its points are appended through `database.append_many`.  -> list of Round3Result with
+    `indices`."""
     from . import database
 
     ns = len(dbs)
+    dbs, resident = database.as_databases(dbs, xs)
     stats = stats if stats is not None else {}
     piv_vals, max_news, n_missings = _per(piv_vals, ns), _per(max_news, ns), _per(n_missings, ns)
     efl, force, rev = _per(ensure_fully_linear, ns), _per(force_rebuild, ns), _per(False if reversed_order is None else reversed_order, ns)
     out = [None] * ns
     lib = _lib.load() if ns else None
-    by_d = {}
-    for p in range(ns):
-        by_d.setdefault(dbs[p].d, []).append(p)
     stats["path"] = "device"
-    for d, members in by_d.items():
-        c = ctx or dbs[members[0]].ctx
-
+    for d, members in _by_d(dbs).items():
         def host(members=members, d=d):
             stats["path"] = "host"
             host_rows = lambda p: _direction_rows(directions[p] if not hasattr(directions[p], "data_ptr") else directions[p].detach().cpu().numpy(),
@@ -983,14 +844,15 @@ def rbf_round3_resident(dbs, lb1s, ub1s, xs, piv_vals, directions, max_news, n_m
                 res = rbf_round3_many([lb1s[p] for p in members], [ub1s[p] for p in members], [xs[p] for p in members],
                                       [piv_vals[p] for p in members], [host_rows(p) for p in members], [max_news[p] for p in members],
                                       [n_missings[p] for p in members], [efl[p] for p in members], [force[p] for p in members])
-            firsts = database.append_many([dbs[p] for p in members], [r.new_points for r in res], ctx=c)
+            firsts = database.append_many([dbs[p] for p in members], [r.new_points for r in res], ctx=ctx)
             for p, r, f in zip(members, res, firsts):
                 r.indices = list(range(f, f + r.new_points.shape[0]))
                 out[p] = r
 
-        if lib.mrbf_dispatch_db_batch(len(members), d) != _lib.DISPATCH_DEVICE:
+        if not resident or lib.mrbf_dispatch_db_batch(len(members), d) != _lib.DISPATCH_DEVICE:
             host()
             continue
+        c = ctx or dbs[members[0]].ctx
         jobs = (_lib.Round3Job * len(members))()
         keep = []
         for q, p in enumerate(members):
@@ -1033,7 +895,7 @@ def rbf_round3_resident(dbs, lb1s, ub1s, xs, piv_vals, directions, max_news, n_m
                 continue
             n_new, first = int(J.n_new), int(J.first_index)
             pts = buf[:n_new].copy()
-            database._adopt_rows(dbs[p], pts)
+            dbs[p]._adopt_rows(pts)
             rebuilt = J.status == _lib.R3_REBUILT
             if rebuilt:
                 rem = _axes(d)[int(J.n_dirs_used):]
@@ -1053,10 +915,10 @@ def rbf_round3_resident(dbs, lb1s, ub1s, xs, piv_vals, directions, max_news, n_m
     return out
 
 
-def prepare_improve_models_resident(dbs, metas, cfgs, xs, deltas, lb, ub, ctx=None, stats=None):
+def prepare_improve_models(dbs, metas, cfgs, xs, deltas, lb, ub, ctx=None, stats=None):
     """prepare_improve_model (RbfModel.jl:699-732) for a batch of starts: every meta that is not fully linear and has improving
-    directions takes one improvement step, all of them in ONE mrbf_db_round3_batch (MRBF_R3_IMPROVE) per d.  The metas (dicts as
-    `prepare_update_models_*` return them) are updated in place and returned."""
+    directions takes one improvement step, all of them through one `rbf_round3_append` (resident databases: ONE mrbf_db_round3_batch,
+    MRBF_R3_IMPROVE, per d).  The metas (dicts as `prepare_update_models` returns them) are updated in place and returned."""
     from .descent import _local_bounds
 
     ns = len(dbs)
@@ -1069,8 +931,8 @@ def prepare_improve_models_resident(dbs, metas, cfgs, xs, deltas, lb, ub, ctx=No
         d1 = cfgs[p].θ_enlarge_1 * deltas[p]
         l1, u1 = _local_bounds(xs[p], d1, lb, ub)
         lb1s.append(l1), ub1s.append(u1), pivs.append(d1 * cfgs[p].θ_pivot)
-    res = rbf_round3_resident([dbs[p] for p in act], lb1s, ub1s, [xs[p] for p in act], pivs, [list(metas[p]["improving_directions"]) for p in act],
-                              1, 1, improve=True, ctx=ctx, stats=stats)
+    res = rbf_round3_append([dbs[p] for p in act], lb1s, ub1s, [xs[p] for p in act], pivs, [list(metas[p]["improving_directions"]) for p in act],
+                            1, 1, improve=True, ctx=ctx, stats=stats)
     for p, r in zip(act, res):
         metas[p]["improving_directions"] = r.remaining_directions
         metas[p]["round1_indices"] = list(metas[p]["round1_indices"]) + list(r.indices)
@@ -1085,14 +947,18 @@ def _num_unevaluated(values):
     return int(np.count_nonzero(np.isnan(V).any(axis=1))) if V.size else 0
 
 
-def _prepare_update_models(cfgs, dbs, xs, x_indices, deltas, delta_max, lb, ub, ensure_fully_linear, max_evals, num_evals, force_rebuild, find,
-                           round3, round4):
-    """prepare_update_model (RbfModel.jl:518-655) for a list of starts, phase by phase; `find`, `round3` and `round4` are the list
-    forms of _find_suitable_points, _rbf_round3 (rebuild included, points appended) and _rbf_round4 on the databases `dbs`.  Round 1 is
-    told which starts skip round 2 whatever it finds (`skips_round2`): the resident form leaves their Z on the device for round 3."""
+def prepare_update_models(cfgs, dbs, xs, x_indices, deltas, delta_max, lb, ub, ensure_fully_linear=False, max_evals=2 ** 63 - 1,
+                          num_evals=0, force_rebuild=False, ctx=None):
+    """prepare_update_model (RbfModel.jl:518-655) for a list of starts on their databases `dbs` (`database.as_databases`: resident or
+    host), phase by phase through `find_suitable_points_many`, `rbf_round3_append` (rebuild included, the new sites appended as
+    unevaluated rows) and `rbf_round4_many`.  Round 1 is told which starts skip round 2 whatever it finds: on resident databases
+    their Z stays on the device for round 3.  -> one meta (dict) per start: center_index, round1..4_indices, fully_linear,
+    improving_directions, rebuilt.  One RBF config per start (_exploit_other_rbf_metas! is not mirrored)."""
+    from . import database
     from .descent import _isapprox, _local_bounds
 
     ns = len(dbs)
+    dbs, _ = database.as_databases(dbs, xs)
     cfgs, deltas, efl, force, num_evals = _per(cfgs, ns), _per(deltas, ns), _per(ensure_fully_linear, ns), _per(force_rebuild, ns), _per(num_evals, ns)
     xs = [np.asarray(x, dtype=np.float64) for x in xs]
     metas = [dict(center_index=int(x_indices[p]), round1_indices=[], round2_indices=[], round3_indices=[], round4_indices=[],
@@ -1115,8 +981,9 @@ def _prepare_update_models(cfgs, dbs, xs, x_indices, deltas, delta_max, lb, ub, 
     skips2 = [bool(force[p] or not cfgs[p].optimized_sampling or efl[p] or
                    (_isapprox(deltas[p], delta_max) and cfgs[p].θ_enlarge_1 == cfgs[p].θ_enlarge_2)) for p in range(ns)]
     for piv, which in groups.items():
-        for p, (picked, drs, cand, Y, Z) in zip(which, find(sub(dbs, which), sub(lb1, which), sub(ub1, which), sub(xs, which), sub(x_indices, which), piv,
-                                                            skips_round2=sub(skips2, which))):
+        res = find_suitable_points_many(sub(dbs, which), sub(lb1, which), sub(ub1, which), sub(xs, which), sub(x_indices, which), piv, ctx=ctx,
+                                        keep_Z_on_device=sub(skips2, which))
+        for p, (picked, drs, cand, Y, Z) in zip(which, res):
             metas[p]["round1_indices"], dirs[p], cand1[p], Y1[p], Z1[p] = list(picked), drs, cand, Y, Z
     # ---- round 2 (:586-603)
     n_missing = [xs[p].size - len(metas[p]["round1_indices"]) for p in range(ns)]
@@ -1129,9 +996,9 @@ def _prepare_update_models(cfgs, dbs, xs, x_indices, deltas, delta_max, lb, ub, 
         else:
             second.setdefault(float(piv1[p]), []).append(p)
     for piv, which in second.items():
-        res = find(sub(dbs, which), sub(lb2, which), sub(ub2, which), sub(xs, which), sub(x_indices, which), piv,
-                   already_inspected_indices=[cand1[p] for p in which], Ys=[Y1[p] for p in which], Zs=[Z1[p] for p in which],
-                   n_missing=[n_missing[p] for p in which], collect_improving_directions=False)
+        res = find_suitable_points_many(sub(dbs, which), sub(lb2, which), sub(ub2, which), sub(xs, which), sub(x_indices, which), piv,
+                                        already_inspected_indices=[cand1[p] for p in which], Ys=[Y1[p] for p in which], Zs=[Z1[p] for p in which],
+                                        n_missing=[n_missing[p] for p in which], collect_improving_directions=False, ctx=ctx)
         for p, r in zip(which, res):
             metas[p]["round2_indices"] = list(r[0])
     # ---- round 3 (:609-639), the rebuild inside the call
@@ -1144,9 +1011,9 @@ def _prepare_update_models(cfgs, dbs, xs, x_indices, deltas, delta_max, lb, ub, 
             third.append(p)
     if third:
         max_new = [max(0, min(max_evals, cfgs[p].max_evals) - 1 - num_evals[p] - _num_unevaluated(dbs[p].values)) for p in third]
-        res = round3(sub(dbs, third), sub(lb1, third), sub(ub1, third), sub(xs, third), sub(piv1, third), [dirs[p] for p in third], max_new,
-                     [n_missing[p] for p in third], [efl[p] for p in third], [force[p] for p in third],
-                     [hasattr(dirs[p], "data_ptr") for p in third])
+        res = rbf_round3_append(sub(dbs, third), sub(lb1, third), sub(ub1, third), sub(xs, third), sub(piv1, third), [dirs[p] for p in third], max_new,
+                                [n_missing[p] for p in third], [efl[p] for p in third], [force[p] for p in third],
+                                reversed_order=[hasattr(dirs[p], "data_ptr") for p in third], ctx=ctx)
         for p, r in zip(third, res):
             m = metas[p]
             if r.rebuilt:   # the recursive call with force_rebuild: rounds 1 and 2 are empty, round 2 is skipped (fully linear so far)
@@ -1159,46 +1026,7 @@ def _prepare_update_models(cfgs, dbs, xs, x_indices, deltas, delta_max, lb, ub, 
     fourth = [p for p in range(ns) if cfgs[p].optimized_sampling]
     if fourth:
         found = [[metas[p]["center_index"], *metas[p]["round1_indices"], *metas[p]["round2_indices"], *metas[p]["round3_indices"]] for p in fourth]
-        for p, r4 in zip(fourth, round4(sub(dbs, fourth), sub(lb2, fourth), sub(ub2, fourth), sub(xs, fourth), sub(deltas, fourth), found, sub(cfgs, fourth))):
+        for p, r4 in zip(fourth, rbf_round4_many(sub(dbs, fourth), sub(lb2, fourth), sub(ub2, fourth), sub(xs, fourth), sub(deltas, fourth), found,
+                                                 sub(cfgs, fourth), ctx=ctx)):
             metas[p]["round4_indices"] = list(r4)
     return metas
-
-
-def prepare_update_models_many(cfgs, dbs, xs, x_indices, deltas, delta_max, lb, ub, ensure_fully_linear=False, max_evals=2 ** 63 - 1,
-                               num_evals=0, force_rebuild=False, ctx=None):
-    """prepare_update_model (RbfModel.jl:518-655) for a list of starts on host databases (`database.HostDatabase`: `sites`, `values`,
-    `append`): the host-array twin of `prepare_update_models_resident`, built from `find_suitable_points_many`, `rbf_round3_many` and
-    `rbf_round4_many`.  -> one meta (dict) per start: center_index, round1..4_indices, fully_linear, improving_directions, rebuilt.
-    One RBF config per start (_exploit_other_rbf_metas! is not mirrored)."""
-    def find(dbs_, *a, skips_round2=None, **kw):
-        return find_suitable_points_many([db.sites for db in dbs_], *a, ctx=ctx, **kw)
-
-    def round3(dbs_, lb1s, ub1s, xs_, pivs, dirs, max_news, n_missings, efl, force, rev):
-        res = rbf_round3_many(lb1s, ub1s, xs_, pivs, dirs, max_news, n_missings, efl, force, reversed_order=rev)
-        for db, r in zip(dbs_, res):
-            first = db.append(r.new_points)
-            r.indices = list(range(first, first + r.new_points.shape[0]))
-        return res
-
-    def round4(dbs_, lb2s, ub2s, xs_, deltas_, found, cfgs_):
-        return rbf_round4_many([db.sites for db in dbs_], lb2s, ub2s, xs_, deltas_, found, cfgs_, ctx=ctx)
-
-    return _prepare_update_models(cfgs, dbs, xs, x_indices, deltas, delta_max, lb, ub, ensure_fully_linear, max_evals, num_evals, force_rebuild,
-                                  find, round3, round4)
-
-
-def prepare_update_models_resident(cfgs, dbs, xs, x_indices, deltas, delta_max, lb, ub, ensure_fully_linear=False, max_evals=2 ** 63 - 1,
-                                   num_evals=0, force_rebuild=False, ctx=None):
-    """`prepare_update_models_many` on resident databases: `find_suitable_points_resident`, `rbf_round3_resident` (one
-    mrbf_db_round3_batch per d, the new sites written straight into the databases) and `rbf_round4_resident`.  Returns the same metas."""
-    def find(dbs_, *a, skips_round2=None, **kw):
-        return find_suitable_points_resident(dbs_, *a, ctx=ctx, keep_Z_on_device=skips_round2, **kw)
-
-    def round3(dbs_, lb1s, ub1s, xs_, pivs, dirs, max_news, n_missings, efl, force, rev):
-        return rbf_round3_resident(dbs_, lb1s, ub1s, xs_, pivs, dirs, max_news, n_missings, efl, force, reversed_order=rev, ctx=ctx)
-
-    def round4(dbs_, lb2s, ub2s, xs_, deltas_, found, cfgs_):
-        return rbf_round4_resident(dbs_, lb2s, ub2s, xs_, deltas_, found, cfgs_, ctx=ctx)
-
-    return _prepare_update_models(cfgs, dbs, xs, x_indices, deltas, delta_max, lb, ub, ensure_fully_linear, max_evals, num_evals, force_rebuild,
-                                  find, round3, round4)

@@ -367,7 +367,7 @@ def test_views_feed_the_affine_filter_unchanged(ctx, three_starts):
             qr.append(first)
             items_view.append((B_.shifted, qr, d - 1, 0.25))
             items_host.append((shifted, qr, d - 1, 0.25))
-        rc_v, res_v, _ = sampling._affine_select_batch_views(items_view, d, ctx=ctx)
+        rc_v, res_v, _ = sampling.affine_select_batch_device(items_view, d, ctx=ctx)
         rc_h, res_h, _ = sampling.affine_select_batch_device(items_host, d, ctx=ctx)
         assert rc_v == 0 and rc_h == 0
         for (got_v, Z_v), (got_h, Z_h) in zip(res_v, res_h):
@@ -388,7 +388,7 @@ def test_views_feed_round4_and_the_fit_unchanged(ctx, three_starts):
         starts = database.gather_many([dbs[p] for p in members], [found] * ns, ctx=ctx)
         for B_, g, p in zip(boxes, starts, members):
             assert g.rc == 0 and B_.indices == sampling.results_in_box_indices(Ss[p], lb, ub, found) and B_.mc > 10
-        rc_v, res_v, _ = sampling._round4_batch_views([(cfg, g.sites, B_.sites, 1.0) for g, B_ in zip(starts, boxes)], d, ctx=ctx)
+        rc_v, res_v, _ = sampling.rbf_round4_batch_device([(cfg, g.sites, B_.sites, 1.0) for g, B_ in zip(starts, boxes)], d, ctx=ctx)
         rc_h, res_h, _ = sampling.rbf_round4_batch_device([(cfg, Ss[p][found], Ss[p][B_.indices], 1.0) for p, B_ in zip(members, boxes)], d, ctx=ctx)
         assert rc_v == 0 and rc_h == 0 and res_v == res_h
         assert all(rc_p == 0 and len(acc) > 5 for rc_p, acc in res_v)
@@ -434,7 +434,7 @@ def test_three_iterations_resident_against_host(ctx):
         # ---- round 1
         s1, s2 = {}, {}
         r1h = sampling.find_suitable_points_many(host, lb1, ub1, xs, x_idx, piv1, stats=s1, ctx=ctx)
-        r1r = sampling.find_suitable_points_resident(dbs, lb1, ub1, xs, x_idx, piv1, stats=s2, ctx=ctx)
+        r1r = sampling.find_suitable_points_many(dbs, lb1, ub1, xs, x_idx, piv1, stats=s2, ctx=ctx)
         assert s1 == s2, (s1, s2)
         same_rounds(r1h, r1r, ("round 1", it))
         print("iteration %d round 1: %r, picks %r" % (it, s1, [len(r[0]) for r in r1h]))
@@ -452,7 +452,7 @@ def test_three_iterations_resident_against_host(ctx):
             sel = lambda seq: [seq[p] for p in todo]
             r2h = sampling.find_suitable_points_many(sel(host), sel(lb2), sel(ub2), sel(xs), sel(x_idx), piv2, sel(inspected), sel(Ys), sel(Zs),
                                                      sel(missing), stats=s1, ctx=ctx)
-            r2r = sampling.find_suitable_points_resident(sel(dbs), sel(lb2), sel(ub2), sel(xs), sel(x_idx), piv2, sel(inspected), sel(Ys),
+            r2r = sampling.find_suitable_points_many(sel(dbs), sel(lb2), sel(ub2), sel(xs), sel(x_idx), piv2, sel(inspected), sel(Ys),
                                                          sel(Zs), sel(missing), stats=s2, ctx=ctx)
             assert s1 == s2, (s1, s2)
             same_rounds(r2h, r2r, ("round 2", it))
@@ -482,7 +482,7 @@ def test_three_iterations_resident_against_host(ctx):
         # ---- round 4
         s1, s2 = {}, {}
         a4h = sampling.rbf_round4_many(host, lb4, ub4, xs, 1.0, found, cfg, ctx=ctx, stats=s1, min_starts=1)
-        a4r = sampling.rbf_round4_resident(dbs, lb4, ub4, xs, 1.0, found, cfg, ctx=ctx, stats=s2, min_starts=1)
+        a4r = sampling.rbf_round4_many(dbs, lb4, ub4, xs, 1.0, found, cfg, ctx=ctx, stats=s2, min_starts=1)
         assert a4h == a4r and s1 == s2 and s1["path"] == "batch" and s1["fallback"] == [], (it, s1, s2)
         # ---- fit
         train = [found[p] + a4h[p] for p in range(ns)]

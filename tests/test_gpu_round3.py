@@ -381,8 +381,8 @@ def test_append_many_and_set_values_many_match_the_single_calls(ctx):
 
 @pytest.mark.parametrize("d", (3, 65))
 def test_three_iterations_of_phase_one_and_fit(ctx, d):
-    """five starts, start 2 with a fixed coordinate (it rebuilds): prepare_update_models_resident + update_models_resident against
-    prepare_update_models_many + update_models_many: equal metas, equal database contents, equal weights"""
+    """five starts, start 2 with a fixed coordinate (it rebuilds): prepare_update_models + update_models_resident on resident databases against
+    prepare_update_models + update_models_many on host databases: equal metas, equal database contents, equal weights"""
     ns, k = 5, 2
     cfg = RbfConfig(kernel="cubic")
     rng = np.random.default_rng(d)
@@ -403,7 +403,7 @@ def test_three_iterations_of_phase_one_and_fit(ctx, d):
     for it in range(3):
         efl = it != 1
         metas = []
-        for dbs, prep in ((host, sampling.prepare_update_models_many), (dev, sampling.prepare_update_models_resident)):
+        for dbs, prep in ((host, sampling.prepare_update_models), (dev, sampling.prepare_update_models)):
             ms = [None] * ns
             for group, (l, u) in (([0, 1, 3, 4], (lb, ub)), ([2], (fixed_lb, fixed_ub))):      # the bounds are one per call
                 res = prep(cfg, [dbs[p] for p in group], [dbs[p].sites[x_idx[p]].copy() for p in group], [x_idx[p] for p in group], delta,
@@ -443,6 +443,51 @@ def test_three_iterations_of_phase_one_and_fit(ctx, d):
         delta = 0.25 if it == 0 else 0.125
 
 
+def test_one_round_on_resident_and_on_host_databases(ctx):
+    """d = 8, three starts of 40 sites: find, round 3 with its sites appended, round 4 -- the three drivers called directly, once on
+    DeviceDatabases and once on HostDatabases holding the same rows: equal tuples, Round3Results, accepted lists, routing stats and
+    database contents.  Every round has work: 5 + p unit steps inside the inner box, the other sites spread over [0, 1]^8."""
+    d, ns, n, k = 8, 3, 40, 2
+    rng = np.random.default_rng(8)
+    cfg = RbfConfig(kernel="cubic")
+    f = lambda X: np.stack([np.sum(X * X, axis=1), np.sum(np.cos(X), axis=1)], axis=1)
+    host = [database.HostDatabase(d, k) for _ in range(ns)]
+    dev = [database.DeviceDatabase(d, k, ctx=ctx, capacity=4) for _ in range(ns)]
+    for p in range(ns):
+        X = rng.integers(0, 65, (n, d)) / 64.0
+        X[: 6 + p] = 0.5
+        for i in range(5 + p):
+            X[1 + i, i] += (8 + i) / 64.0
+        for db in (host[p], dev[p]):
+            db.append(X, f(X))
+    xs, x_idx, piv = [np.full(d, 0.5) for _ in range(ns)], [0] * ns, 1.0 / 16
+    lb1, ub1 = [x - 0.25 for x in xs], [x + 0.25 for x in xs]
+    lb2, ub2 = [np.zeros(d)] * ns, [np.ones(d)] * ns
+    runs = []
+    for dbs in (dev, host):
+        s1, s3, s4 = {}, {}, {}
+        r1 = sampling.find_suitable_points_many(dbs, lb1, ub1, xs, x_idx, piv, stats=s1, ctx=ctx)
+        r3 = sampling.rbf_round3_append(dbs, lb1, ub1, xs, piv, [r[1] for r in r1], 10 ** 9, [d - len(r[0]) for r in r1], ctx=ctx, stats=s3)
+        found = [[0, *r1[p][0], *r3[p].indices] for p in range(ns)]
+        r4 = sampling.rbf_round4_many(dbs, lb2, ub2, xs, 0.125, found, cfg, ctx=ctx, stats=s4, min_starts=1)
+        runs.append((r1, r3, found, r4, s1, s3["path"], s4))
+    (r1d, r3d, fd, r4d, s1d, p3d, s4d), (r1h, r3h, fh, r4h, s1h, p3h, s4h) = runs
+    assert s1d == s1h and s4d == s4h and (p3d, p3h) == ("device", "host") and fd == fh and r4d == r4h
+    for p in range(ns):
+        a, b = r1d[p], r1h[p]
+        assert a[0] == b[0] and a[2] == b[2] and len(a[0]) >= 5 + p and same(a[3], b[3]) and same(a[4], b[4]), p
+        assert len(a[1]) == len(b[1]) and all(same(u, v) for u, v in zip(a[1], b[1])), p
+        a, b = r3d[p], r3h[p]
+        assert same(a.new_points, b.new_points) and a.indices == b.indices and len(a.indices) == d - len(r1h[p][0]) > 0, p
+        assert (a.fully_linear, a.rebuilt) == (b.fully_linear, b.rebuilt) and len(a.remaining_directions) == len(b.remaining_directions), p
+        assert all(same(u, v) for u, v in zip(a.remaining_directions, b.remaining_directions)) and len(r4h[p]) > 0, p
+        S, V = dev[p].read()
+        assert len(dev[p]) == len(host[p]) == dev[p].dims()[0] == n + len(a.indices)
+        assert same(S, host[p].sites) and same(V, host[p].values) and same(dev[p].sites, S) and same(dev[p].values, V), p
+    for db in dev:
+        db.free()
+
+
 def test_filter_Z_left_on_the_device_feeds_round3_in_place(ctx):
     """d = 65, five starts whose databases lie in the subspace x_60 .. x_64 = 1/2 (80 sites around the centre): the batched pick loop
     serves every start and leaves at least five columns in Z.  With `keep_Z_on_device` the final Z is a device tensor holding the bits
@@ -461,9 +506,9 @@ def test_filter_Z_left_on_the_device_feeds_round3_in_place(ctx):
             db.append(X, np.sum(X, axis=1, keepdims=True))
     xs, x_idx = [np.full(d, 0.5) for _ in range(ns)], [0] * ns
     lb1, ub1 = [x - 0.25 for x in xs], [x + 0.25 for x in xs]
-    plain = sampling.find_suitable_points_resident(dev, lb1, ub1, xs, x_idx, 1.0 / 16, ctx=ctx)
+    plain = sampling.find_suitable_points_many(dev, lb1, ub1, xs, x_idx, 1.0 / 16, ctx=ctx)
     st = {}
-    kept = sampling.find_suitable_points_resident(dev, lb1, ub1, xs, x_idx, 1.0 / 16, ctx=ctx, keep_Z_on_device=[True, True, False, True, True], stats=st)
+    kept = sampling.find_suitable_points_many(dev, lb1, ub1, xs, x_idx, 1.0 / 16, ctx=ctx, keep_Z_on_device=[True, True, False, True, True], stats=st)
     assert st["batched"] == list(range(ns))
     for p in range(ns):
         assert plain[p][0] == kept[p][0] and plain[p][2] == kept[p][2] and same(plain[p][3], kept[p][3])
@@ -477,8 +522,8 @@ def test_filter_Z_left_on_the_device_feeds_round3_in_place(ctx):
         assert np.array_equal(bits(T.cpu().numpy()), bits(Z.T))                      # rows of the tensor = columns of Z
         rows = [r for r in T.cpu().numpy()][::-1]
         assert all(np.array_equal(bits(a), bits(b)) for a, b in zip(rows, plain[p][1]))  # last to first = the improving directions
-    mh = sampling.prepare_update_models_many(cfg, host, xs, x_idx, 0.125, 0.5, np.zeros(d), np.ones(d), ensure_fully_linear=True, ctx=ctx)
-    md = sampling.prepare_update_models_resident(cfg, dev, xs, x_idx, 0.125, 0.5, np.zeros(d), np.ones(d), ensure_fully_linear=True, ctx=ctx)
+    mh = sampling.prepare_update_models(cfg, host, xs, x_idx, 0.125, 0.5, np.zeros(d), np.ones(d), ensure_fully_linear=True, ctx=ctx)
+    md = sampling.prepare_update_models(cfg, dev, xs, x_idx, 0.125, 0.5, np.zeros(d), np.ones(d), ensure_fully_linear=True, ctx=ctx)
     for p in range(ns):
         for key in ("center_index", "round1_indices", "round2_indices", "round3_indices", "round4_indices", "fully_linear", "rebuilt"):
             assert mh[p][key] == md[p][key], (p, key, mh[p][key], md[p][key])
@@ -503,7 +548,7 @@ def test_prepare_improve_models_resident(ctx):
     dbs = [database.DeviceDatabase(d, k, ctx=ctx, capacity=4) for _ in range(5)]
     for db in dbs:
         db.append(x[None, :], np.zeros((1, k)))
-    sampling.prepare_improve_models_resident(dbs, metas, cfg, [x] * 5, 0.125, lb, ub, ctx=ctx)
+    sampling.prepare_improve_models(dbs, metas, cfg, [x] * 5, 0.125, lb, ub, ctx=ctx)
     # Delta_1 = .25, box [.25, .75]^2 x {.5}, pivot 1/16: e0 and e1 reach .25 (the tie picks +), e2 reaches 0
     want = [([7, 1], [[0.75, 0.5, 0.5]], [E3[1]], False), ([7, 1], [[0.5, 0.75, 0.5]], [], True), ([7], [], [E3[0]], False), ([7], [], [], False),
             ([7], [], [E3[0]], True)]

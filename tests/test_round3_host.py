@@ -1,5 +1,5 @@
 """The host restatement of round 3 (morbit.jl_amd/sampling.py: _rbf_round3, RbfModel.jl:269-307) against cases derived by hand from the
-reference's text, and the phase-I driver on host databases (prepare_update_models_many, RbfModel.jl:518-655) on a scripted run whose
+reference's text, and the phase-I driver on host databases (prepare_update_models, RbfModel.jl:518-655) on a scripted run whose
 metas are written out literally.  No GPU: the small filters stay on the host and round 4 finds the model full (max_model_points = d + 1)."""
 import numpy as np
 import pytest
@@ -99,7 +99,7 @@ def test_prepare_update_models_many_scripted_run():
     lb, ub, delta_max = np.array([0, 0, .5]), np.array([1, 1, .5]), 0.5
     db = database.HostDatabase(3, 1)
     db.append(np.array([[.5, .5, .5]]), np.array([[0.0]]))
-    run = lambda x_index, delta, efl: sampling.prepare_update_models_many(cfg, [db], [db.sites[x_index].copy()], [x_index], delta, delta_max,
+    run = lambda x_index, delta, efl: sampling.prepare_update_models(cfg, [db], [db.sites[x_index].copy()], [x_index], delta, delta_max,
                                                                            lb, ub, ensure_fully_linear=efl)[0]
     strip = lambda m: {k: (v if k != "improving_directions" else [np.asarray(u).tolist() for u in v]) for k, v in m.items()}
 

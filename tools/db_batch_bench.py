@@ -1,8 +1,7 @@
 """One model-update round of a many-start run at the C4 shape (d = 128, 64 starts, n_db = 1400, boxes holding most of the database,
-cubic kernel with a degree-1 tail, k = 2, models of 257 sites): filter round 1, then round 4, then the fit -- through the host-array
-drivers (find_suitable_points_many, rbf_round4_many, update_models_many on NumPy arrays: the code as it was before the resident
-database) and through the resident twins (find_suitable_points_resident, rbf_round4_resident, update_models_resident), alternating,
-in one process.
+cubic kernel with a degree-1 tail, k = 2, models of 257 sites): filter round 1, then round 4, then the fit -- through the drivers
+(find_suitable_points_many, rbf_round4_many) on NumPy arrays with update_models_many (every site uploaded per call: the code as it
+was before the resident database) and on resident databases with update_models_resident, alternating, in one process.
 
     python tools/db_batch_bench.py [--reps 7] [--starts 64] [--n-db 1400] [--out profiles/db_batch_bench.jsonl]
 
@@ -70,10 +69,10 @@ def main():
 
     def round_resident(t):
         t0 = time.perf_counter()
-        r1 = sampling.find_suitable_points_resident(dbs, lb, ub, xs, x_idx, piv, ctx=ctx)
+        r1 = sampling.find_suitable_points_many(dbs, lb, ub, xs, x_idx, piv, ctx=ctx)
         t1 = time.perf_counter()
         found = [[x_idx[p]] + r1[p][0] for p in range(ns)]
-        acc = sampling.rbf_round4_resident(dbs, lb, ub, xs, 1.0, found, cfg, ctx=ctx)
+        acc = sampling.rbf_round4_many(dbs, lb, ub, xs, 1.0, found, cfg, ctx=ctx)
         t2 = time.perf_counter()
         train = [found[p] + acc[p] for p in range(ns)]
         mods = rm.update_models_resident(cfg, dbs, train, 1.0, ctx=ctx)
@@ -124,13 +123,13 @@ def main():
         items_v.append((B.shifted, qr, d - 1, piv))
         items_h.append((np.asarray(B.shifted), qr, d - 1, piv))
     calls = {"affine_host": best(lambda: sampling.affine_select_batch_device(items_h, d, ctx=ctx)[0]),
-             "affine_views": best(lambda: sampling._affine_select_batch_views(items_v, d, ctx=ctx)[0])}
+             "affine_views": best(lambda: sampling.affine_select_batch_device(items_v, d, ctx=ctx)[0])}
     boxes4 = database.box_many(dbs, lb, ub, xs, found, zero_first_pick=False, ctx=ctx)
     starts = database.gather_many(dbs, found, ctx=ctx)
     r4_v = [(cfg, g.sites, B.sites, 1.0) for g, B in zip(starts, boxes4)]
     r4_h = [(cfg, np.asarray(g.sites), np.asarray(B.sites), 1.0) for g, B in zip(starts, boxes4)]
     calls["round4_host"] = best(lambda: sampling.rbf_round4_batch_device(r4_h, d, ctx=ctx)[0])
-    calls["round4_views"] = best(lambda: sampling._round4_batch_views(r4_v, d, ctx=ctx)[0])
+    calls["round4_views"] = best(lambda: sampling.rbf_round4_batch_device(r4_v, d, ctx=ctx)[0])
     sets = database.gather_many(dbs, train, ctx=ctx)
     fit_h = ([np.asarray(g.sites) for g in sets], [np.asarray(g.values) for g in sets])
     calls["fit_host"] = best(lambda: rm.update_models_many(cfg, fit_h[0], fit_h[1], 1.0, ctx=ctx))

@@ -3,7 +3,7 @@ eval_missing! of those sites, and the append of one trial point per start -- thr
 mrbf_db_set_values_batch, mrbf_db_append_batch: three calls, three synchronisations) and the way a caller did it before them (the host
 mirror of round 3 on the filter's Z, then mrbf_db_append, mrbf_db_set_values and mrbf_db_append once per start: 3 x n_starts calls,
 each with its own synchronisation), alternating, in one process.  Both paths start from the filter's Z as a host array (that is what
-find_suitable_points_resident returns today).
+find_suitable_points_many returns by default).
 
     python tools/round3_batch_bench.py [--reps 7] [--starts 64] [--d 128] [--out profiles/round3_batch_bench.jsonl]
 
@@ -61,7 +61,7 @@ def main():
         def batched(dbs, t, ev=None):
             st = {}
             t0 = time.perf_counter()
-            res = sampling.rbf_round3_resident(dbs, lb1, ub1, xs, piv, Zs, 10 ** 9, n_new, True, False, reversed_order=True, ctx=ctx, stats=st)
+            res = sampling.rbf_round3_append(dbs, lb1, ub1, xs, piv, Zs, 10 ** 9, n_new, True, False, reversed_order=True, ctx=ctx, stats=st)
             t1 = time.perf_counter()
             database.set_values_many(dbs, [r.indices for r in res], [f(r.new_points) for r in res], ctx=ctx)
             t2 = time.perf_counter()
