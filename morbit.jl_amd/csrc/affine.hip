@@ -5,9 +5,11 @@
 // and the FIRST maximiser (the reference's `>` scan keeps the earliest).  Z (d x dz, the p-normalised complement basis of the
 // directions chosen so far) is recomputed by the caller after every pick -- a d x d QR, SURVEY.md section 8 row a12 -- the two
 // tall products and the reduction over up to 10^5..10^6 database sites run here.
-#include "common.hpp"
+#include "affine_host.hpp"  // AFF_G; the validation, counts and arena of mrbf_affine_select_batch
+#include "select_call.hpp"  // chain::SelectCall: the host scaffold of a batched call
 
 namespace mrbf {
+using affine::AFF_G;
 
 // val[c] = norm_p(U[:, c]), U d x mc column-major
 __global__ __launch_bounds__(256) void col_norms_kernel(const double *__restrict__ U, int d, int64_t mc, int use_inf, double *__restrict__ val) {
@@ -81,7 +83,6 @@ struct AffSel {
 // val[c] = | Zs C[j:, c] |_p for eight candidates per workgroup (no rocBLAS inside the pick loop: its lazily loaded kernels cost 50-90 ms the
 // first time a new shape class turns up -- three such hiccups in the twenty iterations of the rehearsal).  Thread t owns rows t, t + 256, ...
 // of the eight products; Zs is read column by column (coalesced), the candidates' trailing coordinates sit in LDS.
-constexpr int AFF_G = 8;
 __global__ __launch_bounds__(256) void affsel_score_kernel(AffSel a, int j) {
     extern __shared__ double sx[];  // [AFF_G][dz]
     __shared__ double red[256];
@@ -792,65 +793,33 @@ extern "C" int32_t mrbf_affine_select_batch(mrbf_ctx *ctx, int64_t n_starts, int
         return fail(ctx, -2, "mrbf_affine_select_batch: %lld starts, d = %d, p_is_inf = %d is outside the batched pick loop (ask mrbf_dispatch_affine_batch first)",
                     (long long)n_starts, d, p_is_inf);
     const size_t N = (size_t)n_starts, D = (size_t)d;
-    int64_t mc_sum = 0;
-    int T = 0;  // launches of the loop
-    int64_t ngrp_max = 0;
-    std::vector<int> want(N);
-    for (size_t p = 0; p < N; ++p) {
-        const mrbf_affine_job &jb = jobs[p];
-        if (jb.mc < 0 || jb.mc > ((int64_t)1 << 26)) return fail(ctx, -5, "jobs[%zu].mc out of range", p);
-        if (jb.j0 < 0 || jb.j0 > d) return fail(ctx, -5, "jobs[%zu].j0 must lie in [0, d]", p);
-        if (jb.j0 > 0 && !jb.Q0) return fail(ctx, -5, "jobs[%zu].Q0 is NULL", p);
-        if (jb.max_picks < 0) return fail(ctx, -5, "jobs[%zu].max_picks < 0", p);
-        if (jb.mc > 0 && !jb.shifted) return fail(ctx, -5, "jobs[%zu].shifted is NULL", p);
-        const int mp = std::min(jb.max_picks, d - jb.j0);
-        if (mp > 0 && !jb.picked_out) return fail(ctx, -5, "jobs[%zu].picked_out is NULL", p);
-        mc_sum += jb.mc;
-        if (mc_sum > ((int64_t)1 << 26)) return fail(ctx, -5, "mrbf_affine_select_batch: more than 2^26 candidates in all");
-        want[p] = jb.mc > 0 ? mp : 0;
-        if (want[p] > 0) {
-            T = std::max(T, want[p]);
-            ngrp_max = std::max(ngrp_max, (jb.mc + AFF_G - 1) / AFF_G);
-        }
-    }
+    const affine::Plan P = affine::plan(n_starts, d, jobs, sizeof(AffJob), 5);
+    if (P.bad) return fail(ctx, P.bad.code, "%s", P.bad.msg.c_str());
     for (size_t p = 0; p < N; ++p) jobs[p].n_picked = 0;
     if (ms_total) *ms_total = 0.f;
-    (void)hipSetDevice(ctx->device);
-    hipStream_t s = ctx->stream;
-    // ---- the arena: state | picks | hv | descriptors | Q | Zs | val | C | S, every piece a multiple of 256 bytes (state and picks come back
-    // in one copy, descriptors and start bases go up in one)
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t hvn = 2 * D + 8, mcs = (size_t)std::max<int64_t>(mc_sum, 1);
-    const size_t bState = up(N * 4 * sizeof(int)), bPicks = up(N * D * sizeof(long long)), bDesc = up(N * sizeof(AffJob)),
-                 bHv = up(N * hvn * sizeof(double)), bQ = up(N * D * D * sizeof(double)), bVal = up(mcs * sizeof(double)),
-                 bC = up(mcs * D * sizeof(double));
-    const size_t oState = 0, oPicks = oState + bState, oHv = oPicks + bPicks, oDesc = oHv + bHv, oQ = oDesc + bDesc, oZs = oQ + bQ,
-                 oVal = oZs + bQ, oC = oVal + bVal, oS = oC + bC, total = oS + bC;
-    char *base;
-    MRBF_TRY(get_buf(ctx, S_AFF_BATCH, total, &base));
-    int *dState = reinterpret_cast<int *>(base + oState);
-    long long *dPicks = reinterpret_cast<long long *>(base + oPicks);
-    AffJob *dDesc = reinterpret_cast<AffJob *>(base + oDesc);
-    double *dHv = reinterpret_cast<double *>(base + oHv), *dQ = reinterpret_cast<double *>(base + oQ), *dZs = reinterpret_cast<double *>(base + oZs),
-           *dVal = reinterpret_cast<double *>(base + oVal), *dC = reinterpret_cast<double *>(base + oC), *dS = reinterpret_cast<double *>(base + oS);
+    chain::SelectCall call(ctx, ms_total);
+    hipStream_t s = call.s;
+    // ---- the arena (affine_host.hpp): state and picks come back in one copy, descriptors and start bases go up in one
+    MRBF_TRY(call.begin());  // (the time includes the host's packing of the upload, as it always has)
+    MRBF_TRY(call.open(S_AFF_BATCH, P.A, P.A.upload_bytes()));
+    int *dState = call.dev<int>(P.oState);
+    const AffJob *dDesc = call.dev<const AffJob>(P.oDesc);
     static const int want_stamps = mrbf_env("MRBF_AFFINE_STAMPS") ? atoi(mrbf_env("MRBF_AFFINE_STAMPS")) : 0;
     unsigned long long *stamps = nullptr;
     if (want_stamps) MRBF_TRY(get_buf(ctx, S_MISC, (size_t)16, &stamps));
-    hipEvent_t e0 = ctx->ev[0], e1 = ctx->ev[1];
-    if (ms_total) MRBF_HIP(ctx, hipEventRecord(e0, s));
-    MRBF_HIP(ctx, hipMemsetAsync(dState, 0, bState, s));
+    MRBF_HIP(ctx, hipMemsetAsync(dState, 0, P.oPicks - P.oState, s));
     // ---- uploads: the start bases (identity with j0 = 0) in one copy, then whatever already lives on the device; the candidates likewise
-    std::vector<char> hup(bDesc + N * D * D * sizeof(double), 0);
-    AffJob *hdesc = reinterpret_cast<AffJob *>(hup.data());
-    double *hq = reinterpret_cast<double *>(hup.data() + bDesc);
+    AffJob *hdesc = call.host<AffJob>(P.oDesc);
+    double *hq = call.host<double>(P.oQ);
     std::vector<char> q_dev(N, 0), s_dev(N, 0);
     size_t coff = 0;
     for (size_t p = 0; p < N; ++p) {
         const mrbf_affine_job &jb = jobs[p];
         AffJob &h = hdesc[p];
-        h.Q = dQ + p * D * D, h.Zs = dZs + p * D * D, h.hv = dHv + p * hvn, h.picks = dPicks + p * D, h.state = dState + p * 4;
-        h.C = dC + coff * D, h.S = dS + coff * D, h.val = dVal + coff;
-        h.mc = jb.mc, h.pivot = jb.pivot_val, h.j0 = jb.j0, h.max_picks = want[p];
+        h.Q = call.dev<double>(P.oQ) + p * D * D, h.Zs = call.dev<double>(P.oZs) + p * D * D, h.hv = call.dev<double>(P.oHv) + p * P.hvn;
+        h.picks = call.dev<long long>(P.oPicks) + p * D, h.state = dState + p * 4;
+        h.C = call.dev<double>(P.oC) + coff * D, h.S = call.dev<double>(P.oS) + coff * D, h.val = call.dev<double>(P.oVal) + coff;
+        h.mc = jb.mc, h.pivot = jb.pivot_val, h.j0 = jb.j0, h.max_picks = P.want[p];
         coff += (size_t)jb.mc;
         double *q = hq + p * D * D;
         if (jb.j0 == 0) {
@@ -860,55 +829,50 @@ extern "C" int32_t mrbf_affine_select_batch(mrbf_ctx *ctx, int64_t n_starts, int
         } else {
             std::memcpy(q, jb.Q0, D * D * sizeof(double));
         }
-        if (want[p] > 0) s_dev[p] = is_device_ptr(jb.shifted) ? 1 : 0;
+        if (P.want[p] > 0) s_dev[p] = is_device_ptr(jb.shifted) ? 1 : 0;
     }
-    MRBF_HIP(ctx, hipMemcpyAsync(dDesc, hup.data(), hup.size(), hipMemcpyHostToDevice, s));
+    MRBF_TRY(call.upload());
     for (size_t p = 0; p < N; ++p)
         if (q_dev[p]) MRBF_HIP(ctx, hipMemcpyAsync(hdesc[p].Q, jobs[p].Q0, D * D * sizeof(double), hipMemcpyDeviceToDevice, s));
-    if (T > 0) {
+    if (P.T > 0) {
         for (size_t p = 0; p < N; ++p)  // the candidates, straight from where they are (a host copy into one block first costs more than it saves)
-            if (want[p] > 0)
+            if (P.want[p] > 0)
                 MRBF_HIP(ctx, hipMemcpyAsync(const_cast<double *>(hdesc[p].S), jobs[p].shifted, (size_t)jobs[p].mc * D * sizeof(double),
                                              s_dev[p] ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
         // ---- C = Q' S and the start bases' Zs for every start, then one launch per pick
-        const dim3 gcand((unsigned)ngrp_max, (unsigned)N);
+        const dim3 gcand((unsigned)P.ngrp_max, (unsigned)N);
         hipLaunchKernelGGL(affsel_project_batch_kernel, gcand, dim3(256), (size_t)AFF_G * D * sizeof(double), s, dDesc, d);
         hipLaunchKernelGGL(affsel_update_batch_kernel, dim3((unsigned)d, (unsigned)N), dim3(256), 0, s, dDesc, d);
         const size_t shm_pick_total = (size_t)AFF_G * (D + 1) * sizeof(double) + (size_t)AFF_G * AFF_NT * sizeof(double);
         MRBF_HIP(ctx, hipFuncSetAttribute((const void *)affsel_pick_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_pick_total));
         std::vector<int> hstate(N * 4);
-        for (int t = 0; t < T; ++t) {
+        for (int t = 0; t < P.T; ++t) {
             hipLaunchKernelGGL(affsel_pick_batch_kernel, gcand, dim3(AFF_NT), shm_pick_total, s, dDesc, dState, d, t, stamps);
             if (t == 0) MRBF_HIP(ctx, hipGetLastError());
-            if ((t & 15) == 15 && t + 1 < T) {  // every start done, or with all the picks it wanted?
+            if ((t & 15) == 15 && t + 1 < P.T) {  // every start done, or with all the picks it wanted?
                 MRBF_HIP(ctx, hipMemcpyAsync(hstate.data(), dState, N * 4 * sizeof(int), hipMemcpyDeviceToHost, s));
                 MRBF_HIP(ctx, hipStreamSynchronize(s));
                 bool all_done = true;
-                for (size_t p = 0; p < N && all_done; ++p) all_done = hstate[p * 4] != 0 || hstate[p * 4 + 1] >= want[p];
+                for (size_t p = 0; p < N && all_done; ++p) all_done = hstate[p * 4] != 0 || hstate[p * 4 + 1] >= P.want[p];
                 if (all_done) break;
             }
         }
-        MRBF_HIP(ctx, hipGetLastError());
     }
     // ---- one read-back: per-start counts and pick lists (state and picks are neighbours in the arena)
-    std::vector<char> hback(bState + N * D * sizeof(long long));
-    MRBF_HIP(ctx, hipMemcpyAsync(hback.data(), base + oState, hback.size(), hipMemcpyDeviceToHost, s));
-    if (ms_total) MRBF_HIP(ctx, hipEventRecord(e1, s));
-    MRBF_HIP(ctx, hipStreamSynchronize(s));
-    if (ms_total) MRBF_HIP(ctx, hipEventElapsedTime(ms_total, e0, e1));
-    if (stamps && T > 0) {  // phases of start 0's last workgroup in the last launch it took part in, us since its start
+    MRBF_TRY(call.finish(P.A.back_bytes()));
+    if (stamps && P.T > 0) {  // phases of start 0's last workgroup in the last launch it took part in, us since its start
         unsigned long long hst[12];
         MRBF_HIP(ctx, hipMemcpy(hst, stamps, sizeof(hst), hipMemcpyDeviceToHost));
         fprintf(stderr, "affsel_pick_batch_kernel phases (us):");
         for (int q2 = 1; q2 < 10; ++q2) fprintf(stderr, " %.2f", (double)(hst[q2] - hst[0]) * 0.01);
         fprintf(stderr, "\n");
     }
-    const int *hst_all = reinterpret_cast<const int *>(hback.data());
-    const long long *hpk = reinterpret_cast<const long long *>(hback.data() + bState);
+    const int *hst_all = reinterpret_cast<const int *>(call.back.p);
+    const long long *hpk = reinterpret_cast<const long long *>(call.back.p + (P.oPicks - P.oState));
     std::vector<double> hz;
     for (size_t p = 0; p < N; ++p) {
         mrbf_affine_job &jb = jobs[p];
-        const int npick = want[p] > 0 ? hst_all[p * 4 + 1] : 0;
+        const int npick = P.want[p] > 0 ? hst_all[p * 4 + 1] : 0;
         for (int i = 0; i < npick; ++i) jb.picked_out[i] = (int64_t)hpk[p * D + i];
         jb.n_picked = npick;
         const int jf = jb.j0 + npick, dz = d - jf;

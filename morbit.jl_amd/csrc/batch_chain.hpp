@@ -17,18 +17,21 @@ struct Arena {
         return at;
     }
 };
-// a host block of `cnt` doubles for the upload or the read-back: in the armed pinned block where it fits in 4 MiB, else pageable
-struct Staging {
-    std::vector<double> own;
-    double *p;
-    Staging(mrbf_ctx *ctx, size_t cnt) {
-        p = reinterpret_cast<double *>(cnt * sizeof(double) <= ((size_t)4 << 20) ? pin_take(ctx, cnt * sizeof(double)) : nullptr);
+// a host block of `cnt` T for the upload or the read-back: in the armed pinned block where it fits in 4 MiB, else pageable
+template <class T>
+struct Block {
+    std::vector<T> own;
+    T *p = nullptr;
+    Block() = default;
+    Block(mrbf_ctx *ctx, size_t cnt) {
+        p = reinterpret_cast<T *>(cnt * sizeof(T) <= ((size_t)4 << 20) ? pin_take(ctx, cnt * sizeof(T)) : nullptr);
         if (!p) {
             own.resize(cnt);
             p = own.data();
         }
     }
 };
+using Staging = Block<double>;  // the descent chains count doubles; select_call.hpp counts bytes
 
 constexpr int64_t MAX_GROUP_LAUNCH = 65535;  // blockIdx.z of the evaluation kernels
 

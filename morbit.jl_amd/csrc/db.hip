@@ -14,8 +14,7 @@
 //                      block, then zeroed in the view when asked
 // mrbf_db_append_batch and mrbf_db_set_values_batch are mrbf_db_append and mrbf_db_set_values for every start of a batch: the host-side
 // rows and index lists of all starts travel in one packed upload behind the descriptors, one launch copies or scatters them.
-#include "batch_chain.hpp"  // chain::Staging: the host blocks of the packed upload and of the read-back
-#include "db_host.hpp"
+#include "select_call.hpp"  // chain::SelectCall, the host scaffold of a batched call; db_host.hpp
 
 namespace mrbf {
 namespace db {
@@ -241,7 +240,7 @@ static int reserve(mrbf_ctx *ctx, mrbf_db *db, int64_t needed) {
     return 0;
 }
 
-static DbInfo info_of(const mrbf_ctx *ctx, const mrbf_db *db) {
+DbInfo info_of(const mrbf_ctx *ctx, const mrbf_db *db) {
     return db ? DbInfo{db, db->d, db->k, db->n, db->ctx == ctx} : DbInfo{nullptr, 0, 0, 0, false};
 }
 
@@ -270,6 +269,24 @@ __global__ __launch_bounds__(NT) void db_set_values_batch_kernel(const SetDesc *
     const SetDesc J = desc[blockIdx.y];
     const long long cv = J.m * J.k, step = (long long)gridDim.x * NT;
     for (long long t = (long long)blockIdx.x * NT + threadIdx.x; t < cv; t += step) J.V[J.idx[t / J.k] * J.k + t % J.k] = J.vals[t];
+}
+
+// a view's `count` doubles to the caller's buffer (host or device), where it gave one
+static bool view_out(double *dst, const double *src, size_t count) {
+    if (!dst || count == 0 || hipMemcpy(dst, src, count * sizeof(double), hipMemcpyDefault) == hipSuccess) return true;
+    (void)hipGetLastError();
+    return false;
+}
+// ---- the one launch of mrbf_db_append_batch / mrbf_db_set_values_batch: at most 1024 workgroups of NT threads per start over cnt_max elements
+template <class Desc>
+static int launch_update(chain::SelectCall &call, void (*kernel)(const Desc *), size_t N, int64_t cnt_max) {
+    MRBF_TRY(call.begin());
+    MRBF_TRY(call.upload());
+    if (cnt_max > 0) {
+        const dim3 grid((unsigned)std::min<int64_t>((cnt_max + NT - 1) / NT, 1024), (unsigned)N);
+        hipLaunchKernelGGL(kernel, grid, dim3(NT), 0, call.s, call.dev<const Desc>(0));
+    }
+    return call.finish(0);
 }
 
 }  // namespace db
@@ -342,7 +359,7 @@ int32_t mrbf_db_set_values(mrbf_ctx *ctx, mrbf_db *h, int64_t m, const int64_t *
         if (indices[i] < 0 || indices[i] >= h->n) return fail(ctx, -4, "mrbf_db_set_values: indices[%lld] = %lld is not a row", (long long)i, (long long)indices[i]);
     (void)hipSetDevice(ctx->device);
     hipStream_t s = ctx->stream;
-    const size_t M = (size_t)m, K = (size_t)h->k, bIdx = db::up256(M * sizeof(int64_t));
+    const size_t M = (size_t)m, K = (size_t)h->k, bIdx = up256(M * sizeof(int64_t));
     char *base;
     MRBF_TRY(get_buf(ctx, S_DB_WS, bIdx + M * K * sizeof(double), &base));
     MRBF_HIP(ctx, hipMemcpyAsync(base, indices, M * sizeof(int64_t), hipMemcpyHostToDevice, s));
@@ -393,70 +410,49 @@ int32_t mrbf_db_free(mrbf_ctx *ctx, mrbf_db *h) {
 
 int32_t mrbf_db_box_batch(mrbf_ctx *ctx, int64_t n_starts, int32_t d, int32_t p_is_inf, mrbf_db_box_job *jobs, float *ms_total) {
     using namespace db;
-    if (!ctx) return -1;
-    if (mrbf_dispatch_db_batch(n_starts, d) != MRBF_DISPATCH_DEVICE)
-        return fail(ctx, -2, "mrbf_db_box_batch: %lld starts, d = %d is outside the batched scan (ask mrbf_dispatch_db_batch first)",
-                    (long long)n_starts, d);
-    if (!jobs) return fail(ctx, -5, "jobs is NULL");
+    std::vector<DbInfo> info;
+    MRBF_TRY(open_batch(ctx, "mrbf_db_box_batch", n_starts, d, jobs, 5, info, [&] { return check_box_jobs(n_starts, d, jobs, info.data(), 5); }));
     const size_t N = (size_t)n_starts, D = (size_t)d;
-    std::vector<DbInfo> info(N);
     std::vector<int64_t> rows(N);
-    for (size_t p = 0; p < N; ++p) info[p] = info_of(ctx, jobs[p].db), rows[p] = info[p].n;
-    if (Defect df = check_box_jobs(n_starts, d, jobs, info.data(), 5)) return fail(ctx, df.code, "mrbf_db_box_batch: %s", df.msg.c_str());
+    for (size_t p = 0; p < N; ++p) rows[p] = info[p].n;
     const BoxLayout L = box_layout(n_starts, d, rows.data(), sizeof(BoxDesc));
-    (void)hipSetDevice(ctx->device);
-    hipStream_t s = ctx->stream;
+    chain::SelectCall call(ctx, ms_total);
+    hipStream_t s = call.s;
     double *views;
-    char *base;
     MRBF_TRY(get_buf(ctx, S_DB_BOX, L.view_doubles, &views));
-    MRBF_TRY(get_buf(ctx, S_DB_WS, L.total_bytes, &base));
-    PinGuard pin(ctx);
     // ---- one upload: descriptors, bounds and centres, exclusion masks
-    chain::Staging up_block(ctx, L.upload_bytes / sizeof(double));
-    char *const up_p = reinterpret_cast<char *>(up_block.p);
-    std::memset(up_p, 0, L.upload_bytes);
-    BoxDesc *hdesc = reinterpret_cast<BoxDesc *>(up_p + L.oDesc);
+    MRBF_TRY(call.open(S_DB_WS, L.A, L.A.upload_bytes()));
+    BoxDesc *hdesc = call.host<BoxDesc>(L.oDesc);
     bool want_idx = false;
     for (size_t p = 0; p < N; ++p) {
         const mrbf_db_box_job &jb = jobs[p];
         const size_t r0 = (size_t)L.roff[p];
         BoxDesc &h = hdesc[p];
         h.S = jb.db->sites;
-        h.bounds = reinterpret_cast<const double *>(base + L.oBounds) + p * 3 * D;
-        h.flag = reinterpret_cast<unsigned char *>(base + L.oMask) + r0;
-        h.norm = reinterpret_cast<double *>(base + L.oNorm) + r0, h.cnorm = reinterpret_cast<double *>(base + L.oCnorm) + r0;
-        h.count = reinterpret_cast<int *>(base + L.oCount) + r0 / ROWS, h.offs = reinterpret_cast<int *>(base + L.oOffs) + r0 / ROWS;
-        h.head = reinterpret_cast<long long *>(base + L.oHead) + 2 * p;
-        h.first = reinterpret_cast<double *>(base + L.oFirst) + p * D;
-        h.idx = reinterpret_cast<long long *>(base + L.oIdx) + r0;
+        h.bounds = call.dev<const double>(L.oBounds) + p * 3 * D, h.flag = call.dev<unsigned char>(L.oMask) + r0;
+        h.norm = call.dev<double>(L.oNorm) + r0, h.cnorm = call.dev<double>(L.oCnorm) + r0;
+        h.count = call.dev<int>(L.oCount) + r0 / ROWS, h.offs = call.dev<int>(L.oOffs) + r0 / ROWS;
+        h.head = call.dev<long long>(L.oHead) + 2 * p, h.first = call.dev<double>(L.oFirst) + p * D, h.idx = call.dev<long long>(L.oIdx) + r0;
         h.vs = views + L.sites_view((int64_t)p, d), h.vh = views + L.shifted_view((int64_t)p, d);
         h.n = rows[p], h.nblk = (int)((rows[p] + ROWS - 1) / ROWS), h.zero = jb.zero_first_pick != 0;
-        double *b = reinterpret_cast<double *>(up_p + L.oBounds) + p * 3 * D;
+        double *b = call.host<double>(L.oBounds) + p * 3 * D;
         std::memcpy(b, jb.lb, D * sizeof(double)), std::memcpy(b + D, jb.ub, D * sizeof(double)), std::memcpy(b + 2 * D, jb.x0, D * sizeof(double));
-        build_mask(rows[p], jb.n_exclude, jb.exclude, reinterpret_cast<unsigned char *>(up_p + L.oMask) + r0);
+        build_mask(rows[p], jb.n_exclude, jb.exclude, call.host<unsigned char>(L.oMask) + r0);
         want_idx = want_idx || jb.indices_out != nullptr;
     }
-    hipEvent_t e0 = ctx->ev[0], e1 = ctx->ev[1];
-    if (ms_total) MRBF_HIP(ctx, hipEventRecord(e0, s));
-    MRBF_HIP(ctx, hipMemcpyAsync(base, up_p, L.upload_bytes, hipMemcpyHostToDevice, s));
-    const BoxDesc *ddesc = reinterpret_cast<const BoxDesc *>(base + L.oDesc);
+    MRBF_TRY(call.begin());
+    MRBF_TRY(call.upload());
+    const BoxDesc *ddesc = call.dev<const BoxDesc>(L.oDesc);
     const dim3 grows((unsigned)std::max<int64_t>(L.nblk_max, 1), (unsigned)N);
     if (L.nblk_max > 0) hipLaunchKernelGGL(db_flag_kernel, grows, dim3(NT), 0, s, ddesc, d, p_is_inf ? 1 : 0);
     hipLaunchKernelGGL(db_scan_kernel, dim3((unsigned)N), dim3(NT), 0, s, ddesc);
     if (L.nblk_max > 0) hipLaunchKernelGGL(db_compact_kernel, grows, dim3(NT), 0, s, ddesc, d);
     hipLaunchKernelGGL(db_pick_kernel, dim3((unsigned)N), dim3(NT), 0, s, ddesc, d);
-    MRBF_HIP(ctx, hipGetLastError());
     // ---- one read-back: counts, first picks and their rows [, the candidates' indices]
-    const size_t back = want_idx ? L.back_bytes : L.back_head_bytes;
-    chain::Staging hb_block(ctx, back / sizeof(double));
-    char *const hb_p = reinterpret_cast<char *>(hb_block.p);
-    MRBF_HIP(ctx, hipMemcpyAsync(hb_p, base + L.oHead, back, hipMemcpyDeviceToHost, s));
-    if (ms_total) MRBF_HIP(ctx, hipEventRecord(e1, s));
-    MRBF_HIP(ctx, hipStreamSynchronize(s));
-    if (ms_total) MRBF_HIP(ctx, hipEventElapsedTime(ms_total, e0, e1));
-    const long long *head = reinterpret_cast<const long long *>(hb_p);
-    const double *first = reinterpret_cast<const double *>(hb_p + (L.oFirst - L.oHead));
-    const long long *idx = reinterpret_cast<const long long *>(hb_p + (L.oIdx - L.oHead));
+    MRBF_TRY(call.finish(want_idx ? L.A.back_bytes() : L.back_head_bytes));
+    const long long *head = reinterpret_cast<const long long *>(call.back.p);
+    const double *first = reinterpret_cast<const double *>(call.back.p + (L.oFirst - L.oHead));
+    const long long *idx = reinterpret_cast<const long long *>(call.back.p + (L.oIdx - L.oHead));
     for (size_t p = 0; p < N; ++p) {
         mrbf_db_box_job &jb = jobs[p];
         const int64_t mc = head[2 * p], pick = head[2 * p + 1];
@@ -464,12 +460,7 @@ int32_t mrbf_db_box_batch(mrbf_ctx *ctx, int64_t n_starts, int32_t d, int32_t p_
             jb.rc = MRBF_EHIP;
             continue;
         }
-        const size_t bytes = (size_t)mc * D * sizeof(double);
-        hipError_t e = hipSuccess;
-        if (jb.sites_out && mc > 0) e = hipMemcpy(jb.sites_out, hdesc[p].vs, bytes, hipMemcpyDefault);
-        if (e == hipSuccess && jb.shifted_out && mc > 0) e = hipMemcpy(jb.shifted_out, hdesc[p].vh, bytes, hipMemcpyDefault);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
+        if (!view_out(jb.sites_out, hdesc[p].vs, (size_t)mc * D) || !view_out(jb.shifted_out, hdesc[p].vh, (size_t)mc * D)) {
             jb.rc = MRBF_EHIP;
             continue;
         }
@@ -485,53 +476,37 @@ int32_t mrbf_db_box_batch(mrbf_ctx *ctx, int64_t n_starts, int32_t d, int32_t p_
 
 int32_t mrbf_db_gather_batch(mrbf_ctx *ctx, int64_t n_starts, int32_t d, mrbf_db_gather_job *jobs, float *ms_total) {
     using namespace db;
-    if (!ctx) return -1;
-    if (mrbf_dispatch_db_batch(n_starts, d) != MRBF_DISPATCH_DEVICE)
-        return fail(ctx, -2, "mrbf_db_gather_batch: %lld starts, d = %d is outside the batched gather (ask mrbf_dispatch_db_batch first)",
-                    (long long)n_starts, d);
-    if (!jobs) return fail(ctx, -4, "jobs is NULL");
+    std::vector<DbInfo> info;
+    MRBF_TRY(open_batch(ctx, "mrbf_db_gather_batch", n_starts, d, jobs, 4, info, [&] { return check_gather_jobs(n_starts, d, jobs, info.data(), 4); }));
     const size_t N = (size_t)n_starts, D = (size_t)d;
-    std::vector<DbInfo> info(N);
-    for (size_t p = 0; p < N; ++p) info[p] = info_of(ctx, jobs[p].db);
-    if (Defect df = check_gather_jobs(n_starts, d, jobs, info.data(), 4)) return fail(ctx, df.code, "mrbf_db_gather_batch: %s", df.msg.c_str());
     std::vector<int64_t> cnt(N);
     std::vector<int> ks(N), rcs(N);
     for (size_t p = 0; p < N; ++p) {
-        rcs[p] = gather_job_rc(info[p].n, jobs[p].n_idx, jobs[p].indices);
+        rcs[p] = index_rc(info[p].n, jobs[p].n_idx, jobs[p].indices, GATHER_RC_INDEX);
         cnt[p] = rcs[p] == 0 ? jobs[p].n_idx : -1;  // a job that failed its own check takes no part
         ks[p] = info[p].k;
     }
     const GatherLayout L = gather_layout(n_starts, d, ks.data(), cnt.data(), sizeof(GatherDesc));
-    (void)hipSetDevice(ctx->device);
-    hipStream_t s = ctx->stream;
+    chain::SelectCall call(ctx, ms_total);
     double *views;
-    char *base;
     MRBF_TRY(get_buf(ctx, S_DB_GATHER, L.view_doubles, &views));
-    MRBF_TRY(get_buf(ctx, S_DB_WS, L.upload_bytes, &base));
-    PinGuard pin(ctx);
-    chain::Staging up_block(ctx, L.upload_bytes / sizeof(double));
-    char *const up_p = reinterpret_cast<char *>(up_block.p);
-    std::memset(up_p, 0, L.upload_bytes);
-    GatherDesc *hdesc = reinterpret_cast<GatherDesc *>(up_p + L.oDesc);
+    MRBF_TRY(call.open(S_DB_WS, L.A, L.A.total));
+    GatherDesc *hdesc = call.host<GatherDesc>(L.oDesc);
     for (size_t p = 0; p < N; ++p) {
         GatherDesc &h = hdesc[p];
         h.S = jobs[p].db->sites, h.V = jobs[p].db->values;
-        h.idx = reinterpret_cast<const long long *>(base + L.oIdx) + L.ioff[p];
+        h.idx = call.dev<const long long>(L.oIdx) + L.ioff[p];
         h.so = views + L.soff[p], h.vo = views + L.voff[p];
         h.m = std::max<int64_t>(cnt[p], 0), h.k = ks[p];
-        if (h.m > 0) std::memcpy(up_p + L.oIdx + (size_t)L.ioff[p] * sizeof(int64_t), jobs[p].indices, (size_t)h.m * sizeof(int64_t));
+        if (h.m > 0) std::memcpy(call.host<int64_t>(L.oIdx) + L.ioff[p], jobs[p].indices, (size_t)h.m * sizeof(int64_t));
     }
-    hipEvent_t e0 = ctx->ev[0], e1 = ctx->ev[1];
-    if (ms_total) MRBF_HIP(ctx, hipEventRecord(e0, s));
-    MRBF_HIP(ctx, hipMemcpyAsync(base, up_p, L.upload_bytes, hipMemcpyHostToDevice, s));
+    MRBF_TRY(call.begin());
+    MRBF_TRY(call.upload());
     if (L.n_idx_max > 0) {
         const dim3 grid((unsigned)std::min<int64_t>((L.n_idx_max + 3) / 4, 1024), (unsigned)N);
-        hipLaunchKernelGGL(db_gather_kernel, grid, dim3(NT), 0, s, reinterpret_cast<const GatherDesc *>(base + L.oDesc), d);
-        MRBF_HIP(ctx, hipGetLastError());
+        hipLaunchKernelGGL(db_gather_kernel, grid, dim3(NT), 0, call.s, call.dev<const GatherDesc>(L.oDesc), d);
     }
-    if (ms_total) MRBF_HIP(ctx, hipEventRecord(e1, s));
-    MRBF_HIP(ctx, hipStreamSynchronize(s));
-    if (ms_total) MRBF_HIP(ctx, hipEventElapsedTime(ms_total, e0, e1));
+    MRBF_TRY(call.finish(0));
     for (size_t p = 0; p < N; ++p) {
         mrbf_db_gather_job &jb = jobs[p];
         if (rcs[p] != 0) {
@@ -539,11 +514,7 @@ int32_t mrbf_db_gather_batch(mrbf_ctx *ctx, int64_t n_starts, int32_t d, mrbf_db
             continue;
         }
         const size_t m = (size_t)jb.n_idx;
-        hipError_t e = hipSuccess;
-        if (jb.sites_out && m > 0) e = hipMemcpy(jb.sites_out, hdesc[p].so, m * D * sizeof(double), hipMemcpyDefault);
-        if (e == hipSuccess && jb.values_out && m > 0) e = hipMemcpy(jb.values_out, hdesc[p].vo, m * (size_t)ks[p] * sizeof(double), hipMemcpyDefault);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
+        if (!view_out(jb.sites_out, hdesc[p].so, m * D) || !view_out(jb.values_out, hdesc[p].vo, m * (size_t)ks[p])) {
             jb.rc = MRBF_EHIP;
             continue;
         }
@@ -555,62 +526,39 @@ int32_t mrbf_db_gather_batch(mrbf_ctx *ctx, int64_t n_starts, int32_t d, mrbf_db
 
 int32_t mrbf_db_append_batch(mrbf_ctx *ctx, int64_t n_starts, mrbf_db_append_job *jobs, float *ms_total) {
     using namespace db;
-    if (!ctx) return -1;
-    if (mrbf_dispatch_db_batch(n_starts, 1) != MRBF_DISPATCH_DEVICE)
-        return fail(ctx, -2, "mrbf_db_append_batch: %lld starts is outside the batched append (ask mrbf_dispatch_db_batch first)", (long long)n_starts);
-    if (!jobs) return fail(ctx, -3, "jobs is NULL");
+    std::vector<DbInfo> info;
+    MRBF_TRY(open_batch(ctx, "mrbf_db_append_batch", n_starts, 1, jobs, 3, info, [&] { return check_append_jobs(n_starts, jobs, info.data(), 3); }));
     const size_t N = (size_t)n_starts;
-    std::vector<DbInfo> info(N);
-    for (size_t p = 0; p < N; ++p) info[p] = info_of(ctx, jobs[p].db);
-    if (Defect df = check_append_jobs(n_starts, jobs, info.data(), 3)) return fail(ctx, df.code, "mrbf_db_append_batch: %s", df.msg.c_str());
-    (void)hipSetDevice(ctx->device);
-    hipStream_t s = ctx->stream;
-    // ---- the layout of the upload: descriptors, then the host-side rows of every start (device-side rows are read in place)
-    PackLayout L;
-    L.take(N * sizeof(AppendDesc));
-    std::vector<size_t> os(N, 0), ov(N, 0);
-    std::vector<char> hs(N, 0), hv(N, 0);
+    chain::SelectCall call(ctx, ms_total);
+    // ---- the upload: the descriptors, then the host-side rows of every start (device-side rows are read in place)
+    ByteArena A;
+    A.take(N * sizeof(AppendDesc));
+    std::vector<size_t> os(N, 0), ov(N, 0);  // (0: read in place, or none)
     int64_t cnt_max = 0;
     for (size_t p = 0; p < N; ++p) {
         const mrbf_db_append_job &jb = jobs[p];
         const size_t M = (size_t)jb.m, D = (size_t)info[p].d, K = (size_t)info[p].k;
         cnt_max = std::max<int64_t>(cnt_max, (int64_t)(M * std::max(D, K)));
         if (M == 0) continue;
-        hs[p] = !is_device_ptr(jb.sites), hv[p] = jb.values && !is_device_ptr(jb.values);
-        if (hs[p]) os[p] = L.take(M * D * sizeof(double));
-        if (hv[p]) ov[p] = L.take(M * K * sizeof(double));
+        if (!is_device_ptr(jb.sites)) os[p] = A.take(M * D * sizeof(double));
+        if (jb.values && !is_device_ptr(jb.values)) ov[p] = A.take(M * K * sizeof(double));
     }
+    A.up_end = A.total;
     for (size_t p = 0; p < N; ++p) MRBF_TRY(reserve(ctx, jobs[p].db, info[p].n + jobs[p].m));
-    char *base;
-    MRBF_TRY(get_buf(ctx, S_DB_WS, L.at, &base));
-    PinGuard pin(ctx);
-    chain::Staging up_block(ctx, L.at / sizeof(double));
-    char *const up_p = reinterpret_cast<char *>(up_block.p);
-    AppendDesc *hdesc = reinterpret_cast<AppendDesc *>(up_p);
+    MRBF_TRY(call.open(S_DB_WS, A, N * sizeof(AppendDesc)));
     for (size_t p = 0; p < N; ++p) {
         const mrbf_db_append_job &jb = jobs[p];
         const mrbf_db *h = jb.db;
         const size_t M = (size_t)jb.m, D = (size_t)h->d, K = (size_t)h->k, n = (size_t)h->n;
-        AppendDesc &a = hdesc[p];
-        std::memset(&a, 0, sizeof(a));
+        AppendDesc &a = call.host<AppendDesc>(0)[p];
         a.S = h->sites + n * D, a.V = h->values + n * K, a.m = jb.m, a.d = h->d, a.k = h->k;
         if (M == 0) continue;
-        a.ss = hs[p] ? reinterpret_cast<const double *>(base + os[p]) : jb.sites;
-        a.sv = !jb.values ? nullptr : (hv[p] ? reinterpret_cast<const double *>(base + ov[p]) : jb.values);
-        if (hs[p]) std::memcpy(up_p + os[p], jb.sites, M * D * sizeof(double));
-        if (hv[p]) std::memcpy(up_p + ov[p], jb.values, M * K * sizeof(double));
+        a.ss = os[p] ? call.dev<const double>(os[p]) : jb.sites;
+        a.sv = ov[p] ? call.dev<const double>(ov[p]) : jb.values;
+        if (os[p]) std::memcpy(call.host<char>(os[p]), jb.sites, M * D * sizeof(double));
+        if (ov[p]) std::memcpy(call.host<char>(ov[p]), jb.values, M * K * sizeof(double));
     }
-    hipEvent_t e0 = ctx->ev[0], e1 = ctx->ev[1];
-    if (ms_total) MRBF_HIP(ctx, hipEventRecord(e0, s));
-    MRBF_HIP(ctx, hipMemcpyAsync(base, up_p, L.at, hipMemcpyHostToDevice, s));
-    if (cnt_max > 0) {
-        const dim3 grid((unsigned)std::min<int64_t>((cnt_max + NT - 1) / NT, 1024), (unsigned)N);
-        hipLaunchKernelGGL(db_append_batch_kernel, grid, dim3(NT), 0, s, reinterpret_cast<const AppendDesc *>(base));
-        MRBF_HIP(ctx, hipGetLastError());
-    }
-    if (ms_total) MRBF_HIP(ctx, hipEventRecord(e1, s));
-    MRBF_HIP(ctx, hipStreamSynchronize(s));  // the callers' buffers are their own again
-    if (ms_total) MRBF_HIP(ctx, hipEventElapsedTime(ms_total, e0, e1));
+    MRBF_TRY(launch_update(call, db_append_batch_kernel, N, cnt_max));  // (synchronised: the callers' buffers are their own again)
     for (size_t p = 0; p < N; ++p) {
         jobs[p].first_index = jobs[p].db->n;
         jobs[p].db->n += jobs[p].m;
@@ -621,62 +569,39 @@ int32_t mrbf_db_append_batch(mrbf_ctx *ctx, int64_t n_starts, mrbf_db_append_job
 
 int32_t mrbf_db_set_values_batch(mrbf_ctx *ctx, int64_t n_starts, mrbf_db_set_values_job *jobs, float *ms_total) {
     using namespace db;
-    if (!ctx) return -1;
-    if (mrbf_dispatch_db_batch(n_starts, 1) != MRBF_DISPATCH_DEVICE)
-        return fail(ctx, -2, "mrbf_db_set_values_batch: %lld starts is outside the batched update (ask mrbf_dispatch_db_batch first)", (long long)n_starts);
-    if (!jobs) return fail(ctx, -3, "jobs is NULL");
+    std::vector<DbInfo> info;
+    MRBF_TRY(open_batch(ctx, "mrbf_db_set_values_batch", n_starts, 1, jobs, 3, info, [&] { return check_set_values_jobs(n_starts, jobs, info.data(), 3); }));
     const size_t N = (size_t)n_starts;
-    std::vector<DbInfo> info(N);
-    for (size_t p = 0; p < N; ++p) info[p] = info_of(ctx, jobs[p].db);
-    if (Defect df = check_set_values_jobs(n_starts, jobs, info.data(), 3)) return fail(ctx, df.code, "mrbf_db_set_values_batch: %s", df.msg.c_str());
-    (void)hipSetDevice(ctx->device);
-    hipStream_t s = ctx->stream;
-    PackLayout L;
-    L.take(N * sizeof(SetDesc));
-    std::vector<size_t> oi(N, 0), ov(N, 0);
-    std::vector<char> hv(N, 0);
+    chain::SelectCall call(ctx, ms_total);
+    ByteArena A;
+    A.take(N * sizeof(SetDesc));
+    std::vector<size_t> oi(N, 0), ov(N, 0);  // (ov 0: read in place)
     std::vector<int> rcs(N, 0);
     int64_t cnt_max = 0;
     for (size_t p = 0; p < N; ++p) {
         const mrbf_db_set_values_job &jb = jobs[p];
-        rcs[p] = set_values_job_rc(info[p].n, jb.m, jb.indices);
+        rcs[p] = index_rc(info[p].n, jb.m, jb.indices, SET_VALUES_RC_INDEX);
         if (rcs[p] != 0 || jb.m == 0) continue;  // a job that failed its own check takes no part
         const size_t M = (size_t)jb.m, K = (size_t)info[p].k;
         cnt_max = std::max<int64_t>(cnt_max, (int64_t)(M * K));
-        hv[p] = !is_device_ptr(jb.values);
-        oi[p] = L.take(M * sizeof(int64_t));
-        if (hv[p]) ov[p] = L.take(M * K * sizeof(double));
+        oi[p] = A.take(M * sizeof(int64_t));
+        if (!is_device_ptr(jb.values)) ov[p] = A.take(M * K * sizeof(double));
     }
-    char *base;
-    MRBF_TRY(get_buf(ctx, S_DB_WS, L.at, &base));
-    PinGuard pin(ctx);
-    chain::Staging up_block(ctx, L.at / sizeof(double));
-    char *const up_p = reinterpret_cast<char *>(up_block.p);
-    SetDesc *hdesc = reinterpret_cast<SetDesc *>(up_p);
+    A.up_end = A.total;
+    MRBF_TRY(call.open(S_DB_WS, A, N * sizeof(SetDesc)));
     for (size_t p = 0; p < N; ++p) {
         const mrbf_db_set_values_job &jb = jobs[p];
-        SetDesc &a = hdesc[p];
-        std::memset(&a, 0, sizeof(a));
+        SetDesc &a = call.host<SetDesc>(0)[p];
         a.V = jb.db->values, a.k = jb.db->k;
         if (rcs[p] != 0 || jb.m == 0) continue;
         const size_t M = (size_t)jb.m, K = (size_t)a.k;
         a.m = jb.m;
-        a.idx = reinterpret_cast<const long long *>(base + oi[p]);
-        a.vals = hv[p] ? reinterpret_cast<const double *>(base + ov[p]) : jb.values;
-        std::memcpy(up_p + oi[p], jb.indices, M * sizeof(int64_t));
-        if (hv[p]) std::memcpy(up_p + ov[p], jb.values, M * K * sizeof(double));
+        a.idx = call.dev<const long long>(oi[p]);
+        a.vals = ov[p] ? call.dev<const double>(ov[p]) : jb.values;
+        std::memcpy(call.host<char>(oi[p]), jb.indices, M * sizeof(int64_t));
+        if (ov[p]) std::memcpy(call.host<char>(ov[p]), jb.values, M * K * sizeof(double));
     }
-    hipEvent_t e0 = ctx->ev[0], e1 = ctx->ev[1];
-    if (ms_total) MRBF_HIP(ctx, hipEventRecord(e0, s));
-    MRBF_HIP(ctx, hipMemcpyAsync(base, up_p, L.at, hipMemcpyHostToDevice, s));
-    if (cnt_max > 0) {
-        const dim3 grid((unsigned)std::min<int64_t>((cnt_max + NT - 1) / NT, 1024), (unsigned)N);
-        hipLaunchKernelGGL(db_set_values_batch_kernel, grid, dim3(NT), 0, s, reinterpret_cast<const SetDesc *>(base));
-        MRBF_HIP(ctx, hipGetLastError());
-    }
-    if (ms_total) MRBF_HIP(ctx, hipEventRecord(e1, s));
-    MRBF_HIP(ctx, hipStreamSynchronize(s));
-    if (ms_total) MRBF_HIP(ctx, hipEventElapsedTime(ms_total, e0, e1));
+    MRBF_TRY(launch_update(call, db_set_values_batch_kernel, N, cnt_max));
     for (size_t p = 0; p < N; ++p) jobs[p].rc = rcs[p];
     return MRBF_OK;
 }

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/mrbf.h"
+#include "select_host.hpp"
 
 namespace mrbf {
 namespace db {
@@ -40,11 +41,8 @@ struct DbInfo {
     int64_t n;       // rows
     bool own;        // created through the context of the call
 };
-struct Defect {
-    int code = 0;  // 0, or -(1-based index of the invalid argument)
-    std::string msg;
-    explicit operator bool() const { return code != 0; }
-};
+DbInfo info_of(const mrbf_ctx *ctx, const mrbf_db *db);  // (db.hip) of a handle, NULL included
+using mrbf::Defect;
 inline Defect defect(int code, const char *what, int64_t p) {
     char buf[160];
     std::snprintf(buf, sizeof(buf), "jobs[%lld]: %s", (long long)p, what);
@@ -66,7 +64,7 @@ inline Defect check_dbs(int64_t n_starts, int d, const DbInfo *info, int arg) {
     for (int64_t p = 0; p < n_starts; ++p) {
         if (!info[p].id) return defect(-arg, "db is NULL", p);
         if (!info[p].own) return defect(-arg, "db belongs to another context", p);
-        if (info[p].d != d) return defect(-arg, "db has another d than the call", p);
+        if (d >= 0 && info[p].d != d) return defect(-arg, "db has another d than the call", p);  // (d < 0: the call has no d)
     }
     const int64_t rep = first_repeated(n_starts, info);
     if (rep >= 0) return defect(-arg, "db appears twice in the batch", rep);
@@ -83,7 +81,7 @@ inline Defect check_box_jobs(int64_t n_starts, int d, const mrbf_db_box_job *job
     }
     return Defect();
 }
-// mrbf_db_gather_batch: `jobs` is argument `arg` (4).  An index out of range is the job's own failure (gather_job_rc), not the call's
+// mrbf_db_gather_batch: `jobs` is argument `arg` (4).  An index out of range is the job's own failure (index_rc), not the call's
 inline Defect check_gather_jobs(int64_t n_starts, int d, const mrbf_db_gather_job *jobs, const DbInfo *info, int arg) {
     if (Defect D = check_dbs(n_starts, d, info, arg)) return D;
     for (int64_t p = 0; p < n_starts; ++p) {
@@ -93,26 +91,17 @@ inline Defect check_gather_jobs(int64_t n_starts, int d, const mrbf_db_gather_jo
     return Defect();
 }
 constexpr int GATHER_RC_INDEX = -3;  // `indices` is the third field of mrbf_db_gather_job
-inline int gather_job_rc(int64_t n_sites, int64_t n_idx, const int64_t *indices) {
-    for (int64_t i = 0; i < n_idx; ++i)
-        if (indices[i] < 0 || indices[i] >= n_sites) return GATHER_RC_INDEX;
+constexpr int SET_VALUES_RC_INDEX = -4;  // what mrbf_db_set_values returns for an index that is not a row
+// a job's own rc: `rc` when one of its m indices is not a row of the database
+inline int index_rc(int64_t n_sites, int64_t m, const int64_t *indices, int rc) {
+    for (int64_t i = 0; i < m; ++i)
+        if (indices[i] < 0 || indices[i] >= n_sites) return rc;
     return 0;
 }
 
-inline size_t up256(size_t b) { return (b + 255) / 256 * 256; }
-
 // mrbf_db_append_batch / mrbf_db_set_values_batch: `jobs` is argument `arg` (3); the databases of a call may differ in d and k
-inline Defect check_dbs_any_d(int64_t n_starts, const DbInfo *info, int arg) {
-    for (int64_t p = 0; p < n_starts; ++p) {
-        if (!info[p].id) return defect(-arg, "db is NULL", p);
-        if (!info[p].own) return defect(-arg, "db belongs to another context", p);
-    }
-    const int64_t rep = first_repeated(n_starts, info);
-    if (rep >= 0) return defect(-arg, "db appears twice in the batch", rep);
-    return Defect();
-}
 inline Defect check_append_jobs(int64_t n_starts, const mrbf_db_append_job *jobs, const DbInfo *info, int arg) {
-    if (Defect D = check_dbs_any_d(n_starts, info, arg)) return D;
+    if (Defect D = check_dbs(n_starts, -1, info, arg)) return D;
     for (int64_t p = 0; p < n_starts; ++p) {
         if (jobs[p].m < 0 || info[p].n + jobs[p].m > ((int64_t)1 << 31) - ROWS) return defect(-arg, "m is negative or beyond the row limit", p);
         if (jobs[p].m > 0 && !jobs[p].sites) return defect(-arg, "sites is NULL", p);
@@ -120,28 +109,14 @@ inline Defect check_append_jobs(int64_t n_starts, const mrbf_db_append_job *jobs
     return Defect();
 }
 inline Defect check_set_values_jobs(int64_t n_starts, const mrbf_db_set_values_job *jobs, const DbInfo *info, int arg) {
-    if (Defect D = check_dbs_any_d(n_starts, info, arg)) return D;
+    if (Defect D = check_dbs(n_starts, -1, info, arg)) return D;
     for (int64_t p = 0; p < n_starts; ++p) {
         if (jobs[p].m < 0) return defect(-arg, "m is negative", p);
         if (jobs[p].m > 0 && (!jobs[p].indices || !jobs[p].values)) return defect(-arg, "indices or values is NULL", p);
     }
     return Defect();
 }
-constexpr int SET_VALUES_RC_INDEX = -4;  // what mrbf_db_set_values returns for an index that is not a row
-inline int set_values_job_rc(int64_t n_sites, int64_t m, const int64_t *indices) {
-    for (int64_t i = 0; i < m; ++i)
-        if (indices[i] < 0 || indices[i] >= n_sites) return SET_VALUES_RC_INDEX;
-    return 0;
-}
-// the packed upload of either call: the descriptors, then piece after piece (bytes, each a multiple of 256)
-struct PackLayout {
-    size_t at = 0;
-    size_t take(size_t bytes) {
-        const size_t o = at;
-        at += up256(bytes);
-        return o;
-    }
-};
+// (the packed upload of either call is a ByteArena: the descriptors, then the host-side pieces of start after start)
 
 // ---- the layout of a box batch.  Start p owns the rows roff[p] .. roff[p] + n_p - 1 of every per-row array (roff: prefix sums of n_p
 // rounded up to ROWS, so a workgroup's rows belong to one start) and the workgroups roff[p] / ROWS ...
@@ -150,14 +125,16 @@ struct PackLayout {
 //   work buffer (bytes): upload = descriptors | lb, ub, x0 (3 d doubles per start) | masks (a byte per row; the flag kernel turns
 //     them into the candidate flags in place); read-back = mc and first pick (2 x int64 per start) | first rows (d doubles per
 //     start) | candidate indices (an int64 per row); scratch = row norms | candidate norms (a double per row each) | counts |
-//     offsets (an int per workgroup each).
+//     offsets (an int per workgroup each).  The marks of `A` bound the upload and the whole read-back; its head (without the
+//     candidate indices) is back_head_bytes.
 struct BoxLayout {
     std::vector<int64_t> roff;  // n_starts + 1
     int64_t rows = 0, nblk_max = 0;
     size_t view_doubles = 0;
-    size_t oDesc = 0, oBounds = 0, oMask = 0, upload_bytes = 0;
-    size_t oHead = 0, oFirst = 0, oIdx = 0, back_bytes = 0, back_head_bytes = 0;
-    size_t oNorm = 0, oCnorm = 0, oCount = 0, oOffs = 0, total_bytes = 0;
+    ByteArena A;
+    size_t oDesc = 0, oBounds = 0, oMask = 0;
+    size_t oHead = 0, oFirst = 0, oIdx = 0, back_head_bytes = 0;
+    size_t oNorm = 0, oCnorm = 0, oCount = 0, oOffs = 0;
     size_t sites_view(int64_t p, int d) const { return (size_t)roff[(size_t)p] * (size_t)d; }
     size_t shifted_view(int64_t p, int d) const { return (size_t)(rows + roff[(size_t)p]) * (size_t)d; }
 };
@@ -173,33 +150,25 @@ inline BoxLayout box_layout(int64_t n_starts, int d, const int64_t *n_sites, siz
     L.rows = L.roff[N];
     const size_t R = (size_t)L.rows, NB = R / ROWS;
     L.view_doubles = 2 * R * D;
-    size_t at = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = at;
-        at += up256(bytes);
-        return o;
-    };
-    L.oDesc = take(N * desc_bytes), L.oBounds = take(N * 3 * D * sizeof(double)), L.oMask = take(R);
-    L.upload_bytes = at;
-    L.oHead = take(N * 2 * sizeof(int64_t)), L.oFirst = take(N * D * sizeof(double));
-    L.back_head_bytes = at - L.oHead;
-    L.oIdx = take(R * sizeof(int64_t));
-    L.back_bytes = at - L.oHead;
-    L.oNorm = take(R * sizeof(double)), L.oCnorm = take(R * sizeof(double));
-    L.oCount = take(NB * sizeof(int)), L.oOffs = take(NB * sizeof(int));
-    L.total_bytes = at;
+    L.oDesc = L.A.take(N * desc_bytes), L.oBounds = L.A.take(N * 3 * D * sizeof(double)), L.oMask = L.A.take(R);
+    L.oHead = L.A.take(N * 2 * sizeof(int64_t)), L.oFirst = L.A.take(N * D * sizeof(double));
+    L.oIdx = L.A.take(R * sizeof(int64_t));
+    L.oNorm = L.A.take(R * sizeof(double)), L.oCnorm = L.A.take(R * sizeof(double));
+    L.oCount = L.A.take(NB * sizeof(int)), L.oOffs = L.A.take(NB * sizeof(int));
+    L.A.up_end = L.A.back_at = L.oHead, L.A.back_end = L.oNorm, L.back_head_bytes = L.oIdx - L.oHead;
     return L;
 }
 
 // ---- the layout of a gather batch: start p's index list at ioff[p] of the uploaded list (prefix sums of the counts of the jobs that
 // take part: n_idx[p] < 0 marks a job that failed its own check), its site rows at soff[p] and its value rows at voff[p] of the
-// views (doubles, every piece a multiple of 16)
+// views (doubles, every piece a multiple of 16); the upload (bytes, `A`) = descriptors | index lists
 struct GatherLayout {
     std::vector<int64_t> ioff;        // n_starts + 1
     std::vector<size_t> soff, voff;   // n_starts
     int64_t n_idx_max = 0;
     size_t view_doubles = 0;
-    size_t oDesc = 0, oIdx = 0, upload_bytes = 0;
+    ByteArena A;
+    size_t oDesc = 0, oIdx = 0;
 };
 inline GatherLayout gather_layout(int64_t n_starts, int d, const int *k, const int64_t *n_idx, size_t desc_bytes) {
     GatherLayout L;
@@ -215,8 +184,8 @@ inline GatherLayout gather_layout(int64_t n_starts, int d, const int *k, const i
         L.voff[p] = at, at += up16((size_t)m * (size_t)k[p]);
     }
     L.view_doubles = at;
-    L.oDesc = 0, L.oIdx = up256(N * desc_bytes);
-    L.upload_bytes = L.oIdx + up256((size_t)L.ioff[N] * sizeof(int64_t));
+    L.oDesc = L.A.take(N * desc_bytes), L.oIdx = L.A.take((size_t)L.ioff[N] * sizeof(int64_t));
+    L.A.up_end = L.A.total;
     return L;
 }
 

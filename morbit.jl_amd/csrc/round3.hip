@@ -12,8 +12,8 @@
 //   the same two again along the axes, launched only when some job may rebuild: every workgroup reads its start's status and returns
 //   at once unless it asks for the rebuild; they overwrite the same rows.
 // Min and max are order-free, so no result depends on the shape of a reduction; no atomics.
-#include "batch_chain.hpp"  // chain::Staging
 #include "round3_host.hpp"
+#include "select_call.hpp"  // chain::SelectCall: the host scaffold of a batched call
 
 namespace mrbf {
 namespace round3 {
@@ -146,21 +146,12 @@ using namespace mrbf;
 
 extern "C" int32_t mrbf_db_round3_batch(mrbf_ctx *ctx, int64_t n_starts, int32_t d, mrbf_round3_job *jobs, float *ms_total) {
     using namespace round3;
-    if (!ctx) return -1;
-    if (mrbf_dispatch_db_batch(n_starts, d) != MRBF_DISPATCH_DEVICE)
-        return fail(ctx, -2, "mrbf_db_round3_batch: %lld starts, d = %d is outside the batched round 3 (ask mrbf_dispatch_db_batch first)",
-                    (long long)n_starts, d);
-    if (!jobs) return fail(ctx, -4, "jobs is NULL");
+    std::vector<DbInfo> info;
+    MRBF_TRY(db::open_batch(ctx, "mrbf_db_round3_batch", n_starts, d, jobs, 4, info, [&] { return check_jobs(n_starts, d, jobs, info.data(), 4); }));
     const size_t N = (size_t)n_starts, D = (size_t)d;
-    std::vector<DbInfo> info(N);
     std::vector<int64_t> rows(N), caps(N);
-    for (size_t p = 0; p < N; ++p) {
-        const mrbf_db *h = jobs[p].db;
-        info[p] = h ? DbInfo{h, h->d, h->k, h->n, h->ctx == ctx} : DbInfo{nullptr, 0, 0, 0, false};
-        rows[p] = info[p].n, caps[p] = h ? h->cap : 0;
-    }
-    if (Defect df = check_jobs(n_starts, d, jobs, info.data(), 4)) return fail(ctx, df.code, "mrbf_db_round3_batch: %s", df.msg.c_str());
-    (void)hipSetDevice(ctx->device);
+    for (size_t p = 0; p < N; ++p) rows[p] = info[p].n, caps[p] = jobs[p].db->cap;
+    chain::SelectCall call(ctx, ms_total);
     std::vector<char> host_flag(N);
     bool *on_host = reinterpret_cast<bool *>(host_flag.data());
     for (size_t p = 0; p < N; ++p) on_host[p] = jobs[p].dirs != nullptr && !is_device_ptr(jobs[p].dirs);
@@ -168,35 +159,26 @@ extern "C" int32_t mrbf_db_round3_batch(mrbf_ctx *ctx, int64_t n_starts, int32_t
     // ---- the reservation: room for the larger of the first attempt and the rebuild; the kernels write only inside it
     for (size_t p = 0; p < N; ++p)
         if (L.cnt[p].rows() > 0) MRBF_TRY(db_reserve(ctx, jobs[p].db, L.reserve[p]));
-    hipStream_t s = ctx->stream;
-    char *base;
-    MRBF_TRY(get_buf(ctx, S_DB_WS, L.total_bytes, &base));
-    PinGuard pin(ctx);
     // ---- one upload: descriptors, x | lb | ub, the host-side direction blocks
-    chain::Staging up_block(ctx, L.upload_bytes / sizeof(double));
-    char *const up_p = reinterpret_cast<char *>(up_block.p);
-    std::memset(up_p, 0, L.oDirs);
-    Desc *hdesc = reinterpret_cast<Desc *>(up_p + L.oDesc);
+    MRBF_TRY(call.open(S_DB_WS, L.A, L.oDirs));
+    Desc *hdesc = call.host<Desc>(L.oDesc);
     bool any_rebuild = false;
     for (size_t p = 0; p < N; ++p) {
         const mrbf_round3_job &jb = jobs[p];
         const Counts &c = L.cnt[p];
         Desc &h = hdesc[p];
         h.S = jb.db->sites + (size_t)rows[p] * D, h.V = jb.db->values + (size_t)rows[p] * (size_t)info[p].k;
-        h.xlu = reinterpret_cast<const double *>(base + L.oXlu) + p * 3 * D;
-        h.stage = reinterpret_cast<double *>(base + L.oStage) + (size_t)L.roff[p] * D;
-        h.fail = reinterpret_cast<int *>(base + L.oFail) + L.roff[p];
-        h.out = reinterpret_cast<int *>(base + L.oOut) + 4 * p;
+        h.xlu = call.dev<const double>(L.oXlu) + p * 3 * D, h.stage = call.dev<double>(L.oStage) + (size_t)L.roff[p] * D;
+        h.fail = call.dev<int>(L.oFail) + L.roff[p], h.out = call.dev<int>(L.oOut) + 4 * p;
         h.pivot = jb.pivot_val;
         h.k = info[p].k, h.n1 = c.n1, h.n2 = c.n2, h.n_dirs = c.n_dirs, h.reversed = jb.reversed != 0, h.n_missing = jb.n_missing;
         h.improve = jb.mode == MRBF_R3_IMPROVE, h.can_rebuild = c.can_rebuild;
-        double *b = reinterpret_cast<double *>(up_p + L.oXlu) + p * 3 * D;
+        double *b = call.host<double>(L.oXlu) + p * 3 * D;
         std::memcpy(b, jb.x, D * sizeof(double)), std::memcpy(b + D, jb.lb, D * sizeof(double)), std::memcpy(b + 2 * D, jb.ub, D * sizeof(double));
         if (c.rc == 0 && jb.dirs && c.n1 > 0) {
             if (on_host[p]) {  // the n1 columns the first attempt reads
-                double *blk = reinterpret_cast<double *>(up_p + L.oDirs) + L.doff[p];
-                std::memcpy(blk, jb.dirs + (size_t)L.first_col(p, h.reversed) * D, (size_t)c.n1 * D * sizeof(double));
-                h.dirs = reinterpret_cast<const double *>(base + L.oDirs) + L.doff[p], h.ncols = c.n1;
+                std::memcpy(call.host<double>(L.oDirs) + L.doff[p], jb.dirs + (size_t)L.first_col(p, h.reversed) * D, (size_t)c.n1 * D * sizeof(double));
+                h.dirs = call.dev<const double>(L.oDirs) + L.doff[p], h.ncols = c.n1;
             } else {
                 h.dirs = jb.dirs, h.ncols = c.n_dirs;
             }
@@ -204,25 +186,18 @@ extern "C" int32_t mrbf_db_round3_batch(mrbf_ctx *ctx, int64_t n_starts, int32_t
         h.vec = (d & 1) == 0 && (reinterpret_cast<uintptr_t>(h.dirs) & 15) == 0;
         any_rebuild = any_rebuild || (c.rc == 0 && c.can_rebuild);
     }
-    hipEvent_t e0 = ctx->ev[0], e1 = ctx->ev[1];
-    if (ms_total) MRBF_HIP(ctx, hipEventRecord(e0, s));
-    MRBF_HIP(ctx, hipMemcpyAsync(base, up_p, L.upload_bytes, hipMemcpyHostToDevice, s));
-    const Desc *ddesc = reinterpret_cast<const Desc *>(base + L.oDesc);
+    MRBF_TRY(call.begin());
+    MRBF_TRY(call.upload());
+    const Desc *ddesc = call.dev<const Desc>(L.oDesc);
     for (int pass = 0; pass < (any_rebuild ? 2 : 1); ++pass) {
         const int rmax = pass ? L.rows_max2 : L.rows_max1;
-        if (rmax > 0) hipLaunchKernelGGL(r3_dir_kernel, dim3((unsigned)((rmax + 3) / 4), (unsigned)N), dim3(NT), 0, s, ddesc, d, pass);
-        hipLaunchKernelGGL(r3_decide_kernel, dim3((unsigned)N), dim3(NT), 0, s, ddesc, d, pass);
+        if (rmax > 0) hipLaunchKernelGGL(r3_dir_kernel, dim3((unsigned)((rmax + 3) / 4), (unsigned)N), dim3(NT), 0, call.s, ddesc, d, pass);
+        hipLaunchKernelGGL(r3_decide_kernel, dim3((unsigned)N), dim3(NT), 0, call.s, ddesc, d, pass);
     }
-    MRBF_HIP(ctx, hipGetLastError());
     // ---- one read-back: status, n_new, fully_linear per start, and the staging rows
-    chain::Staging hb_block(ctx, L.back_bytes / sizeof(double));
-    char *const hb_p = reinterpret_cast<char *>(hb_block.p);
-    MRBF_HIP(ctx, hipMemcpyAsync(hb_p, base + L.oOut, L.back_bytes, hipMemcpyDeviceToHost, s));
-    if (ms_total) MRBF_HIP(ctx, hipEventRecord(e1, s));
-    MRBF_HIP(ctx, hipStreamSynchronize(s));
-    if (ms_total) MRBF_HIP(ctx, hipEventElapsedTime(ms_total, e0, e1));
-    const int *out = reinterpret_cast<const int *>(hb_p);
-    const double *stage = reinterpret_cast<const double *>(hb_p + (L.oStage - L.oOut));
+    MRBF_TRY(call.finish(L.A.back_bytes()));
+    const int *out = reinterpret_cast<const int *>(call.back.p);
+    const double *stage = reinterpret_cast<const double *>(call.back.p + (L.oStage - L.oOut));
     for (size_t p = 0; p < N; ++p) {
         mrbf_round3_job &jb = jobs[p];
         const Counts &c = L.cnt[p];

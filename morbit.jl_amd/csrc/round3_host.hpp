@@ -8,10 +8,7 @@
 namespace mrbf {
 namespace round3 {
 
-using db::DbInfo;
-using db::Defect;
-using db::defect;
-using db::up256;
+using namespace db;  // DbInfo, Defect, defect, check_dbs, grow_capacity
 
 // ---- one start's row counts (RbfModel.jl:274, :634-637, :699-732)
 struct Counts {
@@ -65,9 +62,8 @@ struct Layout {
     std::vector<int64_t> reserve, capacity;  // n_starts
     std::vector<int64_t> roff, doff;      // n_starts + 1
     int rows_max1 = 0, rows_max2 = 0;     // grid of the first attempt / of the rebuild
-    size_t oDesc = 0, oXlu = 0, oDirs = 0, upload_bytes = 0;
-    size_t oOut = 0, oStage = 0, back_bytes = 0;
-    size_t oFail = 0, total_bytes = 0;
+    ByteArena A;                          // its marks bound the upload and the read-back
+    size_t oDesc = 0, oXlu = 0, oDirs = 0, oOut = 0, oStage = 0, oFail = 0;
     // first uploaded column of start p's `dirs` (the kernels index the uploaded block from 0)
     int first_col(size_t p, int reversed) const { return reversed ? cnt[p].n_dirs - cnt[p].n1 : 0; }
 };
@@ -87,18 +83,10 @@ inline Layout layout(int64_t n_starts, int d, const mrbf_round3_job *jobs, const
         L.doff[p + 1] = L.doff[p] + (up + 1) / 2 * 2;  // (16-byte pieces)
         if (c.rc == 0) L.rows_max1 = std::max(L.rows_max1, c.n1), L.rows_max2 = std::max(L.rows_max2, c.n2);
     }
-    size_t at = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = at;
-        at += up256(bytes);
-        return o;
-    };
-    L.oDesc = take(N * desc_bytes), L.oXlu = take(N * 3 * D * sizeof(double)), L.oDirs = take((size_t)L.doff[N] * sizeof(double));
-    L.upload_bytes = at;
-    L.oOut = take(N * 4 * sizeof(int)), L.oStage = take((size_t)L.roff[N] * D * sizeof(double));
-    L.back_bytes = at - L.oOut;
-    L.oFail = take((size_t)L.roff[N] * sizeof(int));
-    L.total_bytes = at;
+    L.oDesc = L.A.take(N * desc_bytes), L.oXlu = L.A.take(N * 3 * D * sizeof(double)), L.oDirs = L.A.take((size_t)L.doff[N] * sizeof(double));
+    L.oOut = L.A.take(N * 4 * sizeof(int)), L.oStage = L.A.take((size_t)L.roff[N] * D * sizeof(double));
+    L.oFail = L.A.take((size_t)L.roff[N] * sizeof(int));
+    L.A.up_end = L.A.back_at = L.oOut, L.A.back_end = L.oFail;
     return L;
 }
 

@@ -31,12 +31,12 @@
 // The polynomial rows follow poly_rows_kernel's convention (round4.hip: [1, x_1 .. x_d] cut to q terms), restated here so that
 // round4.hip stays as it is.
 #include "radial.hpp"
+#include "round4_host.hpp"  // the small range; the validation, routing and arena of mrbf_round4_batch
+#include "select_call.hpp"  // chain::SelectCall: the host scaffold of a batched call
 
 namespace mrbf {
 namespace r4s {
 
-constexpr int R4S_MAX_D = 128, R4S_MAX_N0 = 256, R4S_MAX_MC = 4096, R4S_MAX_ACC = 256;  // the small range (include/mrbf.h)
-constexpr size_t R4S_ARENA_MAX = (size_t)2 << 30;  // starts beyond this much workspace take the single call
 constexpr int NT = 256;
 
 #define R4S_GLOBAL __attribute__((address_space(1)))
@@ -289,145 +289,74 @@ extern "C" int32_t mrbf_round4_batch(mrbf_ctx *ctx, int64_t n_starts, int32_t d,
                     (long long)n_starts, d);
     if (!jobs) return fail(ctx, -4, "jobs is NULL");
     const size_t N = (size_t)n_starts, D = (size_t)d;
-    enum { DONE = 0, BATCHED = 1, SINGLE = 2 };
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    std::vector<int> route(N), caps(N), qs(N);
-    std::vector<size_t> base_off(N);
-    size_t nb_ = 0, used = 0;
-    int cap_max = 0, q_max = 0;
-    int64_t mc_max = 0, n0_max = 0;
-    for (size_t p = 0; p < N; ++p) {
-        const mrbf_round4_job &jb = jobs[p];
-        if (jb.n0 < 1) return fail(ctx, -4, "jobs[%zu].n0 = %lld", p, (long long)jb.n0);
-        if (jb.mc < 0) return fail(ctx, -4, "jobs[%zu].mc = %lld", p, (long long)jb.mc);
-        if (!jb.start_sites) return fail(ctx, -4, "jobs[%zu].start_sites is NULL", p);
-        if (jb.mc > 0 && !jb.cand_sites) return fail(ctx, -4, "jobs[%zu].cand_sites is NULL", p);
-        if (jb.kernel_id < 0 || jb.kernel_id > 4) return fail(ctx, -4, "jobs[%zu].kernel_id out of range", p);
-        if (jb.poly_deg < -1 || jb.poly_deg > 1) return fail(ctx, -4, "jobs[%zu].poly_deg must be -1, 0 or 1", p);
-        const int q = poly_dim(d, jb.poly_deg);
-        const int64_t mp = jb.max_points <= 0 ? (int64_t)(d + 1) * (d + 2) / 2 : jb.max_points;  // RbfModel.jl:356
-        const int64_t cap = std::min<int64_t>(jb.mc, mp - jb.n0);
-        if (cap > 0 && !jb.accepted_out) return fail(ctx, -4, "jobs[%zu].accepted_out is NULL", p);
-        qs[p] = q;
-        if (jb.n0 < q) {
-            route[p] = SINGLE;  // (mrbf_round4 refuses it with its own code)
-        } else if (jb.mc == 0 || cap <= 0) {
-            route[p] = DONE;  // nothing to select (RbfModel.jl:368)
-        } else if (d <= R4S_MAX_D && jb.n0 <= R4S_MAX_N0 && jb.mc <= R4S_MAX_MC && cap <= R4S_MAX_ACC) {
-            const size_t n0 = (size_t)jb.n0, mc = (size_t)jb.mc, Q = (size_t)q, C = (size_t)cap;
-            const size_t need = up(n0 * D * 8) + 2 * up(mc * D * 8) + up(std::max<size_t>(Q * Q, 1) * 8) + up(n0 * n0 * 8) + up(std::max<size_t>(Q * mc, 1) * 8) +
-                                2 * up(n0 * mc * 8) + (q > 0 ? 2 : 1) * up(C * mc * 8);
-            if (used + need > R4S_ARENA_MAX) {
-                route[p] = SINGLE;
-            } else {
-                route[p] = BATCHED;
-                base_off[p] = used;
-                used += need;
-                caps[p] = (int)cap;
-                ++nb_;
-                cap_max = std::max(cap_max, (int)cap), q_max = std::max(q_max, q);
-                mc_max = std::max(mc_max, jb.mc), n0_max = std::max(n0_max, jb.n0);
-            }
-        } else {
-            route[p] = SINGLE;
-        }
-    }
+    const Plan P = plan(n_starts, d, jobs, sizeof(Job), 4);
+    if (P.bad) return fail(ctx, P.bad.code, "%s", P.bad.msg.c_str());
     for (size_t p = 0; p < N; ++p) jobs[p].n_accepted = 0, jobs[p].rc = 0;
     if (ms_total) *ms_total = 0.f;
-    (void)hipSetDevice(ctx->device);
-    hipStream_t s = ctx->stream;
-    std::vector<int> hback_v;
-    const int *hback = nullptr;
-    const size_t ostride = (size_t)cap_max + 2;  // output words of a start: count, flag, list
-    if (nb_ > 0) {
-        PinGuard pin(ctx);
+    std::vector<int> hback;
+    if (P.nb > 0) {
+        // (a scope of its own: guard released, read-back copied out of the pinned block before the single calls below arm it again)
+        chain::SelectCall call(ctx, ms_total);
+        hipStream_t s = call.s;
         // ---- the arena: output words | descriptors | the starts' slices
-        const size_t bOut = up(nb_ * ostride * sizeof(int)), bDesc = up(nb_ * sizeof(Job));
-        char *base;
-        MRBF_TRY(get_buf(ctx, S_R4_BATCH, bOut + bDesc + used, &base));
-        int *dOut = reinterpret_cast<int *>(base);
-        Job *dDesc = reinterpret_cast<Job *>(base + bOut);
-        char *slices = base + bOut + bDesc;
-        std::vector<char> hdesc_v;
-        char *hd = bDesc <= ((size_t)4 << 20) ? pin_take(ctx, bDesc) : nullptr;
-        if (!hd) {
-            hdesc_v.resize(bDesc);
-            hd = hdesc_v.data();
-        }
-        Job *hdesc = reinterpret_cast<Job *>(hd);
-        hipEvent_t e0 = ctx->ev[0], e1 = ctx->ev[1];
-        if (ms_total) MRBF_HIP(ctx, hipEventRecord(e0, s));
-        MRBF_HIP(ctx, hipMemsetAsync(dOut, 0, bOut, s));
+        MRBF_TRY(call.open(S_R4_BATCH, P.A, 0));
+        int *dOut = call.dev<int>(P.oOut);
+        const Job *dDesc = call.dev<const Job>(P.oDesc);
+        Job *hdesc = call.host<Job>(P.oDesc);
+        MRBF_TRY(call.begin());
+        MRBF_HIP(ctx, hipMemsetAsync(dOut, 0, P.A.back_bytes(), s));
         size_t k = 0;
         for (size_t p = 0; p < N; ++p) {
-            if (route[p] != BATCHED) continue;
+            const Start &st = P.st[p];
+            if (st.route != BATCHED) continue;
             const mrbf_round4_job &jb = jobs[p];
-            const size_t n0 = (size_t)jb.n0, mc = (size_t)jb.mc, Q = (size_t)qs[p], C = (size_t)caps[p];
-            char *c = slices + base_off[p];
-            auto carve = [&](size_t bytes) {
-                double *r = reinterpret_cast<double *>(c);
-                c += up(bytes);
-                return r;
-            };
+            const size_t n0 = (size_t)jb.n0, mc = (size_t)jb.mc;
+            auto slice = [&](size_t off) { return call.dev<double>(P.oSlices + off); };
             Job &h = hdesc[k];
-            h.X0 = carve(n0 * D * 8), h.Xc = carve(mc * D * 8), h.XcT = carve(mc * D * 8), h.Ginv = carve(std::max<size_t>(Q * Q, 1) * 8);
-            h.Phi00 = carve(n0 * n0 * 8), h.T = carve(std::max<size_t>(Q * mc, 1) * 8), h.Lam = carve(n0 * mc * 8), h.U = carve(n0 * mc * 8);
-            h.RK = carve(C * mc * 8), h.RH = Q > 0 ? carve(C * mc * 8) : h.RK;
-            h.out = dOut + k * ostride;
+            h.X0 = slice(st.X0), h.Xc = slice(st.Xc), h.XcT = slice(st.XcT), h.Ginv = slice(st.Ginv), h.Phi00 = slice(st.Phi00);
+            h.T = slice(st.T), h.Lam = slice(st.Lam), h.U = slice(st.U), h.RK = slice(st.RK), h.RH = slice(st.RH);
+            h.out = dOut + k * P.ostride;
             h.kp = make_kp(jb.kernel_id, jb.a, jb.b);
             const double th = jb.theta_pivot_cholesky;
             h.thr = (th * th) * (th * th);
-            h.n0 = (int)n0, h.mc = (int)mc, h.q = (int)Q, h.cap = (int)C;
+            h.n0 = (int)n0, h.mc = (int)mc, h.q = st.q, h.cap = st.cap;
             // the sites, straight from where they are (host or device)
             MRBF_HIP(ctx, hipMemcpyAsync(h.X0, jb.start_sites, n0 * D * 8, hipMemcpyDefault, s));
             MRBF_HIP(ctx, hipMemcpyAsync(h.Xc, jb.cand_sites, mc * D * 8, hipMemcpyDefault, s));
             ++k;
         }
-        MRBF_HIP(ctx, hipMemcpyAsync(dDesc, hd, nb_ * sizeof(Job), hipMemcpyHostToDevice, s));
-        const unsigned NB = (unsigned)nb_;
+        MRBF_TRY(call.upload());
+        const unsigned NB = (unsigned)P.nb;
         auto gx = [](int64_t elems) { return (unsigned)std::min<int64_t>(std::max<int64_t>((elems + NT - 1) / NT, 1), 4096); };
-        const size_t shm_g = ((size_t)q_max * q_max + 3 * (size_t)std::max(q_max, 1)) * sizeof(double);
-        const size_t shm_w = (2 * (size_t)mc_max + D + 2 * (size_t)n0_max + (size_t)std::max(q_max, 1) + 2 * (size_t)cap_max) * sizeof(double);
+        const size_t shm_g = ((size_t)P.q_max * P.q_max + 3 * (size_t)std::max(P.q_max, 1)) * sizeof(double);
+        const size_t shm_w = (2 * (size_t)P.mc_max + D + 2 * (size_t)P.n0_max + (size_t)std::max(P.q_max, 1) + 2 * (size_t)P.cap_max) * sizeof(double);
         MRBF_HIP(ctx, hipFuncSetAttribute((const void *)r4s_ginv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_g));
         MRBF_HIP(ctx, hipFuncSetAttribute((const void *)r4s_walk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_w));
         hipLaunchKernelGGL(r4s_ginv_kernel, dim3(NB), dim3(NT), shm_g, s, dDesc, d);
-        hipLaunchKernelGGL(r4s_stage_kernel, dim3(gx(std::max<int64_t>(n0_max * n0_max, mc_max * d)), NB), dim3(NT), 0, s, dDesc, d);
-        hipLaunchKernelGGL(r4s_tail_kernel, dim3(gx((int64_t)q_max * mc_max), NB), dim3(NT), 0, s, dDesc, d);
-        hipLaunchKernelGGL(r4s_lam_kernel, dim3(gx(n0_max * mc_max), NB), dim3(NT), 0, s, dDesc, d);
-        hipLaunchKernelGGL(r4s_u_kernel, dim3(gx(n0_max * mc_max), NB), dim3(NT), 0, s, dDesc);
+        hipLaunchKernelGGL(r4s_stage_kernel, dim3(gx(std::max<int64_t>(P.n0_max * P.n0_max, P.mc_max * d)), NB), dim3(NT), 0, s, dDesc, d);
+        hipLaunchKernelGGL(r4s_tail_kernel, dim3(gx((int64_t)P.q_max * P.mc_max), NB), dim3(NT), 0, s, dDesc, d);
+        hipLaunchKernelGGL(r4s_lam_kernel, dim3(gx(P.n0_max * P.mc_max), NB), dim3(NT), 0, s, dDesc, d);
+        hipLaunchKernelGGL(r4s_u_kernel, dim3(gx(P.n0_max * P.mc_max), NB), dim3(NT), 0, s, dDesc);
         hipLaunchKernelGGL(r4s_walk_kernel, dim3(NB), dim3(NT), shm_w, s, dDesc, d);
-        MRBF_HIP(ctx, hipGetLastError());
         // ---- one read-back: counts, flags and lists of every start
-        const size_t back = nb_ * ostride * sizeof(int);
-        int *hb = reinterpret_cast<int *>(back <= ((size_t)4 << 20) ? pin_take(ctx, back) : nullptr);
-        if (!hb) {
-            hback_v.resize(nb_ * ostride);
-            hb = hback_v.data();
-        }
-        MRBF_HIP(ctx, hipMemcpyAsync(hb, dOut, back, hipMemcpyDeviceToHost, s));
-        if (ms_total) MRBF_HIP(ctx, hipEventRecord(e1, s));
-        MRBF_HIP(ctx, hipStreamSynchronize(s));
-        if (ms_total) MRBF_HIP(ctx, hipEventElapsedTime(ms_total, e0, e1));
-        if (hback_v.empty()) {  // (the pinned block is the next entry's: keep a copy)
-            hback_v.assign(hb, hb + nb_ * ostride);
-        }
-        hback = hback_v.data();
+        MRBF_TRY(call.finish(P.nb * P.ostride * sizeof(int)));
+        hback.assign(reinterpret_cast<const int *>(call.back.p), reinterpret_cast<const int *>(call.back.p) + P.nb * P.ostride);
     }
     // ---- results; starts outside the small range, and starts whose start set the batched chain found rank deficient, take the single
     // call here, after the chain, without a kept state: one such start does not fail the others
     size_t k = 0;
     for (size_t p = 0; p < N; ++p) {
         mrbf_round4_job &jb = jobs[p];
-        if (route[p] == BATCHED) {
-            const int *o = hback + k * ostride;
+        if (P.st[p].route == BATCHED) {
+            const int *o = hback.data() + k * P.ostride;
             ++k;
             if (o[1] == 0) {
-                const int na = std::min(o[0], caps[p]);
+                const int na = std::min(o[0], P.st[p].cap);
                 for (int i = 0; i < na; ++i) jb.accepted_out[i] = o[2 + i];
                 jb.n_accepted = na;
                 continue;
             }
-        } else if (route[p] == DONE) {
+        } else if (P.st[p].route == DONE) {
             continue;
         }
         int32_t na = 0;

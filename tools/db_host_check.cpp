@@ -128,7 +128,7 @@ static void check_jobs() {
                 for (int i = 0, c = code; i < 3; ++i, c /= 5) l[i] = c % 5 - 1;
                 for (int i = 0; i < len; ++i) bad = bad || l[i] < 0 || l[i] >= n;
                 ++g_cases;
-                CHECK(gather_job_rc(n, len, l) == (bad ? -3 : 0));
+                CHECK(index_rc(n, len, l, GATHER_RC_INDEX) == (bad ? -3 : 0));
             }
 }
 
@@ -160,12 +160,12 @@ static void check_layouts() {
                 CHECK(L.rows == L.roff[ns] && L.nblk_max == nblk_max);
                 const size_t R = (size_t)L.rows, NB = R / ROWS;
                 // the pieces in order, each with room for what it holds
-                const size_t at[] = {L.oDesc, L.oBounds, L.oMask, L.oHead, L.oFirst, L.oIdx, L.oNorm, L.oCnorm, L.oCount, L.oOffs, L.total_bytes};
+                const size_t at[] = {L.oDesc, L.oBounds, L.oMask, L.oHead, L.oFirst, L.oIdx, L.oNorm, L.oCnorm, L.oCount, L.oOffs, L.A.total};
                 const size_t need[] = {ns * desc, (size_t)ns * 3 * d * 8, R, (size_t)ns * 16, (size_t)ns * d * 8, R * 8, R * 8, R * 8, NB * 4, NB * 4};
                 CHECK(at[0] == 0);
                 for (int i = 0; i < 10; ++i) CHECK(at[i] % 256 == 0 && at[i] + need[i] <= at[i + 1]);
-                CHECK(L.upload_bytes == L.oHead);
-                CHECK(L.oHead + L.back_head_bytes == L.oIdx && L.oHead + L.back_bytes == L.oNorm);
+                CHECK(L.A.upload_bytes() == L.oHead);
+                CHECK(L.oHead + L.back_head_bytes == L.oIdx && L.oHead + L.A.back_bytes() == L.oNorm);
             }
         }
     // gather: a job that failed its own check (count -1) takes no room; the others' index lists follow each other, their views do not
@@ -189,7 +189,7 @@ static void check_layouts() {
                 end = L.voff[p] + (size_t)mm * k[p];
             }
             CHECK(L.view_doubles >= end && L.n_idx_max == n_max);
-            CHECK(L.oIdx >= 3 * 56 && L.oIdx % 256 == 0 && L.upload_bytes >= L.oIdx + (size_t)L.ioff[3] * 8);
+            CHECK(L.oIdx >= 3 * 56 && L.oIdx % 256 == 0 && L.A.upload_bytes() >= L.oIdx + (size_t)L.ioff[3] * 8);
         }
 }
 

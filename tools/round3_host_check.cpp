@@ -170,10 +170,10 @@ static void check_layout() {
                 CHECK(disjoint(stage) && disjoint(flags) && disjoint(dirs));
                 const size_t R = (size_t)L.roff[(size_t)n];
                 CHECK(L.oDesc == 0 && L.oXlu >= (size_t)n * desc_bytes && L.oDirs >= L.oXlu + (size_t)n * 3 * d * 8);
-                CHECK(L.upload_bytes >= L.oDirs + (size_t)L.doff[(size_t)n] * 8 && L.oOut == L.upload_bytes);
-                CHECK(L.oStage >= L.oOut + (size_t)n * 16 && L.oFail >= L.oStage + R * d * 8 && L.back_bytes == L.oFail - L.oOut);
-                CHECK(L.total_bytes >= L.oFail + R * 4);
-                for (size_t o : {L.oDesc, L.oXlu, L.oDirs, L.upload_bytes, L.oOut, L.oStage, L.oFail, L.total_bytes}) CHECK(o % 256 == 0);
+                CHECK(L.A.upload_bytes() >= L.oDirs + (size_t)L.doff[(size_t)n] * 8 && L.oOut == L.A.upload_bytes());
+                CHECK(L.oStage >= L.oOut + (size_t)n * 16 && L.oFail >= L.oStage + R * d * 8 && L.A.back_bytes() == L.oFail - L.oOut);
+                CHECK(L.A.total >= L.oFail + R * 4);
+                for (size_t o : {L.oDesc, L.oXlu, L.oDirs, L.A.upload_bytes(), L.oOut, L.oStage, L.oFail, L.A.total}) CHECK(o % 256 == 0);
             }
 }
 
