@@ -553,6 +553,7 @@ static bool batch_takes(const mrbf_ctx *ctx, int64_t n, int d, int k, int kernel
     int path = MRBF_PATH_LU;
     if (kernel_id >= 0 && kernel_id <= 4 && n > q && poly_deg >= -1 && poly_deg <= 1 && cpd_order(kernel_id, a, b) <= poly_deg + 1)
         path = q > 0 ? MRBF_PATH_PROJ_CHOL : MRBF_PATH_CHOL;
+    if (path != MRBF_PATH_LU && kp_nonsmooth(make_kp(kernel_id, a, b))) return false;  // as fit_model: the launch chain, difference-form assembly
     return ctx->force_path == 0 && ctx->eval_impl != 1 && small_fit_applies(ctx, n, d, k, q, path);
 }
 

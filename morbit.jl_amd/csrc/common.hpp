@@ -30,6 +30,10 @@ struct KP {
     double phi0;  // phi(0) = diagonal of Phi
 };
 KP make_kp(int kid, double a, double b);
+// phi' (cubic, beta = 1: phi = -rho) or psi = phi' / rho (thin plate spline, k = 1: psi = 2 log rho + 1) is unbounded at rho = 0: a
+// rounding error of rho^2 is magnified without limit there, so these two take the difference-form kernels for every distance
+// (DESIGN.md "Distances near a centre"); every other parameterisation keeps the GEMM form
+inline bool kp_nonsmooth(const KP &p) { return (p.kid == MRBF_CUBIC && p.a == 1.0) || (p.kid == MRBF_THIN_PLATE_SPLINE && p.ik == 1); }
 int cpd_order(int kid, double a, double b);
 inline int poly_dim(int d, int deg) { return deg < 0 ? 0 : (deg == 0 ? 1 : d + 1); }
 

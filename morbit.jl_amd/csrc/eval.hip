@@ -167,12 +167,14 @@ static int eval_gemm_pipeline(mrbf_ctx *ctx, const mrbf_model *M, int64_t m, con
 
 int eval_fused(mrbf_ctx *ctx, const mrbf_model *M, int64_t m, const double *X, double *vals, double *jac,
                mrbf_eval_info *info, EvalHints hints);  // eval_fused.hip
+int eval_diff(mrbf_ctx *ctx, const mrbf_model *M, int64_t m, const double *X, double *vals, double *jac);  // eval_fused.hip
 
 int eval_model(mrbf_ctx *ctx, const mrbf_model *M, int64_t m, const double *Xdev, double *vals_dev, double *jac_dev,
                mrbf_eval_info *info, EvalHints hints) {
     if (info) std::memset(info, 0, sizeof(*info));
     if (m <= 0) return 0;
     if (M->n == 0) return fail(ctx, -2, "model has no centres");
+    if (kp_nonsmooth(M->kp)) return eval_diff(ctx, M, m, Xdev, vals_dev, jac_dev);  // any d: difference form (no times in info)
     if (ctx->eval_impl != 1 && (M->dpad == 64 || M->dpad == 128 || M->dpad == 256)) return eval_fused(ctx, M, m, Xdev, vals_dev, jac_dev, info, hints);
     return eval_gemm_pipeline(ctx, M, m, Xdev, vals_dev, jac_dev, info);
 }

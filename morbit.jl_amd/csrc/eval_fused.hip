@@ -924,10 +924,120 @@ int center_pad_batch(mrbf_ctx *ctx, const EvalDesc *dev_descs, int count, int64_
     return 0;
 }
 
+// ---- difference form: the evaluation of the two radial functions that are not smooth at 0 (kp_nonsmooth) ---------------------------
+// s = sum_t (x_t - c_t)^2 on the coordinates as given -- the difference of two nearby doubles is exact, where the centred coordinates
+// each carry a rounding of their own -- and the Jacobian term as w psi (x - c), not through (sum a) x - sum a c.  Any d, n, k; one
+// workgroup per query point (blockIdx.y = problem of a batch), the centres in chunks of DIFF_CH:
+//   phase A  a wave per centre: the lanes share the coordinates, the sum meets in a fixed shuffle order, phi and psi go to LDS
+//   phase B  a thread per output (values) and per Jacobian entry: the chunk's terms added in the order of the centres onto the entry,
+//            which only this thread touches (it starts as the polynomial tail)
+// The values do not depend on whether Jacobians are asked for.  None of this is on a measured path: plain code, no matrix cores.
+constexpr int DIFF_CH = 256;
+
+__device__ __forceinline__ void nonsmooth_phi_psi(const KP &p, double s, double &phi, double &psi) {
+    if (s <= 0.0) {  // the coincident centre: phi(0) = 0, and the term of the gradient has no limit -> 0 (oracle: dphi_over_rho)
+        phi = 0.0;
+        psi = 0.0;
+    } else if (p.kid == MRBF_CUBIC) {  // beta = 1: phi = sgn rho, psi = sgn / rho
+        const double r = sqrt(s);
+        phi = p.sgn * r;
+        psi = p.sgn / r;
+    } else {  // thin plate spline, k = 1: phi = sgn rho^2 log rho, psi = sgn (2 log rho + 1)
+        const double lg = log(s);
+        phi = p.sgn * s * (0.5 * lg);
+        psi = p.sgn * (lg + 1.0);
+    }
+}
+
+__global__ __launch_bounds__(256) void eval_diff_kernel(EvalDesc one, const EvalDesc *__restrict__ many, int want_jac) {
+    extern __shared__ double dsm[];
+    const EvalDesc &E = many ? many[blockIdx.y] : one;
+    const int64_t p = blockIdx.x, n = E.n, npad = E.npad;
+    if (p >= E.m) return;
+    const int d = E.d, k = E.k, q = E.q;
+    const double *__restrict__ C = E.C, *__restrict__ Wc = E.Wc, *__restrict__ lam = E.lam;
+    double *__restrict__ vals = E.vals, *__restrict__ jac = want_jac ? E.jac : nullptr;
+    const KP kp = E.kp;
+    double *xs = dsm, *ph = dsm + d, *ps = ph + DIFF_CH;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int t = tid; t < d; t += 256) xs[t] = E.X[p * d + t];
+    __syncthreads();
+    // the polynomial tail: p_l(x) = lam_0l + sum_t lam_(t+1)l x_t, grad p_l = lam_(t+1)l
+    if (vals)
+        for (int l = tid; l < k; l += 256) {
+            double v = q > 0 ? lam[l] : 0.0;
+            if (q > 1)
+                for (int t = 0; t < d; ++t) v = fma(lam[(int64_t)(t + 1) * k + l], xs[t], v);
+            vals[p * k + l] = v;
+        }
+    if (jac)
+        for (int64_t e = tid; e < (int64_t)k * d; e += 256) jac[p * (int64_t)k * d + e] = q > 1 ? lam[k + e] : 0.0;  // e = t k + l
+    for (int64_t c0 = 0; c0 < n; c0 += DIFF_CH) {
+        const int nc = (int)min((int64_t)DIFF_CH, n - c0);
+        __syncthreads();  // the previous chunk's phi / psi are used up
+        for (int ci = wave; ci < nc; ci += 4) {
+            const double *cr = C + (c0 + ci) * d;
+            double s = 0.0;
+            for (int t = lane; t < d; t += 64) {
+                const double df = xs[t] - cr[t];
+                s = fma(df, df, s);
+            }
+            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+            if (lane == 0) nonsmooth_phi_psi(kp, s, ph[ci], ps[ci]);
+        }
+        __syncthreads();
+        if (vals)
+            for (int l = tid; l < k; l += 256) {
+                const double *w = Wc + (int64_t)l * npad + c0;
+                double v = vals[p * k + l];
+                for (int ci = 0; ci < nc; ++ci) v = fma(w[ci], ph[ci], v);
+                vals[p * k + l] = v;
+            }
+        if (jac)
+            for (int64_t e = tid; e < (int64_t)k * d; e += 256) {
+                const int t = (int)(e / k), l = (int)(e % k);
+                const double *w = Wc + (int64_t)l * npad + c0;
+                const double x = xs[t];
+                double g = jac[p * (int64_t)k * d + e];
+                for (int ci = 0; ci < nc; ++ci) g = fma(w[ci] * ps[ci], x - C[(c0 + ci) * d + t], g);
+                jac[p * (int64_t)k * d + e] = g;
+            }
+    }
+}
+
+// `count` descriptors (count == 1 and many == nullptr: `one` by value), at most max_m query points and max_d coordinates each
+static int launch_eval_diff(mrbf_ctx *ctx, int64_t max_m, int max_d, const EvalDesc &one, const EvalDesc *many, int count, bool want_jac) {
+    if (max_m <= 0 || count <= 0) return 0;
+    const size_t lds = ((size_t)max_d + 2 * DIFF_CH) * sizeof(double);
+    hipLaunchKernelGGL(eval_diff_kernel, dim3((unsigned)max_m, (unsigned)count), dim3(256), lds, ctx->stream, one, many, want_jac ? 1 : 0);
+    MRBF_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
+int eval_diff(mrbf_ctx *ctx, const mrbf_model *M, int64_t m, const double *X, double *vals, double *jac) {
+    EvalDesc E;
+    std::memset(&E, 0, sizeof(E));
+    eval_desc_model(E, M, m, 1);
+    E.X = X;
+    E.vals = vals;
+    E.jac = jac;
+    return launch_eval_diff(ctx, m, M->d, E, nullptr, 1, jac != nullptr);
+}
+
 int eval_fused_batch(mrbf_ctx *ctx, const KP &kp, int D, int k, bool want_jac, const EvalDesc *host_descs, const EvalDesc *dev_descs, int count,
                      bool centred) {
     if (count <= 0) return 0;
     if (D != 64 && D != 128 && D != 256) return fail(ctx, MRBF_EHIP, "eval_fused_batch needs dpad in {64, 128, 256}");
+    // the members of a launch group share one parameterisation (batch_chain.hpp groups by the whole KP; batch.hip by kernel id and fast
+    // flag, and never holds a non-smooth one: batch_takes): a non-smooth group takes the difference form, all of it
+    for (int p = 0; p < count; ++p)
+        if (kp_nonsmooth(host_descs[p].kp) != kp_nonsmooth(kp))
+            return fail(ctx, MRBF_EHIP, "eval_fused_batch: descriptor %d and its group differ in kp_nonsmooth", p);
+    if (kp_nonsmooth(kp)) {
+        int64_t max_m = 0;
+        for (int p = 0; p < count; ++p) max_m = std::max(max_m, host_descs[p].m);
+        return launch_eval_diff(ctx, max_m, D, host_descs[0], dev_descs, count, want_jac);
+    }
     int64_t max_mpad = 0, max_m = 0;
     int max_split = 1;
     for (int p = 0; p < count; ++p) {

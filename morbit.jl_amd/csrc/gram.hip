@@ -383,7 +383,7 @@ __global__ __launch_bounds__(256, 4) void gram_mfma64_kernel(const double *__res
 int launch_gram(mrbf_ctx *ctx, int mode, const double *C, const double *Xc, const double *sq, int64_t n, int64_t npad,
                 int d, int dpad, const KP &kp, double *Phi, int64_t ld) {
     if (n <= 0) return 0;
-    if (mode == 1) {
+    if (mode == 1 || kp_nonsmooth(kp)) {  // (not smooth at 0: difference form in both modes, DESIGN.md "Distances near a centre")
         const int64_t nt = (n + 63) / 64;
         const int64_t nb = nt * (nt + 1) / 2;
         MRBF_DISPATCH_KID(kp.kid, hipLaunchKernelGGL((gram_diff_kernel<KID>), dim3((unsigned)nb), dim3(256), 0,

@@ -484,6 +484,7 @@ bool gram_w_applies(const mrbf_ctx *ctx, const mrbf_model *M) {
     static const int on = mrbf_env("MRBF_GRAM_FUSED") ? atoi(mrbf_env("MRBF_GRAM_FUSED")) : 1;
     if (!on || ctx->gram_mode != 0) return false;
     if (M->dpad != 64 || M->q < 1 || M->q > 65 || M->n < 1024) return false;
+    if (kp_nonsmooth(M->kp)) return false;  // (thin plate spline k = 1: launch_gram's difference form)
     return M->kp.fast || M->kp.kid == MRBF_GAUSSIAN || M->kp.kid == MRBF_THIN_PLATE_SPLINE;
 }
 

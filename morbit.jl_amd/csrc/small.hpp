@@ -76,6 +76,8 @@ struct EvalDesc {
     KP kp;
     double *vpart, *sapart, *gpart;     // per-split partials (scratch)
     double *vals, *jac;                 // m x k, m x (k x d column-major); jac may be NULL for the whole batch only
+    const double *C;      // the model's n x d centres as given (row-major, not centred): eval_diff_kernel's operand
+    int64_t n;
 };
 // everything a descriptor derives from the model, the number of query points and the split of the centre range (eval_nsplit): a single
 // call and a member of a batch must agree on all of it to agree bit for bit.  The buffers -- X, Xq, xsq, vpart, sapart, gpart, vals,
@@ -83,6 +85,8 @@ struct EvalDesc {
 inline void eval_desc_model(EvalDesc &E, const mrbf_model *M, int64_t m, int nsplit) {
     E.mean = M->mean;
     E.Cc = M->Xc;
+    E.C = M->C;
+    E.n = M->n;
     E.csq = M->sq;
     E.Wc = M->Wc;
     E.lam = M->lam;

@@ -1097,7 +1097,7 @@ int fit_model(mrbf_ctx *ctx, mrbf_model *M, const double *Y, mrbf_fit_info *info
     if (path == MRBF_PATH_PROJ_CHOL && M->q == 0) path = MRBF_PATH_CHOL;
     if (path == MRBF_PATH_MINNORM) {
         MRBF_TRY(fit_minnorm(ctx, M, Y, info));
-    } else if (path != MRBF_PATH_LU && small_fit_applies(ctx, M->n, M->d, M->k, M->q, path)) {
+    } else if (path != MRBF_PATH_LU && !kp_nonsmooth(M->kp) && small_fit_applies(ctx, M->n, M->d, M->k, M->q, path)) {  // (the small fit assembles in GEMM form)
         int not_pd = 0;
         MRBF_TRY(fit_small(ctx, M, Y, info, &not_pd, 0, &small_nc_used, &checked));
         if (not_pd) {
