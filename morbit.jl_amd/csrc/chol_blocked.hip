@@ -24,7 +24,7 @@ typedef double v2d __attribute__((ext_vector_type(2)));
 constexpr int CNB = 128;  // block size of the factorisation
 
 enum { UPD_LOWER_SUB = 0, UPD_OVERWRITE = 1, UPD_FULL_SUB = 2, UPD_COLUMN_SUB = 3 };
-int launch_diag_v4(mrbf_ctx *ctx, hipStream_t st, double *Ajj, int64_t lda, double *Linv, int *dinfo, int col0);  // chol_diag.hip
+int launch_diag(mrbf_ctx *ctx, hipStream_t st, double *Ajj, int64_t lda, double *Linv, int *dinfo, int col0);  // chol_diag.hip
 
 // C(i,j) (op)= sum_k A(i,k) * B(j,k).  A: (tiles_i*TM) x K, B: (tiles_j*128) x K, all column-major.
 // MODE LOWER_SUB: square region, grid.x = lower-triangular tile pairs (TM == 128), C -= ..., strictly-upper
@@ -436,7 +436,7 @@ int debug_diag(mrbf_ctx *ctx, const double *A128_dev, int reps, float *ms_per_ca
     MRBF_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
     for (int r = 0; r < reps; ++r)
         if (ctx->diag_impl != 1)
-            launch_diag_v4(ctx, ctx->stream, W + (size_t)r * CNB * CNB, (int64_t)CNB, Linv, dinfo, 0);
+            launch_diag(ctx, ctx->stream, W + (size_t)r * CNB * CNB, (int64_t)CNB, Linv, dinfo, 0);
         else if (with_stamps)
             hipLaunchKernelGGL(chol_diag_kernel<true>, dim3(1), dim3(512), 0, ctx->stream, W + (size_t)r * CNB * CNB, (int64_t)CNB, Linv,
                                dinfo, 0, st);
@@ -448,14 +448,6 @@ int debug_diag(mrbf_ctx *ctx, const double *A128_dev, int reps, float *ms_per_ca
     float t;
     MRBF_HIP(ctx, hipEventElapsedTime(&t, ctx->ev[0], ctx->ev[1]));
     *ms_per_call = t / reps;
-    if (const char *e = mrbf_env("MRBF_DIAG_DBG")) {
-        if (atoi(e) & 4) {  // per-segment cycle counters of the last launch (chol_diag_core.hpp)
-            double seg[6];
-            MRBF_HIP(ctx, hipMemcpy(seg, Linv, sizeof(seg), hipMemcpyDeviceToHost));
-            fprintf(stderr, "diag segments (wave 0, cycles over 8 panels): pre-leaf %.0f leaf %.0f post-leaf %.0f wait-X %.0f deferred %.0f wait-Y %.0f\n",
-                    seg[0], seg[1], seg[2], seg[3], seg[4], seg[5]);
-        }
-    }
     MRBF_HIP(ctx, hipMemcpy(stamps_host, st, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return 0;
 }
@@ -529,7 +521,7 @@ int potrf_blocked_tall(mrbf_ctx *ctx, int64_t ncols, int64_t mrows, double *A, i
             hipLaunchKernelGGL(chol_diag_kernel<false>, dim3(1), dim3(512), 0, P, Ajj, lda, Linv, dinfo, (int)c,
                                (unsigned long long *)nullptr);
         else
-            launch_diag_v4(ctx, P, Ajj, lda, Linv, dinfo, (int)c);
+            launch_diag(ctx, P, Ajj, lda, Linv, dinfo, (int)c);
         const int64_t m = mrows - c - CNB;  // rows below the diagonal block
         if (m <= 0) break;
         double *A21 = A + (c + CNB) + c * lda;

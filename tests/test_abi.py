@@ -140,7 +140,7 @@ def test_environment_switches_sit_behind_one_gate(lib):
                 if not (os.path.basename(path) == "common.hpp" and m.group(1) in ("MRBF_EXPERIMENTS", "name")):
                     raw.append("%s:%d: %s" % (os.path.basename(path), i + 1, line.strip()))
     assert not raw, "environment read outside the gate:\n" + "\n".join(raw)
-    assert gated >= 100
+    assert gated >= 97  # (104 before the diagonal block's retired v4 core left with its seven reads)
     # every switch is listed in INTEGRATION.md's appendix (regenerate it when one is added: the list is what a maintainer greps)
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     names = set()

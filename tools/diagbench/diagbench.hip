@@ -9,19 +9,17 @@
 #include <vector>
 using namespace mrbf;
 
-template <int V>
-__global__ __launch_bounds__(256, 2) void k(double *A, double *Linv, int *info, unsigned long long *ts, int reps, int dbg) {
-    __shared__ __attribute__((aligned(16))) struct {
-        diagcore::DiagV4Shared s4;
-    } sh;
+__global__ __launch_bounds__(256, 2) void k(double *A, double *Linv, int *info, unsigned long long *ts, int reps, double *scr) {
+    __shared__ __attribute__((aligned(16))) diagcore::DiagV6Shared sh;
     __builtin_amdgcn_s_setprio(3);
     if ((threadIdx.x & 63) == 0) ts[16 + (threadIdx.x >> 6)] = __builtin_amdgcn_s_getreg((31 << 11) | 4);  // HW_REG_HW_ID
     for (int r = 0; r < reps; ++r) {
         double *Ar = A + (size_t)r * 128 * 128;
         const unsigned long long t0 = __builtin_readcyclecounter();
-        int bad;
-        diagcore::v4d acc[diagcore::NSLOT];
-        bad = diagcore::diag_v4_core<true, false, false>(Ar, 128, Linv, sh.s4, acc, nullptr, nullptr, dbg);
+        diagcore::v4d acc[diagcore::NSLOT6];
+        diagcore::diag_v6_load(Ar, 128, acc);
+        // scr: 8 x 256 doubles for the leaf inverses (the core assembles the inverse from them), then the progress word
+        const int bad = diagcore::diag_v6_core(Ar, 128, Linv, sh, acc, scr, reinterpret_cast<unsigned *>(scr + 8 * 256));
         __syncthreads();
         if (threadIdx.x == 0) {
             ts[0] += __builtin_readcyclecounter() - t0;
@@ -31,8 +29,7 @@ __global__ __launch_bounds__(256, 2) void k(double *A, double *Linv, int *info, 
 }
 
 int main(int argc, char **argv) {
-    const int dbg = argc > 1 ? atoi(argv[1]) : 0;  // 4: per-segment cycles of the leaf wave (no inverse check then)
-    const int reps = dbg ? 1 : 64;
+    const int reps = argc > 1 ? atoi(argv[1]) : 64;
     std::mt19937_64 g(1);
     std::normal_distribution<double> nd;
     std::vector<double> G(128 * 160), A(128 * 128), all((size_t)reps * 128 * 128), L(128 * 128), Li(128 * 128);
@@ -43,23 +40,25 @@ int main(int argc, char **argv) {
             for (int k2 = 0; k2 < 160; ++k2) s += G[i * 160 + k2] * G[j * 160 + k2];
             A[i + j * 128] = s / 128 + (i == j);
         }
-    double *dA, *dL;
+    double *dA, *dL, *dscr;
     int *dinfo;
     unsigned long long *dts;
     hipMalloc(&dA, all.size() * 8);
     hipMalloc(&dL, 128 * 128 * 8);
     hipMalloc(&dinfo, 4);
     hipMalloc(&dts, 64 * 8);
-    for (int v = 4; v <= 4; ++v) {
+    hipMalloc(&dscr, (8 * 256 + 16) * 8);
+    {
         for (int r = 0; r < reps; ++r) std::copy(A.begin(), A.end(), all.begin() + (size_t)r * 128 * 128);
         hipMemcpy(dA, all.data(), all.size() * 8, hipMemcpyHostToDevice);
         hipMemset(dinfo, 0, 4);
         hipMemset(dts, 0, 64 * 8);
+        hipMemset(dscr, 0, (8 * 256 + 16) * 8);
         hipEvent_t e0, e1;
         hipEventCreate(&e0);
         hipEventCreate(&e1);
         hipEventRecord(e0, 0);
-        hipLaunchKernelGGL(k<4>, dim3(1), dim3(256), 0, 0, dA, dL, dinfo, dts, reps, dbg);
+        hipLaunchKernelGGL(k, dim3(1), dim3(256), 0, 0, dA, dL, dinfo, dts, reps, dscr);
         hipEventRecord(e1, 0);
         hipEventSynchronize(e1);
         float ms;
@@ -80,13 +79,10 @@ int main(int argc, char **argv) {
                 e = std::max(e, std::fabs(s - A[i + j * 128]));
                 ei = std::max(ei, std::fabs(t - (i == j)));
             }
-        if (dbg & 4)
-            printf("leaf wave cycles over 8 panels: pre-leaf %.0f, leaf %.0f, post-leaf LDS %.0f, barrier X %.0f, look-ahead work %.0f, barrier Y %.0f\n", Li[0], Li[1], Li[2], Li[3], Li[4], Li[5]);
         printf("wave -> simd:");
         for (int w = 0; w < 4; ++w) printf(" %llu(cu %llu)", (ts[16 + w] >> 4) & 3, (ts[16 + w] >> 8) & 15);
         printf("\n");
-        printf("v%d: %.2f us per block (events), %.0f cycles per block (shader clock), info %d, |LL'-A| %.1e |Linv L - I| %.1e\n", v,
-               ms * 1e3 / reps, (double)ts[0] / reps, info, e, ei);
+        printf("%.2f us per block (events), %.0f cycles per block (shader clock), info %d, |LL'-A| %.1e |Linv L - I| %.1e\n", ms * 1e3 / reps, (double)ts[0] / reps, info, e, ei);
     }
     return 0;
 }

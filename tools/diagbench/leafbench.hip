@@ -101,7 +101,7 @@ __global__ __launch_bounds__(64) void ksched(const double *A, double *out, unsig
 }
 
 // Round 4: multipliers through LDS -- 197 -> 156 cycles per column HERE (one wave alone on its CU), but slower inside the factorisation
-// (n = 256 / 2048 / 8192: +14 / +4.5 / +1.5 % with this leaf in diag_v6_core / diag_v4_core: the leaf wave's LDS reads queue behind the
+// (n = 256 / 2048 / 8192: +14 / +4.5 / +1.5 % with this leaf in diag_v6_core and in its predecessor: the leaf wave's LDS reads queue behind the
 // three update waves' operand traffic on the same LDS), so the product keeps the readlane leaf.  Two things learnt on the way:
 // (i) lanes that talk to each other through LDS need wavefront-scope fences (no instructions) -- without them the compiler treats
 // the scratch words as private to a lane and reuses, on the lanes that do not store, the value they loaded two columns ago (the
