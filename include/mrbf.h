@@ -91,6 +91,14 @@ enum {
     MRBF_OPT_ARENA_BYTES = 13,   /* read only: bytes of device memory the context's grow-only arena (named work buffers) and its pool of released
                                   * model blocks hold: constant in steady state (a caller can watch it over its iterations) */
     MRBF_OPT_LIVE_HANDLES = 14,  /* read only: models + round-4 states created through this context and not yet released */
+    MRBF_OPT_SMALL_FIT_MAX_N = 15, /* most sites the one-launch fit takes (mrbf_fit, mrbf_fit_batch): 512 (default) .. 2048; any other value
+                                  is an invalid argument (-2) and the stored value stays.  With 512 every result is what it always
+                                  was.  Above, a start with 512 < n <= the value takes the one-launch fit as well (same shape range
+                                  otherwise): a batch of such starts is one launch instead of a launch chain per start -- the bindings
+                                  raise it around mrbf_fit_batch where mrbf_dispatch_fit_batch_max_n says the batch pays.  A fit is
+                                  reproducible bit for bit under ONE value; the one-launch fit and the chain sum in different orders.
+                                  The context's grow-only arena keeps the scratch of the widest batch (46 MB per start at n = 2048,
+                                  d = 128; MRBF_OPT_ARENA_BYTES shows it) */
     MRBF_OPT_DEBUG_FAULT = 10  /* test hook: bit 0 = one workgroup of the persistent factorisation skips a publish, bit 1 = one workgroup of
                                   the persistent backward substitution does (the next fit must fall back and still return the right weights), bit 2 = one
                                   member of a small fit's workgroup cluster leaves early (the fit is repeated with one workgroup per problem) */
@@ -324,7 +332,7 @@ int32_t mrbf_batch_run(int32_t n_dev, const int32_t *device_ids, int64_t n_probl
  * mrbf_sd_iterate_batch) are, bit for bit, those of mrbf_fit on that start's arguments on the same context; they do not depend on
  * the start's position in the batch or on which other starts share it.  info.path, fallbacks, n and q equal the single call's;
  * rel_residual and max_pitw come from the batch's own check kernel (same quantities, sums in another order).
- * Starts in the range of the one-launch fit (n <= 512, d <= 128, k <= 16, Cholesky paths) share a handful of launches whose grids
+ * Starts in the range of the one-launch fit (n <= the context's MRBF_OPT_SMALL_FIT_MAX_N, d <= 128, k <= 16, Cholesky paths) share a handful of launches whose grids
  * span all of them, one packed descriptor upload and one read-back; every other start, and a start whose batched fit raised a flag
  * (not positive definite, rank-deficient tail), takes mrbf_fit inside the same call.
  * Lifetime: jobs[p].model is a handle like any other -- mrbf_eval, mrbf_sd_iterate_batch, mrbf_ps_step_problem, mrbf_model_dims
@@ -824,6 +832,11 @@ int32_t mrbf_ps_step_batch(mrbf_ctx *ctx, int64_t n_starts, const mrbf_ps_proble
  *                            evaluated (n_nl > 0), d <= 256 (the fused evaluation kernels' range); linear rows alone keep d <= 4096.
  *   mrbf_dispatch_fit_batch  update_model of n_starts starts in one call (mrbf_fit_batch): device iff 1 <= n_starts <= 65535 (a grid
  *                            dimension).  Which starts share the batched launches is decided inside the call, start by start.
+ *   mrbf_dispatch_fit_batch_max_n  the value of MRBF_OPT_SMALL_FIT_MAX_N the bindings set around mrbf_fit_batch for n_starts starts
+ *                            of dimension d: the largest n the one-launch fit should take.  The bindings keep the loop of single
+ *                            calls (512: the option's default, starts beyond it take mrbf_fit inside the call) where the batch does
+ *                            not pay (measured, DESIGN.md section 12: 1684 from 8 starts on, 2048 from 16 on, at 65 <= d <= 128);
+ *                            n_starts < 1 or > 65535, or d outside 1 .. 128: 512.
  *   mrbf_dispatch_round4_batch  _rbf_round4 of n_starts starts in one call (mrbf_round4_batch): device iff 1 <= n_starts <= 65535 (a grid
  *                            dimension) and 1 <= d <= 1024 (mrbf_round4's own limit).  Which starts share the batched launches (the small
  *                            range: d <= 128, q <= n0 <= 256, mc <= 4096, at most 256 sites to accept) is decided inside the call.
@@ -864,6 +877,7 @@ int32_t mrbf_dispatch_affine(int64_t n_candidates, int32_t d);
 int32_t mrbf_dispatch_affine_batch(int64_t n_starts, int32_t d, int32_t p_is_inf);
 int32_t mrbf_dispatch_round4(int64_t n0, int32_t d, int32_t poly_deg, int64_t n_candidates);
 int32_t mrbf_dispatch_fit_batch(int64_t n_starts);
+int64_t mrbf_dispatch_fit_batch_max_n(int64_t n_starts, int32_t d);
 int32_t mrbf_dispatch_round4_batch(int64_t n_starts, int32_t d);
 int32_t mrbf_dispatch_db_batch(int64_t n_starts, int32_t d);
 int32_t mrbf_dispatch_fit(int64_t n_training, int64_t state_n0, int32_t state_q, int32_t state_n_accepted, int32_t same_sites);

@@ -18,6 +18,8 @@ PATH_CHOL, PATH_PROJ_CHOL, PATH_LU, PATH_MINNORM, PATH_ROUND4 = 1, 2, 3, 4, 5
 OPT_GRAM_MODE, OPT_RESIDUAL, OPT_FORCE_PATH, OPT_CHOL_IMPL, OPT_EVAL_IMPL, OPT_TIMING, OPT_DIAG_IMPL, OPT_CHOL_WINDOW = 1, 2, 3, 4, 5, 6, 7, 8
 OPT_SPIN_MS, OPT_DEBUG_FAULT, OPT_LAST_DEVICE_MS, OPT_SLOW_LAUNCHES = 9, 10, 11, 12
 OPT_ARENA_BYTES, OPT_LIVE_HANDLES = 13, 14   # read only
+OPT_SMALL_FIT_MAX_N = 15                     # most sites the one-launch fit takes: 512 (default) .. 2048
+SMALL_FIT_DEFAULT_MAX_N = 512
 FB_CHOL_HOST_DRIVEN, FB_BACKSOLVE_BLOCKED, FB_LU = 1, 2, 4
 
 
@@ -245,6 +247,7 @@ SIGNATURES = {
                                         ctypes.POINTER(Result)]),
     "mrbf_fit_batch": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.POINTER(FitJob), c_fp]),
     "mrbf_dispatch_fit_batch": (ctypes.c_int32, [ctypes.c_int64]),
+    "mrbf_dispatch_fit_batch_max_n": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32]),
     "mrbf_db_create": (ctypes.c_int32, [c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.POINTER(c_vp)]),
     "mrbf_db_append": (ctypes.c_int32, [c_vp, c_vp, ctypes.c_int64, c_vp, c_vp, ctypes.POINTER(ctypes.c_int64)]),
     "mrbf_db_set_values": (ctypes.c_int32, [c_vp, c_vp, ctypes.c_int64, c_vp, c_vp]),

@@ -3,7 +3,7 @@
 // surrogate evaluations per subproblem :217).
 //
 // Problems are dealt round-robin over the GPUs (problem p -> GPU p % n_dev, one host thread + context per GPU, no exchange).  On each
-// GPU the small problems (n <= 512, d <= 128, Cholesky paths -- the regime Morbit runs in) go through a handful of launches whose grids
+// GPU the small problems (n <= 512 or the context's MRBF_OPT_SMALL_FIT_MAX_N, d <= 128, Cholesky paths -- the regime Morbit runs in) go through a handful of launches whose grids
 // span ALL of them:
 //     1   small_fit_kernel            one workgroup per problem: the whole fit (small.hip)
 //     1   center_pad_batch_kernel     queries of all problems (and, for the residual, their sites) centred + padded

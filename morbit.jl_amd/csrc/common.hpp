@@ -148,6 +148,7 @@ struct mrbf_ctx {
     int small_nc = 4;  // 1 after a cluster failure on this context (XCD placement, or a result that one workgroup does not reproduce)
     int small_cluster_ok = 0;    // the device is what the clusters' visibility argument assumes: gfx950, 8 XCDs x 32 CUs (context.hip)
     int small_timeouts = 0;      // barrier time-outs of clustered launches in a row (three: clusters off for this context)
+    int small_fit_max_n = 512;   // MRBF_OPT_SMALL_FIT_MAX_N: most sites the one-launch fit takes (small_fit_applies), 512 .. 2048
     int live_models = 0, live_round4 = 0;  // handles created through this context and not yet released (MRBF_OPT_LIVE_HANDLES)
     int live_dbs = 0;                      // likewise: resident site databases (db.hip)
     unsigned ps_rank_epoch = 0;  // launches of the PS ranking's wave kernel so far (part of the tag its exchanged records carry)

@@ -388,6 +388,10 @@ int32_t mrbf_set_option(mrbf_ctx *ctx, int32_t key, double value) {
         case MRBF_OPT_CHOL_WINDOW: ctx->chol_window = v; break;
         case MRBF_OPT_SPIN_MS: ctx->spin_ms = v > 0 ? v : 1000; break;
         case MRBF_OPT_DEBUG_FAULT: ctx->debug_fault = v; break;
+        case MRBF_OPT_SMALL_FIT_MAX_N:
+            if (!(value >= 512.0 && value <= 2048.0)) return fail(ctx, -2, "MRBF_OPT_SMALL_FIT_MAX_N: %g is not in 512 .. 2048", value);
+            ctx->small_fit_max_n = v;
+            break;
         default: return fail(ctx, -2, "unknown option key %d", key);
     }
     return MRBF_OK;
@@ -407,6 +411,7 @@ int32_t mrbf_get_option(const mrbf_ctx *ctx, int32_t key, double *value) {
         case MRBF_OPT_CHOL_WINDOW: *value = ctx->chol_window; break;
         case MRBF_OPT_SPIN_MS: *value = ctx->spin_ms; break;
         case MRBF_OPT_DEBUG_FAULT: *value = ctx->debug_fault; break;
+        case MRBF_OPT_SMALL_FIT_MAX_N: *value = ctx->small_fit_max_n; break;
         case MRBF_OPT_LAST_DEVICE_MS: *value = ctx->last_device_ms; break;
         case MRBF_OPT_SLOW_LAUNCHES: *value = ctx->slow_launches; break;
         case MRBF_OPT_ARENA_BYTES: {

@@ -9,6 +9,15 @@ constexpr int PS_MAXLAM = 7168, PS_MAXOBJ = 8, PS_MAXMODELS = 8, PS_MAXCON = 32,
 // below this many candidate coordinates one host BLAS call beats a launch + two copies (tools/affine_bench.py)
 constexpr int64_t AFFINE_MIN_WORK = 4096 * 8;
 constexpr int64_t FIT_REUSE_MAX_N = 1024;
+// mrbf_dispatch_fit_batch_max_n: from min_starts starts on, the one-launch fit takes up to max_n sites (rows ascending in both).
+// Measured at d = 128 (tools/fit_batch_bench.py --wide, profiles/fit_batch_wide_bench.jsonl): batch / parent loop = 0.54 - 0.56 at (8 starts,
+// n = 1684), 0.72 - 0.73 at (8, 2048) -- within a run-to-run spread of the 0.8 that admits a cell, so not admitted --, 0.41 at (16, 2048)
+struct FitWideRow {
+    int64_t min_starts, max_n;
+};
+constexpr FitWideRow FIT_WIDE[] = {{8, 1684}, {16, 2048}};
+constexpr int FIT_WIDE_MIN_D = 65;  // the padded dimension the cells were measured at (dpad = 128); d <= 64 has another chain and no measurement
+constexpr int FIT_WIDE_ROWS = (int)(sizeof(FIT_WIDE) / sizeof(FIT_WIDE[0]));
 }  // namespace
 
 extern "C" {
@@ -96,6 +105,20 @@ int32_t mrbf_dispatch_affine_batch(int64_t n_starts, int32_t d, int32_t p_is_inf
 // the model updates of many starts in one call (batch.hip, mrbf_fit_batch): the start on a grid dimension; which starts the batched fit
 // takes and which the single call inside it is decided start by start in the library
 int32_t mrbf_dispatch_fit_batch(int64_t n_starts) { return n_starts >= 1 && n_starts <= 65535 ? MRBF_DISPATCH_DEVICE : MRBF_DISPATCH_REFERENCE; }
+
+// the value of MRBF_OPT_SMALL_FIT_MAX_N the bindings set around mrbf_fit_batch: the largest n the one-launch fit should take for a batch
+// of n_starts starts of dimension d (small.hip: beyond 512 sites the solves are dealt over the cluster as well).  The bindings keep the
+// loop of single calls -- 512, the default: a start beyond it takes mrbf_fit inside the call -- where the batch does not pay: a cell
+// (n_starts, n) is admitted only where the batch took at most 0.8 of the loop's median (tools/fit_batch_bench.py --wide,
+// profiles/fit_batch_wide_bench.jsonl), and between measured cells the rule takes the smaller n of the smaller
+// batch, so that it is monotone in n_starts.  Fewer than 8 starts, and d <= 64 (the launch chain has another front end there, small.hip:
+// TailQ), were not measured: 512.
+int64_t mrbf_dispatch_fit_batch_max_n(int64_t n_starts, int32_t d) {
+    if (n_starts < 1 || n_starts > 65535 || d < FIT_WIDE_MIN_D || d > 128) return 512;
+    for (int i = FIT_WIDE_ROWS - 1; i >= 0; --i)
+        if (n_starts >= FIT_WIDE[i].min_starts) return FIT_WIDE[i].max_n;
+    return 512;
+}
 
 int32_t mrbf_dispatch_round4(int64_t n0, int32_t d, int32_t poly_deg, int64_t n_candidates) {
     const int q = mrbf::poly_dim(d, poly_deg);

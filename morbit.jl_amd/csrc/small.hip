@@ -13,6 +13,12 @@
 // chol_diag_core.hpp, everything else by one generic workgroup GEMM on the fp64 matrix cores with its operands read from global
 // memory (the working set of a problem, ~4 MB, lives in L2 / Infinity Cache).  A problem whose factorisation meets a non-positive
 // pivot, a rank-deficient tail basis or a non-positive shift sets a flag and the caller takes the ordinary path (LU) for it.
+//
+// The ceiling of 512 sites is the context's MRBF_OPT_SMALL_FIT_MAX_N (512 .. 2048): a many-start batch beyond 512 sites is one launch
+// as well where the bindings raise it (mrbf_dispatch_fit_batch_max_n).  Up to npad = 512 the kernel runs the code it always ran; above,
+// the triangular solves and the tail re-projection are dealt over the cluster too (see `wide` in small_fit_kernel).  Scratch is
+// carve(npad, q16) per start, 46 MB at n = 2048, d = 128: the context's arena is grow-only and KEEPS what the widest batch asked
+// for (up to run_small_batch's budget per launch group) until the context is shut down.
 #include "chol_diag_core.hpp"
 #include "radial.hpp"
 #include "small.hpp"
@@ -497,6 +503,14 @@ struct FitShared {
 };
 static_assert(sizeof(FitShared) == 80904, "small_fit_kernel: the LDS footprint (81968 bytes of group segment) is part of its measured behaviour");
 
+// 32-bit index arithmetic at the ceiling of MRBF_OPT_SMALL_FIT_MAX_N (npad = 2048, q16 = 144, ldz = 160, nc <= 16), checked product by
+// product: element counts np * q16 = 294912, np * 16 = 32768, np * k <= 32768, mrows * 128 <= 245760, (np - n16) * q16 <= 16128 and
+// the `e % np`, `e / np`, `e % mrows` taken of them; batched_pass's look-ahead e0 + 256 * 7 <= count + 8 * 256 * 16; wg_gemm's tile
+// count MT * NT2 <= 64 * 64 and idx + 4 * nc; the solves' 128 * c + i + l * np <= 32768 and a + l * ldz <= 2560; the dpad * np = 262144
+// elements of Xc.  Everything that multiplies by np, ld or lda twice -- (int64_t)j * np + i into Phi (np * np = 4194304 would still fit),
+// c * 128 * (ld + 1), c * 128 * 128, 128 * c * np -- is formed in 64 bits, and carve() counts in size_t (5.8 M doubles per start).
+// The barrier's bound stays MRBF_OPT_SPIN_MS (default 1000 ms) for one wait: the longest phase one member works alone is a full
+// 128-column diagonal block (26 us), the longest dealt phase the first trailing update (1920 x 1920 x 128 over >= 16 waves, a few ms).
 __global__ __launch_bounds__(256, 1) void small_fit_kernel(Prob one, const Prob *__restrict__ many, int count, int nc) {
     __shared__ __attribute__((aligned(16))) FitShared shp;
     diagcore::DiagV6Shared &sh = shp.diag;
@@ -754,46 +768,97 @@ __global__ __launch_bounds__(256, 1) void small_fit_kernel(Prob one, const Prob 
             if (tid == 0 && (member == 0 || bad < 0)) P.flags[bad > 0 ? 0 : 3] = bad > 0 ? bad : 1;
             return;
         }
-        if (member != 0) return;  // the triangular solves and the tail are member 0's (one macro tile per wave: nothing to deal out)
+        // up to four block rows the triangular solves and the tail are member 0's (one macro tile per wave: nothing to deal out)
+        if (np <= 512 && member != 0) return;
     }
     __syncthreads();
     MRBF_STAMP();  // 7: potrf
     const int nb = np / 128;
+    const bool wide = np > 512;
     // ---- forward substitution L y = B (block rows; inv(L_cc) from the factorisation), then backward L' x = y
-    for (int c = 0; c < nb; ++c) {
-        if (c > 0) {
-            wg_gemm<false, false, false>(128, 16, 128 * c, Phi + 128 * c, np, Fy, np, [&](int i, int l) { return gld(&Bm[128 * c + i + l * np]); },
-                                         [&](int i, int l, double v, double o) { gst(&Bm[128 * c + i + l * np], o - v); });
+    if (wide) {
+        // Beyond four block rows (MRBF_OPT_SMALL_FIT_MAX_N above 512) the left-looking loops below would be 2 nb dependent steps of one
+        // 128 x 16 output each on member 0: 32 steps at np = 2048, four waves busy, every other member idle.  Right-looking instead:
+        // once block row c is solved with inv(L_cc), ONE product takes its contribution out of all block rows still to come, and the
+        // macro tiles of that product are dealt over the cluster's waves like every other product of the fit.  An element of block row
+        // r receives its updates in the order c = 0 .. r - 1 (backward: nb - 1 .. r + 1), each one a complete 128-deep sum formed by
+        // the one wave that holds its tile in that step, then subtracted: the order is fixed by the step loop, not by who computes
+        // the tile, so the bits are the same for every cluster size.  No reduction is split over members.  Rows beyond n16 are
+        // identity padding (zero off the diagonal, zero right-hand sides) and stay out of the products.
+        for (int c = 0; c < nb; ++c) {
+            wg_gemm<false, false, false>(128, 16, 128, Linv + (int64_t)c * 128 * 128, 128, Bm + 128 * c, np, NoPre(),
+                                         [&](int i, int l, double v, double) { gst(&Fy[128 * c + i + l * np], v); }, member, nc);
+            MRBF_CLB();
+            const int r0 = 128 * (c + 1), mrows = n16 - r0;
+            if (mrows > 0) {  // B(r0 ..) -= L(r0 .., c) y_c
+                wg_gemm<false, false, false>(mrows, 16, 128, Phi + r0 + (int64_t)128 * c * np, np, Fy + 128 * c, np,
+                                             [&](int i, int l) { return gld(&Bm[r0 + i + l * np]); },
+                                             [&](int i, int l, double v, double o) { gst(&Bm[r0 + i + l * np], o - v); }, member, nc);
+                MRBF_CLB();
+            }
+        }
+        for (int c = nb - 1; c >= 0; --c) {
+            wg_gemm<true, false, false>(128, 16, 128, Linv + (int64_t)c * 128 * 128, 128, Fy + 128 * c, np, NoPre(),
+                                        [&](int i, int l, double v, double) { gst(&Xs[128 * c + i + l * np], v); }, member, nc);
+            MRBF_CLB();
+            if (c > 0) {  // y(0 .. 128 c) -= L(c, 0 .. 128 c)' x_c   (the real rows of block row c only)
+                const int kreal = min(128, n16 - 128 * c);
+                wg_gemm<true, false, false>(128 * c, 16, kreal, Phi + 128 * c, np, Xs + 128 * c, np, [&](int i, int l) { return gld(&Fy[i + l * np]); },
+                                            [&](int i, int l, double v, double o) { gst(&Fy[i + l * np], o - v); }, member, nc);
+                MRBF_CLB();
+            }
+        }
+    } else {
+        for (int c = 0; c < nb; ++c) {
+            if (c > 0) {
+                wg_gemm<false, false, false>(128, 16, 128 * c, Phi + 128 * c, np, Fy, np, [&](int i, int l) { return gld(&Bm[128 * c + i + l * np]); },
+                                             [&](int i, int l, double v, double o) { gst(&Bm[128 * c + i + l * np], o - v); });
+                __syncthreads();
+            }
+            wg_gemm<false, false, false>(128, 16, 128, Linv + (int64_t)c * 128 * 128, 128, Bm + 128 * c, np, NoPre(),
+                                         [&](int i, int l, double v, double) { gst(&Fy[128 * c + i + l * np], v); });
             __syncthreads();
         }
-        wg_gemm<false, false, false>(128, 16, 128, Linv + (int64_t)c * 128 * 128, 128, Bm + 128 * c, np, NoPre(),
-                                     [&](int i, int l, double v, double) { gst(&Fy[128 * c + i + l * np], v); });
-        __syncthreads();
-    }
-    for (int c = nb - 1; c >= 0; --c) {
-        const int rest = np - 128 * (c + 1);
-        if (rest > 0) {
-            wg_gemm<true, false, false>(128, 16, rest, Phi + 128 * (c + 1) + (int64_t)128 * c * np, np, Xs + 128 * (c + 1), np,
-                                        [&](int i, int l) { return gld(&Fy[128 * c + i + l * np]); },
-                                        [&](int i, int l, double v, double o) { gst(&Fy[128 * c + i + l * np], o - v); });
+        for (int c = nb - 1; c >= 0; --c) {
+            const int rest = np - 128 * (c + 1);
+            if (rest > 0) {
+                wg_gemm<true, false, false>(128, 16, rest, Phi + 128 * (c + 1) + (int64_t)128 * c * np, np, Xs + 128 * (c + 1), np,
+                                            [&](int i, int l) { return gld(&Fy[128 * c + i + l * np]); },
+                                            [&](int i, int l, double v, double o) { gst(&Fy[128 * c + i + l * np], o - v); });
+                __syncthreads();
+            }
+            wg_gemm<true, false, false>(128, 16, 128, Linv + (int64_t)c * 128 * 128, 128, Fy + 128 * c, np, NoPre(),
+                                        [&](int i, int l, double v, double) { gst(&Xs[128 * c + i + l * np], v); });
             __syncthreads();
         }
-        wg_gemm<true, false, false>(128, 16, 128, Linv + (int64_t)c * 128 * 128, 128, Fy + 128 * c, np, NoPre(),
-                                    [&](int i, int l, double v, double) { gst(&Xs[128 * c + i + l * np], v); });
-        __syncthreads();
     }
     MRBF_STAMP();  // 8: solves
     // ---- tail: re-project w (rounding hygiene), z = Q1' Y - W' w, lam = R^-1 z with R = [[sqrt n, sqrt n mean'], [0, Lx']]
     if (q > 0) {
-        wg_gemm<true, false, false>(q16, 16, n16, Q1, np, Xs, np, NoPre(), [&](int a, int l, double v, double) { gst(&T2[a + l * ldz], v); });
-        __syncthreads();
-        wg_gemm<false, false, false>(n16, 16, q16, Q1, np, T2, ldz, [&](int i, int l) { return gld(&Xs[i + l * np]); },
-                                     [&](int i, int l, double v, double o) { gst(&Xs[i + l * np], o - v); });
-        __syncthreads();
-        wg_gemm<true, false, false>(q16, 16, n16, Wm, np, Xs, np, [&](int a, int l) { return gld(&T1[a + l * ldz]); },
-                                    [&](int a, int l, double v, double o) { gst(&Z[a + l * ldz], o - v); });
-        for (int e = tid; e < 16 * 16; e += 256) Z[q16 + e % 16 + (e / 16) * ldz] = 0.0;  // the rows the next product may read beyond q16
-        __syncthreads();
+        if (wide) {
+            // the same three products with their macro tiles dealt over the cluster (every sum over the sites stays whole, in one wave)
+            wg_gemm<true, false, false>(q16, 16, n16, Q1, np, Xs, np, NoPre(), [&](int a, int l, double v, double) { gst(&T2[a + l * ldz], v); }, member, nc);
+            MRBF_CLB();
+            wg_gemm<false, false, false>(n16, 16, q16, Q1, np, T2, ldz, [&](int i, int l) { return gld(&Xs[i + l * np]); },
+                                         [&](int i, int l, double v, double o) { gst(&Xs[i + l * np], o - v); }, member, nc);
+            MRBF_CLB();
+            wg_gemm<true, false, false>(q16, 16, n16, Wm, np, Xs, np, [&](int a, int l) { return gld(&T1[a + l * ldz]); },
+                                        [&](int a, int l, double v, double o) { gst(&Z[a + l * ldz], o - v); }, member, nc);
+            if (member == 0)
+                for (int e = tid; e < 16 * 16; e += 256) Z[q16 + e % 16 + (e / 16) * ldz] = 0.0;  // the rows the next product may read beyond q16
+            MRBF_CLB();
+        } else {
+            wg_gemm<true, false, false>(q16, 16, n16, Q1, np, Xs, np, NoPre(), [&](int a, int l, double v, double) { gst(&T2[a + l * ldz], v); });
+            __syncthreads();
+            wg_gemm<false, false, false>(n16, 16, q16, Q1, np, T2, ldz, [&](int i, int l) { return gld(&Xs[i + l * np]); },
+                                         [&](int i, int l, double v, double o) { gst(&Xs[i + l * np], o - v); });
+            __syncthreads();
+            wg_gemm<true, false, false>(q16, 16, n16, Wm, np, Xs, np, [&](int a, int l) { return gld(&T1[a + l * ldz]); },
+                                        [&](int a, int l, double v, double o) { gst(&Z[a + l * ldz], o - v); });
+            for (int e = tid; e < 16 * 16; e += 256) Z[q16 + e % 16 + (e / 16) * ldz] = 0.0;  // the rows the next product may read beyond q16
+            __syncthreads();
+        }
+        if (member != 0) return;  // (wide: what is left -- the tail's small solve, the copies into the model -- is member 0's)
         if (q > 1) {
             const int d16 = (d + 15) & ~15;
             // lam_tail = Lx^-T z[1:]  =  inv(Lx)' z[1:]
@@ -812,6 +877,7 @@ __global__ __launch_bounds__(256, 1) void small_fit_kernel(Prob one, const Prob 
             P.lam[(int64_t)t * k + l] = T2[t + l * ldz];
         }
     }
+    if (member != 0) return;
     MRBF_STAMP();  // 9: tail
     // ---- the model's weights: W (n x k row-major), Wc (npad x k column-major, zero padded)
     for (int e = tid; e < np * k; e += 256) {
@@ -1005,7 +1071,7 @@ __global__ __launch_bounds__(256) void tailq_q1_kernel(TailQ t) {
 bool small_fit_applies(const mrbf_ctx *ctx, int64_t n, int d, int k, int q, int path) {
     static const int off = mrbf_env("MRBF_SMALL_FIT") ? atoi(mrbf_env("MRBF_SMALL_FIT")) == 0 : 0;
     if (off || ctx->chol_impl == 1 || ctx->gram_mode == 1) return false;
-    return n >= 1 && n <= 512 && d >= 1 && d <= 128 && k >= 1 && k <= 16 && n > q && (path == MRBF_PATH_CHOL || path == MRBF_PATH_PROJ_CHOL);
+    return n >= 1 && n <= ctx->small_fit_max_n && d >= 1 && d <= 128 && k >= 1 && k <= 16 && n > q && (path == MRBF_PATH_CHOL || path == MRBF_PATH_PROJ_CHOL);
 }
 
 int small_fit_cluster(const mrbf_ctx *ctx, int count) {

@@ -286,6 +286,7 @@ _dispatch_affine(n_candidates, d) = ccall((:mrbf_dispatch_affine, libmrbf), Int3
 _dispatch_affine_batch(n_starts, d, p) =
     ccall((:mrbf_dispatch_affine_batch, libmrbf), Int32, (Int64, Int32, Int32), n_starts, d, isinf(p) ? 1 : 0) == 1
 _dispatch_fit_batch(n_starts) = ccall((:mrbf_dispatch_fit_batch, libmrbf), Int32, (Int64,), n_starts) == 1
+_dispatch_fit_batch_max_n(n_starts, d) = Int(ccall((:mrbf_dispatch_fit_batch_max_n, libmrbf), Int64, (Int64, Int32), n_starts, d))
 _dispatch_round4_batch(n_starts, d) = ccall((:mrbf_dispatch_round4_batch, libmrbf), Int32, (Int64, Int32), n_starts, d) == 1
 _dispatch_round4(n0, d, deg, n_candidates) =
     ccall((:mrbf_dispatch_round4, libmrbf), Int32, (Int64, Int32, Int32, Int64), n0, d, deg, n_candidates) == 1
@@ -1282,11 +1283,17 @@ function affine_select_batch(Ss::AbstractVector{Matrix{Float64}}, Q0s::AbstractV
         (Int.(picks[q][1:np]) .+ 1, Zbufs[q][:, 1:(d - Int(j0s[q]) - np)])
     end
 end
+# (the context's lock is reentrant: hip_update_models_many holds it around the option it sets for this call)
+_fit_batch_locked(ctx, ns, jobs, ms) = _locked(ctx) do hctx
+    ccall((:mrbf_fit_batch, libmrbf), Int32, (Ptr{Cvoid}, Int64, Ptr{MrbfFitJob}, Ref{Float32}), hctx, ns, jobs, ms)
+end
 """
 The model updates of many starts in one device call (`mrbf_fit_batch`): the arithmetic half of `update_model` (RbfModel.jl:743-767) for
 independent starts -- the `Threads.@threads` loop over starts of examples/large_scale_benchmarks.jl:102-109 -- with the models kept.
 `Cs[p]` (d x n_p sites, one per column), `Ys[p]` (k x n_p values), `Δs[p]` and `cfgs[p]` are start p's training data, radius and
-config; `fully_linear[p]` what its meta says.  For every start the model is, bit for bit, the one `mrbf_fit` gives on that start alone.
+config; `fully_linear[p]` what its meta says.  For every start the model is, bit for bit, the one `mrbf_fit` gives on that start alone
+(a start with more than 512 sites that `mrbf_dispatch_fit_batch_max_n` sends into the batch's launch: the one `mrbf_fit` gives with
+`MRBF_OPT_SMALL_FIT_MAX_N` at that value).
 Where the decision table refuses the batch (`mrbf_dispatch_fit_batch`) or the library does (rc -2), every start takes `mrbf_fit`.
 Returns a vector of `HipRbfModel` (`nothing` for a start whose fit failed) and the vector of return codes.  The models of one call
 share one device allocation: its memory is reusable once all of them are released (finalizers, or `_free_model!`).
@@ -1323,8 +1330,23 @@ function hip_update_models_many(cfgs::AbstractVector{HipRbfConfig}, Cs::Abstract
             jobs[q] = MrbfFitJob(size(Cs[q], 2), size(Cs[q], 1), size(Ys[q], 1), kid, cfgs[q].polynomial_degree, a, b, pointer(Cs[q]),
                                  pointer(Ys[q]), C_NULL, C_NULL, C_NULL, 0, 0, zero_info)
         end
-        _locked(ctx) do hctx
-            ccall((:mrbf_fit_batch, libmrbf), Int32, (Ptr{Cvoid}, Int64, Ptr{MrbfFitJob}, Ref{Float32}), hctx, ns, jobs, ms)
+        # starts beyond the one-launch fit's default range share the batch's launch up to the n the table names: the context's
+        # MRBF_OPT_SMALL_FIT_MAX_N (key 15) is raised for this one call and put back behind it, also on error, under the context's lock
+        beyond = [q for q in 1:ns if size(Cs[q], 2) > 512]
+        wide_n = isempty(beyond) ? 512 : minimum(_dispatch_fit_batch_max_n(length(beyond), size(Cs[q], 1)) for q in beyond)
+        if any(size(Cs[q], 2) <= wide_n for q in beyond)
+            _locked(ctx) do hctx
+                previous = Ref{Float64}(512.0)
+                _check(ctx, ccall((:mrbf_get_option, libmrbf), Int32, (Ptr{Cvoid}, Int32, Ref{Float64}), hctx, 15, previous))
+                _check(ctx, ccall((:mrbf_set_option, libmrbf), Int32, (Ptr{Cvoid}, Int32, Float64), hctx, 15, Float64(wide_n)))
+                try
+                    _fit_batch_locked(ctx, ns, jobs, ms)
+                finally
+                    ccall((:mrbf_set_option, libmrbf), Int32, (Ptr{Cvoid}, Int32, Float64), hctx, 15, previous[])
+                end
+            end
+        else
+            _fit_batch_locked(ctx, ns, jobs, ms)
         end
     end
     rc != 0 && _fallback_rc(11, rc) && return loop()           # the library refuses the batch: the single fit per start

@@ -38,7 +38,8 @@ def gpu_solve_shard_keep_models(problems, ctx=None, stats=None):
     """fit + eval of a shard of problem dicts with the models KEPT: one `update_models_many` call fits all of them (mrbf_fit_batch where
     the decision table allows it), then one evaluation per problem.  Returns (records, models): a record per problem as
     `gpu_solve_problem` writes it (a failed fit: its status and NaNs, model None), and the resident models in problem order -- what
-    a many-start driver hands to `descent.sd_iterate_many` (wrapped in its containers) before it frees them."""
+    a many-start driver hands to `descent.sd_iterate_many` (wrapped in its containers) before it frees them.  stats["wide"]: how many
+    problems with more than 512 sites shared the batch's launch (`update_models_many` asks mrbf_dispatch_fit_batch_max_n)."""
     from . import rbf_model as rm
 
     stats = stats if stats is not None else {}

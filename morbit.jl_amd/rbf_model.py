@@ -224,8 +224,10 @@ def update_models_many(cfgs, sites_list, values_list, deltas, fully_linear=False
     RbfModel.jl:743-767) in ONE mrbf_fit_batch call where mrbf_dispatch_fit_batch says so; otherwise, or when the call returns -2, the
     loop over update_model.  cfgs / deltas / fully_linear: one per start, or one for all.  Sites and values may be NumPy arrays or torch
     device tensors (used in place).  Returns a list of RbfModel -- for every start bit for bit the model update_model gives -- with None
-    for a start whose fit failed; stats (optional dict) receives "path" ("batch" or "loop"), "status" (return code per start) and
-    "ms_total"."""
+    for a start whose fit failed; stats (optional dict) receives "path" ("batch" or "loop"), "status" (return code per start),
+    "ms_total" and "wide": how many starts with more than 512 sites shared the batch's launch, the context's
+    MRBF_OPT_SMALL_FIT_MAX_N raised to mrbf_dispatch_fit_batch_max_n's answer for the one call and put back behind it, also on error
+    (such a start is, bit for bit, what mrbf_fit gives under that option value, not under the default)."""
     ctx = ctx or _lib.default_context()
     ns = len(sites_list)
     per = lambda v: list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v] * ns
@@ -241,7 +243,7 @@ def update_models_many(cfgs, sites_list, values_list, deltas, fully_linear=False
             except _lib.MrbfError as e:
                 mods.append(None)
                 status.append(e.code)
-        stats.update(path="loop", status=status, ms_total=float(sum(m.info["ms_total"] for m in mods if m is not None)))
+        stats.update(path="loop", status=status, ms_total=float(sum(m.info["ms_total"] for m in mods if m is not None)), wide=0)
         return mods
 
     if ctx.lib.mrbf_dispatch_fit_batch(ns) != _lib.DISPATCH_DEVICE:
@@ -264,7 +266,21 @@ def update_models_many(cfgs, sites_list, values_list, deltas, fully_linear=False
         J.centres, J.values = _lib.as_ptr(C), _lib.as_ptr(Y)
         J.weights_out, J.poly_out = _lib.as_ptr(W), _lib.as_ptr(L)
     ms = ctypes.c_float()
-    rc = ctx.lib.mrbf_fit_batch(ctx.h, ns, jobs, ctypes.byref(ms))
+    # starts beyond the one-launch fit's default range: the table says up to which n they share the batch's launch
+    # (MRBF_OPT_SMALL_FIT_MAX_N, raised for this one call); with none, nothing is asked and nothing is set
+    beyond = [(n, d) for (_, _, _, _, n, d, _, _) in keep if n > _lib.SMALL_FIT_DEFAULT_MAX_N]
+    wide_n = min((int(ctx.lib.mrbf_dispatch_fit_batch_max_n(len(beyond), d)) for _, d in beyond), default=_lib.SMALL_FIT_DEFAULT_MAX_N)
+    n_wide = sum(1 for n, _ in beyond if n <= wide_n)
+    stats["wide"] = 0
+    if n_wide:
+        previous = ctx.get_option(_lib.OPT_SMALL_FIT_MAX_N)
+        ctx.set_option(_lib.OPT_SMALL_FIT_MAX_N, wide_n)
+        try:
+            rc = ctx.lib.mrbf_fit_batch(ctx.h, ns, jobs, ctypes.byref(ms))
+        finally:
+            ctx.set_option(_lib.OPT_SMALL_FIT_MAX_N, previous)
+    else:
+        rc = ctx.lib.mrbf_fit_batch(ctx.h, ns, jobs, ctypes.byref(ms))
     if rc != 0 and ctx.lib.mrbf_dispatch_after(_lib.ENTRY_FIT_BATCH, rc) == 1:
         return loop()
     ctx.check(rc)
@@ -272,7 +288,7 @@ def update_models_many(cfgs, sites_list, values_list, deltas, fully_linear=False
     for p, (C, Y, W, L, n, d, k, q) in enumerate(keep):
         J = jobs[p]
         mods.append(RbfModel(ctx, _lib.c_vp(J.model), n, d, k, q, fls[p], W, L[:q], J.info.asdict()) if J.status == 0 else None)
-    stats.update(path="batch", status=[int(J.status) for J in jobs], ms_total=float(ms.value))
+    stats.update(path="batch", status=[int(J.status) for J in jobs], ms_total=float(ms.value), wide=n_wide)
     return mods
 
 
@@ -291,7 +307,7 @@ def update_models_resident(cfgs, dbs, index_lists, deltas, fully_linear=False, c
         by_d.setdefault(dbs[p].d, []).append(p)
     per = lambda v: list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v] * ns
     cfgs, deltas, fls = per(cfgs), per(deltas), per(fully_linear)
-    mods, status, ms, paths = [None] * ns, [0] * ns, 0.0, []
+    mods, status, ms, paths, wide = [None] * ns, [0] * ns, 0.0, [], 0
     for members in by_d.values():   # one gather and one fit call per d (a gather's views last until the next gather)
         got = database.gather_many([dbs[p] for p in members], [index_lists[p] for p in members], ctx=ctx)
         for p, g in zip(members, got):
@@ -303,9 +319,10 @@ def update_models_resident(cfgs, dbs, index_lists, deltas, fully_linear=False, c
         for pos, p in enumerate(members):
             mods[p], status[p] = res[pos], st["status"][pos]
         ms += st["ms_total"]
+        wide += st.get("wide", 0)
         paths.append(st["path"])
     if stats is not None:
-        stats.update(path="batch" if "batch" in paths else "loop", status=status, ms_total=ms)
+        stats.update(path="batch" if "batch" in paths else "loop", status=status, ms_total=ms, wide=wide)
     return mods
 
 

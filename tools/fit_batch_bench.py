@@ -7,7 +7,14 @@ mrbf_fit_batch call followed by freeing its models, against the loop of n_starts
 Medians of `--reps` host-clock calls with the event time beside them (the batch call's ms_total; the sum of info.ms_total over the
 loop) and the spread (min, max) of the host-clock calls.  --lib times another build of the library (the parent commit's, which has no
 batch entry: only the loop is timed there); one JSON line per (label, n_starts) is appended to --out.  The batch's weights are checked
-against the loop's (bit identity) before anything is timed.  One GPU process; run one label at a time."""
+against the loop's (bit identity) before anything is timed.  One GPU process; run one label at a time.
+
+    python tools/fit_batch_bench.py --wide --n 645,907,1164,1684,2048 --starts 8,16,64 --out profiles/fit_batch_wide_bench.jsonl
+
+--n times other site counts (the C4 rehearsal's model sizes beyond 512), --d another dimension (at most 128).  --wide raises the context's MRBF_OPT_SMALL_FIT_MAX_N to 2048
+for the batch call, so that starts beyond 512 sites share its one launch; the loop of single fits runs at the option's default (the
+launch chain), which is what the batch replaces.  The bit check then compares the batch with single fits under the raised option.  A
+build without the option (--lib, the parent commit's) times the loop only."""
 import argparse
 import ctypes
 import json
@@ -28,21 +35,39 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fit_batch_bench.jsonl"))
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--starts", default="1,8,64")
+    ap.add_argument("--n", default="257")
+    ap.add_argument("--d", type=int, default=128)
+    ap.add_argument("--wide", action="store_true")
     args = ap.parse_args()
     if args.lib:
         os.environ["MRBF_LIB"] = os.path.abspath(args.lib)
+    import torch  # noqa: F401  (before the library, as every driver here does)
+
+    import morbit.jl_amd as pkg
+    from morbit.jl_amd import _lib
+
+    built = ctypes.CDLL(_lib.LIB_PATH)
+    has_batch = hasattr(built, "mrbf_fit_batch")
+    has_wide = hasattr(built, "mrbf_dispatch_fit_batch_max_n")
+    for name in ("mrbf_fit_batch", "mrbf_dispatch_fit_batch", "mrbf_dispatch_fit_batch_max_n"):
+        if not hasattr(built, name):       # an earlier build: bind what it has, time the loop only
+            _lib.SIGNATURES.pop(name, None)
+    if args.wide and not has_wide:
+        has_batch = False
+    ctx = pkg.Context()
+    lib = ctx.lib
+    for n in (int(v) for v in args.n.split(",")):
+        bench_size(args, ctx, lib, n, has_batch)
+    ctx.close()
+
+
+def bench_size(args, ctx, lib, n, has_batch):
     import torch
 
     import morbit.jl_amd as pkg
     from morbit.jl_amd import _lib
 
-    has_batch = hasattr(ctypes.CDLL(_lib.LIB_PATH), "mrbf_fit_batch")
-    if not has_batch:       # an earlier build: bind what it has, time the loop only
-        for name in ("mrbf_fit_batch", "mrbf_dispatch_fit_batch"):
-            _lib.SIGNATURES.pop(name, None)
-    ctx = pkg.Context()
-    lib = ctx.lib
-    n, d, k, deg = 257, 128, 2, 1
+    d, k, deg = args.d, 2, 1
     kid, a, b = pkg.rbf_model._get_kernel_params(1.0, pkg.RbfConfig(kernel="cubic", polynomial_degree=deg))
     starts = [int(s) for s in args.starts.split(",")]
     P = max(starts)
@@ -67,7 +92,18 @@ def main():
             ctx.check(lib.mrbf_free_model(ctx.h, h))
         return ev
 
+    def option(value):
+        if args.wide and has_batch:
+            ctx.set_option(_lib.OPT_SMALL_FIT_MAX_N, value)
+
     def batch(ns):
+        option(2048)
+        try:
+            return batch_call(ns)
+        finally:
+            option(512)
+
+    def batch_call(ns):
         jobs = (_lib.FitJob * ns)()
         for p in range(ns):
             J = jobs[p]
@@ -91,9 +127,12 @@ def main():
 
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     for ns in starts:
-        rec = {"tool": "fit_batch_bench", "label": args.label, "n_starts": ns, "n": n, "d": d, "k": k, "reps": args.reps}
+        rec = {"tool": "fit_batch_bench", "label": args.label, "n_starts": ns, "n": n, "d": d, "k": k, "reps": args.reps, "wide": bool(args.wide)}
         loop(ns)
         if has_batch:
+            option(2048)     # (the reference of the bit check: single fits under the option value the batch runs with)
+            loop(ns)
+            option(512)
             ref = [W.cpu().numpy().copy() for W in Ws[:ns]]
             for W in Ws[:ns]:
                 W.fill_(float("nan"))
@@ -106,7 +145,6 @@ def main():
         print(line, flush=True)
         with open(args.out, "a") as f:
             f.write(line + "\n")
-    ctx.close()
 
 
 if __name__ == "__main__":
