@@ -99,6 +99,15 @@ enum {
                                   reproducible bit for bit under ONE value; the one-launch fit and the chain sum in different orders.
                                   The context's grow-only arena keeps the scratch of the widest batch (46 MB per start at n = 2048,
                                   d = 128; MRBF_OPT_ARENA_BYTES shows it) */
+    MRBF_OPT_SMALL_LU = 16,    /* 0 (default) or 1; any other value is an invalid argument (-2) and the stored value stays.  With 0 every
+                                  result is, bit for bit, what it always was.  With 1 a fit on the LU path (the kernel's order exceeds
+                                  what the tail covers -- thin plate spline k = 2 or cubic 5 with a linear tail, cubic 3 with a constant
+                                  or no tail, multiquadric without a tail --, n == q, or a Cholesky that gave up) with n <= 512, d <= 128,
+                                  k <= 16, n >= q and a smooth kernel takes ONE launch (small_lu.hip: getrf's arithmetic, one workgroup
+                                  per start) instead of the rocSOLVER chain, and mrbf_fit_batch puts such starts into one launch; the
+                                  bindings raise it around mrbf_fit_batch where mrbf_dispatch_fit_batch_lu says the batch pays.  Not
+                                  honoured with MRBF_OPT_GRAM_MODE 1 or a forced path other than MRBF_PATH_LU.  A fit is reproducible
+                                  bit for bit under ONE value.  Scratch: at most 3.5 MB per start in the context's arena */
     MRBF_OPT_DEBUG_FAULT = 10  /* test hook: bit 0 = one workgroup of the persistent factorisation skips a publish, bit 1 = one workgroup of
                                   the persistent backward substitution does (the next fit must fall back and still return the right weights), bit 2 = one
                                   member of a small fit's workgroup cluster leaves early (the fit is repeated with one workgroup per problem) */
@@ -335,6 +344,10 @@ int32_t mrbf_batch_run(int32_t n_dev, const int32_t *device_ids, int64_t n_probl
  * Starts in the range of the one-launch fit (n <= the context's MRBF_OPT_SMALL_FIT_MAX_N, d <= 128, k <= 16, Cholesky paths) share a handful of launches whose grids
  * span all of them, one packed descriptor upload and one read-back; every other start, and a start whose batched fit raised a flag
  * (not positive definite, rank-deficient tail), takes mrbf_fit inside the same call.
+ * With MRBF_OPT_SMALL_LU at 1 the starts on the LU path inside that option's range share launches of their own in the same way (one
+ * descriptor upload, one LU launch, the residual evaluations and the check kernel, one read-back; their models live in the call's
+ * allocation as well); a singular start among them gets status MRBF_ESINGULAR and no model, and does not disturb its neighbours.
+ * mrbf_batch_run does not look at the option.
  * Lifetime: jobs[p].model is a handle like any other -- mrbf_eval, mrbf_sd_iterate_batch, mrbf_ps_step_problem, mrbf_model_dims
  * accept it, MRBF_OPT_LIVE_HANDLES counts it, and the caller releases it with mrbf_free_model, in any order.  The models of one
  * call that took the batched path are carved from one device allocation of that call; each holds a share, and the allocation goes
@@ -837,6 +850,10 @@ int32_t mrbf_ps_step_batch(mrbf_ctx *ctx, int64_t n_starts, const mrbf_ps_proble
  *                            calls (512: the option's default, starts beyond it take mrbf_fit inside the call) where the batch does
  *                            not pay (measured, DESIGN.md section 12: 1684 from 8 starts on, 2048 from 16 on, at 65 <= d <= 128);
  *                            n_starts < 1 or > 65535, or d outside 1 .. 128: 512.
+ *   mrbf_dispatch_fit_batch_lu  1 where the bindings set MRBF_OPT_SMALL_LU around mrbf_fit_batch: n_lu_starts of the call's starts are
+ *                            on the LU path inside that option's range, the largest of them has n_max sites, their dimension is d.
+ *                            Measured cells only (tools/fit_batch_lu_bench.py; admitted where the batch took at
+ *                            most 0.8 of the loop of single calls), monotone in n_lu_starts; anything else: 0, the option stays off.
  *   mrbf_dispatch_round4_batch  _rbf_round4 of n_starts starts in one call (mrbf_round4_batch): device iff 1 <= n_starts <= 65535 (a grid
  *                            dimension) and 1 <= d <= 1024 (mrbf_round4's own limit).  Which starts share the batched launches (the small
  *                            range: d <= 128, q <= n0 <= 256, mc <= 4096, at most 256 sites to accept) is decided inside the call.
@@ -878,6 +895,7 @@ int32_t mrbf_dispatch_affine_batch(int64_t n_starts, int32_t d, int32_t p_is_inf
 int32_t mrbf_dispatch_round4(int64_t n0, int32_t d, int32_t poly_deg, int64_t n_candidates);
 int32_t mrbf_dispatch_fit_batch(int64_t n_starts);
 int64_t mrbf_dispatch_fit_batch_max_n(int64_t n_starts, int32_t d);
+int32_t mrbf_dispatch_fit_batch_lu(int64_t n_lu_starts, int64_t n_max, int32_t d);
 int32_t mrbf_dispatch_round4_batch(int64_t n_starts, int32_t d);
 int32_t mrbf_dispatch_db_batch(int64_t n_starts, int32_t d);
 int32_t mrbf_dispatch_fit(int64_t n_training, int64_t state_n0, int32_t state_q, int32_t state_n_accepted, int32_t same_sites);

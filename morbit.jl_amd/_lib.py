@@ -20,6 +20,8 @@ OPT_SPIN_MS, OPT_DEBUG_FAULT, OPT_LAST_DEVICE_MS, OPT_SLOW_LAUNCHES = 9, 10, 11,
 OPT_ARENA_BYTES, OPT_LIVE_HANDLES = 13, 14   # read only
 OPT_SMALL_FIT_MAX_N = 15                     # most sites the one-launch fit takes: 512 (default) .. 2048
 SMALL_FIT_DEFAULT_MAX_N = 512
+OPT_SMALL_LU = 16                            # 1: LU-path fits with n <= 512, d <= 128, k <= 16 take the one-launch LU (default 0)
+SMALL_LU_MAX_N, SMALL_LU_MAX_D, SMALL_LU_MAX_K = 512, 128, 16
 FB_CHOL_HOST_DRIVEN, FB_BACKSOLVE_BLOCKED, FB_LU = 1, 2, 4
 
 
@@ -248,6 +250,7 @@ SIGNATURES = {
     "mrbf_fit_batch": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.POINTER(FitJob), c_fp]),
     "mrbf_dispatch_fit_batch": (ctypes.c_int32, [ctypes.c_int64]),
     "mrbf_dispatch_fit_batch_max_n": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32]),
+    "mrbf_dispatch_fit_batch_lu": (ctypes.c_int32, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32]),
     "mrbf_db_create": (ctypes.c_int32, [c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.POINTER(c_vp)]),
     "mrbf_db_append": (ctypes.c_int32, [c_vp, c_vp, ctypes.c_int64, c_vp, c_vp, ctypes.POINTER(ctypes.c_int64)]),
     "mrbf_db_set_values": (ctypes.c_int32, [c_vp, c_vp, ctypes.c_int64, c_vp, c_vp]),

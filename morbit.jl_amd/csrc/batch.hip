@@ -20,6 +20,8 @@
 //     1   small_mean_kernel, 1 small_fit_kernel, 1 center_pad_batch_kernel, 2 eval_fused / eval_combine, 1 batch_check_kernel
 //     1   batch_copy_kernel           weights and tail coefficients -> outputs given as device pointers
 // Starts outside the one-launch range and flagged starts take mrbf_fit on the same context inside the call.
+// Under MRBF_OPT_SMALL_LU the starts on the LU path inside small_lu_applies' range form launch groups of their own: the same
+// launches with small_lu_kernel (small_lu.hip) in the place of small_fit_kernel.  mrbf_batch_run never takes that route.
 #include <algorithm>
 #include <thread>
 
@@ -172,8 +174,11 @@ static int launch_batch_copy(mrbf_ctx *ctx, const CopySeg *hsegs, const CopySeg 
 // keep (mrbf_fit_batch; indexed like `problems`, every m = 0): the model arrays of problem p are keep[p]'s -- storage that outlives the
 // call -- instead of arena positions: the centres are copied (or uploaded) there first, the fit writes Xc, sq, mean, W, Wc and lam
 // there, and weights_out / poly_out receive copies.  *ms_sum (may be NULL) += the event time of every launch group that ran.
+// lu (mrbf_fit_batch under MRBF_OPT_SMALL_LU): the problems are on the LU path inside small_lu_applies' range -- the fit launch is
+// small_lu_kernel (one workgroup per problem, scratch from the arena slot S_SMALL_LU), a singular problem gets status MRBF_ESINGULAR
+// instead of a place in `redo`; everything around the fit launch is the same.
 static int run_small_batch(mrbf_ctx *ctx, const std::vector<int64_t> &idx, const mrbf_problem *problems, mrbf_result *results,
-                           std::vector<int64_t> *redo, int force_nc = 0, const mrbf_model *keep = nullptr, float *ms_sum = nullptr) {
+                           std::vector<int64_t> *redo, int force_nc = 0, const mrbf_model *keep = nullptr, float *ms_sum = nullptr, bool lu = false) {
     const int P = (int)idx.size();
     if (P == 0) return 0;
     (void)hipSetDevice(ctx->device);
@@ -184,7 +189,7 @@ static int run_small_batch(mrbf_ctx *ctx, const std::vector<int64_t> &idx, const
         bool w_host, lam_host;  // weights_out / poly_out are host memory: copied back behind the launches
     };
     std::vector<Lay> lay(P);
-    size_t total = 0;
+    size_t total = 0, lu_total = 0;
     auto take = [&](size_t cnt) {
         const size_t at = total;
         total += al16(std::max<size_t>(cnt, 1));
@@ -218,7 +223,12 @@ static int run_small_batch(mrbf_ctx *ctx, const std::vector<int64_t> &idx, const
             L.Wc = take((size_t)L.npad * k);
             if (!lam_dev) L.lam = take((size_t)std::max(L.q, 1) * k);
         }
-        L.ws = take(smallfit::carve((int)L.npad, q16).total);
+        if (lu) {  // (an offset into S_SMALL_LU)
+            L.ws = lu_total;
+            lu_total += al16(small_lu_scratch_doubles(pr.n, L.q));
+        } else {
+            L.ws = take(smallfit::carve((int)L.npad, q16).total);
+        }
         // evaluation 0: the fit's residual at the sites; evaluation 1: the caller's queries
         L.mpad0 = check ? round_up(pr.n, 64) : 0;
         L.nsplit0 = check ? eval_nsplit(ctx, pr.n, (int)((pr.n + 63) / 64), true) : 1;
@@ -243,14 +253,15 @@ static int run_small_batch(mrbf_ctx *ctx, const std::vector<int64_t> &idx, const
     const size_t arena_budget = (size_t)(mrbf_env("MRBF_BATCH_ARENA_MB") ? atoll(mrbf_env("MRBF_BATCH_ARENA_MB")) : 8192) << 20;
     auto halves = [&]() -> int {
         const std::vector<int64_t> lo(idx.begin(), idx.begin() + P / 2), hi(idx.begin() + P / 2, idx.end());
-        MRBF_TRY(run_small_batch(ctx, lo, problems, results, redo, force_nc, keep, ms_sum));
-        return run_small_batch(ctx, hi, problems, results, redo, force_nc, keep, ms_sum);
+        MRBF_TRY(run_small_batch(ctx, lo, problems, results, redo, force_nc, keep, ms_sum, lu));
+        return run_small_batch(ctx, hi, problems, results, redo, force_nc, keep, ms_sum, lu);
     };
-    if (P > 1 && total * sizeof(double) > arena_budget) return halves();
-    double *base;
+    if (P > 1 && (total + lu_total) * sizeof(double) > arena_budget) return halves();
+    double *base, *lu_base = nullptr;
     int *flags = nullptr;
     {
-        const int rc = get_buf(ctx, S_SMALL_WS, total, &base);
+        int rc = get_buf(ctx, S_SMALL_WS, total, &base);
+        if (rc == 0 && lu) rc = get_buf(ctx, S_SMALL_LU, lu_total, &lu_base);
         if (rc == MRBF_ENOMEM && P > 1) return halves();
         if (rc != 0) return rc;
     }
@@ -327,7 +338,7 @@ static int run_small_batch(mrbf_ctx *ctx, const std::vector<int64_t> &idx, const
             M.Wc = base + L.Wc;
             M.lam = L.lam == (size_t)-1 ? pr.poly_out : base + L.lam;
         }
-        fill_small_prob(ctx, &M, Y, base + L.ws, flags + 4 * i, base + L.out + 5, dcl + smallfit::CL_WORDS * i, &probs[i]);
+        fill_small_prob(ctx, &M, Y, lu ? lu_base + L.ws : base + L.ws, flags + 4 * i, base + L.out + 5, dcl + smallfit::CL_WORDS * i, &probs[i]);
         probs[i].mean_given = 1;  // small_mean_kernel below: the queries are centred beside the fit, not after it
         for (int e = 0; e < 2; ++e) {
             EvalDesc &E = evs[(size_t)e * P + i];  // [residual evaluations of all problems | query evaluations of all problems]
@@ -374,7 +385,7 @@ static int run_small_batch(mrbf_ctx *ctx, const std::vector<int64_t> &idx, const
         MRBF_HIP(ctx, hipMemcpyAsync(ddesc, hd, desc_bytes, hipMemcpyHostToDevice, st));
     }
     MRBF_HIP(ctx, hipEventRecord(ctx->ev[0], st));
-    const int nc = force_nc > 0 ? force_nc : small_fit_cluster(ctx, P);
+    const int nc = lu ? 1 : (force_nc > 0 ? force_nc : small_fit_cluster(ctx, P));
     hipStream_t side = (ctx->panel_stream && ctx->panel_stream != st) ? ctx->panel_stream : st;
     // the centroids first (the fit kernel's own arithmetic, small.hip: column_means), then -- on the side stream, under the
     // latency-bound fit launch -- the centring of all evaluation points of the batch (sites for the residual, queries): 423 MB of
@@ -387,7 +398,10 @@ static int run_small_batch(mrbf_ctx *ctx, const std::vector<int64_t> &idx, const
     }
     // (the fit launch first: its workgroups -- one per CU, clusters that meet at barriers -- are all resident before the centring's
     //  1600 blocks arrive on the high-priority side stream; the other way round the fit took 0.83 or 0.96 ms from run to run)
-    MRBF_TRY(launch_small_fit(ctx, probs.data(), P, dprobs, nc));
+    if (lu)
+        MRBF_TRY(launch_small_lu(ctx, probs.data(), P, dprobs));
+    else
+        MRBF_TRY(launch_small_fit(ctx, probs.data(), P, dprobs, nc));
     MRBF_HIP(ctx, hipEventRecord(ctx->ev[1], st));
     if (keep) {  // coefficients -> outputs in device memory (a launch per group: at most P segments on a grid dimension)
         MRBF_TRY(launch_batch_copy(ctx, segs.data() + P, dsegs + P, P));
@@ -504,7 +518,7 @@ static int run_small_batch(mrbf_ctx *ctx, const std::vector<int64_t> &idx, const
             // solve.hip).  A problem that is ill-conditioned in its own right (near-duplicate sites of a trust region) gives the same
             // residual either way and must not cost a pooled context its clusters for the rest of the process.
             if (worst == 2 || (worst == 1 && ++ctx->small_timeouts >= 3)) ctx->small_nc = 1;
-            const int rc1 = run_small_batch(ctx, idx, problems, results, redo, 1, keep, ms_sum);
+            const int rc1 = run_small_batch(ctx, idx, problems, results, redo, 1, keep, ms_sum, lu);
             if (rc1 == 0 && worst == 0) {
                 for (const auto &sp : suspects) {
                     const double r1 = results[sp.first].fit.rel_residual;
@@ -529,7 +543,14 @@ static int run_small_batch(mrbf_ctx *ctx, const std::vector<int64_t> &idx, const
         res.fit.rel_residual = NAN;
         res.fit.max_pitw = NAN;
         const double *o = &hout[(size_t)8 * i];
-        if (small_fit_verdict(&models[i], &hflags[(size_t)4 * i], o + 5, &res.fit)) {
+        if (lu) {  // as fit_lu sets them
+            res.fit.path = MRBF_PATH_LU;
+            res.fit.factor_info = hflags[(size_t)4 * i];
+            if (res.fit.factor_info != 0) {
+                res.status = MRBF_ESINGULAR;
+                continue;
+            }
+        } else if (small_fit_verdict(&models[i], &hflags[(size_t)4 * i], o + 5, &res.fit)) {
             redo->push_back(idx[i]);  // not positive definite / rank-deficient tail: the per-problem chain takes the LU path
             continue;
         }
@@ -557,6 +578,16 @@ static bool batch_takes(const mrbf_ctx *ctx, int64_t n, int d, int k, int kernel
     return ctx->force_path == 0 && ctx->eval_impl != 1 && small_fit_applies(ctx, n, d, k, q, path);
 }
 
+// ... and the batched LU launch (MRBF_OPT_SMALL_LU; mrbf_fit_batch only): a start that fit_model would send to fit_lu -- the kernel's
+// order beyond the tail, n == q, or the path forced -- inside small_lu_applies' range
+static bool batch_takes_lu(const mrbf_ctx *ctx, int64_t n, int d, int k, int kernel_id, double a, double b, int poly_deg) {
+    if (kernel_id < 0 || kernel_id > 4 || poly_deg < -1 || poly_deg > 1) return false;
+    const int q = poly_dim(d, poly_deg);
+    const bool chol = n > q && cpd_order(kernel_id, a, b) <= poly_deg + 1;
+    if ((chol && ctx->force_path != MRBF_PATH_LU) || ctx->eval_impl == 1) return false;
+    return small_lu_applies(ctx, n, d, k, q, make_kp(kernel_id, a, b));
+}
+
 }  // namespace mrbf
 
 using namespace mrbf;
@@ -573,7 +604,7 @@ extern "C" int32_t mrbf_fit_batch(mrbf_ctx *ctx, int64_t n_starts, mrbf_fit_job 
     }
     (void)hipSetDevice(ctx->device);
     float ms_sum = 0.f;
-    std::vector<int64_t> small, single, redo;
+    std::vector<int64_t> small, small_lu, single, redo;
     std::vector<mrbf_problem> problems((size_t)n_starts);
     std::vector<mrbf_result> results((size_t)n_starts);
     std::vector<mrbf_model> shells((size_t)n_starts);
@@ -597,40 +628,47 @@ extern "C" int32_t mrbf_fit_batch(mrbf_ctx *ctx, int64_t n_starts, mrbf_fit_job 
         pr.values = J.values;
         pr.weights_out = J.weights_out;
         pr.poly_out = J.poly_out;
-        if (!batch_takes(ctx, J.n, J.d, J.k, J.kernel_id, J.a, J.b, J.poly_deg)) {
+        if (batch_takes(ctx, J.n, J.d, J.k, J.kernel_id, J.a, J.b, J.poly_deg)) {
+            small.push_back(p);
+        } else if (batch_takes_lu(ctx, J.n, J.d, J.k, J.kernel_id, J.a, J.b, J.poly_deg)) {
+            small_lu.push_back(p);
+        } else {
             single.push_back(p);
             continue;
         }
         // the model's share of the slab: carved exactly as build_model_shell carves a block of its own
-        small.push_back(p);
         model_set_dims(&shells[p], J.n, J.d, J.k, J.kernel_id, J.a, J.b, J.poly_deg);
         size_t off[7];
         at[p] = total;
         total += model_block_layout(&shells[p], off);
     }
     ModelSlab *slab = nullptr;
-    if (!small.empty()) {
+    if (!small.empty() || !small_lu.empty()) {
         slab = new ModelSlab();
         if (model_block_acquire(ctx, total, &slab->p, &slab->bytes) != 0) {  // no room for the slab: every start on its own
             delete slab;
             slab = nullptr;
             single.insert(single.end(), small.begin(), small.end());
+            single.insert(single.end(), small_lu.begin(), small_lu.end());
             small.clear();
+            small_lu.clear();
         }
     }
     if (slab) {
-        for (int64_t p : small) {
-            size_t off[7];
-            (void)model_block_layout(&shells[p], off);
-            model_carve(&shells[p], (char *)slab->p + at[p], off);
-        }
+        for (const std::vector<int64_t> *list : {&small, &small_lu})
+            for (int64_t p : *list) {
+                size_t off[7];
+                (void)model_block_layout(&shells[p], off);
+                model_carve(&shells[p], (char *)slab->p + at[p], off);
+            }
         // groups of at most 32767 starts: the batched launches put up to two descriptors per start on a grid dimension (65535).  A group
         // whose launches fail has failed as a whole: every start of it carries the return code, none keeps a model or is fitted again.
         constexpr size_t GROUP = 32767;
-        for (size_t g0 = 0; g0 < small.size(); g0 += GROUP) {
-            const std::vector<int64_t> group(small.begin() + g0, small.begin() + std::min(small.size(), g0 + GROUP));
+        for (const std::vector<int64_t> *list : {&small, &small_lu})  // the Cholesky-path starts, then the LU-path starts: launches of their own
+        for (size_t g0 = 0; g0 < list->size(); g0 += GROUP) {
+            const std::vector<int64_t> group(list->begin() + g0, list->begin() + std::min(list->size(), g0 + GROUP));
             std::vector<int64_t> flagged;
-            const int rc = run_small_batch(ctx, group, problems.data(), results.data(), &flagged, 0, shells.data(), &ms_sum);
+            const int rc = run_small_batch(ctx, group, problems.data(), results.data(), &flagged, 0, shells.data(), &ms_sum, list == &small_lu);
             if (rc != 0) {
                 (void)hipStreamSynchronize(ctx->stream);
                 for (int64_t p : group) jobs[p].status = rc;
@@ -640,6 +678,11 @@ extern "C" int32_t mrbf_fit_batch(mrbf_ctx *ctx, int64_t n_starts, mrbf_fit_job 
             for (int64_t p : group) {
                 if (std::binary_search(flagged.begin(), flagged.end(), p)) continue;
                 mrbf_fit_job &J = jobs[p];
+                if (results[p].status != 0) {  // (a singular start of the LU launch: its status and info, no model)
+                    J.status = results[p].status;
+                    J.info = results[p].fit;
+                    continue;
+                }
                 mrbf_model *M = new mrbf_model(shells[p]);
                 M->slab = slab;
                 ++slab->refs;

@@ -42,7 +42,7 @@ enum Slot {
     S_XC = 0, S_SQ, S_MEAN, S_PHI, S_PI, S_Q1, S_W1, S_G, S_R, S_TAU, S_RHS, S_T1, S_T2, S_IPIV, S_INFO,
     S_STAGE_A, S_STAGE_B, S_STAGE_C, S_STAGE_D, S_EVAL_E, S_EVAL_A, S_EVAL_J, S_EVAL_SA, S_EVAL_XC, S_EVAL_XSQ,
     S_OUT_A, S_OUT_B, S_CHOL_WS, S_MISC, S_MEGA_JOBS, S_MEGA_FLAGS, S_MEGA_WQ, S_MEGA_IT, S_BSOLVE_FLAGS, S_MEGA_TRACE, S_MEGA_JLOG,
-    S_T1W, S_PS_STATE, S_PS_STAT, S_PS_POLISH, S_BSOLVE_X, S_V0, S_QR_INV, S_DIAG_SCR, S_SMALL_WS, S_SMALL_DESC, S_SMALL_FLAGS, S_MEGA_STAT, S_BSOLVE_M, S_SMALL_CL, S_GW_PART, S_GW_RS, S_GW_GP, S_GW_M, S_CHECK_SCAL, S_TAIL_PART, S_PS_RANK, S_SD_IN, S_SD_OUT, S_SD_WS, S_NS_IN, S_NS_OUT, S_NS_WS, S_SD_STEP, S_SD_BATCH, S_AFF_BATCH, S_NS_BATCH, S_R4_BATCH, S_DB_BOX, S_DB_GATHER, S_DB_WS, S_NSLOTS
+    S_T1W, S_PS_STATE, S_PS_STAT, S_PS_POLISH, S_BSOLVE_X, S_V0, S_QR_INV, S_DIAG_SCR, S_SMALL_WS, S_SMALL_DESC, S_SMALL_FLAGS, S_MEGA_STAT, S_BSOLVE_M, S_SMALL_CL, S_GW_PART, S_GW_RS, S_GW_GP, S_GW_M, S_CHECK_SCAL, S_TAIL_PART, S_PS_RANK, S_SD_IN, S_SD_OUT, S_SD_WS, S_NS_IN, S_NS_OUT, S_NS_WS, S_SD_STEP, S_SD_BATCH, S_AFF_BATCH, S_NS_BATCH, S_R4_BATCH, S_DB_BOX, S_DB_GATHER, S_DB_WS, S_SMALL_LU, S_NSLOTS
 };
 }  // namespace mrbf
 
@@ -149,6 +149,7 @@ struct mrbf_ctx {
     int small_cluster_ok = 0;    // the device is what the clusters' visibility argument assumes: gfx950, 8 XCDs x 32 CUs (context.hip)
     int small_timeouts = 0;      // barrier time-outs of clustered launches in a row (three: clusters off for this context)
     int small_fit_max_n = 512;   // MRBF_OPT_SMALL_FIT_MAX_N: most sites the one-launch fit takes (small_fit_applies), 512 .. 2048
+    int small_lu = 0;            // MRBF_OPT_SMALL_LU: 1 sends LU-path fits inside small_lu_applies' range to the one-launch LU (small_lu.hip)
     int live_models = 0, live_round4 = 0;  // handles created through this context and not yet released (MRBF_OPT_LIVE_HANDLES)
     int live_dbs = 0;                      // likewise: resident site databases (db.hip)
     unsigned ps_rank_epoch = 0;  // launches of the PS ranking's wave kernel so far (part of the tag its exchanged records carry)

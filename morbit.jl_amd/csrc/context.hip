@@ -392,6 +392,10 @@ int32_t mrbf_set_option(mrbf_ctx *ctx, int32_t key, double value) {
             if (!(value >= 512.0 && value <= 2048.0)) return fail(ctx, -2, "MRBF_OPT_SMALL_FIT_MAX_N: %g is not in 512 .. 2048", value);
             ctx->small_fit_max_n = v;
             break;
+        case MRBF_OPT_SMALL_LU:
+            if (!(value == 0.0 || value == 1.0)) return fail(ctx, -2, "MRBF_OPT_SMALL_LU: %g is not 0 or 1", value);
+            ctx->small_lu = v;
+            break;
         default: return fail(ctx, -2, "unknown option key %d", key);
     }
     return MRBF_OK;
@@ -412,6 +416,7 @@ int32_t mrbf_get_option(const mrbf_ctx *ctx, int32_t key, double *value) {
         case MRBF_OPT_SPIN_MS: *value = ctx->spin_ms; break;
         case MRBF_OPT_DEBUG_FAULT: *value = ctx->debug_fault; break;
         case MRBF_OPT_SMALL_FIT_MAX_N: *value = ctx->small_fit_max_n; break;
+        case MRBF_OPT_SMALL_LU: *value = ctx->small_lu; break;
         case MRBF_OPT_LAST_DEVICE_MS: *value = ctx->last_device_ms; break;
         case MRBF_OPT_SLOW_LAUNCHES: *value = ctx->slow_launches; break;
         case MRBF_OPT_ARENA_BYTES: {

@@ -18,6 +18,16 @@ struct FitWideRow {
 constexpr FitWideRow FIT_WIDE[] = {{8, 1684}, {16, 2048}};
 constexpr int FIT_WIDE_MIN_D = 65;  // the padded dimension the cells were measured at (dpad = 128); d <= 64 has another chain and no measurement
 constexpr int FIT_WIDE_ROWS = (int)(sizeof(FIT_WIDE) / sizeof(FIT_WIDE[0]));
+// mrbf_dispatch_fit_batch_lu: from min_starts LU-path starts on, the one-launch LU takes the batch up to max_n sites and dimension max_d
+// (rows ascending in all three).  Measured (profiles/fit_batch_lu_bench.jsonl: thin plate spline k = 2, degree-1 tail, k = 2, 30 calls
+// each): batch / loop of single calls = 0.87, 1.24, 1.96 with 1 start at (n, d) = (33, 16), (257, 128), (512, 128) -- not admitted --,
+// 0.12, 0.16, 0.25 with 8 starts, 0.065, 0.082, 0.13 with 16 and 0.023, 0.023, 0.035 with 64; 2 .. 7 starts were not measured
+struct FitLuRow {
+    int64_t min_starts, max_n;
+    int max_d;
+};
+constexpr FitLuRow FIT_LU[] = {{8, 512, 128}};
+constexpr int FIT_LU_ROWS = (int)(sizeof(FIT_LU) / sizeof(FIT_LU[0]));
 }  // namespace
 
 extern "C" {
@@ -118,6 +128,18 @@ int64_t mrbf_dispatch_fit_batch_max_n(int64_t n_starts, int32_t d) {
     for (int i = FIT_WIDE_ROWS - 1; i >= 0; --i)
         if (n_starts >= FIT_WIDE[i].min_starts) return FIT_WIDE[i].max_n;
     return 512;
+}
+
+// whether the bindings set MRBF_OPT_SMALL_LU around mrbf_fit_batch: n_lu_starts of the call's starts are on the LU path inside the
+// option's range (small_lu.hip: n <= 512, d <= 128), the largest with n_max sites, of dimension d.  Modelled on the row above: measured
+// cells only -- a row (min_starts, max_n, max_d) is admitted where the batch under the option took at most 0.8 of the median of the loop
+// of single calls with the option off (tools/fit_batch_lu_bench.py, profiles/fit_batch_lu_bench.jsonl) --, rows
+// ascending in all three columns, so that the answer is monotone in n_lu_starts; a shape beyond the largest measured one of its row: 0.
+int32_t mrbf_dispatch_fit_batch_lu(int64_t n_lu_starts, int64_t n_max, int32_t d) {
+    if (n_lu_starts < 1 || n_lu_starts > 65535 || n_max < 1 || n_max > 512 || d < 1 || d > 128) return 0;
+    for (int i = FIT_LU_ROWS - 1; i >= 0; --i)
+        if (n_lu_starts >= FIT_LU[i].min_starts) return n_max <= FIT_LU[i].max_n && d <= FIT_LU[i].max_d ? 1 : 0;
+    return 0;
 }
 
 int32_t mrbf_dispatch_round4(int64_t n0, int32_t d, int32_t poly_deg, int64_t n_candidates) {

@@ -123,6 +123,17 @@ int small_fit_cluster(const mrbf_ctx *ctx, int count);
 // the centroids of `count` problems into their `mean` arrays (what small_fit_kernel computes itself unless Prob::mean_given)
 int launch_small_means(mrbf_ctx *ctx, const smallfit::Prob *dev_probs, int count);
 
+// small_lu.hip: the LU path of a small problem as one launch (opt-in, MRBF_OPT_SMALL_LU).  Does it take a problem of this shape on this
+// context?  The option is on, n <= 512, d <= 128, k <= 16, n >= q, a smooth kernel (GEMM-form assembly), gram_mode 0 and no path
+// forced other than LU.  The caller has already decided that the problem is on the LU path.
+bool small_lu_applies(const mrbf_ctx *ctx, int64_t n, int d, int k, int q, const KP &kp);
+// scratch of one problem (Prob::ws): the saddle matrix and, beside it, sixteen right-hand sides -- N16^2 + 16 N16 doubles with
+// N16 = round_up(n + q, 16), 3.5 MB at most
+size_t small_lu_scratch_doubles(int64_t n, int q);
+// one workgroup per descriptor; count == 1 and dev_probs == nullptr: the descriptor travels as a kernel argument.  Of a descriptor the
+// kernel reads the shape, kp, C, Y, the model's arrays, ws, flags ([0]: getrf's info, the rest zero), scal (zeroed) and mean_given.
+int launch_small_lu(mrbf_ctx *ctx, const smallfit::Prob *host_probs, int count, const smallfit::Prob *dev_probs);
+
 // The tail basis of the launch chain in three launches (small.hip, TailQ): Q1 = [1/sqrt n | Xc Lx^-T], inv(Lx) (128 x 128, identity
 // padded), T1 = Q1' Y, B = Y - Q1 T1 (npad x k, zero rows beyond n) and, if rows_out, the right-hand sides as rows npad .. npad + xt - 1
 // of the matrix; flags[1] = 1-based index of a non-positive pivot of Xc'Xc (affinely dependent sites) or 0.  d <= 64, k <= 16, q = d + 1.

@@ -231,6 +231,7 @@ static int read_info(mrbf_ctx *ctx, const int *dinfo, int *hinfo) {
 }
 
 // ---- LU on the saddle system ---------------------------------------------------------------------
+void fill_small_prob(const mrbf_ctx *ctx, const mrbf_model *M, const double *Y, double *ws, int *flags, double *scal, int *cl, smallfit::Prob *P);
 static int fit_lu(mrbf_ctx *ctx, mrbf_model *M, const double *Y, mrbf_fit_info *info) {
     const int64_t n = M->n, N = n + M->q;
     const int k = M->k, q = M->q;
@@ -268,6 +269,30 @@ static int fit_lu(mrbf_ctx *ctx, mrbf_model *M, const double *Y, mrbf_fit_info *
     MRBF_HIP(ctx, hipEventElapsedTime(&info->ms_project, ctx->ev[1], ctx->ev[5]));
     MRBF_HIP(ctx, hipEventElapsedTime(&info->ms_factor, ctx->ev[5], ctx->ev[2]));
     MRBF_HIP(ctx, hipEventElapsedTime(&info->ms_solve, ctx->ev[2], ctx->ev[3]));
+    return 0;
+}
+
+// The same system as ONE launch (small_lu.hip; MRBF_OPT_SMALL_LU): one read-back, info as fit_lu sets it
+static int fit_small_lu(mrbf_ctx *ctx, mrbf_model *M, const double *Y, mrbf_fit_info *info) {
+    smallfit::Prob P;
+    double *ws, *scal;
+    int *flags;
+    MRBF_TRY(get_buf(ctx, S_SMALL_LU, small_lu_scratch_doubles(M->n, M->q), &ws));
+    MRBF_TRY(get_buf(ctx, S_SMALL_FLAGS, (size_t)4, &flags));
+    MRBF_TRY(get_buf(ctx, S_MISC, (size_t)8, &scal));
+    fill_small_prob(ctx, M, Y, ws, flags, scal, nullptr, &P);
+    int hflags_local[4] = {0, 0, 0, 0};
+    int *hflags = ctx->hpin ? reinterpret_cast<int *>(ctx->hpin + HPIN_SMALL_FLAGS) : hflags_local;
+    MRBF_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    MRBF_TRY(launch_small_lu(ctx, &P, 1, nullptr));
+    MRBF_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    MRBF_HIP(ctx, hipMemcpyAsync(hflags, flags, 4 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    MRBF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    info->factor_info = hflags[0];
+    info->path = MRBF_PATH_LU;
+    if (hflags[0] != 0)
+        return fail(ctx, MRBF_ESINGULAR, "saddle matrix is singular (getrf info = %d, N = %lld)", hflags[0], (long long)(M->n + M->q));
+    MRBF_HIP(ctx, hipEventElapsedTime(&info->ms_factor, ctx->ev[0], ctx->ev[1]));  // one launch: assembly, factorisation, both substitutions
     return 0;
 }
 
@@ -1120,7 +1145,12 @@ int fit_model(mrbf_ctx *ctx, mrbf_model *M, const double *Y, mrbf_fit_info *info
             path = MRBF_PATH_LU;  // retry on the saddle system (re-assembles Phi)
         }
     }
-    if (path == MRBF_PATH_LU) MRBF_TRY(fit_lu(ctx, M, Y, info));
+    if (path == MRBF_PATH_LU) {
+        if (small_lu_applies(ctx, M->n, M->d, M->k, M->q, M->kp))
+            MRBF_TRY(fit_small_lu(ctx, M, Y, info));
+        else
+            MRBF_TRY(fit_lu(ctx, M, Y, info));
+    }
     if (ctx->residual && !(checked && path != MRBF_PATH_LU)) MRBF_TRY(fit_check(ctx, M, Y, info));
     if (ctx->residual && small_nc_used > 1 && path != MRBF_PATH_LU && !(info->rel_residual < 1e-6)) {
         // tripwire of the workgroup clusters (small.hip): a clustered fit that does not interpolate is repeated with one workgroup

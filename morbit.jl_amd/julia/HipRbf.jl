@@ -287,6 +287,16 @@ _dispatch_affine_batch(n_starts, d, p) =
     ccall((:mrbf_dispatch_affine_batch, libmrbf), Int32, (Int64, Int32, Int32), n_starts, d, isinf(p) ? 1 : 0) == 1
 _dispatch_fit_batch(n_starts) = ccall((:mrbf_dispatch_fit_batch, libmrbf), Int32, (Int64,), n_starts) == 1
 _dispatch_fit_batch_max_n(n_starts, d) = Int(ccall((:mrbf_dispatch_fit_batch_max_n, libmrbf), Int64, (Int64, Int32), n_starts, d))
+_dispatch_fit_batch_lu(n_lu_starts, n_max, d) = ccall((:mrbf_dispatch_fit_batch_lu, libmrbf), Int32, (Int64, Int64, Int32), n_lu_starts, n_max, d) == 1
+# is a start on the LU path (fit_model, solve.hip: the kernel's order exceeds what the tail covers, or n == q) and inside the range of
+# MRBF_OPT_SMALL_LU (n <= 512, d <= 128, k <= 16, n >= q, a smooth kernel)?  params = (kernel id, a, b) as _mrbf_kernel_params gives them
+function _takes_small_lu(params, deg, n, d, k)
+    kid, a, b = params
+    q = deg < 0 ? 0 : (deg == 0 ? 1 : d + 1)
+    order = kid == 0 ? ceil(Int, a / 2) : (kid == 2 ? ceil(Int, b) : (kid == 3 ? Int(a) + 1 : 0))
+    nonsmooth = (kid == 0 || kid == 3) && a == 1
+    return !(order <= deg + 1 && n > q) && n >= q && n <= 512 && d <= 128 && k <= 16 && !nonsmooth
+end
 _dispatch_round4_batch(n_starts, d) = ccall((:mrbf_dispatch_round4_batch, libmrbf), Int32, (Int64, Int32), n_starts, d) == 1
 _dispatch_round4(n0, d, deg, n_candidates) =
     ccall((:mrbf_dispatch_round4, libmrbf), Int32, (Int64, Int32, Int32, Int64), n0, d, deg, n_candidates) == 1
@@ -1331,18 +1341,31 @@ function hip_update_models_many(cfgs::AbstractVector{HipRbfConfig}, Cs::Abstract
                                  pointer(Ys[q]), C_NULL, C_NULL, C_NULL, 0, 0, zero_info)
         end
         # starts beyond the one-launch fit's default range share the batch's launch up to the n the table names: the context's
-        # MRBF_OPT_SMALL_FIT_MAX_N (key 15) is raised for this one call and put back behind it, also on error, under the context's lock
+        # MRBF_OPT_SMALL_FIT_MAX_N (key 15) is raised for this one call and put back behind it, also on error, under the context's lock.
+        # Likewise MRBF_OPT_SMALL_LU (key 16) where the table admits the call's LU-path starts (mrbf_dispatch_fit_batch_lu).
         beyond = [q for q in 1:ns if size(Cs[q], 2) > 512]
         wide_n = isempty(beyond) ? 512 : minimum(_dispatch_fit_batch_max_n(length(beyond), size(Cs[q], 1)) for q in beyond)
-        if any(size(Cs[q], 2) <= wide_n for q in beyond)
+        lu = [q for q in 1:ns if _takes_small_lu(params[q], cfgs[q].polynomial_degree, size(Cs[q], 2), size(Cs[q], 1), size(Ys[q], 1))]
+        lu_n = isempty(lu) ? 0 : maximum(size(Cs[q], 2) for q in lu)
+        opts = Tuple{Int32,Float64}[]
+        any(size(Cs[q], 2) <= wide_n for q in beyond) && push!(opts, (Int32(15), Float64(wide_n)))
+        !isempty(lu) && all(_dispatch_fit_batch_lu(length(lu), lu_n, size(Cs[q], 1)) for q in lu) && push!(opts, (Int32(16), 1.0))
+        if !isempty(opts)
             _locked(ctx) do hctx
-                previous = Ref{Float64}(512.0)
-                _check(ctx, ccall((:mrbf_get_option, libmrbf), Int32, (Ptr{Cvoid}, Int32, Ref{Float64}), hctx, 15, previous))
-                _check(ctx, ccall((:mrbf_set_option, libmrbf), Int32, (Ptr{Cvoid}, Int32, Float64), hctx, 15, Float64(wide_n)))
+                previous = map(opts) do (key, _)
+                    v = Ref{Float64}(0.0)
+                    _check(ctx, ccall((:mrbf_get_option, libmrbf), Int32, (Ptr{Cvoid}, Int32, Ref{Float64}), hctx, key, v))
+                    v[]
+                end
                 try
+                    for (key, value) in opts
+                        _check(ctx, ccall((:mrbf_set_option, libmrbf), Int32, (Ptr{Cvoid}, Int32, Float64), hctx, key, value))
+                    end
                     _fit_batch_locked(ctx, ns, jobs, ms)
                 finally
-                    ccall((:mrbf_set_option, libmrbf), Int32, (Ptr{Cvoid}, Int32, Float64), hctx, 15, previous[])
+                    for ((key, _), old) in zip(opts, previous)
+                        ccall((:mrbf_set_option, libmrbf), Int32, (Ptr{Cvoid}, Int32, Float64), hctx, key, old)
+                    end
                 end
             end
         else

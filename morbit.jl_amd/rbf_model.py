@@ -219,6 +219,16 @@ def _as_fit_input(a, rows=None):
     return a.reshape(rows, -1) if rows is not None else a
 
 
+def _takes_small_lu(kid, a, b, deg, n, d, k):
+    """Is a start on the LU path (fit_model, solve.hip: the kernel's order exceeds what the tail covers, or n == q) and inside the range
+    of MRBF_OPT_SMALL_LU (n <= 512, d <= 128, k <= 16, n >= q, a smooth kernel)?  (kid, a, b) as _get_kernel_params gives them."""
+    q = 0 if deg < 0 else (1 if deg == 0 else d + 1)
+    order = math.ceil(a / 2.0) if kid == 0 else (math.ceil(b) if kid == 2 else (int(a) + 1 if kid == 3 else 0))
+    nonsmooth = kid in (0, 3) and a == 1.0
+    chol = order <= deg + 1 and n > q
+    return (not chol) and q <= n <= _lib.SMALL_LU_MAX_N and d <= _lib.SMALL_LU_MAX_D and k <= _lib.SMALL_LU_MAX_K and not nonsmooth
+
+
 def update_models_many(cfgs, sites_list, values_list, deltas, fully_linear=False, ctx=None, stats=None):
     """update_model for a batch of starts (the Threads.@threads loop over starts of examples/large_scale_benchmarks.jl:102-109 around
     RbfModel.jl:743-767) in ONE mrbf_fit_batch call where mrbf_dispatch_fit_batch says so; otherwise, or when the call returns -2, the
@@ -227,7 +237,9 @@ def update_models_many(cfgs, sites_list, values_list, deltas, fully_linear=False
     for a start whose fit failed; stats (optional dict) receives "path" ("batch" or "loop"), "status" (return code per start),
     "ms_total" and "wide": how many starts with more than 512 sites shared the batch's launch, the context's
     MRBF_OPT_SMALL_FIT_MAX_N raised to mrbf_dispatch_fit_batch_max_n's answer for the one call and put back behind it, also on error
-    (such a start is, bit for bit, what mrbf_fit gives under that option value, not under the default)."""
+    (such a start is, bit for bit, what mrbf_fit gives under that option value, not under the default); "lu": how many starts on the LU
+    path shared the one-launch LU (MRBF_OPT_SMALL_LU set to 1 for the one call where mrbf_dispatch_fit_batch_lu admits them, and put back
+    behind it, also on error; such a start is what mrbf_fit gives under that option)."""
     ctx = ctx or _lib.default_context()
     ns = len(sites_list)
     per = lambda v: list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v] * ns
@@ -243,13 +255,13 @@ def update_models_many(cfgs, sites_list, values_list, deltas, fully_linear=False
             except _lib.MrbfError as e:
                 mods.append(None)
                 status.append(e.code)
-        stats.update(path="loop", status=status, ms_total=float(sum(m.info["ms_total"] for m in mods if m is not None)), wide=0)
+        stats.update(path="loop", status=status, ms_total=float(sum(m.info["ms_total"] for m in mods if m is not None)), wide=0, lu=0)
         return mods
 
     if ctx.lib.mrbf_dispatch_fit_batch(ns) != _lib.DISPATCH_DEVICE:
         return loop()
     jobs = (_lib.FitJob * ns)()
-    keep = []
+    keep, lu = [], []
     for p in range(ns):
         C = _as_fit_input(sites_list[p])
         assert C.ndim == 2, "training_sites: n sites of dimension d"
@@ -261,6 +273,8 @@ def update_models_many(cfgs, sites_list, values_list, deltas, fully_linear=False
         q = 0 if deg < 0 else (1 if deg == 0 else d + 1)
         W, L = np.empty((n, k)), np.empty((max(q, 1), k))
         keep.append((C, Y, W, L, n, d, k, q))
+        if _takes_small_lu(kid, a, b, deg, n, d, k):
+            lu.append((n, d))
         J = jobs[p]
         J.n, J.d, J.k, J.kernel_id, J.poly_deg, J.a, J.b = n, d, k, kid, deg, a, b
         J.centres, J.values = _lib.as_ptr(C), _lib.as_ptr(Y)
@@ -271,16 +285,18 @@ def update_models_many(cfgs, sites_list, values_list, deltas, fully_linear=False
     beyond = [(n, d) for (_, _, _, _, n, d, _, _) in keep if n > _lib.SMALL_FIT_DEFAULT_MAX_N]
     wide_n = min((int(ctx.lib.mrbf_dispatch_fit_batch_max_n(len(beyond), d)) for _, d in beyond), default=_lib.SMALL_FIT_DEFAULT_MAX_N)
     n_wide = sum(1 for n, _ in beyond if n <= wide_n)
-    stats["wide"] = 0
-    if n_wide:
-        previous = ctx.get_option(_lib.OPT_SMALL_FIT_MAX_N)
-        ctx.set_option(_lib.OPT_SMALL_FIT_MAX_N, wide_n)
-        try:
-            rc = ctx.lib.mrbf_fit_batch(ctx.h, ns, jobs, ctypes.byref(ms))
-        finally:
-            ctx.set_option(_lib.OPT_SMALL_FIT_MAX_N, previous)
-    else:
+    # starts on the LU path inside the one-launch LU's range: the table says whether they share its launch (MRBF_OPT_SMALL_LU, likewise)
+    n_lu = len(lu) if lu and all(ctx.lib.mrbf_dispatch_fit_batch_lu(len(lu), max(n for n, _ in lu), d) == 1 for _, d in lu) else 0
+    stats["wide"], stats["lu"] = 0, 0
+    options = ([(_lib.OPT_SMALL_FIT_MAX_N, wide_n)] if n_wide else []) + ([(_lib.OPT_SMALL_LU, 1)] if n_lu else [])
+    previous = [(key, ctx.get_option(key)) for key, _ in options]
+    try:
+        for key, value in options:
+            ctx.set_option(key, value)
         rc = ctx.lib.mrbf_fit_batch(ctx.h, ns, jobs, ctypes.byref(ms))
+    finally:
+        for key, value in previous:
+            ctx.set_option(key, value)
     if rc != 0 and ctx.lib.mrbf_dispatch_after(_lib.ENTRY_FIT_BATCH, rc) == 1:
         return loop()
     ctx.check(rc)
@@ -288,7 +304,7 @@ def update_models_many(cfgs, sites_list, values_list, deltas, fully_linear=False
     for p, (C, Y, W, L, n, d, k, q) in enumerate(keep):
         J = jobs[p]
         mods.append(RbfModel(ctx, _lib.c_vp(J.model), n, d, k, q, fls[p], W, L[:q], J.info.asdict()) if J.status == 0 else None)
-    stats.update(path="batch", status=[int(J.status) for J in jobs], ms_total=float(ms.value), wide=n_wide)
+    stats.update(path="batch", status=[int(J.status) for J in jobs], ms_total=float(ms.value), wide=n_wide, lu=n_lu)
     return mods
 
 
@@ -307,7 +323,7 @@ def update_models_resident(cfgs, dbs, index_lists, deltas, fully_linear=False, c
         by_d.setdefault(dbs[p].d, []).append(p)
     per = lambda v: list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v] * ns
     cfgs, deltas, fls = per(cfgs), per(deltas), per(fully_linear)
-    mods, status, ms, paths, wide = [None] * ns, [0] * ns, 0.0, [], 0
+    mods, status, ms, paths, wide, lu = [None] * ns, [0] * ns, 0.0, [], 0, 0
     for members in by_d.values():   # one gather and one fit call per d (a gather's views last until the next gather)
         got = database.gather_many([dbs[p] for p in members], [index_lists[p] for p in members], ctx=ctx)
         for p, g in zip(members, got):
@@ -320,9 +336,10 @@ def update_models_resident(cfgs, dbs, index_lists, deltas, fully_linear=False, c
             mods[p], status[p] = res[pos], st["status"][pos]
         ms += st["ms_total"]
         wide += st.get("wide", 0)
+        lu += st.get("lu", 0)
         paths.append(st["path"])
     if stats is not None:
-        stats.update(path="batch" if "batch" in paths else "loop", status=status, ms_total=ms, wide=wide)
+        stats.update(path="batch" if "batch" in paths else "loop", status=status, ms_total=ms, wide=wide, lu=lu)
     return mods
 
 
