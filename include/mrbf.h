@@ -211,7 +211,14 @@ int32_t mrbf_affine_scores(mrbf_ctx *ctx, int64_t mc, int32_t d, int32_t dz, con
  * after every pick (:59-60, :93-94): O(d^2 + d mc) per pick, no host round trip between picks.  shifted: mc x d row-major rows
  * xi - x0 (host or device; sites chosen already: zero rows).  picked_out[max_picks]: positions of the picked candidates in pick order;
  * Z_out (d x (d - j0 - *n_picked), column-major, host or device, may be NULL): the p-normalised complement basis afterwards -- the
- * filter's final Z (its improving directions, RbfModel.jl:231-235). */
+ * filter's final Z (its improving directions, RbfModel.jl:231-235).
+ * Which d takes which form (1 <= d <= 4096; d > 4096: -3, nothing written):
+ *   inf-norm, d <= 1023          one launch per pick (affsel_pick_kernel; 8 (d + 1) + 8 * 1024 doubles of LDS, 128 KiB at d = 1023)
+ *   2-norm d <= 1024; inf-norm d = 1024
+ *                                three launches per pick (score / decide / update); the score kernel asks for 8 (d - j0) doubles of
+ *                                dynamic LDS plus 2 KiB static: 66 KiB at d - j0 = 1024, which the runtime grants a launch as it stands
+ *                                (it reports 160 KiB per workgroup on gfx950; tests/test_gpu_select_wide.py, cases C11 and C12)
+ *   d >= 1025                    rocBLAS for the two products, the decide / update kernels unchanged */
 int32_t mrbf_affine_select(mrbf_ctx *ctx, int64_t mc, int32_t d, const double *shifted, int32_t j0, const double *Q0, int32_t max_picks,
                            double pivot_val, int32_t p_is_inf, int64_t *picked_out, int32_t *n_picked, double *Z_out);
 

@@ -3,8 +3,9 @@ twins of the many-start drivers against the host mirror.  No tolerance anywhere:
 bits (uint64 views of the doubles; -0.0 and NaN payloads count).
 
 B = 64 is the number of database rows a workgroup of the flag and compaction kernels takes (csrc/db_host.hpp, db::ROWS): the box scans
-run on n_sites in {1, B - 1, B, B + 1, 3 B + 7} = {1, 63, 64, 65, 199}, on d in {1, 3, 65, 128} (less than a wave, an odd row length,
-more than a wave with an odd tail, two coordinates per lane).
+run on n_sites in {1, B - 1, B, B + 1, 3 B + 7} = {1, 63, 64, 65, 199}, on d in {1, 3, 65, 128, 130, 257} (less than a wave, an odd row
+length, more than a wave with an odd tail, two coordinates per lane in exactly one trip, the same with a second, partial trip, an odd
+row of five trips); one scan and one gather run at the library's limit d = 4096.
 
 The sites of test 1 lie on a grid of step 1/2 with the bounds and the centre on that grid: many coordinates sit exactly on lb or ub,
 rows tie in norm, and the sums of squares of the 2-norm are exact in fp64 whatever their order (multiples of 1/4 below 2^11), so that
@@ -137,7 +138,7 @@ def bounds_variants(d):
     return {"finite": (lb, ub), "inf": (lbi, ubi)}
 
 
-@pytest.mark.parametrize("d", [1, 3, 65, 128])
+@pytest.mark.parametrize("d", [1, 3, 65, 128, 130, 257])
 def test_box_scan_against_the_host_mirror(ctx, d):
     """test 1, one start per call: every size, exclude list, bound vector, norm and both settings of zero_first_pick"""
     for n in SIZES:
@@ -156,7 +157,7 @@ def test_box_scan_against_the_host_mirror(ctx, d):
         db.free()
 
 
-@pytest.mark.parametrize("d", [1, 3, 65, 128])
+@pytest.mark.parametrize("d", [1, 3, 65, 128, 130, 257])
 def test_box_scan_five_starts_in_one_call(ctx, d):
     """test 1, a batch: five starts with different n_sites and exclude lists, the B-row start with an empty box, one with infinite bounds"""
     sizes = (B - 1, B, 3 * B + 7, 1, B + 1)
@@ -185,6 +186,25 @@ def test_box_scan_five_starts_in_one_call(ctx, d):
         assert same_bits(np.asarray(got[q].shifted), shifted) and same_bits(host.shifted, shifted) and same_bits(np.asarray(got[q].sites), sites)
     for db in dbs:
         db.free()
+
+
+@pytest.mark.parametrize("zero", [True, False])
+def test_box_scan_at_the_widest_row(ctx, zero):
+    """test 1 at the library's limit d = 4096 (32 trips of two coordinates per lane), n = B + 1 (a second, one-row workgroup), inf-norm"""
+    d, n = 4096, B + 1
+    S = grid_sites(n, d, 4096)
+    db = database.DeviceDatabase(d, 1, ctx=ctx)
+    db.append(S)
+    centre = n // 2
+    x0 = np.nan_to_num(S[centre], nan=0.5)
+    for ename, ex in exclude_variants(n, centre).items():
+        for bname, (lb, ub) in bounds_variants(d).items():
+            rc, jobs, outs = raw_box(ctx, [db], [lb], [ub], [x0], [ex], np.inf, zero, d)
+            assert rc == 0, ctx.lib.mrbf_last_error(ctx.h)
+            check_box(ctx, jobs[0], outs[0], S, lb, ub, x0, ex, np.inf, zero, (d, n, ename, bname, zero))
+    rc, jobs, outs = raw_box(ctx, [db], [np.full(d, -1.0)], [np.full(d, 1.0)], [x0], [[]], np.inf, zero, d)
+    assert rc == 0 and 10 < jobs[0].mc < n              # the scan tells rows apart: some in the box, some out
+    db.free()
 
 
 def test_growth_keeps_every_row(ctx):
@@ -271,6 +291,24 @@ def test_gather(ctx):
     assert ctx.lib.mrbf_db_box_batch(ctx.h, 2, d, 1, bj, None) == -5 and bj[0].mc == -9
     for db in dbs:
         db.free()
+
+
+def test_gather_at_the_widest_row(ctx):
+    """test 3 at d = 4096: a shuffled index list with repeats out of B + 1 rows"""
+    d, n, k = 4096, B + 1, 2
+    rng = np.random.default_rng(4096)
+    S, V = rng.standard_normal((n, d)), rng.standard_normal((n, k))
+    db = database.DeviceDatabase(d, k, ctx=ctx)
+    db.append(S, V)
+    idx = np.concatenate([rng.permutation(n), rng.integers(0, n, 11)]).astype(np.int64)
+    so, vo = np.full((len(idx) + 1, d), SENTINEL), np.full((len(idx) + 1, k), SENTINEL)
+    jobs = (_lib.DbGatherJob * 1)()
+    J = jobs[0]
+    J.db, J.n_idx, J.indices, J.sites_out, J.values_out, J.rc = db.h, len(idx), idx.ctypes.data, so.ctypes.data, vo.ctypes.data, 55
+    assert ctx.lib.mrbf_db_gather_batch(ctx.h, 1, d, jobs, None) == 0 and J.rc == 0
+    assert same_bits(so[:-1], S[idx]) and same_bits(vo[:-1], V[idx]) and np.all(so[-1] == SENTINEL) and np.all(vo[-1] == SENTINEL)
+    assert same_bits(view_to_host(ctx, J.sites_dev, len(idx), d), S[idx])
+    db.free()
 
 
 def test_optional_outputs_may_be_device_memory(ctx):

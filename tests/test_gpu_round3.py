@@ -4,8 +4,9 @@ comparison is an equality of integers or of bits (uint64 views of the doubles, -
 the device must have a NaN and the payload is not compared -- IEEE 754 leaves the sign and payload of the NaN an invalid operation
 (Inf * 0, Inf - Inf) produces to the implementation, and x86 and the GPU choose differently.
 
-d in {1, 2, 3, 65, 128}: a single coordinate, the smallest even and odd row lengths, one lane stride crossed with an odd tail, and the
-two-coordinates-per-lane path filling a wave exactly; one start and five starts per call.  The boxes lie on a grid of step 1/8 and many
+d in {1, 2, 3, 65, 128, 130, 257}: a single coordinate, the smallest even and odd row lengths, one lane stride crossed with an odd tail,
+the two-coordinates-per-lane path filling a wave exactly, the same with a second, partial trip, and an odd row of five trips with more
+than 256 fail flags on the axes (a second pass of the decision's loop); one start and five starts per call.  The boxes lie on a grid of step 1/8 and many
 coordinates sit exactly on a bound."""
 import ctypes
 
@@ -23,7 +24,7 @@ if has_gpu():
     from morbit.jl_amd import _lib, database, sampling
     from morbit.jl_amd.rbf_model import RbfConfig, update_models_many, update_models_resident
 
-DS = (1, 2, 3, 65, 128)
+DS = (1, 2, 3, 65, 128, 130, 257)
 SENTINEL = -777.25
 
 
@@ -214,7 +215,7 @@ def test_failing_direction_beside_passing_starts(ctx, d):
         assert np.array_equal(alone[0], ref[0]) and alone[1:] == ref[1:]
 
 
-@pytest.mark.parametrize("d", (2, 3, 65, 128))
+@pytest.mark.parametrize("d", (2, 3, 65, 128, 130))
 def test_rebuild_that_succeeds(ctx, d):
     """x = (.5, ..), box [.25, .75]^d but lb0 = .5 - 2^-10 and ub1 = .5 + 2^-10.  Along e0 + e1 the steps are -2^-10, +.25 (coordinate 0)
     and -.25, +2^-10 (coordinate 1): sigma+ = sigma- = 2^-10, the offset's norm is below the pivot and the direction fails, while every
@@ -379,7 +380,7 @@ def test_append_many_and_set_values_many_match_the_single_calls(ctx):
 
 # ---- phase I + fit, resident against host ---------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("d", (3, 65))
+@pytest.mark.parametrize("d", (3, 65, 130))
 def test_three_iterations_of_phase_one_and_fit(ctx, d):
     """five starts, start 2 with a fixed coordinate (it rebuilds): prepare_update_models + update_models_resident on resident databases against
     prepare_update_models + update_models_many on host databases: equal metas, equal database contents, equal weights"""

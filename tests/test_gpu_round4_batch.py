@@ -143,6 +143,20 @@ def test_benchmark_shape_once():
     assert all(len(acc) == 128 for _, acc in res)
 
 
+def beyond_small_range_case():
+    return [generic(("d130", sd), "cubic", 1, 130, 131 + sd, (37, 24, 12)[sd], 60 + sd) for sd in range(3)]
+
+
+@pytest.mark.gpu
+def test_every_start_beyond_the_small_range():
+    """d = 130 > 128: no start fits the batched kernel, mrbf_round4 runs inside the call for each: rc 0 per start, the lists of the single
+    calls and of the oracle"""
+    starts = beyond_small_range_case()
+    res = check(starts, 130)
+    assert [len(acc) for _, acc in res] == [37, 24, 12]
+    assert run_batch(starts[::-1], 130) == res[::-1]
+
+
 def ragged_case():
     return [clustered(("rag", 0), "cubic", 1, 3, 4, 40, 0.2, 31),
             generic(("rag", 1), "gaussian", 0, 3, 6, 17, 32, scale=10.0),

@@ -391,7 +391,8 @@ def test_growing_qr_equals_refactoring_from_scratch(d):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("d,n,piv,p", [(128, 300, 0.05, np.inf), (64, 2000, 0.02, np.inf), (33, 500, 0.2, 2), (128, 90, 0.05, np.inf), (7, 5000, 0.45, np.inf)])
+@pytest.mark.parametrize("d,n,piv,p", [(128, 300, 0.05, np.inf), (64, 2000, 0.02, np.inf), (33, 500, 0.2, 2), (128, 90, 0.05, np.inf), (7, 5000, 0.45, np.inf),
+                                       (256, 300, 0.05, np.inf), (200, 260, 0.05, 2)])
 def test_affine_select_on_device_is_the_filter(d, n, piv, p):
     """mrbf_affine_select (round 6): the filter's whole pick loop in one device call, the Householder factorisation of the chosen
     directions grown by a reflector per pick on the device.  Against the host filter (same rule, host scan + `_GrowingQR`) and the
