@@ -376,6 +376,40 @@ typedef struct {
 } mrbf_fit_job;                       /* 168 bytes */
 int32_t mrbf_fit_batch(mrbf_ctx *ctx, int64_t n_starts, mrbf_fit_job *jobs, float *ms_total);
 
+/* ---- many-start evaluation: one call evaluates a batch of kept models (eval_batch.hip, host logic in eval_batch_host.hpp) -----
+ * mrbf_eval for n_jobs independent (model, query block) pairs on ONE context: m(x) and m(x_+) of every start for the acceptance
+ * test of iterate! (src/algorithm.jl:766-767), the container sweeps eval_container_*_at_scaled_sites
+ * (src/SurrogateContainer.jl:234-269) of every start, and plain evaluation of the models mrbf_fit_batch keeps for the reference's
+ * Threads.@threads loop over starts (examples/large_scale_benchmarks.jl:102-109).  For every job, vals_out and jac_out are, bit for
+ * bit, what mrbf_eval(ctx, model, m, X, vals_out, jac_out, NULL) writes on the same context; they do not depend on the job's
+ * position or on which other jobs share the call.  No evaluation arithmetic of its own: the call fills the descriptor arrays of the
+ * single call's kernels, every job with the centre-range split of the single call it stands for.
+ * Models may come from mrbf_fit, mrbf_fit_batch, mrbf_fit_from_round4 or mrbf_model_from_coeffs, may appear in several jobs, and may
+ * differ in n, d, k, kernel and parameters.  Jobs the fused kernels take (dpad in {64, 128, 256}, MRBF_OPT_EVAL_IMPL != 1) share
+ * launches: one group per (kernel and parameters, k, dpad, with or without Jacobians, split or unsplit centre range), a non-smooth
+ * group in the difference form; every other job runs the single call's chain on the same stream inside the call.
+ * One packed upload (descriptors + all host-side query rows), one read-back (all host-side outputs), one synchronisation.  Device-side
+ * X / vals_out / jac_out are read and written in place (the descriptors carry their addresses): no copy, no host round trip.  The
+ * work buffer is one slot of the context's arena: a second identical call allocates nothing.  A call whose work buffer would exceed
+ * 2 GiB is processed in chunks of consecutive jobs inside the call (then: one upload, read-back and synchronisation per chunk).
+ * m == 0 jobs write nothing; a job with both outputs NULL does nothing.  Every job's status is set (0 on success).
+ * Returns 0; -1 without a context; -3 for an invalid job (NULL model, m < 0, NULL X with m > 0; `jobs` NULL): nothing is launched or
+ * written; -4 for a model of another context or device (likewise); -2, and only -2, when mrbf_dispatch_eval_batch refuses n_jobs:
+ * take mrbf_eval per job.  ms_total (may be NULL): hipEvent time of the whole call.
+ * mrbf_eval_batch_limited is the same call with the 2 GiB limit of the chunk rule as an argument (arena_limit_bytes <= 0: 2 GiB): for
+ * tests of the chunk path; the results do not depend on it. */
+typedef struct {
+    const mrbf_model *model;
+    int64_t m;
+    const double *X;     /* m x d row-major, host or device (detected per pointer); may be NULL when m == 0 */
+    double *vals_out;    /* m x k, host or device, or NULL */
+    double *jac_out;     /* m x (k x d column-major blocks), host or device, or NULL */
+    int32_t status;      /* out: what mrbf_eval would have returned for this job */
+    int32_t reserved;
+} mrbf_eval_job;         /* 48 bytes */
+int32_t mrbf_eval_batch(mrbf_ctx *ctx, int64_t n_jobs, mrbf_eval_job *jobs, float *ms_total);
+int32_t mrbf_eval_batch_limited(mrbf_ctx *ctx, int64_t n_jobs, mrbf_eval_job *jobs, float *ms_total, int64_t arena_limit_bytes);
+
 /* ---- resident site database: box scan and gathers for many-start updates (db.hip, host logic in db_host.hpp) -----------------
  * A start's evaluation database -- the ArrayDB of src/Databases.jl: sites (d) and values (k), rows in insertion order, a row's
  * position being its id -- kept on the device and appended to as the run goes, so that the batched calls above read their inputs from
@@ -875,6 +909,12 @@ int32_t mrbf_ps_step_batch(mrbf_ctx *ctx, int64_t n_starts, const mrbf_ps_proble
  *                            1 <= d <= 4096; otherwise the scan and the copies run on the caller's host copy of the database.
  *                            mrbf_db_round3_batch, mrbf_db_append_batch and mrbf_db_set_values_batch (MRBF_ENTRY_DB_ROUND3,
  *                            _DB_APPEND_BATCH, _DB_SET_VALUES_BATCH) are routed by the same rule.
+ *   mrbf_dispatch_eval_batch mrbf_eval of n_jobs (model, query block) pairs in one call (mrbf_eval_batch): device iff
+ *                            1 <= n_jobs <= 65535 (a grid dimension).  Which jobs share launches is decided inside the call.
+ *   mrbf_dispatch_eval_batch_min_jobs  the fewest jobs from which the bindings make that one call instead of the loop of mrbf_eval
+ *                            (measured cells only, tools/eval_batch_bench.py, DESIGN.md section 18: admitted where the batch took
+ *                            at most 0.8 of the loop's median -- 0.48 at 8 C4 evaluations, 0.16 at 8 acceptance-test pairs --;
+ *                            monotone: every job count from the answer, 8, on takes the batch; fewer were not measured).
  *   mrbf_dispatch_after      the return code rc of a device entry point (MRBF_ENTRY_*) that means "take the reference method
  *                            for this call" (start set without the tail or rank deficient, limits of the device path) rather
  *                            than an error: 1 = fall back, 0 = rc is what it says. */
@@ -884,7 +924,7 @@ enum { MRBF_ENTRY_ROUND4 = 1, MRBF_ENTRY_FIT_FROM_ROUND4 = 2, MRBF_ENTRY_PS_STEP
        MRBF_ENTRY_SD = 6, MRBF_ENTRY_NORMAL = 7, MRBF_ENTRY_SD_STEP = 8, MRBF_ENTRY_SD_BATCH = 9, MRBF_ENTRY_AFFINE_BATCH = 10,
        MRBF_ENTRY_FIT_BATCH = 11, MRBF_ENTRY_NORMAL_BATCH = 12, MRBF_ENTRY_ROUND4_BATCH = 13, MRBF_ENTRY_PS_BATCH = 14,
        MRBF_ENTRY_DB_BOX = 15, MRBF_ENTRY_DB_GATHER = 16, MRBF_ENTRY_DB_ROUND3 = 17, MRBF_ENTRY_DB_APPEND_BATCH = 18,
-       MRBF_ENTRY_DB_SET_VALUES_BATCH = 19 };
+       MRBF_ENTRY_DB_SET_VALUES_BATCH = 19, MRBF_ENTRY_EVAL_BATCH = 20 };
 int32_t mrbf_dispatch_ps(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_ps_batch(int64_t n_starts, int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints,
                                int32_t n_lin_constraints, int32_t n_foreign);
@@ -905,6 +945,8 @@ int64_t mrbf_dispatch_fit_batch_max_n(int64_t n_starts, int32_t d);
 int32_t mrbf_dispatch_fit_batch_lu(int64_t n_lu_starts, int64_t n_max, int32_t d);
 int32_t mrbf_dispatch_round4_batch(int64_t n_starts, int32_t d);
 int32_t mrbf_dispatch_db_batch(int64_t n_starts, int32_t d);
+int32_t mrbf_dispatch_eval_batch(int64_t n_jobs);
+int64_t mrbf_dispatch_eval_batch_min_jobs(void);
 int32_t mrbf_dispatch_fit(int64_t n_training, int64_t state_n0, int32_t state_q, int32_t state_n_accepted, int32_t same_sites);
 int32_t mrbf_dispatch_after(int32_t entry, int32_t rc);
 

@@ -74,6 +74,7 @@ ENTRY_DB_GATHER = 16
 ENTRY_DB_ROUND3 = 17
 ENTRY_DB_APPEND_BATCH = 18
 ENTRY_DB_SET_VALUES_BATCH = 19
+ENTRY_EVAL_BATCH = 20
 R3_UPDATE, R3_IMPROVE = 0, 1
 R3_DONE, R3_REBUILT = 0, 1
 SD_OK, SD_NO_OBJECTIVE, SD_INFEASIBLE, SD_GAVE_UP = 0, 1, 2, 3
@@ -155,6 +156,12 @@ class FitJob(ctypes.Structure):
                 ("poly_deg", ctypes.c_int32), ("a", ctypes.c_double), ("b", ctypes.c_double), ("centres", ctypes.c_void_p),
                 ("values", ctypes.c_void_p), ("weights_out", ctypes.c_void_p), ("poly_out", ctypes.c_void_p), ("model", ctypes.c_void_p),
                 ("status", ctypes.c_int32), ("reserved", ctypes.c_int32), ("info", FitInfo)]
+
+
+class EvalJob(ctypes.Structure):
+    """mrbf_eval_job: one (model, query block) pair of mrbf_eval_batch"""
+    _fields_ = [("model", ctypes.c_void_p), ("m", ctypes.c_int64), ("X", ctypes.c_void_p), ("vals_out", ctypes.c_void_p),
+                ("jac_out", ctypes.c_void_p), ("status", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 class DbBoxJob(ctypes.Structure):
@@ -251,6 +258,10 @@ SIGNATURES = {
     "mrbf_dispatch_fit_batch": (ctypes.c_int32, [ctypes.c_int64]),
     "mrbf_dispatch_fit_batch_max_n": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32]),
     "mrbf_dispatch_fit_batch_lu": (ctypes.c_int32, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32]),
+    "mrbf_eval_batch": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.POINTER(EvalJob), c_fp]),
+    "mrbf_eval_batch_limited": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.POINTER(EvalJob), c_fp, ctypes.c_int64]),
+    "mrbf_dispatch_eval_batch": (ctypes.c_int32, [ctypes.c_int64]),
+    "mrbf_dispatch_eval_batch_min_jobs": (ctypes.c_int64, []),
     "mrbf_db_create": (ctypes.c_int32, [c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.POINTER(c_vp)]),
     "mrbf_db_append": (ctypes.c_int32, [c_vp, c_vp, ctypes.c_int64, c_vp, c_vp, ctypes.POINTER(ctypes.c_int64)]),
     "mrbf_db_set_values": (ctypes.c_int32, [c_vp, c_vp, ctypes.c_int64, c_vp, c_vp]),

@@ -685,6 +685,7 @@ extern "C" int32_t mrbf_fit_batch(mrbf_ctx *ctx, int64_t n_starts, mrbf_fit_job 
                 }
                 mrbf_model *M = new mrbf_model(shells[p]);
                 M->slab = slab;
+                M->owner = ctx;
                 ++slab->refs;
                 ++ctx->live_models;
                 J.model = M;

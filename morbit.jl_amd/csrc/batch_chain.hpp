@@ -45,6 +45,14 @@ struct Member {
     bool jac;
     // where the member reads and writes, offsets in doubles from the arena's base: the caller's to set before fill() / launch()
     size_t X = 0, vals = 0, jacs = 0;
+    // ... or, with `ext`, buffers outside the arena (mrbf_eval_batch: a caller's device buffers, used in place) by their addresses;
+    // vals_at may then be NULL (Jacobians only), jac_at is read where `jac` is set
+    bool ext = false;
+    const double *X_at = nullptr;
+    double *vals_at = nullptr, *jac_at = nullptr;
+    const double *x_of(const double *base) const { return ext ? X_at : base + X; }
+    double *vals_of(double *base) const { return ext ? vals_at : base + vals; }
+    double *jac_of(double *base) const { return !jac ? nullptr : (ext ? jac_at : base + jacs); }
     // scratch (carve): offsets likewise
     size_t Xq = 0, xsq = 0, vpart = 0, gpart = 0;
     int64_t mpad = 0;
@@ -113,7 +121,7 @@ struct Plan {
                 EvalDesc E;
                 std::memset(&E, 0, sizeof(E));
                 eval_desc_model(E, S.M, S.mq, S.nsplit);
-                E.X = base + S.X;
+                E.X = S.x_of(base);
                 E.Xq = base + S.Xq;
                 E.xsq = base + S.xsq;
                 if (S.nsplit > 1) {
@@ -121,8 +129,8 @@ struct Plan {
                     E.sapart = E.vpart + (size_t)S.nsplit * S.mpad * S.KO;
                     if (S.jac) E.gpart = base + S.gpart;
                 }
-                E.vals = base + S.vals;
-                E.jac = S.jac ? base + S.jacs : nullptr;
+                E.vals = S.vals_of(base);
+                E.jac = S.jac_of(base);
                 std::memcpy(&hdesc[G.first + r], &E, sizeof(E));
             }
     }
@@ -138,7 +146,7 @@ struct Plan {
         }
         for (const Member &S : mem) {
             if (S.site != site || S.group >= 0) continue;
-            MRBF_TRY(eval_model(ctx, S.M, S.mq, base + S.X, base + S.vals, S.jac ? base + S.jacs : nullptr, nullptr));
+            MRBF_TRY(eval_model(ctx, S.M, S.mq, S.x_of(base), S.vals_of(base), S.jac_of(base), nullptr));
         }
         return 0;
     }

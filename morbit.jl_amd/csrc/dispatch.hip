@@ -28,6 +28,12 @@ struct FitLuRow {
 };
 constexpr FitLuRow FIT_LU[] = {{8, 512, 128}};
 constexpr int FIT_LU_ROWS = (int)(sizeof(FIT_LU) / sizeof(FIT_LU[0]));
+// mrbf_dispatch_eval_batch_min_jobs: from this many jobs on the bindings make one mrbf_eval_batch call instead of the loop of mrbf_eval.
+// Measured at the C4 shape (tools/eval_batch_bench.py, profiles/eval_batch_bench.jsonl: d = 128, n = 257, k = 2, device-resident buffers,
+// medians of 30 host-clock calls): batch / loop of single calls on the parent build = 0.48, 0.40, 0.36 at 8, 16, 64 jobs of m = 6450 with
+// Jacobians, 0.16, 0.083, 0.033 at 8, 16, 64 jobs of m = 2 values only, 0.031 at 64 jobs of d = 3, n = 20; fewer than 8 jobs were not
+// measured and keep the loop
+constexpr int64_t EVAL_BATCH_MIN_JOBS = 8;
 }  // namespace
 
 extern "C" {
@@ -164,6 +170,14 @@ int32_t mrbf_dispatch_db_batch(int64_t n_starts, int32_t d) {
     return n_starts >= 1 && n_starts <= 65535 && d >= 1 && d <= 4096 ? MRBF_DISPATCH_DEVICE : MRBF_DISPATCH_REFERENCE;
 }
 
+// the evaluations of many kept models in one call (eval_batch.hip, mrbf_eval_batch): the job on a grid dimension; which jobs share the
+// fused kernels' launches and which take the single call's chain inside the call is decided there, job by job
+int32_t mrbf_dispatch_eval_batch(int64_t n_jobs) { return n_jobs >= 1 && n_jobs <= 65535 ? MRBF_DISPATCH_DEVICE : MRBF_DISPATCH_REFERENCE; }
+
+// the fewest jobs from which the batch pays (admitted where the batch took at most 0.8 of the median of the loop of single calls on the
+// parent build; monotone: every larger batch takes the call as well; a value above 65535 would mean: the bindings keep the loop)
+int64_t mrbf_dispatch_eval_batch_min_jobs(void) { return EVAL_BATCH_MIN_JOBS; }
+
 int32_t mrbf_dispatch_fit(int64_t n_training, int64_t state_n0, int32_t state_q, int32_t state_n_accepted, int32_t same_sites) {
     if (state_n0 < 1 || state_n_accepted < 1 || !same_sites) return MRBF_FIT_FULL;
     if (state_n0 != state_q) return MRBF_FIT_FULL;  // the kept factor only covers the directions added by round 4
@@ -198,6 +212,7 @@ int32_t mrbf_dispatch_after(int32_t entry, int32_t rc) {
         case MRBF_ENTRY_DB_ROUND3: return rc == -2;
         case MRBF_ENTRY_DB_APPEND_BATCH: return rc == -2;
         case MRBF_ENTRY_DB_SET_VALUES_BATCH: return rc == -2;
+        case MRBF_ENTRY_EVAL_BATCH: return rc == -2;  // the table refuses the job count: mrbf_eval per job; a job's own status is an error
         default: return 0;
     }
 }

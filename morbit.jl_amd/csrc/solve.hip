@@ -208,6 +208,7 @@ int build_model_shell(mrbf_ctx *ctx, int64_t n, int d, int k, const double *Cdev
         return rc_block;
     }
     ++ctx->live_models;  // (MRBF_OPT_LIVE_HANDLES: models and round-4 states created through this context and not yet released)
+    M->owner = ctx;
     model_carve(M, (char *)M->block, off);
     auto init = [&]() -> int {
         if (Cdev != M->C)

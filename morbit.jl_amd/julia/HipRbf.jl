@@ -101,6 +101,13 @@ struct MrbfFitJob           # mirrors mrbf_fit_job, 168 bytes
     info::MrbfFitInfo
 end
 
+struct MrbfEvalJob          # mirrors mrbf_eval_job, 48 bytes
+    model::Ptr{Cvoid}
+    m::Int64
+    X::Ptr{Float64}; vals_out::Ptr{Float64}; jac_out::Ptr{Float64}
+    status::Int32; reserved::Int32
+end
+
 struct MrbfPsProblem        # mirrors mrbf_ps_problem, 72 bytes
     n_models::Int32; n_objectives::Int32
     models::Ptr{Ptr{Cvoid}}; roles::Ptr{Int32}
@@ -297,6 +304,9 @@ function _takes_small_lu(params, deg, n, d, k)
     nonsmooth = (kid == 0 || kid == 3) && a == 1
     return !(order <= deg + 1 && n > q) && n >= q && n <= 512 && d <= 128 && k <= 16 && !nonsmooth
 end
+_dispatch_eval_batch(n_jobs) = ccall((:mrbf_dispatch_eval_batch, libmrbf), Int32, (Int64,), n_jobs) == 1
+# where `hip_eval_models_many` takes the one call: from the job count the table names on (measured, DESIGN.md section 18)
+_eval_batch_pays(n_jobs) = n_jobs >= ccall((:mrbf_dispatch_eval_batch_min_jobs, libmrbf), Int64, ())
 _dispatch_round4_batch(n_starts, d) = ccall((:mrbf_dispatch_round4_batch, libmrbf), Int32, (Int64, Int32), n_starts, d) == 1
 _dispatch_round4(n0, d, deg, n_candidates) =
     ccall((:mrbf_dispatch_round4, libmrbf), Int32, (Int64, Int32, Int32, Int64), n0, d, deg, n_candidates) == 1
@@ -556,6 +566,38 @@ function _mrbf_eval(mod::HipRbfModel, X::Matrix{Float64}; values::Bool = true, j
     end
     _check(mod.ctx, rc)
     return V, J
+end
+
+"""
+`_mrbf_eval` for a batch of (model, site block) pairs -- m(x) and m(x₊) of every start (algorithm.jl:766-767), the container sweeps of
+every start (SurrogateContainer.jl:234-269) -- in one device call (`mrbf_eval_batch`) where the decision table takes the job count
+(`mrbf_dispatch_eval_batch`) and it reaches `mrbf_dispatch_eval_batch_min_jobs`; otherwise, or when the library refuses the call
+(rc -2), the loop of `mrbf_eval`.  `Xs[i]` is d x m_i, one site per column; the models share one context.  Returns a vector of
+`(V, J)`, for every pair bit for bit what `_mrbf_eval(mods[i], Xs[i]; values, jac)` returns.
+"""
+function hip_eval_models_many(mods::AbstractVector{HipRbfModel}, Xs::AbstractVector{Matrix{Float64}}; values::Bool = true, jac::Bool = false,
+                              min_jobs::Union{Nothing,Int} = nothing)
+    nj = length(mods)
+    loop() = [_mrbf_eval(mods[i], Xs[i]; values = values, jac = jac) for i in 1:nj]
+    nj == 0 && return loop()
+    ctx = mods[1].ctx
+    pays = min_jobs === nothing ? _eval_batch_pays(nj) : nj >= min_jobs
+    (_dispatch_eval_batch(nj) && pays && all(m -> m.ctx === ctx, mods)) || return loop()
+    Vs = [values ? Matrix{Float64}(undef, mods[i].num_outputs, size(Xs[i], 2)) : nothing for i in 1:nj]
+    Js = [jac ? Array{Float64,3}(undef, mods[i].num_outputs, mods[i].n_vars, size(Xs[i], 2)) : nothing for i in 1:nj]
+    jobs = Vector{MrbfEvalJob}(undef, nj)
+    ms = Ref{Float32}(0)
+    rc = GC.@preserve Xs Vs Js jobs begin
+        for i in 1:nj
+            jobs[i] = MrbfEvalJob(mods[i].handle, size(Xs[i], 2), pointer(Xs[i]), values ? pointer(Vs[i]) : C_NULL, jac ? pointer(Js[i]) : C_NULL, 0, 0)
+        end
+        _locked(ctx) do hctx
+            ccall((:mrbf_eval_batch, libmrbf), Int32, (Ptr{Cvoid}, Int64, Ptr{MrbfEvalJob}, Ref{Float32}), hctx, nj, jobs, ms)
+        end
+    end
+    rc != 0 && _fallback_rc(20, rc) && return loop()           # the library refuses the batch: the single call per pair
+    _check(ctx, rc)
+    return [(Vs[i], Js[i]) for i in 1:nj]
 end
 
 "Evaluate `mod` at scaled site `x̂` (RbfModel.jl:783-785)."

@@ -34,28 +34,35 @@ def gpu_solve_problem(problem, ctx=None):
     return rec
 
 
-def gpu_solve_shard_keep_models(problems, ctx=None, stats=None):
+def gpu_solve_shard_keep_models(problems, ctx=None, stats=None, eval_min_jobs=None):
     """fit + eval of a shard of problem dicts with the models KEPT: one `update_models_many` call fits all of them (mrbf_fit_batch where
-    the decision table allows it), then one evaluation per problem.  Returns (records, models): a record per problem as
-    `gpu_solve_problem` writes it (a failed fit: its status and NaNs, model None), and the resident models in problem order -- what
-    a many-start driver hands to `descent.sd_iterate_many` (wrapped in its containers) before it frees them.  stats["wide"]: how many
-    problems with more than 512 sites shared the batch's launch (`update_models_many` asks mrbf_dispatch_fit_batch_max_n)."""
+    the decision table allows it), then one `eval_models_many` call evaluates all of them (mrbf_eval_batch where the decision table and
+    its threshold say so, else one mrbf_eval per problem: the same bits either way).  Returns (records, models): a record per problem as
+    `gpu_solve_problem` writes it (a failed fit: its status and NaNs, model None; the evaluation time of a problem that shared the one
+    call is that call's), and the resident models in problem order -- what a many-start driver hands to `descent.sd_iterate_many`
+    (wrapped in its containers) before it frees them.  stats["wide"]: how many problems with more than 512 sites shared the batch's
+    launch (`update_models_many` asks mrbf_dispatch_fit_batch_max_n); stats["eval"]: `eval_models_many`'s own stats (eval_min_jobs: its
+    `min_jobs`)."""
     from . import rbf_model as rm
 
     stats = stats if stats is not None else {}
     mods = rm.update_models_many([p["cfg"] for p in problems], [p["sites"] for p in problems], [p["values"] for p in problems],
                                  [p.get("delta", 1.0) for p in problems], ctx=ctx, stats=stats)
+    todo = [i for i, (problem, mod) in enumerate(zip(problems, mods)) if mod is not None and problem.get("X") is not None and len(problem["X"])]
+    est = {}
+    got = rm.eval_models_many([mods[i] for i in todo], [problems[i]["X"] for i in todo], want_values=True,
+                              want_jac=[problems[i].get("want_jac", True) for i in todo], stats=est, min_jobs=eval_min_jobs)
+    stats["eval"] = est
+    ms_eval = dict(zip(todo, est["ms_jobs"]))
+    vals_of = {i: g[0] for i, g in zip(todo, got)}
     recs = []
-    for problem, mod, status in zip(problems, mods, stats["status"]):
+    for i, (problem, mod, status) in enumerate(zip(problems, mods, stats["status"])):
         if mod is None:
             recs.append([float(problem["id"]), float(status) if status != 0 else -999.0] + [float("nan")] * (RECORD_LEN - 2))
             continue
-        info = {}
-        vals = None
-        if problem.get("X") is not None and len(problem["X"]):
-            vals, _ = mod.eval_sites(problem["X"], want_values=True, want_jac=problem.get("want_jac", True), info=info)
+        vals = vals_of.get(i)
         recs.append([float(problem["id"]), 0.0, float(mod.info["path"]), float(mod.info["rel_residual"]), float(np.sum(mod.weights)),
-                     float(np.sum(vals)) if vals is not None else 0.0, float(mod.info["ms_total"]), float(info.get("ms_total", 0.0))])
+                     float(np.sum(vals)) if vals is not None else 0.0, float(mod.info["ms_total"]), float(ms_eval.get(i, 0.0))])
     return np.asarray(recs, dtype=np.float64).reshape(-1, RECORD_LEN), mods
 
 

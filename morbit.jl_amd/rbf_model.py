@@ -343,6 +343,75 @@ def update_models_resident(cfgs, dbs, index_lists, deltas, fully_linear=False, c
     return mods
 
 
+def eval_models_many(mods, Xs, want_values=True, want_jac=False, outs=None, ctx=None, stats=None, min_jobs=None):
+    """`RbfModel.eval_sites` for a batch of (model, site block) pairs -- m(x) and m(x₊) of every start (src/algorithm.jl:766-767), the
+    container sweeps of every start (src/SurrogateContainer.jl:234-269) -- in ONE mrbf_eval_batch call where mrbf_dispatch_eval_batch
+    takes the job count and it reaches mrbf_dispatch_eval_batch_min_jobs (min_jobs: another threshold, for tests and measurements);
+    otherwise, or when the call returns -2, the loop over eval_sites.  A model may appear several times.  Xs[i]: m_i x d, a NumPy array
+    or a torch device tensor (used in place; then outs[i] = (out_vals, out_jac) device tensors must be given for what is wanted).
+    want_values / want_jac: one for all, or one per pair.  Returns a list of (vals, jac) -- for every pair bit for bit what
+    `mods[i].eval_sites(Xs[i], ...)` returns, in its shapes.  stats (optional dict) receives "path" ("batch" or "loop"), "jobs" (how
+    many pairs the one call carried), "single_inside" (how many of them took the single call's chain inside it: d > 256, or
+    MRBF_OPT_EVAL_IMPL = 1), "ms_total" (the batch call's, or the sum of the loop's) and "ms_jobs" (per pair: its own call's
+    time in the loop, the one call's in the batch)."""
+    n = len(mods)
+    stats = stats if stats is not None else {}
+    per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * n
+    wv, wj = per(want_values), per(want_jac)
+    outs = list(outs) if outs is not None else [(None, None)] * n
+    if n == 0:
+        stats.update(path="loop", jobs=0, single_inside=0, ms_total=0.0, ms_jobs=[])
+        return []
+    ctx = ctx or mods[0].ctx
+
+    def loop():
+        infos = [{} for _ in range(n)]
+        res = [mods[i].eval_sites(Xs[i], want_values=wv[i], want_jac=wj[i], out_vals=outs[i][0], out_jac=outs[i][1], info=infos[i]) for i in range(n)]
+        ms_jobs = [float(info.get("ms_total", 0.0)) for info in infos]
+        stats.update(path="loop", jobs=0, single_inside=0, ms_total=float(sum(ms_jobs)), ms_jobs=ms_jobs)
+        return res
+
+    lib = ctx.lib
+    floor = int(lib.mrbf_dispatch_eval_batch_min_jobs()) if min_jobs is None else int(min_jobs)
+    if lib.mrbf_dispatch_eval_batch(n) != _lib.DISPATCH_DEVICE or n < floor or any(m.ctx is not ctx for m in mods):
+        return loop()
+    jobs = (_lib.EvalJob * n)()
+    keep = []
+    for i, mod in enumerate(mods):
+        X = Xs[i]
+        is_np = not hasattr(X, "data_ptr")
+        X = _lib.host_f64(X).reshape(-1, mod.d) if is_np else X.contiguous()
+        m = int(X.shape[0])
+        vals = jac = None
+        if wv[i]:
+            vals = outs[i][0] if outs[i][0] is not None else (np.empty((m, mod.k)) if is_np else None)
+            assert vals is not None, "pass out_vals for device tensors"
+        if wj[i]:
+            jac = outs[i][1] if outs[i][1] is not None else (np.empty((m, mod.d, mod.k)) if is_np else None)
+            assert jac is not None, "pass out_jac for device tensors"
+        keep.append((X, vals, jac))
+        J = jobs[i]
+        J.model, J.m = mod.model.value if hasattr(mod.model, "value") else mod.model, m
+        J.X, J.vals_out, J.jac_out = (_lib.as_ptr(a).value if a is not None and m > 0 else None for a in (X, vals, jac))
+    ms = ctypes.c_float()
+    rc = lib.mrbf_eval_batch(ctx.h, n, jobs, ctypes.byref(ms))
+    if rc != 0 and lib.mrbf_dispatch_after(_lib.ENTRY_EVAL_BATCH, rc) == 1:
+        return loop()
+    ctx.check(rc)
+    res = []
+    for i, (X, vals, jac) in enumerate(keep):
+        if jac is not None and isinstance(jac, np.ndarray) and outs[i][1] is None:
+            jac = np.transpose(jac, (0, 2, 1))  # per-point k x d column-major block -> (m, k, d) view, as eval_sites
+        res.append((vals, jac))
+    # the pairs that took the single call's chain inside the call: outside the fused kernels' range (d > 256), or all of them under
+    # MRBF_OPT_EVAL_IMPL = 1 (pairs without rows or outputs launch nothing)
+    active = [i for i, (X, vals, jac) in enumerate(keep) if int(X.shape[0]) > 0 and (vals is not None or jac is not None)]
+    gemm = ctx.get_option(_lib.OPT_EVAL_IMPL) == 1
+    stats.update(path="batch", jobs=n, single_inside=sum(1 for i in active if gemm or mods[i].d > 256), ms_total=float(ms.value),
+                 ms_jobs=[float(ms.value)] * n)
+    return res
+
+
 init_model = update_model      # RbfModel.jl:738-741 delegates
 improve_model = update_model   # RbfModel.jl:770-776 delegates
 

@@ -151,10 +151,14 @@ class SurrogateContainer:
 
     def _eval_at_sites(self, kind, scal, X):
         X = np.ascontiguousarray(X, dtype=np.float64)
+        return self._eval_assemble(kind, scal, X, {id(inner): rm.eval_models_at_sites(inner, scal, X) for inner, _ in self._grouped(kind)})
+
+    def _eval_assemble(self, kind, scal, X, sweeps):
+        """the container's rows from the sweeps of its distinct inner models (id(inner) -> m x k values)"""
         offs = self._layout(kind)
         out = np.empty((X.shape[0], offs[-1]))
         for inner, members in self._grouped(kind):
-            V = rm.eval_models_at_sites(inner, scal, X)
+            V = sweeps[id(inner)]
             for pos, s in members:
                 if isinstance(s, CompositeSurrogate):
                     for p in range(X.shape[0]):
@@ -164,13 +168,21 @@ class SurrogateContainer:
                     out[:, offs[pos]:offs[pos + 1]] = V[:, idx]
         return out
 
+    def _jac_needs(self, kind):
+        """(inner model, whether the chain rule of a CompositeSurrogate needs its values too) per distinct inner model"""
+        return [(inner, any(isinstance(s, CompositeSurrogate) for _, s in members)) for inner, members in self._grouped(kind)]
+
     def _jac_at_sites(self, kind, scal, X):
         X = np.ascontiguousarray(X, dtype=np.float64)
+        return self._jac_assemble(kind, scal, X, {id(inner): inner.eval_sites(X, want_values=need_vals, want_jac=True)
+                                                  for inner, need_vals in self._jac_needs(kind)})
+
+    def _jac_assemble(self, kind, scal, X, sweeps):
+        """likewise from id(inner) -> (values or None, m x k x d Jacobians)"""
         offs = self._layout(kind)
         out = np.empty((X.shape[0], offs[-1], X.shape[1]))
         for inner, members in self._grouped(kind):
-            need_vals = any(isinstance(s, CompositeSurrogate) for _, s in members)
-            V, J = inner.eval_sites(X, want_values=need_vals, want_jac=True)
+            V, J = sweeps[id(inner)]
             J = np.ascontiguousarray(J)
             for pos, s in members:
                 if isinstance(s, CompositeSurrogate):
@@ -229,6 +241,31 @@ def container_plan(sc, objectives_only=False):
             "in_order": in_order}
 
 
+# ---- many-start twins of the batched container functions: one container per start (the Threads.@threads loop over starts of
+#      examples/large_scale_benchmarks.jl:102-109 around SurrogateContainer.jl:234-269), the distinct inner models of ALL containers in
+#      one rbf_model.eval_models_many; rows are selected, outer functions and the chain rule applied on the host exactly as the
+#      single-container twins do, so start p's result is what `sc[p]._eval_at_sites(kind, scal, Xs[p])` returns
+def eval_containers_at_scaled_sites(scs, scal, Xs, kind, stats=None, min_jobs=None):
+    Xs = [np.ascontiguousarray(X, dtype=np.float64) for X in Xs]
+    pairs = [(p, inner) for p, sc in enumerate(scs) for inner, _ in sc._grouped(kind)]
+    res = rm.eval_models_many([inner for _, inner in pairs], [Xs[p] for p, _ in pairs], stats=stats, min_jobs=min_jobs)
+    sweeps = [{} for _ in scs]
+    for (p, inner), (V, _) in zip(pairs, res):
+        sweeps[p][id(inner)] = V
+    return [sc._eval_assemble(kind, scal, Xs[p], sweeps[p]) for p, sc in enumerate(scs)]
+
+
+def eval_containers_jacobian_at_scaled_sites(scs, scal, Xs, kind, stats=None, min_jobs=None):
+    Xs = [np.ascontiguousarray(X, dtype=np.float64) for X in Xs]
+    pairs = [(p, inner, need_vals) for p, sc in enumerate(scs) for inner, need_vals in sc._jac_needs(kind)]
+    res = rm.eval_models_many([inner for _, inner, _ in pairs], [Xs[p] for p, _, _ in pairs], want_values=[nv for _, _, nv in pairs],
+                              want_jac=True, stats=stats, min_jobs=min_jobs)
+    sweeps = [{} for _ in scs]
+    for (p, inner, _), VJ in zip(pairs, res):
+        sweeps[p][id(inner)] = VJ
+    return [sc._jac_assemble(kind, scal, Xs[p], sweeps[p]) for p, sc in enumerate(scs)]
+
+
 def _make(kind, plural):
     def at_site(sc, scal, x_scaled):
         return sc._eval_at_site(kind, scal, x_scaled)
@@ -245,7 +282,15 @@ def _make(kind, plural):
     def handles(sc, scal):
         return sc._optim_handles(kind, scal)
 
+    def at_sites_many(scs, scal, Xs, stats=None, min_jobs=None):
+        return eval_containers_at_scaled_sites(scs, scal, Xs, kind, stats=stats, min_jobs=min_jobs)
+
+    def jac_at_sites_many(scs, scal, Xs, stats=None, min_jobs=None):
+        return eval_containers_jacobian_at_scaled_sites(scs, scal, Xs, kind, stats=stats, min_jobs=min_jobs)
+
     g = globals()
+    g["eval_container_%s_at_scaled_sites_many" % plural] = at_sites_many               # many-start twin: one container per start
+    g["eval_container_%s_jacobian_at_scaled_sites_many" % plural] = jac_at_sites_many  # many-start twin
     g["eval_container_%s_at_scaled_site" % plural] = at_site                 # SurrogateContainer.jl:263-267
     g["eval_container_%s_jacobian_at_scaled_site" % plural] = jac_at_site    # SurrogateContainer.jl:257-261
     g["eval_container_%s_at_scaled_sites" % plural] = at_sites               # batched twin
