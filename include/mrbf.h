@@ -186,6 +186,37 @@ int32_t mrbf_model_from_coeffs(mrbf_ctx *ctx, int64_t n, int32_t d, int32_t k, c
 int32_t mrbf_eval(mrbf_ctx *ctx, const mrbf_model *model, int64_t m, const double *X, double *vals_out,
                   double *jac_out, mrbf_eval_info *info);
 
+/* model Hessians at m points: the second derivative of model(x, l) with respect to the scaled site, for the selected outputs l --
+ * what a caller of the reference obtains by differentiating RBF.grad(model, x, l) / get_gradient (src/models/RbfModel.jl:792-795)
+ * once more; neither the reference nor its RBF package has a method for it, so there is no reference method to fall back to and
+ * no decision-table row: the call takes every d the library takes.
+ *     H_l(x) = sum_c w_cl [ psi(s_c) I + chi(s_c) (x - c)(x - c)' ],  s_c = |x - c|^2,  psi = phi'/rho,  chi = (phi'' - phi'/rho)/rho^2
+ * in difference form for every radial function, on the coordinates as given (the polynomial tail has degree <= 1 and contributes
+ * nothing).  A centre with s = 0 contributes w psi(0) I -- psi(0) as in mrbf_eval's Jacobian: the limit, or 0 where none exists --
+ * and no rank-one term.
+ * rows: n_rows 0-based output indices, any order, repeats allowed (repeated rows give identical blocks); NULL with n_rows = 0: all
+ * k outputs (r = k).  hess_out: m x r x d x d doubles, per point and selected output one d x d block; both triangles are written,
+ * the mirrored entry with the bits of its twin, so a block reads the same row-major and in Julia's column-major order.  X and
+ * hess_out may each be host or device memory; a device hess_out may start on any double.  m = 0: nothing to do, 0.
+ * Returns, and writes nothing: -1 no context; -2 NULL model; -4 a model of another context (mrbf_eval_batch's code); -3 m < 0;
+ * -5 n_rows < 0, or n_rows > 0 with NULL rows; -6 a row outside [0, k); with m > 0 also -4 NULL X and -7 NULL hess_out.
+ * The centre range is split over workgroups where the queries alone would not fill the device; the split count is a function of
+ * (m, n, d, r) alone (info->nsplit), the pieces are added in a fixed order, and for a given split count a query's blocks do not
+ * depend, bit for bit, on its position in X or on the other queries.  The same call twice gives the same bits.
+ * A host hess_out is staged through one grow-only work buffer in chunks of whole query points of at most 256 MiB (one point beyond
+ * that is a chunk of its own; info->chunks); results do not depend on the limit, and a second identical call allocates nothing.
+ * mrbf_eval_hessian_limited is the same call with that limit as an argument (stage_bytes <= 0: 256 MiB): for tests. */
+typedef struct {
+    float ms_total;   /* hipEvent time of the launches and read-backs on the ctx stream */
+    int32_t nsplit;   /* pieces the centre range was split into */
+    int32_t chunks;   /* chunks of query points the result was staged in (1 for a device hess_out) */
+    int32_t reserved;
+} mrbf_hess_info;
+int32_t mrbf_eval_hessian(mrbf_ctx *ctx, const mrbf_model *model, int64_t m, const double *X, int32_t n_rows, const int32_t *rows,
+                          double *hess_out, mrbf_hess_info *info);
+int32_t mrbf_eval_hessian_limited(mrbf_ctx *ctx, const mrbf_model *model, int64_t m, const double *X, int32_t n_rows,
+                                  const int32_t *rows, double *hess_out, mrbf_hess_info *info, int64_t stage_bytes);
+
 /* all step sizes of the Armijo backtracking loop in one batch -- replaces the
  * sequential loop of _backtrack (src/descent.jl:150-185) with condition
  * _armijo_condition (src/descent.jl:137-143).  Evaluates x + step0*shrink^i*dir,

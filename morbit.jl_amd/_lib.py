@@ -45,6 +45,14 @@ class EvalInfo(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class HessInfo(ctypes.Structure):
+    """mrbf_hess_info: what mrbf_eval_hessian reports"""
+    _fields_ = [("ms_total", ctypes.c_float), ("nsplit", ctypes.c_int32), ("chunks", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+    def asdict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 class PsOptions(ctypes.Structure):
     _fields_ = [("max_ideal_evals", ctypes.c_int32), ("max_ps_evals", ctypes.c_int32), ("max_polish_evals", ctypes.c_int32),
                 ("reserved", ctypes.c_int32), ("seed", ctypes.c_uint64), ("t0", ctypes.c_double), ("xtol_rel", ctypes.c_double)]
@@ -235,6 +243,9 @@ SIGNATURES = {
                                                 ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_int32,
                                                 ctypes.POINTER(c_vp)]),
     "mrbf_eval": (ctypes.c_int32, [c_vp, c_vp, ctypes.c_int64, c_vp, c_vp, c_vp, ctypes.POINTER(EvalInfo)]),
+    "mrbf_eval_hessian": (ctypes.c_int32, [c_vp, c_vp, ctypes.c_int64, c_vp, ctypes.c_int32, c_vp, c_vp, ctypes.POINTER(HessInfo)]),
+    "mrbf_eval_hessian_limited": (ctypes.c_int32, [c_vp, c_vp, ctypes.c_int64, c_vp, ctypes.c_int32, c_vp, c_vp, ctypes.POINTER(HessInfo),
+                                                   ctypes.c_int64]),
     "mrbf_backtrack": (ctypes.c_int32, [c_vp, c_vp, c_vp, c_vp, ctypes.c_double, ctypes.c_double, ctypes.c_int32,
                                         ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int32, c_vp, c_vp,
                                         c_vp, c_ip]),

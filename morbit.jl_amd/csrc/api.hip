@@ -4,6 +4,7 @@
 #include <thread>
 
 #include "common.hpp"
+#include "hess_host.hpp"
 
 using namespace mrbf;
 
@@ -300,6 +301,30 @@ int32_t mrbf_eval(mrbf_ctx *ctx, const mrbf_model *model, int64_t m, const doubl
     MRBF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     pin.flush();
     return MRBF_OK;
+}
+
+int32_t mrbf_eval_hessian_limited(mrbf_ctx *ctx, const mrbf_model *model, int64_t m, const double *X, int32_t n_rows,
+                                  const int32_t *rows, double *hess_out, mrbf_hess_info *info, int64_t stage_bytes) {
+    hess::Call c;
+    c.has_ctx = ctx != nullptr, c.has_model = model != nullptr;
+    c.foreign = model && model->owner != ctx;
+    c.m = m, c.k = model ? model->k : 0;
+    c.X = X != nullptr, c.out = hess_out != nullptr;
+    c.n_rows = n_rows, c.rows = rows;
+    if (const int rc = hess::validate(c)) {
+        if (!ctx) return rc;
+        static const char *const what[] = {"", "no context", "model is NULL", "m < 0", "the model belongs to another context, or X is NULL",
+                                           "n_rows < 0, or rows is NULL", "a row outside [0, k)", "hess_out is NULL"};
+        return fail(ctx, rc, "mrbf_eval_hessian: %s", what[-rc]);
+    }
+    if (info) std::memset(info, 0, sizeof(*info));
+    if (m == 0) return MRBF_OK;
+    return hess_call(ctx, model, m, X, hess::row_list(c), hess_out, info, stage_bytes);
+}
+
+int32_t mrbf_eval_hessian(mrbf_ctx *ctx, const mrbf_model *model, int64_t m, const double *X, int32_t n_rows, const int32_t *rows,
+                          double *hess_out, mrbf_hess_info *info) {
+    return mrbf_eval_hessian_limited(ctx, model, m, X, n_rows, rows, hess_out, info, 0);
 }
 
 int32_t mrbf_backtrack(mrbf_ctx *ctx, const mrbf_model *model, const double *x, const double *dir, double step0,

@@ -142,6 +142,66 @@ __device__ __forceinline__ void rbf_phi_psi_t(double s, const KP &p, double &phi
     }
 }
 
+// psi(s) = phi'(rho)/rho and chi(s) = 2 dpsi/ds = (phi'' - phi'/rho)/rho^2: the two radial factors of the model Hessian
+//     H = sum_c w_c [ psi(s_c) I + chi(s_c) (x - c)(x - c)' ]                                   (hess.hip, DESIGN.md "Model Hessians").
+// psi is rbf_phi_psi's to rounding, and exactly its value at s = 0 (the limit, or 0 where none exists).  chi is
+// unbounded at 0 for cubic beta <= 3 and thin plate spline k <= 2: the caller never uses chi at s <= 0 (a centre under the query
+// contributes its diagonal term only), so what this returns there is unspecified -- select, never multiply by 0.
+template <int KID, bool FAST>
+__device__ __forceinline__ void rbf_psi_chi(double s, const KP &p, double &psi, double &chi) {
+    if constexpr (KID == MRBF_GAUSSIAN) {
+        const double e = exp(-p.a2 * s);
+        psi = -2.0 * p.a2 * e;
+        chi = 4.0 * p.a2 * p.a2 * e;
+    } else if constexpr (KID == MRBF_MULTIQUADRIC) {
+        const double t = fma(p.a2, s, 1.0);
+        if constexpr (FAST) {  // b = 1/2, sgn = -1: psi = -a^2 t^(-1/2), chi = a^4 t^(-3/2)
+            double sq, rs;
+            fast_sqrt_rsqrt(t, sq, rs);
+            psi = -p.a2 * rs;
+            chi = p.a2 * p.a2 * rs * rs * rs;
+        } else {
+            const double pw = pow(t, p.b);
+            psi = p.sgn * 2.0 * p.a2 * p.b * pw / t;
+            chi = p.sgn * 4.0 * p.a2 * p.a2 * p.b * (p.b - 1.0) * pw / (t * t);
+        }
+    } else if constexpr (KID == MRBF_INV_MULTIQUADRIC) {
+        const double t = fma(p.a2, s, 1.0);
+        if constexpr (FAST) {  // b = 1/2: psi = -a^2 t^(-3/2), chi = 3 a^4 t^(-5/2)
+            double sq, rs;
+            fast_sqrt_rsqrt(t, sq, rs);
+            const double rs3 = rs * rs * rs;
+            psi = -p.a2 * rs3;
+            chi = 3.0 * p.a2 * p.a2 * rs3 * rs * rs;
+        } else {
+            const double pw = pow(t, -p.b);
+            psi = -2.0 * p.a2 * p.b * pw / t;
+            chi = 4.0 * p.a2 * p.a2 * p.b * (p.b + 1.0) * pw / (t * t);
+        }
+    } else if constexpr (KID == MRBF_CUBIC) {
+        if constexpr (FAST) {  // beta = 3: psi = sgn 3 rho, chi = sgn 3 / rho
+            double sq, rs;
+            fast_sqrt_rsqrt(s > 0.0 ? s : 1.0, sq, rs);
+            psi = s > 0.0 ? p.sgn * 3.0 * sq : 0.0;
+            chi = p.sgn * 3.0 * rs;
+        } else {
+            const double r = sqrt(s);
+            psi = (s <= 0.0 && p.a < 2.0) ? 0.0 : p.sgn * p.a * pow(r, p.a - 2.0);
+            chi = p.sgn * p.a * (p.a - 2.0) * pow(r, p.a - 4.0);
+        }
+    } else {  // thin plate spline: psi = sgn s^(k-1) (k log s + 1), chi = sgn 2 s^(k-2) [(k-1)(k log s + 1) + k]
+        if (s <= 0.0) {
+            psi = 0.0;
+            chi = 0.0;
+        } else {
+            const double kl1 = fma((double)p.ik, log(s), 1.0);
+            const double sk2 = p.ik >= 2 ? ipow_small(s, p.ik - 2) : 1.0 / s;
+            psi = p.sgn * (sk2 * s) * kl1;
+            chi = p.sgn * 2.0 * sk2 * fma((double)(p.ik - 1), kl1, (double)p.ik);
+        }
+    }
+}
+
 // host-side dispatch over the kernel id
 #define MRBF_DISPATCH_KID(kid, ...)                                        \
     switch (kid) {                                                         \

@@ -108,6 +108,10 @@ struct MrbfEvalJob          # mirrors mrbf_eval_job, 48 bytes
     status::Int32; reserved::Int32
 end
 
+struct MrbfHessInfo         # mirrors mrbf_hess_info, 16 bytes
+    ms_total::Float32; nsplit::Int32; chunks::Int32; reserved::Int32
+end
+
 struct MrbfPsProblem        # mirrors mrbf_ps_problem, 72 bytes
     n_models::Int32; n_objectives::Int32
     models::Ptr{Ptr{Cvoid}}; roles::Ptr{Int32}
@@ -611,6 +615,34 @@ function get_jacobian(mod::HipRbfModel, scal::AbstractVarScaler, x̂::Vec, rows 
 end
 "Gradient of output `ℓ` (RbfModel.jl:792-795): the Jacobian row, bit for bit (test/rbf_models.jl:105-109)."
 get_gradient(mod::HipRbfModel, scal::AbstractVarScaler, x̂::Vec, ℓ) = vec(get_jacobian(mod, scal, x̂, ℓ))
+
+"""
+Model Hessians at the columns of `X` (d x m, one scaled site per column) in one device call (`mrbf_eval_hessian`): a d x d x r x m
+array, `H[:, :, j, p]` the second derivative of output `rows[j]` with respect to the scaled site at site p (`rows`: 1-based output
+indices, any order, repeats allowed; `nothing`: all outputs).  Both triangles are written with the same bits, so the row-major
+blocks of the library read the same in column-major order.  The reference has no method for this (RbfModel.jl:792-800 stops at
+gradients and Jacobians).  `with_info = true` returns `(H, info)` with the call's `MrbfHessInfo` (time, split count, chunks).
+"""
+function hip_get_hessians_at_sites(mod::HipRbfModel, scal, X::Matrix{Float64}, rows = nothing; with_info::Bool = false)
+    d, m = mod.n_vars, size(X, 2)
+    rows0 = isnothing(rows) ? Int32[] : Int32[Int32(ℓ - 1) for ℓ in rows]
+    r = isnothing(rows) ? mod.num_outputs : length(rows0)
+    H = Array{Float64,4}(undef, d, d, r, m)
+    info = Ref(MrbfHessInfo(0.0f0, 0, 0, 0))
+    (m == 0 || r == 0) && return with_info ? (H, info[]) : H
+    rc = GC.@preserve X rows0 H begin
+        _locked(mod.ctx) do hctx
+            ccall((:mrbf_eval_hessian, libmrbf), Int32,
+                  (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Float64}, Int32, Ptr{Int32}, Ptr{Float64}, Ref{MrbfHessInfo}),
+                  hctx, mod.handle, m, X, length(rows0), isempty(rows0) ? C_NULL : pointer(rows0), H, info)
+        end
+    end
+    _check(mod.ctx, rc)
+    return with_info ? (H, info[]) : H
+end
+"d x d Hessian of output `ℓ` at `x̂` with respect to the scaled site: the derivative of `get_gradient(mod, scal, x̂, ℓ)`."
+hip_get_hessian(mod::HipRbfModel, scal, x̂::Vec, ℓ::Integer) =
+    hip_get_hessians_at_sites(mod, scal, reshape(Vector{Float64}(x̂), :, 1), [ℓ])[:, :, 1, 1]
 
 # batched twins (m sites as the columns of X): one device sweep for all k outputs of all sites
 eval_models_at_sites(mod::HipRbfModel, scal, X::AbstractMatrix) = _mrbf_eval(mod, Matrix{Float64}(X))[1]

@@ -175,6 +175,33 @@ class RbfModel:
             jac = np.transpose(jac, (0, 2, 1))  # per-point k x d column-major block -> (m, k, d) view
         return vals, jac
 
+    def hessian_sites(self, X, rows=None, out=None, info=None, stage_bytes=None):
+        """model Hessians (m x r x d x d) at m scaled sites in one mrbf_eval_hessian call: per site and selected output the second
+        derivative of that output with respect to the scaled site.  rows: 0-based output indices, any order, repeats allowed
+        (None: all k).  X / out may be NumPy arrays (host) or torch CUDA tensors (used in place; pass `out` for those).
+        stage_bytes: the staging limit of a host-side result, for tests (mrbf_eval_hessian_limited)."""
+        lib, ctx = self.ctx.lib, self.ctx
+        is_np = not hasattr(X, "data_ptr")
+        if is_np:
+            X = _lib.host_f64(X).reshape(-1, self.d)
+        m = int(X.shape[0])
+        rows_a = None if rows is None else np.ascontiguousarray(np.atleast_1d(rows), dtype=np.int32)
+        r = self.k if rows_a is None else int(rows_a.size)
+        if rows_a is not None and r == 0:
+            return out if out is not None else np.empty((m, 0, self.d, self.d))
+        if out is None:
+            assert is_np, "pass out for device tensors"
+            out = np.empty((m, r, self.d, self.d))
+        hi = _lib.HessInfo()
+        args = (ctx.h, self.model, m, _lib.as_ptr(X), 0 if rows_a is None else r, _lib.as_ptr(rows_a), _lib.as_ptr(out), ctypes.byref(hi))
+        if stage_bytes is None:
+            ctx.check(lib.mrbf_eval_hessian(*args))
+        else:
+            ctx.check(lib.mrbf_eval_hessian_limited(*args, int(stage_bytes)))
+        if info is not None:
+            info.update(hi.asdict())
+        return out
+
 
 def fully_linear(rbf):
     return rbf.fully_linear  # RbfModel.jl:40
@@ -451,7 +478,18 @@ def get_jacobian(mod, scal, x_hat, rows=None):
     return J if rows is None else J[rows]
 
 
+def get_hessian(mod, scal, x_hat, ell):
+    """d x d Hessian of output `ell` at x̂ with respect to the scaled site: the derivative of get_gradient (RbfModel.jl:792-795),
+    which the reference leaves to the caller."""
+    return mod.hessian_sites(np.asarray(x_hat, dtype=np.float64)[None, :], rows=[int(ell)])[0, 0]
+
+
 # batched twins
+def get_hessians_at_sites(mod, scal, X, rows=None):
+    """(m, r, d, d): the Hessians of the selected outputs (None: all) at the rows of X"""
+    return mod.hessian_sites(X, rows=rows)
+
+
 def eval_models_at_sites(mod, scal, X):
     return mod.eval_sites(X)[0]
 

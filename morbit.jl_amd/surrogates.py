@@ -98,6 +98,16 @@ def get_jacobian(sur, scal, x_hat, rows=None):
     return rm.get_jacobian(sur, scal, x_hat, rows)
 
 
+def get_hessian(sur, scal, x_hat, ell):
+    """d x d Hessian of output `ell` of the surrogate with respect to the scaled site.  A RefSurrogate selects the row of its grouped
+    model; the second-order chain rule through a CompositeSurrogate's outer function is not provided."""
+    if isinstance(sur, CompositeSurrogate):
+        raise NotImplementedError("get_hessian: the second-order chain rule through a CompositeSurrogate's outer function is not provided")
+    if isinstance(sur, RefSurrogate):
+        return rm.get_hessian(sur.model, scal, x_hat, sur.output_indices[ell])
+    return rm.get_hessian(sur, scal, x_hat, ell)
+
+
 def _get_optim_handle(sur, scal, ell):
     """NLopt-style closure (x, g) -> value, filling g in place when non-empty (AbstractSurrogateInterface.jl:98-106)."""
 
