@@ -441,6 +441,53 @@ typedef struct {
 int32_t mrbf_eval_batch(mrbf_ctx *ctx, int64_t n_jobs, mrbf_eval_job *jobs, float *ms_total);
 int32_t mrbf_eval_batch_limited(mrbf_ctx *ctx, int64_t n_jobs, mrbf_eval_job *jobs, float *ms_total, int64_t arena_limit_bytes);
 
+/* ---- many-start model Hessians: one call for a batch of kept models (hess.hip, host logic in hess_batch_host.hpp) ------------
+ * mrbf_eval_hessian for n_jobs independent (model, site block) pairs on ONE context: the second derivative of every start's model at
+ * its own iterate, for the reference's Threads.@threads loop over starts (examples/large_scale_benchmarks.jl:102-109) around a
+ * method the reference does not have (the derivative of get_gradient, src/models/RbfModel.jl:792-800, taken once more).
+ * For every job, hess_out is, bit for bit, what mrbf_eval_hessian(ctx, model, m, X, n_rows, rows, hess_out, NULL) writes on the same
+ * context; it does not depend on the job's position, on which other jobs share the call, or on the limit below.  Every job keeps the
+ * split count of the single call it stands for (job.nsplit: a function of its own m, n, d, r), the same piece length and the same
+ * order of adding the pieces: no arithmetic of its own, the single call's two kernel bodies behind a descriptor array and a table of
+ * first block indices in which a workgroup finds its descriptor.  The price: every job splits as if it were alone on the device.
+ * Models may come from mrbf_fit, mrbf_fit_batch, mrbf_fit_from_round4 or mrbf_model_from_coeffs, may appear in several jobs, and may
+ * differ in n, d, k, kernel and parameters.  Jobs share launches by template instantiation alone -- (radial function, fast form,
+ * outputs per pass) for the main kernel, outputs per pass for the combining kernel --, so starts of one radial function and one r
+ * take one main launch and at most one combining launch whatever their n.  A job beyond 2^30 blocks is cut by points as the single
+ * call cuts it.
+ * One packed upload (descriptors, block tables, row lists, all host-side query rows), one read-back (all host-side results), one
+ * synchronisation.  Device-side X / hess_out are read and written in place (the descriptors carry their addresses).  The work
+ * buffer is one slot of the context's arena: a second identical call allocates nothing.  A call whose work buffer would exceed
+ * 2 GiB is processed in chunks of consecutive jobs (then: one upload, read-back and synchronisation per chunk); a single job beyond
+ * the limit runs the single call's chain, with its 256 MiB staging rule, inside the call (info->single_inside).
+ * m == 0 jobs write nothing and have status 0.
+ * Returns 0; -1 without a context; -2, and only -2, when mrbf_dispatch_hessian_batch refuses n_jobs: take mrbf_eval_hessian per
+ * job; -3 for an invalid job (`jobs` NULL; NULL model; m < 0; n_rows < 0; n_rows > 0 with NULL rows; a row outside [0, k); with m > 0
+ * NULL X or NULL hess_out): nothing is launched or written, and every job's status holds the single call's own code (-2, -3, -5, -6,
+ * -4, -7; 0 for a valid job); -4 for a model of another context (likewise nothing launched or written); -3 goes in front of -4.
+ * info may be NULL.  mrbf_eval_hessian_batch_limited is the same call with the 2 GiB limit of the chunk rule as an argument
+ * (arena_limit_bytes <= 0: 2 GiB): for tests of the chunk path; the results do not depend on it. */
+typedef struct {
+    const mrbf_model *model;
+    int64_t m;
+    const double *X;        /* m x d row-major, host or device (detected per pointer); may be NULL when m == 0 */
+    const int32_t *rows;    /* host memory: n_rows 0-based outputs, any order, repeats allowed; NULL with n_rows = 0: all k */
+    double *hess_out;       /* m x r x d x d, host or device (a device buffer may start on any double); may be NULL when m == 0 */
+    int32_t n_rows;
+    int32_t status;         /* out: what mrbf_eval_hessian would have returned for this job */
+    int32_t nsplit;         /* out: pieces of this job's centre range (0 when nothing ran) */
+    int32_t reserved;
+} mrbf_hess_job;            /* 56 bytes */
+typedef struct {
+    float ms_total;         /* hipEvent time of the whole call on the ctx stream */
+    int32_t chunks;         /* upload / launch / read-back rounds the call took */
+    int32_t groups;         /* kernel groups launched, summed over the chunks */
+    int32_t single_inside;  /* jobs that ran the single call's chain inside the call */
+} mrbf_hess_batch_info;     /* 16 bytes */
+int32_t mrbf_eval_hessian_batch(mrbf_ctx *ctx, int64_t n_jobs, mrbf_hess_job *jobs, mrbf_hess_batch_info *info);
+int32_t mrbf_eval_hessian_batch_limited(mrbf_ctx *ctx, int64_t n_jobs, mrbf_hess_job *jobs, mrbf_hess_batch_info *info,
+                                        int64_t arena_limit_bytes);
+
 /* ---- resident site database: box scan and gathers for many-start updates (db.hip, host logic in db_host.hpp) -----------------
  * A start's evaluation database -- the ArrayDB of src/Databases.jl: sites (d) and values (k), rows in insertion order, a row's
  * position being its id -- kept on the device and appended to as the run goes, so that the batched calls above read their inputs from
@@ -946,6 +993,13 @@ int32_t mrbf_ps_step_batch(mrbf_ctx *ctx, int64_t n_starts, const mrbf_ps_proble
  *                            (measured cells only, tools/eval_batch_bench.py, DESIGN.md section 18: admitted where the batch took
  *                            at most 0.8 of the loop's median -- 0.48 at 8 C4 evaluations, 0.16 at 8 acceptance-test pairs --;
  *                            monotone: every job count from the answer, 8, on takes the batch; fewer were not measured).
+ *   mrbf_dispatch_hessian_batch  mrbf_eval_hessian of n_jobs (model, site block) pairs in one call (mrbf_eval_hessian_batch): device
+ *                            iff 1 <= n_jobs <= 65535, the family's limit.
+ *   mrbf_dispatch_hessian_batch_min_jobs  the fewest jobs from which the bindings make that one call instead of the loop of
+ *                            mrbf_eval_hessian (measured cells only, tools/hessian_batch_bench.py, DESIGN.md section 20: admitted where
+ *                            the batch took at most 0.8 of the loop's median on the parent build -- 0.54 at 2 C4 models with one
+ *                            site each, 0.68 with 16 sites each --; monotone: every job count from the answer, 2, on takes the
+ *                            batch; a value above 65535 would mean: the bindings keep the loop).
  *   mrbf_dispatch_after      the return code rc of a device entry point (MRBF_ENTRY_*) that means "take the reference method
  *                            for this call" (start set without the tail or rank deficient, limits of the device path) rather
  *                            than an error: 1 = fall back, 0 = rc is what it says. */
@@ -955,7 +1009,7 @@ enum { MRBF_ENTRY_ROUND4 = 1, MRBF_ENTRY_FIT_FROM_ROUND4 = 2, MRBF_ENTRY_PS_STEP
        MRBF_ENTRY_SD = 6, MRBF_ENTRY_NORMAL = 7, MRBF_ENTRY_SD_STEP = 8, MRBF_ENTRY_SD_BATCH = 9, MRBF_ENTRY_AFFINE_BATCH = 10,
        MRBF_ENTRY_FIT_BATCH = 11, MRBF_ENTRY_NORMAL_BATCH = 12, MRBF_ENTRY_ROUND4_BATCH = 13, MRBF_ENTRY_PS_BATCH = 14,
        MRBF_ENTRY_DB_BOX = 15, MRBF_ENTRY_DB_GATHER = 16, MRBF_ENTRY_DB_ROUND3 = 17, MRBF_ENTRY_DB_APPEND_BATCH = 18,
-       MRBF_ENTRY_DB_SET_VALUES_BATCH = 19, MRBF_ENTRY_EVAL_BATCH = 20 };
+       MRBF_ENTRY_DB_SET_VALUES_BATCH = 19, MRBF_ENTRY_EVAL_BATCH = 20, MRBF_ENTRY_HESSIAN_BATCH = 21 };
 int32_t mrbf_dispatch_ps(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_ps_batch(int64_t n_starts, int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints,
                                int32_t n_lin_constraints, int32_t n_foreign);
@@ -978,6 +1032,8 @@ int32_t mrbf_dispatch_round4_batch(int64_t n_starts, int32_t d);
 int32_t mrbf_dispatch_db_batch(int64_t n_starts, int32_t d);
 int32_t mrbf_dispatch_eval_batch(int64_t n_jobs);
 int64_t mrbf_dispatch_eval_batch_min_jobs(void);
+int32_t mrbf_dispatch_hessian_batch(int64_t n_jobs);
+int64_t mrbf_dispatch_hessian_batch_min_jobs(void);
 int32_t mrbf_dispatch_fit(int64_t n_training, int64_t state_n0, int32_t state_q, int32_t state_n_accepted, int32_t same_sites);
 int32_t mrbf_dispatch_after(int32_t entry, int32_t rc);
 

@@ -15,7 +15,7 @@ Importing the package does not need a GPU; any compute call does, and fails loud
 from . import _lib  # noqa: F401
 from ._lib import Context, MrbfError, default_context, load  # noqa: F401
 from .rbf_model import (RbfConfig, RbfKernels, RbfModel, combinable, eval_models, eval_models_at_sites,  # noqa: F401
-                        fully_linear, get_gradient, get_hessian, get_hessians_at_sites, get_jacobian, get_jacobians_at_sites,
+                        fully_linear, get_gradient, get_hessian, get_hessians_at_sites, get_hessians_many, get_jacobian, get_jacobians_at_sites,
                         get_matrices, improve_model,
                         init_model, max_evals, model_from_coeffs, num_outputs, parse_shape_param_string,
                         set_fully_linear, update_model, update_models_many, update_models_resident)

@@ -53,6 +53,21 @@ class HessInfo(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class HessJob(ctypes.Structure):
+    """mrbf_hess_job: one (model, site block) pair of mrbf_eval_hessian_batch"""
+    _fields_ = [("model", ctypes.c_void_p), ("m", ctypes.c_int64), ("X", ctypes.c_void_p), ("rows", ctypes.c_void_p),
+                ("hess_out", ctypes.c_void_p), ("n_rows", ctypes.c_int32), ("status", ctypes.c_int32), ("nsplit", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+class HessBatchInfo(ctypes.Structure):
+    """mrbf_hess_batch_info: what mrbf_eval_hessian_batch reports"""
+    _fields_ = [("ms_total", ctypes.c_float), ("chunks", ctypes.c_int32), ("groups", ctypes.c_int32), ("single_inside", ctypes.c_int32)]
+
+    def asdict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 class PsOptions(ctypes.Structure):
     _fields_ = [("max_ideal_evals", ctypes.c_int32), ("max_ps_evals", ctypes.c_int32), ("max_polish_evals", ctypes.c_int32),
                 ("reserved", ctypes.c_int32), ("seed", ctypes.c_uint64), ("t0", ctypes.c_double), ("xtol_rel", ctypes.c_double)]
@@ -83,6 +98,7 @@ ENTRY_DB_ROUND3 = 17
 ENTRY_DB_APPEND_BATCH = 18
 ENTRY_DB_SET_VALUES_BATCH = 19
 ENTRY_EVAL_BATCH = 20
+ENTRY_HESSIAN_BATCH = 21
 R3_UPDATE, R3_IMPROVE = 0, 1
 R3_DONE, R3_REBUILT = 0, 1
 SD_OK, SD_NO_OBJECTIVE, SD_INFEASIBLE, SD_GAVE_UP = 0, 1, 2, 3
@@ -273,6 +289,11 @@ SIGNATURES = {
     "mrbf_eval_batch_limited": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.POINTER(EvalJob), c_fp, ctypes.c_int64]),
     "mrbf_dispatch_eval_batch": (ctypes.c_int32, [ctypes.c_int64]),
     "mrbf_dispatch_eval_batch_min_jobs": (ctypes.c_int64, []),
+    "mrbf_eval_hessian_batch": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.POINTER(HessJob), ctypes.POINTER(HessBatchInfo)]),
+    "mrbf_eval_hessian_batch_limited": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.POINTER(HessJob), ctypes.POINTER(HessBatchInfo),
+                                                         ctypes.c_int64]),
+    "mrbf_dispatch_hessian_batch": (ctypes.c_int32, [ctypes.c_int64]),
+    "mrbf_dispatch_hessian_batch_min_jobs": (ctypes.c_int64, []),
     "mrbf_db_create": (ctypes.c_int32, [c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.POINTER(c_vp)]),
     "mrbf_db_append": (ctypes.c_int32, [c_vp, c_vp, ctypes.c_int64, c_vp, c_vp, ctypes.POINTER(ctypes.c_int64)]),
     "mrbf_db_set_values": (ctypes.c_int32, [c_vp, c_vp, ctypes.c_int64, c_vp, c_vp]),

@@ -327,6 +327,20 @@ int32_t mrbf_eval_hessian(mrbf_ctx *ctx, const mrbf_model *model, int64_t m, con
     return mrbf_eval_hessian_limited(ctx, model, m, X, n_rows, rows, hess_out, info, 0);
 }
 
+int32_t mrbf_eval_hessian_batch_limited(mrbf_ctx *ctx, int64_t n_jobs, mrbf_hess_job *jobs, mrbf_hess_batch_info *info,
+                                        int64_t arena_limit_bytes) {
+    if (!ctx) return -1;
+    if (info) std::memset(info, 0, sizeof(*info));
+    if (mrbf_dispatch_hessian_batch(n_jobs) != MRBF_DISPATCH_DEVICE)
+        return fail(ctx, -2, "mrbf_eval_hessian_batch: %lld jobs outside the device path (ask mrbf_dispatch_hessian_batch first)",
+                    (long long)n_jobs);
+    return hess_batch_call(ctx, n_jobs, jobs, info, arena_limit_bytes);
+}
+
+int32_t mrbf_eval_hessian_batch(mrbf_ctx *ctx, int64_t n_jobs, mrbf_hess_job *jobs, mrbf_hess_batch_info *info) {
+    return mrbf_eval_hessian_batch_limited(ctx, n_jobs, jobs, info, 0);
+}
+
 int32_t mrbf_backtrack(mrbf_ctx *ctx, const mrbf_model *model, const double *x, const double *dir, double step0,
                        double omega, int32_t strict, double const_rhs, double shrink, double min_stepsize,
                        int32_t max_loops, double *x_plus, double *mx_plus, double *step, int32_t *n_loops) {

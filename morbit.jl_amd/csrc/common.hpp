@@ -42,7 +42,7 @@ enum Slot {
     S_XC = 0, S_SQ, S_MEAN, S_PHI, S_PI, S_Q1, S_W1, S_G, S_R, S_TAU, S_RHS, S_T1, S_T2, S_IPIV, S_INFO,
     S_STAGE_A, S_STAGE_B, S_STAGE_C, S_STAGE_D, S_EVAL_E, S_EVAL_A, S_EVAL_J, S_EVAL_SA, S_EVAL_XC, S_EVAL_XSQ,
     S_OUT_A, S_OUT_B, S_CHOL_WS, S_MISC, S_MEGA_JOBS, S_MEGA_FLAGS, S_MEGA_WQ, S_MEGA_IT, S_BSOLVE_FLAGS, S_MEGA_TRACE, S_MEGA_JLOG,
-    S_T1W, S_PS_STATE, S_PS_STAT, S_PS_POLISH, S_BSOLVE_X, S_V0, S_QR_INV, S_DIAG_SCR, S_SMALL_WS, S_SMALL_DESC, S_SMALL_FLAGS, S_MEGA_STAT, S_BSOLVE_M, S_SMALL_CL, S_GW_PART, S_GW_RS, S_GW_GP, S_GW_M, S_CHECK_SCAL, S_TAIL_PART, S_PS_RANK, S_SD_IN, S_SD_OUT, S_SD_WS, S_NS_IN, S_NS_OUT, S_NS_WS, S_SD_STEP, S_SD_BATCH, S_AFF_BATCH, S_NS_BATCH, S_R4_BATCH, S_DB_BOX, S_DB_GATHER, S_DB_WS, S_SMALL_LU, S_EVAL_BATCH, S_HESS_WS, S_HESS_OUT, S_NSLOTS
+    S_T1W, S_PS_STATE, S_PS_STAT, S_PS_POLISH, S_BSOLVE_X, S_V0, S_QR_INV, S_DIAG_SCR, S_SMALL_WS, S_SMALL_DESC, S_SMALL_FLAGS, S_MEGA_STAT, S_BSOLVE_M, S_SMALL_CL, S_GW_PART, S_GW_RS, S_GW_GP, S_GW_M, S_CHECK_SCAL, S_TAIL_PART, S_PS_RANK, S_SD_IN, S_SD_OUT, S_SD_WS, S_NS_IN, S_NS_OUT, S_NS_WS, S_SD_STEP, S_SD_BATCH, S_AFF_BATCH, S_NS_BATCH, S_R4_BATCH, S_DB_BOX, S_DB_GATHER, S_DB_WS, S_SMALL_LU, S_EVAL_BATCH, S_HESS_WS, S_HESS_OUT, S_HESS_BATCH, S_NSLOTS
 };
 }  // namespace mrbf
 
@@ -299,6 +299,8 @@ int eval_model(mrbf_ctx *ctx, const mrbf_model *M, int64_t m, const double *Xdev
 // hess.hip: the validated mrbf_eval_hessian call (rows: the selected outputs; stage_bytes <= 0: the default limit of hess_host.hpp)
 int hess_call(mrbf_ctx *ctx, const mrbf_model *M, int64_t m, const double *X, const std::vector<int32_t> &rows, double *hess_out,
               mrbf_hess_info *info, int64_t stage_bytes);
+// hess.hip: mrbf_eval_hessian_batch behind the context and job-count checks (limit_bytes <= 0: the default limit of hess_batch_host.hpp)
+int hess_batch_call(mrbf_ctx *ctx, int64_t n_jobs, mrbf_hess_job *jobs, mrbf_hess_batch_info *info, int64_t limit_bytes);
 // chol_blocked.hip (the tall factorisation; chol_mega.hip: the same as one persistent launch) / chol.hip
 int potrf_blocked_tall(mrbf_ctx *ctx, int64_t ncols, int64_t mrows, double *A, int64_t lda, int *dinfo, double *linv_all, PotrfOpts opt = {});
 int potrf_mega_tall(mrbf_ctx *ctx, int64_t ncols, int64_t mrows, double *A, int64_t lda, int *dinfo, double *linv_all, PotrfOpts opt = {});

@@ -34,6 +34,13 @@ constexpr int FIT_LU_ROWS = (int)(sizeof(FIT_LU) / sizeof(FIT_LU[0]));
 // Jacobians, 0.16, 0.083, 0.033 at 8, 16, 64 jobs of m = 2 values only, 0.031 at 64 jobs of d = 3, n = 20; fewer than 8 jobs were not
 // measured and keep the loop
 constexpr int64_t EVAL_BATCH_MIN_JOBS = 8;
+// mrbf_dispatch_hessian_batch_min_jobs: from this many jobs on the bindings make one mrbf_eval_hessian_batch call instead of the loop of
+// mrbf_eval_hessian.  Measured (tools/hessian_batch_bench.py, profiles/hessian_batch_bench.jsonl: all outputs of k = 2, device-resident
+// buffers, medians of 30 host-clock calls): batch / loop of single calls on the parent build = 0.54, 0.28, 0.15, 0.097, 0.054 at 2, 4, 8,
+// 16, 64 jobs of the C4 model (d = 128, n = 257) with m = 1 and 0.68, 0.47, 0.37, 0.41, 0.37 with m = 16; 0.16, 0.094 at 8, 64 jobs of
+// the C3 model (d = 64, n = 8192, m = 1); 0.33, 0.31 at 8, 64 jobs of d = 256, n = 1024 (m = 1): every measured cell is admitted; a
+// single job was not measured and keeps the single call
+constexpr int64_t HESSIAN_BATCH_MIN_JOBS = 2;
 }  // namespace
 
 extern "C" {
@@ -178,6 +185,14 @@ int32_t mrbf_dispatch_eval_batch(int64_t n_jobs) { return n_jobs >= 1 && n_jobs 
 // parent build; monotone: every larger batch takes the call as well; a value above 65535 would mean: the bindings keep the loop)
 int64_t mrbf_dispatch_eval_batch_min_jobs(void) { return EVAL_BATCH_MIN_JOBS; }
 
+// the Hessians of many kept models in one call (hess.hip, mrbf_eval_hessian_batch): the family's limit on the job count; which jobs
+// share a launch is decided there, by kernel instantiation alone
+int32_t mrbf_dispatch_hessian_batch(int64_t n_jobs) { return n_jobs >= 1 && n_jobs <= 65535 ? MRBF_DISPATCH_DEVICE : MRBF_DISPATCH_REFERENCE; }
+
+// the fewest jobs from which that call pays (the admission rule of mrbf_dispatch_eval_batch_min_jobs; a value above 65535 would mean: the
+// bindings keep the loop)
+int64_t mrbf_dispatch_hessian_batch_min_jobs(void) { return HESSIAN_BATCH_MIN_JOBS; }
+
 int32_t mrbf_dispatch_fit(int64_t n_training, int64_t state_n0, int32_t state_q, int32_t state_n_accepted, int32_t same_sites) {
     if (state_n0 < 1 || state_n_accepted < 1 || !same_sites) return MRBF_FIT_FULL;
     if (state_n0 != state_q) return MRBF_FIT_FULL;  // the kept factor only covers the directions added by round 4
@@ -213,6 +228,7 @@ int32_t mrbf_dispatch_after(int32_t entry, int32_t rc) {
         case MRBF_ENTRY_DB_APPEND_BATCH: return rc == -2;
         case MRBF_ENTRY_DB_SET_VALUES_BATCH: return rc == -2;
         case MRBF_ENTRY_EVAL_BATCH: return rc == -2;  // the table refuses the job count: mrbf_eval per job; a job's own status is an error
+        case MRBF_ENTRY_HESSIAN_BATCH: return rc == -2;  // likewise: mrbf_eval_hessian per job; a job's own status is an error
         default: return 0;
     }
 }

@@ -112,6 +112,17 @@ struct MrbfHessInfo         # mirrors mrbf_hess_info, 16 bytes
     ms_total::Float32; nsplit::Int32; chunks::Int32; reserved::Int32
 end
 
+struct MrbfHessJob          # mirrors mrbf_hess_job, 56 bytes
+    model::Ptr{Cvoid}
+    m::Int64
+    X::Ptr{Float64}; rows::Ptr{Int32}; hess_out::Ptr{Float64}
+    n_rows::Int32; status::Int32; nsplit::Int32; reserved::Int32
+end
+
+struct MrbfHessBatchInfo    # mirrors mrbf_hess_batch_info, 16 bytes
+    ms_total::Float32; chunks::Int32; groups::Int32; single_inside::Int32
+end
+
 struct MrbfPsProblem        # mirrors mrbf_ps_problem, 72 bytes
     n_models::Int32; n_objectives::Int32
     models::Ptr{Ptr{Cvoid}}; roles::Ptr{Int32}
@@ -311,6 +322,9 @@ end
 _dispatch_eval_batch(n_jobs) = ccall((:mrbf_dispatch_eval_batch, libmrbf), Int32, (Int64,), n_jobs) == 1
 # where `hip_eval_models_many` takes the one call: from the job count the table names on (measured, DESIGN.md section 18)
 _eval_batch_pays(n_jobs) = n_jobs >= ccall((:mrbf_dispatch_eval_batch_min_jobs, libmrbf), Int64, ())
+_dispatch_hessian_batch(n_jobs) = ccall((:mrbf_dispatch_hessian_batch, libmrbf), Int32, (Int64,), n_jobs) == 1
+# where `hip_get_hessians_many` takes the one call: from the job count the table names on (measured, DESIGN.md section 20)
+_hessian_batch_pays(n_jobs) = n_jobs >= ccall((:mrbf_dispatch_hessian_batch_min_jobs, libmrbf), Int64, ())
 _dispatch_round4_batch(n_starts, d) = ccall((:mrbf_dispatch_round4_batch, libmrbf), Int32, (Int64, Int32), n_starts, d) == 1
 _dispatch_round4(n0, d, deg, n_candidates) =
     ccall((:mrbf_dispatch_round4, libmrbf), Int32, (Int64, Int32, Int32, Int64), n0, d, deg, n_candidates) == 1
@@ -643,6 +657,44 @@ end
 "d x d Hessian of output `ℓ` at `x̂` with respect to the scaled site: the derivative of `get_gradient(mod, scal, x̂, ℓ)`."
 hip_get_hessian(mod::HipRbfModel, scal, x̂::Vec, ℓ::Integer) =
     hip_get_hessians_at_sites(mod, scal, reshape(Vector{Float64}(x̂), :, 1), [ℓ])[:, :, 1, 1]
+
+"""
+`hip_get_hessians_at_sites` for a batch of (model, site block) pairs -- the second derivative of every start's model at its own
+iterate -- in one device call (`mrbf_eval_hessian_batch`) where the decision table takes the job count
+(`mrbf_dispatch_hessian_batch`) and it reaches `mrbf_dispatch_hessian_batch_min_jobs`; otherwise, or when the library refuses the
+call (rc -2), the loop of `mrbf_eval_hessian`.  `Xs[i]` is d x m_i, one site per column; `rows`: `nothing` (all outputs), one vector
+of 1-based output indices for all pairs, or one entry (a vector or `nothing`) per pair; the models share one context.  Returns a
+vector of d x d x r x m_i arrays, for every pair bit for bit what `hip_get_hessians_at_sites(mods[i], scal, Xs[i], rows)` returns.
+"""
+function hip_get_hessians_many(mods::AbstractVector{HipRbfModel}, Xs::AbstractVector{Matrix{Float64}}, rows = nothing;
+                               min_jobs::Union{Nothing,Int} = nothing)
+    nj = length(mods)
+    one_for_all = isnothing(rows) || isempty(rows) || first(rows) isa Integer
+    rows_of(i) = one_for_all ? rows : rows[i]
+    loop() = [hip_get_hessians_at_sites(mods[i], nothing, Xs[i], rows_of(i)) for i in 1:nj]
+    nj == 0 && return loop()
+    ctx = mods[1].ctx
+    pays = min_jobs === nothing ? _hessian_batch_pays(nj) : nj >= min_jobs
+    (_dispatch_hessian_batch(nj) && pays && all(m -> m.ctx === ctx, mods)) || return loop()
+    rows0 = [isnothing(rows_of(i)) ? Int32[] : Int32[Int32(ℓ - 1) for ℓ in rows_of(i)] for i in 1:nj]
+    rs = [isnothing(rows_of(i)) ? Int(mods[i].num_outputs) : length(rows0[i]) for i in 1:nj]
+    Hs = [Array{Float64,4}(undef, mods[i].n_vars, mods[i].n_vars, rs[i], size(Xs[i], 2)) for i in 1:nj]
+    jobs = Vector{MrbfHessJob}(undef, nj)
+    info = Ref(MrbfHessBatchInfo(0.0f0, 0, 0, 0))
+    rc = GC.@preserve Xs rows0 Hs jobs begin
+        for i in 1:nj
+            m = rs[i] == 0 ? 0 : size(Xs[i], 2)          # an empty selection is not "all": nothing to ask the library for
+            jobs[i] = MrbfHessJob(mods[i].handle, m, m == 0 ? C_NULL : pointer(Xs[i]), isempty(rows0[i]) ? C_NULL : pointer(rows0[i]),
+                                  m == 0 ? C_NULL : pointer(Hs[i]), length(rows0[i]), 0, 0, 0)
+        end
+        _locked(ctx) do hctx
+            ccall((:mrbf_eval_hessian_batch, libmrbf), Int32, (Ptr{Cvoid}, Int64, Ptr{MrbfHessJob}, Ref{MrbfHessBatchInfo}), hctx, nj, jobs, info)
+        end
+    end
+    rc != 0 && _fallback_rc(21, rc) && return loop()           # the library refuses the batch: the single call per pair
+    _check(ctx, rc)
+    return Hs
+end
 
 # batched twins (m sites as the columns of X): one device sweep for all k outputs of all sites
 eval_models_at_sites(mod::HipRbfModel, scal, X::AbstractMatrix) = _mrbf_eval(mod, Matrix{Float64}(X))[1]

@@ -439,6 +439,71 @@ def eval_models_many(mods, Xs, want_values=True, want_jac=False, outs=None, ctx=
     return res
 
 
+def get_hessians_many(mods, Xs, rows=None, outs=None, ctx=None, stats=None, min_jobs=None, limit_bytes=None):
+    """`RbfModel.hessian_sites` for a batch of (model, site block) pairs -- the second derivative of every start's model at its own
+    iterate -- in ONE mrbf_eval_hessian_batch call where mrbf_dispatch_hessian_batch takes the job count and it reaches
+    mrbf_dispatch_hessian_batch_min_jobs (min_jobs: another threshold, for tests and measurements); otherwise, or when the call
+    returns -2, the loop over hessian_sites.  A model may appear several times.  Xs[i]: m_i x d, a NumPy array or a torch device
+    tensor (used in place; then outs[i], a device tensor, must be given).  rows: None (all outputs), one list of 0-based output
+    indices for all pairs, or one entry (a list or None) per pair.  limit_bytes: the limit of the chunk rule, for tests
+    (mrbf_eval_hessian_batch_limited).  Returns a list with, for every pair, bit for bit what `mods[i].hessian_sites(Xs[i], rows=...)`
+    returns, in its shape.  stats (optional dict) receives "path" ("batch" or "loop"), "jobs" (how many pairs the one call carried),
+    "single_inside", "chunks", "groups", "ms_total" and "nsplit" (per pair)."""
+    n = len(mods)
+    stats = stats if stats is not None else {}
+    outs = list(outs) if outs is not None else [None] * n
+    one_for_all = rows is None or len(rows) == 0 or not (rows[0] is None or hasattr(rows[0], "__len__"))
+    rows_l = [rows] * n if one_for_all else list(rows)
+    assert len(rows_l) == n and len(Xs) == n and len(outs) == n
+    if n == 0:
+        stats.update(path="loop", jobs=0, single_inside=0, chunks=0, groups=0, ms_total=0.0, nsplit=[])
+        return []
+    ctx = ctx or mods[0].ctx
+
+    def loop():
+        infos = [{} for _ in range(n)]
+        res = [mods[i].hessian_sites(Xs[i], rows=rows_l[i], out=outs[i], info=infos[i]) for i in range(n)]
+        stats.update(path="loop", jobs=0, single_inside=0, chunks=0, groups=0,
+                     ms_total=float(sum(info.get("ms_total", 0.0) for info in infos)), nsplit=[int(info.get("nsplit", 0)) for info in infos])
+        return res
+
+    lib = ctx.lib
+    floor = int(lib.mrbf_dispatch_hessian_batch_min_jobs()) if min_jobs is None else int(min_jobs)
+    if lib.mrbf_dispatch_hessian_batch(n) != _lib.DISPATCH_DEVICE or n < floor or any(m.ctx is not ctx for m in mods):
+        return loop()
+    jobs = (_lib.HessJob * n)()
+    keep = []
+    for i, mod in enumerate(mods):
+        X = Xs[i]
+        is_np = not hasattr(X, "data_ptr")
+        X = _lib.host_f64(X).reshape(-1, mod.d) if is_np else X.contiguous()
+        m = int(X.shape[0])
+        rows_a = None if rows_l[i] is None else np.ascontiguousarray(np.atleast_1d(rows_l[i]), dtype=np.int32)
+        r = mod.k if rows_a is None else int(rows_a.size)
+        out = outs[i]
+        empty = rows_a is not None and r == 0   # an empty selection is not "all": nothing to ask the library for
+        if out is None:
+            assert is_np, "pass outs for device tensors"
+            out = np.empty((m, r, mod.d, mod.d))
+        keep.append((X, rows_a, out))
+        J = jobs[i]
+        J.model, J.m = mod.model.value if hasattr(mod.model, "value") else mod.model, 0 if empty else m
+        live = m > 0 and not empty
+        J.X, J.hess_out = (_lib.as_ptr(a).value if live else None for a in (X, out))
+        J.rows, J.n_rows = (None, 0) if rows_a is None or empty else (_lib.as_ptr(rows_a).value, r)
+    bi = _lib.HessBatchInfo()
+    if limit_bytes is None:
+        rc = lib.mrbf_eval_hessian_batch(ctx.h, n, jobs, ctypes.byref(bi))
+    else:
+        rc = lib.mrbf_eval_hessian_batch_limited(ctx.h, n, jobs, ctypes.byref(bi), int(limit_bytes))
+    if rc != 0 and lib.mrbf_dispatch_after(_lib.ENTRY_HESSIAN_BATCH, rc) == 1:
+        return loop()
+    ctx.check(rc)
+    stats.update(path="batch", jobs=n, single_inside=int(bi.single_inside), chunks=int(bi.chunks), groups=int(bi.groups),
+                 ms_total=float(bi.ms_total), nsplit=[int(jobs[i].nsplit) for i in range(n)])
+    return [out for _, _, out in keep]
+
+
 init_model = update_model      # RbfModel.jl:738-741 delegates
 improve_model = update_model   # RbfModel.jl:770-776 delegates
 

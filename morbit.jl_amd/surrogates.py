@@ -98,11 +98,14 @@ def get_jacobian(sur, scal, x_hat, rows=None):
     return rm.get_jacobian(sur, scal, x_hat, rows)
 
 
+_NO_COMPOSITE_HESSIAN = "get_hessian: the second-order chain rule through a CompositeSurrogate's outer function is not provided"
+
+
 def get_hessian(sur, scal, x_hat, ell):
     """d x d Hessian of output `ell` of the surrogate with respect to the scaled site.  A RefSurrogate selects the row of its grouped
     model; the second-order chain rule through a CompositeSurrogate's outer function is not provided."""
     if isinstance(sur, CompositeSurrogate):
-        raise NotImplementedError("get_hessian: the second-order chain rule through a CompositeSurrogate's outer function is not provided")
+        raise NotImplementedError(_NO_COMPOSITE_HESSIAN)
     if isinstance(sur, RefSurrogate):
         return rm.get_hessian(sur.model, scal, x_hat, sur.output_indices[ell])
     return rm.get_hessian(sur, scal, x_hat, ell)
@@ -204,6 +207,42 @@ class SurrogateContainer:
                     out[:, offs[pos]:offs[pos + 1], :] = J[:, idx, :]
         return out
 
+    # ---- Hessians: one hessian_sites call per distinct inner model with the union of the rows its surrogates select
+    def _hess_needs(self, kind):
+        """(inner model, the rows its surrogates select: ascending, each once) per distinct inner model; a CompositeSurrogate is
+        refused as get_hessian refuses it"""
+        needs = []
+        for inner, members in self._grouped(kind):
+            rows = set()
+            for _, s in members:
+                if isinstance(s, CompositeSurrogate):
+                    raise NotImplementedError(_NO_COMPOSITE_HESSIAN)
+                rows.update(s.output_indices if isinstance(s, RefSurrogate) else range(inner.num_outputs))
+            needs.append((inner, sorted(int(r) for r in rows)))
+        return needs
+
+    def _hess_at_site(self, kind, scal, x_scaled):
+        if not self.lists[kind]:
+            return np.empty((0, len(x_scaled), len(x_scaled)), dtype=_MIN_PRECISION)
+        return self._hess_at_sites(kind, scal, np.asarray(x_scaled, dtype=np.float64)[None, :])[0]
+
+    def _hess_at_sites(self, kind, scal, X):
+        """m x (container rows) x d x d"""
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        return self._hess_assemble(kind, X, {id(inner): (rows, inner.hessian_sites(X, rows=rows)) for inner, rows in self._hess_needs(kind)})
+
+    def _hess_assemble(self, kind, X, sweeps):
+        """the container's rows from id(inner) -> (rows, m x len(rows) x d x d Hessians)"""
+        offs = self._layout(kind)
+        out = np.empty((X.shape[0], offs[-1], X.shape[1], X.shape[1]))
+        for inner, members in self._grouped(kind):
+            rows, H = sweeps[id(inner)]
+            at = {row: i for i, row in enumerate(rows)}
+            for pos, s in members:
+                idx = s.output_indices if isinstance(s, RefSurrogate) else list(range(inner.num_outputs))
+                out[:, offs[pos]:offs[pos + 1]] = H[:, [at[int(i)] for i in idx]]
+        return out
+
     def _optim_handles(self, kind, scal):
         return [_get_optim_handle(s, scal, l) for s in self.lists[kind] for l in range(s.num_outputs)]
 
@@ -276,6 +315,19 @@ def eval_containers_jacobian_at_scaled_sites(scs, scal, Xs, kind, stats=None, mi
     return [sc._jac_assemble(kind, scal, Xs[p], sweeps[p]) for p, sc in enumerate(scs)]
 
 
+def eval_containers_hessians_at_scaled_sites(scs, scal, Xs, kind, stats=None, min_jobs=None):
+    """start p's result is what `scs[p]._hess_at_sites(kind, scal, Xs[p])` returns: the distinct inner models of ALL containers in one
+    rbf_model.get_hessians_many"""
+    Xs = [np.ascontiguousarray(X, dtype=np.float64) for X in Xs]
+    pairs = [(p, inner, rows) for p, sc in enumerate(scs) for inner, rows in sc._hess_needs(kind)]
+    res = rm.get_hessians_many([inner for _, inner, _ in pairs], [Xs[p] for p, _, _ in pairs], rows=[rows for _, _, rows in pairs],
+                               stats=stats, min_jobs=min_jobs)
+    sweeps = [{} for _ in scs]
+    for (p, inner, rows), H in zip(pairs, res):
+        sweeps[p][id(inner)] = (rows, H)
+    return [sc._hess_assemble(kind, Xs[p], sweeps[p]) for p, sc in enumerate(scs)]
+
+
 def _make(kind, plural):
     def at_site(sc, scal, x_scaled):
         return sc._eval_at_site(kind, scal, x_scaled)
@@ -288,6 +340,15 @@ def _make(kind, plural):
 
     def jac_at_sites(sc, scal, X):
         return sc._jac_at_sites(kind, scal, X)
+
+    def hess_at_site(sc, scal, x_scaled):
+        return sc._hess_at_site(kind, scal, x_scaled)
+
+    def hess_at_sites(sc, scal, X):
+        return sc._hess_at_sites(kind, scal, X)
+
+    def hess_at_sites_many(scs, scal, Xs, stats=None, min_jobs=None):
+        return eval_containers_hessians_at_scaled_sites(scs, scal, Xs, kind, stats=stats, min_jobs=min_jobs)
 
     def handles(sc, scal):
         return sc._optim_handles(kind, scal)
@@ -305,6 +366,9 @@ def _make(kind, plural):
     g["eval_container_%s_jacobian_at_scaled_site" % plural] = jac_at_site    # SurrogateContainer.jl:257-261
     g["eval_container_%s_at_scaled_sites" % plural] = at_sites               # batched twin
     g["eval_container_%s_jacobian_at_scaled_sites" % plural] = jac_at_sites  # batched twin
+    g["eval_container_%s_hessians_at_scaled_site" % plural] = hess_at_site             # second derivatives: no reference method
+    g["eval_container_%s_hessians_at_scaled_sites" % plural] = hess_at_sites           # batched twin
+    g["eval_container_%s_hessians_at_scaled_sites_many" % plural] = hess_at_sites_many  # many-start twin
     g["get_%s_optim_handles" % plural] = handles                             # SurrogateContainer.jl:248-255
 
 
