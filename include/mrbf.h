@@ -769,6 +769,46 @@ typedef struct {
 int32_t mrbf_sd_criticality(mrbf_ctx *ctx, const mrbf_ps_problem *problem, const double *x, const double *x_n, const double *lb,
                             const double *ub, int32_t normalize, double *d_out, double *dual_out, mrbf_sd_info *info);
 
+/* ---- directed search: its direction QP on the device (ds_qp.hip) ---------------------------------------------------------
+ * mrbf_ds_direction solves the direction problem of the reference's parked directed-search step (src/descent.jl:583-664) for n_qp
+ * QPs of one shape in one launch (one workgroup per QP, exact fp64 primal active-set method with minimum-norm steps; DESIGN.md
+ * section 21):
+ *   minimise 1/2 ||G d - r||_2^2 over d in [l, u] with l_j = max(-1, lb_j - x_j), u_j = min(1, ub_j - x_j) (mrbf_sd_direction's box),
+ *   G d <= 0 (descent.jl:635-639: only non-ascent directions);  1 <= d <= 4096, 1 <= k <= 16, n_qp >= 1.
+ * Per QP (consecutive blocks): G k x d in mrbf_eval's jac_out layout (k x d column-major: a Jacobian from mrbf_eval goes in as it
+ * is), r k (the target change of the model values: minus the direction of _get_global_dir, descent.jl:599-611), x / lb / ub d.
+ * Outputs: d_out (d, inside [l, u] exactly: a variable on a bound carries the bound's bits; not normalised), z_out (k): G d
+ * recomputed from the returned d, omega_out (1): max(0, -max_i z_i) (descent.jl:645), mult_out (k, may be NULL): the multipliers
+ * mu >= 0 of the rows G d <= 0 -- with y = z - r + mu and s = G' y the certificate is s_j = 0 on free variables, s_j >= 0 on the
+ * lower and <= 0 on the upper bound, mu_i z_i = 0 --, status_out (1): MRBF_DS_*, iters_out (2, may be NULL): iterations,
+ * constraints dropped.  CRITICAL (some r_i >= 0 or NaN, descent.jl:615-617): d = 0, z = 0, omega = 0.  INFEASIBLE (some l_j > u_j):
+ * d = 0, omega = -Inf.  GAVE_UP (the iteration cap 8 (d + k) + 16, a failed consistency check, or x outside [lb, ub] so that d = 0
+ * is no start): d = NaN, omega = NaN; the bindings take the host method.  z, omega and the optimal value are unique; d is not where
+ * the free columns of G have a null space: it is defined by the method, does not depend on the QP's position in the batch, and the
+ * same call gives the same bits.  Every array may be host or device memory.  Every QP gets a status; the call fails only on
+ * invalid arguments: -1 no context, -3 n_qp < 1, -4 d outside 1 .. 4096, -5 k outside 1 .. 16, -6 .. -10 NULL G, r, x, lb, ub,
+ * -11 .. -14 NULL d_out, z_out, omega_out, status_out; nothing is written then. */
+enum { MRBF_DS_OK = 0, MRBF_DS_CRITICAL = 1, MRBF_DS_INFEASIBLE = 2, MRBF_DS_GAVE_UP = 3 };
+int32_t mrbf_ds_direction(mrbf_ctx *ctx, int64_t n_qp, int32_t d, int32_t k, const double *G, const double *r, const double *x,
+                          const double *lb, const double *ub, double *d_out, double *z_out, double *omega_out, double *mult_out,
+                          int32_t *status_out, int32_t *iters_out);
+/* The criticality of directed search (src/descent.jl:583-664) for a container given as an mrbf_ps_problem (models, roles; no linear
+ * and no modelled constraints: the formulation the reference wrote down): the objective Jacobians at x_n through the evaluation
+ * kernels, gathered by the roles table, then ONE direction QP at x_n over the global bounds lb / ub (full_bounds_internal) and one
+ * read-back.  r (k): the target change of the model values.  d_out (d) and info->omega are, bit for bit, those of mrbf_ds_direction
+ * on the Jacobian mrbf_eval returns at x_n; mult_out (k, may be NULL).  Returns -2 (take the host method) when the decision table
+ * refuses the shape or the QP gave up (info->status = MRBF_DS_GAVE_UP); -1 no context, -3 .. -8 NULL problem, x_n, lb, ub, r,
+ * d_out, -10 NULL info. */
+typedef struct {
+    int32_t status;      /* MRBF_DS_* */
+    int32_t iterations;  /* active-set iterations */
+    int32_t dropped;     /* constraints dropped from the working set */
+    float ms_total;      /* hipEvent time of the whole call on the ctx stream */
+    double omega;        /* the criticality omega */
+} mrbf_ds_info;
+int32_t mrbf_ds_criticality(mrbf_ctx *ctx, const mrbf_ps_problem *problem, const double *x_n, const double *lb, const double *ub,
+                            const double *r, double *d_out, double *mult_out, mrbf_ds_info *info);
+
 /* ---- the normal step: its LP on the device (normal_lp.hip) ----------------------------------------------------------------
  * mrbf_normal_direction replaces the JuMP / OSQP model of compute_normal_step (src/descent.jl:691-757) for n_lp LPs of one shape
  * in one launch (one workgroup per LP, exact fp64 active-set dual simplex):
@@ -951,6 +991,9 @@ int32_t mrbf_ps_step_batch(mrbf_ctx *ctx, int64_t n_starts, const mrbf_ps_proble
  *                            1024 training sites (beyond that the ordinary fit is as fast and more accurate).
  *   mrbf_dispatch_sd         get_criticality(::SteepestDescentConfig, ...) (src/descent.jl:187-241): device iff no foreign
  *                            surrogate, at least one device model, 1 <= d <= 4096, k >= 1 and k + n_nl + n_lin <= 64 LP rows.
+ *   mrbf_dispatch_ds         the criticality of directed search (src/descent.jl:583-664, mrbf_ds_criticality): device iff no foreign
+ *                            surrogate, at least one device model, 1 <= d <= 4096, 1 <= k <= 16 and neither modelled nor linear
+ *                            constraints -- the formulation the reference wrote down; with constraint rows the host method runs.
  *   mrbf_dispatch_normal     compute_normal_step (src/descent.jl:691-757): device iff no modelled constraint row sits on a
  *                            foreign surrogate, 1 <= d <= 4096 and 1 <= n_nl + n_lin <= 64 LP rows (n_models may be 0).
  *   mrbf_dispatch_sd_step    compute_descent_step(::SteepestDescentConfig, ...) (src/descent.jl:243-318, _backtrack :150-185,
@@ -1009,11 +1052,13 @@ enum { MRBF_ENTRY_ROUND4 = 1, MRBF_ENTRY_FIT_FROM_ROUND4 = 2, MRBF_ENTRY_PS_STEP
        MRBF_ENTRY_SD = 6, MRBF_ENTRY_NORMAL = 7, MRBF_ENTRY_SD_STEP = 8, MRBF_ENTRY_SD_BATCH = 9, MRBF_ENTRY_AFFINE_BATCH = 10,
        MRBF_ENTRY_FIT_BATCH = 11, MRBF_ENTRY_NORMAL_BATCH = 12, MRBF_ENTRY_ROUND4_BATCH = 13, MRBF_ENTRY_PS_BATCH = 14,
        MRBF_ENTRY_DB_BOX = 15, MRBF_ENTRY_DB_GATHER = 16, MRBF_ENTRY_DB_ROUND3 = 17, MRBF_ENTRY_DB_APPEND_BATCH = 18,
-       MRBF_ENTRY_DB_SET_VALUES_BATCH = 19, MRBF_ENTRY_EVAL_BATCH = 20, MRBF_ENTRY_HESSIAN_BATCH = 21 };
+       MRBF_ENTRY_DB_SET_VALUES_BATCH = 19, MRBF_ENTRY_EVAL_BATCH = 20, MRBF_ENTRY_HESSIAN_BATCH = 21,
+       MRBF_ENTRY_DS = 22 };
 int32_t mrbf_dispatch_ps(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_ps_batch(int64_t n_starts, int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints,
                                int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_sd(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
+int32_t mrbf_dispatch_ds(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_normal(int32_t d, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_sd_step(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign,
                               int32_t max_loops);

@@ -99,10 +99,13 @@ ENTRY_DB_APPEND_BATCH = 18
 ENTRY_DB_SET_VALUES_BATCH = 19
 ENTRY_EVAL_BATCH = 20
 ENTRY_HESSIAN_BATCH = 21
+ENTRY_DS = 22
 R3_UPDATE, R3_IMPROVE = 0, 1
 R3_DONE, R3_REBUILT = 0, 1
 SD_OK, SD_NO_OBJECTIVE, SD_INFEASIBLE, SD_GAVE_UP = 0, 1, 2, 3
 NS_OK, NS_INFEASIBLE, NS_GAVE_UP = 0, 1, 2
+DS_OK, DS_CRITICAL, DS_INFEASIBLE, DS_GAVE_UP = 0, 1, 2, 3
+DS_MAXD, DS_MAXK = 4096, 16
 SD_BRANCH_DELTA, SD_BRANCH_ONE, SD_BRANCH_INTERSECT = 0, 1, 2
 
 
@@ -115,6 +118,15 @@ class PsProblem(ctypes.Structure):
 
 class SdInfo(ctypes.Structure):
     _fields_ = [("status", ctypes.c_int32), ("iterations", ctypes.c_int32), ("bound_flips", ctypes.c_int32), ("ms_total", ctypes.c_float),
+                ("omega", ctypes.c_double)]
+
+    def asdict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class DsInfo(ctypes.Structure):
+    """mrbf_ds_info: what mrbf_ds_criticality reports"""
+    _fields_ = [("status", ctypes.c_int32), ("iterations", ctypes.c_int32), ("dropped", ctypes.c_int32), ("ms_total", ctypes.c_float),
                 ("omega", ctypes.c_double)]
 
     def asdict(self):
@@ -330,6 +342,9 @@ SIGNATURES = {
                           + [ctypes.c_int32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mrbf_sd_criticality": (ctypes.c_int32, [c_vp, ctypes.POINTER(PsProblem), c_vp, c_vp, c_vp, c_vp, ctypes.c_int32, c_vp, c_vp,
                                              ctypes.POINTER(SdInfo)]),
+    "mrbf_ds_direction": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32] + [c_vp] * 11),
+    "mrbf_ds_criticality": (ctypes.c_int32, [c_vp, ctypes.POINTER(PsProblem), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(DsInfo)]),
+    "mrbf_dispatch_ds": (ctypes.c_int32, [ctypes.c_int32] * 6),
     "mrbf_normal_direction": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32] + [c_vp] * 12),
     "mrbf_normal_step": (ctypes.c_int32, [c_vp, ctypes.POINTER(PsProblem), ctypes.c_int32, c_vp, c_vp, c_vp, ctypes.c_double, ctypes.c_double,
                                           ctypes.c_double, ctypes.c_int32, c_vp, c_vp, ctypes.POINTER(NormalInfo)]),

@@ -70,6 +70,14 @@ int32_t mrbf_dispatch_sd(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_co
     return (int64_t)k + n_nl_constraints + n_lin_constraints <= 64 ? MRBF_DISPATCH_DEVICE : MRBF_DISPATCH_REFERENCE;
 }
 
+// the direction QP of directed search (ds_qp.hip): the k x k objects are factorised by one thread in LDS (k <= 16), d within the library's
+// limit; constraint rows are not on the device -- the reference's own formulation (descent.jl:635-640) has none
+int32_t mrbf_dispatch_ds(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign) {
+    if (n_foreign != 0 || n_models < 1) return MRBF_DISPATCH_REFERENCE;
+    if (d < 1 || d > 4096 || k < 1 || k > 16) return MRBF_DISPATCH_REFERENCE;
+    return n_nl_constraints == 0 && n_lin_constraints == 0 ? MRBF_DISPATCH_DEVICE : MRBF_DISPATCH_REFERENCE;
+}
+
 // the normal-step LP (normal_lp.hip): at most 64 rows (M^-1 lives in LDS), d within the library's limit; linear rows need no model
 int32_t mrbf_dispatch_normal(int32_t d, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign) {
     if (n_foreign != 0 || n_models < 0 || d < 1 || d > 4096 || n_nl_constraints < 0 || n_lin_constraints < 0) return MRBF_DISPATCH_REFERENCE;
@@ -229,6 +237,7 @@ int32_t mrbf_dispatch_after(int32_t entry, int32_t rc) {
         case MRBF_ENTRY_DB_SET_VALUES_BATCH: return rc == -2;
         case MRBF_ENTRY_EVAL_BATCH: return rc == -2;  // the table refuses the job count: mrbf_eval per job; a job's own status is an error
         case MRBF_ENTRY_HESSIAN_BATCH: return rc == -2;  // likewise: mrbf_eval_hessian per job; a job's own status is an error
+        case MRBF_ENTRY_DS: return rc == -2;  // shape outside the device path, or the QP gave up (MRBF_DS_GAVE_UP)
         default: return 0;
     }
 }

@@ -6,11 +6,14 @@ _steepest_descent_direction (:91-135, HiGHS on the host), get_criticality (:187-
 compute_descent_step (:243-320) with intersect_box / _intersect_bounds (utilities.jl:126-287).  The reference evaluates the <= max_loops
 step sizes one after another; here all of them go to the device in one batch (mrbf_backtrack when the
 objectives are one grouped RbfModel, else one batched container sweep) and the same loop logic picks
-the step, so the returned (x_plus, mx_plus, step) are those of the sequential loop.
+the step, so the returned (x_plus, mx_plus, step) are those of the sequential loop.  Directed search (:583-664, parked in the
+reference): DirectedSearchConfig, the direction QP's host method (_directed_search_direction: the active-set method of ds_qp.hip in
+NumPy), get_criticality_ds (routed to mrbf_ds_criticality) and compute_descent_step_ds (the steepest-descent step on its direction).
 """
 import ctypes
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, field
+from typing import Sequence
 
 import numpy as np
 
@@ -753,3 +756,453 @@ def normal_steps_many(containers, scal, X, deltas, lb, ub, lin=None, kappa_delta
         if not lib.mrbf_dispatch_after(_lib.ENTRY_NORMAL_BATCH, rc):
             (p0["models"][0].ctx if p0["models"] else _lib.default_context()).check(rc)
     return [single(p) for p in range(ns)]
+
+
+# ---- directed search (descent.jl:583-664): the direction QP, its host method, the device calls, the routing -------------------------
+# The constants of the active-set method, shared in value with ds_qp.hip:
+DS_RANK_TOL = 1e-12     # a row of M = G_N G_N' whose residual diagonal falls to DS_RANK_TOL M_ii depends on the rows pivoted before it
+DS_VANISH_TOL = 1e-13   # a step with |dz_i| <= DS_VANISH_TOL (sum_j |G_ij| + |r_i|) in every row has vanished
+DS_DUAL_TOL = 1e-11     # a multiplier violates its sign beyond DS_DUAL_TOL times the magnitudes it was formed from
+DS_FEAS_TOL = 1e-13     # sd_lp.hip's FEAS_TOL: rows g_i . d <= DS_FEAS_TOL sum_j |G_ij|
+
+
+@dataclass
+class DirectedSearchConfig:
+    """the configuration of the parked `compute_descent_step(::Val{:ds}, ...)` (descent.jl:583-664): the reference fields of
+    PascolettiSerafiniConfig that choose the image direction (descent.jl:599-611) and the backtracking fields of
+    SteepestDescentConfig for the step that follows"""
+    reference_point: Sequence[float] = field(default_factory=list)
+    reference_direction: Sequence[float] = field(default_factory=list)
+    max_ideal_point_problem_evals: int = -1
+    reference_algo: str = "GN_ISRES"
+    reference_trust_region_factor: float = 1.1
+    strict_backtracking: bool = True
+    armijo_const_rhs: float = 1e-6
+    armijo_const_shrink: float = 0.75
+    min_stepsize: float = 10 * np.finfo(np.float64).eps
+    max_loops: int = None
+    normalize: bool = True
+
+    def __post_init__(self):
+        assert all(v > 0 for v in self.reference_direction), "The components of the `reference_direction` cannot be negative."
+        if self.max_loops is None:  # descent.jl:61-66
+            base = self.min_stepsize if self.min_stepsize > 0 else np.finfo(np.float64).eps
+            self.max_loops = int(math.floor(math.log(base) / math.log(self.armijo_const_shrink)))
+        assert self.armijo_const_rhs > 0
+
+
+def _ds_factor(M, in_s):
+    """Cholesky of M with pivots taken from the row set S first (largest residual diagonal, lowest index on ties), then from the other
+    rows; a row whose residual diagonal is within DS_RANK_TOL M_ii is left out (it depends on the pivoted rows).  A row of S that is
+    left out leaves S (in place): the working set stays independent, and the row moves with the pivoted rows of S anyway.  Returns
+    (piv, n_s, L): the pivot rows in order, how many of them lie in S, and L (k x rank) with M[piv, piv] = L[piv] L[piv]'."""
+    k = M.shape[0]
+    dg = np.diag(M).copy()
+    tol = DS_RANK_TOL * np.diag(M)
+    L = np.zeros((k, k))
+    piv, done, n_s = [], np.zeros(k, dtype=bool), 0
+    for phase in (True, False):
+        while True:
+            best, bv = -1, 0.0
+            for i in range(k):
+                if not done[i] and bool(in_s[i]) == phase and dg[i] > tol[i] and dg[i] > bv:
+                    best, bv = i, dg[i]
+            if best < 0:
+                break
+            c = len(piv)
+            L[best, c] = math.sqrt(dg[best])
+            done[best] = True
+            piv.append(best)
+            for i in range(k):
+                if done[i]:
+                    continue
+                acc = M[i, best]
+                for q in range(c):
+                    acc -= L[i, q] * L[best, q]
+                L[i, c] = acc / L[best, c]
+                dg[i] -= L[i, c] * L[i, c]
+        if phase:
+            n_s = len(piv)
+            for i in range(k):
+                in_s[i] = bool(done[i])
+    return piv, n_s, L
+
+
+def _ds_step_coeffs(M, in_s, z, rho):
+    """a (k) with the minimum-norm step p_N = G_N' a: dz = M a has dz_S = -z_S (the rows of S stay on zero) and is nearest to rho on
+    the other rows.  Returns (a, factor) or (None, factor) where the small normal equations break down."""
+    k = M.shape[0]
+    piv, n_s, L = fac = _ds_factor(M, in_s)
+    rank = len(piv)
+    c = np.zeros(rank)
+    for a in range(n_s):
+        p = piv[a]
+        acc = -z[p]
+        for q in range(a):
+            acc -= L[p, q] * c[q]
+        c[a] = acc / L[p, a]
+    r2 = rank - n_s
+    T = [i for i in range(k) if not in_s[i]]
+    if r2:
+        t = np.zeros(k)
+        for i in T:
+            acc = rho[i]
+            for q in range(n_s):
+                acc -= L[i, q] * c[q]
+            t[i] = acc
+        if len(T) == r2:      # every other row pivoted: a triangular solve in pivot order
+            for b in range(r2):
+                p = piv[n_s + b]
+                acc = t[p]
+                for q in range(b):
+                    acc -= L[p, n_s + q] * c[n_s + q]
+                c[n_s + b] = acc / L[p, n_s + b]
+        else:                 # least squares over all other rows: normal equations of the r2 columns, Cholesky
+            A = np.zeros((r2, r2))
+            bv = np.zeros(r2)
+            for a in range(r2):
+                for b in range(a + 1):
+                    acc = 0.0
+                    for i in T:
+                        acc += L[i, n_s + a] * L[i, n_s + b]
+                    A[a, b] = acc
+                acc = 0.0
+                for i in T:
+                    acc += L[i, n_s + a] * t[i]
+                bv[a] = acc
+            for a in range(r2):
+                for b in range(a + 1):
+                    acc = A[a, b]
+                    for q in range(b):
+                        acc -= A[a, q] * A[b, q]
+                    if a == b:
+                        if not acc > 0.0:
+                            return None, fac
+                        A[a, a] = math.sqrt(acc)
+                    else:
+                        A[a, b] = acc / A[b, b]
+            for a in range(r2):
+                acc = bv[a]
+                for q in range(a):
+                    acc -= A[a, q] * bv[q]
+                bv[a] = acc / A[a, a]
+            for a in range(r2 - 1, -1, -1):
+                acc = bv[a]
+                for q in range(a + 1, r2):
+                    acc -= A[q, a] * bv[q]
+                bv[a] = acc / A[a, a]
+            c[n_s:] = bv
+    av = np.zeros(k)
+    for a in range(rank - 1, -1, -1):
+        acc = c[a]
+        for q in range(a + 1, rank):
+            acc -= L[piv[q], a] * av[piv[q]]
+        av[piv[a]] = acc / L[piv[a], a]
+    return av, fac
+
+
+def _ds_multipliers(M, fac, rho):
+    """mu (k): M_PP mu_P = (M rho)_P on the pivoted rows P of S, zero elsewhere -- the multipliers of the rows held at zero"""
+    piv, n_s, L = fac
+    k = M.shape[0]
+    mu = np.zeros(k)
+    w = np.zeros(n_s)
+    for a in range(n_s):
+        p = piv[a]
+        acc = 0.0
+        for i in range(k):
+            acc += M[p, i] * rho[i]
+        for q in range(a):
+            acc -= L[p, q] * w[q]
+        w[a] = acc / L[p, a]
+    for a in range(n_s - 1, -1, -1):
+        acc = w[a]
+        for q in range(a + 1, n_s):
+            acc -= L[piv[q], a] * mu[piv[q]]
+        mu[piv[a]] = acc / L[piv[a], a]
+    return mu
+
+
+def _ds_active_set(G, r, lo, hi, stats=None):
+    """The direction QP of directed search, min 1/2 ||G d - r||^2 over lo <= d <= hi, G d <= 0 (descent.jl:635-640), by the primal
+    active-set method with minimum-norm steps that ds_qp.hip runs: d starts at 0 with an empty row set S; a
+    step is p_N = G_N' a on the free variables N, found from the k x k matrix M = G_N G_N' alone; the ratio test adds the bounds and
+    rows that block; where the step vanishes the most violating multiplier is dropped.  After a step of length zero (a degenerate
+    point: more constraints meet than the working set holds) the least index decides instead, rows before variables, for the one
+    constraint that is added and for the one that is dropped (Bland's rule), until a step moves again.  Returns (d, z, omega, mu,
+    status)."""
+    G = np.asarray(G, dtype=np.float64)
+    k, n = G.shape
+    r = np.asarray(r, dtype=np.float64)
+    nan_d = (np.full(n, np.nan), np.full(k, np.nan), np.nan, np.full(k, np.nan), _lib.DS_GAVE_UP)
+
+    def gave_up(why):
+        if stats is not None:
+            stats["gave_up"] = why
+        return nan_d
+
+    if not np.all(r < 0):     # some r_i >= 0, or a NaN (descent.jl:615-617)
+        return np.zeros(n), np.zeros(k), 0.0, np.zeros(k), _lib.DS_CRITICAL
+    if not np.all(lo <= hi):
+        return np.zeros(n), np.zeros(k), -np.inf, np.zeros(k), _lib.DS_INFEASIBLE
+    if not (np.all(lo <= 0.0) and np.all(hi >= 0.0)):
+        return gave_up("start")   # the start d = 0 is outside the box: x is outside [lb, ub] by less than one
+    absG = np.abs(G)
+    rowsum = absG.sum(axis=1)
+    rscale = rowsum + np.abs(r)
+    d = np.zeros(n)
+    flag = np.where(lo == hi, 2, np.where(lo == 0.0, -1, np.where(hi == 0.0, 1, 0)))
+    in_s = np.zeros(k, dtype=bool)
+    degen = False
+    free = flag == 0
+    M = G[:, free] @ G[:, free].T
+    cap = 8 * (n + k) + 16
+    iters = dropped = full = 0
+    mu = np.zeros(k)
+    while True:
+        if iters >= cap:
+            return gave_up("cap")
+        iters += 1
+        z = G @ d
+        rho = r - z
+        av, fac = _ds_step_coeffs(M, in_s, z, rho)
+        if av is None:
+            return gave_up("normal equations")
+        free = flag == 0
+        p = np.where(free, G.T @ av, 0.0)
+        dz = G @ p
+        if full >= 2 or np.all(np.abs(dz) <= DS_VANISH_TOL * rscale):
+            mu = _ds_multipliers(M, fac, rho)
+            y = mu - rho
+            s = G.T @ y
+            sscale = absG.T @ (np.abs(r) + np.abs(z) + np.abs(mu))
+            mscale = float(np.max(np.abs(r) + np.abs(z)))
+            best, kind, idx = 0.0, 0, -1
+            for i in range(k):
+                v = -mu[i] / mscale if in_s[i] else 0.0
+                if v > DS_DUAL_TOL and v > best and not (degen and kind):
+                    best, kind, idx = v, 1, i
+            viol = np.where(flag == -1, -s, np.where(flag == 1, s, 0.0))
+            with np.errstate(divide="ignore", invalid="ignore"):
+                ratio = np.where(sscale > 0, viol / sscale, 0.0)
+            if degen:             # the least index that violates; a row goes first
+                cand = np.flatnonzero(ratio > DS_DUAL_TOL)
+                j = int(cand[0]) if cand.size and not kind else -1
+            else:
+                j = int(np.argmax(ratio)) if n else -1
+            if j >= 0 and ratio[j] > DS_DUAL_TOL and (degen or ratio[j] > best):
+                best, kind, idx = float(ratio[j]), 2, j
+            if kind == 0:
+                break
+            dropped += 1
+            full = 0
+            if kind == 1:
+                in_s[idx] = False
+            else:
+                flag[idx] = 0
+                fr = flag == 0
+                M = G[:, fr] @ G[:, fr].T
+            continue
+        # ---- ratio test over the free variables' bounds and the rows outside S
+        with np.errstate(divide="ignore", invalid="ignore"):
+            av_j = np.where(free & (p < 0), (lo - d) / p, np.where(free & (p > 0), (hi - d) / p, np.inf))
+        av_j = np.where(av_j < 0, 0.0, av_j)
+        alpha = 1.0
+        if n:
+            alpha = min(alpha, float(av_j.min()))
+        ar = np.full(k, np.inf)
+        for i in range(k):
+            if not in_s[i] and dz[i] > DS_VANISH_TOL * rscale[i]:
+                ar[i] = max(0.0, -z[i] / dz[i])
+        alpha = min(alpha, float(ar.min()))
+        hit = free & (av_j <= alpha)
+        rows_hit = ar <= alpha
+        degen = not alpha > 0.0
+        if degen:                 # a step of length zero adds one constraint: the least index that blocks, a row first
+            first_row = np.flatnonzero(rows_hit)
+            rows_hit = np.zeros(k, dtype=bool)
+            if first_row.size:
+                rows_hit[first_row[0]] = True
+                hit = np.zeros(n, dtype=bool)
+            else:
+                first = int(np.argmax(hit))
+                hit = np.zeros(n, dtype=bool)
+                hit[first] = True
+        d = np.where(free, np.minimum(np.maximum(d + alpha * p, lo), hi), d)
+        d = np.where(hit, np.where(p < 0, lo, hi), d)
+        flag = np.where(hit, np.where(p < 0, -1, 1), flag)
+        in_s |= rows_hit
+        nh = int(hit.sum())
+        full = full + 1 if (nh == 0 and not rows_hit.any()) else 0
+        if nh >= 1:           # M from G whenever N changes: a rank-one downdate would cancel against the columns that have left
+            fr = flag == 0
+            M = G[:, fr] @ G[:, fr].T
+    z = G @ d
+    if not np.all(z <= DS_FEAS_TOL * rowsum):
+        return gave_up("rows")
+    if stats is not None:
+        stats["iterations"], stats["dropped"] = iters, dropped
+    return d, z, max(0.0, -float(np.max(z))), mu, _lib.DS_OK
+
+
+def _ds_slsqp(G, r, lo, hi, A_eq, b_eq, A_in, b_in):
+    """the same QP, extended by rows A_eq d = b_eq and A_in d <= b_in, with SciPy's SLSQP from d = 0; None where it fails"""
+    from scipy.optimize import minimize
+
+    n = G.shape[1]
+    cons = [{"type": "ineq", "fun": lambda v: -(G @ v), "jac": lambda v: -G}]
+    if b_eq.size:
+        cons.append({"type": "eq", "fun": lambda v: A_eq @ v - b_eq, "jac": lambda v: A_eq})
+    if b_in.size:
+        cons.append({"type": "ineq", "fun": lambda v: b_in - A_in @ v, "jac": lambda v: -A_in})
+    res = minimize(lambda v: 0.5 * float(np.sum((G @ v - r) ** 2)), np.zeros(n), jac=lambda v: G.T @ (G @ v - r),
+                   bounds=list(zip(lo, hi)), constraints=cons, method="SLSQP", options={"ftol": 1e-15, "maxiter": 1000})
+    # status 8 ("positive directional derivative for linesearch") is SLSQP's usual end at a tight ftol: the point is judged by its rows
+    if res.status not in (0, 8) or not np.all(np.isfinite(res.x)):
+        return None
+    d = np.clip(res.x, lo, hi)
+    tol = 1e-9
+    ok = np.all(G @ d <= tol * (1.0 + np.abs(G).sum(axis=1)))
+    if b_eq.size:
+        ok = ok and np.all(np.abs(A_eq @ d - b_eq) <= tol * (1.0 + np.abs(b_eq) + np.abs(A_eq).sum(axis=1)))
+    if b_in.size:
+        ok = ok and np.all(A_in @ d - b_in <= tol * (1.0 + np.abs(b_in) + np.abs(A_in).sum(axis=1)))
+    return d if ok else None
+
+
+def _directed_search_direction(x, G, r, lb, ub, A_eq=None, b_eq=None, A_ineq=None, b_ineq=None, stats=None):
+    """The host method of the directed-search direction (descent.jl:598-645): min 1/2 ||G d - r||^2 over the box of `_sd_box`,
+    G d <= 0.  Without further rows it runs the device kernel's active-set method in NumPy (`_ds_active_set`); with rows
+    A_eq d = b_eq, A_ineq d <= b_ineq (those of `_sd_host_rows`) -- and where the active-set method gives up -- SciPy's SLSQP solves the
+    extended QP.  Returns (d, z = G d, omega = max(0, -max z), mu, status MRBF_DS_*): mu are the multipliers of G d <= 0 from the
+    active-set method, NaN from SLSQP; CRITICAL and INFEASIBLE as mrbf_ds_direction answers them.  stats["method"]: which one ran."""
+    x = np.asarray(x, dtype=np.float64)
+    n = x.size
+    G = np.asarray(G, dtype=np.float64).reshape(-1, n)
+    k = G.shape[0]
+    r = np.asarray(r, dtype=np.float64).ravel()
+    lo, hi = _sd_box(x, lb, ub)
+    A_eq = np.zeros((0, n)) if b_eq is None or np.asarray(b_eq).size == 0 else np.asarray(A_eq, dtype=np.float64).reshape(-1, n)
+    b_eq = np.zeros(0) if b_eq is None else np.asarray(b_eq, dtype=np.float64).ravel()
+    A_in = np.zeros((0, n)) if b_ineq is None or np.asarray(b_ineq).size == 0 else np.asarray(A_ineq, dtype=np.float64).reshape(-1, n)
+    b_in = np.zeros(0) if b_ineq is None else np.asarray(b_ineq, dtype=np.float64).ravel()
+    if not (b_eq.size or b_in.size):
+        out = _ds_active_set(G, r, lo, hi, stats)
+        if stats is not None:
+            stats["method"] = "active_set"
+        if out[4] != _lib.DS_GAVE_UP:
+            return out
+    elif not np.all(r < 0):
+        return np.zeros(n), np.zeros(k), 0.0, np.zeros(k), _lib.DS_CRITICAL
+    elif not np.all(lo <= hi):
+        return np.zeros(n), np.zeros(k), -np.inf, np.zeros(k), _lib.DS_INFEASIBLE
+    if stats is not None:
+        stats["method"] = "slsqp"
+    d = _ds_slsqp(G, r, lo, hi, A_eq, b_eq, A_in, b_in)
+    if d is None:
+        return np.full(n, np.nan), np.full(k, np.nan), np.nan, np.full(k, np.nan), _lib.DS_GAVE_UP
+    z = G @ d
+    return d, z, max(0.0, -float(np.max(z))), np.full(k, np.nan), _lib.DS_OK
+
+
+def ds_directions_many(G, r, X, lb, ub, ctx=None, want_mult=True):
+    """one mrbf_ds_direction call for a batch of starts: G (n_qp x k x d, the starts' objective Jacobians), r (n_qp x k), X (n_qp x d),
+    lb / ub (d, or n_qp x d).  Returns (rc, d (n_qp x d), z (n_qp x k), omega (n_qp), mu (n_qp x k) or None, status (n_qp),
+    iters (n_qp x 2: iterations, constraints dropped))."""
+    ctx = ctx or _lib.default_context()
+    G = np.asarray(G, dtype=np.float64)
+    nq, k, n = G.shape
+    Gl = np.ascontiguousarray(np.transpose(G, (0, 2, 1)))      # mrbf_eval's jac_out layout: k x d column-major per start
+    r = np.ascontiguousarray(np.asarray(r, dtype=np.float64).reshape(nq, k))
+    X = np.ascontiguousarray(np.asarray(X, dtype=np.float64).reshape(nq, n))
+    lb = np.ascontiguousarray(np.broadcast_to(np.asarray(lb, dtype=np.float64), (nq, n)))
+    ub = np.ascontiguousarray(np.broadcast_to(np.asarray(ub, dtype=np.float64), (nq, n)))
+    d, z, om = np.empty((nq, n)), np.empty((nq, k)), np.empty(nq)
+    mu = np.empty((nq, k)) if want_mult else None
+    status, iters = np.empty(nq, dtype=np.int32), np.empty((nq, 2), dtype=np.int32)
+    rc = ctx.lib.mrbf_ds_direction(ctx.h, nq, n, k, _lib.as_ptr(Gl), _lib.as_ptr(r), _lib.as_ptr(X), _lib.as_ptr(lb), _lib.as_ptr(ub),
+                                   _lib.as_ptr(d), _lib.as_ptr(z), _lib.as_ptr(om), _lib.as_ptr(mu), _lib.as_ptr(status), _lib.as_ptr(iters))
+    return rc, d, z, om, mu, status, iters
+
+
+def ds_criticality_device(plan, x_n, lb, ub, r, want_mult=False):
+    """one mrbf_ds_criticality call; returns (rc, omega, d, info dict[, multipliers])"""
+    ctx = plan["models"][0].ctx
+    x_n = np.ascontiguousarray(x_n, dtype=np.float64)
+    lb, ub = np.ascontiguousarray(lb, dtype=np.float64), np.ascontiguousarray(ub, dtype=np.float64)
+    r = np.ascontiguousarray(r, dtype=np.float64)
+    prob, keep = _sd_problem(plan, (None,) * 4)
+    d = np.empty(x_n.size)
+    mu = np.empty(plan["k"]) if want_mult else None
+    info = _lib.DsInfo()
+    rc = ctx.lib.mrbf_ds_criticality(ctx.h, ctypes.byref(prob), _lib.as_ptr(x_n), _lib.as_ptr(lb), _lib.as_ptr(ub), _lib.as_ptr(r),
+                                     _lib.as_ptr(d), _lib.as_ptr(mu), ctypes.byref(info))
+    out = (rc, float(info.omega), d, info.asdict())
+    return out + (mu,) if want_mult else out
+
+
+def _ds_image_direction(cfg, sc, scal, x, x_n, fx_n, delta, lb, ub, rng, stats):
+    """r of descent.jl:599-611, the target change of the model values: minus the reference direction, or the reference point minus
+    f(x_n), or the local ideal point (descent.jl:404-412, over the trust region stretched by reference_trust_region_factor) minus f(x_n)"""
+    from . import pascoletti_serafini as ps
+
+    fx_n = np.asarray(fx_n, dtype=np.float64)
+    g = ps._get_global_dir(cfg, fx_n)
+    if g is not None:
+        return -g
+    n = int(np.asarray(x_n).size)
+    lb_eff, ub_eff = _local_bounds(x, cfg.reference_trust_region_factor * delta, lb, ub)
+    max_evals = 500 * (n + 1) if cfg.max_ideal_point_problem_evals < 0 else cfg.max_ideal_point_problem_evals
+    rng = np.random.default_rng(0) if rng is None else rng
+    ideal = ps.compute_local_ideal_point(np.asarray(x_n, dtype=np.float64), lb_eff, ub_eff,
+                                         lambda X: sg.eval_container_objectives_at_scaled_sites(sc, scal, X), fx_n.size, max_evals, rng,
+                                         stats=stats)
+    return ideal - fx_n
+
+
+def get_criticality_ds(cfg, sc, scal, x, x_n, fx_n, delta, lb, ub, lin=None, stats=None, rng=None):
+    """The criticality of directed search (descent.jl:583-660 up to the backtracking) as HipRbf.jl's `hip_get_criticality_ds` routes it:
+    the image direction r from the configuration (`_get_global_dir` / `compute_local_ideal_point`), then mrbf_dispatch_ds decides,
+    mrbf_ds_criticality solves the direction QP on the device, and where the decision table or mrbf_dispatch_after say so the host
+    method runs (`_directed_search_direction` on container Jacobians, with the rows of `_sd_host_rows` where the container or the
+    problem has constraints).  lb / ub: the global bounds in scaled variables; lin = (A_eq, b_eq, A_ineq, b_ineq) in scaled variables.
+    Never raises on a size limit.  Returns (omega, d / ||d||_inf), or (0, zeros) when critical or ||d||_inf = 0 (descent.jl:647-660);
+    stats["path"] is "device" or "reference"."""
+    lib = _lib.load()
+    plan = sg.container_plan(sc)
+    x_n = np.asarray(x_n, dtype=np.float64)
+    n = int(x_n.size)
+    lin = lin or (None,) * 4
+    n_lin = sum(0 if b is None else int(np.asarray(b).size) for b in (lin[1], lin[3]))
+    r = _ds_image_direction(cfg, sc, scal, x, x_n, fx_n, delta, lb, ub, rng, stats)
+
+    def result(omega, d, status):
+        nrm = float(np.max(np.abs(d))) if status == _lib.DS_OK and d.size else 0.0
+        if status != _lib.DS_OK or not nrm > 0:
+            return 0.0, np.zeros(n)
+        return float(omega), d / nrm
+
+    if lib.mrbf_dispatch_ds(n, plan["k"], len(plan["models"]), plan["n_con"], n_lin, plan["n_foreign"]) == _lib.DISPATCH_DEVICE:
+        rc, omega, d, info = ds_criticality_device(plan, x_n, lb, ub, r)
+        if stats is not None:
+            stats.update(info)
+            stats["path"] = "device"
+        if rc == 0:
+            return result(omega, d, info["status"])
+        if not lib.mrbf_dispatch_after(_lib.ENTRY_DS, rc):
+            plan["models"][0].ctx.check(rc)
+    if stats is not None:
+        stats["path"] = "reference"
+    if n_lin or plan["n_con"]:
+        G, A_eq, b_eq, A_in, b_in = _sd_host_rows(sc, scal, x, x_n, lin)
+    else:
+        G, A_eq, b_eq, A_in, b_in = sg.eval_container_objectives_jacobian_at_scaled_site(sc, scal, x_n), None, None, None, None
+    d, _, omega, _, status = _directed_search_direction(x_n, G, r, lb, ub, A_eq, b_eq, A_in, b_in, stats)
+    return result(omega, d, status)
+
+
+def compute_descent_step_ds(cfg, sc, scal, x, x_n, delta, lb, ub, omega, d, lin=None, stats=None):
+    """the step of directed search (descent.jl:645-660): what the parked code does with its direction is `_intersect_bounds` and the
+    Armijo sweep -- `compute_descent_step_sd_routed` on (omega, d) of `get_criticality_ds`, no step code of its own.  Returns
+    (omega, x_plus, mx_plus, ||step||_inf)."""
+    return compute_descent_step_sd_routed(cfg, sc, scal, x, x_n, delta, lb, ub, omega, d, lin, stats)

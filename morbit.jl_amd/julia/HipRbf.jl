@@ -47,6 +47,11 @@ struct MrbfSdInfo          # mirrors mrbf_sd_info, 24 bytes
     omega::Float64
 end
 
+struct MrbfDsInfo          # mirrors mrbf_ds_info, 24 bytes
+    status::Int32; iterations::Int32; dropped::Int32; ms_total::Float32
+    omega::Float64
+end
+
 struct MrbfNormalInfo      # mirrors mrbf_normal_info, 32 bytes
     status::Int32; iterations::Int32; bound_flips::Int32; ms_total::Float32
     alpha::Float64; delta::Float64
@@ -291,6 +296,8 @@ _dispatch_ps_batch(n_starts, d, k, n_models, n_nl, n_lin, n_foreign) =
           n_starts, d, k, n_models, n_nl, n_lin, n_foreign) == 1
 _dispatch_sd(d, k, n_models, n_nl, n_lin, n_foreign) =
     ccall((:mrbf_dispatch_sd, libmrbf), Int32, (Int32, Int32, Int32, Int32, Int32, Int32), d, k, n_models, n_nl, n_lin, n_foreign) == 1
+_dispatch_ds(d, k, n_models, n_nl, n_lin, n_foreign) =
+    ccall((:mrbf_dispatch_ds, libmrbf), Int32, (Int32, Int32, Int32, Int32, Int32, Int32), d, k, n_models, n_nl, n_lin, n_foreign) == 1
 _dispatch_normal(d, n_models, n_nl, n_lin, n_foreign) =
     ccall((:mrbf_dispatch_normal, libmrbf), Int32, (Int32, Int32, Int32, Int32, Int32), d, n_models, n_nl, n_lin, n_foreign) == 1
 _dispatch_sd_step(d, k, n_models, n_nl, n_lin, n_foreign, max_loops) =
@@ -999,6 +1006,162 @@ function get_criticality(desc_cfg::SteepestDescentConfig, mop, scal, x_it, x_it_
     _check(ctx, rc)
     Xet = eltype(get_x_scaled(x_it_n))
     return Xet(info[].omega), Xet.(dir)                        # NO_OBJECTIVE / INFEASIBLE: zeros and -Inf, as descent.jl:130-133
+end
+
+"""
+Directed search (descent.jl:583-664, parked in the reference behind "TODO Re-enable Directed Search").  The fields that choose the image
+direction are those of `PascolettiSerafiniConfig` (descent.jl:324-350), the backtracking fields those of `SteepestDescentConfig`
+(descent.jl:55-66): `hip_get_criticality_ds` gives (ω, d), `hip_compute_descent_step` -- typed on `SteepestDescentConfig`, which
+`_ds_step_config` makes of this one -- does the step.
+"""
+struct HipDirectedSearchConfig <: AbstractDescentConfig
+    reference_point::Vector{Float64}
+    reference_direction::Vector{Float64}
+    max_ideal_point_problem_evals::Int
+    reference_algo::Symbol
+    strict_backtracking::Bool
+    armijo_const_rhs::Float64
+    armijo_const_shrink::Float64
+    min_stepsize::Float64
+    max_loops::Int
+    normalize::Bool
+    function HipDirectedSearchConfig(; reference_point = Float64[], reference_direction = Float64[], max_ideal_point_problem_evals = -1,
+                                     reference_algo = :GN_ISRES, strict_backtracking = true, armijo_const_rhs = 1e-6,
+                                     armijo_const_shrink = 0.75, min_stepsize = 10 * eps(Float64),
+                                     max_loops = floor(Int, log(min_stepsize > 0 ? min_stepsize : eps(Float64)) / log(armijo_const_shrink)),
+                                     normalize = true)
+        @assert all(reference_direction .> 0) "The components of the `reference_direction` cannot be negative."
+        @assert armijo_const_rhs > 0
+        return new(reference_point, reference_direction, max_ideal_point_problem_evals, reference_algo, strict_backtracking,
+                   armijo_const_rhs, armijo_const_shrink, min_stepsize, max_loops, normalize)
+    end
+end
+_ds_step_config(cfg::HipDirectedSearchConfig) =
+    SteepestDescentConfig(; strict_backtracking = cfg.strict_backtracking, armijo_const_rhs = cfg.armijo_const_rhs,
+                          armijo_const_shrink = cfg.armijo_const_shrink, min_stepsize = cfg.min_stepsize, max_loops = cfg.max_loops,
+                          normalize = cfg.normalize)
+
+# r of descent.jl:599-611, the target change of the model values: minus the reference direction, or the reference point minus f(x_n),
+# or the local ideal point (descent.jl:404-412) minus f(x_n)
+function _ds_image_direction(cfg::HipDirectedSearchConfig, mop, scal, x_it, x_it_n, sc)
+    fx_n = Vector{Float64}(get_fx(x_it_n))
+    isempty(cfg.reference_direction) || return -Vector{Float64}(cfg.reference_direction)
+    isempty(cfg.reference_point) || return Vector{Float64}(cfg.reference_point) .- fx_n
+    n_vars = length(get_x_scaled(x_it_n))
+    max_evals = cfg.max_ideal_point_problem_evals < 0 ? 500 * (n_vars + 1) : cfg.max_ideal_point_problem_evals
+    objf_handles, eq_handles, ineq_handles = get_raw_optim_handles(mop, sc, scal)
+    lb_eff, ub_eff = local_bounds(scal, get_x_scaled(x_it), get_delta(x_it))
+    return compute_local_ideal_point(x_it_n, lb_eff, ub_eff, objf_handles, eq_handles, ineq_handles, max_evals, cfg.reference_algo) .- fx_n
+end
+
+# the parked body's own route (descent.jl:619-643): the pseudo-inverse without constraints, else its JuMP model, extended by the rows of
+# get_criticality(::SteepestDescentConfig, ...) where there are any -- the host method of this binding
+function _ds_reference_direction(mop, scal, x_it, x_it_n, sc, r)
+    x = get_x_scaled(x_it); x_n = get_x_scaled(x_it_n)
+    n_vars = length(x_n)
+    lb, ub = full_bounds_internal(scal)
+    Dm = eval_container_objectives_jacobian_at_scaled_site(sc, scal, x_n)
+    A_eq, b_eq = transformed_linear_eq_constraints(scal, mop)
+    A_in, b_in = transformed_linear_ineq_constraints(scal, mop)
+    dir_prob = JuMP.Model(LP_OPTIMIZER)
+    JuMP.set_silent(dir_prob)
+    JuMP.@variable(dir_prob, d[1:n_vars])
+    JuMP.@objective(dir_prob, Min, sum((Dm * d .- r) .^ 2))
+    JuMP.@constraint(dir_prob, -1.0 .<= d .<= 1.0)
+    JuMP.@constraint(dir_prob, Dm * d .<= 0)
+    JuMP.@constraint(dir_prob, lb .<= x_n .+ d .<= ub)
+    isempty(b_eq) || JuMP.@constraint(dir_prob, A_eq * (x_n .+ d) .== b_eq)
+    isempty(b_in) || JuMP.@constraint(dir_prob, A_in * (x_n .+ d) .<= b_in)
+    if num_nl_eq_constraints(mop) > 0
+        Dc = eval_container_nl_eq_constraints_jacobian_at_scaled_site(sc, scal, x)
+        JuMP.@constraint(dir_prob, eval_container_nl_eq_constraints_at_scaled_site(sc, scal, x_n) .+ Dc * (x_n .- x .+ d) .== 0)
+    end
+    if num_nl_ineq_constraints(mop) > 0
+        Dc = eval_container_nl_ineq_constraints_jacobian_at_scaled_site(sc, scal, x)
+        JuMP.@constraint(dir_prob, eval_container_nl_ineq_constraints_at_scaled_site(sc, scal, x_n) .+ Dc * (x_n .- x .+ d) .<= 0)
+    end
+    JuMP.optimize!(dir_prob)
+    dir = JuMP.value.(d)
+    return max(0.0, -maximum(Dm * dir)), dir
+end
+
+"""
+The criticality of directed search (descent.jl:583-660 up to the backtracking) on the device (`mrbf_ds_criticality`): the image direction
+r from the configuration, the objective Jacobians at x_n by the evaluation kernels, then the direction QP min ½‖∇m d − r‖², the box of
+the steepest-descent LP, ∇m d ≤ 0 (descent.jl:635-640), solved exactly by an active-set method instead of by JuMP + OSQP.  Whenever the
+decision table says so (`mrbf_dispatch_ds`: a `CompositeSurrogate` or another model family, more than 16 objectives, d > 4096, modelled
+or linear constraints) or the QP gave up, the parked body's own JuMP model runs on the same arguments.  Returns (ω, d / ‖d‖∞) in the
+iterate's float type, or (0, zeros) when critical or ‖d‖∞ = 0 (descent.jl:615-617, :647-660); `hip_compute_descent_step(
+_ds_step_config(cfg), ..., ω, d)` does the step.
+"""
+function hip_get_criticality_ds(desc_cfg::HipDirectedSearchConfig, mop, scal, x_it, x_it_n, data_base, sc::SurrogateContainer, algo_config)
+    x_n = Vector{Float64}(get_x_scaled(x_it_n))
+    Xet = eltype(get_x_scaled(x_it_n))
+    n = length(x_n)
+    r = Vector{Float64}(_ds_image_direction(desc_cfg, mop, scal, x_it, x_it_n, sc))
+    (any(r .>= 0) || any(isnan, r)) && return Xet(0), zeros(Xet, n)           # descent.jl:615-617
+    function result(ω, dir)
+        nrm = norm(dir, Inf)
+        (nrm > 0 && isfinite(nrm)) || return Xet(0), zeros(Xet, n)
+        return Xet(ω), Xet.(dir ./ nrm)
+    end
+    reference() = result(_ds_reference_direction(mop, scal, x_it, x_it_n, sc, r)...)
+    _touches_device(sc) || return reference()      # no HipRbfModel in the container: libmrbf is not touched
+    plan = _container_plan(sc)
+    k = plan.k
+    A_eq, b_eq = transformed_linear_eq_constraints(scal, mop)
+    A_in, b_in = transformed_linear_ineq_constraints(scal, mop)
+    _dispatch_ds(n, k, length(plan.models), plan.n_con, length(b_eq) + length(b_in), plan.n_foreign) || return reference()
+    lb_g, ub_g = full_bounds_internal(scal)
+    lb = Vector{Float64}(lb_g); ub = Vector{Float64}(ub_g)
+    info = Ref{MrbfDsInfo}()
+    dir = Vector{Float64}(undef, n)
+    handles = Ptr{Cvoid}[m.handle for m in plan.models]
+    roles = plan.roles
+    ctx = plan.models[1].ctx
+    rc = GC.@preserve handles roles x_n lb ub r dir begin
+        prob = Ref(MrbfPsProblem(length(handles), k, pointer(handles), pointer(roles), 0, 0, C_NULL, C_NULL, C_NULL, C_NULL, -1.0))
+        _locked(ctx) do hctx
+            ccall((:mrbf_ds_criticality, libmrbf), Int32,
+                  (Ptr{Cvoid}, Ref{MrbfPsProblem}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                   Ref{MrbfDsInfo}),
+                  hctx, prob, x_n, lb, ub, r, dir, C_NULL, info)
+        end
+    end
+    rc != 0 && _fallback_rc(22, rc) && return reference()      # the QP gave up: the JuMP model on the same arguments
+    _check(ctx, rc)
+    info[].status == 0 || return Xet(0), zeros(Xet, n)         # CRITICAL / INFEASIBLE: no direction
+    return result(info[].omega, dir)
+end
+
+"""
+The direction QPs of many starts in one device call (`mrbf_ds_direction`): `Gs[p]` (k × d) is start p's objective Jacobian at
+`X_n[:, p]`, `R[:, p]` its image direction; `lb` / `ub` the global bounds in scaled variables.  Returns (D (d × n), Z (k × n), ω (n),
+status (n)): for every start what `mrbf_ds_criticality` computes on that start alone, unnormalised; status 3 (gave up): take
+`hip_get_criticality_ds` for that start.
+"""
+function hip_ds_directions_many(ctx::MrbfContext, Gs::AbstractVector{<:AbstractMatrix}, R::AbstractMatrix, X_n::AbstractMatrix,
+                                lb::AbstractVector, ub::AbstractVector)
+    ns = length(Gs)
+    k, d = size(Gs[1])
+    G = Array{Float64}(undef, k, d, ns)                          # per start k x d column-major: mrbf_eval's jac_out layout
+    for p in 1:ns
+        G[:, :, p] .= Gs[p]
+    end
+    Rm = Matrix{Float64}(R); Xm = Matrix{Float64}(X_n)
+    LB = repeat(Vector{Float64}(lb), 1, ns); UB = repeat(Vector{Float64}(ub), 1, ns)
+    D = Matrix{Float64}(undef, d, ns); Z = Matrix{Float64}(undef, k, ns); ω = Vector{Float64}(undef, ns)
+    status = Vector{Int32}(undef, ns)
+    rc = GC.@preserve G Rm Xm LB UB D Z ω status begin
+        _locked(ctx) do hctx
+            ccall((:mrbf_ds_direction, libmrbf), Int32,
+                  (Ptr{Cvoid}, Int64, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                   Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}),
+                  hctx, ns, d, k, G, Rm, Xm, LB, UB, D, Z, ω, C_NULL, status, C_NULL)
+        end
+    end
+    _check(ctx, rc)
+    return D, Z, ω, status
 end
 
 """
