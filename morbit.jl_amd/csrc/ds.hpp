@@ -9,7 +9,7 @@
 namespace mrbf {
 namespace ds {
 
-// all device pointers; QPs in chunks so that the per-QP workspaces stay below WS_LIMIT_BYTES.  QP p reads x at x + p x_stride and its
+// all device pointers; QPs in chunks so that the per-QP workspaces stay below dcall::WS_LIMIT_BYTES.  QP p reads x at x + p x_stride and its
 // bounds at lb / ub + p bound_stride (0: one box for every QP); G (k x n column-major), r and the outputs lie in consecutive per-QP blocks.
 int launch(mrbf_ctx *ctx, int64_t n_qp, int n, int k, const double *G, const double *r, const double *x, int64_t x_stride, const double *lb,
            const double *ub, int64_t bound_stride, double *d_out, double *z_out, double *omega_out, double *mult_out, int *status_out,

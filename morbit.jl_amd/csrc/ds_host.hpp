@@ -1,7 +1,7 @@
 // Host logic of the directed-search direction QP (ds_qp.hip: mrbf_ds_direction, mrbf_ds_criticality), free of HIP so that
 // tools/ds_host_check.cpp drives it on the CPU under the sanitizers: the constants of the active-set method, the validation behind
-// mrbf_ds_direction's return codes, the per-QP workspace in the context arena, the rule that cuts a batch into launches, the iteration
-// cap, and the LDS carve -- one function that the launcher and the kernel both call.
+// mrbf_ds_direction's return codes, the per-QP workspace in the context arena (what dcall::chunk of descent_call_host.hpp cuts a batch
+// into launches by), the iteration cap, and the LDS carve -- one function that the launcher and the kernel both call.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -24,7 +24,6 @@ constexpr double RANK_TOL = 1e-12;    // a row of M = G_N G_N' whose residual di
 constexpr double VANISH_TOL = 1e-13;  // a step with |dz_i| <= VANISH_TOL (sum_j |G_ij| + |r_i|) in every row has vanished
 constexpr double DUAL_TOL = 1e-11;    // a multiplier violates its sign beyond DUAL_TOL times the magnitudes it was formed from
 constexpr double FEAS_TOL = 1e-13;    // sd_lp.hip's FEAS_TOL: the returned d has g_i . d <= FEAS_TOL sum_j |G_ij|
-constexpr size_t WS_LIMIT_BYTES = (size_t)256 << 20;  // the per-QP workspaces of one launch stay below this
 
 // what mrbf_ds_direction knows before anything is launched (a flag per pointer: given)
 struct Call {
@@ -63,12 +62,6 @@ constexpr int WS_DOUBLES_PER_VAR = 4;
 inline size_t ws_doubles(int d) { return (size_t)WS_DOUBLES_PER_VAR * (size_t)d; }
 inline size_t ws_ints(int d) { return (size_t)d; }
 inline size_t ws_bytes(int d) { return ws_doubles(d) * sizeof(double) + ws_ints(d) * sizeof(int32_t); }
-// QPs per launch: all of them, unless their workspaces would pass WS_LIMIT_BYTES; at least one
-inline int64_t chunk(int64_t n_qp, int d) {
-    int64_t fit = (int64_t)(WS_LIMIT_BYTES / ws_bytes(d));
-    if (fit < 1) fit = 1;
-    return n_qp < fit ? (n_qp < 1 ? 1 : n_qp) : fit;
-}
 
 // ---- LDS carve (offsets in bytes, each a multiple of 16): three k x k matrices (M, its factor L, the normal equations A), NVEC vectors
 // of MAXK doubles, the reduction scratch (THREADS doubles and THREADS ints), MAXK-int tables and the scalar words

@@ -15,10 +15,14 @@
 // zero -- a degenerate point, where more constraints meet than the working set holds -- the least index decides instead, rows before
 // variables, for the one constraint that is added and the one that is dropped (Bland's rule), until a step moves again.  M is
 // recomputed from G whenever N changes.  Every sum runs in an order fixed by the shape; no atomics.
+#include "descent_call.hpp"
 #include "ds.hpp"
+#include "lp_dev.hpp"
 
 namespace mrbf {
 namespace ds {
+
+static_assert(THREADS == lp::THREADS, "row_pass runs on a workgroup of lp::THREADS");
 
 struct Args {
     int n, k;
@@ -44,25 +48,6 @@ struct Small {
     int *piv, *done, *inS;
     __device__ double *vec(int which) const { return v + which * MAXK; }
 };
-
-// out[i] = sum_{j < n} f(i, j) for rows i < rows: THREADS / rows strided segments per row, their partial sums added in order
-template <class F>
-__device__ void row_pass(int n, int rows, F f, double *part, double *out) {
-    const int t = threadIdx.x, S = THREADS / rows;
-    if (t < rows * S) {
-        const int i = t / S, s = t % S;
-        double acc = 0.0;
-        for (int j = s; j < n; j += S) acc += f(i, j);
-        part[t] = acc;
-    }
-    __syncthreads();
-    if (t < rows) {
-        double acc = 0.0;
-        for (int s = 0; s < S; ++s) acc += part[t * S + s];
-        out[t] = acc;
-    }
-    __syncthreads();
-}
 
 // the smallest (v, idx) pair of the workgroup, lowest index on ties, in rv[0] / ri[0]
 __device__ void block_argmin(double v, int idx, double *rv, int *ri) {
@@ -216,7 +201,7 @@ __device__ void multipliers(const Small &s, int n_s) {
 // orders of magnitude while its error stays), and a pass over the free columns costs k times a pass for p.  Entry (i, i2) and entry
 // (i2, i) add the same products in the same order: M is symmetric to the bit.
 __device__ void refresh_M(const double *G, const int *flag, int n, int k, double *part, double *M) {
-    row_pass(n, k * k, [&](int e, int j) { return flag[j] == 0 ? G[(size_t)j * k + e / k] * G[(size_t)j * k + e % k] : 0.0; }, part, M);
+    lp::row_pass(n, k * k, [&](int e, int j) { return flag[j] == 0 ? G[(size_t)j * k + e / k] * G[(size_t)j * k + e % k] : 0.0; }, part, M);
 }
 
 __global__ __launch_bounds__(THREADS) void ds_qp_kernel(Args a, int64_t qp0) {
@@ -249,7 +234,7 @@ __global__ __launch_bounds__(THREADS) void ds_qp_kernel(Args a, int64_t qp0) {
     }
     empty = __syncthreads_or(empty);
     outside = __syncthreads_or(outside);
-    row_pass(n, k, [&](int i, int j) { return fabs(G[(size_t)j * k + i]); }, part, rowsum);
+    lp::row_pass(n, k, [&](int i, int j) { return fabs(G[(size_t)j * k + i]); }, part, rowsum);
     if (t == 0) {
         int critical = 0;
         for (int i = 0; i < k; ++i) {
@@ -273,7 +258,7 @@ __global__ __launch_bounds__(THREADS) void ds_qp_kernel(Args a, int64_t qp0) {
             }
             ++iters;
             for (int e = t; e < k * k; e += THREADS) sm.L[e] = 0.0;
-            row_pass(n, k, [&](int i, int j) { return G[(size_t)j * k + i] * dv[j]; }, part, z);
+            lp::row_pass(n, k, [&](int i, int j) { return G[(size_t)j * k + i] * dv[j]; }, part, z);
             // ---- the k x k problem: the coefficients a of the step
             if (t == 0) {
                 for (int i = 0; i < k; ++i) rho[i] = rv[i] - z[i];
@@ -293,7 +278,7 @@ __global__ __launch_bounds__(THREADS) void ds_qp_kernel(Args a, int64_t qp0) {
                 pv[j] = acc;
             }
             __syncthreads();
-            row_pass(n, k, [&](int i, int j) { return G[(size_t)j * k + i] * pv[j]; }, part, dz);
+            lp::row_pass(n, k, [&](int i, int j) { return G[(size_t)j * k + i] * pv[j]; }, part, dz);
             // ---- has the step vanished?  then the multipliers; else the rows' part of the ratio test
             if (t == 0) {
                 bool vanish = true;
@@ -416,7 +401,7 @@ __global__ __launch_bounds__(THREADS) void ds_qp_kernel(Args a, int64_t qp0) {
     // ---- outputs: z = G d from the returned d, in row_pass's order
     double *dout = a.d_out + qp * n, *zout = a.z_out + qp * k;
     if (status == MRBF_DS_OK) {
-        row_pass(n, k, [&](int i, int j) { return G[(size_t)j * k + i] * dv[j]; }, part, z);
+        lp::row_pass(n, k, [&](int i, int j) { return G[(size_t)j * k + i] * dv[j]; }, part, z);
         if (t == 0) {
             int bad = 0;
             double mx = -INF;
@@ -452,7 +437,7 @@ __global__ __launch_bounds__(THREADS) void ds_qp_kernel(Args a, int64_t qp0) {
     }
 }
 
-// all device pointers; QPs in chunks so that the per-QP workspaces stay below WS_LIMIT_BYTES
+// all device pointers; QPs in chunks so that the per-QP workspaces stay below dcall::WS_LIMIT_BYTES
 int launch(mrbf_ctx *ctx, int64_t n_qp, int n, int k, const double *G, const double *r, const double *x, int64_t x_stride, const double *lb,
            const double *ub, int64_t bound_stride, double *d_out, double *z_out, double *omega_out, double *mult_out, int *status_out,
            int *iters_out) {
@@ -460,7 +445,7 @@ int launch(mrbf_ctx *ctx, int64_t n_qp, int n, int k, const double *G, const dou
     a.n = n, a.k = k, a.xs = x_stride, a.bs = bound_stride;
     a.G = G, a.r = r, a.x = x, a.lb = lb, a.ub = ub;
     a.d_out = d_out, a.z_out = z_out, a.omega_out = omega_out, a.mult_out = mult_out, a.status_out = status_out, a.iters_out = iters_out;
-    const int64_t per = chunk(n_qp, n);
+    const int64_t per = dcall::chunk(n_qp, ws_bytes(n));
     MRBF_TRY(get_buf(ctx, S_DS_WS, (size_t)per * ws_doubles(n), &a.ws));
     MRBF_TRY(get_buf(ctx, S_DS_WSI, (size_t)per * ws_ints(n), &a.wsi));
     const size_t shm = carve(k).total;
@@ -497,23 +482,10 @@ extern "C" int32_t mrbf_ds_direction(mrbf_ctx *ctx, int64_t n_qp, int32_t d, int
     MRBF_TRY(input_view(ctx, x, N * d, arena, &dx));
     MRBF_TRY(input_view(ctx, lb, N * d, arena, &dlb));
     MRBF_TRY(input_view(ctx, ub, N * d, arena, &dub));
-    // outputs: the caller's device buffers in place, else one staging buffer (doubles, then the int words)
-    const bool dev_d = is_device_ptr(d_out), dev_z = is_device_ptr(z_out), dev_w = is_device_ptr(omega_out);
-    const bool dev_m = mult_out && is_device_ptr(mult_out), dev_s = is_device_ptr(status_out), dev_i = iters_out && is_device_ptr(iters_out);
-    const size_t out_dbl = N * d + 2 * N * k + N, out_int = 3 * N;
-    double *ob;
-    MRBF_TRY(get_buf(ctx, S_DS_OUT, out_dbl + (out_int + 1) / 2 + 1, &ob));
-    double *od = dev_d ? d_out : ob, *oz = dev_z ? z_out : ob + N * d, *ow = dev_w ? omega_out : ob + N * d + N * k;
-    double *om = mult_out ? (dev_m ? mult_out : ob + N * d + N * k + N) : nullptr;
-    int *oi = reinterpret_cast<int *>(ob + out_dbl);
-    int *os = dev_s ? status_out : oi, *ot = iters_out ? (dev_i ? iters_out : oi + N) : nullptr;
-    MRBF_TRY(ds::launch(ctx, n_qp, d, k, dG, dr, dx, d, dlb, dub, d, od, oz, ow, om, os, ot));
-    if (!dev_d) MRBF_HIP(ctx, hipMemcpyAsync(d_out, od, N * d * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (!dev_z) MRBF_HIP(ctx, hipMemcpyAsync(z_out, oz, N * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (!dev_w) MRBF_HIP(ctx, hipMemcpyAsync(omega_out, ow, N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (om && !dev_m) MRBF_HIP(ctx, hipMemcpyAsync(mult_out, om, N * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (!dev_s) MRBF_HIP(ctx, hipMemcpyAsync(status_out, os, N * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    if (ot && !dev_i) MRBF_HIP(ctx, hipMemcpyAsync(iters_out, ot, 2 * N * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    dcall::Outputs out;  // d, z, omega, mult, status, iterations
+    MRBF_TRY(out.open(ctx, S_DS_OUT, {{d_out, N * d, false}, {z_out, N * k, false}, {omega_out, N, false}, {mult_out, N * k, false}, {status_out, N, true}, {iters_out, 2 * N, true}}));
+    MRBF_TRY(ds::launch(ctx, n_qp, d, k, dG, dr, dx, d, dlb, dub, d, out.at<double>(0), out.at<double>(1), out.at<double>(2), out.at<double>(3), out.at<int>(4), out.at<int>(5)));
+    MRBF_TRY(out.copy_back(ctx));
     MRBF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     pin.flush();
     return MRBF_OK;
@@ -544,20 +516,18 @@ extern "C" int32_t mrbf_ds_criticality(mrbf_ctx *ctx, const mrbf_ps_problem *pro
     (void)hipSetDevice(ctx->device);
     PinGuard pin(ctx);
     // ---- host inputs, packed: x_n, lb, ub, r
-    std::vector<double> h((size_t)3 * d + k);
-    MRBF_TRY(input_fetch(ctx, x_n, d, h.data()));
-    MRBF_TRY(input_fetch(ctx, lb, d, h.data() + d));
-    MRBF_TRY(input_fetch(ctx, ub, d, h.data() + 2 * d));
-    MRBF_TRY(input_fetch(ctx, r, k, h.data() + 3 * d));
+    dcall::PackedIn in;
+    const size_t axn = in.fetch(ctx, x_n, d), alb = in.fetch(ctx, lb, d), aub = in.fetch(ctx, ub, d), ar = in.fetch(ctx, r, k);
+    MRBF_TRY(in.rc);
     hipEvent_t e0 = ctx->ev[0], e1 = ctx->ev[1];
     MRBF_HIP(ctx, hipEventRecord(e0, ctx->stream));
     // device arena: inputs | Jacobians | G | outputs (d, z, omega, mult, 3 int words)
-    const size_t out_cnt = (size_t)d + 2 * (size_t)k + 1 + 2;
+    const size_t out_dbl = (size_t)d + 2 * (size_t)k + 1, out_cnt = out_dbl + 2;
     double *base;
-    MRBF_TRY(get_buf(ctx, S_DS_IN, h.size() + at.jtot + (size_t)k * d + out_cnt, &base));
-    double *dJ = base + h.size(), *dG = dJ + at.jtot, *dout = dG + (size_t)k * d;
-    MRBF_HIP(ctx, hipMemcpyAsync(base, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    const double *dxn = base, *dlb = base + d, *dub = base + 2 * d, *dr = base + 3 * d;
+    MRBF_TRY(get_buf(ctx, S_DS_IN, in.total + at.jtot + (size_t)k * d + out_cnt, &base));
+    double *dJ = base + in.total, *dG = dJ + at.jtot, *dout = dG + (size_t)k * d;
+    MRBF_TRY(in.upload(ctx, base));
+    const double *dxn = in.dev(axn), *dlb = in.dev(alb), *dub = in.dev(aub), *dr = in.dev(ar);
     for (int j = 0; j < prob->n_models; ++j)
         if (lay.chosen(j, descent::Slots::OBJECTIVE)) MRBF_TRY(eval_model(ctx, prob->models[j], 1, dxn, nullptr, dJ + at.jac[j], nullptr));
     // ---- G from the Jacobians by the roles table (the objective rows of sd_lp.hip's assembly)
@@ -568,7 +538,7 @@ extern "C" int32_t mrbf_ds_criticality(mrbf_ctx *ctx, const mrbf_ps_problem *pro
     aa.G = dG;
     descent::fill_sources(lay, at, true, aa.src);  // the linear rows are refused above: k objective rows
     MRBF_TRY(sd::launch_assemble(ctx, aa, 1));
-    int *oi = reinterpret_cast<int *>(dout + d + 2 * k + 1);
+    int *oi = reinterpret_cast<int *>(dout + out_dbl);
     MRBF_TRY(ds::launch(ctx, 1, d, k, dG, dr, dxn, 0, dlb, dub, 0, dout, dout + d, dout + d + k, dout + d + k + 1, oi, oi + 1));
     // ---- one read-back
     std::vector<double> hout(out_cnt);
@@ -577,9 +547,7 @@ extern "C" int32_t mrbf_ds_criticality(mrbf_ctx *ctx, const mrbf_ps_problem *pro
     MRBF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     pin.flush();
     MRBF_HIP(ctx, hipEventElapsedTime(&info->ms_total, e0, e1));
-    int words[3];
-    std::memcpy(words, hout.data() + d + 2 * k + 1, sizeof(words));
-    info->status = words[0], info->iterations = words[1], info->dropped = words[2];
+    dcall::read_status(hout.data() + out_dbl, &info->status, &info->iterations, &info->dropped);
     info->omega = hout[d + k];
     MRBF_TRY(output_put(ctx, d_out, hout.data(), d));
     if (mult_out) MRBF_TRY(output_put(ctx, mult_out, hout.data() + d + k + 1, k));

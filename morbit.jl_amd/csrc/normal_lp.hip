@@ -19,10 +19,14 @@
 // nothing accumulates; the primal point and the multipliers are recomputed from it.  A result is accepted only when, besides
 // primal feasibility, every multiplier of an inequality member of W is >= -DUAL_TOL (else GAVE_UP).  Every sum runs in a fixed order that
 // depends on the shape alone, and no atomics touch values: an LP's result does not depend on its position in the batch.
+#include "descent_call.hpp"
+#include "lp_dev.hpp"
 #include "normal.hpp"
 
 namespace mrbf {
 namespace ns {
+
+static_assert(THREADS == lp::THREADS, "row_pass and invert run on a workgroup of lp::THREADS");
 
 constexpr double FEAS_TOL = 1e-13;    // relative to the constraint's magnitude
 constexpr double PIVOT_TOL = 1e-9;    // ratio-test candidates: rate > PIVOT_TOL * the largest |rate|
@@ -78,25 +82,6 @@ __host__ __device__ inline Carve carve(int ms) {
     return c;
 }
 
-// out[i] = sum_{j < n} f(i, j) for rows i < rows: THREADS / rows strided segments per row, their partial sums added in order
-template <class F>
-__device__ void row_pass(int n, int rows, F f, double *part, double *out) {
-    const int t = threadIdx.x, S = THREADS / rows;
-    if (t < rows * S) {
-        const int i = t / S, s = t % S;
-        double acc = 0.0;
-        for (int j = s; j < n; j += S) acc += f(i, j);
-        part[t] = acc;
-    }
-    __syncthreads();
-    if (t < rows) {
-        double acc = 0.0;
-        for (int s = 0; s < S; ++s) acc += part[t * S + s];
-        out[t] = acc;
-    }
-    __syncthreads();
-}
-
 // (key, index) reduction over the workgroup: better(a, b) decides; ties of every kind are settled by the caller's comparison
 template <class B>
 __device__ void argbest(double *key, double *key2, int *idx, B better) {
@@ -107,46 +92,6 @@ __device__ void argbest(double *key, double *key2, int *idx, B better) {
             key[t] = key[t + s], key2[t] = key2[t + s], idx[t] = idx[t + s];
         __syncthreads();
     }
-}
-
-// M^-1 from scratch: Gauss-Jordan with partial pivoting on [M | I] (sz x 2 sz in aug).  false: M is singular.
-__device__ bool invert(int sz, double *aug, double *Minv, double *rowbuf, double *fac, double *cmax, int *flag) {
-    const int t = threadIdx.x, W = 2 * sz;
-    for (int c = t; c < sz; c += THREADS) {
-        double mx = 0.0;
-        for (int r = 0; r < sz; ++r) mx = fmax(mx, fabs(aug[r * W + c]));
-        cmax[c] = mx;
-    }
-    __syncthreads();
-    for (int c = 0; c < sz; ++c) {
-        if (t == 0) {
-            int r = c;
-            double best = fabs(aug[c * W + c]);
-            for (int i = c + 1; i < sz; ++i)
-                if (fabs(aug[i * W + c]) > best) best = fabs(aug[i * W + c]), r = i;
-            *flag = (best > 1e-14 * cmax[c] && best > 0.0) ? r : -1;
-        }
-        __syncthreads();
-        const int r = *flag;
-        if (r < 0) return false;  // uniform
-        const double inv = 1.0 / aug[r * W + c];
-        for (int e = t; e < W; e += THREADS) rowbuf[e] = aug[r * W + e] * inv;
-        for (int i = t; i < sz; i += THREADS) fac[i] = aug[i * W + c];
-        __syncthreads();
-        if (r != c)
-            for (int e = t; e < W; e += THREADS) aug[r * W + e] = aug[c * W + e];
-        __syncthreads();
-        if (r != c && t == 0) fac[r] = fac[c];
-        __syncthreads();
-        for (int e = t; e < sz * W; e += THREADS) {
-            const int i = e / W, cc = e % W;
-            aug[e] = i == c ? rowbuf[cc] : aug[e] - fac[i] * rowbuf[cc];
-        }
-        __syncthreads();
-    }
-    for (int e = t; e < sz * sz; e += THREADS) Minv[e] = aug[(e / sz) * W + sz + e % sz];  // Minv[v * sz + p]: var slot v, row slot p
-    __syncthreads();
-    return true;
 }
 
 __global__ __launch_bounds__(THREADS) void normal_lp_kernel(Args a, int64_t lp0) {
@@ -204,9 +149,9 @@ __global__ __launch_bounds__(THREADS) void normal_lp_kernel(Args a, int64_t lp0)
         }
         __syncthreads();
         if (m > 0) {
-            row_pass(n, m, [&](int i, int j) { return L.c(i, j) * nv[j]; }, part, cn);
-            row_pass(n, m, [&](int i, int j) { return fabs(L.c(i, j)); }, part, cabs);
-            row_pass(n, m, [&](int i, int j) { const double v = L.c(i, j); return v * v; }, part, cnrm);
+            lp::row_pass(n, m, [&](int i, int j) { return L.c(i, j) * nv[j]; }, part, cn);
+            lp::row_pass(n, m, [&](int i, int j) { return fabs(L.c(i, j)); }, part, cabs);
+            lp::row_pass(n, m, [&](int i, int j) { const double v = L.c(i, j); return v * v; }, part, cnrm);
             if (t < m) cnrm[t] = cnrm[t] > 0.0 ? sqrt(cnrm[t]) : 1.0;
             if (t < m) {
                 const double r = cn[t] - bt[t], tol = FEAS_TOL * fmax(1.0, fabs(bt[t]) + cabs[t] * fmax(1.0, a0));
@@ -234,8 +179,8 @@ __global__ __launch_bounds__(THREADS) void normal_lp_kernel(Args a, int64_t lp0)
         const int nr = S.nr, nf = S.nf, sz = nf + 1, fix = S.fix;
         // ---- M: rows R (then the alpha-fixing member), columns the free n_j (then alpha)
         if (m > 0) {
-            row_pass(n, m, [&](int i, int j) { const int p = pin[j]; return p >= BANDL ? sgn(p) * L.c(i, j) : 0.0; }, part, aal);
-            row_pass(n, m, [&](int i, int j) { const int p = pin[j]; return (p == BOXL || p == BOXU) ? L.c(i, j) * sgn(p) * bval(p, j) : 0.0; },
+            lp::row_pass(n, m, [&](int i, int j) { const int p = pin[j]; return p >= BANDL ? sgn(p) * L.c(i, j) : 0.0; }, part, aal);
+            lp::row_pass(n, m, [&](int i, int j) { const int p = pin[j]; return (p == BOXL || p == BOXU) ? L.c(i, j) * sgn(p) * bval(p, j) : 0.0; },
                      part, ccon);
         }
         double kap = -1.0, rf = -a0;
@@ -256,13 +201,13 @@ __global__ __launch_bounds__(THREADS) void normal_lp_kernel(Args a, int64_t lp0)
         if (t < nr) rhs[t] = bt[R[t]] - ccon[R[t]];
         if (t == 0 && fix != FIX_NONE) rhs[nr] = rf;
         __syncthreads();
-        if (!invert(sz, aug, Minv, rowbuf, part, cmaxv, pidx)) {
+        if (!lp::invert(sz, aug, Minv, rowbuf, part, cmaxv, pidx)) {
             if (t == 0) S.status = MRBF_NS_GAVE_UP;
             __syncthreads();
             break;
         }
         // ---- primal point z = M^-1 rhs; multipliers of the rows lamr = -(M^-T c~) for the perturbed costs c~ = (pc, 1)
-        row_pass(n, 1, [&](int, int j) { const int p = pin[j]; return p >= BANDL ? sgn(p) * pc[j] : 0.0; }, part, rv + nf);
+        lp::row_pass(n, 1, [&](int, int j) { const int p = pin[j]; return p >= BANDL ? sgn(p) * pc[j] : 0.0; }, part, rv + nf);
         if (t < nf) rv[t] = pc[F[t]];
         if (t == nf) rv[t] += 1.0;
         __syncthreads();
@@ -309,8 +254,8 @@ __global__ __launch_bounds__(THREADS) void normal_lp_kernel(Args a, int64_t lp0)
         __syncthreads();
         // ---- the rows outside W, alpha >= alpha0
         if (m > 0) {
-            row_pass(n, m, [&](int i, int j) { return L.c(i, j) * nv[j]; }, part, cn);
-            row_pass(n, m, [&](int i, int j) { return fabs(L.c(i, j) * nv[j]); }, part, cabs);
+            lp::row_pass(n, m, [&](int i, int j) { return L.c(i, j) * nv[j]; }, part, cn);
+            lp::row_pass(n, m, [&](int i, int j) { return fabs(L.c(i, j) * nv[j]); }, part, cabs);
         }
         if (t == 0) {
             double bv = cbest;
@@ -550,12 +495,9 @@ int launch(mrbf_ctx *ctx, int64_t n_lp, int n, int meq, int min, const double *x
     a.bs = bound_stride;
     a.x = x, a.lb = lb, a.ub = ub, a.Aeq = Aeq, a.beq = beq, a.Ain = Ain, a.bin = bin;
     a.n_out = n_out, a.alpha_out = alpha_out, a.dual_out = dual_out, a.status_out = status_out, a.iters_out = iters_out;
-    const size_t per = (size_t)n * (6 * sizeof(double) + sizeof(int));
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n_lp, ((size_t)256 << 20) / per));
+    const int64_t chunk = dcall::chunk(n_lp, (size_t)n * (6 * sizeof(double) + sizeof(int)));
     MRBF_TRY(get_buf(ctx, S_NS_WS, (size_t)chunk * n * 6, &a.ws));
-    int *wsi;
-    MRBF_TRY(get_buf(ctx, S_NS_OUT, (size_t)chunk * n * sizeof(int), (void **)&wsi));
-    a.wsi = wsi;
+    MRBF_TRY(get_buf(ctx, S_NS_OUT, (size_t)chunk * n, &a.wsi));
     const size_t shm = carve(a.m + 1).total;
     MRBF_HIP(ctx, hipFuncSetAttribute((const void *)normal_lp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
     for (int64_t l0 = 0; l0 < n_lp; l0 += chunk) {
@@ -608,20 +550,10 @@ extern "C" int32_t mrbf_normal_direction(mrbf_ctx *ctx, int64_t n_lp, int32_t d,
     MRBF_TRY(input_view(ctx, b_eq, N * m_eq, arena, &dbeq));
     MRBF_TRY(input_view(ctx, A_ineq, N * m_ineq * d, arena, &dAin));
     MRBF_TRY(input_view(ctx, b_ineq, N * m_ineq, arena, &dbin));
-    const bool dev_n = is_device_ptr(n_out), dev_a = is_device_ptr(alpha_out), dev_y = dual_out && is_device_ptr(dual_out);
-    const bool dev_s = is_device_ptr(status_out), dev_i = iters_out && is_device_ptr(iters_out);
-    const size_t out_dbl = N * d + N + N * m, out_int = 3 * N;
-    double *ob;
-    MRBF_TRY(get_buf(ctx, S_STAGE_D, out_dbl + (out_int + 1) / 2 + 1, &ob));
-    double *on = dev_n ? n_out : ob, *oa = dev_a ? alpha_out : ob + N * d, *oy = dual_out ? (dev_y ? dual_out : ob + N * d + N) : nullptr;
-    int *oi = reinterpret_cast<int *>(ob + out_dbl);
-    int *os = dev_s ? status_out : oi, *ot = iters_out ? (dev_i ? iters_out : oi + N) : nullptr;
-    MRBF_TRY(ns::launch(ctx, n_lp, d, m_eq, m_ineq, dx, dlb, dub, d, dAeq, dbeq, dAin, dbin, on, oa, oy, os, ot));
-    if (!dev_n) MRBF_HIP(ctx, hipMemcpyAsync(n_out, on, N * d * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (!dev_a) MRBF_HIP(ctx, hipMemcpyAsync(alpha_out, oa, N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (oy && !dev_y) MRBF_HIP(ctx, hipMemcpyAsync(dual_out, oy, N * m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (!dev_s) MRBF_HIP(ctx, hipMemcpyAsync(status_out, os, N * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    if (ot && !dev_i) MRBF_HIP(ctx, hipMemcpyAsync(iters_out, ot, 2 * N * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    dcall::Outputs out;  // n, alpha, dual, status, iterations
+    MRBF_TRY(out.open(ctx, S_STAGE_D, {{n_out, N * d, false}, {alpha_out, N, false}, {dual_out, N * m, false}, {status_out, N, true}, {iters_out, 2 * N, true}}));
+    MRBF_TRY(ns::launch(ctx, n_lp, d, m_eq, m_ineq, dx, dlb, dub, d, dAeq, dbeq, dAin, dbin, out.at<double>(0), out.at<double>(1), out.at<double>(2), out.at<int>(3), out.at<int>(4)));
+    MRBF_TRY(out.copy_back(ctx));
     MRBF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     pin.flush();
     return MRBF_OK;
@@ -656,23 +588,20 @@ extern "C" int32_t mrbf_normal_step(mrbf_ctx *ctx, const mrbf_ps_problem *prob, 
     (void)hipSetDevice(ctx->device);
     PinGuard pin(ctx);
     // ---- host inputs, packed: x, lb, ub, linear rows (eq, then ineq), their b
-    const size_t nlin = (size_t)n_lin;
-    std::vector<double> h((size_t)3 * d + nlin * (d + 1));
-    double *hx = h.data(), *hlb = hx + d, *hub = hlb + d, *hA = hub + d, *hb = hA + nlin * d;
-    MRBF_TRY(input_fetch(ctx, x, d, hx));
-    MRBF_TRY(input_fetch(ctx, lb, d, hlb));
-    MRBF_TRY(input_fetch(ctx, ub, d, hub));
-    MRBF_TRY(fetch_linear_rows(ctx, prob, d, hA, hb));
+    dcall::PackedIn in;
+    const size_t ax = in.fetch(ctx, x, d), alb = in.fetch(ctx, lb, d), aub = in.fetch(ctx, ub, d);
+    const auto [aA, ab] = in.fetch_linear_rows(ctx, prob, d);
+    MRBF_TRY(in.rc);
     hipEvent_t e0 = ctx->ev[0], e1 = ctx->ev[1];
     MRBF_HIP(ctx, hipEventRecord(e0, ctx->stream));
     // device arena: inputs | Jacobians | values | LP data (A_eq, b_eq, A_ineq, b_ineq) | outputs (n, alpha, dual, 3 int words)
-    const size_t lp_cnt = (size_t)m * (d + 1), out_cnt = (size_t)d + 1 + m + 2;
+    const size_t lp_cnt = (size_t)m * (d + 1), out_dbl = (size_t)d + 1 + m, out_cnt = out_dbl + 2;
     double *base;
-    MRBF_TRY(get_buf(ctx, S_NS_IN, h.size() + jtot + vtot + lp_cnt + out_cnt, &base));
-    double *dJ = base + h.size(), *dV = dJ + jtot, *dAeq = dV + vtot, *dbeq = dAeq + (size_t)meq * d;
+    MRBF_TRY(get_buf(ctx, S_NS_IN, in.total + jtot + vtot + lp_cnt + out_cnt, &base));
+    double *dJ = base + in.total, *dV = dJ + jtot, *dAeq = dV + vtot, *dbeq = dAeq + (size_t)meq * d;
     double *dAin = dbeq + meq, *dbin = dAin + (size_t)min * d, *dout = dbin + min;
-    MRBF_HIP(ctx, hipMemcpyAsync(base, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    const double *dx = base, *dlb = base + d, *dub = base + 2 * d, *dA = base + 3 * d, *db = dA + nlin * d;
+    MRBF_TRY(in.upload(ctx, base));
+    const double *dx = in.dev(ax), *dlb = in.dev(alb), *dub = in.dev(aub), *dA = in.dev(aA), *db = in.dev(ab);
     // ---- values and Jacobians at x: one site per model that carries constraint rows
     for (int j = 0; j < prob->n_models; ++j)
         if (lay.has_con[j]) MRBF_TRY(eval_model(ctx, prob->models[j], 1, dx, dV + at.val[j], dJ + at.jac[j], nullptr));
@@ -684,7 +613,7 @@ extern "C" int32_t mrbf_normal_step(mrbf_ctx *ctx, const mrbf_ps_problem *prob, 
     aa.Aeq = dAeq, aa.beq = dbeq, aa.Ain = dAin, aa.bin = dbin;
     descent::fill_sources(lay, at, false, aa.src);
     MRBF_TRY(ns::launch_assemble(ctx, aa, 1));
-    int *oi = reinterpret_cast<int *>(dout + d + 1 + m);
+    int *oi = reinterpret_cast<int *>(dout + out_dbl);
     MRBF_TRY(ns::launch(ctx, 1, d, meq, min, dx, dlb, dub, 0, meq ? dAeq : nullptr, meq ? dbeq : nullptr, min ? dAin : nullptr,
                         min ? dbin : nullptr, dout, dout + d, dout + d + 1, oi, oi + 1));
     // ---- one read-back
@@ -694,9 +623,7 @@ extern "C" int32_t mrbf_normal_step(mrbf_ctx *ctx, const mrbf_ps_problem *prob, 
     MRBF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     pin.flush();
     MRBF_HIP(ctx, hipEventElapsedTime(&info->ms_total, e0, e1));
-    int words[3];
-    std::memcpy(words, hout.data() + d + 1 + m, sizeof(words));
-    info->status = words[0], info->iterations = words[1], info->bound_flips = words[2];
+    dcall::read_status(hout.data() + out_dbl, &info->status, &info->iterations, &info->bound_flips);
     info->alpha = hout[d];
     // ---- compute_normal_step's radius (descent.jl:691-757): the given one, or alpha / kappa_delta up to delta_max
     bool ok = info->status == MRBF_NS_OK;

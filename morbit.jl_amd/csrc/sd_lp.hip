@@ -12,10 +12,14 @@
 // B^-1 every iteration (one pass over the rows, one over the columns), so no update error accumulates in them.  Every sum runs in a
 // fixed order that depends on the shape alone: an LP's result does not depend on its position in the batch, and no atomics touch
 // values (the one LDS atomic only compacts the ratio-test candidates, which are then sorted by (breakpoint, column)).
+#include "descent_call.hpp"
+#include "lp_dev.hpp"
 #include "sd.hpp"
 
 namespace mrbf {
 namespace sd {
+
+static_assert(THREADS == lp::THREADS, "row_pass and invert run on a workgroup of lp::THREADS");
 
 constexpr int REFACTOR_EVERY = 16;
 constexpr double FEAS_TOL = 1e-13;   // relative to the row's magnitude sum |b_i| + sum_j |A_ij| (|d_j| <= 1)
@@ -65,25 +69,6 @@ enum { I_ACT = 0, I_P, I_DIR, I_CNT, I_TE, I_PIV, I_BAD, I_I0 };
 enum { A_PIVOT = 0, A_DONE, A_REFACTOR, A_GIVEUP, A_INFEASIBLE };
 enum { D_SLOPE = 0, D_AMAX };
 
-// out[i] = sum_{j < n} f(i, j) for rows i < rows: THREADS / rows strided segments per row, their partial sums added in order
-template <class F>
-__device__ void row_pass(int n, int rows, F f, double *part, double *out) {
-    const int t = threadIdx.x, S = THREADS / rows;
-    if (t < rows * S) {
-        const int i = t / S, s = t % S;
-        double acc = 0.0;
-        for (int j = s; j < n; j += S) acc += f(i, j);
-        part[t] = acc;
-    }
-    __syncthreads();
-    if (t < rows) {
-        double acc = 0.0;
-        for (int s = 0; s < S; ++s) acc += part[t * S + s];
-        out[t] = acc;
-    }
-    __syncthreads();
-}
-
 __device__ inline double col_entry(const Lp &L, const double *w, int col, int i) {
     if (col < L.n) return L.a(i, col);
     if (col == L.n) return i < L.k ? -w[i] : 0.0;
@@ -99,41 +84,7 @@ __device__ bool refactor(const Lp &L, int m, const double *w, const int *head, d
         aug[e] = c < m ? col_entry(L, w, head[c], r) : (c - m == r ? 1.0 : 0.0);
     }
     __syncthreads();
-    for (int c = t; c < m; c += THREADS) {
-        double mx = 0.0;
-        for (int r = 0; r < m; ++r) mx = fmax(mx, fabs(aug[r * W + c]));
-        cmax[c] = mx;
-    }
-    __syncthreads();
-    for (int c = 0; c < m; ++c) {
-        if (t == 0) {
-            int r = c;
-            double best = fabs(aug[c * W + c]);
-            for (int i = c + 1; i < m; ++i)
-                if (fabs(aug[i * W + c]) > best) best = fabs(aug[i * W + c]), r = i;
-            isc[I_PIV] = (best > 1e-14 * cmax[c] && best > 0.0) ? r : -1;
-        }
-        __syncthreads();
-        const int r = isc[I_PIV];
-        if (r < 0) return false;  // uniform: every thread read the same word
-        const double inv = 1.0 / aug[r * W + c];
-        for (int e = t; e < W; e += THREADS) rowbuf[e] = aug[r * W + e] * inv;
-        for (int i = t; i < m; i += THREADS) fac[i] = aug[i * W + c];
-        __syncthreads();
-        if (r != c)
-            for (int e = t; e < W; e += THREADS) aug[r * W + e] = aug[c * W + e];  // row c moves to r (row r is in rowbuf)
-        __syncthreads();
-        if (r != c && t == 0) fac[r] = fac[c];
-        __syncthreads();
-        for (int e = t; e < m * W; e += THREADS) {
-            const int i = e / W, cc = e % W;
-            aug[e] = i == c ? rowbuf[cc] : aug[e] - fac[i] * rowbuf[cc];
-        }
-        __syncthreads();
-    }
-    for (int e = t; e < m * m; e += THREADS) Binv[e] = aug[(e / m) * W + m + e % m];
-    __syncthreads();
-    return true;
+    return lp::invert(m, aug, Binv, rowbuf, fac, cmax, isc + I_PIV);
 }
 
 __global__ __launch_bounds__(THREADS) void sd_lp_kernel(Args a, int64_t lp0) {
@@ -172,8 +123,8 @@ __global__ __launch_bounds__(THREADS) void sd_lp_kernel(Args a, int64_t lp0) {
         lo[j] = l, hi[j] = u, pos[j] = -1, xv[j] = 0.0;
     }
     bad = __syncthreads_or(bad);
-    row_pass(n, k, [&](int i, int j) { const double g = L.G[(size_t)j * k + i]; return g * g; }, part, w);
-    row_pass(n, m, [&](int i, int j) { return fabs(L.a(i, j)); }, part, ftol);
+    lp::row_pass(n, k, [&](int i, int j) { const double g = L.G[(size_t)j * k + i]; return g * g; }, part, w);
+    lp::row_pass(n, m, [&](int i, int j) { return fabs(L.a(i, j)); }, part, ftol);
     if (t < m) {
         if (t < k) w[t] = a.normalize ? sqrt(w[t]) : 1.0;
         bt[t] = t < k ? 0.0 : (t < k + meq ? a.beq[lp * meq + t - k] : a.bin[lp * a.min + t - k - meq]);
@@ -207,7 +158,7 @@ __global__ __launch_bounds__(THREADS) void sd_lp_kernel(Args a, int64_t lp0) {
         int since = 0;
         while (status == MRBF_SD_OK) {
             // ---- basic values beta = B^-1 (b - N x_N): only structural columns carry non-zero nonbasic values
-            row_pass(n, m, [&](int i, int j) { return pos[j] < 0 ? L.a(i, j) * xv[j] : 0.0; }, part, rhs);
+            lp::row_pass(n, m, [&](int i, int j) { return pos[j] < 0 ? L.a(i, j) * xv[j] : 0.0; }, part, rhs);
             if (t < m) {
                 double acc = 0.0;
                 for (int q = 0; q < m; ++q) acc += Binv[t * m + q] * (bt[q] - rhs[q]);
@@ -399,7 +350,7 @@ __global__ __launch_bounds__(THREADS) void sd_lp_kernel(Args a, int64_t lp0) {
             dj[j] = v;
         }
         __syncthreads();
-        row_pass(n, k, [&](int i, int j) { return L.G[(size_t)j * k + i] * dj[j]; }, part, rhs);
+        lp::row_pass(n, k, [&](int i, int j) { return L.G[(size_t)j * k + i] * dj[j]; }, part, rhs);
         if (t == 0) {
             double mx = -INF;
             for (int i = 0; i < k; ++i)
@@ -467,12 +418,9 @@ int launch(mrbf_ctx *ctx, int64_t n_lp, int n, int k, int meq, int min, int norm
     while (a.p2 < a.nc) a.p2 <<= 1;
     a.G = G, a.x = x, a.lb = lb, a.ub = ub, a.Aeq = Aeq, a.beq = beq, a.Ain = Ain, a.bin = bin;
     a.d_out = d_out, a.omega_out = omega_out, a.dual_out = dual_out, a.status_out = status_out, a.iters_out = iters_out;
-    const size_t per = (size_t)a.nc * (5 * sizeof(double) + sizeof(int));
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n_lp, ((size_t)256 << 20) / per));
+    const int64_t chunk = dcall::chunk(n_lp, (size_t)a.nc * (5 * sizeof(double) + sizeof(int)));
     MRBF_TRY(get_buf(ctx, S_SD_WS, (size_t)chunk * a.nc * 5, &a.ws));
-    int *wsi;
-    MRBF_TRY(get_buf(ctx, S_SD_OUT, (size_t)chunk * a.nc * sizeof(int), (void **)&wsi));
-    a.wsi = wsi;
+    MRBF_TRY(get_buf(ctx, S_SD_OUT, (size_t)chunk * a.nc, &a.wsi));
     const size_t shm = carve(a.m, a.p2).total;
     MRBF_HIP(ctx, hipFuncSetAttribute((const void *)sd_lp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
     for (int64_t lp0 = 0; lp0 < n_lp; lp0 += chunk) {
@@ -527,21 +475,10 @@ extern "C" int32_t mrbf_sd_direction(mrbf_ctx *ctx, int64_t n_lp, int32_t d, int
     MRBF_TRY(input_view(ctx, b_eq, N * m_eq, arena, &dbeq));
     MRBF_TRY(input_view(ctx, A_ineq, N * m_ineq * d, arena, &dAin));
     MRBF_TRY(input_view(ctx, b_ineq, N * m_ineq, arena, &dbin));
-    // outputs: the caller's device buffers in place, else one staging buffer (doubles, then the int words)
-    const bool dev_d = is_device_ptr(d_out), dev_w = is_device_ptr(omega_out), dev_y = dual_out && is_device_ptr(dual_out);
-    const bool dev_s = is_device_ptr(status_out), dev_i = iters_out && is_device_ptr(iters_out);
-    const size_t out_dbl = N * d + N + N * m, out_int = 3 * N;
-    double *ob;
-    MRBF_TRY(get_buf(ctx, S_STAGE_D, out_dbl + (out_int + 1) / 2 + 1, &ob));
-    double *od = dev_d ? d_out : ob, *ow = dev_w ? omega_out : ob + N * d, *oy = dual_out ? (dev_y ? dual_out : ob + N * d + N) : nullptr;
-    int *oi = reinterpret_cast<int *>(ob + out_dbl);
-    int *os = dev_s ? status_out : oi, *ot = iters_out ? (dev_i ? iters_out : oi + N) : nullptr;
-    MRBF_TRY(sd::launch(ctx, n_lp, d, k, m_eq, m_ineq, normalize, dG, dx, d, dlb, dub, d, dAeq, dbeq, dAin, dbin, od, ow, oy, os, ot));
-    if (!dev_d) MRBF_HIP(ctx, hipMemcpyAsync(d_out, od, N * d * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (!dev_w) MRBF_HIP(ctx, hipMemcpyAsync(omega_out, ow, N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (oy && !dev_y) MRBF_HIP(ctx, hipMemcpyAsync(dual_out, oy, N * m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (!dev_s) MRBF_HIP(ctx, hipMemcpyAsync(status_out, os, N * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    if (ot && !dev_i) MRBF_HIP(ctx, hipMemcpyAsync(iters_out, ot, 2 * N * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    dcall::Outputs out;  // d, omega, dual, status, iterations
+    MRBF_TRY(out.open(ctx, S_STAGE_D, {{d_out, N * d, false}, {omega_out, N, false}, {dual_out, N * m, false}, {status_out, N, true}, {iters_out, 2 * N, true}}));
+    MRBF_TRY(sd::launch(ctx, n_lp, d, k, m_eq, m_ineq, normalize, dG, dx, d, dlb, dub, d, dAeq, dbeq, dAin, dbin, out.at<double>(0), out.at<double>(1), out.at<double>(2), out.at<int>(3), out.at<int>(4)));
+    MRBF_TRY(out.copy_back(ctx));
     MRBF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     pin.flush();
     return MRBF_OK;
@@ -573,24 +510,20 @@ extern "C" int32_t mrbf_sd_criticality(mrbf_ctx *ctx, const mrbf_ps_problem *pro
     (void)hipSetDevice(ctx->device);
     PinGuard pin(ctx);
     // ---- host inputs, packed: [x_n; x] (the two evaluation sites), lb, ub, linear rows (eq, then ineq), their b
-    const size_t nlin = (size_t)n_lin;
-    std::vector<double> h((size_t)4 * d + nlin * (d + 1));
-    double *hxn = h.data(), *hx = hxn + d, *hlb = hx + d, *hub = hlb + d, *hA = hub + d, *hb = hA + nlin * d;
-    MRBF_TRY(input_fetch(ctx, x_n, d, hxn));
-    MRBF_TRY(input_fetch(ctx, x, d, hx));
-    MRBF_TRY(input_fetch(ctx, lb, d, hlb));
-    MRBF_TRY(input_fetch(ctx, ub, d, hub));
-    MRBF_TRY(fetch_linear_rows(ctx, prob, d, hA, hb));
+    dcall::PackedIn in;
+    const size_t axn = in.fetch(ctx, x_n, d), ax = in.fetch(ctx, x, d), alb = in.fetch(ctx, lb, d), aub = in.fetch(ctx, ub, d);
+    const auto [aA, ab] = in.fetch_linear_rows(ctx, prob, d);
+    MRBF_TRY(in.rc);
     hipEvent_t e0 = ctx->ev[0], e1 = ctx->ev[1];
     MRBF_HIP(ctx, hipEventRecord(e0, ctx->stream));
     // device arena: inputs | Jacobians | values | LP data (G, A_eq, b_eq, A_ineq, b_ineq) | outputs (d, omega, dual, 3 int words)
-    const size_t lp_cnt = (size_t)k * d + (size_t)(meq + min) * (d + 1), out_cnt = (size_t)d + 1 + m + 2;
+    const size_t lp_cnt = (size_t)k * d + (size_t)(meq + min) * (d + 1), out_dbl = (size_t)d + 1 + m, out_cnt = out_dbl + 2;
     double *base;
-    MRBF_TRY(get_buf(ctx, S_SD_IN, h.size() + jtot + vtot + lp_cnt + out_cnt, &base));
-    double *dJ = base + h.size(), *dV = dJ + jtot, *dG = dV + vtot, *dAeq = dG + (size_t)k * d, *dbeq = dAeq + (size_t)meq * d;
+    MRBF_TRY(get_buf(ctx, S_SD_IN, in.total + jtot + vtot + lp_cnt + out_cnt, &base));
+    double *dJ = base + in.total, *dV = dJ + jtot, *dG = dV + vtot, *dAeq = dG + (size_t)k * d, *dbeq = dAeq + (size_t)meq * d;
     double *dAin = dbeq + meq, *dbin = dAin + (size_t)min * d, *dout = dbin + min;
-    MRBF_HIP(ctx, hipMemcpyAsync(base, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    const double *dxn = base, *dx = base + d, *dlb = base + 2 * d, *dub = base + 3 * d, *dA = base + 4 * d, *db = dA + nlin * d;
+    MRBF_TRY(in.upload(ctx, base));
+    const double *dxn = in.dev(axn), *dx = in.dev(ax), *dlb = in.dev(alb), *dub = in.dev(aub), *dA = in.dev(aA), *db = in.dev(ab);
     // ---- values and Jacobians of every model at x_n and x: one sweep per model
     for (int j = 0; j < prob->n_models; ++j)
         if (lay.chosen(j, descent::Slots::USED)) MRBF_TRY(eval_model(ctx, prob->models[j], 2, dxn, dV + at.val[j], dJ + at.jac[j], nullptr));
@@ -602,7 +535,7 @@ extern "C" int32_t mrbf_sd_criticality(mrbf_ctx *ctx, const mrbf_ps_problem *pro
     aa.G = dG, aa.Aeq = dAeq, aa.beq = dbeq, aa.Ain = dAin, aa.bin = dbin;
     descent::fill_sources(lay, at, true, aa.src);
     MRBF_TRY(sd::launch_assemble(ctx, aa, 1));
-    int *oi = reinterpret_cast<int *>(dout + d + 1 + m);
+    int *oi = reinterpret_cast<int *>(dout + out_dbl);
     MRBF_TRY(sd::launch(ctx, 1, d, k, meq, min, normalize, dG, dxn, 0, dlb, dub, 0, meq ? dAeq : nullptr, meq ? dbeq : nullptr,
                         min ? dAin : nullptr, min ? dbin : nullptr, dout, dout + d, dout + d + 1, oi, oi + 1));
     // ---- one read-back
@@ -612,9 +545,7 @@ extern "C" int32_t mrbf_sd_criticality(mrbf_ctx *ctx, const mrbf_ps_problem *pro
     MRBF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     pin.flush();
     MRBF_HIP(ctx, hipEventElapsedTime(&info->ms_total, e0, e1));
-    int words[3];
-    std::memcpy(words, hout.data() + d + 1 + m, sizeof(words));
-    info->status = words[0], info->iterations = words[1], info->bound_flips = words[2];
+    dcall::read_status(hout.data() + out_dbl, &info->status, &info->iterations, &info->bound_flips);
     info->omega = hout[d];
     MRBF_TRY(output_put(ctx, d_out, hout.data(), d));
     if (dual_out) MRBF_TRY(output_put(ctx, dual_out, hout.data() + d + 1, m));

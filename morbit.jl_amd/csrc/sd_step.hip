@@ -12,6 +12,7 @@
 // order fixed by the shape (lane-strided partials, a fixed shuffle / LDS tree); every min / max is exact; no atomics.  The trial points
 // and Armijo right-hand sides are formed without FMA contraction, so they round exactly as the host loop's `x + s * d` and
 // `s * c * omega` do.  DESIGN.md section 10.
+#include "descent_call.hpp"
 #include "sd.hpp"
 
 namespace mrbf {
@@ -374,16 +375,12 @@ extern "C" int32_t mrbf_sd_step(mrbf_ctx *ctx, const mrbf_ps_problem *prob, cons
     (void)hipSetDevice(ctx->device);
     PinGuard pin(ctx);
     // ---- host inputs, packed: x_n, x, lb, ub, d, linear rows (eq, then ineq), their b, delta, omega
-    const size_t nlin = (size_t)n_lin;
-    std::vector<double> h((size_t)5 * d + nlin * (d + 1) + 2);
-    double *hxn = h.data(), *hx = hxn + d, *hlb = hx + d, *hub = hlb + d, *hd = hub + d, *hA = hd + d, *hb = hA + nlin * d;
-    hb[nlin] = delta, hb[nlin + 1] = omega;
-    MRBF_TRY(input_fetch(ctx, x_n, d, hxn));
-    MRBF_TRY(input_fetch(ctx, x, d, hx));
-    MRBF_TRY(input_fetch(ctx, lb, d, hlb));
-    MRBF_TRY(input_fetch(ctx, ub, d, hub));
-    MRBF_TRY(input_fetch(ctx, dir, d, hd));
-    MRBF_TRY(fetch_linear_rows(ctx, prob, d, hA, hb));
+    dcall::PackedIn in;
+    const size_t axn = in.fetch(ctx, x_n, d), ax = in.fetch(ctx, x, d), alb = in.fetch(ctx, lb, d), aub = in.fetch(ctx, ub, d), adir = in.fetch(ctx, dir, d);
+    const auto [aA, ab] = in.fetch_linear_rows(ctx, prob, d);
+    const size_t asc = in.room(2);
+    MRBF_TRY(in.rc);
+    in.h[asc] = delta, in.h[asc + 1] = omega;
     // the stacked rows over the modelled rows' evaluations at x; one block of (L + 2) x k_j objective values per model with an objective row
     const descent::Offsets con = lay.offsets(1, descent::Slots::CONSTRAINED), objv = lay.offsets(L + 2, descent::Slots::OBJECTIVE);
     const std::vector<RowRef> rows = stacked_rows(lay, con);
@@ -392,18 +389,18 @@ extern "C" int32_t mrbf_sd_step(mrbf_ctx *ctx, const mrbf_ps_problem *prob, cons
     // ---- device arena: inputs | rows table | Jc | Vc | steps | trial rows | objective values | outputs
     const size_t rows_dbl = (rows.size() * sizeof(RowRef) + sizeof(double) - 1) / sizeof(double);
     const size_t out_cnt = (size_t)d + k + ARMIJO_TAIL;
-    const size_t total = h.size() + rows_dbl + jtot + vtot + (L + 1) + 2 + (size_t)(L + 2) * d + otot + out_cnt;
+    const size_t total = in.total + rows_dbl + jtot + vtot + (L + 1) + 2 + (size_t)(L + 2) * d + otot + out_cnt;
     double *base;
     MRBF_TRY(get_buf(ctx, S_SD_STEP, total, &base));
-    double *dRows = base + h.size(), *dJc = dRows + rows_dbl, *dVc = dJc + jtot, *dSteps = dVc + vtot, *dSig = dSteps + (L + 1);
+    double *dRows = base + in.total, *dJc = dRows + rows_dbl, *dVc = dJc + jtot, *dSteps = dVc + vtot, *dSig = dSteps + (L + 1);
     double *dX = dSig + 2, *dV = dX + (size_t)(L + 2) * d, *dOut = dV + otot;
     hipEvent_t e0 = ctx->ev[0], e1 = ctx->ev[1];
     MRBF_HIP(ctx, hipEventRecord(e0, ctx->stream));
-    MRBF_HIP(ctx, hipMemcpyAsync(base, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    MRBF_TRY(in.upload(ctx, base));
     if (!rows.empty())
         MRBF_HIP(ctx, hipMemcpyAsync(dRows, rows.data(), rows.size() * sizeof(RowRef), hipMemcpyHostToDevice, ctx->stream));
-    const double *dxn = base, *dx = base + d, *dlb = base + 2 * d, *dub = base + 3 * d, *ddir = base + 4 * d;
-    const double *dA = base + 5 * d, *db = dA + nlin * d, *ddelta = db + nlin, *domega = ddelta + 1;
+    const double *dxn = in.dev(axn), *dx = in.dev(ax), *dlb = in.dev(alb), *dub = in.dev(aub), *ddir = in.dev(adir);
+    const double *dA = in.dev(aA), *db = in.dev(ab), *ddelta = in.dev(asc), *domega = ddelta + 1;
     // ---- the modelled constraint rows at x (values + Jacobians; the "intersect" branch reads them)
     for (int j = 0; j < prob->n_models; ++j)
         if (lay.has_con[j]) MRBF_TRY(eval_model(ctx, prob->models[j], 1, dx, dVc + con.val[j], dJc + con.jac[j], nullptr));

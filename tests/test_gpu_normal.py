@@ -159,6 +159,40 @@ def test_bit_identity_across_batch_positions_and_runs():
                 assert np.array_equal(a[0], r[i], equal_nan=True), c["idx"]
 
 
+def test_bit_identity_across_pointer_kinds():
+    """One mrbf_normal_direction call with every array in host memory, the same call with every array a device tensor, and once more
+    with n_out and status on the device, the rest in host memory and the duals and iterations NULL: every output given has the same bits."""
+    import torch
+
+    rng = np.random.default_rng(10)
+    N, d = 3, 5
+    lb, ub = -rng.random((N, d)) * 0.9, rng.random((N, d)) * 0.9
+    x = np.zeros((N, d))
+    A = rng.standard_normal((N, 2, d))                                      # one equality row, one inequality row
+    n0 = lb + rng.random((N, d)) * (ub - lb)
+    b = np.einsum("nrd,nd->nr", A, n0) + np.array([0.0, 0.05])
+    host = [np.ascontiguousarray(a) for a in (x, lb, ub, A[:, :1], b[:, :1], A[:, 1:], b[:, 1:])]
+    ctx = _lib.default_context()
+    p = _lib.as_ptr
+
+    def call(kind):
+        outs = [np.empty((N, d)), np.empty(N), np.empty((N, 2)), np.empty(N, dtype=np.int32), np.empty((N, 2), dtype=np.int32)]
+        ins, bufs = host, outs
+        if kind == "device":
+            ins, bufs = [torch.from_numpy(a).cuda() for a in host], [torch.from_numpy(a).cuda() for a in outs]
+        elif kind == "mixed":
+            bufs = [torch.from_numpy(outs[0]).cuda(), outs[1], None, torch.from_numpy(outs[3]).cuda(), None]
+        ctx.check(ctx.lib.mrbf_normal_direction(ctx.h, N, d, 1, 1, *[p(a) for a in ins], *[None if o is None else p(o) for o in bufs]))
+        torch.cuda.synchronize()
+        return [o.cpu().numpy() if isinstance(o, torch.Tensor) else o for o in bufs]
+
+    first = call("host")
+    assert np.all(first[3] == _lib.NS_OK) and np.all(first[1] > 0.0) and np.all(first[4][:, 0] > 0)
+    for kind in ("device", "mixed"):
+        for a, o in zip(first, call(kind)):
+            assert o is None or np.array_equal(a, o, equal_nan=True), kind
+
+
 def two_parabolas(X):
     X = np.atleast_2d(X)
     return np.stack([np.sum((X - 1.0) ** 2, axis=1), np.sum((X + 1.0) ** 2, axis=1)], axis=1)

@@ -156,6 +156,42 @@ def test_bit_identity_across_batch_positions_and_runs():
             assert np.array_equal(a[0], b[i]) and np.array_equal(a[0], s[j]) and np.array_equal(a[0], r[i]), c["idx"]
 
 
+def test_bit_identity_across_pointer_kinds():
+    """One mrbf_sd_direction call with every array in host memory, the same call with every array a device tensor, and once more with
+    d_out and status on the device, the rest in host memory and the duals and iterations NULL: every output given has the same bits."""
+    import torch
+
+    rng = np.random.default_rng(6)
+    N, d, k = 3, 5, 2
+    lb, ub = -rng.random((N, d)), rng.random((N, d))
+    x = (lb + ub) / 2
+    G = rng.standard_normal((N, k, d))
+    A = rng.standard_normal((N, 2, d))                                      # one equality row, one inequality row
+    lo, hi = descent._sd_box(x, lb, ub)
+    d0 = lo + rng.random((N, d)) * (hi - lo)                                # a feasible direction of every LP
+    b = np.einsum("nrd,nd->nr", A, d0) + np.array([0.0, 0.05])
+    host = [np.ascontiguousarray(a) for a in (np.transpose(G, (0, 2, 1)), x, lb, ub, A[:, :1], b[:, :1], A[:, 1:], b[:, 1:])]
+    ctx = _lib.default_context()
+    p = _lib.as_ptr
+
+    def call(kind):
+        outs = [np.empty((N, d)), np.empty(N), np.empty((N, k + 2)), np.empty(N, dtype=np.int32), np.empty((N, 2), dtype=np.int32)]
+        ins, bufs = host, outs
+        if kind == "device":
+            ins, bufs = [torch.from_numpy(a).cuda() for a in host], [torch.from_numpy(a).cuda() for a in outs]
+        elif kind == "mixed":
+            bufs = [torch.from_numpy(outs[0]).cuda(), outs[1], None, torch.from_numpy(outs[3]).cuda(), None]
+        ctx.check(ctx.lib.mrbf_sd_direction(ctx.h, N, d, k, 1, 1, *[p(a) for a in ins], 1, *[None if o is None else p(o) for o in bufs]))
+        torch.cuda.synchronize()
+        return [o.cpu().numpy() if isinstance(o, torch.Tensor) else o for o in bufs]
+
+    first = call("host")
+    assert np.all(first[3] == _lib.SD_OK) and np.all(np.isfinite(first[0])) and np.all(first[4][:, 0] > 0)
+    for kind in ("device", "mixed"):
+        for a, o in zip(first, call(kind)):
+            assert o is None or np.array_equal(a, o, equal_nan=True), kind
+
+
 def two_parabolas(X):
     X = np.atleast_2d(X)
     return np.stack([np.sum((X - 1.0) ** 2, axis=1), np.sum((X + 1.0) ** 2, axis=1)], axis=1)

@@ -10,9 +10,13 @@
 #include <cstring>
 #include <vector>
 
+#include "../morbit.jl_amd/csrc/descent_call_host.hpp"
 #include "../morbit.jl_amd/csrc/ds_host.hpp"
 
 using namespace mrbf::ds;
+using mrbf::dcall::WS_LIMIT_BYTES;
+// QPs per launch, as ds::launch asks for them
+static int64_t chunk(int64_t n_qp, int d) { return mrbf::dcall::chunk(n_qp, ws_bytes(d)); }
 
 static long g_cases = 0;
 static int g_failed = 0;
