@@ -911,6 +911,40 @@ int32_t mrbf_sd_iterate_batch(mrbf_ctx *ctx, int64_t n_starts, const mrbf_ps_pro
                               int32_t normalize, const mrbf_sd_step_options *opts, double *d_out, double *x_plus, double *mx_plus,
                               mrbf_sd_batch_record *records, float *ms_total);
 
+/* ---- many-start directed search: one call for a batch of starts (ds_batch.hip) -------------------------------------------------
+ * The criticality of directed search (src/descent.jl:583-664) followed by its step (descent.jl:645-660: the steepest-descent step on
+ * the normalised direction) for n_starts independent starts of one problem -- the reference's Threads.@threads loop over starts
+ * (examples/large_scale_benchmarks.jl:102-109) -- as one chain on the ctx stream with one upload and one read-back.  For start p the
+ * outputs are, bit for bit, those of this chain on start p's container (the roles table of `shape` with row p of `models`: n_starts
+ * x shape->n_models handles, start-major; shape->models is ignored; no linear and no modelled constraints):
+ *   mrbf_ds_criticality(x_n_p, lb, ub, r_p) -> (omega, d, status, mu);
+ *   the bindings' rule: (omega, d / ||d||_inf) if status = MRBF_DS_OK and ||d||_inf > 0, else (0, zeros);
+ *   mrbf_sd_step(x_p, x_n_p, delta_p, lb, ub, omega', d', opts) -> x+, m(x+) and the step info.
+ * The starts share d, the model count, every model slot's output count and the roles; the number of centres and the kernel parameters
+ * may differ between starts.  x, x_n: n_starts x d; delta: n_starts; lb / ub (d): the one MOP's global bounds; r: n_starts x
+ * n_objectives, the target change of the model values per start; d_out (the normalised direction d'), x_plus: n_starts x d; mx_plus:
+ * n_starts x n_objectives; mult_out (mu; may be NULL): n_starts x n_objectives.  Every array may be a host or a device pointer, records
+ * is host memory; ms_total may be NULL.  CRITICAL / INFEASIBLE starts take the step on (0, zeros): x+ = x_n (the record's omega is 0 /
+ * -Inf, the QP's).  MRBF_DS_GAVE_UP: that start's record carries the status, its d_out, x_plus, mx_plus and mult_out rows are NaN (take
+ * the host method for it); the other starts are unaffected.  Every start gets a record.  Returns 0, or: -1 no context; -2 (take the
+ * single calls per start) when mrbf_dispatch_ds_batch refuses the shape; -3 NULL shape, no models, no roles table or a defect of the
+ * table; -4 NULL models or a defect of the handles; -5 .. -10 NULL x, x_n, delta, lb, ub, r; -11 NULL opts or shrink outside (0, 1);
+ * -12 .. -15 NULL d_out, x_plus, mx_plus, records.  Nothing is written on a negative code. */
+typedef struct {
+    int32_t ds_status;           /* MRBF_DS_* of this start's direction QP */
+    int32_t iterations, dropped; /* as mrbf_ds_info */
+    int32_t branch, loops;       /* as mrbf_sd_step_info */
+    int32_t reserved;
+    double omega;                /* the QP's omega (what mrbf_ds_criticality reports) */
+    double omega_step;           /* what the step returns */
+    double sigma, step_norm;
+    double dnorm;                /* ||d||_inf of the QP's d before normalisation (0 unless the status is MRBF_DS_OK) */
+} mrbf_ds_batch_record;          /* 64 bytes */
+int32_t mrbf_ds_iterate_batch(mrbf_ctx *ctx, int64_t n_starts, const mrbf_ps_problem *shape, const mrbf_model *const *models,
+                              const double *x, const double *x_n, const double *delta, const double *lb, const double *ub,
+                              const double *r, const mrbf_sd_step_options *opts, double *d_out, double *x_plus, double *mx_plus,
+                              double *mult_out, mrbf_ds_batch_record *records, float *ms_total);
+
 /* ---- many-start normal step: one call for a batch of starts (normal_batch.hip) -------------------------------------------------
  * compute_normal_step (src/descent.jl:691-757) for n_starts independent starts of one problem -- the reference's Threads.@threads loop
  * over starts (examples/large_scale_benchmarks.jl:102-109) -- as one chain on the ctx stream with one read-back.  For start p n_out,
@@ -1002,6 +1036,9 @@ int32_t mrbf_ps_step_batch(mrbf_ctx *ctx, int64_t n_starts, const mrbf_ps_proble
  *   mrbf_dispatch_sd_batch   the two calls above for n_starts starts in one (mrbf_sd_iterate_batch): device iff mrbf_dispatch_sd
  *                            and mrbf_dispatch_sd_step both say so, d <= 256 (the fused evaluation kernels' range) and
  *                            1 <= n_starts <= 65535 (a grid dimension).
+ *   mrbf_dispatch_ds_batch   the criticality and the step of directed search for n_starts starts in one call (mrbf_ds_iterate_batch):
+ *                            device iff mrbf_dispatch_ds and mrbf_dispatch_sd_step both say so, d <= 256 (the fused evaluation
+ *                            kernels' range) and 1 <= n_starts <= 65535 (a grid dimension).
  *   mrbf_dispatch_normal_batch  compute_normal_step for n_starts starts in one call (mrbf_normal_step_batch): device iff
  *                            mrbf_dispatch_normal says so, 1 <= n_starts <= 65535 (a grid dimension) and, where modelled rows are
  *                            evaluated (n_nl > 0), d <= 256 (the fused evaluation kernels' range); linear rows alone keep d <= 4096.
@@ -1053,7 +1090,7 @@ enum { MRBF_ENTRY_ROUND4 = 1, MRBF_ENTRY_FIT_FROM_ROUND4 = 2, MRBF_ENTRY_PS_STEP
        MRBF_ENTRY_FIT_BATCH = 11, MRBF_ENTRY_NORMAL_BATCH = 12, MRBF_ENTRY_ROUND4_BATCH = 13, MRBF_ENTRY_PS_BATCH = 14,
        MRBF_ENTRY_DB_BOX = 15, MRBF_ENTRY_DB_GATHER = 16, MRBF_ENTRY_DB_ROUND3 = 17, MRBF_ENTRY_DB_APPEND_BATCH = 18,
        MRBF_ENTRY_DB_SET_VALUES_BATCH = 19, MRBF_ENTRY_EVAL_BATCH = 20, MRBF_ENTRY_HESSIAN_BATCH = 21,
-       MRBF_ENTRY_DS = 22 };
+       MRBF_ENTRY_DS = 22, MRBF_ENTRY_DS_BATCH = 23 };
 int32_t mrbf_dispatch_ps(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_ps_batch(int64_t n_starts, int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints,
                                int32_t n_lin_constraints, int32_t n_foreign);
@@ -1063,6 +1100,8 @@ int32_t mrbf_dispatch_normal(int32_t d, int32_t n_models, int32_t n_nl_constrain
 int32_t mrbf_dispatch_sd_step(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign,
                               int32_t max_loops);
 int32_t mrbf_dispatch_sd_batch(int64_t n_starts, int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints,
+                               int32_t n_lin_constraints, int32_t n_foreign, int32_t max_loops);
+int32_t mrbf_dispatch_ds_batch(int64_t n_starts, int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints,
                                int32_t n_lin_constraints, int32_t n_foreign, int32_t max_loops);
 int32_t mrbf_dispatch_normal_batch(int64_t n_starts, int32_t d, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints,
                                    int32_t n_foreign);

@@ -100,6 +100,7 @@ ENTRY_DB_SET_VALUES_BATCH = 19
 ENTRY_EVAL_BATCH = 20
 ENTRY_HESSIAN_BATCH = 21
 ENTRY_DS = 22
+ENTRY_DS_BATCH = 23
 R3_UPDATE, R3_IMPROVE = 0, 1
 R3_DONE, R3_REBUILT = 0, 1
 SD_OK, SD_NO_OBJECTIVE, SD_INFEASIBLE, SD_GAVE_UP = 0, 1, 2, 3
@@ -158,6 +159,16 @@ class SdBatchRecord(ctypes.Structure):
     _fields_ = [("sd_status", ctypes.c_int32), ("iterations", ctypes.c_int32), ("bound_flips", ctypes.c_int32), ("branch", ctypes.c_int32),
                 ("loops", ctypes.c_int32), ("reserved", ctypes.c_int32), ("omega", ctypes.c_double), ("omega_step", ctypes.c_double),
                 ("sigma", ctypes.c_double), ("step_norm", ctypes.c_double)]
+
+    def asdict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class DsBatchRecord(ctypes.Structure):
+    """mrbf_ds_batch_record: one start of mrbf_ds_iterate_batch"""
+    _fields_ = [("ds_status", ctypes.c_int32), ("iterations", ctypes.c_int32), ("dropped", ctypes.c_int32), ("branch", ctypes.c_int32),
+                ("loops", ctypes.c_int32), ("reserved", ctypes.c_int32), ("omega", ctypes.c_double), ("omega_step", ctypes.c_double),
+                ("sigma", ctypes.c_double), ("step_norm", ctypes.c_double), ("dnorm", ctypes.c_double)]
 
     def asdict(self):
         return {f: getattr(self, f) for f, _ in self._fields_}
@@ -354,6 +365,10 @@ SIGNATURES = {
                                                c_vp, c_vp, ctypes.c_int32, ctypes.POINTER(SdStepOptions), c_vp, c_vp, c_vp,
                                                ctypes.POINTER(SdBatchRecord), c_fp]),
     "mrbf_dispatch_sd_batch": (ctypes.c_int32, [ctypes.c_int64] + [ctypes.c_int32] * 7),
+    "mrbf_ds_iterate_batch": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.POINTER(PsProblem), ctypes.POINTER(ctypes.c_void_p), c_vp, c_vp, c_vp,
+                                               c_vp, c_vp, c_vp, ctypes.POINTER(SdStepOptions), c_vp, c_vp, c_vp, c_vp,
+                                               ctypes.POINTER(DsBatchRecord), c_fp]),
+    "mrbf_dispatch_ds_batch": (ctypes.c_int32, [ctypes.c_int64] + [ctypes.c_int32] * 7),
     "mrbf_normal_step_batch": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.POINTER(PsProblem), ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
                                                 c_vp, c_vp, c_vp, c_vp, ctypes.c_double, ctypes.c_double, ctypes.c_int32, c_vp, c_vp, c_vp,
                                                 ctypes.POINTER(NormalBatchRecord), c_fp]),

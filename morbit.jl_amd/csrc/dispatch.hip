@@ -104,6 +104,15 @@ int32_t mrbf_dispatch_sd_batch(int64_t n_starts, int32_t d, int32_t k, int32_t n
     return mrbf_dispatch_sd_step(d, k, n_models, n_nl_constraints, n_lin_constraints, n_foreign, max_loops);
 }
 
+// directed search for many starts in one call (ds_batch.hip): what both single calls take, inside the fused evaluation kernels' range
+// (dpad in {64, 128, 256}) and with the start on a grid dimension
+int32_t mrbf_dispatch_ds_batch(int64_t n_starts, int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints,
+                               int32_t n_foreign, int32_t max_loops) {
+    if (n_starts < 1 || n_starts > 65535 || d > 256) return MRBF_DISPATCH_REFERENCE;
+    if (mrbf_dispatch_ds(d, k, n_models, n_nl_constraints, n_lin_constraints, n_foreign) != MRBF_DISPATCH_DEVICE) return MRBF_DISPATCH_REFERENCE;
+    return mrbf_dispatch_sd_step(d, k, n_models, n_nl_constraints, n_lin_constraints, n_foreign, max_loops);
+}
+
 // the normal steps of many starts in one call (normal_batch.hip): what the single call takes, with the start on a grid dimension;
 // modelled rows are evaluated by the fused evaluation kernels (dpad in {64, 128, 256}), linear rows alone need no evaluation
 int32_t mrbf_dispatch_normal_batch(int64_t n_starts, int32_t d, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints,
@@ -238,6 +247,7 @@ int32_t mrbf_dispatch_after(int32_t entry, int32_t rc) {
         case MRBF_ENTRY_EVAL_BATCH: return rc == -2;  // the table refuses the job count: mrbf_eval per job; a job's own status is an error
         case MRBF_ENTRY_HESSIAN_BATCH: return rc == -2;  // likewise: mrbf_eval_hessian per job; a job's own status is an error
         case MRBF_ENTRY_DS: return rc == -2;  // shape outside the device path, or the QP gave up (MRBF_DS_GAVE_UP)
+        case MRBF_ENTRY_DS_BATCH: return rc == -2;  // shape outside the device path; a start whose QP gave up says so in its record, not in rc
         default: return 0;
     }
 }

@@ -1160,6 +1160,15 @@ def _ds_image_direction(cfg, sc, scal, x, x_n, fx_n, delta, lb, ub, rng, stats):
     return ideal - fx_n
 
 
+def _ds_normalise(omega, d, status, n):
+    """what the step is given of a direction QP's (omega, d, status) (descent.jl:647-660): (omega, d / ||d||_inf), or (0, zeros) when
+    the status is not OK or ||d||_inf = 0 -- the rule ds_scale_kernel applies on the device for mrbf_ds_iterate_batch"""
+    nrm = float(np.max(np.abs(d))) if status == _lib.DS_OK and d.size else 0.0
+    if status != _lib.DS_OK or not nrm > 0:
+        return 0.0, np.zeros(n)
+    return float(omega), d / nrm
+
+
 def get_criticality_ds(cfg, sc, scal, x, x_n, fx_n, delta, lb, ub, lin=None, stats=None, rng=None):
     """The criticality of directed search (descent.jl:583-660 up to the backtracking) as HipRbf.jl's `hip_get_criticality_ds` routes it:
     the image direction r from the configuration (`_get_global_dir` / `compute_local_ideal_point`), then mrbf_dispatch_ds decides,
@@ -1177,10 +1186,7 @@ def get_criticality_ds(cfg, sc, scal, x, x_n, fx_n, delta, lb, ub, lin=None, sta
     r = _ds_image_direction(cfg, sc, scal, x, x_n, fx_n, delta, lb, ub, rng, stats)
 
     def result(omega, d, status):
-        nrm = float(np.max(np.abs(d))) if status == _lib.DS_OK and d.size else 0.0
-        if status != _lib.DS_OK or not nrm > 0:
-            return 0.0, np.zeros(n)
-        return float(omega), d / nrm
+        return _ds_normalise(omega, d, status, n)
 
     if lib.mrbf_dispatch_ds(n, plan["k"], len(plan["models"]), plan["n_con"], n_lin, plan["n_foreign"]) == _lib.DISPATCH_DEVICE:
         rc, omega, d, info = ds_criticality_device(plan, x_n, lb, ub, r)
@@ -1206,3 +1212,85 @@ def compute_descent_step_ds(cfg, sc, scal, x, x_n, delta, lb, ub, omega, d, lin=
     Armijo sweep -- `compute_descent_step_sd_routed` on (omega, d) of `get_criticality_ds`, no step code of its own.  Returns
     (omega, x_plus, mx_plus, ||step||_inf)."""
     return compute_descent_step_sd_routed(cfg, sc, scal, x, x_n, delta, lb, ub, omega, d, lin, stats)
+
+
+# ---- many starts in one device call (mrbf_ds_iterate_batch): the reference's Threads.@threads loop over starts ---------------------
+def ds_iterate_batch_device(plans, cfg, X, X_n, deltas, lb, ub, R, out=None):
+    """one mrbf_ds_iterate_batch call on the containers' plans (one shape, checked by the caller); X, X_n (n_starts x d), deltas, lb,
+    ub, R (n_starts x k: the image direction per start) may be NumPy arrays or device tensors; out = (d, x_plus, mx_plus, mu) lets the
+    caller pass its own output buffers (host or device).  Returns (rc, d, x_plus, mx_plus, mu, list of record dicts with "branch_name",
+    event ms)."""
+    ctx = plans[0]["models"][0].ctx
+    ns, k = len(plans), plans[0]["k"]
+    X, X_n, deltas, lb, ub, R = _arr(X), _arr(X_n), _arr(deltas), _arr(lb), _arr(ub), _arr(R)
+    n = int(lb.numel() if hasattr(lb, "numel") else lb.size)
+    prob, keep = _sd_problem(plans[0], (None,) * 4)
+    handles = _handles(plans)
+    dd, xp, mxp, mu = out if out is not None else (np.empty((ns, n)), np.empty((ns, n)), np.empty((ns, k)), np.empty((ns, k)))
+    opts = _step_options(cfg)
+    recs = (_lib.DsBatchRecord * ns)()
+    ms = ctypes.c_float()
+    rc = ctx.lib.mrbf_ds_iterate_batch(ctx.h, ns, ctypes.byref(prob), handles, _lib.as_ptr(X), _lib.as_ptr(X_n), _lib.as_ptr(deltas),
+                                       _lib.as_ptr(lb), _lib.as_ptr(ub), _lib.as_ptr(R), ctypes.byref(opts), _lib.as_ptr(dd),
+                                       _lib.as_ptr(xp), _lib.as_ptr(mxp), _lib.as_ptr(mu), recs, ctypes.byref(ms))
+    records = []
+    for r in recs:
+        rd = r.asdict()
+        rd["branch_name"] = _SD_BRANCHES[r.branch] if rc == 0 and 0 <= r.branch < 3 else None
+        records.append(rd)
+    return rc, dd, xp, mxp, mu, records, ms.value
+
+
+def ds_iterate_many(cfg, containers, scal, X, X_n, FX_n, deltas, lb, ub, lin=None, stats=None, rng=None):
+    """`get_criticality_ds` then `compute_descent_step_ds` (descent.jl:583-664) for many independent starts of one problem -- the
+    reference's `Threads.@threads` loop over starts (examples/large_scale_benchmarks.jl:102-109): containers[p] is start p's surrogate
+    container, X[p] / X_n[p] / FX_n[p] / deltas[p] its iterate, normal-step iterate, values there and radius; lb / ub and lin belong to
+    the one MOP.  The image direction r comes per start from `_ds_image_direction`: arithmetic with a reference direction or point,
+    else the per-start ideal-point search (stats["image_direction"] says which: "reference_direction", "reference_point" or
+    "ideal_point").  Where the containers share one plan shape and mrbf_dispatch_ds_batch says so, ONE mrbf_ds_iterate_batch call serves
+    all starts ("batch"); otherwise (a refused shape, constraints, mixed shapes), and for every start whose direction QP gave up, the
+    routed single-start functions run.  Returns a list of (omega, d, x_plus, mx_plus, ||step||_inf); stats gets "path" ("batch" or
+    "loop"), "rerouted" (the starts that took the single-start functions after a batch call), "records" and "ms_total"."""
+    lib = _lib.load()
+    X, X_n = np.asarray(X, dtype=np.float64), np.asarray(X_n, dtype=np.float64)
+    FX_n = np.asarray(FX_n, dtype=np.float64)
+    deltas = np.asarray(deltas, dtype=np.float64).ravel()
+    ns = len(containers)
+    lin = lin or (None,) * 4
+    n_lin = sum(0 if b is None else int(np.asarray(b).size) for b in (lin[1], lin[3]))
+
+    def single(p):
+        omega, d = get_criticality_ds(cfg, containers[p], scal, X[p], X_n[p], FX_n[p], float(deltas[p]), lb, ub, lin, rng=rng)
+        om, xp, mxp, nrm = compute_descent_step_ds(cfg, containers[p], scal, X[p], X_n[p], float(deltas[p]), lb, ub, omega, d, lin)
+        return om, d, xp, mxp, nrm
+
+    if stats is not None:
+        stats["path"], stats["rerouted"] = "loop", []
+        stats["image_direction"] = ("reference_direction" if len(cfg.reference_direction)        # the order of ps._get_global_dir
+                                    else "reference_point" if len(cfg.reference_point) else "ideal_point")
+    if ns == 0:
+        return []
+    plans = [sg.container_plan(sc) for sc in containers]
+    n = int(X_n.shape[1])
+    p0 = plans[0]
+    if _same_plan_shape(plans) and lib.mrbf_dispatch_ds_batch(ns, n, p0["k"], len(p0["models"]), p0["n_con"], n_lin, p0["n_foreign"],
+                                                              int(cfg.max_loops)) == _lib.DISPATCH_DEVICE:
+        R = np.stack([_ds_image_direction(cfg, containers[p], scal, X[p], X_n[p], FX_n[p], float(deltas[p]), lb, ub, rng, None)
+                      for p in range(ns)])
+        rc, dd, xp, mxp, mu, records, ms = ds_iterate_batch_device(plans, cfg, X, X_n, deltas, lb, ub, R)
+        if rc == 0:
+            res, rerouted = [], []
+            for p, r in enumerate(records):
+                if r["ds_status"] == _lib.DS_GAVE_UP:          # this start's QP gave up: the host method for it alone
+                    rerouted.append(p)
+                    res.append(single(p))
+                elif not r["sigma"] > cfg.min_stepsize:        # descent.jl:317: the reference returns integer zeros here
+                    res.append((0, dd[p].copy(), xp[p].copy(), mxp[p].copy(), 0))
+                else:
+                    res.append((r["omega_step"], dd[p].copy(), xp[p].copy(), mxp[p].copy(), r["step_norm"]))
+            if stats is not None:
+                stats.update(path="batch", rerouted=rerouted, records=records, ms_total=ms)
+            return res
+        if not lib.mrbf_dispatch_after(_lib.ENTRY_DS_BATCH, rc):
+            p0["models"][0].ctx.check(rc)
+    return [single(p) for p in range(ns)]

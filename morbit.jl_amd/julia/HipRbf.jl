@@ -72,6 +72,11 @@ struct MrbfSdBatchRecord    # mirrors mrbf_sd_batch_record, 56 bytes
     omega::Float64; omega_step::Float64; sigma::Float64; step_norm::Float64
 end
 
+struct MrbfDsBatchRecord    # mirrors mrbf_ds_batch_record, 64 bytes
+    ds_status::Int32; iterations::Int32; dropped::Int32; branch::Int32; loops::Int32; reserved::Int32
+    omega::Float64; omega_step::Float64; sigma::Float64; step_norm::Float64; dnorm::Float64
+end
+
 struct MrbfNormalBatchRecord    # mirrors mrbf_normal_batch_record, 32 bytes
     status::Int32; iterations::Int32; bound_flips::Int32; reserved::Int32
     alpha::Float64; delta::Float64
@@ -305,6 +310,9 @@ _dispatch_sd_step(d, k, n_models, n_nl, n_lin, n_foreign, max_loops) =
           d, k, n_models, n_nl, n_lin, n_foreign, max_loops) == 1
 _dispatch_sd_batch(n_starts, d, k, n_models, n_nl, n_lin, n_foreign, max_loops) =
     ccall((:mrbf_dispatch_sd_batch, libmrbf), Int32, (Int64, Int32, Int32, Int32, Int32, Int32, Int32, Int32),
+          n_starts, d, k, n_models, n_nl, n_lin, n_foreign, max_loops) == 1
+_dispatch_ds_batch(n_starts, d, k, n_models, n_nl, n_lin, n_foreign, max_loops) =
+    ccall((:mrbf_dispatch_ds_batch, libmrbf), Int32, (Int64, Int32, Int32, Int32, Int32, Int32, Int32, Int32),
           n_starts, d, k, n_models, n_nl, n_lin, n_foreign, max_loops) == 1
 _dispatch_normal_batch(n_starts, d, n_models, n_nl, n_lin, n_foreign) =
     ccall((:mrbf_dispatch_normal_batch, libmrbf), Int32, (Int64, Int32, Int32, Int32, Int32, Int32),
@@ -1331,6 +1339,75 @@ function hip_sd_iterate_many(desc_cfg::SteepestDescentConfig, mop, scal, x_its::
         r.sigma > desc_cfg.min_stepsize ||
             return 0, Xet.(dirs[:, p]), copy(get_x_scaled(x_it_ns[p])), Xet.(MX₊[:, p]), 0    # descent.jl:317
         (Xet(r.omega), Xet.(dirs[:, p]), Xet.(X₊[:, p]), Xet.(MX₊[:, p]), Xet(r.step_norm))
+    end
+end
+
+"""
+Directed search for many starts in one device call (`mrbf_ds_iterate_batch`): `hip_get_criticality_ds` followed by
+`hip_compute_descent_step` for independent starts of one problem -- the `Threads.@threads` loop over starts of
+examples/large_scale_benchmarks.jl:102-109 -- as one chain of launches and one read-back.  `x_its[p]`, `x_it_ns[p]` and `scs[p]` are
+start p's iterate, normal-step iterate and surrogate container; `mop`, `scal` and the configuration belong to the one problem.  The
+image direction r is formed per start (`_ds_image_direction`).  For every start the result is, bit for bit, what the two single-start
+functions return on that start alone.  Where the containers do not share one plan shape, the decision table refuses
+(`mrbf_dispatch_ds_batch`: a foreign surrogate, constraints, d > 256, more than 16 objectives, more than 65535 starts) or a start's
+direction QP gave up, those starts take the two single-start functions.  Returns a vector of (ω, d, x₊, mx₊, ‖step‖∞).
+"""
+function hip_ds_iterate_many(desc_cfg::HipDirectedSearchConfig, mop, scal, x_its::AbstractVector, x_it_ns::AbstractVector, data_base,
+                             scs::AbstractVector{<:SurrogateContainer}, algo_config)
+    step_cfg = _ds_step_config(desc_cfg)
+    function single(p)
+        ω, d = hip_get_criticality_ds(desc_cfg, mop, scal, x_its[p], x_it_ns[p], data_base, scs[p], algo_config)
+        ω₊, x₊, mx₊, nrm = hip_compute_descent_step(step_cfg, mop, scal, x_its[p], x_it_ns[p], data_base, scs[p], algo_config, ω, d)
+        return ω₊, d, x₊, mx₊, nrm
+    end
+    loop() = [single(p) for p in eachindex(scs)]
+    ns = length(scs)
+    (ns >= 1 && all(_touches_device, scs)) || return loop()
+    plans = [_container_plan(sc) for sc in scs]
+    p1 = plans[1]
+    same = all(pl -> pl.roles == p1.roles && pl.k == p1.k && pl.n_con == p1.n_con && pl.n_foreign == p1.n_foreign &&
+                     length(pl.models) == length(p1.models), plans)
+    same || return loop()
+    n, k, nm = length(get_x_scaled(x_it_ns[1])), p1.k, length(p1.models)
+    A_eq, b_eq = transformed_linear_eq_constraints(scal, mop)
+    A_in, b_in = transformed_linear_ineq_constraints(scal, mop)
+    _dispatch_ds_batch(ns, n, k, nm, p1.n_con, length(b_eq) + length(b_in), p1.n_foreign, desc_cfg.max_loops) || return loop()
+    lb_g, ub_g = full_bounds_internal(scal)
+    lb = Vector{Float64}(lb_g); ub = Vector{Float64}(ub_g)
+    X = Matrix{Float64}(undef, n, ns); X_n = Matrix{Float64}(undef, n, ns)     # column p = start p: the n_starts x d row-major array
+    R = Matrix{Float64}(undef, k, ns)
+    for p in 1:ns
+        X[:, p] .= get_x_scaled(x_its[p]); X_n[:, p] .= get_x_scaled(x_it_ns[p])
+        R[:, p] .= _ds_image_direction(desc_cfg, mop, scal, x_its[p], x_it_ns[p], scs[p])
+    end
+    Δ = Float64[get_delta(x_it) for x_it in x_its]
+    opts = Ref(MrbfSdStepOptions(desc_cfg.strict_backtracking, desc_cfg.max_loops, desc_cfg.armijo_const_rhs, desc_cfg.armijo_const_shrink,
+                                 desc_cfg.min_stepsize))
+    dirs = Matrix{Float64}(undef, n, ns); X₊ = Matrix{Float64}(undef, n, ns); MX₊ = Matrix{Float64}(undef, k, ns)
+    records = Vector{MrbfDsBatchRecord}(undef, ns)
+    ms = Ref{Float32}(0)
+    handles = Ptr{Cvoid}[m.handle for pl in plans for m in pl.models]          # start-major
+    roles = p1.roles
+    ctx = p1.models[1].ctx
+    rc = GC.@preserve handles roles X X_n Δ lb ub R dirs X₊ MX₊ records begin
+        prob = Ref(MrbfPsProblem(nm, k, C_NULL, pointer(roles), 0, 0, C_NULL, C_NULL, C_NULL, C_NULL, -1.0))
+        _locked(ctx) do hctx
+            ccall((:mrbf_ds_iterate_batch, libmrbf), Int32,
+                  (Ptr{Cvoid}, Int64, Ref{MrbfPsProblem}, Ptr{Ptr{Cvoid}}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                   Ptr{Float64}, Ptr{Float64}, Ref{MrbfSdStepOptions}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                   Ptr{MrbfDsBatchRecord}, Ref{Float32}),
+                  hctx, ns, prob, handles, X, X_n, Δ, lb, ub, R, opts, dirs, X₊, MX₊, C_NULL, records, ms)
+        end
+    end
+    rc != 0 && _fallback_rc(23, rc) && return loop()           # a shape outside the device path: the single-start functions
+    _check(ctx, rc)
+    Xet = eltype(get_x_scaled(x_it_ns[1]))
+    return map(1:ns) do p
+        r = records[p]
+        r.ds_status == 3 && return single(p)                   # MRBF_DS_GAVE_UP: the JuMP model for this start alone
+        r.sigma > desc_cfg.min_stepsize ||
+            return 0, Xet.(dirs[:, p]), copy(get_x_scaled(x_it_ns[p])), Xet.(MX₊[:, p]), 0    # descent.jl:317
+        (Xet(r.omega_step), Xet.(dirs[:, p]), Xet.(X₊[:, p]), Xet.(MX₊[:, p]), Xet(r.step_norm))
     end
 end
 
