@@ -789,6 +789,7 @@ int32_t mrbf_sd_criticality(mrbf_ctx *ctx, const mrbf_ps_problem *problem, const
  * invalid arguments: -1 no context, -3 n_qp < 1, -4 d outside 1 .. 4096, -5 k outside 1 .. 16, -6 .. -10 NULL G, r, x, lb, ub,
  * -11 .. -14 NULL d_out, z_out, omega_out, status_out; nothing is written then. */
 enum { MRBF_DS_OK = 0, MRBF_DS_CRITICAL = 1, MRBF_DS_INFEASIBLE = 2, MRBF_DS_GAVE_UP = 3 };
+enum { MRBF_DS_NO_START = 4 };  /* mrbf_ds_direction_rows alone: the start d = 0 misses a constraint row */
 int32_t mrbf_ds_direction(mrbf_ctx *ctx, int64_t n_qp, int32_t d, int32_t k, const double *G, const double *r, const double *x,
                           const double *lb, const double *ub, double *d_out, double *z_out, double *omega_out, double *mult_out,
                           int32_t *status_out, int32_t *iters_out);
@@ -808,6 +809,44 @@ typedef struct {
 } mrbf_ds_info;
 int32_t mrbf_ds_criticality(mrbf_ctx *ctx, const mrbf_ps_problem *problem, const double *x_n, const double *lb, const double *ub,
                             const double *r, double *d_out, double *mult_out, mrbf_ds_info *info);
+
+/* ---- directed search with constraint rows: the extended direction QP on the device (ds_qp_rows.hip) ---------------------------
+ * mrbf_ds_direction_rows solves mrbf_ds_direction's QP extended by the rows of get_criticality (src/descent.jl:196-236) -- what the
+ * parked directed-search step (src/descent.jl:598-645) would be given for a constrained problem -- for n_qp QPs of one shape in one
+ * launch (one workgroup per QP, the same exact fp64 active-set method, generalised):
+ *   minimise 1/2 ||G d - r||_2^2 over d in [l, u] (mrbf_sd_direction's box),  G d <= 0,  A_eq d = b_eq,  A_in d <= b_in;
+ *   1 <= d <= 4096, k >= 1, m_eq >= 0, m_in >= 0, K = k + m_eq + m_in <= 16, n_qp >= 1.
+ * Per QP (consecutive blocks): G, r, x, lb, ub as mrbf_ds_direction takes them; A_eq m_eq x d and A_in m_in x d row-major with b_eq
+ * m_eq and b_in m_in, as mrbf_sd_direction takes them (NULL where the count is 0).  The start d = 0 must satisfy the rows: a miss
+ * |b_eq,i| (or -b_in,i where b_in,i < 0) of at most 1e-10 sum_j |A_ij| is clamped to zero before the solve and the returned d is
+ * feasible for the clamped right-hand side; a larger one ends that QP with MRBF_DS_NO_START (there is no phase 1).  Outputs: d_out (d,
+ * inside [l, u] exactly), c_out (K): W d for W = [G; A_eq; A_in] recomputed from the returned d, objective rows first; omega_out (1):
+ * max(0, -max_i (G d)_i); mult_out (K, may be NULL): mu with mu_i >= 0 on objective and inequality rows and free sign on equality
+ * rows -- with y_i = (G d - r + mu)_i on objective rows, y_i = mu_i on the others and s = W' y the certificate is s_j = 0 on free
+ * variables, s_j >= 0 on the lower and <= 0 on the upper bound, mu_i (h_i - c_i) = 0 for h = (0, b_eq, b_in) --; status_out (1):
+ * MRBF_DS_*; iters_out (2, may be NULL): iterations, constraints dropped.  CRITICAL and INFEASIBLE as mrbf_ds_direction answers
+ * them (c = 0, mult = 0).  GAVE_UP (the iteration cap 8 (d + K) + 16, a failed consistency check -- every row of the returned d holds
+ * within 1e-13 (sum_j |W_ij| + |h_i|) --, or x outside [lb, ub]) and NO_START: d, c, omega, mult = NaN; the bindings take the host
+ * method.  G d, omega and the optimal value are unique; d and the constraint rows' values are not.  With m_eq = m_in = 0 the outputs
+ * are mrbf_ds_direction's, bit for bit.  The same call gives the same bits, whatever the QP's position in the batch.  Every array may
+ * be host or device memory.  The call fails only on invalid arguments: -1 no context, -3 n_qp < 1, -4 d outside 1 .. 4096, -5 k
+ * outside 1 .. 16, -6 m_eq < 0, -7 m_in < 0, -8 k + m_eq + m_in > 16, -9 .. -13 NULL G, r, x, lb, ub, -14 / -15 NULL A_eq / b_eq
+ * with m_eq > 0, -16 / -17 NULL A_in / b_in with m_in > 0, -18 .. -21 NULL d_out, c_out, omega_out, status_out; nothing is written
+ * then. */
+int32_t mrbf_ds_direction_rows(mrbf_ctx *ctx, int64_t n_qp, int32_t d, int32_t k, int32_t m_eq, int32_t m_in, const double *G,
+                               const double *r, const double *x, const double *lb, const double *ub, const double *A_eq,
+                               const double *b_eq, const double *A_in, const double *b_in, double *d_out, double *c_out,
+                               double *omega_out, double *mult_out, int32_t *status_out, int32_t *iters_out);
+/* The criticality of directed search for a container with modelled or linear constraints (src/descent.jl:196-236 for the rows,
+ * :598-645 for the QP), given as an mrbf_ps_problem: values and Jacobians at [x_n; x] through the evaluation kernels, G, A_eq / b_eq
+ * (linear rows, then modelled ones), A_ineq / b_ineq (likewise) by mrbf_sd_criticality's assembly kernel, then ONE
+ * mrbf_ds_direction_rows QP at x_n over the global bounds and one read-back.  d_out (d), mult_out (k + m_eq + m_in, may be NULL, row
+ * order as mrbf_sd_criticality's dual_out) and info are, bit for bit, those of mrbf_ds_direction_rows on these rows.  Returns -2 (take
+ * the host method) when mrbf_dispatch_ds_rows refuses the shape, the QP gave up or d = 0 is no start (info->status = MRBF_DS_GAVE_UP /
+ * MRBF_DS_NO_START: with a normal step n != 0 the modelled rows' right-hand side -m(x_n) - Dm(x) n is not small in general); -1 no
+ * context, -3 .. -9 NULL problem, x, x_n, lb, ub, r, d_out, -11 NULL info. */
+int32_t mrbf_ds_criticality_rows(mrbf_ctx *ctx, const mrbf_ps_problem *problem, const double *x, const double *x_n, const double *lb,
+                                 const double *ub, const double *r, double *d_out, double *mult_out, mrbf_ds_info *info);
 
 /* ---- the normal step: its LP on the device (normal_lp.hip) ----------------------------------------------------------------
  * mrbf_normal_direction replaces the JuMP / OSQP model of compute_normal_step (src/descent.jl:691-757) for n_lp LPs of one shape
@@ -1028,6 +1067,9 @@ int32_t mrbf_ps_step_batch(mrbf_ctx *ctx, int64_t n_starts, const mrbf_ps_proble
  *   mrbf_dispatch_ds         the criticality of directed search (src/descent.jl:583-664, mrbf_ds_criticality): device iff no foreign
  *                            surrogate, at least one device model, 1 <= d <= 4096, 1 <= k <= 16 and neither modelled nor linear
  *                            constraints -- the formulation the reference wrote down; with constraint rows the host method runs.
+ *   mrbf_dispatch_ds_rows    the criticality of directed search for a container with constraint rows (src/descent.jl:196-236,
+ *                            :598-645, mrbf_ds_criticality_rows): device iff no foreign surrogate, at least one device model,
+ *                            1 <= d <= 4096, k >= 1, at least one constraint row and k + n_nl + n_lin <= 16 rows.
  *   mrbf_dispatch_normal     compute_normal_step (src/descent.jl:691-757): device iff no modelled constraint row sits on a
  *                            foreign surrogate, 1 <= d <= 4096 and 1 <= n_nl + n_lin <= 64 LP rows (n_models may be 0).
  *   mrbf_dispatch_sd_step    compute_descent_step(::SteepestDescentConfig, ...) (src/descent.jl:243-318, _backtrack :150-185,
@@ -1091,11 +1133,14 @@ enum { MRBF_ENTRY_ROUND4 = 1, MRBF_ENTRY_FIT_FROM_ROUND4 = 2, MRBF_ENTRY_PS_STEP
        MRBF_ENTRY_DB_BOX = 15, MRBF_ENTRY_DB_GATHER = 16, MRBF_ENTRY_DB_ROUND3 = 17, MRBF_ENTRY_DB_APPEND_BATCH = 18,
        MRBF_ENTRY_DB_SET_VALUES_BATCH = 19, MRBF_ENTRY_EVAL_BATCH = 20, MRBF_ENTRY_HESSIAN_BATCH = 21,
        MRBF_ENTRY_DS = 22, MRBF_ENTRY_DS_BATCH = 23 };
+enum { MRBF_ENTRY_DS_ROWS = 24 };
 int32_t mrbf_dispatch_ps(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_ps_batch(int64_t n_starts, int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints,
                                int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_sd(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_ds(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
+int32_t mrbf_dispatch_ds_rows(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints,
+                              int32_t n_foreign);
 int32_t mrbf_dispatch_normal(int32_t d, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_sd_step(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign,
                               int32_t max_loops);

@@ -101,11 +101,13 @@ ENTRY_EVAL_BATCH = 20
 ENTRY_HESSIAN_BATCH = 21
 ENTRY_DS = 22
 ENTRY_DS_BATCH = 23
+ENTRY_DS_ROWS = 24
 R3_UPDATE, R3_IMPROVE = 0, 1
 R3_DONE, R3_REBUILT = 0, 1
 SD_OK, SD_NO_OBJECTIVE, SD_INFEASIBLE, SD_GAVE_UP = 0, 1, 2, 3
 NS_OK, NS_INFEASIBLE, NS_GAVE_UP = 0, 1, 2
 DS_OK, DS_CRITICAL, DS_INFEASIBLE, DS_GAVE_UP = 0, 1, 2, 3
+DS_NO_START = 4
 DS_MAXD, DS_MAXK = 4096, 16
 SD_BRANCH_DELTA, SD_BRANCH_ONE, SD_BRANCH_INTERSECT = 0, 1, 2
 
@@ -356,6 +358,10 @@ SIGNATURES = {
     "mrbf_ds_direction": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32] + [c_vp] * 11),
     "mrbf_ds_criticality": (ctypes.c_int32, [c_vp, ctypes.POINTER(PsProblem), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(DsInfo)]),
     "mrbf_dispatch_ds": (ctypes.c_int32, [ctypes.c_int32] * 6),
+    "mrbf_ds_direction_rows": (ctypes.c_int32, [c_vp, ctypes.c_int64] + [ctypes.c_int32] * 4 + [c_vp] * 15),
+    "mrbf_ds_criticality_rows": (ctypes.c_int32, [c_vp, ctypes.POINTER(PsProblem), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                  ctypes.POINTER(DsInfo)]),
+    "mrbf_dispatch_ds_rows": (ctypes.c_int32, [ctypes.c_int32] * 6),
     "mrbf_normal_direction": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32] + [c_vp] * 12),
     "mrbf_normal_step": (ctypes.c_int32, [c_vp, ctypes.POINTER(PsProblem), ctypes.c_int32, c_vp, c_vp, c_vp, ctypes.c_double, ctypes.c_double,
                                           ctypes.c_double, ctypes.c_int32, c_vp, c_vp, ctypes.POINTER(NormalInfo)]),

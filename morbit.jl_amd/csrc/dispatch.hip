@@ -78,6 +78,15 @@ int32_t mrbf_dispatch_ds(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_co
     return n_nl_constraints == 0 && n_lin_constraints == 0 ? MRBF_DISPATCH_DEVICE : MRBF_DISPATCH_REFERENCE;
 }
 
+// the direction QP of directed search with constraint rows (ds_qp_rows.hip; descent.jl:196-236, :598-645): objective and constraint rows
+// share the K x K objects in LDS (K = k + n_nl + n_lin <= 16); without a constraint row mrbf_dispatch_ds is the table to ask
+int32_t mrbf_dispatch_ds_rows(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign) {
+    if (n_foreign != 0 || n_models < 1) return MRBF_DISPATCH_REFERENCE;
+    if (d < 1 || d > 4096 || k < 1 || n_nl_constraints < 0 || n_lin_constraints < 0) return MRBF_DISPATCH_REFERENCE;
+    if ((int64_t)n_nl_constraints + n_lin_constraints < 1) return MRBF_DISPATCH_REFERENCE;
+    return (int64_t)k + n_nl_constraints + n_lin_constraints <= 16 ? MRBF_DISPATCH_DEVICE : MRBF_DISPATCH_REFERENCE;
+}
+
 // the normal-step LP (normal_lp.hip): at most 64 rows (M^-1 lives in LDS), d within the library's limit; linear rows need no model
 int32_t mrbf_dispatch_normal(int32_t d, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign) {
     if (n_foreign != 0 || n_models < 0 || d < 1 || d > 4096 || n_nl_constraints < 0 || n_lin_constraints < 0) return MRBF_DISPATCH_REFERENCE;
@@ -247,6 +256,7 @@ int32_t mrbf_dispatch_after(int32_t entry, int32_t rc) {
         case MRBF_ENTRY_EVAL_BATCH: return rc == -2;  // the table refuses the job count: mrbf_eval per job; a job's own status is an error
         case MRBF_ENTRY_HESSIAN_BATCH: return rc == -2;  // likewise: mrbf_eval_hessian per job; a job's own status is an error
         case MRBF_ENTRY_DS: return rc == -2;  // shape outside the device path, or the QP gave up (MRBF_DS_GAVE_UP)
+        case MRBF_ENTRY_DS_ROWS: return rc == -2;  // likewise, or d = 0 misses a constraint row (MRBF_DS_NO_START)
         case MRBF_ENTRY_DS_BATCH: return rc == -2;  // shape outside the device path; a start whose QP gave up says so in its record, not in rc
         default: return 0;
     }

@@ -764,6 +764,7 @@ DS_RANK_TOL = 1e-12     # a row of M = G_N G_N' whose residual diagonal falls to
 DS_VANISH_TOL = 1e-13   # a step with |dz_i| <= DS_VANISH_TOL (sum_j |G_ij| + |r_i|) in every row has vanished
 DS_DUAL_TOL = 1e-11     # a multiplier violates its sign beyond DS_DUAL_TOL times the magnitudes it was formed from
 DS_FEAS_TOL = 1e-13     # sd_lp.hip's FEAS_TOL: rows g_i . d <= DS_FEAS_TOL sum_j |G_ij|
+DS_START_TOL = 1e-10    # ds_rows_host.hpp's START_TOL: a constraint row that d = 0 misses by DS_START_TOL sum_j |W_ij| is clamped (section 23)
 
 
 @dataclass
@@ -782,20 +783,24 @@ class DirectedSearchConfig:
     min_stepsize: float = 10 * np.finfo(np.float64).eps
     max_loops: int = None
     normalize: bool = True
+    constraint_rows: str = "host"     # "device": a container or problem with constraint rows takes mrbf_ds_criticality_rows
 
     def __post_init__(self):
         assert all(v > 0 for v in self.reference_direction), "The components of the `reference_direction` cannot be negative."
+        assert self.constraint_rows in ("host", "device")
         if self.max_loops is None:  # descent.jl:61-66
             base = self.min_stepsize if self.min_stepsize > 0 else np.finfo(np.float64).eps
             self.max_loops = int(math.floor(math.log(base) / math.log(self.armijo_const_shrink)))
         assert self.armijo_const_rhs > 0
 
 
-def _ds_factor(M, in_s):
+def _ds_factor(M, in_s, max_rank=None):
     """Cholesky of M with pivots taken from the row set S first (largest residual diagonal, lowest index on ties), then from the other
     rows; a row whose residual diagonal is within DS_RANK_TOL M_ii is left out (it depends on the pivoted rows).  A row of S that is
     left out leaves S (in place): the working set stays independent, and the row moves with the pivoted rows of S anyway.  Returns
-    (piv, n_s, L): the pivot rows in order, how many of them lie in S, and L (k x rank) with M[piv, piv] = L[piv] L[piv]'."""
+    (piv, n_s, L): the pivot rows in order, how many of them lie in S, and L (k x rank) with M[piv, piv] = L[piv] L[piv]'.  max_rank
+    (the rows method's count of free variables) ends the pivoting: the rank of W_N is at most |N|, whatever
+    rounding leaves on a residual diagonal."""
     k = M.shape[0]
     dg = np.diag(M).copy()
     tol = DS_RANK_TOL * np.diag(M)
@@ -807,7 +812,7 @@ def _ds_factor(M, in_s):
             for i in range(k):
                 if not done[i] and bool(in_s[i]) == phase and dg[i] > tol[i] and dg[i] > bv:
                     best, bv = i, dg[i]
-            if best < 0:
+            if best < 0 or len(piv) == max_rank:
                 break
             c = len(piv)
             L[best, c] = math.sqrt(dg[best])
@@ -828,11 +833,11 @@ def _ds_factor(M, in_s):
     return piv, n_s, L
 
 
-def _ds_step_coeffs(M, in_s, z, rho):
+def _ds_step_coeffs(M, in_s, z, rho, max_rank=None):
     """a (k) with the minimum-norm step p_N = G_N' a: dz = M a has dz_S = -z_S (the rows of S stay on zero) and is nearest to rho on
     the other rows.  Returns (a, factor) or (None, factor) where the small normal equations break down."""
     k = M.shape[0]
-    piv, n_s, L = fac = _ds_factor(M, in_s)
+    piv, n_s, L = fac = _ds_factor(M, in_s, max_rank)
     rank = len(piv)
     c = np.zeros(rank)
     for a in range(n_s):
@@ -1045,6 +1050,170 @@ def _ds_active_set(G, r, lo, hi, stats=None):
     return d, z, max(0.0, -float(np.max(z))), mu, _lib.DS_OK
 
 
+def _ds_rows_start(W, k, m_eq, h):
+    """the start rule of the QP with constraint rows: d = 0 must satisfy the rows.  A residual of the start
+    within DS_START_TOL sum_j |W_ij| -- |b_eq,i|, or -b_in,i where b_in,i < 0 -- is clamped to zero (in place); returns False where
+    one is larger."""
+    rowsum = np.abs(W).sum(axis=1)
+    for i in range(k, W.shape[0]):
+        miss = abs(h[i]) if i < k + m_eq else -h[i]
+        if not miss <= 0.0:       # a miss, or a NaN
+            if not miss <= DS_START_TOL * rowsum[i]:
+                return False
+            h[i] = 0.0
+    return True
+
+
+def _ds_active_set_rows(G, r, lo, hi, A_eq, b_eq, A_in, b_in, stats=None):
+    """The direction QP of directed search with constraint rows, min 1/2 ||G d - r||^2 over lo <= d <= hi, G d <= 0, A_eq d = b_eq,
+    A_in d <= b_in (descent.jl:196-236, :598-645), by the active-set method of `_ds_active_set` generalised as ds_qp_rows.hip runs it
+    (DESIGN.md section 23).  W = [G; A_eq; A_in] (K rows), c = W d, h = (0, b_eq, b_in).  The step is p_N = W_N' a with a supported on
+    the universe U = (objective rows) + S: the k x k work of `_ds_active_set` runs on M[U, U], the rows of S move to their right-hand
+    side (dc_S = h_S - c_S), the objective rows outside S towards rho = r - z.  Equality rows start in S and are never dropped; one
+    that the factorisation leaves out as dependent on the free variables blocks any step that would move it (either sign) and joins
+    S again through the ratio test, as a row of the other kinds does, so that multipliers and steps always belong to one working set.
+    Without constraint rows every operation is `_ds_active_set`'s: the same bits.  Returns (d, c, omega, mu, status); c and mu have K
+    entries, objective rows first."""
+    G = np.asarray(G, dtype=np.float64)
+    k, n = G.shape
+    r = np.asarray(r, dtype=np.float64)
+    A_eq = np.zeros((0, n)) if A_eq is None or np.asarray(b_eq).size == 0 else np.asarray(A_eq, dtype=np.float64).reshape(-1, n)
+    A_in = np.zeros((0, n)) if A_in is None or np.asarray(b_in).size == 0 else np.asarray(A_in, dtype=np.float64).reshape(-1, n)
+    m_eq, m_in = A_eq.shape[0], A_in.shape[0]
+    K = k + m_eq + m_in
+    W = G if K == k else np.vstack([G, A_eq, A_in])
+    h = np.zeros(K)
+    if m_eq:
+        h[k:k + m_eq] = np.asarray(b_eq, dtype=np.float64).ravel()
+    if m_in:
+        h[k + m_eq:] = np.asarray(b_in, dtype=np.float64).ravel()
+    is_eq = np.zeros(K, dtype=bool)
+    is_eq[k:k + m_eq] = True
+    rext = np.zeros(K)
+    rext[:k] = r
+
+    def ended(status, why=None):
+        if stats is not None and why is not None:
+            stats["gave_up"] = why
+        return np.full(n, np.nan), np.full(K, np.nan), np.nan, np.full(K, np.nan), status
+
+    if not np.all(r < 0):     # some r_i >= 0, or a NaN (descent.jl:615-617)
+        return np.zeros(n), np.zeros(K), 0.0, np.zeros(K), _lib.DS_CRITICAL
+    if not np.all(lo <= hi):
+        return np.zeros(n), np.zeros(K), -np.inf, np.zeros(K), _lib.DS_INFEASIBLE
+    if not (np.all(lo <= 0.0) and np.all(hi >= 0.0)):
+        return ended(_lib.DS_GAVE_UP, "start")   # the start d = 0 is outside the box: x is outside [lb, ub] by less than one
+    if not _ds_rows_start(W, k, m_eq, h):
+        return ended(_lib.DS_NO_START)           # the start d = 0 misses a constraint row: the method has no phase 1
+    absW = np.abs(W)
+    rowsum = absW.sum(axis=1)
+    rscale = rowsum + np.abs(rext) + np.abs(h)
+    d = np.zeros(n)
+    flag = np.where(lo == hi, 2, np.where(lo == 0.0, -1, np.where(hi == 0.0, 1, 0)))
+    in_s = is_eq.copy()
+    degen = False
+    free = flag == 0
+    M = W[:, free] @ W[:, free].T
+    cap = 8 * (n + K) + 16
+    iters = dropped = full = 0
+    mu = np.zeros(K)
+    while True:
+        if iters >= cap:
+            return ended(_lib.DS_GAVE_UP, "cap")
+        iters += 1
+        c = W @ d
+        rho = rext - c
+        rho[k:] = 0.0
+        U = np.flatnonzero(in_s | (np.arange(K) < k))
+        MU = M if U.size == K else M[np.ix_(U, U)]
+        s_u = in_s[U]
+        av_u, fac = _ds_step_coeffs(MU, s_u, (c - h)[U], rho[U], int(np.count_nonzero(flag == 0)) if K > k else None)
+        in_s[U] = s_u
+        if av_u is None:
+            return ended(_lib.DS_GAVE_UP, "normal equations")
+        av = np.zeros(K)
+        av[U] = av_u
+        free = flag == 0
+        p = np.where(free, W.T @ av, 0.0)
+        dc = W @ p
+        if full >= 2 or np.all(np.abs(dc) <= DS_VANISH_TOL * rscale):
+            mu = np.zeros(K)
+            mu[U] = _ds_multipliers(MU, fac, rho[U])
+            y = mu - rho
+            s = W.T @ y
+            zext = np.where(np.arange(K) < k, c, 0.0)
+            ysc = np.abs(rext) + np.abs(zext) + np.abs(mu)            # |r| + |z| + |mu| on objective rows, |mu| on the others
+            sscale = absW.T @ ysc
+            mscale = float(np.max(np.abs(r) + np.abs(c[:k])))
+            best, kind, idx = 0.0, 0, -1
+            for i in range(K):
+                v = -mu[i] / mscale if in_s[i] and not is_eq[i] else 0.0
+                if v > DS_DUAL_TOL and v > best and not (degen and kind):
+                    best, kind, idx = v, 1, i
+            viol = np.where(flag == -1, -s, np.where(flag == 1, s, 0.0))
+            with np.errstate(divide="ignore", invalid="ignore"):
+                ratio = np.where(sscale > 0, viol / sscale, 0.0)
+            if degen:             # the least index that violates; a row goes first
+                cand = np.flatnonzero(ratio > DS_DUAL_TOL)
+                j = int(cand[0]) if cand.size and not kind else -1
+            else:
+                j = int(np.argmax(ratio)) if n else -1
+            if j >= 0 and ratio[j] > DS_DUAL_TOL and (degen or ratio[j] > best):
+                best, kind, idx = float(ratio[j]), 2, j
+            if kind == 0:
+                break
+            dropped += 1
+            full = 0
+            if kind == 1:
+                in_s[idx] = False
+            else:
+                flag[idx] = 0
+                fr = flag == 0
+                M = W[:, fr] @ W[:, fr].T
+            continue
+        # ---- ratio test over the free variables' bounds and the rows outside S (an equality row there blocks on either side)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            av_j = np.where(free & (p < 0), (lo - d) / p, np.where(free & (p > 0), (hi - d) / p, np.inf))
+        av_j = np.where(av_j < 0, 0.0, av_j)
+        alpha = 1.0
+        if n:
+            alpha = min(alpha, float(av_j.min()))
+        ar = np.full(K, np.inf)
+        for i in range(K):
+            if not in_s[i] and (abs(dc[i]) if is_eq[i] else dc[i]) > DS_VANISH_TOL * rscale[i]:
+                ar[i] = max(0.0, (h[i] - c[i]) / dc[i])
+        alpha = min(alpha, float(ar.min()))
+        hit = free & (av_j <= alpha)
+        rows_hit = ar <= alpha
+        degen = not alpha > 0.0
+        if degen:                 # a step of length zero adds one constraint: the least index that blocks, a row first
+            first_row = np.flatnonzero(rows_hit)
+            rows_hit = np.zeros(K, dtype=bool)
+            if first_row.size:
+                rows_hit[first_row[0]] = True
+                hit = np.zeros(n, dtype=bool)
+            else:
+                first = int(np.argmax(hit))
+                hit = np.zeros(n, dtype=bool)
+                hit[first] = True
+        d = np.where(free, np.minimum(np.maximum(d + alpha * p, lo), hi), d)
+        d = np.where(hit, np.where(p < 0, lo, hi), d)
+        flag = np.where(hit, np.where(p < 0, -1, 1), flag)
+        in_s |= rows_hit
+        nh = int(hit.sum())
+        full = full + 1 if (nh == 0 and not rows_hit.any()) else 0
+        if nh >= 1:           # M from W whenever N changes: a rank-one downdate would cancel against the columns that have left
+            fr = flag == 0
+            M = W[:, fr] @ W[:, fr].T
+    c = W @ d
+    miss = np.where(is_eq, np.abs(c - h), c - h)
+    if not np.all(miss <= DS_FEAS_TOL * (rowsum + np.abs(h))):
+        return ended(_lib.DS_GAVE_UP, "rows")
+    if stats is not None:
+        stats["iterations"], stats["dropped"] = iters, dropped
+    return d, c, max(0.0, -float(np.max(c[:k]))), mu, _lib.DS_OK
+
+
 def _ds_slsqp(G, r, lo, hi, A_eq, b_eq, A_in, b_in):
     """the same QP, extended by rows A_eq d = b_eq and A_in d <= b_in, with SciPy's SLSQP from d = 0; None where it fails"""
     from scipy.optimize import minimize
@@ -1141,6 +1310,57 @@ def ds_criticality_device(plan, x_n, lb, ub, r, want_mult=False):
     return out + (mu,) if want_mult else out
 
 
+def ds_directions_rows_many(G, r, X, lb, ub, A_eq=None, b_eq=None, A_in=None, b_in=None, ctx=None, want_mult=True, want_iters=True):
+    """one mrbf_ds_direction_rows call for a batch of starts: G (n_qp x k x d), r (n_qp x k), X (n_qp x d), lb / ub (d, or n_qp x d),
+    A_eq (n_qp x m_eq x d) with b_eq (n_qp x m_eq), A_in (n_qp x m_in x d) with b_in (n_qp x m_in); None where there are no such rows.
+    Returns (rc, d (n_qp x d), c (n_qp x K: W d, objective rows first), omega (n_qp), mu (n_qp x K) or None, status (n_qp),
+    iters (n_qp x 2: iterations, constraints dropped) or None)."""
+    ctx = ctx or _lib.default_context()
+    G = np.asarray(G, dtype=np.float64)
+    nq, k, n = G.shape
+    Gl = np.ascontiguousarray(np.transpose(G, (0, 2, 1)))      # mrbf_eval's jac_out layout: k x d column-major per start
+    r = np.ascontiguousarray(np.asarray(r, dtype=np.float64).reshape(nq, k))
+    X = np.ascontiguousarray(np.asarray(X, dtype=np.float64).reshape(nq, n))
+    lb = np.ascontiguousarray(np.broadcast_to(np.asarray(lb, dtype=np.float64), (nq, n)))
+    ub = np.ascontiguousarray(np.broadcast_to(np.asarray(ub, dtype=np.float64), (nq, n)))
+
+    def rows(A, b):
+        if b is None or np.asarray(b).size == 0:
+            return 0, None, None
+        b = np.ascontiguousarray(np.asarray(b, dtype=np.float64).reshape(nq, -1))
+        return b.shape[1], np.ascontiguousarray(np.asarray(A, dtype=np.float64).reshape(nq, b.shape[1], n)), b
+
+    m_eq, A_eq, b_eq = rows(A_eq, b_eq)
+    m_in, A_in, b_in = rows(A_in, b_in)
+    K = k + m_eq + m_in
+    d, c, om = np.empty((nq, n)), np.empty((nq, K)), np.empty(nq)
+    mu = np.empty((nq, K)) if want_mult else None
+    status = np.empty(nq, dtype=np.int32)
+    iters = np.empty((nq, 2), dtype=np.int32) if want_iters else None
+    rc = ctx.lib.mrbf_ds_direction_rows(ctx.h, nq, n, k, m_eq, m_in, _lib.as_ptr(Gl), _lib.as_ptr(r), _lib.as_ptr(X), _lib.as_ptr(lb),
+                                        _lib.as_ptr(ub), _lib.as_ptr(A_eq), _lib.as_ptr(b_eq), _lib.as_ptr(A_in), _lib.as_ptr(b_in),
+                                        _lib.as_ptr(d), _lib.as_ptr(c), _lib.as_ptr(om), _lib.as_ptr(mu), _lib.as_ptr(status),
+                                        _lib.as_ptr(iters))
+    return rc, d, c, om, mu, status, iters
+
+
+def ds_criticality_rows_device(plan, x, x_n, lb, ub, r, lin=None, want_mult=False):
+    """one mrbf_ds_criticality_rows call; returns (rc, omega, d, info dict[, multipliers of the K rows])"""
+    ctx = plan["models"][0].ctx
+    x, x_n = np.ascontiguousarray(x, dtype=np.float64), np.ascontiguousarray(x_n, dtype=np.float64)
+    lb, ub = np.ascontiguousarray(lb, dtype=np.float64), np.ascontiguousarray(ub, dtype=np.float64)
+    r = np.ascontiguousarray(r, dtype=np.float64)
+    prob, keep = _sd_problem(plan, lin or (None,) * 4)
+    m = plan["k"] + plan["n_con"] + sum(0 if b is None else b.size for b in (keep[3], keep[5]))
+    d = np.empty(x_n.size)
+    mu = np.empty(m) if want_mult else None
+    info = _lib.DsInfo()
+    rc = ctx.lib.mrbf_ds_criticality_rows(ctx.h, ctypes.byref(prob), _lib.as_ptr(x), _lib.as_ptr(x_n), _lib.as_ptr(lb), _lib.as_ptr(ub),
+                                          _lib.as_ptr(r), _lib.as_ptr(d), _lib.as_ptr(mu), ctypes.byref(info))
+    out = (rc, float(info.omega), d, info.asdict())
+    return out + (mu,) if want_mult else out
+
+
 def _ds_image_direction(cfg, sc, scal, x, x_n, fx_n, delta, lb, ub, rng, stats):
     """r of descent.jl:599-611, the target change of the model values: minus the reference direction, or the reference point minus
     f(x_n), or the local ideal point (descent.jl:404-412, over the trust region stretched by reference_trust_region_factor) minus f(x_n)"""
@@ -1172,7 +1392,8 @@ def _ds_normalise(omega, d, status, n):
 def get_criticality_ds(cfg, sc, scal, x, x_n, fx_n, delta, lb, ub, lin=None, stats=None, rng=None):
     """The criticality of directed search (descent.jl:583-660 up to the backtracking) as HipRbf.jl's `hip_get_criticality_ds` routes it:
     the image direction r from the configuration (`_get_global_dir` / `compute_local_ideal_point`), then mrbf_dispatch_ds decides,
-    mrbf_ds_criticality solves the direction QP on the device, and where the decision table or mrbf_dispatch_after say so the host
+    mrbf_ds_criticality solves the direction QP on the device (with cfg.constraint_rows == "device" and constraint rows:
+    mrbf_dispatch_ds_rows and mrbf_ds_criticality_rows), and where the decision table or mrbf_dispatch_after say so the host
     method runs (`_directed_search_direction` on container Jacobians, with the rows of `_sd_host_rows` where the container or the
     problem has constraints).  lb / ub: the global bounds in scaled variables; lin = (A_eq, b_eq, A_ineq, b_ineq) in scaled variables.
     Never raises on a size limit.  Returns (omega, d / ||d||_inf), or (0, zeros) when critical or ||d||_inf = 0 (descent.jl:647-660);
@@ -1188,7 +1409,17 @@ def get_criticality_ds(cfg, sc, scal, x, x_n, fx_n, delta, lb, ub, lin=None, sta
     def result(omega, d, status):
         return _ds_normalise(omega, d, status, n)
 
-    if lib.mrbf_dispatch_ds(n, plan["k"], len(plan["models"]), plan["n_con"], n_lin, plan["n_foreign"]) == _lib.DISPATCH_DEVICE:
+    if (cfg.constraint_rows == "device" and (n_lin or plan["n_con"]) and
+            lib.mrbf_dispatch_ds_rows(n, plan["k"], len(plan["models"]), plan["n_con"], n_lin, plan["n_foreign"]) == _lib.DISPATCH_DEVICE):
+        rc, omega, d, info = ds_criticality_rows_device(plan, x, x_n, lb, ub, r, lin)
+        if stats is not None:
+            stats.update(info)
+            stats["path"] = "device"
+        if rc == 0:
+            return result(omega, d, info["status"])
+        if not lib.mrbf_dispatch_after(_lib.ENTRY_DS_ROWS, rc):     # -2: the QP gave up, or d = 0 misses a row (stats["status"])
+            plan["models"][0].ctx.check(rc)
+    elif lib.mrbf_dispatch_ds(n, plan["k"], len(plan["models"]), plan["n_con"], n_lin, plan["n_foreign"]) == _lib.DISPATCH_DEVICE:
         rc, omega, d, info = ds_criticality_device(plan, x_n, lb, ub, r)
         if stats is not None:
             stats.update(info)

@@ -311,6 +311,8 @@ _dispatch_sd_step(d, k, n_models, n_nl, n_lin, n_foreign, max_loops) =
 _dispatch_sd_batch(n_starts, d, k, n_models, n_nl, n_lin, n_foreign, max_loops) =
     ccall((:mrbf_dispatch_sd_batch, libmrbf), Int32, (Int64, Int32, Int32, Int32, Int32, Int32, Int32, Int32),
           n_starts, d, k, n_models, n_nl, n_lin, n_foreign, max_loops) == 1
+_dispatch_ds_rows(d, k, n_models, n_nl, n_lin, n_foreign) =
+    ccall((:mrbf_dispatch_ds_rows, libmrbf), Int32, (Int32, Int32, Int32, Int32, Int32, Int32), d, k, n_models, n_nl, n_lin, n_foreign) == 1
 _dispatch_ds_batch(n_starts, d, k, n_models, n_nl, n_lin, n_foreign, max_loops) =
     ccall((:mrbf_dispatch_ds_batch, libmrbf), Int32, (Int64, Int32, Int32, Int32, Int32, Int32, Int32, Int32),
           n_starts, d, k, n_models, n_nl, n_lin, n_foreign, max_loops) == 1
@@ -1033,15 +1035,17 @@ struct HipDirectedSearchConfig <: AbstractDescentConfig
     min_stepsize::Float64
     max_loops::Int
     normalize::Bool
+    constraint_rows::Symbol      # :host (the parked body's JuMP model) or :device (mrbf_ds_criticality_rows) for a problem with rows
     function HipDirectedSearchConfig(; reference_point = Float64[], reference_direction = Float64[], max_ideal_point_problem_evals = -1,
                                      reference_algo = :GN_ISRES, strict_backtracking = true, armijo_const_rhs = 1e-6,
                                      armijo_const_shrink = 0.75, min_stepsize = 10 * eps(Float64),
                                      max_loops = floor(Int, log(min_stepsize > 0 ? min_stepsize : eps(Float64)) / log(armijo_const_shrink)),
-                                     normalize = true)
+                                     normalize = true, constraint_rows = :host)
         @assert all(reference_direction .> 0) "The components of the `reference_direction` cannot be negative."
         @assert armijo_const_rhs > 0
+        @assert constraint_rows in (:host, :device)
         return new(reference_point, reference_direction, max_ideal_point_problem_evals, reference_algo, strict_backtracking,
-                   armijo_const_rhs, armijo_const_shrink, min_stepsize, max_loops, normalize)
+                   armijo_const_rhs, armijo_const_shrink, min_stepsize, max_loops, normalize, constraint_rows)
     end
 end
 _ds_step_config(cfg::HipDirectedSearchConfig) =
@@ -1098,7 +1102,9 @@ The criticality of directed search (descent.jl:583-660 up to the backtracking) o
 r from the configuration, the objective Jacobians at x_n by the evaluation kernels, then the direction QP min ½‖∇m d − r‖², the box of
 the steepest-descent LP, ∇m d ≤ 0 (descent.jl:635-640), solved exactly by an active-set method instead of by JuMP + OSQP.  Whenever the
 decision table says so (`mrbf_dispatch_ds`: a `CompositeSurrogate` or another model family, more than 16 objectives, d > 4096, modelled
-or linear constraints) or the QP gave up, the parked body's own JuMP model runs on the same arguments.  Returns (ω, d / ‖d‖∞) in the
+or linear constraints) or the QP gave up, the parked body's own JuMP model runs on the same arguments.  With
+`constraint_rows = :device` a container or problem with constraint rows takes `mrbf_ds_criticality_rows` where `mrbf_dispatch_ds_rows`
+agrees (at most 16 rows in all), and the JuMP model where that call answers -2 (the QP gave up, or d = 0 misses a row).  Returns (ω, d / ‖d‖∞) in the
 iterate's float type, or (0, zeros) when critical or ‖d‖∞ = 0 (descent.jl:615-617, :647-660); `hip_compute_descent_step(
 _ds_step_config(cfg), ..., ω, d)` does the step.
 """
@@ -1119,7 +1125,7 @@ function hip_get_criticality_ds(desc_cfg::HipDirectedSearchConfig, mop, scal, x_
     k = plan.k
     A_eq, b_eq = transformed_linear_eq_constraints(scal, mop)
     A_in, b_in = transformed_linear_ineq_constraints(scal, mop)
-    _dispatch_ds(n, k, length(plan.models), plan.n_con, length(b_eq) + length(b_in), plan.n_foreign) || return reference()
+    n_lin = length(b_eq) + length(b_in)
     lb_g, ub_g = full_bounds_internal(scal)
     lb = Vector{Float64}(lb_g); ub = Vector{Float64}(ub_g)
     info = Ref{MrbfDsInfo}()
@@ -1127,6 +1133,30 @@ function hip_get_criticality_ds(desc_cfg::HipDirectedSearchConfig, mop, scal, x_
     handles = Ptr{Cvoid}[m.handle for m in plan.models]
     roles = plan.roles
     ctx = plan.models[1].ctx
+    if plan.n_con + n_lin > 0
+        # constraint rows: the extended QP on the device where the configuration asks for it and mrbf_dispatch_ds_rows agrees
+        (desc_cfg.constraint_rows == :device &&
+         _dispatch_ds_rows(n, k, length(plan.models), plan.n_con, n_lin, plan.n_foreign)) || return reference()
+        x = Vector{Float64}(get_x_scaled(x_it))
+        Aeq = Matrix{Float64}(transpose(Matrix(A_eq))); beq = Vector{Float64}(b_eq)
+        Ain = Matrix{Float64}(transpose(Matrix(A_in))); bin = Vector{Float64}(b_in)
+        rc = GC.@preserve handles roles Aeq beq Ain bin x x_n lb ub r dir begin
+            prob = Ref(MrbfPsProblem(length(handles), k, pointer(handles), pointer(roles), length(beq), length(bin),
+                                     isempty(beq) ? C_NULL : pointer(Aeq), isempty(beq) ? C_NULL : pointer(beq),
+                                     isempty(bin) ? C_NULL : pointer(Ain), isempty(bin) ? C_NULL : pointer(bin), -1.0))
+            _locked(ctx) do hctx
+                ccall((:mrbf_ds_criticality_rows, libmrbf), Int32,
+                      (Ptr{Cvoid}, Ref{MrbfPsProblem}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                       Ptr{Float64}, Ref{MrbfDsInfo}),
+                      hctx, prob, x, x_n, lb, ub, r, dir, C_NULL, info)
+            end
+        end
+        rc != 0 && _fallback_rc(24, rc) && return reference()  # gave up, or d = 0 is no start: the JuMP model on the same arguments
+        _check(ctx, rc)
+        info[].status == 0 || return Xet(0), zeros(Xet, n)
+        return result(info[].omega, dir)
+    end
+    _dispatch_ds(n, k, length(plan.models), plan.n_con, n_lin, plan.n_foreign) || return reference()
     rc = GC.@preserve handles roles x_n lb ub r dir begin
         prob = Ref(MrbfPsProblem(length(handles), k, pointer(handles), pointer(roles), 0, 0, C_NULL, C_NULL, C_NULL, C_NULL, -1.0))
         _locked(ctx) do hctx
