@@ -1039,6 +1039,38 @@ int32_t mrbf_ps_step_batch(mrbf_ctx *ctx, int64_t n_starts, const mrbf_ps_proble
                            const mrbf_ps_options *opts, const uint64_t *seeds_or_null, double *x_trial, double *mx_trial, double *r_out,
                            mrbf_ps_info *infos, float *ms_total);
 
+/* ---- local ideal points: the ideal-point phase of the step above as calls of its own (ps_solver.hip) ---------------------------
+ * compute_local_ideal_point (src/descent.jl:404-412: k runs of _min_component, :369-387) for one start, or for n_starts starts in one
+ * call: the k single-objective minimisations of every start side by side -- sweep, ranking and breeding on the device, the
+ * refinements in lockstep -- and nothing else of the step.  It is the phase mrbf_ps_step_problem / mrbf_ps_step_batch run when
+ * r_or_null == NULL, the same code with the same launches: for the same container, box, max_ideal_evals, xtol_rel and seed,
+ * fx_n[l] - ideal_out[l] == r_out[l] of that call, bit for bit, and evals_ideal is equal; and every output of the batch call for
+ * start p (ms_total aside) is, bit for bit, the single call's on start p's container with seeds[p].
+ * problem / shape: roles, linear rows and eq_tol as in the PS calls (the runs carry the constraints); models: n_starts x n_models
+ * handles, start-major (shape->models is ignored).  opts: only max_ideal_evals, seed and xtol_rel are read.  x_n, lb_eff, ub_eff:
+ * (n_starts x) d.  ideal_out (n_starts x) k: the value the phase ends with for objective l, after its refinement; x_ideal_out
+ * (n_starts x) k x d, may be NULL: where that value was found (inside [lb_eff, ub_eff]); mx_out (n_starts x) k, may be NULL: m(x_n).
+ * A run that met no feasible point gives ideal = m_l(x_n) and x_ideal = x_n.  Every one of these arrays may be a host or a device
+ * pointer; infos and seeds_or_null (NULL: opts->seed for every start) are host memory; ms_total may be NULL.
+ * Returns 0; -1 no context; -3 NULL problem / shape, a bad roles table or bad linear rows; -4 NULL models, or models that do not
+ * share the shape; -5 NULL x_n; -6 NULL lb_eff, or lb_eff > ub_eff somewhere; -7 NULL ub_eff; -8 NULL opts; -9 NULL ideal_out; -10
+ * NULL info / infos; -2 (take the reference method, or the single call per start) only when mrbf_dispatch_ideal /
+ * mrbf_dispatch_ideal_batch refuses the shape (n_starts < 1 included).  Nothing is written on a negative code. */
+typedef struct {
+    int32_t evals_ideal;      /* surrogate evaluations spent, all objectives, refinements included */
+    int32_t generations;      /* generations, summed over the objectives' runs */
+    int32_t found;            /* bit l: the run of objective l met a feasible point */
+    int32_t refined;          /* bit l: a refinement of objective l's best point ran */
+    float ms_total;           /* hipEvent time of the whole call on the ctx stream */
+} mrbf_ideal_info;            /* 20 bytes */
+int32_t mrbf_ideal_point_problem(mrbf_ctx *ctx, const mrbf_ps_problem *problem, const double *x_n, const double *lb_eff,
+                                 const double *ub_eff, const mrbf_ps_options *opts, double *ideal_out, double *x_ideal_out,
+                                 double *mx_out, mrbf_ideal_info *info);
+int32_t mrbf_ideal_point_batch(mrbf_ctx *ctx, int64_t n_starts, const mrbf_ps_problem *shape, const mrbf_model *const *models,
+                               const double *x_n, const double *lb_eff, const double *ub_eff, const mrbf_ps_options *opts,
+                               const uint64_t *seeds_or_null, double *ideal_out, double *x_ideal_out, double *mx_out,
+                               mrbf_ideal_info *infos, float *ms_total);
+
 /* ---- the decision table of the host bindings ---------------------------------------------------------------------------
  * Which implementation a binding (morbit.jl_amd/julia/HipRbf.jl, the Python mirror) takes for one call of Morbit's interface:
  * the device entry point (MRBF_DISPATCH_DEVICE) or Morbit's own method on the same arguments (MRBF_DISPATCH_REFERENCE; Julia:
@@ -1104,6 +1136,11 @@ int32_t mrbf_ps_step_batch(mrbf_ctx *ctx, int64_t n_starts, const mrbf_ps_proble
  *                            device iff mrbf_dispatch_ps says so, d <= 256 (the fused evaluation kernels' range) and
  *                            1 <= n_starts <= 65535 (a grid dimension).  The bindings keep the loop of single calls where the
  *                            batch does not pay.
+ *   mrbf_dispatch_ideal      compute_local_ideal_point (src/descent.jl:404-412) as a call of its own (mrbf_ideal_point_problem): what
+ *                            mrbf_dispatch_ps returns -- the kernels and the limits are that step's.
+ *   mrbf_dispatch_ideal_batch  the same for n_starts starts in one call (mrbf_ideal_point_batch): what mrbf_dispatch_ps_batch
+ *                            returns.  The bindings keep the loop of single calls where the batch does not pay (DESIGN.md
+ *                            section 24).
  *   mrbf_dispatch_db_batch   results_in_box_indices (src/Databases.jl:324-327) and the row gathers of n_starts resident databases in one
  *                            call (mrbf_db_box_batch, mrbf_db_gather_batch): device iff 1 <= n_starts <= 65535 (a grid dimension) and
  *                            1 <= d <= 4096; otherwise the scan and the copies run on the caller's host copy of the database.
@@ -1134,9 +1171,13 @@ enum { MRBF_ENTRY_ROUND4 = 1, MRBF_ENTRY_FIT_FROM_ROUND4 = 2, MRBF_ENTRY_PS_STEP
        MRBF_ENTRY_DB_SET_VALUES_BATCH = 19, MRBF_ENTRY_EVAL_BATCH = 20, MRBF_ENTRY_HESSIAN_BATCH = 21,
        MRBF_ENTRY_DS = 22, MRBF_ENTRY_DS_BATCH = 23 };
 enum { MRBF_ENTRY_DS_ROWS = 24 };
+enum { MRBF_ENTRY_IDEAL = 25, MRBF_ENTRY_IDEAL_BATCH = 26 };
 int32_t mrbf_dispatch_ps(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_ps_batch(int64_t n_starts, int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints,
                                int32_t n_lin_constraints, int32_t n_foreign);
+int32_t mrbf_dispatch_ideal(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
+int32_t mrbf_dispatch_ideal_batch(int64_t n_starts, int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints,
+                                  int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_sd(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_ds(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign);
 int32_t mrbf_dispatch_ds_rows(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints,

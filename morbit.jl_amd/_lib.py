@@ -102,6 +102,8 @@ ENTRY_HESSIAN_BATCH = 21
 ENTRY_DS = 22
 ENTRY_DS_BATCH = 23
 ENTRY_DS_ROWS = 24
+ENTRY_IDEAL = 25
+ENTRY_IDEAL_BATCH = 26
 R3_UPDATE, R3_IMPROVE = 0, 1
 R3_DONE, R3_REBUILT = 0, 1
 SD_OK, SD_NO_OBJECTIVE, SD_INFEASIBLE, SD_GAVE_UP = 0, 1, 2, 3
@@ -110,6 +112,15 @@ DS_OK, DS_CRITICAL, DS_INFEASIBLE, DS_GAVE_UP = 0, 1, 2, 3
 DS_NO_START = 4
 DS_MAXD, DS_MAXK = 4096, 16
 SD_BRANCH_DELTA, SD_BRANCH_ONE, SD_BRANCH_INTERSECT = 0, 1, 2
+
+
+class IdealInfo(ctypes.Structure):
+    """mrbf_ideal_info: one start of mrbf_ideal_point_problem / mrbf_ideal_point_batch"""
+    _fields_ = [("evals_ideal", ctypes.c_int32), ("generations", ctypes.c_int32), ("found", ctypes.c_int32), ("refined", ctypes.c_int32),
+                ("ms_total", ctypes.c_float)]
+
+    def asdict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
 
 
 class PsProblem(ctypes.Structure):
@@ -351,6 +362,13 @@ SIGNATURES = {
                                             c_vp, c_vp, ctypes.POINTER(PsOptions), ctypes.POINTER(ctypes.c_uint64), c_vp, c_vp, c_vp,
                                             ctypes.POINTER(PsInfo), c_fp]),
     "mrbf_dispatch_ps_batch": (ctypes.c_int32, [ctypes.c_int64] + [ctypes.c_int32] * 6),
+    "mrbf_ideal_point_problem": (ctypes.c_int32, [c_vp, ctypes.POINTER(PsProblem), c_vp, c_vp, c_vp, ctypes.POINTER(PsOptions), c_vp, c_vp,
+                                                  c_vp, ctypes.POINTER(IdealInfo)]),
+    "mrbf_ideal_point_batch": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.POINTER(PsProblem), ctypes.POINTER(ctypes.c_void_p), c_vp, c_vp,
+                                                c_vp, ctypes.POINTER(PsOptions), ctypes.POINTER(ctypes.c_uint64), c_vp, c_vp, c_vp,
+                                                ctypes.POINTER(IdealInfo), c_fp]),
+    "mrbf_dispatch_ideal": (ctypes.c_int32, [ctypes.c_int32] * 6),
+    "mrbf_dispatch_ideal_batch": (ctypes.c_int32, [ctypes.c_int64] + [ctypes.c_int32] * 6),
     "mrbf_sd_direction": (ctypes.c_int32, [c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32] + [c_vp] * 8
                           + [ctypes.c_int32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mrbf_sd_criticality": (ctypes.c_int32, [c_vp, ctypes.POINTER(PsProblem), c_vp, c_vp, c_vp, c_vp, ctypes.c_int32, c_vp, c_vp,

@@ -63,6 +63,16 @@ int32_t mrbf_dispatch_ps_batch(int64_t n_starts, int32_t d, int32_t k, int32_t n
     return mrbf_dispatch_ps(d, k, n_models, n_nl_constraints, n_lin_constraints, n_foreign);
 }
 
+// the ideal-point phase of that step as calls of its own (ps_solver.hip, mrbf_ideal_point_problem / mrbf_ideal_point_batch): the
+// step's kernels and limits, hence the step's rows
+int32_t mrbf_dispatch_ideal(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign) {
+    return mrbf_dispatch_ps(d, k, n_models, n_nl_constraints, n_lin_constraints, n_foreign);
+}
+int32_t mrbf_dispatch_ideal_batch(int64_t n_starts, int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints,
+                                  int32_t n_lin_constraints, int32_t n_foreign) {
+    return mrbf_dispatch_ps_batch(n_starts, d, k, n_models, n_nl_constraints, n_lin_constraints, n_foreign);
+}
+
 // the direction LP of steepest descent (sd_lp.hip): at most 64 rows (B^-1 lives in LDS), d within the library's limit
 int32_t mrbf_dispatch_sd(int32_t d, int32_t k, int32_t n_models, int32_t n_nl_constraints, int32_t n_lin_constraints, int32_t n_foreign) {
     if (n_foreign != 0 || n_models < 1) return MRBF_DISPATCH_REFERENCE;
@@ -236,6 +246,8 @@ int32_t mrbf_dispatch_after(int32_t entry, int32_t rc) {
         case MRBF_ENTRY_FIT_FROM_ROUND4: return rc == -2 || rc == MRBF_ESINGULAR || rc == MRBF_ENOTPD;
         case MRBF_ENTRY_PS_STEP: return rc == -2;
         case MRBF_ENTRY_PS_BATCH: return rc == -2;  // likewise: the callers run the single call per start; a start's own status is in its info
+        case MRBF_ENTRY_IDEAL: return rc == -2;        // shape outside the device path: the host search
+        case MRBF_ENTRY_IDEAL_BATCH: return rc == -2;  // likewise: the callers run the single call per start
         case MRBF_ENTRY_SD: return rc == -2;  // shape outside the device path, or the LP gave up (MRBF_SD_GAVE_UP)
         case MRBF_ENTRY_NORMAL: return rc == -2;  // likewise (MRBF_NS_GAVE_UP)
         case MRBF_ENTRY_SD_STEP: return rc == -2;  // shape outside the device path

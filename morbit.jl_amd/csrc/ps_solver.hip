@@ -28,6 +28,7 @@
 // launch group (batch_chain.hpp), one ranking and one breeding launch, and the refinements advance in lockstep.  The single call is
 // the batch of one (ps_step_many).  DESIGN.md section 15.
 #include "batch_chain.hpp"
+#include "ideal_host.hpp"
 #include "radial.hpp"
 
 namespace mrbf {
@@ -1708,6 +1709,8 @@ static int fetch_host(mrbf_ctx *ctx, const double *src, size_t cnt, std::vector<
 struct PsStart {
     ps::Problem P;
     std::vector<double> hlb, hub, hxn, hfx, r, mx, xt;
+    std::vector<double> ideal, x_ideal;  // the ideal-point phase: its value per objective and (k x d) where that value was found
+    std::vector<char> found, refined;    // per objective: the run met a feasible point; a refinement of its best point ran
     unsigned long long seed = 0;
     mrbf_ps_info info{};
     ps::Args a{};  // its block of the current phase
@@ -1736,8 +1739,10 @@ static void ps_problem_fill(ps::Problem &P, const descent::Layout &lay, const mr
 // doubles of device memory a start of the step takes in the state slot (run state, evaluation batch, results and the sweeps' scratch):
 // mrbf_ps_step_batch sizes its chunks of starts with it.  An estimate of "the state": the ranking's work space (S_PS_RANK: only while
 // at most 16 runs share a launch) and the refinement's chain (S_PS_POLISH: a few points per start) are not counted.
-static size_t ps_start_doubles(const mrbf_ctx *ctx, const mrbf_model *const *models, int nm, int d, int k, int nftot, bool need_ideal) {
-    const size_t lam_ip = 20 * (size_t)(d + 1), lam_ps = 20 * (size_t)(d + 2);
+// ideal_only: the PS run's part is not there (mrbf_ideal_point_batch).
+static size_t ps_start_doubles(const mrbf_ctx *ctx, const mrbf_model *const *models, int nm, int d, int k, int nftot, bool need_ideal,
+                               bool ideal_only = false) {
+    const size_t lam_ip = 20 * (size_t)(d + 1), lam_ps = ideal_only ? 0 : 20 * (size_t)(d + 2);
     const size_t rows = std::max(need_ideal ? k * lam_ip : 0, lam_ps);
     const size_t state = std::max(need_ideal ? k * (4 * lam_ip * d + 3 * lam_ip) : 0, 4 * lam_ps * (d + 1) + 3 * lam_ps);
     size_t scratch = 0;  // of the larger sweep: centred queries, their norms and the partial sums of a split centre range, per model slot
@@ -1758,7 +1763,11 @@ static size_t ps_start_doubles(const mrbf_ctx *ctx, const mrbf_model *const *mod
 // the optional score launch, the ranking and the breeding for every run of every start that takes part in the phase; the refinements
 // advance in lockstep.  Nothing a start computes depends on another start: its block, its runs' indices and its seed are its own, a
 // finished run is inert in every kernel (R.stat[1], R.stat[3] != gen + 1), the evaluations keep the single call's query counts.
-static int ps_step_many(mrbf_ctx *ctx, std::vector<PsStart> &S, bool need_ideal, const mrbf_ps_options *opts, float *ms_out) {
+// ideal_only (mrbf_ideal_point_problem / mrbf_ideal_point_batch; with need_ideal): the call ends behind the ideal-point phase -- every
+// start's ideal, x_ideal, found, refined, mx = m(x_n) and info.evals_ideal / generations are set, r and the PS run are not touched
+// and the arena holds no room for that run.  Where a piece lies in the arena changes nothing a kernel computes.
+static int ps_step_many(mrbf_ctx *ctx, std::vector<PsStart> &S, bool need_ideal, const mrbf_ps_options *opts, float *ms_out,
+                        bool ideal_only = false) {
     using namespace ps;
     const size_t N = S.size();
     const bool single = N == 1;  // the one start's evaluations are eval_model's own launches (its arena slots, its pinned block)
@@ -1768,7 +1777,7 @@ static int ps_step_many(mrbf_ctx *ctx, std::vector<PsStart> &S, bool need_ideal,
     hipEvent_t e0 = ctx->ev[0], e1 = ctx->ev[1];
     MRBF_HIP(ctx, hipEventRecord(e0, st));
     const int lam_ip = 20 * (d + 1), lam_ps = 20 * (d + 2);
-    const int rows = std::max(need_ideal ? k * lam_ip : 0, lam_ps);
+    const int rows = std::max(need_ideal ? k * lam_ip : 0, ideal_only ? 0 : lam_ps);
     // ---- device arena: linear constraints, the starts' blocks, boxes and start points, mx, r, the runs' best records, then per start the
     // evaluation batch, its results and the runs' state; in a batch also the sweeps' descriptors and scratch (batch_chain.hpp)
     const size_t nlin = (size_t)P0.nlin_eq + P0.nlin_ineq;
@@ -1778,7 +1787,7 @@ static int ps_step_many(mrbf_ctx *ctx, std::vector<PsStart> &S, bool need_ideal,
     chain::Arena ar;
     const size_t oLin = ar.take(nlin * (d + 1)), oArgs = ar.take(N * args_dbl), oBox = ar.take(N * 3 * d), oMx = ar.take(N * k), oR = ar.take(N * k);
     const size_t oBest = ar.take(N * best_per);
-    const size_t start_cnt = (size_t)rows * d + (size_t)rows * nftot + std::max(need_ideal ? k * per_ip : 0, per_ps);
+    const size_t start_cnt = (size_t)rows * d + (size_t)rows * nftot + std::max(need_ideal ? k * per_ip : 0, ideal_only ? 0 : per_ps);
     std::vector<size_t> oStart(N);
     for (size_t p = 0; p < N; ++p) oStart[p] = ar.take(start_cnt);
     chain::Plan ev_ip, ev_ps_all, ev_ps;
@@ -1787,7 +1796,7 @@ static int ps_step_many(mrbf_ctx *ctx, std::vector<PsStart> &S, bool need_ideal,
     if (!single) {
         for (size_t p = 0; p < N && need_ideal; ++p)
             for (int j = 0; j < nm; ++j) ev_ip.add(ctx, SITE_IP, (int64_t)p, j, S[p].P.models[j], (int64_t)k * lam_ip, false, true);
-        for (size_t p = 0; p < N; ++p)
+        for (size_t p = 0; p < N && !ideal_only; ++p)
             for (int j = 0; j < nm; ++j) ev_ps_all.add(ctx, SITE_PS, (int64_t)p, j, S[p].P.models[j], lam_ps, false, true);
         ev_ip.close();
         ev_ps_all.close();
@@ -2032,17 +2041,21 @@ static int ps_step_many(mrbf_ctx *ctx, std::vector<PsStart> &S, bool need_ideal,
         // r = f(x_n) - ideal point (descent.jl:536-538); a run that never met a feasible point contributes its start value.  The runs'
         // best points are refined by gradient steps on their objective -- all descents of all starts in lockstep, one chain of
         // evaluations per iteration
-        std::vector<std::vector<double>> ideal(N, std::vector<double>(k));
         std::vector<DescentGroup> gs;
         std::vector<std::pair<size_t, int>> dl;  // (start, objective) of every descent, group by group
         for (size_t p = 0; p < N; ++p) {
             DescentGroup G;
             G.P = &S[p].P;
+            S[p].ideal.assign(k, 0.0);
+            S[p].x_ideal.assign((size_t)k * d, 0.0);
+            S[p].found.assign(k, 0), S[p].refined.assign(k, 0);
             for (int l = 0; l < k; ++l) {
                 const double *b = &hbest[p * best_per + (size_t)l * (d + 2)];
                 const int *h = &hs[4 * (p * k + l)];
                 const bool found = b[d + 1] == 0.0 && std::isfinite(b[d]);
-                ideal[p][l] = found ? b[d] : S[p].mx[l];
+                S[p].ideal[l] = found ? b[d] : S[p].mx[l];
+                S[p].found[l] = found;
+                std::copy_n(found ? b : S[p].hxn.data(), d, S[p].x_ideal.begin() + (size_t)l * d);
                 S[p].info.evals_ideal += h[0];
                 S[p].info.generations += h[2];
                 const int left = max_ip - h[0];
@@ -2058,7 +2071,7 @@ static int ps_step_many(mrbf_ctx *ctx, std::vector<PsStart> &S, bool need_ideal,
                     D.clamp = false;
                     D.max_evals = left;
                     D.xtol_rel = xtol;
-                    D.val = ideal[p][l];
+                    D.val = S[p].ideal[l];
                     D.x.assign(b, b + d);
                     dl.emplace_back(p, l);
                 }
@@ -2070,13 +2083,23 @@ static int ps_step_many(mrbf_ctx *ctx, std::vector<PsStart> &S, bool need_ideal,
             size_t at = 0;
             for (DescentGroup &G : gs)
                 for (Descent &D : G.ds) {
-                    ideal[dl[at].first][dl[at].second] = D.val;
-                    S[dl[at].first].info.evals_ideal += D.evals;
+                    PsStart &s = S[dl[at].first];
+                    const int l = dl[at].second;
+                    s.ideal[l] = D.val;  // (D.x is where D.val was taken: they change together)
+                    std::copy(D.x.begin(), D.x.end(), s.x_ideal.begin() + (size_t)l * d);
+                    s.refined[l] = D.evals > 0;
+                    s.info.evals_ideal += D.evals;
                     ++at;
                 }
         }
-        for (size_t p = 0; p < N; ++p)
-            for (int l = 0; l < k; ++l) S[p].r[l] = S[p].hfx[l] - ideal[p][l];
+        for (size_t p = 0; p < N && !ideal_only; ++p)
+            for (int l = 0; l < k; ++l) S[p].r[l] = S[p].hfx[l] - S[p].ideal[l];
+    }
+    if (ideal_only) {
+        MRBF_HIP(ctx, hipEventRecord(e1, st));
+        MRBF_HIP(ctx, hipStreamSynchronize(st));
+        MRBF_HIP(ctx, hipEventElapsedTime(ms_out, e0, e1));
+        return MRBF_OK;
     }
     // ---- the Pascoletti-Serafini runs of the starts that are not critical
     std::vector<size_t> act;
@@ -2336,6 +2359,112 @@ extern "C" int32_t mrbf_ps_step_batch(mrbf_ctx *ctx, int64_t n_starts, const mrb
     MRBF_TRY(output_put(ctx, mx_trial, omx.data(), SN * k));
     if (r_out) MRBF_TRY(output_put(ctx, r_out, orr.data(), SN * k));
     return MRBF_OK;
+}
+
+// ---- local ideal points: compute_local_ideal_point (Morbit.jl src/descent.jl:404-412, k runs of _min_component :369-387) as calls of
+// their own -- the ideal-point phase of the step above and nothing behind it (ps_step_many with ideal_only).  The validation, the block
+// the outputs are gathered in and the records' packing are ideal_host.hpp's; nothing reaches the caller before the call has succeeded.
+static int32_t ideal_points(mrbf_ctx *ctx, bool batch, int64_t n_starts, const mrbf_ps_problem *shape, const mrbf_model *const *models,
+                            const double *x_n, const double *lb_eff, const double *ub_eff, const mrbf_ps_options *opts,
+                            const uint64_t *seeds_or_null, double *ideal_out, double *x_ideal_out, double *mx_out, mrbf_ideal_info *infos,
+                            float *ms_total) {
+    const char *name = batch ? "mrbf_ideal_point_batch" : "mrbf_ideal_point_problem";
+    ideal::Call c;
+    c.has_ctx = ctx != nullptr, c.batch = batch, c.n_starts = n_starts;
+    c.problem = shape != nullptr, c.models = models != nullptr, c.x_n = x_n != nullptr, c.lb = lb_eff != nullptr, c.ub = ub_eff != nullptr;
+    c.opts = opts != nullptr, c.ideal_out = ideal_out != nullptr, c.info = infos != nullptr;
+    if (shape) c.n_models = shape->n_models, c.roles = shape->roles != nullptr;
+    if (const int rc = ideal::validate(c)) {
+        if (rc == -1) return -1;
+        return fail(ctx, rc, rc == -2 ? "%s: %lld starts (ask mrbf_dispatch_ideal_batch first)" : "%s: an argument is NULL, or the problem has no models or no roles table",
+                    name, (long long)n_starts);
+    }
+    using namespace ps;
+    const int64_t N = n_starts;
+    const int k = shape->n_objectives, nm = shape->n_models;
+    std::vector<descent::SlotShape> slots;
+    descent::Shape sh = descent_shape(shape, models, N, slots);
+    sh.batch = batch;
+    descent::Layout lay;
+    if (descent::Defect D = descent::read(sh, {true, batch ? descent::Centres::EVERY_SLOT : descent::Centres::UNCHECKED}, lay))
+        return fail(ctx, D.cls == descent::Defect::MODELS ? -4 : -3, "%s: %s", name, D.msg.c_str());
+    const int d = lay.d, n_lin = shape->n_lin_eq + shape->n_lin_ineq;
+    if ((batch ? mrbf_dispatch_ideal_batch(N, d, k, nm, lay.n_nl, n_lin, 0) : mrbf_dispatch_ideal(d, k, nm, lay.n_nl, n_lin, 0)) != MRBF_DISPATCH_DEVICE)
+        return fail(ctx, -2, "%s: %lld starts / d = %d / k = %d / %d constraints outside the device path (ask %s first)", name, (long long)N, d, k,
+                    lay.n_nl + n_lin, batch ? "mrbf_dispatch_ideal_batch" : "mrbf_dispatch_ideal");
+    (void)hipSetDevice(ctx->device);
+    const size_t SN = (size_t)N;
+    // the inputs: host copies (the pointers may be host or device memory)
+    std::vector<double> hx, hlb, hub, A_eq, b_eq, A_ineq, b_ineq;
+    MRBF_TRY(fetch_host(ctx, x_n, SN * d, hx));
+    MRBF_TRY(fetch_host(ctx, lb_eff, SN * d, hlb));
+    MRBF_TRY(fetch_host(ctx, ub_eff, SN * d, hub));
+    for (size_t t = 0; t < SN * d; ++t)
+        if (!(hlb[t] <= hub[t])) return fail(ctx, -6, "%s: start %lld: lb_eff[%d] > ub_eff[%d]", name, (long long)(t / d), (int)(t % d), (int)(t % d));
+    MRBF_TRY(fetch_host(ctx, shape->A_eq, (size_t)shape->n_lin_eq * d, A_eq));
+    MRBF_TRY(fetch_host(ctx, shape->b_eq, (size_t)shape->n_lin_eq, b_eq));
+    MRBF_TRY(fetch_host(ctx, shape->A_ineq, (size_t)shape->n_lin_ineq * d, A_ineq));
+    MRBF_TRY(fetch_host(ctx, shape->b_ineq, (size_t)shape->n_lin_ineq, b_ineq));
+    int nftot = 0;
+    for (int j = 0; j < nm; ++j) nftot += lay.k[j];
+    // a batch whose state exceeds 2 GiB is processed in chunks of starts (MRBF_PS_CHUNK_KB: another limit), as in mrbf_ps_step_batch
+    size_t per_start = 0;
+    for (size_t p = 0; p < SN; ++p) per_start = std::max(per_start, ps_start_doubles(ctx, models + p * nm, nm, d, k, nftot, true, true) * sizeof(double));
+    const size_t limit = mrbf_env("MRBF_PS_CHUNK_KB") ? (size_t)std::max(1, atoi(mrbf_env("MRBF_PS_CHUNK_KB"))) << 10 : (size_t)2 << 30;
+    const size_t chunk = std::max<size_t>(1, limit / per_start);
+    const ideal::Layout L = ideal::layout(N, d, k);
+    std::vector<double> out(L.total);
+    std::vector<mrbf_ideal_info> hinfo(SN);
+    float ms_sum = 0.f;
+    for (size_t p0 = 0; p0 < SN; p0 += chunk) {
+        const size_t n = std::min(chunk, SN - p0);
+        std::vector<PsStart> S(n);
+        for (size_t i = 0; i < n; ++i) {
+            const size_t p = p0 + i;
+            PsStart &s = S[i];
+            ps_problem_fill(s.P, lay, shape, models + p * nm);
+            s.P.A_eq = A_eq, s.P.b_eq = b_eq, s.P.A_ineq = A_ineq, s.P.b_ineq = b_ineq;
+            s.hlb.assign(hlb.begin() + p * d, hlb.begin() + (p + 1) * d);
+            s.hub.assign(hub.begin() + p * d, hub.begin() + (p + 1) * d);
+            s.hxn.assign(hx.begin() + p * d, hx.begin() + (p + 1) * d);
+            s.seed = seeds_or_null ? seeds_or_null[p] : opts->seed;
+        }
+        float ms = 0.f;
+        MRBF_TRY(ps_step_many(ctx, S, true, opts, &ms, true));
+        ms_sum += ms;
+        for (size_t i = 0; i < n; ++i) {
+            const size_t p = p0 + i;
+            const PsStart &s = S[i];
+            ideal::pack(hinfo[p], k, s.info.evals_ideal, s.info.generations, s.found.data(), s.refined.data());
+            std::copy(s.ideal.begin(), s.ideal.end(), out.begin() + L.ideal_at(p, 0));
+            std::copy(s.mx.begin(), s.mx.end(), out.begin() + L.mx_at(p, 0));
+            std::copy(s.x_ideal.begin(), s.x_ideal.end(), out.begin() + L.x_ideal_at(p, 0));
+        }
+    }
+    for (size_t p = 0; p < SN; ++p) hinfo[p].ms_total = ms_sum;
+    MRBF_TRY(output_put(ctx, ideal_out, out.data() + L.ideal, SN * k));
+    if (mx_out) MRBF_TRY(output_put(ctx, mx_out, out.data() + L.mx, SN * k));
+    if (x_ideal_out) MRBF_TRY(output_put(ctx, x_ideal_out, out.data() + L.x_ideal, SN * k * d));
+    std::copy(hinfo.begin(), hinfo.end(), infos);
+    if (ms_total) *ms_total = ms_sum;
+    return MRBF_OK;
+}
+
+extern "C" int32_t mrbf_ideal_point_problem(mrbf_ctx *ctx, const mrbf_ps_problem *problem, const double *x_n, const double *lb_eff,
+                                            const double *ub_eff, const mrbf_ps_options *opts, double *ideal_out, double *x_ideal_out,
+                                            double *mx_out, mrbf_ideal_info *info) {
+    return ideal_points(ctx, false, 1, problem, problem ? problem->models : nullptr, x_n, lb_eff, ub_eff, opts, nullptr, ideal_out, x_ideal_out,
+                        mx_out, info, nullptr);
+}
+
+// For start p every output (ms_total aside) is, bit for bit, that of mrbf_ideal_point_problem on start p's container with seeds[p]: the
+// phase is that call's own with the start on a grid dimension, as in mrbf_ps_step_batch.
+extern "C" int32_t mrbf_ideal_point_batch(mrbf_ctx *ctx, int64_t n_starts, const mrbf_ps_problem *shape, const mrbf_model *const *models,
+                                          const double *x_n, const double *lb_eff, const double *ub_eff, const mrbf_ps_options *opts,
+                                          const uint64_t *seeds_or_null, double *ideal_out, double *x_ideal_out, double *mx_out,
+                                          mrbf_ideal_info *infos, float *ms_total) {
+    return ideal_points(ctx, true, n_starts, shape, models, x_n, lb_eff, ub_eff, opts, seeds_or_null, ideal_out, x_ideal_out, mx_out, infos,
+                        ms_total);
 }
 
 // one grouped model whose outputs are the objectives in order, no constraints: the common case (and the round-2 entry point)

@@ -784,10 +784,12 @@ class DirectedSearchConfig:
     max_loops: int = None
     normalize: bool = True
     constraint_rows: str = "host"     # "device": a container or problem with constraint rows takes mrbf_ds_criticality_rows
+    ideal_point: str = "host"         # "device": the default image direction's ideal-point search takes mrbf_ideal_point_problem / _batch
 
     def __post_init__(self):
         assert all(v > 0 for v in self.reference_direction), "The components of the `reference_direction` cannot be negative."
         assert self.constraint_rows in ("host", "device")
+        assert self.ideal_point in ("host", "device")
         if self.max_loops is None:  # descent.jl:61-66
             base = self.min_stepsize if self.min_stepsize > 0 else np.finfo(np.float64).eps
             self.max_loops = int(math.floor(math.log(base) / math.log(self.armijo_const_shrink)))
@@ -1361,9 +1363,11 @@ def ds_criticality_rows_device(plan, x, x_n, lb, ub, r, lin=None, want_mult=Fals
     return out + (mu,) if want_mult else out
 
 
-def _ds_image_direction(cfg, sc, scal, x, x_n, fx_n, delta, lb, ub, rng, stats):
+def _ds_image_direction(cfg, sc, scal, x, x_n, fx_n, delta, lb, ub, rng, stats, seed=0):
     """r of descent.jl:599-611, the target change of the model values: minus the reference direction, or the reference point minus
-    f(x_n), or the local ideal point (descent.jl:404-412, over the trust region stretched by reference_trust_region_factor) minus f(x_n)"""
+    f(x_n), or the local ideal point (descent.jl:404-412, over the trust region stretched by reference_trust_region_factor) minus f(x_n).
+    The ideal point is the host search's, or with cfg.ideal_point == "device" the device call's (mrbf_ideal_point_problem with `seed`;
+    the box only, as the host search: constraints are not carried); stats["ideal_point_path"] says which ("device" or "reference")."""
     from . import pascoletti_serafini as ps
 
     fx_n = np.asarray(fx_n, dtype=np.float64)
@@ -1372,6 +1376,15 @@ def _ds_image_direction(cfg, sc, scal, x, x_n, fx_n, delta, lb, ub, rng, stats):
         return -g
     n = int(np.asarray(x_n).size)
     lb_eff, ub_eff = _local_bounds(x, cfg.reference_trust_region_factor * delta, lb, ub)
+    if cfg.ideal_point == "device":
+        st = {}
+        ideal = ps.compute_local_ideal_points_many(cfg, [sc], np.asarray(x_n, dtype=np.float64)[None, :], lb_eff[None, :], ub_eff[None, :],
+                                                   seeds=[seed], carry_constraints=False, stats=st, scal=scal)[0]
+        if stats is not None:
+            stats["ideal_point_path"] = "reference" if st["path"] == "reference" else "device"
+        return ideal - fx_n
+    if stats is not None:
+        stats["ideal_point_path"] = "reference"
     max_evals = 500 * (n + 1) if cfg.max_ideal_point_problem_evals < 0 else cfg.max_ideal_point_problem_evals
     rng = np.random.default_rng(0) if rng is None else rng
     ideal = ps.compute_local_ideal_point(np.asarray(x_n, dtype=np.float64), lb_eff, ub_eff,
@@ -1389,22 +1402,25 @@ def _ds_normalise(omega, d, status, n):
     return float(omega), d / nrm
 
 
-def get_criticality_ds(cfg, sc, scal, x, x_n, fx_n, delta, lb, ub, lin=None, stats=None, rng=None):
+def get_criticality_ds(cfg, sc, scal, x, x_n, fx_n, delta, lb, ub, lin=None, stats=None, rng=None, r=None, seed=0):
     """The criticality of directed search (descent.jl:583-660 up to the backtracking) as HipRbf.jl's `hip_get_criticality_ds` routes it:
     the image direction r from the configuration (`_get_global_dir` / `compute_local_ideal_point`), then mrbf_dispatch_ds decides,
     mrbf_ds_criticality solves the direction QP on the device (with cfg.constraint_rows == "device" and constraint rows:
     mrbf_dispatch_ds_rows and mrbf_ds_criticality_rows), and where the decision table or mrbf_dispatch_after say so the host
     method runs (`_directed_search_direction` on container Jacobians, with the rows of `_sd_host_rows` where the container or the
     problem has constraints).  lb / ub: the global bounds in scaled variables; lin = (A_eq, b_eq, A_ineq, b_ineq) in scaled variables.
-    Never raises on a size limit.  Returns (omega, d / ||d||_inf), or (0, zeros) when critical or ||d||_inf = 0 (descent.jl:647-660);
-    stats["path"] is "device" or "reference"."""
+    Never raises on a size limit.  r: a precomputed image direction (ds_iterate_many computes it for all starts at once); seed keys
+    the device ideal-point search (cfg.ideal_point == "device").  Returns (omega, d / ||d||_inf), or (0, zeros) when critical or
+    ||d||_inf = 0 (descent.jl:647-660); stats["path"] is "device" or "reference"."""
     lib = _lib.load()
     plan = sg.container_plan(sc)
     x_n = np.asarray(x_n, dtype=np.float64)
     n = int(x_n.size)
     lin = lin or (None,) * 4
     n_lin = sum(0 if b is None else int(np.asarray(b).size) for b in (lin[1], lin[3]))
-    r = _ds_image_direction(cfg, sc, scal, x, x_n, fx_n, delta, lb, ub, rng, stats)
+    if r is None:
+        r = _ds_image_direction(cfg, sc, scal, x, x_n, fx_n, delta, lb, ub, rng, stats, seed=seed)
+    r = np.asarray(r, dtype=np.float64)
 
     def result(omega, d, status):
         return _ds_normalise(omega, d, status, n)
@@ -1472,14 +1488,18 @@ def ds_iterate_batch_device(plans, cfg, X, X_n, deltas, lb, ub, R, out=None):
     return rc, dd, xp, mxp, mu, records, ms.value
 
 
-def ds_iterate_many(cfg, containers, scal, X, X_n, FX_n, deltas, lb, ub, lin=None, stats=None, rng=None):
+def ds_iterate_many(cfg, containers, scal, X, X_n, FX_n, deltas, lb, ub, lin=None, stats=None, rng=None, seeds=None):
     """`get_criticality_ds` then `compute_descent_step_ds` (descent.jl:583-664) for many independent starts of one problem -- the
     reference's `Threads.@threads` loop over starts (examples/large_scale_benchmarks.jl:102-109): containers[p] is start p's surrogate
     container, X[p] / X_n[p] / FX_n[p] / deltas[p] its iterate, normal-step iterate, values there and radius; lb / ub and lin belong to
     the one MOP.  The image direction r comes per start from `_ds_image_direction`: arithmetic with a reference direction or point,
     else the per-start ideal-point search (stats["image_direction"] says which: "reference_direction", "reference_point" or
-    "ideal_point").  Where the containers share one plan shape and mrbf_dispatch_ds_batch says so, ONE mrbf_ds_iterate_batch call serves
-    all starts ("batch"); otherwise (a refused shape, constraints, mixed shapes), and for every start whose direction QP gave up, the
+    "ideal_point").  With cfg.ideal_point == "device" and that last mode, the ideal points of ALL starts come from one
+    `compute_local_ideal_points_many` call before anything else (seeds[p] keys start p's search, None: 0 for every start;
+    stats["ideal_point_path"] is "device", or "reference" where that call took the host search), and every start is handed its r, the
+    ones that take the single-start functions too: a homogeneous unconstrained batch of at least ps.IDEAL_BATCH_MIN_STARTS starts makes
+    two device calls whatever the number of starts.  Where the containers share one plan shape and mrbf_dispatch_ds_batch says so,
+    ONE mrbf_ds_iterate_batch call serves all starts ("batch"); otherwise (a refused shape, constraints, mixed shapes), and for every start whose direction QP gave up, the
     routed single-start functions run.  Returns a list of (omega, d, x_plus, mx_plus, ||step||_inf); stats gets "path" ("batch" or
     "loop"), "rerouted" (the starts that took the single-start functions after a batch call), "records" and "ms_total"."""
     lib = _lib.load()
@@ -1490,8 +1510,13 @@ def ds_iterate_many(cfg, containers, scal, X, X_n, FX_n, deltas, lb, ub, lin=Non
     lin = lin or (None,) * 4
     n_lin = sum(0 if b is None else int(np.asarray(b).size) for b in (lin[1], lin[3]))
 
+    R_dev = None  # the image directions of all starts, where the device finds the ideal points
+
     def single(p):
-        omega, d = get_criticality_ds(cfg, containers[p], scal, X[p], X_n[p], FX_n[p], float(deltas[p]), lb, ub, lin, rng=rng)
+        if R_dev is None:
+            omega, d = get_criticality_ds(cfg, containers[p], scal, X[p], X_n[p], FX_n[p], float(deltas[p]), lb, ub, lin, rng=rng)
+        else:
+            omega, d = get_criticality_ds(cfg, containers[p], scal, X[p], X_n[p], FX_n[p], float(deltas[p]), lb, ub, lin, rng=rng, r=R_dev[p])
         om, xp, mxp, nrm = compute_descent_step_ds(cfg, containers[p], scal, X[p], X_n[p], float(deltas[p]), lb, ub, omega, d, lin)
         return om, d, xp, mxp, nrm
 
@@ -1501,13 +1526,26 @@ def ds_iterate_many(cfg, containers, scal, X, X_n, FX_n, deltas, lb, ub, lin=Non
                                     else "reference_point" if len(cfg.reference_point) else "ideal_point")
     if ns == 0:
         return []
+    if cfg.ideal_point == "device" and not len(cfg.reference_direction) and not len(cfg.reference_point):
+        from . import pascoletti_serafini as ps
+
+        boxes = [_local_bounds(X[p], cfg.reference_trust_region_factor * float(deltas[p]), lb, ub) for p in range(ns)]
+        st = {}
+        ideal = ps.compute_local_ideal_points_many(cfg, containers, X_n, np.stack([b[0] for b in boxes]), np.stack([b[1] for b in boxes]),
+                                                   seeds=seeds, carry_constraints=False, stats=st, scal=scal)
+        R_dev = ideal - FX_n
+        if stats is not None:
+            stats["ideal_point_path"] = "reference" if st["path"] == "reference" else "device"
+            stats["ideal_point_stats"] = st
+    elif stats is not None and not len(cfg.reference_direction) and not len(cfg.reference_point):
+        stats["ideal_point_path"] = "reference"
     plans = [sg.container_plan(sc) for sc in containers]
     n = int(X_n.shape[1])
     p0 = plans[0]
     if _same_plan_shape(plans) and lib.mrbf_dispatch_ds_batch(ns, n, p0["k"], len(p0["models"]), p0["n_con"], n_lin, p0["n_foreign"],
                                                               int(cfg.max_loops)) == _lib.DISPATCH_DEVICE:
-        R = np.stack([_ds_image_direction(cfg, containers[p], scal, X[p], X_n[p], FX_n[p], float(deltas[p]), lb, ub, rng, None)
-                      for p in range(ns)])
+        R = R_dev if R_dev is not None else np.stack(
+            [_ds_image_direction(cfg, containers[p], scal, X[p], X_n[p], FX_n[p], float(deltas[p]), lb, ub, rng, None) for p in range(ns)])
         rc, dd, xp, mxp, mu, records, ms = ds_iterate_batch_device(plans, cfg, X, X_n, deltas, lb, ub, R)
         if rc == 0:
             res, rerouted = [], []

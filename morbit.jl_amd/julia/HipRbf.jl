@@ -41,6 +41,9 @@ struct MrbfPsInfo           # mirrors mrbf_ps_info, 32 bytes
     status::Int32; generations::Int32; evals_ideal::Int32; evals_ps::Int32; evals_polish::Int32; ms_total::Float32
     tau::Float64
 end
+struct MrbfIdealInfo        # mirrors mrbf_ideal_info, 20 bytes
+    evals_ideal::Int32; generations::Int32; found::Int32; refined::Int32; ms_total::Float32
+end
 
 struct MrbfSdInfo          # mirrors mrbf_sd_info, 24 bytes
     status::Int32; iterations::Int32; bound_flips::Int32; ms_total::Float32
@@ -299,6 +302,11 @@ _dispatch_ps(d, k, n_models, n_nl, n_lin, n_foreign) =
 _dispatch_ps_batch(n_starts, d, k, n_models, n_nl, n_lin, n_foreign) =
     ccall((:mrbf_dispatch_ps_batch, libmrbf), Int32, (Int64, Int32, Int32, Int32, Int32, Int32, Int32),
           n_starts, d, k, n_models, n_nl, n_lin, n_foreign) == 1
+_dispatch_ideal(d, k, n_models, n_nl, n_lin, n_foreign) =
+    ccall((:mrbf_dispatch_ideal, libmrbf), Int32, (Int32, Int32, Int32, Int32, Int32, Int32), d, k, n_models, n_nl, n_lin, n_foreign) == 1
+_dispatch_ideal_batch(n_starts, d, k, n_models, n_nl, n_lin, n_foreign) =
+    ccall((:mrbf_dispatch_ideal_batch, libmrbf), Int32, (Int64, Int32, Int32, Int32, Int32, Int32, Int32),
+          n_starts, d, k, n_models, n_nl, n_lin, n_foreign) == 1
 _dispatch_sd(d, k, n_models, n_nl, n_lin, n_foreign) =
     ccall((:mrbf_dispatch_sd, libmrbf), Int32, (Int32, Int32, Int32, Int32, Int32, Int32), d, k, n_models, n_nl, n_lin, n_foreign) == 1
 _dispatch_ds(d, k, n_models, n_nl, n_lin, n_foreign) =
@@ -357,6 +365,9 @@ _round4_batch_pays(n_starts, max_candidates) = n_starts >= ROUND4_BATCH_MIN_STAR
 # call itself, from two starts on the starts share every generation's launches and every refinement iteration's synchronisation.
 const PS_BATCH_MIN_STARTS = 2
 _ps_batch_pays(n_starts) = n_starts >= PS_BATCH_MIN_STARTS
+# from this many starts on ONE mrbf_ideal_point_batch call, below the loop of mrbf_ideal_point_problem calls (measured, DESIGN.md
+# section 24: batch / loop = 0.81 at 2 starts, above the 0.8 that admits a count; 0.40 at 8)
+const IDEAL_BATCH_MIN_STARTS = 8
 _fallback_rc(entry, rc) = ccall((:mrbf_dispatch_after, libmrbf), Int32, (Int32, Int32), entry, rc) == 1
 
 # ---- two-phase construction: phase I (which sites) stays Morbit's control flow (RbfModel.jl:506-655 is generic in `cfg`); the
@@ -1036,16 +1047,18 @@ struct HipDirectedSearchConfig <: AbstractDescentConfig
     max_loops::Int
     normalize::Bool
     constraint_rows::Symbol      # :host (the parked body's JuMP model) or :device (mrbf_ds_criticality_rows) for a problem with rows
+    ideal_point::Symbol          # :host (compute_local_ideal_point, NLopt) or :device (mrbf_ideal_point_problem / _batch) for the default r
     function HipDirectedSearchConfig(; reference_point = Float64[], reference_direction = Float64[], max_ideal_point_problem_evals = -1,
                                      reference_algo = :GN_ISRES, strict_backtracking = true, armijo_const_rhs = 1e-6,
                                      armijo_const_shrink = 0.75, min_stepsize = 10 * eps(Float64),
                                      max_loops = floor(Int, log(min_stepsize > 0 ? min_stepsize : eps(Float64)) / log(armijo_const_shrink)),
-                                     normalize = true, constraint_rows = :host)
+                                     normalize = true, constraint_rows = :host, ideal_point = :host)
         @assert all(reference_direction .> 0) "The components of the `reference_direction` cannot be negative."
         @assert armijo_const_rhs > 0
         @assert constraint_rows in (:host, :device)
+        @assert ideal_point in (:host, :device)
         return new(reference_point, reference_direction, max_ideal_point_problem_evals, reference_algo, strict_backtracking,
-                   armijo_const_rhs, armijo_const_shrink, min_stepsize, max_loops, normalize, constraint_rows)
+                   armijo_const_rhs, armijo_const_shrink, min_stepsize, max_loops, normalize, constraint_rows, ideal_point)
     end
 end
 _ds_step_config(cfg::HipDirectedSearchConfig) =
@@ -1053,13 +1066,119 @@ _ds_step_config(cfg::HipDirectedSearchConfig) =
                           armijo_const_shrink = cfg.armijo_const_shrink, min_stepsize = cfg.min_stepsize, max_loops = cfg.max_loops,
                           normalize = cfg.normalize)
 
+"""
+The local ideal point (descent.jl:404-412) of one start on the device (`mrbf_ideal_point_problem`): the k single-objective minimisations
+over [lb_eff, ub_eff] side by side -- the ideal-point phase of the Pascoletti-Serafini step as a call of its own.  `plan` is the
+container's plan (`_container_plan`); `lin = (Aeq, beq, Ain, bin)` holds the linear rows in scaled variables, the matrices d × rows
+(the rows × d row-major array); `carry_constraints = false` searches the box only: constraint roles read MRBF_ROLE_NONE (-1) and no
+linear rows are passed.  Returns (ideal (k), x_ideal (d × k), m(x_n) (k), info), or `nothing` where the decision table refuses
+(`mrbf_dispatch_ideal`): take the host search.
+"""
+function hip_local_ideal_point(plan, x_n::Vector{Float64}, lb_eff::Vector{Float64}, ub_eff::Vector{Float64}; max_evals::Integer = -1,
+                               seed::UInt64 = UInt64(0), lin = nothing, carry_constraints::Bool = true)
+    d, k, nm = length(x_n), plan.k, length(plan.models)
+    carry = carry_constraints
+    roles = carry ? plan.roles : Int32[r >= 0 ? r : Int32(-1) for r in plan.roles]
+    Aeq, beq, Ain, bin = (carry && lin !== nothing) ? lin : (zeros(0, 0), Float64[], zeros(0, 0), Float64[])
+    _dispatch_ideal(d, k, nm, carry ? plan.n_con : 0, length(beq) + length(bin), plan.n_foreign) || return nothing
+    opts = Ref(MrbfPsOptions(max_evals, -1, 0, 0, seed, -0.5, 1e-3))
+    info = Ref{MrbfIdealInfo}()
+    ideal = Vector{Float64}(undef, k); x_ideal = Matrix{Float64}(undef, d, k); mx = Vector{Float64}(undef, k)
+    handles = Ptr{Cvoid}[m.handle for m in plan.models]
+    ctx = plan.models[1].ctx
+    rc = GC.@preserve handles roles Aeq beq Ain bin x_n lb_eff ub_eff ideal x_ideal mx begin
+        prob = Ref(MrbfPsProblem(nm, k, pointer(handles), pointer(roles), length(beq), length(bin),
+                                 isempty(beq) ? C_NULL : pointer(Aeq), isempty(beq) ? C_NULL : pointer(beq),
+                                 isempty(bin) ? C_NULL : pointer(Ain), isempty(bin) ? C_NULL : pointer(bin), -1.0))
+        _locked(ctx) do hctx
+            ccall((:mrbf_ideal_point_problem, libmrbf), Int32,
+                  (Ptr{Cvoid}, Ref{MrbfPsProblem}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{MrbfPsOptions}, Ptr{Float64}, Ptr{Float64},
+                   Ptr{Float64}, Ref{MrbfIdealInfo}),
+                  hctx, prob, x_n, lb_eff, ub_eff, opts, ideal, x_ideal, mx, info)
+        end
+    end
+    rc != 0 && _fallback_rc(25, rc) && return nothing          # a shape outside the device path: the host search
+    _check(ctx, rc)
+    return ideal, x_ideal, mx, info[]
+end
+
+"""
+The local ideal points of many starts in one device call (`mrbf_ideal_point_batch`): `plans[p]` is start p's container plan, column p
+of `X_n`, `LB`, `UB` (d × n_starts) its start point and box, `seeds[p]` keys its generator.  For every start the outputs are, bit for
+bit, what `hip_local_ideal_point` returns on that start alone.  Below `IDEAL_BATCH_MIN_STARTS` starts, or where only the single call's
+row of the decision table admits the shape, the loop of single calls runs.  Returns (ideal (k × n_starts), x_ideal (d × k × n_starts),
+m(x_n) (k × n_starts), infos), or `nothing` where the plans do not share one shape or the table refuses a start: take the host search.
+"""
+function hip_local_ideal_points_many(plans::AbstractVector, X_n::Matrix{Float64}, LB::Matrix{Float64}, UB::Matrix{Float64};
+                                     max_evals::Integer = -1, seeds::AbstractVector{UInt64} = zeros(UInt64, length(plans)), lin = nothing,
+                                     carry_constraints::Bool = true)
+    ns = length(plans)
+    ns >= 1 || return nothing
+    p1 = plans[1]
+    d, k, nm = size(X_n, 1), p1.k, length(p1.models)
+    function loop()
+        ideal = Matrix{Float64}(undef, k, ns); x_ideal = Array{Float64,3}(undef, d, k, ns); mx = Matrix{Float64}(undef, k, ns)
+        infos = Vector{MrbfIdealInfo}(undef, ns)
+        for p in 1:ns
+            one = hip_local_ideal_point(plans[p], X_n[:, p], LB[:, p], UB[:, p]; max_evals = max_evals, seed = seeds[p], lin = lin,
+                                        carry_constraints = carry_constraints)
+            one === nothing && return nothing
+            ideal[:, p] .= one[1]; x_ideal[:, :, p] .= one[2]; mx[:, p] .= one[3]; infos[p] = one[4]
+        end
+        return ideal, x_ideal, mx, infos
+    end
+    same = all(pl -> pl.roles == p1.roles && pl.k == p1.k && pl.n_con == p1.n_con && pl.n_foreign == p1.n_foreign &&
+                     length(pl.models) == length(p1.models) &&
+                     all(num_outputs(a) == num_outputs(b) for (a, b) in zip(pl.models, p1.models)), plans)
+    same || return nothing
+    carry = carry_constraints
+    roles = carry ? p1.roles : Int32[r >= 0 ? r : Int32(-1) for r in p1.roles]
+    Aeq, beq, Ain, bin = (carry && lin !== nothing) ? lin : (zeros(0, 0), Float64[], zeros(0, 0), Float64[])
+    (ns >= IDEAL_BATCH_MIN_STARTS &&
+     _dispatch_ideal_batch(ns, d, k, nm, carry ? p1.n_con : 0, length(beq) + length(bin), p1.n_foreign)) || return loop()
+    opts = Ref(MrbfPsOptions(max_evals, -1, 0, 0, UInt64(0), -0.5, 1e-3))
+    infos = Vector{MrbfIdealInfo}(undef, ns)
+    ideal = Matrix{Float64}(undef, k, ns); x_ideal = Array{Float64,3}(undef, d, k, ns); mx = Matrix{Float64}(undef, k, ns)
+    ms = Ref{Float32}(0)
+    seedv = Vector{UInt64}(seeds)
+    handles = Ptr{Cvoid}[m.handle for pl in plans for m in pl.models]          # start-major
+    ctx = p1.models[1].ctx
+    rc = GC.@preserve handles roles Aeq beq Ain bin X_n LB UB seedv ideal x_ideal mx infos begin
+        prob = Ref(MrbfPsProblem(nm, k, C_NULL, pointer(roles), length(beq), length(bin),
+                                 isempty(beq) ? C_NULL : pointer(Aeq), isempty(beq) ? C_NULL : pointer(beq),
+                                 isempty(bin) ? C_NULL : pointer(Ain), isempty(bin) ? C_NULL : pointer(bin), -1.0))
+        _locked(ctx) do hctx
+            ccall((:mrbf_ideal_point_batch, libmrbf), Int32,
+                  (Ptr{Cvoid}, Int64, Ref{MrbfPsProblem}, Ptr{Ptr{Cvoid}}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{MrbfPsOptions},
+                   Ptr{UInt64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{MrbfIdealInfo}, Ref{Float32}),
+                  hctx, ns, prob, handles, X_n, LB, UB, opts, seedv, ideal, x_ideal, mx, infos, ms)
+        end
+    end
+    rc != 0 && _fallback_rc(26, rc) && return loop()           # a shape outside the batch's path: the single call per start
+    _check(ctx, rc)
+    return ideal, x_ideal, mx, infos
+end
+
 # r of descent.jl:599-611, the target change of the model values: minus the reference direction, or the reference point minus f(x_n),
-# or the local ideal point (descent.jl:404-412) minus f(x_n)
-function _ds_image_direction(cfg::HipDirectedSearchConfig, mop, scal, x_it, x_it_n, sc)
+# or the local ideal point (descent.jl:404-412) minus f(x_n) -- the host search's, or with `ideal_point = :device` the device call's
+# (the runs carry the modelled and the linear constraints, as the host search's handles do; `seed` keys its generator), the host
+# search where the decision table refuses
+function _ideal_lin(scal, mop)      # the MOP's linear rows in scaled variables, the matrices d x rows (the rows x d row-major array)
+    A_eq, b_eq = transformed_linear_eq_constraints(scal, mop)
+    A_in, b_in = transformed_linear_ineq_constraints(scal, mop)
+    return (Matrix{Float64}(transpose(Matrix(A_eq))), Vector{Float64}(b_eq), Matrix{Float64}(transpose(Matrix(A_in))), Vector{Float64}(b_in))
+end
+function _ds_image_direction(cfg::HipDirectedSearchConfig, mop, scal, x_it, x_it_n, sc; seed::UInt64 = UInt64(0))
     fx_n = Vector{Float64}(get_fx(x_it_n))
     isempty(cfg.reference_direction) || return -Vector{Float64}(cfg.reference_direction)
     isempty(cfg.reference_point) || return Vector{Float64}(cfg.reference_point) .- fx_n
     n_vars = length(get_x_scaled(x_it_n))
+    if cfg.ideal_point == :device && _touches_device(sc)
+        lb_d, ub_d = local_bounds(scal, Vector{Float64}(get_x_scaled(x_it)), get_delta(x_it))
+        one = hip_local_ideal_point(_container_plan(sc), Vector{Float64}(get_x_scaled(x_it_n)), Vector{Float64}(lb_d), Vector{Float64}(ub_d);
+                                    max_evals = cfg.max_ideal_point_problem_evals, seed = seed, lin = _ideal_lin(scal, mop))
+        one === nothing || return one[1] .- fx_n
+    end
     max_evals = cfg.max_ideal_point_problem_evals < 0 ? 500 * (n_vars + 1) : cfg.max_ideal_point_problem_evals
     objf_handles, eq_handles, ineq_handles = get_raw_optim_handles(mop, sc, scal)
     lb_eff, ub_eff = local_bounds(scal, get_x_scaled(x_it), get_delta(x_it))
@@ -1108,11 +1227,13 @@ agrees (at most 16 rows in all), and the JuMP model where that call answers -2 (
 iterate's float type, or (0, zeros) when critical or ‖d‖∞ = 0 (descent.jl:615-617, :647-660); `hip_compute_descent_step(
 _ds_step_config(cfg), ..., ω, d)` does the step.
 """
-function hip_get_criticality_ds(desc_cfg::HipDirectedSearchConfig, mop, scal, x_it, x_it_n, data_base, sc::SurrogateContainer, algo_config)
+function hip_get_criticality_ds(desc_cfg::HipDirectedSearchConfig, mop, scal, x_it, x_it_n, data_base, sc::SurrogateContainer, algo_config;
+                                r = nothing, seed::UInt64 = UInt64(0))
     x_n = Vector{Float64}(get_x_scaled(x_it_n))
     Xet = eltype(get_x_scaled(x_it_n))
     n = length(x_n)
-    r = Vector{Float64}(_ds_image_direction(desc_cfg, mop, scal, x_it, x_it_n, sc))
+    # (r: an image direction computed beforehand -- hip_ds_iterate_many finds the ideal points of all starts in one call)
+    r = Vector{Float64}(r === nothing ? _ds_image_direction(desc_cfg, mop, scal, x_it, x_it_n, sc; seed = seed) : r)
     (any(r .>= 0) || any(isnan, r)) && return Xet(0), zeros(Xet, n)           # descent.jl:615-617
     function result(ω, dir)
         nrm = norm(dir, Inf)
@@ -1377,16 +1498,34 @@ Directed search for many starts in one device call (`mrbf_ds_iterate_batch`): `h
 `hip_compute_descent_step` for independent starts of one problem -- the `Threads.@threads` loop over starts of
 examples/large_scale_benchmarks.jl:102-109 -- as one chain of launches and one read-back.  `x_its[p]`, `x_it_ns[p]` and `scs[p]` are
 start p's iterate, normal-step iterate and surrogate container; `mop`, `scal` and the configuration belong to the one problem.  The
-image direction r is formed per start (`_ds_image_direction`).  For every start the result is, bit for bit, what the two single-start
+image direction r is formed per start (`_ds_image_direction`); with `ideal_point = :device` and no reference point or direction the
+ideal points of ALL starts come from one `hip_local_ideal_points_many` call before anything else (`seeds[p]` keys start p's search), and
+every start is handed its r, the ones that take the single-start functions too.  For every start the result is, bit for bit, what the two single-start
 functions return on that start alone.  Where the containers do not share one plan shape, the decision table refuses
 (`mrbf_dispatch_ds_batch`: a foreign surrogate, constraints, d > 256, more than 16 objectives, more than 65535 starts) or a start's
 direction QP gave up, those starts take the two single-start functions.  Returns a vector of (ω, d, x₊, mx₊, ‖step‖∞).
 """
 function hip_ds_iterate_many(desc_cfg::HipDirectedSearchConfig, mop, scal, x_its::AbstractVector, x_it_ns::AbstractVector, data_base,
-                             scs::AbstractVector{<:SurrogateContainer}, algo_config)
+                             scs::AbstractVector{<:SurrogateContainer}, algo_config;
+                             seeds::AbstractVector{UInt64} = zeros(UInt64, length(scs)))
     step_cfg = _ds_step_config(desc_cfg)
+    R_dev = nothing                # k × n_starts: the image directions of all starts, where the device finds the ideal points
+    if desc_cfg.ideal_point == :device && isempty(desc_cfg.reference_direction) && isempty(desc_cfg.reference_point) &&
+       length(scs) >= 1 && all(_touches_device, scs)
+        n0 = length(get_x_scaled(x_it_ns[1]))
+        X0 = Matrix{Float64}(undef, n0, length(scs)); LB0 = similar(X0); UB0 = similar(X0)
+        for p in eachindex(scs)
+            X0[:, p] .= get_x_scaled(x_it_ns[p])
+            lb_eff, ub_eff = local_bounds(scal, Vector{Float64}(get_x_scaled(x_its[p])), get_delta(x_its[p]))
+            LB0[:, p] .= lb_eff; UB0[:, p] .= ub_eff
+        end
+        many = hip_local_ideal_points_many([_container_plan(sc) for sc in scs], X0, LB0, UB0;
+                                           max_evals = desc_cfg.max_ideal_point_problem_evals, seeds = seeds, lin = _ideal_lin(scal, mop))
+        many === nothing || (R_dev = many[1] .- hcat([Vector{Float64}(get_fx(x)) for x in x_it_ns]...))
+    end
     function single(p)
-        ω, d = hip_get_criticality_ds(desc_cfg, mop, scal, x_its[p], x_it_ns[p], data_base, scs[p], algo_config)
+        ω, d = hip_get_criticality_ds(desc_cfg, mop, scal, x_its[p], x_it_ns[p], data_base, scs[p], algo_config;
+                                      r = R_dev === nothing ? nothing : R_dev[:, p], seed = seeds[p])
         ω₊, x₊, mx₊, nrm = hip_compute_descent_step(step_cfg, mop, scal, x_its[p], x_it_ns[p], data_base, scs[p], algo_config, ω, d)
         return ω₊, d, x₊, mx₊, nrm
     end
@@ -1408,7 +1547,7 @@ function hip_ds_iterate_many(desc_cfg::HipDirectedSearchConfig, mop, scal, x_its
     R = Matrix{Float64}(undef, k, ns)
     for p in 1:ns
         X[:, p] .= get_x_scaled(x_its[p]); X_n[:, p] .= get_x_scaled(x_it_ns[p])
-        R[:, p] .= _ds_image_direction(desc_cfg, mop, scal, x_its[p], x_it_ns[p], scs[p])
+        R[:, p] .= R_dev === nothing ? _ds_image_direction(desc_cfg, mop, scal, x_its[p], x_it_ns[p], scs[p]; seed = seeds[p]) : R_dev[:, p]
     end
     Δ = Float64[get_delta(x_it) for x_it in x_its]
     opts = Ref(MrbfSdStepOptions(desc_cfg.strict_backtracking, desc_cfg.max_loops, desc_cfg.armijo_const_rhs, desc_cfg.armijo_const_shrink,

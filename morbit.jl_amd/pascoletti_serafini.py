@@ -328,6 +328,29 @@ def get_criticality_device(desc_cfg, model, x, x_n, fx_n, lb_eff, ub_eff, seed=0
     return out
 
 
+def _container_constraints(sc, scal, lin, eq_tol):
+    """the constraint function of the host searches for a container and the MOP's linear rows: X -> (m, n_c), <= 0 feasible; an
+    equality counts as satisfied when |h| <= eq_tol"""
+    from . import surrogates as sg
+
+    def con(X):
+        X = np.atleast_2d(X)
+        cols = []
+        if sc.lists["nl_eq_constraint"]:
+            h = sg.eval_container_nl_eq_constraints_at_scaled_sites(sc, scal, X)
+            cols.append(np.where(np.abs(h) > eq_tol, np.abs(h), 0.0))
+        if sc.lists["nl_ineq_constraint"]:
+            cols.append(sg.eval_container_nl_ineq_constraints_at_scaled_sites(sc, scal, X))
+        if lin[1] is not None and np.asarray(lin[1]).size:
+            h = X @ np.asarray(lin[0], dtype=np.float64).T - np.asarray(lin[1], dtype=np.float64)[None, :]
+            cols.append(np.where(np.abs(h) > eq_tol, np.abs(h), 0.0))
+        if lin[3] is not None and np.asarray(lin[3]).size:
+            cols.append(X @ np.asarray(lin[2], dtype=np.float64).T - np.asarray(lin[3], dtype=np.float64)[None, :])
+        return np.hstack(cols)
+
+    return con
+
+
 def get_criticality_container(desc_cfg, sc, scal, x, x_n, fx_n, lb_eff, ub_eff, lin=None, seed=0, rng=None, stats=None, eq_tol=1e-8):
     """`get_criticality(::PascolettiSerafiniConfig, mop, scal, x_it, x_it_n, db, sc, ac)` (descent.jl:512-581) as HipRbf.jl routes it:
     the decision table of the library (mrbf_dispatch_ps / mrbf_dispatch_after) picks the device solver (objectives and modelled
@@ -359,21 +382,7 @@ def get_criticality_container(desc_cfg, sc, scal, x, x_n, fx_n, lb_eff, ub_eff, 
         return sg.eval_container_objectives_jacobian_at_scaled_sites(sc, scal, X)
 
     has_con = plan["n_con"] > 0 or n_lin > 0
-
-    def con(X):
-        X = np.atleast_2d(X)
-        cols = []
-        if sc.lists["nl_eq_constraint"]:
-            h = sg.eval_container_nl_eq_constraints_at_scaled_sites(sc, scal, X)
-            cols.append(np.where(np.abs(h) > eq_tol, np.abs(h), 0.0))
-        if sc.lists["nl_ineq_constraint"]:
-            cols.append(sg.eval_container_nl_ineq_constraints_at_scaled_sites(sc, scal, X))
-        if lin[1] is not None and np.asarray(lin[1]).size:
-            h = X @ np.asarray(lin[0], dtype=np.float64).T - np.asarray(lin[1], dtype=np.float64)[None, :]
-            cols.append(np.where(np.abs(h) > eq_tol, np.abs(h), 0.0))
-        if lin[3] is not None and np.asarray(lin[3]).size:
-            cols.append(X @ np.asarray(lin[2], dtype=np.float64).T - np.asarray(lin[3], dtype=np.float64)[None, :])
-        return np.hstack(cols)
+    con = _container_constraints(sc, scal, lin, eq_tol)
 
     return get_criticality(desc_cfg, x, x_n, fx_n, lb_eff, ub_eff, ev, eval_jacobians=jac, eval_constraints=con if has_con else None,
                            rng=rng if rng is not None else np.random.default_rng(seed), stats=stats)
@@ -486,6 +495,160 @@ def get_criticality_many(desc_cfg, containers, scal, X, X_n, FX_n, lb_effs, ub_e
         if not lib.mrbf_dispatch_after(_lib.ENTRY_PS_BATCH, rc):
             p0["models"][0].ctx.check(rc)
     return [single(p) for p in range(ns)]
+
+
+# ---- local ideal points on the device (mrbf_ideal_point_problem / mrbf_ideal_point_batch): the ideal-point phase of the step above as
+# calls of its own -- what directed search needs of it (descent._ds_image_direction, descent.ds_iterate_many) ----------------------------
+# Where the batch pays: from this many starts on ONE mrbf_ideal_point_batch call, below the loop of single calls (measured cells only,
+# tools/ideal_point_bench.py, DESIGN.md section 24: a start count is admitted where batch / loop <= 0.8 -- 1.03 at 1 start and 0.81
+# at 2, which miss it, 0.40 at 8, 0.25 at 64; 3 .. 7 starts were not measured and keep the loop).
+IDEAL_BATCH_MIN_STARTS = 8
+
+
+def _ideal_problem(plans, lin, eq_tol, carry_constraints, batch):
+    """the mrbf_ps_problem of an ideal-point call; carry_constraints=False: the box only -- constraint roles read MRBF_ROLE_NONE and
+    no linear rows are passed.  Returns (problem, handles, objects to keep alive)."""
+    import ctypes
+
+    from . import _lib
+
+    p0 = plans[0]
+    roles = list(p0["roles"])
+    if not carry_constraints:
+        roles = [r if r >= 0 else _lib.ROLE_NONE for r in roles]
+        lin = None
+    A_eq, b_eq, A_in, b_in = [None if a is None or np.asarray(a).size == 0 else np.ascontiguousarray(a, dtype=np.float64) for a in (lin or (None,) * 4)]
+    hs = [m.model.value if hasattr(m.model, "value") else m.model for p in plans for m in p["models"]]
+    handles = (ctypes.c_void_p * max(len(hs), 1))(*hs)
+    roles_c = (ctypes.c_int32 * max(len(roles), 1))(*roles)
+    prob = _lib.PsProblem(n_models=len(p0["models"]), n_objectives=p0["k"], models=None if batch else handles, roles=roles_c,
+                          n_lin_eq=0 if b_eq is None else b_eq.size, n_lin_ineq=0 if b_in is None else b_in.size,
+                          A_eq=None if b_eq is None else A_eq.ctypes.data, b_eq=None if b_eq is None else b_eq.ctypes.data,
+                          A_ineq=None if b_in is None else A_in.ctypes.data, b_ineq=None if b_in is None else b_in.ctypes.data, eq_tol=float(eq_tol))
+    return prob, handles, (roles_c, A_eq, b_eq, A_in, b_in)
+
+
+def _ideal_options(cfg, seed=0):
+    from . import _lib
+    return _lib.PsOptions(max_ideal_evals=int(cfg.max_ideal_point_problem_evals), max_ps_evals=-1, max_polish_evals=0, reserved=0,
+                          seed=int(seed) & (2 ** 64 - 1), t0=-0.5, xtol_rel=1e-3)
+
+
+def _n_carried(plan, lin, carry_constraints):
+    """(modelled constraint rows, linear rows) an ideal-point call is given"""
+    if not carry_constraints:
+        return 0, 0
+    lin = lin or (None,) * 4
+    return plan["n_con"], sum(0 if b is None else int(np.asarray(b).size) for b in (lin[1], lin[3]))
+
+
+def ideal_point_problem_device(cfg, plan, x_n, lb_eff, ub_eff, lin=None, seed=0, eq_tol=-1.0, carry_constraints=True):
+    """one mrbf_ideal_point_problem call on a container's plan: compute_local_ideal_point (descent.jl:404-412) over [lb_eff, ub_eff].
+    cfg: any configuration with `max_ideal_point_problem_evals`.  Returns (rc, ideal (k), x_ideal (k x d), m(x_n) (k), info dict)."""
+    import ctypes
+
+    from . import _lib
+
+    ctx = plan["models"][0].ctx
+    x_n, lb, ub = [np.ascontiguousarray(a, dtype=np.float64) for a in (x_n, lb_eff, ub_eff)]
+    d, k = x_n.size, plan["k"]
+    prob, handles, keep = _ideal_problem([plan], lin, eq_tol, carry_constraints, batch=False)
+    opts = _ideal_options(cfg, seed)
+    ideal, x_ideal, mx = np.empty(k), np.empty((k, d)), np.empty(k)
+    info = _lib.IdealInfo()
+    rc = ctx.lib.mrbf_ideal_point_problem(ctx.h, ctypes.byref(prob), _lib.as_ptr(x_n), _lib.as_ptr(lb), _lib.as_ptr(ub), ctypes.byref(opts),
+                                          _lib.as_ptr(ideal), _lib.as_ptr(x_ideal), _lib.as_ptr(mx), ctypes.byref(info))
+    return rc, ideal, x_ideal, mx, info.asdict()
+
+
+def ideal_points_batch_device(cfg, plans, X_n, lb_effs, ub_effs, lin=None, seeds=None, eq_tol=-1.0, carry_constraints=True, out=None):
+    """one mrbf_ideal_point_batch call on the containers' plans (one shape, checked by the caller).  X_n, lb_effs, ub_effs (n_starts x
+    d) may be NumPy arrays or device tensors; out = (ideal, x_ideal, mx) lets the caller pass its own output buffers (host or device;
+    x_ideal and mx may be None).  Returns (rc, ideal (n_starts x k), x_ideal (n_starts x k x d), mx (n_starts x k), list of info
+    dicts, event ms)."""
+    import ctypes
+
+    from . import _lib
+
+    def arr(a):
+        return a if a is None or hasattr(a, "data_ptr") else np.ascontiguousarray(a, dtype=np.float64)
+
+    ctx = plans[0]["models"][0].ctx
+    ns, k = len(plans), plans[0]["k"]
+    X_n, lb, ub = arr(X_n), arr(lb_effs), arr(ub_effs)
+    d = int((X_n.numel() if hasattr(X_n, "numel") else X_n.size) // ns)
+    prob, handles, keep = _ideal_problem(plans, lin, eq_tol, carry_constraints, batch=True)
+    opts = _ideal_options(cfg)
+    seeds_c = None if seeds is None else (ctypes.c_uint64 * ns)(*[int(s) & (2 ** 64 - 1) for s in seeds])
+    ideal, x_ideal, mx = out if out is not None else (np.empty((ns, k)), np.empty((ns, k, d)), np.empty((ns, k)))
+    infos = (_lib.IdealInfo * ns)()
+    ms = ctypes.c_float()
+    rc = ctx.lib.mrbf_ideal_point_batch(ctx.h, ns, ctypes.byref(prob), handles, _lib.as_ptr(X_n), _lib.as_ptr(lb), _lib.as_ptr(ub),
+                                        ctypes.byref(opts), seeds_c, _lib.as_ptr(ideal), _lib.as_ptr(x_ideal), _lib.as_ptr(mx), infos,
+                                        ctypes.byref(ms))
+    return rc, ideal, x_ideal, mx, [i.asdict() for i in infos], ms.value
+
+
+def compute_local_ideal_points_many(cfg, containers, X_n, lb_effs, ub_effs, lin=None, seeds=None, carry_constraints=True, stats=None,
+                                    scal=None, eq_tol=1e-8):
+    """`compute_local_ideal_point` (descent.jl:404-412) for many independent starts of one problem: containers[p] is start p's
+    surrogate container, X_n[p] the point its runs start from, lb_effs[p] / ub_effs[p] its box; lin = (A_eq, b_eq, A_ineq, b_ineq)
+    belongs to the one MOP; seeds[p] keys start p's generator (None: 0 for every start); carry_constraints=False searches the box
+    only.  Where the containers share one plan shape and mrbf_dispatch_ideal_batch says so, ONE mrbf_ideal_point_batch call serves all
+    starts from IDEAL_BATCH_MIN_STARTS starts on ("batch"); below that count, or where only the single call's row admits the shape,
+    the loop of mrbf_ideal_point_problem calls ("loop"); where the table refuses, the host search per start ("reference", which needs
+    `scal`).  Returns the ideal points (n_starts x k); stats gets "path" and, on the device paths, "infos", "x_ideal", "mx" and
+    "ms_total"."""
+    from . import _lib
+    from . import surrogates as sg
+
+    lib = _lib.load()
+    X_n, lb_effs, ub_effs = [np.asarray(a, dtype=np.float64) for a in (X_n, lb_effs, ub_effs)]
+    ns = len(containers)
+    seeds = [0] * ns if seeds is None else [int(s) for s in seeds]
+    if ns == 0:
+        if stats is not None:
+            stats["path"] = "loop"
+        return np.empty((0, 0))
+    plans = [sg.container_plan(sc) for sc in containers]
+    p0 = plans[0]
+    d = int(X_n.shape[1])
+    sig0 = ([m.num_outputs for m in p0["models"]], p0["roles"], p0["k"], p0["n_con"], p0["n_foreign"])
+    same = all(([m.num_outputs for m in p["models"]], p["roles"], p["k"], p["n_con"], p["n_foreign"]) == sig0 for p in plans[1:])
+    n_nl, n_lin = _n_carried(p0, lin, carry_constraints)
+    if (same and ns >= IDEAL_BATCH_MIN_STARTS and
+            lib.mrbf_dispatch_ideal_batch(ns, d, p0["k"], len(p0["models"]), n_nl, n_lin, p0["n_foreign"]) == _lib.DISPATCH_DEVICE):
+        rc, ideal, x_ideal, mx, infos, ms = ideal_points_batch_device(cfg, plans, X_n, lb_effs, ub_effs, lin=lin, seeds=seeds, eq_tol=eq_tol,
+                                                                      carry_constraints=carry_constraints)
+        if rc == 0:
+            if stats is not None:
+                stats.update(path="batch", infos=infos, x_ideal=x_ideal, mx=mx, ms_total=ms)
+            return ideal
+        if not lib.mrbf_dispatch_after(_lib.ENTRY_IDEAL_BATCH, rc):
+            p0["models"][0].ctx.check(rc)
+    out, infos, xs, mxs, path = [], [], [], [], "loop"
+    for p in range(ns):
+        plan = plans[p]
+        n_nl, n_lin = _n_carried(plan, lin, carry_constraints)
+        rc = -2
+        if lib.mrbf_dispatch_ideal(d, plan["k"], len(plan["models"]), n_nl, n_lin, plan["n_foreign"]) == _lib.DISPATCH_DEVICE:
+            rc, ideal, x_ideal, mx, info = ideal_point_problem_device(cfg, plan, X_n[p], lb_effs[p], ub_effs[p], lin=lin, seed=seeds[p],
+                                                                      eq_tol=eq_tol, carry_constraints=carry_constraints)
+            if rc != 0 and not lib.mrbf_dispatch_after(_lib.ENTRY_IDEAL, rc):
+                plan["models"][0].ctx.check(rc)
+        if rc == 0:
+            out.append(ideal), infos.append(info), xs.append(x_ideal), mxs.append(mx)
+            continue
+        path = "reference"       # the host search for this start, with the constraints it is asked to carry
+        max_evals = 500 * (d + 1) if cfg.max_ideal_point_problem_evals < 0 else cfg.max_ideal_point_problem_evals
+        sc = containers[p]
+        con = _container_constraints(sc, scal, lin or (None,) * 4, eq_tol) if carry_constraints and (n_nl or n_lin) else None
+        out.append(compute_local_ideal_point(X_n[p], lb_effs[p], ub_effs[p], lambda X: sg.eval_container_objectives_at_scaled_sites(sc, scal, X),
+                                             plan["k"], max_evals, np.random.default_rng(seeds[p]), con))
+        infos.append(None), xs.append(None), mxs.append(None)
+    if stats is not None:
+        stats.update(path=path, infos=infos, x_ideal=xs, mx=mxs)
+    return np.stack(out)
 
 
 def get_criticality(desc_cfg, x, x_n, fx_n, lb_eff, ub_eff, eval_objectives: Callable, eval_jacobians: Optional[Callable] = None,
