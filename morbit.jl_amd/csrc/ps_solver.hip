@@ -1,6 +1,6 @@
 // Pascoletti-Serafini descent step with the whole subproblem solver on the device -- replaces the NLopt runs of
 // compute_local_ideal_point / _ps_optimization inside get_criticality(::PascolettiSerafiniConfig, ...)
-// (/root/reference/src/descent.jl:369-412, :434-510, :512-581).
+// (Morbit.jl src/descent.jl:369-412, :434-510, :512-581).
 //
 // The reference hands one-point closures to NLopt's GN_ISRES: every candidate costs one sweep over all n centres PER OUTPUT.
 // Here the subproblems are solved by an ISRES-style (mu, lambda) evolution strategy (Runarsson & Yao; population 20 (dim + 1),
@@ -26,20 +26,18 @@
 // descent_method = :ps -- take the same kernels in ONE call (mrbf_ps_step_batch): every start has its block (ps::Args: runs, box,
 // x_n, m(x_n), r, seed, result blocks) in device memory, the start is a grid dimension, a generation of all starts is one sweep per
 // launch group (batch_chain.hpp), one ranking and one breeding launch, and the refinements advance in lockstep.  The single call is
-// the batch of one (ps_step_many).  DESIGN.md section 15.
+// the batch of one (ps_open, ps_ideal_phase, ps_step_phase, ps_close over one PsCall).  DESIGN.md section 15.  The host arithmetic
+// -- limits, sizes, budgets, the refinement's state machine -- is ps_host.hpp's.
 #include "batch_chain.hpp"
 #include "ideal_host.hpp"
+#include "ps_host.hpp"
 #include "radial.hpp"
 
 namespace mrbf {
 
 namespace ps {
 
-constexpr int MAXLAM = 7168;   // population limit: the ranking keeps one run's records in one workgroup's LDS
-constexpr int MAXRUNS = 9;     // k <= 8 ideal-point runs side by side, or the PS run
-constexpr int MAXMODELS = 8;   // grouped models of one container
-constexpr int MAXOBJ = 8;
-constexpr int MAXCON = 32;     // modelled (nonlinear) constraint rows
+// (MAXLAM, MAXRUNS, MAXMODELS, MAXOBJ, MAXCON: ps_host.hpp)
 constexpr int RANK_THREADS = 1024;
 // ranking of a large population on several compute units (ps_rank_wave_kernel): phases between two no-swap tests (the exit-rule
 // period), smallest population that takes this path, compute units the device must have per run for it (the waves of a run wait for
@@ -1198,37 +1196,6 @@ __global__ __launch_bounds__(256) void ps_breed_kernel(const Args *__restrict__ 
     }
 }
 
-// host view of the problem (function table, constraints) shared by the driver and the polish
-struct Problem {
-    int nmodels = 0, nobj = 0, nftot = 0, d = 0;
-    const mrbf_model *models[MAXMODELS] = {};
-    int foff[MAXMODELS] = {};  // first column of model j in the concatenated function vector
-    int obj_model[MAXOBJ] = {}, obj_col[MAXOBJ] = {};
-    int ncon = 0, con_model[MAXCON] = {}, con_col[MAXCON] = {}, con_eq[MAXCON] = {};
-    int nlin_eq = 0, nlin_ineq = 0;
-    std::vector<double> A_eq, b_eq, A_ineq, b_ineq;  // host copies (polish, final feasibility)
-    const double *dA_eq = nullptr, *db_eq = nullptr, *dA_ineq = nullptr, *db_ineq = nullptr;
-    double eq_tol = 1e-8;
-    double objective(const std::vector<double> &allF, int l) const { return allF[foff[obj_model[l]] + obj_col[l]]; }
-    // sum of squared violations of the modelled and linear constraints at x (allF = all model outputs at x)
-    double violation(const std::vector<double> &allF, const double *x) const {
-        double phi = 0.0;
-        for (int c = 0; c < ncon; ++c) {
-            const double v = allF[foff[con_model[c]] + con_col[c]];
-            if (con_eq[c] ? std::fabs(v) > eq_tol : v > 0.0) phi += v * v;
-            if (!(v == v)) phi = INFINITY;
-        }
-        for (int c = 0; c < nlin_eq + nlin_ineq; ++c) {
-            const bool eq = c < nlin_eq;
-            const double *Ar = eq ? &A_eq[(size_t)c * d] : &A_ineq[(size_t)(c - nlin_eq) * d];
-            double s = 0.0;
-            for (int j = 0; j < d; ++j) s = std::fma(Ar[j], x[j], s);
-            s -= eq ? b_eq[c] : b_ineq[c - nlin_eq];
-            if (eq ? std::fabs(s) > eq_tol : s > 0.0) phi += s * s;
-        }
-        return phi;
-    }
-};
 
 }  // namespace ps
 
@@ -1305,6 +1272,28 @@ static void rank_launch(mrbf_ctx *ctx, const ps::Args *dA, int nstarts, int nrun
     hipLaunchKernelGGL(ps_rank_kernel, dim3(NR, NS), dim3(L.threads), L.shm, ctx->stream, dA, gen, 2, L.ws);
 }
 
+// A downloaded evaluation of m points into allF (row-major m x nftot) and, where Jobj is given, the objectives' Jacobian rows
+// ([point][objective][coordinate]).  blocks: model j's m x k_j values at m * foff[j]; Jm[j]: model j's Jacobians, per point k_j x d
+// column-major (read for the objectives' models only).
+static void ps_unpack_eval(const ps::Problem &P, int m, const double *blocks, const double *const *Jm, std::vector<double> &allF,
+                           std::vector<double> *Jobj) {
+    const int d = P.d;
+    allF.resize((size_t)m * P.nftot);
+    for (int j = 0; j < P.nmodels; ++j) {
+        const int kj = P.models[j]->k;
+        for (int p = 0; p < m; ++p)
+            for (int c = 0; c < kj; ++c) allF[(size_t)p * P.nftot + P.foff[j] + c] = blocks[(size_t)m * P.foff[j] + (size_t)p * kj + c];
+    }
+    if (!Jobj) return;
+    Jobj->resize((size_t)m * P.nobj * d);
+    for (int p = 0; p < m; ++p)
+        for (int l = 0; l < P.nobj; ++l) {
+            const int j = P.obj_model[l], kj = P.models[j]->k;
+            const double *Jp = Jm[j] + (size_t)p * kj * d;
+            for (int t = 0; t < d; ++t) (*Jobj)[((size_t)p * P.nobj + l) * d + t] = Jp[(size_t)t * kj + P.obj_col[l]];
+        }
+}
+
 // all model outputs at m points (row-major m x nftot) and, optionally (m == 1), the objectives' Jacobian rows
 static int ps_eval_points(mrbf_ctx *ctx, const ps::Problem &P, const double *x_host, int m, std::vector<double> &allF, std::vector<double> *Jobj) {
     const int d = P.d;
@@ -1337,9 +1326,7 @@ static int ps_eval_points(mrbf_ctx *ctx, const ps::Problem &P, const double *x_h
     }
     std::vector<double *> jp(P.nmodels, nullptr), vp(P.nmodels, nullptr);
     for (int j = 0; j < P.nmodels; ++j) {
-        bool need = false;
-        for (int l = 0; Jobj && l < P.nobj; ++l) need = need || P.obj_model[l] == j;
-        jp[j] = need ? dJ : nullptr;
+        jp[j] = Jobj && P.model_has_objective(j) ? dJ : nullptr;
         vp[j] = dV + (size_t)m * P.foff[j];  // model j's m x k_j block
         MRBF_TRY(eval_model(ctx, P.models[j], m, dX, vp[j], jp[j], nullptr));
         dJ += (size_t)(Jobj ? m : 1) * P.models[j]->k * d;
@@ -1366,209 +1353,9 @@ static int ps_eval_points(mrbf_ctx *ctx, const ps::Problem &P, const double *x_h
             }
     }
     MRBF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    allF.resize((size_t)m * P.nftot);
-    for (int j = 0; j < P.nmodels; ++j) {
-        const int kj = P.models[j]->k;
-        for (int p = 0; p < m; ++p)
-            for (int c = 0; c < kj; ++c) allF[(size_t)p * P.nftot + P.foff[j] + c] = blocks[(size_t)m * P.foff[j] + (size_t)p * kj + c];
-    }
-    if (Jobj) {  // [point][objective][coordinate]
-        Jobj->resize((size_t)m * P.nobj * d);
-        for (int p = 0; p < m; ++p)
-            for (int l = 0; l < P.nobj; ++l) {
-                const int j = P.obj_model[l], kj = P.models[j]->k;
-                const double *Jp = Jm[j] + (size_t)p * kj * d;  // per point k x d column-major
-                for (int t = 0; t < d; ++t) (*Jobj)[((size_t)p * P.nobj + l) * d + t] = Jp[(size_t)t * kj + P.obj_col[l]];
-            }
-    }
+    ps_unpack_eval(P, m, blocks, Jm.data(), allF, Jobj);
     return 0;
 }
-static int ps_eval_point(mrbf_ctx *ctx, const ps::Problem &P, const double *x_host, std::vector<double> &allF, std::vector<double> *Jobj) {
-    return ps_eval_points(ctx, P, x_host, 1, allF, Jobj);
-}
-
-// weights of the proximal minimax step: minimise  sigma / 2 |sum_l lam_l g_l|^2 - sum_l lam_l gap_l  over the simplex (M = G G',
-// gap_l = F_l - max F <= 0), Frank-Wolfe with exact line search.  sigma -> infinity: the minimum-norm point of the hull of ALL
-// gradients (the common descent direction); sigma -> 0: the gradient of the active objective alone.  In between an objective
-// counts as far as a step of that length can make it active -- no fixed "nearly active" tolerance.
-static void prox_weights(int k, const std::vector<double> &M, const std::vector<double> &gap, double sigma, std::vector<double> &lam) {
-    int b0 = 0;
-    for (int a = 1; a < k; ++a)
-        if (gap[a] > gap[b0]) b0 = a;
-    lam.assign(k, 0.0);
-    lam[b0] = 1.0;
-    std::vector<double> Ml(k);
-    for (int it = 0; it < 400; ++it) {
-        double lMl = 0.0, lg = 0.0;
-        for (int a = 0; a < k; ++a) {
-            Ml[a] = 0.0;
-            for (int b = 0; b < k; ++b) Ml[a] += M[(size_t)a * k + b] * lam[b];
-            lMl += lam[a] * Ml[a];
-            lg += lam[a] * gap[a];
-        }
-        int best = 0;
-        double gbest = sigma * Ml[0] - gap[0];
-        for (int a = 1; a < k; ++a) {
-            const double ga = sigma * Ml[a] - gap[a];
-            if (ga < gbest) {
-                gbest = ga;
-                best = a;
-            }
-        }
-        const double slope = (sigma * lMl - lg) - gbest;  // -(directional derivative towards the vertex) >= 0
-        if (slope <= 1e-14 * std::max(std::fabs(sigma * lMl) + std::fabs(lg), 1e-300)) break;
-        const double curv = sigma * (lMl - 2.0 * Ml[best] + M[(size_t)best * k + best]);
-        const double gamma = curv > 0.0 ? std::min(1.0, slope / curv) : 1.0;
-        for (int a = 0; a < k; ++a) lam[a] *= (1.0 - gamma);
-        lam[best] += gamma;
-    }
-}
-
-// Gradient refinement of a point of the box: a proximal steepest-descent method for
-//     min_x  max_{l in objs} (m_l(x) - off_l) / scale_l     subject to the problem's constraints and the box
-// -- the Pascoletti-Serafini subproblem itself with objs = all objectives, off = m(x_n), scale = r (the value is tau, kept in
-// [-1, 0]), one objective of the local ideal point with objs = {l}, off = 0, scale = 1.  (The reference hands a local NLopt
-// algorithm for the polish, descent.jl:560-569; the paper benchmark uses :LD_MMA with 100 (d + 1) evaluations,
-// examples/large_scale_benchmarks.jl:217-219.)  Per iteration one evaluation with Jacobians, then NSTEP trial points
-// x - sigma_u sum_l lam_l(sigma_u) g_l for NSTEP proximity parameters a factor two apart (each with its own weights, see
-// prox_weights), projected onto the box, evaluated as ONE batch; components that the step would push through an active bound are
-// taken out and the weights recomputed.  The best feasible improving trial point is taken; the range of sigma follows the accepted
-// steps.  It stops when the budget is used up or no step down to 1e-9 of the box improves (stationarity), NOT at the first line
-// search without improvement.  Every accepted iterate is feasible.  Each iteration costs 1 + NSTEP evaluations.
-// One proximal minimax descent as a state machine: `trials` writes the NSTEP trial points of the next iteration (false: the descent has
-// ended), `consume` takes their values and Jacobians.  Several independent descents (the k ideal-point refinements) advance in
-// lockstep through ONE evaluation per iteration (ps_descend_groups) -- a round trip per iteration for all of them instead of one each.
-struct Descent {
-    static constexpr int NSTEP = 12;
-    const ps::Problem *P = nullptr;
-    const std::vector<double> *lb = nullptr, *ub = nullptr;
-    std::vector<int> objs;
-    std::vector<double> off, scale;
-    bool clamp = false;
-    int max_evals = 0;
-    double xtol_rel = 0.0;
-    double val = 0.0;
-    std::vector<double> x;
-    // state
-    int evals = 0, nsmall = 0;
-    double width = 0.0, frac = 0.25;  // the largest trial step moves the fastest component by `frac` of the box
-    bool have = false, done = false;  // have: allF / J hold the values and the objectives' Jacobian rows at x
-    std::vector<double> allF, J, XT;
-
-    void start() {
-        const int d = P->d;
-        width = 0.0;
-        for (int t = 0; t < d; ++t) width = std::max(width, (*ub)[t] - (*lb)[t]);
-        XT.assign((size_t)NSTEP * d, 0.0);
-        done = !(width > 0.0);
-    }
-    bool wants_start_eval() const { return !done && !have && evals + 1 + NSTEP <= max_evals; }
-    void take_start(const double *F_row, const double *J_rows) {  // values (nftot) and Jacobian rows (nobj x d) at x
-        allF.assign(F_row, F_row + P->nftot);
-        J.assign(J_rows, J_rows + (size_t)P->nobj * P->d);
-        ++evals;
-        have = true;
-    }
-    // the trial points of the next iteration into XT; false: ended (budget, no gradient, range exhausted)
-    bool trials() {
-        if (done) return false;
-        if (!have || evals + NSTEP > max_evals) {
-            done = true;
-            return false;
-        }
-        const int d = P->d, k = (int)objs.size();
-        std::vector<double> F(k), gap(k), dir(d), M((size_t)k * k), lam, G((size_t)k * d);
-        std::vector<char> fixed(d);
-        double tmax = -INFINITY, gmax = 0.0;
-        for (int l = 0; l < k; ++l) {
-            F[l] = (P->objective(allF, objs[l]) - off[l]) / scale[l];
-            tmax = std::max(tmax, F[l]);
-        }
-        for (int l = 0; l < k; ++l) {
-            gap[l] = F[l] - tmax;
-            for (int t = 0; t < d; ++t) {
-                G[(size_t)l * d + t] = J[(size_t)objs[l] * d + t] / scale[l];
-                gmax = std::max(gmax, std::fabs(G[(size_t)l * d + t]));
-            }
-        }
-        if (!(gmax > 0.0) || !(gmax < INFINITY)) {
-            done = true;
-            return false;
-        }
-        const double sigma0 = frac * width / gmax;
-        for (int u = 0; u < NSTEP; ++u) {
-            const double sigma = sigma0 * std::ldexp(1.0, -u);
-            std::fill(fixed.begin(), fixed.end(), 0);
-            for (int pass = 0; pass < 2; ++pass) {
-                for (int a = 0; a < k; ++a)
-                    for (int b = 0; b <= a; ++b) {
-                        double sdot = 0.0;
-                        for (int t = 0; t < d; ++t)
-                            if (!fixed[t]) sdot += G[(size_t)a * d + t] * G[(size_t)b * d + t];
-                        M[(size_t)a * k + b] = M[(size_t)b * k + a] = sdot;
-                    }
-                prox_weights(k, M, gap, sigma, lam);
-                bool changed = false;
-                for (int t = 0; t < d; ++t) {
-                    double v = 0.0;
-                    if (!fixed[t])
-                        for (int a = 0; a < k; ++a) v -= sigma * lam[a] * G[(size_t)a * d + t];
-                    dir[t] = v;
-                    if (!fixed[t] && ((x[t] <= (*lb)[t] && v < 0.0) || (x[t] >= (*ub)[t] && v > 0.0))) {
-                        fixed[t] = 1;
-                        dir[t] = 0.0;
-                        changed = true;
-                    }
-                }
-                if (!changed) break;
-            }
-            for (int t = 0; t < d; ++t) XT[(size_t)u * d + t] = std::min(std::max(x[t] + dir[t], (*lb)[t]), (*ub)[t]);
-        }
-        return true;
-    }
-    // values (NSTEP x nftot) and Jacobian rows (NSTEP x nobj x d) of the trial points
-    void consume(const double *allFT, const double *JT) {
-        const int d = P->d, k = (int)objs.size();
-        std::vector<double> row(P->nftot);
-        evals += NSTEP;
-        int bestj = -1;
-        double bestv = val - 1e-13 * std::max(1.0, std::fabs(val));
-        for (int j = 0; j < NSTEP; ++j) {
-            for (int c = 0; c < P->nftot; ++c) row[c] = allFT[(size_t)j * P->nftot + c];
-            double tt = -INFINITY;
-            for (int l = 0; l < k; ++l) tt = std::max(tt, (P->objective(row, objs[l]) - off[l]) / scale[l]);
-            if (!(tt == tt) || !(tt < INFINITY)) continue;
-            bool feas = P->violation(row, &XT[(size_t)j * d]) == 0.0;
-            if (clamp) {
-                // tau = the t this x admits, a hair towards 0 so that rounding cannot make the PS constraints fail (descent.jl:443)
-                tt = std::min(std::max(tt < 0.0 ? tt * (1.0 - 1e-14) : tt, -1.0), 0.0);
-                for (int l = 0; l < k; ++l) feas = feas && (P->objective(row, objs[l]) - off[l] - tt * scale[l] <= 0.0);
-            }
-            if (feas && tt < bestv) {
-                bestv = tt;
-                bestj = j;
-            }
-        }
-        if (bestj < 0) {
-            frac *= std::ldexp(1.0, -NSTEP);  // nothing down to 2^-11 of the range improved: continue below it
-            if (frac < 1e-9) done = true;
-            return;
-        }
-        bool small = true;  // NLopt's xtol_rel test (descent.jl:379, :485), on two accepted steps in a row
-        for (int t = 0; t < d; ++t) {
-            const double xn2 = XT[(size_t)bestj * d + t];
-            small = small && std::fabs(xn2 - x[t]) <= xtol_rel * std::max(std::fabs(xn2), 1e-300);
-            x[t] = xn2;
-        }
-        allF.assign(allFT + (size_t)bestj * P->nftot, allFT + (size_t)(bestj + 1) * P->nftot);
-        J.assign(JT + (size_t)bestj * P->nobj * d, JT + (size_t)(bestj + 1) * P->nobj * d);
-        val = bestv;
-        frac = std::min(1.0, frac * std::ldexp(4.0, -bestj));  // the accepted step sits two levels below the top of the next range
-        if (clamp && val <= -1.0) done = true;
-        nsmall = small ? nsmall + 1 : 0;
-        if (nsmall >= 2) done = true;
-    }
-};
 
 // one evaluation of the refinement: all model outputs of problem P at m points (and the objectives' Jacobian rows)
 struct EvalReq {
@@ -1591,11 +1378,7 @@ static int ps_eval_points_many(mrbf_ctx *ctx, std::vector<EvalReq> &reqs) {
     for (size_t i = 0; i < R; ++i) {
         const ps::Problem &P = *reqs[i].P;
         oX[i] = ar.take((size_t)reqs[i].m * P.d);
-        for (int j = 0; j < P.nmodels; ++j) {
-            bool need = false;
-            for (int l = 0; reqs[i].Jobj && l < P.nobj; ++l) need = need || P.obj_model[l] == j;
-            ev.add(ctx, 0, (int64_t)i, j, P.models[j], reqs[i].m, need);
-        }
+        for (int j = 0; j < P.nmodels; ++j) ev.add(ctx, 0, (int64_t)i, j, P.models[j], reqs[i].m, reqs[i].Jobj && P.model_has_objective(j));
     }
     ev.close();
     const size_t oDesc = ar.take(ev.desc_doubles());
@@ -1627,25 +1410,10 @@ static int ps_eval_points_many(mrbf_ctx *ctx, std::vector<EvalReq> &reqs) {
     MRBF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (size_t i = 0; i < R; ++i) {
         const ps::Problem &P = *reqs[i].P;
-        const int m = reqs[i].m, d = P.d;
-        const double *blocks = hdown + (oV[i] - up_cnt);
-        std::vector<double> &allF = *reqs[i].allF;
-        allF.resize((size_t)m * P.nftot);
-        for (int j = 0; j < P.nmodels; ++j) {
-            const int kj = P.models[j]->k;
-            for (int p = 0; p < m; ++p)
-                for (int c = 0; c < kj; ++c) allF[(size_t)p * P.nftot + P.foff[j] + c] = blocks[(size_t)m * P.foff[j] + (size_t)p * kj + c];
-        }
-        if (reqs[i].Jobj) {  // [point][objective][coordinate]
-            std::vector<double> &Jobj = *reqs[i].Jobj;
-            Jobj.resize((size_t)m * P.nobj * d);
-            for (int p = 0; p < m; ++p)
-                for (int l = 0; l < P.nobj; ++l) {
-                    const int j = P.obj_model[l], kj = P.models[j]->k;
-                    const double *Jp = hdown + (oJ[i * ps::MAXMODELS + j] - up_cnt) + (size_t)p * kj * d;  // per point k x d column-major
-                    for (int t = 0; t < d; ++t) Jobj[((size_t)p * P.nobj + l) * d + t] = Jp[(size_t)t * kj + P.obj_col[l]];
-                }
-        }
+        const double *Jm[ps::MAXMODELS] = {};
+        for (int j = 0; j < P.nmodels; ++j)
+            if (reqs[i].Jobj && P.model_has_objective(j)) Jm[j] = hdown + (oJ[i * ps::MAXMODELS + j] - up_cnt);
+        ps_unpack_eval(P, reqs[i].m, hdown + (oV[i] - up_cnt), Jm, *reqs[i].allF, reqs[i].Jobj);
     }
     return 0;
 }
@@ -1737,16 +1505,13 @@ static void ps_problem_fill(ps::Problem &P, const descent::Layout &lay, const mr
 }
 
 // doubles of device memory a start of the step takes in the state slot (run state, evaluation batch, results and the sweeps' scratch):
-// mrbf_ps_step_batch sizes its chunks of starts with it.  An estimate of "the state": the ranking's work space (S_PS_RANK: only while
+// the chunk loop sizes its chunks of starts with it.  An estimate of "the state": the ranking's work space (S_PS_RANK: only while
 // at most 16 runs share a launch) and the refinement's chain (S_PS_POLISH: a few points per start) are not counted.
-// ideal_only: the PS run's part is not there (mrbf_ideal_point_batch).
 static size_t ps_start_doubles(const mrbf_ctx *ctx, const mrbf_model *const *models, int nm, int d, int k, int nftot, bool need_ideal,
-                               bool ideal_only = false) {
-    const size_t lam_ip = 20 * (size_t)(d + 1), lam_ps = ideal_only ? 0 : 20 * (size_t)(d + 2);
-    const size_t rows = std::max(need_ideal ? k * lam_ip : 0, lam_ps);
-    const size_t state = std::max(need_ideal ? k * (4 * lam_ip * d + 3 * lam_ip) : 0, 4 * lam_ps * (d + 1) + 3 * lam_ps);
+                               bool with_ps) {
+    const ps::Sizes z = ps::sizes(d, k, need_ideal, with_ps);
     size_t scratch = 0;  // of the larger sweep: centred queries, their norms and the partial sums of a split centre range, per model slot
-    for (size_t m : {need_ideal ? k * lam_ip : 0, lam_ps}) {
+    for (size_t m : {(size_t)(need_ideal ? k * z.lam_ip : 0), (size_t)z.lam_ps}) {
         size_t s = 0;
         for (int j = 0; j < nm && m; ++j) {
             const size_t mpad = (size_t)round_up((int64_t)m, 64);
@@ -1755,353 +1520,342 @@ static size_t ps_start_doubles(const mrbf_ctx *ctx, const mrbf_model *const *mod
         }
         scratch = std::max(scratch, s);
     }
-    return rows * (d + nftot) + state + scratch + 4096;
+    return (size_t)z.rows * (d + nftot) + z.state + scratch + 4096;
 }
 
-// The step for the starts of S (mrbf_ps_step_problem: one; mrbf_ps_step_batch: a batch, or a chunk of one): the phases of
-// get_criticality(::PascolettiSerafiniConfig, ...) for all starts together.  Per generation ONE population sweep per launch group,
-// the optional score launch, the ranking and the breeding for every run of every start that takes part in the phase; the refinements
-// advance in lockstep.  Nothing a start computes depends on another start: its block, its runs' indices and its seed are its own, a
-// finished run is inert in every kernel (R.stat[1], R.stat[3] != gen + 1), the evaluations keep the single call's query counts.
-// ideal_only (mrbf_ideal_point_problem / mrbf_ideal_point_batch; with need_ideal): the call ends behind the ideal-point phase -- every
-// start's ideal, x_ideal, found, refined, mx = m(x_n) and info.evals_ideal / generations are set, r and the PS run are not touched
-// and the arena holds no room for that run.  Where a piece lies in the arena changes nothing a kernel computes.
-static int ps_step_many(mrbf_ctx *ctx, std::vector<PsStart> &S, bool need_ideal, const mrbf_ps_options *opts, float *ms_out,
-                        bool ideal_only = false) {
-    using namespace ps;
-    const size_t N = S.size();
-    const bool single = N == 1;  // the one start's evaluations are eval_model's own launches (its arena slots, its pinned block)
-    const Problem &P0 = S[0].P;
-    const int d = P0.d, k = P0.nobj, nm = P0.nmodels, nftot = P0.nftot;
-    hipStream_t st = ctx->stream;
-    hipEvent_t e0 = ctx->ev[0], e1 = ctx->ev[1];
-    MRBF_HIP(ctx, hipEventRecord(e0, st));
-    const int lam_ip = 20 * (d + 1), lam_ps = 20 * (d + 2);
-    const int rows = std::max(need_ideal ? k * lam_ip : 0, ideal_only ? 0 : lam_ps);
-    // ---- device arena: linear constraints, the starts' blocks, boxes and start points, mx, r, the runs' best records, then per start the
+// ---- The step for the starts of S (the single calls: one; the batch calls: a batch, or a chunk of one): the phases of
+// get_criticality(::PascolettiSerafiniConfig, ...) for all starts together, as functions over one PsCall -- ps_open, then
+// ps_ideal_phase where no direction was given, then ps_step_phase, then ps_close; the ideal-point calls open without room for the PS
+// run and leave ps_step_phase out.  Per generation ONE population sweep per launch group, the optional score launch, the ranking and
+// the breeding for every run of every start that takes part in the phase; the refinements advance in lockstep.  Nothing a start
+// computes depends on another start: its block, its runs' indices and its seed are its own, a finished run is inert in every kernel
+// (R.stat[1], R.stat[3] != gen + 1), the evaluations keep the single call's query counts.  Where a piece lies in the arena changes
+// nothing a kernel computes.
+enum { SITE_IP = 0, SITE_PS = 1 };
+struct PsCall {
+    mrbf_ctx *ctx = nullptr;
+    std::vector<PsStart> *S = nullptr;
+    const mrbf_ps_options *opts = nullptr;
+    size_t N = 0;
+    bool single = false;  // the one start's evaluations are eval_model's own launches (its arena slots, its pinned block)
+    int d = 0, k = 0, nm = 0, nftot = 0;
+    ps::Sizes sz{};
+    // device arena: linear constraints, the starts' blocks, boxes and start points, mx, r, the runs' best records, then per start the
     // evaluation batch, its results and the runs' state; in a batch also the sweeps' descriptors and scratch (batch_chain.hpp)
+    size_t oLin = 0, oArgs = 0, oBox = 0, oMx = 0, oR = 0, oBest = 0, oDesc = 0;
+    std::vector<size_t> oStart;
+    double *base = nullptr;
+    int *stat = nullptr;
+    const ps::Args *dA = nullptr;
+    const double *dlin[4] = {};  // A_eq, b_eq, A_ineq, b_ineq in the arena
+    chain::Plan ev_ip, ev_ps_all, ev_ps;  // the sweeps of the two phases over all starts; the PS sweep of the starts that take part
+    int max_ip = 0, max_ps = 0, res_ip = 0, res_ps = 0;
+    double xtol = 0.0;
+    int dbg = 0;
+    // host staging: sources and targets of asynchronous copies, alive for the whole call
+    std::vector<double> hbox, hmx, hr, hbest;
+    std::vector<ps::Args> harr;
+    std::vector<EvalDesc> hdesc;
+    std::vector<int> hs;
+    std::vector<std::vector<double>> allF;  // m(x_n), later m(x_trial), per start
+};
+
+// the part of start p's state behind the evaluation batch and its results: where the runs of a phase are laid out
+static double *ps_runs_at(const PsCall &c, size_t p) { return c.base + c.oStart[p] + (size_t)c.sz.rows * c.d + (size_t)c.sz.rows * c.nftot; }
+
+static void ps_make_run(ps::Run &R, int kind, int obj, int lam, int nvar, int off, int max_evals, double *&p, double *best, int *stp) {
+    R.kind = kind, R.obj = obj, R.lam = lam, R.mu = (lam + 6) / 7, R.nvar = nvar, R.off = off, R.max_evals = max_evals;
+    for (int b = 0; b < 2; ++b) {
+        R.X[b] = p, p += (size_t)lam * nvar;
+        R.S[b] = p, p += (size_t)lam * nvar;
+    }
+    R.f = p, p += lam;
+    R.phi = p, p += lam;
+    R.order = (int *)p, p += lam;
+    R.best = best, R.stat = stp;
+}
+
+// the block of start p (everything but the runs)
+static void ps_make_args(const PsCall &c, size_t p) {
+    const int d = c.d, k = c.k;
+    PsStart &s = (*c.S)[p];
+    const ps::Problem &P = s.P;
+    ps::Args &a = s.a;
+    a = ps::Args{};
+    a.d = d, a.nobj = k;
+    a.lb = c.base + c.oBox + p * 3 * d, a.ub = a.lb + d, a.xn = a.ub + d;
+    a.mx = c.base + c.oMx + p * k;
+    a.r = c.base + c.oR + p * k;
+    a.nmodels = c.nm;
+    double *fp = c.base + c.oStart[p] + (size_t)c.sz.rows * d;
+    for (int j = 0; j < c.nm; ++j) {
+        a.F[j] = fp;
+        a.kf[j] = P.models[j]->k;
+        fp += (size_t)c.sz.rows * P.models[j]->k;
+    }
+    for (int l = 0; l < k; ++l) a.obj_model[l] = (short)P.obj_model[l], a.obj_col[l] = (short)P.obj_col[l];
+    a.ncon = P.ncon;
+    for (int q = 0; q < P.ncon; ++q) a.con_model[q] = (short)P.con_model[q], a.con_col[q] = (short)P.con_col[q], a.con_eq[q] = (short)P.con_eq[q];
+    a.nlin_eq = P.nlin_eq, a.nlin_ineq = P.nlin_ineq;
+    a.A_eq = c.dlin[0], a.b_eq = c.dlin[1], a.A_ineq = c.dlin[2], a.b_ineq = c.dlin[3];
+    a.eq_tol = P.eq_tol;
+    a.Xeval = c.base + c.oStart[p];
+    a.seed = s.seed, a.dbg = c.dbg, a.xtol_rel = c.xtol;
+}
+
+// Opening: the arena for the phases that will run (with_ideal: the k single-objective runs; with_ps: the PS run), the uploads,
+// mx = m(x_n), the budgets and the starts' blocks.
+static int ps_open(PsCall &c, mrbf_ctx *ctx, std::vector<PsStart> &S, const mrbf_ps_options *opts, bool with_ideal, bool with_ps) {
+    using namespace ps;
+    c.ctx = ctx, c.S = &S, c.opts = opts;
+    const size_t N = c.N = S.size();
+    c.single = N == 1;
+    const Problem &P0 = S[0].P;
+    const int d = c.d = P0.d, k = c.k = P0.nobj, nm = c.nm = P0.nmodels;
+    c.nftot = P0.nftot;
+    hipStream_t st = ctx->stream;
+    MRBF_HIP(ctx, hipEventRecord(ctx->ev[0], st));
+    const Sizes &z = c.sz = sizes(d, k, with_ideal, with_ps);
     const size_t nlin = (size_t)P0.nlin_eq + P0.nlin_ineq;
-    const size_t per_ip = (size_t)4 * lam_ip * d + (size_t)3 * lam_ip, per_ps = (size_t)4 * lam_ps * (d + 1) + (size_t)3 * lam_ps;
-    const size_t best_per = std::max((size_t)k * (d + 2), (size_t)d + 3);
     const size_t args_dbl = (sizeof(Args) + sizeof(double) - 1) / sizeof(double);
     chain::Arena ar;
-    const size_t oLin = ar.take(nlin * (d + 1)), oArgs = ar.take(N * args_dbl), oBox = ar.take(N * 3 * d), oMx = ar.take(N * k), oR = ar.take(N * k);
-    const size_t oBest = ar.take(N * best_per);
-    const size_t start_cnt = (size_t)rows * d + (size_t)rows * nftot + std::max(need_ideal ? k * per_ip : 0, ideal_only ? 0 : per_ps);
-    std::vector<size_t> oStart(N);
-    for (size_t p = 0; p < N; ++p) oStart[p] = ar.take(start_cnt);
-    chain::Plan ev_ip, ev_ps_all, ev_ps;
-    size_t oDesc = 0;
-    enum { SITE_IP = 0, SITE_PS = 1 };
-    if (!single) {
-        for (size_t p = 0; p < N && need_ideal; ++p)
-            for (int j = 0; j < nm; ++j) ev_ip.add(ctx, SITE_IP, (int64_t)p, j, S[p].P.models[j], (int64_t)k * lam_ip, false, true);
-        for (size_t p = 0; p < N && !ideal_only; ++p)
-            for (int j = 0; j < nm; ++j) ev_ps_all.add(ctx, SITE_PS, (int64_t)p, j, S[p].P.models[j], lam_ps, false, true);
-        ev_ip.close();
-        ev_ps_all.close();
-        oDesc = ar.take(std::max(ev_ip.desc_doubles(), ev_ps_all.desc_doubles()));
+    c.oLin = ar.take(nlin * (d + 1)), c.oArgs = ar.take(N * args_dbl), c.oBox = ar.take(N * 3 * d), c.oMx = ar.take(N * k), c.oR = ar.take(N * k);
+    c.oBest = ar.take(N * z.best_per);
+    const size_t start_cnt = (size_t)z.rows * d + (size_t)z.rows * c.nftot + z.state;
+    c.oStart.resize(N);
+    for (size_t p = 0; p < N; ++p) c.oStart[p] = ar.take(start_cnt);
+    if (!c.single) {
+        for (size_t p = 0; p < N && with_ideal; ++p)
+            for (int j = 0; j < nm; ++j) c.ev_ip.add(ctx, SITE_IP, (int64_t)p, j, S[p].P.models[j], (int64_t)k * z.lam_ip, false, true);
+        for (size_t p = 0; p < N && with_ps; ++p)
+            for (int j = 0; j < nm; ++j) c.ev_ps_all.add(ctx, SITE_PS, (int64_t)p, j, S[p].P.models[j], z.lam_ps, false, true);
+        c.ev_ip.close();
+        c.ev_ps_all.close();
+        c.oDesc = ar.take(std::max(c.ev_ip.desc_doubles(), c.ev_ps_all.desc_doubles()));
         chain::Arena a0, a1;  // (the two phases follow each other: their scratch shares its place)
         a0.total = a1.total = ar.total;
-        ev_ip.carve(a0);
-        ev_ps_all.carve(a1);
+        c.ev_ip.carve(a0);
+        c.ev_ps_all.carve(a1);
         ar.total = std::max(a0.total, a1.total);
-        for (chain::Plan *pl : {&ev_ip, &ev_ps_all})
+        for (chain::Plan *pl : {&c.ev_ip, &c.ev_ps_all})
             for (chain::Member &mb : pl->mem) {
-                mb.X = oStart[mb.p];
-                mb.vals = oStart[mb.p] + (size_t)rows * d + (size_t)rows * P0.foff[mb.j];
+                mb.X = c.oStart[mb.p];
+                mb.vals = c.oStart[mb.p] + (size_t)z.rows * d + (size_t)z.rows * P0.foff[mb.j];
             }
     }
-    double *base;
-    int *stat;
-    MRBF_TRY(get_buf(ctx, S_PS_STATE, ar.total + 64, &base));
-    MRBF_TRY(get_buf(ctx, S_PS_STAT, (size_t)4 * std::max((size_t)MAXRUNS, N * (size_t)k), &stat));
-    const Args *dA = reinterpret_cast<const Args *>(base + oArgs);
-    std::vector<double> hbox(N * 3 * d), hmx(N * k), hr(N * k);
+    MRBF_TRY(get_buf(ctx, S_PS_STATE, ar.total + 64, &c.base));
+    MRBF_TRY(get_buf(ctx, S_PS_STAT, (size_t)4 * std::max((size_t)MAXRUNS, N * (size_t)k), &c.stat));
+    double *base = c.base;
+    c.dA = reinterpret_cast<const Args *>(base + c.oArgs);
+    c.hbox.resize(N * 3 * d), c.hmx.resize(N * k), c.hr.resize(N * k);
     for (size_t p = 0; p < N; ++p) {
-        std::copy(S[p].hlb.begin(), S[p].hlb.end(), hbox.begin() + p * 3 * d);
-        std::copy(S[p].hub.begin(), S[p].hub.end(), hbox.begin() + p * 3 * d + d);
-        std::copy(S[p].hxn.begin(), S[p].hxn.end(), hbox.begin() + p * 3 * d + 2 * d);
+        std::copy(S[p].hlb.begin(), S[p].hlb.end(), c.hbox.begin() + p * 3 * d);
+        std::copy(S[p].hub.begin(), S[p].hub.end(), c.hbox.begin() + p * 3 * d + d);
+        std::copy(S[p].hxn.begin(), S[p].hxn.end(), c.hbox.begin() + p * 3 * d + 2 * d);
     }
-    MRBF_HIP(ctx, hipMemcpyAsync(base + oBox, hbox.data(), hbox.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    {
-        double *p = base + oLin;
-        const double *dev[4];
-        const std::vector<double> *src[4] = {&P0.A_eq, &P0.b_eq, &P0.A_ineq, &P0.b_ineq};
-        for (int q = 0; q < 4; ++q) {
-            dev[q] = p;
-            if (!src[q]->empty()) MRBF_HIP(ctx, hipMemcpyAsync(p, src[q]->data(), src[q]->size() * sizeof(double), hipMemcpyHostToDevice, st));
-            p += src[q]->size();
-        }
-        for (PsStart &s : S) s.P.dA_eq = dev[0], s.P.db_eq = dev[1], s.P.dA_ineq = dev[2], s.P.db_ineq = dev[3];
+    MRBF_HIP(ctx, hipMemcpyAsync(base + c.oBox, c.hbox.data(), c.hbox.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    const std::vector<double> *lin[4] = {&P0.lin->A_eq, &P0.lin->b_eq, &P0.lin->A_ineq, &P0.lin->b_ineq};
+    double *dl = base + c.oLin;
+    for (int q = 0; q < 4; dl += lin[q++]->size()) {
+        c.dlin[q] = dl;
+        if (!lin[q]->empty()) MRBF_HIP(ctx, hipMemcpyAsync(dl, lin[q]->data(), lin[q]->size() * sizeof(double), hipMemcpyHostToDevice, st));
     }
     // mx = m(x_n)  (descent.jl:543)
-    std::vector<std::vector<double>> allF(N);
+    c.allF.resize(N);
     std::vector<EvalReq> reqs;
-    for (size_t p = 0; p < N; ++p) reqs.push_back(EvalReq{&S[p].P, S[p].hxn.data(), 1, &allF[p], nullptr});
+    for (size_t p = 0; p < N; ++p) reqs.push_back(EvalReq{&S[p].P, S[p].hxn.data(), 1, &c.allF[p], nullptr});
     MRBF_TRY(ps_eval_points_many(ctx, reqs));
     for (size_t p = 0; p < N; ++p) {
         S[p].mx.resize(k);
-        for (int l = 0; l < k; ++l) S[p].mx[l] = hmx[p * k + l] = S[p].P.objective(allF[p], l);
+        for (int l = 0; l < k; ++l) S[p].mx[l] = c.hmx[p * k + l] = S[p].P.objective(c.allF[p], l);
     }
-    MRBF_HIP(ctx, hipMemcpyAsync(base + oMx, hmx.data(), hmx.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    const int max_ip = opts->max_ideal_evals < 0 ? 500 * (d + 1) : opts->max_ideal_evals;   // descent.jl:527
-    const int max_ps = opts->max_ps_evals < 0 ? 500 * (d + 1) : opts->max_ps_evals;          // descent.jl:416
-    // The evolution strategy is a global method: in d + 1 >= 25 variables it locates a basin, it does not descend into it (with the
-    // reference's defaults the step at d = 128 stayed at 7 % of what the subproblem allows).  A tenth of every global budget is
-    // therefore kept back for gradient steps from the strategy's best point (ps_descend_groups) -- the evaluations are counted against
-    // the same budget, so the call never evaluates more than the configuration allows.
-    const auto reserve = [&](int budget) { return budget < 20 * 13 ? 0 : budget / 10; };
-    const int res_ip = reserve(max_ip), res_ps = opts->max_polish_evals > 0 ? 0 : reserve(max_ps);
-    const double xtol = opts->xtol_rel > 0.0 ? opts->xtol_rel : 1e-3;                        // descent.jl:379, :485
-    const int dbg = (mrbf_env("MRBF_PS_DBG") ? atoi(mrbf_env("MRBF_PS_DBG")) : 0) & DBG_ALL;
+    MRBF_HIP(ctx, hipMemcpyAsync(base + c.oMx, c.hmx.data(), c.hmx.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    c.max_ip = budget(opts->max_ideal_evals, d);  // descent.jl:527
+    c.max_ps = budget(opts->max_ps_evals, d);     // descent.jl:416
+    // (a polish with a budget of its own leaves the PS run its whole budget)
+    c.res_ip = reserve(c.max_ip), c.res_ps = opts->max_polish_evals > 0 ? 0 : reserve(c.max_ps);
+    c.xtol = opts->xtol_rel > 0.0 ? opts->xtol_rel : 1e-3;  // descent.jl:379, :485
+    c.dbg = (mrbf_env("MRBF_PS_DBG") ? atoi(mrbf_env("MRBF_PS_DBG")) : 0) & DBG_ALL;
+    for (size_t p = 0; p < N; ++p) ps_make_args(c, p);
+    c.hbest.resize(N * z.best_per);
+    c.hs.resize((size_t)4 * std::max((size_t)MAXRUNS, N * (size_t)k));
+    return MRBF_OK;
+}
 
-    auto make_run = [&](Run &R, int kind, int obj, int lam, int nvar, int off, int max_evals, double *&p, double *best, int *stp) {
-        R.kind = kind;
-        R.obj = obj;
-        R.lam = lam;
-        R.mu = (lam + 6) / 7;
-        R.nvar = nvar;
-        R.off = off;
-        R.max_evals = max_evals;
-        for (int b = 0; b < 2; ++b) {
-            R.X[b] = p;
-            p += (size_t)lam * nvar;
-            R.S[b] = p;
-            p += (size_t)lam * nvar;
+// Generations of one phase: the runs of the starts `act` (their blocks' runs are set), generation by generation until every run of
+// every start is done
+static int ps_generations(PsCall &c, const std::vector<size_t> &act, const chain::Plan *plan, int site, double t0, int max_gens) {
+    using namespace ps;
+    mrbf_ctx *ctx = c.ctx;
+    std::vector<PsStart> &S = *c.S;
+    hipStream_t st = ctx->stream;
+    double *base = c.base;
+    const Args *dA = c.dA;
+    const int nm = c.nm;
+    const int NA = (int)act.size();
+    const Args &a0 = S[act[0]].a;
+    const int nruns = a0.nruns;
+    int maxel = 0, nrows = 0;
+    for (int q2 = 0; q2 < nruns; ++q2) {
+        nrows = std::max(nrows, a0.runs[q2].off + a0.runs[q2].lam);
+        maxel = std::max(maxel, a0.runs[q2].lam * a0.runs[q2].nvar);
+    }
+    // large populations: the transposition phases with one wave per 64 individuals (MRBF_PS_MULTI=0, read per call: one workgroup per
+    // run as in rounds 3 / 4) while ALL runs of the launch can be resident together -- their waves wait for each other; beyond that
+    // count every run takes the one-workgroup ranking, and the many runs are the parallelism.  A counter wait that times out -- a
+    // device shared with other work -- costs 5 ms; the host sees the sticky failure word with the status words, every eight
+    // generations, and keeps to one workgroup per run from then on.
+    const bool multi_env = !(mrbf_env("MRBF_PS_MULTI") && atoi(mrbf_env("MRBF_PS_MULTI")) == 0);
+    RankLaunch L;
+    MRBF_TRY(rank_launch_setup(ctx, a0, NA, (int64_t)ctx->ncu >= (int64_t)RS_CUS_PER_RUN * nruns * NA && !ctx->ps_multi_off && multi_env, L));
+    bool phases_possible = a0.ncon + a0.nlin_eq + a0.nlin_ineq > 0 || (a0.dbg & DBG_PHASES);
+    for (int q2 = 0; q2 < nruns; ++q2) phases_possible = phases_possible || a0.runs[q2].kind == 1;
+    // one model, fused evaluation: the breeding kernel writes the next population centred and padded into the evaluation's own query
+    // buffers (a launch per generation less; MRBF_PS_FUSEPAD=0: the evaluation's centring launch).  The one start's buffers are the
+    // arena slots the evaluation will ask for -- same size, same pointer; eval_fused checks that and centres itself otherwise; a
+    // batch's are its members' own.
+    const int fusepad = mrbf_env("MRBF_PS_FUSEPAD") ? atoi(mrbf_env("MRBF_PS_FUSEPAD")) : 1;  // (read per call: the tests switch it inside one process)
+    const int score_fused = (a0.nlin_eq + a0.nlin_ineq == 0 && !(mrbf_env("MRBF_PS_FUSESCORE") && atoi(mrbf_env("MRBF_PS_FUSESCORE")) == 0)) ? 1 : 0;
+    bool fused = fusepad && nm == 1 && ctx->eval_impl != 1 && c.d <= 360;
+    for (int i = 0; i < NA && fused; ++i) {
+        const int dp = S[act[i]].P.models[0]->dpad;
+        fused = dp == 64 || dp == 128 || dp == 256;
+    }
+    double *xq1 = nullptr, *xsq1 = nullptr;
+    if (fused && c.single) {
+        const int64_t mpad = round_up((int64_t)nrows, 64);
+        MRBF_TRY(get_buf(ctx, S_EVAL_XC, (size_t)mpad * S[0].P.models[0]->dpad, &xq1));
+        MRBF_TRY(get_buf(ctx, S_EVAL_XSQ, (size_t)mpad, &xsq1));
+    }
+    c.harr.resize(NA);
+    for (int i = 0; i < NA; ++i) {
+        Args &a = S[act[i]].a;
+        a.rows = nrows, a.t0 = t0, a.grun0 = i * nruns, a.score_fused = score_fused;
+        a.Xq = a.xsq = nullptr, a.xmean = nullptr, a.xqD = 0;
+        if (fused) {
+            const mrbf_model *M0 = S[act[i]].P.models[0];
+            a.Xq = c.single ? xq1 : base + plan->mem[(size_t)i * nm].Xq;
+            a.xsq = c.single ? xsq1 : base + plan->mem[(size_t)i * nm].xsq;
+            a.xmean = M0->mean;
+            a.xqD = M0->dpad;
         }
-        R.best = best;
-        R.f = p;
-        p += lam;
-        R.phi = p;
-        p += lam;
-        R.order = (int *)p;
-        p += lam;
-        R.stat = stp;
-    };
-    // the block of start p (everything but the runs)
-    auto make_args = [&](size_t p) {
-        const Problem &P = S[p].P;
-        Args &a = S[p].a;
-        a = Args{};
-        a.d = d;
-        a.nobj = k;
-        a.lb = base + oBox + p * 3 * d;
-        a.ub = a.lb + d;
-        a.xn = a.ub + d;
-        a.mx = base + oMx + p * k;
-        a.r = base + oR + p * k;
-        a.nmodels = nm;
-        double *fp = base + oStart[p] + (size_t)rows * d;
-        for (int j = 0; j < nm; ++j) {
-            a.F[j] = fp;
-            a.kf[j] = P.models[j]->k;
-            fp += (size_t)rows * P.models[j]->k;
+        c.harr[i] = a;
+    }
+    MRBF_HIP(ctx, hipMemcpyAsync(base + c.oArgs, c.harr.data(), (size_t)NA * sizeof(Args), hipMemcpyHostToDevice, st));
+    const EvalDesc *ddesc = reinterpret_cast<const EvalDesc *>(base + c.oDesc);
+    if (!c.single) {
+        c.hdesc.resize(plan->n_desc);
+        plan->fill(base, c.hdesc.data());
+        if (plan->n_desc) MRBF_HIP(ctx, hipMemcpyAsync(base + c.oDesc, c.hdesc.data(), plan->n_desc * sizeof(EvalDesc), hipMemcpyHostToDevice, st));
+    }
+    hipLaunchKernelGGL(ps_init_kernel, dim3((unsigned)((maxel + 255) / 256), (unsigned)nruns, (unsigned)NA), dim3(256), 0, st, dA);
+    std::vector<int> hstat((size_t)4 * nruns * NA);
+    const unsigned wave_blocks = (unsigned)((nrows + 3) / 4);
+    for (int g = 0; g < max_gens; ++g) {
+        // (generation 0 comes from ps_init_kernel: centred by the evaluation's own launch)
+        if (c.single) {
+            EvalHints hints;
+            hints.population = true;
+            hints.pre_xq = (g > 0 && fused) ? xq1 : nullptr;
+            for (int j = 0; j < nm; ++j) MRBF_TRY(eval_model(ctx, S[0].P.models[j], nrows, a0.Xeval, const_cast<double *>(a0.F[j]), nullptr, nullptr, hints));
+        } else {
+            MRBF_TRY(plan->launch(ctx, site, base, c.hdesc.data(), ddesc, g > 0 && fused));
         }
+        if (!score_fused) hipLaunchKernelGGL(ps_score_kernel, dim3(wave_blocks, (unsigned)NA), dim3(256), 0, st, dA, g);
+        rank_launch(ctx, dA, NA, nruns, g, L, phases_possible);
+        hipLaunchKernelGGL(ps_breed_kernel, dim3(wave_blocks, (unsigned)NA), dim3(256), 0, st, dA, g);
+        if ((g & 7) == 7 || g + 1 == max_gens) {  // status words every 8 generations: stop when every run of every start is done
+            MRBF_HIP(ctx, hipMemcpyAsync(hstat.data(), c.stat, hstat.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+            int hfail = 0;
+            if (L.several) MRBF_HIP(ctx, hipMemcpyAsync(&hfail, L.ws.sticky, sizeof(int), hipMemcpyDeviceToHost, st));
+            MRBF_HIP(ctx, hipStreamSynchronize(st));
+            if (hfail && !(a0.dbg & DBG_GIVE_UP)) {
+                L.several = false;
+                ctx->ps_multi_off = 1;
+            }
+            bool all = true;
+            for (size_t q2 = 0; q2 < hstat.size() / 4; ++q2) all = all && hstat[4 * q2 + 1] != 0;
+            if (all) break;
+        }
+    }
+    MRBF_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
+// Ideal phase -- the local ideal point: the k single-objective minimisations of every start side by side (descent.jl:404-412) and the
+// refinement of their best points.  Every start's ideal, x_ideal, found, refined and info.evals_ideal / generations are set.
+static int ps_ideal_phase(PsCall &c) {
+    mrbf_ctx *ctx = c.ctx;
+    std::vector<PsStart> &S = *c.S;
+    hipStream_t st = ctx->stream;
+    const size_t N = c.N, best_per = c.sz.best_per;
+    const int d = c.d, k = c.k, lam_ip = c.sz.lam_ip;
+    std::vector<size_t> act(N);
+    for (size_t p = 0; p < N; ++p) {
+        act[p] = p;
+        ps::Args &a = S[p].a;
+        double *pp = ps_runs_at(c, p);
+        a.nruns = k;
+        for (int l = 0; l < k; ++l)
+            ps_make_run(a.runs[l], 0, l, lam_ip, d, l * lam_ip, c.max_ip - c.res_ip, pp, c.base + c.oBest + p * best_per + (size_t)l * (d + 2), c.stat + 4 * (p * k + l));
+    }
+    MRBF_TRY(ps_generations(c, act, &c.ev_ip, SITE_IP, 0.0, (c.max_ip - c.res_ip + lam_ip - 1) / lam_ip + 1));
+    MRBF_HIP(ctx, hipMemcpyAsync(c.hbest.data(), c.base + c.oBest, c.hbest.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    MRBF_HIP(ctx, hipMemcpyAsync(c.hs.data(), c.stat, (size_t)4 * N * k * sizeof(int), hipMemcpyDeviceToHost, st));
+    MRBF_HIP(ctx, hipStreamSynchronize(st));
+    // A run that never met a feasible point contributes its start value.  The runs' best points are refined by gradient steps on
+    // their objective -- all descents of all starts in lockstep, one chain of evaluations per iteration
+    std::vector<DescentGroup> gs;
+    std::vector<std::pair<size_t, int>> dl;  // (start, objective) of every descent, group by group
+    for (size_t p = 0; p < N; ++p) {
+        DescentGroup G;
+        G.P = &S[p].P;
+        S[p].ideal.assign(k, 0.0);
+        S[p].x_ideal.assign((size_t)k * d, 0.0);
+        S[p].found.assign(k, 0), S[p].refined.assign(k, 0);
         for (int l = 0; l < k; ++l) {
-            a.obj_model[l] = (short)P.obj_model[l];
-            a.obj_col[l] = (short)P.obj_col[l];
-        }
-        a.ncon = P.ncon;
-        for (int c = 0; c < P.ncon; ++c) {
-            a.con_model[c] = (short)P.con_model[c];
-            a.con_col[c] = (short)P.con_col[c];
-            a.con_eq[c] = (short)P.con_eq[c];
-        }
-        a.nlin_eq = P.nlin_eq;
-        a.nlin_ineq = P.nlin_ineq;
-        a.A_eq = P.dA_eq;
-        a.b_eq = P.db_eq;
-        a.A_ineq = P.dA_ineq;
-        a.b_ineq = P.db_ineq;
-        a.eq_tol = P.eq_tol;
-        a.Xeval = base + oStart[p];
-        a.seed = S[p].seed;
-        a.dbg = dbg;
-        a.xtol_rel = xtol;
-    };
-    std::vector<Args> harr;
-    std::vector<EvalDesc> hdesc;
-    // one phase: the runs of the starts `act` (their blocks' runs are set), generation by generation until every run of every start is done
-    auto run_batch = [&](const std::vector<size_t> &act, const chain::Plan *plan, int site, double t0, int max_gens) -> int {
-        const int NA = (int)act.size();
-        const Args &a0 = S[act[0]].a;
-        const int nruns = a0.nruns;
-        int maxel = 0, nrows = 0;
-        for (int q2 = 0; q2 < nruns; ++q2) {
-            nrows = std::max(nrows, a0.runs[q2].off + a0.runs[q2].lam);
-            maxel = std::max(maxel, a0.runs[q2].lam * a0.runs[q2].nvar);
-        }
-        // large populations: the transposition phases with one wave per 64 individuals (MRBF_PS_MULTI=0, read per call: one workgroup per
-        // run as in rounds 3 / 4) while ALL runs of the launch can be resident together -- their waves wait for each other; beyond that
-        // count every run takes the one-workgroup ranking, and the many runs are the parallelism.  A counter wait that times out -- a
-        // device shared with other work -- costs 5 ms; the host sees the sticky failure word with the status words, every eight
-        // generations, and keeps to one workgroup per run from then on.
-        const bool multi_env = !(mrbf_env("MRBF_PS_MULTI") && atoi(mrbf_env("MRBF_PS_MULTI")) == 0);
-        RankLaunch L;
-        MRBF_TRY(rank_launch_setup(ctx, a0, NA, (int64_t)ctx->ncu >= (int64_t)RS_CUS_PER_RUN * nruns * NA && !ctx->ps_multi_off && multi_env, L));
-        bool phases_possible = a0.ncon + a0.nlin_eq + a0.nlin_ineq > 0 || (a0.dbg & DBG_PHASES);
-        for (int q2 = 0; q2 < nruns; ++q2) phases_possible = phases_possible || a0.runs[q2].kind == 1;
-        // one model, fused evaluation: the breeding kernel writes the next population centred and padded into the evaluation's own query
-        // buffers (a launch per generation less; MRBF_PS_FUSEPAD=0: the evaluation's centring launch).  The one start's buffers are the
-        // arena slots the evaluation will ask for -- same size, same pointer; eval_fused checks that and centres itself otherwise; a
-        // batch's are its members' own.
-        const int fusepad = mrbf_env("MRBF_PS_FUSEPAD") ? atoi(mrbf_env("MRBF_PS_FUSEPAD")) : 1;  // (read per call: the tests switch it inside one process)
-        const int score_fused = (a0.nlin_eq + a0.nlin_ineq == 0 && !(mrbf_env("MRBF_PS_FUSESCORE") && atoi(mrbf_env("MRBF_PS_FUSESCORE")) == 0)) ? 1 : 0;
-        bool fused = fusepad && nm == 1 && ctx->eval_impl != 1 && d <= 360;
-        for (int i = 0; i < NA && fused; ++i) {
-            const int dp = S[act[i]].P.models[0]->dpad;
-            fused = dp == 64 || dp == 128 || dp == 256;
-        }
-        double *xq1 = nullptr, *xsq1 = nullptr;
-        if (fused && single) {
-            const int64_t mpad = round_up((int64_t)nrows, 64);
-            MRBF_TRY(get_buf(ctx, S_EVAL_XC, (size_t)mpad * P0.models[0]->dpad, &xq1));
-            MRBF_TRY(get_buf(ctx, S_EVAL_XSQ, (size_t)mpad, &xsq1));
-        }
-        harr.resize(NA);
-        for (int i = 0; i < NA; ++i) {
-            Args &a = S[act[i]].a;
-            a.rows = nrows;
-            a.t0 = t0;
-            a.grun0 = i * nruns;
-            a.score_fused = score_fused;
-            a.Xq = nullptr;
-            a.xsq = nullptr;
-            a.xmean = nullptr;
-            a.xqD = 0;
-            if (fused) {
-                const mrbf_model *M0 = S[act[i]].P.models[0];
-                a.Xq = single ? xq1 : base + plan->mem[(size_t)i * nm].Xq;
-                a.xsq = single ? xsq1 : base + plan->mem[(size_t)i * nm].xsq;
-                a.xmean = M0->mean;
-                a.xqD = M0->dpad;
-            }
-            harr[i] = a;
-        }
-        MRBF_HIP(ctx, hipMemcpyAsync(base + oArgs, harr.data(), (size_t)NA * sizeof(Args), hipMemcpyHostToDevice, st));
-        const EvalDesc *ddesc = reinterpret_cast<const EvalDesc *>(base + oDesc);
-        if (!single) {
-            hdesc.resize(plan->n_desc);
-            plan->fill(base, hdesc.data());
-            if (plan->n_desc) MRBF_HIP(ctx, hipMemcpyAsync(base + oDesc, hdesc.data(), plan->n_desc * sizeof(EvalDesc), hipMemcpyHostToDevice, st));
-        }
-        hipLaunchKernelGGL(ps_init_kernel, dim3((unsigned)((maxel + 255) / 256), (unsigned)nruns, (unsigned)NA), dim3(256), 0, st, dA);
-        std::vector<int> hstat((size_t)4 * nruns * NA);
-        const unsigned wave_blocks = (unsigned)((nrows + 3) / 4);
-        for (int g = 0; g < max_gens; ++g) {
-            // (generation 0 comes from ps_init_kernel: centred by the evaluation's own launch)
-            if (single) {
-                EvalHints hints;
-                hints.population = true;
-                hints.pre_xq = (g > 0 && fused) ? xq1 : nullptr;
-                for (int j = 0; j < nm; ++j) MRBF_TRY(eval_model(ctx, P0.models[j], nrows, a0.Xeval, const_cast<double *>(a0.F[j]), nullptr, nullptr, hints));
-            } else {
-                MRBF_TRY(plan->launch(ctx, site, base, hdesc.data(), ddesc, g > 0 && fused));
-            }
-            if (!score_fused) hipLaunchKernelGGL(ps_score_kernel, dim3(wave_blocks, (unsigned)NA), dim3(256), 0, st, dA, g);
-            rank_launch(ctx, dA, NA, nruns, g, L, phases_possible);
-            hipLaunchKernelGGL(ps_breed_kernel, dim3(wave_blocks, (unsigned)NA), dim3(256), 0, st, dA, g);
-            if ((g & 7) == 7 || g + 1 == max_gens) {  // status words every 8 generations: stop when every run of every start is done
-                MRBF_HIP(ctx, hipMemcpyAsync(hstat.data(), stat, hstat.size() * sizeof(int), hipMemcpyDeviceToHost, st));
-                int hfail = 0;
-                if (L.several) MRBF_HIP(ctx, hipMemcpyAsync(&hfail, L.ws.sticky, sizeof(int), hipMemcpyDeviceToHost, st));
-                MRBF_HIP(ctx, hipStreamSynchronize(st));
-                if (hfail && !(a0.dbg & DBG_GIVE_UP)) {
-                    L.several = false;
-                    ctx->ps_multi_off = 1;
-                }
-                bool all = true;
-                for (size_t q2 = 0; q2 < hstat.size() / 4; ++q2) all = all && hstat[4 * q2 + 1] != 0;
-                if (all) break;
+            const double *b = &c.hbest[p * best_per + (size_t)l * (d + 2)];
+            const int *h = &c.hs[4 * (p * k + l)];
+            const bool found = b[d + 1] == 0.0 && std::isfinite(b[d]);
+            S[p].ideal[l] = found ? b[d] : S[p].mx[l];
+            S[p].found[l] = found;
+            std::copy_n(found ? b : S[p].hxn.data(), d, S[p].x_ideal.begin() + (size_t)l * d);
+            S[p].info.evals_ideal += h[0];
+            S[p].info.generations += h[2];
+            const int left = c.max_ip - h[0];
+            if (found && left >= 13) {
+                G.ds.push_back(descent_of_objective(&S[p].P, &S[p].hlb, &S[p].hub, l, b, S[p].ideal[l], left, c.xtol));
+                dl.emplace_back(p, l);
             }
         }
-        MRBF_HIP(ctx, hipGetLastError());
-        return 0;
-    };
+        if (!G.ds.empty()) gs.push_back(std::move(G));
+    }
+    MRBF_TRY(ps_descend_groups(ctx, gs));
+    size_t at = 0;
+    for (DescentGroup &G : gs)
+        for (Descent &D : G.ds) {
+            PsStart &s = S[dl[at].first];
+            const int l = dl[at].second;
+            s.ideal[l] = D.val;  // (D.x is where D.val was taken: they change together)
+            std::copy(D.x.begin(), D.x.end(), s.x_ideal.begin() + (size_t)l * d);
+            s.refined[l] = D.evals > 0;
+            s.info.evals_ideal += D.evals;
+            ++at;
+        }
+    return MRBF_OK;
+}
 
-    for (size_t p = 0; p < N; ++p) make_args(p);
-    std::vector<double> hbest(N * best_per);
-    std::vector<int> hs((size_t)4 * std::max((size_t)MAXRUNS, N * (size_t)k));
-    // ---- local ideal point: the k single-objective minimisations of every start side by side (descent.jl:404-412)
-    if (need_ideal) {
-        std::vector<size_t> act(N);
-        for (size_t p = 0; p < N; ++p) {
-            act[p] = p;
-            Args &a = S[p].a;
-            double *pp = base + oStart[p] + (size_t)rows * d + (size_t)rows * nftot;
-            a.nruns = k;
-            for (int l = 0; l < k; ++l)
-                make_run(a.runs[l], 0, l, lam_ip, d, l * lam_ip, max_ip - res_ip, pp, base + oBest + p * best_per + (size_t)l * (d + 2), stat + 4 * (p * k + l));
-        }
-        MRBF_TRY(run_batch(act, &ev_ip, SITE_IP, 0.0, (max_ip - res_ip + lam_ip - 1) / lam_ip + 1));
-        MRBF_HIP(ctx, hipMemcpyAsync(hbest.data(), base + oBest, hbest.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-        MRBF_HIP(ctx, hipMemcpyAsync(hs.data(), stat, (size_t)4 * N * k * sizeof(int), hipMemcpyDeviceToHost, st));
-        MRBF_HIP(ctx, hipStreamSynchronize(st));
-        // r = f(x_n) - ideal point (descent.jl:536-538); a run that never met a feasible point contributes its start value.  The runs'
-        // best points are refined by gradient steps on their objective -- all descents of all starts in lockstep, one chain of
-        // evaluations per iteration
-        std::vector<DescentGroup> gs;
-        std::vector<std::pair<size_t, int>> dl;  // (start, objective) of every descent, group by group
-        for (size_t p = 0; p < N; ++p) {
-            DescentGroup G;
-            G.P = &S[p].P;
-            S[p].ideal.assign(k, 0.0);
-            S[p].x_ideal.assign((size_t)k * d, 0.0);
-            S[p].found.assign(k, 0), S[p].refined.assign(k, 0);
-            for (int l = 0; l < k; ++l) {
-                const double *b = &hbest[p * best_per + (size_t)l * (d + 2)];
-                const int *h = &hs[4 * (p * k + l)];
-                const bool found = b[d + 1] == 0.0 && std::isfinite(b[d]);
-                S[p].ideal[l] = found ? b[d] : S[p].mx[l];
-                S[p].found[l] = found;
-                std::copy_n(found ? b : S[p].hxn.data(), d, S[p].x_ideal.begin() + (size_t)l * d);
-                S[p].info.evals_ideal += h[0];
-                S[p].info.generations += h[2];
-                const int left = max_ip - h[0];
-                if (found && left >= 13) {
-                    G.ds.emplace_back();
-                    Descent &D = G.ds.back();
-                    D.P = &S[p].P;
-                    D.lb = &S[p].hlb;
-                    D.ub = &S[p].hub;
-                    D.objs = std::vector<int>{l};
-                    D.off = std::vector<double>{0.0};
-                    D.scale = std::vector<double>{1.0};
-                    D.clamp = false;
-                    D.max_evals = left;
-                    D.xtol_rel = xtol;
-                    D.val = S[p].ideal[l];
-                    D.x.assign(b, b + d);
-                    dl.emplace_back(p, l);
-                }
-            }
-            if (!G.ds.empty()) gs.push_back(std::move(G));
-        }
-        MRBF_TRY(ps_descend_groups(ctx, gs));
-        {
-            size_t at = 0;
-            for (DescentGroup &G : gs)
-                for (Descent &D : G.ds) {
-                    PsStart &s = S[dl[at].first];
-                    const int l = dl[at].second;
-                    s.ideal[l] = D.val;  // (D.x is where D.val was taken: they change together)
-                    std::copy(D.x.begin(), D.x.end(), s.x_ideal.begin() + (size_t)l * d);
-                    s.refined[l] = D.evals > 0;
-                    s.info.evals_ideal += D.evals;
-                    ++at;
-                }
-        }
-        for (size_t p = 0; p < N && !ideal_only; ++p)
-            for (int l = 0; l < k; ++l) S[p].r[l] = S[p].hfx[l] - S[p].ideal[l];
-    }
-    if (ideal_only) {
-        MRBF_HIP(ctx, hipEventRecord(e1, st));
-        MRBF_HIP(ctx, hipStreamSynchronize(st));
-        MRBF_HIP(ctx, hipEventElapsedTime(ms_out, e0, e1));
-        return MRBF_OK;
-    }
-    // ---- the Pascoletti-Serafini runs of the starts that are not critical
+// PS phase: the direction where the ideal phase ran (r = f(x_n) - ideal point, descent.jl:536-538), the criticality test, the
+// Pascoletti-Serafini runs of the starts that are not critical, their polish, and mx_trial = m(x_trial).
+static int ps_step_phase(PsCall &c, bool r_from_ideal) {
+    mrbf_ctx *ctx = c.ctx;
+    std::vector<PsStart> &S = *c.S;
+    const mrbf_ps_options *opts = c.opts;
+    hipStream_t st = ctx->stream;
+    const size_t N = c.N, best_per = c.sz.best_per;
+    const int d = c.d, k = c.k, nm = c.nm, lam_ps = c.sz.lam_ps;
+    for (size_t p = 0; p < N && r_from_ideal; ++p)
+        for (int l = 0; l < k; ++l) S[p].r[l] = S[p].hfx[l] - S[p].ideal[l];
     std::vector<size_t> act;
     for (size_t p = 0; p < N; ++p) {
         PsStart &s = S[p];
@@ -2110,7 +1864,7 @@ static int ps_step_many(mrbf_ctx *ctx, std::vector<PsStart> &S, bool need_ideal,
         bool critical = false;
         for (int l = 0; l < k; ++l) {
             critical = critical || !(s.r[l] > 0.0);
-            hr[p * k + l] = s.r[l];
+            c.hr[p * k + l] = s.r[l];
         }
         if (critical)
             s.info.status = MRBF_PS_CRITICAL;  // any(r .<= 0): omega = 0, the point itself (descent.jl:546-549)
@@ -2118,31 +1872,31 @@ static int ps_step_many(mrbf_ctx *ctx, std::vector<PsStart> &S, bool need_ideal,
             act.push_back(p);
     }
     if (!act.empty()) {
-        MRBF_HIP(ctx, hipMemcpyAsync(base + oR, hr.data(), hr.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        MRBF_HIP(ctx, hipMemcpyAsync(c.base + c.oR, c.hr.data(), c.hr.size() * sizeof(double), hipMemcpyHostToDevice, st));
         for (size_t i = 0; i < act.size(); ++i) {
             const size_t p = act[i];
-            Args &a = S[p].a;
-            double *pp = base + oStart[p] + (size_t)rows * d + (size_t)rows * nftot;
+            ps::Args &a = S[p].a;
+            double *pp = ps_runs_at(c, p);
             a.nruns = 1;
-            make_run(a.runs[0], 1, 0, lam_ps, d + 1, 0, max_ps - res_ps, pp, base + oBest + p * best_per, stat + 4 * i);
+            ps_make_run(a.runs[0], 1, 0, lam_ps, d + 1, 0, c.max_ps - c.res_ps, pp, c.base + c.oBest + p * best_per, c.stat + 4 * i);
         }
-        if (!single) {  // the sweep of the starts that take part, every member where the plan of all starts has it
+        if (!c.single) {  // the sweep of the starts that take part, every member where the plan of all starts has it
             std::vector<size_t> which;
             for (size_t p : act)
                 for (int j = 0; j < nm; ++j) which.push_back(p * nm + j);
-            ev_ps = ev_ps_all.select(ctx, which);
+            c.ev_ps = c.ev_ps_all.select(ctx, which);
         }
-        MRBF_TRY(run_batch(act, &ev_ps, SITE_PS, opts->t0, (max_ps - res_ps + lam_ps - 1) / lam_ps + 1));
-        MRBF_HIP(ctx, hipMemcpyAsync(hbest.data(), base + oBest, hbest.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-        MRBF_HIP(ctx, hipMemcpyAsync(hs.data(), stat, (size_t)4 * act.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+        MRBF_TRY(ps_generations(c, act, &c.ev_ps, SITE_PS, opts->t0, (c.max_ps - c.res_ps + lam_ps - 1) / lam_ps + 1));
+        MRBF_HIP(ctx, hipMemcpyAsync(c.hbest.data(), c.base + c.oBest, c.hbest.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        MRBF_HIP(ctx, hipMemcpyAsync(c.hs.data(), c.stat, (size_t)4 * act.size() * sizeof(int), hipMemcpyDeviceToHost, st));
         MRBF_HIP(ctx, hipStreamSynchronize(st));
         std::vector<DescentGroup> gs;
         std::vector<size_t> gp;
         const bool own = opts->max_polish_evals > 0;
         for (size_t i = 0; i < act.size(); ++i) {
             PsStart &s = S[act[i]];
-            const double *best = &hbest[act[i] * best_per];
-            const int *h = &hs[4 * i];
+            const double *best = &c.hbest[act[i] * best_per];
+            const int *h = &c.hs[4 * i];
             s.info.evals_ps = h[0];
             s.info.generations += h[2];
             const double bf = best[d + 1], bphi = best[d + 2];
@@ -2155,24 +1909,11 @@ static int ps_step_many(mrbf_ctx *ctx, std::vector<PsStart> &S, bool need_ideal,
             for (int t = 0; t < d; ++t) s.xt[t] = best[1 + t];
             // the polish the configuration asks for (its own budget, descent.jl:423-429); without one, the part of the global budget
             // that was kept back or left over
-            const int pbudget = own ? opts->max_polish_evals : max_ps - h[0];
+            const int pbudget = own ? opts->max_polish_evals : c.max_ps - h[0];
             if (pbudget < 13) continue;
             DescentGroup G;
             G.P = &s.P;
-            G.ds.emplace_back();
-            Descent &D = G.ds.back();
-            D.P = &s.P;
-            D.lb = &s.hlb;
-            D.ub = &s.hub;
-            D.objs.resize(k);
-            for (int l = 0; l < k; ++l) D.objs[l] = l;
-            D.off = s.mx;
-            D.scale = s.r;
-            D.clamp = true;
-            D.max_evals = pbudget;
-            D.xtol_rel = xtol;
-            D.val = s.info.tau;
-            D.x = s.xt;
+            G.ds.push_back(descent_of_ps(&s.P, &s.hlb, &s.hub, s.info.tau, s.xt, s.mx, s.r, pbudget, c.xtol));
             gs.push_back(std::move(G));
             gp.push_back(act[i]);
         }
@@ -2189,16 +1930,121 @@ static int ps_step_many(mrbf_ctx *ctx, std::vector<PsStart> &S, bool need_ideal,
         }
     }
     // mx_trial = m(x_trial)
-    reqs.clear();
+    std::vector<EvalReq> reqs;
     for (size_t p = 0; p < N; ++p)
-        if (S[p].info.status == MRBF_PS_OK) reqs.push_back(EvalReq{&S[p].P, S[p].xt.data(), 1, &allF[p], nullptr});
+        if (S[p].info.status == MRBF_PS_OK) reqs.push_back(EvalReq{&S[p].P, S[p].xt.data(), 1, &c.allF[p], nullptr});
     MRBF_TRY(ps_eval_points_many(ctx, reqs));
     for (size_t p = 0; p < N; ++p)
         if (S[p].info.status == MRBF_PS_OK)
-            for (int l = 0; l < k; ++l) S[p].mx[l] = S[p].P.objective(allF[p], l);
-    MRBF_HIP(ctx, hipEventRecord(e1, st));
-    MRBF_HIP(ctx, hipStreamSynchronize(st));
-    MRBF_HIP(ctx, hipEventElapsedTime(ms_out, e0, e1));
+            for (int l = 0; l < k; ++l) S[p].mx[l] = S[p].P.objective(c.allF[p], l);
+    return MRBF_OK;
+}
+
+// Closing: the call's elapsed device time
+static int ps_close(PsCall &c, float *ms_out) {
+    mrbf_ctx *ctx = c.ctx;
+    MRBF_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    MRBF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    MRBF_HIP(ctx, hipEventElapsedTime(ms_out, ctx->ev[0], ctx->ev[1]));
+    return MRBF_OK;
+}
+
+// ---- the entry points' scaffold.  What differs between them -- return codes, the front of the messages, which phases run -- is a
+// small table per entry; each entry keeps its own NULL checks and reads its own layout.
+struct PsEntry {
+    const char *box_prefix;  // in front of the inverted-box message ("" or the call's name and ": ")
+    bool box_names_start;    // that message names the start
+    int rc_box;              // and the code it comes with
+    bool with_ps;            // the PS phase runs (false: the ideal-point calls)
+};
+// the inputs of N starts as host copies (the pointers may be host or device memory), the box checked
+struct PsInputs {
+    std::vector<double> x, lb, ub, fx, r;  // N x d (x, lb, ub), N x k (fx, r: empty where not given)
+    ps::LinRows lin;
+};
+static int ps_read_inputs(mrbf_ctx *ctx, const PsEntry &E, size_t SN, int d, int k, const mrbf_ps_problem *shape, const double *x_n,
+                          const double *lb_eff, const double *ub_eff, const double *fx_n, const double *r_or_null, PsInputs &in) {
+    MRBF_TRY(fetch_host(ctx, x_n, SN * d, in.x));
+    MRBF_TRY(fetch_host(ctx, lb_eff, SN * d, in.lb));
+    MRBF_TRY(fetch_host(ctx, ub_eff, SN * d, in.ub));
+    if (fx_n) MRBF_TRY(fetch_host(ctx, fx_n, SN * k, in.fx));
+    if (r_or_null) MRBF_TRY(fetch_host(ctx, r_or_null, SN * k, in.r));
+    for (size_t t = 0; t < SN * d; ++t)
+        if (!(in.lb[t] <= in.ub[t])) {
+            const int j = (int)(t % d);
+            if (E.box_names_start) return fail(ctx, E.rc_box, "%sstart %lld: lb_eff[%d] > ub_eff[%d]", E.box_prefix, (long long)(t / d), j, j);
+            return fail(ctx, E.rc_box, "%slb_eff[%d] > ub_eff[%d]", E.box_prefix, j, j);
+        }
+    MRBF_TRY(fetch_host(ctx, shape->A_eq, (size_t)shape->n_lin_eq * d, in.lin.A_eq));
+    MRBF_TRY(fetch_host(ctx, shape->b_eq, (size_t)shape->n_lin_eq, in.lin.b_eq));
+    MRBF_TRY(fetch_host(ctx, shape->A_ineq, (size_t)shape->n_lin_ineq * d, in.lin.A_ineq));
+    MRBF_TRY(fetch_host(ctx, shape->b_ineq, (size_t)shape->n_lin_ineq, in.lin.b_ineq));
+    return MRBF_OK;
+}
+
+// The chunk loop: a batch whose state exceeds 2 GiB is processed in chunks of starts (MRBF_PS_CHUNK_KB: another limit, so that a test
+// can split a small batch).  Per chunk the starts' records are filled from the inputs, the phases run, and `gather` takes what start p
+// (its index in the whole call) came out with.  A given direction (in.r) means no ideal phase.
+typedef void (*PsGather)(void *out, size_t p, const PsStart &s);
+static int ps_run_chunks(mrbf_ctx *ctx, const PsEntry &E, size_t SN, const descent::Layout &lay, const mrbf_ps_problem *shape,
+                         const mrbf_model *const *models, const PsInputs &in, const mrbf_ps_options *opts, const uint64_t *seeds_or_null,
+                         PsGather gather, void *out, float *ms_sum) {
+    const int d = lay.d, k = shape->n_objectives, nm = shape->n_models;
+    const bool with_ideal = in.r.empty();
+    int nftot = 0;
+    for (int j = 0; j < nm; ++j) nftot += lay.k[j];
+    size_t per_start = 0;
+    for (size_t p = 0; p < SN; ++p)
+        per_start = std::max(per_start, ps_start_doubles(ctx, models + p * nm, nm, d, k, nftot, with_ideal, E.with_ps) * sizeof(double));
+    const size_t limit = mrbf_env("MRBF_PS_CHUNK_KB") ? (size_t)std::max(1, atoi(mrbf_env("MRBF_PS_CHUNK_KB"))) << 10 : (size_t)2 << 30;
+    const size_t chunk = std::max<size_t>(1, limit / per_start);
+    *ms_sum = 0.f;
+    for (size_t p0 = 0; p0 < SN; p0 += chunk) {
+        const size_t n = std::min(chunk, SN - p0);
+        std::vector<PsStart> S(n);
+        for (size_t i = 0; i < n; ++i) {
+            const size_t p = p0 + i;
+            PsStart &s = S[i];
+            ps_problem_fill(s.P, lay, shape, models + p * nm);
+            s.P.lin = &in.lin;
+            s.hlb.assign(in.lb.begin() + p * d, in.lb.begin() + (p + 1) * d);
+            s.hub.assign(in.ub.begin() + p * d, in.ub.begin() + (p + 1) * d);
+            s.hxn.assign(in.x.begin() + p * d, in.x.begin() + (p + 1) * d);
+            if (!in.fx.empty()) s.hfx.assign(in.fx.begin() + p * k, in.fx.begin() + (p + 1) * k);
+            s.r.assign(k, 0.0);
+            if (!in.r.empty()) s.r.assign(in.r.begin() + p * k, in.r.begin() + (p + 1) * k);
+            s.seed = seeds_or_null ? seeds_or_null[p] : opts->seed;
+        }
+        PsCall c;
+        float ms = 0.f;
+        MRBF_TRY(ps_open(c, ctx, S, opts, with_ideal, E.with_ps));
+        if (with_ideal) MRBF_TRY(ps_ideal_phase(c));
+        if (E.with_ps) MRBF_TRY(ps_step_phase(c, with_ideal));
+        MRBF_TRY(ps_close(c, &ms));
+        *ms_sum += ms;
+        for (size_t i = 0; i < n; ++i) gather(out, p0 + i, S[i]);
+    }
+    return MRBF_OK;
+}
+
+// what the step calls gather: the records where the caller wants them (the single call: a record of its own -- nothing reaches the
+// caller before the step has succeeded), the arrays in host blocks that are put at the end
+struct PsStepOut {
+    int d, k;
+    mrbf_ps_info *infos;
+    std::vector<double> x, mx, r;
+};
+static void ps_gather_step(void *out, size_t p, const PsStart &s) {
+    PsStepOut &o = *static_cast<PsStepOut *>(out);
+    o.infos[p] = s.info;
+    std::copy(s.xt.begin(), s.xt.end(), o.x.begin() + p * o.d);
+    std::copy(s.mx.begin(), s.mx.end(), o.mx.begin() + p * o.k);
+    std::copy(s.r.begin(), s.r.end(), o.r.begin() + p * o.k);
+}
+static int ps_put_step(mrbf_ctx *ctx, const PsStepOut &o, size_t SN, double *x_trial, double *mx_trial, double *r_out) {
+    MRBF_TRY(output_put(ctx, x_trial, o.x.data(), SN * o.d));
+    MRBF_TRY(output_put(ctx, mx_trial, o.mx.data(), SN * o.k));
+    if (r_out) MRBF_TRY(output_put(ctx, r_out, o.r.data(), SN * o.k));
     return MRBF_OK;
 }
 
@@ -2232,35 +2078,19 @@ extern "C" int32_t mrbf_ps_step_problem(mrbf_ctx *ctx, const mrbf_ps_problem *pr
     if (descent::Defect D = descent::read(descent_shape(prob, prob->models, 1, slots), {true, descent::Centres::UNCHECKED}, lay))
         return fail(ctx, -2, "mrbf_ps_step: %s", D.msg.c_str());
     if (lay.n_nl > MAXCON) return fail(ctx, -2, "mrbf_ps_step: more than %d modelled constraints", MAXCON);
-    std::vector<PsStart> S(1);
-    PsStart &s = S[0];
-    Problem &P = s.P;
-    ps_problem_fill(P, lay, prob, prob->models);
-    const int d = P.d, k = P.nobj;
-    if (mrbf_dispatch_ps(d, k, P.nmodels, P.ncon, prob->n_lin_eq + prob->n_lin_ineq, 0) != MRBF_DISPATCH_DEVICE)
-        return fail(ctx, -2, "mrbf_ps_step: d = %d / k = %d / %d constraints outside the device path (ask mrbf_dispatch_ps first)", d, k, P.ncon);
-    // box, start point, direction: host copies first (the pointers may be host or device memory)
-    s.r.assign(k, 0.0);
-    MRBF_TRY(fetch_host(ctx, lb_eff, d, s.hlb));
-    MRBF_TRY(fetch_host(ctx, ub_eff, d, s.hub));
-    MRBF_TRY(fetch_host(ctx, x_n, d, s.hxn));
-    if (fx_n) MRBF_TRY(fetch_host(ctx, fx_n, k, s.hfx));
-    if (r_or_null) MRBF_TRY(fetch_host(ctx, r_or_null, k, s.r));
-    for (int t = 0; t < d; ++t)
-        if (!(s.hlb[t] <= s.hub[t])) return fail(ctx, -4, "lb_eff[%d] > ub_eff[%d]", t, t);
-    MRBF_TRY(fetch_host(ctx, prob->A_eq, (size_t)P.nlin_eq * d, P.A_eq));
-    MRBF_TRY(fetch_host(ctx, prob->b_eq, (size_t)P.nlin_eq, P.b_eq));
-    MRBF_TRY(fetch_host(ctx, prob->A_ineq, (size_t)P.nlin_ineq * d, P.A_ineq));
-    MRBF_TRY(fetch_host(ctx, prob->b_ineq, (size_t)P.nlin_ineq, P.b_ineq));
-    s.seed = opts->seed;
+    const int d = lay.d, k = prob->n_objectives;
+    if (mrbf_dispatch_ps(d, k, prob->n_models, (int)lay.rows.size(), prob->n_lin_eq + prob->n_lin_ineq, 0) != MRBF_DISPATCH_DEVICE)
+        return fail(ctx, -2, "mrbf_ps_step: d = %d / k = %d / %d constraints outside the device path (ask mrbf_dispatch_ps first)", d, k, (int)lay.rows.size());
+    const PsEntry E{"", false, -4, true};
+    PsInputs in;
+    MRBF_TRY(ps_read_inputs(ctx, E, 1, d, k, prob, x_n, lb_eff, ub_eff, fx_n, r_or_null, in));
+    mrbf_ps_info rec{};
+    PsStepOut o{d, k, &rec, std::vector<double>(d), std::vector<double>(k), std::vector<double>(k)};
     float ms = 0.f;
-    MRBF_TRY(ps_step_many(ctx, S, r_or_null == nullptr, opts, &ms));
-    *info = s.info;
+    MRBF_TRY(ps_run_chunks(ctx, E, 1, lay, prob, prob->models, in, opts, nullptr, ps_gather_step, &o, &ms));
+    *info = rec;
     info->ms_total = ms;
-    MRBF_TRY(output_put(ctx, x_trial, s.xt.data(), d));
-    MRBF_TRY(output_put(ctx, mx_trial, s.mx.data(), k));
-    if (r_out) MRBF_TRY(output_put(ctx, r_out, s.r.data(), k));
-    return MRBF_OK;
+    return ps_put_step(ctx, o, 1, x_trial, mx_trial, r_out);
 }
 
 // ---- many-start Pascoletti-Serafini step: get_criticality(::PascolettiSerafiniConfig, ...) (Morbit.jl src/descent.jl:512-581) for
@@ -2284,7 +2114,6 @@ extern "C" int32_t mrbf_ps_step_batch(mrbf_ctx *ctx, int64_t n_starts, const mrb
     if (!x_trial) return fail(ctx, -12, "x_trial is NULL");
     if (!mx_trial) return fail(ctx, -13, "mx_trial is NULL");
     if (!infos) return fail(ctx, -15, "infos is NULL");
-    using namespace ps;
     if (shape->n_models < 1 || !shape->roles) return fail(ctx, -3, "mrbf_ps_step_batch: grouped models with a roles table are required");
     if (n_starts < 1) return fail(ctx, -2, "mrbf_ps_step_batch: %lld starts (ask mrbf_dispatch_ps_batch first)", (long long)n_starts);
     const int64_t N = n_starts;
@@ -2302,68 +2131,34 @@ extern "C" int32_t mrbf_ps_step_batch(mrbf_ctx *ctx, int64_t n_starts, const mrb
     (void)hipSetDevice(ctx->device);
     const size_t SN = (size_t)N;
     std::memset(infos, 0, SN * sizeof(*infos));
-    // the inputs: host copies (the pointers may be host or device memory)
-    std::vector<double> hx, hlb, hub, hfx, hr, A_eq, b_eq, A_ineq, b_ineq;
-    MRBF_TRY(fetch_host(ctx, x_n, SN * d, hx));
-    MRBF_TRY(fetch_host(ctx, lb_eff, SN * d, hlb));
-    MRBF_TRY(fetch_host(ctx, ub_eff, SN * d, hub));
-    if (fx_n) MRBF_TRY(fetch_host(ctx, fx_n, SN * k, hfx));
-    if (r_or_null) MRBF_TRY(fetch_host(ctx, r_or_null, SN * k, hr));
-    for (size_t t = 0; t < SN * d; ++t)
-        if (!(hlb[t] <= hub[t])) return fail(ctx, -6, "start %lld: lb_eff[%d] > ub_eff[%d]", (long long)(t / d), (int)(t % d), (int)(t % d));
-    MRBF_TRY(fetch_host(ctx, shape->A_eq, (size_t)shape->n_lin_eq * d, A_eq));
-    MRBF_TRY(fetch_host(ctx, shape->b_eq, (size_t)shape->n_lin_eq, b_eq));
-    MRBF_TRY(fetch_host(ctx, shape->A_ineq, (size_t)shape->n_lin_ineq * d, A_ineq));
-    MRBF_TRY(fetch_host(ctx, shape->b_ineq, (size_t)shape->n_lin_ineq, b_ineq));
-    int nftot = 0;
-    for (int j = 0; j < nm; ++j) nftot += lay.k[j];
-    // a batch whose state exceeds 2 GiB is processed in chunks of starts
-    size_t per_start = 0;
-    for (size_t p = 0; p < SN; ++p)
-        per_start = std::max(per_start, ps_start_doubles(ctx, models + p * nm, nm, d, k, nftot, r_or_null == nullptr) * sizeof(double));
-    // (MRBF_PS_CHUNK_KB: another limit, so that a test can split a small batch)
-    const size_t limit = mrbf_env("MRBF_PS_CHUNK_KB") ? (size_t)std::max(1, atoi(mrbf_env("MRBF_PS_CHUNK_KB"))) << 10 : (size_t)2 << 30;
-    const size_t chunk = std::max<size_t>(1, limit / per_start);
-    std::vector<double> ox(SN * d), omx(SN * k), orr(SN * k);
+    const PsEntry E{"", true, -6, true};
+    PsInputs in;
+    MRBF_TRY(ps_read_inputs(ctx, E, SN, d, k, shape, x_n, lb_eff, ub_eff, fx_n, r_or_null, in));
+    PsStepOut o{d, k, infos, std::vector<double>(SN * d), std::vector<double>(SN * k), std::vector<double>(SN * k)};
     float ms_sum = 0.f;
-    for (size_t p0 = 0; p0 < SN; p0 += chunk) {
-        const size_t n = std::min(chunk, SN - p0);
-        std::vector<PsStart> S(n);
-        for (size_t i = 0; i < n; ++i) {
-            const size_t p = p0 + i;
-            PsStart &s = S[i];
-            ps_problem_fill(s.P, lay, shape, models + p * nm);
-            s.P.A_eq = A_eq, s.P.b_eq = b_eq, s.P.A_ineq = A_ineq, s.P.b_ineq = b_ineq;
-            s.hlb.assign(hlb.begin() + p * d, hlb.begin() + (p + 1) * d);
-            s.hub.assign(hub.begin() + p * d, hub.begin() + (p + 1) * d);
-            s.hxn.assign(hx.begin() + p * d, hx.begin() + (p + 1) * d);
-            if (fx_n) s.hfx.assign(hfx.begin() + p * k, hfx.begin() + (p + 1) * k);
-            s.r.assign(k, 0.0);
-            if (r_or_null) s.r.assign(hr.begin() + p * k, hr.begin() + (p + 1) * k);
-            s.seed = seeds_or_null ? seeds_or_null[p] : opts->seed;
-        }
-        float ms = 0.f;
-        MRBF_TRY(ps_step_many(ctx, S, r_or_null == nullptr, opts, &ms));
-        ms_sum += ms;
-        for (size_t i = 0; i < n; ++i) {
-            const size_t p = p0 + i;
-            infos[p] = S[i].info;
-            std::copy(S[i].xt.begin(), S[i].xt.end(), ox.begin() + p * d);
-            std::copy(S[i].mx.begin(), S[i].mx.end(), omx.begin() + p * k);
-            std::copy(S[i].r.begin(), S[i].r.end(), orr.begin() + p * k);
-        }
-    }
+    MRBF_TRY(ps_run_chunks(ctx, E, SN, lay, shape, models, in, opts, seeds_or_null, ps_gather_step, &o, &ms_sum));
     for (size_t p = 0; p < SN; ++p) infos[p].ms_total = ms_sum;
     if (ms_total) *ms_total = ms_sum;
-    MRBF_TRY(output_put(ctx, x_trial, ox.data(), SN * d));
-    MRBF_TRY(output_put(ctx, mx_trial, omx.data(), SN * k));
-    if (r_out) MRBF_TRY(output_put(ctx, r_out, orr.data(), SN * k));
-    return MRBF_OK;
+    return ps_put_step(ctx, o, SN, x_trial, mx_trial, r_out);
 }
 
 // ---- local ideal points: compute_local_ideal_point (Morbit.jl src/descent.jl:404-412, k runs of _min_component :369-387) as calls of
-// their own -- the ideal-point phase of the step above and nothing behind it (ps_step_many with ideal_only).  The validation, the block
-// the outputs are gathered in and the records' packing are ideal_host.hpp's; nothing reaches the caller before the call has succeeded.
+// their own -- the step's opening without room for the PS run, its ideal phase and its closing.  The validation, the block the
+// outputs are gathered in and the records' packing are ideal_host.hpp's; nothing reaches the caller before the call has succeeded.
+struct IdealOut {
+    int k;
+    ideal::Layout L;
+    std::vector<double> out;
+    std::vector<mrbf_ideal_info> info;
+};
+static void ideal_gather(void *out, size_t p, const PsStart &s) {
+    IdealOut &o = *static_cast<IdealOut *>(out);
+    ideal::pack(o.info[p], o.k, s.info.evals_ideal, s.info.generations, s.found.data(), s.refined.data());
+    std::copy(s.ideal.begin(), s.ideal.end(), o.out.begin() + o.L.ideal_at(p, 0));
+    std::copy(s.mx.begin(), s.mx.end(), o.out.begin() + o.L.mx_at(p, 0));
+    std::copy(s.x_ideal.begin(), s.x_ideal.end(), o.out.begin() + o.L.x_ideal_at(p, 0));
+}
+static_assert(ideal::MAX_OBJECTIVES == ps::MAXOBJ, "a bit per objective in mrbf_ideal_info::found / refined");
 static int32_t ideal_points(mrbf_ctx *ctx, bool batch, int64_t n_starts, const mrbf_ps_problem *shape, const mrbf_model *const *models,
                             const double *x_n, const double *lb_eff, const double *ub_eff, const mrbf_ps_options *opts,
                             const uint64_t *seeds_or_null, double *ideal_out, double *x_ideal_out, double *mx_out, mrbf_ideal_info *infos,
@@ -2379,7 +2174,6 @@ static int32_t ideal_points(mrbf_ctx *ctx, bool batch, int64_t n_starts, const m
         return fail(ctx, rc, rc == -2 ? "%s: %lld starts (ask mrbf_dispatch_ideal_batch first)" : "%s: an argument is NULL, or the problem has no models or no roles table",
                     name, (long long)n_starts);
     }
-    using namespace ps;
     const int64_t N = n_starts;
     const int k = shape->n_objectives, nm = shape->n_models;
     std::vector<descent::SlotShape> slots;
@@ -2394,58 +2188,19 @@ static int32_t ideal_points(mrbf_ctx *ctx, bool batch, int64_t n_starts, const m
                     lay.n_nl + n_lin, batch ? "mrbf_dispatch_ideal_batch" : "mrbf_dispatch_ideal");
     (void)hipSetDevice(ctx->device);
     const size_t SN = (size_t)N;
-    // the inputs: host copies (the pointers may be host or device memory)
-    std::vector<double> hx, hlb, hub, A_eq, b_eq, A_ineq, b_ineq;
-    MRBF_TRY(fetch_host(ctx, x_n, SN * d, hx));
-    MRBF_TRY(fetch_host(ctx, lb_eff, SN * d, hlb));
-    MRBF_TRY(fetch_host(ctx, ub_eff, SN * d, hub));
-    for (size_t t = 0; t < SN * d; ++t)
-        if (!(hlb[t] <= hub[t])) return fail(ctx, -6, "%s: start %lld: lb_eff[%d] > ub_eff[%d]", name, (long long)(t / d), (int)(t % d), (int)(t % d));
-    MRBF_TRY(fetch_host(ctx, shape->A_eq, (size_t)shape->n_lin_eq * d, A_eq));
-    MRBF_TRY(fetch_host(ctx, shape->b_eq, (size_t)shape->n_lin_eq, b_eq));
-    MRBF_TRY(fetch_host(ctx, shape->A_ineq, (size_t)shape->n_lin_ineq * d, A_ineq));
-    MRBF_TRY(fetch_host(ctx, shape->b_ineq, (size_t)shape->n_lin_ineq, b_ineq));
-    int nftot = 0;
-    for (int j = 0; j < nm; ++j) nftot += lay.k[j];
-    // a batch whose state exceeds 2 GiB is processed in chunks of starts (MRBF_PS_CHUNK_KB: another limit), as in mrbf_ps_step_batch
-    size_t per_start = 0;
-    for (size_t p = 0; p < SN; ++p) per_start = std::max(per_start, ps_start_doubles(ctx, models + p * nm, nm, d, k, nftot, true, true) * sizeof(double));
-    const size_t limit = mrbf_env("MRBF_PS_CHUNK_KB") ? (size_t)std::max(1, atoi(mrbf_env("MRBF_PS_CHUNK_KB"))) << 10 : (size_t)2 << 30;
-    const size_t chunk = std::max<size_t>(1, limit / per_start);
-    const ideal::Layout L = ideal::layout(N, d, k);
-    std::vector<double> out(L.total);
-    std::vector<mrbf_ideal_info> hinfo(SN);
+    const std::string prefix = std::string(name) + ": ";
+    const PsEntry E{prefix.c_str(), true, -6, false};
+    PsInputs in;
+    MRBF_TRY(ps_read_inputs(ctx, E, SN, d, k, shape, x_n, lb_eff, ub_eff, nullptr, nullptr, in));
+    IdealOut o{k, ideal::layout(N, d, k), {}, std::vector<mrbf_ideal_info>(SN)};
+    o.out.resize(o.L.total);
     float ms_sum = 0.f;
-    for (size_t p0 = 0; p0 < SN; p0 += chunk) {
-        const size_t n = std::min(chunk, SN - p0);
-        std::vector<PsStart> S(n);
-        for (size_t i = 0; i < n; ++i) {
-            const size_t p = p0 + i;
-            PsStart &s = S[i];
-            ps_problem_fill(s.P, lay, shape, models + p * nm);
-            s.P.A_eq = A_eq, s.P.b_eq = b_eq, s.P.A_ineq = A_ineq, s.P.b_ineq = b_ineq;
-            s.hlb.assign(hlb.begin() + p * d, hlb.begin() + (p + 1) * d);
-            s.hub.assign(hub.begin() + p * d, hub.begin() + (p + 1) * d);
-            s.hxn.assign(hx.begin() + p * d, hx.begin() + (p + 1) * d);
-            s.seed = seeds_or_null ? seeds_or_null[p] : opts->seed;
-        }
-        float ms = 0.f;
-        MRBF_TRY(ps_step_many(ctx, S, true, opts, &ms, true));
-        ms_sum += ms;
-        for (size_t i = 0; i < n; ++i) {
-            const size_t p = p0 + i;
-            const PsStart &s = S[i];
-            ideal::pack(hinfo[p], k, s.info.evals_ideal, s.info.generations, s.found.data(), s.refined.data());
-            std::copy(s.ideal.begin(), s.ideal.end(), out.begin() + L.ideal_at(p, 0));
-            std::copy(s.mx.begin(), s.mx.end(), out.begin() + L.mx_at(p, 0));
-            std::copy(s.x_ideal.begin(), s.x_ideal.end(), out.begin() + L.x_ideal_at(p, 0));
-        }
-    }
-    for (size_t p = 0; p < SN; ++p) hinfo[p].ms_total = ms_sum;
-    MRBF_TRY(output_put(ctx, ideal_out, out.data() + L.ideal, SN * k));
-    if (mx_out) MRBF_TRY(output_put(ctx, mx_out, out.data() + L.mx, SN * k));
-    if (x_ideal_out) MRBF_TRY(output_put(ctx, x_ideal_out, out.data() + L.x_ideal, SN * k * d));
-    std::copy(hinfo.begin(), hinfo.end(), infos);
+    MRBF_TRY(ps_run_chunks(ctx, E, SN, lay, shape, models, in, opts, seeds_or_null, ideal_gather, &o, &ms_sum));
+    for (size_t p = 0; p < SN; ++p) o.info[p].ms_total = ms_sum;
+    MRBF_TRY(output_put(ctx, ideal_out, o.out.data() + o.L.ideal, SN * k));
+    if (mx_out) MRBF_TRY(output_put(ctx, mx_out, o.out.data() + o.L.mx, SN * k));
+    if (x_ideal_out) MRBF_TRY(output_put(ctx, x_ideal_out, o.out.data() + o.L.x_ideal, SN * k * d));
+    std::copy(o.info.begin(), o.info.end(), infos);
     if (ms_total) *ms_total = ms_sum;
     return MRBF_OK;
 }

@@ -391,5 +391,7 @@ def test_host_header_includes_no_hip_and_the_phase_exists_once():
     src = open(os.path.join(ROOT, "morbit.jl_amd", "csrc", "ps_solver.hip")).read()
     assert '#include "ideal_host.hpp"' in src
     # one copy of the ideal-point block: one place makes the single-objective runs, one place reads their best records
-    assert src.count("make_run(a.runs[l], 0, l, lam_ip") == 1
-    assert len(re.findall(r"^static int ps_step_many\(", src, flags=re.M)) == 1
+    assert src.count("ps_make_run(a.runs[l], 0, l, lam_ip") == 1
+    assert len(re.findall(r"^static int ps_ideal_phase\(", src, flags=re.M)) == 1
+    assert src.count("MRBF_TRY(ps_ideal_phase(c))") == 1            # and one place runs it, for the step and the ideal-point calls alike
+    assert "ideal_only" not in src

@@ -511,6 +511,13 @@ def test_ps_step_device_critical_and_argument_errors():
     assert f(ctx.h, mod.model, *args(lb=_lib.as_ptr(x + 1.0)), ctypes.byref(opts), _lib.as_ptr(buf), _lib.as_ptr(buf), None, ctypes.byref(info)) == -4
     bad = _lib.PsOptions(-1, -1, 0, 0, 1, 0.5, 1e-3)
     assert f(ctx.h, mod.model, *args(), ctypes.byref(bad), _lib.as_ptr(buf), _lib.as_ptr(buf), None, ctypes.byref(info)) == -8
+    # the NULL arguments of mrbf_ps_step_problem, in the order it looks for them: ub_eff, fx_n without a direction, x_trial, mx_trial, info
+    assert f(ctx.h, mod.model, *args(ub=None), ctypes.byref(opts), _lib.as_ptr(buf), _lib.as_ptr(buf), None, ctypes.byref(info)) == -5
+    no_fx = args()[:3] + [None, None]
+    assert f(ctx.h, mod.model, *no_fx, ctypes.byref(opts), _lib.as_ptr(buf), _lib.as_ptr(buf), None, ctypes.byref(info)) == -6
+    assert f(ctx.h, mod.model, *args(), ctypes.byref(opts), None, _lib.as_ptr(buf), None, ctypes.byref(info)) == -9
+    assert f(ctx.h, mod.model, *args(), ctypes.byref(opts), _lib.as_ptr(buf), None, None, ctypes.byref(info)) == -10
+    assert f(ctx.h, mod.model, *args(), ctypes.byref(opts), _lib.as_ptr(buf), _lib.as_ptr(buf), None, None) == -12
     mod.free()
 
 
